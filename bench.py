@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- interpolated frames/s of the MI355X UNet frame-pair forward.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 Both forms work for N > 1: started WITHOUT a launcher (no WORLD_SIZE in the environment), `--gpus N` makes this
@@ -11,7 +11,11 @@ rendezvous on 127.0.0.1), relays rank 0's JSON line and exits with the worst chi
 A step = one forward of the hot path over one batch of synthetic frame pairs that is already
 resident in HBM.  Default workload = BASELINE.json configs[2]: batch 8 of 1920x1080 pairs, bf16
 MFMA path, one batch per GPU (weak scaling: frame pairs are independent, ranks exchange
-nothing inside the timed region).  Rank 0 prints ONE JSON line; `value` is always this leg.
+nothing inside the timed region).  Rank 0 prints ONE JSON line; `value` is always this leg, and
+`ms_per_step` is the wall time of one of the `--steps` timed steps.  Weights and frames are seeded,
+so the same arguments give the same inputs on every run; `--dump-outputs DIR` writes rank 0's
+output of the last timed step there (`dump_outputs`), so that two builds can be compared output
+for output.
 
 Extra objects on that line:
   roofline      -- dominant kernel (by time) of the forward: algorithmic FLOPs per launch / its
@@ -478,6 +482,31 @@ def tile4k_leg(model, dev, dist, rank, world, reps):
     return res
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6   # --dump-outputs writes at most this much in all
+DUMP_SAMPLE = 1 << 22            # values in the sample of an output larger than the budget
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out: torch.Tensor, dirpath: str) -> dict:
+    """Write what the timed path's last step returned (the interpolated frames, fp32 [B, 1, H, W]) to `dirpath`.
+    Within DUMP_BUDGET_BYTES: the whole array as interpolated.npy.  Larger: DUMP_SAMPLE values at flat indices drawn
+    by a CPU generator seeded DUMP_SAMPLE_SEED (so the same for every run of the same shape), in ascending order, as
+    interpolated_sample.npy (float32), and those indices as interpolated_sample_flat_index.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    out = out.detach().float()
+    n = out.numel()
+    if n * 4 + 4096 <= DUMP_BUDGET_BYTES:   # (+ room for the .npy header)
+        np.save(os.path.join(dirpath, "interpolated.npy"), out.cpu().numpy())
+        return {"dir": dirpath, "files": {"interpolated": list(out.shape)}, "sampled": False}
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SAMPLE_SEED))[:DUMP_SAMPLE].sort().values
+    vals = out.reshape(-1)[idx.to(out.device)].cpu().numpy()
+    np.save(os.path.join(dirpath, "interpolated_sample.npy"), vals)
+    np.save(os.path.join(dirpath, "interpolated_sample_flat_index.npy"), idx.numpy().astype(np.float64))
+    return {"dir": dirpath, "files": {"interpolated_sample": [len(vals)], "interpolated_sample_flat_index": [len(vals)]},
+            "sampled": True, "of_shape": list(out.shape), "seed": DUMP_SAMPLE_SEED}
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` with no launcher around it: be the launcher.  This process has made NO GPU call
     (importing torch and this package does not initialise HIP; nothing below does either) and never exec()s: it
@@ -539,7 +568,14 @@ def main():
     ap.add_argument("--no-tile4k", action="store_true")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 legs (A/B runs)")
     ap.add_argument("--no-power", action="store_true", help="skip the rocm-smi power / clock sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's output of the last timed step to DIR/*.npy (dump_outputs: at most 64 MB, "
+                         "a fixed seeded sample of a larger output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))   # no launcher around us: be one (no GPU call so far, none in there)
@@ -611,9 +647,11 @@ def main():
     gc.collect()
     gc.disable()
     barrier()
+    out = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        model(f1, f2)
+        del out                # the previous step's output goes back to the allocator before the next one is made
+        out = model(f1, f2)
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
@@ -623,6 +661,8 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    del out
     default_workload = (b, h, w, args.precision, args.unfused) == (8, 1080, 1920, "bf16", False)
     power = None
 
@@ -638,7 +678,7 @@ def main():
             if "timeout" in err:  # a hung transfer: nothing after it can run on this communicator
                 if rank == 0:
                     print(json.dumps(headline(args, world, elapsed, rows, nfw, default_workload,
-                                              video_res, None, None, None)))
+                                              video_res, None, None, None, dumped=dumped)))
                     sys.stdout.flush()
                 os._exit(3)  # the headline is printed, but a hung leg must show in the return code
     if world == 1 and default_workload and not args.no_tile4k:
@@ -654,7 +694,7 @@ def main():
             if "timeout" in err:
                 if rank == 0:
                     print(json.dumps(headline(args, world, elapsed, rows, nfw, default_workload,
-                                              video_res, tile_res, None, None)))
+                                              video_res, tile_res, None, None, dumped=dumped)))
                     sys.stdout.flush()
                 os._exit(3)
 
@@ -697,7 +737,7 @@ def main():
     if world == 1 and not args.no_cpu_baseline:
         cpu_baseline, parity = cpu_legs(dev, args.precision)
     print(json.dumps(headline(args, world, elapsed, rows, nfw, default_workload, video_res, tile_res,
-                              cpu_baseline, parity, fp32, power, rgb, x2, small)))
+                              cpu_baseline, parity, fp32, power, rgb, x2, small, dumped)))
     if dist is not None:
         dist.destroy_process_group()
 
@@ -1023,7 +1063,7 @@ def small_frames_leg(dev):
 
 
 def headline(args, world, elapsed, rows, nfw, default_workload, video_res, tile_res, cpu_baseline, parity,
-             fp32=None, power=None, rgb=None, x2=None, small=None):
+             fp32=None, power=None, rgb=None, x2=None, small=None, dumped=None):
     b, h, w = args.batch, args.height, args.width
     fps = world * b * args.steps / elapsed
     ms_step = elapsed / args.steps * 1e3
@@ -1126,6 +1166,8 @@ def headline(args, world, elapsed, rows, nfw, default_workload, video_res, tile_
             result["collective_backend"] = video_res.get("backend")
     if tile_res is not None:
         result["tile4k"] = tile_res
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     return result
 
 
