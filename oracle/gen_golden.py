@@ -69,6 +69,26 @@ def gen_rgb():
         np.savez_compressed(os.path.join(GOLD, f"out_{name}.npz"), seed=seed,
                             weight_seed=RGB_WEIGHT_SEED, frame1=f1.numpy(), frame2=f2.numpy(),
                             out=out.numpy())
+    # 1080p, the frame size bench.py's RGB leg runs at: strided sample + float64 sums only, as for the gray
+    # out_b1_1080x1920_sample.npz (u8_hist counts all three colour planes)
+    seed = 17
+    f1, f2 = O.make_frames(seed, 1, 1080, 1920, c=3)
+    t0 = time.time()
+    with torch.no_grad():
+        out = inner(torch.cat([f1, f2], dim=1))
+    print(f"rgb 1080p reference forward: {time.time() - t0:.1f} s")
+    mine = O.unet_forward(sd, f1, f2)
+    print(f"rgb_b1_1080x1920: out std {out.std():.4f} min {out.min():.3f} max {out.max():.3f} "
+          f"|restatement-ref| {float((mine - out).abs().max()):.3e}")
+    idx, vals = strided_sample(out, 4096)
+    u8 = O.postprocess_tensor(out)
+    np.savez_compressed(
+        os.path.join(GOLD, "out_rgb_b1_1080x1920_sample.npz"),
+        seed=seed, weight_seed=RGB_WEIGHT_SEED, idx=idx, val=vals,
+        sum=np.float64(out.double().sum().item()),
+        abssum=np.float64(out.double().abs().sum().item()),
+        u8_hist=np.bincount(u8.reshape(-1), minlength=256).astype(np.int64),
+    )
 
 
 SSIM_CASES = (  # name, seed, B, C, H, W, value range, noise

@@ -384,7 +384,11 @@ def test_random_shapes_fp32_and_bf16_vs_oracle(model, dev, seeded_sd):
                                                  ("bf16", 1, 48, 80, True), ("fp32", 1, 64, 96, False),
                                                  ("bf16", 3, 40, 56, False), ("fp32", 3, 33, 47, False),
                                                  ("bf16x2", 1, 64, 96, False), ("bf16x2", 1, 33, 47, False),
-                                                 ("bf16x2", 3, 40, 56, False)])
+                                                 ("bf16x2", 3, 40, 56, False),
+                                                 # RGB at 2 040 stem tiles: the persistent RGB stem's workgroups run
+                                                 # 3-4 tiles each, crossing an image boundary, with partial edge tiles
+                                                 ("bf16", 3, 530, 950, False), ("bf16x2", 3, 530, 950, False),
+                                                 ("fp32", 3, 530, 950, False)])
 def test_u8_read_and_write_fused_into_stem_and_head_bitwise(dev, prec, cf, h, w, unfused):
     """fiunet_forward_u8 == fiunet_preprocess_u8 -> fiunet_forward -> fiunet_postprocess_u8 bit for bit
     (inference.py:31-35, :54-61), whether the uint8 frames are read by the fused stem / written by the fused

@@ -98,6 +98,24 @@ def test_rgb_oracle_equals_reference_unet_6_3(golden_dir, name):
         assert np.abs(C.unet_forward(sd, f1, f2, n_classes=3) - g["out"]).max() <= 5e-5
 
 
+def test_rgb_1080p_oracle_equals_reference_sample(golden_dir):
+    """The 6->3 variant at the frame size bench.py's RGB leg runs: the oracle reproduces the 4 096-point sample, the
+    float64 sum and the uint8 histogram of the reference's own UNet(6, 3, bilinear=True) at 1x3x1080x1920 (gen_rgb).
+    The GPU tests compare against the oracle at other shapes; this ties the oracle to the reference at this one."""
+    g = np.load(os.path.join(golden_dir, "out_rgb_b1_1080x1920_sample.npz"))
+    assert g["idx"].shape == g["val"].shape == (4096,)
+    assert int(g["u8_hist"].sum()) == 3 * 1080 * 1920
+    sd = O.make_seeded_state_dict(int(g["weight_seed"]), n_channels=6, n_classes=3)
+    f1, f2 = O.make_frames(int(g["seed"]), 1, 1080, 1920, c=3)
+    out = O.unet_forward(sd, f1, f2)
+    assert out.shape == (1, 3, 1080, 1920)
+    got = out.reshape(-1)[torch.from_numpy(g["idx"])].numpy()
+    assert (np.abs(got - g["val"]) <= 2e-5 * np.maximum(1.0, np.abs(g["val"]))).all(), np.abs(got - g["val"]).max()
+    assert abs(out.double().sum().item() - float(g["sum"])) <= 1e-6 * float(g["abssum"])
+    hist = np.bincount(O.postprocess_tensor(out).reshape(-1), minlength=256)
+    assert np.abs(hist - g["u8_hist"]).sum() <= 20  # pixels straddling a truncation boundary
+
+
 def test_interpolating_checkpoint_interpolates():
     """make_interpolating_state_dict: output = 0.5*(f1+f2) + a small deep-network term, so PSNR
     against a true middle frame is ~30+ dB (not the ~15 dB of a random network) and the deep
