@@ -126,112 +126,6 @@ inline uint16_t f32_to_bf16_feedback(float v, double& carry)
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-struct Plan {
-    int hs[5], ws[5];
-    size_t act_off[NCONV];
-    size_t pool_off[4];  // MaxPool2d(2) of x1..x4: kCout[2k+1] channels at level k+1
-    size_t scratch_off;
-    size_t up_off[NCONV];  // upsampled half of a concat input, where it is materialised (else unused)
-    size_t slab_off;   // split-K partial sums (small problems), kSlabBytes
-    size_t total;
-};
-
-// Workspace plan.  The reference, under no_grad, frees every non-skip tensor as soon as its consumer
-// has run (model/unet.py:84-95 keeps only x1..x4 alive); here the same liveness is turned into a
-// static layout: every buffer gets the interval [stage that writes it, last stage that reads it]
-// (stage i = conv i of the 18) and buffers whose intervals do not overlap share bytes (first-fit
-// over the buffers in order of their first stage).  B=8 1080p bf16 needs 6.4 GB this way instead of
-// the 16.2 GB of one private buffer per tensor.  `keep_all` (FIUNET_OPT_KEEP_ALL, the debug
-// read-back) pins every activation to the end; `unfused` adds the ablation path's concat scratch;
-// the fused stem / fused head leave activations 0 / 17 out altogether.
-struct PlanOpts {
-    bool keep_all = false, unfused = false, fused_stem = false, fused_head = false, gather_up = false;
-    const int* cout = kCoutBil;   // architecture: output channels per conv
-    bool convt = false;           // bilinear=False: the upsampled half is a ConvTranspose2d output, always materialised
-    bool x2 = false;              // FIUNET_BF16X2: activations are two-piece [hi | lo] bf16 tensors of 2 * C channels
-};
-
-// A concat conv whose output spans several 128-cout tiles would bilinearly interpolate every input
-// tile once per cout tile (4x at up1, 2x at up2): there the upsampled half is written to HBM once
-// (upsample_kernel) and gathered by plain LDS-DMA like the skip half.  bf16 only: on the fp32 matrix
-// cores the interpolation is small beside the 16x slower MFMAs, and the tensor twice as big.
-// Small problems (launch-bound, K-split) keep the fused gather: `pixels` = B x H x W at the stage's level.
-// Small problems keep the fused gather - unless the conv then qualifies for the in-workgroup K cut (conv3x3_kwave.hip.h,
-// direct sources only): a quarter of the serial step chain is worth the extra upsample dispatch (ONE 256x256 pair: up1.0
-// 34 -> 23 us, up2.0 30 -> 18 us).  B, H, W: the stage's level.
-inline bool kwave_applies(int B, int H, int W, int Cin, int Cout);
-inline bool fp32_concat_takes_kwave(int B, int H, int W, int Cin, int Cout);
-inline bool materialise_up(int stage, int precision, bool unfused, int B, int H, int W, const int* cout = kCoutBil,
-                           bool convt = false)
-{
-    if (convt || precision == FIUNET_BF16X2) return kMode[stage] == SRC_CONCAT_UP;   // (no in-gather form for these)
-    if (unfused || kMode[stage] != SRC_CONCAT_UP) return false;
-    if (precision == FIUNET_FP32) return fp32_concat_takes_kwave(B, H, W, cout[kSrc0[stage]] + cout[kSrc1[stage]], cout[stage]);
-    if (precision != FIUNET_BF16) return false;
-    if (cout[stage] >= 256 && (long long)B * H * W >= 65536) return true;
-    return kwave_applies(B, H, W, cout[kSrc0[stage]] + cout[kSrc1[stage]], cout[stage]);
-}
-
-bool make_plan(int B, int H, int W, int precision, const PlanOpts& o, Plan& p)
-{
-    if (B < 1 || H < 16 || W < 16) return false;
-    // the kernels address a pixel record inside one image plane with 32 bits: H*W*64 B < 4 GiB.
-    // Larger frames go through fiunet_forward_strip band by band.
-    if ((long long)H * W >= (1LL << 26)) return false;
-    const size_t es = precision == FIUNET_FP32 ? 4 : (o.x2 ? 4 : 2);   // bytes per activation element
-    p.hs[0] = H; p.ws[0] = W;
-    for (int k = 1; k < 5; ++k) { p.hs[k] = p.hs[k - 1] / 2; p.ws[k] = p.ws[k - 1] / 2; }
-    struct Buf { size_t bytes; int first, last; size_t* off; };
-    std::vector<Buf> bufs;
-    const int END = NCONV;  // "still live after the last conv" (the unfused head, the debug read-back)
-    for (int i = 0; i < NCONV; ++i) {
-        p.act_off[i] = 0;
-        if ((i == 0 && o.fused_stem) || (i == NCONV - 1 && o.fused_head)) continue;  // never materialised
-        int last = i;  // conv j reads act i as its direct / skip source (kSrc0) or low-res source (kSrc1)
-        for (int j = i + 1; j < NCONV; ++j)
-            if (kSrc0[j] == i || kSrc1[j] == i) last = j;
-        if (i == NCONV - 1 || o.keep_all) last = END;
-        bufs.push_back({align256((size_t)B * p.hs[kLevel[i]] * p.ws[kLevel[i]] * o.cout[i] * es), i, last,
-                        &p.act_off[i]});
-    }
-    for (int k = 0; k < 4; ++k) {  // MaxPool2d(2) of x1..x4: written by conv 2k+1, read by conv 2k+2
-        bufs.push_back({align256((size_t)B * p.hs[k + 1] * p.ws[k + 1] * o.cout[2 * k + 1] * es), 2 * k + 1,
-                        o.keep_all ? END : 2 * k + 2, &p.pool_off[k]});
-    }
-    for (int i = 0; i < NCONV; ++i) {
-        p.up_off[i] = 0;
-        if (materialise_up(i, precision, o.unfused || o.gather_up, B, p.hs[kLevel[i]], p.ws[kLevel[i]], o.cout, o.convt))
-            bufs.push_back({align256((size_t)B * p.hs[kLevel[i]] * p.ws[kLevel[i]] *
-                                     (o.convt ? o.cout[kSrc1[i]] / 2 : o.cout[kSrc1[i]]) * es), i,
-                            o.keep_all ? END : i, &p.up_off[i]});
-    }
-    p.scratch_off = 0;
-    if (o.unfused && !o.convt)  // ablation path: concat tensor (<= 128 ch at level 0), rewritten by every Up block
-        bufs.push_back({align256((size_t)B * H * W * 128 * es), 0, END, &p.scratch_off});
-    bufs.push_back({kSlabBytes, 0, END, &p.slab_off});  // split-K partial sums (small problems)
-    std::stable_sort(bufs.begin(), bufs.end(), [](const Buf& a, const Buf& b) { return a.first < b.first; });
-    struct Live { size_t off, bytes; int last; };
-    std::vector<Live> live;
-    size_t total = 0;
-    for (const Buf& b : bufs) {
-        // buffers whose last reader ran before this one's writer are dead (a conv never reads and
-        // writes the same bytes: its sources are live through its own stage)
-        live.erase(std::remove_if(live.begin(), live.end(), [&](const Live& l) { return l.last < b.first; }),
-                   live.end());
-        std::sort(live.begin(), live.end(), [](const Live& a, const Live& c) { return a.off < c.off; });
-        size_t off = 0;
-        for (const Live& l : live) {
-            if (off + b.bytes <= l.off) break;
-            off = std::max(off, l.off + l.bytes);
-        }
-        *b.off = off;
-        live.push_back({off, b.bytes, b.last});
-        total = std::max(total, off + b.bytes);
-    }
-    p.total = total;
-    return true;
-}
-
 }  // namespace
 
 struct fiunet_ctx {
@@ -263,8 +157,6 @@ struct fiunet_ctx {
 
 namespace {
 
-// which activations a forward of this context materialises (must agree with forward_impl)
-PlanOpts plan_opts(const fiunet_ctx* ctx, int H, int W, int precision);
 
 int dev_upload(fiunet_ctx* ctx, const void* host, size_t bytes, void** out)
 {
@@ -288,66 +180,54 @@ void free_weights(fiunet_ctx* ctx)
 
 thread_local std::string* g_name_out = nullptr;  // where the next conv launch reports its kernel
 
+// One conv kernel on `nblk` workgroups of `threads` with `lds` bytes of dynamic LDS: more than 64 KiB needs the opt-in
+// attribute, set once per kernel and device (a duplicate hipFuncSetAttribute is harmless); `name` is what the profiler
+// reports for the stage (fiunet_profile_read).
+template <auto Kernel>
+int launch_lds(const char* name, long long nblk, int threads, int lds, const ConvArgs& a, hipStream_t s)
+{
+    if (g_name_out) *g_name_out = name;
+    if (nblk <= 0 || nblk > 0x7fffffffLL) return fail(FIUNET_ERR_INVALID_ARG, "conv grid too large");
+    static std::atomic<bool> lds_attr_set[64];
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev >= 0 && dev < 64 && !lds_attr_set[dev].load(std::memory_order_acquire)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        lds_attr_set[dev].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)nblk), dim3(threads), lds, s, a);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
 template <typename T, int BN, int TH, int TW, int MODE, int EPI>
 int launch_conv_cfg(ConvArgs a, hipStream_t s)
 {
-    using Tile = ConvTile<BN, TH, TW, MODE>;
-    if (g_name_out) {
-        char buf[128];
-        std::snprintf(buf, sizeof buf, "conv3x3_mfma_kernel<%s,%d,%d,%d,%d,%d>",
-                      sizeof(T) == 2 ? "bf16" : "f32", BN, TH, TW, MODE, EPI);
-        *g_name_out = buf;
-    }
+    char name[128] = "";
+    if (g_name_out)
+        std::snprintf(name, sizeof name, "conv3x3_mfma_kernel<%s,%d,%d,%d,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BN, TH, TW,
+                      MODE, EPI);
     a.tilesX = (a.W + TW - 1) / TW;
     a.tilesY = (a.H + TH - 1) / TH;
     a.nct = a.Cout / BN;
     const long long nblk = (long long)a.B * a.tilesX * a.tilesY * a.nct * (epi_is_splitk(EPI) ? a.ksplit : 1);
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return fail(FIUNET_ERR_INVALID_ARG, "conv grid too large");
-    // > 64 KiB of dynamic LDS needs the opt-in attribute, once per kernel and device
-    static std::atomic<bool> lds_attr_set[64];  // a duplicate hipFuncSetAttribute is harmless
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !lds_attr_set[dev].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&conv3x3_mfma_kernel<T, BN, TH, TW, MODE, EPI>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, Tile::LDS_BYTES));
-        lds_attr_set[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<T, BN, TH, TW, MODE, EPI>), dim3((unsigned)nblk),
-                       dim3(256), Tile::LDS_BYTES, s, a);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return launch_lds<&conv3x3_mfma_kernel<T, BN, TH, TW, MODE, EPI>>(name, nblk, 256, ConvTile<BN, TH, TW, MODE>::LDS_BYTES,
+                                                                       a, s);
 }
 
 // One 8-wave workgroup per CU on two pixel tiles with a shared weight ring (conv3x3_pair.hip.h).
 template <typename T, int BN, int TH, int TW, int EPI>
 int launch_pair_cfg(ConvArgs a, hipStream_t s)
 {
-    using Tile = PairTile<BN, TH, TW>;
-    if (g_name_out) {
-        char buf[128];
-        std::snprintf(buf, sizeof buf, "conv3x3_pair_kernel<%s,%d,%d,%d,%d>",
-                      sizeof(T) == 2 ? "bf16" : "f32", BN, TH, TW, EPI);
-        *g_name_out = buf;
-    }
+    char name[128] = "";
+    if (g_name_out)
+        std::snprintf(name, sizeof name, "conv3x3_pair_kernel<%s,%d,%d,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BN, TH, TW, EPI);
     a.tilesX = (a.W + TW - 1) / TW;
     a.tilesY = (a.H + TH - 1) / TH;
     a.nct = a.Cout / BN;
     const long long ntiles = (long long)a.B * a.tilesX * a.tilesY;
-    const long long nblk = (ntiles + 1) / 2 * a.nct;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return fail(FIUNET_ERR_INVALID_ARG, "conv grid too large");
-    static std::atomic<bool> lds_attr_set[64];
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !lds_attr_set[dev].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pair_kernel<T, BN, TH, TW, EPI>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, Tile::LDS_BYTES));
-        lds_attr_set[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((conv3x3_pair_kernel<T, BN, TH, TW, EPI>), dim3((unsigned)nblk), dim3(512),
-                       Tile::LDS_BYTES, s, a);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return launch_lds<&conv3x3_pair_kernel<T, BN, TH, TW, EPI>>(name, (ntiles + 1) / 2 * a.nct, 512,
+                                                                PairTile<BN, TH, TW>::LDS_BYTES, a, s);
 }
 
 inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 256 * 32); }
@@ -384,7 +264,7 @@ inline bool prefer_wide(int H, int W, int THw, int TWw, int THn, int TWn)
 // the batch size for frames whose batches are compared bit for bit (a video's ragged last chunk, B=1 vs B=8 at 1080p):
 // layers with >= 64 big-tile workgroups PER IMAGE are cut only below 128 workgroups in total, which such a layer never has
 // for B >= 2 (a SINGLE pair with 64..127 workgroups per image, e.g. the deepest level of a 720p frame, is); small frames,
-// where a single pair is cut anyway, below 256.  fiunet_min_unsplit_batch answers from the same function.
+// where a single pair is cut anyway, below 256.  fiunet_min_unsplit_batch answers from the stage plan (plan_stages).
 struct TileShape { int BN, TH, TW; };
 struct ConvCfg { bool small; int ksplit; bool kwave = false; };   // kwave: the K loop cut over the four waves of a workgroup (conv3x3_kwave.hip.h)
 
@@ -539,6 +419,191 @@ inline bool fp32_concat_takes_kwave(int B, int H, int W, int Cin, int Cout)
     return choose_conv_cfg(true, false, B, H, W, Cin, Cout, true, -1, 0, true, false, false).kwave;
 }
 
+// ---- the stage plan: how every stage of one forward launches -------------------------------------------------------
+// plan_stages is the one place that decides, per stage, the source form, the epilogue, the split-K slab and the launch
+// configuration (choose_conv_cfg, overrides included).  The forward walks the plan; make_plan lays the workspace out from
+// it; fiunet_min_unsplit_batch and fiunet_debug_stage_cfg read it.
+enum StemForm {          // stage 0: which kernel computes the stem (unet.py:72, first conv of inc)
+    STEM_FUSED = 0,      //   none: conv 1 evaluates it inside its gather (FORM_STEM)
+    STEM_FIRST = 1,      //   conv3x3_first_kernel
+    STEM_RGB_SPLIT = 2,  //   stem_rgb_split_kernel (RGB, bf16 / bf16x2)
+};
+enum SrcForm {               // stages 1..17: what the conv gathers
+    FORM_DIRECT = 0,         //   an activation
+    FORM_POOL = 1,           //   MaxPool2d(2) of one (the producer's EPI_POOL, or maxpool2_kernel on the ablation path)
+    FORM_CONCAT_GATHER = 2,  //   skip + the bilinear 2x upsample of the low-res tensor, interpolated in the gather (SRC_CONCAT_UP)
+    FORM_CONCAT_UP = 3,      //   skip + that upsample materialised first (upsample_kernel / x2_upsample_kernel)
+    FORM_CONCAT_CONVT = 4,   //   skip + ConvTranspose2d of the low-res tensor (convt2x2_kernel; bilinear=False)
+    FORM_CONCAT_UPCAT = 5,   //   the ablation path: the whole concat tensor written by upcat_kernel
+    FORM_STEM = 6,           //   the gray stem evaluated in the gather (SRC_STEM / SRC_STEM_X2)
+};
+struct StageLaunch {
+    int form = FORM_DIRECT;   // stage 0: StemForm
+    int epi = EPI_PLAIN;      // EPI_PLAIN | EPI_POOL | EPI_HEAD | EPI_HEAD3
+    bool slab = false;        // gets the split-K slab
+    bool stored = true;       // its output is a tensor in the workspace
+    ConvCfg cfg{false, 1, false};
+};
+
+// What the plan depends on besides precision and shape.
+struct NetDesc {
+    int cf = 1;                        // channels per frame
+    bool bilinear = true;              // false: ConvTranspose2d decoder (unet.py:42-44)
+    const int* cout = kCoutBil;        // output channels per conv of this architecture
+    unsigned flags = 0;                // FIUNET_OPT_*
+    bool stem_w = false;               // the fused-stem weight copy exists (gray)
+    const int* force_tile = nullptr;   // diagnostic overrides per conv (fiunet_debug_force_cfg), nullptr = none
+    const int* force_ksplit = nullptr;
+};
+
+// input channels of conv i >= 1
+inline int conv_cin(const int* cout, bool bilinear, int i)
+{
+    if (kMode[i] != SRC_CONCAT_UP) return cout[kSrc0[i]];
+    return cout[kSrc0[i]] + (bilinear ? cout[kSrc1[i]] : cout[kSrc1[i]] / 2);
+}
+
+// A bf16 / fp32 bilinear concat conv: is its upsampled half written to HBM first?  One whose output spans several 128-cout
+// tiles would bilinearly interpolate every input tile once per cout tile (4x at up1, 2x at up2): there the upsampled half is
+// written once (upsample_kernel) and gathered by plain LDS-DMA like the skip half.  bf16 only: on the fp32 matrix cores the
+// interpolation is small beside the 16x slower MFMAs, and the tensor twice as big.  Small problems (launch-bound, K-split)
+// keep the fused gather - unless the conv then qualifies for the in-workgroup K cut (conv3x3_kwave.hip.h, direct sources
+// only): a quarter of the serial step chain is worth the extra upsample dispatch (ONE 256x256 pair: up1.0 34 -> 23 us, up2.0
+// 30 -> 18 us).  B, H, W: the stage's level.
+inline bool materialise_up(int precision, int B, int H, int W, int Cin, int Cout)
+{
+    if (precision == FIUNET_FP32) return fp32_concat_takes_kwave(B, H, W, Cin, Cout);
+    if (Cout >= 256 && (long long)B * H * W >= 65536) return true;
+    return kwave_applies(B, H, W, Cin, Cout);
+}
+
+void plan_stages(const NetDesc& n, int precision, int B, int H, int W, StageLaunch L[NCONV])
+{
+    const bool fp32 = precision == FIUNET_FP32, x2 = precision == FIUNET_BF16X2;
+    const bool keep_all = n.flags & FIUNET_OPT_KEEP_ALL;
+    // bf16x2 has no ablation path and no in-gather upsample
+    const bool unfused = !x2 && (n.flags & FIUNET_OPT_UNFUSED), gather_up = !x2 && (n.flags & FIUNET_OPT_GATHER_UPSAMPLE);
+    int hs[5] = {H}, ws[5] = {W};
+    for (int k = 1; k < 5; ++k) { hs[k] = hs[k - 1] / 2; ws[k] = ws[k - 1] / 2; }
+    // gray bf16 / bf16x2: the stem is evaluated inside conv 1's gather (16x32 tiles only), unless the ablation path needs its
+    // output in HBM.  The debug read-back (KEEP_ALL) runs the stem kernel for tap 0 as well: in bf16 conv 1 still evaluates the
+    // stem in its gather (the fused numerics are what the read-back must show downstream), in bf16x2 it reads tap 0.
+    const bool fuse_stem = !fp32 && n.cf == 1 && n.stem_w && !unfused && !(x2 && keep_all) && prefer_wide(H, W, 16, 32, 32, 16);
+    L[0] = StageLaunch{};
+    L[0].form = fuse_stem && !keep_all ? STEM_FUSED : n.cf == 3 && !fp32 ? STEM_RGB_SPLIT : STEM_FIRST;
+    L[0].stored = L[0].form != STEM_FUSED;
+    for (int i = 1; i < NCONV; ++i) {
+        StageLaunch& st = L[i];
+        st = StageLaunch{};
+        const int h = hs[kLevel[i]], w = ws[kLevel[i]], cin = conv_cin(n.cout, n.bilinear, i), cout = n.cout[i];
+        if (i == 1 && fuse_stem) st.form = FORM_STEM;
+        else if (kMode[i] == SRC_POOL) st.form = FORM_POOL;
+        else if (kMode[i] == SRC_CONCAT_UP) {
+            if (!n.bilinear) st.form = FORM_CONCAT_CONVT;
+            else if (x2) st.form = FORM_CONCAT_UP;
+            else if (unfused) st.form = FORM_CONCAT_UPCAT;
+            else st.form = !gather_up && materialise_up(precision, B, h, w, cin, cout) ? FORM_CONCAT_UP : FORM_CONCAT_GATHER;
+        }
+        if (kPoolOut[i] >= 0 && !unfused) st.epi = EPI_POOL;                            // also MaxPool2d(2) of the output (unet.py:28)
+        if (i == NCONV - 1 && !unfused) st.epi = n.cf == 1 ? EPI_HEAD : EPI_HEAD3;      // OutConv (unet.py:60) in the last epilogue
+        // the last conv is never K-split: its fused-head form cannot be, and the ablation path must accumulate in the same
+        // order to stay bit-identical with it
+        st.slab = i != NCONV - 1;
+        st.stored = !(i == NCONV - 1 && st.epi != EPI_PLAIN && !keep_all);
+        const bool stem = st.form == FORM_STEM, gather = st.form == FORM_CONCAT_GATHER, direct = !stem && !gather;
+        const bool plain_or_pool = st.epi == EPI_PLAIN || st.epi == EPI_POOL;
+        // an fp32 concat conv on the ablation path whose fused counterpart keeps the in-gather form takes that form's
+        // configuration (same K cut, never conv3x3_kwave_kernel), so that the two paths stay bit-identical per stage
+        const bool as_gather = st.form == FORM_CONCAT_UPCAT && fp32 && !fp32_concat_takes_kwave(B, h, w, cin, cout);
+        st.cfg = choose_conv_cfg(fp32, x2, B, h, w, cin, cout, !stem && plain_or_pool && st.slab,
+                                 (n.force_tile ? n.force_tile[i] : 0) - 1, stem || !n.force_ksplit ? 0 : n.force_ksplit[i],
+                                 direct && plain_or_pool && !as_gather, direct || (gather && cout >= 256), gather || as_gather);
+    }
+}
+
+struct Plan {
+    StageLaunch st[NCONV];
+    int hs[5], ws[5];
+    size_t act_off[NCONV];
+    size_t pool_off[4];  // MaxPool2d(2) of x1..x4: kCout[2k+1] channels at level k+1
+    size_t scratch_off;
+    size_t up_off[NCONV];  // upsampled half of a concat input, where it is materialised (else unused)
+    size_t slab_off;   // split-K partial sums (small problems), kSlabBytes
+    size_t total;
+};
+
+// The stage plan and the workspace plan of one forward.  The reference, under no_grad, frees every non-skip tensor as soon
+// as its consumer has run (model/unet.py:84-95 keeps only x1..x4 alive); here the same liveness is turned into a static
+// layout: every buffer gets the interval [stage that writes it, last stage that reads it] (stage i = conv i of the 18) and
+// buffers whose intervals do not overlap share bytes (first-fit over the buffers in order of their first stage).  B=8 1080p
+// bf16 needs 6.4 GB this way instead of the 16.2 GB of one private buffer per tensor.  FIUNET_OPT_KEEP_ALL (the debug
+// read-back) pins every activation to the end; the ablation path adds its concat scratch; the fused stem / fused head leave
+// activations 0 / 17 out altogether.
+bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p)
+{
+    if (B < 1 || H < 16 || W < 16) return false;
+    // the kernels address a pixel record inside one image plane with 32 bits: H*W*64 B < 4 GiB.
+    // Larger frames go through fiunet_forward_strip band by band.
+    if ((long long)H * W >= (1LL << 26)) return false;
+    plan_stages(n, precision, B, H, W, p.st);
+    const bool keep_all = n.flags & FIUNET_OPT_KEEP_ALL;
+    const size_t es = precision == FIUNET_BF16 ? 2 : 4;   // bytes per activation element (bf16x2: two pieces)
+    p.hs[0] = H; p.ws[0] = W;
+    for (int k = 1; k < 5; ++k) { p.hs[k] = p.hs[k - 1] / 2; p.ws[k] = p.ws[k - 1] / 2; }
+    struct Buf { size_t bytes; int first, last; size_t* off; };
+    std::vector<Buf> bufs;
+    const int END = NCONV;  // "still live after the last conv" (the unfused head, the debug read-back)
+    for (int i = 0; i < NCONV; ++i) {
+        p.act_off[i] = 0;
+        if (!p.st[i].stored) continue;
+        int last = i;  // conv j reads act i as its direct / skip source (kSrc0) or low-res source (kSrc1)
+        for (int j = i + 1; j < NCONV; ++j)
+            if (kSrc0[j] == i || kSrc1[j] == i) last = j;
+        if (i == NCONV - 1 || keep_all) last = END;
+        bufs.push_back({align256((size_t)B * p.hs[kLevel[i]] * p.ws[kLevel[i]] * n.cout[i] * es), i, last,
+                        &p.act_off[i]});
+    }
+    for (int k = 0; k < 4; ++k) {  // MaxPool2d(2) of x1..x4: written by conv 2k+1, read by conv 2k+2
+        bufs.push_back({align256((size_t)B * p.hs[k + 1] * p.ws[k + 1] * n.cout[2 * k + 1] * es), 2 * k + 1,
+                        keep_all ? END : 2 * k + 2, &p.pool_off[k]});
+    }
+    bool upcat = false;
+    for (int i = 0; i < NCONV; ++i) {
+        p.up_off[i] = 0;
+        const int form = i ? p.st[i].form : -1;
+        upcat |= form == FORM_CONCAT_UPCAT;
+        if (form == FORM_CONCAT_UP || form == FORM_CONCAT_CONVT)
+            bufs.push_back({align256((size_t)B * p.hs[kLevel[i]] * p.ws[kLevel[i]] *
+                                     (form == FORM_CONCAT_CONVT ? n.cout[kSrc1[i]] / 2 : n.cout[kSrc1[i]]) * es), i,
+                            keep_all ? END : i, &p.up_off[i]});
+    }
+    p.scratch_off = 0;
+    if (upcat)  // ablation path: concat tensor (<= 128 ch at level 0), rewritten by every Up block
+        bufs.push_back({align256((size_t)B * H * W * 128 * es), 0, END, &p.scratch_off});
+    bufs.push_back({kSlabBytes, 0, END, &p.slab_off});  // split-K partial sums (small problems)
+    std::stable_sort(bufs.begin(), bufs.end(), [](const Buf& a, const Buf& b) { return a.first < b.first; });
+    struct Live { size_t off, bytes; int last; };
+    std::vector<Live> live;
+    size_t total = 0;
+    for (const Buf& b : bufs) {
+        // buffers whose last reader ran before this one's writer are dead (a conv never reads and
+        // writes the same bytes: its sources are live through its own stage)
+        live.erase(std::remove_if(live.begin(), live.end(), [&](const Live& l) { return l.last < b.first; }),
+                   live.end());
+        std::sort(live.begin(), live.end(), [](const Live& a, const Live& c) { return a.off < c.off; });
+        size_t off = 0;
+        for (const Live& l : live) {
+            if (off + b.bytes <= l.off) break;
+            off = std::max(off, l.off + l.bytes);
+        }
+        *b.off = off;
+        live.push_back({off, b.bytes, b.last});
+        total = std::max(total, off + b.bytes);
+    }
+    p.total = total;
+    return true;
+}
+
 // pair kernel: direct sources, plain / pooled epilogue, enough tile pairs to fill the 256 CUs
 template <typename T, int BN, int TH, int TW, int MODE, int EPI>
 constexpr bool pair_capable() { return MODE == SRC_DIRECT && (EPI == EPI_PLAIN || EPI == EPI_POOL) && BN == 128; }
@@ -547,27 +612,14 @@ constexpr bool pair_capable() { return MODE == SRC_DIRECT && (EPI == EPI_PLAIN |
 template <typename T, int EPI, bool X2> int launch_kwave(ConvArgs a, hipStream_t s)
 {
     using Tile = KWaveTile;
-    if (g_name_out) {
-        char buf[96];
-        std::snprintf(buf, sizeof buf, "conv3x3_kwave_kernel<%s%s,64,2,32,%d>+kwave4", sizeof(T) == 2 ? "bf16" : "f32", X2 ? "x2" : "", EPI);
-        *g_name_out = buf;
-    }
+    char name[96] = "";
+    if (g_name_out)
+        std::snprintf(name, sizeof name, "conv3x3_kwave_kernel<%s%s,64,2,32,%d>+kwave4", sizeof(T) == 2 ? "bf16" : "f32", X2 ? "x2" : "", EPI);
     a.tilesX = (a.W + Tile::TW - 1) / Tile::TW;
     a.tilesY = (a.H + Tile::TH - 1) / Tile::TH;
     a.nct = a.Cout / Tile::BN;
-    const long long nblk = (long long)a.B * a.tilesX * a.tilesY * a.nct;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return fail(FIUNET_ERR_INVALID_ARG, "conv grid too large");
-    static std::atomic<bool> lds_attr_set[64];
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !lds_attr_set[dev].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kwave_kernel<EPI, X2, T>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, Tile::LDS_BYTES));
-        lds_attr_set[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((conv3x3_kwave_kernel<EPI, X2, T>), dim3((unsigned)nblk), dim3(256), Tile::LDS_BYTES, s, a);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return launch_lds<&conv3x3_kwave_kernel<EPI, X2, T>>(name, (long long)a.B * a.tilesX * a.tilesY * a.nct, 256, Tile::LDS_BYTES,
+                                                          a, s);
 }
 
 // One conv launch in a given tile shape; ksplit > 1: the K loop (planes) cut over `ksplit` workgroups that store raw
@@ -599,39 +651,11 @@ int launch_conv_maybe_split(ConvArgs a, hipStream_t s, int ksplit)
     return launch_conv_cfg<T, BN, TH, TW, MODE, EPI>(a, s);
 }
 
-PlanOpts plan_opts(const fiunet_ctx* ctx, int H, int W, int precision)
+template <typename T, int MODE, int EPI> int launch_conv_shape(const ConvArgs& a, const ConvCfg& cfg, hipStream_t s)
 {
-    PlanOpts o;
-    o.keep_all = ctx->flags & FIUNET_OPT_KEEP_ALL;
-    o.unfused = ctx->flags & FIUNET_OPT_UNFUSED;
-    o.gather_up = ctx->flags & FIUNET_OPT_GATHER_UPSAMPLE;
-    // bf16 gray network: the stem is evaluated inside conv 1's gather (SRC_STEM, 16x32 tiles only),
-    // unless the ablation path or the debug read-back needs its output in HBM
-    o.fused_stem = precision == FIUNET_BF16 && ctx->cf == 1 && !o.unfused && !o.keep_all &&
-                   ctx->stem_w_split != nullptr && prefer_wide(H, W, 16, 32, 32, 16);
-    o.fused_head = !o.unfused && !o.keep_all;  // OutConv reduced in the last conv's epilogue
-    o.cout = ctx->cout;
-    o.convt = !ctx->bilinear;
-    o.x2 = precision == FIUNET_BF16X2;
-    if (o.x2) {   // gray: the stem is evaluated inside conv 1's gather (SRC_STEM_X2) unless the read-back wants its output
-        o.fused_stem = ctx->cf == 1 && !o.keep_all && ctx->stem_w_split != nullptr && prefer_wide(H, W, 16, 32, 32, 16);
-        o.fused_head = !o.keep_all;
-        o.unfused = o.gather_up = false;
-    }
-    return o;
-}
-
-template <typename T, int MODE, int EPI> int launch_conv_shape(const ConvArgs& a, hipStream_t s)
-{
-    constexpr bool splittable_kind = !src_is_stem(MODE) && (EPI == EPI_PLAIN || EPI == EPI_POOL);
     if (a.Cout != 64 && a.Cout % 128 != 0) return fail(FIUNET_ERR_INVALID_ARG, "Cout must be 64 or k*128");
     if ((EPI == EPI_HEAD || EPI == EPI_HEAD3) && a.Cout != 64) return fail(FIUNET_ERR_INVALID_ARG, "fused head needs Cout == 64");
-    constexpr bool kwave_kind = (MODE == SRC_DIRECT || MODE == SRC_DIRECT_X2) && (EPI == EPI_PLAIN || EPI == EPI_POOL);
-    const ConvCfg cfg = choose_conv_cfg(sizeof(T) == 4, src_is_x2(MODE), a.B, a.H, a.W, a.C0 + a.C1, a.Cout,
-                                        splittable_kind && a.kslab && a.dst, a.force_tile - 1, a.force_ksplit, kwave_kind && !a.concat_origin,
-                                        (MODE == SRC_DIRECT || MODE == SRC_DIRECT_X2 || (MODE == SRC_CONCAT_UP && a.Cout >= 256)),
-                                        MODE == SRC_CONCAT_UP || a.concat_origin);
-    if constexpr (kwave_kind) {
+    if constexpr ((MODE == SRC_DIRECT || MODE == SRC_DIRECT_X2) && (EPI == EPI_PLAIN || EPI == EPI_POOL)) {
         if (cfg.kwave) return launch_kwave<T, EPI, MODE == SRC_DIRECT_X2>(a, s);
     }
     if (cfg.small) return launch_conv_maybe_split<T, 64, 8, 32, MODE, EPI>(a, s, cfg.ksplit);
@@ -648,52 +672,59 @@ template <typename T, int MODE, int EPI> int launch_conv_shape(const ConvArgs& a
     return fail(FIUNET_ERR_INVALID_ARG, "fused head needs Cout == 64");
 }
 
-// mode: SRC_DIRECT | SRC_CONCAT_UP; epi: EPI_PLAIN | EPI_HEAD | EPI_HEAD3 | EPI_POOL (direct sources only)
-template <typename T> int launch_conv(const ConvArgs& a, int mode, int epi, hipStream_t s)
+// mode: SRC_DIRECT | SRC_CONCAT_UP | SRC_DIRECT_X2 | SRC_STEM | SRC_STEM_X2; epi: EPI_PLAIN | EPI_HEAD | EPI_HEAD3 | EPI_POOL
+// (direct sources only); cfg: the stage's (plan_stages)
+template <typename T> int launch_conv(const ConvArgs& a, int mode, int epi, const ConvCfg& cfg, hipStream_t s)
 {
     constexpr int PL = Elem<T>::PL;
     if (a.C0 % PL || a.C1 % PL) return fail(FIUNET_ERR_INVALID_ARG, "channels not a plane multiple");
-    if (mode == SRC_CONCAT_UP && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_CONCAT_UP, EPI_PLAIN>(a, s);
-    if (mode == SRC_DIRECT && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_DIRECT, EPI_PLAIN>(a, s);
-    if (mode == SRC_DIRECT && epi == EPI_HEAD) return launch_conv_shape<T, SRC_DIRECT, EPI_HEAD>(a, s);
-    if (mode == SRC_DIRECT && epi == EPI_HEAD3) return launch_conv_shape<T, SRC_DIRECT, EPI_HEAD3>(a, s);
-    if (mode == SRC_DIRECT && epi == EPI_POOL) return launch_conv_shape<T, SRC_DIRECT, EPI_POOL>(a, s);
+    if (mode == SRC_CONCAT_UP && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_CONCAT_UP, EPI_PLAIN>(a, cfg, s);
+    if (mode == SRC_DIRECT && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_DIRECT, EPI_PLAIN>(a, cfg, s);
+    if (mode == SRC_DIRECT && epi == EPI_HEAD) return launch_conv_shape<T, SRC_DIRECT, EPI_HEAD>(a, cfg, s);
+    if (mode == SRC_DIRECT && epi == EPI_HEAD3) return launch_conv_shape<T, SRC_DIRECT, EPI_HEAD3>(a, cfg, s);
+    if (mode == SRC_DIRECT && epi == EPI_POOL) return launch_conv_shape<T, SRC_DIRECT, EPI_POOL>(a, cfg, s);
     if constexpr (sizeof(T) == 2) {   // FIUNET_BF16X2: two-piece operands
-        if (mode == SRC_DIRECT_X2 && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_PLAIN>(a, s);
-        if (mode == SRC_DIRECT_X2 && epi == EPI_POOL) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_POOL>(a, s);
-        if (mode == SRC_DIRECT_X2 && epi == EPI_HEAD) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_HEAD>(a, s);
-        if (mode == SRC_DIRECT_X2 && epi == EPI_HEAD3) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_HEAD3>(a, s);
-
-    }
-    if constexpr (sizeof(T) == 2) {
+        if (mode == SRC_DIRECT_X2 && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_PLAIN>(a, cfg, s);
+        if (mode == SRC_DIRECT_X2 && epi == EPI_POOL) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_POOL>(a, cfg, s);
+        if (mode == SRC_DIRECT_X2 && epi == EPI_HEAD) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_HEAD>(a, cfg, s);
+        if (mode == SRC_DIRECT_X2 && epi == EPI_HEAD3) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_HEAD3>(a, cfg, s);
         if ((mode == SRC_STEM || mode == SRC_STEM_X2) && epi == EPI_POOL && a.Cout == 64) {  // 32-wide tiles only (the patch layout)
-            const bool small = choose_conv_cfg(false, mode == SRC_STEM_X2, a.B, a.H, a.W, 64, 64, false, a.force_tile - 1, 0).small;
             if (mode == SRC_STEM)
-                return small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM, EPI_POOL>(a, s)
-                             : launch_conv_cfg<T, 64, 16, 32, SRC_STEM, EPI_POOL>(a, s);
-            return small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM_X2, EPI_POOL>(a, s)
-                         : launch_conv_cfg<T, 64, 16, 32, SRC_STEM_X2, EPI_POOL>(a, s);
+                return cfg.small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM, EPI_POOL>(a, s)
+                                 : launch_conv_cfg<T, 64, 16, 32, SRC_STEM, EPI_POOL>(a, s);
+            return cfg.small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM_X2, EPI_POOL>(a, s)
+                             : launch_conv_cfg<T, 64, 16, 32, SRC_STEM_X2, EPI_POOL>(a, s);
         }
     }
     return fail(FIUNET_ERR_INVALID_ARG, "unsupported gather/epilogue combination");
 }
 
-// The band [y_origin, y_origin + H) of an image of Hg rows (un-tiled: y_origin = 0, Hg = H).
+// The band [y_origin, y_origin + H) of an image of Hg rows (un-tiled: y_origin = 0, Hg = H), launched as the plan `p.st`
+// says.  T = float (FIUNET_FP32) or __bf16 (FIUNET_BF16, FIUNET_BF16X2).
+// FIUNET_BF16X2: the fp32 contract on the bf16 pipe (include/fiunet.h).  Activations are two-piece bf16 tensors
+// [hi planes | lo planes] (4 B per element), weights [wh | wl]; every conv is the bf16 direct kernel in mode
+// SRC_DIRECT_X2 (three virtual planes per real plane: (xh, wh), (xh, wl) on the same in-tile, (xl, wh)), the stem is the
+// exact-fp32 kernel with a splitting epilogue (no dither), the upsampled halves are always materialised
+// (x2_upsample_kernel: fp32 interpolation of hi + lo; bilinear=False: convt2x2_kernel<bf16, X2>), the head is the usual
+// fused fp32 reduction; no ablation path.
+// u1/u2 (uint8 frames) replace f1/f2 only where the stem reads the frames itself (fused stem, RGB split stem); out_u8
+// replaces out only where the head is fused into the last conv's epilogue (fiunet_forward_u8 decides)
 template <typename T>
-int forward_impl(fiunet_ctx* ctx, const float* f1, const float* f2, float* out, int B, int H,
-                 int W, char* ws, const Plan& p, hipStream_t s, int y_origin, int Hg,
-                 const uint8_t* u1 = nullptr, const uint8_t* u2 = nullptr, uint8_t* out_u8 = nullptr,
+int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f2, float* out, int B, int H, int W,
+                 char* ws, const Plan& p, hipStream_t s, int y_origin, int Hg, const uint8_t* u1 = nullptr,
+                 const uint8_t* u2 = nullptr, uint8_t* out_u8 = nullptr,
                  size_t out_img_stride = 0 /* elements between images of out / out_u8; 0 = contiguous */)
 {
-    // u1/u2 (uint8 frames) replace f1/f2 only where the stem is fused into conv 1's gather; out_u8 replaces
-    // out only where the head is fused into the last conv's epilogue (fiunet_forward_u8 decides)
+    const bool x2 = precision == FIUNET_BF16X2, bf16 = precision == FIUNET_BF16;
+    if (x2 && !ctx->x2_ready)
+        return fail(FIUNET_ERR_NOT_LOADED, "precision bf16x2: call fiunet_prepare_precision(ctx, FIUNET_BF16X2) after "
+                                           "fiunet_load_weights (it builds the two-piece weight copies)");
+    const StageLaunch* L = p.st;
+    const size_t es = x2 ? 4 : sizeof(T);   // bytes per activation element
     int hg[5];  // rows of the whole image at each pyramid level (floor halving, unet.py:28)
     hg[0] = Hg;
     for (int l = 1; l < 5; ++l) hg[l] = hg[l - 1] / 2;
-    const bool bf16 = sizeof(T) == 2;
-    const bool unfused = ctx->flags & FIUNET_OPT_UNFUSED;
-    auto act = [&](int i) { return (T*)(ws + p.act_off[i]); };
-    T* scratch = (T*)(ws + p.scratch_off);
+    auto act = [&](int i) { return ws + p.act_off[i]; };
 
     // optional per-layer timing: event e[0] before the stem, e[i+1] after stage i
     hipEvent_t* ev = nullptr;
@@ -707,89 +738,84 @@ int forward_impl(fiunet_ctx* ctx, const float* f1, const float* f2, float* out, 
         ctx->ev_used += NCONV + 1;
         HIP_TRY(hipEventRecord(ev[0], s));
     }
-    // bf16 gray network: the stem is evaluated inside conv 1's gather (SRC_STEM), unless the
-    // ablation path or the debug readback needs its output in HBM
-    const PlanOpts po = plan_opts(ctx, H, W, bf16 ? FIUNET_BF16 : FIUNET_FP32);
-    // with KEEP_ALL the stem also runs as its own kernel (tap 0 in HBM) while conv 1 still
-    // evaluates it in its gather: the fused numerics are what the read-back must show downstream
-    const bool fuse_stem = po.fused_stem || (bf16 && ctx->cf == 1 && !unfused && ctx->stem_w_split != nullptr &&
-                                             prefer_wide(H, W, 16, 32, 32, 16));
-    const bool run_stem = !po.fused_stem;
     // bf16 only: ordered input dither of the stem (conv3x3_mfma.hip.h, stem_dither); 2^-8 = a quarter of
     // an 8-bit input step peak to peak
-    const float stem_dither_amp = (bf16 && !(ctx->flags & FIUNET_OPT_NO_DITHER)) ? 0.00390625f : 0.f;
-    // conv 0: fp32 stem (unet.py:72, first conv of inc)
-    bool stem_split_rgb = false;
-    if (run_stem) {
-        const ConvWeights& cw = ctx->conv[0];
+    const float dither = bf16 && !(ctx->flags & FIUNET_OPT_NO_DITHER) ? 0.00390625f : 0.f;
+    const ConvWeights& c0 = ctx->conv[0];
+    const double stem_flops = 2.0 * B * H * W * 9.0 * c0.cin * c0.cout;
+    if (L[0].form == STEM_RGB_SPLIT) {
+        // RGB: split-bf16 MFMA stem (pointwise.hip.h), also on the ablation path (all 18 stage outputs of the RGB bf16
+        // network stay bit-identical fused vs unfused); bf16x2 with a two-piece epilogue (the exact-fp32 MFMA stem needs 56
+        // fp32 MFMAs per 16 pixels: it was the longest stage of the RGB network); it reads the uint8 frames itself on the
+        // video path.  Persistent workgroups, one tile after the other: exactly as many as are resident at once
+        // (FIUNET_RGB_STEM_OCC = 2 per CU, the kernel's __launch_bounds__: 176 registers); with more than that the surplus
+        // ran a second round on a fraction of the chip
+        const long long ntiles = (long long)B * ((H + 15) / 16) * ((W + 31) / 32);
+        const dim3 g2((unsigned)std::min<long long>(ntiles, 256 * FIUNET_RGB_STEM_OCC));
+        if (x2)
+            hipLaunchKernelGGL(stem_rgb_split_kernel<true>, g2, dim3(256), 0, s, f1, f2, (const float*)c0.w_f32, c0.scale,
+                               c0.shift, (__bf16*)act(0), B, H, W, dither, u1, u2);
+        else
+            hipLaunchKernelGGL(stem_rgb_split_kernel<false>, g2, dim3(256), 0, s, f1, f2, (const float*)c0.w_f32, c0.scale,
+                               c0.shift, (__bf16*)act(0), B, H, W, dither, u1, u2);
+        HIP_TRY(hipGetLastError());
+    } else if (L[0].form == STEM_FIRST) {   // the exact fp32 stem kernel (bf16x2: its epilogue splits into the two pieces)
         const long long nruns = (long long)B * H * (((W + 15) / 16 + 7) / 8);  // 8-tile row runs
-        dim3 grid((unsigned)std::min<long long>((nruns + 3) / 4, 256 * 64));
-        if (ctx->cf == 1)
-            hipLaunchKernelGGL((conv3x3_first_kernel<T, 1>), grid, dim3(256), 0, s, f1, f2,
-                               (const float*)cw.w_f32, cw.scale, cw.shift, act(0), B, H, W, stem_dither_amp);
-        else if (bf16) {
-            // RGB bf16: split-bf16 MFMA stem (pointwise.hip.h), also on the ablation path (all 18 stage outputs of
-            // the RGB bf16 network stay bit-identical fused vs unfused); the fp32 network keeps the exact kernel
-            if constexpr (sizeof(T) == 2) {
-                const long long ntiles = (long long)B * ((H + 15) / 16) * ((W + 31) / 32);
-                // persistent workgroups, one tile after the other: exactly as many as are resident at once
-                // (FIUNET_RGB_STEM_OCC = 2 per CU, the kernel's __launch_bounds__: 176 registers); with more than that the
-                // surplus ran a second round on a fraction of the chip
-                dim3 g2((unsigned)std::min<long long>(ntiles, 256 * FIUNET_RGB_STEM_OCC));
-                hipLaunchKernelGGL(stem_rgb_split_kernel<false>, g2, dim3(256), 0, s, f1, f2, (const float*)cw.w_f32, cw.scale,
-                                   cw.shift, (__bf16*)act(0), B, H, W, stem_dither_amp, u1, u2);
-                stem_split_rgb = true;
-            }
-        } else
-            hipLaunchKernelGGL((conv3x3_first_kernel<T, 3>), grid, dim3(256), 0, s, f1, f2,
-                               (const float*)cw.w_f32, cw.scale, cw.shift, act(0), B, H, W, stem_dither_amp);
+        const dim3 grid((unsigned)std::min<long long>((nruns + 3) / 4, 256 * 64));
+        if (x2)
+            hipLaunchKernelGGL((conv3x3_first_kernel<__bf16, 1, true>), grid, dim3(256), 0, s, f1, f2, (const float*)c0.w_f32,
+                               c0.scale, c0.shift, (__bf16*)act(0), B, H, W, dither);
+        else if (ctx->cf == 1)
+            hipLaunchKernelGGL((conv3x3_first_kernel<T, 1>), grid, dim3(256), 0, s, f1, f2, (const float*)c0.w_f32, c0.scale,
+                               c0.shift, (T*)act(0), B, H, W, dither);
+        else if constexpr (sizeof(T) == 4)   // (RGB bf16 runs the split stem)
+            hipLaunchKernelGGL((conv3x3_first_kernel<T, 3>), grid, dim3(256), 0, s, f1, f2, (const float*)c0.w_f32, c0.scale,
+                               c0.shift, (T*)act(0), B, H, W, dither);
         HIP_TRY(hipGetLastError());
     }
     if (ev) {
-        const ConvWeights& cw = ctx->conv[0];
         HIP_TRY(hipEventRecord(ev[1], s));
-        ctx->layer_name[0] = stem_split_rgb ? std::string("stem_rgb_split_kernel")
-                             : run_stem ? std::string("conv3x3_first_kernel<") + (bf16 ? "bf16" : "f32") +
-                                            "," + std::to_string(ctx->cf) + ">"
-                                      : std::string("(stem fused into next stage)");
-        ctx->layer_flops[0] = run_stem ? 2.0 * B * H * W * 9.0 * cw.cin * cw.cout : 0.0;
+        if (L[0].form == STEM_FUSED) ctx->layer_name[0] = "(stem fused into next stage)";
+        else if (x2) ctx->layer_name[0] = L[0].form == STEM_FIRST ? "conv3x3_first_kernel<f32 arithmetic, two-piece output>"
+                                                                  : "stem_rgb_split_kernel<two-piece output>";
+        else ctx->layer_name[0] = L[0].form == STEM_FIRST ? std::string("conv3x3_first_kernel<") + (bf16 ? "bf16" : "f32") + "," +
+                                                                std::to_string(ctx->cf) + ">"
+                                                          : std::string("stem_rgb_split_kernel");
+        ctx->layer_flops[0] = L[0].form == STEM_FUSED ? 0.0 : stem_flops;
     }
     for (int i = 1; i < NCONV; ++i) {
+        const StageLaunch& st = L[i];
         const ConvWeights& cw = ctx->conv[i];
         const int lv = kLevel[i];
         ConvArgs a;
         std::memset(&a, 0, sizeof(a));
         a.B = B; a.H = p.hs[lv]; a.W = p.ws[lv];
         a.Cout = cw.cout;
-        a.wgt = bf16 ? cw.w_bf16 : cw.w_f32;
+        a.wgt = x2 ? cw.w_x2 : bf16 ? cw.w_bf16 : cw.w_f32;
         a.scale = cw.scale; a.shift = cw.shift;
         a.relu = 1;
         a.zero_page = ctx->zero_page;
         a.ksplit = 1;
         a.pair = (ctx->flags & FIUNET_OPT_PAIR_TILES) ? 1 : 0;
-        // the last conv is never K-split: its fused-head form cannot be, and the ablation path must
-        // accumulate in the same order to stay bit-identical with it
-        a.kslab = i == NCONV - 1 ? nullptr : (float*)(ws + p.slab_off);
+        a.kslab = st.slab ? (float*)(ws + p.slab_off) : nullptr;
         a.stamp = (ctx->stamps && i == ctx->stamp_layer) ? ctx->stamps : nullptr;
         a.stamp_cap = (unsigned)kStampWaves;
-        a.force_tile = ctx->force_tile[i]; a.force_ksplit = ctx->force_ksplit[i];
-        a.dst = act(i);
-        int mode = kMode[i];
+        a.dst = st.stored ? act(i) : nullptr;
         a.src0 = act(kSrc0[i]);
-        a.C0 = ctx->cout[kSrc0[i]];
-        if (mode == SRC_POOL) {
+        a.C0 = ctx->cout[kSrc0[i]];   // (bf16x2: REAL channels: the kernel knows both pieces of a tensor)
+        int mode = x2 ? SRC_DIRECT_X2 : SRC_DIRECT;
+        if (st.form == FORM_POOL) {
             // MaxPool2d(2) of the source (unet.py:28): already materialised by the producer's
-            // epilogue (EPI_POOL below), or by maxpool2_kernel right here on the ablation path
-            T* pooled = (T*)(ws + p.pool_off[lv - 1]);
-            if (unfused) {
+            // epilogue (EPI_POOL), or by maxpool2_kernel right here on the ablation path
+            char* pooled = ws + p.pool_off[lv - 1];
+            if (L[i - 1].epi != EPI_POOL) {
                 const size_t n = (size_t)B * a.H * a.W * (a.C0 * sizeof(T) / 16);
                 hipLaunchKernelGGL((maxpool2_kernel<T>), dim3(grid_for(n)), dim3(256), 0, s,
-                                   (const T*)a.src0, pooled, B, p.hs[lv - 1], p.ws[lv - 1], a.C0);
+                                   (const T*)a.src0, (T*)pooled, B, p.hs[lv - 1], p.ws[lv - 1], a.C0);
                 HIP_TRY(hipGetLastError());
             }
             a.src0 = pooled;
-            mode = SRC_DIRECT;
-        } else if (mode == SRC_CONCAT_UP) {
+        } else if (kMode[i] == SRC_CONCAT_UP) {
             a.src1 = act(kSrc1[i]);
             a.C1 = ctx->cout[kSrc1[i]];
             a.lowH = p.hs[lv + 1]; a.lowW = p.ws[lv + 1];
@@ -803,230 +829,81 @@ int forward_impl(fiunet_ctx* ctx, const float* f1, const float* f2, float* out, 
             // aten area_pixel_compute_scale, align_corners=True: (in - 1) / (out - 1) in fp32
             a.sy = 2 * a.lowHg > 1 ? (float)(a.lowHg - 1) / (float)(2 * a.lowHg - 1) : 0.f;
             a.sx = 2 * a.lowW > 1 ? (float)(a.lowW - 1) / (float)(2 * a.lowW - 1) : 0.f;
-        }
-        if (mode == SRC_CONCAT_UP && !ctx->bilinear) {
-            // bilinear=False (unet.py:42-44): ConvTranspose2d(C, C / 2, 2, 2) of the low-res tensor + F.pad, written once
-            // as a full-resolution tensor; the conv then gathers two full-resolution sources (skip planes, then these)
-            const auto& ct = ctx->convt[(i - 10) / 2];
-            T* up = (T*)(ws + p.up_off[i]);
-            ConvTArgs c;
-            std::memset(&c, 0, sizeof(c));
-            c.low = a.src1; c.wgt = bf16 ? ct.w_bf16 : ct.w_f32; c.bias = ct.bias; c.dst = up;
-            c.B = B; c.H = a.H; c.W = a.W; c.lowH = a.lowH; c.lowW = a.lowW; c.Cin = ct.cin; c.Cout = ct.cout;
-            c.padT = a.padT; c.padL = a.padL; c.upOffY = a.upOffY; c.lowOffY = a.lowOffY; c.lowHg = a.lowHg;
-            if (a.C1 != ct.cin) return fail(FIUNET_ERR_INVALID_ARG, "internal: transposed-conv channel plan mismatch");
-            if (y_origin != 0 || Hg != H || a.H != 2 * a.lowH || a.W != 2 * a.lowW)   // F.pad rows / columns (and a band's edges)
-                HIP_TRY(hipMemsetAsync(up, 0, (size_t)B * a.H * a.W * ct.cout * sizeof(T), s));
-            const long long units = (long long)B * a.lowH * ((a.lowW + 31) / 32) * (ct.cout / 64);   // 32 pixels per wave
-            hipLaunchKernelGGL((convt2x2_kernel<T>), dim3((unsigned)std::min<long long>((units + 3) / 4, 256 * 16)),
-                               dim3(256), 0, s, c);
-            HIP_TRY(hipGetLastError());
-            a.src1 = up; a.C1 = ct.cout; mode = SRC_DIRECT;
-        }
-        if (a.C0 + a.C1 != cw.cin) return fail(FIUNET_ERR_INVALID_ARG, "internal: channel plan mismatch");
-        if (i == 1 && fuse_stem) {
-            mode = SRC_STEM;
-            a.f1 = f1; a.f2 = f2;
-            a.u1 = u1; a.u2 = u2;
-            a.stem_w = ctx->stem_w_split;
-            a.dither = stem_dither_amp;
-        }
-        if (unfused && mode == SRC_CONCAT_UP) {
-            const size_t n = (size_t)B * a.H * a.W * ((a.C0 + a.C1) * sizeof(T) / 16);
-            hipLaunchKernelGGL((upcat_kernel<T>), dim3(grid_for(n)), dim3(256), 0, s, a, scratch);
-            HIP_TRY(hipGetLastError());
-            a.src0 = scratch; a.C0 = a.C0 + a.C1; a.C1 = 0; a.src1 = nullptr; mode = SRC_DIRECT;
-            if (!bf16 && !fp32_concat_takes_kwave(B, a.H, a.W, a.C0, a.Cout)) a.concat_origin = 1;
-        }
-        if (mode == SRC_CONCAT_UP &&
-            materialise_up(i, bf16 ? FIUNET_BF16 : FIUNET_FP32, unfused || po.gather_up, B, a.H, a.W, ctx->cout)) {
-            T* up = (T*)(ws + p.up_off[i]);
-            const dim3 grid((unsigned)((a.W * 4 + 255) / 256), (unsigned)((a.H + UPS_ROWS - 1) / UPS_ROWS),
-                            (unsigned)(B * (a.C1 / Elem<T>::PL)));
-            if (grid.y > 65535u || grid.z > 65535u) return fail(FIUNET_ERR_INVALID_ARG, "upsample grid too large");
-            hipLaunchKernelGGL((upsample_kernel<T>), grid, dim3(256), 0, s, a, up);
-            HIP_TRY(hipGetLastError());
-            a.src1 = up; mode = SRC_DIRECT;  // two full-resolution sources: skip planes, then these
-        }
-        int epi = EPI_PLAIN;
-        if (kPoolOut[i] >= 0 && !unfused) {  // also emit MaxPool2d(2) of this output (unet.py:28)
-            epi = EPI_POOL;
-            a.pool_dst = ws + p.pool_off[kPoolOut[i]];
-        }
-        if (i == NCONV - 1 && !unfused) {  // fuse OutConv (unet.py:60) into the last epilogue
-            epi = ctx->cf == 1 ? EPI_HEAD : EPI_HEAD3;
-            a.head_w = ctx->head_w; a.head_b = ctx->head_b; a.head_out = out; a.head_out_u8 = out_u8; a.head_nc = ctx->cf;
-            a.head_img_stride = out_img_stride ? out_img_stride : (size_t)ctx->cf * H * W;
-            if (!(ctx->flags & FIUNET_OPT_KEEP_ALL)) a.dst = nullptr;
-        }
-        g_name_out = ev ? &ctx->layer_name[i] : nullptr;
-        const int rc = launch_conv<T>(a, mode, epi, s);
-        g_name_out = nullptr;
-        if (rc != FIUNET_OK) return rc;
-        if (ev) {
-            ctx->layer_flops[i] = 2.0 * B * a.H * a.W * 9.0 * cw.cin * cw.cout;
-            if (i == 1 && fuse_stem && !run_stem)  // the fused stage also does the stem's FLOPs
-                ctx->layer_flops[i] += 2.0 * B * H * W * 9.0 * ctx->conv[0].cin * ctx->conv[0].cout;
-            if (i < NCONV - 1 || !unfused) HIP_TRY(hipEventRecord(ev[i + 1], s));
-        }
-    }
-    if (unfused) {
-        const size_t n = (size_t)B * H * W;
-        hipLaunchKernelGGL((head1x1_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                           (const T*)act(NCONV - 1), ctx->head_w, ctx->head_b, out, B, H, W, ctx->cf);
-        HIP_TRY(hipGetLastError());
-        if (ev) HIP_TRY(hipEventRecord(ev[NCONV], s));
-    }
-    return FIUNET_OK;
-}
-
-// FIUNET_BF16X2: the fp32 contract on the bf16 pipe (include/fiunet.h).  Activations are two-piece bf16 tensors
-// [hi planes | lo planes] (4 B per element), weights [wh | wl]; every conv is the bf16 direct kernel in mode
-// SRC_DIRECT_X2 (three virtual planes per real plane: (xh, wh), (xh, wl) on the same in-tile, (xl, wh)), the stem is the
-// exact-fp32 kernel with a splitting epilogue, the upsampled halves are always materialised (x2_upsample_kernel: fp32
-// interpolation of hi + lo; bilinear=False: convt2x2_kernel<bf16, X2>), the head is the usual fused fp32 reduction.
-// Small problems cut K like the other precisions (choose_conv_cfg: over workgroups with the tile reduce pass, or over the waves of
-// a workgroup).  FIUNET_OPT_KEEP_ALL keeps every activation for the read-back; no ablation path.
-int forward_x2(fiunet_ctx* ctx, const float* f1, const float* f2, float* out, int B, int H, int W, char* ws,
-               const Plan& p, hipStream_t s, int y_origin, int Hg, uint8_t* out_u8, const uint8_t* u1 = nullptr,
-               const uint8_t* u2 = nullptr, size_t out_img_stride = 0)
-{
-    using T = __bf16;
-    if (!ctx->x2_ready)
-        return fail(FIUNET_ERR_NOT_LOADED, "precision bf16x2: call fiunet_prepare_precision(ctx, FIUNET_BF16X2) after "
-                                           "fiunet_load_weights (it builds the two-piece weight copies)");
-    const bool keep_all = ctx->flags & FIUNET_OPT_KEEP_ALL;
-    int hg[5];
-    hg[0] = Hg;
-    for (int l = 1; l < 5; ++l) hg[l] = hg[l - 1] / 2;
-    auto act = [&](int i) { return ws + p.act_off[i]; };
-    hipEvent_t* ev = nullptr;
-    if (ctx->profiling) {
-        if (ctx->ev_used + NCONV + 1 > ctx->ev_pool.size()) {
-            const size_t old = ctx->ev_pool.size();
-            ctx->ev_pool.resize(old + 64 * (NCONV + 1));
-            for (size_t k = old; k < ctx->ev_pool.size(); ++k) HIP_TRY(hipEventCreate(&ctx->ev_pool[k]));
-        }
-        ev = ctx->ev_pool.data() + ctx->ev_used;
-        ctx->ev_used += NCONV + 1;
-        HIP_TRY(hipEventRecord(ev[0], s));
-    }
-    const bool fuse_stem = plan_opts(ctx, H, W, FIUNET_BF16X2).fused_stem;   // gray, wide tiles, no read-back
-    if (fuse_stem) {
-        if (ev) {
-            HIP_TRY(hipEventRecord(ev[1], s));
-            ctx->layer_name[0] = "(stem fused into next stage)";
-            ctx->layer_flops[0] = 0.0;
-        }
-    } else {   // conv 0: exact-fp32 stem (no dither: this is the fp32-contract path), its epilogue splits into the two pieces
-        const ConvWeights& cw = ctx->conv[0];
-        const long long nruns = (long long)B * H * (((W + 15) / 16 + 7) / 8);
-        dim3 grid((unsigned)std::min<long long>((nruns + 3) / 4, 256 * 64));
-        if (ctx->cf == 1)
-            hipLaunchKernelGGL((conv3x3_first_kernel<__bf16, 1, true>), grid, dim3(256), 0, s, f1, f2, (const float*)cw.w_f32,
-                               cw.scale, cw.shift, (__bf16*)act(0), B, H, W, 0.f);
-        else {   // RGB: the split-bf16 MFMA stem with a two-piece epilogue (the exact-fp32 MFMA stem needs 56 fp32 MFMAs per
-                 // 16 pixels: it was the longest stage of the RGB network); it reads the uint8 frames itself on the video path
-            const long long ntiles = (long long)B * ((H + 15) / 16) * ((W + 31) / 32);
-            dim3 g2((unsigned)std::min<long long>(ntiles, 256 * FIUNET_RGB_STEM_OCC));
-            hipLaunchKernelGGL(stem_rgb_split_kernel<true>, g2, dim3(256), 0, s, f1, f2, (const float*)cw.w_f32, cw.scale,
-                               cw.shift, (__bf16*)act(0), B, H, W, 0.f, u1, u2);
-        }
-        HIP_TRY(hipGetLastError());
-        if (ev) {
-            HIP_TRY(hipEventRecord(ev[1], s));
-            ctx->layer_name[0] = ctx->cf == 1 ? "conv3x3_first_kernel<f32 arithmetic, two-piece output>"
-                                              : "stem_rgb_split_kernel<two-piece output>";
-            ctx->layer_flops[0] = 2.0 * B * H * W * 9.0 * cw.cin * cw.cout;
-        }
-    }
-    for (int i = 1; i < NCONV; ++i) {
-        const ConvWeights& cw = ctx->conv[i];
-        const int lv = kLevel[i];
-        ConvArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.B = B; a.H = p.hs[lv]; a.W = p.ws[lv];
-        a.Cout = cw.cout;
-        a.wgt = cw.w_x2;
-        a.scale = cw.scale; a.shift = cw.shift;
-        a.relu = 1;
-        a.zero_page = ctx->zero_page;
-        a.ksplit = 1;
-        a.kslab = i == NCONV - 1 ? nullptr : (float*)(ws + p.slab_off);   // small problems: K-split like the other paths
-        a.stamp = (ctx->stamps && i == ctx->stamp_layer) ? ctx->stamps : nullptr;
-        a.stamp_cap = (unsigned)kStampWaves;
-        a.force_tile = ctx->force_tile[i]; a.force_ksplit = ctx->force_ksplit[i];
-        a.dst = act(i);
-        a.src0 = act(kSrc0[i]);
-        a.C0 = ctx->cout[kSrc0[i]];                // REAL channels: the kernel knows both pieces of a tensor
-        if (kMode[i] == SRC_POOL) {
-            a.src0 = ws + p.pool_off[lv - 1];
-        } else if (kMode[i] == SRC_CONCAT_UP) {
-            a.src1 = act(kSrc1[i]);
-            a.C1 = ctx->cout[kSrc1[i]];
-            a.lowH = p.hs[lv + 1]; a.lowW = p.ws[lv + 1];
-            a.lowHg = hg[lv + 1];
-            a.upOffY = y_origin >> lv;
-            a.lowOffY = y_origin >> (lv + 1);
-            const int dy = hg[lv] - 2 * a.lowHg, dx = a.W - 2 * a.lowW;
-            a.padT = dy / 2; a.padL = dx / 2;
-            a.sy = 2 * a.lowHg > 1 ? (float)(a.lowHg - 1) / (float)(2 * a.lowHg - 1) : 0.f;
-            a.sx = 2 * a.lowW > 1 ? (float)(a.lowW - 1) / (float)(2 * a.lowW - 1) : 0.f;
             char* up = ws + p.up_off[i];
-            if (ctx->bilinear) {
-                const dim3 grid((unsigned)((a.W * 4 + 255) / 256), (unsigned)((a.H + UPS_ROWS - 1) / UPS_ROWS),
-                                (unsigned)(B * (a.C1 / 32)));
-                if (grid.y > 65535u || grid.z > 65535u) return fail(FIUNET_ERR_INVALID_ARG, "upsample grid too large");
-                hipLaunchKernelGGL(x2_upsample_kernel, grid, dim3(256), 0, s, a, up);
-                HIP_TRY(hipGetLastError());
-            } else {   // bilinear=False (unet.py:42-44): ConvTranspose2d(C, C / 2, 2, 2) + F.pad on two-piece operands
+            if (st.form == FORM_CONCAT_CONVT) {
+                // bilinear=False (unet.py:42-44): ConvTranspose2d(C, C / 2, 2, 2) of the low-res tensor + F.pad, written once
+                // as a full-resolution tensor; the conv then gathers two full-resolution sources (skip planes, then these)
                 const auto& ct = ctx->convt[(i - 10) / 2];
                 ConvTArgs c;
                 std::memset(&c, 0, sizeof(c));
-                c.low = a.src1; c.wgt = ct.w_x2; c.bias = ct.bias; c.dst = up;
+                c.low = a.src1; c.wgt = x2 ? ct.w_x2 : bf16 ? ct.w_bf16 : ct.w_f32; c.bias = ct.bias; c.dst = up;
                 c.B = B; c.H = a.H; c.W = a.W; c.lowH = a.lowH; c.lowW = a.lowW; c.Cin = ct.cin; c.Cout = ct.cout;
                 c.padT = a.padT; c.padL = a.padL; c.upOffY = a.upOffY; c.lowOffY = a.lowOffY; c.lowHg = a.lowHg;
                 if (a.C1 != ct.cin) return fail(FIUNET_ERR_INVALID_ARG, "internal: transposed-conv channel plan mismatch");
                 if (y_origin != 0 || Hg != H || a.H != 2 * a.lowH || a.W != 2 * a.lowW)   // F.pad rows / columns (and a band's edges)
-                    HIP_TRY(hipMemsetAsync(up, 0, (size_t)B * a.H * a.W * ct.cout * 4, s));
-                const long long units = (long long)B * a.lowH * ((a.lowW + 31) / 32) * (ct.cout / 64);
-                hipLaunchKernelGGL((convt2x2_kernel<T, true>), dim3((unsigned)std::min<long long>((units + 3) / 4, 256 * 16)),
-                                   dim3(256), 0, s, c);
+                    HIP_TRY(hipMemsetAsync(up, 0, (size_t)B * a.H * a.W * ct.cout * es, s));
+                const long long units = (long long)B * a.lowH * ((a.lowW + 31) / 32) * (ct.cout / 64);   // 32 pixels per wave
+                const dim3 grid((unsigned)std::min<long long>((units + 3) / 4, 256 * 16));
+                if (x2) {
+                    if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((convt2x2_kernel<T, true>), grid, dim3(256), 0, s, c);
+                } else
+                    hipLaunchKernelGGL((convt2x2_kernel<T>), grid, dim3(256), 0, s, c);
                 HIP_TRY(hipGetLastError());
-                a.C1 = ct.cout;
-            }
-            a.src1 = up;
-        }
-        if (a.C0 + a.C1 != cw.cin) return fail(FIUNET_ERR_INVALID_ARG, "internal: bf16x2 channel plan mismatch");
-        int mode = SRC_DIRECT_X2;
-        if (i == 1 && fuse_stem) {   // the stem's two-piece output exists only as this conv's LDS tiles
-            mode = SRC_STEM_X2;
-            a.f1 = f1; a.f2 = f2; a.u1 = u1; a.u2 = u2;
+                a.src1 = up; a.C1 = ct.cout;
+            } else if (st.form == FORM_CONCAT_UPCAT) {
+                T* scratch = (T*)(ws + p.scratch_off);
+                const size_t n = (size_t)B * a.H * a.W * ((a.C0 + a.C1) * sizeof(T) / 16);
+                hipLaunchKernelGGL((upcat_kernel<T>), dim3(grid_for(n)), dim3(256), 0, s, a, scratch);
+                HIP_TRY(hipGetLastError());
+                a.src0 = scratch; a.C0 = a.C0 + a.C1; a.C1 = 0; a.src1 = nullptr;
+            } else if (st.form == FORM_CONCAT_UP) {   // two full-resolution sources: skip planes, then these
+                const dim3 grid((unsigned)((a.W * 4 + 255) / 256), (unsigned)((a.H + UPS_ROWS - 1) / UPS_ROWS),
+                                (unsigned)(B * (a.C1 / Elem<T>::PL)));
+                if (grid.y > 65535u || grid.z > 65535u) return fail(FIUNET_ERR_INVALID_ARG, "upsample grid too large");
+                if (x2)
+                    hipLaunchKernelGGL(x2_upsample_kernel, grid, dim3(256), 0, s, a, up);
+                else
+                    hipLaunchKernelGGL((upsample_kernel<T>), grid, dim3(256), 0, s, a, (T*)up);
+                HIP_TRY(hipGetLastError());
+                a.src1 = up;
+            } else
+                mode = SRC_CONCAT_UP;
+        } else if (st.form == FORM_STEM) {   // the stem's output exists only as this conv's LDS tiles
+            mode = x2 ? SRC_STEM_X2 : SRC_STEM;
+            a.f1 = f1; a.f2 = f2;
+            a.u1 = u1; a.u2 = u2;
             a.stem_w = ctx->stem_w_split;
-            a.dither = 0.f;
+            a.dither = dither;
         }
-        int epi = EPI_PLAIN;
-        if (kPoolOut[i] >= 0) {
-            epi = EPI_POOL;
-            a.pool_dst = ws + p.pool_off[kPoolOut[i]];
-        }
-        if (i == NCONV - 1) {
-            epi = ctx->cf == 1 ? EPI_HEAD : EPI_HEAD3;
+        if (a.C0 + a.C1 != cw.cin) return fail(FIUNET_ERR_INVALID_ARG, "internal: channel plan mismatch");
+        if (st.epi == EPI_POOL) a.pool_dst = ws + p.pool_off[kPoolOut[i]];
+        if (st.epi == EPI_HEAD || st.epi == EPI_HEAD3) {
             a.head_w = ctx->head_w; a.head_b = ctx->head_b; a.head_out = out; a.head_out_u8 = out_u8; a.head_nc = ctx->cf;
             a.head_img_stride = out_img_stride ? out_img_stride : (size_t)ctx->cf * H * W;
-            if (!keep_all) a.dst = nullptr;
         }
         g_name_out = ev ? &ctx->layer_name[i] : nullptr;
-        const int rc = launch_conv<T>(a, mode, epi, s);
+        const int rc = launch_conv<T>(a, mode, st.epi, st.cfg, s);
         g_name_out = nullptr;
         if (rc != FIUNET_OK) return rc;
         if (ev) {
-            ctx->layer_flops[i] = 2.0 * B * a.H * a.W * 9.0 * cw.cin * cw.cout;   // algorithmic (the kernel executes 3x)
-            if (i == 1 && fuse_stem) ctx->layer_flops[i] += 2.0 * B * H * W * 9.0 * ctx->conv[0].cin * ctx->conv[0].cout;
-            HIP_TRY(hipEventRecord(ev[i + 1], s));
+            ctx->layer_flops[i] = 2.0 * B * a.H * a.W * 9.0 * cw.cin * cw.cout;   // algorithmic (bf16x2 executes 3x)
+            if (st.form == FORM_STEM && L[0].form == STEM_FUSED) ctx->layer_flops[i] += stem_flops;   // the fused stage does the stem's too
+            if (i < NCONV - 1) HIP_TRY(hipEventRecord(ev[i + 1], s));
         }
     }
+    if (L[NCONV - 1].epi == EPI_PLAIN) {   // the ablation path's OutConv
+        const size_t n = (size_t)B * H * W;
+        hipLaunchKernelGGL((head1x1_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                           (const T*)act(NCONV - 1), ctx->head_w, ctx->head_b, out, B, H, W, ctx->cf);
+        HIP_TRY(hipGetLastError());
+    }
+    if (ev) HIP_TRY(hipEventRecord(ev[NCONV], s));
     return FIUNET_OK;
+}
+
+NetDesc net_of(const fiunet_ctx* c)
+{
+    return NetDesc{c->cf, c->bilinear, c->cout, c->flags, c->stem_w_split != nullptr, c->force_tile, c->force_ksplit};
 }
 
 }  // namespace
@@ -1101,10 +978,7 @@ int fiunet_load_weights(fiunet_ctx* ctx, int n, const char* const* names,
         const std::string bn = pre + (second ? "4" : "1");
         const int* kCout = ctx->cout;
         const int cout = kCout[i];
-        int cin;
-        if (i == 0) cin = cin0;
-        else if (kMode[i] == SRC_CONCAT_UP) cin = kCout[kSrc0[i]] + (ctx->bilinear ? kCout[kSrc1[i]] : kCout[kSrc1[i]] / 2);
-        else cin = kCout[kSrc0[i]];
+        const int cin = i == 0 ? cin0 : conv_cin(kCout, ctx->bilinear, i);
         const float *w, *g, *be, *mu, *var;
         int rc;
         if ((rc = get(wk, (int64_t)cout * cin * 9, &w))) return rc;
@@ -1274,42 +1148,29 @@ int fiunet_min_unsplit_batch(const fiunet_ctx* ctx, int H, int W, int precision)
         g_err = "fiunet_min_unsplit_batch: bad arguments";
         return 0;
     }
-    if (!ctx->loaded) {   // the rule walks the loaded architecture's channel counts
+    if (!ctx->loaded) {   // the plan depends on the loaded weights (the fused-stem copy)
         g_err = "fiunet_min_unsplit_batch before fiunet_load_weights";
         return 0;
     }
-    int hs[5] = {H}, ws[5] = {W};
-    for (int k = 1; k < 5; ++k) { hs[k] = hs[k - 1] / 2; ws[k] = ws[k - 1] / 2; }
-    const PlanOpts po = plan_opts(ctx, H, W, precision);
+    // the stage plan the forwards launch: no stage cuts its K loop (the stem stages and conv 17 never do)
+    StageLaunch L[NCONV];
     for (int B = 1; B <= 64; ++B) {
-        bool split = false;
-        // conv 0 = stem kernel; conv 17 is never cut (its fused-head form cannot be, and the forwards give it no slab on
-        // the ablation / read-back paths either, so that both accumulate in the same order)
-        for (int i = 1; i < NCONV - 1 && !split; ++i) {
-            if (i == 1 && po.fused_stem) continue;            // SRC_STEM launches are never cut
-            const bool direct = kMode[i] != SRC_CONCAT_UP || po.unfused ||
-                                materialise_up(i, precision, po.unfused || po.gather_up, B, hs[kLevel[i]], ws[kLevel[i]], ctx->cout, po.convt);
-            // fp32 concat convs: the direct form (and its in-workgroup cut) only where fp32_concat_takes_kwave says so and the
-            // options let the upsampled half be a tensor; else the fused gather's configuration, on the ablation path too
-            const bool concat = kMode[i] == SRC_CONCAT_UP;
-            const bool fp32_as_direct = concat && precision == FIUNET_FP32 && direct &&
-                                        fp32_concat_takes_kwave(B, hs[kLevel[i]], ws[kLevel[i]], ctx->conv[i].cin, ctx->cout[i]);
-            const ConvCfg c = choose_conv_cfg(precision == FIUNET_FP32, precision == FIUNET_BF16X2, B, hs[kLevel[i]], ws[kLevel[i]],
-                                              ctx->conv[i].cin, ctx->cout[i], true, ctx->force_tile[i] - 1, ctx->force_ksplit[i],
-                                              precision == FIUNET_FP32 && concat ? fp32_as_direct : direct, false,
-                                              concat && !fp32_as_direct);
-            split = c.ksplit > 1 || c.kwave;
-        }
-        if (!split) return B;
+        plan_stages(net_of(ctx), precision, B, H, W, L);
+        if (std::none_of(L + 1, L + NCONV, [](const StageLaunch& st) { return st.cfg.ksplit > 1 || st.cfg.kwave; })) return B;
     }
     return 65;
+}
+
+static bool ctx_plan(const fiunet_ctx* ctx, int B, int H, int W, int precision, Plan& p)
+{
+    return ctx && (precision == FIUNET_FP32 || precision == FIUNET_BF16 || precision == FIUNET_BF16X2) &&
+           make_plan(net_of(ctx), B, H, W, precision, p);
 }
 
 size_t fiunet_workspace_bytes(const fiunet_ctx* ctx, int B, int H, int W, int precision)
 {
     Plan p;
-    if (!ctx || (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2) ||
-        !make_plan(B, H, W, precision, plan_opts(ctx, H, W, precision), p)) {
+    if (!ctx_plan(ctx, B, H, W, precision, p)) {
         g_err = "fiunet_workspace_bytes: bad arguments";
         return 0;
     }
@@ -1341,39 +1202,37 @@ int fiunet_forward_strip(fiunet_ctx* ctx, const float* frame1, const float* fram
     if (H < 16 || W < 16)
         return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
     Plan p;
-    if (!make_plan(B, H, W, precision, plan_opts(ctx, H, W, precision), p))
+    if (!make_plan(net_of(ctx), B, H, W, precision, p))
         return fail(FIUNET_ERR_BAD_SHAPE, "H*W must be below 2^26 pixels per call: cut taller frames into "
                                           "bands (fiunet_forward_strip)");
     if (workspace_bytes < p.total) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (precision == FIUNET_BF16X2)
-        return forward_x2(ctx, frame1, frame2, out, B, H, W, (char*)workspace, p, s, y_origin, H_image, nullptr);
-    if (precision == FIUNET_BF16)
-        return forward_impl<__bf16>(ctx, frame1, frame2, out, B, H, W, (char*)workspace, p, s, y_origin,
-                                    H_image);
-    return forward_impl<float>(ctx, frame1, frame2, out, B, H, W, (char*)workspace, p, s, y_origin, H_image);
+    auto fwd = precision == FIUNET_FP32 ? forward_impl<float> : forward_impl<__bf16>;
+    return fwd(ctx, precision, frame1, frame2, out, B, H, W, (char*)workspace, p, (hipStream_t)stream, y_origin, H_image,
+               nullptr, nullptr, nullptr, 0);
 }
 
-// fiunet_forward_u8: which of the three fp32 frame buffers (frame1, frame2, output logits) a forward of
-// this shape still needs - none where the stem reads the uint8 frames itself (fused stem: bf16 gray; split stem: bf16 RGB) and the
-// fused head writes uint8 itself (every fused-head forward).
-static void u8_buffers(const fiunet_ctx* ctx, int H, int W, int precision, bool* in_f32, bool* out_f32)
+// fiunet_forward_u8: which of the three fp32 frame buffers (frame1, frame2, output logits) a forward still needs - the
+// frames only where the stem kernel is the exact one that reads fp32 (the fused stem and the RGB split stem read the uint8
+// frames themselves), the logits only where the last activation is a tensor (the ablation path's separate head, the debug
+// read-back): everywhere else the fused head writes uint8 itself.
+static size_t u8_extra_bytes(const fiunet_ctx* ctx, const Plan& p, int B, int H, int W, bool* in_f32, bool* out_f32)
 {
-    const PlanOpts po = plan_opts(ctx, H, W, precision);
-    // the bf16 / bf16x2 RGB stem (stem_rgb_split_kernel) reads the uint8 frames itself too
-    *in_f32 = !(po.fused_stem || ((precision == FIUNET_BF16 || precision == FIUNET_BF16X2) && ctx->cf == 3));
-    *out_f32 = !po.fused_head;
+    *in_f32 = p.st[0].form == STEM_FIRST;
+    *out_f32 = p.st[NCONV - 1].stored;
+    return ((*in_f32 ? 2 : 0) + (*out_f32 ? 1 : 0)) * align256((size_t)B * ctx->cf * H * W * 4);
 }
 
 size_t fiunet_workspace_bytes_u8(const fiunet_ctx* ctx, int B, int H, int W, int precision)
 {
-    const size_t base = fiunet_workspace_bytes(ctx, B, H, W, precision);
-    if (!base) return 0;
+    Plan p;
+    if (!ctx_plan(ctx, B, H, W, precision, p)) {
+        g_err = "fiunet_workspace_bytes: bad arguments";
+        return 0;
+    }
     bool in_f32, out_f32;
-    u8_buffers(ctx, H, W, precision, &in_f32, &out_f32);
-    return base + ((in_f32 ? 2 : 0) + (out_f32 ? 1 : 0)) * align256((size_t)B * ctx->cf * H * W * 4);
+    return p.total + u8_extra_bytes(ctx, p, B, H, W, &in_f32, &out_f32);
 }
 
 int fiunet_forward_u8(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
@@ -1390,16 +1249,17 @@ int fiunet_forward_u8_strided(fiunet_ctx* ctx, const uint8_t* frame1, const uint
     if (!ctx || !frame1 || !frame2 || !out || !workspace)
         return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
     if (!ctx->loaded) return fail(FIUNET_ERR_NOT_LOADED, "fiunet_forward before fiunet_load_weights");
-    const size_t base = fiunet_workspace_bytes(ctx, B, H, W, precision);
-    if (!base) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
+    Plan p;
+    if (!ctx_plan(ctx, B, H, W, precision, p))
+        return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
+    const size_t base = p.total;
     bool in_f32, out_f32;
-    u8_buffers(ctx, H, W, precision, &in_f32, &out_f32);
+    const size_t extra_bytes = u8_extra_bytes(ctx, p, B, H, W, &in_f32, &out_f32);
     const size_t img = (size_t)ctx->cf * H * W;
     if (out_image_stride == 0) out_image_stride = img;
     if (out_image_stride < img) return fail(FIUNET_ERR_INVALID_ARG, "out_image_stride smaller than one image");
     const size_t n = (size_t)B * img, fb = align256(n * 4);
-    if (workspace_bytes < base + ((in_f32 ? 2 : 0) + (out_f32 ? 1 : 0)) * fb)
-        return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if (workspace_bytes < base + extra_bytes) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
     char* ws = (char*)workspace;
     char* extra = ws + base;
@@ -1411,22 +1271,12 @@ int fiunet_forward_u8_strided(fiunet_ctx* ctx, const uint8_t* frame1, const uint
         if ((rc = fiunet_preprocess_u8(frame2, b, n, stream))) return rc;
     }
     if (out_f32) o = (float*)extra;
-    Plan p;
-    if (!make_plan(B, H, W, precision, plan_opts(ctx, H, W, precision), p)) return fail(FIUNET_ERR_BAD_SHAPE, "bad shape");
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    const uint8_t* u1 = in_f32 ? nullptr : frame1;
-    const uint8_t* u2 = in_f32 ? nullptr : frame2;
-    uint8_t* ou = out_f32 ? nullptr : out;
     // the fused head writes the (possibly strided) uint8 destination itself; the fp32 staging buffer is contiguous
-    const size_t hs = out_f32 ? 0 : out_image_stride;
-    if (precision == FIUNET_BF16X2)
-        rc = forward_x2(ctx, a, b, o, B, H, W, ws, p, s, 0, H, ou, u1, u2, hs);
-    else if (precision == FIUNET_BF16)
-        rc = forward_impl<__bf16>(ctx, a, b, o, B, H, W, ws, p, s, 0, H, u1, u2, ou, hs);
-    else
-        rc = forward_impl<float>(ctx, a, b, o, B, H, W, ws, p, s, 0, H, u1, u2, ou, hs);
-    if (rc) return rc;
+    auto fwd = precision == FIUNET_FP32 ? forward_impl<float> : forward_impl<__bf16>;
+    if ((rc = fwd(ctx, precision, a, b, o, B, H, W, ws, p, (hipStream_t)stream, 0, H, in_f32 ? nullptr : frame1,
+                  in_f32 ? nullptr : frame2, out_f32 ? nullptr : out, out_f32 ? 0 : out_image_stride)))
+        return rc;
     if (!out_f32) return FIUNET_OK;
     if (out_image_stride == img) return fiunet_postprocess_u8(o, out, n, stream);
     for (int i = 0; i < B; ++i)   // (ablation / read-back configurations only: one elementwise launch per image)
@@ -1594,24 +1444,53 @@ int fiunet_debug_force_cfg(fiunet_ctx* ctx, int layer, int tile, int ksplit)
     return FIUNET_OK;
 }
 
-// diagnostic (not part of the ABI): what choose_conv_cfg answers for one conv launch - pure host arithmetic, no device
-// call, so the rule (tile family, K cut, the batch-invariance gates) is testable without a GPU (tests/test_cfg_rule.py).
-// out[0] = 1 small tile, out[1] = K slices over workgroups, out[2] = 1 in-workgroup K cut (conv3x3_kwave_kernel),
-// out[3] = would a concat conv of this shape have its upsampled half materialised (stage index in `concat_stage`, 0 = n/a)
+// diagnostic (not part of the ABI): the rule alone - what choose_conv_cfg answers for one conv of the bilinear network
+// whose inputs the caller states (tests/test_cfg_rule.py); fiunet_debug_stage_cfg below answers what a forward launches.
+// Pure host arithmetic, no device call.  out[0] = 1 small tile, out[1] = K slices over workgroups, out[2] = 1 in-workgroup K
+// cut (conv3x3_kwave_kernel), out[3] = would a concat conv of this shape have its upsampled half materialised (stage index
+// in `concat_stage`, 0 = n/a); a concat conv has the direct form exactly there, and `kwave_ok` then stands for that.
 int fiunet_debug_choose_cfg(int precision, int B, int H, int W, int Cin, int Cout, int splittable, int concat_stage,
                             int kwave_ok, int* out /* [4] */)
 {
     if (!out || B < 1 || H < 1 || W < 1 || Cin < 32 || (Cout != 64 && Cout % 128 != 0) ||
         (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2))
         return fail(FIUNET_ERR_INVALID_ARG, "fiunet_debug_choose_cfg: bad arguments");
-    out[3] = concat_stage >= 10 && concat_stage < NCONV && kMode[concat_stage] == SRC_CONCAT_UP
-                 ? materialise_up(concat_stage, precision, false, B, H, W) : 0;
     const bool concat = concat_stage >= 10;
-    const bool tail_rule_ok = kwave_ok != 0;
-    if (concat) kwave_ok = out[3];   // a concat conv has the direct form exactly where its upsampled half is a tensor
+    out[3] = concat && concat_stage < NCONV && kMode[concat_stage] == SRC_CONCAT_UP &&
+             (precision == FIUNET_BF16X2 ||
+              materialise_up(precision, B, H, W, conv_cin(kCoutBil, true, concat_stage), kCoutBil[concat_stage]));
     const ConvCfg c = choose_conv_cfg(precision == FIUNET_FP32, precision == FIUNET_BF16X2, B, H, W, Cin, Cout, splittable != 0,
-                                      -1, 0, kwave_ok != 0, tail_rule_ok, concat && !(precision == FIUNET_FP32 && out[3]));
+                                      -1, 0, concat ? out[3] != 0 : kwave_ok != 0, kwave_ok != 0,
+                                      concat && !(precision == FIUNET_FP32 && out[3]));
     out[0] = c.small; out[1] = c.ksplit; out[2] = c.kwave;
+    return FIUNET_OK;
+}
+
+// diagnostic (not part of the ABI): how stage `stage` (0 = the stem, 1..17 = the convs) of a forward of this architecture,
+// option set, precision and shape launches - plan_stages itself, pure host arithmetic with no device call, so the launch
+// rule (tile family, K cut, the batch-invariance gates) is testable without a GPU (tests/test_cfg_rule.py).  A gray network
+// is taken with its fused-stem weights loaded, and without diagnostic overrides.
+// out[0] = 1 small tile, out[1] = K slices over workgroups, out[2] = 1 in-workgroup K cut (conv3x3_kwave_kernel),
+// out[3] = 1 the upsampled half is a tensor (upsample / ConvTranspose2d), out[4] = source form (SrcForm; stage 0: StemForm),
+// out[5] = epilogue (EPI_*)
+int fiunet_debug_stage_cfg(int frame_channels, int bilinear, unsigned flags, int precision, int B, int H, int W, int stage,
+                           int* out /* [6] */)
+{
+    if (!out || (frame_channels != 1 && frame_channels != 3) || B < 1 || H < 16 || W < 16 || stage < 0 || stage >= NCONV ||
+        (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2))
+        return fail(FIUNET_ERR_INVALID_ARG, "fiunet_debug_stage_cfg: bad arguments");
+    NetDesc n;
+    n.cf = frame_channels;
+    n.bilinear = bilinear != 0;
+    n.cout = n.bilinear ? kCoutBil : kCoutCT;
+    n.flags = flags;
+    n.stem_w = frame_channels == 1;
+    StageLaunch L[NCONV];
+    plan_stages(n, precision, B, H, W, L);
+    const StageLaunch& st = L[stage];
+    out[0] = st.cfg.small; out[1] = st.cfg.ksplit; out[2] = st.cfg.kwave;
+    out[3] = stage > 0 && (st.form == FORM_CONCAT_UP || st.form == FORM_CONCAT_CONVT);
+    out[4] = st.form; out[5] = st.epi;
     return FIUNET_OK;
 }
 
@@ -1691,7 +1570,7 @@ int fiunet_debug_read_activation(fiunet_ctx* ctx, const void* workspace, int B, 
     if (dst && !(ctx->flags & FIUNET_OPT_KEEP_ALL))
         return fail(FIUNET_ERR_INVALID_ARG, "read-back needs FIUNET_OPT_KEEP_ALL set for the forward: without it "
                                             "activations share workspace bytes and are overwritten");
-    if (!make_plan(B, H, W, precision, plan_opts(ctx, H, W, precision), p))
+    if (!make_plan(net_of(ctx), B, H, W, precision, p))
         return fail(FIUNET_ERR_BAD_SHAPE, "bad shape");
     // channels of THIS architecture (the ConvTranspose2d decoder is wider than the bilinear one at taps 8, 9, 11, 13, 15)
     int C, lv;
@@ -1701,11 +1580,10 @@ int fiunet_debug_read_activation(fiunet_ctx* ctx, const void* workspace, int B, 
     } else {   // taps 18..21: `self.up(x1)` + F.pad of up1..up4 (unet.py:47-53) where it is a tensor of its own
         const int i = 10 + 2 * (tap - NCONV);
         lv = kLevel[i];
-        const PlanOpts po = plan_opts(ctx, H, W, precision);
-        if (!materialise_up(i, precision, po.unfused || po.gather_up, B, p.hs[lv], p.ws[lv], ctx->cout, po.convt))
+        if (p.st[i].form != FORM_CONCAT_UP && p.st[i].form != FORM_CONCAT_CONVT)
             return fail(FIUNET_ERR_UNSUPPORTED, "read-back: the upsampled half of this stage is interpolated inside the "
                                                 "conv's gather in this configuration, never stored");
-        C = po.convt ? ctx->cout[kSrc1[i]] / 2 : ctx->cout[kSrc1[i]];
+        C = p.st[i].form == FORM_CONCAT_CONVT ? ctx->cout[kSrc1[i]] / 2 : ctx->cout[kSrc1[i]];
         off = p.up_off[i];
     }
     const int h = p.hs[lv], w = p.ws[lv];

@@ -638,3 +638,36 @@ def test_in_workgroup_k_cut_kernel(model, dev, seeded_sd, prec):
         else:
             assert (out.cpu() - ref).abs().max().item() <= 1e-3, (b, h, w, (out.cpu() - ref).abs().max().item())
     model.precision = "fp32"
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "bf16x2"])
+@pytest.mark.parametrize("bilinear", [True, False])
+def test_min_unsplit_batch_agrees_with_the_launches(model, convt_model, dev, bilinear, prec):
+    """`fiunet_min_unsplit_batch` (the batch the video loop pads a ragged chunk to) is the smallest batch whose forward
+    cuts no K loop: the launches at `bmin` report neither a cut over workgroups nor the in-workgroup cut, one batch less
+    does (both decoders; for bilinear=False fp32 the query once answered from a re-derivation of the launch flags)."""
+    m = model if bilinear else convt_model
+    m.precision = prec
+    m.set_options()
+    code = {"fp32": _native.FP32, "bf16": _native.BF16, "bf16x2": _native.BF16X2}[prec]
+
+    def cut(b, h, w):
+        f1, f2 = O.make_frames(3, b, h, w)
+        f1, f2 = f1.to(dev), f2.to(dev)
+        ctx = m._context(dev)
+        ctx.profile_enable(True)
+        m(f1, f2)
+        torch.cuda.synchronize()
+        _, rows = ctx.profile_read()
+        ctx.profile_enable(False)
+        return [r[0] for r in rows if "+splitk" in r[0] or "kwave" in r[0]]
+
+    try:
+        for h, w in ((135, 240), (64, 96)):
+            bmin = m._context(dev).min_unsplit_batch(h, w, code)
+            assert 1 <= bmin <= 64, (h, w, bmin)
+            assert cut(bmin, h, w) == [], (h, w, bmin)
+            if bmin > 1:
+                assert cut(bmin - 1, h, w), (h, w, bmin)
+    finally:
+        m.precision = "fp32"
