@@ -7,9 +7,11 @@ inputs + expected outputs as small fixtures.  The reference cannot travel to the
 these vectors (data only) do.
 
     python oracle/gen_golden.py            # writes tests/golden/
+    python oracle/gen_golden.py --trained-like   # only the trained-like statistics and their reference outputs
 """
 from __future__ import annotations
 
+import copy
 import os
 import sys
 import time
@@ -233,7 +235,163 @@ def gen_ssim():
                             mse=np.float32(mse.item()))
 
 
+# ---- trained-like checkpoints (tests/golden/bn_trained_like_*.npz and the fixtures of their reference outputs) --------
+TL_CASES = {  # variant -> [(fixture name, frame seed, B, H, W)]; above 64x64 only a strided sample is kept
+    "gray": [("tl_gray_b1_32x48", 61, 1, 32, 48), ("tl_gray_b1_135x240", 62, 1, 135, 240)],
+    "rgb": [("tl_rgb_b2_40x56", 63, 2, 40, 56)],
+    "convt": [("tl_convt_b1_34x52", 64, 1, 34, 52)],
+}
+TL_LAYERS = ("tl_gray_b1_32x48", 61, 1, 32, 48)  # the 18 per-layer taps of the gray variant
+
+
+def calibrate_trained_like(variant):
+    """Per-channel statistics that look like a trained network's, calibrated on a fixed frame pair in float64.
+    Per conv: every output filter scaled by 10**U(-3, 1.5); running_mean / running_var start from that conv's pre-BN
+    output on the calibration pair (the upstream layers already carry their final statistics), the mean then offset by
+    U(-3, 3) std (channels that are almost always off or on) and the variance multiplied by 10**U(-2, 2); gamma ~15 %
+    negative, ~5 % exactly 0, ~10 % tiny (+-1e-4), ~10 % large (3-5), the rest O(1); beta ~ N(0, 0.5); two channels
+    per layer get a raw running_var of 1e-6 and |gamma| 3-4 (scale ~1e3), one is saturated (always on, gain ~100).  ConvTranspose2d output channels scaled by
+    10**U(-2, 1) with biases of 10**U(-1, 1) magnitude; the head's input channels scaled by 10**U(-2, 0.5)."""
+    seed, nc, ncl, bil, fname = O.TRAINED_LIKE[variant]
+    rng = np.random.default_rng(seed)
+    stats = {"seed": np.int64(seed)}
+    shapes = {k: s for k, s, _ in O.state_dict_schema(nc, ncl, bil)}
+    for prefix, _, _, _ in O.double_conv_table(nc, bil):
+        for conv_i in (0, 3):
+            cout = shapes[f"{prefix}.double_conv.{conv_i}.weight"][0]
+            stats[f"{prefix}.double_conv.{conv_i}|filter_scale"] = 10.0 ** rng.uniform(-3, 1.5, cout)
+    if not bil:
+        for k in range(1, 5):
+            cout = shapes[f"unet.up{k}.up.bias"][0]
+            stats[f"unet.up{k}.up|scale"] = 10.0 ** rng.uniform(-2, 1, cout)
+            stats[f"unet.up{k}.up|bias"] = rng.standard_normal(cout) * 10.0 ** rng.uniform(-1, 1, cout)
+    stats["unet.outc|scale"] = 10.0 ** rng.uniform(-2, 0.5, 64)
+    stats["unet.outc|bias"] = rng.standard_normal(ncl) * 0.5
+    sd = O.state_dict_to(O.make_trained_like_state_dict(nc, ncl, bil, seed=seed, stats=stats), torch.float64)
+
+    def pre_bn(bn, z):
+        c = z.shape[1]
+        zz = z.transpose(0, 1).reshape(c, -1)
+        mu, std = zz.mean(1).numpy(), zz.std(1).numpy()
+        mean = mu + rng.uniform(-3, 3, c) * std
+        var = std ** 2 * 10.0 ** rng.uniform(-2, 2, c)
+        u = rng.random(c)
+        sign = np.where(rng.random(c) < 0.5, -1.0, 1.0)
+        gamma = rng.uniform(0.3, 1.5, c)                                                   # O(1)
+        gamma = np.where(u < 0.15, -rng.uniform(0.3, 1.5, c), gamma)                       # negative
+        gamma = np.where((u >= 0.15) & (u < 0.20), 0.0, gamma)                             # exactly zero
+        gamma = np.where((u >= 0.20) & (u < 0.30), sign * 1e-4 * rng.uniform(0.5, 1.5, c), gamma)  # tiny
+        gamma = np.where((u >= 0.30) & (u < 0.40), sign * rng.uniform(3, 5, c), gamma)    # large
+        # hot channels: a filter whose output barely varies (std 1e-3) behind a running_var of 1e-6 - the folded scale
+        # is ~1e3 and the folded weights are ordinary, as in a trained network; z is rescaled in place (the conv is
+        # linear and has no bias), so the layers downstream see the rescaled filter
+        hot = rng.choice(np.flatnonzero((gamma != 0) & (std > 0)), 2, replace=False)
+        fac = 1e-3 / std[hot]
+        conv = bn[:-1] + ("0" if bn.endswith("1") else "3")
+        stats[f"{conv}|filter_scale"][hot] *= fac
+        z[:, hot] *= torch.from_numpy(fac).view(1, -1, 1, 1)
+        mean[hot] = mu[hot] * fac + rng.uniform(-3, 3, 2) * 1e-3
+        var[hot] = 1e-6
+        gamma[hot] = sign[hot] * rng.uniform(3, 4, 2)
+        # one saturated channel: almost always on, large gain (|activation| in the hundreds)
+        sat = rng.choice(np.setdiff1d(np.flatnonzero(std > 0), hot), 1)
+        gamma[sat], mean[sat], var[sat] = rng.uniform(3, 5), mu[sat] - 3 * std[sat], std[sat] ** 2 * 1e-3
+        beta = rng.standard_normal(c) * 0.5
+        for field, key, v in (("gamma", "weight", gamma), ("beta", "bias", beta), ("mean", "running_mean", mean),
+                              ("var", "running_var", var)):
+            v32 = v.astype(np.float32)
+            stats[f"{bn}|{field}"] = v32
+            sd[f"{bn}.{key}"] = torch.from_numpy(v32.astype(np.float64))   # downstream layers see the final values
+
+    f1, f2 = O.make_frames(seed, 1, 64, 96, c=ncl)
+    O.unet_forward(sd, f1.double(), f2.double(), pre_bn=pre_bn)
+    out = {k: (np.asarray(v, dtype=np.float32) if k != "seed" else v) for k, v in stats.items()}
+    np.savez_compressed(os.path.join(GOLD, fname), **out)
+    return out
+
+
+def _hook_taps(model, names_ok=lambda n: True):
+    acts, handles = {}, []
+
+    def hook(name):
+        def fn(_m, _inp, outp):
+            acts[name] = outp.detach().clone()
+        return fn
+    for mod_name, mod in model.named_modules():   # the ReLUs behind the convs are inplace: hook them (see main())
+        if mod_name.endswith("double_conv.2") or mod_name.endswith("double_conv.5"):
+            conv_idx = "0" if mod_name.endswith(".2") else "3"
+            handles.append(mod.register_forward_hook(hook(mod_name.rsplit(".", 1)[0] + "." + conv_idx)))
+        if mod_name == "unet.outc":
+            handles.append(mod.register_forward_hook(hook("unet.outc")))
+    return acts, handles
+
+
+def gen_trained_like():
+    """Trained-like checkpoints in the reference's own classes (strict load_state_dict, .eval()): whole-network outputs
+    in float32 and, from model.double(), in float64; the 18 per-layer taps + head of the gray variant at 32x48."""
+    sys.path.insert(0, REF_DIR)
+    from unet import FrameInterpolationUNet, UNet
+    torch.manual_seed(0)
+    torch.set_num_threads(8)
+    for variant in ("gray", "rgb", "convt"):
+        calibrate_trained_like(variant)
+        seed, nc, ncl, bil, _ = O.TRAINED_LIKE[variant]
+        sd = O.make_trained_like_state_dict(nc, ncl, bil)
+        if variant == "rgb":   # the reference's parametric UNet(6, 3) on cat([frame1, frame2]) (see gen_rgb)
+            model = UNet(n_channels=6, n_classes=3, bilinear=True)
+            print(variant, model.load_state_dict({k[len("unet."):]: v for k, v in sd.items()}, strict=True))
+            run = lambda m, a, b: m(torch.cat([a, b], dim=1))  # noqa: E731
+        else:
+            model = FrameInterpolationUNet(bilinear=bil) if bil else FrameInterpolationUNet()
+            assert model.unet.bilinear is bil
+            print(variant, model.load_state_dict(sd, strict=True))
+            run = lambda m, a, b: m(a, b)  # noqa: E731
+        model.eval()
+        model64 = copy.deepcopy(model).double()
+        for name, fseed, b, h, w in TL_CASES[variant]:
+            f1, f2 = O.make_frames(fseed, b, h, w, c=ncl)
+            with torch.no_grad():
+                out32 = run(model, f1, f2)
+                out64 = run(model64, f1.double(), f2.double())
+            rel = float((out32.double() - out64).norm() / out64.norm())
+            print(f"{name}: out std {out64.std():.4g} max|out| {out64.abs().max():.4g} fp32 rel-L2 vs float64 {rel:.3e}")
+            fix = dict(seed=fseed, frame1=f1.numpy(), frame2=f2.numpy())
+            if h * w > 64 * 64:
+                idx, _ = strided_sample(out32, 4096)
+                fix.update(idx=idx, val32=out32.reshape(-1)[idx].numpy(), val64=out64.reshape(-1)[idx].numpy(),
+                           sum64=np.float64(out64.sum().item()), abssum64=np.float64(out64.abs().sum().item()),
+                           sqsum64=np.float64(out64.pow(2).sum().item()),
+                           err32_sq=np.float64((out32.double() - out64).pow(2).sum().item()),
+                           err32_max=np.float64((out32.double() - out64).abs().max().item()))
+                del fix["frame1"], fix["frame2"]   # rebuilt from the seed (O.make_frames)
+            else:
+                fix.update(out32=out32.numpy(), out64=out64.numpy())
+            np.savez_compressed(os.path.join(GOLD, f"out_{name}.npz"), **fix)
+        if variant == "gray":   # the 18 per-layer taps (as layers_b1_32x48.npz) in float32 and float64
+            name, fseed, b, h, w = TL_LAYERS
+            f1, f2 = O.make_frames(fseed, b, h, w)
+            fix = {}
+            for tag, m, a, c in (("32", model, f1, f2), ("64", model64, f1.double(), f2.double())):
+                acts, handles = _hook_taps(m)
+                with torch.no_grad():
+                    run(m, a, c)
+                for hd in handles:
+                    hd.remove()
+                assert len(acts) == 19, sorted(acts)
+                for k, v in acts.items():
+                    idx, _ = strided_sample(v, 1024)
+                    fix[f"{k}|idx"] = idx
+                    fix[f"{k}|val{tag}"] = v.reshape(-1)[idx].numpy()
+                    fix[f"{k}|shape"] = np.array(v.shape, dtype=np.int64)
+                    fix[f"{k}|sum{tag}"] = np.float64(v.double().sum().item())
+                    fix[f"{k}|abssum{tag}"] = np.float64(v.double().abs().sum().item())
+            np.savez_compressed(os.path.join(GOLD, f"layers_{name}.npz"), frame1=f1.numpy(), frame2=f2.numpy(), **fix)
+
+
 def main():
+    if "--trained-like" in sys.argv:
+        os.makedirs(GOLD, exist_ok=True)
+        return gen_trained_like()
     if "--ssim-only" in sys.argv:
         os.makedirs(GOLD, exist_ok=True)
         return gen_ssim()

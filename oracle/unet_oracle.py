@@ -24,6 +24,7 @@ data_range=255, restated as 10*log10(255^2/MSE) in float64).
 from __future__ import annotations
 
 import math
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -171,6 +172,64 @@ def make_interpolating_state_dict(seed: int = 4321, n_channels: int = 2, n_class
     return sd
 
 
+# Trained-like checkpoints: the seeded conv weights plus per-channel statistics that look like a trained network's
+# (negative, zero, tiny and large gammas; running variances over decades; dead and saturated channels).  The statistics
+# were calibrated once in float64 (oracle/gen_golden.py --trained-like) and are committed as data, so every machine builds
+# the same tensors: variant -> (seed, n_channels, n_classes, bilinear, fixture file in tests/golden/).
+TRAINED_LIKE = {
+    "gray": (2025, 2, 1, True, "bn_trained_like_gray.npz"),
+    "rgb": (2026, 6, 3, True, "bn_trained_like_rgb.npz"),
+    "convt": (2027, 2, 1, False, "bn_trained_like_convt.npz"),
+}
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+
+
+def trained_like_variant(n_channels: int = 2, n_classes: int = 1, bilinear: bool = True) -> str:
+    for name, (_, nc, ncl, bil, _) in TRAINED_LIKE.items():
+        if (nc, ncl, bil) == (n_channels, n_classes, bilinear):
+            return name
+    raise ValueError(f"no trained-like statistics for n_channels={n_channels}, n_classes={n_classes}, bilinear={bilinear}")
+
+
+def make_trained_like_state_dict(n_channels: int = 2, n_classes: int = 1, bilinear: bool = True, seed=None,
+                                 stats=None):
+    """make_seeded_state_dict(seed) with the per-filter factors and BatchNorm statistics of
+    tests/golden/bn_trained_like_{gray,rgb,convt}.npz: conv filter o scaled by `{conv}|filter_scale`[o]; gamma, beta,
+    running_mean, running_var replaced; ConvTranspose2d output channel o scaled by `{up}|scale`[o] and its bias
+    replaced; the head's input channel c scaled by `unet.outc|scale`[c] and its bias replaced.  `stats`: a dict of those
+    arrays instead of the committed file (oracle/gen_golden.py, while it calibrates them)."""
+    variant = trained_like_variant(n_channels, n_classes, bilinear)
+    seed = TRAINED_LIKE[variant][0] if seed is None else seed
+    if stats is None:
+        stats = dict(np.load(os.path.join(GOLDEN_DIR, TRAINED_LIKE[variant][4])))
+        assert int(stats["seed"]) == seed, (int(stats["seed"]), seed)
+    sd = make_seeded_state_dict(seed, n_channels, n_classes, bilinear)
+    t = lambda k: torch.from_numpy(np.ascontiguousarray(stats[k], dtype=np.float32))  # noqa: E731
+    for prefix, _, _, _ in double_conv_table(n_channels, bilinear):
+        for conv_i, bn_i in ((0, 1), (3, 4)):
+            conv, bn = f"{prefix}.double_conv.{conv_i}", f"{prefix}.double_conv.{bn_i}"
+            if f"{conv}|filter_scale" not in stats:
+                continue   # (while calibrating: not reached yet)
+            sd[f"{conv}.weight"] = sd[f"{conv}.weight"] * t(f"{conv}|filter_scale").view(-1, 1, 1, 1)
+            for field, key in (("gamma", "weight"), ("beta", "bias"), ("mean", "running_mean"), ("var", "running_var")):
+                if f"{bn}|{field}" in stats:
+                    sd[f"{bn}.{key}"] = t(f"{bn}|{field}").clone()
+    for k in range(1, 5):
+        up = f"unet.up{k}.up"
+        if f"{up}|scale" in stats:
+            sd[f"{up}.weight"] = sd[f"{up}.weight"] * t(f"{up}|scale").view(1, -1, 1, 1)
+            sd[f"{up}.bias"] = t(f"{up}|bias").clone()
+    if "unet.outc|scale" in stats:
+        sd["unet.outc.conv.weight"] = sd["unet.outc.conv.weight"] * t("unet.outc|scale").view(1, -1, 1, 1)
+        sd["unet.outc.conv.bias"] = t("unet.outc|bias").clone()
+    return sd
+
+
+def state_dict_to(sd, dtype):
+    """The floating-point tensors of a state dict in `dtype` (float64 for the high-precision references)."""
+    return OrderedDict((k, v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items())
+
+
 def make_frames(seed: int, b: int, h: int, w: int, c: int = 1):
     """Uniform [-1,1] synthetic frame pair, seeded (SURVEY 8d 'Config 1/2')."""
     g = torch.Generator().manual_seed(seed)
@@ -179,8 +238,10 @@ def make_frames(seed: int, b: int, h: int, w: int, c: int = 1):
     return f1, f2
 
 
-def _conv_bn_relu(x, sd, prefix, conv_i, bn_i):
+def _conv_bn_relu(x, sd, prefix, conv_i, bn_i, pre_bn=None):
     x = F.conv2d(x, sd[f"{prefix}.double_conv.{conv_i}.weight"], bias=None, padding=1)
+    if pre_bn is not None:  # calibration hook: sees the conv output before BatchNorm (may set the statistics)
+        pre_bn(f"{prefix}.double_conv.{bn_i}", x)
     x = F.batch_norm(
         x,
         sd[f"{prefix}.double_conv.{bn_i}.running_mean"],
@@ -193,11 +254,11 @@ def _conv_bn_relu(x, sd, prefix, conv_i, bn_i):
     return F.relu(x)
 
 
-def _double_conv(x, sd, prefix, taps):
-    x = _conv_bn_relu(x, sd, prefix, 0, 1)
+def _double_conv(x, sd, prefix, taps, pre_bn=None):
+    x = _conv_bn_relu(x, sd, prefix, 0, 1, pre_bn)
     if taps is not None:
         taps[f"{prefix}.double_conv.0"] = x
-    x = _conv_bn_relu(x, sd, prefix, 3, 4)
+    x = _conv_bn_relu(x, sd, prefix, 3, 4, pre_bn)
     if taps is not None:
         taps[f"{prefix}.double_conv.3"] = x
     return x
@@ -220,24 +281,25 @@ def upsample_pad_concat(x_low, x_skip, up_weight=None, up_bias=None, taps=None, 
 
 
 @torch.no_grad()
-def unet_forward(sd, frame1, frame2, taps=None):
-    """FrameInterpolationUNet.forward in eval mode (unet.py:105-112 -> unet.py:84-95)."""
+def unet_forward(sd, frame1, frame2, taps=None, pre_bn=None):
+    """FrameInterpolationUNet.forward in eval mode (unet.py:105-112 -> unet.py:84-95).  Runs in the dtype of its
+    inputs (float64 with a float64 state dict).  pre_bn(name, z): called with every conv's output before its BatchNorm."""
     x = torch.cat([frame1, frame2], dim=1)
-    x1 = _double_conv(x, sd, "unet.inc", taps)
+    x1 = _double_conv(x, sd, "unet.inc", taps, pre_bn)
     skips = [x1]
     cur = x1
     for k in (1, 2, 3, 4):
         cur = F.max_pool2d(cur, 2)
         if taps is not None:
             taps[f"unet.down{k}.pool"] = cur
-        cur = _double_conv(cur, sd, f"unet.down{k}.maxpool_conv.1", taps)
+        cur = _double_conv(cur, sd, f"unet.down{k}.maxpool_conv.1", taps, pre_bn)
         skips.append(cur)
     for k, skip in zip((1, 2, 3, 4), (skips[3], skips[2], skips[1], skips[0])):
         cat = upsample_pad_concat(cur, skip, sd.get(f"unet.up{k}.up.weight"), sd.get(f"unet.up{k}.up.bias"), taps,
                                   f"unet.up{k}.up")
         if taps is not None:
             taps[f"unet.up{k}.cat"] = cat
-        cur = _double_conv(cat, sd, f"unet.up{k}.conv", taps)
+        cur = _double_conv(cat, sd, f"unet.up{k}.conv", taps, pre_bn)
     out = F.conv2d(cur, sd["unet.outc.conv.weight"], sd["unet.outc.conv.bias"])
     if taps is not None:
         taps["unet.outc"] = out

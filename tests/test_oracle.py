@@ -149,3 +149,130 @@ def test_convtranspose_variant_oracle_equals_reference_default_constructor(golde
     out = O.unet_forward(sd, torch.from_numpy(g["frame1"]), torch.from_numpy(g["frame2"])).numpy()
     assert out.shape == g["out"].shape
     assert np.abs(out - g["out"]).max() <= 2e-5 * max(1.0, np.abs(g["out"]).max())
+
+
+# ---- trained-like checkpoints (oracle.make_trained_like_state_dict; oracle/gen_golden.py --trained-like) ---------------
+TL = [("gray", "tl_gray_b1_32x48"), ("gray", "tl_gray_b1_135x240"), ("rgb", "tl_rgb_b2_40x56"),
+      ("convt", "tl_convt_b1_34x52")]
+
+
+def _tl_sd(variant, dtype=torch.float32):
+    _, nc, ncl, bil, _ = O.TRAINED_LIKE[variant]
+    return O.state_dict_to(O.make_trained_like_state_dict(nc, ncl, bil), dtype), ncl
+
+
+def _tl_frames(g, name, ncl):
+    if "frame1" in g.files:
+        return torch.from_numpy(g["frame1"]), torch.from_numpy(g["frame2"])
+    import re
+    b, h, w = (int(x) for x in re.search(r"_b(\d+)_(\d+)x(\d+)$", name).groups())
+    return O.make_frames(int(g["seed"]), b, h, w, c=ncl)
+
+
+@pytest.mark.parametrize("variant,name", TL)
+def test_oracle_reproduces_trained_like_reference_outputs(golden_dir, variant, name):
+    """The restatement equals the reference's own class on the trained-like checkpoints (BatchNorm eps included):
+    in fp32 within 2^-16 of the head's summed |terms| M, in float64 to 1e-12 of M."""
+    from oracle import stage_oracle as S
+    g = np.load(os.path.join(golden_dir, f"out_{name}.npz"))
+    for dtype, key, tol in ((torch.float32, "32", 2.0 ** -16), (torch.float64, "64", 1e-12)):
+        sd, ncl = _tl_sd(variant, dtype)
+        f1, f2 = _tl_frames(g, name, ncl)
+        taps = {}
+        out = O.unet_forward(sd, f1.to(dtype), f2.to(dtype), taps)
+        m = S.stage_reference(sd, S.HEAD, taps)[1]
+        if "idx" in g.files:
+            idx = torch.from_numpy(g["idx"])
+            got, want, m = out.reshape(-1)[idx].double().numpy(), g[f"val{key}"], m.reshape(-1)[idx].numpy()
+        else:
+            got, want, m = out.double().numpy(), g[f"out{key}"], m.numpy()
+        assert (np.abs(got - want) <= tol * m).all(), (key, (np.abs(got - want) / m).max())
+
+
+def test_oracle_reproduces_trained_like_per_layer_taps(golden_dir):
+    """The 18 per-layer taps and the head of the gray trained-like checkpoint at 32x48, fp32 and float64."""
+    from oracle import stage_oracle as S
+    g = np.load(os.path.join(golden_dir, "layers_tl_gray_b1_32x48.npz"))
+    names = sorted({k.split("|")[0] for k in g.files if "|" in k})
+    assert len(names) == 19
+    for dtype, key, tol in ((torch.float32, "32", 2.0 ** -16), (torch.float64, "64", 1e-12)):
+        sd, _ = _tl_sd("gray", dtype)
+        taps = {"frame1": torch.from_numpy(g["frame1"]).to(dtype), "frame2": torch.from_numpy(g["frame2"]).to(dtype)}
+        out = O.unet_forward(sd, taps["frame1"], taps["frame2"], taps)
+        taps[S.HEAD] = out
+        for n in names:
+            stage = S.HEAD if n == S.HEAD else S.TAP.index(n)
+            m = S.stage_reference(sd, stage, taps)[1].reshape(-1)
+            idx = torch.from_numpy(g[f"{n}|idx"])
+            t = taps[n]
+            assert tuple(t.shape) == tuple(g[f"{n}|shape"])
+            err = np.abs(t.reshape(-1)[idx].double().numpy() - g[f"{n}|val{key}"])
+            assert (err <= tol * m[idx].numpy()).all(), (n, key, (err / m[idx].numpy()).max())
+
+
+@pytest.mark.parametrize("variant", ["gray", "rgb", "convt"])
+def test_trained_like_statistics_are_adversarial(variant):
+    """Negative and zero gammas, running variances over 1e-6 .. 1e1 at least, folded scales over six decades with both
+    signs - in every variant."""
+    sd, _ = _tl_sd(variant)
+    g = torch.cat([v for k, v in sd.items() if k.endswith(".weight") and v.dim() == 1])
+    var = torch.cat([v for k, v in sd.items() if k.endswith("running_var")])
+    sc = g.double() / torch.sqrt(var.double() + O.BN_EPS)
+    assert (g < 0).any() and (g == 0).any()
+    assert var.min() <= 1e-6 and var.max() >= 1e1
+    nz = sc[sc != 0].abs()
+    assert nz.max() / nz.min() >= 1e6 and (sc < 0).any() and (sc > 0).any()
+
+
+@pytest.mark.parametrize("variant", ["gray", "rgb", "convt"])
+def test_trained_like_network_is_alive(variant):
+    """Not vacuous: every layer has >= 10 % of its elements > 0 and >= 10 % of its channels nonzero somewhere, and a
+    channel with |activation| > 100; the output is not constant (std >= 5 % of max |out|)."""
+    from oracle import stage_oracle as S
+    sd, ncl = _tl_sd(variant, torch.float64)
+    f1, f2 = O.make_frames(O.TRAINED_LIKE[variant][0], 1, 64, 96, c=ncl)   # the calibration pair
+    taps = {}
+    out = O.unet_forward(sd, f1.double(), f2.double(), taps)
+    for n in S.TAP:
+        t = taps[n]
+        assert (t > 0).double().mean() >= 0.1, n
+        assert (t.amax(dim=(0, 2, 3)) > 0).double().mean() >= 0.1, n
+        assert t.abs().max() > 100, (n, t.abs().max().item())
+    assert out.std() >= 0.05 * out.abs().max()
+
+
+def test_trained_like_fixture_is_what_the_builder_uses():
+    """The committed statistics rebuild the same state dict everywhere: the builder reads the fixture (seed checked)."""
+    for variant, (seed, nc, ncl, bil, fname) in O.TRAINED_LIKE.items():
+        st = np.load(os.path.join(O.GOLDEN_DIR, fname))
+        assert int(st["seed"]) == seed
+        sd = O.make_trained_like_state_dict(nc, ncl, bil)
+        assert [k for k in sd] == [k for k, _, _ in O.state_dict_schema(nc, ncl, bil)]
+        bn = "unet.inc.double_conv.1"
+        assert np.array_equal(sd[f"{bn}.running_var"].numpy(), st[f"{bn}|var"])
+
+
+def test_bf16_feedback_restatement_matches_definition():
+    """oracle.stage_oracle.bf16_feedback against a scalar restatement of f32_to_bf16_feedback (csrc/fiunet.hip)."""
+    import struct
+    from oracle import stage_oracle as S
+    rng = np.random.default_rng(3)
+    w = (rng.standard_normal((5, 300)) * 10.0 ** rng.uniform(-4, 3, (5, 300))).astype(np.float32)
+    w[0, :4] = [0.0, 1.0, -2.5, 3.0]
+    got = S.bf16_feedback(w)
+    for r in range(w.shape[0]):
+        carry = 0.0
+        for k in range(w.shape[1]):
+            v = float(w[r, k])
+            u = struct.unpack("<I", struct.pack("<f", w[r, k]))[0]
+            f0 = struct.unpack("<f", struct.pack("<I", u & 0xFFFF0000))[0]
+            f1 = struct.unpack("<f", struct.pack("<I", (u & 0xFFFF0000) + 0x10000))[0]
+            if f0 == v:
+                want = f0
+            else:
+                e0, e1 = v - f0, v - f1
+                pick0 = abs(carry + e0) <= abs(carry + e1)
+                carry += e0 if pick0 else e1
+                want = f0 if pick0 else f1
+            assert got[r, k] == np.float32(want), (r, k)
+    assert np.array_equal(S.bf16_rne(np.float32([1.00390625, 1.01171875, -3.0])), np.float32([1.0, 1.015625, -3.0]))
