@@ -24,7 +24,7 @@ CSRC = os.path.join(_PKG, "csrc")
 ABI_VERSION = 5        # include/fiunet.h FIUNET_ABI_VERSION this binding is written for
 ABI_MIN_COMPAT = 4     # oldest A/B library (FIUNET_LIB) whose shared entry points have today's signatures
 FP32, BF16, BF16X2 = 0, 1, 2   # include/fiunet.h: enum fiunet_precision
-OPT_UNFUSED, OPT_KEEP_ALL, OPT_PAIR_TILES, OPT_GATHER_UPSAMPLE = 1, 2, 8, 16
+OPT_UNFUSED, OPT_KEEP_ALL, OPT_GATHER_UPSAMPLE = 1, 2, 16
 OPT_RNE_WEIGHTS, OPT_NO_DITHER = 32, 64
 
 #: every symbol include/fiunet.h declares (tests/test_abi.py checks the header against this)

@@ -65,19 +65,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_kwave_kernel(const ConvArgs a)
     const unsigned lds_in_addr = lds_addr_of(lds_in);
     const unsigned lds_w_addr = lds_addr_of(lds_w);
 
-    // XCD-aware, bijective block remap (as conv3x3_mfma_kernel)
-    int lid;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    const int ct = lid % a.nct;
-    int t = lid / a.nct;
-    const int tx = t % a.tilesX; t /= a.tilesX;
-    const int ty = t % a.tilesY;
-    const int b = t / a.tilesY;
-    const int y0 = ty * TH, x0 = tx * TW;
+    const ConvTileId id = conv_tile_decode(a, conv_block_remap());
+    const int ct = id.ct, b = id.b;
+    const int y0 = id.ty * TH, x0 = id.tx * TW;
     const int aH = a.H, aW = a.W;
 
     // this wave's quarter of the K loop (planes); the BatchNorm shift starts wave 0's accumulators, zero the others'

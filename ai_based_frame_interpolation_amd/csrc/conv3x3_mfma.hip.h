@@ -94,8 +94,6 @@ struct ConvArgs {
     int lowHg;           //   rows of the WHOLE image's low-res tensor (padT, sy are global too)
     int tilesX, tilesY, nct;
     int relu;
-    const void* zero_page; // >= 64 zero bytes: padding source of the tile-pair kernel's gather (this kernel zeroes
-                           // the padding slots of its in-tile once and masks those lanes out of the DMAs)
     // SRC_STEM (bf16, gray): the 2->64 stem conv + BN + ReLU (unet.py:72) is evaluated inside the
     // in-tile gather of the NEXT conv, so its 64-channel output never goes to HBM.
     const float* f1;          // frame1 [B][1][H][W] fp32
@@ -108,7 +106,6 @@ struct ConvArgs {
     // raw fp32 partial sums to kslab[s][tile][wave][fragment][lane]; splitk_finalize_tile_kernel adds the slices in
     // index order (deterministic) on top of the BatchNorm shift and runs the epilogue.
     int ksplit;
-    int pair;            // host side only: 8-wave tile-pair kernel where it applies (FIUNET_OPT_PAIR_TILES)
     float* kslab;
     unsigned long long* stamp;  // diagnostic builds (-DFIUNET_STAMP / -DFIUNET_CLOCK) only: one 128-B record (16 cycle sums) per wave
     unsigned stamp_cap;         //   records the buffer holds (waves beyond it do not write)
@@ -240,18 +237,11 @@ __device__ __forceinline__ uint4 chunk_bilerp(const uint4& a, const uint4& b, co
 template <typename T>
 __device__ __forceinline__ void chunk_hlerp(const uint4& a, const uint4& b, float hx, float lx, float* h)
 {
-    [[maybe_unused]] constexpr int NE = Elem<T>::NE;
-#ifdef FIUNET_DIAG_NO_HLERP
-    // timing diagnostic (results are garbage): what the consumer's gather would cost if the HORIZONTAL lerp had been
-    // done by the producer (review item 6): one staged chunk per low-res row, unpacked, no arithmetic
-    (void)b; (void)hx; (void)lx;
-    chunk_unpack<T>(a, h);
-#else
+    constexpr int NE = Elem<T>::NE;
     float fa[NE], fb[NE];
     chunk_unpack<T>(a, fa); chunk_unpack<T>(b, fb);
 #pragma unroll
     for (int i = 0; i < NE; ++i) h[i] = fmaf(lx, fb[i], __fmul_rn(hx, fa[i]));
-#endif
 }
 template <typename T>
 __device__ __forceinline__ uint4 chunk_vlerp(const float* top, const float* bot, float hy, float ly)
@@ -533,7 +523,29 @@ constexpr int conv_occupancy(int BN, int TH, int TW, int lds_bytes = 0)
     return conv_wave_frags(BN, TH, TW) == 4 && lds_bytes * 3 <= 160 * 1024 ? 3 : 2;
 }
 
-// ---- accumulator set-up and epilogue shared by the conv kernels ---------------------------------
+// ---- tile indexing, accumulator set-up and epilogue shared by the conv kernels -----------------
+
+// XCD-aware, bijective block remap: blocks sharing an input tile (different cout tiles) and neighbouring
+// tiles get consecutive logical ids on ONE XCD so the re-reads hit its L2.
+__device__ __forceinline__ int conv_block_remap()
+{
+    const int nblk = gridDim.x, bid = blockIdx.x;
+    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
+// Logical tile index -> (cout tile, image, tile row, tile column); the cout tile varies fastest.
+struct ConvTileId { int ct, b, ty, tx; };
+__device__ __forceinline__ ConvTileId conv_tile_decode(const ConvArgs& a, int t)
+{
+    ConvTileId d;
+    d.ct = t % a.nct; t /= a.nct;
+    d.tx = t % a.tilesX; t /= a.tilesX;
+    d.ty = t % a.tilesY;
+    d.b = t / a.tilesY;
+    return d;
+}
+
 // Eval-mode BatchNorm is folded on both sides of the K loop: its scale into the packed weights
 // (fiunet_load_weights) and its shift into the INITIAL value of the accumulators, so the epilogue is
 // just y = relu(acc).  Which couts a lane holds: accumulator tile m, register j of lane group lc is
@@ -916,23 +928,13 @@ __global__ __launch_bounds__(256, conv_occupancy(BN, TH, TW, ConvTile<BN, TH, TW
     const unsigned lds_in_addr = lds_addr_of(lds_in);
     const unsigned lds_w_addr = lds_addr_of(lds_w);
 
-    // XCD-aware, bijective block remap: blocks sharing an input tile (different cout tiles) and
-    // neighbouring tiles get consecutive logical ids on ONE XCD so the re-reads hit its L2.
-    int lid;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    int lid = conv_block_remap();
     const int ksplit = epi_is_splitk(EPI) ? a.ksplit : 1;
     const int split = lid % ksplit;
     lid /= ksplit;
-    const int ct = lid % a.nct;
-    int t = lid / a.nct;
-    const int tx = t % a.tilesX; t /= a.tilesX;
-    const int ty = t % a.tilesY;
-    const int b = t / a.tilesY;
-    const int y0 = ty * TH, x0 = tx * TW;
+    const ConvTileId id = conv_tile_decode(a, lid);
+    const int ct = id.ct, b = id.b;
+    const int y0 = id.ty * TH, x0 = id.tx * TW;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1218,17 +1220,11 @@ __global__ __launch_bounds__(256, conv_occupancy(BN, TH, TW, ConvTile<BN, TH, TW
             // float pairs (v_pk_fma_f32: null), s_setprio 3 for the walk (null).
 #pragma unroll 1
             for (int py = rbeg; py < rend; ++py) {
-#ifdef FIUNET_YTAB_LDS  // A/B: the row entry through LDS
-                const uint4 yt = *reinterpret_cast<const uint4*>(ytab + py * 16);  // same address in every lane
-                const int o0 = __builtin_amdgcn_readfirstlane((int)yt.x);
-                const int o1 = __builtin_amdgcn_readfirstlane((int)yt.y);
-#else
                 const uint4 yt = make_uint4((unsigned)__builtin_amdgcn_readlane((int)yrow.x, py),
                                             (unsigned)__builtin_amdgcn_readlane((int)yrow.y, py),
                                             (unsigned)__builtin_amdgcn_readlane((int)yrow.z, py),
                                             (unsigned)__builtin_amdgcn_readlane((int)yrow.w, py));
                 const int o0 = (int)yt.x, o1 = (int)yt.y;
-#endif
                 uint4 v = make_uint4(0u, 0u, 0u, 0u);
                 if (o0 >= 0) {  // rows outside the image / the upsampled extent stay zero (conv pad, F.pad)
                     if (o0 != c0) {
@@ -1482,9 +1478,6 @@ __global__ __launch_bounds__(256, conv_occupancy(BN, TH, TW, ConvTile<BN, TH, TW
         }
     };
     auto gather_plane = [&](int plane, int idle_slot, bool first) __attribute__((always_inline)) {
-#ifdef FIUNET_DIAG_NO_GATHER  // timing diagnostic: compute side alone (stale LDS, results are garbage)
-        return;
-#endif
         if constexpr (STEM && X2) {   // virtual planes 0 / 2 / 3 / 5 = (plane 0 hi, plane 0 lo, plane 1 hi, plane 1 lo)
             if (first) {
                 gather_plane_stem(stem_w0, false);
@@ -1555,11 +1548,7 @@ __global__ __launch_bounds__(256, conv_occupancy(BN, TH, TW, ConvTile<BN, TH, TW
             // in-tile row (tap ky = 1) the rolling window holds everything the rest of the step needs,
             // so a barrier there declares the in-tile dead and the next plane's DMA is issued BEFORE
             // the remaining 64 MFMAs, which cover its round trip (no second in-tile buffer needed).
-#ifndef FIUNET_NO_EARLY_GATHER
             constexpr bool EARLY_OK = ROLL && DIRECT;  // (the concat kernels would spill 6-8 registers)
-#else
-            constexpr bool EARLY_OK = false;
-#endif
             bool early = false;
             if constexpr (EARLY_OK)
                 early = kx == 2 && gather_next && (DIRECT || plane + 1 < p0);
@@ -1589,11 +1578,7 @@ __global__ __launch_bounds__(256, conv_occupancy(BN, TH, TW, ConvTile<BN, TH, TW
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
 #pragma unroll
-                        for (int n = 0; n < NF; ++n) {
-#ifndef FIUNET_DIAG_NO_MFMA  // timing diagnostic: memory side alone (results are garbage)
-                            mma_chunk<T>(acc[m][n], wa[m], xb[n / FR + ky][n % FR]);
-#endif
-                        }
+                        for (int n = 0; n < NF; ++n) mma_chunk<T>(acc[m][n], wa[m], xb[n / FR + ky][n % FR]);
                 }
             } else {
 #pragma unroll
@@ -1613,11 +1598,7 @@ __global__ __launch_bounds__(256, conv_occupancy(BN, TH, TW, ConvTile<BN, TH, TW
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
 #pragma unroll
-                        for (int n = 0; n < NF; ++n) {
-#ifndef FIUNET_DIAG_NO_MFMA
-                            mma_chunk<T>(acc[m][n], wa[m], xb[n]);
-#endif
-                        }
+                        for (int n = 0; n < NF; ++n) mma_chunk<T>(acc[m][n], wa[m], xb[n]);
                 }
             }
 #ifdef FIUNET_STAMP

@@ -9,7 +9,6 @@
 // gfx950 only; no CPU fallback: every entry point either launches HIP kernels or returns an error.
 #include "../../include/fiunet.h"
 #include "pointwise.hip.h"
-#include "conv3x3_pair.hip.h"
 #include "conv3x3_kwave.hip.h"
 #include "metrics.hip.h"
 
@@ -140,7 +139,6 @@ struct fiunet_ctx {
     ConvWeights conv[NCONV];
     float* head_w = nullptr;  // [cf][64]
     float* head_b = nullptr;  // [cf]
-    void* zero_page = nullptr;  // 256 zero bytes (LDS-DMA source for conv padding)
     void* stem_w_split = nullptr;  // gray stem weights x BatchNorm scale as bf16 hi/lo pairs [2][64][32] (fused stem)
     unsigned long long* stamps = nullptr;  // per-wave cycle records (diagnostic -DFIUNET_STAMP builds)
     int stamp_layer = -1;
@@ -180,11 +178,11 @@ void free_weights(fiunet_ctx* ctx)
 
 thread_local std::string* g_name_out = nullptr;  // where the next conv launch reports its kernel
 
-// One conv kernel on `nblk` workgroups of `threads` with `lds` bytes of dynamic LDS: more than 64 KiB needs the opt-in
+// One conv kernel on `nblk` workgroups of 256 threads with `lds` bytes of dynamic LDS: more than 64 KiB needs the opt-in
 // attribute, set once per kernel and device (a duplicate hipFuncSetAttribute is harmless); `name` is what the profiler
 // reports for the stage (fiunet_profile_read).
 template <auto Kernel>
-int launch_lds(const char* name, long long nblk, int threads, int lds, const ConvArgs& a, hipStream_t s)
+int launch_lds(const char* name, long long nblk, int lds, const ConvArgs& a, hipStream_t s)
 {
     if (g_name_out) *g_name_out = name;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return fail(FIUNET_ERR_INVALID_ARG, "conv grid too large");
@@ -195,7 +193,7 @@ int launch_lds(const char* name, long long nblk, int threads, int lds, const Con
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         lds_attr_set[dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL(Kernel, dim3((unsigned)nblk), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)nblk), dim3(256), lds, s, a);
     HIP_TRY(hipGetLastError());
     return FIUNET_OK;
 }
@@ -211,23 +209,7 @@ int launch_conv_cfg(ConvArgs a, hipStream_t s)
     a.tilesY = (a.H + TH - 1) / TH;
     a.nct = a.Cout / BN;
     const long long nblk = (long long)a.B * a.tilesX * a.tilesY * a.nct * (epi_is_splitk(EPI) ? a.ksplit : 1);
-    return launch_lds<&conv3x3_mfma_kernel<T, BN, TH, TW, MODE, EPI>>(name, nblk, 256, ConvTile<BN, TH, TW, MODE>::LDS_BYTES,
-                                                                       a, s);
-}
-
-// One 8-wave workgroup per CU on two pixel tiles with a shared weight ring (conv3x3_pair.hip.h).
-template <typename T, int BN, int TH, int TW, int EPI>
-int launch_pair_cfg(ConvArgs a, hipStream_t s)
-{
-    char name[128] = "";
-    if (g_name_out)
-        std::snprintf(name, sizeof name, "conv3x3_pair_kernel<%s,%d,%d,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BN, TH, TW, EPI);
-    a.tilesX = (a.W + TW - 1) / TW;
-    a.tilesY = (a.H + TH - 1) / TH;
-    a.nct = a.Cout / BN;
-    const long long ntiles = (long long)a.B * a.tilesX * a.tilesY;
-    return launch_lds<&conv3x3_pair_kernel<T, BN, TH, TW, EPI>>(name, (ntiles + 1) / 2 * a.nct, 512,
-                                                                PairTile<BN, TH, TW>::LDS_BYTES, a, s);
+    return launch_lds<&conv3x3_mfma_kernel<T, BN, TH, TW, MODE, EPI>>(name, nblk, ConvTile<BN, TH, TW, MODE>::LDS_BYTES, a, s);
 }
 
 inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 256 * 32); }
@@ -604,10 +586,6 @@ bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p)
     return true;
 }
 
-// pair kernel: direct sources, plain / pooled epilogue, enough tile pairs to fill the 256 CUs
-template <typename T, int BN, int TH, int TW, int MODE, int EPI>
-constexpr bool pair_capable() { return MODE == SRC_DIRECT && (EPI == EPI_PLAIN || EPI == EPI_POOL) && BN == 128; }
-
 // The K loop cut over the four waves of a workgroup (small problems, direct sources, every precision): conv3x3_kwave.hip.h.
 template <typename T, int EPI, bool X2> int launch_kwave(ConvArgs a, hipStream_t s)
 {
@@ -618,8 +596,7 @@ template <typename T, int EPI, bool X2> int launch_kwave(ConvArgs a, hipStream_t
     a.tilesX = (a.W + Tile::TW - 1) / Tile::TW;
     a.tilesY = (a.H + Tile::TH - 1) / Tile::TH;
     a.nct = a.Cout / Tile::BN;
-    return launch_lds<&conv3x3_kwave_kernel<EPI, X2, T>>(name, (long long)a.B * a.tilesX * a.tilesY * a.nct, 256, Tile::LDS_BYTES,
-                                                          a, s);
+    return launch_lds<&conv3x3_kwave_kernel<EPI, X2, T>>(name, (long long)a.B * a.tilesX * a.tilesY * a.nct, Tile::LDS_BYTES, a, s);
 }
 
 // One conv launch in a given tile shape; ksplit > 1: the K loop (planes) cut over `ksplit` workgroups that store raw
@@ -642,11 +619,6 @@ int launch_conv_maybe_split(ConvArgs a, hipStream_t s, int ksplit)
             if (g_name_out) *g_name_out += "+splitk" + std::to_string(ksplit);
             return FIUNET_OK;
         }
-    }
-    if constexpr (pair_capable<T, BN, TH, TW, MODE, EPI>()) {
-        const long long ntiles = (long long)a.B * ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
-        if (a.pair && a.C1 == 0 && (ntiles + 1) / 2 * (a.Cout / BN) >= 256)  // (its gather knows one source)
-            return launch_pair_cfg<T, BN, TH, TW, EPI>(a, s);
     }
     return launch_conv_cfg<T, BN, TH, TW, MODE, EPI>(a, s);
 }
@@ -794,9 +766,7 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
         a.wgt = x2 ? cw.w_x2 : bf16 ? cw.w_bf16 : cw.w_f32;
         a.scale = cw.scale; a.shift = cw.shift;
         a.relu = 1;
-        a.zero_page = ctx->zero_page;
         a.ksplit = 1;
-        a.pair = (ctx->flags & FIUNET_OPT_PAIR_TILES) ? 1 : 0;
         a.kslab = st.slab ? (float*)(ws + p.slab_off) : nullptr;
         a.stamp = (ctx->stamps && i == ctx->stamp_layer) ? ctx->stamps : nullptr;
         a.stamp_cap = (unsigned)kStampWaves;
@@ -1092,8 +1062,6 @@ int fiunet_load_weights(fiunet_ctx* ctx, int n, const char* const* names,
         if ((rc = get("unet.outc.conv.bias", ctx->cf, &bi))) return rc;
         if ((rc = dev_upload(ctx, w, (size_t)ctx->cf * 64 * 4, (void**)&ctx->head_w))) return rc;
         if ((rc = dev_upload(ctx, bi, (size_t)ctx->cf * 4, (void**)&ctx->head_b))) return rc;
-        const std::vector<char> zeros(256, 0);
-        if ((rc = dev_upload(ctx, zeros.data(), zeros.size(), &ctx->zero_page))) return rc;
 #if defined(FIUNET_STAMP) || defined(FIUNET_CLOCK)
         {   // one 128-B record per wave of the largest launch (B=8 1080p: 32 640 workgroups); the kernels bound their index
             void* d = nullptr;

@@ -216,15 +216,14 @@ class FrameInterpolationUNet(nn.Module):
         """Call after editing parameters in place so the next forward re-uploads them."""
         self._ctx_dirty = True
 
-    def set_options(self, *, unfused: bool = False, keep_all: bool = False, pair_tiles: bool = False,
-                    gather_upsample: bool = False, rne_weights: bool = False, no_dither: bool = False):
-        """unfused / keep_all / pair_tiles / gather_upsample: ablation and test switches (include/fiunet.h).
+    def set_options(self, *, unfused: bool = False, keep_all: bool = False, gather_upsample: bool = False,
+                    rne_weights: bool = False, no_dither: bool = False):
+        """unfused / keep_all / gather_upsample: ablation and test switches (include/fiunet.h).
         rne_weights: bf16 weights rounded to nearest instead of with the per-filter error feedback;
         no_dither: no ordered input dither in the bf16 stem - both for comparing a real checkpoint both
         ways (the defaults are what the PSNR criterion was measured with)."""
         old = self._options
         self._options = ((_native.OPT_UNFUSED if unfused else 0) | (_native.OPT_KEEP_ALL if keep_all else 0)
-                         | (_native.OPT_PAIR_TILES if pair_tiles else 0)
                          | (_native.OPT_GATHER_UPSAMPLE if gather_upsample else 0)
                          | (_native.OPT_RNE_WEIGHTS if rne_weights else 0)
                          | (_native.OPT_NO_DITHER if no_dither else 0))

@@ -46,7 +46,7 @@ enum fiunet_precision {
                           product is wh*xh + wl*xh + wh*xl with fp32 accumulation (~1e-5 relative end to end); fp32 frames
                           in, fp32 logits out, exact-fp32 stem and head.  Needs fiunet_prepare_precision(ctx, FIUNET_BF16X2)
                           once after fiunet_load_weights.  Both decoders; FIUNET_OPT_KEEP_ALL + read-back work, the other
-                          A/B options (UNFUSED, GATHER_UPSAMPLE, PAIR_TILES) are ignored in this mode */
+                          A/B options (UNFUSED, GATHER_UPSAMPLE) are ignored in this mode */
 };
 
 /* Bit flags for fiunet_set_options. */
@@ -55,8 +55,6 @@ enum fiunet_option {
                                separate kernels instead of fusing them into the consumer conv */
     FIUNET_OPT_KEEP_ALL = 2,/* also store the last 64-ch activation (tap 17) that the fused 1x1
                                head otherwise keeps in registers; for fiunet_debug_read_activation */
-    FIUNET_OPT_PAIR_TILES = 8, /* A/B runs: direct >=128-channel convs on the 8-wave tile-pair kernel
-                               (conv3x3_pair.hip.h: shared weight ring, double-buffered in-tile); same bits */
     FIUNET_OPT_RNE_WEIGHTS = 32, /* A/B runs: round the bf16 conv weights to nearest instead of with the per-filter
                                error feedback (fiunet.hip, f32_to_bf16_feedback).  Read by fiunet_load_weights: set it
                                BEFORE loading */
