@@ -21,11 +21,12 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FIUNET_LIB") or os.path.join(_PKG, "libfiunet_hip.so")  # FIUNET_LIB: A/B builds
 CSRC = os.path.join(_PKG, "csrc")
 
-ABI_VERSION = 5        # include/fiunet.h FIUNET_ABI_VERSION this binding is written for
+ABI_VERSION = 6        # include/fiunet.h FIUNET_ABI_VERSION this binding is written for
 ABI_MIN_COMPAT = 4     # oldest A/B library (FIUNET_LIB) whose shared entry points have today's signatures
 FP32, BF16, BF16X2 = 0, 1, 2   # include/fiunet.h: enum fiunet_precision
 OPT_UNFUSED, OPT_KEEP_ALL, OPT_GATHER_UPSAMPLE = 1, 2, 16
 OPT_RNE_WEIGHTS, OPT_NO_DITHER = 32, 64
+YUV_MPEG2, YUV_BT709, YUV_FULL_RANGE = 1, 2, 4   # include/fiunet.h: enum fiunet_colour
 
 #: every symbol include/fiunet.h declares (tests/test_abi.py checks the header against this)
 SYMBOLS = (
@@ -37,6 +38,7 @@ SYMBOLS = (
     "fiunet_postprocess_u8", "fiunet_debug_read_activation", "fiunet_profile_enable",
     "fiunet_profile_read", "fiunet_metrics_workspace_bytes", "fiunet_psnr_u8", "fiunet_ssim_u8",
     "fiunet_ssim_gauss_workspace_bytes", "fiunet_ssim_gauss_f32",
+    "fiunet_yuv420_to_rgb_u8", "fiunet_rgb_to_yuv420_u8", "fiunet_workspace_bytes_yuv420", "fiunet_forward_yuv420",
 )
 
 _lib = None
@@ -105,6 +107,12 @@ def lib() -> ctypes.CDLL:
     L.fiunet_forward_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, sz, vp]
     L.fiunet_forward_u8_strided.argtypes = [vp, vp, vp, vp, sz, ci, ci, ci, ci, vp, sz, vp]
     L.fiunet_preprocess_u8.argtypes = [vp, vp, sz, vp]
+    cu = ctypes.c_uint
+    L.fiunet_yuv420_to_rgb_u8.argtypes = [vp, sz, vp, ci, ci, ci, cu, vp]
+    L.fiunet_rgb_to_yuv420_u8.argtypes = [vp, vp, sz, ci, ci, ci, cu, vp]
+    L.fiunet_workspace_bytes_yuv420.argtypes = [vp, ci, ci, ci, ci]
+    L.fiunet_workspace_bytes_yuv420.restype = sz
+    L.fiunet_forward_yuv420.argtypes = [vp, vp, vp, vp, sz, ci, ci, ci, cu, ci, vp, sz, vp]
     L.fiunet_postprocess_u8.argtypes = [vp, vp, sz, vp]
     L.fiunet_debug_read_activation.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz,
                                                ctypes.POINTER(ci), vp]
@@ -198,9 +206,11 @@ class Context:
             check(lib().fiunet_prepare_precision(self._h, precision), "fiunet_prepare_precision")
             self._prepared.add(precision)
 
-    def workspace_bytes(self, b, h, w, precision, u8=False) -> int:
+    def workspace_bytes(self, b, h, w, precision, u8=False, yuv=False) -> int:
+        """yuv: fiunet_forward_yuv420's workspace (u8: fiunet_forward_u8's; neither: fiunet_forward's)."""
         self.prepare(precision)   # every forward path sizes its workspace first
-        fn = lib().fiunet_workspace_bytes_u8 if u8 else lib().fiunet_workspace_bytes
+        fn = (lib().fiunet_workspace_bytes_yuv420 if yuv else
+              lib().fiunet_workspace_bytes_u8 if u8 else lib().fiunet_workspace_bytes)
         n = fn(self._h, b, h, w, precision)
         if n == 0:
             if h < 16 or w < 16:
@@ -250,6 +260,16 @@ class Context:
                                               w, precision, workspace.data_ptr(), workspace.numel(), s),
               "fiunet_forward_u8_strided")
 
+    def forward_yuv420(self, f1, f2, out, h, w, colour, precision, workspace, stream=None):
+        """f1, f2: uint8 [B, F] packed I420 frames, contiguous; `out`: uint8 [B, F] whose rows are contiguous and may lie
+        further apart (every second frame of the video loop's interleaved result)."""
+        b = f1.shape[0]
+        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        st = out.stride(0) if b > 1 else out.shape[1]
+        check(lib().fiunet_forward_yuv420(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), st, b, h, w, colour,
+                                          precision, workspace.data_ptr(), workspace.numel(), s),
+              "fiunet_forward_yuv420")
+
     def profile_enable(self, on: bool):
         check(lib().fiunet_profile_enable(self._h, 1 if on else 0), "fiunet_profile_enable")
 
@@ -296,3 +316,21 @@ def postprocess_u8(src_f32: "torch.Tensor") -> "torch.Tensor":
     check(lib().fiunet_postprocess_u8(src_f32.data_ptr(), out.data_ptr(), src_f32.numel(), s),
           "fiunet_postprocess_u8")
     return out
+
+
+def yuv420_to_rgb_u8(frames: "torch.Tensor", out: "torch.Tensor", h: int, w: int, colour: int) -> None:
+    """fiunet_yuv420_to_rgb_u8: uint8 [B, F] packed I420 (rows contiguous, any row stride) -> uint8 [B, 3, h, w]."""
+    b = frames.shape[0]
+    st = frames.stride(0) if b > 1 else frames.shape[1]
+    s = torch.cuda.current_stream(frames.device).cuda_stream
+    check(lib().fiunet_yuv420_to_rgb_u8(frames.data_ptr(), st, out.data_ptr(), b, h, w, colour, s),
+          "fiunet_yuv420_to_rgb_u8")
+
+
+def rgb_to_yuv420_u8(rgb: "torch.Tensor", out: "torch.Tensor", colour: int) -> None:
+    """fiunet_rgb_to_yuv420_u8: uint8 [B, 3, h, w] contiguous -> uint8 [B, F] (rows contiguous, any row stride)."""
+    b, _, h, w = rgb.shape
+    st = out.stride(0) if b > 1 else out.shape[1]
+    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    check(lib().fiunet_rgb_to_yuv420_u8(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s),
+          "fiunet_rgb_to_yuv420_u8")

@@ -1,0 +1,98 @@
+"""YUV 4:2:0 colour video for the RGB (6->3) network: option parsing and the two device conversions.
+
+A frame is packed I420 - the Y plane H x W, then U, then V, each ceil(H/2) x ceil(W/2) bytes - exactly a Y4M frame
+payload, so a decoded video (`ffmpeg -i in.mp4 -pix_fmt yuv420p in.y4m`) reaches the network without a host-side
+conversion.  The conversion is defined in integer arithmetic (csrc/colour.hip.h, DESIGN.md "Colour video") and runs
+in HIP kernels (`fiunet_yuv420_to_rgb_u8`, `fiunet_rgb_to_yuv420_u8`); the network's forward between them is
+`FrameInterpolationUNet.forward_yuv420`.
+
+Options (the keywords of every colour entry point):
+  siting        "jpeg" (Y4M C420jpeg, C420 or no tag: chroma centred in its 2x2 luma block) or "mpeg2" (C420mpeg2:
+                co-sited with the even luma column, centred vertically)
+  matrix        "bt709" (the default: the inputs are HD video; Y4M does not carry the matrix) or "bt601"
+  colour_range  "limited" (Y 16-235, C 16-240; the default, and what a Y4M header without XCOLORRANGE means) or "full"
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _native
+
+SITINGS = {"jpeg": 0, "mpeg2": _native.YUV_MPEG2}
+MATRICES = {"bt601": 0, "bt709": _native.YUV_BT709}
+RANGES = {"limited": 0, "full": _native.YUV_FULL_RANGE}
+
+#: Y4M colourspace tags the RGB network reads, and the chroma siting each one means
+Y4M_SITING = {"420jpeg": "jpeg", "420": "jpeg", "420mpeg2": "mpeg2"}
+
+
+def colour_flags(siting: str = "jpeg", matrix: str = "bt709", colour_range: str = "limited") -> int:
+    """-> the `colour` flags word of the C ABI (include/fiunet.h, enum fiunet_colour)."""
+    for name, value, table in (("siting", siting, SITINGS), ("matrix", matrix, MATRICES),
+                               ("colour_range", colour_range, RANGES)):
+        if value not in table:
+            raise ValueError(f"{name} must be one of {sorted(table)}, got {value!r}")
+    return SITINGS[siting] | MATRICES[matrix] | RANGES[colour_range]
+
+
+def i420_frame_bytes(height: int, width: int) -> int:
+    """Bytes of one packed I420 frame: H*W + 2 * ceil(H/2) * ceil(W/2)."""
+    return height * width + 2 * ((height + 1) // 2) * ((width + 1) // 2)
+
+
+def siting_of_y4m(colourspace: str) -> str:
+    """Chroma siting of a Y4M `C` tag; ValueError naming the tag for the layouts the RGB network does not read."""
+    try:
+        return Y4M_SITING[colourspace]
+    except KeyError:
+        raise ValueError(f"Y4M colourspace C{colourspace} is not supported by the RGB network: it reads 4:2:0 "
+                         f"video tagged {', '.join('C' + t for t in Y4M_SITING)} or untagged") from None
+
+
+def _check_frames(frames: torch.Tensor, height: int, width: int, what: str) -> None:
+    fb = i420_frame_bytes(height, width)
+    if frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[1] != fb:
+        raise ValueError(f"{what} must be uint8 [B, {fb}] packed I420 frames of {height}x{width}, "
+                         f"got {frames.dtype} {tuple(frames.shape)}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"{what} must be on the GPU: there is no CPU path in this package")
+    if frames.shape[0] > 1 and (frames.stride(1) != 1 or frames.stride(0) < fb):
+        raise ValueError(f"{what}: every frame must be contiguous (strides {tuple(frames.stride())})")
+
+
+@torch.no_grad()
+def yuv420_to_rgb(frames: torch.Tensor, height: int, width: int, *, siting: str = "jpeg", matrix: str = "bt709",
+                  colour_range: str = "limited", out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [B, F] packed I420 frames on the GPU -> uint8 planar RGB [B, 3, H, W] (`fiunet_yuv420_to_rgb_u8`)."""
+    flags = colour_flags(siting, matrix, colour_range)
+    _check_frames(frames, height, width, "frames")
+    shape = (frames.shape[0], 3, height, width)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != frames.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 {shape} tensor on {frames.device}")
+    with torch.cuda.device(frames.device):
+        _native.yuv420_to_rgb_u8(frames, out, height, width, flags)
+    return out
+
+
+@torch.no_grad()
+def rgb_to_yuv420(rgb: torch.Tensor, *, siting: str = "jpeg", matrix: str = "bt709", colour_range: str = "limited",
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 planar RGB [B, 3, H, W] on the GPU -> uint8 [B, F] packed I420 frames (`fiunet_rgb_to_yuv420_u8`).
+    `out` may be a view whose frames lie further apart than F bytes; the bytes between them are left untouched."""
+    flags = colour_flags(siting, matrix, colour_range)
+    if rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[1] != 3:
+        raise ValueError(f"rgb must be uint8 [B, 3, H, W], got {rgb.dtype} {tuple(rgb.shape)}")
+    if not rgb.is_cuda:
+        raise RuntimeError("rgb must be on the GPU: there is no CPU path in this package")
+    b, _, h, w = rgb.shape
+    rgb = rgb.contiguous()
+    if out is None:
+        out = torch.empty((b, i420_frame_bytes(h, w)), dtype=torch.uint8, device=rgb.device)
+    elif out.device != rgb.device or out.shape[0] != b:
+        raise ValueError(f"out must hold {b} frames on {rgb.device}")
+    _check_frames(out, h, w, "out")
+    with torch.cuda.device(rgb.device):
+        _native.rgb_to_yuv420_u8(rgb, out, flags)
+    return out

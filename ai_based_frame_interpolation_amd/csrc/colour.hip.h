@@ -1,0 +1,229 @@
+// colour.hip.h -- YUV 4:2:0 <-> planar RGB on device for the RGB (6->3) network, gfx950 only.
+//
+//   yuv420_to_rgb_kernel : packed I420 frames (Y plane H x W, then U, then V, each ceil(H/2) x ceil(W/2); the
+//                          frames `in_stride` bytes apart: a Y4M frame payload) -> planar RGB uint8 [B,3,H,W],
+//                          the layout fiunet_forward_u8 takes for frame_channels == 3
+//   rgb_to_yuv420_kernel : the inverse, writing packed I420 frames `out_stride` bytes apart
+//
+// The reference has no colour path, so the conversion is defined here, in integer arithmetic, so that the device
+// and a numpy restatement (tests/colour_ref.py) agree bit for bit.  S = 2^14.
+//
+//   matrix   BT.601 (Kr 0.299, Kb 0.114) or BT.709 (Kr 0.2126, Kb 0.0722); Kg = 1 - Kr - Kb
+//   range    limited: Y = 16 + 219 E'Y, C = 128 + 224 E'P;  full: Y = 255 E'Y, C = 128 + 255 E'P
+//            ys = 219/255 or 1, cs = 224/255 or 1 (scale per RGB code); yoff = 16 or 0
+//   rnd(x)   floor(x * S + 0.5), in double
+//   encode   yr = rnd(Kr ys), yb = rnd(Kb ys), yg = rnd(ys) - yr - yb                 (row sums to rnd(ys))
+//            cbr = rnd(-Kr / (2 (1 - Kb)) cs), cbb = rnd(0.5 cs), cbg = -cbr - cbb      (row sums to 0)
+//            crr = rnd(0.5 cs), crb = rnd(-Kb / (2 (1 - Kr)) cs), crg = -crr - crb      (row sums to 0)
+//            so R = G = B gives Cb = Cr = 128 exactly
+//   decode   dy = rnd(1 / ys), dcr = rnd(2 (1 - Kr) / cs), dcb = rnd(2 (1 - Kb) / cs),
+//            dgb = rnd(-2 Kb (1 - Kb) / Kg / cs), dgr = rnd(-2 Kr (1 - Kr) / Kg / cs)
+//   siting   jpeg (also plain 420 / no tag): a chroma sample sits at the centre of its 2x2 luma block;
+//            mpeg2: co-sited with the even luma column, centred vertically.  Outside the image rows and columns
+//            are replicated (the last chroma row / column of an odd size covers a 2x1, 1x2 or 1x1 block).
+//   Y        clamp((yr R + yg G + yb B + yoff S + S/2) >> 14)
+//   Cb, Cr   from sums over n samples: jpeg n = 4, the 2x2 block; mpeg2 n = 8, the horizontal [1,2,1] at
+//            x = 2j-1, 2j, 2j+1 times the vertical [1,1] at y = 2i, 2i+1
+//            C = clamp((c_r SR + c_g SG + c_b SB + 128 n S + n S/2) >> (14 + log2 n))
+//   up-sample chroma x16, not rounded: vertical 3 x nearest + 1 x next-nearest row (both sitings); horizontal
+//            jpeg 3 x nearest + 1 x next-nearest column (together 9a + 3b + 3c + d), mpeg2 4 x its own sample at an
+//            even x, 2 x the sum of the two neighbours at an odd x
+//   RGB      with Y' = Y - yoff, U = Cb16 - 2048, V = Cr16 - 2048 (int32, at most ~1.6e8):
+//            R = clamp((16 dy Y' + dcr V + 2^17) >> 18), G = clamp((16 dy Y' + dgb U + dgr V + 2^17) >> 18),
+//            B = clamp((16 dy Y' + dcb U + 2^17) >> 18); `>>` is an arithmetic shift (round half up)
+//
+// Both kernels are HBM-bound elementwise work.  A thread covers 4 luma columns of a row (decode) or of a row pair
+// (encode), so a wave reads and writes 256 contiguous bytes of every luma / RGB row; with W % 4 == 0 and 4-B aligned
+// bases (VEC) those are single 4-byte accesses, otherwise bytes with the edge clamped.  Chroma is read / written
+// as bytes (half the columns, one quarter of the samples).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cmath>
+
+#include "../../include/fiunet.h"
+
+namespace fiunet {
+
+struct ColourCoef {
+    int yr, yg, yb, yoff;     // encode, luma row
+    int cbr, cbg, cbb;        // encode, Cb row
+    int crr, crg, crb;        // encode, Cr row
+    int dy, dcr, dgb, dgr, dcb;  // decode
+    int mpeg2;                // siting
+};
+
+constexpr unsigned kColourFlags = FIUNET_YUV_MPEG2 | FIUNET_YUV_BT709 | FIUNET_YUV_FULL_RANGE;
+
+inline int colour_rnd(double x) { return (int)std::floor(x * 16384.0 + 0.5); }
+
+inline ColourCoef colour_coef(unsigned flags)
+{
+    const bool full = flags & FIUNET_YUV_FULL_RANGE, bt709 = flags & FIUNET_YUV_BT709;
+    const double kr = bt709 ? 0.2126 : 0.299, kb = bt709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
+    const double ys = full ? 1.0 : 219.0 / 255.0, cs = full ? 1.0 : 224.0 / 255.0;
+    ColourCoef k;
+    k.yr = colour_rnd(kr * ys);
+    k.yb = colour_rnd(kb * ys);
+    k.yg = colour_rnd(ys) - k.yr - k.yb;
+    k.yoff = full ? 0 : 16;
+    k.cbr = colour_rnd(-kr / (2.0 * (1.0 - kb)) * cs);
+    k.cbb = colour_rnd(0.5 * cs);
+    k.cbg = -k.cbr - k.cbb;
+    k.crr = colour_rnd(0.5 * cs);
+    k.crb = colour_rnd(-kb / (2.0 * (1.0 - kr)) * cs);
+    k.crg = -k.crr - k.crb;
+    k.dy = colour_rnd(1.0 / ys);
+    k.dcr = colour_rnd(2.0 * (1.0 - kr) / cs);
+    k.dcb = colour_rnd(2.0 * (1.0 - kb) / cs);
+    k.dgb = colour_rnd(-2.0 * kb * (1.0 - kb) / kg / cs);
+    k.dgr = colour_rnd(-2.0 * kr * (1.0 - kr) / kg / cs);
+    k.mpeg2 = (flags & FIUNET_YUV_MPEG2) ? 1 : 0;
+    return k;
+}
+
+__device__ __forceinline__ uint8_t clamp_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
+
+constexpr int kColourBlock = 128;   // threads per workgroup; each covers 4 luma columns
+
+// grid = (ceil(ceil(W/4) / 128), H, B)
+template <bool VEC>
+__global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const uint8_t* __restrict__ in, size_t in_stride,
+                                                                     uint8_t* __restrict__ out, int H, int W,
+                                                                     ColourCoef k)
+{
+    const int t = blockIdx.x * kColourBlock + threadIdx.x, x0 = 4 * t, y = blockIdx.y;
+    if (x0 >= W) return;
+    const int Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
+    const size_t plane = (size_t)H * W;
+    const uint8_t* fy = in + (size_t)blockIdx.z * in_stride;
+    const uint8_t* fu = fy + plane;
+    const uint8_t* fv = fu + (size_t)Hc * Wc;
+    // chroma rows: the nearest (weight 3) and the next-nearest (weight 1), both sitings
+    const int i0 = y >> 1, i1 = min(max((y & 1) ? i0 + 1 : i0 - 1, 0), Hc - 1);
+    // chroma columns 2t-1 .. 2t+2 (clamped) cover every neighbour of luma columns 4t .. 4t+3
+    int u4[4], v4[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = min(max(2 * t - 1 + q, 0), Wc - 1);
+        u4[q] = 3 * fu[(size_t)i0 * Wc + j] + fu[(size_t)i1 * Wc + j];
+        v4[q] = 3 * fv[(size_t)i0 * Wc + j] + fv[(size_t)i1 * Wc + j];
+    }
+    int yv[4];
+    const uint8_t* row = fy + (size_t)y * W + x0;
+    if (VEC) {
+        const uchar4 p = *reinterpret_cast<const uchar4*>(row);
+        yv[0] = p.x; yv[1] = p.y; yv[2] = p.z; yv[3] = p.w;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) yv[c] = row[min(c, W - 1 - x0)];
+    }
+    uint8_t r[4], g[4], b[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        // pixel x0 + c: nearest chroma column index 1 + (c >> 1) in u4 / v4; jpeg's next-nearest is to the left at an
+        // even x and to the right at an odd x; mpeg2 takes its own sample at an even x and the two neighbours at an odd x
+        const int n = 1 + (c >> 1), f = (c & 1) ? n + 1 : n - 1;
+        int U, V;
+        if (k.mpeg2) {
+            U = (c & 1) ? 2 * (u4[n] + u4[n + 1]) : 4 * u4[n];
+            V = (c & 1) ? 2 * (v4[n] + v4[n + 1]) : 4 * v4[n];
+        } else {
+            U = 3 * u4[n] + u4[f];
+            V = 3 * v4[n] + v4[f];
+        }
+        U -= 2048;
+        V -= 2048;
+        const int yy = 16 * k.dy * (yv[c] - k.yoff) + (1 << 17);
+        r[c] = clamp_u8((yy + k.dcr * V) >> 18);
+        g[c] = clamp_u8((yy + k.dgb * U + k.dgr * V) >> 18);
+        b[c] = clamp_u8((yy + k.dcb * U) >> 18);
+    }
+    uint8_t* o = out + (size_t)blockIdx.z * 3 * plane + (size_t)y * W + x0;
+    if (VEC) {
+        *reinterpret_cast<uchar4*>(o) = make_uchar4(r[0], r[1], r[2], r[3]);
+        *reinterpret_cast<uchar4*>(o + plane) = make_uchar4(g[0], g[1], g[2], g[3]);
+        *reinterpret_cast<uchar4*>(o + 2 * plane) = make_uchar4(b[0], b[1], b[2], b[3]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (x0 + c < W) {
+                o[c] = r[c];
+                o[plane + c] = g[c];
+                o[2 * plane + c] = b[c];
+            }
+    }
+}
+
+// grid = (ceil(ceil(W/4) / 128), ceil(H/2), B): a thread covers luma rows 2i, 2i+1 and columns 4t .. 4t+3, i.e.
+// chroma samples (i, 2t) and (i, 2t+1)
+template <bool VEC>
+__global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const uint8_t* __restrict__ in,
+                                                                     uint8_t* __restrict__ out, size_t out_stride,
+                                                                     int H, int W, ColourCoef k)
+{
+    const int t = blockIdx.x * kColourBlock + threadIdx.x, x0 = 4 * t, i = blockIdx.y;
+    if (x0 >= W) return;
+    const int Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
+    const size_t plane = (size_t)H * W;
+    const int ya = 2 * i, yb = min(2 * i + 1, H - 1);
+    const uint8_t* src = in + (size_t)blockIdx.z * 3 * plane;
+    // px[ch][row][1 + c] = channel ch at (row ya / yb, column x0 + c), c = -1 .. 3, columns clamped into the image
+    int px[3][2][5];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const uint8_t* row = src + ch * plane + (size_t)(rr ? yb : ya) * W;
+            px[ch][rr][0] = row[max(x0 - 1, 0)];
+            if (VEC) {
+                const uchar4 p = *reinterpret_cast<const uchar4*>(row + x0);
+                px[ch][rr][1] = p.x; px[ch][rr][2] = p.y; px[ch][rr][3] = p.z; px[ch][rr][4] = p.w;
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) px[ch][rr][1 + c] = row[min(x0 + c, W - 1)];
+            }
+        }
+    uint8_t* fy = out + (size_t)blockIdx.z * out_stride;
+    uint8_t* fu = fy + plane;
+    uint8_t* fv = fu + (size_t)Hc * Wc;
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        if (2 * i + rr >= H) break;
+        uint8_t yv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            yv[c] = clamp_u8((k.yr * px[0][rr][1 + c] + k.yg * px[1][rr][1 + c] + k.yb * px[2][rr][1 + c] +
+                              k.yoff * 16384 + 8192) >> 14);
+        uint8_t* o = fy + (size_t)(2 * i + rr) * W + x0;
+        if (VEC) {
+            *reinterpret_cast<uchar4*>(o) = make_uchar4(yv[0], yv[1], yv[2], yv[3]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (x0 + c < W) o[c] = yv[c];
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int j = 2 * t + m;
+        if (j >= Wc) break;
+        int s[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            // local column of luma x = 2j is 1 + 2m in px; jpeg: 2j, 2j+1; mpeg2: [1,2,1] over 2j-1, 2j, 2j+1
+            const int a = 1 + 2 * m;
+            s[ch] = 0;
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr)
+                s[ch] += k.mpeg2 ? px[ch][rr][a - 1] + 2 * px[ch][rr][a] + px[ch][rr][a + 1]
+                                 : px[ch][rr][a] + px[ch][rr][a + 1];
+        }
+        const int sh = k.mpeg2 ? 17 : 16, bias = (128 << sh) + (1 << (sh - 1));
+        fu[(size_t)i * Wc + j] = clamp_u8((k.cbr * s[0] + k.cbg * s[1] + k.cbb * s[2] + bias) >> sh);
+        fv[(size_t)i * Wc + j] = clamp_u8((k.crr * s[0] + k.crg * s[1] + k.crb * s[2] + bias) >> sh);
+    }
+}
+
+}  // namespace fiunet

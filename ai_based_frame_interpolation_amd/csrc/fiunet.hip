@@ -11,6 +11,7 @@
 #include "pointwise.hip.h"
 #include "conv3x3_kwave.hip.h"
 #include "metrics.hip.h"
+#include "colour.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1250,6 +1251,95 @@ int fiunet_forward_u8_strided(fiunet_ctx* ctx, const uint8_t* frame1, const uint
     for (int i = 0; i < B; ++i)   // (ablation / read-back configurations only: one elementwise launch per image)
         if ((rc = fiunet_postprocess_u8(o + (size_t)i * img, out + (size_t)i * out_image_stride, img, stream))) return rc;
     return FIUNET_OK;
+}
+
+// ---- colour video (csrc/colour.hip.h): packed I420 <-> planar RGB, and the RGB network's forward between them ----
+static inline size_t i420_frame_bytes(int H, int W)
+{
+    return (size_t)H * W + 2 * (size_t)((H + 1) / 2) * ((W + 1) / 2);
+}
+
+static int check_colour_args(const void* in, const void* out, int B, int H, int W, unsigned colour)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (colour & ~kColourFlags) return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits");
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    return FIUNET_OK;
+}
+
+int fiunet_yuv420_to_rgb_u8(const uint8_t* in, size_t in_frame_stride, uint8_t* out, int B, int H, int W,
+                            unsigned colour, void* stream)
+{
+    int rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour))) return rc;
+    const size_t fb = i420_frame_bytes(H, W);
+    if (in_frame_stride == 0) in_frame_stride = fb;
+    if (in_frame_stride < fb) return fail(FIUNET_ERR_INVALID_ARG, "in_frame_stride smaller than one frame");
+    const bool vec = W % 4 == 0 && in_frame_stride % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 3) == 0;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
+    const ColourCoef k = colour_coef(colour);
+    if (vec)
+        hipLaunchKernelGGL(yuv420_to_rgb_kernel<true>, grid, dim3(kColourBlock), 0, (hipStream_t)stream, in,
+                           in_frame_stride, out, H, W, k);
+    else
+        hipLaunchKernelGGL(yuv420_to_rgb_kernel<false>, grid, dim3(kColourBlock), 0, (hipStream_t)stream, in,
+                           in_frame_stride, out, H, W, k);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_rgb_to_yuv420_u8(const uint8_t* in, uint8_t* out, size_t out_frame_stride, int B, int H, int W,
+                            unsigned colour, void* stream)
+{
+    int rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour))) return rc;
+    const size_t fb = i420_frame_bytes(H, W);
+    if (out_frame_stride == 0) out_frame_stride = fb;
+    if (out_frame_stride < fb) return fail(FIUNET_ERR_INVALID_ARG, "out_frame_stride smaller than one frame");
+    const bool vec = W % 4 == 0 && out_frame_stride % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 3) == 0;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)((H + 1) / 2), (unsigned)B);
+    const ColourCoef k = colour_coef(colour);
+    if (vec)
+        hipLaunchKernelGGL(rgb_to_yuv420_kernel<true>, grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, out,
+                           out_frame_stride, H, W, k);
+    else
+        hipLaunchKernelGGL(rgb_to_yuv420_kernel<false>, grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, out,
+                           out_frame_stride, H, W, k);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+size_t fiunet_workspace_bytes_yuv420(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    const size_t base = fiunet_workspace_bytes_u8(ctx, B, H, W, precision);
+    if (base == 0) return 0;
+    return align256(base) + 3 * align256((size_t)B * 3 * H * W);
+}
+
+int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
+                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
+                          void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3) return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_yuv420 needs the RGB network (frame_channels 3)");
+    if (colour & ~kColourFlags) return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits");
+    const size_t need = fiunet_workspace_bytes_yuv420(ctx, B, H, W, precision);
+    if (need == 0) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    const size_t fb = i420_frame_bytes(H, W);
+    if (out_frame_stride == 0) out_frame_stride = fb;
+    if (out_frame_stride < fb) return fail(FIUNET_ERR_INVALID_ARG, "out_frame_stride smaller than one frame");
+    const size_t base = align256(fiunet_workspace_bytes_u8(ctx, B, H, W, precision));
+    const size_t rgb = align256((size_t)B * 3 * H * W);
+    uint8_t* a = (uint8_t*)workspace + base;
+    uint8_t* b = a + rgb;
+    uint8_t* o = b + rgb;
+    int rc;
+    if ((rc = fiunet_yuv420_to_rgb_u8(frame1, fb, a, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_yuv420_to_rgb_u8(frame2, fb, b, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
+    return fiunet_rgb_to_yuv420_u8(o, out, out_frame_stride, B, H, W, colour, stream);
 }
 
 static inline int ssim_tiles(int H, int W, int* tiles_x)

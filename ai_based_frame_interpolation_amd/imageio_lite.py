@@ -230,17 +230,16 @@ def write_png(path: str, img: np.ndarray) -> None:
 # uncompressed container every player / ffmpeg reads and writes (`ffmpeg -i in.mp4 in.y4m`), which makes
 # FrameInterpolator.interpolate_video work on real video files: header line
 # "YUV4MPEG2 W<w> H<h> F<num>:<den> [I<p>] [A<n>:<d>] [C<colourspace>]", then per frame "FRAME\n" + planes.
-def read_y4m(path: str):
-    """-> (y [N, H, W] uint8, chroma or None, fps (num, den), colourspace tag).  `chroma` is a pair of
-    [N, Hc, Wc] uint8 arrays (U, V) for the 4:2:0 / 4:2:2 / 4:4:4 layouts, None for mono."""
-    with open(path, "rb") as f:
-        data = f.read()
+def _y4m_header(data: bytes):
+    """Parse the stream header -> (fields, offset of the first FRAME marker).  fields: width, height, fps (num, den),
+    colourspace (the `C` tag, "420jpeg" when absent), colour_range ("FULL" / "LIMITED" from an `XCOLORRANGE=` token,
+    None when absent), chroma (rows, cols) of each of U and V ((0, 0) for mono), frame_bytes."""
     nl = data.index(b"\n")
     head = data[:nl].split(b" ")
     if head[0] != b"YUV4MPEG2":
         raise ValueError("not a YUV4MPEG2 stream")
     w = h = None
-    fps, cs = (30, 1), "420jpeg"
+    fps, cs, rng = (30, 1), "420jpeg", None
     for tok in head[1:]:
         if tok[:1] == b"W":
             w = int(tok[1:])
@@ -251,6 +250,10 @@ def read_y4m(path: str):
             fps = (int(n), int(d))
         elif tok[:1] == b"C":
             cs = tok[1:].decode()
+        elif tok.startswith(b"XCOLORRANGE="):
+            rng = tok[len(b"XCOLORRANGE="):].decode().upper()
+            if rng not in ("FULL", "LIMITED"):
+                raise ValueError(f"Y4M: unknown XCOLORRANGE={rng}")
     if not w or not h:
         raise ValueError("Y4M header without W/H")
     if cs.startswith("mono"):
@@ -265,9 +268,13 @@ def read_y4m(path: str):
         raise ValueError(f"unsupported Y4M colourspace C{cs}")
     if any(c in cs for c in ("p10", "p12", "p14", "p16", "mono16")):
         raise ValueError(f"unsupported Y4M bit depth C{cs}")
-    fsz = w * h + 2 * cw * ch
-    ys, us, vs = [], [], []
-    pos = nl + 1
+    return dict(width=w, height=h, fps=fps, colourspace=cs, colour_range=rng, chroma=(ch, cw),
+                frame_bytes=w * h + 2 * cw * ch), nl + 1
+
+
+def _y4m_payloads(data: bytes, pos: int, fsz: int) -> list:
+    """Offsets of the frame payloads from `pos` on (each after its FRAME line)."""
+    offs = []
     while pos < len(data):
         e = data.index(b"\n", pos)
         if not data[pos:e].startswith(b"FRAME"):
@@ -275,27 +282,58 @@ def read_y4m(path: str):
         pos = e + 1
         if pos + fsz > len(data):
             raise ValueError("Y4M: truncated frame")
-        fr = np.frombuffer(data, np.uint8, fsz, pos)
+        offs.append(pos)
+        pos += fsz
+    if not offs:
+        raise ValueError("Y4M: no frames")
+    return offs
+
+
+def read_y4m(path: str):
+    """-> (y [N, H, W] uint8, chroma or None, fps (num, den), colourspace tag).  `chroma` is a pair of
+    [N, Hc, Wc] uint8 arrays (U, V) for the 4:2:0 / 4:2:2 / 4:4:4 layouts, None for mono."""
+    with open(path, "rb") as f:
+        data = f.read()
+    hdr, pos = _y4m_header(data)
+    w, h, (ch, cw), fsz = hdr["width"], hdr["height"], hdr["chroma"], hdr["frame_bytes"]
+    ys, us, vs = [], [], []
+    for off in _y4m_payloads(data, pos, fsz):
+        fr = np.frombuffer(data, np.uint8, fsz, off)
         ys.append(fr[:w * h].reshape(h, w))
         if cw:
             us.append(fr[w * h:w * h + cw * ch].reshape(ch, cw))
             vs.append(fr[w * h + cw * ch:].reshape(ch, cw))
-        pos += fsz
-    if not ys:
-        raise ValueError("Y4M: no frames")
     chroma = (np.stack(us), np.stack(vs)) if cw else None
-    return np.stack(ys), chroma, fps, cs
+    return np.stack(ys), chroma, hdr["fps"], hdr["colourspace"]
 
 
-def write_y4m(path: str, y: np.ndarray, chroma=None, fps=(30, 1), colourspace: str = None) -> None:
-    """y: [N, H, W] uint8; chroma: None (-> Cmono) or (U, V) planes as read_y4m returns them."""
+def read_y4m_packed(path: str):
+    """-> (frames [N, frame_bytes] uint8, header fields as `_y4m_header` returns them).  Each row is one frame payload
+    as stored (Y, then U, then V): for 4:2:0 the packed I420 frame that `FrameInterpolationUNet.forward_yuv420` takes."""
+    with open(path, "rb") as f:
+        data = f.read()
+    hdr, pos = _y4m_header(data)
+    fsz = hdr["frame_bytes"]
+    frames = np.stack([np.frombuffer(data, np.uint8, fsz, off) for off in _y4m_payloads(data, pos, fsz)])
+    return frames, hdr
+
+
+def write_y4m(path: str, y: np.ndarray, chroma=None, fps=(30, 1), colourspace: str = None,
+              colour_range: str = None) -> None:
+    """y: [N, H, W] uint8; chroma: None (-> Cmono) or (U, V) planes as read_y4m returns them.  colour_range: None (no
+    XCOLORRANGE token: the header is byte for byte what it always was), "FULL" or "LIMITED"."""
     y = np.ascontiguousarray(y, dtype=np.uint8)
     n, h, w = y.shape
     cs = colourspace or ("mono" if chroma is None else "420jpeg")
     if (chroma is None) != cs.startswith("mono"):
         raise ValueError("chroma planes and colourspace tag disagree")
+    ext = ""
+    if colour_range is not None:
+        if colour_range.upper() not in ("FULL", "LIMITED"):
+            raise ValueError(f"colour_range must be FULL or LIMITED, got {colour_range!r}")
+        ext = f" XCOLORRANGE={colour_range.upper()}"
     with open(path, "wb") as f:
-        f.write(f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{cs}\n".encode())
+        f.write(f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{cs}{ext}\n".encode())
         for i in range(n):
             f.write(b"FRAME\n")
             f.write(y[i].tobytes())

@@ -25,7 +25,7 @@ import torch
 from struct import error as struct_error
 from zlib import error as zlib_error
 
-from . import _native, imageio_lite
+from . import _native, colour, imageio_lite
 from .unet import FrameInterpolationUNet
 
 
@@ -141,23 +141,30 @@ def _forward_u8_chunk(model, a: torch.Tensor, b: torch.Tensor, batch: int, out: 
     or to the full `batch` where even that still splits (256x256 at batch 8): every pair of a sequence is
     computed exactly as in a full batch, the result does not depend on the sequence length or on how the
     sequence is sharded over ranks (`sequence_pair_fn`) - and a one-pair 720p clip costs 5 forwards, not 8."""
+    return _padded_chunk(model, model.forward_u8, a, b, a.shape[-2], a.shape[-1], batch, out)
+
+
+def _padded_chunk(model, fwd, a: torch.Tensor, b: torch.Tensor, h: int, w: int, batch: int,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """`fwd(a, b, out=...)` of one chunk of pairs of h x w frames, a ragged chunk padded as `_forward_u8_chunk` says
+    (the rule is shared by every frame layout: the frames are only ever indexed along dim 0 here)."""
     cnt = a.shape[0]
     target = cnt
     if cnt < batch:
-        bmin = model.batch_invariant_from(a.shape[-2], a.shape[-1], a.device)
+        bmin = model.batch_invariant_from(h, w, a.device)
         target = batch if bmin > batch else max(cnt, bmin)
     if target > cnt:
         rep = [1] * a.dim()
         rep[0] = target - cnt
         a = torch.cat([a, a[-1:].repeat(*rep)])
         b = torch.cat([b, b[-1:].repeat(*rep)])
-        res = model.forward_u8(a, b)[:cnt]
+        res = fwd(a, b)[:cnt]
         if out is not None:
             out.copy_(res)
             return out
         return res
     # `out` (the video loops: every second frame of the interleaved result): the fused head stores each frame in place
-    return model.forward_u8(a, b, out=out)
+    return fwd(a, b, out=out)
 
 
 def sequence_pair_fn(model, batch: int = 8):
@@ -188,6 +195,28 @@ def interpolate_sequence(model, frames_u8: torch.Tensor, batch: int = 8) -> torc
     for s, cnt in _pair_batches(n - 1, batch):   # each middle is written where it belongs (no temporary, no strided copy)
         _forward_u8_chunk(model, fr[s:s + cnt], fr[s + 1:s + cnt + 1], batch, out=out[2 * s + 1: 2 * (s + cnt): 2])
     return out.squeeze(1) if squeeze else out
+
+
+@torch.no_grad()
+def interpolate_sequence_yuv420(model, frames: torch.Tensor, height: int, width: int, batch: int = 8,
+                                **colour) -> torch.Tensor:
+    """factor-2 video loop of the RGB network on colour video: device uint8 [N, F] packed I420 frames of
+    height x width (a Y4M frame payload each) -> [2N-1, F] = F0, M0, F1, ..., F(N-1), where Mi =
+    model.forward_yuv420(Fi, Fi+1, **colour).  The originals are copied byte for byte; each middle is written in
+    place; a ragged last chunk is padded as in `interpolate_sequence`, so the result does not depend on N.
+    colour: siting / matrix / colour_range (colour.py)."""
+    h, w = int(height), int(width)
+    n = frames.shape[0]
+    out = torch.empty((2 * n - 1, frames.shape[1]), dtype=torch.uint8, device=frames.device)
+    out[0::2] = frames
+
+    def fwd(a, b, out=None):
+        return model.forward_yuv420(a, b, h, w, out=out, **colour)
+
+    for s, cnt in _pair_batches(n - 1, batch):
+        _padded_chunk(model, fwd, frames[s:s + cnt], frames[s + 1:s + cnt + 1], h, w, batch,
+                      out=out[2 * s + 1: 2 * (s + cnt): 2])
+    return out
 
 
 @torch.no_grad()
@@ -260,8 +289,9 @@ class FrameInterpolator:
     same shape; colour images are processed per channel with the 2->1 grayscale network unless
     the checkpoint is the 6->3 variant.
     interpolate_video(input_path, output_path, factor=2): raw .npy frame stack or uncompressed
-    YUV4MPEG2 (`.y4m`) video in/out; factor must be a power of two (recursive bisection; factor 2 is the only semantics the
-    reference's flags imply, main.py:57-62)."""
+    YUV4MPEG2 (`.y4m`) video in/out (4:2:0 colour through the RGB network: `interpolate_sequence_yuv420`); factor
+    must be a power of two (recursive bisection; factor 2 is the only semantics the reference's flags imply,
+    main.py:57-62)."""
 
     def __init__(self, model_path=None, device="cuda", precision=None, model=None, batch=8):
         self.device = torch.device("cuda" if device in ("auto", None) else device)
@@ -312,12 +342,44 @@ class FrameInterpolator:
             np.save(output_path, t.cpu().numpy())
         return t.shape[0]
 
-    def interpolate_video(self, input_path, output_path, factor=2):
+    def _interpolate_y4m_colour(self, input_path, output_path, factor, matrix):
+        """4:2:0 YUV4MPEG2 in -> out through the RGB (6->3) network: every frame is converted to planar RGB on the
+        device, the network interpolates all three channels, and the middle frames are converted back
+        (`interpolate_sequence_yuv420`).  Chroma siting from the `C` tag (420jpeg / 420 / none, or 420mpeg2), range
+        from `XCOLORRANGE` (limited when absent); the matrix is not in the container: `matrix`.  The output has the
+        input's tag and range and fps x factor."""
+        if not str(output_path).lower().endswith(".y4m"):
+            raise ValueError("colour Y4M video through the RGB network is written as .y4m (no .npy output)")
+        frames, hdr = imageio_lite.read_y4m_packed(input_path)
+        siting = colour.siting_of_y4m(hdr["colourspace"])   # rejects 422 / 444 / mono / 420paldv before any GPU work
+        opts = dict(siting=siting, matrix=matrix,
+                    colour_range="full" if hdr["colour_range"] == "FULL" else "limited")
+        colour.colour_flags(**opts)   # a bad `matrix` fails here, before any GPU work
+        h, w = hdr["height"], hdr["width"]
+        t = torch.from_numpy(frames).to(self.device)
+        f = factor
+        while f > 1:
+            t = interpolate_sequence_yuv420(self.model, t, h, w, self.batch, **opts)
+            f //= 2
+        res = t.cpu().numpy()
+        (hc, wc), ny = hdr["chroma"], h * w
+        u = res[:, ny:ny + hc * wc].reshape(-1, hc, wc)
+        v = res[:, ny + hc * wc:].reshape(-1, hc, wc)
+        imageio_lite.write_y4m(output_path, res[:, :ny].reshape(-1, h, w), (u, v),
+                               (hdr["fps"][0] * factor, hdr["fps"][1]), hdr["colourspace"],
+                               colour_range=hdr["colour_range"])
+        return res.shape[0]
+
+    def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709"):
+        """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video, or
+        "bt601"; the container does not carry it).  The grayscale network's Y4M path does not use it."""
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Video file not found: {input_path}")
         if str(input_path).lower().endswith(".y4m"):
+            if self.model.frame_channels == 3:
+                return self._interpolate_y4m_colour(input_path, output_path, factor, matrix)
             return self._interpolate_y4m(input_path, output_path, factor)
         frames = np.load(input_path)
         if frames.dtype != np.uint8 or frames.ndim not in (3, 4):

@@ -252,10 +252,10 @@ class FrameInterpolationUNet(nn.Module):
             self._weights_gen += 1
         return self._ctx
 
-    def _workspace(self, ctx, device, b, h, w, prec, u8=False):
+    def _workspace(self, ctx, device, b, h, w, prec, u8=False, yuv=False):
         """One scratch block, kept at the largest size any call has needed (a smaller batch or the
         ragged last chunk of a video reuses it instead of freeing and reallocating gigabytes)."""
-        nbytes = ctx.workspace_bytes(b, h, w, prec, u8)
+        nbytes = ctx.workspace_bytes(b, h, w, prec, u8, yuv)
         if self._ws is None or self._ws.device != device or self._ws.numel() < nbytes:
             self._ws = None  # release before allocating the next one
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -276,6 +276,9 @@ class FrameInterpolationUNet(nn.Module):
         if frame1.shape[1] != self.frame_channels:
             raise RuntimeError(
                 f"expected {self.frame_channels} channel(s) per frame, got {frame1.shape[1]}")
+        self._check_device_mode_dtype(frame1, frame2, dtype_ok)
+
+    def _check_device_mode_dtype(self, frame1, frame2, dtype_ok):
         if not frame1.is_cuda or not frame2.is_cuda:
             raise RuntimeError(
                 "FrameInterpolationUNet (MI355X build) runs only on a HIP device: move the model "
@@ -344,6 +347,40 @@ class FrameInterpolationUNet(nn.Module):
             raise ValueError(f"out must be a uint8 {tuple(f1.shape)} tensor on {f1.device}")
         with torch.cuda.device(f1.device):
             ctx.forward_u8(f1, f2, out, prec, ws)
+        return out
+
+    @torch.no_grad()
+    def forward_yuv420(self, frame1: torch.Tensor, frame2: torch.Tensor, height: int, width: int, *,
+                       siting: str = "jpeg", matrix: str = "bt709", colour_range: str = "limited",
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+        """The RGB network on colour video: uint8 [B, F] packed I420 frames in (F = H*W + 2*ceil(H/2)*ceil(W/2), a Y4M
+        frame payload) -> uint8 [B, F] interpolated frames, `fiunet_forward_yuv420`: YUV -> planar RGB, `forward_u8`,
+        RGB -> YUV, all on device in the integer conversion of csrc/colour.hip.h.  siting / matrix / colour_range: see
+        colour.py (matrix defaults to "bt709", a convention for HD video: Y4M does not carry it).  `out`: write there -
+        uint8 [B, F] on the same device, every frame contiguous; the frames may lie apart (the video loop passes every
+        second frame of its interleaved result)."""
+        from .colour import colour_flags, i420_frame_bytes
+        flags = colour_flags(siting, matrix, colour_range)
+        if self.frame_channels != 3:
+            raise RuntimeError("forward_yuv420 runs the RGB network (frame_channels=3); this model is grayscale")
+        h, w = int(height), int(width)
+        fb = i420_frame_bytes(h, w)
+        if frame1.dim() != 2 or frame1.shape != frame2.shape or frame1.shape[1] != fb:
+            raise RuntimeError(f"expected two [B,{fb}] tensors (packed I420 frames of {h}x{w}) of equal shape, got "
+                               f"{tuple(frame1.shape)} and {tuple(frame2.shape)}")
+        self._check_device_mode_dtype(frame1, frame2, (torch.uint8,))
+        f1, f2 = frame1.contiguous(), frame2.contiguous()
+        b = f1.shape[0]
+        prec = self._precision_code()
+        ctx = self._context(f1.device)
+        ws = self._workspace(ctx, f1.device, b, h, w, prec, yuv=True)
+        if out is None:
+            out = torch.empty_like(f1)
+        elif (out.dtype != torch.uint8 or out.shape != f1.shape or out.device != f1.device
+              or out.stride(1) != 1 or (b > 1 and out.stride(0) < fb)):
+            raise ValueError(f"out must be a uint8 {tuple(f1.shape)} tensor on {f1.device} whose frames are contiguous")
+        with torch.cuda.device(f1.device):
+            ctx.forward_yuv420(f1, f2, out, h, w, flags, prec, ws)
         return out
 
     @torch.no_grad()

@@ -21,7 +21,8 @@
 extern "C" {
 #endif
 
-#define FIUNET_ABI_VERSION 5   /* 4: fiunet_prepare_precision; fiunet_debug_read_activation takes the capacity of dst; 5: fiunet_forward_u8_strided */
+#define FIUNET_ABI_VERSION 6   /* 4: fiunet_prepare_precision; fiunet_debug_read_activation takes the capacity of dst; 5: fiunet_forward_u8_strided;
+                                  6: YUV 4:2:0 colour video (fiunet_yuv420_to_rgb_u8, fiunet_rgb_to_yuv420_u8, fiunet_forward_yuv420) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -164,6 +165,41 @@ int fiunet_forward_u8(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* fra
 int fiunet_forward_u8_strided(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
                               size_t out_image_stride, int B, int H, int W, int precision, void* workspace,
                               size_t workspace_bytes, void* stream);
+
+/* Colour video for the RGB (frame_channels == 3) network.  The reference has no colour path; these entry points link
+ * the container a decoder gives (YUV 4:2:0, `ffmpeg -i in.mp4 -pix_fmt yuv420p in.y4m`) to the planar RGB network.
+ * A frame is packed I420, exactly a Y4M frame payload: the Y plane H x W, then U, then V, each ceil(H/2) x ceil(W/2)
+ * bytes (fiunet frame size F = H*W + 2*ceil(H/2)*ceil(W/2)).  The conversion is defined in integer arithmetic
+ * (csrc/colour.hip.h, DESIGN.md "Colour video"), so it is the same bits on every device.  `colour` is a set of flags;
+ * 0 = jpeg siting (also Y4M `420` / no tag), BT.601, limited range; any other bit is FIUNET_ERR_INVALID_ARG. */
+enum fiunet_colour {
+    FIUNET_YUV_MPEG2 = 1,      /* chroma siting 420mpeg2: co-sited with the even luma column, centred vertically
+                                  (default: 420jpeg, centred in its 2x2 luma block) */
+    FIUNET_YUV_BT709 = 2,      /* matrix BT.709 (Kr 0.2126, Kb 0.0722); default BT.601 (Kr 0.299, Kb 0.114) */
+    FIUNET_YUV_FULL_RANGE = 4  /* Y 0-255, C = 128 + 255 E'P; default limited: Y 16-235, C 16-240 */
+};
+
+/* Packed I420 frames (`in_frame_stride` bytes apart, 0 = F) -> planar RGB uint8 [B, 3, H, W] (the layout
+ * fiunet_forward_u8 takes for frame_channels == 3).  Device pointers; any H, W >= 1 (odd sizes included).
+ * Asynchronous on `stream`; no allocation, no synchronisation. */
+int fiunet_yuv420_to_rgb_u8(const uint8_t* in, size_t in_frame_stride, uint8_t* out, int B, int H, int W,
+                            unsigned colour, void* stream);
+/* The inverse: planar RGB uint8 [B, 3, H, W] -> packed I420 frames `out_frame_stride` bytes apart (0 = F; bytes
+ * between frames are left untouched). */
+int fiunet_rgb_to_yuv420_u8(const uint8_t* in, uint8_t* out, size_t out_frame_stride, int B, int H, int W,
+                            unsigned colour, void* stream);
+/* Workspace of fiunet_forward_yuv420: fiunet_workspace_bytes_u8 plus three planar RGB batches; 0 on bad arguments
+ * (query it after fiunet_set_options). */
+size_t fiunet_workspace_bytes_yuv420(const fiunet_ctx* ctx, int B, int H, int W, int precision);
+/* The video-path forward on packed I420 frames: frame1, frame2 are B frames of F bytes each, contiguous; the B
+ * interpolated frames go to `out`, `out_frame_stride` bytes apart (0 = F; the video loop hands over every second frame
+ * of its interleaved result).  Three steps in the caller's workspace: fiunet_yuv420_to_rgb_u8 of both inputs,
+ * fiunet_forward_u8_strided into a planar RGB buffer, fiunet_rgb_to_yuv420_u8 into `out` - bit for bit the chain of
+ * those public calls.  FIUNET_ERR_UNSUPPORTED on a context with frame_channels != 3.  Neither allocates nor
+ * synchronises: it captures into a graph as fiunet_forward_u8 does. */
+int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
+                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* Replaces preprocess_image's arithmetic (model/inference.py:31-35): out = 2*(in/255) - 1. */
 int fiunet_preprocess_u8(const uint8_t* in, float* out, size_t n, void* stream);
