@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- interpolated frames/s of the MI355X UNet frame-pair forward.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 Both forms work for N > 1: started WITHOUT a launcher (no WORLD_SIZE in the environment), `--gpus N` makes this
@@ -17,10 +17,16 @@ so the same arguments give the same inputs on every run; `--dump-outputs DIR` wr
 output of the last timed step there (`dump_outputs`), so that two builds can be compared output
 for output.
 
-Extra objects on that line:
+A plain run does only what that line's headline needs: it sets up, warms up, times the steps, dumps if asked and
+prints the line, which carries beside the headline fields (and `dumped_outputs`)
   roofline      -- dominant kernel (by time) of the forward: algorithmic FLOPs per launch / its
                    average launch duration, measured live with HIP events recorded on the launch
-                   stream between the stages (fiunet_profile_*), vs the dense MFMA peak.
+                   stream between the stages (fiunet_profile_*) of the timed steps themselves, vs the
+                   dense MFMA peak.
+`--full` adds every other leg below, each measured after the timed steps, never inside them;
+`--no-cpu-baseline`, `--no-fp32`, `--no-tile4k`, `--no-power` and `--video-frames` choose among those legs.
+
+Objects that `--full` adds to that line:
   cpu_baseline  -- the PyTorch-CPU oracle (a port of the reference's forward, pinned to reference
                    outputs) timed on this box's host cores: 1080p (1 warm-up + median of 3) and
                    BASELINE configs[0] (one 256x256 pair, 3 warm-up + 10 timed, median), thread
@@ -38,6 +44,8 @@ Extra objects on that line:
                    tiling.forward_tiled_distributed (uint8 on the wire); N = 1: the un-tiled pair, the four
                    config-5 bands each and back to back, tiled == un-tiled.
                    video_sharded also carries the HOST-resident (PCIe-inclusive) rate at N = 1.
+  rgb_6to3, fp32_contract_on_bf16_pipe, latency_256, power -- N = 1: see rgb_leg, bf16x2_leg,
+                   small_frames_leg and power_leg.
 The oracle is only the baseline/checker here; the measured path never touches it.
 """
 from __future__ import annotations
@@ -563,8 +571,11 @@ def main():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--unfused", action="store_true", help="ablation: separate pool/upsample/head kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg: CPU baseline and parity, fp32 / bf16x2 / "
+                         "RGB / 256x256 figures, power, the video and 4K tiling legs (default: the headline only)")
     ap.add_argument("--video-frames", type=int, default=-1,
-                    help="frames of the config-4 video leg (default 3000 = BASELINE configs[3]; 0 = skip)")
+                    help="frames of the config-4 video leg of --full (default 3000 = BASELINE configs[3]; 0 = skip)")
     ap.add_argument("--no-tile4k", action="store_true")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 legs (A/B runs)")
     ap.add_argument("--no-power", action="store_true", help="skip the rocm-smi power / clock sample")
@@ -576,6 +587,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if args.video_frames > 0 and not args.full:
+        ap.error("--video-frames sizes a leg of --full: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))   # no launcher around us: be one (no GPU call so far, none in there)
@@ -666,8 +679,9 @@ def main():
     default_workload = (b, h, w, args.precision, args.unfused) == (8, 1080, 1920, "bf16", False)
     power = None
 
+    # ---- everything below the timed steps runs with --full only: a plain run dumps and prints the headline ----
     # ---- config 4 / config 5 legs (every rank takes part; bounded, failures are reported) ----
-    n_video = args.video_frames if args.video_frames >= 0 else (3000 if default_workload else 0)
+    n_video = (args.video_frames if args.video_frames >= 0 else (3000 if default_workload else 0)) if args.full else 0
     video_res = tile_res = None
     if n_video >= 2:
         with _quiet_native_stdout():
@@ -681,12 +695,12 @@ def main():
                                               video_res, None, None, None, dumped=dumped)))
                     sys.stdout.flush()
                 os._exit(3)  # the headline is printed, but a hung leg must show in the return code
-    if world == 1 and default_workload and not args.no_tile4k:
+    if args.full and world == 1 and default_workload and not args.no_tile4k:
         with _quiet_native_stdout():
             tile_res, err = _run_bounded(lambda: tile4k_single_gpu_leg(model, dev), 120.0)
         if err:
             tile_res = {"error": err, "strips": 4}
-    if dist is not None and world >= 2 and default_workload and not args.no_tile4k:
+    if args.full and dist is not None and world >= 2 and default_workload and not args.no_tile4k:
         with _quiet_native_stdout():
             tile_res, err = _run_bounded(lambda: tile4k_leg(model, dev, dist, rank, world, 10), 120.0)
         if err:
@@ -701,7 +715,7 @@ def main():
     # (after the config-4 / config-5 legs since round 6: four seconds of back-to-back forwards right before the 5.7-s video
     # leg heat-soaked the chip it was then compared on - on a warm box the video rate read 3-4 % under `value` while the
     # host-resident variant, which starts after seconds of host-side staging, did not)
-    if world == 1 and default_workload and not args.no_power:
+    if args.full and world == 1 and default_workload and not args.no_power:
         try:
             power = power_leg(model, f1, f2, dev)
         except Exception as e:  # an extra leg must never cost the headline line
@@ -714,7 +728,7 @@ def main():
         return
 
     cpu_baseline = parity = fp32 = rgb = x2 = None
-    if world == 1 and default_workload and not args.no_fp32:
+    if args.full and world == 1 and default_workload and not args.no_fp32:
         try:
             rgb = rgb_leg(dev, with_oracle=not args.no_cpu_baseline)
         except Exception as e:  # an extra leg must never cost the headline line
@@ -723,18 +737,18 @@ def main():
             x2 = bf16x2_leg(dev, with_oracle=not args.no_cpu_baseline)
         except Exception as e:
             x2 = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and default_workload and not args.no_fp32:
+    if args.full and world == 1 and default_workload and not args.no_fp32:
         try:
             fp32 = fp32_legs(dev)
         except Exception as e:  # an extra leg must never cost the headline line
             fp32 = {"error": f"{type(e).__name__}: {e}"}
     small = None
-    if world == 1 and default_workload and not args.no_fp32:
+    if args.full and world == 1 and default_workload and not args.no_fp32:
         try:
             small = small_frames_leg(dev)
         except Exception as e:  # an extra leg must never cost the headline line
             small = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu_baseline, parity = cpu_legs(dev, args.precision)
     print(json.dumps(headline(args, world, elapsed, rows, nfw, default_workload, video_res, tile_res,
                               cpu_baseline, parity, fp32, power, rgb, x2, small, dumped)))

@@ -68,3 +68,34 @@ def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
     f2 = torch.rand(b, 1, h, w, device=dev, generator=gen) * 2 - 1
     want = model(f1, f2).cpu().numpy()
     assert got.dtype == np.float32 and np.array_equal(got, want)
+
+
+def test_bench_video_frames_needs_full():
+    """The video leg belongs to --full: sizing it on a plain run is an argument error, not a silent no-op."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--video-frames", "9"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr and not r.stdout.strip(), (r.returncode, r.stdout, r.stderr[-500:])
+
+
+# objects only `--full` puts on the line: a plain run measures nothing beyond its timed steps
+FULL_ONLY = ("cpu_baseline", "parity", "fp32", "rgb_6to3", "fp32_contract_on_bf16_pipe", "latency_256", "power",
+             "video_sharded", "video_sharded_efficiency", "tile4k")
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_only():
+    """The default workload without --full: one JSON line with the headline and the roofline of the timed steps,
+    and none of the legs --full adds."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["metric"] == "interpolated frames/sec at 1080p" and d["unit"] == "frames/s" and d["dtype"] == "bf16"
+    assert d["higher_is_better"] is True and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 8e3 / d["ms_per_step"]) <= 0.01 * d["value"]   # 8 frame pairs per step
+    assert d["roofline"]["events_forwards"] == 2 and len(d["roofline"]["stages"]) > 0
+    assert not [k for k in FULL_ONLY if k in d], sorted(d)

@@ -162,7 +162,7 @@ def test_bench_gpus_2_self_launches_on_one_card():
     env["FIUNET_BENCH_REHEARSE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--batch", "2", "--height", "360", "--width", "640", "--no-cpu-baseline", "--no-power",
-                        "--no-fp32", "--video-frames", "9"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-fp32", "--full", "--video-frames", "9"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -185,7 +185,7 @@ def test_bench_under_torch_distributed_run_one_rccl_rank():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
                         "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "360", "--width", "640",
-                        "--no-cpu-baseline", "--no-power", "--no-fp32", "--video-frames", "9"],
+                        "--no-cpu-baseline", "--no-power", "--no-fp32", "--full", "--video-frames", "9"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]

@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out/full
 O=gpurun_out/full
 timeout -k 10 1100 python -m pytest tests -q -m gpu -x > $O/gpu_tests.log 2>&1 || { tail -40 $O/gpu_tests.log; exit 1; }
 tail -3 $O/gpu_tests.log
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/full/bench_default.json").read().strip().splitlines()[-1])
