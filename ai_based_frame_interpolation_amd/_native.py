@@ -21,12 +21,12 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FIUNET_LIB") or os.path.join(_PKG, "libfiunet_hip.so")  # FIUNET_LIB: A/B builds
 CSRC = os.path.join(_PKG, "csrc")
 
-ABI_VERSION = 6        # include/fiunet.h FIUNET_ABI_VERSION this binding is written for
+ABI_VERSION = 7        # include/fiunet.h FIUNET_ABI_VERSION this binding is written for
 ABI_MIN_COMPAT = 4     # oldest A/B library (FIUNET_LIB) whose shared entry points have today's signatures
 FP32, BF16, BF16X2 = 0, 1, 2   # include/fiunet.h: enum fiunet_precision
 OPT_UNFUSED, OPT_KEEP_ALL, OPT_GATHER_UPSAMPLE = 1, 2, 16
 OPT_RNE_WEIGHTS, OPT_NO_DITHER = 32, 64
-YUV_MPEG2, YUV_BT709, YUV_FULL_RANGE = 1, 2, 4   # include/fiunet.h: enum fiunet_colour
+YUV_MPEG2, YUV_BT709, YUV_FULL_RANGE, YUV_BT2020 = 1, 2, 4, 8   # include/fiunet.h: enum fiunet_colour
 
 #: every symbol include/fiunet.h declares (tests/test_abi.py checks the header against this)
 SYMBOLS = (
@@ -39,6 +39,9 @@ SYMBOLS = (
     "fiunet_profile_read", "fiunet_metrics_workspace_bytes", "fiunet_psnr_u8", "fiunet_ssim_u8",
     "fiunet_ssim_gauss_workspace_bytes", "fiunet_ssim_gauss_f32",
     "fiunet_yuv420_to_rgb_u8", "fiunet_rgb_to_yuv420_u8", "fiunet_workspace_bytes_yuv420", "fiunet_forward_yuv420",
+    "fiunet_preprocess_p10", "fiunet_postprocess_p10", "fiunet_workspace_bytes_p10", "fiunet_forward_p10",
+    "fiunet_yuv420p10_to_rgb_p10", "fiunet_rgb_p10_to_yuv420p10", "fiunet_workspace_bytes_yuv420p10",
+    "fiunet_forward_yuv420p10",
 )
 
 _lib = None
@@ -114,6 +117,16 @@ def lib() -> ctypes.CDLL:
     L.fiunet_workspace_bytes_yuv420.restype = sz
     L.fiunet_forward_yuv420.argtypes = [vp, vp, vp, vp, sz, ci, ci, ci, cu, ci, vp, sz, vp]
     L.fiunet_postprocess_u8.argtypes = [vp, vp, sz, vp]
+    L.fiunet_preprocess_p10.argtypes = [vp, vp, sz, vp]
+    L.fiunet_postprocess_p10.argtypes = [vp, vp, sz, vp]
+    L.fiunet_workspace_bytes_p10.argtypes = [vp, ci, ci, ci, ci]
+    L.fiunet_workspace_bytes_p10.restype = sz
+    L.fiunet_forward_p10.argtypes = [vp, vp, vp, vp, sz, ci, ci, ci, ci, vp, sz, vp]
+    L.fiunet_yuv420p10_to_rgb_p10.argtypes = [vp, sz, vp, ci, ci, ci, cu, vp]
+    L.fiunet_rgb_p10_to_yuv420p10.argtypes = [vp, vp, sz, ci, ci, ci, cu, vp]
+    L.fiunet_workspace_bytes_yuv420p10.argtypes = [vp, ci, ci, ci, ci]
+    L.fiunet_workspace_bytes_yuv420p10.restype = sz
+    L.fiunet_forward_yuv420p10.argtypes = [vp, vp, vp, vp, sz, ci, ci, ci, cu, ci, vp, sz, vp]
     L.fiunet_debug_read_activation.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz,
                                                ctypes.POINTER(ci), vp]
     L.fiunet_metrics_workspace_bytes.argtypes = [ci, ci, ci]
@@ -206,11 +219,15 @@ class Context:
             check(lib().fiunet_prepare_precision(self._h, precision), "fiunet_prepare_precision")
             self._prepared.add(precision)
 
-    def workspace_bytes(self, b, h, w, precision, u8=False, yuv=False) -> int:
-        """yuv: fiunet_forward_yuv420's workspace (u8: fiunet_forward_u8's; neither: fiunet_forward's)."""
+    def workspace_bytes(self, b, h, w, precision, u8=False, yuv=False, p10=False) -> int:
+        """yuv: fiunet_forward_yuv420's workspace (u8: fiunet_forward_u8's; neither: fiunet_forward's); with p10 the
+        10-bit entry points' (fiunet_forward_yuv420p10 / fiunet_forward_p10)."""
         self.prepare(precision)   # every forward path sizes its workspace first
-        fn = (lib().fiunet_workspace_bytes_yuv420 if yuv else
-              lib().fiunet_workspace_bytes_u8 if u8 else lib().fiunet_workspace_bytes)
+        if p10:
+            fn = lib().fiunet_workspace_bytes_yuv420p10 if yuv else lib().fiunet_workspace_bytes_p10
+        else:
+            fn = (lib().fiunet_workspace_bytes_yuv420 if yuv else
+                  lib().fiunet_workspace_bytes_u8 if u8 else lib().fiunet_workspace_bytes)
         n = fn(self._h, b, h, w, precision)
         if n == 0:
             if h < 16 or w < 16:
@@ -269,6 +286,33 @@ class Context:
         check(lib().fiunet_forward_yuv420(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), st, b, h, w, colour,
                                           precision, workspace.data_ptr(), workspace.numel(), s),
               "fiunet_forward_yuv420")
+
+    def forward_p10(self, f1, f2, out, precision, workspace, stream=None):
+        """10-bit frames: uint16 [B, C, H, W] contiguous in; `out` uint16 [B, C, H, W] whose images are contiguous and
+        may lie further apart (every second frame of the video loop's interleaved result).  Strides in samples."""
+        b, c, h, w = f1.shape
+        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        image_stride = 0   # contiguous
+        if not out.is_contiguous():
+            st = out.stride()
+            # (the stride of a size-1 dim is arbitrary: a one-channel image is contiguous whatever st[1] says)
+            if (c > 1 and st[1] != h * w) or tuple(st[2:]) != (w, 1) or (b > 1 and st[0] < c * h * w):
+                raise ValueError(f"out: every image must be contiguous (strides {tuple(st)} for shape "
+                                 f"{tuple(out.shape)})")
+            image_stride = st[0] if b > 1 else 0
+        check(lib().fiunet_forward_p10(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), image_stride, b, h,
+                                       w, precision, workspace.data_ptr(), workspace.numel(), s),
+              "fiunet_forward_p10")
+
+    def forward_yuv420p10(self, f1, f2, out, h, w, colour, precision, workspace, stream=None):
+        """f1, f2: uint16 [B, F] packed 4:2:0 10-bit frames, contiguous; `out`: uint16 [B, F] whose rows are contiguous
+        and may lie further apart.  Strides in samples."""
+        b = f1.shape[0]
+        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        st = out.stride(0) if b > 1 else out.shape[1]
+        check(lib().fiunet_forward_yuv420p10(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), st, b, h, w,
+                                             colour, precision, workspace.data_ptr(), workspace.numel(), s),
+              "fiunet_forward_yuv420p10")
 
     def profile_enable(self, on: bool):
         check(lib().fiunet_profile_enable(self._h, 1 if on else 0), "fiunet_profile_enable")
@@ -334,3 +378,40 @@ def rgb_to_yuv420_u8(rgb: "torch.Tensor", out: "torch.Tensor", colour: int) -> N
     s = torch.cuda.current_stream(rgb.device).cuda_stream
     check(lib().fiunet_rgb_to_yuv420_u8(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s),
           "fiunet_rgb_to_yuv420_u8")
+
+
+def preprocess_p10(src: "torch.Tensor") -> "torch.Tensor":
+    """fiunet_preprocess_p10: uint16 10-bit codes (contiguous) -> fp32 x / 1023 * 2 - 1, same shape."""
+    out = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    s = torch.cuda.current_stream(src.device).cuda_stream
+    check(lib().fiunet_preprocess_p10(src.data_ptr(), out.data_ptr(), src.numel(), s), "fiunet_preprocess_p10")
+    return out
+
+
+def postprocess_p10(src_f32: "torch.Tensor") -> "torch.Tensor":
+    """fiunet_postprocess_p10: fp32 (contiguous) -> uint16 trunc(clamp((t + 1) / 2, 0, 1) * 1023), same shape."""
+    out = torch.empty(src_f32.shape, dtype=torch.uint16, device=src_f32.device)
+    s = torch.cuda.current_stream(src_f32.device).cuda_stream
+    check(lib().fiunet_postprocess_p10(src_f32.data_ptr(), out.data_ptr(), src_f32.numel(), s),
+          "fiunet_postprocess_p10")
+    return out
+
+
+def yuv420p10_to_rgb_p10(frames: "torch.Tensor", out: "torch.Tensor", h: int, w: int, colour: int) -> None:
+    """fiunet_yuv420p10_to_rgb_p10: uint16 [B, F] packed 4:2:0 (rows contiguous, any row stride) -> uint16
+    [B, 3, h, w]."""
+    b = frames.shape[0]
+    st = frames.stride(0) if b > 1 else frames.shape[1]
+    s = torch.cuda.current_stream(frames.device).cuda_stream
+    check(lib().fiunet_yuv420p10_to_rgb_p10(frames.data_ptr(), st, out.data_ptr(), b, h, w, colour, s),
+          "fiunet_yuv420p10_to_rgb_p10")
+
+
+def rgb_p10_to_yuv420p10(rgb: "torch.Tensor", out: "torch.Tensor", colour: int) -> None:
+    """fiunet_rgb_p10_to_yuv420p10: uint16 [B, 3, h, w] contiguous -> uint16 [B, F] (rows contiguous, any row
+    stride)."""
+    b, _, h, w = rgb.shape
+    st = out.stride(0) if b > 1 else out.shape[1]
+    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    check(lib().fiunet_rgb_p10_to_yuv420p10(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s),
+          "fiunet_rgb_p10_to_yuv420p10")

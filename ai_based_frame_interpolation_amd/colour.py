@@ -6,10 +6,14 @@ conversion.  The conversion is defined in integer arithmetic (csrc/colour.hip.h,
 in HIP kernels (`fiunet_yuv420_to_rgb_u8`, `fiunet_rgb_to_yuv420_u8`); the network's forward between them is
 `FrameInterpolationUNet.forward_yuv420`.
 
+10-bit video (`C420p10` Y4M: every sample a 10-bit code in a little-endian 16-bit word) has the same layout in uint16
+samples: `yuv420p10_to_rgb` / `rgb_to_yuv420p10` and `FrameInterpolationUNet.forward_yuv420p10`.
+
 Options (the keywords of every colour entry point):
   siting        "jpeg" (Y4M C420jpeg, C420 or no tag: chroma centred in its 2x2 luma block) or "mpeg2" (C420mpeg2:
                 co-sited with the even luma column, centred vertically)
-  matrix        "bt709" (the default: the inputs are HD video; Y4M does not carry the matrix) or "bt601"
+  matrix        "bt709" (the default: the inputs are HD video; Y4M does not carry the matrix) or "bt601"; for 10-bit
+                video also "bt2020" (non-constant luminance, the matrix of HDR10 / HLG content)
   colour_range  "limited" (Y 16-235, C 16-240; the default, and what a Y4M header without XCOLORRANGE means) or "full"
 """
 from __future__ import annotations
@@ -20,24 +24,34 @@ from . import _native
 
 SITINGS = {"jpeg": 0, "mpeg2": _native.YUV_MPEG2}
 MATRICES = {"bt601": 0, "bt709": _native.YUV_BT709}
+MATRICES_P10 = dict(MATRICES, bt2020=_native.YUV_BT2020)   # BT.2020 defines 10- and 12-bit coding only
 RANGES = {"limited": 0, "full": _native.YUV_FULL_RANGE}
 
 #: Y4M colourspace tags the RGB network reads, and the chroma siting each one means
 Y4M_SITING = {"420jpeg": "jpeg", "420": "jpeg", "420mpeg2": "mpeg2"}
 
 
-def colour_flags(siting: str = "jpeg", matrix: str = "bt709", colour_range: str = "limited") -> int:
-    """-> the `colour` flags word of the C ABI (include/fiunet.h, enum fiunet_colour)."""
-    for name, value, table in (("siting", siting, SITINGS), ("matrix", matrix, MATRICES),
+def colour_flags(siting: str = "jpeg", matrix: str = "bt709", colour_range: str = "limited", bits: int = 8) -> int:
+    """-> the `colour` flags word of the C ABI (include/fiunet.h, enum fiunet_colour).  bits: 8 or 10, the sample depth
+    of the entry point the flags go to; matrix "bt2020" is valid with 10 only."""
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+    matrices = MATRICES_P10 if bits == 10 else MATRICES
+    for name, value, table in (("siting", siting, SITINGS), ("matrix", matrix, matrices),
                                ("colour_range", colour_range, RANGES)):
         if value not in table:
-            raise ValueError(f"{name} must be one of {sorted(table)}, got {value!r}")
-    return SITINGS[siting] | MATRICES[matrix] | RANGES[colour_range]
+            raise ValueError(f"{name} must be one of {sorted(table)} for {bits}-bit video, got {value!r}")
+    return SITINGS[siting] | matrices[matrix] | RANGES[colour_range]
 
 
 def i420_frame_bytes(height: int, width: int) -> int:
     """Bytes of one packed I420 frame: H*W + 2 * ceil(H/2) * ceil(W/2)."""
     return height * width + 2 * ((height + 1) // 2) * ((width + 1) // 2)
+
+
+def yuv420p10_frame_samples(height: int, width: int) -> int:
+    """Samples (uint16 words) of one packed 4:2:0 10-bit frame: H*W + 2 * ceil(H/2) * ceil(W/2)."""
+    return i420_frame_bytes(height, width)
 
 
 def siting_of_y4m(colourspace: str) -> str:
@@ -49,11 +63,12 @@ def siting_of_y4m(colourspace: str) -> str:
                          f"video tagged {', '.join('C' + t for t in Y4M_SITING)} or untagged") from None
 
 
-def _check_frames(frames: torch.Tensor, height: int, width: int, what: str) -> None:
+def _check_frames(frames: torch.Tensor, height: int, width: int, what: str, dtype=torch.uint8) -> None:
     fb = i420_frame_bytes(height, width)
-    if frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[1] != fb:
-        raise ValueError(f"{what} must be uint8 [B, {fb}] packed I420 frames of {height}x{width}, "
-                         f"got {frames.dtype} {tuple(frames.shape)}")
+    if frames.dtype != dtype or frames.dim() != 2 or frames.shape[1] != fb:
+        kind = "I420" if dtype == torch.uint8 else "4:2:0 10-bit"
+        raise ValueError(f"{what} must be {str(dtype).split('.')[-1]} [B, {fb}] packed {kind} frames of "
+                         f"{height}x{width}, got {frames.dtype} {tuple(frames.shape)}")
     if not frames.is_cuda:
         raise RuntimeError(f"{what} must be on the GPU: there is no CPU path in this package")
     if frames.shape[0] > 1 and (frames.stride(1) != 1 or frames.stride(0) < fb):
@@ -95,4 +110,45 @@ def rgb_to_yuv420(rgb: torch.Tensor, *, siting: str = "jpeg", matrix: str = "bt7
     _check_frames(out, h, w, "out")
     with torch.cuda.device(rgb.device):
         _native.rgb_to_yuv420_u8(rgb, out, flags)
+    return out
+
+
+@torch.no_grad()
+def yuv420p10_to_rgb(frames: torch.Tensor, height: int, width: int, *, siting: str = "jpeg", matrix: str = "bt709",
+                     colour_range: str = "limited", out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint16 [B, F] packed 4:2:0 10-bit frames on the GPU -> uint16 planar RGB [B, 3, H, W] of 10-bit codes
+    (`fiunet_yuv420p10_to_rgb_p10`).  Samples above 1023 are read as 1023."""
+    flags = colour_flags(siting, matrix, colour_range, bits=10)
+    _check_frames(frames, height, width, "frames", torch.uint16)
+    shape = (frames.shape[0], 3, height, width)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint16, device=frames.device)
+    elif out.dtype != torch.uint16 or tuple(out.shape) != shape or out.device != frames.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint16 {shape} tensor on {frames.device}")
+    with torch.cuda.device(frames.device):
+        _native.yuv420p10_to_rgb_p10(frames, out, height, width, flags)
+    return out
+
+
+@torch.no_grad()
+def rgb_to_yuv420p10(rgb: torch.Tensor, *, siting: str = "jpeg", matrix: str = "bt709", colour_range: str = "limited",
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint16 planar RGB [B, 3, H, W] of 10-bit codes on the GPU -> uint16 [B, F] packed 4:2:0 10-bit frames
+    (`fiunet_rgb_p10_to_yuv420p10`).  `out` may be a view whose frames lie further apart than F samples; the samples
+    between them are left untouched."""
+    flags = colour_flags(siting, matrix, colour_range, bits=10)
+    if rgb.dtype != torch.uint16 or rgb.dim() != 4 or rgb.shape[1] != 3:
+        raise ValueError(f"rgb must be uint16 [B, 3, H, W], got {rgb.dtype} {tuple(rgb.shape)}")
+    if not rgb.is_cuda:
+        raise RuntimeError("rgb must be on the GPU: there is no CPU path in this package")
+    b, _, h, w = rgb.shape
+    if not rgb.is_contiguous():
+        raise ValueError("rgb must be contiguous")
+    if out is None:
+        out = torch.empty((b, yuv420p10_frame_samples(h, w)), dtype=torch.uint16, device=rgb.device)
+    elif out.device != rgb.device or out.shape[0] != b:
+        raise ValueError(f"out must hold {b} frames on {rgb.device}")
+    _check_frames(out, h, w, "out", torch.uint16)
+    with torch.cuda.device(rgb.device):
+        _native.rgb_p10_to_yuv420p10(rgb, out, flags)
     return out

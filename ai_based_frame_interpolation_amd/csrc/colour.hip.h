@@ -4,13 +4,22 @@
 //                          frames `in_stride` bytes apart: a Y4M frame payload) -> planar RGB uint8 [B,3,H,W],
 //                          the layout fiunet_forward_u8 takes for frame_channels == 3
 //   rgb_to_yuv420_kernel : the inverse, writing packed I420 frames `out_stride` bytes apart
+//   the 10-bit kernels (yuv420p10_to_rgb / rgb_to_yuv420p10) are the same two templates on uint16 samples
+//                          (<uint16_t, VEC>): 10-bit codes in uint16 words, a C420p10 Y4M frame payload, strides counted
+//                          in samples, and planar RGB uint16, the layout fiunet_forward_p10 takes.  The template
+//                          parameter is the sample type (ColourSample); the uint8_t instantiations compile to the
+//                          instructions the 8-bit kernels had before it (only the symbol name changed).
 //
 // The reference has no colour path, so the conversion is defined here, in integer arithmetic, so that the device
 // and a numpy restatement (tests/colour_ref.py) agree bit for bit.  S = 2^14.
 //
-//   matrix   BT.601 (Kr 0.299, Kb 0.114) or BT.709 (Kr 0.2126, Kb 0.0722); Kg = 1 - Kr - Kb
+//   matrix   BT.601 (Kr 0.299, Kb 0.114) or BT.709 (Kr 0.2126, Kb 0.0722); 10-bit only: BT.2020 non-constant
+//            luminance (Kr 0.2627, Kb 0.0593); Kg = 1 - Kr - Kb
 //   range    limited: Y = 16 + 219 E'Y, C = 128 + 224 E'P;  full: Y = 255 E'Y, C = 128 + 255 E'P
 //            ys = 219/255 or 1, cs = 224/255 or 1 (scale per RGB code); yoff = 16 or 0
+//            10-bit: Y = 64 + 876 E'Y, C = 512 + 896 E'P;  full: Y = 1023 E'Y, C = 512 + 1023 E'P
+//            ys = 876/1023 or 1, cs = 896/1023 or 1; yoff = 64 or 0; chroma centre 512 (128 at 8 bits) and
+//            every result clamped to [0, 1023]; input samples above 1023 are read as 1023
 //   rnd(x)   floor(x * S + 0.5), in double
 //   encode   yr = rnd(Kr ys), yb = rnd(Kb ys), yg = rnd(ys) - yr - yb                 (row sums to rnd(ys))
 //            cbr = rnd(-Kr / (2 (1 - Kb)) cs), cbb = rnd(0.5 cs), cbg = -cbr - cbb      (row sums to 0)
@@ -24,18 +33,21 @@
 //   Y        clamp((yr R + yg G + yb B + yoff S + S/2) >> 14)
 //   Cb, Cr   from sums over n samples: jpeg n = 4, the 2x2 block; mpeg2 n = 8, the horizontal [1,2,1] at
 //            x = 2j-1, 2j, 2j+1 times the vertical [1,1] at y = 2i, 2i+1
-//            C = clamp((c_r SR + c_g SG + c_b SB + 128 n S + n S/2) >> (14 + log2 n))
+//            C = clamp((c_r SR + c_g SG + c_b SB + centre n S + n S/2) >> (14 + log2 n))
 //   up-sample chroma x16, not rounded: vertical 3 x nearest + 1 x next-nearest row (both sitings); horizontal
 //            jpeg 3 x nearest + 1 x next-nearest column (together 9a + 3b + 3c + d), mpeg2 4 x its own sample at an
 //            even x, 2 x the sum of the two neighbours at an odd x
-//   RGB      with Y' = Y - yoff, U = Cb16 - 2048, V = Cr16 - 2048 (int32, at most ~1.6e8):
+//   RGB      with Y' = Y - yoff, U = Cb16 - 16 centre, V = Cr16 - 16 centre (U = Cb16 - 2048 at 8 bits, - 8192 at 10):
 //            R = clamp((16 dy Y' + dcr V + 2^17) >> 18), G = clamp((16 dy Y' + dgb U + dgr V + 2^17) >> 18),
 //            B = clamp((16 dy Y' + dcb U + 2^17) >> 18); `>>` is an arithmetic shift (round half up)
+//            int32 bound: |intermediate| <= ~1.6e8 at 8 bits, <= 6.0e8 at 10 bits over every matrix and range (0.28 of
+//            2^31; tests/test_p10_host.py recomputes it from the coefficients).  The encode stays below 2.1e8.  12 bits
+//            would overflow: not supported.
 //
-// Both kernels are HBM-bound elementwise work.  A thread covers 4 luma columns of a row (decode) or of a row pair
-// (encode), so a wave reads and writes 256 contiguous bytes of every luma / RGB row; with W % 4 == 0 and 4-B aligned
-// bases (VEC) those are single 4-byte accesses, otherwise bytes with the edge clamped.  Chroma is read / written
-// as bytes (half the columns, one quarter of the samples).
+// All four kernels are HBM-bound elementwise work.  A thread covers 4 luma columns of a row (decode) or of a row pair
+// (encode), so a wave reads and writes 256 contiguous samples of every luma / RGB row; with W % 4 == 0 and aligned
+// bases (VEC) those are single 4-sample accesses (4 bytes at 8 bits, 8 bytes at 10), otherwise samples with the edge
+// clamped.  Chroma is read / written per sample (half the columns, one quarter of the samples).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,19 +67,24 @@ struct ColourCoef {
 };
 
 constexpr unsigned kColourFlags = FIUNET_YUV_MPEG2 | FIUNET_YUV_BT709 | FIUNET_YUV_FULL_RANGE;
+constexpr unsigned kColourFlagsP10 = kColourFlags | FIUNET_YUV_BT2020;   // BT.2020 is defined for 10 and 12 bits only
 
 inline int colour_rnd(double x) { return (int)std::floor(x * 16384.0 + 0.5); }
 
-inline ColourCoef colour_coef(unsigned flags)
+// bits: 8 (ABI v6) or 10 (ABI v7); the flags are checked by the caller (FIUNET_YUV_BT2020 only with 10)
+inline ColourCoef colour_coef(unsigned flags, int bits = 8)
 {
-    const bool full = flags & FIUNET_YUV_FULL_RANGE, bt709 = flags & FIUNET_YUV_BT709;
-    const double kr = bt709 ? 0.2126 : 0.299, kb = bt709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
-    const double ys = full ? 1.0 : 219.0 / 255.0, cs = full ? 1.0 : 224.0 / 255.0;
+    const bool full = flags & FIUNET_YUV_FULL_RANGE, bt709 = flags & FIUNET_YUV_BT709,
+               bt2020 = flags & FIUNET_YUV_BT2020, p10 = bits == 10;
+    const double kr = bt2020 ? 0.2627 : bt709 ? 0.2126 : 0.299, kb = bt2020 ? 0.0593 : bt709 ? 0.0722 : 0.114,
+                 kg = 1.0 - kr - kb;
+    const double ys = full ? 1.0 : p10 ? 876.0 / 1023.0 : 219.0 / 255.0,
+                 cs = full ? 1.0 : p10 ? 896.0 / 1023.0 : 224.0 / 255.0;
     ColourCoef k;
     k.yr = colour_rnd(kr * ys);
     k.yb = colour_rnd(kb * ys);
     k.yg = colour_rnd(ys) - k.yr - k.yb;
-    k.yoff = full ? 0 : 16;
+    k.yoff = full ? 0 : p10 ? 64 : 16;
     k.cbr = colour_rnd(-kr / (2.0 * (1.0 - kb)) * cs);
     k.cbb = colour_rnd(0.5 * cs);
     k.cbg = -k.cbr - k.cbb;
@@ -83,23 +100,46 @@ inline ColourCoef colour_coef(unsigned flags)
     return k;
 }
 
-__device__ __forceinline__ uint8_t clamp_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
+// The sample types: 8-bit I420 (ABI v6) and 10-bit codes in uint16 words (ABI v7).  read() is how a kernel takes an
+// input sample (10 bits: anything above 1023 reads as 1023), clamp() how it stores a result.
+template <typename T>
+struct ColourSample;
+template <>
+struct ColourSample<uint8_t> {
+    static constexpr int kMax = 255, kCentre = 128;
+    using Vec4 = uchar4;
+    __device__ static __forceinline__ int read(uint8_t v) { return v; }
+    __device__ static __forceinline__ uint8_t clamp(int v) { return (uint8_t)min(max(v, 0), 255); }
+    __device__ static __forceinline__ Vec4 make(uint8_t a, uint8_t b, uint8_t c, uint8_t d) { return make_uchar4(a, b, c, d); }
+};
+template <>
+struct ColourSample<uint16_t> {
+    static constexpr int kMax = 1023, kCentre = 512;
+    using Vec4 = ushort4;
+    __device__ static __forceinline__ int read(uint16_t v) { return min((int)v, 1023); }
+    __device__ static __forceinline__ uint16_t clamp(int v) { return (uint16_t)min(max(v, 0), 1023); }
+    __device__ static __forceinline__ Vec4 make(uint16_t a, uint16_t b, uint16_t c, uint16_t d)
+    {
+        return make_ushort4(a, b, c, d);
+    }
+};
 
 constexpr int kColourBlock = 128;   // threads per workgroup; each covers 4 luma columns
 
-// grid = (ceil(ceil(W/4) / 128), H, B)
-template <bool VEC>
-__global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const uint8_t* __restrict__ in, size_t in_stride,
-                                                                     uint8_t* __restrict__ out, int H, int W,
-                                                                     ColourCoef k)
+// grid = (ceil(ceil(W/4) / 128), H, B); strides and offsets in samples
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const T* __restrict__ in, size_t in_stride,
+                                                                     T* __restrict__ out, int H, int W, ColourCoef k)
 {
+    using S = ColourSample<T>;
+    using Vec4 = typename S::Vec4;
     const int t = blockIdx.x * kColourBlock + threadIdx.x, x0 = 4 * t, y = blockIdx.y;
     if (x0 >= W) return;
     const int Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
     const size_t plane = (size_t)H * W;
-    const uint8_t* fy = in + (size_t)blockIdx.z * in_stride;
-    const uint8_t* fu = fy + plane;
-    const uint8_t* fv = fu + (size_t)Hc * Wc;
+    const T* fy = in + (size_t)blockIdx.z * in_stride;
+    const T* fu = fy + plane;
+    const T* fv = fu + (size_t)Hc * Wc;
     // chroma rows: the nearest (weight 3) and the next-nearest (weight 1), both sitings
     const int i0 = y >> 1, i1 = min(max((y & 1) ? i0 + 1 : i0 - 1, 0), Hc - 1);
     // chroma columns 2t-1 .. 2t+2 (clamped) cover every neighbour of luma columns 4t .. 4t+3
@@ -107,19 +147,19 @@ __global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const uint8
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int j = min(max(2 * t - 1 + q, 0), Wc - 1);
-        u4[q] = 3 * fu[(size_t)i0 * Wc + j] + fu[(size_t)i1 * Wc + j];
-        v4[q] = 3 * fv[(size_t)i0 * Wc + j] + fv[(size_t)i1 * Wc + j];
+        u4[q] = 3 * S::read(fu[(size_t)i0 * Wc + j]) + S::read(fu[(size_t)i1 * Wc + j]);
+        v4[q] = 3 * S::read(fv[(size_t)i0 * Wc + j]) + S::read(fv[(size_t)i1 * Wc + j]);
     }
     int yv[4];
-    const uint8_t* row = fy + (size_t)y * W + x0;
+    const T* row = fy + (size_t)y * W + x0;
     if (VEC) {
-        const uchar4 p = *reinterpret_cast<const uchar4*>(row);
-        yv[0] = p.x; yv[1] = p.y; yv[2] = p.z; yv[3] = p.w;
+        const Vec4 p = *reinterpret_cast<const Vec4*>(row);
+        yv[0] = S::read(p.x); yv[1] = S::read(p.y); yv[2] = S::read(p.z); yv[3] = S::read(p.w);
     } else {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) yv[c] = row[min(c, W - 1 - x0)];
+        for (int c = 0; c < 4; ++c) yv[c] = S::read(row[min(c, W - 1 - x0)]);
     }
-    uint8_t r[4], g[4], b[4];
+    T r[4], g[4], b[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         // pixel x0 + c: nearest chroma column index 1 + (c >> 1) in u4 / v4; jpeg's next-nearest is to the left at an
@@ -133,18 +173,18 @@ __global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const uint8
             U = 3 * u4[n] + u4[f];
             V = 3 * v4[n] + v4[f];
         }
-        U -= 2048;
-        V -= 2048;
+        U -= 16 * S::kCentre;
+        V -= 16 * S::kCentre;
         const int yy = 16 * k.dy * (yv[c] - k.yoff) + (1 << 17);
-        r[c] = clamp_u8((yy + k.dcr * V) >> 18);
-        g[c] = clamp_u8((yy + k.dgb * U + k.dgr * V) >> 18);
-        b[c] = clamp_u8((yy + k.dcb * U) >> 18);
+        r[c] = S::clamp((yy + k.dcr * V) >> 18);
+        g[c] = S::clamp((yy + k.dgb * U + k.dgr * V) >> 18);
+        b[c] = S::clamp((yy + k.dcb * U) >> 18);
     }
-    uint8_t* o = out + (size_t)blockIdx.z * 3 * plane + (size_t)y * W + x0;
+    T* o = out + (size_t)blockIdx.z * 3 * plane + (size_t)y * W + x0;
     if (VEC) {
-        *reinterpret_cast<uchar4*>(o) = make_uchar4(r[0], r[1], r[2], r[3]);
-        *reinterpret_cast<uchar4*>(o + plane) = make_uchar4(g[0], g[1], g[2], g[3]);
-        *reinterpret_cast<uchar4*>(o + 2 * plane) = make_uchar4(b[0], b[1], b[2], b[3]);
+        *reinterpret_cast<Vec4*>(o) = S::make(r[0], r[1], r[2], r[3]);
+        *reinterpret_cast<Vec4*>(o + plane) = S::make(g[0], g[1], g[2], g[3]);
+        *reinterpret_cast<Vec4*>(o + 2 * plane) = S::make(b[0], b[1], b[2], b[3]);
     } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -158,47 +198,49 @@ __global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const uint8
 
 // grid = (ceil(ceil(W/4) / 128), ceil(H/2), B): a thread covers luma rows 2i, 2i+1 and columns 4t .. 4t+3, i.e.
 // chroma samples (i, 2t) and (i, 2t+1)
-template <bool VEC>
-__global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const uint8_t* __restrict__ in,
-                                                                     uint8_t* __restrict__ out, size_t out_stride,
-                                                                     int H, int W, ColourCoef k)
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const T* __restrict__ in, T* __restrict__ out,
+                                                                     size_t out_stride, int H, int W, ColourCoef k)
 {
+    using S = ColourSample<T>;
+    using Vec4 = typename S::Vec4;
     const int t = blockIdx.x * kColourBlock + threadIdx.x, x0 = 4 * t, i = blockIdx.y;
     if (x0 >= W) return;
     const int Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
     const size_t plane = (size_t)H * W;
     const int ya = 2 * i, yb = min(2 * i + 1, H - 1);
-    const uint8_t* src = in + (size_t)blockIdx.z * 3 * plane;
+    const T* src = in + (size_t)blockIdx.z * 3 * plane;
     // px[ch][row][1 + c] = channel ch at (row ya / yb, column x0 + c), c = -1 .. 3, columns clamped into the image
     int px[3][2][5];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
-            const uint8_t* row = src + ch * plane + (size_t)(rr ? yb : ya) * W;
-            px[ch][rr][0] = row[max(x0 - 1, 0)];
+            const T* row = src + ch * plane + (size_t)(rr ? yb : ya) * W;
+            px[ch][rr][0] = S::read(row[max(x0 - 1, 0)]);
             if (VEC) {
-                const uchar4 p = *reinterpret_cast<const uchar4*>(row + x0);
-                px[ch][rr][1] = p.x; px[ch][rr][2] = p.y; px[ch][rr][3] = p.z; px[ch][rr][4] = p.w;
+                const Vec4 p = *reinterpret_cast<const Vec4*>(row + x0);
+                px[ch][rr][1] = S::read(p.x); px[ch][rr][2] = S::read(p.y);
+                px[ch][rr][3] = S::read(p.z); px[ch][rr][4] = S::read(p.w);
             } else {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) px[ch][rr][1 + c] = row[min(x0 + c, W - 1)];
+                for (int c = 0; c < 4; ++c) px[ch][rr][1 + c] = S::read(row[min(x0 + c, W - 1)]);
             }
         }
-    uint8_t* fy = out + (size_t)blockIdx.z * out_stride;
-    uint8_t* fu = fy + plane;
-    uint8_t* fv = fu + (size_t)Hc * Wc;
+    T* fy = out + (size_t)blockIdx.z * out_stride;
+    T* fu = fy + plane;
+    T* fv = fu + (size_t)Hc * Wc;
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
         if (2 * i + rr >= H) break;
-        uint8_t yv[4];
+        T yv[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            yv[c] = clamp_u8((k.yr * px[0][rr][1 + c] + k.yg * px[1][rr][1 + c] + k.yb * px[2][rr][1 + c] +
+            yv[c] = S::clamp((k.yr * px[0][rr][1 + c] + k.yg * px[1][rr][1 + c] + k.yb * px[2][rr][1 + c] +
                               k.yoff * 16384 + 8192) >> 14);
-        uint8_t* o = fy + (size_t)(2 * i + rr) * W + x0;
+        T* o = fy + (size_t)(2 * i + rr) * W + x0;
         if (VEC) {
-            *reinterpret_cast<uchar4*>(o) = make_uchar4(yv[0], yv[1], yv[2], yv[3]);
+            *reinterpret_cast<Vec4*>(o) = S::make(yv[0], yv[1], yv[2], yv[3]);
         } else {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -220,9 +262,9 @@ __global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const uint8
                 s[ch] += k.mpeg2 ? px[ch][rr][a - 1] + 2 * px[ch][rr][a] + px[ch][rr][a + 1]
                                  : px[ch][rr][a] + px[ch][rr][a + 1];
         }
-        const int sh = k.mpeg2 ? 17 : 16, bias = (128 << sh) + (1 << (sh - 1));
-        fu[(size_t)i * Wc + j] = clamp_u8((k.cbr * s[0] + k.cbg * s[1] + k.cbb * s[2] + bias) >> sh);
-        fv[(size_t)i * Wc + j] = clamp_u8((k.crr * s[0] + k.crg * s[1] + k.crb * s[2] + bias) >> sh);
+        const int sh = k.mpeg2 ? 17 : 16, bias = (S::kCentre << sh) + (1 << (sh - 1));
+        fu[(size_t)i * Wc + j] = S::clamp((k.cbr * s[0] + k.cbg * s[1] + k.cbb * s[2] + bias) >> sh);
+        fv[(size_t)i * Wc + j] = S::clamp((k.crr * s[0] + k.crg * s[1] + k.crb * s[2] + bias) >> sh);
     }
 }
 

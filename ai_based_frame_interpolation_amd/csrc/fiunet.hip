@@ -1279,11 +1279,11 @@ int fiunet_yuv420_to_rgb_u8(const uint8_t* in, size_t in_frame_stride, uint8_t* 
     const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
     const ColourCoef k = colour_coef(colour);
     if (vec)
-        hipLaunchKernelGGL(yuv420_to_rgb_kernel<true>, grid, dim3(kColourBlock), 0, (hipStream_t)stream, in,
-                           in_frame_stride, out, H, W, k);
+        hipLaunchKernelGGL((yuv420_to_rgb_kernel<uint8_t, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
+                           in, in_frame_stride, out, H, W, k);
     else
-        hipLaunchKernelGGL(yuv420_to_rgb_kernel<false>, grid, dim3(kColourBlock), 0, (hipStream_t)stream, in,
-                           in_frame_stride, out, H, W, k);
+        hipLaunchKernelGGL((yuv420_to_rgb_kernel<uint8_t, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
+                           in, in_frame_stride, out, H, W, k);
     HIP_TRY(hipGetLastError());
     return FIUNET_OK;
 }
@@ -1300,11 +1300,11 @@ int fiunet_rgb_to_yuv420_u8(const uint8_t* in, uint8_t* out, size_t out_frame_st
     const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)((H + 1) / 2), (unsigned)B);
     const ColourCoef k = colour_coef(colour);
     if (vec)
-        hipLaunchKernelGGL(rgb_to_yuv420_kernel<true>, grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, out,
-                           out_frame_stride, H, W, k);
+        hipLaunchKernelGGL((rgb_to_yuv420_kernel<uint8_t, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
+                           in, out, out_frame_stride, H, W, k);
     else
-        hipLaunchKernelGGL(rgb_to_yuv420_kernel<false>, grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, out,
-                           out_frame_stride, H, W, k);
+        hipLaunchKernelGGL((rgb_to_yuv420_kernel<uint8_t, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
+                           in, out, out_frame_stride, H, W, k);
     HIP_TRY(hipGetLastError());
     return FIUNET_OK;
 }
@@ -1340,6 +1340,136 @@ int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t*
     if ((rc = fiunet_yuv420_to_rgb_u8(frame2, fb, b, B, H, W, colour, stream))) return rc;
     if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
     return fiunet_rgb_to_yuv420_u8(o, out, out_frame_stride, B, H, W, colour, stream);
+}
+
+// ---- 10-bit video (ABI v7): uint16 samples, pre10 / post10 around the fp32 forward; the colour
+//      conversions of csrc/colour.hip.h on 10-bit samples.  Strides are counted in samples.
+static int check_colour_p10_flags(unsigned colour)
+{
+    if (colour & ~kColourFlagsP10) return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits");
+    if ((colour & FIUNET_YUV_BT709) && (colour & FIUNET_YUV_BT2020))
+        return fail(FIUNET_ERR_INVALID_ARG, "colour: FIUNET_YUV_BT709 and FIUNET_YUV_BT2020 together");
+    return FIUNET_OK;
+}
+
+size_t fiunet_workspace_bytes_p10(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    const size_t base = fiunet_workspace_bytes(ctx, B, H, W, precision);
+    if (base == 0) return 0;
+    return align256(base) + 3 * align256((size_t)B * ctx->cf * H * W * 4);
+}
+
+int fiunet_forward_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
+                       size_t out_image_stride, int B, int H, int W, int precision, void* workspace,
+                       size_t workspace_bytes, void* stream)
+{
+    if (!frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (B < 1) return fail(FIUNET_ERR_INVALID_ARG, "B < 1");
+    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
+    if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (!ctx->loaded) return fail(FIUNET_ERR_NOT_LOADED, "fiunet_forward before fiunet_load_weights");
+    const size_t need = fiunet_workspace_bytes_p10(ctx, B, H, W, precision);
+    if (need == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
+    const size_t img = (size_t)ctx->cf * H * W, n = (size_t)B * img;
+    if (out_image_stride == 0) out_image_stride = img;
+    if (out_image_stride < img) return fail(FIUNET_ERR_INVALID_ARG, "out_image_stride smaller than one image");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    // [fiunet_forward's workspace | frame1 fp32 | frame2 fp32 | output logits fp32]
+    const size_t base = align256(fiunet_workspace_bytes(ctx, B, H, W, precision)), fb = align256(n * 4);
+    float* a = (float*)((char*)workspace + base);
+    float* b = (float*)((char*)a + fb);
+    float* o = (float*)((char*)b + fb);
+    int rc;
+    if ((rc = fiunet_preprocess_p10(frame1, a, n, stream))) return rc;
+    if ((rc = fiunet_preprocess_p10(frame2, b, n, stream))) return rc;
+    if ((rc = fiunet_forward(ctx, a, b, o, B, H, W, precision, workspace, base, stream))) return rc;
+    if (out_image_stride == img) return fiunet_postprocess_p10(o, out, n, stream);
+    for (int i = 0; i < B; ++i)   // images apart (the video loop's interleaved result): one elementwise launch each
+        if ((rc = fiunet_postprocess_p10(o + (size_t)i * img, out + (size_t)i * out_image_stride, img, stream))) return rc;
+    return FIUNET_OK;
+}
+
+int fiunet_yuv420p10_to_rgb_p10(const uint16_t* in, size_t in_frame_stride, uint16_t* out, int B, int H, int W,
+                                unsigned colour, void* stream)
+{
+    int rc;
+    if ((rc = check_colour_p10_flags(colour))) return rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour & kColourFlags))) return rc;
+    const size_t fs = i420_frame_bytes(H, W);   // samples per frame
+    if (in_frame_stride == 0) in_frame_stride = fs;
+    if (in_frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, "in_frame_stride smaller than one frame");
+    const bool vec = W % 4 == 0 && in_frame_stride % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 7) == 0;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
+    const ColourCoef k = colour_coef(colour, 10);
+    if (vec)
+        hipLaunchKernelGGL((yuv420_to_rgb_kernel<uint16_t, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
+                           in, in_frame_stride, out, H, W, k);
+    else
+        hipLaunchKernelGGL((yuv420_to_rgb_kernel<uint16_t, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
+                           in, in_frame_stride, out, H, W, k);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_rgb_p10_to_yuv420p10(const uint16_t* in, uint16_t* out, size_t out_frame_stride, int B, int H, int W,
+                                unsigned colour, void* stream)
+{
+    int rc;
+    if ((rc = check_colour_p10_flags(colour))) return rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour & kColourFlags))) return rc;
+    const size_t fs = i420_frame_bytes(H, W);
+    if (out_frame_stride == 0) out_frame_stride = fs;
+    if (out_frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, "out_frame_stride smaller than one frame");
+    const bool vec = W % 4 == 0 && out_frame_stride % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 7) == 0;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)((H + 1) / 2), (unsigned)B);
+    const ColourCoef k = colour_coef(colour, 10);
+    if (vec)
+        hipLaunchKernelGGL((rgb_to_yuv420_kernel<uint16_t, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
+                           in, out, out_frame_stride, H, W, k);
+    else
+        hipLaunchKernelGGL((rgb_to_yuv420_kernel<uint16_t, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
+                           in, out, out_frame_stride, H, W, k);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+size_t fiunet_workspace_bytes_yuv420p10(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    const size_t base = fiunet_workspace_bytes_p10(ctx, B, H, W, precision);
+    if (base == 0) return 0;
+    return align256(base) + 3 * align256((size_t)B * 3 * H * W * 2);
+}
+
+int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
+                             size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
+                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    int rc;
+    if ((rc = check_colour_p10_flags(colour))) return rc;
+    if (B < 1) return fail(FIUNET_ERR_INVALID_ARG, "B < 1");
+    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
+    const size_t fs = i420_frame_bytes(H, W);
+    if (out_frame_stride == 0) out_frame_stride = fs;
+    if (out_frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, "out_frame_stride smaller than one frame");
+    if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3)
+        return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_yuv420p10 needs the RGB network (frame_channels 3)");
+    const size_t need = fiunet_workspace_bytes_yuv420p10(ctx, B, H, W, precision);
+    if (need == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    // [fiunet_forward_p10's workspace | frame1 RGB | frame2 RGB | output RGB], uint16 planar [B, 3, H, W] each
+    const size_t base = align256(fiunet_workspace_bytes_p10(ctx, B, H, W, precision));
+    const size_t rgb = align256((size_t)B * 3 * H * W * 2);
+    uint16_t* a = (uint16_t*)((char*)workspace + base);
+    uint16_t* b = (uint16_t*)((char*)a + rgb);
+    uint16_t* o = (uint16_t*)((char*)b + rgb);
+    if ((rc = fiunet_yuv420p10_to_rgb_p10(frame1, fs, a, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_yuv420p10_to_rgb_p10(frame2, fs, b, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
+    return fiunet_rgb_p10_to_yuv420p10(o, out, out_frame_stride, B, H, W, colour, stream);
 }
 
 static inline int ssim_tiles(int H, int W, int* tiles_x)
@@ -1482,6 +1612,24 @@ int fiunet_postprocess_u8(const float* in, uint8_t* out, size_t n, void* stream)
     if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
     if (!n) return FIUNET_OK;
     hipLaunchKernelGGL(postprocess_u8_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, in, out, n);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_preprocess_p10(const uint16_t* in, float* out, size_t n, void* stream)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (!n) return FIUNET_OK;
+    hipLaunchKernelGGL(preprocess_p10_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, in, out, n);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_postprocess_p10(const float* in, uint16_t* out, size_t n, void* stream)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (!n) return FIUNET_OK;
+    hipLaunchKernelGGL(postprocess_p10_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, in, out, n);
     HIP_TRY(hipGetLastError());
     return FIUNET_OK;
 }

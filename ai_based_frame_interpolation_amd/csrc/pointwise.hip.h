@@ -10,7 +10,8 @@
 //   head1x1_kernel         : OutConv 1x1 + bias, NHWC in -> fp32 NCHW out (ablation path; normally
 //                            fused into the epilogue of up4.conv.double_conv.3) -- unet.py:60
 //   nhwc_to_nchw_f32_kernel: parity-test readback of an intermediate (blocked) activation as NCHW
-//   pre/postprocess kernels: model/inference.py:31-35 and :54-61 on device
+//   pre/postprocess kernels: model/inference.py:31-35 and :54-61 on device; their 10-bit counterparts (pre10 / post10,
+//                            DESIGN.md 3.3d) for the 10-bit video path
 #pragma once
 #include "conv3x3_mfma.hip.h"
 
@@ -732,6 +733,39 @@ __global__ __launch_bounds__(256) void postprocess_u8_kernel(const float* __rest
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         out[i] = postprocess_u8_value(in[i]);
+    }
+}
+
+// 10-bit video: pre10(x) = x / 1023 * 2 - 1, x a 10-bit code in a uint16 word (above 1023 reads as
+// 1023).  The quotient is the IEEE one: __fdiv_rn is correctly rounded here (hipcc's default
+// -fhip-fp32-correctly-rounded-divide-sqrt), so no reciprocal trick has to be proved for 1023 (tests/test_gpu_p10.py
+// checks all 65536 inputs bit for bit against numpy).  Then 2q - 1 exactly as preprocess_u8_value.
+__device__ __forceinline__ float preprocess_p10_value(uint16_t u)
+{
+    const float q = __fdiv_rn((float)min((int)u, 1023), 1023.0f);
+    return __fsub_rn(__fmul_rn(2.0f, q), 1.0f);
+}
+// post10(t) = trunc(clamp((t + 1) / 2, 0, 1) * 1023): postprocess_u8_value's operations in its order (NaN -> 0)
+__device__ __forceinline__ uint16_t postprocess_p10_value(float x)
+{
+    float v = __fdiv_rn(__fadd_rn(x, 1.0f), 2.0f);
+    v = fminf(fmaxf(v, 0.0f), 1.0f);
+    return (uint16_t)(int)__fmul_rn(v, 1023.0f);
+}
+
+__global__ __launch_bounds__(256) void preprocess_p10_kernel(const uint16_t* __restrict__ in,
+                                                             float* __restrict__ out, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        out[i] = preprocess_p10_value(in[i]);
+    }
+}
+
+__global__ __launch_bounds__(256) void postprocess_p10_kernel(const float* __restrict__ in,
+                                                              uint16_t* __restrict__ out, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        out[i] = postprocess_p10_value(in[i]);
     }
 }
 

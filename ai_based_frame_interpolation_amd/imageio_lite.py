@@ -233,7 +233,16 @@ def write_png(path: str, img: np.ndarray) -> None:
 def _y4m_header(data: bytes):
     """Parse the stream header -> (fields, offset of the first FRAME marker).  fields: width, height, fps (num, den),
     colourspace (the `C` tag, "420jpeg" when absent), colour_range ("FULL" / "LIMITED" from an `XCOLORRANGE=` token,
-    None when absent), chroma (rows, cols) of each of U and V ((0, 0) for mono), frame_bytes."""
+    None when absent), chroma (rows, cols) of each of U and V ((0, 0) for mono), frame_bytes.  8-bit streams only."""
+    hdr, pos = _y4m_fields(data)
+    cs = hdr["colourspace"]
+    if any(c in cs for c in ("p10", "p12", "p14", "p16", "mono16")):
+        raise ValueError(f"unsupported Y4M bit depth C{cs}")
+    return hdr, pos
+
+
+def _y4m_fields(data: bytes):
+    """`_y4m_header` without the bit-depth check (frame_bytes counts one byte per sample)."""
     nl = data.index(b"\n")
     head = data[:nl].split(b" ")
     if head[0] != b"YUV4MPEG2":
@@ -266,8 +275,6 @@ def _y4m_header(data: bytes):
         cw, ch = w, h
     else:
         raise ValueError(f"unsupported Y4M colourspace C{cs}")
-    if any(c in cs for c in ("p10", "p12", "p14", "p16", "mono16")):
-        raise ValueError(f"unsupported Y4M bit depth C{cs}")
     return dict(width=w, height=h, fps=fps, colourspace=cs, colour_range=rng, chroma=(ch, cw),
                 frame_bytes=w * h + 2 * cw * ch), nl + 1
 
@@ -340,3 +347,86 @@ def write_y4m(path: str, y: np.ndarray, chroma=None, fps=(30, 1), colourspace: s
             if chroma is not None:
                 f.write(np.ascontiguousarray(chroma[0][i], dtype=np.uint8).tobytes())
                 f.write(np.ascontiguousarray(chroma[1][i], dtype=np.uint8).tobytes())
+
+
+# ---- 10-bit Y4M: every sample a 10-bit code in a little-endian 16-bit word -----------------------------------------
+# The tags ffmpeg writes for yuv420p10le / yuv422p10le / yuv444p10le / gray10le (`ffmpeg -i in.mkv in.y4m` keeps a
+# 10-bit source's format): "C420p10 XYSCSS=420P10" and so on, "Cmono10".  12-, 14- and 16-bit streams are refused
+# (the colour conversion of DESIGN.md 3.3d is defined for 10 bits).
+Y4M_P10_TAGS = ("420p10", "422p10", "444p10", "mono10")
+
+
+def _y4m_header_p10(data: bytes):
+    hdr, pos = _y4m_fields(data)
+    cs = hdr["colourspace"]
+    if cs not in Y4M_P10_TAGS:
+        if any(c in cs for c in ("p9", "p12", "p14", "p16", "mono9", "mono12", "mono14", "mono16")):
+            raise ValueError(f"unsupported Y4M bit depth C{cs}: the 10-bit reader takes "
+                             f"{', '.join('C' + t for t in Y4M_P10_TAGS)}")
+        raise ValueError(f"Y4M colourspace C{cs} is not a 10-bit layout ({', '.join('C' + t for t in Y4M_P10_TAGS)}): "
+                         "read 8-bit video with read_y4m")
+    samples = hdr["frame_bytes"]
+    hdr.update(bits=10, frame_samples=samples, frame_bytes=2 * samples)
+    return hdr, pos
+
+
+def read_y4m_packed_p10(path: str):
+    """-> (frames [N, frame_samples] uint16, header fields as `_y4m_header` returns them plus bits = 10 and
+    frame_samples; frame_bytes counts the 2 bytes per sample).  Each row is one frame payload (Y, then U, then V):
+    for C420p10 the packed frame that `FrameInterpolationUNet.forward_yuv420p10` takes.  Samples are read as stored
+    (values above 1023 included; the device kernels read those as 1023)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    hdr, pos = _y4m_header_p10(data)
+    n = hdr["frame_samples"]
+    frames = np.stack([np.frombuffer(data, "<u2", n, off) for off in _y4m_payloads(data, pos, hdr["frame_bytes"])])
+    return frames.astype(np.uint16), hdr
+
+
+def read_y4m_p10(path: str):
+    """`read_y4m` for 10-bit streams -> (y [N, H, W] uint16, chroma or None, fps (num, den), colourspace tag)."""
+    frames, hdr = read_y4m_packed_p10(path)
+    w, h, (ch, cw) = hdr["width"], hdr["height"], hdr["chroma"]
+    n, ny, nc = frames.shape[0], w * h, cw * ch
+    y = frames[:, :ny].reshape(n, h, w)
+    chroma = None
+    if cw:
+        chroma = (frames[:, ny:ny + nc].reshape(n, ch, cw), frames[:, ny + nc:].reshape(n, ch, cw))
+    return y, chroma, hdr["fps"], hdr["colourspace"]
+
+
+def write_y4m_p10(path: str, y: np.ndarray, chroma=None, fps=(30, 1), colourspace: str = None,
+                  colour_range: str = None) -> None:
+    """y: [N, H, W] uint16 10-bit codes; chroma: None (-> Cmono10) or (U, V) planes as read_y4m_p10 returns them
+    (-> C420p10 unless `colourspace` says 422p10 / 444p10).  Samples go out as little-endian 16-bit words, with the
+    header ffmpeg writes (`C420p10 XYSCSS=420P10`); colour_range: None (no XCOLORRANGE token), "FULL" or "LIMITED"."""
+    y = np.ascontiguousarray(y, dtype=np.uint16)
+    n, h, w = y.shape
+    cs = colourspace or ("mono10" if chroma is None else "420p10")
+    if cs not in Y4M_P10_TAGS:
+        raise ValueError(f"colourspace must be one of {Y4M_P10_TAGS}, got {cs!r}")
+    if (chroma is None) != cs.startswith("mono"):
+        raise ValueError("chroma planes and colourspace tag disagree")
+    ext = "" if cs.startswith("mono") else f" XYSCSS={cs.upper()}"
+    if colour_range is not None:
+        if colour_range.upper() not in ("FULL", "LIMITED"):
+            raise ValueError(f"colour_range must be FULL or LIMITED, got {colour_range!r}")
+        ext += f" XCOLORRANGE={colour_range.upper()}"
+    with open(path, "wb") as f:
+        f.write(f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{cs}{ext}\n".encode())
+        for i in range(n):
+            f.write(b"FRAME\n")
+            f.write(y[i].astype("<u2").tobytes())
+            if chroma is not None:
+                f.write(np.ascontiguousarray(chroma[0][i], dtype=np.uint16).astype("<u2").tobytes())
+                f.write(np.ascontiguousarray(chroma[1][i], dtype=np.uint16).astype("<u2").tobytes())
+
+
+def y4m_colourspace(path: str) -> str:
+    """The `C` tag of a Y4M file's stream header ("420jpeg" when absent), read from its first line only."""
+    with open(path, "rb") as f:
+        line = f.readline(4096)
+    for tok in line.rstrip(b"\n").split(b" ")[1:]:
+        if tok[:1] == b"C":
+            return tok[1:].decode()
+    return "420jpeg"

@@ -219,6 +219,59 @@ def interpolate_sequence_yuv420(model, frames: torch.Tensor, height: int, width:
     return out
 
 
+# torch's uint16 is a dtype of limited support on the GPU (no guaranteed cat / repeat kernels): the 10-bit loops pad and
+# interleave int16 views of their uint16 frames (same bits) and hand uint16 views to the model.
+def _i16(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.int16)
+
+
+def _u16(t: torch.Tensor | None) -> torch.Tensor | None:
+    return None if t is None else t.view(torch.uint16)
+
+
+@torch.no_grad()
+def interpolate_sequence_p10(model, frames: torch.Tensor, batch: int = 8) -> torch.Tensor:
+    """factor-2 video loop on 10-bit frames: device uint16 [N,H,W] (or [N,C,H,W]) 10-bit codes -> [2N-1, ...] = F0, M0,
+    F1, ..., F(N-1), where Mi = model.forward_p10(Fi, Fi+1).  Both networks.  The originals are copied sample for
+    sample; each middle is written in place; a ragged last chunk is padded as in `interpolate_sequence`, so the result
+    does not depend on N.  Use precision bf16x2 (or fp32) for 10-bit video: bf16 is about 5 codes off."""
+    squeeze = frames.dim() == 3
+    fr = frames.unsqueeze(1) if squeeze else frames
+    n, _, h, w = fr.shape
+    out = torch.empty((2 * n - 1,) + tuple(fr.shape[1:]), dtype=torch.uint16, device=fr.device)
+    f16, o16 = _i16(fr), _i16(out)
+    o16[0::2] = f16
+
+    def fwd(a, b, out=None):
+        return _i16(model.forward_p10(_u16(a), _u16(b), out=_u16(out)))
+
+    for s, cnt in _pair_batches(n - 1, batch):
+        _padded_chunk(model, fwd, f16[s:s + cnt], f16[s + 1:s + cnt + 1], h, w, batch,
+                      out=o16[2 * s + 1: 2 * (s + cnt): 2])
+    return out.squeeze(1) if squeeze else out
+
+
+@torch.no_grad()
+def interpolate_sequence_yuv420p10(model, frames: torch.Tensor, height: int, width: int, batch: int = 8,
+                                   **colour) -> torch.Tensor:
+    """`interpolate_sequence_yuv420` on 10-bit video: device uint16 [N, F] packed 4:2:0 10-bit frames (a C420p10 Y4M
+    frame payload each) -> [2N-1, F], Mi = model.forward_yuv420p10(Fi, Fi+1, **colour).  The originals are copied
+    sample for sample; the result does not depend on N.  colour: siting / matrix (also "bt2020") / colour_range."""
+    h, w = int(height), int(width)
+    n = frames.shape[0]
+    out = torch.empty((2 * n - 1, frames.shape[1]), dtype=torch.uint16, device=frames.device)
+    f16, o16 = _i16(frames), _i16(out)
+    o16[0::2] = f16
+
+    def fwd(a, b, out=None):
+        return _i16(model.forward_yuv420p10(_u16(a), _u16(b), h, w, out=_u16(out), **colour))
+
+    for s, cnt in _pair_batches(n - 1, batch):
+        _padded_chunk(model, fwd, f16[s:s + cnt], f16[s + 1:s + cnt + 1], h, w, batch,
+                      out=o16[2 * s + 1: 2 * (s + cnt): 2])
+    return out
+
+
 @torch.no_grad()
 def interpolate_sequence_host(model, frames_u8_cpu: torch.Tensor, batch: int = 8,
                               out: torch.Tensor | None = None) -> torch.Tensor:
@@ -282,6 +335,18 @@ def _interleave_average_u8(planes: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _interleave_average_p10(planes: torch.Tensor) -> torch.Tensor:
+    """`_interleave_average_u8` for 10-bit chroma: [N, h, w] int32 -> [2N-1, h, w] int32, the originals as they are and
+    the rounded average of each neighbouring pair in between (samples above 1023 read as 1023)."""
+    n = planes.shape[0]
+    out = torch.empty((2 * n - 1,) + tuple(planes.shape[1:]), dtype=torch.int32, device=planes.device)
+    out[0::2] = planes
+    if n > 1:
+        c = planes.clamp(max=1023)
+        out[1::2] = (c[:-1] + c[1:] + 1) >> 1
+    return out
+
+
 class FrameInterpolator:
     """What main.py:95-129 expects from `model.inference` (it is missing in the reference).
 
@@ -289,9 +354,10 @@ class FrameInterpolator:
     same shape; colour images are processed per channel with the 2->1 grayscale network unless
     the checkpoint is the 6->3 variant.
     interpolate_video(input_path, output_path, factor=2): raw .npy frame stack or uncompressed
-    YUV4MPEG2 (`.y4m`) video in/out (4:2:0 colour through the RGB network: `interpolate_sequence_yuv420`); factor
-    must be a power of two (recursive bisection; factor 2 is the only semantics the reference's flags imply,
-    main.py:57-62)."""
+    YUV4MPEG2 (`.y4m`) video in/out (4:2:0 colour through the RGB network: `interpolate_sequence_yuv420`; 10-bit
+    `C420p10` / `C422p10` / `C444p10` / `Cmono10` through `interpolate_sequence_p10` (gray) or
+    `interpolate_sequence_yuv420p10` (RGB, 4:2:0 only)); factor must be a power of two (recursive bisection; factor 2
+    is the only semantics the reference's flags imply, main.py:57-62)."""
 
     def __init__(self, model_path=None, device="cuda", precision=None, model=None, batch=8):
         self.device = torch.device("cuda" if device in ("auto", None) else device)
@@ -342,7 +408,67 @@ class FrameInterpolator:
             np.save(output_path, t.cpu().numpy())
         return t.shape[0]
 
-    def _interpolate_y4m_colour(self, input_path, output_path, factor, matrix):
+    def _interpolate_y4m_p10(self, input_path, output_path, factor):
+        """10-bit YUV4MPEG2 (`C420p10`, `C422p10`, `C444p10`, `Cmono10`) through the grayscale network: the luma plane
+        through `interpolate_sequence_p10`; the chroma of an inserted frame is the rounded average of its neighbours',
+        in int32.  The output keeps the input's tag and range, fps x factor.  Output: `.y4m`, or a `.npy` stack of the
+        uint16 luma frames."""
+        frames, hdr = imageio_lite.read_y4m_packed_p10(input_path)
+        h, w, (hc, wc) = hdr["height"], hdr["width"], hdr["chroma"]
+        ny, nc = h * w, hc * wc
+        t = torch.from_numpy(np.ascontiguousarray(frames[:, :ny]).reshape(-1, h, w)).to(self.device)
+        cu = cv = None
+        if nc:
+            cu, cv = (torch.from_numpy(frames[:, ny + i * nc:ny + (i + 1) * nc].astype(np.int32).reshape(-1, hc, wc))
+                      .to(self.device) for i in (0, 1))
+        f = factor
+        while f > 1:
+            t = interpolate_sequence_p10(self.model, t, self.batch)
+            if cu is not None:
+                cu, cv = (_interleave_average_p10(c) for c in (cu, cv))
+            f //= 2
+        y = t.cpu().numpy()
+        if str(output_path).lower().endswith(".y4m"):
+            imageio_lite.write_y4m_p10(output_path, y,
+                                       None if cu is None else (cu.cpu().numpy().astype(np.uint16),
+                                                                cv.cpu().numpy().astype(np.uint16)),
+                                       (hdr["fps"][0] * factor, hdr["fps"][1]), hdr["colourspace"],
+                                       colour_range=hdr["colour_range"])
+        else:
+            np.save(output_path, y)
+        return y.shape[0]
+
+    def _interpolate_y4m_colour_p10(self, input_path, output_path, factor, matrix, siting):
+        """10-bit 4:2:0 YUV4MPEG2 (`C420p10`) through the RGB network (`interpolate_sequence_yuv420p10`).  The tag does
+        not carry the siting: `siting` None means "mpeg2" (left-sited: what HEVC, AV1 and H.264 decoders give).  Range
+        from `XCOLORRANGE` (limited when absent); `matrix` also takes "bt2020".  The output keeps the tag and range,
+        fps x factor."""
+        cs = imageio_lite.y4m_colourspace(input_path)
+        if cs != "420p10":
+            raise ValueError(f"Y4M colourspace C{cs} is not supported by the RGB network: it reads 10-bit 4:2:0 video "
+                             "tagged C420p10")
+        if not str(output_path).lower().endswith(".y4m"):
+            raise ValueError("colour Y4M video through the RGB network is written as .y4m (no .npy output)")
+        frames, hdr = imageio_lite.read_y4m_packed_p10(input_path)
+        opts = dict(siting="mpeg2" if siting is None else siting, matrix=matrix,
+                    colour_range="full" if hdr["colour_range"] == "FULL" else "limited")
+        colour.colour_flags(**opts, bits=10)   # a bad `matrix` / `siting` fails here, before any GPU work
+        h, w = hdr["height"], hdr["width"]
+        t = torch.from_numpy(frames).to(self.device)
+        f = factor
+        while f > 1:
+            t = interpolate_sequence_yuv420p10(self.model, t, h, w, self.batch, **opts)
+            f //= 2
+        res = t.cpu().numpy()
+        (hc, wc), ny = hdr["chroma"], h * w
+        u = res[:, ny:ny + hc * wc].reshape(-1, hc, wc)
+        v = res[:, ny + hc * wc:].reshape(-1, hc, wc)
+        imageio_lite.write_y4m_p10(output_path, res[:, :ny].reshape(-1, h, w), (u, v),
+                                   (hdr["fps"][0] * factor, hdr["fps"][1]), hdr["colourspace"],
+                                   colour_range=hdr["colour_range"])
+        return res.shape[0]
+
+    def _interpolate_y4m_colour(self, input_path, output_path, factor, matrix, siting=None):
         """4:2:0 YUV4MPEG2 in -> out through the RGB (6->3) network: every frame is converted to planar RGB on the
         device, the network interpolates all three channels, and the middle frames are converted back
         (`interpolate_sequence_yuv420`).  Chroma siting from the `C` tag (420jpeg / 420 / none, or 420mpeg2), range
@@ -351,8 +477,8 @@ class FrameInterpolator:
         if not str(output_path).lower().endswith(".y4m"):
             raise ValueError("colour Y4M video through the RGB network is written as .y4m (no .npy output)")
         frames, hdr = imageio_lite.read_y4m_packed(input_path)
-        siting = colour.siting_of_y4m(hdr["colourspace"])   # rejects 422 / 444 / mono / 420paldv before any GPU work
-        opts = dict(siting=siting, matrix=matrix,
+        tag_siting = colour.siting_of_y4m(hdr["colourspace"])   # rejects 422 / 444 / mono / 420paldv before any GPU work
+        opts = dict(siting=tag_siting if siting is None else siting, matrix=matrix,
                     colour_range="full" if hdr["colour_range"] == "FULL" else "limited")
         colour.colour_flags(**opts)   # a bad `matrix` fails here, before any GPU work
         h, w = hdr["height"], hdr["width"]
@@ -370,16 +496,25 @@ class FrameInterpolator:
                                colour_range=hdr["colour_range"])
         return res.shape[0]
 
-    def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709"):
-        """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video, or
-        "bt601"; the container does not carry it).  The grayscale network's Y4M path does not use it."""
+    def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None):
+        """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
+        "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
+        siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
+        tag (8-bit: C420jpeg / C420 -> "jpeg", C420mpeg2 -> "mpeg2"; 10-bit: C420p10 does not carry it -> "mpeg2",
+        what HEVC, AV1 and H.264 decoders give).  The grayscale network's Y4M path uses neither.  10-bit video keeps
+        10 bits end to end; run it in precision bf16x2 (or fp32): bf16 is about 5 codes off."""
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Video file not found: {input_path}")
         if str(input_path).lower().endswith(".y4m"):
+            p10 = imageio_lite.y4m_colourspace(input_path) in imageio_lite.Y4M_P10_TAGS
             if self.model.frame_channels == 3:
-                return self._interpolate_y4m_colour(input_path, output_path, factor, matrix)
+                if p10:
+                    return self._interpolate_y4m_colour_p10(input_path, output_path, factor, matrix, siting)
+                return self._interpolate_y4m_colour(input_path, output_path, factor, matrix, siting)
+            if p10:
+                return self._interpolate_y4m_p10(input_path, output_path, factor)
             return self._interpolate_y4m(input_path, output_path, factor)
         frames = np.load(input_path)
         if frames.dtype != np.uint8 or frames.ndim not in (3, 4):

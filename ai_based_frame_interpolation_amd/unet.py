@@ -252,10 +252,10 @@ class FrameInterpolationUNet(nn.Module):
             self._weights_gen += 1
         return self._ctx
 
-    def _workspace(self, ctx, device, b, h, w, prec, u8=False, yuv=False):
+    def _workspace(self, ctx, device, b, h, w, prec, u8=False, yuv=False, p10=False):
         """One scratch block, kept at the largest size any call has needed (a smaller batch or the
         ragged last chunk of a video reuses it instead of freeing and reallocating gigabytes)."""
-        nbytes = ctx.workspace_bytes(b, h, w, prec, u8, yuv)
+        nbytes = ctx.workspace_bytes(b, h, w, prec, u8, yuv, p10)
         if self._ws is None or self._ws.device != device or self._ws.numel() < nbytes:
             self._ws = None  # release before allocating the next one
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -381,6 +381,64 @@ class FrameInterpolationUNet(nn.Module):
             raise ValueError(f"out must be a uint8 {tuple(f1.shape)} tensor on {f1.device} whose frames are contiguous")
         with torch.cuda.device(f1.device):
             ctx.forward_yuv420(f1, f2, out, h, w, flags, prec, ws)
+        return out
+
+    @torch.no_grad()
+    def forward_p10(self, frame1: torch.Tensor, frame2: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """10-bit frames: uint16 [B,C,H,W] of 10-bit codes in (above 1023 reads as 1023) -> uint16 interpolated frames,
+        `fiunet_forward_p10`: x / 1023 * 2 - 1 on device, the fp32-in forward, trunc(clamp((y+1)/2, 0, 1) * 1023) on
+        device - bit for bit `postprocess_p10(forward(preprocess_p10(a), preprocess_p10(b)))`.  Both networks.
+        Accuracy: fp32 and bf16x2 within 1 code of the fp32 oracle; bf16 about 5 codes (8 significant bits in every
+        activation, a stem dither of 2 codes peak to peak): use bf16x2 for 10-bit video.  `out`: as for `forward_u8`
+        (uint16, every image contiguous, the images may lie apart)."""
+        self._check_pair(frame1, frame2, (torch.uint16,))
+        if not frame1.is_contiguous() or not frame2.is_contiguous():
+            raise ValueError("forward_p10 takes contiguous frames")
+        b, _, h, w = frame1.shape
+        prec = self._precision_code()
+        ctx = self._context(frame1.device)
+        ws = self._workspace(ctx, frame1.device, b, h, w, prec, p10=True)
+        if out is None:
+            out = torch.empty_like(frame1)
+        elif out.dtype != torch.uint16 or out.shape != frame1.shape or out.device != frame1.device:
+            raise ValueError(f"out must be a uint16 {tuple(frame1.shape)} tensor on {frame1.device}")
+        with torch.cuda.device(frame1.device):
+            ctx.forward_p10(frame1, frame2, out, prec, ws)
+        return out
+
+    @torch.no_grad()
+    def forward_yuv420p10(self, frame1: torch.Tensor, frame2: torch.Tensor, height: int, width: int, *,
+                          siting: str = "jpeg", matrix: str = "bt709", colour_range: str = "limited",
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+        """The RGB network on 10-bit colour video: uint16 [B, F] packed 4:2:0 10-bit frames in (F = H*W +
+        2*ceil(H/2)*ceil(W/2) samples, a C420p10 Y4M frame payload) -> uint16 [B, F] interpolated frames,
+        `fiunet_forward_yuv420p10`: YUV -> planar RGB, `forward_p10`, RGB -> YUV on device.  matrix
+        also takes "bt2020".  The network interpolates code values, as it does for 8-bit video (no PQ / HLG
+        linearisation).  Use bf16x2 (or fp32): bf16 is about 5 codes off.  `out`: as for `forward_yuv420`."""
+        from .colour import colour_flags, yuv420p10_frame_samples
+        flags = colour_flags(siting, matrix, colour_range, bits=10)
+        if self.frame_channels != 3:
+            raise RuntimeError("forward_yuv420p10 runs the RGB network (frame_channels=3); this model is grayscale")
+        h, w = int(height), int(width)
+        fs = yuv420p10_frame_samples(h, w)
+        if frame1.dim() != 2 or frame1.shape != frame2.shape or frame1.shape[1] != fs:
+            raise RuntimeError(f"expected two [B,{fs}] tensors (packed 4:2:0 10-bit frames of {h}x{w}) of equal shape, "
+                               f"got {tuple(frame1.shape)} and {tuple(frame2.shape)}")
+        self._check_device_mode_dtype(frame1, frame2, (torch.uint16,))
+        if not frame1.is_contiguous() or not frame2.is_contiguous():
+            raise ValueError("forward_yuv420p10 takes contiguous frames")
+        b = frame1.shape[0]
+        prec = self._precision_code()
+        ctx = self._context(frame1.device)
+        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=True)
+        if out is None:
+            out = torch.empty_like(frame1)
+        elif (out.dtype != torch.uint16 or out.shape != frame1.shape or out.device != frame1.device
+              or out.stride(1) != 1 or (b > 1 and out.stride(0) < fs)):
+            raise ValueError(f"out must be a uint16 {tuple(frame1.shape)} tensor on {frame1.device} whose frames are "
+                             "contiguous")
+        with torch.cuda.device(frame1.device):
+            ctx.forward_yuv420p10(frame1, frame2, out, h, w, flags, prec, ws)
         return out
 
     @torch.no_grad()

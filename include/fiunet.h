@@ -21,8 +21,9 @@
 extern "C" {
 #endif
 
-#define FIUNET_ABI_VERSION 6   /* 4: fiunet_prepare_precision; fiunet_debug_read_activation takes the capacity of dst; 5: fiunet_forward_u8_strided;
-                                  6: YUV 4:2:0 colour video (fiunet_yuv420_to_rgb_u8, fiunet_rgb_to_yuv420_u8, fiunet_forward_yuv420) */
+#define FIUNET_ABI_VERSION 7   /* 4: fiunet_prepare_precision; fiunet_debug_read_activation takes the capacity of dst; 5: fiunet_forward_u8_strided;
+                                  6: YUV 4:2:0 colour video (fiunet_yuv420_to_rgb_u8, fiunet_rgb_to_yuv420_u8, fiunet_forward_yuv420);
+                                  7: 10-bit video (fiunet_forward_p10, fiunet_forward_yuv420p10 and their pieces; FIUNET_YUV_BT2020) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -176,7 +177,11 @@ enum fiunet_colour {
     FIUNET_YUV_MPEG2 = 1,      /* chroma siting 420mpeg2: co-sited with the even luma column, centred vertically
                                   (default: 420jpeg, centred in its 2x2 luma block) */
     FIUNET_YUV_BT709 = 2,      /* matrix BT.709 (Kr 0.2126, Kb 0.0722); default BT.601 (Kr 0.299, Kb 0.114) */
-    FIUNET_YUV_FULL_RANGE = 4  /* Y 0-255, C = 128 + 255 E'P; default limited: Y 16-235, C 16-240 */
+    FIUNET_YUV_FULL_RANGE = 4, /* Y 0-255, C = 128 + 255 E'P; default limited: Y 16-235, C 16-240
+                                  (10-bit: Y 0-1023, C = 512 + 1023 E'P; limited Y 64-940, C 64-960) */
+    FIUNET_YUV_BT2020 = 8      /* matrix BT.2020 non-constant luminance (Kr 0.2627, Kb 0.0593): the 10-bit entry points
+                                  only (the 8-bit ones reject it: BT.2020 defines 10- and 12-bit coding); together with
+                                  FIUNET_YUV_BT709 it is FIUNET_ERR_INVALID_ARG */
 };
 
 /* Packed I420 frames (`in_frame_stride` bytes apart, 0 = F) -> planar RGB uint8 [B, 3, H, W] (the layout
@@ -200,6 +205,42 @@ size_t fiunet_workspace_bytes_yuv420(const fiunet_ctx* ctx, int B, int H, int W,
 int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
                           size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* 10-bit video (ABI v7).  The reference has no counterpart.  A sample is a 10-bit code in a uint16 word (what a
+ * `C420p10` / `Cmono10` Y4M payload holds, little-endian); any sample above 1023 is read as 1023.  The network sees
+ * pre10(x) = x / 1023 * 2 - 1 (the IEEE fp32 quotient) and its output is written as post10(t) =
+ * trunc(clamp((t + 1) / 2, 0, 1) * 1023): the u8 pre/post-processing with 1023 in place of 255.
+ * Device pointers; asynchronous on `stream`; no allocation, no synchronisation. */
+int fiunet_preprocess_p10(const uint16_t* in, float* out, size_t n, void* stream);
+int fiunet_postprocess_p10(const float* in, uint16_t* out, size_t n, void* stream);
+/* Workspace of fiunet_forward_p10: fiunet_workspace_bytes plus three fp32 frame batches; 0 on bad arguments (query it
+ * after fiunet_set_options). */
+size_t fiunet_workspace_bytes_p10(const fiunet_ctx* ctx, int B, int H, int W, int precision);
+/* The forward on 10-bit frames, both networks: frame1, frame2 device uint16 [B, frame_channels, H, W]; the B output
+ * images go to `out`, `out_image_stride` SAMPLES apart (0 = contiguous; >= frame_channels * H * W).  pre10 of both
+ * inputs into fp32 staging, fiunet_forward, post10 into `out` - bit for bit fiunet_preprocess_p10 -> fiunet_forward
+ * -> fiunet_postprocess_p10.  Accuracy: fp32 and FIUNET_BF16X2 within 1 code of the fp32 oracle; FIUNET_BF16 about
+ * 5 codes (8 significant bits; its stem dither is 2 ten-bit codes peak to peak): use FIUNET_BF16X2 for 10-bit video. */
+int fiunet_forward_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
+                       size_t out_image_stride, int B, int H, int W, int precision, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* 10-bit YUV 4:2:0 <-> planar RGB: the 8-bit conversions above on 10-bit samples (a frame is F = H*W +
+ * 2*ceil(H/2)*ceil(W/2) SAMPLES, a C420p10 Y4M payload; every frame stride is counted in SAMPLES, 0 = F).  Limited
+ * range Y = 64 + 876 E'Y, C = 512 + 896 E'P; full range Y = 1023 E'Y, C = 512 + 1023 E'P; results clamped to
+ * [0, 1023].  `colour` as for the 8-bit calls plus FIUNET_YUV_BT2020. */
+int fiunet_yuv420p10_to_rgb_p10(const uint16_t* in, size_t in_frame_stride, uint16_t* out, int B, int H, int W,
+                                unsigned colour, void* stream);
+int fiunet_rgb_p10_to_yuv420p10(const uint16_t* in, uint16_t* out, size_t out_frame_stride, int B, int H, int W,
+                                unsigned colour, void* stream);
+/* Workspace of fiunet_forward_yuv420p10: fiunet_workspace_bytes_p10 plus three planar RGB uint16 batches. */
+size_t fiunet_workspace_bytes_yuv420p10(const fiunet_ctx* ctx, int B, int H, int W, int precision);
+/* fiunet_forward_yuv420 on 10-bit frames: B packed 4:2:0 frames of F samples each, contiguous, in; the B interpolated
+ * frames to `out`, `out_frame_stride` SAMPLES apart (0 = F).  Bit for bit fiunet_yuv420p10_to_rgb_p10 (both inputs) ->
+ * fiunet_forward_p10 -> fiunet_rgb_p10_to_yuv420p10.  FIUNET_ERR_UNSUPPORTED on a context with frame_channels != 3.
+ * Neither allocates nor synchronises. */
+int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
+                             size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* Replaces preprocess_image's arithmetic (model/inference.py:31-35): out = 2*(in/255) - 1. */
 int fiunet_preprocess_u8(const uint8_t* in, float* out, size_t n, void* stream);

@@ -1,0 +1,98 @@
+"""Time the 10-bit video path's extra passes against the RGB network's step.
+
+  forward          the fp32-in forward at B=8 1080p (the network alone)
+  forward_p10      pre10 of both frames, the same forward, post10 (uint16 planar RGB in and out)
+  forward_yuv420p10  two 10-bit 4:2:0 -> RGB decodes, forward_p10, one encode
+  forward_u8       the 8-bit planar RGB forward (fused u8 stem / head where they exist), for comparison
+
+Device time from HIP events around `--iters` back-to-back calls after `--warmup` calls of the same shape; every case is
+repeated `--reps` times, interleaved, and the median and the spread are printed, for each precision.  One JSON line
+last.
+
+    python tools/p10_timing.py [--batch 8 --height 1080 --width 1920 --precisions bf16,bf16x2]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import ai_based_frame_interpolation_amd as P  # noqa: E402
+from oracle import unet_oracle as O  # noqa: E402
+
+
+def _time(fn, iters):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--precisions", default="bf16,bf16x2")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "p10_timing measures on the GPU; there is no CPU path"
+    dev = torch.device("cuda:0")
+    b, h, w = a.batch, a.height, a.width
+    fs = P.yuv420p10_frame_samples(h, w)
+    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3)
+    m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
+    m = m.to(dev).eval()
+    g = torch.Generator(device=dev).manual_seed(0)
+    # uint16 tensors are made as int16 and viewed (torch's uint16 has limited GPU support)
+    y1, y2 = (torch.randint(0, 1024, (b, fs), dtype=torch.int16, device=dev, generator=g).view(torch.uint16)
+              for _ in range(2))
+    r1, r2 = P.yuv420p10_to_rgb(y1, h, w), P.yuv420p10_to_rgb(y2, h, w)
+    f1, f2 = (torch.rand((b, 3, h, w), device=dev, generator=g) * 2 - 1 for _ in range(2))
+    u1, u2 = (torch.randint(0, 256, (b, 3, h, w), dtype=torch.uint8, device=dev, generator=g) for _ in range(2))
+    rgb_out = torch.empty_like(r1)
+    yuv_out = torch.empty_like(y1)
+    u8_out = torch.empty_like(u1)
+    cases = {
+        "forward": lambda: m(f1, f2),
+        "forward_p10": lambda: m.forward_p10(r1, r2, out=rgb_out),
+        "forward_yuv420p10": lambda: m.forward_yuv420p10(y1, y2, h, w, out=yuv_out),
+        "forward_u8": lambda: m.forward_u8(u1, u2, out=u8_out),
+    }
+    res = {"shape": [b, h, w], "network": "rgb 6->3", "ms": {}, "spread_ms": {}, "share_of_step": {},
+           "protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of "
+                       f"{a.iters} calls"}
+    for prec in a.precisions.split(","):
+        m.precision = prec
+        for fn in cases.values():
+            for _ in range(a.warmup):
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in cases}
+        for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
+            for k, fn in cases.items():
+                ms[k].append(_time(fn, a.iters))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        res["ms"][prec] = med
+        res["spread_ms"][prec] = {k: [min(v), max(v)] for k, v in ms.items()}
+        res["share_of_step"][prec] = {k: (med[k] - med["forward"]) / med[k]
+                                      for k in ("forward_p10", "forward_yuv420p10")}
+        for k in cases:
+            print(f"{prec:7s} {k:18s} {med[k]:8.3f} ms  (reps {min(ms[k]):.3f}-{max(ms[k]):.3f})")
+        for k, v in res["share_of_step"][prec].items():
+            print(f"{prec:7s} extra passes of {k}: {100 * v:.2f} % of its step")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
