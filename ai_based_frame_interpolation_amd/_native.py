@@ -21,9 +21,9 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FIUNET_LIB") or os.path.join(_PKG, "libfiunet_hip.so")  # FIUNET_LIB: A/B builds
 CSRC = os.path.join(_PKG, "csrc")
 
-ABI_VERSION = 7        # include/fiunet.h FIUNET_ABI_VERSION this binding is written for
+ABI_VERSION = 8        # include/fiunet.h FIUNET_ABI_VERSION this binding is written for
 ABI_MIN_COMPAT = 4     # oldest A/B library (FIUNET_LIB) whose shared entry points have today's signatures
-FP32, BF16, BF16X2 = 0, 1, 2   # include/fiunet.h: enum fiunet_precision
+FP32, BF16, BF16X2, FP16 = 0, 1, 2, 3   # include/fiunet.h: enum fiunet_precision
 OPT_UNFUSED, OPT_KEEP_ALL, OPT_GATHER_UPSAMPLE = 1, 2, 16
 OPT_RNE_WEIGHTS, OPT_NO_DITHER = 32, 64
 YUV_MPEG2, YUV_BT709, YUV_FULL_RANGE, YUV_BT2020 = 1, 2, 4, 8   # include/fiunet.h: enum fiunet_colour
@@ -213,8 +213,8 @@ class Context:
         self._prepared = set()
 
     def prepare(self, precision: int) -> None:
-        """Weight copies a precision needs beyond the load's (bf16x2: the two-piece copies, built on first use so
-        that fp32 / bf16 users pay neither their memory nor their packing time).  Allocates: not under capture."""
+        """Weight copies a precision needs beyond the load's (bf16x2: the two-piece copies; fp16: the fp16 copies; built on
+        first use so that fp32 / bf16 users pay neither their memory nor their packing time).  Allocates: not under capture."""
         if precision not in self._prepared:
             check(lib().fiunet_prepare_precision(self._h, precision), "fiunet_prepare_precision")
             self._prepared.add(precision)

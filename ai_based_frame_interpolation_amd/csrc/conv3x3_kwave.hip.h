@@ -1,7 +1,7 @@
 // conv3x3_kwave.hip.h -- the fused 3x3 conv of conv3x3_mfma.hip.h for SMALL problems with a long K loop, with the K
 // loop cut INSIDE the workgroup: the four waves of a workgroup work on the SAME 64 couts x 2x32 pixels, each on its own
 // quarter of the input planes, against its own private in-tile and weight ring in LDS, and meet once, through LDS, at
-// the end.  gfx950 only; all three precisions.
+// the end.  gfx950 only; every precision.
 //
 // Why (round 6): the reference itself only ever forwards ONE 256x256 pair
 // (/root/reference/model/inference.py:29,101-122).  At that size a deep layer has 4-64 tiles and 8-32 planes of K; a lone
@@ -41,7 +41,8 @@ struct KWaveTile {
 // X2: precision "bf16x2" (SRC_DIRECT_X2 of conv3x3_mfma.hip.h): two-piece activations [hi planes | lo planes] and weights
 // [wh | wl]; a wave's quarter is a range of REAL planes, each run as three virtual planes - (xh, wh), (xh, wl) on the same
 // in-tile, (xl, wh) - and the epilogue writes the two pieces of the output.
-// T: __bf16 (precisions "bf16" / "bf16x2") or float (the exact-fp32 path: same 64-B plane records and LDS images, 16
+// T: __bf16 (precisions "bf16" / "bf16x2"), _Float16 (precision "fp16": the bf16 form on v_mfma_f32_16x16x32_f16) or
+// float (the exact-fp32 path: same 64-B plane records and LDS images, 16
 // channels per plane, four fp32 MFMAs per fragment pair - there a step is MFMA time, so the kernel is chosen where it keeps
 // every SIMD of the chip busy, i.e. from 256 workgroups x 4 waves on, and what it saves is the slab and the reduce dispatch).
 template <int EPI, bool X2 = false, typename T = __bf16>
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_kwave_kernel(const ConvArgs a)
 {
     using Tile = KWaveTile;
     constexpr int PL = Elem<T>::PL;
-    static_assert(!X2 || sizeof(T) == 2, "two-piece operands are bf16");
+    static_assert(!X2 || std::is_same_v<T, __bf16>, "two-piece operands are bf16");
     constexpr int TWP = Tile::TWP, THP = Tile::THP, TW = Tile::TW, TH = Tile::TH, BN = Tile::BN;
     constexpr int FR = 2, NF = 4, ROWS_W = 2;
     static_assert(EPI == EPI_PLAIN || EPI == EPI_POOL, "plain or pooled epilogue");

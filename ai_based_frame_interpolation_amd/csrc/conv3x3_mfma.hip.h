@@ -6,7 +6,7 @@
 //   * MaxPool2d(2) of Down (unet.py:28)           -> EPI_POOL: the producer also writes the pooled copy
 //   * Upsample + F.pad + torch.cat of Up (:46-54) -> SRC_CONCAT_UP: interpolated inside the gather
 //   * OutConv 1x1 + bias (:60)                    -> EPI_HEAD / EPI_HEAD3: reduced in the epilogue
-//   * the 2->64 stem conv (:72), bf16 gray path   -> SRC_STEM: evaluated inside the gather
+//   * the 2->64 stem conv (:72), bf16 / fp16 gray -> SRC_STEM: evaluated inside the gather
 // so none of the pooled-input re-reads, upsampled, concatenated, stem-output or last-activation
 // tensors is ever materialised in HBM.  The same kernel runs precision "bf16x2" (gather mode SRC_DIRECT_X2: two bf16
 // pieces per activation and weight, three MFMAs per product - the reference's fp32 tolerance on the bf16 pipe).
@@ -36,7 +36,8 @@
 //     The in-tile row pitch is padded to a multiple of 8 pixels so the swizzle term of a lane
 //     does not depend on the tile row.
 //   * Each wave owns 64 couts x 128 pixels = 4 x 8 accumulator tiles (128 VGPRs).
-//   * bf16: v_mfma_f32_16x16x32_bf16 (one per A/B chunk pair); fp32: 4 x v_mfma_f32_16x16x4_f32
+//   * bf16: v_mfma_f32_16x16x32_bf16 (one per A/B chunk pair); fp16: v_mfma_f32_16x16x32_f16 (same shape and operand
+//     layout: the bf16 instantiations with IEEE half values); fp32: 4 x v_mfma_f32_16x16x4_f32
 //     per chunk pair (exact fp32 FMA chain) -- same kernel body, same LDS images.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,6 +48,7 @@ namespace fiunet {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 enum SrcMode { SRC_DIRECT = 0, SRC_POOL = 1 /* host-side tag only */, SRC_CONCAT_UP = 2,
                SRC_STEM = 3 /* input = stem conv of the raw frame pair, computed in the gather */,
@@ -131,6 +133,11 @@ template <> struct Elem<__bf16> {
     static constexpr int PL = 32;
     static constexpr int NE = 8;
 };
+// precision "fp16": the bf16 layout (2-byte elements, 32 channels per plane) with IEEE half values
+template <> struct Elem<_Float16> {
+    static constexpr int PL = 32;
+    static constexpr int NE = 8;
+};
 
 // ---- 16-byte chunk helpers -------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ void chunk_unpack(const uint4& c, float* f);
@@ -145,6 +152,14 @@ template <> __device__ __forceinline__ void chunk_unpack<__bf16>(const uint4& c,
     f[2] = __uint_as_float(c.y << 16); f[3] = __uint_as_float(c.y & 0xffff0000u);
     f[4] = __uint_as_float(c.z << 16); f[5] = __uint_as_float(c.z & 0xffff0000u);
     f[6] = __uint_as_float(c.w << 16); f[7] = __uint_as_float(c.w & 0xffff0000u);
+}
+template <> __device__ __forceinline__ void chunk_unpack<_Float16>(const uint4& c, float* f)
+{
+    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+    const f16x2 a = __builtin_bit_cast(f16x2, c.x), b = __builtin_bit_cast(f16x2, c.y);
+    const f16x2 d = __builtin_bit_cast(f16x2, c.z), e = __builtin_bit_cast(f16x2, c.w);
+    f[0] = (float)a[0]; f[1] = (float)a[1]; f[2] = (float)b[0]; f[3] = (float)b[1];
+    f[4] = (float)d[0]; f[5] = (float)d[1]; f[6] = (float)e[0]; f[7] = (float)e[1];
 }
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi)
 {
@@ -162,6 +177,27 @@ __device__ __forceinline__ unsigned pack_bf16x2_pk(float lo, float hi)
     typedef __attribute__((ext_vector_type(2))) float f32x2;
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
 }
+// fp32 pair -> fp16 pair, round to nearest even (v_cvt_pk_f16_f32; never the round-toward-zero pkrtz form), SATURATED:
+// clamped to +-65504 first (one v_med3_f32 each), so that a value beyond the fp16 range becomes the largest finite one
+// instead of inf (and a later inf * 0 = NaN).  fp16 subnormals are kept (no denormal flush in this library's flags).
+__device__ __forceinline__ unsigned pack_f16x2(float lo, float hi)
+{
+    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+    typedef __attribute__((ext_vector_type(2))) float f32x2;
+    const float a = __builtin_amdgcn_fmed3f(lo, -65504.0f, 65504.0f), b = __builtin_amdgcn_fmed3f(hi, -65504.0f, 65504.0f);
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, f16x2));
+}
+// The 2-byte packing of the element type: the bf16 kernels keep their two spellings (see above), fp16 has one.
+template <typename T> __device__ __forceinline__ unsigned pack2(float lo, float hi)
+{
+    if constexpr (std::is_same_v<T, _Float16>) return pack_f16x2(lo, hi);
+    else return pack_bf16x2(lo, hi);
+}
+template <typename T> __device__ __forceinline__ unsigned pack2_pk(float lo, float hi)
+{
+    if constexpr (std::is_same_v<T, _Float16>) return pack_f16x2(lo, hi);
+    else return pack_bf16x2_pk(lo, hi);
+}
 template <typename T> __device__ __forceinline__ uint4 chunk_pack(const float* f);
 template <> __device__ __forceinline__ uint4 chunk_pack<float>(const float* f)
 {
@@ -172,6 +208,11 @@ template <> __device__ __forceinline__ uint4 chunk_pack<__bf16>(const float* f)
 {
     return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]),
                       pack_bf16x2(f[6], f[7]));
+}
+template <> __device__ __forceinline__ uint4 chunk_pack<_Float16>(const float* f)
+{
+    return make_uint4(pack_f16x2(f[0], f[1]), pack_f16x2(f[2], f[3]), pack_f16x2(f[4], f[5]),
+                      pack_f16x2(f[6], f[7]));
 }
 
 typedef __attribute__((ext_vector_type(2))) short s16x2;
@@ -196,6 +237,14 @@ __device__ __forceinline__ uint4 chunk_max4<__bf16>(const uint4& a, const uint4&
                       pk_max_i16(pk_max_i16(a.y, b.y), pk_max_i16(c.y, d.y)),
                       pk_max_i16(pk_max_i16(a.z, b.z), pk_max_i16(c.z, d.z)),
                       pk_max_i16(pk_max_i16(a.w, b.w), pk_max_i16(c.w, d.w)));
+}
+
+// fp16: the same integer max - for x >= 0 the fp16 order is the int16 order of the bit patterns too
+template <>
+__device__ __forceinline__ uint4 chunk_max4<_Float16>(const uint4& a, const uint4& b, const uint4& c,
+                                                      const uint4& d)
+{
+    return chunk_max4<__bf16>(a, b, c, d);
 }
 
 template <>
@@ -428,6 +477,13 @@ __device__ __forceinline__ void mma_chunk<__bf16>(f32x4& acc, const uint4& wa, c
                                                   __builtin_bit_cast(bf16x8, xb), acc, 0, 0, 0);
 }
 template <>
+__device__ __forceinline__ void mma_chunk<_Float16>(f32x4& acc, const uint4& wa, const uint4& xb)
+{
+    // the same shape, operand layout (8 values per lane, k-slots lane group*8 .. +7) and rate as the bf16 instruction
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wa),
+                                                 __builtin_bit_cast(f16x8, xb), acc, 0, 0, 0);
+}
+template <>
 __device__ __forceinline__ void mma_chunk<float>(f32x4& acc, const uint4& wa, const uint4& xb)
 {
     // lane group g = lane>>4 holds channels 4g..4g+3 of the plane in both operands; MFMA i
@@ -577,6 +633,7 @@ __device__ __forceinline__ void conv_acc_init(const ConvArgs& a, f32x4 (&acc)[4]
 }
 
 // bf16 pair -> relu on the packed pair: for x < 0 (sign bit set, incl. -0.0) the int16 pattern is negative
+// (the same holds for an fp16 pair: the fp16 kernels use it too)
 __device__ __forceinline__ unsigned relu_pk_bf16(unsigned p) { return pk_max_i16(p, 0u); }
 // sum += max(x, lo) * w: v_max_f32 + v_fmac_f32 as one block (fmaxf() costs a canonicalising
 // v_max(x, x) in front, and a lone inline-asm v_max an s_nop behind)
@@ -708,7 +765,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4]
     if constexpr (X2) {
         // precision "bf16x2": relu(acc) in fp32 -> two bf16 pieces, stored [hi planes | lo planes] (two 16-B stores per
         // lane and tile pair; a fused-head conv stores only when the read-back keeps its activation)
-        static_assert(sizeof(T) == 2, "the two-piece epilogue belongs to the bf16 kernels");
+        static_assert(std::is_same_v<T, __bf16>, "the two-piece epilogue belongs to the bf16 kernels");
         if (HNC > 0 && !a.dst) return;
         const size_t ps = (size_t)aH * aW * 64;                  // bytes of one 32-channel plane
         const int npo = a.Cout / 32;                             // planes per piece; the tensor has 2 * npo
@@ -792,10 +849,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4]
                 char* o = out_img + (size_t)(y * aW + x) * 64;
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
-                    uint4 v = make_uint4(pack_bf16x2_pk(acc[2 * g][nn][0], acc[2 * g][nn][1]),
-                                         pack_bf16x2_pk(acc[2 * g][nn][2], acc[2 * g][nn][3]),
-                                         pack_bf16x2_pk(acc[2 * g + 1][nn][0], acc[2 * g + 1][nn][1]),
-                                         pack_bf16x2_pk(acc[2 * g + 1][nn][2], acc[2 * g + 1][nn][3]));
+                    uint4 v = make_uint4(pack2_pk<T>(acc[2 * g][nn][0], acc[2 * g][nn][1]),
+                                         pack2_pk<T>(acc[2 * g][nn][2], acc[2 * g][nn][3]),
+                                         pack2_pk<T>(acc[2 * g + 1][nn][0], acc[2 * g + 1][nn][1]),
+                                         pack2_pk<T>(acc[2 * g + 1][nn][2], acc[2 * g + 1][nn][3]));
                     if (a.relu) v = make_uint4(relu_pk_bf16(v.x), relu_pk_bf16(v.y), relu_pk_bf16(v.z), relu_pk_bf16(v.w));
                     pk[r][g] = v;
                     if (ok && out_img) *reinterpret_cast<uint4*>(o + g * plane_stride) = v;
@@ -828,10 +885,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4]
             if constexpr (PERM) {
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
-                    uint4 pk = make_uint4(pack_bf16x2(acc[2 * g][n][0], acc[2 * g][n][1]),
-                                          pack_bf16x2(acc[2 * g][n][2], acc[2 * g][n][3]),
-                                          pack_bf16x2(acc[2 * g + 1][n][0], acc[2 * g + 1][n][1]),
-                                          pack_bf16x2(acc[2 * g + 1][n][2], acc[2 * g + 1][n][3]));
+                    uint4 pk = make_uint4(pack2<T>(acc[2 * g][n][0], acc[2 * g][n][1]),
+                                          pack2<T>(acc[2 * g][n][2], acc[2 * g][n][3]),
+                                          pack2<T>(acc[2 * g + 1][n][0], acc[2 * g + 1][n][1]),
+                                          pack2<T>(acc[2 * g + 1][n][2], acc[2 * g + 1][n][3]));
                     if (a.relu) pk = make_uint4(relu_pk_bf16(pk.x), relu_pk_bf16(pk.y), relu_pk_bf16(pk.z), relu_pk_bf16(pk.w));
                     *reinterpret_cast<uint4*>(o + g * plane_stride) = pk;
                 }
@@ -882,10 +939,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4]
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int m = 2 * g + h;
-                        const unsigned a0 = pk_max_i16(pack_bf16x2_pk(acc[m][n][0], acc[m][n][1]),
-                                                       pack_bf16x2_pk(acc[m][n + FR][0], acc[m][n + FR][1]));
-                        const unsigned a1 = pk_max_i16(pack_bf16x2_pk(acc[m][n][2], acc[m][n][3]),
-                                                       pack_bf16x2_pk(acc[m][n + FR][2], acc[m][n + FR][3]));
+                        const unsigned a0 = pk_max_i16(pack2_pk<T>(acc[m][n][0], acc[m][n][1]),
+                                                       pack2_pk<T>(acc[m][n + FR][0], acc[m][n + FR][1]));
+                        const unsigned a1 = pk_max_i16(pack2_pk<T>(acc[m][n][2], acc[m][n][3]),
+                                                       pack2_pk<T>(acc[m][n + FR][2], acc[m][n + FR][3]));
                         r[2 * h] = pk_max_i16(a0, dpp_swap_pairs(a0));
                         r[2 * h + 1] = pk_max_i16(a1, dpp_swap_pairs(a1));
                         if (a.relu) { r[2 * h] = relu_pk_bf16(r[2 * h]); r[2 * h + 1] = relu_pk_bf16(r[2 * h + 1]); }
@@ -919,8 +976,8 @@ __global__ __launch_bounds__(256, conv_occupancy(BN, TH, TW, ConvTile<BN, TH, TW
     constexpr bool X2 = src_is_x2(MODE);
     constexpr bool STEM = src_is_stem(MODE);
     constexpr bool DIRECT = MODE == SRC_DIRECT || MODE == SRC_DIRECT_X2;
-    static_assert(!X2 || sizeof(T) == 2, "two-piece operands are bf16");
-    static_assert(!STEM || (sizeof(T) == 2 && BN == 64), "fused stem: bf16, 64 couts");
+    static_assert(!X2 || std::is_same_v<T, __bf16>, "two-piece operands are bf16");
+    static_assert(!STEM || (sizeof(T) == 2 && BN == 64), "fused stem: 2-byte output (bf16 / fp16), 64 couts");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const lds_in = smem;
@@ -1425,19 +1482,20 @@ __global__ __launch_bounds__(256, conv_occupancy(BN, TH, TW, ConvTile<BN, TH, TW
 #pragma unroll
                 for (int h = 0; h < 2; ++h) s4[h] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int h = 0; h < 2; ++h) mma_chunk<T>(s4[h], w.wl[h], f.bh);
+                for (int h = 0; h < 2; ++h) mma_chunk<__bf16>(s4[h], w.wl[h], f.bh);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) mma_chunk<T>(s4[h], w.wh[h], f.bl);
+                for (int h = 0; h < 2; ++h) mma_chunk<__bf16>(s4[h], w.wh[h], f.bl);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) mma_chunk<T>(s4[h], w.wh[h], f.bh);
+                for (int h = 0; h < 2; ++h) mma_chunk<__bf16>(s4[h], w.wh[h], f.bh);
                 // packed row lc*4 + j of tile h is channel lc*8 + h*4 + j of the plane (host:
                 // bf16_row_to_cout): the lane's 8 values are ONE 16-B chunk of the pixel's record - one
                 // ds_write_b128 (2-way bank conflicts) instead of two ds_write_b64 (4-way)
                 const int row = f.dst;
-                uint4 pk = make_uint4(relu_pk_bf16(pack_bf16x2_pk(s4[0][0], s4[0][1])),
-                                      relu_pk_bf16(pack_bf16x2_pk(s4[0][2], s4[0][3])),
-                                      relu_pk_bf16(pack_bf16x2_pk(s4[1][0], s4[1][1])),
-                                      relu_pk_bf16(pack_bf16x2_pk(s4[1][2], s4[1][3])));
+                // (the split MFMAs are bf16 whatever the output type; precision "fp16" rounds the result to fp16 here)
+                uint4 pk = make_uint4(relu_pk_bf16(pack2_pk<T>(s4[0][0], s4[0][1])),
+                                      relu_pk_bf16(pack2_pk<T>(s4[0][2], s4[0][3])),
+                                      relu_pk_bf16(pack2_pk<T>(s4[1][0], s4[1][1])),
+                                      relu_pk_bf16(pack2_pk<T>(s4[1][2], s4[1][3])));
                 if constexpr (X2) {
                     if (lo_piece) {   // (wave-uniform) lo = RNE bf16 of relu(v) - hi; a negative v has hi = lo = +0
                         auto lo2 = [](float v0, float v1, unsigned hi) __attribute__((always_inline)) {

@@ -74,6 +74,7 @@ struct ConvWeights {
     void* w_f32 = nullptr;   // packed [cin/16][kx][ky][cout][16] fp32   (conv 0: [9][cin][64])
     void* w_bf16 = nullptr;  // packed [cin/32][kx][ky][cout][32] bf16
     void* w_x2 = nullptr;    // FIUNET_BF16X2 (fiunet_prepare_precision): two pieces [wh | wl], each packed like w_bf16
+    void* w_f16 = nullptr;   // FIUNET_FP16 (fiunet_prepare_precision): packed like w_bf16, IEEE half values
     float* scale = nullptr;
     float* shift = nullptr;
 };
@@ -126,6 +127,15 @@ inline uint16_t f32_to_bf16_feedback(float v, double& carry)
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+inline bool valid_precision(int p) { return p == FIUNET_FP32 || p == FIUNET_BF16 || p == FIUNET_BF16X2 || p == FIUNET_FP16; }
+// bf16 and fp16: one 2-byte element per activation and weight (32 channels per 64-B plane, the same MFMA shape), so both
+// take every branch of the launch rule and the same workspace layout; fp32 and bf16x2 (two bf16 pieces) have 4 bytes
+inline bool two_byte_elems(int p) { return p != FIUNET_FP32 && p != FIUNET_BF16X2; }
+template <typename T> constexpr const char* elem_name()
+{
+    return std::is_same_v<T, _Float16> ? "f16" : sizeof(T) == 2 ? "bf16" : "f32";
+}
+
 }  // namespace
 
 struct fiunet_ctx {
@@ -133,8 +143,9 @@ struct fiunet_ctx {
     int cf = 1;  // channels per frame
     bool bilinear = true;          // false: ConvTranspose2d decoder (unet.py:42-44)
     const int* cout = kCoutBil;    // output channels per conv of this architecture
-    struct { int cin = 0, cout = 0; void* w_f32 = nullptr; void* w_bf16 = nullptr; void* w_x2 = nullptr; float* bias = nullptr; } convt[4];
+    struct { int cin = 0, cout = 0; void* w_f32 = nullptr; void* w_bf16 = nullptr; void* w_x2 = nullptr; void* w_f16 = nullptr; float* bias = nullptr; } convt[4];
     bool x2_ready = false;         // the two-piece weight copies exist (fiunet_prepare_precision(FIUNET_BF16X2))
+    bool f16_ready = false;        // the fp16 weight copies exist (fiunet_prepare_precision(FIUNET_FP16))
     unsigned flags = 0;
     bool loaded = false;
     ConvWeights conv[NCONV];
@@ -173,8 +184,9 @@ void free_weights(fiunet_ctx* ctx)
     ctx->owned.clear();
     ctx->loaded = false;
     ctx->x2_ready = false;
-    for (auto& c : ctx->conv) c.w_x2 = nullptr;     // (fiunet_prepare_precision reuses a non-null copy)
-    for (auto& c : ctx->convt) c.w_x2 = nullptr;
+    ctx->f16_ready = false;
+    for (auto& c : ctx->conv) c.w_x2 = c.w_f16 = nullptr;     // (fiunet_prepare_precision reuses a non-null copy)
+    for (auto& c : ctx->convt) c.w_x2 = c.w_f16 = nullptr;
 }
 
 thread_local std::string* g_name_out = nullptr;  // where the next conv launch reports its kernel
@@ -204,7 +216,7 @@ int launch_conv_cfg(ConvArgs a, hipStream_t s)
 {
     char name[128] = "";
     if (g_name_out)
-        std::snprintf(name, sizeof name, "conv3x3_mfma_kernel<%s,%d,%d,%d,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BN, TH, TW,
+        std::snprintf(name, sizeof name, "conv3x3_mfma_kernel<%s,%d,%d,%d,%d,%d>", elem_name<T>(), BN, TH, TW,
                       MODE, EPI);
     a.tilesX = (a.W + TW - 1) / TW;
     a.tilesY = (a.H + TH - 1) / TH;
@@ -530,7 +542,7 @@ bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p)
     if ((long long)H * W >= (1LL << 26)) return false;
     plan_stages(n, precision, B, H, W, p.st);
     const bool keep_all = n.flags & FIUNET_OPT_KEEP_ALL;
-    const size_t es = precision == FIUNET_BF16 ? 2 : 4;   // bytes per activation element (bf16x2: two pieces)
+    const size_t es = two_byte_elems(precision) ? 2 : 4;   // bytes per activation element (bf16x2: two pieces)
     p.hs[0] = H; p.ws[0] = W;
     for (int k = 1; k < 5; ++k) { p.hs[k] = p.hs[k - 1] / 2; p.ws[k] = p.ws[k - 1] / 2; }
     struct Buf { size_t bytes; int first, last; size_t* off; };
@@ -593,7 +605,7 @@ template <typename T, int EPI, bool X2> int launch_kwave(ConvArgs a, hipStream_t
     using Tile = KWaveTile;
     char name[96] = "";
     if (g_name_out)
-        std::snprintf(name, sizeof name, "conv3x3_kwave_kernel<%s%s,64,2,32,%d>+kwave4", sizeof(T) == 2 ? "bf16" : "f32", X2 ? "x2" : "", EPI);
+        std::snprintf(name, sizeof name, "conv3x3_kwave_kernel<%s%s,64,2,32,%d>+kwave4", elem_name<T>(), X2 ? "x2" : "", EPI);
     a.tilesX = (a.W + Tile::TW - 1) / Tile::TW;
     a.tilesY = (a.H + Tile::TH - 1) / Tile::TH;
     a.nct = a.Cout / Tile::BN;
@@ -656,24 +668,28 @@ template <typename T> int launch_conv(const ConvArgs& a, int mode, int epi, cons
     if (mode == SRC_DIRECT && epi == EPI_HEAD) return launch_conv_shape<T, SRC_DIRECT, EPI_HEAD>(a, cfg, s);
     if (mode == SRC_DIRECT && epi == EPI_HEAD3) return launch_conv_shape<T, SRC_DIRECT, EPI_HEAD3>(a, cfg, s);
     if (mode == SRC_DIRECT && epi == EPI_POOL) return launch_conv_shape<T, SRC_DIRECT, EPI_POOL>(a, cfg, s);
-    if constexpr (sizeof(T) == 2) {   // FIUNET_BF16X2: two-piece operands
+    if constexpr (std::is_same_v<T, __bf16>) {   // FIUNET_BF16X2: two-piece operands
         if (mode == SRC_DIRECT_X2 && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_PLAIN>(a, cfg, s);
         if (mode == SRC_DIRECT_X2 && epi == EPI_POOL) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_POOL>(a, cfg, s);
         if (mode == SRC_DIRECT_X2 && epi == EPI_HEAD) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_HEAD>(a, cfg, s);
         if (mode == SRC_DIRECT_X2 && epi == EPI_HEAD3) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_HEAD3>(a, cfg, s);
-        if ((mode == SRC_STEM || mode == SRC_STEM_X2) && epi == EPI_POOL && a.Cout == 64) {  // 32-wide tiles only (the patch layout)
-            if (mode == SRC_STEM)
-                return cfg.small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM, EPI_POOL>(a, s)
-                                 : launch_conv_cfg<T, 64, 16, 32, SRC_STEM, EPI_POOL>(a, s);
+        if (mode == SRC_STEM_X2 && epi == EPI_POOL && a.Cout == 64)
             return cfg.small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM_X2, EPI_POOL>(a, s)
                              : launch_conv_cfg<T, 64, 16, 32, SRC_STEM_X2, EPI_POOL>(a, s);
-        }
+    }
+    if constexpr (sizeof(T) == 2) {   // the fused gray stem (bf16, fp16): 32-wide tiles only (the patch layout)
+        if (mode == SRC_STEM && epi == EPI_POOL && a.Cout == 64)
+            return cfg.small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM, EPI_POOL>(a, s)
+                             : launch_conv_cfg<T, 64, 16, 32, SRC_STEM, EPI_POOL>(a, s);
     }
     return fail(FIUNET_ERR_INVALID_ARG, "unsupported gather/epilogue combination");
 }
 
 // The band [y_origin, y_origin + H) of an image of Hg rows (un-tiled: y_origin = 0, Hg = H), launched as the plan `p.st`
-// says.  T = float (FIUNET_FP32) or __bf16 (FIUNET_BF16, FIUNET_BF16X2).
+// says.  T = float (FIUNET_FP32), __bf16 (FIUNET_BF16, FIUNET_BF16X2) or _Float16 (FIUNET_FP16).
+// FIUNET_FP16: the bf16 launch plan with IEEE half activations and weights (fiunet_prepare_precision builds the weight
+// copies): the same kernels instantiated for _Float16 (v_mfma_f32_16x16x32_f16), every rounding to fp16 RNE and saturated,
+// no stem dither; the stems keep the bf16 path's arithmetic (split-bf16 MFMAs / the exact fp32 kernel) and round to fp16.
 // FIUNET_BF16X2: the fp32 contract on the bf16 pipe (include/fiunet.h).  Activations are two-piece bf16 tensors
 // [hi planes | lo planes] (4 B per element), weights [wh | wl]; every conv is the bf16 direct kernel in mode
 // SRC_DIRECT_X2 (three virtual planes per real plane: (xh, wh), (xh, wl) on the same in-tile, (xl, wh)), the stem is the
@@ -688,10 +704,13 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
                  const uint8_t* u2 = nullptr, uint8_t* out_u8 = nullptr,
                  size_t out_img_stride = 0 /* elements between images of out / out_u8; 0 = contiguous */)
 {
-    const bool x2 = precision == FIUNET_BF16X2, bf16 = precision == FIUNET_BF16;
+    const bool x2 = precision == FIUNET_BF16X2, bf16 = precision == FIUNET_BF16, f16 = precision == FIUNET_FP16;
     if (x2 && !ctx->x2_ready)
         return fail(FIUNET_ERR_NOT_LOADED, "precision bf16x2: call fiunet_prepare_precision(ctx, FIUNET_BF16X2) after "
                                            "fiunet_load_weights (it builds the two-piece weight copies)");
+    if (f16 && !ctx->f16_ready)
+        return fail(FIUNET_ERR_NOT_LOADED, "precision fp16: call fiunet_prepare_precision(ctx, FIUNET_FP16) after "
+                                           "fiunet_load_weights (it builds the fp16 weight copies)");
     const StageLaunch* L = p.st;
     const size_t es = x2 ? 4 : sizeof(T);   // bytes per activation element
     int hg[5];  // rows of the whole image at each pyramid level (floor halving, unet.py:28)
@@ -728,6 +747,9 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
         if (x2)
             hipLaunchKernelGGL(stem_rgb_split_kernel<true>, g2, dim3(256), 0, s, f1, f2, (const float*)c0.w_f32, c0.scale,
                                c0.shift, (__bf16*)act(0), B, H, W, dither, u1, u2);
+        else if (f16)
+            hipLaunchKernelGGL((stem_rgb_split_kernel<false, _Float16>), g2, dim3(256), 0, s, f1, f2, (const float*)c0.w_f32, c0.scale,
+                               c0.shift, (_Float16*)act(0), B, H, W, 0.f, u1, u2);
         else
             hipLaunchKernelGGL(stem_rgb_split_kernel<false>, g2, dim3(256), 0, s, f1, f2, (const float*)c0.w_f32, c0.scale,
                                c0.shift, (__bf16*)act(0), B, H, W, dither, u1, u2);
@@ -751,9 +773,9 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
         if (L[0].form == STEM_FUSED) ctx->layer_name[0] = "(stem fused into next stage)";
         else if (x2) ctx->layer_name[0] = L[0].form == STEM_FIRST ? "conv3x3_first_kernel<f32 arithmetic, two-piece output>"
                                                                   : "stem_rgb_split_kernel<two-piece output>";
-        else ctx->layer_name[0] = L[0].form == STEM_FIRST ? std::string("conv3x3_first_kernel<") + (bf16 ? "bf16" : "f32") + "," +
+        else ctx->layer_name[0] = L[0].form == STEM_FIRST ? std::string("conv3x3_first_kernel<") + elem_name<T>() + "," +
                                                                 std::to_string(ctx->cf) + ">"
-                                                          : std::string("stem_rgb_split_kernel");
+                                                          : std::string(f16 ? "stem_rgb_split_kernel<fp16 output>" : "stem_rgb_split_kernel");
         ctx->layer_flops[0] = L[0].form == STEM_FUSED ? 0.0 : stem_flops;
     }
     for (int i = 1; i < NCONV; ++i) {
@@ -764,7 +786,7 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
         std::memset(&a, 0, sizeof(a));
         a.B = B; a.H = p.hs[lv]; a.W = p.ws[lv];
         a.Cout = cw.cout;
-        a.wgt = x2 ? cw.w_x2 : bf16 ? cw.w_bf16 : cw.w_f32;
+        a.wgt = x2 ? cw.w_x2 : bf16 ? cw.w_bf16 : f16 ? cw.w_f16 : cw.w_f32;
         a.scale = cw.scale; a.shift = cw.shift;
         a.relu = 1;
         a.ksplit = 1;
@@ -807,7 +829,7 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
                 const auto& ct = ctx->convt[(i - 10) / 2];
                 ConvTArgs c;
                 std::memset(&c, 0, sizeof(c));
-                c.low = a.src1; c.wgt = x2 ? ct.w_x2 : bf16 ? ct.w_bf16 : ct.w_f32; c.bias = ct.bias; c.dst = up;
+                c.low = a.src1; c.wgt = x2 ? ct.w_x2 : bf16 ? ct.w_bf16 : f16 ? ct.w_f16 : ct.w_f32; c.bias = ct.bias; c.dst = up;
                 c.B = B; c.H = a.H; c.W = a.W; c.lowH = a.lowH; c.lowW = a.lowW; c.Cin = ct.cin; c.Cout = ct.cout;
                 c.padT = a.padT; c.padL = a.padL; c.upOffY = a.upOffY; c.lowOffY = a.lowOffY; c.lowHg = a.lowHg;
                 if (a.C1 != ct.cin) return fail(FIUNET_ERR_INVALID_ARG, "internal: transposed-conv channel plan mismatch");
@@ -816,7 +838,7 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
                 const long long units = (long long)B * a.lowH * ((a.lowW + 31) / 32) * (ct.cout / 64);   // 32 pixels per wave
                 const dim3 grid((unsigned)std::min<long long>((units + 3) / 4, 256 * 16));
                 if (x2) {
-                    if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((convt2x2_kernel<T, true>), grid, dim3(256), 0, s, c);
+                    if constexpr (std::is_same_v<T, __bf16>) hipLaunchKernelGGL((convt2x2_kernel<T, true>), grid, dim3(256), 0, s, c);
                 } else
                     hipLaunchKernelGGL((convt2x2_kernel<T>), grid, dim3(256), 0, s, c);
                 HIP_TRY(hipGetLastError());
@@ -870,6 +892,12 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
     }
     if (ev) HIP_TRY(hipEventRecord(ev[NCONV], s));
     return FIUNET_OK;
+}
+
+// the forward instantiation of a (valid) precision
+auto forward_of(int precision)
+{
+    return precision == FIUNET_FP32 ? forward_impl<float> : precision == FIUNET_FP16 ? forward_impl<_Float16> : forward_impl<__bf16>;
 }
 
 NetDesc net_of(const fiunet_ctx* c)
@@ -1080,9 +1108,35 @@ int fiunet_load_weights(fiunet_ctx* ctx, int n, const char* const* names,
 int fiunet_prepare_precision(fiunet_ctx* ctx, int precision)
 {
     if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "ctx is NULL");
-    if (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2)
-        return fail(FIUNET_ERR_INVALID_ARG, "bad precision");
+    if (!valid_precision(precision)) return fail(FIUNET_ERR_INVALID_ARG, "bad precision");
     if (!ctx->loaded) return fail(FIUNET_ERR_NOT_LOADED, "fiunet_prepare_precision before fiunet_load_weights");
+    if (precision == FIUNET_FP16) {
+        if (ctx->f16_ready) return FIUNET_OK;
+        HIP_TRY(hipSetDevice(ctx->device));
+        // fp16 weights, packed on the device from the fp32 copy (BatchNorm scale folded in) like the bf16 copy: ~35 MB more
+        auto pack16 = [&](const void* w32, int cin, int cout, int convt, void** out) -> int {
+            const size_t n = (size_t)cin * (convt ? 4 : 9) * cout;
+            void* d = *out;
+            if (!d) {
+                HIP_TRY(hipMalloc(&d, n * 2));
+                ctx->owned.push_back(d);
+                *out = d;
+            }
+            hipLaunchKernelGGL(f16_pack_weights_kernel, dim3(grid_for(n / 2)), dim3(256), 0, 0, (const float*)w32,
+                               (unsigned*)d, cin, cout, convt);
+            HIP_TRY(hipGetLastError());
+            return FIUNET_OK;
+        };
+        int rc;
+        for (int i = 1; i < NCONV; ++i)
+            if ((rc = pack16(ctx->conv[i].w_f32, ctx->conv[i].cin, ctx->conv[i].cout, 0, &ctx->conv[i].w_f16))) return rc;
+        if (!ctx->bilinear)
+            for (int k = 0; k < 4; ++k)
+                if ((rc = pack16(ctx->convt[k].w_f32, ctx->convt[k].cin, ctx->convt[k].cout, 1, &ctx->convt[k].w_f16))) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        ctx->f16_ready = true;
+        return FIUNET_OK;
+    }
     if (precision != FIUNET_BF16X2 || ctx->x2_ready) return FIUNET_OK;   // fp32 / bf16 copies are made by the load
     HIP_TRY(hipSetDevice(ctx->device));
     // two-piece weights [wh | wl], packed on the device from the fp32 copy (BatchNorm scale folded in): ~69 MB more
@@ -1113,7 +1167,7 @@ int fiunet_prepare_precision(fiunet_ctx* ctx, int precision)
 
 int fiunet_min_unsplit_batch(const fiunet_ctx* ctx, int H, int W, int precision)
 {
-    if (!ctx || H < 16 || W < 16 || (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2)) {
+    if (!ctx || H < 16 || W < 16 || !valid_precision(precision)) {
         g_err = "fiunet_min_unsplit_batch: bad arguments";
         return 0;
     }
@@ -1132,8 +1186,7 @@ int fiunet_min_unsplit_batch(const fiunet_ctx* ctx, int H, int W, int precision)
 
 static bool ctx_plan(const fiunet_ctx* ctx, int B, int H, int W, int precision, Plan& p)
 {
-    return ctx && (precision == FIUNET_FP32 || precision == FIUNET_BF16 || precision == FIUNET_BF16X2) &&
-           make_plan(net_of(ctx), B, H, W, precision, p);
+    return ctx && valid_precision(precision) && make_plan(net_of(ctx), B, H, W, precision, p);
 }
 
 size_t fiunet_workspace_bytes(const fiunet_ctx* ctx, int B, int H, int W, int precision)
@@ -1165,8 +1218,7 @@ int fiunet_forward_strip(fiunet_ctx* ctx, const float* frame1, const float* fram
     if (y_origin + H != H_image && H % 16 != 0)
         return fail(FIUNET_ERR_BAD_SHAPE, "strip: rows must be a multiple of 16 unless it ends the image");
     if (!ctx->loaded) return fail(FIUNET_ERR_NOT_LOADED, "fiunet_forward before fiunet_load_weights");
-    if (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2)
-        return fail(FIUNET_ERR_INVALID_ARG, "bad precision");
+    if (!valid_precision(precision)) return fail(FIUNET_ERR_INVALID_ARG, "bad precision");
     if (B < 1) return fail(FIUNET_ERR_INVALID_ARG, "B < 1");
     if (H < 16 || W < 16)
         return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
@@ -1177,7 +1229,7 @@ int fiunet_forward_strip(fiunet_ctx* ctx, const float* frame1, const float* fram
     if (workspace_bytes < p.total) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
     HIP_TRY(hipSetDevice(ctx->device));
-    auto fwd = precision == FIUNET_FP32 ? forward_impl<float> : forward_impl<__bf16>;
+    auto fwd = forward_of(precision);
     return fwd(ctx, precision, frame1, frame2, out, B, H, W, (char*)workspace, p, (hipStream_t)stream, y_origin, H_image,
                nullptr, nullptr, nullptr, 0);
 }
@@ -1242,7 +1294,7 @@ int fiunet_forward_u8_strided(fiunet_ctx* ctx, const uint8_t* frame1, const uint
     if (out_f32) o = (float*)extra;
     HIP_TRY(hipSetDevice(ctx->device));
     // the fused head writes the (possibly strided) uint8 destination itself; the fp32 staging buffer is contiguous
-    auto fwd = precision == FIUNET_FP32 ? forward_impl<float> : forward_impl<__bf16>;
+    auto fwd = forward_of(precision);
     if ((rc = fwd(ctx, precision, a, b, o, B, H, W, ws, p, (hipStream_t)stream, 0, H, in_f32 ? nullptr : frame1,
                   in_f32 ? nullptr : frame2, out_f32 ? nullptr : out, out_f32 ? 0 : out_image_stride)))
         return rc;
@@ -1658,8 +1710,7 @@ int fiunet_debug_force_cfg(fiunet_ctx* ctx, int layer, int tile, int ksplit)
 int fiunet_debug_choose_cfg(int precision, int B, int H, int W, int Cin, int Cout, int splittable, int concat_stage,
                             int kwave_ok, int* out /* [4] */)
 {
-    if (!out || B < 1 || H < 1 || W < 1 || Cin < 32 || (Cout != 64 && Cout % 128 != 0) ||
-        (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2))
+    if (!out || B < 1 || H < 1 || W < 1 || Cin < 32 || (Cout != 64 && Cout % 128 != 0) || !valid_precision(precision))
         return fail(FIUNET_ERR_INVALID_ARG, "fiunet_debug_choose_cfg: bad arguments");
     const bool concat = concat_stage >= 10;
     out[3] = concat && concat_stage < NCONV && kMode[concat_stage] == SRC_CONCAT_UP &&
@@ -1683,7 +1734,7 @@ int fiunet_debug_stage_cfg(int frame_channels, int bilinear, unsigned flags, int
                            int* out /* [6] */)
 {
     if (!out || (frame_channels != 1 && frame_channels != 3) || B < 1 || H < 16 || W < 16 || stage < 0 || stage >= NCONV ||
-        (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2))
+        !valid_precision(precision))
         return fail(FIUNET_ERR_INVALID_ARG, "fiunet_debug_stage_cfg: bad arguments");
     NetDesc n;
     n.cf = frame_channels;
@@ -1770,8 +1821,7 @@ int fiunet_debug_read_activation(fiunet_ctx* ctx, const void* workspace, int B, 
 {
     if (!ctx || tap < 0 || tap >= NCONV + 4 || (dst && !workspace))
         return fail(FIUNET_ERR_INVALID_ARG, "bad argument");
-    if (precision != FIUNET_FP32 && precision != FIUNET_BF16 && precision != FIUNET_BF16X2)
-        return fail(FIUNET_ERR_INVALID_ARG, "bad precision");
+    if (!valid_precision(precision)) return fail(FIUNET_ERR_INVALID_ARG, "bad precision");
     Plan p;
     if (dst && !(ctx->flags & FIUNET_OPT_KEEP_ALL))
         return fail(FIUNET_ERR_INVALID_ARG, "read-back needs FIUNET_OPT_KEEP_ALL set for the forward: without it "
@@ -1806,6 +1856,9 @@ int fiunet_debug_read_activation(fiunet_ctx* ctx, const void* workspace, int B, 
     else if (precision == FIUNET_BF16)
         hipLaunchKernelGGL((nhwc_to_nchw_f32_kernel<__bf16>), dim3(grid_for(n)), dim3(256), 0,
                            (hipStream_t)stream, (const __bf16*)src, dst, B, C, h, w);
+    else if (precision == FIUNET_FP16)
+        hipLaunchKernelGGL((nhwc_to_nchw_f32_kernel<_Float16>), dim3(grid_for(n)), dim3(256), 0,
+                           (hipStream_t)stream, (const _Float16*)src, dst, B, C, h, w);
     else
         hipLaunchKernelGGL((nhwc_to_nchw_f32_kernel<float>), dim3(grid_for(n)), dim3(256), 0,
                            (hipStream_t)stream, (const float*)src, dst, B, C, h, w);

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_kernel(
             for (int g = 0; g < KG; ++g) {
                 const int xx = x + dxs[g];
                 v[g] = (xx >= 0 && xx < W) ? p[g][(xt - xt0) * 16 + dxs[g]] : 0.f;
-                if constexpr (sizeof(T) == 2 && !X2) {  // the conv's zero padding stays exactly zero
+                if constexpr (std::is_same_v<T, __bf16> && !X2) {  // (bf16 only) the conv's zero padding stays exactly zero
                     // (row and frame of this k-slot are re-derived from koff through an opaque copy of y, so
                     // that hipcc does not hoist one more register per k-group out of the tile loop: the RGB
                     // instantiation would drop to one wave per SIMD)
@@ -182,10 +182,12 @@ __global__ __launch_bounds__(256) void conv3x3_first_kernel(
 #endif
 // X2 (precision bf16x2): `dst` is the two-piece tensor [hi planes | lo planes] of 2 x 64 channels - relu(acc) split in fp32
 // (the split-bf16 MFMAs' ~2^-16 relative accuracy is that precision's own class; no dither: the caller passes 0)
-template <bool X2 = false>
+// T: the element type of `dst` - __bf16, or _Float16 for precision "fp16": the split MFMAs are bf16 either way, only the
+// rounding of the output differs (fp16 runs without dither: the caller passes 0).
+template <bool X2 = false, typename T = __bf16>
 __global__ __launch_bounds__(256, FIUNET_RGB_STEM_OCC) void stem_rgb_split_kernel(
     const float* __restrict__ f1, const float* __restrict__ f2, const float* __restrict__ w,  // w: [9 taps][6][64] fp32
-    const float* __restrict__ scale, const float* __restrict__ shift, __bf16* __restrict__ dst, int B, int H, int W,
+    const float* __restrict__ scale, const float* __restrict__ shift, T* __restrict__ dst, int B, int H, int W,
     float dither, const uint8_t* __restrict__ u1, const uint8_t* __restrict__ u2)
 {
     // u1 / u2 != nullptr (fiunet_forward_u8): the uint8 frames [B][3][H][W] are read and normalised right here
@@ -348,8 +350,8 @@ __global__ __launch_bounds__(256, FIUNET_RGB_STEM_OCC) void stem_rgb_split_kerne
                     x2_split_store(o2, blk, c0);
                     x2_split_store(o2 + plane_bytes, blk, c1);
                 } else {
-                    *reinterpret_cast<uint4*>(op) = chunk_pack<__bf16>(o16);
-                    *reinterpret_cast<uint4*>(op + plane_bytes) = chunk_pack<__bf16>(o16 + 8);
+                    *reinterpret_cast<uint4*>(op) = chunk_pack<T>(o16);
+                    *reinterpret_cast<uint4*>(op + plane_bytes) = chunk_pack<T>(o16 + 8);
                 }
             }
         }
@@ -379,7 +381,7 @@ struct ConvTArgs {
 template <typename T, bool X2 = false>
 __global__ __launch_bounds__(256) void convt2x2_kernel(const ConvTArgs a)
 {
-    static_assert(!X2 || sizeof(T) == 2, "two-piece operands are bf16");
+    static_assert(!X2 || std::is_same_v<T, __bf16>, "two-piece operands are bf16");
     constexpr int PL = Elem<T>::PL;
     constexpr int NPX = 2;   // 16-pixel fragments per wave: every weight fragment is used for 32 pixels
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -457,7 +459,7 @@ __global__ __launch_bounds__(256) void convt2x2_kernel(const ConvTArgs a)
                             pack_bf16x2_pk(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xffff0000u)),
                             pack_bf16x2_pk(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xffff0000u)));
                     } else if constexpr (sizeof(T) == 2)
-                        *reinterpret_cast<uint2*>(op) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+                        *reinterpret_cast<uint2*>(op) = make_uint2(pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]));
                     else
                         *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[2], v[3]);
                 }
@@ -719,6 +721,30 @@ __global__ __launch_bounds__(256) void x2_pack_weights_kernel(const float* __res
 }
 
 // model/inference.py:31-35: image.astype(float32) / 255.0 ; 2.0 * image - 1.0
+// Weights of precision fp16, built on the device from the same packed fp32 copy: the layout of the bf16 copy (rows
+// permuted for the 3x3 convs, natural for the ConvTranspose2d taps), one piece, round to nearest even and saturated
+// (pack_f16x2); folded weights below 2^-14 stay fp16 subnormals.  No error feedback: fp16's 11 significant bits leave a
+// filter's net rounding error 8x smaller than bf16's.  out [cin/32][9][cout][32] (convt: [4][cin/32][cout][32]).
+__global__ __launch_bounds__(256) void f16_pack_weights_kernel(const float* __restrict__ w32, unsigned* __restrict__ out,
+                                                               int cin, int cout, int convt)
+{
+    const int taps = convt ? 4 : 9;
+    const size_t total = (size_t)cin * taps * cout / 2;   // one thread = two consecutive input channels
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        size_t r = i;
+        const int k = (int)(r % 16) * 2; r /= 16;
+        const int R = (int)(r % cout); r /= cout;
+        int plane, slot;
+        if (convt) { plane = (int)(r % (cin / 32)); slot = (int)(r / (cin / 32)); }
+        else { slot = (int)(r % 9); plane = (int)(r / 9); }
+        const int ci = plane * 32 + k;
+        const int co = convt ? R : (R & ~31) + ((R & 15) >> 2) * 8 + ((R >> 4) & 1) * 4 + (R & 3);
+        const size_t src = convt ? (((size_t)slot * (cin / 16) + ci / 16) * cout + co) * 16 + ci % 16
+                                 : (((size_t)(ci / 16) * 9 + slot) * cout + co) * 16 + ci % 16;
+        out[i] = pack_f16x2(w32[src], w32[src + 1]);   // ci, ci + 1: same 16-channel group (ci even)
+    }
+}
+
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __restrict__ in,
                                                             float* __restrict__ out, size_t n)
 {

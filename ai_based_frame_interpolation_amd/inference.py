@@ -234,7 +234,7 @@ def interpolate_sequence_p10(model, frames: torch.Tensor, batch: int = 8) -> tor
     """factor-2 video loop on 10-bit frames: device uint16 [N,H,W] (or [N,C,H,W]) 10-bit codes -> [2N-1, ...] = F0, M0,
     F1, ..., F(N-1), where Mi = model.forward_p10(Fi, Fi+1).  Both networks.  The originals are copied sample for
     sample; each middle is written in place; a ragged last chunk is padded as in `interpolate_sequence`, so the result
-    does not depend on N.  Use precision bf16x2 (or fp32) for 10-bit video: bf16 is about 5 codes off."""
+    does not depend on N.  Use precision fp16 (or bf16x2, fp32) for 10-bit video: bf16 is about 5 codes off."""
     squeeze = frames.dim() == 3
     fr = frames.unsqueeze(1) if squeeze else frames
     n, _, h, w = fr.shape
@@ -502,7 +502,7 @@ class FrameInterpolator:
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
         tag (8-bit: C420jpeg / C420 -> "jpeg", C420mpeg2 -> "mpeg2"; 10-bit: C420p10 does not carry it -> "mpeg2",
         what HEVC, AV1 and H.264 decoders give).  The grayscale network's Y4M path uses neither.  10-bit video keeps
-        10 bits end to end; run it in precision bf16x2 (or fp32): bf16 is about 5 codes off."""
+        10 bits end to end; run it in precision fp16 (or bf16x2, fp32): bf16 is about 5 codes off."""
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         if not os.path.exists(input_path):

@@ -45,7 +45,7 @@ TAP_NAMES = tuple(
 UP_TAP_NAMES = ("unet.up1.up", "unet.up2.up", "unet.up3.up", "unet.up4.up")
 
 _PRECISIONS = {"fp32": _native.FP32, "float32": _native.FP32, "bf16x2": _native.BF16X2, "bf16": _native.BF16,
-               "bfloat16": _native.BF16}
+               "bfloat16": _native.BF16, "fp16": _native.FP16, "float16": _native.FP16, "half": _native.FP16}
 
 
 class _Holder(nn.Module):
@@ -147,7 +147,9 @@ class FrameInterpolationUNet(nn.Module):
       precision:      "fp32" (default; exact-fp32 MFMA, |d| <= 1e-3 contract), "bf16" (bf16 storage + MFMA,
                       fp32 accumulate) or "bf16x2" (the fp32 contract on the bf16 pipe - activations
                       and weights as two bf16 pieces, three MFMAs per product, ~1e-5 relative end to end, about
-                      3x the speed of "fp32"; both decoders).  Env FIUNET_PRECISION is the default when the
+                      3x the speed of "fp32"; both decoders) or "fp16" (aliases "float16", "half": IEEE fp16 storage
+                      + MFMA, fp32 accumulate - bf16's kernels with 11 significant bits instead of 8, round to
+                      nearest, no dither).  Env FIUNET_PRECISION is the default when the
                       argument is None.  The attribute may be reassigned between forwards.
     """
 
@@ -388,8 +390,8 @@ class FrameInterpolationUNet(nn.Module):
         """10-bit frames: uint16 [B,C,H,W] of 10-bit codes in (above 1023 reads as 1023) -> uint16 interpolated frames,
         `fiunet_forward_p10`: x / 1023 * 2 - 1 on device, the fp32-in forward, trunc(clamp((y+1)/2, 0, 1) * 1023) on
         device - bit for bit `postprocess_p10(forward(preprocess_p10(a), preprocess_p10(b)))`.  Both networks.
-        Accuracy: fp32 and bf16x2 within 1 code of the fp32 oracle; bf16 about 5 codes (8 significant bits in every
-        activation, a stem dither of 2 codes peak to peak): use bf16x2 for 10-bit video.  `out`: as for `forward_u8`
+        Accuracy: fp32, bf16x2 and fp16 within 1 code of the fp32 oracle; bf16 about 5 codes (8 significant bits in every
+        activation, a stem dither of 2 codes peak to peak): use fp16 (or bf16x2) for 10-bit video.  `out`: as for `forward_u8`
         (uint16, every image contiguous, the images may lie apart)."""
         self._check_pair(frame1, frame2, (torch.uint16,))
         if not frame1.is_contiguous() or not frame2.is_contiguous():
@@ -414,7 +416,7 @@ class FrameInterpolationUNet(nn.Module):
         2*ceil(H/2)*ceil(W/2) samples, a C420p10 Y4M frame payload) -> uint16 [B, F] interpolated frames,
         `fiunet_forward_yuv420p10`: YUV -> planar RGB, `forward_p10`, RGB -> YUV on device.  matrix
         also takes "bt2020".  The network interpolates code values, as it does for 8-bit video (no PQ / HLG
-        linearisation).  Use bf16x2 (or fp32): bf16 is about 5 codes off.  `out`: as for `forward_yuv420`."""
+        linearisation).  Use fp16 (or bf16x2, fp32): bf16 is about 5 codes off.  `out`: as for `forward_yuv420`."""
         from .colour import colour_flags, yuv420p10_frame_samples
         flags = colour_flags(siting, matrix, colour_range, bits=10)
         if self.frame_channels != 3:

@@ -21,9 +21,10 @@
 extern "C" {
 #endif
 
-#define FIUNET_ABI_VERSION 7   /* 4: fiunet_prepare_precision; fiunet_debug_read_activation takes the capacity of dst; 5: fiunet_forward_u8_strided;
+#define FIUNET_ABI_VERSION 8   /* 4: fiunet_prepare_precision; fiunet_debug_read_activation takes the capacity of dst; 5: fiunet_forward_u8_strided;
                                   6: YUV 4:2:0 colour video (fiunet_yuv420_to_rgb_u8, fiunet_rgb_to_yuv420_u8, fiunet_forward_yuv420);
-                                  7: 10-bit video (fiunet_forward_p10, fiunet_forward_yuv420p10 and their pieces; FIUNET_YUV_BT2020) */
+                                  7: 10-bit video (fiunet_forward_p10, fiunet_forward_yuv420p10 and their pieces; FIUNET_YUV_BT2020);
+                                  8: precision FIUNET_FP16 */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -38,17 +39,24 @@ enum fiunet_status {
 };
 
 /* Arithmetic type of the conv path.  FP32: fp32 storage, exact-fp32 MFMA (v_mfma_f32_16x16x4_f32).
- * BF16: bf16 activations/weights in HBM, v_mfma_f32_16x16x32_bf16 with fp32 accumulation; the
- * first (Cin=2) conv and the final 1x1 conv stay fp32 arithmetic in both modes. */
+ * BF16 / FP16: bf16 / fp16 activations/weights in HBM, v_mfma_f32_16x16x32_bf16 / _f16 with fp32 accumulation; the
+ * first (Cin=2) conv and the final 1x1 conv stay fp32 arithmetic in every mode. */
 enum fiunet_precision {
     FIUNET_FP32 = 0,   /* exact fp32: v_mfma_f32_16x16x4_f32 (the reference's own arithmetic) */
     FIUNET_BF16 = 1,   /* bf16 storage and MFMA operands, fp32 accumulation */
-    FIUNET_BF16X2 = 2  /* the fp32 CONTRACT (|d| <= 1e-3) on the bf16 pipe - every activation and weight is two bf16
+    FIUNET_BF16X2 = 2, /* the fp32 CONTRACT (|d| <= 1e-3) on the bf16 pipe - every activation and weight is two bf16
                           pieces (hi + lo, 16 significant bits; activations [hi planes | lo planes], 4 B per element), a
                           product is wh*xh + wl*xh + wh*xl with fp32 accumulation (~1e-5 relative end to end); fp32 frames
                           in, fp32 logits out, exact-fp32 stem and head.  Needs fiunet_prepare_precision(ctx, FIUNET_BF16X2)
                           once after fiunet_load_weights.  Both decoders; FIUNET_OPT_KEEP_ALL + read-back work, the other
                           A/B options (UNFUSED, GATHER_UPSAMPLE) are ignored in this mode */
+    FIUNET_FP16 = 3    /* IEEE fp16 storage and MFMA operands (v_mfma_f32_16x16x32_f16, bf16's shape and rate), fp32
+                          accumulation: bf16's kernels, tiles and launch plan with 11 significant bits instead of 8.  Every
+                          rounding to fp16 is to nearest even and saturates at +-65504; the weights are rounded to nearest
+                          (no error feedback) and the stem has no dither - FIUNET_OPT_RNE_WEIGHTS and FIUNET_OPT_NO_DITHER are
+                          bf16-only and change nothing here.  The stems keep bf16's arithmetic (split-bf16 MFMAs / exact fp32)
+                          and round their output to fp16; the 1x1 head is fp32.  UNFUSED, KEEP_ALL and GATHER_UPSAMPLE work as
+                          in BF16.  Needs fiunet_prepare_precision(ctx, FIUNET_FP16) once after fiunet_load_weights */
 };
 
 /* Bit flags for fiunet_set_options. */
@@ -93,7 +101,8 @@ int fiunet_load_weights(fiunet_ctx* ctx, int n, const char* const* names,
                         const float* const* host_ptrs, const int64_t* numels);
 
 /* Builds the weight copies a precision needs beyond what fiunet_load_weights made (FP32, BF16: nothing; BF16X2: the
- * two-piece [wh | wl] copies, ~69 MB, packed on the device from the fp32 copy).  Call it after fiunet_load_weights and
+ * two-piece [wh | wl] copies, ~69 MB, packed on the device from the fp32 copy; FP16: the fp16 copies, ~35 MB, rounded
+ * to nearest even on the device from the fp32 copy).  Call it after fiunet_load_weights and
  * before the first forward in that precision (a forward without it returns FIUNET_ERR_NOT_LOADED); idempotent;
  * allocates and synchronises - so not under stream capture.  The reference has no counterpart: its one precision is
  * whatever dtype the module's tensors have (model/inference.py:96). */
@@ -220,7 +229,8 @@ size_t fiunet_workspace_bytes_p10(const fiunet_ctx* ctx, int B, int H, int W, in
  * images go to `out`, `out_image_stride` SAMPLES apart (0 = contiguous; >= frame_channels * H * W).  pre10 of both
  * inputs into fp32 staging, fiunet_forward, post10 into `out` - bit for bit fiunet_preprocess_p10 -> fiunet_forward
  * -> fiunet_postprocess_p10.  Accuracy: fp32 and FIUNET_BF16X2 within 1 code of the fp32 oracle; FIUNET_BF16 about
- * 5 codes (8 significant bits; its stem dither is 2 ten-bit codes peak to peak): use FIUNET_BF16X2 for 10-bit video. */
+ * 5 codes (8 significant bits; its stem dither is 2 ten-bit codes peak to peak); FIUNET_FP16 within 1 code at nearly
+ * bf16's speed: use FIUNET_FP16 (or FIUNET_BF16X2) for 10-bit video. */
 int fiunet_forward_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
                        size_t out_image_stride, int B, int H, int W, int precision, void* workspace,
                        size_t workspace_bytes, void* stream);
