@@ -42,6 +42,7 @@ SYMBOLS = (
     "fiunet_preprocess_p10", "fiunet_postprocess_p10", "fiunet_workspace_bytes_p10", "fiunet_forward_p10",
     "fiunet_yuv420p10_to_rgb_p10", "fiunet_rgb_p10_to_yuv420p10", "fiunet_workspace_bytes_yuv420p10",
     "fiunet_forward_yuv420p10",
+    "fiunet_pair_sad_u8", "fiunet_pair_sad_p10", "fiunet_scene_cuts", "fiunet_hold_cut_frames",
 )
 
 _lib = None
@@ -127,6 +128,10 @@ def lib() -> ctypes.CDLL:
     L.fiunet_workspace_bytes_yuv420p10.argtypes = [vp, ci, ci, ci, ci]
     L.fiunet_workspace_bytes_yuv420p10.restype = sz
     L.fiunet_forward_yuv420p10.argtypes = [vp, vp, vp, vp, sz, ci, ci, ci, cu, ci, vp, sz, vp]
+    L.fiunet_pair_sad_u8.argtypes = [vp, ci, sz, vp, vp]
+    L.fiunet_pair_sad_p10.argtypes = [vp, ci, sz, vp, vp]
+    L.fiunet_scene_cuts.argtypes = [vp, ci, sz, ci, ctypes.c_double, vp, vp, vp]
+    L.fiunet_hold_cut_frames.argtypes = [vp, ci, sz, ci, vp, vp]
     L.fiunet_debug_read_activation.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz,
                                                ctypes.POINTER(ci), vp]
     L.fiunet_metrics_workspace_bytes.argtypes = [ci, ci, ci]
@@ -415,3 +420,29 @@ def rgb_p10_to_yuv420p10(rgb: "torch.Tensor", out: "torch.Tensor", colour: int) 
     s = torch.cuda.current_stream(rgb.device).cuda_stream
     check(lib().fiunet_rgb_p10_to_yuv420p10(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s),
           "fiunet_rgb_p10_to_yuv420p10")
+
+
+def pair_sad(frames: "torch.Tensor", sums: "torch.Tensor", bits: int) -> None:
+    """fiunet_pair_sad_u8 / fiunet_pair_sad_p10: ACCUMULATES sum |F[i+1] - F[i]| of a contiguous stack [N, ...] (uint8 at
+    8 bits; 16-bit words, int16 or uint16, at 10) into the int64 `sums` [N-1]."""
+    n = frames.shape[0]
+    fs = frames[0].numel() if n else 0
+    fn = lib().fiunet_pair_sad_p10 if bits == 10 else lib().fiunet_pair_sad_u8
+    s = torch.cuda.current_stream(frames.device).cuda_stream
+    check(fn(frames.data_ptr(), n, fs, sums.data_ptr(), s), "fiunet_pair_sad_" + ("p10" if bits == 10 else "u8"))
+
+
+def scene_cuts(sums: "torch.Tensor", n_frames: int, count: int, bits: int, threshold: float,
+               scores: "torch.Tensor", flags: "torch.Tensor") -> None:
+    """fiunet_scene_cuts: int64 sums [N-1] -> fp64 scores [N-1], uint8 flags [N-1]."""
+    s = torch.cuda.current_stream(sums.device).cuda_stream
+    check(lib().fiunet_scene_cuts(sums.data_ptr(), n_frames, count, bits, float(threshold), scores.data_ptr(),
+                                  flags.data_ptr(), s), "fiunet_scene_cuts")
+
+
+def hold_cut_frames(video: "torch.Tensor", n_frames: int, factor: int, flags: "torch.Tensor") -> None:
+    """fiunet_hold_cut_frames on a contiguous interleaved result [(n_frames-1)*factor+1, ...], in place."""
+    fb = video[0].numel() * video.element_size() if video.shape[0] else 0
+    s = torch.cuda.current_stream(video.device).cuda_stream
+    check(lib().fiunet_hold_cut_frames(video.data_ptr(), n_frames, fb, factor, flags.data_ptr(), s),
+          "fiunet_hold_cut_frames")

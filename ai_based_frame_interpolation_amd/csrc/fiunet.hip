@@ -12,6 +12,7 @@
 #include "conv3x3_kwave.hip.h"
 #include "metrics.hip.h"
 #include "colour.hip.h"
+#include "scene.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1683,6 +1684,74 @@ int fiunet_postprocess_p10(const float* in, uint16_t* out, size_t n, void* strea
     if (!n) return FIUNET_OK;
     hipLaunchKernelGGL(postprocess_p10_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, in, out, n);
     HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+// ---- scene cuts (csrc/scene.hip.h) -------------------------------------------------------------
+constexpr int kMaxGridY = 65535;   // pairs / intervals per launch (grid.y)
+
+extern "C++" {   // (a template inside the extern "C" block)
+template <typename T>
+static int pair_sad(const T* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
+{
+    if (!frames || !sums) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    if (n_frames < 2 || frame_samples == 0) return FIUNET_OK;
+    // ~4 x 16 B per thread and at most 128 workgroups (= atomics) per pair, as fiunet_psnr_u8
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
+    for (int p0 = 0; p0 < n_frames - 1; p0 += kMaxGridY) {
+        const int np = std::min(n_frames - 1 - p0, kMaxGridY);
+        hipLaunchKernelGGL(pair_sad_kernel<T>, dim3(bx, (unsigned)np), dim3(kSceneBlock), 0, (hipStream_t)stream,
+                           frames + (size_t)p0 * frame_samples, frame_samples,
+                           reinterpret_cast<unsigned long long*>(sums + p0));
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_pair_sad_u8(const uint8_t* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
+{
+    return pair_sad(frames, n_frames, frame_samples, sums, stream);
+}
+
+int fiunet_pair_sad_p10(const uint16_t* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
+{
+    return pair_sad(frames, n_frames, frame_samples, sums, stream);
+}
+
+int fiunet_scene_cuts(const int64_t* sums, int n_frames, size_t count, int bits, double threshold, double* scores,
+                      uint8_t* flags, void* stream)
+{
+    if (!sums || !scores || !flags) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
+    if (!(threshold > 0.0 && threshold <= 100.0)) return fail(FIUNET_ERR_INVALID_ARG, "threshold outside (0, 100]");
+    if (count == 0) return fail(FIUNET_ERR_INVALID_ARG, "count == 0");
+    if (n_frames < 2) return FIUNET_OK;
+    const int intervals = n_frames - 1;
+    hipLaunchKernelGGL(scene_cuts_kernel, dim3((unsigned)((intervals + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, reinterpret_cast<const long long*>(sums), intervals, (double)count,
+                       (double)(1 << bits), threshold, scores, flags);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_hold_cut_frames(uint8_t* video, int n_frames, size_t frame_bytes, int factor, const uint8_t* flags,
+                           void* stream)
+{
+    if (!video || !flags) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    if (factor < 2 || (factor & (factor - 1)) || factor > (1 << 20))
+        return fail(FIUNET_ERR_INVALID_ARG, "factor must be a power of two in [2, 2^20]");
+    if (n_frames < 2 || frame_bytes == 0) return FIUNET_OK;
+    const unsigned gx = (unsigned)kHoldBlocks * (unsigned)(factor - 1);
+    for (int i0 = 0; i0 < n_frames - 1; i0 += kMaxGridY) {
+        const int ni = std::min(n_frames - 1 - i0, kMaxGridY);
+        hipLaunchKernelGGL(hold_cut_frames_kernel, dim3(gx, (unsigned)ni), dim3(kSceneBlock), 0, (hipStream_t)stream,
+                           video + (size_t)i0 * factor * frame_bytes, frame_bytes, factor, flags + i0);
+        HIP_TRY(hipGetLastError());
+    }
     return FIUNET_OK;
 }
 

@@ -25,7 +25,7 @@ import torch
 from struct import error as struct_error
 from zlib import error as zlib_error
 
-from . import _native, colour, imageio_lite
+from . import _native, colour, imageio_lite, scene
 from .unet import FrameInterpolationUNet
 
 
@@ -182,30 +182,51 @@ def sequence_pair_fn(model, batch: int = 8):
     return pair_fn
 
 
+def _cut_flags(thr, stacks, bits):
+    """Device uint8 flags of the cut intervals of the input frames (scene.detect_cuts), or None when scene_cut is off."""
+    if thr is None:
+        return None
+    return scene.detect_cuts([p.contiguous() for p in stacks], thr, bits)[1]
+
+
+def _hold(flags, factor, *videos):
+    """scene.hold_cut_frames on each interleaved result (the planes of one video) when scene_cut is on."""
+    if flags is not None:
+        for v in videos:
+            scene.hold_cut_frames(v, flags, factor)
+
+
 @torch.no_grad()
-def interpolate_sequence(model, frames_u8: torch.Tensor, batch: int = 8) -> torch.Tensor:
+def interpolate_sequence(model, frames_u8: torch.Tensor, batch: int = 8, *, scene_cut: float | None = None) -> torch.Tensor:
     """factor-2 video loop on one GPU: device uint8 frames [N,H,W] (or [N,C,H,W]) ->
     [2N-1, ...] = F0, M0, F1, M1, ..., F(N-1), where Mi = model(Fi, Fi+1) through the fused
-    uint8 path (pre/post-processing on device).  Semantics per SURVEY.md 8a row 11."""
+    uint8 path (pre/post-processing on device).  Semantics per SURVEY.md 8a row 11.
+    scene_cut: None (off) or a threshold in (0, 100]: the middle of every interval scene.detect_cuts flags is a copy of
+    Fi (scene.py); every other frame is unchanged."""
+    thr = scene.check_threshold(scene_cut)
     squeeze = frames_u8.dim() == 3
     fr = frames_u8.unsqueeze(1) if squeeze else frames_u8
+    flags = _cut_flags(thr, [fr], 8)
     n = fr.shape[0]
     out = torch.empty((2 * n - 1,) + tuple(fr.shape[1:]), dtype=torch.uint8, device=fr.device)
     out[0::2] = fr
     for s, cnt in _pair_batches(n - 1, batch):   # each middle is written where it belongs (no temporary, no strided copy)
         _forward_u8_chunk(model, fr[s:s + cnt], fr[s + 1:s + cnt + 1], batch, out=out[2 * s + 1: 2 * (s + cnt): 2])
+    _hold(flags, 2, out)
     return out.squeeze(1) if squeeze else out
 
 
 @torch.no_grad()
-def interpolate_sequence_yuv420(model, frames: torch.Tensor, height: int, width: int, batch: int = 8,
-                                **colour) -> torch.Tensor:
+def interpolate_sequence_yuv420(model, frames: torch.Tensor, height: int, width: int, batch: int = 8, *,
+                                scene_cut: float | None = None, **colour) -> torch.Tensor:
     """factor-2 video loop of the RGB network on colour video: device uint8 [N, F] packed I420 frames of
     height x width (a Y4M frame payload each) -> [2N-1, F] = F0, M0, F1, ..., F(N-1), where Mi =
     model.forward_yuv420(Fi, Fi+1, **colour).  The originals are copied byte for byte; each middle is written in
     place; a ragged last chunk is padded as in `interpolate_sequence`, so the result does not depend on N.
-    colour: siting / matrix / colour_range (colour.py)."""
+    colour: siting / matrix / colour_range (colour.py).  scene_cut: as for `interpolate_sequence`, on all three planes."""
+    thr = scene.check_threshold(scene_cut)
     h, w = int(height), int(width)
+    flags = _cut_flags(thr, [frames], 8)
     n = frames.shape[0]
     out = torch.empty((2 * n - 1, frames.shape[1]), dtype=torch.uint8, device=frames.device)
     out[0::2] = frames
@@ -216,6 +237,7 @@ def interpolate_sequence_yuv420(model, frames: torch.Tensor, height: int, width:
     for s, cnt in _pair_batches(n - 1, batch):
         _padded_chunk(model, fwd, frames[s:s + cnt], frames[s + 1:s + cnt + 1], h, w, batch,
                       out=out[2 * s + 1: 2 * (s + cnt): 2])
+    _hold(flags, 2, out)
     return out
 
 
@@ -230,16 +252,19 @@ def _u16(t: torch.Tensor | None) -> torch.Tensor | None:
 
 
 @torch.no_grad()
-def interpolate_sequence_p10(model, frames: torch.Tensor, batch: int = 8) -> torch.Tensor:
+def interpolate_sequence_p10(model, frames: torch.Tensor, batch: int = 8, *, scene_cut: float | None = None) -> torch.Tensor:
     """factor-2 video loop on 10-bit frames: device uint16 [N,H,W] (or [N,C,H,W]) 10-bit codes -> [2N-1, ...] = F0, M0,
     F1, ..., F(N-1), where Mi = model.forward_p10(Fi, Fi+1).  Both networks.  The originals are copied sample for
     sample; each middle is written in place; a ragged last chunk is padded as in `interpolate_sequence`, so the result
-    does not depend on N.  Use precision fp16 (or bf16x2, fp32) for 10-bit video: bf16 is about 5 codes off."""
+    does not depend on N.  Use precision fp16 (or bf16x2, fp32) for 10-bit video: bf16 is about 5 codes off.
+    scene_cut: as for `interpolate_sequence` (samples above 1023 read as 1023 by the detection)."""
+    thr = scene.check_threshold(scene_cut)
     squeeze = frames.dim() == 3
     fr = frames.unsqueeze(1) if squeeze else frames
     n, _, h, w = fr.shape
     out = torch.empty((2 * n - 1,) + tuple(fr.shape[1:]), dtype=torch.uint16, device=fr.device)
     f16, o16 = _i16(fr), _i16(out)
+    flags = _cut_flags(thr, [f16], 10)
     o16[0::2] = f16
 
     def fwd(a, b, out=None):
@@ -248,19 +273,23 @@ def interpolate_sequence_p10(model, frames: torch.Tensor, batch: int = 8) -> tor
     for s, cnt in _pair_batches(n - 1, batch):
         _padded_chunk(model, fwd, f16[s:s + cnt], f16[s + 1:s + cnt + 1], h, w, batch,
                       out=o16[2 * s + 1: 2 * (s + cnt): 2])
+    _hold(flags, 2, o16)
     return out.squeeze(1) if squeeze else out
 
 
 @torch.no_grad()
-def interpolate_sequence_yuv420p10(model, frames: torch.Tensor, height: int, width: int, batch: int = 8,
-                                   **colour) -> torch.Tensor:
+def interpolate_sequence_yuv420p10(model, frames: torch.Tensor, height: int, width: int, batch: int = 8, *,
+                                   scene_cut: float | None = None, **colour) -> torch.Tensor:
     """`interpolate_sequence_yuv420` on 10-bit video: device uint16 [N, F] packed 4:2:0 10-bit frames (a C420p10 Y4M
     frame payload each) -> [2N-1, F], Mi = model.forward_yuv420p10(Fi, Fi+1, **colour).  The originals are copied
-    sample for sample; the result does not depend on N.  colour: siting / matrix (also "bt2020") / colour_range."""
+    sample for sample; the result does not depend on N.  colour: siting / matrix (also "bt2020") / colour_range.
+    scene_cut: as for `interpolate_sequence`, on all three planes."""
+    thr = scene.check_threshold(scene_cut)
     h, w = int(height), int(width)
     n = frames.shape[0]
     out = torch.empty((2 * n - 1, frames.shape[1]), dtype=torch.uint16, device=frames.device)
     f16, o16 = _i16(frames), _i16(out)
+    flags = _cut_flags(thr, [f16], 10)
     o16[0::2] = f16
 
     def fwd(a, b, out=None):
@@ -269,6 +298,7 @@ def interpolate_sequence_yuv420p10(model, frames: torch.Tensor, height: int, wid
     for s, cnt in _pair_batches(n - 1, batch):
         _padded_chunk(model, fwd, f16[s:s + cnt], f16[s + 1:s + cnt + 1], h, w, batch,
                       out=o16[2 * s + 1: 2 * (s + cnt): 2])
+    _hold(flags, 2, o16)
     return out
 
 
@@ -381,7 +411,7 @@ class FrameInterpolator:
         o = o[0] if self.model.frame_channels == img1.shape[2] else o[:, 0]
         return o.permute(1, 2, 0).contiguous().cpu().numpy()
 
-    def _interpolate_y4m(self, input_path, output_path, factor):
+    def _interpolate_y4m(self, input_path, output_path, factor, thr=None):
         """Uncompressed YUV4MPEG2 in -> out (`ffmpeg -i in.mp4 in.y4m` makes one; no codec exists in this
         image).  The network is the reference's grayscale 2->1 model, so it interpolates the LUMA plane;
         the chroma planes of an inserted frame are the rounded average of its neighbours' (an extension:
@@ -394,12 +424,14 @@ class FrameInterpolator:
         cu = cv = None
         if chroma is not None:
             cu, cv = (torch.from_numpy(c).to(self.device) for c in chroma)
+        flags = _cut_flags(thr, [p for p in (t, cu, cv) if p is not None], 8)
         f = factor
         while f > 1:
             t = interpolate_sequence(self.model, t, self.batch)
             if cu is not None:
                 cu, cv = (_interleave_average_u8(c) for c in (cu, cv))
             f //= 2
+        _hold(flags, factor, *(p for p in (t, cu, cv) if p is not None))
         if str(output_path).lower().endswith(".y4m"):
             imageio_lite.write_y4m(output_path, t.cpu().numpy(),
                                    None if cu is None else (cu.cpu().numpy(), cv.cpu().numpy()),
@@ -408,7 +440,7 @@ class FrameInterpolator:
             np.save(output_path, t.cpu().numpy())
         return t.shape[0]
 
-    def _interpolate_y4m_p10(self, input_path, output_path, factor):
+    def _interpolate_y4m_p10(self, input_path, output_path, factor, thr=None):
         """10-bit YUV4MPEG2 (`C420p10`, `C422p10`, `C444p10`, `Cmono10`) through the grayscale network: the luma plane
         through `interpolate_sequence_p10`; the chroma of an inserted frame is the rounded average of its neighbours',
         in int32.  The output keeps the input's tag and range, fps x factor.  Output: `.y4m`, or a `.npy` stack of the
@@ -421,12 +453,15 @@ class FrameInterpolator:
         if nc:
             cu, cv = (torch.from_numpy(frames[:, ny + i * nc:ny + (i + 1) * nc].astype(np.int32).reshape(-1, hc, wc))
                       .to(self.device) for i in (0, 1))
+        # the chroma lives in int32 here: its low 16 bits are the samples as stored
+        flags = _cut_flags(thr, [_i16(t)] + ([] if cu is None else [c.to(torch.int16) for c in (cu, cv)]), 10)
         f = factor
         while f > 1:
             t = interpolate_sequence_p10(self.model, t, self.batch)
             if cu is not None:
                 cu, cv = (_interleave_average_p10(c) for c in (cu, cv))
             f //= 2
+        _hold(flags, factor, *(p for p in (t, cu, cv) if p is not None))
         y = t.cpu().numpy()
         if str(output_path).lower().endswith(".y4m"):
             imageio_lite.write_y4m_p10(output_path, y,
@@ -438,7 +473,7 @@ class FrameInterpolator:
             np.save(output_path, y)
         return y.shape[0]
 
-    def _interpolate_y4m_colour_p10(self, input_path, output_path, factor, matrix, siting):
+    def _interpolate_y4m_colour_p10(self, input_path, output_path, factor, matrix, siting, thr=None):
         """10-bit 4:2:0 YUV4MPEG2 (`C420p10`) through the RGB network (`interpolate_sequence_yuv420p10`).  The tag does
         not carry the siting: `siting` None means "mpeg2" (left-sited: what HEVC, AV1 and H.264 decoders give).  Range
         from `XCOLORRANGE` (limited when absent); `matrix` also takes "bt2020".  The output keeps the tag and range,
@@ -455,10 +490,12 @@ class FrameInterpolator:
         colour.colour_flags(**opts, bits=10)   # a bad `matrix` / `siting` fails here, before any GPU work
         h, w = hdr["height"], hdr["width"]
         t = torch.from_numpy(frames).to(self.device)
+        flags = _cut_flags(thr, [_i16(t)], 10)
         f = factor
         while f > 1:
             t = interpolate_sequence_yuv420p10(self.model, t, h, w, self.batch, **opts)
             f //= 2
+        _hold(flags, factor, t)
         res = t.cpu().numpy()
         (hc, wc), ny = hdr["chroma"], h * w
         u = res[:, ny:ny + hc * wc].reshape(-1, hc, wc)
@@ -468,7 +505,7 @@ class FrameInterpolator:
                                    colour_range=hdr["colour_range"])
         return res.shape[0]
 
-    def _interpolate_y4m_colour(self, input_path, output_path, factor, matrix, siting=None):
+    def _interpolate_y4m_colour(self, input_path, output_path, factor, matrix, siting=None, thr=None):
         """4:2:0 YUV4MPEG2 in -> out through the RGB (6->3) network: every frame is converted to planar RGB on the
         device, the network interpolates all three channels, and the middle frames are converted back
         (`interpolate_sequence_yuv420`).  Chroma siting from the `C` tag (420jpeg / 420 / none, or 420mpeg2), range
@@ -483,10 +520,12 @@ class FrameInterpolator:
         colour.colour_flags(**opts)   # a bad `matrix` fails here, before any GPU work
         h, w = hdr["height"], hdr["width"]
         t = torch.from_numpy(frames).to(self.device)
+        flags = _cut_flags(thr, [t], 8)
         f = factor
         while f > 1:
             t = interpolate_sequence_yuv420(self.model, t, h, w, self.batch, **opts)
             f //= 2
+        _hold(flags, factor, t)
         res = t.cpu().numpy()
         (hc, wc), ny = hdr["chroma"], h * w
         u = res[:, ny:ny + hc * wc].reshape(-1, hc, wc)
@@ -496,13 +535,18 @@ class FrameInterpolator:
                                colour_range=hdr["colour_range"])
         return res.shape[0]
 
-    def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None):
+    def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
         tag (8-bit: C420jpeg / C420 -> "jpeg", C420mpeg2 -> "mpeg2"; 10-bit: C420p10 does not carry it -> "mpeg2",
         what HEVC, AV1 and H.264 decoders give).  The grayscale network's Y4M path uses neither.  10-bit video keeps
-        10 bits end to end; run it in precision fp16 (or bf16x2, fp32): bf16 is about 5 codes off."""
+        10 bits end to end; run it in precision fp16 (or bf16x2, fp32): bf16 is about 5 codes off.
+        scene_cut: None (off) or a threshold in (0, 100].  Cuts are detected once on the input frames, over every
+        sample as stored (all planes, all channels; scene.py), and every frame inserted into a cut
+        interval - factor - 1 of them, chroma included - is a byte copy of the frame before the cut.  10 separates
+        a hard cut from ordinary motion."""
+        thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         if not os.path.exists(input_path):
@@ -511,15 +555,16 @@ class FrameInterpolator:
             p10 = imageio_lite.y4m_colourspace(input_path) in imageio_lite.Y4M_P10_TAGS
             if self.model.frame_channels == 3:
                 if p10:
-                    return self._interpolate_y4m_colour_p10(input_path, output_path, factor, matrix, siting)
-                return self._interpolate_y4m_colour(input_path, output_path, factor, matrix, siting)
+                    return self._interpolate_y4m_colour_p10(input_path, output_path, factor, matrix, siting, thr)
+                return self._interpolate_y4m_colour(input_path, output_path, factor, matrix, siting, thr)
             if p10:
-                return self._interpolate_y4m_p10(input_path, output_path, factor)
-            return self._interpolate_y4m(input_path, output_path, factor)
+                return self._interpolate_y4m_p10(input_path, output_path, factor, thr)
+            return self._interpolate_y4m(input_path, output_path, factor, thr)
         frames = np.load(input_path)
         if frames.dtype != np.uint8 or frames.ndim not in (3, 4):
             raise ValueError("expected a uint8 .npy stack [N,H,W] or [N,H,W,3]")
         t = torch.from_numpy(frames).to(self.device)
+        flags = _cut_flags(thr, [t], 8)   # [N,H,W] or [N,H,W,3]: every channel of a frame counts
         if t.dim() == 4:
             t = t.permute(0, 3, 1, 2).contiguous()
             if self.model.frame_channels == 1:  # per-channel application of the 2->1 network
@@ -533,11 +578,13 @@ class FrameInterpolator:
                         seq = interpolate_sequence(self.model, seq, self.batch); f //= 2
                     outs.append(seq)
                 res = torch.stack(outs, dim=-1)
+                _hold(flags, factor, res)
                 np.save(output_path, res.cpu().numpy())
                 return res.shape[0]
         f = factor
         while f > 1:
             t = interpolate_sequence(self.model, t, self.batch); f //= 2
+        _hold(flags, factor, t)
         if t.dim() == 4:
             t = t.permute(0, 2, 3, 1)
         np.save(output_path, t.cpu().numpy())

@@ -24,7 +24,8 @@ extern "C" {
 #define FIUNET_ABI_VERSION 8   /* 4: fiunet_prepare_precision; fiunet_debug_read_activation takes the capacity of dst; 5: fiunet_forward_u8_strided;
                                   6: YUV 4:2:0 colour video (fiunet_yuv420_to_rgb_u8, fiunet_rgb_to_yuv420_u8, fiunet_forward_yuv420);
                                   7: 10-bit video (fiunet_forward_p10, fiunet_forward_yuv420p10 and their pieces; FIUNET_YUV_BT2020);
-                                  8: precision FIUNET_FP16 */
+                                  8: precision FIUNET_FP16; v8 also: scene-cut entry points (fiunet_pair_sad_u8,
+                                     fiunet_pair_sad_p10, fiunet_scene_cuts, fiunet_hold_cut_frames), backwards-compatible */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -251,6 +252,28 @@ size_t fiunet_workspace_bytes_yuv420p10(const fiunet_ctx* ctx, int B, int H, int
 int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
                              size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene cuts in the video loops (ABI v8, added without a version bump: nothing existing changed).  The reference has
+ * no video loop; the definition is our own.  For N frames and the N-1 intervals i between F[i] and
+ * F[i+1]: sad[i] = sum over every sample of |F[i+1] - F[i]| (exact int64; 10-bit samples above 1023 read as 1023),
+ * mafd[i] = sad[i] * 100.0 / count / 2^bits in IEEE double in that order (count = samples per frame, all planes),
+ * score[i] = min(mafd[i], |mafd[i] - mafd[i-1]|, |mafd[i] - mafd[i+1]|) (a missing neighbour left out), and interval
+ * i is a cut iff score[i] >= threshold.  Device pointers; asynchronous on `stream`; no allocation, no
+ * synchronisation; n_frames < 2 is a no-op.  FIUNET_ERR_INVALID_ARG on NULL pointers or n_frames < 0. */
+/* ACCUMULATES sad[i] into sums[n_frames - 1] (zeroed by the caller): `frames` is a contiguous stack of n_frames frames
+ * of frame_samples samples, so one sad can span several planar stacks (Y, U, V) of the same frames. */
+int fiunet_pair_sad_u8(const uint8_t* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream);
+int fiunet_pair_sad_p10(const uint16_t* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream);
+/* sums[n_frames - 1] -> scores[n_frames - 1] (double) and flags[n_frames - 1] (1 = cut).  count = samples per frame
+ * over every stack that went into the sums; bits 8 or 10; threshold in (0, 100] (NaN rejected). */
+int fiunet_scene_cuts(const int64_t* sums, int n_frames, size_t count, int bits, double threshold, double* scores,
+                      uint8_t* flags, void* stream);
+/* Sample-and-hold on the interleaved result of a factor-`factor` loop over n_frames input frames ((n_frames - 1) *
+ * factor + 1 frames of frame_bytes bytes, contiguous): for every i with flags[i] != 0, frames i*factor + 1 ..
+ * i*factor + factor - 1 become byte copies of frame i*factor.  Bytes, so every sample depth shares it.  The flags are
+ * read on the device.  factor: a power of two in [2, 2^20]. */
+int fiunet_hold_cut_frames(uint8_t* video, int n_frames, size_t frame_bytes, int factor, const uint8_t* flags,
+                           void* stream);
 
 /* Replaces preprocess_image's arithmetic (model/inference.py:31-35): out = 2*(in/255) - 1. */
 int fiunet_preprocess_u8(const uint8_t* in, float* out, size_t n, void* stream);
