@@ -1,0 +1,94 @@
+"""Command line: `python -m ai_based_frame_interpolation_amd.cli video --input IN --output OUT [--factor 2] ...`
+
+The reference's `main.py video` flags (--input, --output, --factor, --model, --device), plus --precision, --matrix,
+--siting, --scene-cut, --batch and --chunk-frames.  The command always streams (stream.py), so a clip of
+any length runs in memory bounded by the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
+
+    ffmpeg -i in.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - \\
+        --model best_model.pth | ffmpeg -f yuv4mpegpipe -i - out.mkv
+
+Standard output then carries nothing but Y4M: the model-loading lines go to standard error.  The network (grayscale
+2->1 or RGB 6->3) is read from the checkpoint.
+"""
+from __future__ import annotations
+
+import argparse
+import contextlib
+import sys
+
+import torch
+
+FIRST_CONV = "unet.inc.double_conv.0.weight"
+
+
+def frame_channels_of(state_dict) -> int:
+    """1 (grayscale 2->1 network) or 3 (RGB 6->3) from the input channels of the first convolution."""
+    sd = state_dict.get("model_state_dict", state_dict)
+    if FIRST_CONV not in sd:
+        raise ValueError(f"checkpoint has no {FIRST_CONV}: not a frame-interpolation UNet")
+    cin = int(sd[FIRST_CONV].shape[1])
+    if cin not in (2, 6):
+        raise ValueError(f"{FIRST_CONV} has {cin} input channels: expected 2 (grayscale) or 6 (RGB)")
+    return cin // 2
+
+
+def _scene_cut(v: str):
+    return None if v.lower() in ("none", "off") else float(v)
+
+
+def _siting(v: str):
+    return None if v.lower() == "none" else v
+
+
+def parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m ai_based_frame_interpolation_amd.cli",
+                                 description="AI frame interpolation on the MI355X")
+    sub = ap.add_subparsers(dest="command", required=True)
+    v = sub.add_parser("video", help="Interpolate frames in a video (Y4M or .npy; '-' is stdin / stdout)")
+    v.add_argument("--input", required=True, help="Input video path, or - for standard input (Y4M)")
+    v.add_argument("--output", required=True, help="Output video path, or - for standard output (Y4M)")
+    v.add_argument("--factor", type=int, default=2, help="Interpolation factor (a power of two)")
+    v.add_argument("--model", default="best_model.pth", help="Path to trained model")
+    v.add_argument("--device", default="auto", help="Device to use (cuda/auto)")
+    v.add_argument("--precision", default=None, help="fp32 / bf16x2 / bf16 / fp16 (default: the library's)")
+    v.add_argument("--matrix", default="bt709", help="YUV matrix of colour video through the RGB network")
+    v.add_argument("--siting", type=_siting, default=None, help="Chroma siting jpeg / mpeg2 (default: from the tag)")
+    v.add_argument("--scene-cut", type=_scene_cut, default=None, help="Scene-cut threshold in (0, 100], or none")
+    v.add_argument("--batch", type=int, default=8, help="Frame pairs per forward")
+    v.add_argument("--chunk-frames", type=int, default=None, help="Frame pairs per streamed chunk (default 4 x batch)")
+    return ap
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    a = parser().parse_args(argv)
+    if a.chunk_frames is None:
+        a.chunk_frames = 4 * a.batch
+    return a
+
+
+def run_video(a: argparse.Namespace) -> int:
+    from . import stream
+    from .inference import FrameInterpolator, load_model
+    stream.check_chunk_frames(a.chunk_frames)
+    device = torch.device("cuda" if a.device in ("auto", None) else a.device)
+    fc = frame_channels_of(torch.load(a.model, map_location="cpu"))
+    with contextlib.redirect_stdout(sys.stderr):   # standard output carries the video only
+        model = load_model(a.model, device, a.precision, frame_channels=fc)
+    fi = FrameInterpolator(model=model, device=device, batch=a.batch)
+    src = sys.stdin.buffer if a.input == "-" else a.input
+    dst = sys.stdout.buffer if a.output == "-" else a.output
+    n = fi.interpolate_video(src, dst, a.factor, matrix=a.matrix, siting=a.siting, scene_cut=a.scene_cut,
+                             chunk_frames=a.chunk_frames)
+    print(f"wrote {n} frames", file=sys.stderr)
+    return n
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
+    if a.command == "video":
+        run_video(a)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

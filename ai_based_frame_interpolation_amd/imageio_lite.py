@@ -20,6 +20,7 @@ if `cv2` is importable the callers use it instead.
 """
 from __future__ import annotations
 
+import os
 import struct
 import zlib
 
@@ -334,13 +335,9 @@ def write_y4m(path: str, y: np.ndarray, chroma=None, fps=(30, 1), colourspace: s
     cs = colourspace or ("mono" if chroma is None else "420jpeg")
     if (chroma is None) != cs.startswith("mono"):
         raise ValueError("chroma planes and colourspace tag disagree")
-    ext = ""
-    if colour_range is not None:
-        if colour_range.upper() not in ("FULL", "LIMITED"):
-            raise ValueError(f"colour_range must be FULL or LIMITED, got {colour_range!r}")
-        ext = f" XCOLORRANGE={colour_range.upper()}"
+    head = _y4m_header_line(w, h, fps, cs, colour_range, 8)
     with open(path, "wb") as f:
-        f.write(f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{cs}{ext}\n".encode())
+        f.write(head)
         for i in range(n):
             f.write(b"FRAME\n")
             f.write(y[i].tobytes())
@@ -407,13 +404,9 @@ def write_y4m_p10(path: str, y: np.ndarray, chroma=None, fps=(30, 1), colourspac
         raise ValueError(f"colourspace must be one of {Y4M_P10_TAGS}, got {cs!r}")
     if (chroma is None) != cs.startswith("mono"):
         raise ValueError("chroma planes and colourspace tag disagree")
-    ext = "" if cs.startswith("mono") else f" XYSCSS={cs.upper()}"
-    if colour_range is not None:
-        if colour_range.upper() not in ("FULL", "LIMITED"):
-            raise ValueError(f"colour_range must be FULL or LIMITED, got {colour_range!r}")
-        ext += f" XCOLORRANGE={colour_range.upper()}"
+    head = _y4m_header_line(w, h, fps, cs, colour_range, 10)
     with open(path, "wb") as f:
-        f.write(f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{cs}{ext}\n".encode())
+        f.write(head)
         for i in range(n):
             f.write(b"FRAME\n")
             f.write(y[i].astype("<u2").tobytes())
@@ -430,3 +423,191 @@ def y4m_colourspace(path: str) -> str:
         if tok[:1] == b"C":
             return tok[1:].decode()
     return "420jpeg"
+
+
+def _y4m_header_line(w: int, h: int, fps, cs: str, colour_range, bits: int) -> bytes:
+    """The stream header `write_y4m` (bits 8) / `write_y4m_p10` (bits 10) write: 10-bit layouts other than mono carry
+    ffmpeg's `XYSCSS=` token; `XCOLORRANGE=` only when colour_range is given."""
+    ext = "" if bits == 8 or cs.startswith("mono") else f" XYSCSS={cs.upper()}"
+    if colour_range is not None:
+        if colour_range.upper() not in ("FULL", "LIMITED"):
+            raise ValueError(f"colour_range must be FULL or LIMITED, got {colour_range!r}")
+        ext += f" XCOLORRANGE={colour_range.upper()}"
+    return f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{cs}{ext}\n".encode()
+
+
+# ---- incremental Y4M: a stream of any length through a bounded buffer (stream.py, DESIGN.md 3.3g) -------------------
+def _y4m_stream_header(line: bytes, bits):
+    """Header fields of one header line (with its newline) as `_y4m_header` (8-bit) or `_y4m_header_p10` (10-bit)
+    return them, plus `bits`.  bits None picks the reader from the tag; 8 or 10 applies that reader's checks."""
+    if bits is None:
+        tag = b"420jpeg"
+        for tok in line.rstrip(b"\n").split(b" ")[1:]:
+            if tok[:1] == b"C":
+                tag = tok[1:]
+        bits = 10 if tag.decode(errors="replace") in Y4M_P10_TAGS else 8
+    if bits == 10:
+        hdr, _ = _y4m_header_p10(line)
+    elif bits == 8:
+        hdr, _ = _y4m_header(line)
+        hdr.update(bits=8, frame_samples=hdr["frame_bytes"])
+    else:
+        raise ValueError(f"bits must be None, 8 or 10, got {bits!r}")
+    return hdr
+
+
+class Y4MReader:
+    """Frame-at-a-time YUV4MPEG2 reader.  `src`: a path or a readable binary file object (a pipe, `sys.stdin.buffer`);
+    it is never seeked and nothing past the frames asked for is read from it.  The header is read on construction; its
+    fields (`width`, `height`, `fps`, `colourspace`, `colour_range`, `chroma`, `frame_bytes`, `frame_samples`, `bits`)
+    are those of `_y4m_header` / `_y4m_header_p10`, also as attributes.  bits: None (8 or 10 from the tag), or 8 / 10
+    to apply that whole-file reader's bit-depth checks and messages.
+
+    `read_into(buf, max_frames)` fills rows 0.. of a caller-owned C-contiguous array (any dtype; each row holds
+    `frame_bytes` bytes: uint8 [M, frame_bytes], uint16 [M, frame_samples], or the numpy view of a pinned tensor) with
+    the next frame payloads and returns how many it read: fewer than asked only at the end of the stream."""
+
+    def __init__(self, src, bits=None):
+        self._own = isinstance(src, (str, bytes, os.PathLike))
+        self._f = open(src, "rb") if self._own else src
+        try:
+            line = self._f.readline()
+            if not line.startswith(b"YUV4MPEG2"):
+                raise ValueError("not a YUV4MPEG2 stream")
+            if not line.endswith(b"\n"):
+                raise ValueError("Y4M: truncated stream header")
+            self.header = _y4m_stream_header(line, bits)
+        except BaseException:
+            self.close()
+            raise
+        for k, v in self.header.items():
+            setattr(self, k, v)
+        self.frames_read = 0
+        self._eof = False
+
+    def _fill(self, mv: memoryview) -> int:
+        got = 0
+        readinto = getattr(self._f, "readinto", None)
+        while got < len(mv):
+            if readinto is not None:
+                k = readinto(mv[got:])
+            else:
+                b = self._f.read(len(mv) - got)
+                k = len(b)
+                mv[got:got + k] = b
+            if not k:
+                break
+            got += k
+        return got
+
+    def read_into(self, buf: np.ndarray, max_frames: int = None) -> int:
+        rows = buf.reshape(buf.shape[0], -1) if buf.ndim != 2 else buf
+        if not rows.flags.c_contiguous or rows[0].nbytes != self.frame_bytes:
+            raise ValueError(f"read_into needs a C-contiguous array of rows of {self.frame_bytes} bytes, "
+                             f"got {buf.dtype} {buf.shape}")
+        want = rows.shape[0] if max_frames is None else min(int(max_frames), rows.shape[0])
+        n = 0
+        while n < want and not self._eof:
+            line = self._f.readline()
+            if not line:
+                self._eof = True
+                break
+            if not line.startswith(b"FRAME") or not line.endswith(b"\n"):
+                raise ValueError("Y4M: FRAME marker expected")
+            mv = memoryview(rows[n]).cast("B")
+            if self._fill(mv) < len(mv):
+                raise ValueError("Y4M: truncated frame")
+            n += 1
+        self.frames_read += n
+        if self._eof and not self.frames_read:
+            raise ValueError("Y4M: no frames")
+        return n
+
+    def close(self) -> None:
+        if self._own:
+            self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def y4m_frame_count(path) -> int:
+    """Frames in a Y4M file, by a pass that reads the FRAME lines and seeks past the payloads (a regular file only:
+    the frame count of a pipe is not known before it has been read)."""
+    with Y4MReader(path) as r:
+        f = r._f
+        size = os.fstat(f.fileno()).st_size
+        n = 0
+        while True:
+            line = f.readline()
+            if not line:
+                break
+            if not line.startswith(b"FRAME") or not line.endswith(b"\n"):
+                raise ValueError("Y4M: FRAME marker expected")
+            if f.tell() + r.frame_bytes > size:
+                raise ValueError("Y4M: truncated frame")
+            f.seek(r.frame_bytes, os.SEEK_CUR)
+            n += 1
+        if not n:
+            raise ValueError("Y4M: no frames")
+        return n
+
+
+class Y4MWriter:
+    """Frame-at-a-time YUV4MPEG2 writer.  `dst`: a path or a writable binary file object.  The header is written on
+    construction, byte for byte what `write_y4m` (bits 8; colourspace default "420jpeg") / `write_y4m_p10` (bits 10;
+    default "420p10") write for the same arguments.  `write(frames)` appends each row of a C-contiguous array (rows of
+    `frame_bytes` bytes: packed Y, U, V payloads; 16-bit samples in the host's little-endian order) behind a
+    `FRAME` line, straight from the array's memory (a pinned slot included): no per-frame copy."""
+
+    def __init__(self, dst, width: int, height: int, fps=(30, 1), colourspace: str = None, colour_range: str = None,
+                 bits: int = 8):
+        if bits == 10:
+            cs = colourspace or "420p10"
+            if cs not in Y4M_P10_TAGS:
+                raise ValueError(f"colourspace must be one of {Y4M_P10_TAGS}, got {cs!r}")
+        elif bits == 8:
+            cs = colourspace or "420jpeg"
+        else:
+            raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+        head = _y4m_header_line(int(width), int(height), fps, cs, colour_range, bits)
+        self.header = _y4m_stream_header(head, bits)
+        self.frame_bytes = self.header["frame_bytes"]
+        self.frames_written = 0
+        self._own = isinstance(dst, (str, bytes, os.PathLike))
+        self._f = open(dst, "wb") if self._own else dst
+        self._f.write(head)
+
+    def write(self, frames: np.ndarray) -> None:
+        if frames.shape[0] == 0:
+            return
+        rows = frames.reshape(frames.shape[0], -1)
+        if not rows.flags.c_contiguous or rows[0].nbytes != self.frame_bytes:
+            raise ValueError(f"write needs C-contiguous rows of {self.frame_bytes} bytes, got {frames.dtype} "
+                             f"{frames.shape}")
+        if rows.dtype.itemsize > 1 and rows.dtype.byteorder == ">":
+            raise ValueError("16-bit samples must be little-endian")
+        for row in rows:
+            self._f.write(b"FRAME\n")
+            self._f.write(memoryview(row).cast("B"))
+        self.frames_written += rows.shape[0]
+
+    def flush(self) -> None:
+        self._f.flush()
+
+    def close(self) -> None:
+        if self._own:
+            self._f.close()
+        else:
+            self._f.flush()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -535,7 +535,21 @@ class FrameInterpolator:
                                colour_range=hdr["colour_range"])
         return res.shape[0]
 
-    def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None):
+    def _interpolate_video_stream(self, input_path, output_path, factor, matrix, siting, thr, chunk_frames):
+        from . import stream
+        stream.check_chunk_frames(chunk_frames)
+        is_path = isinstance(input_path, (str, os.PathLike))
+        if is_path and not os.path.exists(input_path):
+            raise FileNotFoundError(f"Video file not found: {input_path}")
+        if not is_path or str(input_path).lower().endswith(".y4m"):
+            return stream.interpolate_y4m_stream(self.model, input_path, output_path, factor, batch=self.batch,
+                                                 chunk_frames=chunk_frames, matrix=matrix, siting=siting,
+                                                 scene_cut=thr)
+        return stream.interpolate_npy_stream(self.model, input_path, output_path, factor, batch=self.batch,
+                                             chunk_frames=chunk_frames, scene_cut=thr)
+
+    def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
+                          chunk_frames=None):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -545,10 +559,15 @@ class FrameInterpolator:
         scene_cut: None (off) or a threshold in (0, 100].  Cuts are detected once on the input frames, over every
         sample as stored (all planes, all channels; scene.py), and every frame inserted into a cut
         interval - factor - 1 of them, chroma included - is a byte copy of the frame before the cut.  10 separates
-        a hard cut from ordinary motion."""
+        a hard cut from ordinary motion.
+        chunk_frames: None holds the whole clip (host and device); an int streams it `chunk_frames` pairs at a time in
+        memory bounded by the chunk (stream.py), with a byte-identical result.  Streamed, the input
+        may also be a readable binary file object (Y4M: a pipe) and the output a writable one (Y4M)."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
+        if chunk_frames is not None:
+            return self._interpolate_video_stream(input_path, output_path, factor, matrix, siting, thr, chunk_frames)
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Video file not found: {input_path}")
         if str(input_path).lower().endswith(".y4m"):

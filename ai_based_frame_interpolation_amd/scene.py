@@ -99,6 +99,30 @@ def detect_cuts(stacks: Stacks, threshold: float, bits: int) -> Tuple[torch.Tens
 
 
 @torch.no_grad()
+def score_window(sums: torch.Tensor, count: int, bits: int, threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (scores float64 [K], flags uint8 [K]) on the device for a window of K consecutive interval sums (int64, as
+    `pair_sad` returns them) of frames of `count` samples: `fiunet_scene_cuts` on the window alone, so the first and
+    last interval of the window are scored without their outer neighbour.  The streaming loop (stream.py) passes the
+    carried interval, a chunk's intervals and the lookahead interval, and keeps the chunk's own: each of those has both
+    neighbours in the window (or sits at the clip's edge), so its score equals `detect_cuts` on the whole clip."""
+    thr = check_threshold(threshold)
+    if thr is None:
+        raise ValueError("score_window needs a threshold in (0, 100]")
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+    if sums.dtype != torch.int64 or sums.dim() != 1 or not sums.is_cuda:
+        raise ValueError("sums must be an int64 [K] device tensor")
+    k = sums.shape[0]
+    sums = sums.contiguous()
+    scores = torch.zeros(k, dtype=torch.float64, device=sums.device)
+    flags = torch.zeros(k, dtype=torch.uint8, device=sums.device)
+    if k and count:
+        with torch.cuda.device(sums.device):
+            _native.scene_cuts(sums, k + 1, int(count), bits, thr, scores, flags)
+    return scores, flags
+
+
+@torch.no_grad()
 def hold_cut_frames(video: torch.Tensor, flags: torch.Tensor, factor: int) -> torch.Tensor:
     """In place on the contiguous interleaved result [(N-1)*factor + 1, ...] of a factor-`factor` loop (any dtype): for
     every flagged interval i, frames i*factor + 1 .. i*factor + factor - 1 become byte copies of frame i*factor.
@@ -121,4 +145,4 @@ def hold_cut_frames(video: torch.Tensor, flags: torch.Tensor, factor: int) -> to
     return video
 
 
-__all__ = ["check_threshold", "pair_sad", "detect_cuts", "hold_cut_frames"]
+__all__ = ["check_threshold", "pair_sad", "detect_cuts", "score_window", "hold_cut_frames"]

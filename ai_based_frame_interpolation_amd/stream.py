@@ -1,0 +1,460 @@
+"""Streaming video: interpolate a clip of any length, from a file or a pipe, in memory bounded by the chunk.
+
+`FrameInterpolator.interpolate_video` (chunk_frames=None) holds the whole clip in host memory and on the device.  This
+module runs the same routes chunk by chunk:
+
+  chunk      `chunk_frames` input pairs plus the overlap frame it shares with the next chunk.  On the device each
+             chunk runs the helpers the resident routes call (`interpolate_sequence*`, `_interleave_average_*`,
+             `_padded_chunk` inside them, `_hold`), one level per factor bit.  Every middle depends only on its two
+             neighbours and `_padded_chunk` makes a pair's result independent of the pairs that share its call, so the
+             output is byte for byte the resident one for every chunk_frames >= 1.  The overlap frame is written once.
+  scene cuts the two-sided score of interval i needs mafd[i-1] and mafd[i+1]: with `scene_cut` on, a chunk carries
+             one lookahead frame and the previous chunk's last interval sum; `scene.score_window` scores the window
+             (carried interval, the chunk's intervals, lookahead interval) and the chunk keeps its own flags, which
+             equal `scene.detect_cuts` on the whole clip bit for bit.
+  pipeline   a reader thread fills a ring of pinned input slots; H2D copies go on one copy stream, the chunk computes
+             on the caller's stream, D2H copies of the result go into pinned output slots on a second copy stream, and
+             a writer thread writes each slot once its event has completed.  Events order the streams (no device-wide
+             synchronise per chunk); the host waits only for a slot it is about to reuse.
+
+Memory is bounded by the chunk, never by the clip (C = chunk_frames, F = factor, one frame of the input layout):
+  host pinned    3 x (C + 2) input frames + 2 x (C x F + 1) output frames
+  device         2 x (C + 2) input frames + one chunk's levels + the previous chunk's result (C x F + 1 frames of
+                 the output layout; at factor 2 the levels are one result, at factor F about 2 x (C x F + 1) frames)
+"""
+from __future__ import annotations
+
+import numbers
+import os
+import queue
+import stat
+import threading
+
+import numpy as np
+import torch
+
+from . import colour, imageio_lite, scene
+from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
+                        interpolate_sequence_p10, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10)
+
+R_IN, R_OUT = 3, 2   # pinned input / output slots in the rings
+
+
+# ---- argument checks (host only: nothing here touches the device) ---------------------------------------------------
+def check_chunk_frames(chunk_frames) -> int:
+    if isinstance(chunk_frames, bool) or not isinstance(chunk_frames, numbers.Integral) or chunk_frames < 1:
+        raise ValueError(f"chunk_frames must be a positive int, got {chunk_frames!r}")
+    return int(chunk_frames)
+
+
+def _check_common(factor, batch, chunk_frames, scene_cut):
+    thr = scene.check_threshold(scene_cut)
+    if isinstance(factor, bool) or not isinstance(factor, numbers.Integral) or factor < 2 or factor & (factor - 1):
+        raise ValueError("factor must be a power of two (the network has no time input)")
+    if isinstance(batch, bool) or not isinstance(batch, numbers.Integral) or batch < 1:
+        raise ValueError(f"batch must be a positive int, got {batch!r}")
+    return thr, check_chunk_frames(chunk_frames)
+
+
+def _is_path(x) -> bool:
+    return isinstance(x, (str, os.PathLike))
+
+
+def _levels(factor: int) -> int:
+    return factor.bit_length() - 1
+
+
+# ---- routes: one chunk [k, row] of input frames -> [(k-1) x factor + 1, out_row] output rows on the device -----------
+class _Route:
+    """bits: sample depth (8: uint8 rows; 10: int16 words of 10-bit codes on the device, uint16 on the host); row /
+    out_row: samples per input / output frame; run(d, factor): the levels of one chunk, the same helpers as the
+    resident route."""
+
+    def __init__(self, bits, row, out_row, run):
+        self.bits, self.row, self.out_row, self.run = bits, row, out_row, run
+        self.tdtype = torch.uint8 if bits == 8 else torch.int16
+        self.ndtype = np.uint8 if bits == 8 else np.uint16
+
+
+def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
+    """The route `interpolate_video` takes for this stream header and model, with its refusals and messages."""
+    h, w, (hc, wc), bits = hdr["height"], hdr["width"], hdr["chroma"], hdr["bits"]
+    ny, nc, row = h * w, hc * wc, hdr["frame_samples"]
+    if model.frame_channels == 3:
+        rng = "full" if hdr["colour_range"] == "FULL" else "limited"
+        if bits == 10:
+            if hdr["colourspace"] != "420p10":
+                raise ValueError(f"Y4M colourspace C{hdr['colourspace']} is not supported by the RGB network: it "
+                                 "reads 10-bit 4:2:0 video tagged C420p10")
+            if npy_out:
+                raise ValueError("colour Y4M video through the RGB network is written as .y4m (no .npy output)")
+            opts = dict(siting="mpeg2" if siting is None else siting, matrix=matrix, colour_range=rng)
+            colour.colour_flags(**opts, bits=10)
+
+            def run(d, factor):
+                t = d.view(torch.uint16)
+                for _ in range(_levels(factor)):
+                    t = interpolate_sequence_yuv420p10(model, t, h, w, batch, **opts)
+                return t.view(torch.int16)
+            return _Route(10, row, row, run)
+        if npy_out:
+            raise ValueError("colour Y4M video through the RGB network is written as .y4m (no .npy output)")
+        tag_siting = colour.siting_of_y4m(hdr["colourspace"])
+        opts = dict(siting=tag_siting if siting is None else siting, matrix=matrix, colour_range=rng)
+        colour.colour_flags(**opts)
+
+        def run(d, factor):
+            for _ in range(_levels(factor)):
+                d = interpolate_sequence_yuv420(model, d, h, w, batch, **opts)
+            return d
+        return _Route(8, row, row, run)
+    if model.frame_channels != 1:
+        raise ValueError("Y4M video goes through the grayscale (2->1) network")
+    out_row = ny if npy_out else row
+
+    def run(d, factor):
+        k = d.shape[0]
+        y = d[:, :ny].reshape(k, h, w).contiguous()
+        cu = cv = None
+        if nc:
+            cu, cv = (d[:, ny + i * nc:ny + (i + 1) * nc].reshape(k, hc, wc) for i in (0, 1))
+            if bits == 10:   # the resident route's int32 chroma: the 16-bit words as unsigned samples
+                cu, cv = ((c.to(torch.int32) & 0xFFFF) for c in (cu, cv))
+            else:
+                cu, cv = cu.contiguous(), cv.contiguous()
+        if bits == 10:
+            y = y.view(torch.uint16)
+        for _ in range(_levels(factor)):
+            if bits == 10:
+                y = interpolate_sequence_p10(model, y, batch)
+                if cu is not None:
+                    cu, cv = (_interleave_average_p10(c) for c in (cu, cv))
+            else:
+                y = interpolate_sequence(model, y, batch)
+                if cu is not None:
+                    cu, cv = (_interleave_average_u8(c) for c in (cu, cv))
+        n = y.shape[0]
+        y = (y.view(torch.int16) if bits == 10 else y).reshape(n, ny)
+        if npy_out or cu is None:
+            return y
+        return torch.cat([y] + [c.to(y.dtype).reshape(n, nc) for c in (cu, cv)], dim=1)
+    return _Route(bits, row, out_row, run)
+
+
+def _npy_route(model, shape, batch: int) -> _Route:
+    """`interpolate_video`'s .npy route for uint8 frames of `shape` ([H,W] or [H,W,C])."""
+    row = int(np.prod(shape))
+    if len(shape) == 2:
+        h, w = shape
+
+        def run(d, factor):
+            t = d.reshape(d.shape[0], h, w)
+            for _ in range(_levels(factor)):
+                t = interpolate_sequence(model, t, batch)
+            return t.reshape(t.shape[0], row)
+        return _Route(8, row, row, run)
+    h, w, c = shape
+
+    def run(d, factor):
+        k = d.shape[0]
+        t = d.reshape(k, h, w, c).permute(0, 3, 1, 2).contiguous()
+        if model.frame_channels == 1:   # per-channel application of the 2->1 network
+            t = t.permute(1, 0, 2, 3).reshape(c * k, h, w)
+            outs = []
+            for ci in range(c):
+                seq = t[ci * k:(ci + 1) * k]
+                for _ in range(_levels(factor)):
+                    seq = interpolate_sequence(model, seq, batch)
+                outs.append(seq)
+            res = torch.stack(outs, dim=-1)
+        else:
+            for _ in range(_levels(factor)):
+                t = interpolate_sequence(model, t, batch)
+            res = t.permute(0, 2, 3, 1).contiguous()
+        return res.reshape(res.shape[0], row)
+    return _Route(8, row, row, run)
+
+
+# ---- sources and sinks over .npy files --------------------------------------------------------------------------
+class _NpyRows:
+    """`read_into` over the rows of a memory-mapped .npy stack (Y4MReader's interface)."""
+
+    def __init__(self, mm: np.ndarray):
+        self.mm, self.pos = mm, 0
+
+    def read_into(self, buf: np.ndarray, max_frames: int) -> int:
+        k = min(int(max_frames), self.mm.shape[0] - self.pos)
+        if k > 0:
+            buf[:k] = self.mm[self.pos:self.pos + k].reshape(k, -1)
+            self.pos += k
+        return max(k, 0)
+
+
+class _NpyWriter:
+    """`write` of output rows into a .npy file made by `np.lib.format.open_memmap` (the header np.save writes), at
+    `<path>.part` until `close(ok)` renames it (or removes it)."""
+
+    def __init__(self, path, dtype, shape):
+        self.path, self.part = path, path + ".part"
+        self.mm = np.lib.format.open_memmap(self.part, mode="w+", dtype=dtype, shape=tuple(shape))
+        self.pos = 0
+
+    def write(self, rows: np.ndarray) -> None:
+        k = rows.shape[0]
+        self.mm[self.pos:self.pos + k] = rows.reshape((k,) + self.mm.shape[1:])
+        self.pos += k
+
+    def close(self, ok: bool) -> None:
+        self.mm.flush()
+        del self.mm
+        if ok:
+            os.replace(self.part, self.path)
+        else:
+            os.remove(self.part)
+
+
+# ---- the engine ---------------------------------------------------------------------------------------------------
+class _Failure:
+    def __init__(self):
+        self.exc = None
+        self.stop = threading.Event()
+
+    def set(self, exc):
+        if self.exc is None:
+            self.exc = exc
+        self.stop.set()
+
+    def get(self, q: queue.Queue):
+        """q.get() that gives up once another thread has failed."""
+        while True:
+            try:
+                return q.get(timeout=0.05)
+            except queue.Empty:
+                if self.stop.is_set():
+                    raise _Stopped()
+
+
+class _Stopped(Exception):
+    pass
+
+
+@torch.no_grad()
+def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, thr, scene_log=None) -> int:
+    """Stream `reader` through `route` into `write(rows)`; returns the number of output frames."""
+    dev = next(model.parameters()).device
+    C, look = chunk_frames, 1 if thr is not None else 0
+    in_rows, out_rows = C + 1 + look, C * factor + 1
+    in_slots = [torch.empty((in_rows, route.row), dtype=route.tdtype).pin_memory() for _ in range(R_IN)]
+    out_slots = [torch.empty((out_rows, route.out_row), dtype=route.tdtype).pin_memory() for _ in range(R_OUT)]
+    in_np = [s.numpy().view(route.ndtype) for s in in_slots]
+    out_np = [s.numpy().view(route.ndtype) for s in out_slots]
+    free_in, filled, free_out, done = queue.Queue(), queue.Queue(), queue.Queue(), queue.Queue()
+    for i in range(R_IN):
+        free_in.put(i)
+    for i in range(R_OUT):
+        free_out.put(i)
+    fail = _Failure()
+
+    def reader_main():
+        try:
+            s, carry, prev, prev_m = 0, 0, None, 0
+            while True:
+                i = fail.get(free_in)
+                buf = in_np[i]
+                if carry:   # the overlap frame (and the lookahead frame) of the previous chunk
+                    buf[:carry] = in_np[prev][prev_m - carry:prev_m]
+                m = carry + reader.read_into(buf[carry:], in_rows - carry)
+                if m == in_rows:
+                    filled.put((i, s, m, C, False))
+                    s, carry, prev, prev_m = s + C, 1 + look, i, m
+                    continue
+                if m == 0:
+                    raise ValueError("no frames to interpolate")
+                if m > 1 or s == 0:   # the last chunk (a one-frame clip is one chunk without pairs)
+                    filled.put((i, s, m, m - 1, True))
+                filled.put(None)
+                return
+        except _Stopped:
+            pass
+        except BaseException as e:  # noqa: BLE001 - re-raised by the main thread
+            fail.set(e)
+
+    def writer_main():
+        try:
+            while True:
+                item = fail.get(done)
+                if item is None:
+                    return
+                o, n, ev = item
+                ev.synchronize()
+                write(out_np[o][:n])
+                free_out.put(o)
+        except _Stopped:
+            pass
+        except BaseException as e:  # noqa: BLE001
+            fail.set(e)
+
+    threads = [threading.Thread(target=reader_main, daemon=True), threading.Thread(target=writer_main, daemon=True)]
+    for t in threads:
+        t.start()
+    compute = torch.cuda.current_stream(dev)
+    h2d, d2h = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    d_in = [torch.empty((in_rows, route.row), dtype=route.tdtype, device=dev) for _ in range(2)]
+    d_free = [None, None]   # event: the compute stream's last read of d_in[j]
+    count = route.row       # samples per frame, as scene.detect_cuts counts them
+    carried = None          # int64 [1]: the previous chunk's last interval sum
+    total, j = 0, 0
+    try:
+        while True:
+            item = fail.get(filled)
+            if item is None:
+                break
+            i, s, m, c, _last = item
+            # the output slot of chunk i - R_OUT: written out, and (R_OUT = 2) that chunk's result is back in the
+            # allocator before this chunk allocates: the device holds this chunk's levels and the previous result
+            o = fail.get(free_out)
+            with torch.cuda.stream(h2d):
+                if d_free[j] is not None:
+                    h2d.wait_event(d_free[j])
+                d_in[j][:m].copy_(in_slots[i][:m], non_blocking=True)
+                up = torch.cuda.Event()
+                up.record(h2d)
+            compute.wait_event(up)
+            d = d_in[j][:m]
+            flags = None
+            if thr is not None and c > 0:
+                sums = scene.pair_sad([d], route.bits)   # c own intervals, then the lookahead interval if read
+                window = sums if carried is None else torch.cat([carried, sums])
+                scores, fl = scene.score_window(window, count, route.bits, thr)
+                off = 0 if carried is None else 1
+                flags = fl[off:off + c]
+                carried = sums[c - 1:c]
+                if scene_log is not None:
+                    scene_log.append((scores[off:off + c].cpu().numpy(), flags.cpu().numpy()))
+            out = route.run(d[:c + 1], factor)   # (a one-frame clip: the frame itself)
+            _hold(flags, factor, out)
+            d_free[j] = torch.cuda.Event()
+            d_free[j].record(compute)
+            rows = out if s == 0 else out[1:]   # a later chunk's first frame is the previous chunk's last
+            with torch.cuda.stream(d2h):
+                d2h.wait_stream(compute)
+                out_slots[o][:rows.shape[0]].copy_(rows, non_blocking=True)
+                out.record_stream(d2h)
+                ev = torch.cuda.Event()
+                ev.record(d2h)
+            done.put((o, rows.shape[0], ev))
+            total += rows.shape[0]
+            up.synchronize()   # the input slot's H2D copy has completed: the reader may refill it
+            free_in.put(i)
+            j ^= 1
+        done.put(None)
+        threads[1].join()
+    except _Stopped:
+        pass
+    except BaseException as e:  # noqa: BLE001
+        fail.set(e)
+    if fail.exc is not None:
+        fail.stop.set()
+        for t in threads:
+            t.join(timeout=5.0)
+        compute.synchronize()
+        raise fail.exc
+    threads[0].join()
+    d2h.synchronize()
+    compute.synchronize()
+    for t in d_in:   # read by the h2d stream: back to the allocator only after it
+        t.record_stream(h2d)
+    return total
+
+
+def _open_sink(dst):
+    """-> (file object, finish(ok)).  A path is written to `<dst>.part` and renamed on success, removed on error; a
+    file object (a pipe) keeps what was written before an error."""
+    if not _is_path(dst):
+        return dst, lambda ok: dst.flush()
+    part = os.fspath(dst) + ".part"
+    f = open(part, "wb")
+
+    def finish(ok):
+        f.close()
+        if ok:
+            os.replace(part, dst)
+        else:
+            os.remove(part)
+    return f, finish
+
+
+def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
+                           matrix: str = "bt709", siting: str | None = None, scene_cut: float | None = None,
+                           scene_log: list | None = None) -> int:
+    """Y4M in (a path or a readable binary file: a pipe, `sys.stdin.buffer`) -> Y4M out (a path or a writable binary
+    file), or a `.npy` path of the luma frames (grayscale network; the input must then be a regular file, whose frame
+    count a first pass reads).  Every route, header, refusal and result is that of `FrameInterpolator.interpolate_video`
+    on the same arguments, byte for byte, for any `chunk_frames` >= 1.  Returns the output frame count.  Every argument
+    is checked before anything is pinned, before any GPU work and before the output exists.  scene_log: a list that
+    receives (scores float64, flags uint8) host arrays of each chunk's intervals (tests; costs a synchronise)."""
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
+    npy_out = isinstance(dst, (str, os.PathLike)) and os.fspath(dst).lower().endswith(".npy")
+    if npy_out:
+        if not _is_path(src) or not stat.S_ISREG(os.stat(src).st_mode):
+            raise ValueError("a .npy output needs the frame count up front, and a Y4M stream from a pipe cannot be "
+                             "counted before it is read: write Y4M, or read the stream from a regular file")
+    reader = imageio_lite.Y4MReader(src)
+    try:
+        route = _y4m_route(model, reader.header, npy_out, batch, matrix, siting)
+        hdr = reader.header
+        fps = (hdr["fps"][0] * factor, hdr["fps"][1])
+        if npy_out:
+            n = imageio_lite.y4m_frame_count(src)
+            shape = ((n - 1) * factor + 1, hdr["height"], hdr["width"])
+            sink = _NpyWriter(os.fspath(dst), np.uint16 if route.bits == 10 else np.uint8, shape)
+            ok = False
+            try:
+                total = _run(model, route, reader, sink.write, factor, C, thr, scene_log)
+                ok = True
+            finally:
+                sink.close(ok)
+            return total
+        f, finish = _open_sink(dst)
+        ok = False
+        try:
+            w = imageio_lite.Y4MWriter(f, hdr["width"], hdr["height"], fps, hdr["colourspace"],
+                                       hdr["colour_range"] if (route.bits == 10 or model.frame_channels == 3) else None,
+                                       bits=route.bits)
+            total = _run(model, route, reader, w.write, factor, C, thr, scene_log)
+            ok = True
+        finally:
+            finish(ok)
+        return total
+    finally:
+        reader.close()
+
+
+def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
+                           scene_cut: float | None = None, scene_log: list | None = None) -> int:
+    """`.npy` stack in (uint8 [N,H,W] or [N,H,W,C], read through `np.load(mmap_mode="r")`) -> `.npy` out (written
+    through `np.lib.format.open_memmap`): byte for byte the file `interpolate_video` saves.  Returns the output frame
+    count."""
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
+    if not _is_path(dst):
+        raise ValueError("a .npy output is a path")
+    dst = os.fspath(dst)
+    if not dst.endswith(".npy"):   # what np.save does with the name
+        dst += ".npy"
+    mm = np.load(src, mmap_mode="r")
+    if mm.dtype != np.uint8 or mm.ndim not in (3, 4):
+        raise ValueError("expected a uint8 .npy stack [N,H,W] or [N,H,W,3]")
+    if mm.shape[0] < 1:
+        raise ValueError("no frames to interpolate")
+    route = _npy_route(model, mm.shape[1:], batch)
+    sink = _NpyWriter(dst, np.uint8, ((mm.shape[0] - 1) * factor + 1,) + mm.shape[1:])
+    ok = False
+    try:
+        total = _run(model, route, _NpyRows(mm), sink.write, factor, C, thr, scene_log)
+        ok = True
+    finally:
+        sink.close(ok)
+    return total
+
+
+__all__ = ["check_chunk_frames", "interpolate_y4m_stream", "interpolate_npy_stream"]
