@@ -12,7 +12,7 @@ from .serving import InterpolationService  # noqa: F401
 from .colour import (  # noqa: F401
     i420_frame_bytes, rgb_to_yuv420, rgb_to_yuv420p10, yuv420_to_rgb, yuv420p10_frame_samples, yuv420p10_to_rgb,
 )
-from . import colour, evaluation, metrics, optical_flow, scene, serving, stream, synthetic, tiling, transport, video  # noqa: F401
+from . import colour, evaluation, metrics, optical_flow, retime, scene, serving, stream, synthetic, tiling, transport, video  # noqa: F401
 
 __all__ = [
     "FrameInterpolationUNet", "GraphedForward", "UNet", "count_parameters", "FrameInterpolator",
@@ -22,5 +22,5 @@ __all__ = [
     "yuv420_to_rgb", "rgb_to_yuv420", "yuv420p10_frame_samples", "yuv420p10_to_rgb", "rgb_to_yuv420p10",
     "transport", "optical_flow",
     "load_model", "postprocess_image", "preprocess_image", "evaluation", "metrics", "tiling", "video",
-    "InterpolationService", "serving", "synthetic", "scene", "stream",
+    "InterpolationService", "serving", "synthetic", "scene", "stream", "retime",
 ]

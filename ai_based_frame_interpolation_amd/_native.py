@@ -43,6 +43,7 @@ SYMBOLS = (
     "fiunet_yuv420p10_to_rgb_p10", "fiunet_rgb_p10_to_yuv420p10", "fiunet_workspace_bytes_yuv420p10",
     "fiunet_forward_yuv420p10",
     "fiunet_pair_sad_u8", "fiunet_pair_sad_p10", "fiunet_scene_cuts", "fiunet_hold_cut_frames",
+    "fiunet_retime_u8", "fiunet_retime_p10",
 )
 
 _lib = None
@@ -132,6 +133,9 @@ def lib() -> ctypes.CDLL:
     L.fiunet_pair_sad_p10.argtypes = [vp, ci, sz, vp, vp]
     L.fiunet_scene_cuts.argtypes = [vp, ci, sz, ci, ctypes.c_double, vp, vp, vp]
     L.fiunet_hold_cut_frames.argtypes = [vp, ci, sz, ci, vp, vp]
+    u64, u32 = ctypes.c_uint64, ctypes.c_uint32
+    L.fiunet_retime_u8.argtypes = [vp, ci, sz, ci, u64, u64, ci, u32, u32, ci, vp, vp, vp]
+    L.fiunet_retime_p10.argtypes = [vp, ci, sz, ci, u64, u64, ci, u32, u32, ci, vp, vp, vp]
     L.fiunet_debug_read_activation.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz,
                                                ctypes.POINTER(ci), vp]
     L.fiunet_metrics_workspace_bytes.argtypes = [ci, ci, ci]
@@ -446,3 +450,15 @@ def hold_cut_frames(video: "torch.Tensor", n_frames: int, factor: int, flags: "t
     s = torch.cuda.current_stream(video.device).cuda_stream
     check(lib().fiunet_hold_cut_frames(video.data_ptr(), n_frames, fb, factor, flags.data_ptr(), s),
           "fiunet_hold_cut_frames")
+
+
+def retime(grid: "torch.Tensor", n_intervals: int, depth: int, first_interval: int, j0: int, n_out: int, p: int,
+           q: int, mode: int, flags, out: "torch.Tensor", bits: int) -> None:
+    """fiunet_retime_u8 / fiunet_retime_p10: a contiguous grid [(n_intervals << depth) + 1, ...] (uint8 at 8 bits; 16-bit
+    words at 10) -> `out` [n_out, ...], clip output frames j0 .. j0 + n_out - 1; flags uint8 [n_intervals] or None."""
+    fs = grid[0].numel()
+    fn = lib().fiunet_retime_p10 if bits == 10 else lib().fiunet_retime_u8
+    s = torch.cuda.current_stream(grid.device).cuda_stream
+    check(fn(grid.data_ptr(), n_intervals, fs, depth, first_interval, j0, n_out, p, q, mode,
+             None if flags is None else flags.data_ptr(), out.data_ptr(), s),
+          "fiunet_retime_" + ("p10" if bits == 10 else "u8"))

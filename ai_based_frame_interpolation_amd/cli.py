@@ -1,11 +1,15 @@
 """Command line: `python -m ai_based_frame_interpolation_amd.cli video --input IN --output OUT [--factor 2] ...`
 
 The reference's `main.py video` flags (--input, --output, --factor, --model, --device), plus --precision, --matrix,
---siting, --scene-cut, --batch and --chunk-frames.  The command always streams (stream.py), so a clip of
-any length runs in memory bounded by the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
+--siting, --scene-cut, --batch, --chunk-frames and the frame-rate conversion's --fps, --src-fps, --time-depth and
+--retime.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
+the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 
     ffmpeg -i in.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - \\
         --model best_model.pth | ffmpeg -f yuv4mpegpipe -i - out.mkv
+
+With `--fps 60000/1001` (a fraction or an integer, never a decimal) the output has that frame rate instead of
+--factor times the input's (retime.py): 23.976 -> 59.94, 24 -> 60, 25 -> 60, 50 -> 120.
 
 Standard output then carries nothing but Y4M: the model-loading lines go to standard error.  The network (grayscale
 2->1 or RGB 6->3) is read from the checkpoint.
@@ -17,6 +21,8 @@ import contextlib
 import sys
 
 import torch
+
+from . import retime
 
 FIRST_CONV = "unet.inc.double_conv.0.weight"
 
@@ -40,6 +46,13 @@ def _siting(v: str):
     return None if v.lower() == "none" else v
 
 
+def _fps(v: str):
+    try:
+        return retime.parse_fps(v)
+    except ValueError as e:   # argparse prints an ArgumentTypeError's own text
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m ai_based_frame_interpolation_amd.cli",
                                  description="AI frame interpolation on the MI355X")
@@ -56,6 +69,13 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--scene-cut", type=_scene_cut, default=None, help="Scene-cut threshold in (0, 100], or none")
     v.add_argument("--batch", type=int, default=8, help="Frame pairs per forward")
     v.add_argument("--chunk-frames", type=int, default=None, help="Frame pairs per streamed chunk (default 4 x batch)")
+    v.add_argument("--fps", type=_fps, default=None,
+                   help="Output frame rate as n or n/d (60, 60000/1001); replaces --factor")
+    v.add_argument("--src-fps", type=_fps, default=None,
+                   help="Source frame rate as n or n/d (default: the Y4M header's)")
+    v.add_argument("--time-depth", type=int, default=2, choices=(1, 2, 3, 4), help="Bisection levels under --fps")
+    v.add_argument("--retime", default="blend", choices=retime.MODES,
+                   help="How --fps picks between the two bisection frames around an output time")
     return ap
 
 
@@ -78,7 +98,8 @@ def run_video(a: argparse.Namespace) -> int:
     src = sys.stdin.buffer if a.input == "-" else a.input
     dst = sys.stdout.buffer if a.output == "-" else a.output
     n = fi.interpolate_video(src, dst, a.factor, matrix=a.matrix, siting=a.siting, scene_cut=a.scene_cut,
-                             chunk_frames=a.chunk_frames)
+                             chunk_frames=a.chunk_frames, fps=a.fps, src_fps=a.src_fps, time_depth=a.time_depth,
+                             retime=a.retime)
     print(f"wrote {n} frames", file=sys.stderr)
     return n
 

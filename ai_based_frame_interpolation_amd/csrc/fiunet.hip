@@ -13,6 +13,7 @@
 #include "metrics.hip.h"
 #include "colour.hip.h"
 #include "scene.hip.h"
+#include "retime.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1753,6 +1754,55 @@ int fiunet_hold_cut_frames(uint8_t* video, int n_frames, size_t frame_bytes, int
         HIP_TRY(hipGetLastError());
     }
     return FIUNET_OK;
+}
+
+// ---- frame-rate conversion (csrc/retime.hip.h) ---------------------------------------------------
+extern "C++" {
+template <typename T>
+static int retime(const T* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval, uint64_t j0,
+                  int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, T* out, void* stream)
+{
+    if (!grid || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_intervals < 0 || n_out < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
+    if (depth < 1 || depth > 4) return fail(FIUNET_ERR_INVALID_ARG, "depth outside 1..4");
+    if (p == 0 || p >= q) return fail(FIUNET_ERR_INVALID_ARG, "need 0 < p < q");
+    if (q > kRetimeMaxQ) return fail(FIUNET_ERR_INVALID_ARG, "q above 2^20");
+    if (mode != 0 && mode != 1) return fail(FIUNET_ERR_INVALID_ARG, "mode must be 0 (blend) or 1 (nearest)");
+    if (n_out == 0) return FIUNET_OK;
+    // the first and the last requested frame lie in the grid (the times in between do, being monotonic); in 128 bits,
+    // so that the kernel's 64-bit j * p cannot wrap
+    const unsigned __int128 t0 = (unsigned __int128)j0 * p, t1 = ((unsigned __int128)j0 + (unsigned)(n_out - 1)) * p;
+    if (t1 >> 64) return fail(FIUNET_ERR_INVALID_ARG, "frame index too large");
+    const unsigned __int128 end = (unsigned __int128)first_interval + (unsigned)n_intervals;
+    if (t0 / q < first_interval) return fail(FIUNET_ERR_INVALID_ARG, "first frame lies before the grid");
+    if (t1 / q > end || (t1 / q == end && t1 % q != 0))
+        return fail(FIUNET_ERR_INVALID_ARG, "last frame lies behind the grid");
+    if (frame_samples == 0) return FIUNET_OK;
+    // ~4 x 16 B per thread and at most 128 workgroups per frame, as fiunet_pair_sad_u8
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
+    for (int k0 = 0; k0 < n_out; k0 += kMaxGridY) {
+        const int nk = std::min(n_out - k0, kMaxGridY);
+        hipLaunchKernelGGL(retime_kernel<T>, dim3(bx, (unsigned)nk), dim3(kRetimeBlock), 0, (hipStream_t)stream, grid,
+                           frame_samples, depth, (unsigned long long)first_interval, (unsigned long long)(j0 + k0), p, q,
+                           mode, flags, out + (size_t)k0 * frame_samples);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_retime_u8(const uint8_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
+                     uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint8_t* out,
+                     void* stream)
+{
+    return retime(grid, n_intervals, frame_samples, depth, first_interval, j0, n_out, p, q, mode, flags, out, stream);
+}
+
+int fiunet_retime_p10(const uint16_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
+                      uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint16_t* out,
+                      void* stream)
+{
+    return retime(grid, n_intervals, frame_samples, depth, first_interval, j0, n_out, p, q, mode, flags, out, stream);
 }
 
 // diagnostic (not part of the ABI, no declaration in include/fiunet.h): override choose_conv_cfg for one conv (1..17) of

@@ -535,21 +535,23 @@ class FrameInterpolator:
                                colour_range=hdr["colour_range"])
         return res.shape[0]
 
-    def _interpolate_video_stream(self, input_path, output_path, factor, matrix, siting, thr, chunk_frames):
+    def _interpolate_video_stream(self, input_path, output_path, factor, matrix, siting, thr, chunk_frames, **rate):
+        """rate: fps / src_fps / time_depth / retime; with fps, chunk_frames None is the whole clip as one chunk."""
         from . import stream
-        stream.check_chunk_frames(chunk_frames)
+        if chunk_frames is not None or rate.get("fps") is None:
+            stream.check_chunk_frames(chunk_frames)
         is_path = isinstance(input_path, (str, os.PathLike))
         if is_path and not os.path.exists(input_path):
             raise FileNotFoundError(f"Video file not found: {input_path}")
         if not is_path or str(input_path).lower().endswith(".y4m"):
             return stream.interpolate_y4m_stream(self.model, input_path, output_path, factor, batch=self.batch,
                                                  chunk_frames=chunk_frames, matrix=matrix, siting=siting,
-                                                 scene_cut=thr)
+                                                 scene_cut=thr, **rate)
         return stream.interpolate_npy_stream(self.model, input_path, output_path, factor, batch=self.batch,
-                                             chunk_frames=chunk_frames, scene_cut=thr)
+                                             chunk_frames=chunk_frames, scene_cut=thr, **rate)
 
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
-                          chunk_frames=None):
+                          chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend"):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -562,12 +564,24 @@ class FrameInterpolator:
         a hard cut from ordinary motion.
         chunk_frames: None holds the whole clip (host and device); an int streams it `chunk_frames` pairs at a time in
         memory bounded by the chunk (stream.py), with a byte-identical result.  Streamed, the input
-        may also be a readable binary file object (Y4M: a pipe) and the output a writable one (Y4M)."""
+        may also be a readable binary file object (Y4M: a pipe) and the output a writable one (Y4M).
+        fps: None, or the frame rate of the output, above the source's: an int, a Fraction, an (n, d) pair or an "n/d"
+        string such as "60000/1001" (no floats: 59.94 is not 60000/1001).  `factor` then stays 2; every route builds
+        the frames of a 2**time_depth bisection (time_depth 1..4; what factor = 2**time_depth computes, cut holds
+        included) and resamples them on the device to the times j x source rate / fps (retime.py):
+        retime "blend" weighs the two bisection frames around each time, "nearest" takes the closer one; no frame
+        blends across a flagged cut.  The Y4M header carries fps reduced.  src_fps: the source rate, required for
+        .npy input; for Y4M it overrides the header's."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
-        if chunk_frames is not None:
-            return self._interpolate_video_stream(input_path, output_path, factor, matrix, siting, thr, chunk_frames)
+        from . import stream
+        rate = dict(zip(("fps", "src_fps", "time_depth", "retime"),
+                        stream.check_retime(fps, src_fps, time_depth, retime, factor)))
+        # (an `fps` run without chunk_frames takes the same routes with the whole clip as one chunk: stream._run_whole)
+        if chunk_frames is not None or rate["fps"] is not None:
+            return self._interpolate_video_stream(input_path, output_path, factor, matrix, siting, thr, chunk_frames,
+                                                  **rate)
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Video file not found: {input_path}")
         if str(input_path).lower().endswith(".y4m"):

@@ -17,10 +17,19 @@ module runs the same routes chunk by chunk:
              a writer thread writes each slot once its event has completed.  Events order the streams (no device-wide
              synchronise per chunk); the host waits only for a slot it is about to reuse.
 
+  fps        with `fps=` (retime.py) a chunk of c intervals starting at s builds its c x G + 1-frame
+             grid as the factor = G run does (G = 2**time_depth), holds it, and `retime.resample` writes the frames of
+             `plan.span(s, c, last)` from it: a time belongs to exactly one chunk, so the overlap frame is written
+             once.  A clip that ends on a chunk's edge sends one more chunk of no intervals for its last frame.
+
 Memory is bounded by the chunk, never by the clip (C = chunk_frames, F = factor, one frame of the input layout):
   host pinned    3 x (C + 2) input frames + 2 x (C x F + 1) output frames
   device         2 x (C + 2) input frames + one chunk's levels + the previous chunk's result (C x F + 1 frames of
                  the output layout; at factor 2 the levels are one result, at factor F about 2 x (C x F + 1) frames)
+With `fps=` (source / target rate = p / q, G = 2**time_depth) F is G in the levels, a chunk's result is its
+R = ceil(C x q / p) + 1 resampled frames, and the device holds them beside the grid:
+  host pinned    3 x (C + 2) input frames + 2 x R output frames
+  device         2 x (C + 2) input frames + one chunk's levels (about 2 x (C x G + 1) frames) + 2 x R output frames
 """
 from __future__ import annotations
 
@@ -34,6 +43,7 @@ import numpy as np
 import torch
 
 from . import colour, imageio_lite, scene
+from . import retime as _retime
 from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
                         interpolate_sequence_p10, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10)
 
@@ -47,13 +57,26 @@ def check_chunk_frames(chunk_frames) -> int:
     return int(chunk_frames)
 
 
-def _check_common(factor, batch, chunk_frames, scene_cut):
+def _check_common(factor, batch, chunk_frames, scene_cut, whole_ok=False):
+    """whole_ok: chunk_frames None (the whole clip as one chunk: `fps` runs only) passes as None."""
     thr = scene.check_threshold(scene_cut)
     if isinstance(factor, bool) or not isinstance(factor, numbers.Integral) or factor < 2 or factor & (factor - 1):
         raise ValueError("factor must be a power of two (the network has no time input)")
     if isinstance(batch, bool) or not isinstance(batch, numbers.Integral) or batch < 1:
         raise ValueError(f"batch must be a positive int, got {batch!r}")
-    return thr, check_chunk_frames(chunk_frames)
+    return thr, None if (whole_ok and chunk_frames is None) else check_chunk_frames(chunk_frames)
+
+
+def check_retime(fps, src_fps, time_depth, retime, factor):
+    """The checks of the frame-rate keywords that need no source: -> (fps Fraction or None, src_fps Fraction or None,
+    time_depth, retime).  With `fps`, `factor` must be left at 2."""
+    depth, mode = _retime.check_time_depth(time_depth), _retime.check_mode(retime)
+    if fps is None:
+        return None, None, depth, mode
+    if factor != 2:
+        raise ValueError(f"fps and factor are two ways to say how many frames to make: with fps={fps!r} leave factor "
+                         f"at 2 (got factor={factor!r}); time_depth sets the bisection depth")
+    return _retime.parse_fps(fps), None if src_fps is None else _retime.parse_fps(src_fps), depth, mode
 
 
 def _is_path(x) -> bool:
@@ -239,11 +262,15 @@ class _Stopped(Exception):
 
 
 @torch.no_grad()
-def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, thr, scene_log=None) -> int:
-    """Stream `reader` through `route` into `write(rows)`; returns the number of output frames."""
+def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, thr, scene_log=None, plan=None,
+         mode: str = "blend") -> int:
+    """Stream `reader` through `route` into `write(rows)`; returns the number of output frames.  plan: a `retime.Plan`
+    (then factor is its G): each chunk's grid is resampled to the plan's frames."""
     dev = next(model.parameters()).device
     C, look = chunk_frames, 1 if thr is not None else 0
     in_rows, out_rows = C + 1 + look, C * factor + 1
+    if plan is not None:
+        out_rows = -(-C * plan.q // plan.p) + 1
     in_slots = [torch.empty((in_rows, route.row), dtype=route.tdtype).pin_memory() for _ in range(R_IN)]
     out_slots = [torch.empty((out_rows, route.out_row), dtype=route.tdtype).pin_memory() for _ in range(R_OUT)]
     in_np = [s.numpy().view(route.ndtype) for s in in_slots]
@@ -270,7 +297,9 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
                     continue
                 if m == 0:
                     raise ValueError("no frames to interpolate")
-                if m > 1 or s == 0:   # the last chunk (a one-frame clip is one chunk without pairs)
+                # the last chunk (a one-frame clip is one chunk without pairs; with a plan, so is the last frame of a
+                # clip that ended on the previous chunk's edge)
+                if m > 1 or s == 0 or plan is not None:
                     filled.put((i, s, m, m - 1, True))
                 filled.put(None)
                 return
@@ -301,6 +330,10 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
     h2d, d2h = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
     d_in = [torch.empty((in_rows, route.row), dtype=route.tdtype, device=dev) for _ in range(2)]
     d_free = [None, None]   # event: the compute stream's last read of d_in[j]
+    # with a plan, the resampled frames of a chunk go into the device twin of its pinned output slot: every chunk's
+    # result has the same allocation, whatever its frame count, and the grid is released before the next chunk runs
+    d_out = None if plan is None else [torch.empty((out_rows, route.out_row), dtype=route.tdtype, device=dev)
+                                       for _ in range(R_OUT)]
     count = route.row       # samples per frame, as scene.detect_cuts counts them
     carried = None          # int64 [1]: the previous chunk's last interval sum
     total, j = 0, 0
@@ -309,7 +342,7 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
             item = fail.get(filled)
             if item is None:
                 break
-            i, s, m, c, _last = item
+            i, s, m, c, last = item
             # the output slot of chunk i - R_OUT: written out, and (R_OUT = 2) that chunk's result is back in the
             # allocator before this chunk allocates: the device holds this chunk's levels and the previous result
             o = fail.get(free_out)
@@ -335,11 +368,19 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
             _hold(flags, factor, out)
             d_free[j] = torch.cuda.Event()
             d_free[j].record(compute)
-            rows = out if s == 0 else out[1:]   # a later chunk's first frame is the previous chunk's last
+            if plan is None:
+                rows = out if s == 0 else out[1:]   # a later chunk's first frame is the previous chunk's last
+            else:
+                # (pinned slot o is free, so the D2H copy that last read d_out[o] has completed)
+                j0, nj = plan.span(s, c, last)
+                rows = _retime.resample(out, plan, s, j0, nj, bits=route.bits, flags=flags, mode=mode,
+                                        out=d_out[o][:nj])
+                out = None   # the grid is used on the compute stream alone: it may go back to the allocator now
             with torch.cuda.stream(d2h):
                 d2h.wait_stream(compute)
                 out_slots[o][:rows.shape[0]].copy_(rows, non_blocking=True)
-                out.record_stream(d2h)
+                if plan is None:   # `rows` is a view of this chunk's `out`, which is dropped while the copy may run;
+                    rows.record_stream(d2h)   # d_out[o] lives for the whole run and is guarded by the free_out queue
                 ev = torch.cuda.Event()
                 ev.record(d2h)
             done.put((o, rows.shape[0], ev))
@@ -367,6 +408,60 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
     return total
 
 
+@torch.no_grad()
+def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode: str, n_frames=None) -> int:
+    """The resident form of `_run` with a plan: the whole clip on the device, one grid, one resample.  n_frames: the
+    clip's frame count where it is known up front (a regular file): the clip is then read into one array; a stream of
+    unknown length is uploaded 64 frames at a time, so that the host never holds it twice."""
+    dev = next(model.parameters()).device
+
+    def upload(a):
+        return torch.from_numpy(a.view(np.int16) if route.bits == 10 else a).to(dev)
+    if n_frames is not None:
+        frames = np.empty((n_frames, route.row), dtype=route.ndtype)
+        if reader.read_into(frames, n_frames) != n_frames:
+            raise ValueError("the clip has fewer frames than were counted")
+        d = upload(frames)
+        del frames
+    else:
+        parts = []
+        while True:
+            buf = np.empty((64, route.row), dtype=route.ndtype)
+            k = reader.read_into(buf, 64)
+            if k:
+                parts.append(upload(buf[:k]))
+            if k < 64:
+                break
+        if not parts:
+            raise ValueError("no frames to interpolate")
+        d = parts[0] if len(parts) == 1 else torch.cat(parts)
+        del parts
+    flags = None
+    if thr is not None and d.shape[0] > 1:
+        flags = scene.detect_cuts([d], thr, route.bits)[1]
+    grid = route.run(d, factor)
+    _hold(flags, factor, grid)
+    n = plan.n_out(d.shape[0])
+    rows = _retime.resample(grid, plan, 0, 0, n, bits=route.bits, flags=flags, mode=mode)
+    write(rows.cpu().numpy().view(route.ndtype))
+    return n
+
+
+def _plan_of(fps, src_fps, header_fps, depth):
+    """The plan of a checked `fps` (None: no plan) against `src_fps`, or the stream header's rate when that is None."""
+    if fps is None:
+        return None
+    if src_fps is None:
+        if header_fps is None:
+            raise ValueError("a .npy stack carries no frame rate: pass src_fps with fps")
+        try:
+            src_fps = _retime.parse_fps(tuple(int(v) for v in header_fps))
+        except ValueError:
+            raise ValueError(f"the Y4M header's frame rate F{header_fps[0]}:{header_fps[1]} is not a rate: pass "
+                             "src_fps") from None
+    return _retime.plan(src_fps, fps, depth)
+
+
 def _open_sink(dst):
     """-> (file object, finish(ok)).  A path is written to `<dst>.part` and renamed on success, removed on error; a
     file object (a pipe) keeps what was written before an error."""
@@ -386,14 +481,20 @@ def _open_sink(dst):
 
 def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
                            matrix: str = "bt709", siting: str | None = None, scene_cut: float | None = None,
-                           scene_log: list | None = None) -> int:
+                           scene_log: list | None = None, fps=None, src_fps=None, time_depth: int = 2,
+                           retime: str = "blend") -> int:
     """Y4M in (a path or a readable binary file: a pipe, `sys.stdin.buffer`) -> Y4M out (a path or a writable binary
     file), or a `.npy` path of the luma frames (grayscale network; the input must then be a regular file, whose frame
     count a first pass reads).  Every route, header, refusal and result is that of `FrameInterpolator.interpolate_video`
     on the same arguments, byte for byte, for any `chunk_frames` >= 1.  Returns the output frame count.  Every argument
     is checked before anything is pinned, before any GPU work and before the output exists.  scene_log: a list that
-    receives (scores float64, flags uint8) host arrays of each chunk's intervals (tests; costs a synchronise)."""
-    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
+    receives (scores float64, flags uint8) host arrays of each chunk's intervals (tests; costs a synchronise).
+    fps / src_fps / time_depth / retime: frame-rate conversion (retime.py): the output has `fps` frames per second,
+    resampled from a 2**time_depth bisection; src_fps overrides the header's rate; factor stays 2.  With fps,
+    chunk_frames may be None: the whole clip is one chunk, resident on the device (`interpolate_video` without
+    chunk_frames)."""
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut, whole_ok=fps is not None)
+    fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     npy_out = isinstance(dst, (str, os.PathLike)) and os.fspath(dst).lower().endswith(".npy")
     if npy_out:
         if not _is_path(src) or not stat.S_ISREG(os.stat(src).st_mode):
@@ -403,14 +504,25 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     try:
         route = _y4m_route(model, reader.header, npy_out, batch, matrix, siting)
         hdr = reader.header
-        fps = (hdr["fps"][0] * factor, hdr["fps"][1])
+        plan = _plan_of(fps, src_fps, hdr["fps"], depth)
+        if plan is None:
+            fps = (hdr["fps"][0] * factor, hdr["fps"][1])
+        else:
+            factor, fps = plan.G, (plan.fps.numerator, plan.fps.denominator)
+
+        def run(write):
+            if C is None:
+                count = (imageio_lite.y4m_frame_count(src)
+                         if _is_path(src) and stat.S_ISREG(os.stat(src).st_mode) else None)
+                return _run_whole(model, route, reader, write, factor, thr, plan, mode, count)
+            return _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode)
         if npy_out:
             n = imageio_lite.y4m_frame_count(src)
-            shape = ((n - 1) * factor + 1, hdr["height"], hdr["width"])
+            shape = ((n - 1) * factor + 1 if plan is None else plan.n_out(n), hdr["height"], hdr["width"])
             sink = _NpyWriter(os.fspath(dst), np.uint16 if route.bits == 10 else np.uint8, shape)
             ok = False
             try:
-                total = _run(model, route, reader, sink.write, factor, C, thr, scene_log)
+                total = run(sink.write)
                 ok = True
             finally:
                 sink.close(ok)
@@ -421,7 +533,7 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
             w = imageio_lite.Y4MWriter(f, hdr["width"], hdr["height"], fps, hdr["colourspace"],
                                        hdr["colour_range"] if (route.bits == 10 or model.frame_channels == 3) else None,
                                        bits=route.bits)
-            total = _run(model, route, reader, w.write, factor, C, thr, scene_log)
+            total = run(w.write)
             ok = True
         finally:
             finish(ok)
@@ -431,11 +543,17 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
 
 
 def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
-                           scene_cut: float | None = None, scene_log: list | None = None) -> int:
+                           scene_cut: float | None = None, scene_log: list | None = None, fps=None, src_fps=None,
+                           time_depth: int = 2, retime: str = "blend") -> int:
     """`.npy` stack in (uint8 [N,H,W] or [N,H,W,C], read through `np.load(mmap_mode="r")`) -> `.npy` out (written
     through `np.lib.format.open_memmap`): byte for byte the file `interpolate_video` saves.  Returns the output frame
-    count."""
-    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
+    count.  fps / src_fps / time_depth / retime, and chunk_frames None with fps: as for `interpolate_y4m_stream`; a
+    .npy stack carries no rate, so `fps` needs `src_fps`."""
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut, whole_ok=fps is not None)
+    fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
+    plan = _plan_of(fps, src_fps, None, depth)
+    if plan is not None:
+        factor = plan.G
     if not _is_path(dst):
         raise ValueError("a .npy output is a path")
     dst = os.fspath(dst)
@@ -447,14 +565,18 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     if mm.shape[0] < 1:
         raise ValueError("no frames to interpolate")
     route = _npy_route(model, mm.shape[1:], batch)
-    sink = _NpyWriter(dst, np.uint8, ((mm.shape[0] - 1) * factor + 1,) + mm.shape[1:])
+    n_out = (mm.shape[0] - 1) * factor + 1 if plan is None else plan.n_out(mm.shape[0])
+    sink = _NpyWriter(dst, np.uint8, (n_out,) + mm.shape[1:])
     ok = False
     try:
-        total = _run(model, route, _NpyRows(mm), sink.write, factor, C, thr, scene_log)
+        if C is None:
+            total = _run_whole(model, route, _NpyRows(mm), sink.write, factor, thr, plan, mode, mm.shape[0])
+        else:
+            total = _run(model, route, _NpyRows(mm), sink.write, factor, C, thr, scene_log, plan, mode)
         ok = True
     finally:
         sink.close(ok)
     return total
 
 
-__all__ = ["check_chunk_frames", "interpolate_y4m_stream", "interpolate_npy_stream"]
+__all__ = ["check_chunk_frames", "check_retime", "interpolate_y4m_stream", "interpolate_npy_stream"]

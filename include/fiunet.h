@@ -25,7 +25,8 @@ extern "C" {
                                   6: YUV 4:2:0 colour video (fiunet_yuv420_to_rgb_u8, fiunet_rgb_to_yuv420_u8, fiunet_forward_yuv420);
                                   7: 10-bit video (fiunet_forward_p10, fiunet_forward_yuv420p10 and their pieces; FIUNET_YUV_BT2020);
                                   8: precision FIUNET_FP16; v8 also: scene-cut entry points (fiunet_pair_sad_u8,
-                                     fiunet_pair_sad_p10, fiunet_scene_cuts, fiunet_hold_cut_frames), backwards-compatible */
+                                     fiunet_pair_sad_p10, fiunet_scene_cuts, fiunet_hold_cut_frames) and frame-rate conversion
+                                     (fiunet_retime_u8, fiunet_retime_p10), backwards-compatible */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -274,6 +275,25 @@ int fiunet_scene_cuts(const int64_t* sums, int n_frames, size_t count, int bits,
  * read on the device.  factor: a power of two in [2, 2^20]. */
 int fiunet_hold_cut_frames(uint8_t* video, int n_frames, size_t frame_bytes, int factor, const uint8_t* flags,
                            void* stream);
+
+/* Frame-rate conversion (ABI v8, added without a version bump: nothing existing changed).  `grid` holds
+ * the frames of a `depth`-level bisection, G = 2^depth: [(n_intervals << depth) + 1][frame_samples], row k*G + m at
+ * clip time first_interval + k + m / G.  With source rate / target rate = p / q reduced (0 < p < q <= 2^20), output
+ * row k is clip output frame j = j0 + k at time j * p / q: i = j*p / q, r = j*p % q, lo = r*G / q, wn = r*G % q, and
+ *   mode 0 (blend)    out = (A * (q - wn) + B * wn + q / 2) / q per sample in integers, A = the grid row at time
+ *                     i + lo / G, B the row after it; 10-bit words above 1023 read as 1023; wn == 0: a byte copy of A
+ *   mode 1 (nearest)  a byte copy of B if 2 * wn > q, else of A
+ *   cut               flags != NULL, flags[i - first_interval] != 0 and r != 0: a byte copy of the grid row at time i
+ * flags: [n_intervals] on the device (read there), or NULL.  out: [n_out][frame_samples].  Device pointers;
+ * asynchronous on `stream`; no allocation, no synchronisation; n_out == 0 is a no-op.  FIUNET_ERR_INVALID_ARG, checked
+ * on the host before any launch: NULL grid / out, depth outside 1..4, p == 0, p >= q, q > 2^20, a mode other than 0 /
+ * 1, a negative count, or a first / last requested frame whose rows fall outside the grid. */
+int fiunet_retime_u8(const uint8_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
+                     uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint8_t* out,
+                     void* stream);
+int fiunet_retime_p10(const uint16_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
+                      uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint16_t* out,
+                      void* stream);
 
 /* Replaces preprocess_image's arithmetic (model/inference.py:31-35): out = 2*(in/255) - 1. */
 int fiunet_preprocess_u8(const uint8_t* in, float* out, size_t n, void* stream);
