@@ -44,7 +44,22 @@ SYMBOLS = (
     "fiunet_forward_yuv420p10",
     "fiunet_pair_sad_u8", "fiunet_pair_sad_p10", "fiunet_scene_cuts", "fiunet_hold_cut_frames",
     "fiunet_retime_u8", "fiunet_retime_p10",
+    "fiunet_nv12_to_rgb_u8", "fiunet_rgb_to_nv12_u8", "fiunet_workspace_bytes_nv12", "fiunet_forward_nv12",
+    "fiunet_p010_to_rgb_p10", "fiunet_rgb_p10_to_p010", "fiunet_workspace_bytes_p010", "fiunet_forward_p010",
 )
+
+
+class SurfaceLayout(ctypes.Structure):
+    """include/fiunet.h: fiunet_surface_layout (NV12 / P010 surfaces; every field in samples, 0 = tight)."""
+    _fields_ = [("luma_pitch", ctypes.c_size_t), ("chroma_offset", ctypes.c_size_t),
+                ("chroma_pitch", ctypes.c_size_t), ("frame_stride", ctypes.c_size_t)]
+
+
+def _surface(layout, frame_stride: int):
+    """A resolved colour.SurfaceLayout (or None: tight) with the frames `frame_stride` samples apart -> the C struct."""
+    if layout is None:
+        return ctypes.byref(SurfaceLayout(0, 0, 0, frame_stride))
+    return ctypes.byref(SurfaceLayout(layout.luma_pitch, layout.chroma_offset, layout.chroma_pitch, frame_stride))
 
 _lib = None
 
@@ -136,6 +151,16 @@ def lib() -> ctypes.CDLL:
     u64, u32 = ctypes.c_uint64, ctypes.c_uint32
     L.fiunet_retime_u8.argtypes = [vp, ci, sz, ci, u64, u64, ci, u32, u32, ci, vp, vp, vp]
     L.fiunet_retime_p10.argtypes = [vp, ci, sz, ci, u64, u64, ci, u32, u32, ci, vp, vp, vp]
+    L.fiunet_nv12_to_rgb_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
+    L.fiunet_rgb_to_nv12_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
+    L.fiunet_p010_to_rgb_p10.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
+    L.fiunet_rgb_p10_to_p010.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
+    L.fiunet_workspace_bytes_nv12.argtypes = [vp, ci, ci, ci, ci]
+    L.fiunet_workspace_bytes_nv12.restype = sz
+    L.fiunet_workspace_bytes_p010.argtypes = [vp, ci, ci, ci, ci]
+    L.fiunet_workspace_bytes_p010.restype = sz
+    L.fiunet_forward_nv12.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cu, ci, vp, sz, vp]
+    L.fiunet_forward_p010.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cu, ci, vp, sz, vp]
     L.fiunet_debug_read_activation.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz,
                                                ctypes.POINTER(ci), vp]
     L.fiunet_metrics_workspace_bytes.argtypes = [ci, ci, ci]
@@ -323,6 +348,18 @@ class Context:
                                              colour, precision, workspace.data_ptr(), workspace.numel(), s),
               "fiunet_forward_yuv420p10")
 
+    def forward_surface(self, f1, f2, layout, out, out_layout, h, w, colour, precision, workspace, bits, stream=None):
+        """fiunet_forward_nv12 (bits 8: uint8) / fiunet_forward_p010 (bits 10: uint16 words) on [B, frame_stride] rows:
+        f1, f2 contiguous in `layout`; `out` in `out_layout`, its rows contiguous and possibly further apart.  The
+        layouts are resolved colour.SurfaceLayout tuples or None (tight); the workspace is the 4:2:0 entry point's."""
+        b = f1.shape[0]
+        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        st = out.stride(0) if b > 1 else out.shape[1]
+        fn, name = ((lib().fiunet_forward_p010, "fiunet_forward_p010") if bits == 10 else
+                    (lib().fiunet_forward_nv12, "fiunet_forward_nv12"))
+        check(fn(self._h, f1.data_ptr(), f2.data_ptr(), _surface(layout, f1.shape[1]), out.data_ptr(),
+                 _surface(out_layout, st), b, h, w, colour, precision, workspace.data_ptr(), workspace.numel(), s), name)
+
     def profile_enable(self, on: bool):
         check(lib().fiunet_profile_enable(self._h, 1 if on else 0), "fiunet_profile_enable")
 
@@ -424,6 +461,28 @@ def rgb_p10_to_yuv420p10(rgb: "torch.Tensor", out: "torch.Tensor", colour: int) 
     s = torch.cuda.current_stream(rgb.device).cuda_stream
     check(lib().fiunet_rgb_p10_to_yuv420p10(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s),
           "fiunet_rgb_p10_to_yuv420p10")
+
+
+def surface_to_rgb(frames: "torch.Tensor", layout, out: "torch.Tensor", h: int, w: int, colour: int, bits: int) -> None:
+    """fiunet_nv12_to_rgb_u8 (bits 8) / fiunet_p010_to_rgb_p10 (bits 10): [B, frame_stride] surfaces (rows contiguous,
+    any row stride) in the resolved `layout` (None: tight) -> planar RGB [B, 3, h, w]."""
+    b = frames.shape[0]
+    st = frames.stride(0) if b > 1 else frames.shape[1]
+    s = torch.cuda.current_stream(frames.device).cuda_stream
+    fn, name = ((lib().fiunet_p010_to_rgb_p10, "fiunet_p010_to_rgb_p10") if bits == 10 else
+                (lib().fiunet_nv12_to_rgb_u8, "fiunet_nv12_to_rgb_u8"))
+    check(fn(frames.data_ptr(), _surface(layout, st), out.data_ptr(), b, h, w, colour, s), name)
+
+
+def rgb_to_surface(rgb: "torch.Tensor", out: "torch.Tensor", layout, colour: int, bits: int) -> None:
+    """fiunet_rgb_to_nv12_u8 (bits 8) / fiunet_rgb_p10_to_p010 (bits 10): planar RGB [B, 3, h, w] contiguous -> [B,
+    frame_stride] surfaces (rows contiguous, any row stride) in the resolved `layout` (None: tight)."""
+    b, _, h, w = rgb.shape
+    st = out.stride(0) if b > 1 else out.shape[1]
+    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    fn, name = ((lib().fiunet_rgb_p10_to_p010, "fiunet_rgb_p10_to_p010") if bits == 10 else
+                (lib().fiunet_rgb_to_nv12_u8, "fiunet_rgb_to_nv12_u8"))
+    check(fn(rgb.data_ptr(), out.data_ptr(), _surface(layout, st), b, h, w, colour, s), name)
 
 
 def pair_sad(frames: "torch.Tensor", sums: "torch.Tensor", bits: int) -> None:

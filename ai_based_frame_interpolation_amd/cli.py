@@ -1,8 +1,8 @@
 """Command line: `python -m ai_based_frame_interpolation_amd.cli video --input IN --output OUT [--factor 2] ...`
 
 The reference's `main.py video` flags (--input, --output, --factor, --model, --device), plus --precision, --matrix,
---siting, --scene-cut, --batch, --chunk-frames and the frame-rate conversion's --fps, --src-fps, --time-depth and
---retime.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
+--siting, --scene-cut, --batch, --chunk-frames, the frame-rate conversion's --fps, --src-fps, --time-depth and
+--retime, and --raw / --size for headerless NV12 video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
 the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 
     ffmpeg -i in.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - \\
@@ -11,7 +11,14 @@ the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 With `--fps 60000/1001` (a fraction or an integer, never a decimal) the output has that frame rate instead of
 --factor times the input's (retime.py): 23.976 -> 59.94, 24 -> 60, 25 -> 60, 50 -> 120.
 
-Standard output then carries nothing but Y4M: the model-loading lines go to standard error.  The network (grayscale
+With `--raw nv12 --size 1920x1080 --src-fps 24` input and output are headerless tight NV12 frames, the layout hardware
+decoders and encoders use, converted on the device without a repack:
+
+    ffmpeg -i in.mkv -f rawvideo -pix_fmt nv12 - | python -m ai_based_frame_interpolation_amd.cli video --input - \\
+        --output - --raw nv12 --size 1920x1080 --src-fps 24 --model rgb.pth | \\
+        ffmpeg -f rawvideo -pix_fmt nv12 -s 1920x1080 -r 48 -i - out.mkv
+
+Standard output then carries nothing but video: the model-loading lines go to standard error.  The network (grayscale
 2->1 or RGB 6->3) is read from the checkpoint.
 """
 from __future__ import annotations
@@ -53,6 +60,14 @@ def _fps(v: str):
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _size(v: str):
+    """"WxH" -> (width, height)"""
+    parts = v.lower().split("x")
+    if len(parts) != 2 or not all(p.isdigit() and int(p) > 0 for p in parts):
+        raise argparse.ArgumentTypeError(f"expected WIDTHxHEIGHT such as 1920x1080, got {v!r}")
+    return int(parts[0]), int(parts[1])
+
+
 def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m ai_based_frame_interpolation_amd.cli",
                                  description="AI frame interpolation on the MI355X")
@@ -76,13 +91,21 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--time-depth", type=int, default=2, choices=(1, 2, 3, 4), help="Bisection levels under --fps")
     v.add_argument("--retime", default="blend", choices=retime.MODES,
                    help="How --fps picks between the two bisection frames around an output time")
+    v.add_argument("--raw", default=None, choices=("nv12",),
+                   help="Headerless raw video in and out (tight NV12 frames); needs --size and --src-fps")
+    v.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
     return ap
 
 
 def parse_args(argv=None) -> argparse.Namespace:
-    a = parser().parse_args(argv)
+    ap = parser()
+    a = ap.parse_args(argv)
     if a.chunk_frames is None:
         a.chunk_frames = 4 * a.batch
+    if a.raw is not None and (a.size is None or a.src_fps is None):
+        ap.error("--raw needs --size WIDTHxHEIGHT and --src-fps (raw video has no header)")
+    if a.raw is None and a.size is not None:
+        ap.error("--size describes --raw video")
     return a
 
 
@@ -99,7 +122,8 @@ def run_video(a: argparse.Namespace) -> int:
     dst = sys.stdout.buffer if a.output == "-" else a.output
     n = fi.interpolate_video(src, dst, a.factor, matrix=a.matrix, siting=a.siting, scene_cut=a.scene_cut,
                              chunk_frames=a.chunk_frames, fps=a.fps, src_fps=a.src_fps, time_depth=a.time_depth,
-                             retime=a.retime)
+                             retime=a.retime, raw=a.raw, width=a.size[0] if a.size else None,
+                             height=a.size[1] if a.size else None)
     print(f"wrote {n} frames", file=sys.stderr)
     return n
 

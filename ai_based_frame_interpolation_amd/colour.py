@@ -9,6 +9,12 @@ in HIP kernels (`fiunet_yuv420_to_rgb_u8`, `fiunet_rgb_to_yuv420_u8`); the netwo
 10-bit video (`C420p10` Y4M: every sample a 10-bit code in a little-endian 16-bit word) has the same layout in uint16
 samples: `yuv420p10_to_rgb` / `rgb_to_yuv420p10` and `FrameInterpolationUNet.forward_yuv420p10`.
 
+Decoder surfaces: a hardware decoder leaves semi-planar frames in device memory - NV12 at 8 bits (the
+Y plane, then one plane of interleaved U,V pairs), P010 at 10 (the same in 16-bit words, the code in the upper ten bits),
+rows a pitch apart.  `nv12_to_rgb` / `rgb_to_nv12`, `p010_to_rgb` / `rgb_to_p010` and
+`FrameInterpolationUNet.forward_nv12` / `forward_p010` are the conversions above on that layout (`SurfaceLayout`), with
+the same arithmetic bit for bit.
+
 Options (the keywords of every colour entry point):
   siting        "jpeg" (Y4M C420jpeg, C420 or no tag: chroma centred in its 2x2 luma block) or "mpeg2" (C420mpeg2:
                 co-sited with the even luma column, centred vertically)
@@ -17,6 +23,9 @@ Options (the keywords of every colour entry point):
   colour_range  "limited" (Y 16-235, C 16-240; the default, and what a Y4M header without XCOLORRANGE means) or "full"
 """
 from __future__ import annotations
+
+import numbers
+from typing import NamedTuple
 
 import torch
 
@@ -54,6 +63,40 @@ def yuv420p10_frame_samples(height: int, width: int) -> int:
     return i420_frame_bytes(height, width)
 
 
+class SurfaceLayout(NamedTuple):
+    """Where the samples of an NV12 / P010 frame lie, every field in samples (bytes at 8 bits, 16-bit words at 10); 0 =
+    the tight value.  A frame is H luma rows `luma_pitch` apart, then, `chroma_offset` samples after the frame's base,
+    ceil(H/2) chroma rows `chroma_pitch` apart, each ceil(W/2) pairs U0 V0 U1 V1 ...; frames `frame_stride` apart.
+    Tight: luma_pitch W, chroma_offset H*W, chroma_pitch 2*ceil(W/2), frame_stride `i420_frame_bytes(H, W)`."""
+    luma_pitch: int = 0
+    chroma_offset: int = 0
+    chroma_pitch: int = 0
+    frame_stride: int = 0
+
+
+def resolve_layout(layout: SurfaceLayout | None, height: int, width: int) -> SurfaceLayout:
+    """-> `layout` with every 0 replaced by its tight value (None: the tight layout); ValueError where it cannot hold
+    a height x width frame (the rules of include/fiunet.h, fiunet_surface_layout)."""
+    h, w = int(height), int(width)
+    if h < 1 or w < 1:
+        raise ValueError(f"bad frame size {height!r}x{width!r}")
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+    vals = tuple(layout) if layout is not None else (0, 0, 0, 0)
+    if len(vals) != 4 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0 or v > 1 << 40 for v in vals):
+        raise ValueError(f"layout must be a SurfaceLayout of four ints in [0, 2^40] (samples), got {layout!r}")
+    lp, co, cp, fs = (int(v) or t for v, t in zip(vals, (w, h * w, 2 * wc, i420_frame_bytes(h, w))))
+    if lp < w:
+        raise ValueError(f"layout: luma_pitch {lp} < width {w}")
+    if cp < 2 * wc:
+        raise ValueError(f"layout: chroma_pitch {cp} < {2 * wc}, the {wc} U,V pairs of a row")
+    if co < (h - 1) * lp + w:
+        raise ValueError(f"layout: chroma_offset {co} lies inside the luma plane ({(h - 1) * lp + w} samples)")
+    if fs < co + (hc - 1) * cp + 2 * wc:
+        raise ValueError(f"layout: frame_stride {fs} does not cover the chroma plane (it ends at "
+                         f"{co + (hc - 1) * cp + 2 * wc} samples)")
+    return SurfaceLayout(lp, co, cp, fs)
+
+
 def siting_of_y4m(colourspace: str) -> str:
     """Chroma siting of a Y4M `C` tag; ValueError naming the tag for the layouts the RGB network does not read."""
     try:
@@ -63,10 +106,14 @@ def siting_of_y4m(colourspace: str) -> str:
                          f"video tagged {', '.join('C' + t for t in Y4M_SITING)} or untagged") from None
 
 
-def _check_frames(frames: torch.Tensor, height: int, width: int, what: str, dtype=torch.uint8) -> None:
-    fb = i420_frame_bytes(height, width)
+def _check_frames(frames: torch.Tensor, height: int, width: int, what: str, dtype=torch.uint8,
+                  layout: SurfaceLayout | None = None) -> None:
+    """layout: a resolved SurfaceLayout: the frames are NV12 / P010 surfaces of layout.frame_stride samples."""
+    fb = i420_frame_bytes(height, width) if layout is None else layout.frame_stride
     if frames.dtype != dtype or frames.dim() != 2 or frames.shape[1] != fb:
         kind = "I420" if dtype == torch.uint8 else "4:2:0 10-bit"
+        if layout is not None:
+            kind = "NV12" if dtype == torch.uint8 else "P010"
         raise ValueError(f"{what} must be {str(dtype).split('.')[-1]} [B, {fb}] packed {kind} frames of "
                          f"{height}x{width}, got {frames.dtype} {tuple(frames.shape)}")
     if not frames.is_cuda:
@@ -152,3 +199,77 @@ def rgb_to_yuv420p10(rgb: torch.Tensor, *, siting: str = "jpeg", matrix: str = "
     with torch.cuda.device(rgb.device):
         _native.rgb_p10_to_yuv420p10(rgb, out, flags)
     return out
+
+
+def _surface_to_rgb(frames, height, width, siting, matrix, colour_range, out, layout, bits):
+    dtype = torch.uint16 if bits == 10 else torch.uint8
+    flags = colour_flags(siting, matrix, colour_range, bits=bits)
+    lay = resolve_layout(layout, height, width)
+    _check_frames(frames, height, width, "frames", dtype, lay)
+    shape = (frames.shape[0], 3, height, width)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=frames.device)
+    elif out.dtype != dtype or tuple(out.shape) != shape or out.device != frames.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {str(dtype).split('.')[-1]} {shape} tensor on {frames.device}")
+    with torch.cuda.device(frames.device):
+        _native.surface_to_rgb(frames, lay, out, height, width, flags, bits)
+    return out
+
+
+def _rgb_to_surface(rgb, siting, matrix, colour_range, out, layout, bits):
+    dtype = torch.uint16 if bits == 10 else torch.uint8
+    flags = colour_flags(siting, matrix, colour_range, bits=bits)
+    if rgb.dtype != dtype or rgb.dim() != 4 or rgb.shape[1] != 3:
+        raise ValueError(f"rgb must be {str(dtype).split('.')[-1]} [B, 3, H, W], got {rgb.dtype} {tuple(rgb.shape)}")
+    if not rgb.is_cuda:
+        raise RuntimeError("rgb must be on the GPU: there is no CPU path in this package")
+    b, _, h, w = rgb.shape
+    lay = resolve_layout(layout, h, w)
+    if not rgb.is_contiguous():
+        raise ValueError("rgb must be contiguous")
+    if out is None:
+        # (a pitched surface has samples no frame covers: they are never written, so a new one starts as zeros)
+        out = (torch.empty if lay == resolve_layout(None, h, w) else torch.zeros)(
+            (b, lay.frame_stride), dtype=dtype, device=rgb.device)
+    elif out.device != rgb.device or out.shape[0] != b:
+        raise ValueError(f"out must hold {b} frames on {rgb.device}")
+    _check_frames(out, h, w, "out", dtype, lay)
+    with torch.cuda.device(rgb.device):
+        _native.rgb_to_surface(rgb, out, lay, flags, bits)
+    return out
+
+
+@torch.no_grad()
+def nv12_to_rgb(frames: torch.Tensor, height: int, width: int, *, siting: str = "mpeg2", matrix: str = "bt709",
+                colour_range: str = "limited", out: torch.Tensor | None = None,
+                layout: SurfaceLayout | None = None) -> torch.Tensor:
+    """uint8 [B, frame_stride] NV12 surfaces on the GPU ([B, F] when tight: layout None) -> uint8 planar RGB
+    [B, 3, H, W] (`fiunet_nv12_to_rgb_u8`): `yuv420_to_rgb` on the semi-planar layout, bit for bit.  siting defaults
+    to "mpeg2", what decoders produce."""
+    return _surface_to_rgb(frames, int(height), int(width), siting, matrix, colour_range, out, layout, 8)
+
+
+@torch.no_grad()
+def rgb_to_nv12(rgb: torch.Tensor, *, siting: str = "mpeg2", matrix: str = "bt709", colour_range: str = "limited",
+                out: torch.Tensor | None = None, layout: SurfaceLayout | None = None) -> torch.Tensor:
+    """uint8 planar RGB [B, 3, H, W] on the GPU -> uint8 [B, frame_stride] NV12 surfaces (`fiunet_rgb_to_nv12_u8`).
+    Samples outside the used columns and between the planes and frames are left untouched (zero in a surface made
+    here).  `out` may be a view whose frames lie further apart than frame_stride."""
+    return _rgb_to_surface(rgb, siting, matrix, colour_range, out, layout, 8)
+
+
+@torch.no_grad()
+def p010_to_rgb(frames: torch.Tensor, height: int, width: int, *, siting: str = "mpeg2", matrix: str = "bt709",
+                colour_range: str = "limited", out: torch.Tensor | None = None,
+                layout: SurfaceLayout | None = None) -> torch.Tensor:
+    """uint16 [B, frame_stride] P010 surfaces on the GPU (a word is code << 6; the low six bits are ignored) -> uint16
+    planar RGB [B, 3, H, W] of 10-bit codes (`fiunet_p010_to_rgb_p10`).  matrix also takes "bt2020"."""
+    return _surface_to_rgb(frames, int(height), int(width), siting, matrix, colour_range, out, layout, 10)
+
+
+@torch.no_grad()
+def rgb_to_p010(rgb: torch.Tensor, *, siting: str = "mpeg2", matrix: str = "bt709", colour_range: str = "limited",
+                out: torch.Tensor | None = None, layout: SurfaceLayout | None = None) -> torch.Tensor:
+    """uint16 planar RGB [B, 3, H, W] of 10-bit codes on the GPU -> uint16 [B, frame_stride] P010 surfaces, every word
+    code << 6 with the low six bits zero (`fiunet_rgb_p10_to_p010`).  `out` / `layout`: as for `rgb_to_nv12`."""
+    return _rgb_to_surface(rgb, siting, matrix, colour_range, out, layout, 10)

@@ -48,6 +48,17 @@
 // (encode), so a wave reads and writes 256 contiguous samples of every luma / RGB row; with W % 4 == 0 and aligned
 // bases (VEC) those are single 4-sample accesses (4 bytes at 8 bits, 8 bytes at 10), otherwise samples with the edge
 // clamped.  Chroma is read / written per sample (half the columns, one quarter of the samples).
+//
+// Semi-planar surfaces (NV12 at 8 bits, P010 at 10: what a hardware decoder returns) go through the same
+// two bodies with the layout as a template parameter (NV): the arithmetic above is untouched, only where a sample lives
+// changes.  A frame is H luma rows `luma_pitch` samples apart, then, `chroma_offset` samples after the frame's base,
+// ceil(H/2) chroma rows `chroma_pitch` apart, each ceil(W/2) pairs U0 V0 U1 V1 ...; frames `frame_stride` apart
+// (ColourSurface, every field in samples).  A P010 word is code << 6: read as word >> 6 (the low six bits are ignored),
+// written with the low six bits zero.  The chroma pairs 2t and 2t+1 a thread owns are adjacent, so with VEC (W, every
+// pitch, offset and stride a multiple of 4 samples, bases aligned) they are one 4-sample access - a load in the decode,
+// a store in the encode, where I420 takes four scalar accesses - and the decode's two neighbour pairs one 2-sample
+// load each; otherwise every access is per sample.  Samples outside the W / 2 ceil(W/2) used columns and between the
+// planes are never read and never written.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,6 +119,7 @@ template <>
 struct ColourSample<uint8_t> {
     static constexpr int kMax = 255, kCentre = 128;
     using Vec4 = uchar4;
+    using Vec2 = uchar2;
     __device__ static __forceinline__ int read(uint8_t v) { return v; }
     __device__ static __forceinline__ uint8_t clamp(int v) { return (uint8_t)min(max(v, 0), 255); }
     __device__ static __forceinline__ Vec4 make(uint8_t a, uint8_t b, uint8_t c, uint8_t d) { return make_uchar4(a, b, c, d); }
@@ -116,6 +128,7 @@ template <>
 struct ColourSample<uint16_t> {
     static constexpr int kMax = 1023, kCentre = 512;
     using Vec4 = ushort4;
+    using Vec2 = ushort2;
     __device__ static __forceinline__ int read(uint16_t v) { return min((int)v, 1023); }
     __device__ static __forceinline__ uint16_t clamp(int v) { return (uint16_t)min(max(v, 0), 1023); }
     __device__ static __forceinline__ Vec4 make(uint16_t a, uint16_t b, uint16_t c, uint16_t d)
@@ -124,40 +137,80 @@ struct ColourSample<uint16_t> {
     }
 };
 
+// A semi-planar surface, every field in samples and resolved by the caller (no zeros): see the head of this file.
+struct ColourSurface {
+    size_t luma_pitch, chroma_offset, chroma_pitch, frame_stride;
+};
+
+// How a stored YUV word holds its code.  Planar frames (NV = false): the code itself (ColourSample).  Semi-planar
+// surfaces: the same at 8 bits (NV12); at 10 bits (P010) the code sits in the upper ten bits of the word.
+template <typename T, bool NV>
+struct ColourWord {
+    static constexpr int kShift = (NV && sizeof(T) == 2) ? 6 : 0;
+    __device__ static __forceinline__ int read(T v) { return kShift ? (int)(v >> kShift) : ColourSample<T>::read(v); }
+    __device__ static __forceinline__ T store(int v) { return (T)(ColourSample<T>::clamp(v) << kShift); }
+};
+
 constexpr int kColourBlock = 128;   // threads per workgroup; each covers 4 luma columns
 
-// grid = (ceil(ceil(W/4) / 128), H, B); strides and offsets in samples
-template <typename T, bool VEC>
-__global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const T* __restrict__ in, size_t in_stride,
-                                                                     T* __restrict__ out, int H, int W, ColourCoef k)
+// The decode of one thread.  NV = false: packed I420 frames sf.frame_stride apart (the other fields unused); NV = true:
+// the semi-planar surface sf.  Strides and offsets in samples.
+template <typename T, bool VEC, bool NV>
+__device__ __forceinline__ void colour_decode(const T* __restrict__ in, const ColourSurface& sf, T* __restrict__ out,
+                                              int H, int W, const ColourCoef& k)
 {
     using S = ColourSample<T>;
+    using Y = ColourWord<T, NV>;
     using Vec4 = typename S::Vec4;
+    using Vec2 = typename S::Vec2;
     const int t = blockIdx.x * kColourBlock + threadIdx.x, x0 = 4 * t, y = blockIdx.y;
     if (x0 >= W) return;
     const int Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
     const size_t plane = (size_t)H * W;
-    const T* fy = in + (size_t)blockIdx.z * in_stride;
-    const T* fu = fy + plane;
-    const T* fv = fu + (size_t)Hc * Wc;
+    const T* fy = in + (size_t)blockIdx.z * sf.frame_stride;
     // chroma rows: the nearest (weight 3) and the next-nearest (weight 1), both sitings
     const int i0 = y >> 1, i1 = min(max((y & 1) ? i0 + 1 : i0 - 1, 0), Hc - 1);
     // chroma columns 2t-1 .. 2t+2 (clamped) cover every neighbour of luma columns 4t .. 4t+3
     int u4[4], v4[4];
+    if (NV) {
+        const T* c0 = fy + sf.chroma_offset + (size_t)i0 * sf.chroma_pitch;
+        const T* c1 = fy + sf.chroma_offset + (size_t)i1 * sf.chroma_pitch;
+        if (VEC) {
+            // W % 4 == 0: pairs 2t and 2t+1 exist and lie at samples 4t .. 4t+3 of the row; the neighbours are one pair each
+            const int jl = max(2 * t - 1, 0), jr = min(2 * t + 2, Wc - 1);
+            const Vec4 m0 = *reinterpret_cast<const Vec4*>(c0 + 4 * t), m1 = *reinterpret_cast<const Vec4*>(c1 + 4 * t);
+            const Vec2 l0 = *reinterpret_cast<const Vec2*>(c0 + 2 * jl), l1 = *reinterpret_cast<const Vec2*>(c1 + 2 * jl);
+            const Vec2 r0 = *reinterpret_cast<const Vec2*>(c0 + 2 * jr), r1 = *reinterpret_cast<const Vec2*>(c1 + 2 * jr);
+            u4[0] = 3 * Y::read(l0.x) + Y::read(l1.x); v4[0] = 3 * Y::read(l0.y) + Y::read(l1.y);
+            u4[1] = 3 * Y::read(m0.x) + Y::read(m1.x); v4[1] = 3 * Y::read(m0.y) + Y::read(m1.y);
+            u4[2] = 3 * Y::read(m0.z) + Y::read(m1.z); v4[2] = 3 * Y::read(m0.w) + Y::read(m1.w);
+            u4[3] = 3 * Y::read(r0.x) + Y::read(r1.x); v4[3] = 3 * Y::read(r0.y) + Y::read(r1.y);
+        } else {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int j = min(max(2 * t - 1 + q, 0), Wc - 1);
-        u4[q] = 3 * S::read(fu[(size_t)i0 * Wc + j]) + S::read(fu[(size_t)i1 * Wc + j]);
-        v4[q] = 3 * S::read(fv[(size_t)i0 * Wc + j]) + S::read(fv[(size_t)i1 * Wc + j]);
+            for (int q = 0; q < 4; ++q) {
+                const int j = min(max(2 * t - 1 + q, 0), Wc - 1);
+                u4[q] = 3 * Y::read(c0[2 * j]) + Y::read(c1[2 * j]);
+                v4[q] = 3 * Y::read(c0[2 * j + 1]) + Y::read(c1[2 * j + 1]);
+            }
+        }
+    } else {
+        const T* fu = fy + plane;
+        const T* fv = fu + (size_t)Hc * Wc;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = min(max(2 * t - 1 + q, 0), Wc - 1);
+            u4[q] = 3 * S::read(fu[(size_t)i0 * Wc + j]) + S::read(fu[(size_t)i1 * Wc + j]);
+            v4[q] = 3 * S::read(fv[(size_t)i0 * Wc + j]) + S::read(fv[(size_t)i1 * Wc + j]);
+        }
     }
     int yv[4];
-    const T* row = fy + (size_t)y * W + x0;
+    const T* row = fy + (size_t)y * (NV ? sf.luma_pitch : (size_t)W) + x0;
     if (VEC) {
         const Vec4 p = *reinterpret_cast<const Vec4*>(row);
-        yv[0] = S::read(p.x); yv[1] = S::read(p.y); yv[2] = S::read(p.z); yv[3] = S::read(p.w);
+        yv[0] = Y::read(p.x); yv[1] = Y::read(p.y); yv[2] = Y::read(p.z); yv[3] = Y::read(p.w);
     } else {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) yv[c] = S::read(row[min(c, W - 1 - x0)]);
+        for (int c = 0; c < 4; ++c) yv[c] = Y::read(row[min(c, W - 1 - x0)]);
     }
     T r[4], g[4], b[4];
 #pragma unroll
@@ -196,13 +249,30 @@ __global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const T* __
     }
 }
 
-// grid = (ceil(ceil(W/4) / 128), ceil(H/2), B): a thread covers luma rows 2i, 2i+1 and columns 4t .. 4t+3, i.e.
-// chroma samples (i, 2t) and (i, 2t+1)
+// grid = (ceil(ceil(W/4) / 128), H, B); strides and offsets in samples
 template <typename T, bool VEC>
-__global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const T* __restrict__ in, T* __restrict__ out,
-                                                                     size_t out_stride, int H, int W, ColourCoef k)
+__global__ __launch_bounds__(kColourBlock) void yuv420_to_rgb_kernel(const T* __restrict__ in, size_t in_stride,
+                                                                     T* __restrict__ out, int H, int W, ColourCoef k)
+{
+    colour_decode<T, VEC, false>(in, ColourSurface{0, 0, 0, in_stride}, out, H, W, k);
+}
+
+// the same grid; NV12 (uint8_t) / P010 (uint16_t) surfaces `sf` -> planar RGB codes
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kColourBlock) void nv12_to_rgb_kernel(const T* __restrict__ in, ColourSurface sf,
+                                                                   T* __restrict__ out, int H, int W, ColourCoef k)
+{
+    colour_decode<T, VEC, true>(in, sf, out, H, W, k);
+}
+
+// The encode of one thread: luma rows 2i, 2i+1 and columns 4t .. 4t+3, i.e. chroma samples (i, 2t) and (i, 2t+1).
+// NV as for colour_decode.
+template <typename T, bool VEC, bool NV>
+__device__ __forceinline__ void colour_encode(const T* __restrict__ in, T* __restrict__ out, const ColourSurface& sf,
+                                              int H, int W, const ColourCoef& k)
 {
     using S = ColourSample<T>;
+    using Y = ColourWord<T, NV>;
     using Vec4 = typename S::Vec4;
     const int t = blockIdx.x * kColourBlock + threadIdx.x, x0 = 4 * t, i = blockIdx.y;
     if (x0 >= W) return;
@@ -227,18 +297,19 @@ __global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const T* __
                 for (int c = 0; c < 4; ++c) px[ch][rr][1 + c] = S::read(row[min(x0 + c, W - 1)]);
             }
         }
-    T* fy = out + (size_t)blockIdx.z * out_stride;
-    T* fu = fy + plane;
+    T* fy = out + (size_t)blockIdx.z * sf.frame_stride;
+    T* fu = fy + plane;                  // I420: the U and V planes
     T* fv = fu + (size_t)Hc * Wc;
+    T* fc = fy + sf.chroma_offset + (size_t)i * sf.chroma_pitch;   // NV: this thread's row of U,V pairs
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
         if (2 * i + rr >= H) break;
         T yv[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            yv[c] = S::clamp((k.yr * px[0][rr][1 + c] + k.yg * px[1][rr][1 + c] + k.yb * px[2][rr][1 + c] +
+            yv[c] = Y::store((k.yr * px[0][rr][1 + c] + k.yg * px[1][rr][1 + c] + k.yb * px[2][rr][1 + c] +
                               k.yoff * 16384 + 8192) >> 14);
-        T* o = fy + (size_t)(2 * i + rr) * W + x0;
+        T* o = fy + (size_t)(2 * i + rr) * (NV ? sf.luma_pitch : (size_t)W) + x0;
         if (VEC) {
             *reinterpret_cast<Vec4*>(o) = S::make(yv[0], yv[1], yv[2], yv[3]);
         } else {
@@ -247,10 +318,11 @@ __global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const T* __
                 if (x0 + c < W) o[c] = yv[c];
         }
     }
+    T cu[2], cv[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const int j = 2 * t + m;
-        if (j >= Wc) break;
+        if (!(NV && VEC) && j >= Wc) break;   // (NV && VEC: W % 4 == 0, both pairs exist)
         int s[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
@@ -263,9 +335,33 @@ __global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const T* __
                                  : px[ch][rr][a] + px[ch][rr][a + 1];
         }
         const int sh = k.mpeg2 ? 17 : 16, bias = (S::kCentre << sh) + (1 << (sh - 1));
-        fu[(size_t)i * Wc + j] = S::clamp((k.cbr * s[0] + k.cbg * s[1] + k.cbb * s[2] + bias) >> sh);
-        fv[(size_t)i * Wc + j] = S::clamp((k.crr * s[0] + k.crg * s[1] + k.crb * s[2] + bias) >> sh);
+        cu[m] = Y::store((k.cbr * s[0] + k.cbg * s[1] + k.cbb * s[2] + bias) >> sh);
+        cv[m] = Y::store((k.crr * s[0] + k.crg * s[1] + k.crb * s[2] + bias) >> sh);
+        if (!NV) {
+            fu[(size_t)i * Wc + j] = cu[m];
+            fv[(size_t)i * Wc + j] = cv[m];
+        } else if (!VEC) {
+            fc[2 * j] = cu[m];
+            fc[2 * j + 1] = cv[m];
+        }
     }
+    if (NV && VEC) *reinterpret_cast<Vec4*>(fc + 4 * t) = S::make(cu[0], cv[0], cu[1], cv[1]);   // U V U V, one store
+}
+
+// grid = (ceil(ceil(W/4) / 128), ceil(H/2), B)
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kColourBlock) void rgb_to_yuv420_kernel(const T* __restrict__ in, T* __restrict__ out,
+                                                                     size_t out_stride, int H, int W, ColourCoef k)
+{
+    colour_encode<T, VEC, false>(in, out, ColourSurface{0, 0, 0, out_stride}, H, W, k);
+}
+
+// the same grid; planar RGB codes -> NV12 (uint8_t) / P010 (uint16_t) surfaces `sf`
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kColourBlock) void rgb_to_nv12_kernel(const T* __restrict__ in, T* __restrict__ out,
+                                                                   ColourSurface sf, int H, int W, ColourCoef k)
+{
+    colour_encode<T, VEC, true>(in, out, sf, H, W, k);
 }
 
 }  // namespace fiunet

@@ -1526,6 +1526,171 @@ int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint
     return fiunet_rgb_p10_to_yuv420p10(o, out, out_frame_stride, B, H, W, colour, stream);
 }
 
+// ---- NV12 / P010 decoder surfaces: the colour conversions on semi-planar, pitched frames ----
+// The caller's layout (NULL or zero fields = tight) -> the resolved one, refused before any launch where it cannot
+// hold an H x W frame.  Every quantity in samples.
+static int resolve_surface(const fiunet_surface_layout* l, int H, int W, ColourSurface* sf)
+{
+    const size_t Hc = (size_t)(H + 1) / 2, Wc = (size_t)(W + 1) / 2;
+    sf->luma_pitch = l && l->luma_pitch ? l->luma_pitch : (size_t)W;
+    sf->chroma_offset = l && l->chroma_offset ? l->chroma_offset : (size_t)H * W;
+    sf->chroma_pitch = l && l->chroma_pitch ? l->chroma_pitch : 2 * Wc;
+    sf->frame_stride = l && l->frame_stride ? l->frame_stride : i420_frame_bytes(H, W);
+    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
+    if (sf->luma_pitch > big || sf->chroma_pitch > big || sf->chroma_offset > big || sf->frame_stride > big)
+        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: a value above 2^40 samples");
+    if (sf->luma_pitch < (size_t)W) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: luma_pitch < W");
+    if (sf->chroma_pitch < 2 * Wc) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_pitch < 2*ceil(W/2)");
+    if (sf->chroma_offset < (size_t)(H - 1) * sf->luma_pitch + W)
+        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_offset inside the luma plane");
+    if (sf->frame_stride < sf->chroma_offset + (Hc - 1) * sf->chroma_pitch + 2 * Wc)
+        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: frame_stride does not cover the chroma plane");
+    return FIUNET_OK;
+}
+
+extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
+// one 4-sample access per luma quad and per pair of owned chroma pairs: everything a multiple of 4 samples
+template <typename T>
+static bool surface_vec(const ColourSurface& sf, int W, const void* a, const void* b)
+{
+    return W % 4 == 0 && (sf.luma_pitch | sf.chroma_offset | sf.chroma_pitch | sf.frame_stride) % 4 == 0 &&
+           (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
+}
+
+template <typename T>
+static int surface_to_rgb(const T* in, const fiunet_surface_layout* layout, T* out, int B, int H, int W,
+                          unsigned colour, int bits, void* stream)
+{
+    int rc;
+    if (bits == 10 && (rc = check_colour_p10_flags(colour))) return rc;
+    if ((rc = check_colour_args(in, out, B, H, W, bits == 10 ? colour & kColourFlags : colour))) return rc;
+    ColourSurface sf;
+    if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
+    const ColourCoef k = colour_coef(colour, bits);
+    if (surface_vec<T>(sf, W, in, out))
+        hipLaunchKernelGGL((nv12_to_rgb_kernel<T, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, sf, out,
+                           H, W, k);
+    else
+        hipLaunchKernelGGL((nv12_to_rgb_kernel<T, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, sf, out,
+                           H, W, k);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+template <typename T>
+static int rgb_to_surface(const T* in, T* out, const fiunet_surface_layout* layout, int B, int H, int W,
+                          unsigned colour, int bits, void* stream)
+{
+    int rc;
+    if (bits == 10 && (rc = check_colour_p10_flags(colour))) return rc;
+    if ((rc = check_colour_args(in, out, B, H, W, bits == 10 ? colour & kColourFlags : colour))) return rc;
+    ColourSurface sf;
+    if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)((H + 1) / 2), (unsigned)B);
+    const ColourCoef k = colour_coef(colour, bits);
+    if (surface_vec<T>(sf, W, in, out))
+        hipLaunchKernelGGL((rgb_to_nv12_kernel<T, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, out, sf,
+                           H, W, k);
+    else
+        hipLaunchKernelGGL((rgb_to_nv12_kernel<T, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, out, sf,
+                           H, W, k);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_nv12_to_rgb_u8(const uint8_t* in, const fiunet_surface_layout* in_layout, uint8_t* out, int B, int H, int W,
+                          unsigned colour, void* stream)
+{
+    return surface_to_rgb<uint8_t>(in, in_layout, out, B, H, W, colour, 8, stream);
+}
+
+int fiunet_rgb_to_nv12_u8(const uint8_t* in, uint8_t* out, const fiunet_surface_layout* out_layout, int B, int H, int W,
+                          unsigned colour, void* stream)
+{
+    return rgb_to_surface<uint8_t>(in, out, out_layout, B, H, W, colour, 8, stream);
+}
+
+int fiunet_p010_to_rgb_p10(const uint16_t* in, const fiunet_surface_layout* in_layout, uint16_t* out, int B, int H,
+                           int W, unsigned colour, void* stream)
+{
+    return surface_to_rgb<uint16_t>(in, in_layout, out, B, H, W, colour, 10, stream);
+}
+
+int fiunet_rgb_p10_to_p010(const uint16_t* in, uint16_t* out, const fiunet_surface_layout* out_layout, int B, int H,
+                           int W, unsigned colour, void* stream)
+{
+    return rgb_to_surface<uint16_t>(in, out, out_layout, B, H, W, colour, 10, stream);
+}
+
+size_t fiunet_workspace_bytes_nv12(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return fiunet_workspace_bytes_yuv420(ctx, B, H, W, precision);
+}
+
+size_t fiunet_workspace_bytes_p010(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return fiunet_workspace_bytes_yuv420p10(ctx, B, H, W, precision);
+}
+
+int fiunet_forward_nv12(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
+                        const fiunet_surface_layout* in_layout, uint8_t* out, const fiunet_surface_layout* out_layout,
+                        int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                        void* stream)
+{
+    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3) return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_nv12 needs the RGB network (frame_channels 3)");
+    if (colour & ~kColourFlags) return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits");
+    const size_t need = fiunet_workspace_bytes_nv12(ctx, B, H, W, precision);
+    if (need == 0) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    int rc;
+    ColourSurface sf;   // both layouts are refused here, before the first launch
+    if ((rc = resolve_surface(in_layout, H, W, &sf)) || (rc = resolve_surface(out_layout, H, W, &sf))) return rc;
+    const size_t base = align256(fiunet_workspace_bytes_u8(ctx, B, H, W, precision));
+    const size_t rgb = align256((size_t)B * 3 * H * W);
+    uint8_t* a = (uint8_t*)workspace + base;
+    uint8_t* b = a + rgb;
+    uint8_t* o = b + rgb;
+    if ((rc = fiunet_nv12_to_rgb_u8(frame1, in_layout, a, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_nv12_to_rgb_u8(frame2, in_layout, b, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
+    return fiunet_rgb_to_nv12_u8(o, out, out_layout, B, H, W, colour, stream);
+}
+
+int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2,
+                        const fiunet_surface_layout* in_layout, uint16_t* out, const fiunet_surface_layout* out_layout,
+                        int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                        void* stream)
+{
+    if (!frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    int rc;
+    if ((rc = check_colour_p10_flags(colour))) return rc;
+    if (B < 1) return fail(FIUNET_ERR_INVALID_ARG, "B < 1");
+    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
+    ColourSurface sf;   // both layouts are refused here, before the first launch
+    if ((rc = resolve_surface(in_layout, H, W, &sf)) || (rc = resolve_surface(out_layout, H, W, &sf))) return rc;
+    if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3)
+        return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_p010 needs the RGB network (frame_channels 3)");
+    const size_t need = fiunet_workspace_bytes_p010(ctx, B, H, W, precision);
+    if (need == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    // [fiunet_forward_p10's workspace | frame1 RGB | frame2 RGB | output RGB], uint16 planar [B, 3, H, W] each
+    const size_t base = align256(fiunet_workspace_bytes_p10(ctx, B, H, W, precision));
+    const size_t rgb = align256((size_t)B * 3 * H * W * 2);
+    uint16_t* a = (uint16_t*)((char*)workspace + base);
+    uint16_t* b = (uint16_t*)((char*)a + rgb);
+    uint16_t* o = (uint16_t*)((char*)b + rgb);
+    if ((rc = fiunet_p010_to_rgb_p10(frame1, in_layout, a, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_p010_to_rgb_p10(frame2, in_layout, b, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
+    return fiunet_rgb_p10_to_p010(o, out, out_layout, B, H, W, colour, stream);
+}
+
 static inline int ssim_tiles(int H, int W, int* tiles_x)
 {
     const int ow = W - 2 * SSIM_PAD, oh = H - 2 * SSIM_PAD;

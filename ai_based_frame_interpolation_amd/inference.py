@@ -241,6 +241,31 @@ def interpolate_sequence_yuv420(model, frames: torch.Tensor, height: int, width:
     return out
 
 
+@torch.no_grad()
+def interpolate_sequence_nv12(model, frames: torch.Tensor, height: int, width: int, batch: int = 8, *,
+                              scene_cut: float | None = None, **colour) -> torch.Tensor:
+    """`interpolate_sequence_yuv420` on decoder frames: device uint8 [N, F] tight NV12 frames of height x width (the Y
+    plane, then interleaved U,V pairs) -> [2N-1, F] = F0, M0, F1, ..., F(N-1), Mi = model.forward_nv12(Fi, Fi+1,
+    **colour).  The same contract: originals byte for byte, middles written in place, a ragged last chunk padded.  A
+    tight NV12 frame holds the samples of its I420 frame in another order, so the scene-cut flags - sums over every
+    sample - are those of the I420 run.  colour: siting (None: "mpeg2") / matrix / colour_range."""
+    thr = scene.check_threshold(scene_cut)
+    h, w = int(height), int(width)
+    flags = _cut_flags(thr, [frames], 8)
+    n = frames.shape[0]
+    out = torch.empty((2 * n - 1, frames.shape[1]), dtype=torch.uint8, device=frames.device)
+    out[0::2] = frames
+
+    def fwd(a, b, out=None):
+        return model.forward_nv12(a.contiguous(), b.contiguous(), h, w, out=out, **colour)
+
+    for s, cnt in _pair_batches(n - 1, batch):
+        _padded_chunk(model, fwd, frames[s:s + cnt], frames[s + 1:s + cnt + 1], h, w, batch,
+                      out=out[2 * s + 1: 2 * (s + cnt): 2])
+    _hold(flags, 2, out)
+    return out
+
+
 # torch's uint16 is a dtype of limited support on the GPU (no guaranteed cat / repeat kernels): the 10-bit loops pad and
 # interleave int16 views of their uint16 frames (same bits) and hand uint16 views to the model.
 def _i16(t: torch.Tensor) -> torch.Tensor:
@@ -551,7 +576,8 @@ class FrameInterpolator:
                                              chunk_frames=chunk_frames, scene_cut=thr, **rate)
 
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
-                          chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend"):
+                          chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend", raw=None,
+                          width=None, height=None):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -571,11 +597,24 @@ class FrameInterpolator:
         included) and resamples them on the device to the times j x source rate / fps (retime.py):
         retime "blend" weighs the two bisection frames around each time, "nearest" takes the closer one; no frame
         blends across a flagged cut.  The Y4M header carries fps reduced.  src_fps: the source rate, required for
-        .npy input; for Y4M it overrides the header's."""
+        .npy input; for Y4M it overrides the header's.
+        raw: None, or "nv12": input and output are headerless tight NV12 frames of `height` x `width` (files, or file
+        objects: pipes), what `ffmpeg -f rawvideo -pix_fmt nv12` reads and writes and what a hardware decoder's
+        surfaces hold; they go through the RGB network on the device without a repack (`interpolate_sequence_nv12`,
+        stream.interpolate_raw_stream).  width, height and src_fps are then required (the stream has no
+        header); siting None means "mpeg2", the range is limited; factor, fps, scene_cut and chunk_frames work as for
+        Y4M."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         from . import stream
+        if raw is not None:
+            return stream.interpolate_raw_stream(self.model, input_path, output_path, factor, raw=raw, width=width,
+                                                 height=height, batch=self.batch, chunk_frames=chunk_frames,
+                                                 matrix=matrix, siting=siting, scene_cut=thr, fps=fps, src_fps=src_fps,
+                                                 time_depth=time_depth, retime=retime)
+        if width is not None or height is not None:
+            raise ValueError("width and height describe raw video: pass raw=\"nv12\" with them")
         rate = dict(zip(("fps", "src_fps", "time_depth", "retime"),
                         stream.check_retime(fps, src_fps, time_depth, retime, factor)))
         # (an `fps` run without chunk_frames takes the same routes with the whole clip as one chunk: stream._run_whole)

@@ -26,6 +26,10 @@ Memory is bounded by the chunk, never by the clip (C = chunk_frames, F = factor,
   host pinned    3 x (C + 2) input frames + 2 x (C x F + 1) output frames
   device         2 x (C + 2) input frames + one chunk's levels + the previous chunk's result (C x F + 1 frames of
                  the output layout; at factor 2 the levels are one result, at factor F about 2 x (C x F + 1) frames)
+Raw video (`interpolate_raw_stream`): headerless tight NV12 frames, what `ffmpeg -f rawvideo -pix_fmt
+nv12` writes and reads, through the same engine with `interpolate_sequence_nv12` as the level: factor, fps, scene_cut
+and chunk_frames work as they do for Y4M (the retime and hold kernels see packed rows of samples, whatever their order).
+
 With `fps=` (source / target rate = p / q, G = 2**time_depth) F is G in the levels, a chunk's result is its
 R = ceil(C x q / p) + 1 resampled frames, and the device holds them beside the grid:
   host pinned    3 x (C + 2) input frames + 2 x R output frames
@@ -45,7 +49,8 @@ import torch
 from . import colour, imageio_lite, scene
 from . import retime as _retime
 from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
-                        interpolate_sequence_p10, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10)
+                        interpolate_sequence_nv12, interpolate_sequence_p10, interpolate_sequence_yuv420,
+                        interpolate_sequence_yuv420p10)
 
 R_IN, R_OUT = 3, 2   # pinned input / output slots in the rings
 
@@ -162,6 +167,62 @@ def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
             return y
         return torch.cat([y] + [c.to(y.dtype).reshape(n, nc) for c in (cu, cv)], dim=1)
     return _Route(bits, row, out_row, run)
+
+
+RAW_FORMATS = ("nv12",)
+
+
+def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, siting) -> _Route:
+    """The route of headerless raw video (`raw`: "nv12", tight frames), with its refusals.  Nothing in the stream says
+    how it was made: siting None is "mpeg2" (what decoders produce) and the range is limited."""
+    if raw not in RAW_FORMATS:
+        raise ValueError(f"raw must be one of {list(RAW_FORMATS)} (or None: Y4M / .npy), got {raw!r}")
+    for name, v in (("height", height), ("width", width)):
+        if v is None:
+            raise ValueError(f"raw {raw} video has no header: pass width and height (missing: {name})")
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
+            raise ValueError(f"{name} must be a positive int, got {v!r}")
+    if model.frame_channels != 3:
+        raise ValueError(f"raw {raw} video goes through the RGB (6->3) network; this model is grayscale")
+    if npy_out:
+        raise ValueError(f"raw {raw} video through the RGB network is written as raw {raw} (no .npy output)")
+    h, w = int(height), int(width)
+    opts = dict(siting="mpeg2" if siting is None else siting, matrix=matrix, colour_range="limited")
+    colour.colour_flags(**opts)
+    row = colour.i420_frame_bytes(h, w)
+
+    def run(d, factor):
+        for _ in range(_levels(factor)):
+            d = interpolate_sequence_nv12(model, d, h, w, batch, **opts)
+        return d
+    return _Route(8, row, row, run)
+
+
+class _RawReader:
+    """`read_into` over headerless frames of `row` bytes from a binary file object (Y4MReader's interface).  A stream
+    that ends inside a frame is an error at that point."""
+
+    def __init__(self, f, row: int):
+        self.f, self.row, self.frames = f, row, 0
+
+    def read_into(self, buf: np.ndarray, max_frames: int) -> int:
+        flat = memoryview(buf).cast("B")
+        k = 0
+        while k < max_frames:
+            got, frame = 0, flat[k * self.row:(k + 1) * self.row]
+            while got < self.row:   # a pipe hands over what it has
+                n = self.f.readinto(frame[got:])
+                if not n:
+                    break
+                got += n
+            if got == 0:
+                break
+            if got < self.row:
+                raise ValueError(f"the raw stream ends inside a frame ({got} of {self.row} bytes of frame "
+                                 f"{self.frames + k})")
+            k += 1
+        self.frames += k
+        return k
 
 
 def _npy_route(model, shape, batch: int) -> _Route:
@@ -410,7 +471,7 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
 
 @torch.no_grad()
 def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode: str, n_frames=None) -> int:
-    """The resident form of `_run` with a plan: the whole clip on the device, one grid, one resample.  n_frames: the
+    """The resident form of `_run` (with a plan: one grid, one resample): the whole clip on the device.  n_frames: the
     clip's frame count where it is known up front (a regular file): the clip is then read into one array; a stream of
     unknown length is uploaded 64 frames at a time, so that the host never holds it twice."""
     dev = next(model.parameters()).device
@@ -441,6 +502,9 @@ def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode
         flags = scene.detect_cuts([d], thr, route.bits)[1]
     grid = route.run(d, factor)
     _hold(flags, factor, grid)
+    if plan is None:   # (the raw route without fps: the factor run's frames as they are)
+        write(grid.cpu().numpy().view(route.ndtype))
+        return grid.shape[0]
     n = plan.n_out(d.shape[0])
     rows = _retime.resample(grid, plan, 0, 0, n, bits=route.bits, flags=flags, mode=mode)
     write(rows.cpu().numpy().view(route.ndtype))
@@ -579,4 +643,61 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     return total
 
 
-__all__ = ["check_chunk_frames", "check_retime", "interpolate_y4m_stream", "interpolate_npy_stream"]
+def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12", width=None, height=None,
+                           batch: int = 8, chunk_frames: int | None = 32, matrix: str = "bt709",
+                           siting: str | None = None, scene_cut: float | None = None, scene_log: list | None = None,
+                           fps=None, src_fps=None, time_depth: int = 2, retime: str = "blend") -> int:
+    """Headerless raw video in (a path or a readable binary file: a pipe) -> the same format out (a path or a writable
+    binary file): tight NV12 frames of height x width (`ffmpeg ... -f rawvideo -pix_fmt nv12 -`) through the RGB
+    network, `interpolate_sequence_nv12` per level.  factor, scene_cut, chunk_frames (None: the whole clip resident)
+    and fps / time_depth / retime as for `interpolate_y4m_stream`; the stream carries no rate, so src_fps is required
+    (with fps it sets the resampling; the output has fps, or src_fps x factor, frames per second - pass that rate to
+    whatever reads the result).  siting None is "mpeg2", the range limited.  Every argument - the model's network, the
+    output name, the size of a regular input file (a whole number of frames) - is checked before any GPU work and
+    before the output exists; a pipe that ends inside a frame is an error at that point.  Returns the output frame
+    count."""
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut, whole_ok=True)
+    if src_fps is None:
+        raise ValueError("raw video carries no frame rate: pass src_fps")
+    src_rate = _retime.parse_fps(src_fps)
+    fps, _, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
+    npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
+    route = _raw_route(model, raw, height, width, npy_out, batch, matrix, siting)
+    plan = _plan_of(fps, src_rate, None, depth)
+    if plan is not None:
+        factor = plan.G
+    count = None
+    if _is_path(src):
+        if not os.path.exists(src):
+            raise FileNotFoundError(f"Video file not found: {src}")
+        st = os.stat(src)
+        if stat.S_ISREG(st.st_mode):
+            if st.st_size % route.row:
+                raise ValueError(f"{os.fspath(src)}: {st.st_size} bytes is not a whole number of {width}x{height} "
+                                 f"{raw} frames of {route.row} bytes")
+            count = st.st_size // route.row
+            if count == 0:
+                raise ValueError("no frames to interpolate")
+    fin = open(src, "rb") if _is_path(src) else src
+    try:
+        reader = _RawReader(fin, route.row)
+        f, finish = _open_sink(dst)
+        ok = False
+        try:
+            def write(rows):
+                f.write(np.ascontiguousarray(rows).data)
+            if C is None:
+                total = _run_whole(model, route, reader, write, factor, thr, plan, mode, count)
+            else:
+                total = _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode)
+            ok = True
+        finally:
+            finish(ok)
+        return total
+    finally:
+        if _is_path(src):
+            fin.close()
+
+
+__all__ = ["check_chunk_frames", "check_retime", "interpolate_y4m_stream", "interpolate_npy_stream",
+           "interpolate_raw_stream"]

@@ -443,6 +443,64 @@ class FrameInterpolationUNet(nn.Module):
             ctx.forward_yuv420p10(frame1, frame2, out, h, w, flags, prec, ws)
         return out
 
+    def _forward_surface(self, name, bits, frame1, frame2, height, width, layout, out, out_layout, siting, matrix,
+                         colour_range):
+        from .colour import colour_flags, resolve_layout
+        dtype, kind = (torch.uint16, "P010") if bits == 10 else (torch.uint8, "NV12")
+        flags = colour_flags("mpeg2" if siting is None else siting, matrix, colour_range, bits=bits)
+        if self.frame_channels != 3:
+            raise RuntimeError(f"{name} runs the RGB network (frame_channels=3); this model is grayscale")
+        h, w = int(height), int(width)
+        lay = resolve_layout(layout, h, w)
+        olay = resolve_layout(out_layout, h, w)
+        if frame1.dim() != 2 or frame1.shape != frame2.shape or frame1.shape[1] != lay.frame_stride:
+            raise RuntimeError(f"expected two [B,{lay.frame_stride}] tensors ({kind} surfaces of {h}x{w}) of equal "
+                               f"shape, got {tuple(frame1.shape)} and {tuple(frame2.shape)}")
+        self._check_device_mode_dtype(frame1, frame2, (dtype,))
+        if not frame1.is_contiguous() or not frame2.is_contiguous():
+            raise ValueError(f"{name} takes contiguous frames")
+        b = frame1.shape[0]
+        prec = self._precision_code()
+        ctx = self._context(frame1.device)
+        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=bits == 10)
+        shape = (b, olay.frame_stride)
+        if out is None:
+            # (a pitched surface has samples no frame covers: they are never written, so a new one starts as zeros)
+            out = (torch.empty if olay == resolve_layout(None, h, w) else torch.zeros)(shape, dtype=dtype,
+                                                                                        device=frame1.device)
+        elif (out.dtype != dtype or tuple(out.shape) != shape or out.device != frame1.device
+              or out.stride(1) != 1 or (b > 1 and out.stride(0) < olay.frame_stride)):
+            raise ValueError(f"out must be a {str(dtype).split('.')[-1]} {shape} tensor on {frame1.device} whose "
+                             "frames are contiguous")
+        with torch.cuda.device(frame1.device):
+            ctx.forward_surface(frame1, frame2, lay, out, olay, h, w, flags, prec, ws, bits)
+        return out
+
+    @torch.no_grad()
+    def forward_nv12(self, frame1: torch.Tensor, frame2: torch.Tensor, height: int, width: int, *, layout=None,
+                     out: torch.Tensor | None = None, out_layout=None, siting: str | None = None,
+                     matrix: str = "bt709", colour_range: str = "limited") -> torch.Tensor:
+        """The RGB network on decoder surfaces: uint8 NV12 frames in (the Y plane, then interleaved U,V pairs; what a
+        hardware decoder leaves in device memory) -> uint8 NV12 interpolated frames, `fiunet_forward_nv12`: bit for
+        bit `forward_yuv420` on the same samples, only their place in memory differs.  layout /
+        out_layout: a `colour.SurfaceLayout` (pitches, chroma offset and frame stride in samples) or None for tight
+        frames; the tensors are [B, frame_stride], [B, F] when tight.  siting None means "mpeg2", which is what
+        decoders produce.  `out`: write there - frames contiguous, possibly further apart; samples outside the used
+        columns and between the planes are left untouched."""
+        return self._forward_surface("forward_nv12", 8, frame1, frame2, height, width, layout, out, out_layout, siting,
+                                     matrix, colour_range)
+
+    @torch.no_grad()
+    def forward_p010(self, frame1: torch.Tensor, frame2: torch.Tensor, height: int, width: int, *, layout=None,
+                     out: torch.Tensor | None = None, out_layout=None, siting: str | None = None,
+                     matrix: str = "bt709", colour_range: str = "limited") -> torch.Tensor:
+        """`forward_nv12` on 10-bit surfaces: uint16 P010 frames (a word is code << 6: read as word >> 6, written with
+        the low six bits zero), `fiunet_forward_p010`: bit for bit `forward_yuv420p10` on the same codes.  matrix also
+        takes "bt2020"; siting None means "mpeg2", which is what decoders produce.  Use fp16 (or bf16x2, fp32): bf16
+        is about 5 codes off."""
+        return self._forward_surface("forward_p010", 10, frame1, frame2, height, width, layout, out, out_layout, siting,
+                                     matrix, colour_range)
+
     @torch.no_grad()
     def debug_activations(self, frame1, frame2, taps=None, with_up=False):
         """Parity-test hook: run one forward keeping every stage and return

@@ -26,7 +26,10 @@ extern "C" {
                                   7: 10-bit video (fiunet_forward_p10, fiunet_forward_yuv420p10 and their pieces; FIUNET_YUV_BT2020);
                                   8: precision FIUNET_FP16; v8 also: scene-cut entry points (fiunet_pair_sad_u8,
                                      fiunet_pair_sad_p10, fiunet_scene_cuts, fiunet_hold_cut_frames) and frame-rate conversion
-                                     (fiunet_retime_u8, fiunet_retime_p10), backwards-compatible */
+                                     (fiunet_retime_u8, fiunet_retime_p10), backwards-compatible; v8 also, added the same
+                                     way: NV12 / P010 decoder surfaces (fiunet_surface_layout, fiunet_nv12_to_rgb_u8,
+                                     fiunet_rgb_to_nv12_u8, fiunet_forward_nv12, fiunet_p010_to_rgb_p10,
+                                     fiunet_rgb_p10_to_p010, fiunet_forward_p010 and the two workspace queries) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -253,6 +256,55 @@ size_t fiunet_workspace_bytes_yuv420p10(const fiunet_ctx* ctx, int B, int H, int
 int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
                              size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* Semi-planar decoder surfaces (ABI v8, added without a version bump: nothing existing changed): NV12
+ * at 8 bits and P010 at 10, what a hardware decoder (VCN behind rocDecode, ffmpeg's hwaccel `nv12` / `p010le`) leaves in
+ * device memory and what hardware encoders take.  The arithmetic is exactly that of the 4:2:0 entry points above
+ * (csrc/colour.hip.h: siting, matrix, range, rounding and clamps); only where a sample lives differs.
+ * Layout, every quantity in SAMPLES (bytes at 8 bits, 16-bit words at 10), with Hc = ceil(H/2), Wc = ceil(W/2): a frame
+ * is H luma rows `luma_pitch` apart; from `chroma_offset` samples after the frame's base come Hc chroma rows
+ * `chroma_pitch` apart, each holding Wc pairs U0 V0 U1 V1 ...; frames are `frame_stride` apart.  The tight layout is
+ * luma_pitch = W, chroma_offset = H*W, chroma_pitch = 2*Wc, frame_stride = H*W + 2*Hc*Wc = F, the size of an I420
+ * frame.  A field that is 0 takes its tight value (a pitched surface names every field that differs); a NULL layout is
+ * the tight one.  FIUNET_ERR_INVALID_ARG, before any launch: luma_pitch < W, chroma_pitch < 2*Wc, chroma_offset <
+ * (H-1)*luma_pitch + W, or frame_stride < chroma_offset + (Hc-1)*chroma_pitch + 2*Wc (it does not cover the chroma
+ * plane).  Samples outside the W / 2*Wc used columns and between the planes are never read and never written.
+ * P010: a word is code << 6; read as word >> 6, the low six bits ignored whatever they hold; written with them zero.
+ * For a rocDecode / VCN surface: luma_pitch = chroma_pitch = the surface pitch (in samples), chroma_offset = pitch x
+ * the aligned surface height, frame_stride = the distance between surfaces (or 0 with B = 1 and a tight one). */
+typedef struct fiunet_surface_layout {
+    size_t luma_pitch, chroma_offset, chroma_pitch, frame_stride;
+} fiunet_surface_layout;
+/* NV12 surfaces -> planar RGB uint8 [B, 3, H, W], and back: fiunet_yuv420_to_rgb_u8 / fiunet_rgb_to_yuv420_u8 on the
+ * layout above.  With W, every layout value and the bases multiples of 4 samples, a thread's two chroma pairs are one
+ * 4-sample access.  Device pointers; any H, W >= 1; asynchronous on `stream`; no allocation, no synchronisation. */
+int fiunet_nv12_to_rgb_u8(const uint8_t* in, const fiunet_surface_layout* in_layout, uint8_t* out, int B, int H, int W,
+                          unsigned colour, void* stream);
+int fiunet_rgb_to_nv12_u8(const uint8_t* in, uint8_t* out, const fiunet_surface_layout* out_layout, int B, int H, int W,
+                          unsigned colour, void* stream);
+/* Workspace of fiunet_forward_nv12: that of fiunet_forward_yuv420. */
+size_t fiunet_workspace_bytes_nv12(const fiunet_ctx* ctx, int B, int H, int W, int precision);
+/* fiunet_forward_yuv420 on NV12 surfaces (layout above): frame1 and frame2 in `in_layout`, the B interpolated frames to
+ * `out` in `out_layout`.  Bit for bit fiunet_nv12_to_rgb_u8 (both inputs) -> fiunet_forward_u8_strided ->
+ * fiunet_rgb_to_nv12_u8; both layouts are checked before the first launch.  FIUNET_ERR_UNSUPPORTED on a context with
+ * frame_channels != 3.  Neither allocates nor synchronises. */
+int fiunet_forward_nv12(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
+                        const fiunet_surface_layout* in_layout, uint8_t* out, const fiunet_surface_layout* out_layout,
+                        int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                        void* stream);
+/* The same on P010 surfaces (uint16 words, code << 6) and planar RGB uint16 of 10-bit codes (the layout
+ * fiunet_forward_p10 takes): fiunet_yuv420p10_to_rgb_p10 / fiunet_rgb_p10_to_yuv420p10 on the layout above; `colour` as
+ * for those.  fiunet_forward_p010 is bit for bit fiunet_p010_to_rgb_p10 (both inputs) -> fiunet_forward_p10 ->
+ * fiunet_rgb_p10_to_p010 in the workspace of fiunet_forward_yuv420p10. */
+int fiunet_p010_to_rgb_p10(const uint16_t* in, const fiunet_surface_layout* in_layout, uint16_t* out, int B, int H,
+                           int W, unsigned colour, void* stream);
+int fiunet_rgb_p10_to_p010(const uint16_t* in, uint16_t* out, const fiunet_surface_layout* out_layout, int B, int H,
+                           int W, unsigned colour, void* stream);
+size_t fiunet_workspace_bytes_p010(const fiunet_ctx* ctx, int B, int H, int W, int precision);
+int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2,
+                        const fiunet_surface_layout* in_layout, uint16_t* out, const fiunet_surface_layout* out_layout,
+                        int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 /* Scene cuts in the video loops (ABI v8, added without a version bump: nothing existing changed).  The reference has
  * no video loop; the definition is our own.  For N frames and the N-1 intervals i between F[i] and

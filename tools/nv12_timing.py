@@ -1,0 +1,169 @@
+"""Time the NV12 / P010 conversions beside the I420 / C420p10 kernels they restate, in one process.
+
+  kernels   decode (YUV -> planar RGB) and encode (planar RGB -> YUV) of B frames, 1080p and 2160p, 8 and 10 bits:
+              i420_a, i420_b   the planar kernels (fiunet_yuv420_to_rgb_u8 ...), measured as two cases: the difference
+                               between them is the run-to-run spread of this job
+              nv12             the semi-planar kernels on tight frames (fiunet_nv12_to_rgb_u8 ...; P010 at 10 bits)
+              nv12_pitched     the same on surfaces of pitch W + 64 with the chroma plane at an aligned height
+            The kernels are HBM-bound and a decoder's surface comes from memory, not from a cache: the calls rotate over
+            a set of inputs and outputs of at least `--set-gb` GB together (several times the 256 MB Infinity Cache).
+            Device time from HIP events around `--iters` back-to-back calls after `--warmup` calls; `--reps` repetitions
+            interleaved over the cases; median and spread.  Bytes moved: one frame of F samples plus three planes of
+            H x W samples per frame, at either layout.
+  forward   forward_nv12 beside forward_yuv420 at B = 8, 1080p, bf16 (the conversions are two of its launches).
+One JSON line last.
+
+    python tools/nv12_timing.py [--batch 8 --set-gb 1 --iters 200 --reps 7]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import ai_based_frame_interpolation_amd as P  # noqa: E402
+from ai_based_frame_interpolation_amd import _native  # noqa: E402
+from ai_based_frame_interpolation_amd.colour import SurfaceLayout, resolve_layout  # noqa: E402
+from oracle import unet_oracle as O  # noqa: E402
+
+
+def _time(fn, iters):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / iters
+
+
+class _Rotate:
+    """Calls fn(k) with k = 0, 1, ..., n - 1, 0, ... : each call works on the next member of a set."""
+
+    def __init__(self, fn, n):
+        self.fn, self.n, self.k = fn, n, 0
+
+    def __call__(self):
+        self.fn(self.k)
+        self.k = (self.k + 1) % self.n
+
+
+def _kernel_cases(dev, bits, b, h, w, set_bytes):
+    """The YUV buffers are shared by every layout (a conversion's time does not depend on the values): one set of
+    `n_set` YUV batches wide enough for the pitched surface and one set of RGB batches."""
+    dtype, hi, sb = (torch.uint8, 256, 1) if bits == 8 else (torch.uint16, 1024, 2)
+    fs = P.i420_frame_bytes(h, w)
+    pitch, hal = w + 64, (h + 15) // 16 * 16
+    pitched = resolve_layout(SurfaceLayout(pitch, pitch * hal, pitch, pitch * (hal + hal // 2)), h, w)
+    moved = b * (fs + 3 * h * w) * sb
+    n_set = max(2, -(-set_bytes // (b * (pitched.frame_stride + 3 * h * w) * sb)))
+    g = torch.Generator(device=dev).manual_seed(bits)
+
+    def rnd(shape):   # (torch has no uint16 randint: 10-bit codes are drawn as int16, the same bits)
+        t = torch.randint(0, hi, shape, dtype=torch.uint8 if bits == 8 else torch.int16, device=dev, generator=g)
+        return t.view(dtype)
+    yuv = [rnd((b, pitched.frame_stride)) for _ in range(n_set)]
+    rgb = [rnd((b, 3, h, w)) for _ in range(n_set)]
+    flags = P.colour.colour_flags("mpeg2", "bt709", "limited", bits=bits)
+    tight = resolve_layout(None, h, w)
+    dec420 = _native.yuv420p10_to_rgb_p10 if bits == 10 else _native.yuv420_to_rgb_u8
+    enc420 = _native.rgb_p10_to_yuv420p10 if bits == 10 else _native.rgb_to_yuv420_u8
+
+    def planar(decode):
+        if decode:
+            return _Rotate(lambda k: dec420(yuv[k][:, :fs], rgb[k], h, w, flags), n_set)
+        return _Rotate(lambda k: enc420(rgb[k], yuv[k][:, :fs], flags), n_set)
+
+    def semi(decode, lay):
+        n = lay.frame_stride
+        if decode:
+            return _Rotate(lambda k: _native.surface_to_rgb(yuv[k][:, :n], lay, rgb[k], h, w, flags, bits), n_set)
+        return _Rotate(lambda k: _native.rgb_to_surface(rgb[k], yuv[k][:, :n], lay, flags, bits), n_set)
+    cases = {}
+    for name, decode in (("decode", True), ("encode", False)):
+        cases[f"{name} i420_a"] = planar(decode)
+        cases[f"{name} nv12"] = semi(decode, tight)
+        cases[f"{name} nv12_pitched"] = semi(decode, pitched)
+        cases[f"{name} i420_b"] = planar(decode)
+    return cases, moved, dict(batch=b, frame_samples=fs, pitch=pitch, set_members=n_set,
+                              set_mb=round(n_set * b * (pitched.frame_stride + 3 * h * w) * sb / 2**20))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--set-gb", type=float, default=1.0, help="least size of the rotating set of inputs and outputs")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--shapes", default="1080x1920,2160x3840")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "nv12_timing measures on the GPU; there is no CPU path"
+    dev = torch.device("cuda:0")
+    res = {"kernels": {}, "forward": {},
+           "protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of {a.iters} "
+                       f"calls rotating over a set of at least {a.set_gb} GB"}
+    for shape in a.shapes.split(","):
+        h, w = (int(v) for v in shape.split("x"))
+        for bits in (8, 10):
+            cases, moved, info = _kernel_cases(dev, bits, a.batch, h, w, int(a.set_gb * 1e9))
+            for fn in cases.values():
+                for _ in range(a.warmup):
+                    fn()
+            torch.cuda.synchronize()
+            ms = {k: [] for k in cases}
+            for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
+                for k, fn in cases.items():
+                    ms[k].append(_time(fn, a.iters))
+            leg = dict(info)
+            for k in cases:
+                med = statistics.median(ms[k])
+                leg[k] = dict(ms=round(med, 4), spread_ms=[round(min(ms[k]), 4), round(max(ms[k]), 4)],
+                              gb_per_s=round(moved / (med * 1e-3) / 1e9, 1))
+                print(f"{h}x{w} {bits:2d} bit {k:20s} {med:8.4f} ms  (reps {min(ms[k]):.4f}-{max(ms[k]):.4f})  "
+                      f"{leg[k]['gb_per_s']:7.1f} GB/s", flush=True)
+            for name in ("decode", "encode"):
+                ia, ib = leg[f"{name} i420_a"]["gb_per_s"], leg[f"{name} i420_b"]["gb_per_s"]
+                leg[f"{name} i420_spread"] = round(abs(ia - ib) / max(ia, ib), 4)
+                leg[f"{name} nv12_vs_i420"] = round(leg[f"{name} nv12"]["gb_per_s"] / min(ia, ib), 3)
+                leg[f"{name} nv12_pitched_vs_i420"] = round(leg[f"{name} nv12_pitched"]["gb_per_s"] / min(ia, ib), 3)
+            res["kernels"][f"{h}x{w}_{bits}bit"] = leg
+            del cases
+            torch.cuda.empty_cache()
+
+    b, h, w = 8, 1080, 1920
+    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
+    m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
+    m = m.to(dev).eval()
+    g = torch.Generator(device=dev).manual_seed(1)
+    f1, f2 = (torch.randint(0, 256, (b, P.i420_frame_bytes(h, w)), dtype=torch.uint8, device=dev, generator=g)
+              for _ in range(2))
+    out = torch.empty_like(f1)
+    opts = dict(siting="mpeg2", matrix="bt709", colour_range="limited")
+    runs = {"forward_yuv420_a": lambda: m.forward_yuv420(f1, f2, h, w, out=out, **opts),
+            "forward_nv12": lambda: m.forward_nv12(f1, f2, h, w, out=out, **opts),
+            "forward_yuv420_b": lambda: m.forward_yuv420(f1, f2, h, w, out=out, **opts)}
+    for fn in runs.values():
+        for _ in range(a.warmup):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in runs}
+    for _ in range(a.reps):
+        for k, fn in runs.items():
+            ms[k].append(_time(fn, 5))
+    for k in runs:
+        med = statistics.median(ms[k])
+        res["forward"][k] = dict(ms=round(med, 3), spread_ms=[round(min(ms[k]), 3), round(max(ms[k]), 3)],
+                                 frames_per_s=round(b / (med * 1e-3), 1))
+        print(f"{b}x{h}x{w} bf16 {k:18s} {med:8.3f} ms  (reps {min(ms[k]):.3f}-{max(ms[k]):.3f})  "
+              f"{res['forward'][k]['frames_per_s']:7.1f} frames/s", flush=True)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
