@@ -7,8 +7,12 @@ what earlier layers passed on, and a bound in units of M holds whatever the Batc
 
 The bf16 path's weights are restated bit for bit (`fold_bn`, `bf16_feedback`: csrc/fiunet.hip fiunet_load_weights,
 f32_to_bf16_feedback), so a bf16 stage is compared against its own weights and the bound only covers the accumulation
-and the rounding of its output.  `emulate_forward` runs the whole network with the activations rounded where a
-precision stores them.
+and the rounding of its output.  The fp16 path's likewise (`f16_rne_sat`: csrc/pointwise.hip.h f16_pack_weights_kernel).
+`emulate_forward` runs the whole network with the activations rounded where a precision stores them.
+
+`stage_error` / `check_stage` hold a stage's read-back output to the precision's per-element bound (stated in
+tests/test_gpu_bn_stats.py, which checks the device with it; tests/test_stage_oracle_fp16_host.py checks on the CPU that
+the fp16 bound rejects what it is there to catch).
 """
 from __future__ import annotations
 
@@ -63,6 +67,19 @@ def bf16_feedback(w):
     return out
 
 
+# ---- fp16 rounding, restated from the device code -------------------------------------------------------------------------
+F16_MAX = 65504.0
+
+
+def f16_rne_sat(x):
+    """pack_f16x2 (csrc/conv3x3_mfma.hip.h), fp32 in, fp32 out: clamp to +-65504, then round to nearest even to IEEE
+    half, subnormals kept (spacing 2^-24 below 2^-14).  `np.clip(x, -65504, 65504).astype(np.float16)` does exactly
+    this: numpy's float32 -> float16 conversion rounds to nearest even and keeps subnormals, and after the clamp no
+    value reaches the overflow threshold 65520."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    return np.clip(x, np.float32(-F16_MAX), np.float32(F16_MAX)).astype(np.float16).astype(np.float32)
+
+
 def fold_bn(sd, stage, exact=True):
     """(scale, shift) of a stage's BatchNorm: float64 from the statistics when `exact`, else the host's fp32
     arithmetic (inv = 1/sqrt(var + 1e-5f), scale = gamma * inv, shift = beta - mean * scale)."""
@@ -82,6 +99,7 @@ def stage_weights(sd, stage, weights="exact", cache=None):
     """(W [Cout, Cin, 3, 3], shift [Cout]) float64 of a conv stage as the device's precision holds them.
     exact: W * scale and the shift in float64.  bf16_feedback / bf16_rne: the host's fp32 product W * scale rounded to
     bf16 per filter over (ci, tap) in OIHW order, and its fp32 shift (the stem keeps exact weights in every precision).
+    fp16_rne: that fp32 product through f16_rne_sat, each weight on its own (f16_pack_weights_kernel bit for bit).
     cache: a dict the caller owns for one unchanging state dict (the feedback rounding walks every filter in order)."""
     key = (stage, weights)
     if cache is not None and key in cache:
@@ -94,23 +112,26 @@ def stage_weights(sd, stage, weights="exact", cache=None):
     else:
         sc, sh = fold_bn(sd, stage, exact=False)
         w32 = (w.numpy().astype(np.float32) * sc.astype(np.float32)[:, None, None, None]).reshape(w.shape[0], -1)
-        wb = bf16_feedback(w32) if weights == "bf16_feedback" else bf16_rne(w32)
-        assert weights in ("bf16_feedback", "bf16_rne"), weights
+        wb = _ROUND_WEIGHTS[weights](w32)
         res = (wb.reshape(w.shape).astype(np.float64), sh)
     if cache is not None:
         cache[key] = res
     return res
 
 
+_ROUND_WEIGHTS = {"bf16_feedback": bf16_feedback, "bf16_rne": bf16_rne, "fp16_rne": f16_rne_sat}
+
+
 def convt_weights(sd, k, weights="exact"):
-    """ConvTranspose2d of up{k} [Cin, Cout, 2, 2] and bias, float64; bf16 modes round per filter = (cout, tap) over ci."""
+    """ConvTranspose2d of up{k} [Cin, Cout, 2, 2] and bias, float64; bf16 modes round per filter = (cout, tap) over ci,
+    fp16_rne every weight on its own."""
     w = sd[f"unet.up{k}.up.weight"].numpy().astype(np.float32)
     b = sd[f"unet.up{k}.up.bias"].double().numpy()
     if weights == "exact":
         return w.astype(np.float64), b
     cin, cout = w.shape[:2]
     rows = w.transpose(1, 2, 3, 0).reshape(cout * 4, cin)       # filter (co, tap), K = ci
-    rb = bf16_feedback(rows) if weights == "bf16_feedback" else bf16_rne(rows)
+    rb = _ROUND_WEIGHTS[weights](rows)
     return rb.reshape(cout, 2, 2, cin).transpose(3, 0, 1, 2).astype(np.float64), b
 
 
@@ -130,6 +151,17 @@ def _bf16_uncertain(v, err):
     r = bf16_rne(a.astype(np.float32)).astype(np.float64)
     ulp = np.ldexp(1.0, np.frexp(np.abs(a))[1] - 8)               # bf16 ulp in the binade of |v|
     to_mid = ulp / 2 - np.abs(a - r)                                 # distance to the nearest rounding midpoint
+    slack = np.where(to_mid <= err.numpy() + np.abs(a) * 2.0 ** -22, ulp, 0.0)
+    return torch.from_numpy(r), torch.from_numpy(slack)
+
+
+def _f16_uncertain(v, err):
+    """_bf16_uncertain for fp16 (f16_rne_sat): the ulp of the binade of |v| is 2^(e-11) for 2^(e-1) <= |v| < 2^e, and
+    never below 2^-24, the subnormal spacing."""
+    a = np.clip(v.numpy(), -F16_MAX, F16_MAX)
+    r = f16_rne_sat(a.astype(np.float32)).astype(np.float64)
+    ulp = np.ldexp(1.0, np.maximum(np.frexp(np.abs(a))[1] - 11, -24))
+    to_mid = ulp / 2 - np.abs(a - r)
     slack = np.where(to_mid <= err.numpy() + np.abs(a) * 2.0 ** -22, ulp, 0.0)
     return torch.from_numpy(r), torch.from_numpy(slack)
 
@@ -168,14 +200,15 @@ def stage_input(sd, stage, inputs, weights="exact", stem="tap", cache=None):
     """(x, slack) float64 input of conv stage `stage` formed from the device's taps: max-pool, or upsample + F.pad +
     concat.  bf16 modes round the lerped upsample half to bf16 as the kernels do (slack marks values that may round the
     other way); stem="fused" forms inc.3's input as the fused bf16 stem does (split-bf16 evaluation of the stem, ~2^-16
-    of its terms, then bf16) instead of reading tap 0."""
+    of its terms, then bf16) instead of reading tap 0.  Weight mode fp16_rne: the same two roundings to fp16."""
     bf16 = weights != "exact"
+    uncertain = _f16_uncertain if weights == "fp16_rne" else _bf16_uncertain
     if stage == 0:
         x = torch.cat([_t(inputs["frame1"]), _t(inputs["frame2"])], 1)
         return x, torch.zeros_like(x)
     if stage == 1 and stem == "fused":
         y, m = stage_reference(sd, 0, inputs, "exact")
-        return _bf16_uncertain(y, m * 2.0 ** -14)
+        return uncertain(y, m * 2.0 ** -14)
     if stage in POOL_OF:
         x = F.max_pool2d(_t(inputs[TAP[POOL_OF[stage]]]), 2)
         return x, torch.zeros_like(x)
@@ -192,7 +225,7 @@ def stage_input(sd, stage, inputs, weights="exact", stem="tap", cache=None):
             # only a value within one fp32 ulp of a bf16 rounding midpoint (the fma's double rounding here) is uncertain
             up = _pad_to(upsample_fp32(low), skip)
             if bf16:
-                up, slack_up = _bf16_uncertain(up, up.abs() * 2.0 ** -22)
+                up, slack_up = uncertain(up, up.abs() * 2.0 ** -22)
         x = torch.cat([skip, up], 1)
         slack = torch.zeros_like(x)
         if slack_up is not None:
@@ -209,9 +242,11 @@ def stage_reference(sd, stage, inputs, weights="exact", stem="tap", with_slack=F
     stage: 0..17 (conv + BatchNorm + ReLU: y_ref = relu(conv(x, W*sc) + sh), M = conv(|x|, |W*sc|) + |sh|), "unet.outc"
     (the 1x1 head, no ReLU) or "unet.up{k}.up" (the ConvTranspose2d half of a bilinear=False decoder: before F.pad, as the
     reference's module returns it).  inputs: {"frame1", "frame2", tap name: tensor} - the read-back taps (NCHW) of the
-    stages that feed this one.  weights: "exact", "bf16_feedback" (the default bf16 rounding) or "bf16_rne".
-    with_slack: also return the bound's extra term for inputs the kernel rounds to bf16 itself (lerped upsample half,
-    fused stem), conv(slack, |W*sc|): one bf16 ulp of each input that may round the other way.
+    stages that feed this one.  weights: "exact", "bf16_feedback" (the default bf16 rounding), "bf16_rne" or "fp16_rne"
+    (precision fp16, whose stores saturate: y_ref = min(relu(...), 65504), a ConvTranspose2d half clamped on both sides;
+    the clamp is monotonic and 1-Lipschitz, so a bound on the unclamped value holds for the clamped one).
+    with_slack: also return the bound's extra term for inputs the kernel rounds to bf16 / fp16 itself (lerped upsample
+    half, fused stem), conv(slack, |W*sc|): one ulp of each input that may round the other way.
     cache: see stage_weights."""
     if stage == HEAD:
         x = _t(inputs[TAP[17]])
@@ -227,16 +262,84 @@ def stage_reference(sd, stage, inputs, weights="exact", stem="tap", with_slack=F
         w, b = torch.from_numpy(w), torch.from_numpy(b)
         y = F.conv_transpose2d(x, w, b, stride=2)
         m = F.conv_transpose2d(x.abs(), w.abs(), b.abs(), stride=2)
+        if weights == "fp16_rne":
+            y = y.clamp(-F16_MAX, F16_MAX)
         return (y, m, torch.zeros_like(y)) if with_slack else (y, m)
     x, slack = stage_input(sd, stage, inputs, weights, stem, cache)
     w, sh = stage_weights(sd, stage, weights, cache)
     w, sh = torch.from_numpy(w), torch.from_numpy(sh)
     y = F.relu(F.conv2d(x, w, sh, padding=1))
+    if weights == "fp16_rne":
+        y = y.clamp(max=F16_MAX)
     m = F.conv2d(x.abs(), w.abs(), sh.abs(), padding=1)
     if not with_slack:
         return y, m
     e = F.conv2d(slack, w.abs(), padding=1) if slack.any() else torch.zeros_like(y)
     return y, m, e
+
+
+# ---- the per-element bound of a stage ------------------------------------------------------------------------------------
+def stage_family(stage):
+    if stage == HEAD:
+        return "head"
+    if isinstance(stage, str):
+        return "convt"
+    return {0: "stem", 1: "inc.3"}.get(stage, "pool-fed" if stage in POOL_OF else
+                                        "concat" if stage in SKIP_OF_CONCAT else "direct")
+
+
+def stage_bound(prec, stage, y, m, e):
+    """The largest |y_dev - y| a precision may show on one stage, per element (tests/test_gpu_bn_stats.py derives each
+    term).  y, m, e: stage_reference(..., with_slack=True)."""
+    if prec == "fp32":
+        return 2.0 ** -16 * m
+    if prec == "bf16x2":
+        return 2.0 ** -14 * m + 2.0 ** -16 * y.abs()
+    if prec == "bf16":
+        return 2.0 ** -8 * m if stage == HEAD else 2.0 ** -8 * y.abs() + 2.0 ** -14 * m + e
+    assert prec == "fp16", prec
+    return 2.0 ** -11 * m if stage == HEAD else 2.0 ** -11 * y.abs() + 2.0 ** -25 + 2.0 ** -14 * m + e
+
+
+def stage_error(sd, stage, acts, prec, weights, stem="tap", cache=None):
+    """(y_dev, y_ref, M, error / bound, error / M) of one stage, float64: acts holds the stage's own read-back output
+    under its tap name next to its inputs (a ConvTranspose2d half as F.pad leaves it)."""
+    name = stage if isinstance(stage, str) else TAP[stage]
+    y_dev = acts[name].double().cpu()
+    y, m, e = stage_reference(sd, stage, acts, weights, stem, with_slack=True, cache=cache)
+    if isinstance(stage, str) and stage != HEAD:
+        skip = acts[TAP[SKIP_OF_CONCAT[10 + 2 * UP.index(stage)]]]
+        y, m, e = (_pad_to(t, skip) for t in (y, m, e))
+    assert y_dev.shape == y.shape, (name, y_dev.shape, y.shape)
+    bound = stage_bound(prec, stage, y, m, e)
+    err = (y_dev - y).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.inf, 0.0))
+    return y_dev, y, m, ratio, err / m.clamp_min(1e-300)
+
+
+def check_stage(sd, stage, acts, prec, weights, stem="tap", label="", cache=None, report=None):
+    """Assert the per-element bound of one stage; on failure report stage, channel, element, error/M, gamma and var.
+    report: a dict that collects the worst error / bound and error / M per (precision, stage family)."""
+    name = stage if isinstance(stage, str) else TAP[stage]
+    y_dev, y, m, ratio, over_m = stage_error(sd, stage, acts, prec, weights, stem, cache)
+    if report is not None:
+        r = report.setdefault((prec, stage_family(stage)), {"max_err_over_bound": 0.0, "max_err_over_M": 0.0})
+        r["max_err_over_bound"] = max(r["max_err_over_bound"], ratio.max().item())
+        r["max_err_over_M"] = max(r["max_err_over_M"], over_m.max().item())
+    if ratio.max().item() > 1.0:
+        i = int(ratio.argmax())
+        b, c, py, px = np.unravel_index(i, tuple(y.shape))
+        extra = ""
+        if isinstance(stage, int):
+            p, _, bi = STAGES[stage]
+            g = sd[f"{p}.double_conv.{bi}.weight"][c].item()
+            var = sd[f"{p}.double_conv.{bi}.running_var"][c].item()
+            extra = f" gamma {g:.4g} running_var {var:.4g}"
+        bad = int((ratio > 1).sum())
+        raise AssertionError(
+            f"{label} {prec} stage {name}: {bad} element(s) over the bound; worst at (b={b}, c={c}, y={py}, x={px}): "
+            f"device {y_dev.reshape(-1)[i].item():.9g} ref {y.reshape(-1)[i].item():.9g} err/M {over_m.reshape(-1)[i].item():.3e} "
+            f"err/bound {ratio.max().item():.3g}{extra}")
 
 
 # ---- whole-network emulation of a precision's storage points -------------------------------------------------------------
@@ -266,18 +369,22 @@ def _store(x, precision):
     if precision == "bf16x2":
         hi, lo = bf16_split(x.numpy().astype(np.float32))
         return torch.from_numpy(hi.astype(np.float64) + lo.astype(np.float64))
+    if precision == "fp16":
+        return torch.from_numpy(f16_rne_sat(x.numpy().astype(np.float32)).astype(np.float64))
     return x
 
 
 @torch.no_grad()
-def emulate_forward(sd, frame1, frame2, precision, dither=True, weights="bf16_feedback", dtype=torch.float64):
+def emulate_forward(sd, frame1, frame2, precision, dither=True, weights="bf16_feedback", dtype=torch.float64, keep=None):
     """The network in float64 with the activations rounded where `precision` stores them: "bf16" - bf16 weights
     (`weights`), the dithered frames into an fp32-grade stem, every conv output but the last (which feeds the fp32 head
     from registers) and every upsampled half rounded to bf16; "bf16x2" - the same points rounded to two bf16 pieces,
-    and every conv's product formed from two-piece operands as the kernels form it (wh*xh + wl*xh + wh*xl).  The
+    and every conv's product formed from two-piece operands as the kernels form it (wh*xh + wl*xh + wh*xl); "fp16" -
+    bf16's storage points rounded to fp16 (f16_rne_sat), "fp16_rne" weights whatever `weights` says, no dither.  The
     summation order is not the kernels', so this models the rounding, not the bits.  dtype: the arithmetic of the convs
-    (float32 also models the kernels' fp32 accumulation, at a fraction of float64's cost)."""
-    wmode = weights if precision == "bf16" else "exact"
+    (float32 also models the kernels' fp32 accumulation, at a fraction of float64's cost).  keep: a dict that receives
+    the frames as the stem saw them, every tap and every upsampled half as stored (what debug_activations reads back)."""
+    wmode = weights if precision == "bf16" else "fp16_rne" if precision == "fp16" else "exact"
     f1, f2 = frame1.double(), frame2.double()
     if precision == "bf16" and dither:
         d = stem_dither(f1.shape[2], f1.shape[3]).double()
@@ -311,4 +418,6 @@ def emulate_forward(sd, frame1, frame2, precision, dither=True, weights="bf16_fe
                 up = upsample_fp32(low)
             taps[UP[k - 1]] = _store(_pad_to(up, skip), precision)
         conv(i)
+    if keep is not None:
+        keep.update(taps)
     return stage_reference(sd, HEAD, taps)[0]

@@ -20,7 +20,15 @@ the error of one kernel, not what earlier layers passed on.  Bounds per element,
                                                       y * (h - 1) / (2h - 1) carries ~2^-23 * h into the lerp weights
                                                       (a 2^-21 band alone let 154 of 2.1 M elements of up4.0 through
                                                       at 135x240, none at 50x70).
-The bf16 head reads the last conv's fp32 accumulators, the read-back tap holds them rounded to bf16: 2^-8 M.
+  fp16    |y - y_ref| <= 2^-11 |y_ref| + 2^-25        y_ref from the device's exact fp16 weights (the fp32 fold through
+                         + 2^-14 M + E                pack_f16x2's clamp and RNE, subnormals kept, restated bit for bit) and
+                                                      clamped at 65504 as the store is: one RNE rounding to 11 significant
+                                                      bits, half the subnormal spacing 2^-24 for outputs below 2^-14, bf16's
+                                                      accumulation term (the same fp32 accumulators and summation orders)
+                                                      and E with fp16 ulps (never below 2^-24).
+The bf16 head reads the last conv's fp32 accumulators, the read-back tap holds them rounded to bf16: 2^-8 M; fp16: 2^-11 M.
+The bound itself is oracle.stage_oracle.stage_bound; tests/test_stage_oracle_fp16_host.py shows on the CPU that the fp16
+line rejects flushed subnormal weights and a wrong column at a tile seam.
 """
 import ctypes
 import json
@@ -39,7 +47,7 @@ from oracle import unet_oracle as O
 pytestmark = pytest.mark.gpu
 
 VARIANTS = {"gray": (2, 1, True), "rgb": (6, 3, True), "convt": (2, 1, False)}
-WEIGHTS = {"fp32": "exact", "bf16x2": "exact", "bf16": "bf16_feedback"}
+WEIGHTS = {"fp32": "exact", "bf16x2": "exact", "bf16": "bf16_feedback", "fp16": "fp16_rne"}
 _REPORT = {}   # (precision, stage family) -> worst error / bound and error / M seen
 
 
@@ -79,58 +87,14 @@ def _stage1_fused(prec, cf, bilinear, flags, b, h, w):
     fn = _native.lib().fiunet_debug_stage_cfg
     fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]
     out = (ctypes.c_int * 6)()
-    code = {"fp32": _native.FP32, "bf16": _native.BF16, "bf16x2": _native.BF16X2}[prec]
+    code = {"fp32": _native.FP32, "bf16": _native.BF16, "bf16x2": _native.BF16X2, "fp16": _native.FP16}[prec]
     assert fn(cf, int(bilinear), flags, code, b, h, w, 1, out) == 0
     return out[4] == 6
 
 
-def _family(stage):
-    if stage == S.HEAD:
-        return "head"
-    if isinstance(stage, str):
-        return "convt"
-    return {0: "stem", 1: "inc.3"}.get(stage, "pool-fed" if stage in S.POOL_OF else
-                                        "concat" if stage in S.SKIP_OF_CONCAT else "direct")
-
-
 def check_stage(sd, stage, acts, prec, weights, stem="tap", label="", cache=None):
-    """Assert the per-element bound of one stage; on failure report stage, channel, element, error/M, gamma and var."""
-    name = stage if isinstance(stage, str) else S.TAP[stage]
-    y_dev = acts[name].double().cpu()
-    y, m, e = S.stage_reference(sd, stage, acts, weights, stem, with_slack=True, cache=cache)
-    if isinstance(stage, str) and stage != S.HEAD:                  # a ConvTranspose2d half, as F.pad leaves it
-        skip = acts[S.TAP[S.SKIP_OF_CONCAT[10 + 2 * S.UP.index(stage)]]]
-        y, m, e = (S._pad_to(t, skip) for t in (y, m, e))
-    assert y_dev.shape == y.shape, (label, name, y_dev.shape, y.shape)
-    if prec == "fp32":
-        bound = 2.0 ** -16 * m
-    elif prec == "bf16x2":
-        bound = 2.0 ** -14 * m + 2.0 ** -16 * y.abs()
-    elif stage == S.HEAD:
-        bound = 2.0 ** -8 * m
-    else:
-        bound = 2.0 ** -8 * y.abs() + 2.0 ** -14 * m + e
-    err = (y_dev - y).abs()
-    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.inf, 0.0))
-    over_m = err / m.clamp_min(1e-300)
-    key = (prec, _family(stage))
-    r = _REPORT.setdefault(key, {"max_err_over_bound": 0.0, "max_err_over_M": 0.0})
-    r["max_err_over_bound"] = max(r["max_err_over_bound"], ratio.max().item())
-    r["max_err_over_M"] = max(r["max_err_over_M"], over_m.max().item())
-    if ratio.max().item() > 1.0:
-        i = int(ratio.argmax())
-        b, c, py, px = np.unravel_index(i, tuple(y.shape))
-        extra = ""
-        if isinstance(stage, int):
-            p, _, bi = S.STAGES[stage]
-            g = sd[f"{p}.double_conv.{bi}.weight"][c].item()
-            var = sd[f"{p}.double_conv.{bi}.running_var"][c].item()
-            extra = f" gamma {g:.4g} running_var {var:.4g}"
-        bad = int((ratio > 1).sum())
-        raise AssertionError(
-            f"{label} {prec} stage {name}: {bad} element(s) over the bound; worst at (b={b}, c={c}, y={py}, x={px}): "
-            f"device {y_dev.reshape(-1)[i].item():.9g} ref {y.reshape(-1)[i].item():.9g} err/M {over_m.reshape(-1)[i].item():.3e} "
-            f"err/bound {ratio.max().item():.3g}{extra}")
+    """oracle.stage_oracle.check_stage with this module's report of the worst ratios."""
+    S.check_stage(sd, stage, acts, prec, weights, stem, label, cache, report=_REPORT)
 
 
 def run_layer_local(model, sd, variant, prec, b, h, w, unfused=False, rne=False, seed=71, stages=None, frames=None,
@@ -169,13 +133,14 @@ def dev_of(model):
 
 # fused and unfused in fp32 and bf16; bf16x2 has no ablation path (plan_stages ignores FIUNET_OPT_UNFUSED for it), so
 # its unfused run would repeat the fused one
-_FU = {"fp32": (False, True), "bf16": (False, True), "bf16x2": (False,)}
+_FU = {"fp32": (False, True), "bf16": (False, True), "bf16x2": (False,), "fp16": (False, True)}
+_PRECS = ("fp32", "bf16x2", "bf16", "fp16")
 LAYER_CASES = (
-    [("gray", p, 1, 32, 48, u) for p in ("fp32", "bf16x2", "bf16") for u in _FU[p]]
-    + [("gray", p, 1, 135, 240, False) for p in ("fp32", "bf16x2", "bf16")]
-    + [("gray", p, 2, 50, 70, u) for p in ("fp32", "bf16x2", "bf16") for u in _FU[p]]
-    + [("rgb", p, 2, 45, 71, u) for p in ("fp32", "bf16x2", "bf16") for u in _FU[p]]
-    + [("convt", p, 1, 34, 52, u) for p in ("fp32", "bf16x2", "bf16") for u in _FU[p]]
+    [("gray", p, 1, 32, 48, u) for p in _PRECS for u in _FU[p]]
+    + [("gray", p, 1, 135, 240, False) for p in _PRECS]
+    + [("gray", p, 2, 50, 70, u) for p in _PRECS for u in _FU[p]]
+    + [("rgb", p, 2, 45, 71, u) for p in _PRECS for u in _FU[p]]
+    + [("convt", p, 1, 34, 52, u) for p in _PRECS for u in _FU[p]]
 )
 
 
@@ -185,12 +150,13 @@ def test_every_stage_within_its_precision_bound(models, sds, caches, variant, pr
     run_layer_local(models[variant], sds[variant], variant, prec, b, h, w, unfused, cache=caches[variant])
 
 
-@pytest.mark.parametrize("variant", ["gray", "rgb"])
-@pytest.mark.parametrize("prec", ["fp32", "bf16x2", "bf16"])
+@pytest.mark.parametrize("prec,variant", [(p, v) for p in ("fp32", "bf16x2", "bf16") for v in ("gray", "rgb")]
+                         + [("fp16", "gray")])
 def test_multi_tile_size_stem_and_deep_stages(models, sds, caches, variant, prec):
     """B=2 540x960, where the launches are the production ones (tuned tiles, whole K loops, the persistent RGB stem's
     multi-tile loop, the in-gather upsample of a deep concat conv in bf16): the stem, inc.3 and the deep stages
-    down4.0, down4.3 and up1.0, checked on the second image (all of the batch is launched)."""
+    down4.0, down4.3 and up1.0, checked on the second image (all of the batch is launched).  fp16: gray only, where
+    its fused stem and the tuned-tile instantiations run."""
     run_layer_local(models[variant], sds[variant], variant, prec, 2, 540, 960, stages=[0, 1, 8, 9, 10], seed=73,
                     cache=caches[variant], image=1)
 
@@ -201,7 +167,7 @@ def test_bf16_round_to_nearest_weights_stage_by_stage(models, sds):
 
 
 @pytest.mark.parametrize("variant", ["gray", "rgb"])
-@pytest.mark.parametrize("prec", ["fp32", "bf16", "bf16x2"])
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "bf16x2", "fp16"])
 def test_forced_tile_families_and_k_cuts(models, sds, caches, variant, prec):
     """Every tile family and K cut the configuration tests force (tests/test_gpu_configs.py): a cut K sum must add the
     shift exactly once, and the large shifts of this checkpoint make a mistake there visible.  On the uncut K loop the
@@ -279,10 +245,10 @@ def test_whole_network_fp32_against_float64_reference(models, golden_dir, varian
 
 
 @pytest.mark.parametrize("variant,name", [w for w in WHOLE if "135x240" not in w[1]])
-@pytest.mark.parametrize("prec", ["bf16x2", "bf16"])
+@pytest.mark.parametrize("prec", ["bf16x2", "bf16", "fp16"])
 def test_whole_network_reduced_precision_against_its_emulation(models, sds, golden_dir, variant, name, prec):
-    """bf16 / bf16x2 end to end with the default options (dither on): the device's rel-L2 against the float64 reference
-    is at most 2x that of a CPU emulation of the precision's storage points on the same checkpoint
+    """bf16 / bf16x2 / fp16 end to end with the default options (bf16: dither on): the device's rel-L2 against the float64
+    reference is at most 2x that of a CPU emulation of the precision's storage points on the same checkpoint
     (oracle.stage_oracle.emulate_forward), plus the reference's own fp32 rel-L2 (the arithmetic the emulation does not
     model: fp32 accumulation, which dominates bf16x2's storage rounding only where both are ~1e-6)."""
     m, sd = models[variant], sds[variant]
@@ -299,7 +265,7 @@ def test_whole_network_reduced_precision_against_its_emulation(models, sds, gold
     m.precision = "fp32"
 
 
-@pytest.mark.parametrize("prec", ["fp32", "bf16x2", "bf16"])
+@pytest.mark.parametrize("prec", ["fp32", "bf16x2", "bf16", "fp16"])
 def test_u8_path_bitwise_on_trained_like_checkpoint(models, prec):
     """forward_u8 == preprocess -> forward -> postprocess bit for bit (gray, where bf16 fuses the uint8 read into the
     stem, and RGB)."""

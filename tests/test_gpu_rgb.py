@@ -29,7 +29,8 @@ pytestmark = pytest.mark.gpu
 
 FP32_TOL = 1e-3
 RGB_WEIGHT_SEED = 77
-PRECISIONS = ["bf16", "bf16x2", "fp32"]
+PRECISIONS = ["bf16", "bf16x2", "fp32", "fp16"]
+REL_L2 = {"bf16": 2e-2, "fp16": 5e-3}   # the whole network against the oracle / the reference's sample
 STEM_GRID = 512          # 256 CUs x FIUNET_RGB_STEM_OCC: workgroups of the persistent RGB stem
 STEM_TH, STEM_TW = 16, 32
 K0 = "unet.inc.double_conv.0"
@@ -110,6 +111,13 @@ def _check_bf16_whole(out, ref, what):
     assert rel <= 2e-2 and d <= 0.04 * rng, (what, rel, d, rng)
 
 
+def _check_fp16_whole(out, ref, what):
+    """fp16's contract against the oracle (tests/test_gpu_fp16.py): rel-L2 <= 5e-3."""
+    assert out.shape == ref.shape and torch.isfinite(out).all(), what
+    rel = ((out - ref).norm() / ref.norm()).item()
+    assert rel <= REL_L2["fp16"], (what, rel)
+
+
 def _check_fp32_contract(out, ref, rel_tol, what):
     assert out.shape == ref.shape, what
     d = (out - ref).abs().max().item()
@@ -122,7 +130,8 @@ def test_rgb_stem_tap0_multi_tile(models, dev, oracle, prec, shape):
     """The stem's own output (tap 0, dither off: it perturbs the input by +-2^-9) over the whole tensor against the
     oracle's relu(bn(conv(cat(f1, f2)))), at tile counts where the persistent stem's workgroups run more than one tile.
     bf16: one bf16 rounding plus the split arithmetic (test_gpu_configs.py, RGB bf16 stem); bf16x2: the per-layer
-    bound, 2e-4 of the layer's range; fp32: 1e-4 relative."""
+    bound, 2e-4 of the layer's range; fp32: 1e-4 relative; fp16 (stem_rgb_split_kernel<false, _Float16>): bf16's line with
+    one fp16 rounding, 2^-11 relative."""
     b, h, w = shape
     f1, f2, _, want = oracle(shape)
     m = models[prec]
@@ -135,6 +144,7 @@ def test_rgb_stem_tap0_multi_tile(models, dev, oracle, prec, shape):
     assert got.shape == want.shape == (b, 64, h, w)
     err = (got - want).abs()
     bound = {"bf16": (2.0 ** -8 + 2.0 ** -13) * want.abs() + 5e-4,
+             "fp16": (2.0 ** -11 + 2.0 ** -13) * want.abs() + 5e-4,
              "bf16x2": torch.full_like(want, 2e-4 * want.abs().max().item()),
              "fp32": torch.full_like(want, 1e-4 * max(1.0, want.abs().max().item()))}[prec]
     bad = err > bound
@@ -163,6 +173,8 @@ def test_rgb_whole_net_multi_tile_vs_oracle(models, dev, oracle, prec):
             what = f"{prec} unfused={unfused}"
             if prec == "bf16":
                 _check_bf16_whole(out, ref, what)
+            elif prec == "fp16":
+                _check_fp16_whole(out, ref, what)
             else:
                 _check_fp32_contract(out, ref, 1e-4 if prec == "fp32" else 2e-4, what)
     finally:
@@ -182,9 +194,9 @@ def test_rgb_1080p_against_reference_sample(models, dev, rgb_sd, sample, prec):
     out = m(f1.to(dev), f2.to(dev)).cpu()
     assert out.shape == (1, 3, 1080, 1920) and torch.isfinite(out).all()
     got = out.reshape(-1)[torch.from_numpy(g["idx"])].numpy()
-    if prec == "bf16":
+    if prec in ("bf16", "fp16"):
         rel = np.linalg.norm(got - g["val"]) / np.linalg.norm(g["val"])
-        assert rel <= 2e-2, rel
+        assert rel <= REL_L2[prec], rel
         return
     assert np.abs(got - g["val"]).max() <= FP32_TOL, np.abs(got - g["val"]).max()
     if prec == "fp32":
@@ -215,7 +227,8 @@ def batch8(dev, sample):
 def test_rgb_1080p_batch8_properties(models, dev, sample, batch8, prec):
     """At the benchmark shape (~64 tiles per workgroup of the persistent stem; fp32's stem past its workgroup cap): the
     pair at position 5 of the batch equals the pair run alone bit for bit (no layer cuts K by batch from 1080p up),
-    and in bf16 two forwards agree bit for bit, every output is finite and the lone pair meets the sample's bound."""
+    and in bf16 and fp16 two forwards agree bit for bit, every output is finite and the lone pair meets the sample's
+    bound."""
     g, f1, f2 = sample
     b1, b2 = batch8
     m = models[prec]
@@ -223,13 +236,13 @@ def test_rgb_1080p_batch8_properties(models, dev, sample, batch8, prec):
     out_a = m(b1, b2)
     single = m(f1.to(dev), f2.to(dev))
     assert torch.equal(single[0], out_a[5])               # batch / position invariant
-    if prec == "bf16":
+    if prec in ("bf16", "fp16"):
         out_b = m(b1, b2)
         assert torch.equal(out_a, out_b)                  # deterministic
         assert torch.isfinite(out_a).all()
         got = single.cpu().reshape(-1)[torch.from_numpy(g["idx"])].numpy()
         rel = np.linalg.norm(got - g["val"]) / np.linalg.norm(g["val"])
-        assert rel <= 2e-2, rel
+        assert rel <= REL_L2[prec], rel
 
 
 def test_rgb_1080p_batch8_forward_u8_bitwise(models, dev, rgb_sd):
