@@ -311,15 +311,17 @@ class Context:
                                               w, precision, workspace.data_ptr(), workspace.numel(), s),
               "fiunet_forward_u8_strided")
 
-    def forward_yuv420(self, f1, f2, out, h, w, colour, precision, workspace, stream=None):
-        """f1, f2: uint8 [B, F] packed I420 frames, contiguous; `out`: uint8 [B, F] whose rows are contiguous and may lie
-        further apart (every second frame of the video loop's interleaved result)."""
+    def forward_yuv420(self, f1, f2, out, h, w, colour, precision, workspace, bits, stream=None):
+        """fiunet_forward_yuv420 (bits 8: uint8) / fiunet_forward_yuv420p10 (bits 10: uint16): f1, f2 [B, F] packed
+        4:2:0 frames, contiguous; `out` [B, F] whose rows are contiguous and may lie further apart (every second frame
+        of the video loop's interleaved result).  Strides in samples."""
         b = f1.shape[0]
         s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
         st = out.stride(0) if b > 1 else out.shape[1]
-        check(lib().fiunet_forward_yuv420(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), st, b, h, w, colour,
-                                          precision, workspace.data_ptr(), workspace.numel(), s),
-              "fiunet_forward_yuv420")
+        fn, name = ((lib().fiunet_forward_yuv420p10, "fiunet_forward_yuv420p10") if bits == 10 else
+                    (lib().fiunet_forward_yuv420, "fiunet_forward_yuv420"))
+        check(fn(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), st, b, h, w, colour, precision,
+                 workspace.data_ptr(), workspace.numel(), s), name)
 
     def forward_p10(self, f1, f2, out, precision, workspace, stream=None):
         """10-bit frames: uint16 [B, C, H, W] contiguous in; `out` uint16 [B, C, H, W] whose images are contiguous and
@@ -337,16 +339,6 @@ class Context:
         check(lib().fiunet_forward_p10(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), image_stride, b, h,
                                        w, precision, workspace.data_ptr(), workspace.numel(), s),
               "fiunet_forward_p10")
-
-    def forward_yuv420p10(self, f1, f2, out, h, w, colour, precision, workspace, stream=None):
-        """f1, f2: uint16 [B, F] packed 4:2:0 10-bit frames, contiguous; `out`: uint16 [B, F] whose rows are contiguous
-        and may lie further apart.  Strides in samples."""
-        b = f1.shape[0]
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
-        st = out.stride(0) if b > 1 else out.shape[1]
-        check(lib().fiunet_forward_yuv420p10(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), st, b, h, w,
-                                             colour, precision, workspace.data_ptr(), workspace.numel(), s),
-              "fiunet_forward_yuv420p10")
 
     def forward_surface(self, f1, f2, layout, out, out_layout, h, w, colour, precision, workspace, bits, stream=None):
         """fiunet_forward_nv12 (bits 8: uint8) / fiunet_forward_p010 (bits 10: uint16 words) on [B, frame_stride] rows:
@@ -392,75 +384,54 @@ class Context:
         return dst
 
 
-def preprocess_u8(src_u8: "torch.Tensor") -> "torch.Tensor":
-    out = torch.empty(src_u8.shape, dtype=torch.float32, device=src_u8.device)
-    s = torch.cuda.current_stream(src_u8.device).cuda_stream
-    check(lib().fiunet_preprocess_u8(src_u8.data_ptr(), out.data_ptr(), src_u8.numel(), s),
-          "fiunet_preprocess_u8")
+def _pointwise(name: str, src: "torch.Tensor", dtype) -> "torch.Tensor":
+    """One of the four pre / post-processing kernels on contiguous samples -> `dtype`, same shape."""
+    out = torch.empty(src.shape, dtype=dtype, device=src.device)
+    s = torch.cuda.current_stream(src.device).cuda_stream
+    check(getattr(lib(), name)(src.data_ptr(), out.data_ptr(), src.numel(), s), name)
     return out
+
+
+def preprocess_u8(src_u8: "torch.Tensor") -> "torch.Tensor":
+    """fiunet_preprocess_u8: uint8 -> fp32 x / 255 * 2 - 1."""
+    return _pointwise("fiunet_preprocess_u8", src_u8, torch.float32)
 
 
 def postprocess_u8(src_f32: "torch.Tensor") -> "torch.Tensor":
-    out = torch.empty(src_f32.shape, dtype=torch.uint8, device=src_f32.device)
-    s = torch.cuda.current_stream(src_f32.device).cuda_stream
-    check(lib().fiunet_postprocess_u8(src_f32.data_ptr(), out.data_ptr(), src_f32.numel(), s),
-          "fiunet_postprocess_u8")
-    return out
-
-
-def yuv420_to_rgb_u8(frames: "torch.Tensor", out: "torch.Tensor", h: int, w: int, colour: int) -> None:
-    """fiunet_yuv420_to_rgb_u8: uint8 [B, F] packed I420 (rows contiguous, any row stride) -> uint8 [B, 3, h, w]."""
-    b = frames.shape[0]
-    st = frames.stride(0) if b > 1 else frames.shape[1]
-    s = torch.cuda.current_stream(frames.device).cuda_stream
-    check(lib().fiunet_yuv420_to_rgb_u8(frames.data_ptr(), st, out.data_ptr(), b, h, w, colour, s),
-          "fiunet_yuv420_to_rgb_u8")
-
-
-def rgb_to_yuv420_u8(rgb: "torch.Tensor", out: "torch.Tensor", colour: int) -> None:
-    """fiunet_rgb_to_yuv420_u8: uint8 [B, 3, h, w] contiguous -> uint8 [B, F] (rows contiguous, any row stride)."""
-    b, _, h, w = rgb.shape
-    st = out.stride(0) if b > 1 else out.shape[1]
-    s = torch.cuda.current_stream(rgb.device).cuda_stream
-    check(lib().fiunet_rgb_to_yuv420_u8(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s),
-          "fiunet_rgb_to_yuv420_u8")
+    """fiunet_postprocess_u8: fp32 -> uint8 trunc(clamp((t + 1) / 2, 0, 1) * 255)."""
+    return _pointwise("fiunet_postprocess_u8", src_f32, torch.uint8)
 
 
 def preprocess_p10(src: "torch.Tensor") -> "torch.Tensor":
-    """fiunet_preprocess_p10: uint16 10-bit codes (contiguous) -> fp32 x / 1023 * 2 - 1, same shape."""
-    out = torch.empty(src.shape, dtype=torch.float32, device=src.device)
-    s = torch.cuda.current_stream(src.device).cuda_stream
-    check(lib().fiunet_preprocess_p10(src.data_ptr(), out.data_ptr(), src.numel(), s), "fiunet_preprocess_p10")
-    return out
+    """fiunet_preprocess_p10: uint16 10-bit codes -> fp32 x / 1023 * 2 - 1."""
+    return _pointwise("fiunet_preprocess_p10", src, torch.float32)
 
 
 def postprocess_p10(src_f32: "torch.Tensor") -> "torch.Tensor":
-    """fiunet_postprocess_p10: fp32 (contiguous) -> uint16 trunc(clamp((t + 1) / 2, 0, 1) * 1023), same shape."""
-    out = torch.empty(src_f32.shape, dtype=torch.uint16, device=src_f32.device)
-    s = torch.cuda.current_stream(src_f32.device).cuda_stream
-    check(lib().fiunet_postprocess_p10(src_f32.data_ptr(), out.data_ptr(), src_f32.numel(), s),
-          "fiunet_postprocess_p10")
-    return out
+    """fiunet_postprocess_p10: fp32 -> uint16 trunc(clamp((t + 1) / 2, 0, 1) * 1023)."""
+    return _pointwise("fiunet_postprocess_p10", src_f32, torch.uint16)
 
 
-def yuv420p10_to_rgb_p10(frames: "torch.Tensor", out: "torch.Tensor", h: int, w: int, colour: int) -> None:
-    """fiunet_yuv420p10_to_rgb_p10: uint16 [B, F] packed 4:2:0 (rows contiguous, any row stride) -> uint16
-    [B, 3, h, w]."""
+def yuv420_to_rgb(frames: "torch.Tensor", out: "torch.Tensor", h: int, w: int, colour: int, bits: int) -> None:
+    """fiunet_yuv420_to_rgb_u8 (bits 8: uint8) / fiunet_yuv420p10_to_rgb_p10 (bits 10: uint16): [B, F] packed 4:2:0
+    frames (rows contiguous, any row stride) -> planar RGB [B, 3, h, w]."""
     b = frames.shape[0]
     st = frames.stride(0) if b > 1 else frames.shape[1]
     s = torch.cuda.current_stream(frames.device).cuda_stream
-    check(lib().fiunet_yuv420p10_to_rgb_p10(frames.data_ptr(), st, out.data_ptr(), b, h, w, colour, s),
-          "fiunet_yuv420p10_to_rgb_p10")
+    fn, name = ((lib().fiunet_yuv420p10_to_rgb_p10, "fiunet_yuv420p10_to_rgb_p10") if bits == 10 else
+                (lib().fiunet_yuv420_to_rgb_u8, "fiunet_yuv420_to_rgb_u8"))
+    check(fn(frames.data_ptr(), st, out.data_ptr(), b, h, w, colour, s), name)
 
 
-def rgb_p10_to_yuv420p10(rgb: "torch.Tensor", out: "torch.Tensor", colour: int) -> None:
-    """fiunet_rgb_p10_to_yuv420p10: uint16 [B, 3, h, w] contiguous -> uint16 [B, F] (rows contiguous, any row
-    stride)."""
+def rgb_to_yuv420(rgb: "torch.Tensor", out: "torch.Tensor", colour: int, bits: int) -> None:
+    """fiunet_rgb_to_yuv420_u8 (bits 8: uint8) / fiunet_rgb_p10_to_yuv420p10 (bits 10: uint16): planar RGB [B, 3, h, w]
+    contiguous -> [B, F] packed 4:2:0 frames (rows contiguous, any row stride)."""
     b, _, h, w = rgb.shape
     st = out.stride(0) if b > 1 else out.shape[1]
     s = torch.cuda.current_stream(rgb.device).cuda_stream
-    check(lib().fiunet_rgb_p10_to_yuv420p10(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s),
-          "fiunet_rgb_p10_to_yuv420p10")
+    fn, name = ((lib().fiunet_rgb_p10_to_yuv420p10, "fiunet_rgb_p10_to_yuv420p10") if bits == 10 else
+                (lib().fiunet_rgb_to_yuv420_u8, "fiunet_rgb_to_yuv420_u8"))
+    check(fn(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s), name)
 
 
 def surface_to_rgb(frames: "torch.Tensor", layout, out: "torch.Tensor", h: int, w: int, colour: int, bits: int) -> None:

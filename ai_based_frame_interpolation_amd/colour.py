@@ -134,7 +134,7 @@ def yuv420_to_rgb(frames: torch.Tensor, height: int, width: int, *, siting: str 
     elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != frames.device or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous uint8 {shape} tensor on {frames.device}")
     with torch.cuda.device(frames.device):
-        _native.yuv420_to_rgb_u8(frames, out, height, width, flags)
+        _native.yuv420_to_rgb(frames, out, height, width, flags, 8)
     return out
 
 
@@ -156,7 +156,7 @@ def rgb_to_yuv420(rgb: torch.Tensor, *, siting: str = "jpeg", matrix: str = "bt7
         raise ValueError(f"out must hold {b} frames on {rgb.device}")
     _check_frames(out, h, w, "out")
     with torch.cuda.device(rgb.device):
-        _native.rgb_to_yuv420_u8(rgb, out, flags)
+        _native.rgb_to_yuv420(rgb, out, flags, 8)
     return out
 
 
@@ -173,7 +173,7 @@ def yuv420p10_to_rgb(frames: torch.Tensor, height: int, width: int, *, siting: s
     elif out.dtype != torch.uint16 or tuple(out.shape) != shape or out.device != frames.device or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous uint16 {shape} tensor on {frames.device}")
     with torch.cuda.device(frames.device):
-        _native.yuv420p10_to_rgb_p10(frames, out, height, width, flags)
+        _native.yuv420_to_rgb(frames, out, height, width, flags, 10)
     return out
 
 
@@ -197,7 +197,7 @@ def rgb_to_yuv420p10(rgb: torch.Tensor, *, siting: str = "jpeg", matrix: str = "
         raise ValueError(f"out must hold {b} frames on {rgb.device}")
     _check_frames(out, h, w, "out", torch.uint16)
     with torch.cuda.device(rgb.device):
-        _native.rgb_p10_to_yuv420p10(rgb, out, flags)
+        _native.rgb_to_yuv420(rgb, out, flags, 10)
     return out
 
 

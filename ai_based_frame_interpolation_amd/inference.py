@@ -11,7 +11,9 @@ never defines: `.interpolate_frames(img1, img2)` and
 `.interpolate_video(input, output, factor)`.
 
 The arithmetic of pre/post-processing and the network runs in HIP kernels; this file is
-plumbing (file I/O, shapes, batching).  No cv2/imageio in this image: image files go through cv2 if
+plumbing (file I/O, shapes, batching).  One loop (`_sequence`) is behind the five `interpolate_sequence*` functions;
+the video routes live in stream.py alone, and `FrameInterpolator.interpolate_video` checks its arguments and dispatches
+into them (`chunk_frames=None`, the resident call, is the whole clip as one chunk).  No cv2/imageio in this image: image files go through cv2 if
 it happens to be importable, else through imageio_lite (PNG, BMP, PGM/PPM, `.npy`; cv2.resize's
 fixed-point INTER_LINEAR restated); videos are raw `.npy` frame stacks [N,H,W] / [N,H,W,3] uint8.
 """
@@ -25,7 +27,7 @@ import torch
 from struct import error as struct_error
 from zlib import error as zlib_error
 
-from . import _native, colour, imageio_lite, scene
+from . import _native, imageio_lite, scene
 from .unet import FrameInterpolationUNet
 
 
@@ -196,6 +198,32 @@ def _hold(flags, factor, *videos):
             scene.hold_cut_frames(v, flags, factor)
 
 
+# torch's uint16 is a dtype of limited support on the GPU (no guaranteed cat / repeat kernels): the 10-bit loops pad and
+# interleave int16 views of their uint16 frames (same bits) and hand uint16 views to the model.
+def _i16(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.int16)
+
+
+def _u16(t: torch.Tensor | None) -> torch.Tensor | None:
+    return None if t is None else t.view(torch.uint16)
+
+
+def _sequence(model, fr: torch.Tensor, fwd, h: int, w: int, batch: int, thr, bits: int) -> torch.Tensor:
+    """The one factor-2 loop behind every `interpolate_sequence*`: device frames [N, ...] of h x w pictures in the dtype
+    the loop may cat / repeat (uint8; int16 words at 10 bits) -> [2N-1, ...] = F0, M0, F1, ..., F(N-1) in that dtype.  The
+    originals are copied as they are; `fwd(a, b, out=)` writes each chunk's middles where they belong (no temporary, no
+    strided copy), a ragged chunk padded as `_forward_u8_chunk` says; thr: a checked scene_cut threshold (None: off) -
+    the middle of every interval scene.detect_cuts flags, over every sample of a frame, is a copy of the frame before."""
+    flags = _cut_flags(thr, [fr], bits)
+    n = fr.shape[0]
+    out = torch.empty((2 * n - 1,) + tuple(fr.shape[1:]), dtype=fr.dtype, device=fr.device)
+    out[0::2] = fr
+    for s, cnt in _pair_batches(n - 1, batch):
+        _padded_chunk(model, fwd, fr[s:s + cnt], fr[s + 1:s + cnt + 1], h, w, batch, out=out[2 * s + 1: 2 * (s + cnt): 2])
+    _hold(flags, 2, out)
+    return out
+
+
 @torch.no_grad()
 def interpolate_sequence(model, frames_u8: torch.Tensor, batch: int = 8, *, scene_cut: float | None = None) -> torch.Tensor:
     """factor-2 video loop on one GPU: device uint8 frames [N,H,W] (or [N,C,H,W]) ->
@@ -206,13 +234,7 @@ def interpolate_sequence(model, frames_u8: torch.Tensor, batch: int = 8, *, scen
     thr = scene.check_threshold(scene_cut)
     squeeze = frames_u8.dim() == 3
     fr = frames_u8.unsqueeze(1) if squeeze else frames_u8
-    flags = _cut_flags(thr, [fr], 8)
-    n = fr.shape[0]
-    out = torch.empty((2 * n - 1,) + tuple(fr.shape[1:]), dtype=torch.uint8, device=fr.device)
-    out[0::2] = fr
-    for s, cnt in _pair_batches(n - 1, batch):   # each middle is written where it belongs (no temporary, no strided copy)
-        _forward_u8_chunk(model, fr[s:s + cnt], fr[s + 1:s + cnt + 1], batch, out=out[2 * s + 1: 2 * (s + cnt): 2])
-    _hold(flags, 2, out)
+    out = _sequence(model, fr, model.forward_u8, fr.shape[-2], fr.shape[-1], batch, thr, 8)
     return out.squeeze(1) if squeeze else out
 
 
@@ -226,19 +248,10 @@ def interpolate_sequence_yuv420(model, frames: torch.Tensor, height: int, width:
     colour: siting / matrix / colour_range (colour.py).  scene_cut: as for `interpolate_sequence`, on all three planes."""
     thr = scene.check_threshold(scene_cut)
     h, w = int(height), int(width)
-    flags = _cut_flags(thr, [frames], 8)
-    n = frames.shape[0]
-    out = torch.empty((2 * n - 1, frames.shape[1]), dtype=torch.uint8, device=frames.device)
-    out[0::2] = frames
 
     def fwd(a, b, out=None):
         return model.forward_yuv420(a, b, h, w, out=out, **colour)
-
-    for s, cnt in _pair_batches(n - 1, batch):
-        _padded_chunk(model, fwd, frames[s:s + cnt], frames[s + 1:s + cnt + 1], h, w, batch,
-                      out=out[2 * s + 1: 2 * (s + cnt): 2])
-    _hold(flags, 2, out)
-    return out
+    return _sequence(model, frames, fwd, h, w, batch, thr, 8)
 
 
 @torch.no_grad()
@@ -251,29 +264,10 @@ def interpolate_sequence_nv12(model, frames: torch.Tensor, height: int, width: i
     sample - are those of the I420 run.  colour: siting (None: "mpeg2") / matrix / colour_range."""
     thr = scene.check_threshold(scene_cut)
     h, w = int(height), int(width)
-    flags = _cut_flags(thr, [frames], 8)
-    n = frames.shape[0]
-    out = torch.empty((2 * n - 1, frames.shape[1]), dtype=torch.uint8, device=frames.device)
-    out[0::2] = frames
 
     def fwd(a, b, out=None):
         return model.forward_nv12(a.contiguous(), b.contiguous(), h, w, out=out, **colour)
-
-    for s, cnt in _pair_batches(n - 1, batch):
-        _padded_chunk(model, fwd, frames[s:s + cnt], frames[s + 1:s + cnt + 1], h, w, batch,
-                      out=out[2 * s + 1: 2 * (s + cnt): 2])
-    _hold(flags, 2, out)
-    return out
-
-
-# torch's uint16 is a dtype of limited support on the GPU (no guaranteed cat / repeat kernels): the 10-bit loops pad and
-# interleave int16 views of their uint16 frames (same bits) and hand uint16 views to the model.
-def _i16(t: torch.Tensor) -> torch.Tensor:
-    return t.view(torch.int16)
-
-
-def _u16(t: torch.Tensor | None) -> torch.Tensor | None:
-    return None if t is None else t.view(torch.uint16)
+    return _sequence(model, frames, fwd, h, w, batch, thr, 8)
 
 
 @torch.no_grad()
@@ -286,19 +280,11 @@ def interpolate_sequence_p10(model, frames: torch.Tensor, batch: int = 8, *, sce
     thr = scene.check_threshold(scene_cut)
     squeeze = frames.dim() == 3
     fr = frames.unsqueeze(1) if squeeze else frames
-    n, _, h, w = fr.shape
-    out = torch.empty((2 * n - 1,) + tuple(fr.shape[1:]), dtype=torch.uint16, device=fr.device)
-    f16, o16 = _i16(fr), _i16(out)
-    flags = _cut_flags(thr, [f16], 10)
-    o16[0::2] = f16
+    _, _, h, w = fr.shape
 
     def fwd(a, b, out=None):
         return _i16(model.forward_p10(_u16(a), _u16(b), out=_u16(out)))
-
-    for s, cnt in _pair_batches(n - 1, batch):
-        _padded_chunk(model, fwd, f16[s:s + cnt], f16[s + 1:s + cnt + 1], h, w, batch,
-                      out=o16[2 * s + 1: 2 * (s + cnt): 2])
-    _hold(flags, 2, o16)
+    out = _u16(_sequence(model, _i16(fr), fwd, h, w, batch, thr, 10))
     return out.squeeze(1) if squeeze else out
 
 
@@ -311,20 +297,10 @@ def interpolate_sequence_yuv420p10(model, frames: torch.Tensor, height: int, wid
     scene_cut: as for `interpolate_sequence`, on all three planes."""
     thr = scene.check_threshold(scene_cut)
     h, w = int(height), int(width)
-    n = frames.shape[0]
-    out = torch.empty((2 * n - 1, frames.shape[1]), dtype=torch.uint16, device=frames.device)
-    f16, o16 = _i16(frames), _i16(out)
-    flags = _cut_flags(thr, [f16], 10)
-    o16[0::2] = f16
 
     def fwd(a, b, out=None):
         return _i16(model.forward_yuv420p10(_u16(a), _u16(b), h, w, out=_u16(out), **colour))
-
-    for s, cnt in _pair_batches(n - 1, batch):
-        _padded_chunk(model, fwd, f16[s:s + cnt], f16[s + 1:s + cnt + 1], h, w, batch,
-                      out=o16[2 * s + 1: 2 * (s + cnt): 2])
-    _hold(flags, 2, o16)
-    return out
+    return _u16(_sequence(model, _i16(frames), fwd, h, w, batch, thr, 10))
 
 
 @torch.no_grad()
@@ -436,145 +412,6 @@ class FrameInterpolator:
         o = o[0] if self.model.frame_channels == img1.shape[2] else o[:, 0]
         return o.permute(1, 2, 0).contiguous().cpu().numpy()
 
-    def _interpolate_y4m(self, input_path, output_path, factor, thr=None):
-        """Uncompressed YUV4MPEG2 in -> out (`ffmpeg -i in.mp4 in.y4m` makes one; no codec exists in this
-        image).  The network is the reference's grayscale 2->1 model, so it interpolates the LUMA plane;
-        the chroma planes of an inserted frame are the rounded average of its neighbours' (an extension:
-        the reference has no colour or video path to be faithful to).  The frame rate is multiplied by
-        `factor`.  Output: `.y4m`, or a `.npy` stack of the luma frames."""
-        if self.model.frame_channels != 1:
-            raise ValueError("Y4M video goes through the grayscale (2->1) network")
-        y, chroma, fps, cs = imageio_lite.read_y4m(input_path)
-        t = torch.from_numpy(y).to(self.device)
-        cu = cv = None
-        if chroma is not None:
-            cu, cv = (torch.from_numpy(c).to(self.device) for c in chroma)
-        flags = _cut_flags(thr, [p for p in (t, cu, cv) if p is not None], 8)
-        f = factor
-        while f > 1:
-            t = interpolate_sequence(self.model, t, self.batch)
-            if cu is not None:
-                cu, cv = (_interleave_average_u8(c) for c in (cu, cv))
-            f //= 2
-        _hold(flags, factor, *(p for p in (t, cu, cv) if p is not None))
-        if str(output_path).lower().endswith(".y4m"):
-            imageio_lite.write_y4m(output_path, t.cpu().numpy(),
-                                   None if cu is None else (cu.cpu().numpy(), cv.cpu().numpy()),
-                                   (fps[0] * factor, fps[1]), cs)
-        else:
-            np.save(output_path, t.cpu().numpy())
-        return t.shape[0]
-
-    def _interpolate_y4m_p10(self, input_path, output_path, factor, thr=None):
-        """10-bit YUV4MPEG2 (`C420p10`, `C422p10`, `C444p10`, `Cmono10`) through the grayscale network: the luma plane
-        through `interpolate_sequence_p10`; the chroma of an inserted frame is the rounded average of its neighbours',
-        in int32.  The output keeps the input's tag and range, fps x factor.  Output: `.y4m`, or a `.npy` stack of the
-        uint16 luma frames."""
-        frames, hdr = imageio_lite.read_y4m_packed_p10(input_path)
-        h, w, (hc, wc) = hdr["height"], hdr["width"], hdr["chroma"]
-        ny, nc = h * w, hc * wc
-        t = torch.from_numpy(np.ascontiguousarray(frames[:, :ny]).reshape(-1, h, w)).to(self.device)
-        cu = cv = None
-        if nc:
-            cu, cv = (torch.from_numpy(frames[:, ny + i * nc:ny + (i + 1) * nc].astype(np.int32).reshape(-1, hc, wc))
-                      .to(self.device) for i in (0, 1))
-        # the chroma lives in int32 here: its low 16 bits are the samples as stored
-        flags = _cut_flags(thr, [_i16(t)] + ([] if cu is None else [c.to(torch.int16) for c in (cu, cv)]), 10)
-        f = factor
-        while f > 1:
-            t = interpolate_sequence_p10(self.model, t, self.batch)
-            if cu is not None:
-                cu, cv = (_interleave_average_p10(c) for c in (cu, cv))
-            f //= 2
-        _hold(flags, factor, *(p for p in (t, cu, cv) if p is not None))
-        y = t.cpu().numpy()
-        if str(output_path).lower().endswith(".y4m"):
-            imageio_lite.write_y4m_p10(output_path, y,
-                                       None if cu is None else (cu.cpu().numpy().astype(np.uint16),
-                                                                cv.cpu().numpy().astype(np.uint16)),
-                                       (hdr["fps"][0] * factor, hdr["fps"][1]), hdr["colourspace"],
-                                       colour_range=hdr["colour_range"])
-        else:
-            np.save(output_path, y)
-        return y.shape[0]
-
-    def _interpolate_y4m_colour_p10(self, input_path, output_path, factor, matrix, siting, thr=None):
-        """10-bit 4:2:0 YUV4MPEG2 (`C420p10`) through the RGB network (`interpolate_sequence_yuv420p10`).  The tag does
-        not carry the siting: `siting` None means "mpeg2" (left-sited: what HEVC, AV1 and H.264 decoders give).  Range
-        from `XCOLORRANGE` (limited when absent); `matrix` also takes "bt2020".  The output keeps the tag and range,
-        fps x factor."""
-        cs = imageio_lite.y4m_colourspace(input_path)
-        if cs != "420p10":
-            raise ValueError(f"Y4M colourspace C{cs} is not supported by the RGB network: it reads 10-bit 4:2:0 video "
-                             "tagged C420p10")
-        if not str(output_path).lower().endswith(".y4m"):
-            raise ValueError("colour Y4M video through the RGB network is written as .y4m (no .npy output)")
-        frames, hdr = imageio_lite.read_y4m_packed_p10(input_path)
-        opts = dict(siting="mpeg2" if siting is None else siting, matrix=matrix,
-                    colour_range="full" if hdr["colour_range"] == "FULL" else "limited")
-        colour.colour_flags(**opts, bits=10)   # a bad `matrix` / `siting` fails here, before any GPU work
-        h, w = hdr["height"], hdr["width"]
-        t = torch.from_numpy(frames).to(self.device)
-        flags = _cut_flags(thr, [_i16(t)], 10)
-        f = factor
-        while f > 1:
-            t = interpolate_sequence_yuv420p10(self.model, t, h, w, self.batch, **opts)
-            f //= 2
-        _hold(flags, factor, t)
-        res = t.cpu().numpy()
-        (hc, wc), ny = hdr["chroma"], h * w
-        u = res[:, ny:ny + hc * wc].reshape(-1, hc, wc)
-        v = res[:, ny + hc * wc:].reshape(-1, hc, wc)
-        imageio_lite.write_y4m_p10(output_path, res[:, :ny].reshape(-1, h, w), (u, v),
-                                   (hdr["fps"][0] * factor, hdr["fps"][1]), hdr["colourspace"],
-                                   colour_range=hdr["colour_range"])
-        return res.shape[0]
-
-    def _interpolate_y4m_colour(self, input_path, output_path, factor, matrix, siting=None, thr=None):
-        """4:2:0 YUV4MPEG2 in -> out through the RGB (6->3) network: every frame is converted to planar RGB on the
-        device, the network interpolates all three channels, and the middle frames are converted back
-        (`interpolate_sequence_yuv420`).  Chroma siting from the `C` tag (420jpeg / 420 / none, or 420mpeg2), range
-        from `XCOLORRANGE` (limited when absent); the matrix is not in the container: `matrix`.  The output has the
-        input's tag and range and fps x factor."""
-        if not str(output_path).lower().endswith(".y4m"):
-            raise ValueError("colour Y4M video through the RGB network is written as .y4m (no .npy output)")
-        frames, hdr = imageio_lite.read_y4m_packed(input_path)
-        tag_siting = colour.siting_of_y4m(hdr["colourspace"])   # rejects 422 / 444 / mono / 420paldv before any GPU work
-        opts = dict(siting=tag_siting if siting is None else siting, matrix=matrix,
-                    colour_range="full" if hdr["colour_range"] == "FULL" else "limited")
-        colour.colour_flags(**opts)   # a bad `matrix` fails here, before any GPU work
-        h, w = hdr["height"], hdr["width"]
-        t = torch.from_numpy(frames).to(self.device)
-        flags = _cut_flags(thr, [t], 8)
-        f = factor
-        while f > 1:
-            t = interpolate_sequence_yuv420(self.model, t, h, w, self.batch, **opts)
-            f //= 2
-        _hold(flags, factor, t)
-        res = t.cpu().numpy()
-        (hc, wc), ny = hdr["chroma"], h * w
-        u = res[:, ny:ny + hc * wc].reshape(-1, hc, wc)
-        v = res[:, ny + hc * wc:].reshape(-1, hc, wc)
-        imageio_lite.write_y4m(output_path, res[:, :ny].reshape(-1, h, w), (u, v),
-                               (hdr["fps"][0] * factor, hdr["fps"][1]), hdr["colourspace"],
-                               colour_range=hdr["colour_range"])
-        return res.shape[0]
-
-    def _interpolate_video_stream(self, input_path, output_path, factor, matrix, siting, thr, chunk_frames, **rate):
-        """rate: fps / src_fps / time_depth / retime; with fps, chunk_frames None is the whole clip as one chunk."""
-        from . import stream
-        if chunk_frames is not None or rate.get("fps") is None:
-            stream.check_chunk_frames(chunk_frames)
-        is_path = isinstance(input_path, (str, os.PathLike))
-        if is_path and not os.path.exists(input_path):
-            raise FileNotFoundError(f"Video file not found: {input_path}")
-        if not is_path or str(input_path).lower().endswith(".y4m"):
-            return stream.interpolate_y4m_stream(self.model, input_path, output_path, factor, batch=self.batch,
-                                                 chunk_frames=chunk_frames, matrix=matrix, siting=siting,
-                                                 scene_cut=thr, **rate)
-        return stream.interpolate_npy_stream(self.model, input_path, output_path, factor, batch=self.batch,
-                                             chunk_frames=chunk_frames, scene_cut=thr, **rate)
-
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
                           chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend", raw=None,
                           width=None, height=None):
@@ -588,9 +425,12 @@ class FrameInterpolator:
         sample as stored (all planes, all channels; scene.py), and every frame inserted into a cut
         interval - factor - 1 of them, chroma included - is a byte copy of the frame before the cut.  10 separates
         a hard cut from ordinary motion.
-        chunk_frames: None holds the whole clip (host and device); an int streams it `chunk_frames` pairs at a time in
-        memory bounded by the chunk (stream.py), with a byte-identical result.  Streamed, the input
-        may also be a readable binary file object (Y4M: a pipe) and the output a writable one (Y4M).
+        chunk_frames: None holds the whole clip (host and device) as one chunk; an int streams it `chunk_frames` pairs
+        at a time in memory bounded by the chunk (the same routes: stream.py), with a byte-identical
+        result.  The input may also be a readable binary file object (Y4M: a pipe) and the output a writable one (Y4M).
+        A path output is written as `<output>.part` and renamed on success.  Output naming: `.npy` is a stack of the
+        luma frames (grayscale network), anything else Y4M; a whole-clip Y4M call (no chunk_frames, no fps) keeps its
+        older rule - whatever does not end in `.y4m` is a `.npy` stack, `.npy` appended where the name lacks it.
         fps: None, or the frame rate of the output, above the source's: an int, a Fraction, an (n, d) pair or an "n/d"
         string such as "60000/1001" (no floats: 59.94 is not 60000/1001).  `factor` then stays 2; every route builds
         the frames of a 2**time_depth bisection (time_depth 1..4; what factor = 2**time_depth computes, cut holds
@@ -608,56 +448,25 @@ class FrameInterpolator:
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         from . import stream
+        run = dict(batch=self.batch, chunk_frames=chunk_frames, scene_cut=thr, fps=fps, src_fps=src_fps,
+                   time_depth=time_depth, retime=retime)
         if raw is not None:
             return stream.interpolate_raw_stream(self.model, input_path, output_path, factor, raw=raw, width=width,
-                                                 height=height, batch=self.batch, chunk_frames=chunk_frames,
-                                                 matrix=matrix, siting=siting, scene_cut=thr, fps=fps, src_fps=src_fps,
-                                                 time_depth=time_depth, retime=retime)
+                                                 height=height, matrix=matrix, siting=siting, **run)
         if width is not None or height is not None:
             raise ValueError("width and height describe raw video: pass raw=\"nv12\" with them")
-        rate = dict(zip(("fps", "src_fps", "time_depth", "retime"),
-                        stream.check_retime(fps, src_fps, time_depth, retime, factor)))
-        # (an `fps` run without chunk_frames takes the same routes with the whole clip as one chunk: stream._run_whole)
-        if chunk_frames is not None or rate["fps"] is not None:
-            return self._interpolate_video_stream(input_path, output_path, factor, matrix, siting, thr, chunk_frames,
-                                                  **rate)
-        if not os.path.exists(input_path):
+        stream.check_retime(fps, src_fps, time_depth, retime, factor)
+        if chunk_frames is not None:
+            stream.check_chunk_frames(chunk_frames)
+        is_path = isinstance(input_path, (str, os.PathLike))
+        if is_path and not os.path.exists(input_path):
             raise FileNotFoundError(f"Video file not found: {input_path}")
-        if str(input_path).lower().endswith(".y4m"):
-            p10 = imageio_lite.y4m_colourspace(input_path) in imageio_lite.Y4M_P10_TAGS
-            if self.model.frame_channels == 3:
-                if p10:
-                    return self._interpolate_y4m_colour_p10(input_path, output_path, factor, matrix, siting, thr)
-                return self._interpolate_y4m_colour(input_path, output_path, factor, matrix, siting, thr)
-            if p10:
-                return self._interpolate_y4m_p10(input_path, output_path, factor, thr)
-            return self._interpolate_y4m(input_path, output_path, factor, thr)
-        frames = np.load(input_path)
-        if frames.dtype != np.uint8 or frames.ndim not in (3, 4):
-            raise ValueError("expected a uint8 .npy stack [N,H,W] or [N,H,W,3]")
-        t = torch.from_numpy(frames).to(self.device)
-        flags = _cut_flags(thr, [t], 8)   # [N,H,W] or [N,H,W,3]: every channel of a frame counts
-        if t.dim() == 4:
-            t = t.permute(0, 3, 1, 2).contiguous()
-            if self.model.frame_channels == 1:  # per-channel application of the 2->1 network
-                n, c, h, w = t.shape
-                t = t.permute(1, 0, 2, 3).reshape(c * n, h, w)
-                outs = []
-                for ci in range(c):
-                    seq = t[ci * n:(ci + 1) * n]
-                    f = factor
-                    while f > 1:
-                        seq = interpolate_sequence(self.model, seq, self.batch); f //= 2
-                    outs.append(seq)
-                res = torch.stack(outs, dim=-1)
-                _hold(flags, factor, res)
-                np.save(output_path, res.cpu().numpy())
-                return res.shape[0]
-        f = factor
-        while f > 1:
-            t = interpolate_sequence(self.model, t, self.batch); f //= 2
-        _hold(flags, factor, t)
-        if t.dim() == 4:
-            t = t.permute(0, 2, 3, 1)
-        np.save(output_path, t.cpu().numpy())
-        return t.shape[0]
+        if is_path and not str(input_path).lower().endswith(".y4m"):
+            return stream.interpolate_npy_stream(self.model, input_path, output_path, factor, **run)
+        if chunk_frames is None and fps is None and isinstance(output_path, (str, os.PathLike)):
+            # the whole-clip call's older naming rule: whatever is not `.y4m` is a `.npy` stack, named as np.save names it
+            name = os.fspath(output_path)
+            if not name.lower().endswith(".y4m") and not name.endswith(".npy"):
+                output_path = name + ".npy"
+        return stream.interpolate_y4m_stream(self.model, input_path, output_path, factor, matrix=matrix, siting=siting,
+                                             **run)

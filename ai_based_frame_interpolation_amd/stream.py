@@ -1,13 +1,15 @@
-"""Streaming video: interpolate a clip of any length, from a file or a pipe, in memory bounded by the chunk.
+"""The video routes: interpolate a clip of any length, from a file or a pipe, whole or in memory bounded by the chunk.
 
-`FrameInterpolator.interpolate_video` (chunk_frames=None) holds the whole clip in host memory and on the device.  This
-module runs the same routes chunk by chunk:
+There is one implementation of each route (`_y4m_route`, `_npy_route`, `_raw_route`: what it computes, refuses and
+writes); `FrameInterpolator.interpolate_video` dispatches into the three `interpolate_*_stream` functions here.
+"Resident" (chunk_frames=None) means one chunk: `_run_whole` holds the whole clip in host memory and on the device.
+`_run` takes the same route chunk by chunk:
 
   chunk      `chunk_frames` input pairs plus the overlap frame it shares with the next chunk.  On the device each
-             chunk runs the helpers the resident routes call (`interpolate_sequence*`, `_interleave_average_*`,
-             `_padded_chunk` inside them, `_hold`), one level per factor bit.  Every middle depends only on its two
-             neighbours and `_padded_chunk` makes a pair's result independent of the pairs that share its call, so the
-             output is byte for byte the resident one for every chunk_frames >= 1.  The overlap frame is written once.
+             chunk runs the route's levels (`interpolate_sequence*`, `_interleave_average_*`, `_padded_chunk` inside
+             them, `_hold`), one level per factor bit.  Every middle depends only on its two neighbours and
+             `_padded_chunk` makes a pair's result independent of the pairs that share its call, so the output is byte
+             for byte the whole-clip one for every chunk_frames >= 1.  The overlap frame is written once.
   scene cuts the two-sided score of interval i needs mafd[i-1] and mafd[i+1]: with `scene_cut` on, a chunk carries
              one lookahead frame and the previous chunk's last interval sum; `scene.score_window` scores the window
              (carried interval, the chunk's intervals, lookahead interval) and the chunk keeps its own flags, which
@@ -62,14 +64,14 @@ def check_chunk_frames(chunk_frames) -> int:
     return int(chunk_frames)
 
 
-def _check_common(factor, batch, chunk_frames, scene_cut, whole_ok=False):
-    """whole_ok: chunk_frames None (the whole clip as one chunk: `fps` runs only) passes as None."""
+def _check_common(factor, batch, chunk_frames, scene_cut):
+    """chunk_frames None (the whole clip as one chunk, `_run_whole`) passes as None."""
     thr = scene.check_threshold(scene_cut)
     if isinstance(factor, bool) or not isinstance(factor, numbers.Integral) or factor < 2 or factor & (factor - 1):
         raise ValueError("factor must be a power of two (the network has no time input)")
     if isinstance(batch, bool) or not isinstance(batch, numbers.Integral) or batch < 1:
         raise ValueError(f"batch must be a positive int, got {batch!r}")
-    return thr, None if (whole_ok and chunk_frames is None) else check_chunk_frames(chunk_frames)
+    return thr, None if chunk_frames is None else check_chunk_frames(chunk_frames)
 
 
 def check_retime(fps, src_fps, time_depth, retime, factor):
@@ -95,8 +97,7 @@ def _levels(factor: int) -> int:
 # ---- routes: one chunk [k, row] of input frames -> [(k-1) x factor + 1, out_row] output rows on the device -----------
 class _Route:
     """bits: sample depth (8: uint8 rows; 10: int16 words of 10-bit codes on the device, uint16 on the host); row /
-    out_row: samples per input / output frame; run(d, factor): the levels of one chunk, the same helpers as the
-    resident route."""
+    out_row: samples per input / output frame; run(d, factor): the levels of one chunk (the whole clip is one chunk)."""
 
     def __init__(self, bits, row, out_row, run):
         self.bits, self.row, self.out_row, self.run = bits, row, out_row, run
@@ -105,7 +106,9 @@ class _Route:
 
 
 def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
-    """The route `interpolate_video` takes for this stream header and model, with its refusals and messages."""
+    """The route of Y4M video for this stream header and model, with its refusals and messages: the RGB network on
+    4:2:0 frames (8-bit: siting from the tag; `C420p10`: siting None is "mpeg2"; range from `XCOLORRANGE`), or the
+    grayscale network on the luma plane with the chroma of an inserted frame the rounded average of its neighbours'."""
     h, w, (hc, wc), bits = hdr["height"], hdr["width"], hdr["chroma"], hdr["bits"]
     ny, nc, row = h * w, hc * wc, hdr["frame_samples"]
     if model.frame_channels == 3:
@@ -146,7 +149,7 @@ def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
         cu = cv = None
         if nc:
             cu, cv = (d[:, ny + i * nc:ny + (i + 1) * nc].reshape(k, hc, wc) for i in (0, 1))
-            if bits == 10:   # the resident route's int32 chroma: the 16-bit words as unsigned samples
+            if bits == 10:   # 10-bit chroma is averaged in int32: the 16-bit words as unsigned samples
                 cu, cv = ((c.to(torch.int32) & 0xFFFF) for c in (cu, cv))
             else:
                 cu, cv = cu.contiguous(), cv.contiguous()
@@ -226,7 +229,7 @@ class _RawReader:
 
 
 def _npy_route(model, shape, batch: int) -> _Route:
-    """`interpolate_video`'s .npy route for uint8 frames of `shape` ([H,W] or [H,W,C])."""
+    """The .npy route for uint8 frames of `shape` ([H,W] or [H,W,C])."""
     row = int(np.prod(shape))
     if len(shape) == 2:
         h, w = shape
@@ -471,7 +474,8 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
 
 @torch.no_grad()
 def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode: str, n_frames=None) -> int:
-    """The resident form of `_run` (with a plan: one grid, one resample): the whole clip on the device.  n_frames: the
+    """The resident form of `_run`: the whole clip on the device as one chunk (flags once over every sample of the
+    packed rows, one run of the route, one hold at the full factor; with a plan: one grid, one resample).  n_frames: the
     clip's frame count where it is known up front (a regular file): the clip is then read into one array; a stream of
     unknown length is uploaded 64 frames at a time, so that the host never holds it twice."""
     dev = next(model.parameters()).device
@@ -549,15 +553,15 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
                            retime: str = "blend") -> int:
     """Y4M in (a path or a readable binary file: a pipe, `sys.stdin.buffer`) -> Y4M out (a path or a writable binary
     file), or a `.npy` path of the luma frames (grayscale network; the input must then be a regular file, whose frame
-    count a first pass reads).  Every route, header, refusal and result is that of `FrameInterpolator.interpolate_video`
-    on the same arguments, byte for byte, for any `chunk_frames` >= 1.  Returns the output frame count.  Every argument
+    count a first pass reads).  This is what `FrameInterpolator.interpolate_video` runs; the result is the same, byte
+    for byte, for any `chunk_frames` >= 1 and for None (the whole clip as one chunk, resident on the device).  The
+    output header has the input's `C` tag, rate x factor, and the input's `XCOLORRANGE` except on the 8-bit grayscale
+    route, which writes none.  Returns the output frame count.  Every argument
     is checked before anything is pinned, before any GPU work and before the output exists.  scene_log: a list that
     receives (scores float64, flags uint8) host arrays of each chunk's intervals (tests; costs a synchronise).
     fps / src_fps / time_depth / retime: frame-rate conversion (retime.py): the output has `fps` frames per second,
-    resampled from a 2**time_depth bisection; src_fps overrides the header's rate; factor stays 2.  With fps,
-    chunk_frames may be None: the whole clip is one chunk, resident on the device (`interpolate_video` without
-    chunk_frames)."""
-    thr, C = _check_common(factor, batch, chunk_frames, scene_cut, whole_ok=fps is not None)
+    resampled from a 2**time_depth bisection; src_fps overrides the header's rate; factor stays 2."""
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     npy_out = isinstance(dst, (str, os.PathLike)) and os.fspath(dst).lower().endswith(".npy")
     if npy_out:
@@ -610,10 +614,11 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
                            scene_cut: float | None = None, scene_log: list | None = None, fps=None, src_fps=None,
                            time_depth: int = 2, retime: str = "blend") -> int:
     """`.npy` stack in (uint8 [N,H,W] or [N,H,W,C], read through `np.load(mmap_mode="r")`) -> `.npy` out (written
-    through `np.lib.format.open_memmap`): byte for byte the file `interpolate_video` saves.  Returns the output frame
-    count.  fps / src_fps / time_depth / retime, and chunk_frames None with fps: as for `interpolate_y4m_stream`; a
-    .npy stack carries no rate, so `fps` needs `src_fps`."""
-    thr, C = _check_common(factor, batch, chunk_frames, scene_cut, whole_ok=fps is not None)
+    through `np.lib.format.open_memmap`, the file `np.save` would write; a name without `.npy` gets it).  An
+    [N,H,W,C] stack goes through the RGB network, or channel by channel through the grayscale one.  Returns the output
+    frame count.  fps / src_fps / time_depth / retime and chunk_frames None: as for `interpolate_y4m_stream`; a .npy
+    stack carries no rate, so `fps` needs `src_fps`."""
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     plan = _plan_of(fps, src_fps, None, depth)
     if plan is not None:
@@ -656,7 +661,7 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     output name, the size of a regular input file (a whole number of frames) - is checked before any GPU work and
     before the output exists; a pipe that ends inside a frame is an error at that point.  Returns the output frame
     count."""
-    thr, C = _check_common(factor, batch, chunk_frames, scene_cut, whole_ok=True)
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     if src_fps is None:
         raise ValueError("raw video carries no frame rate: pass src_fps")
     src_rate = _retime.parse_fps(src_fps)

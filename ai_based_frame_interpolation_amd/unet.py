@@ -361,29 +361,7 @@ class FrameInterpolationUNet(nn.Module):
         colour.py (matrix defaults to "bt709", a convention for HD video: Y4M does not carry it).  `out`: write there -
         uint8 [B, F] on the same device, every frame contiguous; the frames may lie apart (the video loop passes every
         second frame of its interleaved result)."""
-        from .colour import colour_flags, i420_frame_bytes
-        flags = colour_flags(siting, matrix, colour_range)
-        if self.frame_channels != 3:
-            raise RuntimeError("forward_yuv420 runs the RGB network (frame_channels=3); this model is grayscale")
-        h, w = int(height), int(width)
-        fb = i420_frame_bytes(h, w)
-        if frame1.dim() != 2 or frame1.shape != frame2.shape or frame1.shape[1] != fb:
-            raise RuntimeError(f"expected two [B,{fb}] tensors (packed I420 frames of {h}x{w}) of equal shape, got "
-                               f"{tuple(frame1.shape)} and {tuple(frame2.shape)}")
-        self._check_device_mode_dtype(frame1, frame2, (torch.uint8,))
-        f1, f2 = frame1.contiguous(), frame2.contiguous()
-        b = f1.shape[0]
-        prec = self._precision_code()
-        ctx = self._context(f1.device)
-        ws = self._workspace(ctx, f1.device, b, h, w, prec, yuv=True)
-        if out is None:
-            out = torch.empty_like(f1)
-        elif (out.dtype != torch.uint8 or out.shape != f1.shape or out.device != f1.device
-              or out.stride(1) != 1 or (b > 1 and out.stride(0) < fb)):
-            raise ValueError(f"out must be a uint8 {tuple(f1.shape)} tensor on {f1.device} whose frames are contiguous")
-        with torch.cuda.device(f1.device):
-            ctx.forward_yuv420(f1, f2, out, h, w, flags, prec, ws)
-        return out
+        return self._forward_packed("forward_yuv420", 8, frame1, frame2, height, width, out, siting, matrix, colour_range)
 
     @torch.no_grad()
     def forward_p10(self, frame1: torch.Tensor, frame2: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -417,30 +395,37 @@ class FrameInterpolationUNet(nn.Module):
         `fiunet_forward_yuv420p10`: YUV -> planar RGB, `forward_p10`, RGB -> YUV on device.  matrix
         also takes "bt2020".  The network interpolates code values, as it does for 8-bit video (no PQ / HLG
         linearisation).  Use fp16 (or bf16x2, fp32): bf16 is about 5 codes off.  `out`: as for `forward_yuv420`."""
-        from .colour import colour_flags, yuv420p10_frame_samples
-        flags = colour_flags(siting, matrix, colour_range, bits=10)
+        return self._forward_packed("forward_yuv420p10", 10, frame1, frame2, height, width, out, siting, matrix,
+                                    colour_range)
+
+    def _forward_packed(self, name, bits, frame1, frame2, height, width, out, siting, matrix, colour_range):
+        from .colour import colour_flags, i420_frame_bytes
+        dtype, kind = (torch.uint16, "4:2:0 10-bit") if bits == 10 else (torch.uint8, "I420")
+        flags = colour_flags(siting, matrix, colour_range, bits=bits)
         if self.frame_channels != 3:
-            raise RuntimeError("forward_yuv420p10 runs the RGB network (frame_channels=3); this model is grayscale")
+            raise RuntimeError(f"{name} runs the RGB network (frame_channels=3); this model is grayscale")
         h, w = int(height), int(width)
-        fs = yuv420p10_frame_samples(h, w)
+        fs = i420_frame_bytes(h, w)   # samples per packed 4:2:0 frame, at either depth
         if frame1.dim() != 2 or frame1.shape != frame2.shape or frame1.shape[1] != fs:
-            raise RuntimeError(f"expected two [B,{fs}] tensors (packed 4:2:0 10-bit frames of {h}x{w}) of equal shape, "
-                               f"got {tuple(frame1.shape)} and {tuple(frame2.shape)}")
-        self._check_device_mode_dtype(frame1, frame2, (torch.uint16,))
-        if not frame1.is_contiguous() or not frame2.is_contiguous():
-            raise ValueError("forward_yuv420p10 takes contiguous frames")
+            raise RuntimeError(f"expected two [B,{fs}] tensors (packed {kind} frames of {h}x{w}) of equal shape, got "
+                               f"{tuple(frame1.shape)} and {tuple(frame2.shape)}")
+        self._check_device_mode_dtype(frame1, frame2, (dtype,))
+        if bits == 8:
+            frame1, frame2 = frame1.contiguous(), frame2.contiguous()
+        elif not frame1.is_contiguous() or not frame2.is_contiguous():
+            raise ValueError(f"{name} takes contiguous frames")
         b = frame1.shape[0]
         prec = self._precision_code()
         ctx = self._context(frame1.device)
-        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=True)
+        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=bits == 10)
         if out is None:
             out = torch.empty_like(frame1)
-        elif (out.dtype != torch.uint16 or out.shape != frame1.shape or out.device != frame1.device
+        elif (out.dtype != dtype or out.shape != frame1.shape or out.device != frame1.device
               or out.stride(1) != 1 or (b > 1 and out.stride(0) < fs)):
-            raise ValueError(f"out must be a uint16 {tuple(frame1.shape)} tensor on {frame1.device} whose frames are "
-                             "contiguous")
+            raise ValueError(f"out must be a {str(dtype).split('.')[-1]} {tuple(frame1.shape)} tensor on "
+                             f"{frame1.device} whose frames are contiguous")
         with torch.cuda.device(frame1.device):
-            ctx.forward_yuv420p10(frame1, frame2, out, h, w, flags, prec, ws)
+            ctx.forward_yuv420(frame1, frame2, out, h, w, flags, prec, ws, bits)
         return out
 
     def _forward_surface(self, name, bits, frame1, frame2, height, width, layout, out, out_layout, siting, matrix,

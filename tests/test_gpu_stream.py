@@ -1,7 +1,8 @@
 """GPU (MI355X): streamed video (stream.py) against the resident whole-clip path.
 
-  1. byte identity of the output file of `interpolate_video(..., chunk_frames=k)` and the resident run: every Y4M and
-     .npy route, factor 2 / 4 / 8, scene_cut None / 10, chunk_frames 1 / 3 / 8 / > N, odd sizes, N = 1 and 2
+  1. byte identity of the output file of `interpolate_video(..., chunk_frames=k)` and the resident run (the same route
+     with the whole clip as one chunk): every Y4M and .npy route, factor 2 / 4 / 8, scene_cut None / 10, chunk_frames
+     1 / 3 / 8 / > N, odd sizes, N = 1 and 2; the output naming of the two calls
   2. scene cuts at a chunk's first interval, its last interval and its lookahead interval: streamed scores and flags
      equal scene.detect_cuts on the whole clip, and the held frames sit where the resident run holds them
   3. device memory bounded by the chunk: equal streamed peaks at N = 9 and N = 41, resident peaks far apart
@@ -136,6 +137,27 @@ def test_npy_stream_is_byte_identical(dev, models, tmp_path, fc, shape, n, facto
     fi = P.FrameInterpolator(model=models(fc, "bf16"), device=dev)
     ref, got = _both(fi, tmp_path, src, ".npy", factor, sc, cf)
     assert got == ref
+
+
+def test_resident_output_naming(dev, models, tmp_path):
+    """A whole-clip Y4M call writes a `.npy` stack of the luma frames to any name that does not end in `.y4m`, named as
+    np.save names it; a streamed call writes Y4M to every name but `.npy`."""
+    n, h, w = 3, 37, 53
+    src = str(tmp_path / "in.y4m")
+    frames = _y4m(src, n, h, w, "420jpeg", 8, seed=12)
+    fi = P.FrameInterpolator(model=models(1, "bf16"), device=dev)
+    assert fi.interpolate_video(src, str(tmp_path / "out.npy"), 2) == 2 * n - 1
+    assert fi.interpolate_video(src, str(tmp_path / "out.bin"), 2) == 2 * n - 1
+    assert sorted(p.name for p in tmp_path.iterdir() if p.name.startswith("out")) == ["out.bin.npy", "out.npy"]
+    assert (tmp_path / "out.bin.npy").read_bytes() == (tmp_path / "out.npy").read_bytes()
+    stack = np.load(tmp_path / "out.npy")
+    assert stack.dtype == np.uint8 and stack.shape == (2 * n - 1, h, w)
+    assert np.array_equal(stack[0::2], frames[:, :h * w].reshape(n, h, w))
+    assert fi.interpolate_video(src, str(tmp_path / "out2.bin"), 2, chunk_frames=2) == 2 * n - 1
+    assert not (tmp_path / "out2.bin.npy").exists()
+    out, hdr = IO.read_y4m_packed(str(tmp_path / "out2.bin"))
+    assert out.shape == (2 * n - 1, frames.shape[1]) and (hdr["height"], hdr["width"]) == (h, w)
+    assert np.array_equal(out[:, :h * w].reshape(-1, h, w), stack)
 
 
 # ---- 2. scene cuts across chunk edges -----------------------------------------------------------------------------

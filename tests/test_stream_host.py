@@ -221,6 +221,29 @@ def test_bad_colour_and_scene_arguments(tmp_path, no_gpu, kw, match):
     assert _no_output(tmp_path)
 
 
+@pytest.fixture
+def no_gpu_resident(no_gpu, monkeypatch):
+    """`no_gpu` for the whole-clip call: its engine, `stream._run_whole`, fails the test too."""
+    def boom(*a, **k):
+        raise AssertionError("GPU work started before the arguments were checked")
+    monkeypatch.setattr(stream, "_run_whole", boom)
+
+
+@pytest.mark.parametrize("tag,out,kw,match", [
+    ("422", "out.y4m", {}, "C422 is not supported by the RGB network"),
+    ("420jpeg", "out.npy", {}, r"written as \.y4m \(no \.npy output\)"),
+    ("420jpeg", "out.y4m", dict(matrix="bt2021"), "matrix"),
+    ("420jpeg", "out.y4m", dict(scene_cut=0), "scene_cut"),
+    ("420jpeg", "out.y4m", dict(factor=3), "factor"),
+])
+def test_resident_refusals_before_gpu_work(tmp_path, no_gpu_resident, tag, out, kw, match):
+    y, chroma = _planes(tag, 3, 6, 8, 8, 12)
+    _write_whole(str(tmp_path / "in.y4m"), tag, y, chroma, 8)
+    with pytest.raises(ValueError, match=match):
+        _fi(3).interpolate_video(str(tmp_path / "in.y4m"), str(tmp_path / out), **kw)
+    assert _no_output(tmp_path)
+
+
 def test_y4m_from_a_pipe_to_npy_is_refused(tmp_path, no_gpu):
     rfd, wfd = os.pipe()
     os.close(wfd)

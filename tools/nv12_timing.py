@@ -71,13 +71,11 @@ def _kernel_cases(dev, bits, b, h, w, set_bytes):
     rgb = [rnd((b, 3, h, w)) for _ in range(n_set)]
     flags = P.colour.colour_flags("mpeg2", "bt709", "limited", bits=bits)
     tight = resolve_layout(None, h, w)
-    dec420 = _native.yuv420p10_to_rgb_p10 if bits == 10 else _native.yuv420_to_rgb_u8
-    enc420 = _native.rgb_p10_to_yuv420p10 if bits == 10 else _native.rgb_to_yuv420_u8
 
     def planar(decode):
         if decode:
-            return _Rotate(lambda k: dec420(yuv[k][:, :fs], rgb[k], h, w, flags), n_set)
-        return _Rotate(lambda k: enc420(rgb[k], yuv[k][:, :fs], flags), n_set)
+            return _Rotate(lambda k: _native.yuv420_to_rgb(yuv[k][:, :fs], rgb[k], h, w, flags, bits), n_set)
+        return _Rotate(lambda k: _native.rgb_to_yuv420(rgb[k], yuv[k][:, :fs], flags, bits), n_set)
 
     def semi(decode, lay):
         n = lay.frame_stride
