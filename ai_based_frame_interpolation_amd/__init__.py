@@ -5,15 +5,16 @@ from .unet import FrameInterpolationUNet, GraphedForward, UNet, count_parameters
 from .inference import (  # noqa: F401
     FrameInterpolator, generate_multiple_intermediate_frames, interpolate_frames,
     interpolate_sequence, interpolate_sequence_host, interpolate_sequence_nv12, interpolate_sequence_p10,
-    interpolate_sequence_yuv420, interpolate_sequence_yuv420p10, load_model, postprocess_image,
-    preprocess_image, sequence_pair_fn,
+    interpolate_sequence_rgb_packed, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10, load_model,
+    postprocess_image, preprocess_image, sequence_pair_fn,
 )
 from .serving import InterpolationService  # noqa: F401
 from .colour import (  # noqa: F401
     SurfaceLayout, i420_frame_bytes, nv12_to_rgb, p010_to_rgb, rgb_to_nv12, rgb_to_p010, rgb_to_yuv420,
     rgb_to_yuv420p10, yuv420_to_rgb, yuv420p10_frame_samples, yuv420p10_to_rgb,
 )
-from . import colour, evaluation, metrics, optical_flow, retime, scene, serving, stream, synthetic, tiling, transport, video  # noqa: F401
+from .packed import PackedLayout  # noqa: F401
+from . import colour, evaluation, metrics, optical_flow, packed, retime, scene, serving, stream, synthetic, tiling, transport, video  # noqa: F401
 
 __all__ = [
     "FrameInterpolationUNet", "GraphedForward", "UNet", "count_parameters", "FrameInterpolator",
@@ -25,4 +26,5 @@ __all__ = [
     "load_model", "postprocess_image", "preprocess_image", "evaluation", "metrics", "tiling", "video",
     "InterpolationService", "serving", "synthetic", "scene", "stream", "retime",
     "SurfaceLayout", "nv12_to_rgb", "rgb_to_nv12", "p010_to_rgb", "rgb_to_p010", "interpolate_sequence_nv12",
+    "packed", "PackedLayout", "interpolate_sequence_rgb_packed",
 ]

@@ -44,6 +44,9 @@ SYMBOLS = (
     "fiunet_forward_yuv420p10",
     "fiunet_pair_sad_u8", "fiunet_pair_sad_p10", "fiunet_scene_cuts", "fiunet_hold_cut_frames",
     "fiunet_retime_u8", "fiunet_retime_p10",
+    # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
+    "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
+    "fiunet_forward_rgb_packed",
     "fiunet_nv12_to_rgb_u8", "fiunet_rgb_to_nv12_u8", "fiunet_workspace_bytes_nv12", "fiunet_forward_nv12",
     "fiunet_p010_to_rgb_p10", "fiunet_rgb_p10_to_p010", "fiunet_workspace_bytes_p010", "fiunet_forward_p010",
 )
@@ -60,6 +63,17 @@ def _surface(layout, frame_stride: int):
     if layout is None:
         return ctypes.byref(SurfaceLayout(0, 0, 0, frame_stride))
     return ctypes.byref(SurfaceLayout(layout.luma_pitch, layout.chroma_offset, layout.chroma_pitch, frame_stride))
+
+
+
+class PackedLayout(ctypes.Structure):
+    """include/fiunet.h: fiunet_packed_layout (packed RGB frames; both fields in bytes, 0 = tight)."""
+    _fields_ = [("row_pitch", ctypes.c_size_t), ("frame_stride", ctypes.c_size_t)]
+
+
+def _packed(layout, frame_stride: int):
+    """A resolved packed.PackedLayout with the frames `frame_stride` bytes apart -> the C struct."""
+    return ctypes.byref(PackedLayout(layout.row_pitch, frame_stride))
 
 _lib = None
 
@@ -161,6 +175,11 @@ def lib() -> ctypes.CDLL:
     L.fiunet_workspace_bytes_p010.restype = sz
     L.fiunet_forward_nv12.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cu, ci, vp, sz, vp]
     L.fiunet_forward_p010.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cu, ci, vp, sz, vp]
+    L.fiunet_packed_to_rgb_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    L.fiunet_rgb_to_packed_u8.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    L.fiunet_workspace_bytes_rgb_packed.argtypes = [vp, ci, ci, ci, ci]
+    L.fiunet_workspace_bytes_rgb_packed.restype = sz
+    L.fiunet_forward_rgb_packed.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, sz, vp]
     L.fiunet_debug_read_activation.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz,
                                                ctypes.POINTER(ci), vp]
     L.fiunet_metrics_workspace_bytes.argtypes = [ci, ci, ci]
@@ -352,6 +371,18 @@ class Context:
         check(fn(self._h, f1.data_ptr(), f2.data_ptr(), _surface(layout, f1.shape[1]), out.data_ptr(),
                  _surface(out_layout, st), b, h, w, colour, precision, workspace.data_ptr(), workspace.numel(), s), name)
 
+    def forward_rgb_packed(self, f1, f2, layout, out, out_layout, h, w, fmt, precision, workspace, stream=None):
+        """fiunet_forward_rgb_packed on uint8 [B, frame_stride] rows: f1, f2 contiguous in `layout`; `out` in
+        `out_layout`, its rows contiguous and possibly further apart.  The layouts are resolved packed.PackedLayout
+        tuples; fmt: the fiunet_packed_format code; the workspace is the 4:2:0 entry point's."""
+        b = f1.shape[0]
+        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        st = out.stride(0) if b > 1 else out.shape[1]
+        check(lib().fiunet_forward_rgb_packed(self._h, f1.data_ptr(), f2.data_ptr(), _packed(layout, f1.shape[1]),
+                                              out.data_ptr(), _packed(out_layout, st), b, h, w, fmt, precision,
+                                              workspace.data_ptr(), workspace.numel(), s),
+              "fiunet_forward_rgb_packed")
+
     def profile_enable(self, on: bool):
         check(lib().fiunet_profile_enable(self._h, 1 if on else 0), "fiunet_profile_enable")
 
@@ -454,6 +485,31 @@ def rgb_to_surface(rgb: "torch.Tensor", out: "torch.Tensor", layout, colour: int
     fn, name = ((lib().fiunet_rgb_p10_to_p010, "fiunet_rgb_p10_to_p010") if bits == 10 else
                 (lib().fiunet_rgb_to_nv12_u8, "fiunet_rgb_to_nv12_u8"))
     check(fn(rgb.data_ptr(), out.data_ptr(), _surface(layout, st), b, h, w, colour, s), name)
+
+
+def _row_stride(t: "torch.Tensor") -> int:
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def packed_to_rgb(frames: "torch.Tensor", layout, out: "torch.Tensor", alpha, h: int, w: int, fmt: int) -> None:
+    """fiunet_packed_to_rgb_u8: uint8 [B, frame_stride] packed frames (rows contiguous, any row stride) in the resolved
+    `layout` -> planar RGB [B, 3, h, w]; alpha: None, or the contiguous [B, h, w] tensor the alpha plane goes to."""
+    s = torch.cuda.current_stream(frames.device).cuda_stream
+    check(lib().fiunet_packed_to_rgb_u8(frames.data_ptr(), _packed(layout, _row_stride(frames)), out.data_ptr(),
+                                        None if alpha is None else alpha.data_ptr(), frames.shape[0], h, w, fmt, s),
+          "fiunet_packed_to_rgb_u8")
+
+
+def rgb_to_packed(rgb: "torch.Tensor", out: "torch.Tensor", layout, alphas, alpha_layout, fmt: int) -> None:
+    """fiunet_rgb_to_packed_u8: planar RGB [B, 3, h, w] contiguous -> uint8 [B, frame_stride] packed frames (rows
+    contiguous, any row stride) in the resolved `layout`; alphas: a tuple of 0, 1 or 2 packed tensors of one row stride
+    in the resolved `alpha_layout`."""
+    b, _, h, w = rgb.shape
+    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    a = [t.data_ptr() for t in alphas] + [None, None]
+    al = _packed(alpha_layout, _row_stride(alphas[0])) if alphas else None
+    check(lib().fiunet_rgb_to_packed_u8(rgb.data_ptr(), out.data_ptr(), _packed(layout, _row_stride(out)), a[0], a[1],
+                                        al, b, h, w, fmt, s), "fiunet_rgb_to_packed_u8")
 
 
 def pair_sad(frames: "torch.Tensor", sums: "torch.Tensor", bits: int) -> None:

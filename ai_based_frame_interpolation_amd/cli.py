@@ -2,7 +2,7 @@
 
 The reference's `main.py video` flags (--input, --output, --factor, --model, --device), plus --precision, --matrix,
 --siting, --scene-cut, --batch, --chunk-frames, the frame-rate conversion's --fps, --src-fps, --time-depth and
---retime, and --raw / --size for headerless NV12 video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
+--retime, and --raw / --size for headerless NV12 or packed RGB video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
 the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 
     ffmpeg -i in.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - \\
@@ -17,6 +17,14 @@ decoders and encoders use, converted on the device without a repack (DESIGN.md 3
     ffmpeg -i in.mkv -f rawvideo -pix_fmt nv12 - | python -m ai_based_frame_interpolation_amd.cli video --input - \\
         --output - --raw nv12 --size 1920x1080 --src-fps 24 --model rgb.pth | \\
         ffmpeg -f rawvideo -pix_fmt nv12 -s 1920x1080 -r 48 -i - out.mkv
+
+`--raw rgb24` (or bgr24, rgba, bgra) does the same for packed RGB frames - screen capture, renders, image sequences -
+which keep their colour: no chroma subsampling and no colour matrix on the way (--matrix and --siting
+are not used; the alpha of an inserted rgba / bgra frame is the rounded average of its neighbours'):
+
+    ffmpeg -i capture.mkv -f rawvideo -pix_fmt rgb24 - | python -m ai_based_frame_interpolation_amd.cli video \\
+        --input - --output - --raw rgb24 --size 1920x1080 --src-fps 30 --model rgb.pth | \\
+        ffmpeg -f rawvideo -pix_fmt rgb24 -s 1920x1080 -r 60 -i - out.mkv
 
 Standard output then carries nothing but video: the model-loading lines go to standard error.  The network (grayscale
 2->1 or RGB 6->3) is read from the checkpoint.
@@ -91,8 +99,8 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--time-depth", type=int, default=2, choices=(1, 2, 3, 4), help="Bisection levels under --fps")
     v.add_argument("--retime", default="blend", choices=retime.MODES,
                    help="How --fps picks between the two bisection frames around an output time")
-    v.add_argument("--raw", default=None, choices=("nv12",),
-                   help="Headerless raw video in and out (tight NV12 frames); needs --size and --src-fps")
+    v.add_argument("--raw", default=None, choices=("nv12", "rgb24", "bgr24", "rgba", "bgra"),
+                   help="Headerless raw video in and out (tight NV12 or packed RGB frames); needs --size and --src-fps")
     v.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
     return ap
 

@@ -12,6 +12,7 @@
 #include "conv3x3_kwave.hip.h"
 #include "metrics.hip.h"
 #include "colour.hip.h"
+#include "packed.hip.h"
 #include "scene.hip.h"
 #include "retime.hip.h"
 
@@ -1689,6 +1690,148 @@ int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t*
     if ((rc = fiunet_p010_to_rgb_p10(frame2, in_layout, b, B, H, W, colour, stream))) return rc;
     if ((rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
     return fiunet_rgb_p10_to_p010(o, out, out_layout, B, H, W, colour, stream);
+}
+
+// ---- packed RGB frames: rgb24 / bgr24 / rgba / bgra, rows a pitch apart, <-> planar RGB ----
+static int packed_bpp(int format)
+{
+    return format == FIUNET_PACKED_RGB24 || format == FIUNET_PACKED_BGR24 ? 3
+         : format == FIUNET_PACKED_RGBA || format == FIUNET_PACKED_BGRA ? 4 : 0;
+}
+
+// The caller's layout (NULL or zero fields = tight) -> the resolved one, refused before any launch where it cannot hold
+// an H x W frame of bpp bytes per pixel.  Every quantity in bytes.
+static int resolve_packed(const fiunet_packed_layout* l, int H, int W, int bpp, PackedLayout* pl)
+{
+    const size_t row = (size_t)W * bpp, big = (size_t)1 << 40;   // (keeps every product below in range)
+    pl->row_pitch = l && l->row_pitch ? l->row_pitch : row;
+    if (pl->row_pitch > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
+    pl->frame_stride = l && l->frame_stride ? l->frame_stride : (size_t)H * pl->row_pitch;
+    if (pl->frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
+    if (pl->row_pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: row_pitch < W*bpp");
+    if (pl->frame_stride < (size_t)(H - 1) * pl->row_pitch + row)
+        return fail(FIUNET_ERR_INVALID_ARG, "packed layout: frame_stride does not cover the last row");
+    return FIUNET_OK;
+}
+
+static int check_packed_args(const void* in, const void* out, int B, int H, int W, int format)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (!packed_bpp(format)) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    return FIUNET_OK;
+}
+
+// dword and 16-byte packed accesses, uchar4 plane accesses: W and every pitch, stride and base a multiple of 4 bytes
+static bool packed_vec(int W, const PackedLayout& l, uintptr_t bases)
+{
+    return W % 4 == 0 && (l.row_pitch | l.frame_stride) % 4 == 0 && (bases & 3) == 0;
+}
+
+extern "C++" {   // (templates over the format, inside this file's extern "C" part)
+template <int BPP, bool SWAP>
+static void launch_packed_to_rgb(bool vec, dim3 grid, hipStream_t st, const uint8_t* in, PackedLayout li, uint8_t* out,
+                                 uint8_t* alpha, int H, int W)
+{
+    if (vec)
+        hipLaunchKernelGGL((packed_to_rgb_kernel<BPP, SWAP, true>), grid, dim3(kColourBlock), 0, st, in, li, out, alpha, H, W);
+    else
+        hipLaunchKernelGGL((packed_to_rgb_kernel<BPP, SWAP, false>), grid, dim3(kColourBlock), 0, st, in, li, out, alpha, H, W);
+}
+
+template <int BPP, bool SWAP>
+static void launch_rgb_to_packed(bool vec, dim3 grid, hipStream_t st, const uint8_t* in, uint8_t* out, PackedLayout lo,
+                                 const uint8_t* a1, const uint8_t* a2, PackedLayout la, int H, int W)
+{
+    if (vec)
+        hipLaunchKernelGGL((rgb_to_packed_kernel<BPP, SWAP, true>), grid, dim3(kColourBlock), 0, st, in, out, lo, a1, a2, la, H, W);
+    else
+        hipLaunchKernelGGL((rgb_to_packed_kernel<BPP, SWAP, false>), grid, dim3(kColourBlock), 0, st, in, out, lo, a1, a2, la, H, W);
+}
+}  // extern "C++"
+
+int fiunet_packed_to_rgb_u8(const uint8_t* in, const fiunet_packed_layout* in_layout, uint8_t* out_rgb,
+                            uint8_t* alpha_out, int B, int H, int W, int format, void* stream)
+{
+    int rc;
+    if ((rc = check_packed_args(in, out_rgb, B, H, W, format))) return rc;
+    const int bpp = packed_bpp(format);
+    if (alpha_out && bpp != 4) return fail(FIUNET_ERR_INVALID_ARG, "alpha_out: the format has no alpha byte");
+    PackedLayout li;
+    if ((rc = resolve_packed(in_layout, H, W, bpp, &li))) return rc;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
+    const bool vec = packed_vec(W, li, (uintptr_t)in | (uintptr_t)out_rgb | (uintptr_t)alpha_out);
+    hipStream_t st = (hipStream_t)stream;
+    switch (format) {
+    case FIUNET_PACKED_RGB24: launch_packed_to_rgb<3, false>(vec, grid, st, in, li, out_rgb, alpha_out, H, W); break;
+    case FIUNET_PACKED_BGR24: launch_packed_to_rgb<3, true>(vec, grid, st, in, li, out_rgb, alpha_out, H, W); break;
+    case FIUNET_PACKED_RGBA: launch_packed_to_rgb<4, false>(vec, grid, st, in, li, out_rgb, alpha_out, H, W); break;
+    default: launch_packed_to_rgb<4, true>(vec, grid, st, in, li, out_rgb, alpha_out, H, W); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_rgb_to_packed_u8(const uint8_t* in_rgb, uint8_t* out, const fiunet_packed_layout* out_layout,
+                            const uint8_t* alpha1, const uint8_t* alpha2, const fiunet_packed_layout* alpha_layout,
+                            int B, int H, int W, int format, void* stream)
+{
+    int rc;
+    if ((rc = check_packed_args(in_rgb, out, B, H, W, format))) return rc;
+    const int bpp = packed_bpp(format);
+    if ((alpha1 || alpha2) && bpp != 4) return fail(FIUNET_ERR_INVALID_ARG, "alpha source: the format has no alpha byte");
+    if (alpha2 && !alpha1) return fail(FIUNET_ERR_INVALID_ARG, "alpha2 without alpha1");
+    PackedLayout lo, la;
+    if ((rc = resolve_packed(out_layout, H, W, bpp, &lo))) return rc;
+    if ((rc = resolve_packed(alpha_layout, H, W, bpp, &la))) return rc;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
+    const bool vec = packed_vec(W, lo, (uintptr_t)in_rgb | (uintptr_t)out | (uintptr_t)alpha1 | (uintptr_t)alpha2) &&
+                     (!alpha1 || packed_vec(W, la, 0));
+    hipStream_t st = (hipStream_t)stream;
+    switch (format) {
+    case FIUNET_PACKED_RGB24: launch_rgb_to_packed<3, false>(vec, grid, st, in_rgb, out, lo, alpha1, alpha2, la, H, W); break;
+    case FIUNET_PACKED_BGR24: launch_rgb_to_packed<3, true>(vec, grid, st, in_rgb, out, lo, alpha1, alpha2, la, H, W); break;
+    case FIUNET_PACKED_RGBA: launch_rgb_to_packed<4, false>(vec, grid, st, in_rgb, out, lo, alpha1, alpha2, la, H, W); break;
+    default: launch_rgb_to_packed<4, true>(vec, grid, st, in_rgb, out, lo, alpha1, alpha2, la, H, W); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+size_t fiunet_workspace_bytes_rgb_packed(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return fiunet_workspace_bytes_yuv420(ctx, B, H, W, precision);
+}
+
+int fiunet_forward_rgb_packed(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
+                              const fiunet_packed_layout* in_layout, uint8_t* out, const fiunet_packed_layout* out_layout,
+                              int B, int H, int W, int format, int precision, void* workspace, size_t workspace_bytes,
+                              void* stream)
+{
+    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3)
+        return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_rgb_packed needs the RGB network (frame_channels 3)");
+    const int bpp = packed_bpp(format);
+    if (!bpp) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
+    const size_t need = fiunet_workspace_bytes_rgb_packed(ctx, B, H, W, precision);
+    if (need == 0) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    int rc;
+    PackedLayout pl;   // both layouts are refused here, before the first launch
+    if ((rc = resolve_packed(in_layout, H, W, bpp, &pl)) || (rc = resolve_packed(out_layout, H, W, bpp, &pl))) return rc;
+    // [fiunet_forward_u8's workspace | frame1 RGB | frame2 RGB | output RGB], uint8 planar [B, 3, H, W] each
+    const size_t base = align256(fiunet_workspace_bytes_u8(ctx, B, H, W, precision));
+    const size_t rgb = align256((size_t)B * 3 * H * W);
+    uint8_t* a = (uint8_t*)workspace + base;
+    uint8_t* b = a + rgb;
+    uint8_t* o = b + rgb;
+    if ((rc = fiunet_packed_to_rgb_u8(frame1, in_layout, a, NULL, B, H, W, format, stream))) return rc;
+    if ((rc = fiunet_packed_to_rgb_u8(frame2, in_layout, b, NULL, B, H, W, format, stream))) return rc;
+    if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
+    const bool alpha = bpp == 4;   // the inserted frame's alpha: the rounded average of its neighbours'
+    return fiunet_rgb_to_packed_u8(o, out, out_layout, alpha ? frame1 : NULL, alpha ? frame2 : NULL, in_layout, B, H, W,
+                                   format, stream);
 }
 
 static inline int ssim_tiles(int H, int W, int* tiles_x)

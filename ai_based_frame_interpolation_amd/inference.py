@@ -271,6 +271,24 @@ def interpolate_sequence_nv12(model, frames: torch.Tensor, height: int, width: i
 
 
 @torch.no_grad()
+def interpolate_sequence_rgb_packed(model, frames: torch.Tensor, height: int, width: int, format: str, batch: int = 8, *,
+                                    scene_cut: float | None = None) -> torch.Tensor:
+    """factor-2 video loop of the RGB network on packed RGB video: device uint8 [N, F] tight "rgb24" / "bgr24" / "rgba" /
+    "bgra" frames of height x width (F = H*W*bpp) -> [2N-1, F] = F0, M0, F1, ..., F(N-1), Mi =
+    model.forward_rgb_packed(Fi, Fi+1, format=format): no colour conversion anywhere.  The same contract as
+    `interpolate_sequence_yuv420`: originals byte for byte, middles written in place, a ragged last chunk padded.  The
+    scene-cut sums run over every byte of a frame: for rgb24 / bgr24 they are those of the same frames as planar RGB; for
+    rgba / bgra they include the alpha byte (a quarter of the bytes; constant alpha adds nothing to a sum and lowers
+    every percentage by a quarter)."""
+    thr = scene.check_threshold(scene_cut)
+    h, w = int(height), int(width)
+
+    def fwd(a, b, out=None):
+        return model.forward_rgb_packed(a.contiguous(), b.contiguous(), h, w, format=format, out=out)
+    return _sequence(model, frames, fwd, h, w, batch, thr, 8)
+
+
+@torch.no_grad()
 def interpolate_sequence_p10(model, frames: torch.Tensor, batch: int = 8, *, scene_cut: float | None = None) -> torch.Tensor:
     """factor-2 video loop on 10-bit frames: device uint16 [N,H,W] (or [N,C,H,W]) 10-bit codes -> [2N-1, ...] = F0, M0,
     F1, ..., F(N-1), where Mi = model.forward_p10(Fi, Fi+1).  Both networks.  The originals are copied sample for
@@ -443,7 +461,10 @@ class FrameInterpolator:
         surfaces hold; they go through the RGB network on the device without a repack (`interpolate_sequence_nv12`,
         stream.interpolate_raw_stream).  width, height and src_fps are then required (the stream has no
         header); siting None means "mpeg2", the range is limited; factor, fps, scene_cut and chunk_frames work as for
-        Y4M."""
+        Y4M.  raw "rgb24", "bgr24", "rgba" or "bgra": headerless tight packed RGB frames (`ffmpeg -f rawvideo -pix_fmt
+        rgb24`), through the RGB network with their colour as it is (`interpolate_sequence_rgb_packed`):
+        matrix and siting are not used; the alpha of an inserted rgba / bgra frame is the rounded average of its
+        neighbours', and scene_cut then counts the alpha bytes too."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")

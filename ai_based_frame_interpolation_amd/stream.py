@@ -31,6 +31,8 @@ Memory is bounded by the chunk, never by the clip (C = chunk_frames, F = factor,
 Raw video (`interpolate_raw_stream`): headerless tight NV12 frames, what `ffmpeg -f rawvideo -pix_fmt
 nv12` writes and reads, through the same engine with `interpolate_sequence_nv12` as the level: factor, fps, scene_cut
 and chunk_frames work as they do for Y4M (the retime and hold kernels see packed rows of samples, whatever their order).
+The packed RGB formats rgb24 / bgr24 / rgba / bgra take the same route with
+`interpolate_sequence_rgb_packed` as the level and no colour conversion.
 
 With `fps=` (source / target rate = p / q, G = 2**time_depth) F is G in the levels, a chunk's result is its
 R = ceil(C x q / p) + 1 resampled frames, and the device holds them beside the grid:
@@ -48,11 +50,11 @@ import threading
 import numpy as np
 import torch
 
-from . import colour, imageio_lite, scene
+from . import colour, imageio_lite, packed, scene
 from . import retime as _retime
 from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
-                        interpolate_sequence_nv12, interpolate_sequence_p10, interpolate_sequence_yuv420,
-                        interpolate_sequence_yuv420p10)
+                        interpolate_sequence_nv12, interpolate_sequence_p10, interpolate_sequence_rgb_packed,
+                        interpolate_sequence_yuv420, interpolate_sequence_yuv420p10)
 
 R_IN, R_OUT = 3, 2   # pinned input / output slots in the rings
 
@@ -172,12 +174,13 @@ def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
     return _Route(bits, row, out_row, run)
 
 
-RAW_FORMATS = ("nv12",)
+RAW_FORMATS = ("nv12", "rgb24", "bgr24", "rgba", "bgra")
 
 
 def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, siting) -> _Route:
-    """The route of headerless raw video (`raw`: "nv12", tight frames), with its refusals.  Nothing in the stream says
-    how it was made: siting None is "mpeg2" (what decoders produce) and the range is limited."""
+    """The route of headerless raw video (`raw`: one of RAW_FORMATS, tight frames), with its refusals.  Nothing in the
+    stream says how it was made: for "nv12" siting None is "mpeg2" (what decoders produce) and the range is limited.
+    The packed RGB formats (packed.FORMATS) have no colour conversion: matrix and siting are not used."""
     if raw not in RAW_FORMATS:
         raise ValueError(f"raw must be one of {list(RAW_FORMATS)} (or None: Y4M / .npy), got {raw!r}")
     for name, v in (("height", height), ("width", width)):
@@ -190,6 +193,14 @@ def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, sit
     if npy_out:
         raise ValueError(f"raw {raw} video through the RGB network is written as raw {raw} (no .npy output)")
     h, w = int(height), int(width)
+    if raw in packed.FORMATS:
+        row = packed.frame_bytes(raw, h, w)
+
+        def run_packed(d, factor):
+            for _ in range(_levels(factor)):
+                d = interpolate_sequence_rgb_packed(model, d, h, w, raw, batch)
+            return d
+        return _Route(8, row, row, run_packed)
     opts = dict(siting="mpeg2" if siting is None else siting, matrix=matrix, colour_range="limited")
     colour.colour_flags(**opts)
     row = colour.i420_frame_bytes(h, w)
@@ -654,7 +665,8 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
                            fps=None, src_fps=None, time_depth: int = 2, retime: str = "blend") -> int:
     """Headerless raw video in (a path or a readable binary file: a pipe) -> the same format out (a path or a writable
     binary file): tight NV12 frames of height x width (`ffmpeg ... -f rawvideo -pix_fmt nv12 -`) through the RGB
-    network, `interpolate_sequence_nv12` per level.  factor, scene_cut, chunk_frames (None: the whole clip resident)
+    network, `interpolate_sequence_nv12` per level; or, with raw "rgb24" / "bgr24" / "rgba" / "bgra", tight packed RGB
+    frames (`-pix_fmt rgb24`), `interpolate_sequence_rgb_packed` per level, where matrix and siting are not used.  factor, scene_cut, chunk_frames (None: the whole clip resident)
     and fps / time_depth / retime as for `interpolate_y4m_stream`; the stream carries no rate, so src_fps is required
     (with fps it sets the resampling; the output has fps, or src_fps x factor, frames per second - pass that rate to
     whatever reads the result).  siting None is "mpeg2", the range limited.  Every argument - the model's network, the

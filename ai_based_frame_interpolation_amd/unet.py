@@ -487,6 +487,51 @@ class FrameInterpolationUNet(nn.Module):
                                      matrix, colour_range)
 
     @torch.no_grad()
+    def forward_rgb_packed(self, frame1: torch.Tensor, frame2: torch.Tensor, height: int, width: int, *,
+                           format: str = "rgb24", layout=None, out: torch.Tensor | None = None,
+                           out_layout=None) -> torch.Tensor:
+        """The RGB network on packed RGB frames: uint8 "rgb24" / "bgr24" / "rgba" / "bgra" frames in (interleaved pixels:
+        raw video, screen grabs, renders, `cv2.imread` images) -> interpolated frames of the same format,
+        `fiunet_forward_rgb_packed`: bit for bit `packed.packed_to_rgb` on both -> `forward_u8` ->
+        `packed.rgb_to_packed(alpha_from=(frame1, frame2))`, with no colour conversion at all.  The alpha
+        of rgba / bgra does not go through the network: the result's is the rounded average of the inputs'.  layout /
+        out_layout: a `packed.PackedLayout` (row pitch and frame stride in bytes) or None for tight frames; the tensors
+        are [B, frame_stride], [B, H*W*bpp] when tight.  `out`: write there - frames contiguous, possibly further apart;
+        bytes outside the used columns and between frames are left untouched."""
+        from .packed import FORMATS, resolve_layout
+        if format not in FORMATS:
+            raise ValueError(f"format must be one of {list(FORMATS)}, got {format!r}")
+        code = FORMATS[format][0]
+        if self.frame_channels != 3:
+            raise RuntimeError("forward_rgb_packed runs the RGB network (frame_channels=3); this model is grayscale")
+        h, w = int(height), int(width)
+        lay = resolve_layout(layout, format, h, w)
+        olay = resolve_layout(out_layout, format, h, w)
+        if (not isinstance(frame1, torch.Tensor) or not isinstance(frame2, torch.Tensor) or frame1.dim() != 2
+                or frame1.shape != frame2.shape or frame1.shape[1] != lay.frame_stride):
+            raise RuntimeError(f"expected two [B,{lay.frame_stride}] tensors (packed {format} frames of {h}x{w}) of "
+                               f"equal shape, got {tuple(getattr(frame1, 'shape', ()))} and "
+                               f"{tuple(getattr(frame2, 'shape', ()))}")
+        self._check_device_mode_dtype(frame1, frame2, (torch.uint8,))
+        if not frame1.is_contiguous() or not frame2.is_contiguous():
+            raise ValueError("forward_rgb_packed takes contiguous frames")
+        b = frame1.shape[0]
+        prec = self._precision_code()
+        ctx = self._context(frame1.device)
+        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True)
+        shape = (b, olay.frame_stride)
+        if out is None:
+            # (a pitched frame has bytes no pixel covers: they are never written, so a new one starts as zeros)
+            out = (torch.empty if olay == resolve_layout(None, format, h, w) else torch.zeros)(
+                shape, dtype=torch.uint8, device=frame1.device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != frame1.device
+              or out.stride(1) != 1 or (b > 1 and out.stride(0) < olay.frame_stride)):
+            raise ValueError(f"out must be a uint8 {shape} tensor on {frame1.device} whose frames are contiguous")
+        with torch.cuda.device(frame1.device):
+            ctx.forward_rgb_packed(frame1, frame2, lay, out, olay, h, w, code, prec, ws)
+        return out
+
+    @torch.no_grad()
     def debug_activations(self, frame1, frame2, taps=None, with_up=False):
         """Parity-test hook: run one forward keeping every stage and return
         ({tap name: fp32 NCHW tensor}, output).  with_up: also the four upsampled + padded halves

@@ -29,7 +29,10 @@ extern "C" {
                                      (fiunet_retime_u8, fiunet_retime_p10), backwards-compatible; v8 also, added the same
                                      way: NV12 / P010 decoder surfaces (fiunet_surface_layout, fiunet_nv12_to_rgb_u8,
                                      fiunet_rgb_to_nv12_u8, fiunet_forward_nv12, fiunet_p010_to_rgb_p10,
-                                     fiunet_rgb_p10_to_p010, fiunet_forward_p010 and the two workspace queries) */
+                                     fiunet_rgb_p10_to_p010, fiunet_forward_p010 and the two workspace queries); v8 also, added
+                                     the same way: packed RGB frames (fiunet_packed_format, fiunet_packed_layout,
+                                     fiunet_packed_to_rgb_u8, fiunet_rgb_to_packed_u8, fiunet_forward_rgb_packed and its
+                                     workspace query) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -305,6 +308,50 @@ int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t*
                         const fiunet_surface_layout* in_layout, uint16_t* out, const fiunet_surface_layout* out_layout,
                         int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
                         void* stream);
+
+/* Packed RGB frames (ABI v8, added without a version bump: nothing existing changed): interleaved
+ * pixels, what `ffmpeg -f rawvideo -pix_fmt rgb24 | bgr24 | rgba | bgra` pipes and what a screen grab, a render or an
+ * image library (BGR rows a line size apart) leaves in memory.  They reach the RGB network with their colour as it is:
+ * no chroma subsampling, no colour matrix.  A pixel is 3 or 4 consecutive bytes in the order of the format's name. */
+enum fiunet_packed_format {
+    FIUNET_PACKED_RGB24 = 0,  /* R G B */
+    FIUNET_PACKED_BGR24 = 1,  /* B G R */
+    FIUNET_PACKED_RGBA = 2,   /* R G B A */
+    FIUNET_PACKED_BGRA = 3    /* B G R A */
+};
+/* Layout in BYTES, bpp = 3 or 4 by format: a frame is H rows `row_pitch` apart, each W*bpp bytes of pixels; frames are
+ * `frame_stride` apart.  A field that is 0 takes its tight value (row_pitch = W*bpp, frame_stride = H*row_pitch); a NULL
+ * layout is the tight one.  FIUNET_ERR_INVALID_ARG, before any launch: row_pitch < W*bpp, or frame_stride <
+ * (H-1)*row_pitch + W*bpp.  Bytes between W*bpp and row_pitch, and between frames, are never read and never written. */
+typedef struct fiunet_packed_layout {
+    size_t row_pitch, frame_stride;
+} fiunet_packed_layout;
+/* Packed frames -> planar RGB uint8 [B, 3, H, W] (the layout fiunet_forward_u8 takes), a move of bytes.  alpha_out: NULL,
+ * or (4-byte formats only) where the alpha plane uint8 [B, H, W] goes.  With W, both layout values and every base a
+ * multiple of 4 bytes a thread moves its 4 pixels as three dword (bpp 3) or one 16-byte (bpp 4) access and one 4-byte
+ * access per plane; otherwise byte by byte.  Device pointers; any H, W >= 1; asynchronous on `stream`; no allocation,
+ * no synchronisation.  Errors as for the surface entry points: NULL or an unknown format FIUNET_ERR_INVALID_ARG, a bad
+ * shape FIUNET_ERR_BAD_SHAPE. */
+int fiunet_packed_to_rgb_u8(const uint8_t* in, const fiunet_packed_layout* in_layout, uint8_t* out_rgb,
+                            uint8_t* alpha_out, int B, int H, int W, int format, void* stream);
+/* The inverse.  The fourth byte of a 4-byte format: 255 with alpha1 = alpha2 = NULL; a copy of alpha1's alpha byte with
+ * alpha1 alone; (a1 + a2 + 1) >> 1 with both.  alpha1 / alpha2 are packed frames of `format`, both in `alpha_layout`
+ * (NULL: tight), which need not be `out_layout`.  3-byte formats take no alpha source (FIUNET_ERR_INVALID_ARG), and so
+ * does alpha2 without alpha1. */
+int fiunet_rgb_to_packed_u8(const uint8_t* in_rgb, uint8_t* out, const fiunet_packed_layout* out_layout,
+                            const uint8_t* alpha1, const uint8_t* alpha2, const fiunet_packed_layout* alpha_layout,
+                            int B, int H, int W, int format, void* stream);
+/* Workspace of fiunet_forward_rgb_packed: that of fiunet_forward_yuv420. */
+size_t fiunet_workspace_bytes_rgb_packed(const fiunet_ctx* ctx, int B, int H, int W, int precision);
+/* The RGB network on packed frames: frame1 and frame2 in `in_layout`, the B interpolated frames to `out` in
+ * `out_layout`.  Bit for bit fiunet_packed_to_rgb_u8 (both inputs) -> fiunet_forward_u8_strided ->
+ * fiunet_rgb_to_packed_u8 with frame1 and frame2 as the alpha sources (4-byte formats: the inserted frame's alpha is the
+ * rounded average of its neighbours'); both layouts are checked before the first launch.  FIUNET_ERR_UNSUPPORTED on a
+ * context with frame_channels != 3.  Neither allocates nor synchronises. */
+int fiunet_forward_rgb_packed(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
+                              const fiunet_packed_layout* in_layout, uint8_t* out, const fiunet_packed_layout* out_layout,
+                              int B, int H, int W, int format, int precision, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* Scene cuts in the video loops (ABI v8, added without a version bump: nothing existing changed).  The reference has
  * no video loop; the definition is our own.  For N frames and the N-1 intervals i between F[i] and
