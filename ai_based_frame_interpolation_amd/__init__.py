@@ -14,7 +14,7 @@ from .colour import (  # noqa: F401
     rgb_to_yuv420p10, yuv420_to_rgb, yuv420p10_frame_samples, yuv420p10_to_rgb,
 )
 from .packed import PackedLayout  # noqa: F401
-from . import colour, evaluation, metrics, optical_flow, packed, retime, scene, serving, stream, synthetic, tiling, transport, video  # noqa: F401
+from . import colour, evaluation, holdout, metrics, optical_flow, packed, retime, scene, serving, stream, synthetic, tiling, transport, video  # noqa: F401
 
 __all__ = [
     "FrameInterpolationUNet", "GraphedForward", "UNet", "count_parameters", "FrameInterpolator",
@@ -26,5 +26,5 @@ __all__ = [
     "load_model", "postprocess_image", "preprocess_image", "evaluation", "metrics", "tiling", "video",
     "InterpolationService", "serving", "synthetic", "scene", "stream", "retime",
     "SurfaceLayout", "nv12_to_rgb", "rgb_to_nv12", "p010_to_rgb", "rgb_to_p010", "interpolate_sequence_nv12",
-    "packed", "PackedLayout", "interpolate_sequence_rgb_packed",
+    "packed", "PackedLayout", "interpolate_sequence_rgb_packed", "holdout",
 ]

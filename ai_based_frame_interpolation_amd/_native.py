@@ -38,6 +38,7 @@ SYMBOLS = (
     "fiunet_postprocess_u8", "fiunet_debug_read_activation", "fiunet_profile_enable",
     "fiunet_profile_read", "fiunet_metrics_workspace_bytes", "fiunet_psnr_u8", "fiunet_ssim_u8",
     "fiunet_ssim_gauss_workspace_bytes", "fiunet_ssim_gauss_f32",
+    "fiunet_plane_metrics_workspace_bytes", "fiunet_plane_psnr", "fiunet_plane_ssim",
     "fiunet_yuv420_to_rgb_u8", "fiunet_rgb_to_yuv420_u8", "fiunet_workspace_bytes_yuv420", "fiunet_forward_yuv420",
     "fiunet_preprocess_p10", "fiunet_postprocess_p10", "fiunet_workspace_bytes_p10", "fiunet_forward_p10",
     "fiunet_yuv420p10_to_rgb_p10", "fiunet_rgb_p10_to_yuv420p10", "fiunet_workspace_bytes_yuv420p10",
@@ -186,6 +187,10 @@ def lib() -> ctypes.CDLL:
     L.fiunet_metrics_workspace_bytes.restype = sz
     L.fiunet_psnr_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp, sz, vp]
     L.fiunet_ssim_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp, sz, vp]
+    L.fiunet_plane_metrics_workspace_bytes.argtypes = [ci, ci, ci]
+    L.fiunet_plane_metrics_workspace_bytes.restype = sz
+    L.fiunet_plane_psnr.argtypes = [vp, sz, sz, vp, sz, sz, ci, ci, ci, ci, vp, vp, vp, sz, vp]
+    L.fiunet_plane_ssim.argtypes = [vp, sz, sz, vp, sz, sz, ci, ci, ci, ci, vp, vp, sz, vp]
     L.fiunet_ssim_gauss_workspace_bytes.argtypes = [ci, ci, ci]
     L.fiunet_ssim_gauss_workspace_bytes.restype = sz
     L.fiunet_ssim_gauss_f32.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]

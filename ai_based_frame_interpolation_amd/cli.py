@@ -28,6 +28,14 @@ are not used; the alpha of an inserted rgba / bgra frame is the rounded average 
 
 Standard output then carries nothing but video: the model-loading lines go to standard error.  The network (grayscale
 2->1 or RGB 6->3) is read from the checkpoint.
+
+`evaluate` scores a checkpoint on a clip by hold-out (holdout.py): every held-out frame is rebuilt from
+its two neighbours by the network, by blending and by repeating a frame, and compared with the frame that was there:
+
+    ffmpeg -i clip.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli evaluate --input - \\
+        --model best_model.pth --json scores.json --csv frames.csv
+
+The summary table goes to standard error, the whole result to --json and one line per scored frame to --csv.
 """
 from __future__ import annotations
 
@@ -76,6 +84,14 @@ def _size(v: str):
     return int(parts[0]), int(parts[1])
 
 
+def _methods(v: str):
+    names = tuple(s.strip() for s in v.split(",") if s.strip())
+    bad = [n for n in names if n not in ("unet", "linear", "repeat")]
+    if not names or bad or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError(f"expected a comma-separated choice of unet, linear, repeat, got {v!r}")
+    return names
+
+
 def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m ai_based_frame_interpolation_amd.cli",
                                  description="AI frame interpolation on the MI355X")
@@ -102,6 +118,23 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--raw", default=None, choices=("nv12", "rgb24", "bgr24", "rgba", "bgra"),
                    help="Headerless raw video in and out (tight NV12 or packed RGB frames); needs --size and --src-fps")
     v.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
+    e = sub.add_parser("evaluate", help="Score a checkpoint on a clip by hold-out (Y4M or .npy; '-' is stdin)")
+    e.add_argument("--input", required=True, help="Clip to score: a .y4m or .npy path, or - for standard input (Y4M)")
+    e.add_argument("--model", default="best_model.pth", help="Path to trained model")
+    e.add_argument("--device", default="auto", help="Device to use (cuda/auto)")
+    e.add_argument("--triplets", default="sliding", choices=("sliding", "disjoint"),
+                   help="sliding: every frame but the first and last is held out; disjoint: every second frame")
+    e.add_argument("--methods", type=_methods, default=("unet", "linear", "repeat"),
+                   help="Comma-separated: unet, linear (blend), repeat (frame duplication)")
+    e.add_argument("--precision", default=None, help="fp32 / bf16x2 / bf16 / fp16 (default: the library's)")
+    e.add_argument("--matrix", default="bt709", help="YUV matrix of colour video through the RGB network")
+    e.add_argument("--siting", type=_siting, default=None, help="Chroma siting jpeg / mpeg2 (default: from the tag)")
+    e.add_argument("--batch", type=int, default=8, help="Frame pairs per forward")
+    e.add_argument("--chunk-frames", type=int, default=None, help="Held-out frames per chunk (default 4 x batch)")
+    e.add_argument("--src-fps", type=_fps, default=None,
+                   help="Source frame rate as n or n/d, for the time stamps (default: the Y4M header's)")
+    e.add_argument("--json", default=None, metavar="FILE", help="Write the whole result here (arrays as lists)")
+    e.add_argument("--csv", default=None, metavar="FILE", help="Write one line per scored frame here")
     return ap
 
 
@@ -110,6 +143,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     a = ap.parse_args(argv)
     if a.chunk_frames is None:
         a.chunk_frames = 4 * a.batch
+    if a.command != "video":
+        return a
     if a.raw is not None and (a.size is None or a.src_fps is None):
         ap.error("--raw needs --size WIDTHxHEIGHT and --src-fps (raw video has no header)")
     if a.raw is None and a.size is not None:
@@ -136,10 +171,35 @@ def run_video(a: argparse.Namespace) -> int:
     return n
 
 
+def run_evaluate(a: argparse.Namespace) -> dict:
+    import json
+
+    from . import holdout, stream
+    from .inference import load_model
+    stream.check_chunk_frames(a.chunk_frames)
+    device = torch.device("cuda" if a.device in ("auto", None) else a.device)
+    fc = frame_channels_of(torch.load(a.model, map_location="cpu"))
+    with contextlib.redirect_stdout(sys.stderr):
+        model = load_model(a.model, device, a.precision, frame_channels=fc)
+    src = sys.stdin.buffer if a.input == "-" else a.input
+    res = holdout.score_video(model, src, triplets=a.triplets, methods=a.methods, batch=a.batch,
+                              chunk_frames=a.chunk_frames, matrix=a.matrix, siting=a.siting, src_fps=a.src_fps)
+    print(holdout.summary_table(res), file=sys.stderr)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(holdout.to_jsonable(res), f, allow_nan=False)
+    if a.csv:
+        with open(a.csv, "w") as f:
+            f.writelines(line + "\n" for line in holdout.csv_lines(res))
+    return res
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
     if a.command == "video":
         run_video(a)
+    elif a.command == "evaluate":
+        run_evaluate(a)
     return 0
 
 

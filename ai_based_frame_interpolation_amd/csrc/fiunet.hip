@@ -1897,6 +1897,116 @@ int fiunet_ssim_u8(const uint8_t* pred, const uint8_t* target, int images, int H
     return FIUNET_OK;
 }
 
+size_t fiunet_plane_metrics_workspace_bytes(int images, int H, int W)
+{
+    if (images < 1 || H < 1 || W < 1) {
+        g_err = "fiunet_plane_metrics_workspace_bytes: bad arguments";
+        return 0;
+    }
+    return fiunet_metrics_workspace_bytes(images, H, W);
+}
+
+// The checks both plane metrics share; every refusal is FIUNET_ERR_INVALID_ARG and comes before any pointer is used.
+static int check_planes(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                        size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
+                        const void* out, const void* workspace, size_t workspace_bytes, size_t need)
+{
+    if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
+    if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_INVALID_ARG, "bad plane shape");
+    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
+    if (pred_row_pitch < (size_t)W || target_row_pitch < (size_t)W)
+        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: row_pitch < W");
+    const size_t limit = (size_t)1 << 40;
+    if (pred_row_pitch > limit || target_row_pitch > limit || pred_image_stride > limit || target_image_stride > limit)
+        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: a value above 2^40 samples");
+    if (images > 1 && (pred_image_stride < (size_t)(H - 1) * pred_row_pitch + W ||
+                       target_image_stride < (size_t)(H - 1) * target_row_pitch + W))
+        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: image_stride smaller than one plane");
+    const size_t align = bits == 10 ? 1 : 0;
+    if ((((uintptr_t)pred | (uintptr_t)target) & align) != 0)
+        return fail(FIUNET_ERR_INVALID_ARG, "10-bit planes are 16-bit words: odd address");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_INVALID_ARG, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    return FIUNET_OK;
+}
+
+extern "C++" {   // (a template over the sample type, inside this file's extern "C" part)
+template <typename T>
+static int launch_plane_psnr(const void* pred, size_t ps, size_t pp, const void* target, size_t ts, size_t tp,
+                             int images, int H, int W, unsigned long long* sums, hipStream_t s)
+{
+    // a plane whose rows follow each other on both sides is one run of H*W samples, cut into PLANE_SEG pieces
+    // (a multiple of 16 bytes, so every piece of an aligned plane keeps the 16-byte path)
+    const size_t n = (size_t)H * W;
+    const bool flat = pp == (size_t)W && tp == (size_t)W;
+    if (flat && (n + PLANE_SEG - 1) / PLANE_SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
+    const unsigned rows = flat ? (unsigned)((n + PLANE_SEG - 1) / PLANE_SEG) : (unsigned)H;
+    const unsigned w = flat ? (unsigned)PLANE_SEG : (unsigned)W;
+    const unsigned w_last = flat ? (unsigned)(n - (size_t)(rows - 1) * PLANE_SEG) : (unsigned)W;
+    const size_t pa = flat ? (size_t)PLANE_SEG : pp, pb = flat ? (size_t)PLANE_SEG : tp;
+    // one wave per row and step, at most 128 workgroups (= atomics) per image
+    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
+    hipLaunchKernelGGL(plane_sqdiff_kernel<T>, dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)pred, ps, pa,
+                       (const T*)target, ts, pb, rows, w, w_last, sums);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_plane_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                      size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
+                      double* out_psnr, unsigned long long* out_sse, void* workspace, size_t workspace_bytes,
+                      void* stream)
+{
+    const size_t need = images > 0 ? align256((size_t)images * 8) : 0;
+    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
+                              bits, images, H, W, out_psnr, workspace, workspace_bytes, need))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* sums = (unsigned long long*)workspace;
+    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)images * 8, s));
+    if (int rc = bits == 10 ? launch_plane_psnr<uint16_t>(pred, pred_image_stride, pred_row_pitch, target,
+                                                          target_image_stride, target_row_pitch, images, H, W, sums, s)
+                            : launch_plane_psnr<uint8_t>(pred, pred_image_stride, pred_row_pitch, target,
+                                                         target_image_stride, target_row_pitch, images, H, W, sums, s))
+        return rc;
+    hipLaunchKernelGGL(plane_psnr_finalize_kernel, dim3((images + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
+                       bits == 10 ? 1023.0 : 255.0, out_psnr, out_sse, images);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                      size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
+                      double* out_ssim, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (H < SSIM_WIN || W < SSIM_WIN)
+        return fail(FIUNET_ERR_INVALID_ARG, "SSIM: the 7x7 window exceeds the plane (skimage raises too)");
+    const size_t need = images > 0 ? fiunet_metrics_workspace_bytes(images, H, W) : 0;
+    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
+                              bits, images, H, W, out_ssim, workspace, workspace_bytes, need))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    int tx = 0;
+    const int tiles = ssim_tiles(H, W, &tx);
+    double* partial = (double*)((char*)workspace + align256((size_t)images * 8));
+    const dim3 grid((unsigned)tiles, (unsigned)images);
+    if (bits == 10)
+        hipLaunchKernelGGL(plane_ssim_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)pred, pred_image_stride,
+                           pred_row_pitch, (const uint16_t*)target, target_image_stride, target_row_pitch, H, W, tx,
+                           partial);
+    else
+        hipLaunchKernelGGL(plane_ssim_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)pred, pred_image_stride,
+                           pred_row_pitch, (const uint8_t*)target, target_image_stride, target_row_pitch, H, W, tx,
+                           partial);
+    HIP_TRY(hipGetLastError());
+    const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
+    hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out_ssim);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
 static inline int gssim_tiles(int H, int W, int* tiles_x)
 {
     const int tx = (W + GSSIM_TX - 1) / GSSIM_TX, ty = (H + GSSIM_TY - 1) / GSSIM_TY;

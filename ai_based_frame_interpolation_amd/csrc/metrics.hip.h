@@ -157,6 +157,164 @@ __global__ __launch_bounds__(256) void ssim_finalize_kernel(const double* __rest
     if (tid == 0) out[blockIdx.x] = red[0] / count;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The same two metrics on planes where they lie (hold-out scoring, holdout.py): images `image stride`
+// samples apart, rows `row pitch` samples apart, 8-bit samples (uint8_t, peak 255) or 10-bit codes in
+// 16-bit words (uint16_t, peak 1023; a word above 1023 reads as 1023, as in every 10-bit kernel here, so
+// every sum below stays inside int32).  One template over the sample type; at uint8_t the arithmetic is
+// that of the two kernels above, statement for statement, so the values are the same to the last bit.
+template <typename T> struct PlaneSample;
+template <> struct PlaneSample<uint8_t> {
+    static constexpr int PEAK = 255;
+    static __device__ __forceinline__ int get(unsigned v) { return (int)v; }
+};
+template <> struct PlaneSample<uint16_t> {
+    static constexpr int PEAK = 1023;
+    static __device__ __forceinline__ int get(unsigned v) { return (int)min(v, 1023u); }
+};
+
+constexpr int PLANE_SEG = 4096;  // samples per wave and step of a plane whose rows are contiguous
+
+// sum (a-b)^2 of every sample of one 32-bit word pair
+template <typename T> __device__ __forceinline__ unsigned sqdiff_word(unsigned wa, unsigned wb)
+{
+    constexpr int BITS = 8 * sizeof(T), N = 4 / sizeof(T);
+    constexpr unsigned MASK = (1u << BITS) - 1u;
+    unsigned acc = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const int d = PlaneSample<T>::get((wa >> (BITS * j)) & MASK) - PlaneSample<T>::get((wb >> (BITS * j)) & MASK);
+        acc += (unsigned)(d * d);
+    }
+    return acc;
+}
+
+// grid = (blocks per image, images); `sums` zeroed by the caller.  One wave per row at a time: `rows` rows of
+// `W` samples (the last one `w_last`).  A row whose two base addresses sit at the same offset inside a 16-byte
+// line goes 16 bytes per lane from the first aligned sample on, with a scalar head and tail; any other row
+// (an I420 chroma plane against a contiguous copy, an odd pitch on one side) is read sample by sample.
+template <typename T>
+__global__ __launch_bounds__(256) void plane_sqdiff_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
+                                                           const T* __restrict__ b, size_t b_image, size_t b_pitch,
+                                                           unsigned rows, unsigned W, unsigned w_last,
+                                                           unsigned long long* __restrict__ sums)
+{
+    constexpr unsigned VEC = 16 / sizeof(T);
+    const size_t img = blockIdx.y;
+    const T* ia = a + img * a_image;
+    const T* ib = b + img * b_image;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long s = 0;
+    for (unsigned r = blockIdx.x * 4 + wave; r < rows; r += gridDim.x * 4) {
+        const T* pa = ia + (size_t)r * a_pitch;
+        const T* pb = ib + (size_t)r * b_pitch;
+        const unsigned len = r + 1 == rows ? w_last : W;
+        const bool same = (((uintptr_t)pa ^ (uintptr_t)pb) & 15) == 0;
+        const unsigned head = same ? min(len, (unsigned)(((16 - ((uintptr_t)pa & 15)) & 15) / sizeof(T))) : len;
+        const unsigned nv = (len - head) / VEC;
+        for (unsigned i = lane; i < head; i += 64) {
+            const int d = PlaneSample<T>::get(pa[i]) - PlaneSample<T>::get(pb[i]);
+            s += (unsigned)(d * d);
+        }
+        const uint4* qa = reinterpret_cast<const uint4*>(pa + head);
+        const uint4* qb = reinterpret_cast<const uint4*>(pb + head);
+        for (unsigned i = lane; i < nv; i += 64) {
+            const uint4 va = qa[i], vb = qb[i];
+            s += sqdiff_word<T>(va.x, vb.x) + sqdiff_word<T>(va.y, vb.y) + sqdiff_word<T>(va.z, vb.z) +
+                 sqdiff_word<T>(va.w, vb.w);
+        }
+        for (unsigned i = head + nv * VEC + lane; i < len; i += 64) {
+            const int d = PlaneSample<T>::get(pa[i]) - PlaneSample<T>::get(pb[i]);
+            s += (unsigned)(d * d);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    __shared__ unsigned long long part[4];
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
+        if (t) atomicAdd(sums + img, t);
+    }
+}
+
+// psnr_finalize_kernel with the peak as an argument; out_sse (may be NULL) receives the integer sums
+__global__ void plane_psnr_finalize_kernel(const unsigned long long* __restrict__ sums, size_t n, double peak,
+                                           double* __restrict__ out, unsigned long long* __restrict__ out_sse,
+                                           int images)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= images) return;
+    const double mse = (double)sums[i] / (double)n;
+    out[i] = sums[i] == 0 ? __longlong_as_double(0x7ff0000000000000LL) : 10.0 * log10((peak * peak) / mse);
+    if (out_sse) out_sse[i] = sums[i];
+}
+
+// ssim_u8_kernel on strided planes of either depth: same tiles, same order of every sum
+template <typename T>
+__global__ __launch_bounds__(256) void plane_ssim_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
+                                                         const T* __restrict__ b, size_t b_image, size_t b_pitch,
+                                                         int H, int W, int tiles_x, double* __restrict__ partial)
+{
+    constexpr int IW = SSIM_TX + SSIM_WIN - 1, IH = SSIM_TY + SSIM_WIN - 1, IWP = IW + 2;
+    __shared__ T ta[IH * IWP], tb[IH * IWP];
+    __shared__ int hs[5][IH][SSIM_TX];  // horizontal 7-sums of a, b, a^2, b^2, ab (<= 7 * 1023^2)
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x;
+    const size_t img = blockIdx.y;
+    const T* pa = a + img * a_image;
+    const T* pb = b + img * b_image;
+    const int oy0 = ty * SSIM_TY, ox0 = tx * SSIM_TX;
+    const int OH = H - 2 * SSIM_PAD, OW = W - 2 * SSIM_PAD;
+    for (int i = tid; i < IH * IW; i += 256) {
+        const int r = i / IW, c = i - r * IW;
+        const int y = min(oy0 + r, H - 1), x = min(ox0 + c, W - 1);
+        ta[r * IWP + c] = (T)PlaneSample<T>::get(pa[(size_t)y * a_pitch + x]);
+        tb[r * IWP + c] = (T)PlaneSample<T>::get(pb[(size_t)y * b_pitch + x]);
+    }
+    __syncthreads();
+    for (int i = tid; i < IH * SSIM_TX; i += 256) {
+        const int r = i / SSIM_TX, c = i - r * SSIM_TX;
+        int sa = 0, sb = 0, saa = 0, sbb = 0, sab = 0;
+#pragma unroll
+        for (int k = 0; k < SSIM_WIN; ++k) {
+            const int va = ta[r * IWP + c + k], vb = tb[r * IWP + c + k];
+            sa += va; sb += vb; saa += va * va; sbb += vb * vb; sab += va * vb;
+        }
+        hs[0][r][c] = sa; hs[1][r][c] = sb; hs[2][r][c] = saa; hs[3][r][c] = sbb; hs[4][r][c] = sab;
+    }
+    __syncthreads();
+    constexpr double PEAK = (double)PlaneSample<T>::PEAK;
+    const double NP = 49.0, cov_norm = NP / (NP - 1.0);
+    const double C1 = (0.01 * PEAK) * (0.01 * PEAK), C2 = (0.03 * PEAK) * (0.03 * PEAK);
+    double acc = 0.0;
+    for (int i = tid; i < SSIM_TY * SSIM_TX; i += 256) {
+        const int r = i / SSIM_TX, c = i - r * SSIM_TX;
+        if (oy0 + r >= OH || ox0 + c >= OW) continue;
+        int s[5] = {0, 0, 0, 0, 0};  // <= 49 * 1023^2 = 51,279,921
+#pragma unroll
+        for (int k = 0; k < SSIM_WIN; ++k)
+#pragma unroll
+            for (int q = 0; q < 5; ++q) s[q] += hs[q][r + k][c];
+        const double ux = (double)s[0] / NP, uy = (double)s[1] / NP;
+        const double uxx = (double)s[2] / NP, uyy = (double)s[3] / NP, uxy = (double)s[4] / NP;
+        const double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy);
+        const double vxy = cov_norm * (uxy - ux * uy);
+        const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2;
+        const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
+        acc += (A1 * A2) / (B1 * B2);
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) partial[img * gridDim.x + tile] = red[0];
+}
+
 
 // ---------------------------------------------------------------------------------------------------
 // Gaussian-window SSIM of the training loss (/root/reference/model/train.py:18-73, SSIMLoss._ssim):

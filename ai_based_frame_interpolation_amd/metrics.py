@@ -4,6 +4,10 @@ defaults: PSNR with data_range 255; SSIM with a 7x7 uniform window, sample covar
 K2 0.03, mean over the image minus a 3-pixel border.  Inputs stay on the device; results are
 float64 tensors, one value per [H, W] plane.  No CPU fallback.
 
+`psnr_planes` / `ssim_planes` are the same two metrics on planes WHERE THEY LIE - any row stride, one stride over the
+leading dimensions, uint8 or 10-bit codes in 16-bit words (peak 1023) - for hold-out scoring of video (holdout.py,
+DESIGN.md 3.3k): the Y, U and V planes of packed 4:2:0 rows are scored without a copy.
+
 Also here: the reference's OTHER SSIM, the Gaussian-window one of its training loss
 (model/train.py:18-87: `SSIMLoss`, `CombinedLoss`) - the only SSIM in the reference that is pure torch,
 so the only one whose values are pinned by fixtures recorded from the reference itself
@@ -55,6 +59,85 @@ def psnr_u8(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
 def ssim_u8(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """compute_ssim(pred, target) (evaluation.py:207-218) for every [H, W] plane."""
     return _run("fiunet_ssim_u8", pred, target)
+
+
+def _plane_layout(t: torch.Tensor, name: str):
+    """[..., H, W] -> (image stride, row pitch) in samples, as the tensor lies: no copy.  The leading dimensions must
+    advance by one stride (a stack, every second frame of one, channel c of [N, C, H, W], a slice of packed rows)."""
+    h, w = t.shape[-2:]
+    st = t.stride()
+    if w > 1 and st[-1] != 1:
+        raise ValueError(f"{name}: the last dimension must have stride 1 (strides {tuple(st)})")
+    pitch = st[-2] if h > 1 else w
+    lead = [(n, s) for n, s in zip(t.shape[:-2], st[:-2]) if n != 1]
+    for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
+        if s0 != s1 * n1:
+            raise ValueError(f"{name}: the leading dimensions must advance by one stride (shape {tuple(t.shape)}, "
+                             f"strides {tuple(st)})")
+    return (lead[-1][1] if lead else (h - 1) * pitch + w), pitch
+
+
+def _plane_args(pred: torch.Tensor, target: torch.Tensor, bits: int):
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+    if pred.shape != target.shape or pred.dim() < 2:
+        raise ValueError(f"expected two tensors of equal shape [..., H, W], got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    ok = (torch.uint8,) if bits == 8 else (torch.uint16, torch.int16)
+    if pred.dtype not in ok or target.dtype not in ok:
+        raise ValueError(f"{bits}-bit planes are {' or '.join(str(d) for d in ok)} tensors, got {pred.dtype} and "
+                         f"{target.dtype}")
+    if not pred.is_cuda or not target.is_cuda or pred.device != target.device:
+        raise RuntimeError("device metrics need CUDA/HIP tensors on one device; there is no CPU fallback here")
+    h, w = pred.shape[-2:]
+    if h < 1 or w < 1:
+        raise ValueError(f"empty planes {tuple(pred.shape)}")
+    n = pred.numel() // (h * w)
+    return n, h, w, _plane_layout(pred, "pred"), _plane_layout(target, "target")
+
+
+def _plane_workspace(n, h, w, device):
+    nbytes = _native.lib().fiunet_plane_metrics_workspace_bytes(n, h, w)
+    if nbytes == 0:
+        _native.check(1, "fiunet_plane_metrics_workspace_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def psnr_planes(pred: torch.Tensor, target: torch.Tensor, bits: int, *, return_sse: bool = False):
+    """PSNR of every [H, W] plane of two device tensors [..., H, W] WHERE THEY LIE (fiunet_plane_psnr): uint8 at bits 8
+    (peak 255), uint16 or int16 words of 10-bit codes at bits 10 (peak 1023).  The last dimension has stride 1; any row
+    stride and any single stride of the leading dimensions go to the kernel as they are (no `.contiguous()`).
+    -> float64 [...]; with return_sse also the exact sums of squared differences, int64 [...] (the bits of the
+    library's uint64)."""
+    n, h, w, (ps, pp), (ts, tp) = _plane_args(pred, target, bits)
+    lead = pred.shape[:-2]
+    out = torch.empty(n, dtype=torch.float64, device=pred.device)
+    sse = torch.empty(n, dtype=torch.int64, device=pred.device) if return_sse else None
+    if n:
+        ws, nbytes = _plane_workspace(n, h, w, pred.device)
+        with torch.cuda.device(pred.device):
+            s = torch.cuda.current_stream(pred.device).cuda_stream
+            _native.check(_native.lib().fiunet_plane_psnr(
+                pred.data_ptr(), ps, pp, target.data_ptr(), ts, tp, bits, n, h, w, out.data_ptr(),
+                None if sse is None else sse.data_ptr(), ws.data_ptr(), ctypes.c_size_t(nbytes), s), "fiunet_plane_psnr")
+    return (out.view(lead), sse.view(lead)) if return_sse else out.view(lead)
+
+
+def ssim_planes(pred: torch.Tensor, target: torch.Tensor, bits: int) -> torch.Tensor:
+    """SSIM (skimage's defaults, data_range = the peak) of every [H, W] plane where it lies (fiunet_plane_ssim); the
+    arguments are `psnr_planes`'; H, W >= 7.  -> float64 [...]."""
+    n, h, w, (ps, pp), (ts, tp) = _plane_args(pred, target, bits)
+    if h < 7 or w < 7:
+        raise ValueError(f"SSIM: the 7x7 window exceeds the {h}x{w} plane")
+    out = torch.empty(n, dtype=torch.float64, device=pred.device)
+    if n:
+        ws, nbytes = _plane_workspace(n, h, w, pred.device)
+        with torch.cuda.device(pred.device):
+            s = torch.cuda.current_stream(pred.device).cuda_stream
+            _native.check(_native.lib().fiunet_plane_ssim(
+                pred.data_ptr(), ps, pp, target.data_ptr(), ts, tp, bits, n, h, w, out.data_ptr(), ws.data_ptr(),
+                ctypes.c_size_t(nbytes), s), "fiunet_plane_ssim")
+    return out.view(pred.shape[:-2])
 
 
 _WINDOWS = {}

@@ -32,7 +32,8 @@ extern "C" {
                                      fiunet_rgb_p10_to_p010, fiunet_forward_p010 and the two workspace queries); v8 also, added
                                      the same way: packed RGB frames (fiunet_packed_format, fiunet_packed_layout,
                                      fiunet_packed_to_rgb_u8, fiunet_rgb_to_packed_u8, fiunet_forward_rgb_packed and its
-                                     workspace query) */
+                                     workspace query); v8 also, added the same way: PSNR / SSIM on strided 8- and 10-bit
+                                     planes (fiunet_plane_psnr, fiunet_plane_ssim and their workspace query) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -413,6 +414,29 @@ int fiunet_psnr_u8(const uint8_t* pred, const uint8_t* target, int images, int H
                    void* workspace, size_t workspace_bytes, void* stream);
 int fiunet_ssim_u8(const uint8_t* pred, const uint8_t* target, int images, int H, int W, double* out,
                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same two metrics on planes where they lie (hold-out scoring of video: the Y, U and V planes of packed 4:2:0
+ * rows, every second row of a stack): `images` planes of H x W samples, image i of `pred` at pred + i *
+ * pred_image_stride, its rows pred_row_pitch apart; strides and pitches in SAMPLES.  bits 8: uint8_t samples, peak 255
+ * (on contiguous planes the values are fiunet_psnr_u8's / fiunet_ssim_u8's to the last bit); bits 10: uint16_t words of
+ * 10-bit codes, peak 1023 (a word above 1023 reads as 1023, as in the 10-bit conversions).  pred and target may point
+ * into one allocation.  out_psnr / out_ssim: device double[images]; out_sse (may be NULL): device uint64[images], the
+ * exact sum of squared differences PSNR = 10 log10(peak^2 / (sse / (H*W))) is made from (+inf at 0).  SSIM: the
+ * definition above with C1 = (0.01 peak)^2, C2 = (0.03 peak)^2; exact integer window sums, fp64 map and mean in a
+ * fixed order.  workspace: fiunet_plane_metrics_workspace_bytes(images, H, W), 256-B aligned.  Asynchronous on
+ * `stream`; no allocation, no synchronisation.  FIUNET_ERR_INVALID_ARG, before any launch and before any pointer is
+ * used: NULL pointers, bits not 8 or 10, images / H / W < 1 (SSIM: H or W < 7), more than 65535 images, a row pitch
+ * < W, images > 1 with an image stride smaller than one plane ((H-1) * pitch + W), a workspace that is too small or
+ * not aligned. */
+size_t fiunet_plane_metrics_workspace_bytes(int images, int H, int W);
+int fiunet_plane_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch,
+                      const void* target, size_t target_image_stride, size_t target_row_pitch,
+                      int bits, int images, int H, int W, double* out_psnr, unsigned long long* out_sse,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch,
+                      const void* target, size_t target_image_stride, size_t target_row_pitch,
+                      int bits, int images, int H, int W, double* out_ssim,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* The training loss' SSIM on device: SSIMLoss._ssim (model/train.py:37-56) - the
  * window_size x window_size Gaussian window (sigma 1.5, normalised as at train.py:27-35) applied as a
