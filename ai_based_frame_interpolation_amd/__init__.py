@@ -5,13 +5,14 @@ from .unet import FrameInterpolationUNet, GraphedForward, UNet, count_parameters
 from .inference import (  # noqa: F401
     FrameInterpolator, generate_multiple_intermediate_frames, interpolate_frames,
     interpolate_sequence, interpolate_sequence_host, interpolate_sequence_nv12, interpolate_sequence_p10,
-    interpolate_sequence_rgb_packed, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10, load_model,
+    interpolate_sequence_rgb_packed, interpolate_sequence_yuv, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10, load_model,
     postprocess_image, preprocess_image, sequence_pair_fn,
 )
 from .serving import InterpolationService  # noqa: F401
 from .colour import (  # noqa: F401
     SurfaceLayout, i420_frame_bytes, nv12_to_rgb, p010_to_rgb, rgb_to_nv12, rgb_to_p010, rgb_to_yuv420,
     rgb_to_yuv420p10, yuv420_to_rgb, yuv420p10_frame_samples, yuv420p10_to_rgb,
+    YUV_FORMATS, rgb_to_yuv, yuv_frame_samples, yuv_to_rgb,
 )
 from .packed import PackedLayout  # noqa: F401
 from . import colour, evaluation, holdout, metrics, optical_flow, packed, retime, scene, serving, stream, synthetic, tiling, transport, video  # noqa: F401
@@ -27,4 +28,5 @@ __all__ = [
     "InterpolationService", "serving", "synthetic", "scene", "stream", "retime",
     "SurfaceLayout", "nv12_to_rgb", "rgb_to_nv12", "p010_to_rgb", "rgb_to_p010", "interpolate_sequence_nv12",
     "packed", "PackedLayout", "interpolate_sequence_rgb_packed", "holdout",
+    "YUV_FORMATS", "yuv_to_rgb", "rgb_to_yuv", "yuv_frame_samples", "interpolate_sequence_yuv",
 ]

@@ -45,6 +45,9 @@ SYMBOLS = (
     "fiunet_forward_yuv420p10",
     "fiunet_pair_sad_u8", "fiunet_pair_sad_p10", "fiunet_scene_cuts", "fiunet_hold_cut_frames",
     "fiunet_retime_u8", "fiunet_retime_p10",
+    # YUV 4:2:2 / 4:4:4 frames
+    "fiunet_yuv_to_rgb_u8", "fiunet_rgb_to_yuv_u8", "fiunet_yuv_to_rgb_p10", "fiunet_rgb_p10_to_yuv",
+    "fiunet_workspace_bytes_yuv", "fiunet_forward_yuv", "fiunet_forward_yuv_p10",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -181,6 +184,14 @@ def lib() -> ctypes.CDLL:
     L.fiunet_workspace_bytes_rgb_packed.argtypes = [vp, ci, ci, ci, ci]
     L.fiunet_workspace_bytes_rgb_packed.restype = sz
     L.fiunet_forward_rgb_packed.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, sz, vp]
+    L.fiunet_yuv_to_rgb_u8.argtypes = [vp, ci, sz, sz, vp, ci, ci, ci, cu, vp]
+    L.fiunet_yuv_to_rgb_p10.argtypes = [vp, ci, sz, sz, vp, ci, ci, ci, cu, vp]
+    L.fiunet_rgb_to_yuv_u8.argtypes = [vp, vp, ci, sz, sz, ci, ci, ci, cu, vp]
+    L.fiunet_rgb_p10_to_yuv.argtypes = [vp, vp, ci, sz, sz, ci, ci, ci, cu, vp]
+    L.fiunet_workspace_bytes_yuv.argtypes = [vp, ci, ci, ci, ci, ci]
+    L.fiunet_workspace_bytes_yuv.restype = sz
+    L.fiunet_forward_yuv.argtypes = [vp, vp, vp, ci, sz, sz, vp, sz, sz, ci, ci, ci, cu, ci, vp, sz, vp]
+    L.fiunet_forward_yuv_p10.argtypes = [vp, vp, vp, ci, sz, sz, vp, sz, sz, ci, ci, ci, cu, ci, vp, sz, vp]
     L.fiunet_debug_read_activation.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, sz,
                                                ctypes.POINTER(ci), vp]
     L.fiunet_metrics_workspace_bytes.argtypes = [ci, ci, ci]
@@ -388,6 +399,19 @@ class Context:
                                               workspace.data_ptr(), workspace.numel(), s),
               "fiunet_forward_rgb_packed")
 
+    def forward_yuv(self, f1, f2, fmt, layout, out, out_layout, h, w, colour, precision, workspace, bits, stream=None):
+        """fiunet_forward_yuv (bits 8: uint8) / fiunet_forward_yuv_p10 (bits 10: uint16) on [B, frame_stride] rows of the
+        fiunet_yuv_format `fmt`: f1, f2 contiguous in `layout`; `out` in `out_layout`, its rows contiguous and possibly
+        further apart.  The layouts are resolved packed.PackedLayout tuples (row_pitch 0 for the planar formats); the
+        workspace is the 4:2:0 entry point's."""
+        b = f1.shape[0]
+        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        fn, name = ((lib().fiunet_forward_yuv_p10, "fiunet_forward_yuv_p10") if bits == 10 else
+                    (lib().fiunet_forward_yuv, "fiunet_forward_yuv"))
+        check(fn(self._h, f1.data_ptr(), f2.data_ptr(), fmt, layout.row_pitch, f1.shape[1], out.data_ptr(),
+                 out_layout.row_pitch, _row_stride(out), b, h, w, colour, precision, workspace.data_ptr(),
+                 workspace.numel(), s), name)
+
     def profile_enable(self, on: bool):
         check(lib().fiunet_profile_enable(self._h, 1 if on else 0), "fiunet_profile_enable")
 
@@ -515,6 +539,27 @@ def rgb_to_packed(rgb: "torch.Tensor", out: "torch.Tensor", layout, alphas, alph
     al = _packed(alpha_layout, _row_stride(alphas[0])) if alphas else None
     check(lib().fiunet_rgb_to_packed_u8(rgb.data_ptr(), out.data_ptr(), _packed(layout, _row_stride(out)), a[0], a[1],
                                         al, b, h, w, fmt, s), "fiunet_rgb_to_packed_u8")
+
+
+def yuv_to_rgb(frames: "torch.Tensor", fmt: int, layout, out: "torch.Tensor", h: int, w: int, colour: int,
+               bits: int) -> None:
+    """fiunet_yuv_to_rgb_u8 (bits 8) / fiunet_yuv_to_rgb_p10 (bits 10): [B, frame_stride] frames of the
+    fiunet_yuv_format `fmt` (rows contiguous, any row stride) in the resolved `layout` -> planar RGB [B, 3, h, w]."""
+    s = torch.cuda.current_stream(frames.device).cuda_stream
+    fn, name = ((lib().fiunet_yuv_to_rgb_p10, "fiunet_yuv_to_rgb_p10") if bits == 10 else
+                (lib().fiunet_yuv_to_rgb_u8, "fiunet_yuv_to_rgb_u8"))
+    check(fn(frames.data_ptr(), fmt, layout.row_pitch, _row_stride(frames), out.data_ptr(), frames.shape[0], h, w,
+             colour, s), name)
+
+
+def rgb_to_yuv(rgb: "torch.Tensor", out: "torch.Tensor", fmt: int, layout, colour: int, bits: int) -> None:
+    """fiunet_rgb_to_yuv_u8 (bits 8) / fiunet_rgb_p10_to_yuv (bits 10): planar RGB [B, 3, h, w] contiguous -> [B,
+    frame_stride] frames of the fiunet_yuv_format `fmt` (rows contiguous, any row stride) in the resolved `layout`."""
+    b, _, h, w = rgb.shape
+    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    fn, name = ((lib().fiunet_rgb_p10_to_yuv, "fiunet_rgb_p10_to_yuv") if bits == 10 else
+                (lib().fiunet_rgb_to_yuv_u8, "fiunet_rgb_to_yuv_u8"))
+    check(fn(rgb.data_ptr(), out.data_ptr(), fmt, layout.row_pitch, _row_stride(out), b, h, w, colour, s), name)
 
 
 def pair_sad(frames: "torch.Tensor", sums: "torch.Tensor", bits: int) -> None:

@@ -2,7 +2,7 @@
 
 The reference's `main.py video` flags (--input, --output, --factor, --model, --device), plus --precision, --matrix,
 --siting, --scene-cut, --batch, --chunk-frames, the frame-rate conversion's --fps, --src-fps, --time-depth and
---retime, and --raw / --size for headerless NV12 or packed RGB video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
+--retime, and --raw / --size for headerless NV12, packed RGB or 4:2:2 / 4:4:4 YUV video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
 the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 
     ffmpeg -i in.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - \\
@@ -25,6 +25,18 @@ are not used; the alpha of an inserted rgba / bgra frame is the rounded average 
     ffmpeg -i capture.mkv -f rawvideo -pix_fmt rgb24 - | python -m ai_based_frame_interpolation_amd.cli video \\
         --input - --output - --raw rgb24 --size 1920x1080 --src-fps 30 --model rgb.pth | \\
         ffmpeg -f rawvideo -pix_fmt rgb24 -s 1920x1080 -r 60 -i - out.mkv
+
+`--raw yuv422p10le` (or yuv422p, yuv444p, yuv444p10le, uyvy422, yuyv422) takes 4:2:2 and 4:4:4 video at its own chroma
+resolution: what ProRes, DNxHR and XDCAM decode to and what capture cards deliver.  --matrix and
+--siting apply as for nv12 (siting defaults to mpeg2; bt2020 with the 10-bit formats); run 10-bit video in fp16:
+
+    ffmpeg -i prores.mov -f rawvideo -pix_fmt yuv422p10le - | python -m ai_based_frame_interpolation_amd.cli video \\
+        --input - --output - --raw yuv422p10le --size 1920x1080 --src-fps 24 --precision fp16 --model rgb.pth | \\
+        ffmpeg -f rawvideo -pix_fmt yuv422p10le -s 1920x1080 -r 48 -i - -c:v prores_ks -profile:v 3 out.mov
+
+    ffmpeg -f decklink -i 'DeckLink Mini Recorder' -f rawvideo -pix_fmt uyvy422 - | \\
+        python -m ai_based_frame_interpolation_amd.cli video --input - --output - --raw uyvy422 --size 1920x1080 \\
+        --src-fps 30 --model rgb.pth | ffmpeg -f rawvideo -pix_fmt uyvy422 -s 1920x1080 -r 60 -i - out.mkv
 
 Standard output then carries nothing but video: the model-loading lines go to standard error.  The network (grayscale
 2->1 or RGB 6->3) is read from the checkpoint.
@@ -115,8 +127,11 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--time-depth", type=int, default=2, choices=(1, 2, 3, 4), help="Bisection levels under --fps")
     v.add_argument("--retime", default="blend", choices=retime.MODES,
                    help="How --fps picks between the two bisection frames around an output time")
-    v.add_argument("--raw", default=None, choices=("nv12", "rgb24", "bgr24", "rgba", "bgra"),
-                   help="Headerless raw video in and out (tight NV12 or packed RGB frames); needs --size and --src-fps")
+    v.add_argument("--raw", default=None,
+                   choices=("nv12", "rgb24", "bgr24", "rgba", "bgra", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le",
+                            "uyvy422", "yuyv422"),
+                   help="Headerless raw video in and out (tight NV12, packed RGB or 4:2:2 / 4:4:4 YUV frames, named as "
+                        "ffmpeg's -pix_fmt); needs --size and --src-fps")
     v.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
     e = sub.add_parser("evaluate", help="Score a checkpoint on a clip by hold-out (Y4M or .npy; '-' is stdin)")
     e.add_argument("--input", required=True, help="Clip to score: a .y4m or .npy path, or - for standard input (Y4M)")

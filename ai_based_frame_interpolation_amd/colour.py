@@ -15,6 +15,12 @@ rows a pitch apart.  `nv12_to_rgb` / `rgb_to_nv12`, `p010_to_rgb` / `rgb_to_p010
 `FrameInterpolationUNet.forward_nv12` / `forward_p010` are the conversions above on that layout (`SurfaceLayout`), with
 the same arithmetic bit for bit.
 
+4:2:2 and 4:4:4 video: `YUV_FORMATS` names, by ffmpeg's -pix_fmt names, what mezzanine codecs decode to
+("yuv422p10le"), what capture cards deliver ("uyvy422", "yuyv422") and what YUV screen and grading sources hold
+("yuv444p", "yuv444p10le"), plus "yuv422p".  `yuv_to_rgb` / `rgb_to_yuv` and `FrameInterpolationUNet.forward_yuv` take them
+by name; the arithmetic is the 4:2:0 one with the sub-sampling pattern changed (4:2:2 is its horizontal half, 4:4:4 has
+none), siting defaults to "mpeg2" for 4:2:2 and means nothing for 4:4:4.
+
 Options (the keywords of every colour entry point):
   siting        "jpeg" (Y4M C420jpeg, C420 or no tag: chroma centred in its 2x2 luma block) or "mpeg2" (C420mpeg2:
                 co-sited with the even luma column, centred vertically)
@@ -95,6 +101,135 @@ def resolve_layout(layout: SurfaceLayout | None, height: int, width: int) -> Sur
         raise ValueError(f"layout: frame_stride {fs} does not cover the chroma plane (it ends at "
                          f"{co + (hc - 1) * cp + 2 * wc} samples)")
     return SurfaceLayout(lp, co, cp, fs)
+
+
+#: name (ffmpeg's -pix_fmt) -> (fiunet_yuv_format code, bits, kind): "422" / "444" planar, "packed" one-plane 4:2:2
+YUV_FORMATS = {"yuv422p": (0, 8, "422"), "yuv444p": (1, 8, "444"), "yuv422p10le": (0, 10, "422"),
+               "yuv444p10le": (1, 10, "444"), "uyvy422": (2, 8, "packed"), "yuyv422": (3, 8, "packed")}
+
+
+def _yuv_format(format) -> tuple[int, int, str]:
+    try:
+        return YUV_FORMATS[format]
+    except (KeyError, TypeError):
+        raise ValueError(f"format must be one of {list(YUV_FORMATS)}, got {format!r}") from None
+
+
+def yuv_frame_samples(format: str, height: int, width: int) -> int:
+    """Samples of one tight frame of `format` (bytes at 8 bits, 16-bit words at 10): H*W + 2*H*ceil(W/2) for planar
+    4:2:2, 3*H*W for 4:4:4, 2*H*W for uyvy422 / yuyv422, which need an even width."""
+    _, _, kind = _yuv_format(format)
+    h, w = int(height), int(width)
+    if h < 1 or w < 1:
+        raise ValueError(f"bad frame size {height!r}x{width!r}")
+    if kind == "packed":
+        if w % 2:
+            raise ValueError(f"{format} frames have an even width (two pixels share a chroma pair), got {w}")
+        return 2 * h * w
+    return 3 * h * w if kind == "444" else h * w + 2 * h * ((w + 1) // 2)
+
+
+def resolve_yuv_layout(layout, format: str, height: int, width: int):
+    """-> a `packed.PackedLayout` (row_pitch, frame_stride) in samples with every 0 of `layout` replaced by its tight
+    value (None: the tight layout); ValueError where it cannot hold a height x width frame of `format` (the rules of
+    include/fiunet.h, fiunet_yuv_to_rgb_u8).  Planar frames are tight inside: their row_pitch stays 0 and must be 0."""
+    from .packed import PackedLayout
+    _, _, kind = _yuv_format(format)
+    tight = yuv_frame_samples(format, height, width)
+    h, w = int(height), int(width)
+    vals = tuple(layout) if layout is not None else (0, 0)
+    if len(vals) != 2 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0 or v > 1 << 40 for v in vals):
+        raise ValueError(f"layout must be a PackedLayout of two ints in [0, 2^40] (samples), got {layout!r}")
+    if kind != "packed":
+        if vals[0]:
+            raise ValueError(f"layout: {format} frames are tight inside (row_pitch must be 0, got {vals[0]})")
+        fs = int(vals[1]) or tight
+        if fs < tight:
+            raise ValueError(f"layout: frame_stride {fs} is smaller than one frame ({tight} samples)")
+        return PackedLayout(0, fs)
+    rp = int(vals[0]) or 2 * w
+    fs = int(vals[1]) or h * rp
+    if rp < 2 * w:
+        raise ValueError(f"layout: row_pitch {rp} < {2 * w}, the {w} {format} pixels of a row")
+    if fs < (h - 1) * rp + 2 * w:
+        raise ValueError(f"layout: frame_stride {fs} does not cover the last row (it ends at {(h - 1) * rp + 2 * w} bytes)")
+    return PackedLayout(rp, fs)
+
+
+def yuv_flags(format: str, siting, matrix: str, colour_range: str) -> int:
+    """`colour_flags` at the depth of `format`; siting None means "mpeg2" (what decoders and ffmpeg assume for 4:2:2;
+    4:4:4 has no siting: any valid value is accepted and ignored)."""
+    return colour_flags("mpeg2" if siting is None else siting, matrix, colour_range, bits=_yuv_format(format)[1])
+
+
+def _check_yuv_frames(frames, height, width, what, format, layout) -> None:
+    """layout: resolved.  [B, layout.frame_stride] in the dtype of `format` on the GPU, every frame contiguous."""
+    dtype = torch.uint16 if _yuv_format(format)[1] == 10 else torch.uint8
+    fb = layout.frame_stride
+    if not isinstance(frames, torch.Tensor) or frames.dtype != dtype or frames.dim() != 2 or frames.shape[1] != fb:
+        got = f"{frames.dtype} {tuple(frames.shape)}" if isinstance(frames, torch.Tensor) else repr(type(frames))
+        raise ValueError(f"{what} must be {str(dtype).split('.')[-1]} [B, {fb}] {format} frames of {height}x{width}, "
+                         f"got {got}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"{what} must be on the GPU: there is no CPU path in this package")
+    if frames.stride(1) != 1 or (frames.shape[0] > 1 and frames.stride(0) < fb):
+        raise ValueError(f"{what}: every frame must be contiguous (strides {tuple(frames.stride())})")
+
+
+@torch.no_grad()
+def yuv_to_rgb(frames: torch.Tensor, height: int, width: int, format: str, *, siting: str | None = None,
+               matrix: str = "bt709", colour_range: str = "limited", layout=None,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """[B, frame_stride] frames of `format` (a `YUV_FORMATS` name; uint8 at 8 bits, uint16 words of 10-bit codes at
+    10, above 1023 read as 1023) on the GPU -> planar RGB [B, 3, H, W] of the same dtype (`fiunet_yuv_to_rgb_u8` /
+    `fiunet_yuv_to_rgb_p10`).  layout: a `packed.PackedLayout` in samples or None for tight frames - uyvy422 / yuyv422
+    take a row pitch and a frame stride, the planar formats a frame stride only; `frames` may be a view whose frames
+    lie further apart.  siting None is "mpeg2"; matrix also takes "bt2020" at 10 bits."""
+    code, bits, _ = _yuv_format(format)
+    h, w = int(height), int(width)
+    lay = resolve_yuv_layout(layout, format, h, w)
+    flags = yuv_flags(format, siting, matrix, colour_range)
+    _check_yuv_frames(frames, h, w, "frames", format, lay)
+    dtype = frames.dtype
+    shape = (frames.shape[0], 3, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=frames.device)
+    elif out.dtype != dtype or tuple(out.shape) != shape or out.device != frames.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {str(dtype).split('.')[-1]} {shape} tensor on {frames.device}")
+    with torch.cuda.device(frames.device):
+        _native.yuv_to_rgb(frames, code, lay, out, h, w, flags, bits)
+    return out
+
+
+@torch.no_grad()
+def rgb_to_yuv(rgb: torch.Tensor, format: str, *, siting: str | None = None, matrix: str = "bt709",
+               colour_range: str = "limited", layout=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Planar RGB [B, 3, H, W] on the GPU (uint8, or uint16 of 10-bit codes for a 10-bit format) -> [B, frame_stride]
+    frames of `format` (`fiunet_rgb_to_yuv_u8` / `fiunet_rgb_p10_to_yuv`).  Samples outside the used columns of a
+    pitched row and between frames are left untouched (zero in a tensor made here).  `out` may be a view whose frames
+    lie further apart than frame_stride.  layout, siting, matrix: as for `yuv_to_rgb`."""
+    code, bits, _ = _yuv_format(format)
+    dtype = torch.uint16 if bits == 10 else torch.uint8
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != dtype or rgb.dim() != 4 or rgb.shape[1] != 3:
+        got = f"{rgb.dtype} {tuple(rgb.shape)}" if isinstance(rgb, torch.Tensor) else repr(type(rgb))
+        raise ValueError(f"rgb must be {str(dtype).split('.')[-1]} [B, 3, H, W] for {format}, got {got}")
+    b, _, h, w = rgb.shape
+    lay = resolve_yuv_layout(layout, format, h, w)
+    flags = yuv_flags(format, siting, matrix, colour_range)
+    if not rgb.is_cuda:
+        raise RuntimeError("rgb must be on the GPU: there is no CPU path in this package")
+    if not rgb.is_contiguous():
+        raise ValueError("rgb must be contiguous")
+    if out is None:
+        # (a pitched frame has bytes no pixel covers: they are never written, so a new one starts as zeros)
+        out = (torch.empty if lay == resolve_yuv_layout(None, format, h, w) else torch.zeros)(
+            (b, lay.frame_stride), dtype=dtype, device=rgb.device)
+    elif not isinstance(out, torch.Tensor) or out.device != rgb.device or out.shape[0] != b:
+        raise ValueError(f"out must hold {b} frames on {rgb.device}")
+    _check_yuv_frames(out, h, w, "out", format, lay)
+    with torch.cuda.device(rgb.device):
+        _native.rgb_to_yuv(rgb, out, code, lay, flags, bits)
+    return out
 
 
 def siting_of_y4m(colourspace: str) -> str:

@@ -44,6 +44,22 @@
 //            2^31; tests/test_p10_host.py recomputes it from the coefficients).  The encode stays below 2.1e8.  12 bits
 //            would overflow: not supported.
 //
+// 4:2:2 and 4:4:4 (the kernels are in yuv4xx.hip.h) extend this definition along its one remaining axis,
+// the sub-sampling pattern; coefficients, range, clamps, the Y row and the RGB stage above are unchanged, and chroma
+// reaches the RGB stage at the same x16 unrounded scale.
+//   4:4:4    encode, per pixel (n = 1): C = clamp((c_r R + c_g G + c_b B + centre S + S/2) >> 14)
+//            decode: Cb16 = 16 Cb, Cr16 = 16 Cr.  Siting has no meaning: accepted and ignored.
+//   4:2:2    the horizontal half of the 4:2:0 rule; chroma row y belongs to luma row y
+//            encode jpeg (centred): the sum over columns 2j, 2j+1, n = 2, shift 15; mpeg2 (co-sited with the even
+//            column): [1,2,1] over 2j-1, 2j, 2j+1, n = 4, shift 16; columns clamped into the image; bias
+//            centre n S + n S/2
+//            decode: the 4:2:0 horizontal taps times 4: jpeg 4 (3a + b); mpeg2 16a at an even x, 8 (a + b) at an odd x
+//            default siting where the caller gives none: mpeg2
+//            On chroma that does not change down a column this decode is the 4:2:0 decode, on RGB rows that come in
+//            equal pairs chroma row 2i of this encode is chroma row i of the 4:2:0 encode, bit for bit; every
+//            intermediate is bounded by its 4:2:0 counterpart, so the int32 bound above carries over
+//            (tests/test_yuv4xx_host.py recomputes it).
+//
 // All four kernels are HBM-bound elementwise work.  A thread covers 4 luma columns of a row (decode) or of a row pair
 // (encode), so a wave reads and writes 256 contiguous samples of every luma / RGB row; with W % 4 == 0 and aligned
 // bases (VEC) those are single 4-sample accesses (4 bytes at 8 bits, 8 bytes at 10), otherwise samples with the edge

@@ -13,6 +13,7 @@
 #include "metrics.hip.h"
 #include "colour.hip.h"
 #include "packed.hip.h"
+#include "yuv4xx.hip.h"
 #include "scene.hip.h"
 #include "retime.hip.h"
 
@@ -1690,6 +1691,216 @@ int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t*
     if ((rc = fiunet_p010_to_rgb_p10(frame2, in_layout, b, B, H, W, colour, stream))) return rc;
     if ((rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
     return fiunet_rgb_p10_to_p010(o, out, out_layout, B, H, W, colour, stream);
+}
+
+// ---- YUV 4:2:2 / 4:4:4 frames (csrc/yuv4xx.hip.h): planar and one-plane packed, <-> planar RGB ----
+// samples of one tight frame of `format` (bytes at 8 bits); 0: not a fiunet_yuv_format
+static size_t yuv_frame_samples(int format, int H, int W)
+{
+    switch (format) {
+    case FIUNET_YUV_422P: return (size_t)H * W + 2 * (size_t)H * ((W + 1) / 2);
+    case FIUNET_YUV_444P: return 3 * (size_t)H * W;
+    case FIUNET_YUV_UYVY422:
+    case FIUNET_YUV_YUYV422: return 2 * (size_t)H * W;
+    default: return 0;
+    }
+}
+
+// The caller's pitch and stride (0 = tight) -> the resolved layout, with every refusal that needs no pointer: before
+// any launch.  bits: the entry point's sample depth.
+static int resolve_yuv(int format, int bits, size_t row_pitch, size_t frame_stride, int B, int H, int W, unsigned colour,
+                       YuvLayout* lay)
+{
+    int rc;
+    if (bits == 10) {
+        if ((rc = check_colour_p10_flags(colour))) return rc;
+    } else if (colour & ~kColourFlags) {
+        return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits (FIUNET_YUV_BT2020 needs the 10-bit entry points)");
+    }
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    const size_t tight = yuv_frame_samples(format, H, W);
+    if (!tight) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_yuv_format");
+    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
+    if (row_pitch > big || frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: a value above 2^40");
+    if (yuv_is_packed(format)) {
+        if (bits != 8) return fail(FIUNET_ERR_INVALID_ARG, "format: uyvy422 / yuyv422 are 8-bit formats");
+        if (W & 1) return fail(FIUNET_ERR_INVALID_ARG, "uyvy422 / yuyv422 need an even width");
+        const size_t row = 2 * (size_t)W;
+        lay->row_pitch = row_pitch ? row_pitch : row;
+        if (lay->row_pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: row_pitch < 2*W");
+        lay->frame_stride = frame_stride ? frame_stride : (size_t)H * lay->row_pitch;
+        if (lay->frame_stride < (size_t)(H - 1) * lay->row_pitch + row)
+            return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: frame_stride does not cover the last row");
+        return FIUNET_OK;
+    }
+    if (row_pitch) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: planar frames are tight (row_pitch must be 0)");
+    lay->row_pitch = 0;
+    lay->frame_stride = frame_stride ? frame_stride : tight;
+    if (lay->frame_stride < tight) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: frame_stride smaller than one frame");
+    return FIUNET_OK;
+}
+
+extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
+// vector accesses: W and every pitch and stride a multiple of 4 samples, bases aligned to 4 samples
+template <typename T>
+static bool yuv_vec(const YuvLayout& lay, int W, const void* a, const void* b)
+{
+    return W % 4 == 0 && (lay.row_pitch | lay.frame_stride) % 4 == 0 &&
+           (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
+}
+
+template <typename T, int FMT>
+static void launch_yuv_to_rgb(bool vec, dim3 grid, hipStream_t st, const T* in, YuvLayout lay, T* out, int H, int W,
+                              const ColourCoef& k)
+{
+    if (vec)
+        hipLaunchKernelGGL((yuv_to_rgb_kernel<T, FMT, true>), grid, dim3(kColourBlock), 0, st, in, lay, out, H, W, k);
+    else
+        hipLaunchKernelGGL((yuv_to_rgb_kernel<T, FMT, false>), grid, dim3(kColourBlock), 0, st, in, lay, out, H, W, k);
+}
+
+template <typename T, int FMT>
+static void launch_rgb_to_yuv(bool vec, dim3 grid, hipStream_t st, const T* in, T* out, YuvLayout lay, int H, int W,
+                              const ColourCoef& k)
+{
+    if (vec)
+        hipLaunchKernelGGL((rgb_to_yuv_kernel<T, FMT, true>), grid, dim3(kColourBlock), 0, st, in, out, lay, H, W, k);
+    else
+        hipLaunchKernelGGL((rgb_to_yuv_kernel<T, FMT, false>), grid, dim3(kColourBlock), 0, st, in, out, lay, H, W, k);
+}
+
+template <typename T>
+static int yuv_to_rgb(const T* in, int format, size_t row_pitch, size_t frame_stride, T* out, int B, int H, int W,
+                      unsigned colour, int bits, void* stream)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    int rc;
+    YuvLayout lay;
+    if ((rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay))) return rc;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
+    const ColourCoef k = colour_coef(colour, bits);
+    const bool vec = yuv_vec<T>(lay, W, in, out);
+    hipStream_t st = (hipStream_t)stream;
+    if (format == FIUNET_YUV_422P) launch_yuv_to_rgb<T, FIUNET_YUV_422P>(vec, grid, st, in, lay, out, H, W, k);
+    else if (format == FIUNET_YUV_444P) launch_yuv_to_rgb<T, FIUNET_YUV_444P>(vec, grid, st, in, lay, out, H, W, k);
+    else if constexpr (sizeof(T) == 1) {
+        if (format == FIUNET_YUV_UYVY422) launch_yuv_to_rgb<T, FIUNET_YUV_UYVY422>(vec, grid, st, in, lay, out, H, W, k);
+        else launch_yuv_to_rgb<T, FIUNET_YUV_YUYV422>(vec, grid, st, in, lay, out, H, W, k);
+    }
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+template <typename T>
+static int rgb_to_yuv(const T* in, T* out, int format, size_t row_pitch, size_t frame_stride, int B, int H, int W,
+                      unsigned colour, int bits, void* stream)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    int rc;
+    YuvLayout lay;
+    if ((rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay))) return rc;
+    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
+    const ColourCoef k = colour_coef(colour, bits);
+    const bool vec = yuv_vec<T>(lay, W, in, out);
+    hipStream_t st = (hipStream_t)stream;
+    if (format == FIUNET_YUV_422P) launch_rgb_to_yuv<T, FIUNET_YUV_422P>(vec, grid, st, in, out, lay, H, W, k);
+    else if (format == FIUNET_YUV_444P) launch_rgb_to_yuv<T, FIUNET_YUV_444P>(vec, grid, st, in, out, lay, H, W, k);
+    else if constexpr (sizeof(T) == 1) {
+        if (format == FIUNET_YUV_UYVY422) launch_rgb_to_yuv<T, FIUNET_YUV_UYVY422>(vec, grid, st, in, out, lay, H, W, k);
+        else launch_rgb_to_yuv<T, FIUNET_YUV_YUYV422>(vec, grid, st, in, out, lay, H, W, k);
+    }
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_yuv_to_rgb_u8(const uint8_t* in, int format, size_t row_pitch, size_t frame_stride, uint8_t* out, int B,
+                         int H, int W, unsigned colour, void* stream)
+{
+    return yuv_to_rgb<uint8_t>(in, format, row_pitch, frame_stride, out, B, H, W, colour, 8, stream);
+}
+
+int fiunet_rgb_to_yuv_u8(const uint8_t* in, uint8_t* out, int format, size_t row_pitch, size_t frame_stride, int B,
+                         int H, int W, unsigned colour, void* stream)
+{
+    return rgb_to_yuv<uint8_t>(in, out, format, row_pitch, frame_stride, B, H, W, colour, 8, stream);
+}
+
+int fiunet_yuv_to_rgb_p10(const uint16_t* in, int format, size_t row_pitch, size_t frame_stride, uint16_t* out, int B,
+                          int H, int W, unsigned colour, void* stream)
+{
+    return yuv_to_rgb<uint16_t>(in, format, row_pitch, frame_stride, out, B, H, W, colour, 10, stream);
+}
+
+int fiunet_rgb_p10_to_yuv(const uint16_t* in, uint16_t* out, int format, size_t row_pitch, size_t frame_stride, int B,
+                          int H, int W, unsigned colour, void* stream)
+{
+    return rgb_to_yuv<uint16_t>(in, out, format, row_pitch, frame_stride, B, H, W, colour, 10, stream);
+}
+
+size_t fiunet_workspace_bytes_yuv(const fiunet_ctx* ctx, int B, int H, int W, int precision, int bits)
+{
+    if (bits == 8) return fiunet_workspace_bytes_yuv420(ctx, B, H, W, precision);
+    if (bits == 10) return fiunet_workspace_bytes_yuv420p10(ctx, B, H, W, precision);
+    g_err = "fiunet_workspace_bytes_yuv: bits must be 8 or 10";
+    return 0;
+}
+
+int fiunet_forward_yuv(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, int format, size_t in_row_pitch,
+                       size_t in_frame_stride, uint8_t* out, size_t out_row_pitch, size_t out_frame_stride, int B, int H,
+                       int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3) return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_yuv needs the RGB network (frame_channels 3)");
+    int rc;
+    YuvLayout lay;   // format, colour and both layouts are refused here, before the first launch
+    if ((rc = resolve_yuv(format, 8, in_row_pitch, in_frame_stride, B, H, W, colour, &lay)) ||
+        (rc = resolve_yuv(format, 8, out_row_pitch, out_frame_stride, B, H, W, colour, &lay)))
+        return rc;
+    const size_t need = fiunet_workspace_bytes_yuv(ctx, B, H, W, precision, 8);
+    if (need == 0) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    // [fiunet_forward_u8's workspace | frame1 RGB | frame2 RGB | output RGB], uint8 planar [B, 3, H, W] each
+    const size_t base = align256(fiunet_workspace_bytes_u8(ctx, B, H, W, precision));
+    const size_t rgb = align256((size_t)B * 3 * H * W);
+    uint8_t* a = (uint8_t*)workspace + base;
+    uint8_t* b = a + rgb;
+    uint8_t* o = b + rgb;
+    if ((rc = fiunet_yuv_to_rgb_u8(frame1, format, in_row_pitch, in_frame_stride, a, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_yuv_to_rgb_u8(frame2, format, in_row_pitch, in_frame_stride, b, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
+    return fiunet_rgb_to_yuv_u8(o, out, format, out_row_pitch, out_frame_stride, B, H, W, colour, stream);
+}
+
+int fiunet_forward_yuv_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, int format,
+                           size_t in_row_pitch, size_t in_frame_stride, uint16_t* out, size_t out_row_pitch,
+                           size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision, void* workspace,
+                           size_t workspace_bytes, void* stream)
+{
+    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3)
+        return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_yuv_p10 needs the RGB network (frame_channels 3)");
+    int rc;
+    YuvLayout lay;   // format, colour and both layouts are refused here, before the first launch
+    if ((rc = resolve_yuv(format, 10, in_row_pitch, in_frame_stride, B, H, W, colour, &lay)) ||
+        (rc = resolve_yuv(format, 10, out_row_pitch, out_frame_stride, B, H, W, colour, &lay)))
+        return rc;
+    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
+    const size_t need = fiunet_workspace_bytes_yuv(ctx, B, H, W, precision, 10);
+    if (need == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    // [fiunet_forward_p10's workspace | frame1 RGB | frame2 RGB | output RGB], uint16 planar [B, 3, H, W] each
+    const size_t base = align256(fiunet_workspace_bytes_p10(ctx, B, H, W, precision));
+    const size_t rgb = align256((size_t)B * 3 * H * W * 2);
+    uint16_t* a = (uint16_t*)((char*)workspace + base);
+    uint16_t* b = (uint16_t*)((char*)a + rgb);
+    uint16_t* o = (uint16_t*)((char*)b + rgb);
+    if ((rc = fiunet_yuv_to_rgb_p10(frame1, format, in_row_pitch, in_frame_stride, a, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_yuv_to_rgb_p10(frame2, format, in_row_pitch, in_frame_stride, b, B, H, W, colour, stream))) return rc;
+    if ((rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
+    return fiunet_rgb_p10_to_yuv(o, out, format, out_row_pitch, out_frame_stride, B, H, W, colour, stream);
 }
 
 // ---- packed RGB frames: rgb24 / bgr24 / rgba / bgra, rows a pitch apart, <-> planar RGB ----

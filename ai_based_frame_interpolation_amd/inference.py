@@ -289,6 +289,30 @@ def interpolate_sequence_rgb_packed(model, frames: torch.Tensor, height: int, wi
 
 
 @torch.no_grad()
+def interpolate_sequence_yuv(model, frames: torch.Tensor, height: int, width: int, format: str, batch: int = 8, *,
+                             scene_cut: float | None = None, **colour) -> torch.Tensor:
+    """factor-2 video loop of the RGB network on 4:2:2 / 4:4:4 video: device [N, F] tight frames of `format` (a
+    `colour.YUV_FORMATS` name; uint8 at 8 bits, uint16 at 10) of height x width -> [2N-1, F] = F0, M0, F1, ..., F(N-1), Mi
+    = model.forward_yuv(Fi, Fi+1, format=format, **colour).  The same contract as `interpolate_sequence_yuv420`:
+    originals sample for sample, middles written in place, a ragged last chunk padded.  The scene-cut sums run over every
+    sample of a frame.  colour: siting (None: "mpeg2") / matrix / colour_range."""
+    from .colour import YUV_FORMATS
+    thr = scene.check_threshold(scene_cut)
+    h, w = int(height), int(width)
+    if format not in YUV_FORMATS:
+        raise ValueError(f"format must be one of {list(YUV_FORMATS)}, got {format!r}")
+    if YUV_FORMATS[format][1] == 10:
+        def fwd10(a, b, out=None):
+            return _i16(model.forward_yuv(_u16(a.contiguous()), _u16(b.contiguous()), h, w, format=format,
+                                          out=_u16(out), **colour))
+        return _u16(_sequence(model, _i16(frames), fwd10, h, w, batch, thr, 10))
+
+    def fwd(a, b, out=None):
+        return model.forward_yuv(a.contiguous(), b.contiguous(), h, w, format=format, out=out, **colour)
+    return _sequence(model, frames, fwd, h, w, batch, thr, 8)
+
+
+@torch.no_grad()
 def interpolate_sequence_p10(model, frames: torch.Tensor, batch: int = 8, *, scene_cut: float | None = None) -> torch.Tensor:
     """factor-2 video loop on 10-bit frames: device uint16 [N,H,W] (or [N,C,H,W]) 10-bit codes -> [2N-1, ...] = F0, M0,
     F1, ..., F(N-1), where Mi = model.forward_p10(Fi, Fi+1).  Both networks.  The originals are copied sample for
@@ -464,7 +488,12 @@ class FrameInterpolator:
         Y4M.  raw "rgb24", "bgr24", "rgba" or "bgra": headerless tight packed RGB frames (`ffmpeg -f rawvideo -pix_fmt
         rgb24`), through the RGB network with their colour as it is (`interpolate_sequence_rgb_packed`):
         matrix and siting are not used; the alpha of an inserted rgba / bgra frame is the rounded average of its
-        neighbours', and scene_cut then counts the alpha bytes too."""
+        neighbours', and scene_cut then counts the alpha bytes too.  raw "yuv422p", "yuv444p", "yuv422p10le",
+        "yuv444p10le", "uyvy422" or "yuyv422": headerless tight 4:2:2 / 4:4:4 frames (`ffmpeg -f rawvideo -pix_fmt
+        yuv422p10le`: ProRes / DNxHR decodes, capture cards), through the RGB network at their own chroma resolution
+        (`interpolate_sequence_yuv`): matrix and siting apply as for nv12 (siting None: "mpeg2"; bt2020
+        at 10 bits), the range is limited; run the 10-bit formats in precision fp16.  Y4M tagged C422 / C444 is still
+        refused by the RGB network: such clips take this raw route."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")

@@ -32,7 +32,9 @@ Raw video (`interpolate_raw_stream`): headerless tight NV12 fram
 nv12` writes and reads, through the same engine with `interpolate_sequence_nv12` as the level: factor, fps, scene_cut
 and chunk_frames work as they do for Y4M (the retime and hold kernels see packed rows of samples, whatever their order).
 The packed RGB formats rgb24 / bgr24 / rgba / bgra take the same route with
-`interpolate_sequence_rgb_packed` as the level and no colour conversion.
+`interpolate_sequence_rgb_packed` as the level and no colour conversion.  The 4:2:2 / 4:4:4 formats yuv422p, yuv444p,
+yuv422p10le, yuv444p10le, uyvy422 and yuyv422 take it with `interpolate_sequence_yuv` as the level; the
+10-bit ones are two bytes per sample on the wire (little-endian words) and int16 words in the rings.
 
 With `fps=` (source / target rate = p / q, G = 2**time_depth) F is G in the levels, a chunk's result is its
 R = ceil(C x q / p) + 1 resampled frames, and the device holds them beside the grid:
@@ -54,7 +56,7 @@ from . import colour, imageio_lite, packed, scene
 from . import retime as _retime
 from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
                         interpolate_sequence_nv12, interpolate_sequence_p10, interpolate_sequence_rgb_packed,
-                        interpolate_sequence_yuv420, interpolate_sequence_yuv420p10)
+                        interpolate_sequence_yuv, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10)
 
 R_IN, R_OUT = 3, 2   # pinned input / output slots in the rings
 
@@ -174,13 +176,15 @@ def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
     return _Route(bits, row, out_row, run)
 
 
-RAW_FORMATS = ("nv12", "rgb24", "bgr24", "rgba", "bgra")
+RAW_FORMATS = ("nv12", "rgb24", "bgr24", "rgba", "bgra") + tuple(colour.YUV_FORMATS)
 
 
 def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, siting) -> _Route:
     """The route of headerless raw video (`raw`: one of RAW_FORMATS, tight frames), with its refusals.  Nothing in the
     stream says how it was made: for "nv12" siting None is "mpeg2" (what decoders produce) and the range is limited.
-    The packed RGB formats (packed.FORMATS) have no colour conversion: matrix and siting are not used."""
+    The packed RGB formats (packed.FORMATS) have no colour conversion: matrix and siting are not used.
+    The 4:2:2 / 4:4:4 formats (colour.YUV_FORMATS) take matrix and siting as "nv12" does; the 10-bit ones
+    give a 10-bit route, whose `row` counts 16-bit samples."""
     if raw not in RAW_FORMATS:
         raise ValueError(f"raw must be one of {list(RAW_FORMATS)} (or None: Y4M / .npy), got {raw!r}")
     for name, v in (("height", height), ("width", width)):
@@ -201,6 +205,18 @@ def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, sit
                 d = interpolate_sequence_rgb_packed(model, d, h, w, raw, batch)
             return d
         return _Route(8, row, row, run_packed)
+    if raw in colour.YUV_FORMATS:
+        bits = colour.YUV_FORMATS[raw][1]
+        row = colour.yuv_frame_samples(raw, h, w)   # (refuses an odd width of uyvy422 / yuyv422)
+        opts = dict(siting=siting, matrix=matrix, colour_range="limited")
+        colour.yuv_flags(raw, **opts)
+
+        def run_yuv(d, factor):
+            t = d.view(torch.uint16) if bits == 10 else d
+            for _ in range(_levels(factor)):
+                t = interpolate_sequence_yuv(model, t, h, w, raw, batch, **opts)
+            return t.view(torch.int16) if bits == 10 else t
+        return _Route(bits, row, row, run_yuv)
     opts = dict(siting="mpeg2" if siting is None else siting, matrix=matrix, colour_range="limited")
     colour.colour_flags(**opts)
     row = colour.i420_frame_bytes(h, w)
@@ -214,7 +230,8 @@ def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, sit
 
 class _RawReader:
     """`read_into` over headerless frames of `row` bytes from a binary file object (Y4MReader's interface).  A stream
-    that ends inside a frame is an error at that point."""
+    that ends inside a frame is an error at that point.  row: BYTES per frame on the wire (a 10-bit route's
+    samples x 2: little-endian words, what the rings' uint16 rows hold on a little-endian host)."""
 
     def __init__(self, f, row: int):
         self.f, self.row, self.frames = f, row, 0
@@ -666,7 +683,9 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     """Headerless raw video in (a path or a readable binary file: a pipe) -> the same format out (a path or a writable
     binary file): tight NV12 frames of height x width (`ffmpeg ... -f rawvideo -pix_fmt nv12 -`) through the RGB
     network, `interpolate_sequence_nv12` per level; or, with raw "rgb24" / "bgr24" / "rgba" / "bgra", tight packed RGB
-    frames (`-pix_fmt rgb24`), `interpolate_sequence_rgb_packed` per level, where matrix and siting are not used.  factor, scene_cut, chunk_frames (None: the whole clip resident)
+    frames (`-pix_fmt rgb24`), `interpolate_sequence_rgb_packed` per level, where matrix and siting are not used; or, with
+    raw "yuv422p" / "yuv444p" / "yuv422p10le" / "yuv444p10le" / "uyvy422" / "yuyv422", tight 4:2:2 / 4:4:4 frames
+    (`-pix_fmt yuv422p10le`; 10 bits: little-endian 16-bit words), `interpolate_sequence_yuv` per level.  factor, scene_cut, chunk_frames (None: the whole clip resident)
     and fps / time_depth / retime as for `interpolate_y4m_stream`; the stream carries no rate, so src_fps is required
     (with fps it sets the resampling; the output has fps, or src_fps x factor, frames per second - pass that rate to
     whatever reads the result).  siting None is "mpeg2", the range limited.  Every argument - the model's network, the
@@ -683,21 +702,22 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     plan = _plan_of(fps, src_rate, None, depth)
     if plan is not None:
         factor = plan.G
+    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire
     count = None
     if _is_path(src):
         if not os.path.exists(src):
             raise FileNotFoundError(f"Video file not found: {src}")
         st = os.stat(src)
         if stat.S_ISREG(st.st_mode):
-            if st.st_size % route.row:
+            if st.st_size % wire_row:
                 raise ValueError(f"{os.fspath(src)}: {st.st_size} bytes is not a whole number of {width}x{height} "
-                                 f"{raw} frames of {route.row} bytes")
-            count = st.st_size // route.row
+                                 f"{raw} frames of {wire_row} bytes")
+            count = st.st_size // wire_row
             if count == 0:
                 raise ValueError("no frames to interpolate")
     fin = open(src, "rb") if _is_path(src) else src
     try:
-        reader = _RawReader(fin, route.row)
+        reader = _RawReader(fin, wire_row)
         f, finish = _open_sink(dst)
         ok = False
         try:

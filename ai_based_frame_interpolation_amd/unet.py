@@ -532,6 +532,56 @@ class FrameInterpolationUNet(nn.Module):
         return out
 
     @torch.no_grad()
+    def forward_yuv(self, frame1: torch.Tensor, frame2: torch.Tensor, height: int, width: int, *, format: str,
+                    siting: str | None = None, matrix: str = "bt709", colour_range: str = "limited", layout=None,
+                    out_layout=None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The RGB network on 4:2:2 / 4:4:4 video: frames of `format` in (a `colour.YUV_FORMATS` name - "yuv422p",
+        "yuv444p", "yuv422p10le", "yuv444p10le", "uyvy422", "yuyv422"; uint8 at 8 bits, uint16 words of 10-bit codes at
+        10) -> interpolated frames of the same format, `fiunet_forward_yuv` / `fiunet_forward_yuv_p10`: bit for bit
+        `colour.yuv_to_rgb` on both -> `forward_u8` / `forward_p10` -> `colour.rgb_to_yuv`.  siting None
+        means "mpeg2" (what decoders and ffmpeg assume for 4:2:2; 4:4:4 has none); matrix also takes "bt2020" at 10
+        bits.  layout / out_layout: a `packed.PackedLayout` in samples or None for tight frames (uyvy422 / yuyv422: row
+        pitch and frame stride of a capture buffer; planar formats: a frame stride only); the tensors are [B,
+        frame_stride].  `out`: write there - frames contiguous, possibly further apart; bytes outside the used columns
+        and between frames are left untouched.  Use fp16 (or bf16x2, fp32) for the 10-bit formats: bf16 is about 5
+        codes off."""
+        from .colour import YUV_FORMATS, resolve_yuv_layout, yuv_flags
+        if format not in YUV_FORMATS:
+            raise ValueError(f"format must be one of {list(YUV_FORMATS)}, got {format!r}")
+        code, bits, _ = YUV_FORMATS[format]
+        dtype = torch.uint16 if bits == 10 else torch.uint8
+        h, w = int(height), int(width)
+        lay = resolve_yuv_layout(layout, format, h, w)
+        olay = resolve_yuv_layout(out_layout, format, h, w)
+        flags = yuv_flags(format, siting, matrix, colour_range)
+        if self.frame_channels != 3:
+            raise RuntimeError("forward_yuv runs the RGB network (frame_channels=3); this model is grayscale")
+        if (not isinstance(frame1, torch.Tensor) or not isinstance(frame2, torch.Tensor) or frame1.dim() != 2
+                or frame1.shape != frame2.shape or frame1.shape[1] != lay.frame_stride):
+            raise RuntimeError(f"expected two [B,{lay.frame_stride}] tensors ({format} frames of {h}x{w}) of equal "
+                               f"shape, got {tuple(getattr(frame1, 'shape', ()))} and "
+                               f"{tuple(getattr(frame2, 'shape', ()))}")
+        self._check_device_mode_dtype(frame1, frame2, (dtype,))
+        if not frame1.is_contiguous() or not frame2.is_contiguous():
+            raise ValueError("forward_yuv takes contiguous frames")
+        b = frame1.shape[0]
+        prec = self._precision_code()
+        ctx = self._context(frame1.device)
+        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=bits == 10)
+        shape = (b, olay.frame_stride)
+        if out is None:
+            # (a pitched frame has bytes no pixel covers: they are never written, so a new one starts as zeros)
+            out = (torch.empty if olay == resolve_yuv_layout(None, format, h, w) else torch.zeros)(
+                shape, dtype=dtype, device=frame1.device)
+        elif (out.dtype != dtype or tuple(out.shape) != shape or out.device != frame1.device
+              or out.stride(1) != 1 or (b > 1 and out.stride(0) < olay.frame_stride)):
+            raise ValueError(f"out must be a {str(dtype).split('.')[-1]} {shape} tensor on {frame1.device} whose "
+                             "frames are contiguous")
+        with torch.cuda.device(frame1.device):
+            ctx.forward_yuv(frame1, frame2, code, lay, out, olay, h, w, flags, prec, ws, bits)
+        return out
+
+    @torch.no_grad()
     def debug_activations(self, frame1, frame2, taps=None, with_up=False):
         """Parity-test hook: run one forward keeping every stage and return
         ({tap name: fp32 NCHW tensor}, output).  with_up: also the four upsampled + padded halves

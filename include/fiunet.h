@@ -310,6 +310,54 @@ int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t*
                         int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* YUV 4:2:2 and 4:4:4 frames (ABI v8, added without a version bump: nothing existing changed): what
+ * ProRes / DNxHR / XDCAM decode to (yuv422p10le), what SDI and HDMI capture cards deliver (uyvy422 / yuyv422) and what
+ * screen and grading sources that stay in YUV hold (yuv444p / yuv444p10le).  The arithmetic extends that of the 4:2:0
+ * entry points (csrc/colour.hip.h, csrc/yuv4xx.hip.h): coefficients, ranges, clamps, the Y row and the RGB stage are
+ * the same; 4:4:4 chroma is coded per pixel and decoded as it is (the siting flag is ignored); 4:2:2 is the horizontal
+ * half of the 4:2:0 rule, chroma row y belonging to luma row y.  The format names are ffmpeg's -pix_fmt names; the
+ * sample depth is the entry point's: 8 bits (uint8_t) or 10 (uint16_t words holding the code, little-endian in a file;
+ * a word above 1023 reads as 1023). */
+enum fiunet_yuv_format {
+    FIUNET_YUV_422P = 0,     /* planar: Y plane H x W, then U, then V, each H x ceil(W/2)  (yuv422p, yuv422p10le) */
+    FIUNET_YUV_444P = 1,     /* planar: Y, U, V each H x W                                 (yuv444p, yuv444p10le) */
+    FIUNET_YUV_UYVY422 = 2,  /* one plane, U0 Y0 V0 Y1 per two pixels; 8 bits only, W even (uyvy422) */
+    FIUNET_YUV_YUYV422 = 3   /* one plane, Y0 U0 Y1 V0 per two pixels; 8 bits only, W even (yuyv422) */
+};
+/* Frames of `format` -> planar RGB [B, 3, H, W] (the layout fiunet_forward_u8 / fiunet_forward_p10 take), and back.
+ * Planar formats: frames are tight, `frame_stride` SAMPLES apart (0 = the frame size: 2*H*W for 4:2:2 with W even,
+ * H*W + 2*H*ceil(W/2) in general, 3*H*W for 4:4:4); `row_pitch` must be 0; any H, W >= 1.  The two one-plane formats:
+ * rows of 2*W bytes `row_pitch` bytes apart (0 = 2*W), frames `frame_stride` bytes apart (0 = H*row_pitch); bytes
+ * between 2*W and row_pitch, and between frames, are never read and never written.  With W % 4 == 0 and every base,
+ * pitch and stride a multiple of 4 samples a thread's accesses are vector accesses, otherwise per sample.
+ * `colour`: as for the 4:2:0 calls of the same depth.  FIUNET_ERR_INVALID_ARG, before any launch: NULL pointers, an
+ * unknown format, a one-plane format at 10 bits, FIUNET_YUV_BT2020 at 8 bits, an odd W with a one-plane format, a
+ * row_pitch below 2*W (or not 0 with a planar format), a frame_stride that does not cover a frame.  Device pointers;
+ * asynchronous on `stream`; no allocation, no synchronisation. */
+int fiunet_yuv_to_rgb_u8(const uint8_t* in, int format, size_t row_pitch, size_t frame_stride, uint8_t* out, int B,
+                         int H, int W, unsigned colour, void* stream);
+int fiunet_rgb_to_yuv_u8(const uint8_t* in, uint8_t* out, int format, size_t row_pitch, size_t frame_stride, int B,
+                         int H, int W, unsigned colour, void* stream);
+int fiunet_yuv_to_rgb_p10(const uint16_t* in, int format, size_t row_pitch, size_t frame_stride, uint16_t* out, int B,
+                          int H, int W, unsigned colour, void* stream);
+int fiunet_rgb_p10_to_yuv(const uint16_t* in, uint16_t* out, int format, size_t row_pitch, size_t frame_stride, int B,
+                          int H, int W, unsigned colour, void* stream);
+/* Workspace of fiunet_forward_yuv (bits 8: that of fiunet_forward_yuv420) and fiunet_forward_yuv_p10 (bits 10: that
+ * of fiunet_forward_yuv420p10); 0 on bad arguments. */
+size_t fiunet_workspace_bytes_yuv(const fiunet_ctx* ctx, int B, int H, int W, int precision, int bits);
+/* The RGB network on frames of `format`: frame1 and frame2 B contiguous frames in (in_row_pitch, in_frame_stride), the
+ * B interpolated frames to `out` in (out_row_pitch, out_frame_stride).  Bit for bit fiunet_yuv_to_rgb_u8 (both inputs)
+ * -> fiunet_forward_u8_strided -> fiunet_rgb_to_yuv_u8, and at 10 bits fiunet_yuv_to_rgb_p10 -> fiunet_forward_p10 ->
+ * fiunet_rgb_p10_to_yuv; every argument is checked before the first launch.  FIUNET_ERR_UNSUPPORTED on a context with
+ * frame_channels != 3.  Neither allocates nor synchronises. */
+int fiunet_forward_yuv(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, int format, size_t in_row_pitch,
+                       size_t in_frame_stride, uint8_t* out, size_t out_row_pitch, size_t out_frame_stride, int B, int H,
+                       int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes, void* stream);
+int fiunet_forward_yuv_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, int format,
+                           size_t in_row_pitch, size_t in_frame_stride, uint16_t* out, size_t out_row_pitch,
+                           size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* Packed RGB frames (ABI v8, added without a version bump: nothing existing changed): interleaved
  * pixels, what `ffmpeg -f rawvideo -pix_fmt rgb24 | bgr24 | rgba | bgra` pipes and what a screen grab, a render or an
  * image library (BGR rows a line size apart) leaves in memory.  They reach the RGB network with their colour as it is:

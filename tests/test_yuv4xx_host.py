@@ -1,0 +1,438 @@
+"""CPU: 4:2:2 / 4:4:4 YUV video - the tests' numpy restatement against the 4:2:0 one and the textbook
+formulas, the int32 bound, the format table and frame sizes, the layout rules in Python and in the library, the raw
+route's refusals (before any GPU work, leaving no output), the command line, and the header against the binding.  No GPU
+is touched."""
+import ctypes
+import io
+import itertools
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import colour10_ref as C10  # noqa: E402
+import colour_ref as C8  # noqa: E402
+import yuv4xx_ref as R  # noqa: E402
+
+import ai_based_frame_interpolation_amd as P  # noqa: E402
+from ai_based_frame_interpolation_amd import _native, cli, colour, packed, stream  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ["fiunet_yuv_to_rgb_u8", "fiunet_rgb_to_yuv_u8", "fiunet_yuv_to_rgb_p10", "fiunet_rgb_p10_to_yuv",
+       "fiunet_workspace_bytes_yuv", "fiunet_forward_yuv", "fiunet_forward_yuv_p10"]
+NAMES = ["yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le", "uyvy422", "yuyv422"]
+CONFIGS8 = [(m, r) for m in ("bt601", "bt709") for r in ("limited", "full")]
+CONFIGS10 = [(m, r) for m in ("bt601", "bt709", "bt2020") for r in ("limited", "full")]
+CONFIGS = [(8, m, r) for m, r in CONFIGS8] + [(10, m, r) for m, r in CONFIGS10]
+
+
+def _rand(rng, shape, bits):
+    """Random samples over the full code range; at 10 bits some words above 1023 (read as 1023)."""
+    if bits == 8:
+        return rng.integers(0, 256, shape).astype(np.uint8)
+    x = rng.integers(0, 1024, shape)
+    x[rng.random(shape) < 0.05] = rng.integers(1024, 65536)
+    return x.astype(np.uint16)
+
+
+# ---- the reference against the 4:2:0 reference -------------------------------------------------------------------
+@pytest.mark.parametrize("siting", ["jpeg", "mpeg2"])
+@pytest.mark.parametrize("bits", [8, 10])
+@pytest.mark.parametrize("h,w", [(6, 9), (5, 8), (1, 1), (4, 2)])
+def test_decode_equals_420_on_column_constant_chroma(bits, siting, h, w):
+    """Chroma that does not change down a column: the 4:2:2 decode is the 4:2:0 decode (3a + a = 4a), bit for bit."""
+    ref = R.ref_of(bits)
+    rng = np.random.default_rng(h * 100 + w + bits)
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+    y = _rand(rng, (2, h, w), bits)
+    u1, v1 = _rand(rng, (2, 1, wc), bits), _rand(rng, (2, 1, wc), bits)
+    f420 = R.join_planar(y, np.repeat(u1, hc, 1), np.repeat(v1, hc, 1))
+    dec420 = ref.yuv420p10_to_rgb if bits == 10 else ref.yuv420_to_rgb
+    for matrix, rng_ in (CONFIGS10 if bits == 10 else CONFIGS8):
+        want = dec420(f420, h, w, siting, matrix, rng_)
+        got = R.planes_to_rgb(y, np.repeat(u1, h, 1), np.repeat(v1, h, 1), "422", bits, siting, matrix, rng_)
+        assert got.dtype == want.dtype and np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("siting", ["jpeg", "mpeg2"])
+@pytest.mark.parametrize("bits", [8, 10])
+@pytest.mark.parametrize("h,w", [(6, 9), (4, 8), (2, 1), (8, 2)])
+def test_encode_equals_420_on_equal_row_pairs(bits, siting, h, w):
+    """RGB rows in equal pairs: chroma row 2i of the 4:2:2 encode is chroma row i of the 4:2:0 encode, bit for bit."""
+    ref = R.ref_of(bits)
+    rng = np.random.default_rng(h * 100 + w + bits)
+    rgb = np.repeat(_rand(rng, (2, 3, h // 2, w), bits), 2, axis=2)
+    enc420 = ref.rgb_to_yuv420p10 if bits == 10 else ref.rgb_to_yuv420
+    hc, wc = h // 2, (w + 1) // 2
+    for matrix, rng_ in (CONFIGS10 if bits == 10 else CONFIGS8):
+        f = enc420(rgb, siting, matrix, rng_)
+        y, u, v = R.rgb_to_planes(rgb, "422", bits, siting, matrix, rng_)
+        assert np.array_equal(y.reshape(2, -1), f[:, :h * w])
+        assert np.array_equal(u[:, 0::2].reshape(2, -1), f[:, h * w:h * w + hc * wc])
+        assert np.array_equal(v[:, 0::2].reshape(2, -1), f[:, h * w + hc * wc:])
+        assert np.array_equal(u[:, 0::2], u[:, 1::2]) and np.array_equal(v[:, 0::2], v[:, 1::2])
+
+
+@pytest.mark.parametrize("bits,matrix,colour_range", CONFIGS)
+def test_grey_encodes_to_centre_chroma_exactly(bits, matrix, colour_range):
+    top = 1024 if bits == 10 else 256
+    centre = top // 2
+    v = np.arange(top).reshape(1, 1, 1, top)
+    rgb = np.broadcast_to(v, (1, 3, 1, top)).astype(np.uint16 if bits == 10 else np.uint8)
+    for kind, siting in (("444", "mpeg2"), ("422", "jpeg"), ("422", "mpeg2")):
+        # (4:2:2 sums grey neighbours of different levels: every channel sum is the same number, so chroma is still centre)
+        _, cb, cr = R.rgb_to_planes(rgb, kind, bits, siting, matrix, colour_range)
+        assert (cb == centre).all() and (cr == centre).all()
+
+
+@pytest.mark.parametrize("bits,matrix,colour_range", CONFIGS)
+def test_encode_within_one_code_of_textbook(bits, matrix, colour_range):
+    """Flat footprints (n = 1: 4:4:4; n = 2, 4: the two 4:2:2 sitings) against the float64 textbook formulas, within the
+    one code tests/test_colour_host.py allows the 4:2:0 encode."""
+    ref = R.ref_of(bits)
+    k = ref.coef(matrix, colour_range)
+    top = 1023 if bits == 10 else 255
+    g = np.unique(np.r_[np.arange(0, top + 1, 8 if bits == 10 else 3), top]).astype(np.int64)
+    r, gg, b = (a.ravel() for a in np.meshgrid(g, g, g, indexing="ij"))
+    _, tcb, tcr = ref.textbook_encode(r, gg, b, matrix, colour_range)
+    for n in (1, 2, 4):
+        cb, cr = (c.astype(np.int64) for c in R.encode_c(n * r, n * gg, n * b, n, k, bits))
+        assert np.abs(cb - np.clip(tcb, 0, top)).max() <= 1
+        assert np.abs(cr - np.clip(tcr, 0, top)).max() <= 1
+
+
+@pytest.mark.parametrize("bits,matrix,colour_range", CONFIGS)
+def test_decode_within_one_code_of_textbook(bits, matrix, colour_range):
+    """Flat chroma through every decode pattern (all of them give 16 x the sample) against the textbook formulas."""
+    ref = R.ref_of(bits)
+    top = 1023 if bits == 10 else 255
+    lo, yhi, chi = ((16, 235, 240) if bits == 8 else (64, 940, 960)) if colour_range == "limited" else (0, top, top)
+    step = 8 if bits == 10 else 3
+    ys = np.unique(np.r_[np.arange(lo, yhi + 1, step), yhi])
+    cs = np.unique(np.r_[np.arange(lo, chi + 1, step), chi])
+    y, cb, cr = (a.reshape(1, -1, 1) for a in np.meshgrid(ys, cs, cs, indexing="ij"))
+    dt = np.uint16 if bits == 10 else np.uint8
+    yy = np.repeat(y, 4, axis=2).astype(dt)
+    want = [np.clip(t, 0, top) for t in ref.textbook_decode(yy, cb, cr, matrix, colour_range)]
+    for kind, siting, wc in (("444", "mpeg2", 4), ("422", "jpeg", 2), ("422", "mpeg2", 2)):
+        got = R.planes_to_rgb(yy, np.repeat(cb, wc, 2).astype(dt), np.repeat(cr, wc, 2).astype(dt), kind, bits, siting,
+                              matrix, colour_range)
+        for ch in range(3):
+            assert np.abs(got[:, ch].astype(np.int64) - want[ch]).max() <= 1
+
+
+@pytest.mark.parametrize("bits,matrix,colour_range", CONFIGS)
+def test_int32_bounds_of_the_new_patterns(bits, matrix, colour_range):
+    """The worst-case intermediates over every input (the corners of the sample cube: every term is linear in one
+    input), recomputed from the coefficients for the new patterns.  Decode: every pattern hands the RGB stage chroma x16
+    in [0, 16 max] - 4:4:4 16c; 4:2:2 4 (3a + b), 16a, 8 (a + b) - the range of the 4:2:0 up-sampling, so the RGB stage's
+    bound is the 4:2:0 one (6.0e8 at 10 bits, 1.6e8 at 8).  Encode: n = 1, 2, 4 with shifts 14, 15, 16 stay below the
+    4:2:0 encode's n = 4, 8 (2.1e8 at 10 bits)."""
+    ref = R.ref_of(bits)
+    k = ref.coef(matrix, colour_range)
+    top = 1023 if bits == 10 else 255
+    centre = 512 if bits == 10 else 128
+    # the decode patterns at the corners: the largest chroma x16 any of them makes
+    a = np.array([0, top], np.int64)
+    ups = [16 * a.max(), (4 * (3 * a[:, None] + a[None, :])).max(), (8 * (a[:, None] + a[None, :])).max()]
+    assert max(ups) == 16 * top
+    yoff = k["yoff"]
+    dec = 0
+    for y, u, v in itertools.product((0, top), (0, 16 * top), (0, 16 * top)):
+        yy = 16 * k["dy"] * (y - yoff) + (1 << 17)
+        uu, vv = u - 16 * centre, v - 16 * centre
+        dec = max(dec, abs(yy + k["dcr"] * vv), abs(yy + k["dgb"] * uu + k["dgr"] * vv), abs(yy + k["dcb"] * uu))
+    assert dec <= (6.0e8 if bits == 10 else 1.6e8) < 2 ** 31
+    enc, enc420 = 0, 0
+    for n, sh, store in ((1, 14, "new"), (2, 15, "new"), (4, 16, "both"), (8, 17, "old")):
+        bias = (centre << sh) + (1 << (sh - 1))
+        for row in (("cbr", "cbg", "cbb"), ("crr", "crg", "crb")):
+            worst = sum(abs(k[c]) for c in row) * n * top + bias
+            if store in ("new", "both"):
+                enc = max(enc, worst)
+            if store in ("old", "both"):
+                enc420 = max(enc420, worst)
+    assert enc <= enc420 <= 2.1e8 < 2 ** 31
+
+
+@pytest.mark.parametrize("fmt", ["uyvy422", "yuyv422"])
+def test_reference_pack_unpack(fmt):
+    rng = np.random.default_rng(7)
+    h, w = 3, 6
+    y, u, v = (rng.integers(0, 256, s).astype(np.uint8) for s in ((2, h, w), (2, h, w // 2), (2, h, w // 2)))
+    fr = R.pack422(y, u, v, fmt)
+    assert fr.shape == (2, 2 * h * w)
+    first = fr[0, :4].tolist()
+    want = [u[0, 0, 0], y[0, 0, 0], v[0, 0, 0], y[0, 0, 1]] if fmt == "uyvy422" else \
+        [y[0, 0, 0], u[0, 0, 0], y[0, 0, 1], v[0, 0, 0]]
+    assert first == [int(t) for t in want]
+    for a, b in zip(R.unpack422(fr, fmt, h, w), (y, u, v)):
+        assert np.array_equal(a, b)
+    rp, fs = 2 * w + 5, h * (2 * w + 5) + 3
+    pitched = R.pack422(y, u, v, fmt, rp, fs, fill=0xA5)
+    assert pitched.shape == (2, fs) and (pitched == 0xA5).sum() >= 2 * (fs - 2 * h * w)
+    for a, b in zip(R.unpack422(pitched, fmt, h, w, rp), (y, u, v)):
+        assert np.array_equal(a, b)
+
+
+# ---- formats, frame sizes, layouts ---------------------------------------------------------------------------------
+def test_format_table():
+    assert list(colour.YUV_FORMATS) == NAMES == list(R.FORMATS)
+    assert {n: (v[1], v[2]) for n, v in colour.YUV_FORMATS.items()} == R.FORMATS
+    src = open(os.path.join(ROOT, "include", "fiunet.h")).read()
+    for enum, name in (("422P", "yuv422p"), ("444P", "yuv444p"), ("UYVY422", "uyvy422"), ("YUYV422", "yuyv422")):
+        assert re.search(rf"FIUNET_YUV_{enum} = {colour.YUV_FORMATS[name][0]}\b", src), name
+    assert colour.YUV_FORMATS["yuv422p10le"][0] == colour.YUV_FORMATS["yuv422p"][0]
+    assert colour.YUV_FORMATS["yuv444p10le"][0] == colour.YUV_FORMATS["yuv444p"][0]
+    assert set(NAMES) < set(stream.RAW_FORMATS) and "nv12" in stream.RAW_FORMATS and "rgb24" in stream.RAW_FORMATS
+    assert P.YUV_FORMATS is colour.YUV_FORMATS and P.yuv_to_rgb is colour.yuv_to_rgb
+    assert P.rgb_to_yuv is colour.rgb_to_yuv and callable(P.interpolate_sequence_yuv)
+
+
+@pytest.mark.parametrize("h,w", [(37, 53), (38, 54), (1, 1), (2, 3), (48, 64)])
+def test_frame_samples(h, w):
+    wc = (w + 1) // 2
+    for fmt in ("yuv422p", "yuv422p10le"):
+        assert colour.yuv_frame_samples(fmt, h, w) == h * w + 2 * h * wc == R.frame_samples(fmt, h, w)
+    for fmt in ("yuv444p", "yuv444p10le"):
+        assert colour.yuv_frame_samples(fmt, h, w) == 3 * h * w == R.frame_samples(fmt, h, w)
+    for fmt in ("uyvy422", "yuyv422"):
+        if w % 2:
+            with pytest.raises(ValueError, match="even width"):
+                colour.yuv_frame_samples(fmt, h, w)
+        else:
+            assert colour.yuv_frame_samples(fmt, h, w) == 2 * h * w == R.frame_samples(fmt, h, w)
+
+
+def test_layouts():
+    h, w = 6, 8
+    for fmt in ("uyvy422", "yuyv422"):
+        assert colour.resolve_yuv_layout(None, fmt, h, w) == packed.PackedLayout(16, 96)
+        assert colour.resolve_yuv_layout(packed.PackedLayout(20), fmt, h, w) == (20, 120)
+        edge = (20, 5 * 20 + 16)
+        assert colour.resolve_yuv_layout(edge, fmt, h, w) == edge
+        with pytest.raises(ValueError, match="row_pitch"):
+            colour.resolve_yuv_layout((15, 0), fmt, h, w)
+        with pytest.raises(ValueError, match="frame_stride"):
+            colour.resolve_yuv_layout((20, edge[1] - 1), fmt, h, w)
+        with pytest.raises(ValueError, match="even width"):
+            colour.resolve_yuv_layout(None, fmt, h, 7)
+    assert colour.resolve_yuv_layout(None, "yuv422p", h, w) == (0, 96)
+    assert colour.resolve_yuv_layout((0, 200), "yuv444p10le", h, w) == (0, 200)
+    with pytest.raises(ValueError, match="row_pitch"):
+        colour.resolve_yuv_layout((8, 0), "yuv422p", h, w)
+    with pytest.raises(ValueError, match="frame_stride"):
+        colour.resolve_yuv_layout((0, 95), "yuv422p", h, w)
+    for bad in ((-1, 0), (0, 1.5), (True, 0), (1 << 41, 0), (0, 0, 0)):
+        with pytest.raises(ValueError, match="layout"):
+            colour.resolve_yuv_layout(bad, "uyvy422", h, w)
+
+
+def test_tensor_api_refusals_before_gpu_work():
+    h, w = 6, 8
+    x = torch.zeros((1, 96), dtype=torch.uint8)
+    rgb = torch.zeros((1, 3, h, w), dtype=torch.uint8)
+    with pytest.raises(ValueError, match="format"):
+        colour.yuv_to_rgb(x, h, w, "yuv420p")
+    with pytest.raises(ValueError, match="format"):
+        colour.rgb_to_yuv(rgb, "v210")
+    with pytest.raises(ValueError, match="even width"):
+        colour.yuv_to_rgb(x, h, 7, "uyvy422")
+    with pytest.raises(ValueError, match="even width"):
+        colour.rgb_to_yuv(torch.zeros((1, 3, h, 7), dtype=torch.uint8), "yuyv422")
+    with pytest.raises(ValueError, match="matrix"):
+        colour.yuv_to_rgb(x, h, w, "yuv422p", matrix="bt2020")
+    with pytest.raises(ValueError, match="matrix"):
+        colour.rgb_to_yuv(rgb, "uyvy422", matrix="bt2020")
+    assert colour.yuv_flags("yuv422p10le", None, "bt2020", "full") == \
+        _native.YUV_MPEG2 | _native.YUV_BT2020 | _native.YUV_FULL_RANGE
+    with pytest.raises(ValueError, match="siting"):
+        colour.yuv_to_rgb(x, h, w, "yuv444p", siting="left")
+    with pytest.raises(ValueError, match="uint16"):
+        colour.yuv_to_rgb(x, h, w, "yuv422p10le")
+    with pytest.raises(ValueError, match="uint16"):
+        colour.rgb_to_yuv(rgb, "yuv444p10le")
+    with pytest.raises(ValueError, match="frames of 6x8"):
+        colour.yuv_to_rgb(x[:, :-1], h, w, "yuv422p")
+    with pytest.raises(RuntimeError, match="GPU"):
+        colour.yuv_to_rgb(x, h, w, "yuv422p")
+    with pytest.raises(RuntimeError, match="GPU"):
+        colour.rgb_to_yuv(rgb, "uyvy422")
+    m3 = P.FrameInterpolationUNet(bilinear=True, frame_channels=3)
+    m1 = P.FrameInterpolationUNet(bilinear=True, frame_channels=1)
+    with pytest.raises(ValueError, match="format"):
+        m3.forward_yuv(x, x, h, w, format="nv12")
+    with pytest.raises(ValueError, match="even width"):
+        m3.forward_yuv(x, x, h, 7, format="uyvy422")
+    with pytest.raises(ValueError, match="matrix"):
+        m3.forward_yuv(x, x, h, w, format="yuv422p", matrix="bt2020")
+    with pytest.raises(RuntimeError, match="grayscale"):
+        m1.forward_yuv(x, x, h, w, format="yuv422p")
+    with pytest.raises(ValueError, match="format"):
+        P.interpolate_sequence_yuv(m3, x, h, w, "yuv411p")
+
+
+# ---- the library's host-side checks -------------------------------------------------------------------------------
+def test_library_argument_checks(hip_lib_built):
+    """Every refusal is made on the host, before any launch (no device here: a launch would fail with another status)."""
+    lib = _native.lib()
+    buf = ctypes.create_string_buffer(64)   # never dereferenced
+    p = ctypes.addressof(buf)
+    INVALID, BAD_SHAPE = 1, 2
+    h, w = 16, 16
+
+    def err():
+        return lib.fiunet_last_error_string().decode()
+    for dec, enc, bits in ((lib.fiunet_yuv_to_rgb_u8, lib.fiunet_rgb_to_yuv_u8, 8),
+                           (lib.fiunet_yuv_to_rgb_p10, lib.fiunet_rgb_p10_to_yuv, 10)):
+        for call in (lambda fmt, rp, fs, hh, ww, c: dec(p, fmt, rp, fs, p, 1, hh, ww, c, None),
+                     lambda fmt, rp, fs, hh, ww, c: enc(p, p, fmt, rp, fs, 1, hh, ww, c, None)):
+            assert call(4, 0, 0, h, w, 0) == INVALID and "format" in err()
+            assert call(-1, 0, 0, h, w, 0) == INVALID
+            assert call(0, 0, 0, h, w, 1 << 31) == INVALID
+            assert call(0, 0, 0, 0, w, 0) == BAD_SHAPE
+            assert call(0, 16, 0, h, w, 0) == INVALID and "row_pitch" in err()      # planar frames are tight
+            assert call(0, 0, 511, h, w, 0) == INVALID and "frame_stride" in err()  # a 4:2:2 frame is 512 samples
+            assert call(1, 0, 767, h, w, 0) == INVALID and "frame_stride" in err()  # a 4:4:4 frame is 768
+            if bits == 8:
+                assert call(0, 0, 0, h, w, _native.YUV_BT2020) == INVALID            # BT.2020 at 8 bits
+                assert call(2, 0, 0, h, 15, 0) == INVALID and "even" in err()
+                assert call(3, 31, 0, h, w, 0) == INVALID and "row_pitch" in err()
+                assert call(2, 36, 15 * 36 + 31, h, w, 0) == INVALID and "frame_stride" in err()
+            else:
+                assert call(0, 0, 0, h, w, _native.YUV_BT709 | _native.YUV_BT2020) == INVALID
+                assert call(2, 0, 0, h, w, 0) == INVALID and "8-bit" in err()        # packed at 10 bits
+                assert call(3, 0, 0, h, w, 0) == INVALID
+        assert dec(None, 0, 0, 0, p, 1, h, w, 0, None) == INVALID
+        assert enc(p, None, 0, 0, 0, 1, h, w, 0, None) == INVALID
+    assert lib.fiunet_workspace_bytes_yuv(None, 1, 64, 64, 0, 8) == 0
+    assert lib.fiunet_workspace_bytes_yuv(None, 1, 64, 64, 0, 12) == 0
+    for fwd in (lib.fiunet_forward_yuv, lib.fiunet_forward_yuv_p10):
+        assert fwd(None, p, p, 0, 0, 0, p, 0, 0, 1, 64, 64, 0, 0, p, 64, None) == INVALID
+
+
+# ---- the raw route: refusals before any GPU work ------------------------------------------------------------------
+@pytest.fixture
+def no_gpu(monkeypatch):
+    def boom(*a, **k):
+        raise AssertionError("GPU work started before the arguments were checked")
+    monkeypatch.setattr(torch.Tensor, "pin_memory", boom)
+    monkeypatch.setattr(stream, "_run", boom)
+    monkeypatch.setattr(stream, "_run_whole", boom)
+
+
+def _fi(frame_channels):
+    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=frame_channels)
+    return P.FrameInterpolator(model=m, device="cpu")
+
+
+def _no_output(tmp_path):
+    return [p.name for p in tmp_path.iterdir() if p.name.startswith("out")] == []
+
+
+GOOD = dict(raw="yuv422p", width=8, height=6, src_fps=24)
+
+
+@pytest.mark.parametrize("cf,out,kw,match", [
+    (3, "out.yuv", dict(raw="yuv420p10le"), "raw must be one of"),
+    (3, "out.yuv", dict(raw="v210"), "raw must be one of"),
+    (3, "out.yuv", dict(raw="nv21"), "raw must be one of"),
+    (3, "out.yuv", dict(raw="rgb48le"), "raw must be one of"),
+    (3, "out.yuv", dict(raw="uyvy422", width=7), "even width"),
+    (3, "out.yuv", dict(raw="yuyv422", width=7), "even width"),
+    (3, "out.yuv", dict(matrix="bt2020"), "matrix"),
+    (3, "out.yuv", dict(raw="uyvy422", matrix="bt2020"), "matrix"),
+    (3, "out.yuv", dict(siting="left"), "siting"),
+    (1, "out.yuv", {}, "grayscale"),
+    (1, "out.yuv", dict(raw="yuv444p10le"), "grayscale"),
+    (3, "out.npy", {}, "no .npy output"),
+    (3, "out.yuv", dict(width=None), "width"),
+    (3, "out.yuv", dict(height=None), "height"),
+    (3, "out.yuv", dict(src_fps=None), "src_fps"),
+    (3, "out.yuv", dict(raw="yuv444p"), "whole number"),        # (the file gets 48 more bytes: 2 1/3 frames)
+    (3, "out.yuv", dict(raw="yuv422p10le"), "whole number"),    # 1.5 frames of two-byte samples
+    (3, "out.yuv", dict(chunk_frames=0), "chunk_frames"),
+], ids=["420p10", "v210", "nv21", "rgb48le", "odd-uyvy", "odd-yuyv", "bt2020-8bit", "bt2020-uyvy", "siting", "gray",
+        "gray-444p10", "npy", "no-width", "no-height", "no-src-fps", "file-size-444", "file-size-10bit", "chunk"])
+def test_raw_route_refusals(tmp_path, no_gpu, cf, out, kw, match):
+    src = tmp_path / "in.yuv"
+    n = 3 * colour.yuv_frame_samples("yuv422p", 6, 8) + (48 if kw.get("raw") == "yuv444p" else 0)
+    src.write_bytes(bytes(n))
+    with pytest.raises(ValueError, match=match):
+        _fi(cf).interpolate_video(str(src), str(tmp_path / out), **dict(GOOD, **kw))
+    assert _no_output(tmp_path)
+
+
+@pytest.mark.parametrize("fmt", NAMES)
+def test_raw_route_rows(fmt):
+    """The route of every format: rows in samples, 8 or 10 bits; bt2020 passes at 10 bits only."""
+    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3)
+    bits = R.FORMATS[fmt][0]
+    r = stream._raw_route(m, fmt, 6, 8, False, 2, "bt709", None)
+    assert (r.bits, r.row, r.out_row) == (bits, R.frame_samples(fmt, 6, 8), R.frame_samples(fmt, 6, 8))
+    assert r.ndtype == (np.uint16 if bits == 10 else np.uint8)
+    if bits == 10:
+        stream._raw_route(m, fmt, 6, 8, False, 2, "bt2020", "jpeg")
+    for bad in ("nv21", "rgb48le"):
+        with pytest.raises(ValueError, match="raw must be one of"):
+            stream._raw_route(m, bad, 6, 8, False, 2, "bt709", None)
+
+
+@pytest.mark.parametrize("fmt", ["yuv422p", "yuv422p10le", "uyvy422"])
+def test_truncated_stream_is_an_error_at_that_point(tmp_path, monkeypatch, fmt):
+    """A pipe that ends inside a frame: the reader raises where the data stops, two-byte samples included (the run is
+    replaced by one that only reads, so no GPU is needed); whole frames before it are read as little-endian words."""
+    seen = []
+
+    def read_only(model, route, reader, write, *a, **k):
+        buf = np.zeros((1, route.row), route.ndtype)
+        while True:
+            k_ = reader.read_into(buf, 1)
+            if not k_:
+                return 0
+            seen.append(buf[:k_].copy())
+    monkeypatch.setattr(stream, "_run_whole", read_only)
+    item = 2 if fmt.endswith("10le") else 1
+    samples = colour.yuv_frame_samples(fmt, 6, 8)
+    data = (np.arange(2 * samples) % 1024).astype("<u2" if item == 2 else np.uint8)
+    out = tmp_path / "out.yuv"
+    kw = dict(GOOD, raw=fmt)
+    with pytest.raises(ValueError, match=f"ends inside a frame \\(7 of {samples * item} bytes of frame 2\\)"):
+        _fi(3).interpolate_video(io.BytesIO(data.tobytes() + bytes(7)), str(out), **kw)
+    assert not out.exists()
+    got = np.concatenate(seen)
+    assert got.shape == (2, samples) and np.array_equal(got.ravel(), data)
+
+
+# ---- the CLI ----------------------------------------------------------------------------------------------------
+def test_cli_raw_arguments():
+    base = ["video", "--input", "-", "--output", "-"]
+    for fmt in NAMES:
+        a = cli.parse_args(base + ["--raw", fmt, "--size", "64x48", "--src-fps", "30000/1001", "--fps", "60",
+                                   "--scene-cut", "10", "--chunk-frames", "16", "--matrix", "bt601", "--siting", "jpeg"])
+        assert a.raw == fmt and a.size == (64, 48) and a.matrix == "bt601" and a.siting == "jpeg"
+    for bad in ("nv21", "rgb48le", "v210", "yuv420p"):
+        with pytest.raises(SystemExit):
+            cli.parse_args(base + ["--raw", bad, "--size", "64x48", "--src-fps", "24"])
+    assert "yuv422p10le" in cli.__doc__ and "uyvy422" in cli.__doc__
+
+
+# ---- header and binding -----------------------------------------------------------------------------------------
+def test_new_header_names_are_in_the_binding():
+    src = open(os.path.join(ROOT, "include", "fiunet.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = re.findall(r"\b(fiunet_[a-z0-9_]+)\s*\(", src)
+    assert set(NEW) <= set(declared) and set(NEW) <= set(_native.SYMBOLS)
+    assert re.search(r"#define FIUNET_ABI_VERSION 8\b", src) and _native.ABI_VERSION == 8
+    for name in NEW:   # the name patterns three older tests read the header by
+        assert not re.search(r"nv12|p010|packed", name) and not name.startswith("fiunet_plane_")
+    # the new names stand before the packed RGB / surface block, which stays the tail
+    sym = list(_native.SYMBOLS)
+    assert max(sym.index(n) for n in NEW) < sym.index("fiunet_packed_to_rgb_u8")
+    assert sym[-1] == "fiunet_forward_p010"
+    mk = open(os.path.join(ROOT, "ai_based_frame_interpolation_amd", "csrc", "Makefile")).read()
+    assert "yuv4xx.hip.h" in re.search(r"^HDRS := (.*)$", mk, flags=re.M).group(1)
