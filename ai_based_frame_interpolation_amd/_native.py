@@ -26,12 +26,13 @@ ABI_MIN_COMPAT = 4     # oldest A/B library (FIUNET_LIB) whose shared entry poin
 FP32, BF16, BF16X2, FP16 = 0, 1, 2, 3   # include/fiunet.h: enum fiunet_precision
 OPT_UNFUSED, OPT_KEEP_ALL, OPT_GATHER_UPSAMPLE = 1, 2, 16
 OPT_RNE_WEIGHTS, OPT_NO_DITHER = 32, 64
+WEIGHT_PREPS = ("host", "device")   # Context.load_state_dict(prep=): fiunet_load_weights / fiunet_load_weights_device
 YUV_MPEG2, YUV_BT709, YUV_FULL_RANGE, YUV_BT2020 = 1, 2, 4, 8   # include/fiunet.h: enum fiunet_colour
 
 #: every symbol include/fiunet.h declares (tests/test_abi.py checks the header against this)
 SYMBOLS = (
     "fiunet_abi_version", "fiunet_last_error_string", "fiunet_create", "fiunet_destroy",
-    "fiunet_set_options", "fiunet_load_weights", "fiunet_prepare_precision", "fiunet_workspace_bytes", "fiunet_forward",
+    "fiunet_set_options", "fiunet_load_weights", "fiunet_load_weights_device", "fiunet_prepare_precision", "fiunet_workspace_bytes", "fiunet_forward",
     "fiunet_min_unsplit_batch",
     "fiunet_forward_strip",
     "fiunet_workspace_bytes_u8", "fiunet_forward_u8", "fiunet_forward_u8_strided", "fiunet_preprocess_u8",
@@ -133,6 +134,8 @@ def lib() -> ctypes.CDLL:
     L.fiunet_set_options.argtypes = [vp, ctypes.c_uint]
     L.fiunet_load_weights.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_char_p),
                                       ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]
+    L.fiunet_load_weights_device.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_char_p),
+                                             ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64), vp]
     L.fiunet_prepare_precision.argtypes = [vp, ci]
     L.fiunet_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
     L.fiunet_workspace_bytes.restype = sz
@@ -265,21 +268,42 @@ class Context:
         fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         check(fn(self._h, layer, tile, ksplit), "fiunet_debug_force_cfg")
 
-    def load_state_dict(self, sd) -> None:
+    def load_state_dict(self, sd, prep: str = "host") -> None:
+        """prep "host": fiunet_load_weights - every tensor goes to the host, where one thread folds, packs and rounds, then
+        uploads.  prep "device": fiunet_load_weights_device - the tensors stay (or are put by torch) on this context's GPU
+        as contiguous fp32 and the library's kernels prepare the same bytes there, asynchronously on the current stream,
+        into the buffers of the load before when there was one."""
+        if prep not in WEIGHT_PREPS:
+            raise ValueError(f"prep must be one of {list(WEIGHT_PREPS)}, got {prep!r}")
+        dev = torch.device("cuda", self.device_index) if prep == "device" else torch.device("cpu")
         names, ptrs, numels, keep = [], [], [], []
         for k, v in sd.items():
             if k.endswith("num_batches_tracked"):
                 continue
-            t = v.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            keep.append(t)
+            t = v.detach().to(device=dev, dtype=torch.float32).contiguous()
+            keep.append(t)   # (alive until the call returns; a converted copy's memory is then reused in stream order)
             names.append(k.encode())
             ptrs.append(t.data_ptr())
             numels.append(t.numel())
         n = len(names)
-        check(lib().fiunet_load_weights(
-            self._h, n, (ctypes.c_char_p * n)(*names), (ctypes.c_void_p * n)(*ptrs),
-            (ctypes.c_int64 * n)(*numels)), "fiunet_load_weights")
+        args = (self._h, n, (ctypes.c_char_p * n)(*names), (ctypes.c_void_p * n)(*ptrs), (ctypes.c_int64 * n)(*numels))
+        if prep == "device":
+            with torch.cuda.device(dev):
+                check(lib().fiunet_load_weights_device(*args, torch.cuda.current_stream(dev).cuda_stream),
+                      "fiunet_load_weights_device")
+        else:
+            check(lib().fiunet_load_weights(*args), "fiunet_load_weights")
         self._prepared = set()
+
+    def weight_buffer(self, layer: int, which: int):
+        """Diagnostic (tests; not part of the ABI): (device pointer, bytes) of one prepared weight buffer -
+        fiunet_debug_weight_buffer in csrc/fiunet.hip lists the layers and buffers; (None, 0) where there is none."""
+        fn = lib().fiunet_debug_weight_buffer
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                       ctypes.POINTER(ctypes.c_size_t)]
+        p, b = ctypes.c_void_p(), ctypes.c_size_t()
+        check(fn(self._h, layer, which, ctypes.byref(p), ctypes.byref(b)), "fiunet_debug_weight_buffer")
+        return p.value, b.value
 
     def prepare(self, precision: int) -> None:
         """Weight copies a precision needs beyond the load's (bf16x2: the two-piece copies; fp16: the fp16 copies; built on

@@ -115,6 +115,8 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--model", default="best_model.pth", help="Path to trained model")
     v.add_argument("--device", default="auto", help="Device to use (cuda/auto)")
     v.add_argument("--precision", default=None, help="fp32 / bf16x2 / bf16 / fp16 (default: the library's)")
+    v.add_argument("--weight-prep", default=None, choices=("host", "device"),
+                   help="Where the checkpoint is folded, packed and rounded (default: host, or FIUNET_WEIGHT_PREP)")
     v.add_argument("--matrix", default="bt709", help="YUV matrix of colour video through the RGB network")
     v.add_argument("--siting", type=_siting, default=None, help="Chroma siting jpeg / mpeg2 (default: from the tag)")
     v.add_argument("--scene-cut", type=_scene_cut, default=None, help="Scene-cut threshold in (0, 100], or none")
@@ -142,6 +144,8 @@ def parser() -> argparse.ArgumentParser:
     e.add_argument("--methods", type=_methods, default=("unet", "linear", "repeat"),
                    help="Comma-separated: unet, linear (blend), repeat (frame duplication)")
     e.add_argument("--precision", default=None, help="fp32 / bf16x2 / bf16 / fp16 (default: the library's)")
+    e.add_argument("--weight-prep", default=None, choices=("host", "device"),
+                   help="Where the checkpoint is folded, packed and rounded (default: host, or FIUNET_WEIGHT_PREP)")
     e.add_argument("--matrix", default="bt709", help="YUV matrix of colour video through the RGB network")
     e.add_argument("--siting", type=_siting, default=None, help="Chroma siting jpeg / mpeg2 (default: from the tag)")
     e.add_argument("--batch", type=int, default=8, help="Frame pairs per forward")
@@ -174,7 +178,7 @@ def run_video(a: argparse.Namespace) -> int:
     device = torch.device("cuda" if a.device in ("auto", None) else a.device)
     fc = frame_channels_of(torch.load(a.model, map_location="cpu"))
     with contextlib.redirect_stdout(sys.stderr):   # standard output carries the video only
-        model = load_model(a.model, device, a.precision, frame_channels=fc)
+        model = load_model(a.model, device, a.precision, frame_channels=fc, weight_prep=a.weight_prep)
     fi = FrameInterpolator(model=model, device=device, batch=a.batch)
     src = sys.stdin.buffer if a.input == "-" else a.input
     dst = sys.stdout.buffer if a.output == "-" else a.output
@@ -195,7 +199,7 @@ def run_evaluate(a: argparse.Namespace) -> dict:
     device = torch.device("cuda" if a.device in ("auto", None) else a.device)
     fc = frame_channels_of(torch.load(a.model, map_location="cpu"))
     with contextlib.redirect_stdout(sys.stderr):
-        model = load_model(a.model, device, a.precision, frame_channels=fc)
+        model = load_model(a.model, device, a.precision, frame_channels=fc, weight_prep=a.weight_prep)
     src = sys.stdin.buffer if a.input == "-" else a.input
     res = holdout.score_video(model, src, triplets=a.triplets, methods=a.methods, batch=a.batch,
                               chunk_frames=a.chunk_frames, matrix=a.matrix, siting=a.siting, src_fps=a.src_fps)

@@ -16,6 +16,7 @@
 #include "yuv4xx.hip.h"
 #include "scene.hip.h"
 #include "retime.hip.h"
+#include "weights.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -83,51 +84,8 @@ struct ConvWeights {
     float* shift = nullptr;
 };
 
-// bf16 kernels: packed weight row R (= MFMA A row within its 32-cout group) holds this cout, so
-// that accumulator tiles 2g and 2g+1 give a lane 8 consecutive couts (conv3x3_mfma.hip.h epilogue)
-inline int bf16_row_to_cout(int R)
-{
-    const int r = R & 15;
-    return (R & ~31) + (r >> 2) * 8 + ((R >> 4) & 1) * 4 + (r & 3);
-}
-
-uint16_t f32_to_bf16_rne(float f)
-{
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// bf16 rounding of a conv filter's weights with error feedback: each weight goes to one of its two
-// bf16 neighbours (per-weight error < 1 ulp instead of <= 1/2), whichever keeps the filter's running sum
-// of rounding errors `carry` closest to zero.  Round-to-nearest leaves every filter with a random net
-// error of ~0.29 ulp * sqrt(9 Cin), i.e. a fixed gain / offset error per output channel that the
-// (positive, smooth) post-ReLU inputs turn into a systematic error of the layer; with the feedback the
-// summed error of a filter stays below one ulp.  Measured on the bf16 path (540x960 / 1080p): output
-// rel-L2 vs fp32 1.26 -> 0.64 % (seeded checkpoint), 3.3 -> 2.4 % (bench network); PSNR difference to
-// the CPU reference on the interpolating checkpoint 0.042-0.072 -> 0.025-0.048 dB.  The carry runs over
-// the whole filter (all input channels, taps innermost); restarting it per input channel is worse.
-inline uint16_t f32_to_bf16_feedback(float v, double& carry)
-{
-    uint32_t u;
-    std::memcpy(&u, &v, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return f32_to_bf16_rne(v);  // inf / NaN
-    const uint16_t toward0 = (uint16_t)(u >> 16);
-    uint32_t b0 = (uint32_t)toward0 << 16;
-    float f0;
-    std::memcpy(&f0, &b0, 4);
-    if (f0 == v) return toward0;  // representable (zeros stay zeros)
-    const uint16_t away = (uint16_t)(toward0 + 1);
-    uint32_t b1 = (uint32_t)away << 16;
-    float f1;
-    std::memcpy(&f1, &b1, 4);
-    const double e0 = (double)v - f0, e1 = (double)v - f1;
-    const bool pick0 = std::fabs(carry + e0) <= std::fabs(carry + e1);
-    carry += pick0 ? e0 : e1;
-    return pick0 ? toward0 : away;
-}
+// (bf16_row_to_cout, f32_to_bf16_rne, f32_to_bf16_feedback: weights.hip.h - one definition for the host loop of
+// fiunet_load_weights and the kernels of fiunet_load_weights_device)
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -161,6 +119,7 @@ struct fiunet_ctx {
     int force_tile[NCONV] = {0};     // diagnostic overrides of choose_conv_cfg per conv (fiunet_debug_force_cfg; tools/cfg_sweep.py)
     int force_ksplit[NCONV] = {0};
     std::vector<void*> owned;
+    hipEvent_t load_done = nullptr;  // recorded behind the kernels of fiunet_load_weights_device (fiunet_prepare_precision waits for it)
     // per-layer HIP-event profiling (fiunet_profile_*): NCONV+1 events per recorded forward
     bool profiling = false;
     std::vector<hipEvent_t> ev_pool;
@@ -189,8 +148,12 @@ void free_weights(fiunet_ctx* ctx)
     ctx->loaded = false;
     ctx->x2_ready = false;
     ctx->f16_ready = false;
-    for (auto& c : ctx->conv) c.w_x2 = c.w_f16 = nullptr;     // (fiunet_prepare_precision reuses a non-null copy)
-    for (auto& c : ctx->convt) c.w_x2 = c.w_f16 = nullptr;
+    // (fiunet_prepare_precision and fiunet_load_weights_device reuse a non-null buffer: none may outlive its memory)
+    for (auto& c : ctx->conv) { c.w_f32 = c.w_bf16 = c.w_x2 = c.w_f16 = nullptr; c.scale = c.shift = nullptr; }
+    for (auto& c : ctx->convt) { c.w_f32 = c.w_bf16 = c.w_x2 = c.w_f16 = nullptr; c.bias = nullptr; }
+    ctx->head_w = ctx->head_b = nullptr;
+    ctx->stem_w_split = nullptr;
+    ctx->stamps = nullptr;
 }
 
 thread_local std::string* g_name_out = nullptr;  // where the next conv launch reports its kernel
@@ -941,6 +904,7 @@ int fiunet_destroy(fiunet_ctx* ctx)
     if (!ctx) return FIUNET_OK;
     (void)hipSetDevice(ctx->device);
     free_weights(ctx);
+    if (ctx->load_done) (void)hipEventDestroy(ctx->load_done);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     delete ctx;
     return FIUNET_OK;
@@ -1109,6 +1073,132 @@ int fiunet_load_weights(fiunet_ctx* ctx, int n, const char* const* names,
     return FIUNET_OK;
 }
 
+int fiunet_load_weights_device(fiunet_ctx* ctx, int n, const char* const* names,
+                               const float* const* device_ptrs, const int64_t* numels, void* stream)
+{
+    if (!ctx || n < 0 || !names || !device_ptrs || !numels)
+        return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    std::map<std::string, std::pair<const float*, int64_t>> tab;
+    for (int i = 0; i < n; ++i)
+        if (names[i] && device_ptrs[i]) tab[names[i]] = {device_ptrs[i], numels[i]};
+    auto get = [&](const std::string& k, int64_t want, const float** out) -> int {
+        auto it = tab.find(k);
+        if (it == tab.end()) return fail(FIUNET_ERR_MISSING_WEIGHT, "missing state-dict key " + k);
+        if (it->second.second != want)
+            return fail(FIUNET_ERR_MISSING_WEIGHT, "size mismatch for " + k + ": got " +
+                            std::to_string(it->second.second) + ", want " + std::to_string(want));
+        *out = it->second.first;
+        return FIUNET_OK;
+    };
+    // 1. every key, in the host entry's order (the same first complaint), before anything on the context or the device
+    //    changes: a failed call leaves the weights of the load before it in place
+    WpTable t;
+    std::memset(&t, 0, sizeof(t));
+    const int* kCout = ctx->cout;
+    int rc;
+    for (int i = 0; i < NCONV; ++i) {
+        const int blk = i / 2, second = i % 2;
+        const std::string pre = std::string(kBlockPrefix[blk]) + ".double_conv.";
+        const std::string wk = pre + (second ? "3" : "0") + ".weight";
+        const std::string bn = pre + (second ? "4" : "1");
+        WpConv& L = t.conv[i];
+        L.cout = kCout[i];
+        L.cin = i == 0 ? 2 * ctx->cf : conv_cin(kCout, ctx->bilinear, i);
+        if ((rc = get(wk, (int64_t)L.cout * L.cin * 9, &L.w))) return rc;
+        if ((rc = get(bn + ".weight", L.cout, &L.gamma))) return rc;
+        if ((rc = get(bn + ".bias", L.cout, &L.beta))) return rc;
+        if ((rc = get(bn + ".running_mean", L.cout, &L.mean))) return rc;
+        if ((rc = get(bn + ".running_var", L.cout, &L.var))) return rc;
+    }
+    const float* ct_bias[4] = {nullptr, nullptr, nullptr, nullptr};
+    t.nconvt = ctx->bilinear ? 0 : 4;
+    for (int k = 0; k < t.nconvt; ++k) {
+        WpConvT& L = t.convt[k];
+        L.cin = kCout[kSrc1[10 + 2 * k]];
+        L.cout = L.cin / 2;
+        const std::string pre = "unet.up" + std::to_string(k + 1) + ".up.";
+        if ((rc = get(pre + "weight", (int64_t)L.cin * L.cout * 4, &L.w))) return rc;
+        if ((rc = get(pre + "bias", L.cout, &ct_bias[k]))) return rc;
+    }
+    const float *head_w, *head_b;
+    if ((rc = get("unet.outc.conv.weight", (int64_t)ctx->cf * 64, &head_w))) return rc;
+    if ((rc = get("unet.outc.conv.bias", ctx->cf, &head_b))) return rc;
+
+    // 2. the prepared buffers: the ones a load before this one left (their sizes depend on the architecture alone, which a
+    //    context keeps for life) - then nothing below allocates, frees or waits for the device - or new ones
+    HIP_TRY(hipSetDevice(ctx->device));
+    auto buf = [&](auto** p, size_t bytes) -> int {
+        if (*p) return FIUNET_OK;
+        void* d = nullptr;
+        HIP_TRY(hipMalloc(&d, bytes));
+        ctx->owned.push_back(d);
+        *p = static_cast<std::remove_reference_t<decltype(*p)>>(d);
+        return FIUNET_OK;
+    };
+    if (!ctx->load_done) HIP_TRY(hipEventCreateWithFlags(&ctx->load_done, hipEventDisableTiming));
+    for (int i = 0; i < NCONV; ++i) {
+        ConvWeights& cw = ctx->conv[i];
+        WpConv& L = t.conv[i];
+        const size_t nel = (size_t)9 * L.cin * L.cout;
+        if ((rc = buf(&cw.scale, (size_t)L.cout * 4))) return rc;
+        if ((rc = buf(&cw.shift, (size_t)L.cout * 4))) return rc;
+        if ((rc = buf(&cw.w_f32, nel * 4))) return rc;
+        if (i > 0 && (rc = buf(&cw.w_bf16, nel * 2))) return rc;
+        L.scale = cw.scale; L.shift = cw.shift; L.w_f32 = (float*)cw.w_f32; L.w_bf16 = (uint16_t*)cw.w_bf16;
+    }
+    if (ctx->cf == 1) {
+        if ((rc = buf(&ctx->stem_w_split, (size_t)2 * 64 * 32 * 2))) return rc;
+        t.stem_split = (uint16_t*)ctx->stem_w_split;
+    }
+    for (int k = 0; k < t.nconvt; ++k) {
+        auto& ct = ctx->convt[k];
+        WpConvT& L = t.convt[k];
+        const size_t nel = (size_t)4 * L.cin * L.cout;
+        if ((rc = buf(&ct.w_f32, nel * 4))) return rc;
+        if ((rc = buf(&ct.w_bf16, nel * 2))) return rc;
+        if ((rc = buf(&ct.bias, (size_t)L.cout * 4))) return rc;
+        L.w_f32 = (float*)ct.w_f32; L.w_bf16 = (uint16_t*)ct.w_bf16;
+    }
+    if ((rc = buf(&ctx->head_w, (size_t)ctx->cf * 64 * 4))) return rc;
+    if ((rc = buf(&ctx->head_b, (size_t)ctx->cf * 4))) return rc;
+#if defined(FIUNET_STAMP) || defined(FIUNET_CLOCK)
+    if (!ctx->stamps) {
+        if ((rc = buf(&ctx->stamps, kStampWaves * kStampRec * 8))) return rc;
+        HIP_TRY(hipMemset(ctx->stamps, 0, kStampWaves * kStampRec * 8));
+    }
+#endif
+
+    // 3. the kernels (weights.hip.h), asynchronous on `stream`.  From here on the buffers change: the copies a precision
+    //    derives from them are stale exactly as after a host load (kept allocated: fiunet_prepare_precision packs into them)
+    hipStream_t s = (hipStream_t)stream;
+    ctx->loaded = false;
+    ctx->x2_ready = false;
+    ctx->f16_ready = false;
+    for (int i = 0; i < NCONV; ++i) { ctx->conv[i].cin = t.conv[i].cin; ctx->conv[i].cout = t.conv[i].cout; }
+    for (int k = 0; k < t.nconvt; ++k) { ctx->convt[k].cin = t.convt[k].cin; ctx->convt[k].cout = t.convt[k].cout; }
+    const unsigned gy = (unsigned)(NCONV - 1 + t.nconvt);
+    hipLaunchKernelGGL(wp_fold_bn_kernel, dim3(4, NCONV), dim3(256), 0, s, t);   // (cout <= 1024 = 4 x 256)
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(wp_pack_f32_kernel, dim3(512, gy + 1), dim3(256), 0, s, t);
+    HIP_TRY(hipGetLastError());
+    if (ctx->flags & FIUNET_OPT_RNE_WEIGHTS)  // read at LOAD time
+        hipLaunchKernelGGL(wp_pack_bf16_rne_kernel, dim3(512, gy), dim3(256), 0, s, t);
+    else   // (at most 1024 conv filters, 4 x 512 ConvTranspose2d filters in a layer = 32 x 64)
+        hipLaunchKernelGGL(wp_pack_bf16_feedback_kernel, dim3(32, gy), dim3(64), 0, s, t);
+    HIP_TRY(hipGetLastError());
+    if (t.stem_split) {
+        hipLaunchKernelGGL(wp_stem_split_kernel, dim3(1), dim3(64), 0, s, t);
+        HIP_TRY(hipGetLastError());
+    }
+    for (int k = 0; k < t.nconvt; ++k)
+        HIP_TRY(hipMemcpyAsync(ctx->convt[k].bias, ct_bias[k], (size_t)t.convt[k].cout * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->head_w, head_w, (size_t)ctx->cf * 64 * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->head_b, head_b, (size_t)ctx->cf * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipEventRecord(ctx->load_done, s));
+    ctx->loaded = true;
+    return FIUNET_OK;
+}
+
 int fiunet_prepare_precision(fiunet_ctx* ctx, int precision)
 {
     if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "ctx is NULL");
@@ -1117,6 +1207,8 @@ int fiunet_prepare_precision(fiunet_ctx* ctx, int precision)
     if (precision == FIUNET_FP16) {
         if (ctx->f16_ready) return FIUNET_OK;
         HIP_TRY(hipSetDevice(ctx->device));
+        // the packs below run on this device's null stream: behind a device-side load's kernels, whichever stream those are on
+        if (ctx->load_done) HIP_TRY(hipStreamWaitEvent(nullptr, ctx->load_done, 0));
         // fp16 weights, packed on the device from the fp32 copy (BatchNorm scale folded in) like the bf16 copy: ~35 MB more
         auto pack16 = [&](const void* w32, int cin, int cout, int convt, void** out) -> int {
             const size_t n = (size_t)cin * (convt ? 4 : 9) * cout;
@@ -1143,6 +1235,8 @@ int fiunet_prepare_precision(fiunet_ctx* ctx, int precision)
     }
     if (precision != FIUNET_BF16X2 || ctx->x2_ready) return FIUNET_OK;   // fp32 / bf16 copies are made by the load
     HIP_TRY(hipSetDevice(ctx->device));
+    // the packs below run on this device's null stream: behind a device-side load's kernels, whichever stream those are on
+    if (ctx->load_done) HIP_TRY(hipStreamWaitEvent(nullptr, ctx->load_done, 0));
     // two-piece weights [wh | wl], packed on the device from the fp32 copy (BatchNorm scale folded in): ~69 MB more
     // (a copy that a failed earlier attempt already allocated is packed again in place: a retry allocates nothing twice)
     auto pack = [&](const void* w32, int cin, int cout, int convt, void** out) -> int {
@@ -2447,6 +2541,41 @@ int fiunet_debug_force_cfg(fiunet_ctx* ctx, int layer, int tile, int ksplit)
     }
     ctx->force_tile[layer] = tile;
     ctx->force_ksplit[layer] = ksplit;
+    return FIUNET_OK;
+}
+
+// diagnostic (not part of the ABI, no declaration in include/fiunet.h): where one prepared weight buffer lives and how
+// many bytes it has, for comparing two contexts byte for byte (tests/test_gpu_weight_prep.py).  layer 0..17 = the convs,
+// 18..21 = the ConvTranspose2d of up1..up4, 22 = the 1x1 head; which: 0 scale, 1 shift, 2 w_f32 (the head: its weight),
+// 3 w_bf16, 4 stem_w_split (layer 0), 5 bias (ConvTranspose2d, head).  A buffer this context does not have (or a
+// combination that names none) answers NULL and 0 bytes.
+int fiunet_debug_weight_buffer(const fiunet_ctx* ctx, int layer, int which, const void** ptr, size_t* bytes)
+{
+    if (!ctx || !ptr || !bytes || layer < 0 || layer > NCONV + 4 || which < 0 || which > 5)
+        return fail(FIUNET_ERR_INVALID_ARG, "fiunet_debug_weight_buffer: bad arguments");
+    if (!ctx->loaded) return fail(FIUNET_ERR_NOT_LOADED, "fiunet_debug_weight_buffer before a load");
+    const void* p = nullptr;
+    size_t b = 0;
+    if (layer < NCONV) {
+        const ConvWeights& cw = ctx->conv[layer];
+        const size_t nel = (size_t)9 * cw.cin * cw.cout;
+        if (which == 0) { p = cw.scale; b = (size_t)cw.cout * 4; }
+        else if (which == 1) { p = cw.shift; b = (size_t)cw.cout * 4; }
+        else if (which == 2) { p = cw.w_f32; b = nel * 4; }
+        else if (which == 3) { p = cw.w_bf16; b = nel * 2; }
+        else if (which == 4 && layer == 0) { p = ctx->stem_w_split; b = (size_t)2 * 64 * 32 * 2; }
+    } else if (layer < NCONV + 4) {
+        const auto& ct = ctx->convt[layer - NCONV];
+        const size_t nel = (size_t)4 * ct.cin * ct.cout;
+        if (which == 2) { p = ct.w_f32; b = nel * 4; }
+        else if (which == 3) { p = ct.w_bf16; b = nel * 2; }
+        else if (which == 5) { p = ct.bias; b = (size_t)ct.cout * 4; }
+    } else {
+        if (which == 2) { p = ctx->head_w; b = (size_t)ctx->cf * 64 * 4; }
+        else if (which == 5) { p = ctx->head_b; b = (size_t)ctx->cf * 4; }
+    }
+    *ptr = p;
+    *bytes = p ? b : 0;
     return FIUNET_OK;
 }
 

@@ -90,10 +90,12 @@ def postprocess_image(tensor: torch.Tensor) -> np.ndarray:
     return _native.postprocess_u8(t).squeeze().cpu().numpy()
 
 
-def load_model(model_path, device, precision=None, frame_channels=1):
+def load_model(model_path, device, precision=None, frame_channels=1, weight_prep=None):
     """Construct bilinear=True, load `{'model_state_dict': ...}` or a bare state-dict, move to
-    device, eval (inference.py:77-97).  FileNotFoundError if the file is missing (:80-81)."""
-    model = FrameInterpolationUNet(bilinear=True, frame_channels=frame_channels, precision=precision)
+    device, eval (inference.py:77-97).  FileNotFoundError if the file is missing (:80-81).  weight_prep: "host" /
+    "device" / None = the default (FrameInterpolationUNet)."""
+    model = FrameInterpolationUNet(bilinear=True, frame_channels=frame_channels, precision=precision,
+                                   weight_prep=weight_prep)
     if not os.path.exists(model_path):
         raise FileNotFoundError(f"Model file not found: {model_path}")
     checkpoint = torch.load(model_path, map_location="cpu")

@@ -43,11 +43,21 @@ class InterpolationService:
 
     def __init__(self, model_path: Optional[str] = None, device: str = "cuda", precision: Optional[str] = None,
                  model: Optional[FrameInterpolationUNet] = None, target_size: Optional[Tuple[int, int]] = (256, 256),
-                 use_graph: bool = True):
+                 use_graph: bool = True, weight_prep: Optional[str] = None):
         self.device = torch.device("cuda" if device in ("auto", None) else device)
         if self.device.type != "cuda":
             raise RuntimeError("InterpolationService (MI355X build) needs a HIP device; there is no CPU fallback")
-        self.model = model if model is not None else load_model(model_path, self.device, precision)
+        if model is not None and weight_prep is not None:
+            # the service holds the caller's model, not a copy: like a plain `model.weight_prep = ...`, this is seen by
+            # every other user of that model (outputs are the same either way); an invalid value leaves it as it was
+            previous, model.weight_prep = model.weight_prep, weight_prep
+            try:
+                model._weight_prep_checked()
+            except ValueError:
+                model.weight_prep = previous
+                raise
+        self.model = model if model is not None else load_model(model_path, self.device, precision,
+                                                                weight_prep=weight_prep)
         self.model.eval()
         self.target_size = target_size      # (width, height) like preprocess_image; None = keep size
         self.use_graph = use_graph

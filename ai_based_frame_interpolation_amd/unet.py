@@ -151,15 +151,24 @@ class FrameInterpolationUNet(nn.Module):
                       + MFMA, fp32 accumulate - bf16's kernels with 11 significant bits instead of 8, round to
                       nearest, no dither).  Env FIUNET_PRECISION is the default when the
                       argument is None.  The attribute may be reassigned between forwards.
+      weight_prep:    where a checkpoint becomes what the kernels read (BatchNorm fold, repack, bf16 rounding): "host"
+                      (default; one thread of `fiunet_load_weights`, every tensor through host memory) or "device"
+                      (`fiunet_load_weights_device`: HIP kernels on the tensors where they are, into the same buffers
+                      at every reload) - the same bytes either way.  Env FIUNET_WEIGHT_PREP is the default when the
+                      argument is None.  The attribute may be reassigned; the next forward then prepares again.
     """
 
-    def __init__(self, bilinear: bool = False, frame_channels: int = 1, precision: str | None = None):
+    def __init__(self, bilinear: bool = False, frame_channels: int = 1, precision: str | None = None,
+                 weight_prep: str | None = None):
         super().__init__()
         self.unet = UNet(n_channels=2 * frame_channels, n_classes=frame_channels, bilinear=bilinear)
         self.frame_channels = frame_channels
         self.precision = precision or os.environ.get("FIUNET_PRECISION", "fp32")
         if self.precision not in _PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
+        self.weight_prep = weight_prep or os.environ.get("FIUNET_WEIGHT_PREP", "host")
+        self._weight_prep_checked()
+        self._prep_loaded = None  # the weight_prep the device copy was made with
         self._ctx = None          # _native.Context, per device
         self._ctx_dirty = True    # weights on the device are stale w.r.t. the parameters
         self._weights_gen = 0     # bumped at every upload (GraphedForward re-captures on change)
@@ -246,10 +255,12 @@ class FrameInterpolationUNet(nn.Module):
             self._ctx = _native.Context(idx, self.frame_channels, self.unet.bilinear)
             self._ctx_dirty = True
         fp = self._current_fingerprint()
-        if self._ctx_dirty or fp != self._fingerprint:
+        prep = self._weight_prep_checked()
+        if self._ctx_dirty or fp != self._fingerprint or prep != self._prep_loaded:
             self._ctx.set_options(self._options)  # (the weight-rounding option is read at load time)
-            self._ctx.load_state_dict(self.state_dict())
+            self._ctx.load_state_dict(self.state_dict(), prep=prep)
             self._ctx_dirty = False
+            self._prep_loaded = prep
             self._fingerprint = fp
             self._weights_gen += 1
         return self._ctx
@@ -262,6 +273,12 @@ class FrameInterpolationUNet(nn.Module):
             self._ws = None  # release before allocating the next one
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         return self._ws
+
+    def _weight_prep_checked(self) -> str:
+        """`weight_prep` is a plain attribute like `precision`: validated where it is used."""
+        if self.weight_prep not in _native.WEIGHT_PREPS:
+            raise ValueError(f"weight_prep must be one of {list(_native.WEIGHT_PREPS)}, got {self.weight_prep!r}")
+        return self.weight_prep
 
     def _precision_code(self) -> int:
         """`precision` is a plain attribute and may be reassigned between forwards: validated where it is used."""
@@ -660,7 +677,7 @@ class GraphedForward:
 
     def _stale(self) -> bool:
         m = self.model
-        return (m._ctx is not self._ctx or m._ctx_dirty or m.precision != self._prec
+        return (m._ctx is not self._ctx or m._ctx_dirty or m.precision != self._prec or m.weight_prep != m._prep_loaded
                 or m._weights_gen != self._gen or m._current_fingerprint() != m._fingerprint)
 
     def __call__(self, frame1: torch.Tensor, frame2: torch.Tensor) -> torch.Tensor:

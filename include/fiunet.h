@@ -109,6 +109,21 @@ int fiunet_set_options(fiunet_ctx* ctx, unsigned flags);
 int fiunet_load_weights(fiunet_ctx* ctx, int n, const char* const* names,
                         const float* const* host_ptrs, const int64_t* numels);
 
+/* fiunet_load_weights for tensors that are already in the memory of the context's GPU (v8, added without a version
+ * bump): the same keys, the same sizes and the same FIUNET_ERR_MISSING_WEIGHT messages, `device_ptrs[i]` contiguous fp32
+ * device arrays.  HIP kernels fold, repack and round there and leave, bit for bit, the buffers fiunet_load_weights
+ * leaves (the rounding mode of FIUNET_OPT_RNE_WEIGHTS is read at this call, as there).  Every key is checked before
+ * anything changes: a call that fails on a key leaves the weights loaded before it in place and usable.  The first
+ * load of a context allocates; a later one (after either entry point) packs into the same buffers - no allocation, no
+ * free, no host synchronisation, the kernels asynchronous on `stream`, which is also where they read `device_ptrs`:
+ * keep those alive, and order forwards on other streams, behind it.  The copies of fiunet_prepare_precision are stale
+ * afterwards, as after fiunet_load_weights: call it again (it waits for this load on the device, not on the host).
+ * The one exception to "bit for bit": a NaN that the fold itself creates - an infinite weight in a channel whose folded
+ * scale is zero - has the sign bit set from the host (x86) and clear from the GPU.  NaN and infinite weights with a
+ * non-zero scale come out identical. */
+int fiunet_load_weights_device(fiunet_ctx* ctx, int n, const char* const* names,
+                               const float* const* device_ptrs, const int64_t* numels, void* stream);
+
 /* Builds the weight copies a precision needs beyond what fiunet_load_weights made (FP32, BF16: nothing; BF16X2: the
  * two-piece [wh | wl] copies, ~69 MB, packed on the device from the fp32 copy; FP16: the fp16 copies, ~35 MB, rounded
  * to nearest even on the device from the fp32 copy).  Call it after fiunet_load_weights and
