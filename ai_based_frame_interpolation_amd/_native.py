@@ -235,6 +235,25 @@ def check(rc: int, what: str) -> None:
         raise NativeError(what, rc, msg.decode() if msg else "?")
 
 
+PLAN_KINDS = ("act", "pool", "up", "scratch", "slab")   # csrc/fiunet.hip BufKind
+
+
+def debug_plan(frame_channels: int, bilinear: bool, flags: int, precision: int, b: int, h: int, w: int):
+    """Diagnostic (tests; not part of the ABI): the workspace plan of one forward - fiunet_debug_plan in csrc/fiunet.hip,
+    pure host arithmetic with no device call.  -> ([{"kind": one of PLAN_KINDS, "index", "offset", "bytes", "first",
+    "last"}] per buffer the plan placed, total bytes); stages count 0..17, last = 18: live after the last conv."""
+    fn = lib().fiunet_debug_plan
+    fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint] + [ctypes.c_int] * 4 + [
+        ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_ulonglong)]
+    cap = 64
+    recs, n, total = (ctypes.c_longlong * (6 * cap))(), ctypes.c_int(), ctypes.c_ulonglong()
+    check(fn(frame_channels, int(bilinear), flags, precision, b, h, w, recs, cap, ctypes.byref(n), ctypes.byref(total)),
+          "fiunet_debug_plan")
+    keys = ("index", "offset", "bytes", "first", "last")
+    return ([dict(zip(keys, recs[6 * k + 1:6 * k + 6]), kind=PLAN_KINDS[recs[6 * k]]) for k in range(n.value)],
+            total.value)
+
+
 class Context:
     """Owns one fiunet_ctx (device-resident prepared weights) on one GPU."""
 

@@ -494,14 +494,20 @@ struct Plan {
     size_t total;
 };
 
+// One buffer of the workspace plan: what it holds, how many bytes, the live interval [first, last] in stages, and where its
+// offset goes in the Plan (fiunet_debug_plan reads the placed list back).
+enum BufKind { BUF_ACT = 0, BUF_POOL = 1, BUF_UP = 2, BUF_SCRATCH = 3, BUF_SLAB = 4 };
+struct PlanBuf { int kind, index; size_t bytes; int first, last; size_t* off; };
+
 // The stage plan and the workspace plan of one forward.  The reference, under no_grad, frees every non-skip tensor as soon
 // as its consumer has run (model/unet.py:84-95 keeps only x1..x4 alive); here the same liveness is turned into a static
 // layout: every buffer gets the interval [stage that writes it, last stage that reads it] (stage i = conv i of the 18) and
 // buffers whose intervals do not overlap share bytes (first-fit over the buffers in order of their first stage).  B=8 1080p
-// bf16 needs 6.4 GB this way instead of the 16.2 GB of one private buffer per tensor.  FIUNET_OPT_KEEP_ALL (the debug
-// read-back) pins every activation to the end; the ablation path adds its concat scratch; the fused stem / fused head leave
-// activations 0 / 17 out altogether.
-bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p)
+// bf16 needs 6.2 GB this way instead of the 12.7 GB of one private buffer per tensor (tests/test_workspace_plan.py holds
+// both figures).  FIUNET_OPT_KEEP_ALL (the debug read-back) pins every activation to the end (17.0 GB there); the ablation
+// path adds its concat scratch; the fused stem / fused head leave activations 0 / 17 out altogether.
+// `placed` (diagnostic): receives the buffers in placement order, their `off` pointing into `p`.
+bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p, std::vector<PlanBuf>* placed = nullptr)
 {
     if (B < 1 || H < 16 || W < 16) return false;
     // the kernels address a pixel record inside one image plane with 32 bits: H*W*64 B < 4 GiB.
@@ -512,7 +518,7 @@ bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p)
     const size_t es = two_byte_elems(precision) ? 2 : 4;   // bytes per activation element (bf16x2: two pieces)
     p.hs[0] = H; p.ws[0] = W;
     for (int k = 1; k < 5; ++k) { p.hs[k] = p.hs[k - 1] / 2; p.ws[k] = p.ws[k - 1] / 2; }
-    struct Buf { size_t bytes; int first, last; size_t* off; };
+    using Buf = PlanBuf;
     std::vector<Buf> bufs;
     const int END = NCONV;  // "still live after the last conv" (the unfused head, the debug read-back)
     for (int i = 0; i < NCONV; ++i) {
@@ -522,11 +528,11 @@ bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p)
         for (int j = i + 1; j < NCONV; ++j)
             if (kSrc0[j] == i || kSrc1[j] == i) last = j;
         if (i == NCONV - 1 || keep_all) last = END;
-        bufs.push_back({align256((size_t)B * p.hs[kLevel[i]] * p.ws[kLevel[i]] * n.cout[i] * es), i, last,
+        bufs.push_back({BUF_ACT, i, align256((size_t)B * p.hs[kLevel[i]] * p.ws[kLevel[i]] * n.cout[i] * es), i, last,
                         &p.act_off[i]});
     }
     for (int k = 0; k < 4; ++k) {  // MaxPool2d(2) of x1..x4: written by conv 2k+1, read by conv 2k+2
-        bufs.push_back({align256((size_t)B * p.hs[k + 1] * p.ws[k + 1] * n.cout[2 * k + 1] * es), 2 * k + 1,
+        bufs.push_back({BUF_POOL, k, align256((size_t)B * p.hs[k + 1] * p.ws[k + 1] * n.cout[2 * k + 1] * es), 2 * k + 1,
                         keep_all ? END : 2 * k + 2, &p.pool_off[k]});
     }
     bool upcat = false;
@@ -535,14 +541,14 @@ bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p)
         const int form = i ? p.st[i].form : -1;
         upcat |= form == FORM_CONCAT_UPCAT;
         if (form == FORM_CONCAT_UP || form == FORM_CONCAT_CONVT)
-            bufs.push_back({align256((size_t)B * p.hs[kLevel[i]] * p.ws[kLevel[i]] *
-                                     (form == FORM_CONCAT_CONVT ? n.cout[kSrc1[i]] / 2 : n.cout[kSrc1[i]]) * es), i,
+            bufs.push_back({BUF_UP, i, align256((size_t)B * p.hs[kLevel[i]] * p.ws[kLevel[i]] *
+                                             (form == FORM_CONCAT_CONVT ? n.cout[kSrc1[i]] / 2 : n.cout[kSrc1[i]]) * es), i,
                             keep_all ? END : i, &p.up_off[i]});
     }
     p.scratch_off = 0;
     if (upcat)  // ablation path: concat tensor (<= 128 ch at level 0), rewritten by every Up block
-        bufs.push_back({align256((size_t)B * H * W * 128 * es), 0, END, &p.scratch_off});
-    bufs.push_back({kSlabBytes, 0, END, &p.slab_off});  // split-K partial sums (small problems)
+        bufs.push_back({BUF_SCRATCH, 0, align256((size_t)B * H * W * 128 * es), 0, END, &p.scratch_off});
+    bufs.push_back({BUF_SLAB, 0, kSlabBytes, 0, END, &p.slab_off});  // split-K partial sums (small problems)
     std::stable_sort(bufs.begin(), bufs.end(), [](const Buf& a, const Buf& b) { return a.first < b.first; });
     struct Live { size_t off, bytes; int last; };
     std::vector<Live> live;
@@ -563,6 +569,7 @@ bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p)
         total = std::max(total, off + b.bytes);
     }
     p.total = total;
+    if (placed) *placed = bufs;
     return true;
 }
 
@@ -2625,6 +2632,42 @@ int fiunet_debug_stage_cfg(int frame_channels, int bilinear, unsigned flags, int
     out[0] = st.cfg.small; out[1] = st.cfg.ksplit; out[2] = st.cfg.kwave;
     out[3] = stage > 0 && (st.form == FORM_CONCAT_UP || st.form == FORM_CONCAT_CONVT);
     out[4] = st.form; out[5] = st.epi;
+    return FIUNET_OK;
+}
+
+// diagnostic (not part of the ABI): the workspace plan of a forward of this architecture, option set, precision and shape -
+// make_plan itself on the NetDesc fiunet_debug_stage_cfg builds, pure host arithmetic with no device call, so the layout
+// (sizes, live intervals, the sharing of bytes) is testable without a GPU (tests/test_workspace_plan.py).  One record of six
+// values per buffer make_plan placed, in placement order: kind (0 activation `index`, 1 MaxPool2d(2) of x1..x4 `index` 0..3,
+// 2 the upsampled half of stage `index`, 3 the ablation path's concat scratch, 4 the split-K slab), index, offset, bytes,
+// first stage, last stage (18 = still live after the last conv).  A stage that is not stored has no record.  *n_records =
+// how many there are (also when `capacity` records do not hold them: FIUNET_ERR_INVALID_ARG, nothing written), *total =
+// what fiunet_workspace_bytes answers.
+int fiunet_debug_plan(int frame_channels, int bilinear, unsigned flags, int precision, int B, int H, int W,
+                      long long* records /* [capacity][6] */, int capacity, int* n_records, unsigned long long* total)
+{
+    if (!records || capacity < 0 || !n_records || !total || (frame_channels != 1 && frame_channels != 3) || B < 1 || H < 16 ||
+        W < 16 || !valid_precision(precision))
+        return fail(FIUNET_ERR_INVALID_ARG, "fiunet_debug_plan: bad arguments");
+    NetDesc n;
+    n.cf = frame_channels;
+    n.bilinear = bilinear != 0;
+    n.cout = n.bilinear ? kCoutBil : kCoutCT;
+    n.flags = flags;
+    n.stem_w = frame_channels == 1;
+    Plan p;
+    std::vector<PlanBuf> bufs;
+    if (!make_plan(n, B, H, W, precision, p, &bufs)) return fail(FIUNET_ERR_BAD_SHAPE, "fiunet_debug_plan: bad shape");
+    *n_records = (int)bufs.size();
+    *total = p.total;
+    if (bufs.size() > (size_t)capacity)
+        return fail(FIUNET_ERR_INVALID_ARG, "fiunet_debug_plan: " + std::to_string(bufs.size()) + " records, room for " +
+                                                std::to_string(capacity));
+    for (size_t k = 0; k < bufs.size(); ++k) {
+        const PlanBuf& b = bufs[k];
+        long long* r = records + 6 * k;
+        r[0] = b.kind; r[1] = b.index; r[2] = (long long)*b.off; r[3] = (long long)b.bytes; r[4] = b.first; r[5] = b.last;
+    }
     return FIUNET_OK;
 }
 
