@@ -235,6 +235,11 @@ def check(rc: int, what: str) -> None:
         raise NativeError(what, rc, msg.decode() if msg else "?")
 
 
+def _stream(t: "torch.Tensor", stream=None) -> int:
+    """The stream a call runs on: the caller's raw handle, or the current stream of `t`'s device."""
+    return torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+
+
 PLAN_KINDS = ("act", "pool", "up", "scratch", "slab")   # csrc/fiunet.hip BufKind
 
 
@@ -359,7 +364,7 @@ class Context:
 
     def forward(self, f1, f2, out, precision, workspace, stream=None):
         b, _, h, w = f1.shape
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        s = _stream(f1, stream)
         check(lib().fiunet_forward(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), b, h, w,
                                    precision, workspace.data_ptr(), workspace.numel(), s),
               "fiunet_forward")
@@ -367,7 +372,7 @@ class Context:
     def forward_strip(self, f1, f2, out, y_origin, h_image, precision, workspace, stream=None):
         """The forward on rows [y_origin, y_origin + h) of an image of h_image rows."""
         b, _, h, w = f1.shape
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        s = _stream(f1, stream)
         check(lib().fiunet_forward_strip(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), b, h,
                                          w, y_origin, h_image, precision, workspace.data_ptr(),
                                          workspace.numel(), s), "fiunet_forward_strip")
@@ -376,7 +381,7 @@ class Context:
         """`out`: uint8 [B, C, H, W] whose images are contiguous; they may lie further apart than one image (a strided
         view such as every second frame of the video loop's interleaved result): the fused head writes them in place."""
         b, c, h, w = f1.shape
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        s = _stream(f1, stream)
         if out.is_contiguous():
             check(lib().fiunet_forward_u8(self._h, f1.data_ptr(), f2.data_ptr(), out.data_ptr(), b, h,
                                           w, precision, workspace.data_ptr(), workspace.numel(), s),
@@ -394,7 +399,7 @@ class Context:
         4:2:0 frames, contiguous; `out` [B, F] whose rows are contiguous and may lie further apart (every second frame
         of the video loop's interleaved result).  Strides in samples."""
         b = f1.shape[0]
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        s = _stream(f1, stream)
         st = out.stride(0) if b > 1 else out.shape[1]
         fn, name = ((lib().fiunet_forward_yuv420p10, "fiunet_forward_yuv420p10") if bits == 10 else
                     (lib().fiunet_forward_yuv420, "fiunet_forward_yuv420"))
@@ -405,7 +410,7 @@ class Context:
         """10-bit frames: uint16 [B, C, H, W] contiguous in; `out` uint16 [B, C, H, W] whose images are contiguous and
         may lie further apart (every second frame of the video loop's interleaved result).  Strides in samples."""
         b, c, h, w = f1.shape
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        s = _stream(f1, stream)
         image_stride = 0   # contiguous
         if not out.is_contiguous():
             st = out.stride()
@@ -423,7 +428,7 @@ class Context:
         f1, f2 contiguous in `layout`; `out` in `out_layout`, its rows contiguous and possibly further apart.  The
         layouts are resolved colour.SurfaceLayout tuples or None (tight); the workspace is the 4:2:0 entry point's."""
         b = f1.shape[0]
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        s = _stream(f1, stream)
         st = out.stride(0) if b > 1 else out.shape[1]
         fn, name = ((lib().fiunet_forward_p010, "fiunet_forward_p010") if bits == 10 else
                     (lib().fiunet_forward_nv12, "fiunet_forward_nv12"))
@@ -435,7 +440,7 @@ class Context:
         `out_layout`, its rows contiguous and possibly further apart.  The layouts are resolved packed.PackedLayout
         tuples; fmt: the fiunet_packed_format code; the workspace is the 4:2:0 entry point's."""
         b = f1.shape[0]
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        s = _stream(f1, stream)
         st = out.stride(0) if b > 1 else out.shape[1]
         check(lib().fiunet_forward_rgb_packed(self._h, f1.data_ptr(), f2.data_ptr(), _packed(layout, f1.shape[1]),
                                               out.data_ptr(), _packed(out_layout, st), b, h, w, fmt, precision,
@@ -448,7 +453,7 @@ class Context:
         further apart.  The layouts are resolved packed.PackedLayout tuples (row_pitch 0 for the planar formats); the
         workspace is the 4:2:0 entry point's."""
         b = f1.shape[0]
-        s = torch.cuda.current_stream(f1.device).cuda_stream if stream is None else stream
+        s = _stream(f1, stream)
         fn, name = ((lib().fiunet_forward_yuv_p10, "fiunet_forward_yuv_p10") if bits == 10 else
                     (lib().fiunet_forward_yuv, "fiunet_forward_yuv"))
         check(fn(self._h, f1.data_ptr(), f2.data_ptr(), fmt, layout.row_pitch, f1.shape[1], out.data_ptr(),
@@ -480,7 +485,7 @@ class Context:
               "fiunet_debug_read_activation (dims query)")
         c, hh, ww = tuple(dims)
         dst = torch.empty((b, c, hh, ww), dtype=torch.float32, device=workspace.device)
-        s = torch.cuda.current_stream(workspace.device).cuda_stream
+        s = _stream(workspace)
         check(lib().fiunet_debug_read_activation(self._h, workspace.data_ptr(), b, h, w, precision,
                                                  tap, dst.data_ptr(), dst.numel(), dims, s),
               "fiunet_debug_read_activation")
@@ -490,7 +495,7 @@ class Context:
 def _pointwise(name: str, src: "torch.Tensor", dtype) -> "torch.Tensor":
     """One of the four pre / post-processing kernels on contiguous samples -> `dtype`, same shape."""
     out = torch.empty(src.shape, dtype=dtype, device=src.device)
-    s = torch.cuda.current_stream(src.device).cuda_stream
+    s = _stream(src)
     check(getattr(lib(), name)(src.data_ptr(), out.data_ptr(), src.numel(), s), name)
     return out
 
@@ -520,7 +525,7 @@ def yuv420_to_rgb(frames: "torch.Tensor", out: "torch.Tensor", h: int, w: int, c
     frames (rows contiguous, any row stride) -> planar RGB [B, 3, h, w]."""
     b = frames.shape[0]
     st = frames.stride(0) if b > 1 else frames.shape[1]
-    s = torch.cuda.current_stream(frames.device).cuda_stream
+    s = _stream(frames)
     fn, name = ((lib().fiunet_yuv420p10_to_rgb_p10, "fiunet_yuv420p10_to_rgb_p10") if bits == 10 else
                 (lib().fiunet_yuv420_to_rgb_u8, "fiunet_yuv420_to_rgb_u8"))
     check(fn(frames.data_ptr(), st, out.data_ptr(), b, h, w, colour, s), name)
@@ -531,7 +536,7 @@ def rgb_to_yuv420(rgb: "torch.Tensor", out: "torch.Tensor", colour: int, bits: i
     contiguous -> [B, F] packed 4:2:0 frames (rows contiguous, any row stride)."""
     b, _, h, w = rgb.shape
     st = out.stride(0) if b > 1 else out.shape[1]
-    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    s = _stream(rgb)
     fn, name = ((lib().fiunet_rgb_p10_to_yuv420p10, "fiunet_rgb_p10_to_yuv420p10") if bits == 10 else
                 (lib().fiunet_rgb_to_yuv420_u8, "fiunet_rgb_to_yuv420_u8"))
     check(fn(rgb.data_ptr(), out.data_ptr(), st, b, h, w, colour, s), name)
@@ -542,7 +547,7 @@ def surface_to_rgb(frames: "torch.Tensor", layout, out: "torch.Tensor", h: int, 
     any row stride) in the resolved `layout` (None: tight) -> planar RGB [B, 3, h, w]."""
     b = frames.shape[0]
     st = frames.stride(0) if b > 1 else frames.shape[1]
-    s = torch.cuda.current_stream(frames.device).cuda_stream
+    s = _stream(frames)
     fn, name = ((lib().fiunet_p010_to_rgb_p10, "fiunet_p010_to_rgb_p10") if bits == 10 else
                 (lib().fiunet_nv12_to_rgb_u8, "fiunet_nv12_to_rgb_u8"))
     check(fn(frames.data_ptr(), _surface(layout, st), out.data_ptr(), b, h, w, colour, s), name)
@@ -553,7 +558,7 @@ def rgb_to_surface(rgb: "torch.Tensor", out: "torch.Tensor", layout, colour: int
     frame_stride] surfaces (rows contiguous, any row stride) in the resolved `layout` (None: tight)."""
     b, _, h, w = rgb.shape
     st = out.stride(0) if b > 1 else out.shape[1]
-    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    s = _stream(rgb)
     fn, name = ((lib().fiunet_rgb_p10_to_p010, "fiunet_rgb_p10_to_p010") if bits == 10 else
                 (lib().fiunet_rgb_to_nv12_u8, "fiunet_rgb_to_nv12_u8"))
     check(fn(rgb.data_ptr(), out.data_ptr(), _surface(layout, st), b, h, w, colour, s), name)
@@ -566,7 +571,7 @@ def _row_stride(t: "torch.Tensor") -> int:
 def packed_to_rgb(frames: "torch.Tensor", layout, out: "torch.Tensor", alpha, h: int, w: int, fmt: int) -> None:
     """fiunet_packed_to_rgb_u8: uint8 [B, frame_stride] packed frames (rows contiguous, any row stride) in the resolved
     `layout` -> planar RGB [B, 3, h, w]; alpha: None, or the contiguous [B, h, w] tensor the alpha plane goes to."""
-    s = torch.cuda.current_stream(frames.device).cuda_stream
+    s = _stream(frames)
     check(lib().fiunet_packed_to_rgb_u8(frames.data_ptr(), _packed(layout, _row_stride(frames)), out.data_ptr(),
                                         None if alpha is None else alpha.data_ptr(), frames.shape[0], h, w, fmt, s),
           "fiunet_packed_to_rgb_u8")
@@ -577,7 +582,7 @@ def rgb_to_packed(rgb: "torch.Tensor", out: "torch.Tensor", layout, alphas, alph
     contiguous, any row stride) in the resolved `layout`; alphas: a tuple of 0, 1 or 2 packed tensors of one row stride
     in the resolved `alpha_layout`."""
     b, _, h, w = rgb.shape
-    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    s = _stream(rgb)
     a = [t.data_ptr() for t in alphas] + [None, None]
     al = _packed(alpha_layout, _row_stride(alphas[0])) if alphas else None
     check(lib().fiunet_rgb_to_packed_u8(rgb.data_ptr(), out.data_ptr(), _packed(layout, _row_stride(out)), a[0], a[1],
@@ -588,7 +593,7 @@ def yuv_to_rgb(frames: "torch.Tensor", fmt: int, layout, out: "torch.Tensor", h:
                bits: int) -> None:
     """fiunet_yuv_to_rgb_u8 (bits 8) / fiunet_yuv_to_rgb_p10 (bits 10): [B, frame_stride] frames of the
     fiunet_yuv_format `fmt` (rows contiguous, any row stride) in the resolved `layout` -> planar RGB [B, 3, h, w]."""
-    s = torch.cuda.current_stream(frames.device).cuda_stream
+    s = _stream(frames)
     fn, name = ((lib().fiunet_yuv_to_rgb_p10, "fiunet_yuv_to_rgb_p10") if bits == 10 else
                 (lib().fiunet_yuv_to_rgb_u8, "fiunet_yuv_to_rgb_u8"))
     check(fn(frames.data_ptr(), fmt, layout.row_pitch, _row_stride(frames), out.data_ptr(), frames.shape[0], h, w,
@@ -599,7 +604,7 @@ def rgb_to_yuv(rgb: "torch.Tensor", out: "torch.Tensor", fmt: int, layout, colou
     """fiunet_rgb_to_yuv_u8 (bits 8) / fiunet_rgb_p10_to_yuv (bits 10): planar RGB [B, 3, h, w] contiguous -> [B,
     frame_stride] frames of the fiunet_yuv_format `fmt` (rows contiguous, any row stride) in the resolved `layout`."""
     b, _, h, w = rgb.shape
-    s = torch.cuda.current_stream(rgb.device).cuda_stream
+    s = _stream(rgb)
     fn, name = ((lib().fiunet_rgb_p10_to_yuv, "fiunet_rgb_p10_to_yuv") if bits == 10 else
                 (lib().fiunet_rgb_to_yuv_u8, "fiunet_rgb_to_yuv_u8"))
     check(fn(rgb.data_ptr(), out.data_ptr(), fmt, layout.row_pitch, _row_stride(out), b, h, w, colour, s), name)
@@ -611,14 +616,14 @@ def pair_sad(frames: "torch.Tensor", sums: "torch.Tensor", bits: int) -> None:
     n = frames.shape[0]
     fs = frames[0].numel() if n else 0
     fn = lib().fiunet_pair_sad_p10 if bits == 10 else lib().fiunet_pair_sad_u8
-    s = torch.cuda.current_stream(frames.device).cuda_stream
+    s = _stream(frames)
     check(fn(frames.data_ptr(), n, fs, sums.data_ptr(), s), "fiunet_pair_sad_" + ("p10" if bits == 10 else "u8"))
 
 
 def scene_cuts(sums: "torch.Tensor", n_frames: int, count: int, bits: int, threshold: float,
                scores: "torch.Tensor", flags: "torch.Tensor") -> None:
     """fiunet_scene_cuts: int64 sums [N-1] -> fp64 scores [N-1], uint8 flags [N-1]."""
-    s = torch.cuda.current_stream(sums.device).cuda_stream
+    s = _stream(sums)
     check(lib().fiunet_scene_cuts(sums.data_ptr(), n_frames, count, bits, float(threshold), scores.data_ptr(),
                                   flags.data_ptr(), s), "fiunet_scene_cuts")
 
@@ -626,7 +631,7 @@ def scene_cuts(sums: "torch.Tensor", n_frames: int, count: int, bits: int, thres
 def hold_cut_frames(video: "torch.Tensor", n_frames: int, factor: int, flags: "torch.Tensor") -> None:
     """fiunet_hold_cut_frames on a contiguous interleaved result [(n_frames-1)*factor+1, ...], in place."""
     fb = video[0].numel() * video.element_size() if video.shape[0] else 0
-    s = torch.cuda.current_stream(video.device).cuda_stream
+    s = _stream(video)
     check(lib().fiunet_hold_cut_frames(video.data_ptr(), n_frames, fb, factor, flags.data_ptr(), s),
           "fiunet_hold_cut_frames")
 
@@ -637,7 +642,7 @@ def retime(grid: "torch.Tensor", n_intervals: int, depth: int, first_interval: i
     words at 10) -> `out` [n_out, ...], clip output frames j0 .. j0 + n_out - 1; flags uint8 [n_intervals] or None."""
     fs = grid[0].numel()
     fn = lib().fiunet_retime_p10 if bits == 10 else lib().fiunet_retime_u8
-    s = torch.cuda.current_stream(grid.device).cuda_stream
+    s = _stream(grid)
     check(fn(grid.data_ptr(), n_intervals, fs, depth, first_interval, j0, n_out, p, q, mode,
              None if flags is None else flags.data_ptr(), out.data_ptr(), s),
           "fiunet_retime_" + ("p10" if bits == 10 else "u8"))

@@ -178,6 +178,17 @@ int launch_lds(const char* name, long long nblk, int lds, const ConvArgs& a, hip
     return FIUNET_OK;
 }
 
+// One of a format conversion's two instantiations on blocks of kColourBlock threads: the one with vector accesses where
+// `vec` says that every base, pitch and stride allows them, the scalar one otherwise.
+template <auto VecKernel, auto ScalarKernel, typename... Args>
+int launch_vec(bool vec, dim3 grid, void* stream, Args... args)
+{
+    if (vec) hipLaunchKernelGGL(VecKernel, grid, dim3(kColourBlock), 0, (hipStream_t)stream, args...);
+    else hipLaunchKernelGGL(ScalarKernel, grid, dim3(kColourBlock), 0, (hipStream_t)stream, args...);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
 template <typename T, int BN, int TH, int TW, int MODE, int EPI>
 int launch_conv_cfg(ConvArgs a, hipStream_t s)
 {
@@ -1411,104 +1422,103 @@ int fiunet_forward_u8_strided(fiunet_ctx* ctx, const uint8_t* frame1, const uint
 }
 
 // ---- colour video (csrc/colour.hip.h): packed I420 <-> planar RGB, and the RGB network's forward between them ----
-static inline size_t i420_frame_bytes(int H, int W)
+static inline size_t i420_frame_bytes(int H, int W)   // (samples per frame, at either depth)
 {
     return (size_t)H * W + 2 * (size_t)((H + 1) / 2) * ((W + 1) / 2);
 }
 
-static int check_colour_args(const void* in, const void* out, int B, int H, int W, unsigned colour)
+// `colour` at an entry point of `bits` bits: FIUNET_YUV_BT2020 is a 10-bit flag, and excludes FIUNET_YUV_BT709
+static int check_colour_flags(unsigned colour, int bits)
 {
-    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (colour & ~kColourFlags) return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits");
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
-    return FIUNET_OK;
-}
-
-int fiunet_yuv420_to_rgb_u8(const uint8_t* in, size_t in_frame_stride, uint8_t* out, int B, int H, int W,
-                            unsigned colour, void* stream)
-{
-    int rc;
-    if ((rc = check_colour_args(in, out, B, H, W, colour))) return rc;
-    const size_t fb = i420_frame_bytes(H, W);
-    if (in_frame_stride == 0) in_frame_stride = fb;
-    if (in_frame_stride < fb) return fail(FIUNET_ERR_INVALID_ARG, "in_frame_stride smaller than one frame");
-    const bool vec = W % 4 == 0 && in_frame_stride % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 3) == 0;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
-    const ColourCoef k = colour_coef(colour);
-    if (vec)
-        hipLaunchKernelGGL((yuv420_to_rgb_kernel<uint8_t, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
-                           in, in_frame_stride, out, H, W, k);
-    else
-        hipLaunchKernelGGL((yuv420_to_rgb_kernel<uint8_t, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
-                           in, in_frame_stride, out, H, W, k);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int fiunet_rgb_to_yuv420_u8(const uint8_t* in, uint8_t* out, size_t out_frame_stride, int B, int H, int W,
-                            unsigned colour, void* stream)
-{
-    int rc;
-    if ((rc = check_colour_args(in, out, B, H, W, colour))) return rc;
-    const size_t fb = i420_frame_bytes(H, W);
-    if (out_frame_stride == 0) out_frame_stride = fb;
-    if (out_frame_stride < fb) return fail(FIUNET_ERR_INVALID_ARG, "out_frame_stride smaller than one frame");
-    const bool vec = W % 4 == 0 && out_frame_stride % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 3) == 0;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)((H + 1) / 2), (unsigned)B);
-    const ColourCoef k = colour_coef(colour);
-    if (vec)
-        hipLaunchKernelGGL((rgb_to_yuv420_kernel<uint8_t, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
-                           in, out, out_frame_stride, H, W, k);
-    else
-        hipLaunchKernelGGL((rgb_to_yuv420_kernel<uint8_t, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
-                           in, out, out_frame_stride, H, W, k);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-size_t fiunet_workspace_bytes_yuv420(const fiunet_ctx* ctx, int B, int H, int W, int precision)
-{
-    const size_t base = fiunet_workspace_bytes_u8(ctx, B, H, W, precision);
-    if (base == 0) return 0;
-    return align256(base) + 3 * align256((size_t)B * 3 * H * W);
-}
-
-int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
-                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
-                          void* workspace, size_t workspace_bytes, void* stream)
-{
-    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->cf != 3) return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_yuv420 needs the RGB network (frame_channels 3)");
-    if (colour & ~kColourFlags) return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits");
-    const size_t need = fiunet_workspace_bytes_yuv420(ctx, B, H, W, precision);
-    if (need == 0) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
-    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    const size_t fb = i420_frame_bytes(H, W);
-    if (out_frame_stride == 0) out_frame_stride = fb;
-    if (out_frame_stride < fb) return fail(FIUNET_ERR_INVALID_ARG, "out_frame_stride smaller than one frame");
-    const size_t base = align256(fiunet_workspace_bytes_u8(ctx, B, H, W, precision));
-    const size_t rgb = align256((size_t)B * 3 * H * W);
-    uint8_t* a = (uint8_t*)workspace + base;
-    uint8_t* b = a + rgb;
-    uint8_t* o = b + rgb;
-    int rc;
-    if ((rc = fiunet_yuv420_to_rgb_u8(frame1, fb, a, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_yuv420_to_rgb_u8(frame2, fb, b, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
-    return fiunet_rgb_to_yuv420_u8(o, out, out_frame_stride, B, H, W, colour, stream);
-}
-
-// ---- 10-bit video (ABI v7): uint16 samples, pre10 / post10 around the fp32 forward; the colour
-//      conversions of csrc/colour.hip.h on 10-bit samples.  Strides are counted in samples.
-static int check_colour_p10_flags(unsigned colour)
-{
-    if (colour & ~kColourFlagsP10) return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits");
+    if (colour & ~(bits == 10 ? kColourFlagsP10 : kColourFlags))
+        return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits (FIUNET_YUV_BT2020 needs the 10-bit entry points)");
     if ((colour & FIUNET_YUV_BT709) && (colour & FIUNET_YUV_BT2020))
         return fail(FIUNET_ERR_INVALID_ARG, "colour: FIUNET_YUV_BT709 and FIUNET_YUV_BT2020 together");
     return FIUNET_OK;
 }
 
+static int check_colour_args(const void* in, const void* out, int B, int H, int W, unsigned colour, int bits)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = check_colour_flags(colour, bits)) return rc;
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    return FIUNET_OK;
+}
+
+// the conversions' grid: a thread per four columns, `rows` rows (a chroma row covers two luma rows), B frames
+static dim3 colour_grid(int W, int rows, int B)
+{
+    return dim3((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)rows, (unsigned)B);
+}
+
+extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
+// the caller's frame stride (0 = tight) -> the resolved one, refused where a frame does not fit; `which`: "in" / "out"
+static int resolve_i420_stride(size_t* frame_stride, int H, int W, const char* which)
+{
+    const size_t fs = i420_frame_bytes(H, W);
+    if (*frame_stride == 0) *frame_stride = fs;
+    if (*frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, std::string(which) + "_frame_stride smaller than one frame");
+    return FIUNET_OK;
+}
+
+// one 4-sample access per luma quad and per chroma pair: W, the stride and both bases a multiple of 4 samples
+template <typename T>
+static bool i420_vec(int W, size_t frame_stride, const void* a, const void* b)
+{
+    return W % 4 == 0 && frame_stride % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
+}
+
+template <typename T>
+static int yuv420_to_rgb(const T* in, size_t in_frame_stride, T* out, int B, int H, int W, unsigned colour, int bits,
+                         void* stream)
+{
+    int rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
+    if ((rc = resolve_i420_stride(&in_frame_stride, H, W, "in"))) return rc;
+    return launch_vec<&yuv420_to_rgb_kernel<T, true>, &yuv420_to_rgb_kernel<T, false>>(
+        i420_vec<T>(W, in_frame_stride, in, out), colour_grid(W, H, B), stream, in, in_frame_stride, out, H, W,
+        colour_coef(colour, bits));
+}
+
+template <typename T>
+static int rgb_to_yuv420(const T* in, T* out, size_t out_frame_stride, int B, int H, int W, unsigned colour, int bits,
+                         void* stream)
+{
+    int rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
+    if ((rc = resolve_i420_stride(&out_frame_stride, H, W, "out"))) return rc;
+    return launch_vec<&rgb_to_yuv420_kernel<T, true>, &rgb_to_yuv420_kernel<T, false>>(
+        i420_vec<T>(W, out_frame_stride, in, out), colour_grid(W, (H + 1) / 2, B), stream, in, out, out_frame_stride, H, W,
+        colour_coef(colour, bits));
+}
+}  // extern "C++"
+
+int fiunet_yuv420_to_rgb_u8(const uint8_t* in, size_t in_frame_stride, uint8_t* out, int B, int H, int W,
+                            unsigned colour, void* stream)
+{
+    return yuv420_to_rgb<uint8_t>(in, in_frame_stride, out, B, H, W, colour, 8, stream);
+}
+
+int fiunet_rgb_to_yuv420_u8(const uint8_t* in, uint8_t* out, size_t out_frame_stride, int B, int H, int W,
+                            unsigned colour, void* stream)
+{
+    return rgb_to_yuv420<uint8_t>(in, out, out_frame_stride, B, H, W, colour, 8, stream);
+}
+
+int fiunet_yuv420p10_to_rgb_p10(const uint16_t* in, size_t in_frame_stride, uint16_t* out, int B, int H, int W,
+                                unsigned colour, void* stream)
+{
+    return yuv420_to_rgb<uint16_t>(in, in_frame_stride, out, B, H, W, colour, 10, stream);
+}
+
+int fiunet_rgb_p10_to_yuv420p10(const uint16_t* in, uint16_t* out, size_t out_frame_stride, int B, int H, int W,
+                                unsigned colour, void* stream)
+{
+    return rgb_to_yuv420<uint16_t>(in, out, out_frame_stride, B, H, W, colour, 10, stream);
+}
+
+// ---- 10-bit frames (ABI v7): uint16 samples, pre10 / post10 around the fp32 forward.  Strides are
+//      counted in samples.
 size_t fiunet_workspace_bytes_p10(const fiunet_ctx* ctx, int B, int H, int W, int precision)
 {
     const size_t base = fiunet_workspace_bytes(ctx, B, H, W, precision);
@@ -1547,86 +1557,97 @@ int fiunet_forward_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* 
     return FIUNET_OK;
 }
 
-int fiunet_yuv420p10_to_rgb_p10(const uint16_t* in, size_t in_frame_stride, uint16_t* out, int B, int H, int W,
-                                unsigned colour, void* stream)
+// ---- the staged-RGB forward: how a frame format goes through the RGB network.  Every
+//      fiunet_forward_<format> below is this chain with its own conversion pair; nothing else differs between them.
+// [the inner forward's workspace | frame1 RGB | frame2 RGB | output RGB]: planar [B, 3, H, W] batches of `sample`-byte
+// samples behind the workspace of fiunet_forward_u8 (1 byte) / fiunet_forward_p10 (2), every part rounded up to 256 B.
+struct StagedWorkspace {
+    size_t inner, rgb, total;   // total 0: bad arguments (the inner query has said which)
+};
+
+static StagedWorkspace staged_workspace(const fiunet_ctx* ctx, int B, int H, int W, int precision, size_t sample)
 {
-    int rc;
-    if ((rc = check_colour_p10_flags(colour))) return rc;
-    if ((rc = check_colour_args(in, out, B, H, W, colour & kColourFlags))) return rc;
-    const size_t fs = i420_frame_bytes(H, W);   // samples per frame
-    if (in_frame_stride == 0) in_frame_stride = fs;
-    if (in_frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, "in_frame_stride smaller than one frame");
-    const bool vec = W % 4 == 0 && in_frame_stride % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 7) == 0;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
-    const ColourCoef k = colour_coef(colour, 10);
-    if (vec)
-        hipLaunchKernelGGL((yuv420_to_rgb_kernel<uint16_t, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
-                           in, in_frame_stride, out, H, W, k);
-    else
-        hipLaunchKernelGGL((yuv420_to_rgb_kernel<uint16_t, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
-                           in, in_frame_stride, out, H, W, k);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    const size_t inner = sample == 1 ? fiunet_workspace_bytes_u8(ctx, B, H, W, precision)
+                                     : fiunet_workspace_bytes_p10(ctx, B, H, W, precision);
+    if (inner == 0) return {0, 0, 0};
+    const size_t base = align256(inner), rgb = align256((size_t)B * 3 * H * W * sample);
+    return {base, rgb, base + 3 * rgb};
 }
 
-int fiunet_rgb_p10_to_yuv420p10(const uint16_t* in, uint16_t* out, size_t out_frame_stride, int B, int H, int W,
-                                unsigned colour, void* stream)
+extern "C++" {
+// T: uint8_t (through fiunet_forward_u8_strided) or uint16_t (through fiunet_forward_p10).  What a format supplies:
+//   check()           host only: its format code, colour flags and both layouts (anything its conversions would refuse);
+//   to_rgb(in, rgb)   its frames -> a planar RGB batch;
+//   from_rgb(rgb)     a planar RGB batch -> `out` in its format.
+// Every refusal comes before the first launch.  `name`: the entry point, for the wrong-network message.
+template <typename T, typename Check, typename ToRgb, typename FromRgb>
+static int forward_staged(const char* name, fiunet_ctx* ctx, const T* frame1, const T* frame2, const T* out, int B,
+                          int H, int W, int precision, void* workspace, size_t workspace_bytes, void* stream,
+                          Check check, ToRgb to_rgb, FromRgb from_rgb)
 {
+    if (!frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
     int rc;
-    if ((rc = check_colour_p10_flags(colour))) return rc;
-    if ((rc = check_colour_args(in, out, B, H, W, colour & kColourFlags))) return rc;
-    const size_t fs = i420_frame_bytes(H, W);
-    if (out_frame_stride == 0) out_frame_stride = fs;
-    if (out_frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, "out_frame_stride smaller than one frame");
-    const bool vec = W % 4 == 0 && out_frame_stride % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 7) == 0;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)((H + 1) / 2), (unsigned)B);
-    const ColourCoef k = colour_coef(colour, 10);
-    if (vec)
-        hipLaunchKernelGGL((rgb_to_yuv420_kernel<uint16_t, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
-                           in, out, out_frame_stride, H, W, k);
+    if ((rc = check())) return rc;
+    if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3)
+        return fail(FIUNET_ERR_UNSUPPORTED, std::string(name) + " needs the RGB network (frame_channels 3)");
+    if (!ctx->loaded) return fail(FIUNET_ERR_NOT_LOADED, "fiunet_forward before fiunet_load_weights");
+    const StagedWorkspace ws = staged_workspace(ctx, B, H, W, precision, sizeof(T));
+    if (ws.total == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
+    if (workspace_bytes < ws.total) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    T* a = (T*)((char*)workspace + ws.inner);
+    T* b = (T*)((char*)a + ws.rgb);
+    T* o = (T*)((char*)b + ws.rgb);
+    if ((rc = to_rgb(frame1, a)) || (rc = to_rgb(frame2, b))) return rc;
+    if constexpr (sizeof(T) == 1)
+        rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, ws.inner, stream);
     else
-        hipLaunchKernelGGL((rgb_to_yuv420_kernel<uint16_t, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream,
-                           in, out, out_frame_stride, H, W, k);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+        rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, ws.inner, stream);
+    return rc ? rc : from_rgb(o);
+}
+
+template <typename T>
+static int forward_yuv420(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2, T* out,
+                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision, void* workspace,
+                          size_t workspace_bytes, void* stream)
+{
+    return forward_staged<T>(
+        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
+        [&] {
+            const int rc = check_colour_flags(colour, bits);
+            return rc ? rc : resolve_i420_stride(&out_frame_stride, H, W, "out");
+        },
+        [&](const T* in, T* rgb) { return yuv420_to_rgb<T>(in, 0, rgb, B, H, W, colour, bits, stream); },
+        [&](const T* rgb) { return rgb_to_yuv420<T>(rgb, out, out_frame_stride, B, H, W, colour, bits, stream); });
+}
+}  // extern "C++"
+
+size_t fiunet_workspace_bytes_yuv420(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return staged_workspace(ctx, B, H, W, precision, 1).total;
 }
 
 size_t fiunet_workspace_bytes_yuv420p10(const fiunet_ctx* ctx, int B, int H, int W, int precision)
 {
-    const size_t base = fiunet_workspace_bytes_p10(ctx, B, H, W, precision);
-    if (base == 0) return 0;
-    return align256(base) + 3 * align256((size_t)B * 3 * H * W * 2);
+    return staged_workspace(ctx, B, H, W, precision, 2).total;
+}
+
+int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
+                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
+                          void* workspace, size_t workspace_bytes, void* stream)
+{
+    return forward_yuv420<uint8_t>("fiunet_forward_yuv420", 8, ctx, frame1, frame2, out, out_frame_stride, B, H, W, colour,
+                                   precision, workspace, workspace_bytes, stream);
 }
 
 int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
                              size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
                              void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    int rc;
-    if ((rc = check_colour_p10_flags(colour))) return rc;
-    if (B < 1) return fail(FIUNET_ERR_INVALID_ARG, "B < 1");
-    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
-    const size_t fs = i420_frame_bytes(H, W);
-    if (out_frame_stride == 0) out_frame_stride = fs;
-    if (out_frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, "out_frame_stride smaller than one frame");
-    if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->cf != 3)
-        return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_yuv420p10 needs the RGB network (frame_channels 3)");
-    const size_t need = fiunet_workspace_bytes_yuv420p10(ctx, B, H, W, precision);
-    if (need == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
-    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    // [fiunet_forward_p10's workspace | frame1 RGB | frame2 RGB | output RGB], uint16 planar [B, 3, H, W] each
-    const size_t base = align256(fiunet_workspace_bytes_p10(ctx, B, H, W, precision));
-    const size_t rgb = align256((size_t)B * 3 * H * W * 2);
-    uint16_t* a = (uint16_t*)((char*)workspace + base);
-    uint16_t* b = (uint16_t*)((char*)a + rgb);
-    uint16_t* o = (uint16_t*)((char*)b + rgb);
-    if ((rc = fiunet_yuv420p10_to_rgb_p10(frame1, fs, a, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_yuv420p10_to_rgb_p10(frame2, fs, b, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
-    return fiunet_rgb_p10_to_yuv420p10(o, out, out_frame_stride, B, H, W, colour, stream);
+    return forward_yuv420<uint16_t>("fiunet_forward_yuv420p10", 10, ctx, frame1, frame2, out, out_frame_stride, B, H, W,
+                                    colour, precision, workspace, workspace_bytes, stream);
 }
 
 // ---- NV12 / P010 decoder surfaces: the colour conversions on semi-planar, pitched frames ----
@@ -1665,20 +1686,11 @@ static int surface_to_rgb(const T* in, const fiunet_surface_layout* layout, T* o
                           unsigned colour, int bits, void* stream)
 {
     int rc;
-    if (bits == 10 && (rc = check_colour_p10_flags(colour))) return rc;
-    if ((rc = check_colour_args(in, out, B, H, W, bits == 10 ? colour & kColourFlags : colour))) return rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
     ColourSurface sf;
     if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
-    const ColourCoef k = colour_coef(colour, bits);
-    if (surface_vec<T>(sf, W, in, out))
-        hipLaunchKernelGGL((nv12_to_rgb_kernel<T, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, sf, out,
-                           H, W, k);
-    else
-        hipLaunchKernelGGL((nv12_to_rgb_kernel<T, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, sf, out,
-                           H, W, k);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return launch_vec<&nv12_to_rgb_kernel<T, true>, &nv12_to_rgb_kernel<T, false>>(
+        surface_vec<T>(sf, W, in, out), colour_grid(W, H, B), stream, in, sf, out, H, W, colour_coef(colour, bits));
 }
 
 template <typename T>
@@ -1686,20 +1698,30 @@ static int rgb_to_surface(const T* in, T* out, const fiunet_surface_layout* layo
                           unsigned colour, int bits, void* stream)
 {
     int rc;
-    if (bits == 10 && (rc = check_colour_p10_flags(colour))) return rc;
-    if ((rc = check_colour_args(in, out, B, H, W, bits == 10 ? colour & kColourFlags : colour))) return rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
     ColourSurface sf;
     if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)((H + 1) / 2), (unsigned)B);
-    const ColourCoef k = colour_coef(colour, bits);
-    if (surface_vec<T>(sf, W, in, out))
-        hipLaunchKernelGGL((rgb_to_nv12_kernel<T, true>), grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, out, sf,
-                           H, W, k);
-    else
-        hipLaunchKernelGGL((rgb_to_nv12_kernel<T, false>), grid, dim3(kColourBlock), 0, (hipStream_t)stream, in, out, sf,
-                           H, W, k);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return launch_vec<&rgb_to_nv12_kernel<T, true>, &rgb_to_nv12_kernel<T, false>>(
+        surface_vec<T>(sf, W, in, out), colour_grid(W, (H + 1) / 2, B), stream, in, out, sf, H, W,
+        colour_coef(colour, bits));
+}
+
+template <typename T>
+static int forward_surface(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2,
+                           const fiunet_surface_layout* in_layout, T* out, const fiunet_surface_layout* out_layout, int B,
+                           int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                           void* stream)
+{
+    return forward_staged<T>(
+        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
+        [&] {
+            ColourSurface sf;
+            int rc = check_colour_flags(colour, bits);
+            if (!rc && !(rc = resolve_surface(in_layout, H, W, &sf))) rc = resolve_surface(out_layout, H, W, &sf);
+            return rc;
+        },
+        [&](const T* in, T* rgb) { return surface_to_rgb<T>(in, in_layout, rgb, B, H, W, colour, bits, stream); },
+        [&](const T* rgb) { return rgb_to_surface<T>(rgb, out, out_layout, B, H, W, colour, bits, stream); });
 }
 }  // extern "C++"
 
@@ -1729,12 +1751,12 @@ int fiunet_rgb_p10_to_p010(const uint16_t* in, uint16_t* out, const fiunet_surfa
 
 size_t fiunet_workspace_bytes_nv12(const fiunet_ctx* ctx, int B, int H, int W, int precision)
 {
-    return fiunet_workspace_bytes_yuv420(ctx, B, H, W, precision);
+    return staged_workspace(ctx, B, H, W, precision, 1).total;
 }
 
 size_t fiunet_workspace_bytes_p010(const fiunet_ctx* ctx, int B, int H, int W, int precision)
 {
-    return fiunet_workspace_bytes_yuv420p10(ctx, B, H, W, precision);
+    return staged_workspace(ctx, B, H, W, precision, 2).total;
 }
 
 int fiunet_forward_nv12(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
@@ -1742,25 +1764,8 @@ int fiunet_forward_nv12(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* f
                         int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
                         void* stream)
 {
-    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->cf != 3) return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_nv12 needs the RGB network (frame_channels 3)");
-    if (colour & ~kColourFlags) return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits");
-    const size_t need = fiunet_workspace_bytes_nv12(ctx, B, H, W, precision);
-    if (need == 0) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
-    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    int rc;
-    ColourSurface sf;   // both layouts are refused here, before the first launch
-    if ((rc = resolve_surface(in_layout, H, W, &sf)) || (rc = resolve_surface(out_layout, H, W, &sf))) return rc;
-    const size_t base = align256(fiunet_workspace_bytes_u8(ctx, B, H, W, precision));
-    const size_t rgb = align256((size_t)B * 3 * H * W);
-    uint8_t* a = (uint8_t*)workspace + base;
-    uint8_t* b = a + rgb;
-    uint8_t* o = b + rgb;
-    if ((rc = fiunet_nv12_to_rgb_u8(frame1, in_layout, a, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_nv12_to_rgb_u8(frame2, in_layout, b, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
-    return fiunet_rgb_to_nv12_u8(o, out, out_layout, B, H, W, colour, stream);
+    return forward_surface<uint8_t>("fiunet_forward_nv12", 8, ctx, frame1, frame2, in_layout, out, out_layout, B, H, W,
+                                    colour, precision, workspace, workspace_bytes, stream);
 }
 
 int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2,
@@ -1768,30 +1773,8 @@ int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t*
                         int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
                         void* stream)
 {
-    if (!frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    int rc;
-    if ((rc = check_colour_p10_flags(colour))) return rc;
-    if (B < 1) return fail(FIUNET_ERR_INVALID_ARG, "B < 1");
-    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
-    ColourSurface sf;   // both layouts are refused here, before the first launch
-    if ((rc = resolve_surface(in_layout, H, W, &sf)) || (rc = resolve_surface(out_layout, H, W, &sf))) return rc;
-    if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->cf != 3)
-        return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_p010 needs the RGB network (frame_channels 3)");
-    const size_t need = fiunet_workspace_bytes_p010(ctx, B, H, W, precision);
-    if (need == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
-    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    // [fiunet_forward_p10's workspace | frame1 RGB | frame2 RGB | output RGB], uint16 planar [B, 3, H, W] each
-    const size_t base = align256(fiunet_workspace_bytes_p10(ctx, B, H, W, precision));
-    const size_t rgb = align256((size_t)B * 3 * H * W * 2);
-    uint16_t* a = (uint16_t*)((char*)workspace + base);
-    uint16_t* b = (uint16_t*)((char*)a + rgb);
-    uint16_t* o = (uint16_t*)((char*)b + rgb);
-    if ((rc = fiunet_p010_to_rgb_p10(frame1, in_layout, a, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_p010_to_rgb_p10(frame2, in_layout, b, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
-    return fiunet_rgb_p10_to_p010(o, out, out_layout, B, H, W, colour, stream);
+    return forward_surface<uint16_t>("fiunet_forward_p010", 10, ctx, frame1, frame2, in_layout, out, out_layout, B, H, W,
+                                     colour, precision, workspace, workspace_bytes, stream);
 }
 
 // ---- YUV 4:2:2 / 4:4:4 frames (csrc/yuv4xx.hip.h): planar and one-plane packed, <-> planar RGB ----
@@ -1812,12 +1795,7 @@ static size_t yuv_frame_samples(int format, int H, int W)
 static int resolve_yuv(int format, int bits, size_t row_pitch, size_t frame_stride, int B, int H, int W, unsigned colour,
                        YuvLayout* lay)
 {
-    int rc;
-    if (bits == 10) {
-        if ((rc = check_colour_p10_flags(colour))) return rc;
-    } else if (colour & ~kColourFlags) {
-        return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits (FIUNET_YUV_BT2020 needs the 10-bit entry points)");
-    }
+    if (int rc = check_colour_flags(colour, bits)) return rc;
     if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
     const size_t tight = yuv_frame_samples(format, H, W);
     if (!tight) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_yuv_format");
@@ -1850,24 +1828,19 @@ static bool yuv_vec(const YuvLayout& lay, int W, const void* a, const void* b)
            (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
 }
 
-template <typename T, int FMT>
-static void launch_yuv_to_rgb(bool vec, dim3 grid, hipStream_t st, const T* in, YuvLayout lay, T* out, int H, int W,
-                              const ColourCoef& k)
-{
-    if (vec)
-        hipLaunchKernelGGL((yuv_to_rgb_kernel<T, FMT, true>), grid, dim3(kColourBlock), 0, st, in, lay, out, H, W, k);
-    else
-        hipLaunchKernelGGL((yuv_to_rgb_kernel<T, FMT, false>), grid, dim3(kColourBlock), 0, st, in, lay, out, H, W, k);
-}
+template <int F>
+using YuvFormat = std::integral_constant<int, F>;
 
-template <typename T, int FMT>
-static void launch_rgb_to_yuv(bool vec, dim3 grid, hipStream_t st, const T* in, T* out, YuvLayout lay, int H, int W,
-                              const ColourCoef& k)
+// go(YuvFormat<F>{}) for the resolved `format` (the one-plane formats exist at 8 bits only: resolve_yuv has refused them
+// at 10, and their uint16 kernels are never instantiated)
+template <typename T, typename Go>
+static int for_yuv_format(int format, Go go)
 {
-    if (vec)
-        hipLaunchKernelGGL((rgb_to_yuv_kernel<T, FMT, true>), grid, dim3(kColourBlock), 0, st, in, out, lay, H, W, k);
-    else
-        hipLaunchKernelGGL((rgb_to_yuv_kernel<T, FMT, false>), grid, dim3(kColourBlock), 0, st, in, out, lay, H, W, k);
+    if (format == FIUNET_YUV_422P) return go(YuvFormat<FIUNET_YUV_422P>{});
+    if (format == FIUNET_YUV_444P) return go(YuvFormat<FIUNET_YUV_444P>{});
+    if constexpr (sizeof(T) == 1)
+        return format == FIUNET_YUV_UYVY422 ? go(YuvFormat<FIUNET_YUV_UYVY422>{}) : go(YuvFormat<FIUNET_YUV_YUYV422>{});
+    return FIUNET_OK;
 }
 
 template <typename T>
@@ -1875,21 +1848,13 @@ static int yuv_to_rgb(const T* in, int format, size_t row_pitch, size_t frame_st
                       unsigned colour, int bits, void* stream)
 {
     if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    int rc;
     YuvLayout lay;
-    if ((rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay))) return rc;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
-    const ColourCoef k = colour_coef(colour, bits);
-    const bool vec = yuv_vec<T>(lay, W, in, out);
-    hipStream_t st = (hipStream_t)stream;
-    if (format == FIUNET_YUV_422P) launch_yuv_to_rgb<T, FIUNET_YUV_422P>(vec, grid, st, in, lay, out, H, W, k);
-    else if (format == FIUNET_YUV_444P) launch_yuv_to_rgb<T, FIUNET_YUV_444P>(vec, grid, st, in, lay, out, H, W, k);
-    else if constexpr (sizeof(T) == 1) {
-        if (format == FIUNET_YUV_UYVY422) launch_yuv_to_rgb<T, FIUNET_YUV_UYVY422>(vec, grid, st, in, lay, out, H, W, k);
-        else launch_yuv_to_rgb<T, FIUNET_YUV_YUYV422>(vec, grid, st, in, lay, out, H, W, k);
-    }
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    if (int rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay)) return rc;
+    return for_yuv_format<T>(format, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        return launch_vec<&yuv_to_rgb_kernel<T, F, true>, &yuv_to_rgb_kernel<T, F, false>>(
+            yuv_vec<T>(lay, W, in, out), colour_grid(W, H, B), stream, in, lay, out, H, W, colour_coef(colour, bits));
+    });
 }
 
 template <typename T>
@@ -1897,21 +1862,34 @@ static int rgb_to_yuv(const T* in, T* out, int format, size_t row_pitch, size_t 
                       unsigned colour, int bits, void* stream)
 {
     if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    int rc;
     YuvLayout lay;
-    if ((rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay))) return rc;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
-    const ColourCoef k = colour_coef(colour, bits);
-    const bool vec = yuv_vec<T>(lay, W, in, out);
-    hipStream_t st = (hipStream_t)stream;
-    if (format == FIUNET_YUV_422P) launch_rgb_to_yuv<T, FIUNET_YUV_422P>(vec, grid, st, in, out, lay, H, W, k);
-    else if (format == FIUNET_YUV_444P) launch_rgb_to_yuv<T, FIUNET_YUV_444P>(vec, grid, st, in, out, lay, H, W, k);
-    else if constexpr (sizeof(T) == 1) {
-        if (format == FIUNET_YUV_UYVY422) launch_rgb_to_yuv<T, FIUNET_YUV_UYVY422>(vec, grid, st, in, out, lay, H, W, k);
-        else launch_rgb_to_yuv<T, FIUNET_YUV_YUYV422>(vec, grid, st, in, out, lay, H, W, k);
-    }
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    if (int rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay)) return rc;
+    return for_yuv_format<T>(format, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        return launch_vec<&rgb_to_yuv_kernel<T, F, true>, &rgb_to_yuv_kernel<T, F, false>>(
+            yuv_vec<T>(lay, W, in, out), colour_grid(W, H, B), stream, in, out, lay, H, W, colour_coef(colour, bits));
+    });
+}
+
+template <typename T>
+static int forward_yuv(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2, int format,
+                       size_t in_row_pitch, size_t in_frame_stride, T* out, size_t out_row_pitch, size_t out_frame_stride,
+                       int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                       void* stream)
+{
+    return forward_staged<T>(
+        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
+        [&] {
+            YuvLayout lay;
+            const int rc = resolve_yuv(format, bits, in_row_pitch, in_frame_stride, B, H, W, colour, &lay);
+            return rc ? rc : resolve_yuv(format, bits, out_row_pitch, out_frame_stride, B, H, W, colour, &lay);
+        },
+        [&](const T* in, T* rgb) {
+            return yuv_to_rgb<T>(in, format, in_row_pitch, in_frame_stride, rgb, B, H, W, colour, bits, stream);
+        },
+        [&](const T* rgb) {
+            return rgb_to_yuv<T>(rgb, out, format, out_row_pitch, out_frame_stride, B, H, W, colour, bits, stream);
+        });
 }
 }  // extern "C++"
 
@@ -1941,8 +1919,7 @@ int fiunet_rgb_p10_to_yuv(const uint16_t* in, uint16_t* out, int format, size_t 
 
 size_t fiunet_workspace_bytes_yuv(const fiunet_ctx* ctx, int B, int H, int W, int precision, int bits)
 {
-    if (bits == 8) return fiunet_workspace_bytes_yuv420(ctx, B, H, W, precision);
-    if (bits == 10) return fiunet_workspace_bytes_yuv420p10(ctx, B, H, W, precision);
+    if (bits == 8 || bits == 10) return staged_workspace(ctx, B, H, W, precision, bits == 8 ? 1 : 2).total;
     g_err = "fiunet_workspace_bytes_yuv: bits must be 8 or 10";
     return 0;
 }
@@ -1951,27 +1928,9 @@ int fiunet_forward_yuv(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* fr
                        size_t in_frame_stride, uint8_t* out, size_t out_row_pitch, size_t out_frame_stride, int B, int H,
                        int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->cf != 3) return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_yuv needs the RGB network (frame_channels 3)");
-    int rc;
-    YuvLayout lay;   // format, colour and both layouts are refused here, before the first launch
-    if ((rc = resolve_yuv(format, 8, in_row_pitch, in_frame_stride, B, H, W, colour, &lay)) ||
-        (rc = resolve_yuv(format, 8, out_row_pitch, out_frame_stride, B, H, W, colour, &lay)))
-        return rc;
-    const size_t need = fiunet_workspace_bytes_yuv(ctx, B, H, W, precision, 8);
-    if (need == 0) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
-    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    // [fiunet_forward_u8's workspace | frame1 RGB | frame2 RGB | output RGB], uint8 planar [B, 3, H, W] each
-    const size_t base = align256(fiunet_workspace_bytes_u8(ctx, B, H, W, precision));
-    const size_t rgb = align256((size_t)B * 3 * H * W);
-    uint8_t* a = (uint8_t*)workspace + base;
-    uint8_t* b = a + rgb;
-    uint8_t* o = b + rgb;
-    if ((rc = fiunet_yuv_to_rgb_u8(frame1, format, in_row_pitch, in_frame_stride, a, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_yuv_to_rgb_u8(frame2, format, in_row_pitch, in_frame_stride, b, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
-    return fiunet_rgb_to_yuv_u8(o, out, format, out_row_pitch, out_frame_stride, B, H, W, colour, stream);
+    return forward_yuv<uint8_t>("fiunet_forward_yuv", 8, ctx, frame1, frame2, format, in_row_pitch, in_frame_stride, out,
+                                out_row_pitch, out_frame_stride, B, H, W, colour, precision, workspace, workspace_bytes,
+                                stream);
 }
 
 int fiunet_forward_yuv_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, int format,
@@ -1979,29 +1938,9 @@ int fiunet_forward_yuv_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16
                            size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision, void* workspace,
                            size_t workspace_bytes, void* stream)
 {
-    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->cf != 3)
-        return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_yuv_p10 needs the RGB network (frame_channels 3)");
-    int rc;
-    YuvLayout lay;   // format, colour and both layouts are refused here, before the first launch
-    if ((rc = resolve_yuv(format, 10, in_row_pitch, in_frame_stride, B, H, W, colour, &lay)) ||
-        (rc = resolve_yuv(format, 10, out_row_pitch, out_frame_stride, B, H, W, colour, &lay)))
-        return rc;
-    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
-    const size_t need = fiunet_workspace_bytes_yuv(ctx, B, H, W, precision, 10);
-    if (need == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
-    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    // [fiunet_forward_p10's workspace | frame1 RGB | frame2 RGB | output RGB], uint16 planar [B, 3, H, W] each
-    const size_t base = align256(fiunet_workspace_bytes_p10(ctx, B, H, W, precision));
-    const size_t rgb = align256((size_t)B * 3 * H * W * 2);
-    uint16_t* a = (uint16_t*)((char*)workspace + base);
-    uint16_t* b = (uint16_t*)((char*)a + rgb);
-    uint16_t* o = (uint16_t*)((char*)b + rgb);
-    if ((rc = fiunet_yuv_to_rgb_p10(frame1, format, in_row_pitch, in_frame_stride, a, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_yuv_to_rgb_p10(frame2, format, in_row_pitch, in_frame_stride, b, B, H, W, colour, stream))) return rc;
-    if ((rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
-    return fiunet_rgb_p10_to_yuv(o, out, format, out_row_pitch, out_frame_stride, B, H, W, colour, stream);
+    return forward_yuv<uint16_t>("fiunet_forward_yuv_p10", 10, ctx, frame1, frame2, format, in_row_pitch, in_frame_stride,
+                                 out, out_row_pitch, out_frame_stride, B, H, W, colour, precision, workspace,
+                                 workspace_bytes, stream);
 }
 
 // ---- packed RGB frames: rgb24 / bgr24 / rgba / bgra, rows a pitch apart, <-> planar RGB ----
@@ -2040,25 +1979,23 @@ static bool packed_vec(int W, const PackedLayout& l, uintptr_t bases)
     return W % 4 == 0 && (l.row_pitch | l.frame_stride) % 4 == 0 && (bases & 3) == 0;
 }
 
-extern "C++" {   // (templates over the format, inside this file's extern "C" part)
+extern "C++" {
 template <int BPP, bool SWAP>
-static void launch_packed_to_rgb(bool vec, dim3 grid, hipStream_t st, const uint8_t* in, PackedLayout li, uint8_t* out,
-                                 uint8_t* alpha, int H, int W)
-{
-    if (vec)
-        hipLaunchKernelGGL((packed_to_rgb_kernel<BPP, SWAP, true>), grid, dim3(kColourBlock), 0, st, in, li, out, alpha, H, W);
-    else
-        hipLaunchKernelGGL((packed_to_rgb_kernel<BPP, SWAP, false>), grid, dim3(kColourBlock), 0, st, in, li, out, alpha, H, W);
-}
+struct PackedFormat {
+    static constexpr int bpp = BPP;
+    static constexpr bool swap = SWAP;
+};
 
-template <int BPP, bool SWAP>
-static void launch_rgb_to_packed(bool vec, dim3 grid, hipStream_t st, const uint8_t* in, uint8_t* out, PackedLayout lo,
-                                 const uint8_t* a1, const uint8_t* a2, PackedLayout la, int H, int W)
+// go(PackedFormat<bpp, swap>{}) for a format that packed_bpp() knows
+template <typename Go>
+static int for_packed_format(int format, Go go)
 {
-    if (vec)
-        hipLaunchKernelGGL((rgb_to_packed_kernel<BPP, SWAP, true>), grid, dim3(kColourBlock), 0, st, in, out, lo, a1, a2, la, H, W);
-    else
-        hipLaunchKernelGGL((rgb_to_packed_kernel<BPP, SWAP, false>), grid, dim3(kColourBlock), 0, st, in, out, lo, a1, a2, la, H, W);
+    switch (format) {
+    case FIUNET_PACKED_RGB24: return go(PackedFormat<3, false>{});
+    case FIUNET_PACKED_BGR24: return go(PackedFormat<3, true>{});
+    case FIUNET_PACKED_RGBA: return go(PackedFormat<4, false>{});
+    default: return go(PackedFormat<4, true>{});
+    }
 }
 }  // extern "C++"
 
@@ -2071,17 +2008,12 @@ int fiunet_packed_to_rgb_u8(const uint8_t* in, const fiunet_packed_layout* in_la
     if (alpha_out && bpp != 4) return fail(FIUNET_ERR_INVALID_ARG, "alpha_out: the format has no alpha byte");
     PackedLayout li;
     if ((rc = resolve_packed(in_layout, H, W, bpp, &li))) return rc;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
     const bool vec = packed_vec(W, li, (uintptr_t)in | (uintptr_t)out_rgb | (uintptr_t)alpha_out);
-    hipStream_t st = (hipStream_t)stream;
-    switch (format) {
-    case FIUNET_PACKED_RGB24: launch_packed_to_rgb<3, false>(vec, grid, st, in, li, out_rgb, alpha_out, H, W); break;
-    case FIUNET_PACKED_BGR24: launch_packed_to_rgb<3, true>(vec, grid, st, in, li, out_rgb, alpha_out, H, W); break;
-    case FIUNET_PACKED_RGBA: launch_packed_to_rgb<4, false>(vec, grid, st, in, li, out_rgb, alpha_out, H, W); break;
-    default: launch_packed_to_rgb<4, true>(vec, grid, st, in, li, out_rgb, alpha_out, H, W); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return for_packed_format(format, [&](auto f) {
+        using F = decltype(f);
+        return launch_vec<&packed_to_rgb_kernel<F::bpp, F::swap, true>, &packed_to_rgb_kernel<F::bpp, F::swap, false>>(
+            vec, colour_grid(W, H, B), stream, in, li, out_rgb, alpha_out, H, W);
+    });
 }
 
 int fiunet_rgb_to_packed_u8(const uint8_t* in_rgb, uint8_t* out, const fiunet_packed_layout* out_layout,
@@ -2096,23 +2028,18 @@ int fiunet_rgb_to_packed_u8(const uint8_t* in_rgb, uint8_t* out, const fiunet_pa
     PackedLayout lo, la;
     if ((rc = resolve_packed(out_layout, H, W, bpp, &lo))) return rc;
     if ((rc = resolve_packed(alpha_layout, H, W, bpp, &la))) return rc;
-    const dim3 grid((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)H, (unsigned)B);
     const bool vec = packed_vec(W, lo, (uintptr_t)in_rgb | (uintptr_t)out | (uintptr_t)alpha1 | (uintptr_t)alpha2) &&
                      (!alpha1 || packed_vec(W, la, 0));
-    hipStream_t st = (hipStream_t)stream;
-    switch (format) {
-    case FIUNET_PACKED_RGB24: launch_rgb_to_packed<3, false>(vec, grid, st, in_rgb, out, lo, alpha1, alpha2, la, H, W); break;
-    case FIUNET_PACKED_BGR24: launch_rgb_to_packed<3, true>(vec, grid, st, in_rgb, out, lo, alpha1, alpha2, la, H, W); break;
-    case FIUNET_PACKED_RGBA: launch_rgb_to_packed<4, false>(vec, grid, st, in_rgb, out, lo, alpha1, alpha2, la, H, W); break;
-    default: launch_rgb_to_packed<4, true>(vec, grid, st, in_rgb, out, lo, alpha1, alpha2, la, H, W); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return for_packed_format(format, [&](auto f) {
+        using F = decltype(f);
+        return launch_vec<&rgb_to_packed_kernel<F::bpp, F::swap, true>, &rgb_to_packed_kernel<F::bpp, F::swap, false>>(
+            vec, colour_grid(W, H, B), stream, in_rgb, out, lo, alpha1, alpha2, la, H, W);
+    });
 }
 
 size_t fiunet_workspace_bytes_rgb_packed(const fiunet_ctx* ctx, int B, int H, int W, int precision)
 {
-    return fiunet_workspace_bytes_yuv420(ctx, B, H, W, precision);
+    return staged_workspace(ctx, B, H, W, precision, 1).total;
 }
 
 int fiunet_forward_rgb_packed(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
@@ -2120,30 +2047,21 @@ int fiunet_forward_rgb_packed(fiunet_ctx* ctx, const uint8_t* frame1, const uint
                               int B, int H, int W, int format, int precision, void* workspace, size_t workspace_bytes,
                               void* stream)
 {
-    if (!ctx || !frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->cf != 3)
-        return fail(FIUNET_ERR_UNSUPPORTED, "fiunet_forward_rgb_packed needs the RGB network (frame_channels 3)");
     const int bpp = packed_bpp(format);
-    if (!bpp) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
-    const size_t need = fiunet_workspace_bytes_rgb_packed(ctx, B, H, W, precision);
-    if (need == 0) return fail(H < 16 || W < 16 ? FIUNET_ERR_BAD_SHAPE : FIUNET_ERR_INVALID_ARG, "bad shape");
-    if (workspace_bytes < need) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    int rc;
-    PackedLayout pl;   // both layouts are refused here, before the first launch
-    if ((rc = resolve_packed(in_layout, H, W, bpp, &pl)) || (rc = resolve_packed(out_layout, H, W, bpp, &pl))) return rc;
-    // [fiunet_forward_u8's workspace | frame1 RGB | frame2 RGB | output RGB], uint8 planar [B, 3, H, W] each
-    const size_t base = align256(fiunet_workspace_bytes_u8(ctx, B, H, W, precision));
-    const size_t rgb = align256((size_t)B * 3 * H * W);
-    uint8_t* a = (uint8_t*)workspace + base;
-    uint8_t* b = a + rgb;
-    uint8_t* o = b + rgb;
-    if ((rc = fiunet_packed_to_rgb_u8(frame1, in_layout, a, NULL, B, H, W, format, stream))) return rc;
-    if ((rc = fiunet_packed_to_rgb_u8(frame2, in_layout, b, NULL, B, H, W, format, stream))) return rc;
-    if ((rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, base, stream))) return rc;
     const bool alpha = bpp == 4;   // the inserted frame's alpha: the rounded average of its neighbours'
-    return fiunet_rgb_to_packed_u8(o, out, out_layout, alpha ? frame1 : NULL, alpha ? frame2 : NULL, in_layout, B, H, W,
-                                   format, stream);
+    return forward_staged<uint8_t>(
+        "fiunet_forward_rgb_packed", ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
+        [&] {
+            if (!bpp) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
+            PackedLayout pl;
+            const int rc = resolve_packed(in_layout, H, W, bpp, &pl);
+            return rc ? rc : resolve_packed(out_layout, H, W, bpp, &pl);
+        },
+        [&](const uint8_t* in, uint8_t* rgb) { return fiunet_packed_to_rgb_u8(in, in_layout, rgb, NULL, B, H, W, format, stream); },
+        [&](const uint8_t* rgb) {
+            return fiunet_rgb_to_packed_u8(rgb, out, out_layout, alpha ? frame1 : NULL, alpha ? frame2 : NULL, in_layout, B,
+                                           H, W, format, stream);
+        });
 }
 
 static inline int ssim_tiles(int H, int W, int* tiles_x)

@@ -378,7 +378,7 @@ class FrameInterpolationUNet(nn.Module):
         colour.py (matrix defaults to "bt709", a convention for HD video: Y4M does not carry it).  `out`: write there -
         uint8 [B, F] on the same device, every frame contiguous; the frames may lie apart (the video loop passes every
         second frame of its interleaved result)."""
-        return self._forward_packed("forward_yuv420", 8, frame1, frame2, height, width, out, siting, matrix, colour_range)
+        return self._forward_i420("forward_yuv420", 8, frame1, frame2, height, width, out, siting, matrix, colour_range)
 
     @torch.no_grad()
     def forward_p10(self, frame1: torch.Tensor, frame2: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -412,70 +412,66 @@ class FrameInterpolationUNet(nn.Module):
         `fiunet_forward_yuv420p10`: YUV -> planar RGB, `forward_p10`, RGB -> YUV on device.  matrix
         also takes "bt2020".  The network interpolates code values, as it does for 8-bit video (no PQ / HLG
         linearisation).  Use fp16 (or bf16x2, fp32): bf16 is about 5 codes off.  `out`: as for `forward_yuv420`."""
-        return self._forward_packed("forward_yuv420p10", 10, frame1, frame2, height, width, out, siting, matrix,
-                                    colour_range)
+        return self._forward_i420("forward_yuv420p10", 10, frame1, frame2, height, width, out, siting, matrix,
+                                  colour_range)
 
-    def _forward_packed(self, name, bits, frame1, frame2, height, width, out, siting, matrix, colour_range):
+    def _forward_i420(self, name, bits, frame1, frame2, height, width, out, siting, matrix, colour_range):
         from .colour import colour_flags, i420_frame_bytes
         dtype, kind = (torch.uint16, "4:2:0 10-bit") if bits == 10 else (torch.uint8, "I420")
         flags = colour_flags(siting, matrix, colour_range, bits=bits)
-        if self.frame_channels != 3:
-            raise RuntimeError(f"{name} runs the RGB network (frame_channels=3); this model is grayscale")
+        self._need_rgb(name)
         h, w = int(height), int(width)
         fs = i420_frame_bytes(h, w)   # samples per packed 4:2:0 frame, at either depth
-        if frame1.dim() != 2 or frame1.shape != frame2.shape or frame1.shape[1] != fs:
-            raise RuntimeError(f"expected two [B,{fs}] tensors (packed {kind} frames of {h}x{w}) of equal shape, got "
-                               f"{tuple(frame1.shape)} and {tuple(frame2.shape)}")
-        self._check_device_mode_dtype(frame1, frame2, (dtype,))
-        if bits == 8:
-            frame1, frame2 = frame1.contiguous(), frame2.contiguous()
-        elif not frame1.is_contiguous() or not frame2.is_contiguous():
-            raise ValueError(f"{name} takes contiguous frames")
-        b = frame1.shape[0]
-        prec = self._precision_code()
-        ctx = self._context(frame1.device)
-        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=bits == 10)
-        if out is None:
-            out = torch.empty_like(frame1)
-        elif (out.dtype != dtype or out.shape != frame1.shape or out.device != frame1.device
-              or out.stride(1) != 1 or (b > 1 and out.stride(0) < fs)):
-            raise ValueError(f"out must be a {str(dtype).split('.')[-1]} {tuple(frame1.shape)} tensor on "
-                             f"{frame1.device} whose frames are contiguous")
-        with torch.cuda.device(frame1.device):
-            ctx.forward_yuv420(frame1, frame2, out, h, w, flags, prec, ws, bits)
-        return out
+        return self._forward_frames(
+            name, f"packed {kind} frames", dtype, frame1, frame2, h, w, fs, fs, True, out, bits == 10,
+            lambda ctx, f1, f2, o, prec, ws: ctx.forward_yuv420(f1, f2, o, h, w, flags, prec, ws, bits), copy=bits == 8)
 
     def _forward_surface(self, name, bits, frame1, frame2, height, width, layout, out, out_layout, siting, matrix,
                          colour_range):
         from .colour import colour_flags, resolve_layout
         dtype, kind = (torch.uint16, "P010") if bits == 10 else (torch.uint8, "NV12")
         flags = colour_flags("mpeg2" if siting is None else siting, matrix, colour_range, bits=bits)
-        if self.frame_channels != 3:
-            raise RuntimeError(f"{name} runs the RGB network (frame_channels=3); this model is grayscale")
+        self._need_rgb(name)
         h, w = int(height), int(width)
         lay = resolve_layout(layout, h, w)
         olay = resolve_layout(out_layout, h, w)
-        if frame1.dim() != 2 or frame1.shape != frame2.shape or frame1.shape[1] != lay.frame_stride:
-            raise RuntimeError(f"expected two [B,{lay.frame_stride}] tensors ({kind} surfaces of {h}x{w}) of equal "
-                               f"shape, got {tuple(frame1.shape)} and {tuple(frame2.shape)}")
+        return self._forward_frames(
+            name, f"{kind} surfaces", dtype, frame1, frame2, h, w, lay.frame_stride, olay.frame_stride,
+            olay == resolve_layout(None, h, w), out, bits == 10,
+            lambda ctx, f1, f2, o, prec, ws: ctx.forward_surface(f1, f2, lay, o, olay, h, w, flags, prec, ws, bits))
+
+    def _need_rgb(self, name):
+        if self.frame_channels != 3:
+            raise RuntimeError(f"{name} runs the RGB network (frame_channels=3); this model is grayscale")
+
+    def _forward_frames(self, name, what, dtype, frame1, frame2, h, w, fs, out_fs, tight_out, out, p10, call, copy=False):
+        """The body every frame-format forward shares, behind the public method's own pre-checks: two [B, fs] tensors of
+        `dtype` (fs: the input layout's frame stride; `what`: the message's words for the frames) -> `out` [B, out_fs], new
+        unless given, through one native call `call(ctx, frame1, frame2, out, prec, ws)`.  tight_out: the output layout
+        leaves no sample unwritten.  copy: make non-contiguous frames contiguous instead of refusing them."""
+        if (not isinstance(frame1, torch.Tensor) or not isinstance(frame2, torch.Tensor) or frame1.dim() != 2
+                or frame1.shape != frame2.shape or frame1.shape[1] != fs):
+            raise RuntimeError(f"expected two [B,{fs}] tensors ({what} of {h}x{w}) of equal shape, got "
+                               f"{tuple(getattr(frame1, 'shape', ()))} and {tuple(getattr(frame2, 'shape', ()))}")
         self._check_device_mode_dtype(frame1, frame2, (dtype,))
-        if not frame1.is_contiguous() or not frame2.is_contiguous():
+        if copy:
+            frame1, frame2 = frame1.contiguous(), frame2.contiguous()
+        elif not frame1.is_contiguous() or not frame2.is_contiguous():
             raise ValueError(f"{name} takes contiguous frames")
         b = frame1.shape[0]
         prec = self._precision_code()
         ctx = self._context(frame1.device)
-        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=bits == 10)
-        shape = (b, olay.frame_stride)
+        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=p10)
+        shape = (b, out_fs)
         if out is None:
-            # (a pitched surface has samples no frame covers: they are never written, so a new one starts as zeros)
-            out = (torch.empty if olay == resolve_layout(None, h, w) else torch.zeros)(shape, dtype=dtype,
-                                                                                        device=frame1.device)
+            # (a pitched frame has samples no pixel covers: they are never written, so a new one starts as zeros)
+            out = (torch.empty if tight_out else torch.zeros)(shape, dtype=dtype, device=frame1.device)
         elif (out.dtype != dtype or tuple(out.shape) != shape or out.device != frame1.device
-              or out.stride(1) != 1 or (b > 1 and out.stride(0) < olay.frame_stride)):
+              or out.stride(1) != 1 or (b > 1 and out.stride(0) < out_fs)):
             raise ValueError(f"out must be a {str(dtype).split('.')[-1]} {shape} tensor on {frame1.device} whose "
                              "frames are contiguous")
         with torch.cuda.device(frame1.device):
-            ctx.forward_surface(frame1, frame2, lay, out, olay, h, w, flags, prec, ws, bits)
+            call(ctx, frame1, frame2, out, prec, ws)
         return out
 
     @torch.no_grad()
@@ -519,34 +515,14 @@ class FrameInterpolationUNet(nn.Module):
         if format not in FORMATS:
             raise ValueError(f"format must be one of {list(FORMATS)}, got {format!r}")
         code = FORMATS[format][0]
-        if self.frame_channels != 3:
-            raise RuntimeError("forward_rgb_packed runs the RGB network (frame_channels=3); this model is grayscale")
+        self._need_rgb("forward_rgb_packed")
         h, w = int(height), int(width)
         lay = resolve_layout(layout, format, h, w)
         olay = resolve_layout(out_layout, format, h, w)
-        if (not isinstance(frame1, torch.Tensor) or not isinstance(frame2, torch.Tensor) or frame1.dim() != 2
-                or frame1.shape != frame2.shape or frame1.shape[1] != lay.frame_stride):
-            raise RuntimeError(f"expected two [B,{lay.frame_stride}] tensors (packed {format} frames of {h}x{w}) of "
-                               f"equal shape, got {tuple(getattr(frame1, 'shape', ()))} and "
-                               f"{tuple(getattr(frame2, 'shape', ()))}")
-        self._check_device_mode_dtype(frame1, frame2, (torch.uint8,))
-        if not frame1.is_contiguous() or not frame2.is_contiguous():
-            raise ValueError("forward_rgb_packed takes contiguous frames")
-        b = frame1.shape[0]
-        prec = self._precision_code()
-        ctx = self._context(frame1.device)
-        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True)
-        shape = (b, olay.frame_stride)
-        if out is None:
-            # (a pitched frame has bytes no pixel covers: they are never written, so a new one starts as zeros)
-            out = (torch.empty if olay == resolve_layout(None, format, h, w) else torch.zeros)(
-                shape, dtype=torch.uint8, device=frame1.device)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != frame1.device
-              or out.stride(1) != 1 or (b > 1 and out.stride(0) < olay.frame_stride)):
-            raise ValueError(f"out must be a uint8 {shape} tensor on {frame1.device} whose frames are contiguous")
-        with torch.cuda.device(frame1.device):
-            ctx.forward_rgb_packed(frame1, frame2, lay, out, olay, h, w, code, prec, ws)
-        return out
+        return self._forward_frames(
+            "forward_rgb_packed", f"packed {format} frames", torch.uint8, frame1, frame2, h, w, lay.frame_stride,
+            olay.frame_stride, olay == resolve_layout(None, format, h, w), out, False,
+            lambda ctx, f1, f2, o, prec, ws: ctx.forward_rgb_packed(f1, f2, lay, o, olay, h, w, code, prec, ws))
 
     @torch.no_grad()
     def forward_yuv(self, frame1: torch.Tensor, frame2: torch.Tensor, height: int, width: int, *, format: str,
@@ -571,32 +547,11 @@ class FrameInterpolationUNet(nn.Module):
         lay = resolve_yuv_layout(layout, format, h, w)
         olay = resolve_yuv_layout(out_layout, format, h, w)
         flags = yuv_flags(format, siting, matrix, colour_range)
-        if self.frame_channels != 3:
-            raise RuntimeError("forward_yuv runs the RGB network (frame_channels=3); this model is grayscale")
-        if (not isinstance(frame1, torch.Tensor) or not isinstance(frame2, torch.Tensor) or frame1.dim() != 2
-                or frame1.shape != frame2.shape or frame1.shape[1] != lay.frame_stride):
-            raise RuntimeError(f"expected two [B,{lay.frame_stride}] tensors ({format} frames of {h}x{w}) of equal "
-                               f"shape, got {tuple(getattr(frame1, 'shape', ()))} and "
-                               f"{tuple(getattr(frame2, 'shape', ()))}")
-        self._check_device_mode_dtype(frame1, frame2, (dtype,))
-        if not frame1.is_contiguous() or not frame2.is_contiguous():
-            raise ValueError("forward_yuv takes contiguous frames")
-        b = frame1.shape[0]
-        prec = self._precision_code()
-        ctx = self._context(frame1.device)
-        ws = self._workspace(ctx, frame1.device, b, h, w, prec, yuv=True, p10=bits == 10)
-        shape = (b, olay.frame_stride)
-        if out is None:
-            # (a pitched frame has bytes no pixel covers: they are never written, so a new one starts as zeros)
-            out = (torch.empty if olay == resolve_yuv_layout(None, format, h, w) else torch.zeros)(
-                shape, dtype=dtype, device=frame1.device)
-        elif (out.dtype != dtype or tuple(out.shape) != shape or out.device != frame1.device
-              or out.stride(1) != 1 or (b > 1 and out.stride(0) < olay.frame_stride)):
-            raise ValueError(f"out must be a {str(dtype).split('.')[-1]} {shape} tensor on {frame1.device} whose "
-                             "frames are contiguous")
-        with torch.cuda.device(frame1.device):
-            ctx.forward_yuv(frame1, frame2, code, lay, out, olay, h, w, flags, prec, ws, bits)
-        return out
+        self._need_rgb("forward_yuv")
+        return self._forward_frames(
+            "forward_yuv", f"{format} frames", dtype, frame1, frame2, h, w, lay.frame_stride, olay.frame_stride,
+            olay == resolve_yuv_layout(None, format, h, w), out, bits == 10,
+            lambda ctx, f1, f2, o, prec, ws: ctx.forward_yuv(f1, f2, code, lay, o, olay, h, w, flags, prec, ws, bits))
 
     @torch.no_grad()
     def debug_activations(self, frame1, frame2, taps=None, with_up=False):

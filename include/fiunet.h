@@ -234,7 +234,8 @@ size_t fiunet_workspace_bytes_yuv420(const fiunet_ctx* ctx, int B, int H, int W,
  * of its interleaved result).  Three steps in the caller's workspace: fiunet_yuv420_to_rgb_u8 of both inputs,
  * fiunet_forward_u8_strided into a planar RGB buffer, fiunet_rgb_to_yuv420_u8 into `out` - bit for bit the chain of
  * those public calls.  FIUNET_ERR_UNSUPPORTED on a context with frame_channels != 3.  Neither allocates nor
- * synchronises: it captures into a graph as fiunet_forward_u8 does. */
+ * synchronises: it captures into a graph as fiunet_forward_u8 does.  This and every fiunet_forward_<format> below make
+ * every refusal before their first launch, FIUNET_ERR_NOT_LOADED on a context without weights included. */
 int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
                           size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
                           void* workspace, size_t workspace_bytes, void* stream);
