@@ -14,6 +14,7 @@ There is no CPU fallback: CPU tensors, train mode and a missing/unbuilt extensio
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -553,31 +554,45 @@ class FrameInterpolationUNet(nn.Module):
             olay == resolve_yuv_layout(None, format, h, w), out, bits == 10,
             lambda ctx, f1, f2, o, prec, ws: ctx.forward_yuv(f1, f2, code, lay, o, olay, h, w, flags, prec, ws, bits))
 
-    @torch.no_grad()
+    @contextlib.contextmanager
+    def debug_taps(self, frame1, frame2, strip=None):
+        """Parity-test hook: run one forward keeping every stage (strip=(y_origin, image_height): `forward_strip`) and
+        yield (read, output) while the workspace still holds it.  read(tap) -> the fp32 NCHW tensor of tap 0..17 (the 18
+        conv stages) or 18..21 (the upsampled + padded halves of up1..up4), on the device, so that a caller can cut what it
+        needs there before copying; None for an upsampled half that is not stored in this configuration.  No other
+        forward of this model may run inside the block."""
+        saved = self._options
+        self._options = saved | _native.OPT_KEEP_ALL
+        self._ctx_or_none_set_options()
+        try:
+            with torch.no_grad():
+                out = self.forward(frame1, frame2) if strip is None else self.forward_strip(frame1, frame2, *strip)
+            b, _, h, w = frame1.shape
+            prec = self._precision_code()
+
+            def read(tap):
+                try:
+                    return self._ctx.read_activation(self._ws, b, h, w, prec, tap)
+                except _native.NativeError as e:
+                    if tap < 18 or e.status != _native.ERR_UNSUPPORTED:   # (unsupported = not stored in this configuration)
+                        raise
+                    return None
+            yield read, out
+        finally:
+            self._options = saved
+            self._ctx_or_none_set_options()
+
     def debug_activations(self, frame1, frame2, taps=None, with_up=False):
         """Parity-test hook: run one forward keeping every stage and return
         ({tap name: fp32 NCHW tensor}, output).  with_up: also the four upsampled + padded halves
         (`unet.up{k}.up`, as F.pad leaves them: unet.py:47-53) where they are stored - always with the
         ConvTranspose2d decoder and in precision "bf16x2"; a stage that interpolates inside its gather is skipped."""
-        saved = self._options
-        self._options = saved | _native.OPT_KEEP_ALL
-        self._ctx_or_none_set_options()
-        try:
-            out = self.forward(frame1, frame2)
-            b, _, h, w = frame1.shape
-            prec = self._precision_code()
-            acts = {}
-            for t in (range(18) if taps is None else taps):
-                acts[TAP_NAMES[t]] = self._ctx.read_activation(self._ws, b, h, w, prec, t)
+        with self.debug_taps(frame1, frame2) as (read, out):
+            acts = {TAP_NAMES[t]: read(t) for t in (range(18) if taps is None else taps)}
             for k in (range(4) if with_up else ()):
-                try:
-                    acts[UP_TAP_NAMES[k]] = self._ctx.read_activation(self._ws, b, h, w, prec, 18 + k)
-                except _native.NativeError as e:
-                    if e.status != _native.ERR_UNSUPPORTED:   # (unsupported = not stored in this configuration)
-                        raise
-        finally:
-            self._options = saved
-            self._ctx.set_options(saved)
+                up = read(18 + k)
+                if up is not None:
+                    acts[UP_TAP_NAMES[k]] = up
         return acts, out
 
 

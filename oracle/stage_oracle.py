@@ -342,6 +342,204 @@ def check_stage(sd, stage, acts, prec, weights, stem="tap", label="", cache=None
             f"err/bound {ratio.max().item():.3g}{extra}")
 
 
+# ---- the same reference on a window of one image ---------------------------------------------------------------------------
+def _crop(t, b, y0, y1, x0, x1):
+    """float64 host copy of image b, rows [y0, y1), columns [x0, x1) of an NCHW tensor (cut where the tensor lives: a
+    device tap is cropped on the device, and only the crop is copied)."""
+    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))
+    return t[b:b + 1, :, y0:y1, x0:x1].double().cpu()
+
+
+def _zero_extend(ts, region, clipped):
+    """Tensors that cover `clipped` = (y0, y1, x0, x1), zero-padded out to `region` (which contains it)."""
+    (ry0, ry1, rx0, rx1), (cy0, cy1, cx0, cx1) = region, clipped
+    pad = [cx0 - rx0, rx1 - cx1, cy0 - ry0, ry1 - cy1]
+    return tuple(F.pad(t, pad) if any(pad) else t for t in ts)
+
+
+def _clip(region, h, w):
+    y0, y1, x0, x1 = region
+    y0, y1, x0, x1 = max(y0, 0), min(y1, h), max(x0, 0), min(x1, w)
+    return y0, max(y1, y0), x0, max(x1, x0)
+
+
+def _level_shape(inputs, stage):
+    """(h, w) of conv stage `stage`'s level, from the shapes of the taps alone."""
+    if stage in (0, 1) and "frame1" in inputs:
+        return tuple(inputs["frame1"].shape[2:])
+    if stage in POOL_OF:
+        h, w = inputs[TAP[POOL_OF[stage]]].shape[2:]
+        return h // 2, w // 2
+    if stage in SKIP_OF_CONCAT:
+        return tuple(inputs[TAP[SKIP_OF_CONCAT[stage]]].shape[2:])
+    return tuple(inputs[TAP[stage - 1]].shape[2:])
+
+
+def _up_window(low, b, n_rows, n_cols, clipped):
+    """upsample_fp32 of image b of `low`, rows / columns `clipped` of the (2 n_rows) x (2 n_cols) result: the whole-image
+    _up_axis indices and weights, and only the low-res rows and columns they name are cut out of the tap."""
+    y0, y1, x0, x1 = clipped
+    gy0, gy1, hy, ly = (a[y0:y1] for a in _up_axis(n_rows))
+    gx0, gx1, hx, lx = (a[x0:x1] for a in _up_axis(n_cols))
+    ry, rx = int(gy0.min()), int(gx0.min())
+    a = _crop(low, b, ry, int(gy1.max()) + 1, rx, int(gx1.max()) + 1).numpy().astype(np.float32)
+    rows = _fma32(lx, a[..., gx1 - rx], (hx * a[..., gx0 - rx]).astype(np.float32))
+    top, bot = rows[:, :, gy0 - ry], rows[:, :, gy1 - ry]
+    out = _fma32(ly[:, None], bot, (hy[:, None] * top).astype(np.float32))
+    return torch.from_numpy(out.astype(np.float64))
+
+
+def _convt_window(sd, k, inputs, b, region, weights):
+    """(y, M) of the ConvTranspose2d half of up{k} on `region` of its F.pad-ded form (the level of the skip): zero in the
+    F.pad band and outside the image, the 2x2 transposed conv of the low-res rows and columns it needs elsewhere."""
+    low = inputs[TAP[8 + 2 * (k - 1) + 1]]
+    hl, wl = low.shape[2:]
+    hs, ws = inputs[TAP[SKIP_OF_CONCAT[10 + 2 * (k - 1)]]].shape[2:]
+    py, px = (hs - 2 * hl) // 2, (ws - 2 * wl) // 2
+    ry0, ry1, rx0, rx1 = region
+    u = _clip((ry0 - py, ry1 - py, rx0 - px, rx1 - px), 2 * hl, 2 * wl)     # in the coordinates of the unpadded result
+    cout = sd[f"unet.up{k}.up.weight"].shape[1]
+    if u[1] == u[0] or u[3] == u[2]:
+        z = torch.zeros(1, cout, ry1 - ry0, rx1 - rx0, dtype=torch.float64)
+        return z, z.clone()
+    ly0, lx0 = u[0] // 2, u[2] // 2
+    x = _crop(low, b, ly0, (u[1] - 1) // 2 + 1, lx0, (u[3] - 1) // 2 + 1)
+    w, bias = (torch.from_numpy(t) for t in convt_weights(sd, k, weights))
+    sl = (..., slice(u[0] - 2 * ly0, u[1] - 2 * ly0), slice(u[2] - 2 * lx0, u[3] - 2 * lx0))
+    y = F.conv_transpose2d(x, w, bias, stride=2)[sl]
+    m = F.conv_transpose2d(x.abs(), w.abs(), bias.abs(), stride=2)[sl]
+    if weights == "fp16_rne":
+        y = y.clamp(-F16_MAX, F16_MAX)
+    return _zero_extend((y, m), region, (u[0] + py, u[1] + py, u[2] + px, u[3] + px))
+
+
+def stage_input_window(sd, stage, inputs, b, region, weights="exact", stem="tap", cache=None):
+    """stage_input on `region` = (y0, y1, x0, x1) of image b at the stage's level; the region may reach past the image,
+    where it reads zero (the conv's padding).  Only the crops the region needs are cut out of the taps."""
+    bf16 = weights != "exact"
+    uncertain = _f16_uncertain if weights == "fp16_rne" else _bf16_uncertain
+    h, w = _level_shape(inputs, stage)
+    c = _clip(region, h, w)
+    slack = None
+    if stage == 0:
+        x = torch.cat([_crop(inputs["frame1"], b, *c), _crop(inputs["frame2"], b, *c)], 1)
+    elif stage == 1 and stem == "fused":
+        y, m, _ = stage_reference_window(sd, 0, inputs, (b,) + c, "exact")
+        x, slack = uncertain(y, m * 2.0 ** -14)
+    elif stage in POOL_OF:
+        x = F.max_pool2d(_crop(inputs[TAP[POOL_OF[stage]]], b, 2 * c[0], 2 * c[1], 2 * c[2], 2 * c[3]), 2)
+    elif stage in SKIP_OF_CONCAT:
+        skip = _crop(inputs[TAP[SKIP_OF_CONCAT[stage]]], b, *c)
+        k = (stage - 10) // 2 + 1
+        if UP[k - 1] in inputs:
+            up = _crop(inputs[UP[k - 1]], b, *c)
+        elif f"unet.up{k}.up.weight" in sd:
+            up = _convt_window(sd, k, inputs, b, c, weights)[0]
+        else:
+            low = inputs[TAP[stage - 1]]
+            hl, wl = low.shape[2:]
+            py, px = (h - 2 * hl) // 2, (w - 2 * wl) // 2             # F.pad in whole-image coordinates
+            u = _clip((c[0] - py, c[1] - py, c[2] - px, c[3] - px), 2 * hl, 2 * wl)
+            if u[1] > u[0] and u[3] > u[2]:
+                up = _up_window(low, b, hl, wl, u)
+            else:
+                up = torch.zeros(1, low.shape[1], u[1] - u[0], u[3] - u[2], dtype=torch.float64)
+            (up,) = _zero_extend((up,), c, (u[0] + py, u[1] + py, u[2] + px, u[3] + px))
+            if bf16:
+                up, slack_up = uncertain(up, up.abs() * 2.0 ** -22)
+                slack = torch.cat([torch.zeros_like(skip), slack_up], 1)
+        x = torch.cat([skip, up], 1)
+    else:
+        x = _crop(inputs[TAP[stage - 1]], b, *c)
+    if slack is None:
+        slack = torch.zeros_like(x)
+    return _zero_extend((x, slack), region, c)
+
+
+@torch.no_grad()
+def stage_reference_window(sd, stage, inputs, window, weights="exact", stem="tap", with_slack=True, cache=None):
+    """(y_ref, M, E) of stage_reference on the output window (b, y0, y1, x0, x1) of ONE image: rows [y0, y1) and columns
+    [x0, x1) at the stage's level, each [1, Cout, y1 - y0, x1 - x0].  No whole-tensor float64 input is formed: the taps in
+    `inputs` (host or device tensors, whole) are cut to the window plus its 1-pixel conv halo - the 2x region of the
+    producer for a pool-fed stage; the skip crop and the upsampled half of the crop alone for a concat stage (whole-image
+    lerp indices and fp32 weights, F.pad in whole-image coordinates, the bf16 / fp16 rounding with its slack band); one
+    more halo pixel of the frames for the fused stem - and the halo is zero only where it leaves the image.  A
+    ConvTranspose2d half ("unet.up{k}.up") takes its window in the coordinates of the read-back tap, i.e. as F.pad leaves
+    it at the level of the skip.  with_slack=False returns (y_ref, M)."""
+    b, y0, y1, x0, x1 = window
+    if stage == HEAD:
+        x = _crop(inputs[TAP[17]], b, y0, y1, x0, x1)
+        w = sd["unet.outc.conv.weight"].double()
+        bias = sd["unet.outc.conv.bias"].double()
+        y = F.conv2d(x, w, bias)
+        m = F.conv2d(x.abs(), w.abs(), bias.abs())
+        return (y, m, torch.zeros_like(y)) if with_slack else (y, m)
+    if isinstance(stage, str):
+        y, m = _convt_window(sd, UP.index(stage) + 1, inputs, b, (y0, y1, x0, x1), weights)
+        return (y, m, torch.zeros_like(y)) if with_slack else (y, m)
+    x, slack = stage_input_window(sd, stage, inputs, b, (y0 - 1, y1 + 1, x0 - 1, x1 + 1), weights, stem, cache)
+    w, sh = stage_weights(sd, stage, weights, cache)
+    w, sh = torch.from_numpy(w), torch.from_numpy(sh)
+    y = F.relu(F.conv2d(x, w, sh))
+    if weights == "fp16_rne":
+        y = y.clamp(max=F16_MAX)
+    m = F.conv2d(x.abs(), w.abs(), sh.abs())
+    if not with_slack:
+        return y, m
+    e = F.conv2d(slack, w.abs()) if slack.any() else torch.zeros_like(y)
+    return y, m, e
+
+
+def tile_window(ty, tx, th, tw, h, w, ring=2):
+    """(y0, y1, x0, x1) of tile (ty, tx) of a TH x TW grid over h x w with a `ring`-pixel band of its neighbours, cut to
+    the image: every in-tile position and all four seams of the tile lie inside."""
+    return _clip((ty * th - ring, (ty + 1) * th + ring, tx * tw - ring, (tx + 1) * tw + ring), h, w)
+
+
+def check_stage_windows(sd, stage, acts, windows, prec, weights, stem="tap", label="", cache=None, report=None,
+                        tile=None, family=None):
+    """check_stage on windows: the unchanged stage_bound per element of every window (b, y0, y1, x0, x1) of the stage's
+    own read-back output `acts[name]` (whole, on the host or the device; only the windows are copied), against
+    stage_reference_window on the taps in `acts`.  tile: (TH, TW) of the stage's launch, for the failure's position inside
+    its tile.  report / family: as check_stage, under (precision, family or stage_family(stage))."""
+    name = stage if isinstance(stage, str) else TAP[stage]
+    worst = (0.0, None)
+    n_bad = 0
+    for win in windows:
+        b, y0, y1, x0, x1 = win
+        y_dev = _crop(acts[name], b, y0, y1, x0, x1)
+        y, m, e = stage_reference_window(sd, stage, acts, win, weights, stem, True, cache)
+        assert y_dev.shape == y.shape, (name, win, y_dev.shape, y.shape)
+        bound = stage_bound(prec, stage, y, m, e)
+        err = (y_dev - y).abs()
+        ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.inf, 0.0))
+        over_m = err / m.clamp_min(1e-300)
+        if report is not None:
+            r = report.setdefault((prec, family or stage_family(stage)), {"max_err_over_bound": 0.0, "max_err_over_M": 0.0})
+            r["max_err_over_bound"] = max(r["max_err_over_bound"], ratio.max().item())
+            r["max_err_over_M"] = max(r["max_err_over_M"], over_m.max().item())
+        n_bad += int((ratio > 1).sum())
+        if ratio.max().item() > max(worst[0], 1.0):
+            i = int(ratio.argmax())
+            worst = (ratio.max().item(), (win, i, y_dev.reshape(-1)[i].item(), y.reshape(-1)[i].item(),
+                                          over_m.reshape(-1)[i].item(), tuple(y.shape)))
+    if worst[1] is not None:
+        win, i, dv, rv, om, shape = worst[1]
+        _, c, wy, wx = np.unravel_index(i, shape)
+        py, px = win[1] + int(wy), win[3] + int(wx)
+        extra = ""
+        if isinstance(stage, int):
+            p, _, bi = STAGES[stage]
+            g = sd[f"{p}.double_conv.{bi}.weight"][c].item()
+            var = sd[f"{p}.double_conv.{bi}.running_var"][c].item()
+            extra = f" gamma {g:.4g} running_var {var:.4g}"
+        where = f" in-tile (y%{tile[0]}={py % tile[0]}, x%{tile[1]}={px % tile[1]})" if tile else ""
+        raise AssertionError(
+            f"{label} {prec} stage {name}: {n_bad} element(s) over the bound; worst at (b={win[0]}, c={c}, y={py}, x={px}): "
+            f"device {dv:.9g} ref {rv:.9g} err/M {om:.3e} err/bound {worst[0]:.3g}{extra}; window "
+            f"rows {win[1]}:{win[2]} cols {win[3]}:{win[4]}{where}")
+
+
 # ---- whole-network emulation of a precision's storage points -------------------------------------------------------------
 def stem_dither(h, w, amplitude=2.0 ** -8):
     """The bf16 stem's ordered input dither d(y, x) (conv3x3_mfma.hip.h stem_dither): +d on frame 1, -d on frame 2."""
