@@ -49,6 +49,8 @@ SYMBOLS = (
     # YUV 4:2:2 / 4:4:4 frames
     "fiunet_yuv_to_rgb_u8", "fiunet_rgb_to_yuv_u8", "fiunet_yuv_to_rgb_p10", "fiunet_rgb_p10_to_yuv",
     "fiunet_workspace_bytes_yuv", "fiunet_forward_yuv", "fiunet_forward_yuv_p10",
+    # Farneback flow and flow-compensated warps
+    "fiunet_flow_workspace_bytes", "fiunet_farneback_flow", "fiunet_flow_warp",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -205,6 +207,10 @@ def lib() -> ctypes.CDLL:
     L.fiunet_plane_metrics_workspace_bytes.restype = sz
     L.fiunet_plane_psnr.argtypes = [vp, sz, sz, vp, sz, sz, ci, ci, ci, ci, vp, vp, vp, sz, vp]
     L.fiunet_plane_ssim.argtypes = [vp, sz, sz, vp, sz, sz, ci, ci, ci, ci, vp, vp, sz, vp]
+    L.fiunet_flow_workspace_bytes.argtypes = [ci, ci, ci]
+    L.fiunet_flow_workspace_bytes.restype = sz
+    L.fiunet_farneback_flow.argtypes = [vp, vp, ci, ci, ci, ci, sz, sz, vp, vp, sz, vp]
+    L.fiunet_flow_warp.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, sz, sz, ci, ci, vp, sz, sz, vp]
     L.fiunet_ssim_gauss_workspace_bytes.argtypes = [ci, ci, ci]
     L.fiunet_ssim_gauss_workspace_bytes.restype = sz
     L.fiunet_ssim_gauss_f32.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]
@@ -257,6 +263,33 @@ def debug_plan(frame_channels: int, bilinear: bool, flags: int, precision: int, 
     keys = ("index", "offset", "bytes", "first", "last")
     return ([dict(zip(keys, recs[6 * k + 1:6 * k + 6]), kind=PLAN_KINDS[recs[6 * k]]) for k in range(n.value)],
             total.value)
+
+
+FLOW_MODES = ("reference", "motion")   # include/fiunet.h: enum fiunet_flow_mode
+FLOW_STAGES = ("pyramid", "poly_exp", "update_matrices", "box_solve", "flow_resize")   # fiunet_debug_flow_stage 1..5
+
+
+def debug_flow_plan(h: int, w: int):
+    """Diagnostic (tests; not part of the ABI): the pyramid fiunet_farneback_flow builds for an h x w frame -
+    fiunet_debug_flow_plan in csrc/fiunet.hip, pure host arithmetic.  -> [(h, w, ksize, sigma)] for level 0 .. levels."""
+    fn = lib().fiunet_debug_flow_plan
+    fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                   ctypes.POINTER(ctypes.c_double)]
+    n, dims, sigma = ctypes.c_int(), (ctypes.c_int * 12)(), (ctypes.c_double * 4)()
+    check(fn(h, w, ctypes.byref(n), dims, sigma), "fiunet_debug_flow_plan")
+    return [(dims[3 * k], dims[3 * k + 1], dims[3 * k + 2], sigma[k]) for k in range(n.value + 1)]
+
+
+def debug_flow_stage(stage: str, in0, in1, in2, out, scratch, bits: int, level: int, b: int, H: int, W: int, h: int,
+                     w: int, image_stride: int = 0, row_pitch: int = 0, mul=(1.0, 1.0)) -> None:
+    """Diagnostic (tests; not part of the ABI): one stage of the flow (FLOW_STAGES) on the caller's buffers -
+    fiunet_debug_flow_stage in csrc/fiunet.hip says what each stage reads and writes."""
+    fn = lib().fiunet_debug_flow_stage
+    vp, ci, sz, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
+    fn.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, sz, sz, cf, cf, vp]
+    ptr = lambda t: None if t is None else t.data_ptr()
+    check(fn(FLOW_STAGES.index(stage) + 1, ptr(in0), ptr(in1), ptr(in2), ptr(out), ptr(scratch), bits, level, b, H, W,
+             h, w, image_stride, row_pitch, mul[0], mul[1], _stream(out)), "fiunet_debug_flow_stage")
 
 
 class Context:

@@ -98,9 +98,10 @@ def _size(v: str):
 
 def _methods(v: str):
     names = tuple(s.strip() for s in v.split(",") if s.strip())
-    bad = [n for n in names if n not in ("unet", "linear", "repeat")]
+    from .holdout import ALL_METHODS as known
+    bad = [n for n in names if n not in known]
     if not names or bad or len(set(names)) != len(names):
-        raise argparse.ArgumentTypeError(f"expected a comma-separated choice of unet, linear, repeat, got {v!r}")
+        raise argparse.ArgumentTypeError(f"expected a comma-separated choice of {', '.join(known)}, got {v!r}")
     return names
 
 
@@ -142,7 +143,8 @@ def parser() -> argparse.ArgumentParser:
     e.add_argument("--triplets", default="sliding", choices=("sliding", "disjoint"),
                    help="sliding: every frame but the first and last is held out; disjoint: every second frame")
     e.add_argument("--methods", type=_methods, default=("unet", "linear", "repeat"),
-                   help="Comma-separated: unet, linear (blend), repeat (frame duplication)")
+                   help="Comma-separated: unet, linear (blend), repeat (frame duplication), motion (Farneback flow, "
+                        "symmetric warp), optical_flow (the reference evaluators' flow formula)")
     e.add_argument("--precision", default=None, help="fp32 / bf16x2 / bf16 / fp16 (default: the library's)")
     e.add_argument("--weight-prep", default=None, choices=("host", "device"),
                    help="Where the checkpoint is folded, packed and rounded (default: host, or FIUNET_WEIGHT_PREP)")

@@ -10,7 +10,9 @@ reference: `cv2.calcOpticalFlowFarneback` + `cv2.remap`.  When `cv2` is importab
 host, with the reference's parameters; otherwise (every image this code has run on) the method runs
 `optical_flow.py`, a torch RESTATEMENT of Farneback's algorithm and of remap's fixed-point sampling that is
 **parity-unpinned against OpenCV** (no OpenCV here to compare with, no fixtures in the reference) - the result
-dict says which backend produced the numbers (`optical_flow_backend`).  Only the scoring runs in HIP kernels.
+dict says which backend produced the numbers (`optical_flow_backend`).  `flow_backend="hip"` runs the same definition
+in the HIP kernels of csrc/flow.hip.h instead (optical_flow.interpolate), batched over the triplets of
+a call; `flow_backend=None` is the behaviour above.  The scoring always runs in HIP kernels.
 Statistics per method follow evaluation_simple.py:226-242 (numpy mean / population std / min / max).
 """
 from __future__ import annotations
@@ -26,8 +28,16 @@ METHODS = ("unet", "linear")          # the default pair (no flow estimation)
 ALL_METHODS = METHODS + ("optical_flow",)  # the reference's three (evaluation_simple.py:134-244)
 
 
-def optical_flow_backend() -> str:
-    """Which implementation the "optical_flow" method uses in this process."""
+FLOW_BACKENDS = (None, "hip", "torch")
+
+
+def optical_flow_backend(flow_backend=None) -> str:
+    """Which implementation the "optical_flow" method uses in this process (flow_backend: evaluate_triplets')."""
+    if flow_backend == "hip":
+        return ("hip (csrc/flow.hip.h, the definition of ai_based_frame_interpolation_amd.optical_flow; parity unpinned "
+                "against OpenCV)")
+    if flow_backend == "torch":
+        return "restated (ai_based_frame_interpolation_amd.optical_flow; parity unpinned against OpenCV)"
     try:
         import cv2  # type: ignore  # noqa: F401
         return "opencv"
@@ -35,7 +45,7 @@ def optical_flow_backend() -> str:
         return "restated (ai_based_frame_interpolation_amd.optical_flow; parity unpinned against OpenCV)"
 
 
-def _optical_flow_u8(f0: torch.Tensor, f1: torch.Tensor) -> torch.Tensor:
+def _optical_flow_u8(f0: torch.Tensor, f1: torch.Tensor, flow_backend=None) -> torch.Tensor:
     """optical_flow_interpolation_baseline (evaluation_simple.py:76-103), frame by frame: Farneback flow
     f0 -> f1 (pyr_scale 0.5, 3 levels, winsize 15, 3 iterations, poly_n 5, poly_sigma 1.1), frame 0 sampled at
     (x, y) + flow/2 clipped to the image, bilinear, replicated border (as written in the reference: this moves
@@ -44,6 +54,8 @@ def _optical_flow_u8(f0: torch.Tensor, f1: torch.Tensor) -> torch.Tensor:
     restatement of optical_flow.py on the frames' own device."""
     if f0.shape[1] != 1:
         raise RuntimeError("the optical-flow baseline is defined on grayscale frames (one channel)")
+    if flow_backend is not None:
+        return optical_flow.interpolate(f0[:, 0], f1[:, 0], "reference", flow_backend).unsqueeze(1)
     try:
         import cv2  # type: ignore
     except ImportError:
@@ -78,14 +90,18 @@ def _frame_psnr(pred: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate_triplets(model, frame_t0: torch.Tensor, frame_t1: torch.Tensor, ground_truth: torch.Tensor,
-                      methods: Iterable[str] = METHODS, batch: int = 8) -> Dict:
-    """frame_t0, frame_t1, ground_truth: uint8 [N, C, H, W] on the model's device.  Returns the
+                      methods: Iterable[str] = METHODS, batch: int = 8, flow_backend=None) -> Dict:
+    """frame_t0, frame_t1, ground_truth: uint8 [N, C, H, W] on the model's device.  flow_backend: what runs the
+    "optical_flow" method - None: OpenCV when importable, else the restatement; "hip": the kernels; "torch": the
+    restatement.  Returns the
     reference's result layout: {'total_triplets', 'methods', 'metrics_by_method': {m: {average_psnr,
     average_ssim, std_*, min_*, max_*}}, 'per_triplet': {m: {'psnr': ndarray, 'ssim': ndarray}}}."""
     methods = tuple(methods)
     for m in methods:
         if m not in ALL_METHODS:
             raise ValueError(f"unknown method {m!r}; choose from {ALL_METHODS}")
+    if flow_backend not in FLOW_BACKENDS:
+        raise ValueError(f"flow_backend must be one of {list(FLOW_BACKENDS)}, got {flow_backend!r}")
     if "optical_flow" in methods and frame_t0.shape[1] != 1:
         raise RuntimeError("the optical-flow baseline is defined on grayscale frames (one channel)")
     if not (frame_t0.shape == frame_t1.shape == ground_truth.shape) or frame_t0.dim() != 4:
@@ -97,14 +113,14 @@ def evaluate_triplets(model, frame_t0: torch.Tensor, frame_t1: torch.Tensor, gro
         f0, f1, gt = frame_t0[s:e], frame_t1[s:e], ground_truth[s:e]
         for m in methods:
             pred = (model.forward_u8(f0, f1) if m == "unet" else
-                    _linear_u8(f0, f1) if m == "linear" else _optical_flow_u8(f0, f1))
+                    _linear_u8(f0, f1) if m == "linear" else _optical_flow_u8(f0, f1, flow_backend))
             # one value per frame: channels (RGB variant) are averaged, as skimage's channel_axis does
             per[m]["psnr"].append(_frame_psnr(pred, gt))
             per[m]["ssim"].append(metrics.ssim_u8(pred, gt).mean(dim=1))
     out = {"total_triplets": n, "successful_evaluations": n, "methods": list(methods),
            "metrics_by_method": {}, "per_triplet": {}}
     if "optical_flow" in methods:
-        out["optical_flow_backend"] = optical_flow_backend()
+        out["optical_flow_backend"] = optical_flow_backend(flow_backend)
     for m in methods:
         ps = torch.cat(per[m]["psnr"]).cpu().numpy() if n else np.zeros(0)
         ss = torch.cat(per[m]["ssim"]).cpu().numpy() if n else np.zeros(0)

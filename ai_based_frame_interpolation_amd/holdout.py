@@ -8,7 +8,14 @@ chunk.
   methods    each turns a decimated chunk d [k, row] into [2k-1, out_row] rows whose odd rows are the predictions:
              "unet" is `route.run(d, 2)`, the forward of whatever route the clip takes (stream.py: `_y4m_route`,
              `_npy_route`, with their refusals); "linear" the project's integer average (a + b + 1) >> 1 of every
-             sample of the row; "repeat" the earlier neighbour, which is what a frame duplicator shows.
+             sample of the row; "repeat" the earlier neighbour, which is what a frame duplicator shows.  Beyond the
+             default three (ALL_METHODS), the classical motion-compensated baseline: Farneback flow
+             between the two neighbours on the device (optical_flow.farneback_flow, the HIP kernels; its source is the Y
+             plane of Y4M, the plane of a gray .npy, the rounded channel mean of an [N,H,W,C] .npy), in sub-batches of
+             `batch` pairs, and every plane of the row warped along it (sub-sampled chroma along the resampled, rescaled
+             flow): "optical_flow" is the reference evaluators' formula, frame 0 at p + flow / 2, which moves AGAINST
+             the motion and is kept for comparison with them; "motion" the symmetric warp (frame 0 at p - flow / 2 +
+             frame 1 at p + flow / 2 + 1) >> 1, the baseline a user wants to beat.
   planes     Y4M: "y", then "u" and "v" when the stream has chroma (on the grayscale route the chroma of an inserted
              frame is the neighbour average the route writes: that is what ends up in the file, so it is scored);
              .npy [N,H,W]: "gray"; .npy [N,H,W,C]: "c0".. (made planar by one permute per chunk).  The plane views
@@ -21,7 +28,7 @@ chunk.
              (`_padded_chunk`), so the result is the same to the last bit for every chunk_frames.
 
 Out of scope: raw NV12 and packed-RGB input, leaving out triplets that straddle a scene cut (the per-frame arrays let a
-caller filter), the optical-flow baseline (`evaluation.evaluate_triplets` has it for frames in memory), several GPUs.
+caller filter), several GPUs.
 """
 from __future__ import annotations
 
@@ -31,13 +38,16 @@ import os
 import numpy as np
 import torch
 
-from . import imageio_lite, metrics
+from . import imageio_lite, metrics, optical_flow
 from . import retime as _retime
 from .inference import _interleave_average_p10, _interleave_average_u8
 from .stream import _NpyRows, _is_path, _npy_route, _y4m_route, check_chunk_frames
 
 TRIPLETS = ("sliding", "disjoint")
 METHODS = ("unet", "linear", "repeat")
+FLOW_METHODS = {"optical_flow": "reference", "motion": "motion"}   # method -> optical_flow.MODES
+ALL_METHODS = METHODS + tuple(FLOW_METHODS)
+FLOW_BACKEND = "hip (csrc/flow.hip.h, the definition of optical_flow.py; parity unpinned against OpenCV)"
 STATS = ("average_psnr", "std_psnr", "min_psnr", "max_psnr", "average_ssim", "std_ssim", "min_ssim", "max_ssim",
          "psnr_of_mean_mse", "identical_frames")
 
@@ -154,6 +164,34 @@ def _predict(method: str, route, d: torch.Tensor) -> torch.Tensor:
     return _interleave_average_u8(d)[1::2]
 
 
+def _predict_flow(methods, source: _Source, d: torch.Tensor, batch: int) -> dict:
+    """The k-1 predicted rows of a decimated chunk d [k, row] for each of the flow methods asked for: one flow per
+    pair, shared by the methods, `batch` pairs at a time (a pair's flow and warp do not depend on the pairs beside it)."""
+    bits, k = source.route.bits, d.shape[0]
+    if source.channels:   # [N,H,W,C]: planar copies, flow on the rounded channel mean
+        c = source.channels
+        _, _, h, w = source.planes[0]
+        planar = d.reshape(k, h, w, c).permute(0, 3, 1, 2).contiguous()
+        planes = [planar[:, i] for i in range(c)]
+        lead = ((planar.sum(1, dtype=torch.int32) * 2 + c) // (2 * c)).to(torch.uint8)
+        outs = {m: torch.empty((k - 1, c, h, w), dtype=d.dtype, device=d.device) for m in methods}
+        dst = {m: [outs[m][:, i] for i in range(c)] for m in methods}
+    else:
+        planes = _plane_views(d, source)
+        lead = planes[0]
+        outs = {m: torch.empty_like(d[:-1]) for m in methods}
+        dst = {m: _plane_views(outs[m], source) for m in methods}
+    for s in range(0, k - 1, batch):
+        e = min(s + batch, k - 1)
+        flow = optical_flow.farneback_flow(lead[s:e], lead[s + 1:e + 1], "hip", bits=bits)
+        for m in methods:
+            for p, o in zip(planes, dst[m]):
+                optical_flow.warp(p[s:e], p[s + 1:e + 1], flow, FLOW_METHODS[m], "hip", bits=bits, out=o[s:e])
+    if source.channels:
+        return {m: outs[m].permute(0, 2, 3, 1).reshape(k - 1, -1) for m in methods}
+    return outs
+
+
 def _plane_views(rows: torch.Tensor, source: _Source):
     """rows [m, row] (any row stride) -> the planes' [m, h, w] views, in the order of source.planes."""
     if source.channels:
@@ -163,8 +201,9 @@ def _plane_views(rows: torch.Tensor, source: _Source):
     return [rows[:, off:off + h * w].unflatten(1, (h, w)) for _, off, h, w in source.planes]
 
 
-def _score_chunk(source: _Source, methods, d_all: torch.Tensor, n_targets: int, step: int):
+def _score_chunk(source: _Source, methods, d_all: torch.Tensor, n_targets: int, step: int, batch: int = 8):
     """-> {method: {plane: (psnr, ssim, sse)}}, host arrays over the chunk's targets in order."""
+    flow_methods = [m for m in methods if m in FLOW_METHODS]
     bits = source.route.bits
     res = {m: {p[0]: (np.empty(n_targets), np.full(n_targets, np.nan), np.empty(n_targets, np.uint64))
                for p in source.planes} for m in methods}
@@ -175,8 +214,9 @@ def _score_chunk(source: _Source, methods, d_all: torch.Tensor, n_targets: int, 
             continue
         truth = _plane_views(d_all[off + 1::2][:k - 1], source)
         where = slice(off, None, 2) if step == 1 else slice(None)
+        flowed = _predict_flow(flow_methods, source, d, batch) if flow_methods else {}
         for m in methods:
-            pred = _plane_views(_predict(m, source.route, d), source)
+            pred = _plane_views(flowed[m] if m in flowed else _predict(m, source.route, d), source)
             for (name, _, h, w), p, t in zip(source.planes, pred, truth):
                 ps, sse = metrics.psnr_planes(p, t, bits, return_sse=True)
                 out = res[m][name]
@@ -205,7 +245,8 @@ def _stats(psnr, ssim, sse, pixels: int, peak: int) -> dict:
 @torch.no_grad()
 def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch: int = 8, chunk_frames: int = 32,
                 matrix: str = "bt709", siting=None, src_fps=None) -> dict:
-    """Hold-out scores of `model` on a clip.  src: a path (.y4m, or a uint8 .npy stack [N,H,W] / [N,H,W,C]) or a
+    """Hold-out scores of `model` on a clip (methods: any of ALL_METHODS; with "optical_flow" or "motion" the result
+    also has "flow_backend").  src: a path (.y4m, or a uint8 .npy stack [N,H,W] / [N,H,W,C]) or a
     readable binary file object carrying Y4M (a pipe): what `interpolate_y4m_stream` / `interpolate_npy_stream` take
     for this model, with those routes' refusals.  batch / matrix / siting: the routes' arguments; chunk_frames: held-out
     frames per chunk (memory: chunk_frames + 2 source frames, "disjoint" 2 x chunk_frames + 1, on the host and on the
@@ -219,10 +260,10 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     triplets = _check_triplets(triplets)
     methods = tuple([methods] if isinstance(methods, str) else methods)
     for m in methods:
-        if m not in METHODS:
-            raise ValueError(f"unknown method {m!r}; choose from {list(METHODS)}")
+        if m not in ALL_METHODS:
+            raise ValueError(f"unknown method {m!r}; choose from {list(ALL_METHODS)}")
     if not methods or len(set(methods)) != len(methods):
-        raise ValueError(f"methods: one or more of {list(METHODS)}, each once")
+        raise ValueError(f"methods: one or more of {list(ALL_METHODS)}, each once")
     c = check_chunk_frames(chunk_frames)
     if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
         raise ValueError(f"batch must be a positive int, got {batch!r}")
@@ -245,7 +286,7 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
                 break
             _, count, targets = span
             d_all = torch.from_numpy(buf[:count].view(np.int16) if route.bits == 10 else buf[:count]).to(dev)
-            parts.append(_score_chunk(source, methods, d_all, len(targets), step))
+            parts.append(_score_chunk(source, methods, d_all, len(targets), step, int(batch)))
             scored += targets
             if have + got < want:   # the stream ended inside this chunk
                 break
@@ -261,12 +302,15 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     per = {m: {p: {key: np.concatenate([part[m][p][j] for part in parts])
                    for j, key in enumerate(("psnr", "ssim", "sse"))} for p in names} for m in methods}
     pixels = {p[0]: p[2] * p[3] for p in source.planes}
-    return {"frames": frames, "triplets": triplets, "bits": route.bits, "peak": peak, "planes": names,
-            "methods": list(methods), "fps": None if source.fps is None else (source.fps.numerator,
-                                                                              source.fps.denominator),
-            "scored_frames": np.asarray(scored, dtype=np.int64), "per_frame": per,
-            "summary": {m: {p: _stats(per[m][p]["psnr"], per[m][p]["ssim"], per[m][p]["sse"], pixels[p], peak)
-                            for p in names} for m in methods}}
+    out = {"frames": frames, "triplets": triplets, "bits": route.bits, "peak": peak, "planes": names,
+           "methods": list(methods), "fps": None if source.fps is None else (source.fps.numerator,
+                                                                             source.fps.denominator),
+           "scored_frames": np.asarray(scored, dtype=np.int64), "per_frame": per,
+           "summary": {m: {p: _stats(per[m][p]["psnr"], per[m][p]["ssim"], per[m][p]["sse"], pixels[p], peak)
+                           for p in names} for m in methods}}
+    if any(m in FLOW_METHODS for m in methods):
+        out["flow_backend"] = FLOW_BACKEND
+    return out
 
 
 # ---- the result as text ---------------------------------------------------------------------------------------------
@@ -306,14 +350,15 @@ def csv_lines(result: dict):
 
 
 def summary_table(result: dict) -> str:
+    mw = max([8] + [len(m) + 1 for m in result["methods"]])   # the method column fits "optical_flow"
     lines = [f"{result['frames']} frames, {len(result['scored_frames'])} held out ({result['triplets']}), "
              f"{result['bits']}-bit, peak {result['peak']}",
-             f"{'method':<8}{'plane':<6}{'PSNR mean':>11}{'std':>8}{'min':>9}{'max':>9}{'of mean MSE':>13}"
+             f"{'method':<{mw}}{'plane':<6}{'PSNR mean':>11}{'std':>8}{'min':>9}{'max':>9}{'of mean MSE':>13}"
              f"{'SSIM mean':>11}{'min':>9}{'identical':>11}"]
     for m in result["methods"]:
         for p in result["planes"]:
             s = result["summary"][m][p]
-            lines.append(f"{m:<8}{p:<6}{s['average_psnr']:>11.3f}{s['std_psnr']:>8.3f}{s['min_psnr']:>9.3f}"
+            lines.append(f"{m:<{mw}}{p:<6}{s['average_psnr']:>11.3f}{s['std_psnr']:>8.3f}{s['min_psnr']:>9.3f}"
                          f"{s['max_psnr']:>9.3f}{s['psnr_of_mean_mse']:>13.3f}{s['average_ssim']:>11.5f}"
                          f"{s['min_ssim']:>9.5f}{s['identical_frames']:>11d}")
     return "\n".join(lines)

@@ -16,11 +16,17 @@ motion, so on translating content this baseline scores BELOW the linear blend (e
 tests/test_host.py::test_optical_flow_baseline_is_the_references_formula).  When `cv2` IS importable the evaluator calls
 OpenCV itself (evaluation.py) and this module is not used.
 
-Everything is plain torch on whatever device the frames are on (host plumbing, not a hot path: the reference
-runs it frame by frame on the CPU).
+The functions of the restatement are plain torch on whatever device the frames are on, one pair at a time (the
+reference runs it frame by frame on the CPU).  They are the DEFINITION.  The batched entry points at the end of the
+file - `farneback_flow`, `warp`, `interpolate` - run the same definition in HIP kernels (csrc/flow.hip.h, DESIGN.md
+3.3n: backend "hip") or loop the restatement (backend "torch"); hold-out scoring (holdout.py) and
+`evaluation.evaluate_triplets(flow_backend="hip")` use them.  Beside the reference's formula (mode "reference") they
+have the symmetric warp a motion-compensated baseline needs (mode "motion": frame 0 at p - flow / 2 averaged with
+frame 1 at p + flow / 2).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Tuple
 
@@ -242,11 +248,9 @@ def calc_optical_flow_farneback(prev_u8: torch.Tensor, next_u8: torch.Tensor, py
 _INTER_BITS, _REMAP_COEF_BITS = 5, 15
 
 
-@torch.no_grad()
-def remap_bilinear_u8(src_u8: torch.Tensor, map_x: torch.Tensor, map_y: torch.Tensor) -> torch.Tensor:
-    """cv2.remap(src, map_x, map_y, INTER_LINEAR, borderMode=BORDER_REPLICATE) on an [H, W] uint8 image:
-    coordinates rounded to 1/32 pixel, integer weights of 15 bits, result (sum + 2^14) >> 15."""
-    h, w = src_u8.shape
+def _remap_bilinear(src: torch.Tensor, map_x: torch.Tensor, map_y: torch.Tensor) -> torch.Tensor:
+    """remap's fixed-point bilinear sampling of an [H, W] integer image -> int64 [H, W] (samples of any depth)."""
+    h, w = src.shape
     tab = 1 << _INTER_BITS
     sx = torch.round(map_x.to(torch.float64) * tab).long()
     sy = torch.round(map_y.to(torch.float64) * tab).long()
@@ -262,9 +266,16 @@ def remap_bilinear_u8(src_u8: torch.Tensor, map_x: torch.Tensor, map_y: torch.Te
     iw.scatter_add_(-1, big, diff[..., None])
     xa, xb = x0.clamp(0, w - 1), (x0 + 1).clamp(0, w - 1)
     ya, yb = y0.clamp(0, h - 1), (y0 + 1).clamp(0, h - 1)
-    s = src_u8.long()
+    s = src.long()
     acc = s[ya, xa] * iw[..., 0] + s[ya, xb] * iw[..., 1] + s[yb, xa] * iw[..., 2] + s[yb, xb] * iw[..., 3]
-    return ((acc + (1 << (_REMAP_COEF_BITS - 1))) >> _REMAP_COEF_BITS).clamp(0, 255).to(torch.uint8)
+    return (acc + (1 << (_REMAP_COEF_BITS - 1))) >> _REMAP_COEF_BITS
+
+
+@torch.no_grad()
+def remap_bilinear_u8(src_u8: torch.Tensor, map_x: torch.Tensor, map_y: torch.Tensor) -> torch.Tensor:
+    """cv2.remap(src, map_x, map_y, INTER_LINEAR, borderMode=BORDER_REPLICATE) on an [H, W] uint8 image:
+    coordinates rounded to 1/32 pixel, integer weights of 15 bits, result (sum + 2^14) >> 15."""
+    return _remap_bilinear(src_u8, map_x, map_y).clamp(0, 255).to(torch.uint8)
 
 
 @torch.no_grad()
@@ -279,3 +290,167 @@ def optical_flow_interpolation_baseline(frame0_u8: torch.Tensor, frame1_u8: torc
     new_x = (xs + flow[..., 0] * 0.5).clamp(0, w - 1)
     new_y = (ys + flow[..., 1] * 0.5).clamp(0, h - 1)
     return remap_bilinear_u8(frame0_u8, new_x, new_y)
+
+
+# ---- batched entry points: the HIP kernels (csrc/flow.hip.h), or the restatement in a loop -----------------------------
+BACKENDS = ("hip", "torch")
+MODES = ("reference", "motion")
+# (device, H, W) -> the flow workspace, one torch buffer per frame size, sized for the largest batch seen (a smaller
+# batch uses its front; a larger one replaces it).  Calls of one size are assumed to be on ONE stream at a time: the
+# buffer is scratch of the call in flight and nothing orders two streams that share it.
+_workspaces = {}
+
+
+def _check_backend(backend) -> str:
+    if backend not in BACKENDS:
+        raise ValueError(f"backend must be one of {list(BACKENDS)}, got {backend!r}")
+    return backend
+
+
+def _check_mode(mode) -> str:
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {list(MODES)}, got {mode!r}")
+    return mode
+
+
+def _check_pair(a: torch.Tensor, b: torch.Tensor, bits: int) -> None:
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+    if a.shape != b.shape or a.dim() != 3:
+        raise ValueError(f"expected two [B, H, W] frame stacks of equal shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    ok = (torch.uint8,) if bits == 8 else (torch.uint16, torch.int16)
+    if a.dtype not in ok or b.dtype not in ok or a.dtype != b.dtype:
+        raise ValueError(f"{bits}-bit frames are {' or '.join(str(d) for d in ok)} tensors of one dtype, got {a.dtype} "
+                         f"and {b.dtype}")
+
+
+def _codes(t: torch.Tensor, bits: int) -> torch.Tensor:
+    """The samples as int64 codes (10-bit: the 16-bit words unsigned, a word above 1023 read as 1023)."""
+    if bits == 8:
+        return t.long()
+    return (t.view(torch.int16).to(torch.int64) & 0xFFFF).clamp(max=1023)
+
+
+def _same_layout(a: torch.Tensor, b: torch.Tensor):
+    """Both stacks as the kernels take them: one (image stride, row pitch) in samples for the two; views are passed
+    where they lie (metrics._plane_layout), anything else is copied."""
+    from . import metrics
+    try:
+        la, lb = metrics._plane_layout(a, "frame0"), metrics._plane_layout(b, "frame1")
+    except ValueError:
+        la, lb = 0, 1
+    if la != lb:
+        a, b = a.contiguous(), b.contiguous()
+        la = metrics._plane_layout(a, "frame0")
+    return a, b, la
+
+
+def _need_gpu(*ts) -> None:
+    if not all(t.is_cuda and t.device == ts[0].device for t in ts):
+        raise RuntimeError("the hip backend needs CUDA/HIP tensors on one device; there is no CPU fallback for it "
+                           "(backend='torch' runs the restatement anywhere)")
+
+
+@torch.no_grad()
+def farneback_flow(prev: torch.Tensor, next: torch.Tensor, backend: str = "hip", *, bits: int = 8) -> torch.Tensor:
+    """Dense flow prev -> next of B frame pairs: [B, H, W] uint8 stacks (bits 10: uint16 / int16 words of 10-bit
+    codes, which enter as code / 4) -> float32 [B, H, W, 2] = (dx, dy), the reference's parameters.  backend "hip":
+    fiunet_farneback_flow on the frames where they lie; "torch": `calc_optical_flow_farneback` pair by pair."""
+    _check_backend(backend)
+    _check_pair(prev, next, bits)
+    b, h, w = prev.shape
+    if backend == "torch":
+        conv = (lambda t: t) if bits == 8 else (lambda t: _codes(t, 10).to(torch.float32) / 4.0)
+        if b == 0:
+            return torch.empty((0, h, w, 2), dtype=torch.float32, device=prev.device)
+        return torch.stack([calc_optical_flow_farneback(conv(prev[i]), conv(next[i])) for i in range(b)])
+    from . import _native
+    _need_gpu(prev, next)
+    out = torch.empty((b, h, w, 2), dtype=torch.float32, device=prev.device)
+    if b == 0:
+        return out
+    prev, next, (stride, pitch) = _same_layout(prev, next)
+    L = _native.lib()
+    nbytes = L.fiunet_flow_workspace_bytes(b, h, w)
+    if nbytes == 0:
+        _native.check(1, "fiunet_flow_workspace_bytes")
+    key = (prev.device, h, w)
+    ws = _workspaces.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=prev.device)
+    with torch.cuda.device(prev.device):
+        _native.check(L.fiunet_farneback_flow(prev.data_ptr(), next.data_ptr(), bits, b, h, w, stride, pitch,
+                                              out.data_ptr(), ws.data_ptr(), ctypes.c_size_t(nbytes),
+                                              _native._stream(prev)), "fiunet_farneback_flow")
+    return out
+
+
+def resample_flow(flow: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """An [h, w, 2] flow field for a plane of another size (the luma flow, a sub-sampled chroma plane): cv2.resize's
+    linear rule, dx scaled by width / w and dy by height / h.  The same size: the field itself."""
+    h, w = flow.shape[:2]
+    if (h, w) == (height, width):
+        return flow
+    mul = torch.tensor([width / w, height / h], dtype=flow.dtype, device=flow.device)
+    return _resize_linear(flow, width, height) * mul
+
+
+def _warp_torch(f0: torch.Tensor, f1: torch.Tensor, flow: torch.Tensor, mode: str, bits: int) -> torch.Tensor:
+    """One [H, W] pair along an [h, w, 2] flow field, the definition of both modes -> int64 [H, W]."""
+    h, w = f0.shape
+    flow = resample_flow(flow.to(torch.float32), h, w)
+    ys, xs = torch.meshgrid(torch.arange(h, device=flow.device, dtype=torch.float32),
+                            torch.arange(w, device=flow.device, dtype=torch.float32), indexing="ij")
+    hx, hy = flow[..., 0] * 0.5, flow[..., 1] * 0.5
+    fwd = _remap_bilinear(_codes(f0, bits) if mode == "reference" else _codes(f1, bits),
+                          (xs + hx).clamp(0, w - 1), (ys + hy).clamp(0, h - 1))
+    if mode == "reference":
+        return fwd
+    back = _remap_bilinear(_codes(f0, bits), (xs - hx).clamp(0, w - 1), (ys - hy).clamp(0, h - 1))
+    return (back + fwd + 1) >> 1
+
+
+@torch.no_grad()
+def warp(frame0: torch.Tensor, frame1: torch.Tensor, flow: torch.Tensor, mode: str = "reference",
+         backend: str = "hip", *, bits: int = 8, out: torch.Tensor = None) -> torch.Tensor:
+    """The frame halfway between B pairs of [B, H, W] planes along `flow` [B, h, w, 2] (another size than the plane:
+    `resample_flow`).  mode "reference": frame 0 at p + flow / 2 (the reference's formula, which samples against the
+    motion); "motion": (frame 0 at p - flow / 2 + frame 1 at p + flow / 2 + 1) >> 1.  remap's arithmetic: clamped
+    coordinates rounded to 1/32 pixel, 15-bit weights.  `out`: a [B, H, W] tensor or view of the frames' dtype to
+    write into (last stride 1, not overlapping the frames)."""
+    _check_mode(mode)
+    _check_backend(backend)
+    _check_pair(frame0, frame1, bits)
+    b, h, w = frame0.shape
+    if flow.dim() != 4 or flow.shape[0] != b or flow.shape[3] != 2 or flow.dtype != torch.float32:
+        raise ValueError(f"flow: expected float32 [{b}, h, w, 2], got {flow.dtype} {tuple(flow.shape)}")
+    if out is None:
+        out = torch.empty((b, h, w), dtype=frame0.dtype, device=frame0.device)
+    elif out.shape != frame0.shape or out.dtype != frame0.dtype:
+        raise ValueError(f"out: expected {frame0.dtype} {tuple(frame0.shape)}, got {out.dtype} {tuple(out.shape)}")
+    if b == 0:
+        return out
+    if backend == "torch":
+        for i in range(b):
+            v = _warp_torch(frame0[i], frame1[i], flow[i], mode, bits)
+            out[i] = v.to(torch.uint8) if bits == 8 else v.to(torch.int16).view(out.dtype)
+        return out
+    from . import _native, metrics
+    _need_gpu(frame0, frame1, flow, out)
+    frame0, frame1, (stride, pitch) = _same_layout(frame0, frame1)
+    ostride, opitch = metrics._plane_layout(out, "out")
+    flow = flow.contiguous()
+    with torch.cuda.device(frame0.device):
+        _native.check(_native.lib().fiunet_flow_warp(
+            frame0.data_ptr(), frame1.data_ptr(), flow.data_ptr(), MODES.index(mode), bits, b, h, w, stride, pitch,
+            flow.shape[1], flow.shape[2], out.data_ptr(), ostride, opitch, _native._stream(frame0)), "fiunet_flow_warp")
+    return out
+
+
+@torch.no_grad()
+def interpolate(frame0: torch.Tensor, frame1: torch.Tensor, mode: str = "reference", backend: str = "hip", *,
+                bits: int = 8) -> torch.Tensor:
+    """The flow-compensated middle frame of B pairs of [B, H, W] frames: `farneback_flow`, then `warp`.  mode
+    "reference" with backend "torch" is `optical_flow_interpolation_baseline` pair by pair."""
+    _check_mode(mode)
+    return warp(frame0, frame1, farneback_flow(frame0, frame1, backend, bits=bits), mode, backend, bits=bits)

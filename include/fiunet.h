@@ -33,7 +33,9 @@ extern "C" {
                                      the same way: packed RGB frames (fiunet_packed_format, fiunet_packed_layout,
                                      fiunet_packed_to_rgb_u8, fiunet_rgb_to_packed_u8, fiunet_forward_rgb_packed and its
                                      workspace query); v8 also, added the same way: PSNR / SSIM on strided 8- and 10-bit
-                                     planes (fiunet_plane_psnr, fiunet_plane_ssim and their workspace query) */
+                                     planes (fiunet_plane_psnr, fiunet_plane_ssim and their workspace query); v8 also, added
+                                     the same way: Farneback flow and flow-compensated warps (fiunet_flow_workspace_bytes,
+                                     fiunet_farneback_flow, fiunet_flow_warp, fiunet_flow_mode) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -501,6 +503,33 @@ int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_ro
                       const void* target, size_t target_image_stride, size_t target_row_pitch,
                       int bits, int images, int H, int W, double* out_ssim,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* The classical motion-compensated baseline of the evaluators on device: dense Farneback flow with the
+ * reference's parameters (model/evaluation_simple.py:76-103: pyr_scale 0.5, 3 levels, winsize 15, 3 iterations, poly_n 5,
+ * poly_sigma 1.1, flags 0; the definition is the package's optical_flow.py, parity-unpinned against OpenCV) and remap's
+ * fixed-point bilinear warp along it.
+ * fiunet_farneback_flow: prev, next: B frames of H x W samples each, frame i at base + i * image_stride, rows row_pitch
+ * apart, both in SAMPLES and the same for both (bits 8: uint8_t; bits 10: uint16_t words of 10-bit codes, which enter
+ * the flow as code / 4).  flow_out: device float [B, H, W, 2] = (dx, dy) of prev -> next, 8-byte aligned.  workspace:
+ * fiunet_flow_workspace_bytes(B, H, W) (0 for bad arguments), 256-B aligned.  A pair's flow does not depend on B or on
+ * its place in the batch.
+ * fiunet_flow_warp: one plane of B frame pairs along `flow` [B, flow_h, flow_w, 2]; where flow_h x flow_w is not H x W
+ * (the luma flow, a sub-sampled chroma plane) the flow is resampled to the plane first (cv2.resize's linear rule) and
+ * scaled by W / flow_w and H / flow_h.  FIUNET_FLOW_REFERENCE: frame0 at p + flow(p) / 2, the reference's formula (it
+ * samples AGAINST the motion); frame1 is not read but must not be NULL.  FIUNET_FLOW_MOTION: (frame0 at p - flow(p) / 2
+ * + frame1 at p + flow(p) / 2 + 1) >> 1.  Coordinates are clamped to the plane in fp32, rounded half-to-even to 1/32
+ * pixel and sampled with 15-bit integer weights, (acc + 2^14) >> 15.  out: samples of the same depth with its own
+ * strides; it must not overlap the frames.
+ * Both: asynchronous on `stream`; no allocation, no synchronisation.  Before any launch: NULL pointers, bits not 8 or
+ * 10, a bad mode, B / H / W < 1, B > 4096, a side above 32768, a row pitch < W, B > 1 with an image stride smaller than
+ * one frame and misaligned pointers are FIUNET_ERR_INVALID_ARG; a workspace that is too small is FIUNET_ERR_WORKSPACE. */
+enum fiunet_flow_mode { FIUNET_FLOW_REFERENCE = 0, FIUNET_FLOW_MOTION = 1 };
+size_t fiunet_flow_workspace_bytes(int B, int H, int W);
+int fiunet_farneback_flow(const void* prev, const void* next, int bits, int B, int H, int W, size_t image_stride,
+                          size_t row_pitch, float* flow_out, void* workspace, size_t workspace_bytes, void* stream);
+int fiunet_flow_warp(const void* frame0, const void* frame1, const float* flow, int mode, int bits, int B, int H, int W,
+                     size_t image_stride, size_t row_pitch, int flow_h, int flow_w, void* out, size_t out_image_stride,
+                     size_t out_row_pitch, void* stream);
 
 /* The training loss' SSIM on device: SSIMLoss._ssim (model/train.py:37-56) - the
  * window_size x window_size Gaussian window (sigma 1.5, normalised as at train.py:27-35) applied as a

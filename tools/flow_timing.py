@@ -1,0 +1,161 @@
+"""Time the motion-compensated baseline: the HIP flow and warp kernels beside the torch restatement they
+restate, on the same device in the same process, and the baseline's share of a hold-out run.
+
+  pairs     Farneback flow plus the "motion" warp of B frame pairs (B = 8 at 1080p, B = 8 at 256x256; a moving texture,
+            uint8), per pair:
+              hip      optical_flow.farneback_flow + optical_flow.warp, backend "hip" (fiunet_farneback_flow,
+                       fiunet_flow_warp; the workspace is the cached one, the outputs are allocated per call as a caller's
+                       would be); device time from HIP events around `--iters` back-to-back calls after `--warmup` calls
+              torch    the same two calls with backend "torch": `calc_optical_flow_farneback` and the fixed-point remap pair
+                       by pair, on the same device tensors - the YARDSTICK.  A few hundred small tensor operations per
+                       pair, some of them with host synchronisation, so it is timed by the wall clock behind a device
+                       synchronise, `--torch-iters` calls.
+            `--reps` repetitions interleaved over the cases; median and spread.  The flow alone is timed the same way.
+  score     one `holdout.score_video` run of a `--clip-frames`-frame 1080p C420jpeg clip (tools/holdout_timing.py's
+            moving texture), sliding triplets, all five methods, RGB network at bf16: wall time behind a device
+            synchronise, and the share of it inside the flow methods (`holdout._predict_flow`, timed behind synchronises of
+            its own in a second run).
+One JSON line last.
+
+    python tools/flow_timing.py [--batch 8 --iters 20 --torch-iters 1 --reps 5 --clip-frames 65]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import ai_based_frame_interpolation_amd as P  # noqa: E402
+from ai_based_frame_interpolation_amd import holdout, optical_flow as OF  # noqa: E402
+from oracle import unet_oracle as O  # noqa: E402
+from holdout_timing import _clip  # noqa: E402
+
+
+def _events(fn, iters):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / iters
+
+
+def _wall(fn, iters):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def _pairs(dev, b, h, w):
+    """B pairs of a moving texture, uint8 [B, h, w] each: pair i moves by (2 + i, 1) pixels."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    tex = lambda dx, dy: 128 + 90 * np.sin((xx - dx) / 9.0) * np.cos((yy - dy) / 13.0) + 30 * np.cos((xx - dx + yy - dy) / 5.0)
+    f0 = np.stack([tex(0.3 * i, 0) for i in range(b)])
+    f1 = np.stack([tex(0.3 * i + 2 + i % 3, 1) for i in range(b)])
+    q = lambda a: torch.from_numpy(np.clip(np.rint(a), 0, 255).astype(np.uint8)).to(dev)
+    return q(f0), q(f1)
+
+
+def _pair_leg(dev, b, h, w, a):
+    f0, f1 = _pairs(dev, b, h, w)
+    both = lambda backend: OF.warp(f0, f1, OF.farneback_flow(f0, f1, backend), "motion", backend)
+    cases = {"hip flow": (lambda: OF.farneback_flow(f0, f1, "hip"), _events, a.iters),
+             "hip flow+warp": (lambda: both("hip"), _events, a.iters),
+             "torch flow": (lambda: OF.farneback_flow(f0, f1, "torch"), _wall, a.torch_iters),
+             "torch flow+warp": (lambda: both("torch"), _wall, a.torch_iters)}
+    gap = (both("hip").int() - both("torch").int()).abs()            # (also the warm-up of both)
+    for name, (fn, _, _) in cases.items():
+        for _ in range(a.warmup if name.startswith("hip") else 0):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, (fn, timer, iters) in cases.items():
+            ms[k].append(timer(fn, iters) / b)
+    leg = dict(batch=b, shape=f"{h}x{w}", pixels_differing=round(float((gap != 0).float().mean()), 6),
+               largest_difference=int(gap.max()))
+    for k in cases:
+        med = statistics.median(ms[k])
+        leg[k] = dict(ms_per_pair=round(med, 4), spread_ms=[round(min(ms[k]), 4), round(max(ms[k]), 4)])
+        print(f"{b}x{h}x{w} {k:16s} {med:10.4f} ms / pair  (reps {min(ms[k]):.4f}-{max(ms[k]):.4f})", flush=True)
+    for k in ("flow", "flow+warp"):
+        leg[f"torch / hip time, {k}"] = round(leg[f"torch {k}"]["ms_per_pair"] / leg[f"hip {k}"]["ms_per_pair"], 2)
+        print(f"{b}x{h}x{w} torch / hip time, {k}: {leg[f'torch / hip time, {k}']}", flush=True)
+    return leg
+
+
+def _score(dev, frames, h, w):
+    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
+    m.load_state_dict(O.make_interpolating_state_dict(n_channels=6, n_classes=3))
+    m = m.to(dev).eval()
+    spent = [0.0]
+    inner = holdout._predict_flow
+
+    def timed(*a, **k):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = inner(*a, **k)
+        torch.cuda.synchronize()
+        spent[0] += time.perf_counter() - t0
+        return res
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        src = os.path.join(tmp, "clip.y4m")
+        _clip(src, frames, h, w)
+        holdout.score_video(m, src, methods=holdout.ALL_METHODS, chunk_frames=8)   # warm-up
+        for name, methods in (("three methods", holdout.METHODS), ("five methods", holdout.ALL_METHODS)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = holdout.score_video(m, src, methods=methods)
+            torch.cuda.synchronize()
+            out[f"wall_s, {name}"] = round(time.perf_counter() - t0, 3)
+        holdout._predict_flow = timed
+        try:
+            t0 = time.perf_counter()
+            holdout.score_video(m, src, methods=holdout.ALL_METHODS)
+            torch.cuda.synchronize()
+            wall2 = time.perf_counter() - t0
+        finally:
+            holdout._predict_flow = inner
+    print(holdout.summary_table(res), flush=True)
+    out.update(frames=frames, scored_frames=len(res["scored_frames"]), timed_run_wall_s=round(wall2, 3),
+               flow_s=round(spent[0], 3), flow_share=round(spent[0] / wall2, 3))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--torch-iters", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--clip-frames", type=int, default=65)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "flow_timing measures on the GPU; there is no CPU path"
+    dev = torch.device("cuda:0")
+    res = {"protocol": f"hip: HIP events, {a.warmup} warm-up calls, {a.iters} calls; torch: wall clock behind a synchronise, "
+                       f"{a.torch_iters} call(s); median of {a.reps} interleaved reps, per pair"}
+    res["1080p"] = _pair_leg(dev, a.batch, 1080, 1920, a)
+    res["256x256"] = _pair_leg(dev, a.batch, 256, 256, a)
+    torch.cuda.empty_cache()
+    res["score_video"] = _score(dev, a.clip_frames, 1080, 1920)
+    print("score_video:", res["score_video"], flush=True)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
