@@ -40,6 +40,7 @@ SYMBOLS = (
     "fiunet_profile_read", "fiunet_metrics_workspace_bytes", "fiunet_psnr_u8", "fiunet_ssim_u8",
     "fiunet_ssim_gauss_workspace_bytes", "fiunet_ssim_gauss_f32",
     "fiunet_plane_metrics_workspace_bytes", "fiunet_plane_psnr", "fiunet_plane_ssim",
+    "fiunet_interleaved_psnr", "fiunet_stepped_ssim",
     "fiunet_yuv420_to_rgb_u8", "fiunet_rgb_to_yuv420_u8", "fiunet_workspace_bytes_yuv420", "fiunet_forward_yuv420",
     "fiunet_preprocess_p10", "fiunet_postprocess_p10", "fiunet_workspace_bytes_p10", "fiunet_forward_p10",
     "fiunet_yuv420p10_to_rgb_p10", "fiunet_rgb_p10_to_yuv420p10", "fiunet_workspace_bytes_yuv420p10",
@@ -207,6 +208,8 @@ def lib() -> ctypes.CDLL:
     L.fiunet_plane_metrics_workspace_bytes.restype = sz
     L.fiunet_plane_psnr.argtypes = [vp, sz, sz, vp, sz, sz, ci, ci, ci, ci, vp, vp, vp, sz, vp]
     L.fiunet_plane_ssim.argtypes = [vp, sz, sz, vp, sz, sz, ci, ci, ci, ci, vp, vp, sz, vp]
+    L.fiunet_interleaved_psnr.argtypes = [vp, sz, sz, vp, sz, sz, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]
+    L.fiunet_stepped_ssim.argtypes = [vp, sz, sz, ci, vp, sz, sz, ci, ci, ci, ci, ci, vp, vp, sz, vp]
     L.fiunet_flow_workspace_bytes.argtypes = [ci, ci, ci]
     L.fiunet_flow_workspace_bytes.restype = sz
     L.fiunet_farneback_flow.argtypes = [vp, vp, ci, ci, ci, ci, sz, sz, vp, vp, sz, vp]

@@ -47,7 +47,12 @@ its two neighbours by the network, by blending and by repeating a frame, and com
     ffmpeg -i clip.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli evaluate --input - \\
         --model best_model.pth --json scores.json --csv frames.csv
 
-The summary table goes to standard error, the whole result to --json and one line per scored frame to --csv.
+The summary table goes to standard error, the whole result to --json and one line per scored frame to --csv.  Raw
+video is scored as the `video` command reads it (--raw, --size; --src-fps for the time stamps), and --scene-cut leaves
+the held-out frames next to a hard cut out of the summary:
+
+    ffmpeg -i clip.mkv -f rawvideo -pix_fmt nv12 - | python -m ai_based_frame_interpolation_amd.cli evaluate \\
+        --input - --raw nv12 --size 1920x1080 --src-fps 24 --model rgb_model.pth --scene-cut 10 --json scores.json
 """
 from __future__ import annotations
 
@@ -105,6 +110,10 @@ def _methods(v: str):
     return names
 
 
+RAW_CHOICES = ("nv12", "rgb24", "bgr24", "rgba", "bgra", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le", "uyvy422",
+               "yuyv422")
+
+
 def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m ai_based_frame_interpolation_amd.cli",
                                  description="AI frame interpolation on the MI355X")
@@ -130,14 +139,13 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--time-depth", type=int, default=2, choices=(1, 2, 3, 4), help="Bisection levels under --fps")
     v.add_argument("--retime", default="blend", choices=retime.MODES,
                    help="How --fps picks between the two bisection frames around an output time")
-    v.add_argument("--raw", default=None,
-                   choices=("nv12", "rgb24", "bgr24", "rgba", "bgra", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le",
-                            "uyvy422", "yuyv422"),
+    v.add_argument("--raw", default=None, choices=RAW_CHOICES,
                    help="Headerless raw video in and out (tight NV12, packed RGB or 4:2:2 / 4:4:4 YUV frames, named as "
                         "ffmpeg's -pix_fmt); needs --size and --src-fps")
     v.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
-    e = sub.add_parser("evaluate", help="Score a checkpoint on a clip by hold-out (Y4M or .npy; '-' is stdin)")
-    e.add_argument("--input", required=True, help="Clip to score: a .y4m or .npy path, or - for standard input (Y4M)")
+    e = sub.add_parser("evaluate", help="Score a checkpoint on a clip by hold-out (Y4M, .npy or --raw; '-' is stdin)")
+    e.add_argument("--input", required=True,
+                   help="Clip to score: a .y4m or .npy path, or - for standard input (Y4M, or --raw video)")
     e.add_argument("--model", default="best_model.pth", help="Path to trained model")
     e.add_argument("--device", default="auto", help="Device to use (cuda/auto)")
     e.add_argument("--triplets", default="sliding", choices=("sliding", "disjoint"),
@@ -154,6 +162,12 @@ def parser() -> argparse.ArgumentParser:
     e.add_argument("--chunk-frames", type=int, default=None, help="Held-out frames per chunk (default 4 x batch)")
     e.add_argument("--src-fps", type=_fps, default=None,
                    help="Source frame rate as n or n/d, for the time stamps (default: the Y4M header's)")
+    e.add_argument("--raw", default=None, choices=RAW_CHOICES,
+                   help="Headerless raw video (tight frames, named as ffmpeg's -pix_fmt); needs --size")
+    e.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
+    e.add_argument("--scene-cut", type=_scene_cut, default=None,
+                   help="Scene-cut threshold in (0, 100], or none: held-out frames next to a cut are left out of the "
+                        "summary")
     e.add_argument("--json", default=None, metavar="FILE", help="Write the whole result here (arrays as lists)")
     e.add_argument("--csv", default=None, metavar="FILE", help="Write one line per scored frame here")
     return ap
@@ -164,6 +178,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     a = ap.parse_args(argv)
     if a.chunk_frames is None:
         a.chunk_frames = 4 * a.batch
+    if a.command == "evaluate":
+        if a.raw is not None and a.size is None:
+            ap.error("--raw needs --size WIDTHxHEIGHT (raw video has no header)")
+        if a.raw is None and a.size is not None:
+            ap.error("--size describes --raw video")
+        return a
     if a.command != "video":
         return a
     if a.raw is not None and (a.size is None or a.src_fps is None):
@@ -204,7 +224,9 @@ def run_evaluate(a: argparse.Namespace) -> dict:
         model = load_model(a.model, device, a.precision, frame_channels=fc, weight_prep=a.weight_prep)
     src = sys.stdin.buffer if a.input == "-" else a.input
     res = holdout.score_video(model, src, triplets=a.triplets, methods=a.methods, batch=a.batch,
-                              chunk_frames=a.chunk_frames, matrix=a.matrix, siting=a.siting, src_fps=a.src_fps)
+                              chunk_frames=a.chunk_frames, matrix=a.matrix, siting=a.siting, src_fps=a.src_fps,
+                              raw=a.raw, width=a.size[0] if a.size else None, height=a.size[1] if a.size else None,
+                              scene_cut=a.scene_cut)
     print(holdout.summary_table(res), file=sys.stderr)
     if a.json:
         with open(a.json, "w") as f:

@@ -2138,21 +2138,25 @@ size_t fiunet_plane_metrics_workspace_bytes(int images, int H, int W)
 }
 
 // The checks both plane metrics share; every refusal is FIUNET_ERR_INVALID_ARG and comes before any pointer is used.
+// pred_row / target_row: the samples a row spans on each side (W; W*S interleaved; (W-1)*step + 1 stepped).
 static int check_planes(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
                         size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
-                        const void* out, const void* workspace, size_t workspace_bytes, size_t need)
+                        const void* out, const void* workspace, size_t workspace_bytes, size_t need,
+                        size_t pred_row = 0, size_t target_row = 0)
 {
     if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
     if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
     if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_INVALID_ARG, "bad plane shape");
     if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
-    if (pred_row_pitch < (size_t)W || target_row_pitch < (size_t)W)
+    if (!pred_row) pred_row = (size_t)W;
+    if (!target_row) target_row = (size_t)W;
+    if (pred_row_pitch < pred_row || target_row_pitch < target_row)
         return fail(FIUNET_ERR_INVALID_ARG, "plane layout: row_pitch < W");
     const size_t limit = (size_t)1 << 40;
     if (pred_row_pitch > limit || target_row_pitch > limit || pred_image_stride > limit || target_image_stride > limit)
         return fail(FIUNET_ERR_INVALID_ARG, "plane layout: a value above 2^40 samples");
-    if (images > 1 && (pred_image_stride < (size_t)(H - 1) * pred_row_pitch + W ||
-                       target_image_stride < (size_t)(H - 1) * target_row_pitch + W))
+    if (images > 1 && (pred_image_stride < (size_t)(H - 1) * pred_row_pitch + pred_row ||
+                       target_image_stride < (size_t)(H - 1) * target_row_pitch + target_row))
         return fail(FIUNET_ERR_INVALID_ARG, "plane layout: image_stride smaller than one plane");
     const size_t align = bits == 10 ? 1 : 0;
     if ((((uintptr_t)pred | (uintptr_t)target) & align) != 0)
@@ -2208,15 +2212,19 @@ int fiunet_plane_psnr(const void* pred, size_t pred_image_stride, size_t pred_ro
     return FIUNET_OK;
 }
 
-int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
-                      size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
-                      double* out_ssim, void* workspace, size_t workspace_bytes, void* stream)
+int fiunet_stepped_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, int pred_step,
+                              const void* target, size_t target_image_stride, size_t target_row_pitch, int target_step,
+                              int bits, int images, int H, int W, double* out_ssim, void* workspace,
+                              size_t workspace_bytes, void* stream)
 {
+    if (pred_step < 1 || pred_step > 4 || target_step < 1 || target_step > 4)
+        return fail(FIUNET_ERR_INVALID_ARG, "sample step must be 1, 2, 3 or 4");
     if (H < SSIM_WIN || W < SSIM_WIN)
         return fail(FIUNET_ERR_INVALID_ARG, "SSIM: the 7x7 window exceeds the plane (skimage raises too)");
     const size_t need = images > 0 ? fiunet_metrics_workspace_bytes(images, H, W) : 0;
     if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
-                              bits, images, H, W, out_ssim, workspace, workspace_bytes, need))
+                              bits, images, H, W, out_ssim, workspace, workspace_bytes, need,
+                              (size_t)(W - 1) * pred_step + 1, (size_t)(W - 1) * target_step + 1))
         return rc;
     hipStream_t s = (hipStream_t)stream;
     int tx = 0;
@@ -2225,15 +2233,87 @@ int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_ro
     const dim3 grid((unsigned)tiles, (unsigned)images);
     if (bits == 10)
         hipLaunchKernelGGL(plane_ssim_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)pred, pred_image_stride,
-                           pred_row_pitch, (const uint16_t*)target, target_image_stride, target_row_pitch, H, W, tx,
-                           partial);
+                           pred_row_pitch, (unsigned)pred_step, (const uint16_t*)target, target_image_stride,
+                           target_row_pitch, (unsigned)target_step, H, W, tx, partial);
     else
         hipLaunchKernelGGL(plane_ssim_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)pred, pred_image_stride,
-                           pred_row_pitch, (const uint8_t*)target, target_image_stride, target_row_pitch, H, W, tx,
-                           partial);
+                           pred_row_pitch, (unsigned)pred_step, (const uint8_t*)target, target_image_stride,
+                           target_row_pitch, (unsigned)target_step, H, W, tx, partial);
     HIP_TRY(hipGetLastError());
     const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
     hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out_ssim);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                      size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
+                      double* out_ssim, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return fiunet_stepped_ssim(pred, pred_image_stride, pred_row_pitch, 1, target, target_image_stride,
+                                     target_row_pitch, 1, bits, images, H, W, out_ssim, workspace, workspace_bytes,
+                                     stream);
+}
+
+extern "C++" {
+template <typename T, int S>
+static int launch_interleaved_sqdiff(const void* pred, size_t ps, size_t pp, const void* target, size_t ts, size_t tp,
+                                     int images, int H, int W, unsigned long long* sums, hipStream_t s)
+{
+    // rows that follow each other on both sides are one run of H*W*S samples, cut into interleaved_seg(S) pieces (a
+    // multiple of S and of 16 bytes: a piece starts at component 0 and an aligned run keeps the 16-byte path)
+    constexpr size_t SEG = interleaved_seg(S);
+    const size_t row = (size_t)W * S, n = (size_t)H * row;
+    const bool flat = pp == row && tp == row;
+    if (flat && (n + SEG - 1) / SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
+    const unsigned rows = flat ? (unsigned)((n + SEG - 1) / SEG) : (unsigned)H;
+    const unsigned len = flat ? (unsigned)SEG : (unsigned)row;
+    const unsigned l_last = flat ? (unsigned)(n - (size_t)(rows - 1) * SEG) : (unsigned)row;
+    const size_t pa = flat ? SEG : pp, pb = flat ? SEG : tp;
+    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
+    hipLaunchKernelGGL((interleaved_sqdiff_kernel<T, S>), dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)pred, ps,
+                       pa, (const T*)target, ts, pb, rows, len, l_last, sums);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+template <typename T>
+static int launch_interleaved_psnr(int S, const void* pred, size_t ps, size_t pp, const void* target, size_t ts,
+                                   size_t tp, int images, int H, int W, unsigned long long* sums, hipStream_t s)
+{
+    if (S == 2) return launch_interleaved_sqdiff<T, 2>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
+    if (S == 3) return launch_interleaved_sqdiff<T, 3>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
+    return launch_interleaved_sqdiff<T, 4>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
+}
+}  // extern "C++"
+
+int fiunet_interleaved_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                            size_t target_image_stride, size_t target_row_pitch, int bits, int components, int images,
+                            int H, int W, double* out_psnr, unsigned long long* out_sse, void* workspace,
+                            size_t workspace_bytes, void* stream)
+{
+    if (components < 2 || components > 4) return fail(FIUNET_ERR_INVALID_ARG, "components must be 2, 3 or 4");
+    if (W > (1 << 29)) return fail(FIUNET_ERR_INVALID_ARG, "bad plane shape");
+    if (images > 65535 / components)
+        return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 component planes (images x components) per call");
+    const size_t row = W > 0 ? (size_t)W * components : 0;
+    const size_t need = images > 0 ? align256((size_t)images * components * 8) : 0;
+    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
+                              bits, images, H, W, out_psnr, workspace, workspace_bytes, need, row, row))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* sums = (unsigned long long*)workspace;
+    const int planes = images * components;
+    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)planes * 8, s));
+    if (int rc = bits == 10 ? launch_interleaved_psnr<uint16_t>(components, pred, pred_image_stride, pred_row_pitch,
+                                                                target, target_image_stride, target_row_pitch, images,
+                                                                H, W, sums, s)
+                            : launch_interleaved_psnr<uint8_t>(components, pred, pred_image_stride, pred_row_pitch,
+                                                               target, target_image_stride, target_row_pitch, images, H,
+                                                               W, sums, s))
+        return rc;
+    hipLaunchKernelGGL(plane_psnr_finalize_kernel, dim3((planes + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
+                       bits == 10 ? 1023.0 : 255.0, out_psnr, out_sse, planes);
     HIP_TRY(hipGetLastError());
     return FIUNET_OK;
 }

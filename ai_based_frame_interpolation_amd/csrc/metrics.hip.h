@@ -239,6 +239,107 @@ __global__ __launch_bounds__(256) void plane_sqdiff_kernel(const T* __restrict__
     }
 }
 
+// Interleaved rows: a row is W*S samples and the sample at position p belongs to component p % S (U V of NV12,
+// R G B [A] of packed RGB, the byte positions of uyvy422 / yuyv422).  plane_sqdiff_kernel's access pattern - one wave
+// per row at a time, 16 bytes per lane between a scalar head and tail where both row bases share their place in a
+// 16-byte line, sample by sample otherwise - with S sums per lane, so one pass over the bytes gives every component.
+// Where the rows follow each other on both sides the host cuts the run into pieces of interleaved_seg(S) samples, a
+// multiple of S and of 16 bytes: every row and every piece starts at component 0.
+__host__ __device__ constexpr unsigned interleaved_seg(int S) { return S == 3 ? 3072u : (unsigned)PLANE_SEG; }
+
+// (a-b)^2 of sample J of a 16-byte vector pair
+template <typename T, int J> __device__ __forceinline__ unsigned sqdiff_at(const unsigned (&wa)[4], const unsigned (&wb)[4])
+{
+    constexpr int BITS = 8 * sizeof(T), N = 4 / sizeof(T);
+    constexpr unsigned MASK = (1u << BITS) - 1u;
+    const int d = PlaneSample<T>::get((wa[J / N] >> (BITS * (J % N))) & MASK) -
+                  PlaneSample<T>::get((wb[J / N] >> (BITS * (J % N))) & MASK);
+    return (unsigned)(d * d);
+}
+
+template <typename T, int S, int J = 0> struct VecSlots {   // slot[j % S] += (a-b)^2 of sample j, j = J .. VEC-1
+    static __device__ __forceinline__ void add(const unsigned (&wa)[4], const unsigned (&wb)[4], unsigned (&slot)[S])
+    {
+        slot[J % S] += sqdiff_at<T, J>(wa, wb);
+        VecSlots<T, S, J + 1>::add(wa, wb, slot);
+    }
+};
+template <typename T, int S> struct VecSlots<T, S, (int)(16 / sizeof(T))> {
+    static __device__ __forceinline__ void add(const unsigned (&)[4], const unsigned (&)[4], unsigned (&)[S]) {}
+};
+
+// grid = (blocks per image, images); `sums` [images * S] zeroed by the caller, image-major.
+template <typename T, int S>
+__global__ __launch_bounds__(256) void interleaved_sqdiff_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
+                                                                 const T* __restrict__ b, size_t b_image, size_t b_pitch,
+                                                                 unsigned rows, unsigned L, unsigned l_last,
+                                                                 unsigned long long* __restrict__ sums)
+{
+    constexpr unsigned VEC = 16 / sizeof(T);
+    const size_t img = blockIdx.y;
+    const T* ia = a + img * a_image;
+    const T* ib = b + img * b_image;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long s[S];
+#pragma unroll
+    for (int c = 0; c < S; ++c) s[c] = 0;
+    for (unsigned r = blockIdx.x * 4 + wave; r < rows; r += gridDim.x * 4) {
+        const T* pa = ia + (size_t)r * a_pitch;
+        const T* pb = ib + (size_t)r * b_pitch;
+        const unsigned len = r + 1 == rows ? l_last : L;
+        const bool same = (((uintptr_t)pa ^ (uintptr_t)pb) & 15) == 0;
+        const unsigned head = same ? min(len, (unsigned)(((16 - ((uintptr_t)pa & 15)) & 15) / sizeof(T))) : len;
+        const unsigned nv = (len - head) / VEC;
+        // head (the whole row where the vector path does not apply): position i is component i % S
+        for (unsigned i = lane; i < head; i += 64) {
+            const int d = PlaneSample<T>::get(pa[i]) - PlaneSample<T>::get(pb[i]);
+            const unsigned q = (unsigned)(d * d), c0 = i % S;
+#pragma unroll
+            for (int c = 0; c < S; ++c) s[c] += c0 == (unsigned)c ? q : 0u;
+        }
+        const uint4* qa = reinterpret_cast<const uint4*>(pa + head);
+        const uint4* qb = reinterpret_cast<const uint4*>(pb + head);
+        for (unsigned i = lane; i < nv; i += 64) {
+            const uint4 va = qa[i], vb = qb[i];
+            const unsigned wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
+            unsigned slot[S];   // by position inside the vector: <= 16 * 255^2, 8 * 1023^2
+#pragma unroll
+            for (int c = 0; c < S; ++c) slot[c] = 0;
+            VecSlots<T, S>::add(wa, wb, slot);
+            // the vector's first sample is position head + i * VEC of the row: at S = 3 that phase turns from one
+            // vector to the next and again when the lane advances by 64 vectors; at S = 2, 4 it is head % S
+            const unsigned phase = (head + i * VEC) % S;
+#pragma unroll
+            for (int c = 0; c < S; ++c) {   // component c sits in slot (c - phase) mod S
+                unsigned v = 0;
+#pragma unroll
+                for (int k = 0; k < S; ++k) v = (phase + k) % S == (unsigned)c ? slot[k] : v;
+                s[c] += v;
+            }
+        }
+        for (unsigned i = head + nv * VEC + lane; i < len; i += 64) {
+            const int d = PlaneSample<T>::get(pa[i]) - PlaneSample<T>::get(pb[i]);
+            const unsigned q = (unsigned)(d * d), c0 = i % S;
+#pragma unroll
+            for (int c = 0; c < S; ++c) s[c] += c0 == (unsigned)c ? q : 0u;
+        }
+    }
+    __shared__ unsigned long long part[4][S];
+#pragma unroll
+    for (int c = 0; c < S; ++c) {
+        unsigned long long v = s[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) part[wave][c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < S) {
+        const unsigned long long t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] +
+                                     part[3][threadIdx.x];
+        if (t) atomicAdd(sums + img * S + threadIdx.x, t);
+    }
+}
+
 // psnr_finalize_kernel with the peak as an argument; out_sse (may be NULL) receives the integer sums
 __global__ void plane_psnr_finalize_kernel(const unsigned long long* __restrict__ sums, size_t n, double peak,
                                            double* __restrict__ out, unsigned long long* __restrict__ out_sse,
@@ -251,11 +352,14 @@ __global__ void plane_psnr_finalize_kernel(const unsigned long long* __restrict_
     if (out_sse) out_sse[i] = sums[i];
 }
 
-// ssim_u8_kernel on strided planes of either depth: same tiles, same order of every sum
+// ssim_u8_kernel on strided planes of either depth: same tiles, same order of every sum.  Sample (y, x) of an image
+// lies at y * pitch + x * step (step 1: a plane of its own; 2..4: one component of interleaved samples, the U of NV12,
+// a byte of packed RGB, the Y of uyvy422).  The step enters the tile load and nothing else.
 template <typename T>
 __global__ __launch_bounds__(256) void plane_ssim_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
-                                                         const T* __restrict__ b, size_t b_image, size_t b_pitch,
-                                                         int H, int W, int tiles_x, double* __restrict__ partial)
+                                                         unsigned a_step, const T* __restrict__ b, size_t b_image,
+                                                         size_t b_pitch, unsigned b_step, int H, int W, int tiles_x,
+                                                         double* __restrict__ partial)
 {
     constexpr int IW = SSIM_TX + SSIM_WIN - 1, IH = SSIM_TY + SSIM_WIN - 1, IWP = IW + 2;
     __shared__ T ta[IH * IWP], tb[IH * IWP];
@@ -271,8 +375,8 @@ __global__ __launch_bounds__(256) void plane_ssim_kernel(const T* __restrict__ a
     for (int i = tid; i < IH * IW; i += 256) {
         const int r = i / IW, c = i - r * IW;
         const int y = min(oy0 + r, H - 1), x = min(ox0 + c, W - 1);
-        ta[r * IWP + c] = (T)PlaneSample<T>::get(pa[(size_t)y * a_pitch + x]);
-        tb[r * IWP + c] = (T)PlaneSample<T>::get(pb[(size_t)y * b_pitch + x]);
+        ta[r * IWP + c] = (T)PlaneSample<T>::get(pa[(size_t)y * a_pitch + (size_t)x * a_step]);
+        tb[r * IWP + c] = (T)PlaneSample<T>::get(pb[(size_t)y * b_pitch + (size_t)x * b_step]);
     }
     __syncthreads();
     for (int i = tid; i < IH * SSIM_TX; i += 256) {

@@ -21,27 +21,44 @@ chunk.
              .npy [N,H,W]: "gray"; .npy [N,H,W,C]: "c0".. (made planar by one permute per chunk).  The plane views
              go to `metrics.psnr_planes` / `ssim_planes` as they lie in the rows: no plane is copied.  A plane smaller
              than 7x7 gets PSNR only (its SSIM is NaN).
+  raw        with `raw=` (one of stream.RAW_FORMATS, with width and height) the source is headerless tight frames, what
+             `interpolate_raw_stream` takes, through `stream._raw_route`: "y" "u" "v" for nv12, the planar 4:2:2 /
+             4:4:4 formats and uyvy422 / yuyv422, "r" "g" "b" (and "a": the alpha of an inserted frame is what the route
+             writes, so it is scored) for packed RGB (`raw_planes`).  A plane is (name, offset, h, w, row
+             pitch, sample step): interleaved planes (U V of nv12, the bytes of packed RGB, the byte positions of the
+             capture formats) are scored where they lie - all components of a group in one `metrics.psnr_interleaved`
+             call per method, SSIM plane by plane through the stepped kernel.  Contiguous copies of stepped planes exist
+             for the flow methods only: the flow source (Y; for packed RGB the rounded mean of r, g, b) and the planes
+             the warp kernel reads and writes, which are copied back into the prediction rows.
+  scene cuts with `scene_cut=` (scene.py's threshold) every uploaded chunk also goes through `scene.pair_sad` - the whole
+             frame as stored, the video loops' definition - and the interval sums are kept on the host by source
+             interval: 8 bytes per source frame, the one quantity here that grows with the clip.  After the last chunk
+             one `scene.score_window` over all of them gives the flags `scene.detect_cuts` gives on the whole clip.  A
+             held-out frame t is EXCLUDED when interval t-1 (frames t-1, t) or interval t (frames t, t+1) is a cut: it
+             is still predicted and scored (`per_frame` and `scored_frames` are those of a run without scene_cut), but
+             `summary` is taken over the other targets.
   chunks     `chunk_spans` cuts the clip so that a chunk holds `chunk_frames` held-out frames, their neighbours
              included; the loop reads a chunk through the route's reader, uploads it, runs the methods, scores, keeps
              the few numbers per frame on the host and carries the overlap frames into the next chunk.  Every held-out
              frame is scored exactly once and a pair's forward does not depend on the pairs that share its call
              (`_padded_chunk`), so the result is the same to the last bit for every chunk_frames.
 
-Out of scope: raw NV12 and packed-RGB input, leaving out triplets that straddle a scene cut (the per-frame arrays let a
-caller filter), several GPUs.
+Out of scope: pitched raw input, several GPUs.
 """
 from __future__ import annotations
 
 import math
 import os
+import stat
 
 import numpy as np
 import torch
 
-from . import imageio_lite, metrics, optical_flow
+from . import colour, imageio_lite, metrics, optical_flow, packed, scene
 from . import retime as _retime
 from .inference import _interleave_average_p10, _interleave_average_u8
-from .stream import _NpyRows, _is_path, _npy_route, _y4m_route, check_chunk_frames
+from .stream import (RAW_FORMATS, _NpyRows, _RawReader, _is_path, _npy_route, _raw_route, _y4m_route,
+                     check_chunk_frames)
 
 TRIPLETS = ("sliding", "disjoint")
 METHODS = ("unet", "linear", "repeat")
@@ -105,15 +122,73 @@ def _too_short(n):
 
 
 class _Source:
-    """route, reader, the planes [(name, offset in the row, h, w)] (channels: the C of an [N,H,W,C] stack, whose planes
-    are cut after a permute), the frame rate (a Fraction or None) and close()."""
+    """route, reader, the planes [(name, offset in the row, h, w, row pitch, sample step)] in samples (channels: the C of
+    an [N,H,W,C] stack, whose planes are cut after a permute), the frame rate (a Fraction or None) and close().
+    groups: [(S, offset, h, w, row pitch, {plane name: component})], the interleaved groups whose PSNR comes from one
+    `psnr_interleaved` call (w: samples per component and row); lead: the plane names the flow is estimated on (one:
+    that plane; three: their rounded mean)."""
 
-    def __init__(self, route, reader, planes, channels, fps, close):
-        self.route, self.reader, self.planes, self.channels, self.fps, self.close = (route, reader, planes, channels,
-                                                                                     fps, close)
+    def __init__(self, route, reader, planes, channels, fps, close, groups=(), lead=None):
+        self.route, self.reader, self.channels, self.fps, self.close = route, reader, channels, fps, close
+        self.planes = [tuple(p) + (p[3], 1) if len(p) == 4 else tuple(p) for p in planes]
+        self.groups, self.lead = list(groups), lead or (self.planes[0][0],)
 
 
-def _open(model, src, batch, matrix, siting, src_fps) -> _Source:
+_PACKED_BYTES = {"rgb24": "rgb", "bgr24": "bgr", "rgba": "rgba", "bgra": "bgra"}
+
+
+def raw_planes(raw: str, height: int, width: int):
+    """The planes of one tight frame of `raw` (stream.RAW_FORMATS) -> (planes [(name, offset, h, w, row pitch, sample
+    step)], groups [(S, offset, h, w, row pitch, {name: component})]), everything in samples.  Every sample of the frame
+    belongs to exactly one plane."""
+    if raw not in RAW_FORMATS:
+        raise ValueError(f"raw must be one of {list(RAW_FORMATS)}, got {raw!r}")
+    h, w = int(height), int(width)
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+    if raw == "nv12":
+        return ([("y", 0, h, w, w, 1), ("u", h * w, hc, wc, 2 * wc, 2), ("v", h * w + 1, hc, wc, 2 * wc, 2)],
+                [(2, h * w, hc, wc, 2 * wc, {"u": 0, "v": 1})])
+    if raw in _PACKED_BYTES:
+        order = _PACKED_BYTES[raw]
+        s = len(order)
+        names = "rgb" + ("a" if s == 4 else "")
+        return ([(c, order.index(c), h, w, s * w, s) for c in names], [(s, 0, h, w, s * w, {c: order.index(c) for c in names})])
+    kind = colour.YUV_FORMATS[raw][2]
+    if kind == "packed":
+        colour.yuv_frame_samples(raw, h, w)   # (refuses an odd width)
+        y, u, v = (1, 0, 2) if raw == "uyvy422" else (0, 1, 3)
+        return ([("y", y, h, w, 2 * w, 2), ("u", u, h, w // 2, 2 * w, 4), ("v", v, h, w // 2, 2 * w, 4)],
+                [(2, 0, h, w, 2 * w, {"y": y}), (4, 0, h, w // 2, 2 * w, {"u": u, "v": v})])
+    cw = w if kind == "444" else wc
+    return [("y", 0, h, w, w, 1), ("u", h * w, h, cw, cw, 1), ("v", h * w + h * cw, h, cw, cw, 1)], []
+
+
+def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height) -> _Source:
+    if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
+        raise ValueError(f"raw={raw!r} describes headerless video; a .npy stack carries its own shape (leave raw None)")
+    route = _raw_route(model, raw, height, width, False, batch, matrix, siting)
+    planes, groups = raw_planes(raw, height, width)
+    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire
+    if _is_path(src):
+        if not os.path.exists(src):
+            raise FileNotFoundError(f"Video file not found: {src}")
+        st = os.stat(src)
+        if stat.S_ISREG(st.st_mode):
+            if st.st_size % wire_row:
+                raise ValueError(f"{os.fspath(src)}: {st.st_size} bytes is not a whole number of {width}x{height} "
+                                 f"{raw} frames of {wire_row} bytes")
+            if st.st_size // wire_row < 3:
+                raise _too_short(st.st_size // wire_row)
+    fin = open(src, "rb") if _is_path(src) else src
+    return _Source(route, _RawReader(fin, wire_row), planes, 0, src_fps, fin.close if _is_path(src) else (lambda: None),
+                   groups, ("r", "g", "b") if raw in packed.FORMATS else ("y",))
+
+
+def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, height=None) -> _Source:
+    if raw is not None:
+        return _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height)
+    if width is not None or height is not None:
+        raise ValueError("width and height describe raw video: pass raw= with them")
     if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
         mm = np.load(src, mmap_mode="r")
         if mm.dtype != np.uint8 or mm.ndim not in (3, 4):
@@ -170,17 +245,27 @@ def _predict_flow(methods, source: _Source, d: torch.Tensor, batch: int) -> dict
     bits, k = source.route.bits, d.shape[0]
     if source.channels:   # [N,H,W,C]: planar copies, flow on the rounded channel mean
         c = source.channels
-        _, _, h, w = source.planes[0]
+        _, _, h, w = source.planes[0][:4]
         planar = d.reshape(k, h, w, c).permute(0, 3, 1, 2).contiguous()
         planes = [planar[:, i] for i in range(c)]
         lead = ((planar.sum(1, dtype=torch.int32) * 2 + c) // (2 * c)).to(torch.uint8)
         outs = {m: torch.empty((k - 1, c, h, w), dtype=d.dtype, device=d.device) for m in methods}
         dst = {m: [outs[m][:, i] for i in range(c)] for m in methods}
     else:
-        planes = _plane_views(d, source)
-        lead = planes[0]
+        views = _plane_views(d, source)
+        stepped = [p[5] != 1 for p in source.planes]
+        # (the warp kernel reads and writes rows of stride 1: a stepped plane goes through a contiguous copy)
+        planes = [v.contiguous() if st else v for v, st in zip(views, stepped)]
+        by_name = {p[0]: v for p, v in zip(source.planes, planes)}
+        if len(source.lead) == 1:
+            lead = by_name[source.lead[0]]
+        else:   # packed RGB: the rounded mean of r, g and b (not alpha), the [N,H,W,C] .npy rule
+            c = len(source.lead)
+            total = sum(by_name[n].to(torch.int32) for n in source.lead)
+            lead = ((total * 2 + c) // (2 * c)).to(torch.uint8)
         outs = {m: torch.empty_like(d[:-1]) for m in methods}
-        dst = {m: _plane_views(outs[m], source) for m in methods}
+        back = {m: _plane_views(outs[m], source) for m in methods}
+        dst = {m: [torch.empty_like(p[:-1]) if st else o for p, o, st in zip(planes, back[m], stepped)] for m in methods}
     for s in range(0, k - 1, batch):
         e = min(s + batch, k - 1)
         flow = optical_flow.farneback_flow(lead[s:e], lead[s + 1:e + 1], "hip", bits=bits)
@@ -189,16 +274,29 @@ def _predict_flow(methods, source: _Source, d: torch.Tensor, batch: int) -> dict
                 optical_flow.warp(p[s:e], p[s + 1:e + 1], flow, FLOW_METHODS[m], "hip", bits=bits, out=o[s:e])
     if source.channels:
         return {m: outs[m].permute(0, 2, 3, 1).reshape(k - 1, -1) for m in methods}
+    for m in methods:
+        for o, b, st in zip(dst[m], back[m], stepped):
+            if st:
+                b.copy_(o)
     return outs
+
+
+def _strided(rows: torch.Tensor, off: int, shape, strides):
+    return rows.as_strided((rows.shape[0],) + tuple(shape), (rows.stride(0),) + tuple(strides), rows.storage_offset() + off)
 
 
 def _plane_views(rows: torch.Tensor, source: _Source):
     """rows [m, row] (any row stride) -> the planes' [m, h, w] views, in the order of source.planes."""
     if source.channels:
-        _, _, h, w = source.planes[0]
+        _, _, h, w = source.planes[0][:4]
         planar = rows.reshape(rows.shape[0], h, w, source.channels).permute(0, 3, 1, 2).contiguous()
         return [planar[:, c] for c in range(source.channels)]
-    return [rows[:, off:off + h * w].unflatten(1, (h, w)) for _, off, h, w in source.planes]
+    return [_strided(rows, off, (h, w), (pitch, step)) for _, off, h, w, pitch, step in source.planes]
+
+
+def _group_views(rows: torch.Tensor, source: _Source):
+    """rows [m, row] -> the interleaved groups' [m, h, w, S] views, in the order of source.groups."""
+    return [_strided(rows, off, (h, w, comp), (pitch, comp, 1)) for comp, off, h, w, pitch, _ in source.groups]
 
 
 def _score_chunk(source: _Source, methods, d_all: torch.Tensor, n_targets: int, step: int, batch: int = 8):
@@ -207,21 +305,30 @@ def _score_chunk(source: _Source, methods, d_all: torch.Tensor, n_targets: int, 
     bits = source.route.bits
     res = {m: {p[0]: (np.empty(n_targets), np.full(n_targets, np.nan), np.empty(n_targets, np.uint64))
                for p in source.planes} for m in methods}
+    grouped = {name for g in source.groups for name in g[5]}
     for off in range(3 - step):   # sliding: the frames at even offsets, then those at odd offsets
         d = d_all[off::2].contiguous()
         k = d.shape[0]
         if k < 2:
             continue
-        truth = _plane_views(d_all[off + 1::2][:k - 1], source)
+        truth_rows = d_all[off + 1::2][:k - 1]
+        truth, truth_groups = _plane_views(truth_rows, source), _group_views(truth_rows, source)
         where = slice(off, None, 2) if step == 1 else slice(None)
         flowed = _predict_flow(flow_methods, source, d, batch) if flow_methods else {}
         for m in methods:
-            pred = _plane_views(flowed[m] if m in flowed else _predict(m, source.route, d), source)
-            for (name, _, h, w), p, t in zip(source.planes, pred, truth):
-                ps, sse = metrics.psnr_planes(p, t, bits, return_sse=True)
+            rows = flowed[m] if m in flowed else _predict(m, source.route, d)
+            # every component of an interleaved group in one pass over its samples
+            for g, p, t in zip(source.groups, _group_views(rows, source), truth_groups):
+                ps, sse = metrics.psnr_interleaved(p, t, bits, return_sse=True)
+                ps, sse = ps.cpu().numpy(), sse.cpu().numpy().view(np.uint64)
+                for name, comp in g[5].items():
+                    res[m][name][0][where], res[m][name][2][where] = ps[:, comp], sse[:, comp]
+            for (name, _, h, w, _, _), p, t in zip(source.planes, _plane_views(rows, source), truth):
                 out = res[m][name]
-                out[0][where] = ps.cpu().numpy()
-                out[2][where] = sse.cpu().numpy().view(np.uint64)
+                if name not in grouped:
+                    ps, sse = metrics.psnr_planes(p, t, bits, return_sse=True)
+                    out[0][where] = ps.cpu().numpy()
+                    out[2][where] = sse.cpu().numpy().view(np.uint64)
                 if h >= 7 and w >= 7:
                     out[1][where] = metrics.ssim_planes(p, t, bits).cpu().numpy()
     return res
@@ -242,21 +349,49 @@ def _stats(psnr, ssim, sse, pixels: int, peak: int) -> dict:
     return {k: out[k] for k in STATS}
 
 
+def _kept_stats(a: dict, keep, pixels: int, peak: int) -> dict:
+    """`_stats` over the targets of the mask `keep` (None: all of them); with none left every figure is NaN and
+    identical_frames 0."""
+    if keep is None:
+        return _stats(a["psnr"], a["ssim"], a["sse"], pixels, peak)
+    if not keep.any():
+        return {k: 0 if k == "identical_frames" else float("nan") for k in STATS}
+    return _stats(a["psnr"][keep], a["ssim"][keep], a["sse"][keep], pixels, peak)
+
+
+def excluded_targets(cut_flags, scored_frames) -> np.ndarray:
+    """bool mask over `scored_frames`: held-out frame t is excluded when interval t-1 (frames t-1, t) or interval t
+    (frames t, t+1) is a cut.  cut_flags: one value per source interval."""
+    cut = np.asarray(cut_flags).astype(bool)
+    t = np.asarray(scored_frames, dtype=np.int64)
+    return cut[t - 1] | cut[t] if t.size else np.zeros(0, bool)
+
+
 @torch.no_grad()
 def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch: int = 8, chunk_frames: int = 32,
-                matrix: str = "bt709", siting=None, src_fps=None) -> dict:
+                matrix: str = "bt709", siting=None, src_fps=None, raw=None, width=None, height=None,
+                scene_cut=None) -> dict:
     """Hold-out scores of `model` on a clip (methods: any of ALL_METHODS; with "optical_flow" or "motion" the result
     also has "flow_backend").  src: a path (.y4m, or a uint8 .npy stack [N,H,W] / [N,H,W,C]) or a
     readable binary file object carrying Y4M (a pipe): what `interpolate_y4m_stream` / `interpolate_npy_stream` take
-    for this model, with those routes' refusals.  batch / matrix / siting: the routes' arguments; chunk_frames: held-out
+    for this model, with those routes' refusals; with raw (one of stream.RAW_FORMATS), width and height: a path or a
+    readable binary file object of headerless tight frames, what `interpolate_raw_stream` takes, with that route's
+    refusals (a grayscale model, a missing size, an odd width of uyvy422 / yuyv422).  batch / matrix / siting: the
+    routes' arguments; chunk_frames: held-out
     frames per chunk (memory: chunk_frames + 2 source frames, "disjoint" 2 x chunk_frames + 1, on the host and on the
     device, beside each method's predictions); src_fps: the clip's frame rate where the stream carries none (kept in
-    the result for time stamps).  Every argument is checked before any GPU work.  Returns
+    the result for time stamps); scene_cut: None, or scene.py's threshold in (0, 100]: held-out frames next to a cut
+    are left out of the summary (8 bytes per source frame are kept for it).  Every argument is checked before any GPU
+    work.  Returns
 
       {"frames", "triplets", "bits", "peak", "planes", "methods", "fps", "scored_frames": int64 source frame indices,
        "per_frame": {method: {plane: {"psnr": f64[], "ssim": f64[], "sse": uint64[]}}},
        "summary": {method: {plane: {average_ / std_ / min_ / max_psnr over the finite values (numpy mean, population
-                   std), the same of ssim, psnr_of_mean_mse, identical_frames}}}}"""
+                   std), the same of ssim, psnr_of_mean_mse, identical_frames}}}}
+
+    and, with scene_cut, "scene_cut", "scene_scores" (float64 [frames - 1]), "cut_intervals" (int64), "excluded_frames"
+    (int64 source indices) and "excluded" (bool, aligned with scored_frames); the summary is then over the targets
+    that are not excluded (all NaN and identical_frames 0 if none is left)."""
     triplets = _check_triplets(triplets)
     methods = tuple([methods] if isinstance(methods, str) else methods)
     for m in methods:
@@ -267,25 +402,37 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     c = check_chunk_frames(chunk_frames)
     if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
         raise ValueError(f"batch must be a positive int, got {batch!r}")
+    thr = scene.check_threshold(scene_cut)
     if src_fps is not None:
         src_fps = _retime.parse_fps(src_fps)
-    source = _open(model, src, batch, matrix, siting, src_fps)
+    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height)
     try:
         route, step = source.route, _step(triplets)
         dev = next(model.parameters()).device
         buf = np.empty((_nominal(0, c, triplets)[1], route.row), dtype=route.ndtype)
         have = frames = 0          # rows of buf carried over; frames read so far
         scored, parts = [], []
+        sad = []                   # with scene_cut: (first interval, int64 sums) of every chunk: 8 bytes per frame
         i = 0
         while True:
             first, want = _nominal(i, c, triplets)
             got = source.reader.read_into(buf[have:], want - have)
             frames += got
             span = _span(i, frames, c, triplets)
+            count = 0 if span is None else span[1]
+            d_up = None
+            if thr is not None and got and have + got >= 2:
+                # every frame read, a trailing one no triplet uses included: the flags are the whole clip's
+                up = have + got
+                d_up = torch.from_numpy(buf[:up].view(np.int16) if route.bits == 10 else buf[:up]).to(dev)
+                sums = scene.pair_sad(d_up, route.bits).cpu().numpy()
+                # (an interval two chunks share has the same sum in both: only the new ones are kept)
+                sad.append((first + max(have - 1, 0), sums[max(have - 1, 0):]))
             if span is None:
                 break
             _, count, targets = span
-            d_all = torch.from_numpy(buf[:count].view(np.int16) if route.bits == 10 else buf[:count]).to(dev)
+            d_all = (torch.from_numpy(buf[:count].view(np.int16) if route.bits == 10 else buf[:count]).to(dev)
+                     if d_up is None else d_up[:count])
             parts.append(_score_chunk(source, methods, d_all, len(targets), step, int(batch)))
             scored += targets
             if have + got < want:   # the stream ended inside this chunk
@@ -302,12 +449,25 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     per = {m: {p: {key: np.concatenate([part[m][p][j] for part in parts])
                    for j, key in enumerate(("psnr", "ssim", "sse"))} for p in names} for m in methods}
     pixels = {p[0]: p[2] * p[3] for p in source.planes}
+    scored = np.asarray(scored, dtype=np.int64)
+    cuts = keep = None
+    if thr is not None:
+        sums = np.empty(frames - 1, dtype=np.int64)
+        for at, part in sad:
+            sums[at:at + part.size] = part
+        scores, flags = scene.score_window(torch.from_numpy(sums).to(dev), route.row, route.bits, thr)
+        cuts = flags.cpu().numpy().astype(bool)
+        excluded = excluded_targets(cuts, scored)
+        keep = ~excluded
     out = {"frames": frames, "triplets": triplets, "bits": route.bits, "peak": peak, "planes": names,
            "methods": list(methods), "fps": None if source.fps is None else (source.fps.numerator,
                                                                              source.fps.denominator),
-           "scored_frames": np.asarray(scored, dtype=np.int64), "per_frame": per,
-           "summary": {m: {p: _stats(per[m][p]["psnr"], per[m][p]["ssim"], per[m][p]["sse"], pixels[p], peak)
-                           for p in names} for m in methods}}
+           "scored_frames": scored, "per_frame": per,
+           "summary": {m: {p: _kept_stats(per[m][p], keep, pixels[p], peak) for p in names} for m in methods}}
+    if thr is not None:
+        out.update({"scene_cut": thr, "scene_scores": scores.cpu().numpy(),
+                    "cut_intervals": np.flatnonzero(cuts).astype(np.int64), "excluded_frames": scored[excluded],
+                    "excluded": excluded})
     if any(m in FLOW_METHODS for m in methods):
         out["flow_backend"] = FLOW_BACKEND
     return out
@@ -326,6 +486,8 @@ def to_jsonable(result: dict) -> dict:
         if isinstance(v, dict):
             return {k: conv(x) for k, x in v.items()}
         if isinstance(v, np.ndarray):
+            if v.dtype.kind == "b":
+                return [bool(x) for x in v]
             return [int(x) for x in v] if v.dtype.kind in "iu" else [_json_number(x) for x in v]
         if isinstance(v, (list, tuple)):
             return [conv(x) for x in v]
@@ -336,13 +498,17 @@ def to_jsonable(result: dict) -> dict:
 
 
 def csv_lines(result: dict):
-    """A header line, then one line per scored frame: frame, time (seconds; empty without a frame rate), then psnr,
-    ssim and sse of every method and plane."""
+    """A header line, then one line per scored frame: frame, time (seconds; empty without a frame rate), excluded
+    (0 / 1; only in a result of a scene_cut run), then psnr, ssim and sse of every method and plane."""
     cols = [(m, p) for m in result["methods"] for p in result["planes"]]
-    yield ",".join(["frame", "time"] + [f"{m}_{p}_{k}" for m, p in cols for k in ("psnr", "ssim", "sse")])
+    excluded = result.get("excluded")
+    yield ",".join(["frame", "time"] + (["excluded"] if excluded is not None else [])
+                   + [f"{m}_{p}_{k}" for m, p in cols for k in ("psnr", "ssim", "sse")])
     fps = result["fps"]
     for j, f in enumerate(result["scored_frames"]):
         row = [str(int(f)), "" if fps is None else repr(int(f) * fps[1] / fps[0])]
+        if excluded is not None:
+            row.append(str(int(excluded[j])))
         for m, p in cols:
             a = result["per_frame"][m][p]
             row += [repr(float(a["psnr"][j])), repr(float(a["ssim"][j])), str(int(a["sse"][j]))]
@@ -351,8 +517,12 @@ def csv_lines(result: dict):
 
 def summary_table(result: dict) -> str:
     mw = max([8] + [len(m) + 1 for m in result["methods"]])   # the method column fits "optical_flow"
+    left_out = ""
+    if "excluded" in result:
+        n_cuts = len(result["cut_intervals"])
+        left_out = f", {int(np.sum(result['excluded']))} left out at {n_cuts} scene cut{'' if n_cuts == 1 else 's'}"
     lines = [f"{result['frames']} frames, {len(result['scored_frames'])} held out ({result['triplets']}), "
-             f"{result['bits']}-bit, peak {result['peak']}",
+             f"{result['bits']}-bit, peak {result['peak']}{left_out}",
              f"{'method':<{mw}}{'plane':<6}{'PSNR mean':>11}{'std':>8}{'min':>9}{'max':>9}{'of mean MSE':>13}"
              f"{'SSIM mean':>11}{'min':>9}{'identical':>11}"]
     for m in result["methods"]:

@@ -6,7 +6,9 @@ float64 tensors, one value per [H, W] plane.  No CPU fallback.
 
 `psnr_planes` / `ssim_planes` are the same two metrics on planes WHERE THEY LIE - any row stride, one stride over the
 leading dimensions, uint8 or 10-bit codes in 16-bit words (peak 1023) - for hold-out scoring of video (holdout.py,
-DESIGN.md 3.3k): the Y, U and V planes of packed 4:2:0 rows are scored without a copy.
+DESIGN.md 3.3k): the Y, U and V planes of packed 4:2:0 rows are scored without a copy.  Interleaved samples (DESIGN.md
+3.3o: U V of NV12, the bytes of packed RGB, uyvy422 / yuyv422) are scored where they lie too: `psnr_interleaved` gives
+every component of [..., H, W, S] rows in one pass, `ssim_planes` takes a last-dimension stride of 1..4.
 
 Also here: the reference's OTHER SSIM, the Gaussian-window one of its training loss
 (model/train.py:18-87: `SSIMLoss`, `CombinedLoss`) - the only SSIM in the reference that is pure torch,
@@ -61,39 +63,51 @@ def ssim_u8(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _run("fiunet_ssim_u8", pred, target)
 
 
-def _plane_layout(t: torch.Tensor, name: str):
-    """[..., H, W] -> (image stride, row pitch) in samples, as the tensor lies: no copy.  The leading dimensions must
-    advance by one stride (a stack, every second frame of one, channel c of [N, C, H, W], a slice of packed rows)."""
+def _stepped_layout(t: torch.Tensor, name: str, max_step: int):
+    """[..., H, W] -> (image stride, row pitch, sample step) in samples, as the tensor lies: no copy.  The leading
+    dimensions must advance by one stride (a stack, every second frame of one, channel c of [N, C, H, W], a slice of
+    packed rows); the last dimension has a stride of 1..max_step (above 1: one component of interleaved samples)."""
     h, w = t.shape[-2:]
     st = t.stride()
-    if w > 1 and st[-1] != 1:
-        raise ValueError(f"{name}: the last dimension must have stride 1 (strides {tuple(st)})")
-    pitch = st[-2] if h > 1 else w
+    step = st[-1] if w > 1 else 1
+    if not 1 <= step <= max_step:
+        raise ValueError(f"{name}: the last dimension must have stride 1{f'..{max_step}' if max_step > 1 else ''} "
+                         f"(strides {tuple(st)})")
+    row = (w - 1) * step + 1
+    pitch = st[-2] if h > 1 else row
     lead = [(n, s) for n, s in zip(t.shape[:-2], st[:-2]) if n != 1]
     for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
         if s0 != s1 * n1:
             raise ValueError(f"{name}: the leading dimensions must advance by one stride (shape {tuple(t.shape)}, "
                              f"strides {tuple(st)})")
-    return (lead[-1][1] if lead else (h - 1) * pitch + w), pitch
+    return (lead[-1][1] if lead else (h - 1) * pitch + row), pitch, step
 
 
-def _plane_args(pred: torch.Tensor, target: torch.Tensor, bits: int):
+def _plane_layout(t: torch.Tensor, name: str):
+    """`_stepped_layout` of a plane whose last dimension has stride 1 -> (image stride, row pitch)."""
+    return _stepped_layout(t, name, 1)[:2]
+
+
+def _plane_args(pred: torch.Tensor, target: torch.Tensor, bits: int, max_step: int = 1, tail: int = 2):
+    """tail: the trailing dimensions of one image (2: [H, W]; 3: [H, W, S] interleaved)."""
     if bits not in (8, 10):
         raise ValueError(f"bits must be 8 or 10, got {bits!r}")
-    if pred.shape != target.shape or pred.dim() < 2:
-        raise ValueError(f"expected two tensors of equal shape [..., H, W], got {tuple(pred.shape)} and "
-                         f"{tuple(target.shape)}")
+    if pred.shape != target.shape or pred.dim() < tail:
+        raise ValueError(f"expected two tensors of equal shape [..., H, W{', S' if tail == 3 else ''}], got "
+                         f"{tuple(pred.shape)} and {tuple(target.shape)}")
     ok = (torch.uint8,) if bits == 8 else (torch.uint16, torch.int16)
     if pred.dtype not in ok or target.dtype not in ok:
         raise ValueError(f"{bits}-bit planes are {' or '.join(str(d) for d in ok)} tensors, got {pred.dtype} and "
                          f"{target.dtype}")
     if not pred.is_cuda or not target.is_cuda or pred.device != target.device:
         raise RuntimeError("device metrics need CUDA/HIP tensors on one device; there is no CPU fallback here")
+    if tail == 3:
+        return None
     h, w = pred.shape[-2:]
     if h < 1 or w < 1:
         raise ValueError(f"empty planes {tuple(pred.shape)}")
     n = pred.numel() // (h * w)
-    return n, h, w, _plane_layout(pred, "pred"), _plane_layout(target, "target")
+    return n, h, w, _stepped_layout(pred, "pred", max_step), _stepped_layout(target, "target", max_step)
 
 
 def _plane_workspace(n, h, w, device):
@@ -109,7 +123,7 @@ def psnr_planes(pred: torch.Tensor, target: torch.Tensor, bits: int, *, return_s
     stride and any single stride of the leading dimensions go to the kernel as they are (no `.contiguous()`).
     -> float64 [...]; with return_sse also the exact sums of squared differences, int64 [...] (the bits of the
     library's uint64)."""
-    n, h, w, (ps, pp), (ts, tp) = _plane_args(pred, target, bits)
+    n, h, w, (ps, pp, _), (ts, tp, _) = _plane_args(pred, target, bits)
     lead = pred.shape[:-2]
     out = torch.empty(n, dtype=torch.float64, device=pred.device)
     sse = torch.empty(n, dtype=torch.int64, device=pred.device) if return_sse else None
@@ -123,10 +137,55 @@ def psnr_planes(pred: torch.Tensor, target: torch.Tensor, bits: int, *, return_s
     return (out.view(lead), sse.view(lead)) if return_sse else out.view(lead)
 
 
+def _interleaved_layout(t: torch.Tensor, name: str):
+    """[..., H, W, S] -> (image stride, row pitch) in samples: stride 1 over S, S over W, anything over the rows."""
+    h, w, comp = t.shape[-3:]
+    st = t.stride()
+    if st[-1] != 1 or (w > 1 and st[-2] != comp):
+        raise ValueError(f"{name}: interleaved samples have stride 1 in the last dimension and S = {comp} in the one "
+                         f"before it (strides {tuple(st)})")
+    pitch = st[-3] if h > 1 else w * comp
+    lead = [(n, s) for n, s in zip(t.shape[:-3], st[:-3]) if n != 1]
+    for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
+        if s0 != s1 * n1:
+            raise ValueError(f"{name}: the leading dimensions must advance by one stride (shape {tuple(t.shape)}, "
+                             f"strides {tuple(st)})")
+    return (lead[-1][1] if lead else (h - 1) * pitch + w * comp), pitch
+
+
+def psnr_interleaved(pred: torch.Tensor, target: torch.Tensor, bits: int, *, return_sse: bool = False):
+    """PSNR of every component of interleaved device tensors [..., H, W, S], S in {2, 3, 4}, where they lie, in ONE pass
+    over the samples (fiunet_interleaved_psnr): the last dimension has stride 1, the W dimension stride S, the rows and
+    the leading dimensions as for `psnr_planes`.  -> float64 [..., S]; with return_sse also int64 [..., S].  Component c
+    is, to the last bit, `psnr_planes` of a contiguous copy of `[..., c]`."""
+    if pred.dim() >= 3 and pred.shape[-1] not in (2, 3, 4):
+        raise ValueError(f"interleaved samples have 2, 3 or 4 components, got {pred.shape[-1]} (shape "
+                         f"{tuple(pred.shape)})")
+    _plane_args(pred, target, bits, tail=3)
+    h, w, comp = pred.shape[-3:]
+    if h < 1 or w < 1:
+        raise ValueError(f"empty planes {tuple(pred.shape)}")
+    n = pred.numel() // (h * w * comp)
+    (ps, pp), (ts, tp) = _interleaved_layout(pred, "pred"), _interleaved_layout(target, "target")
+    lead = pred.shape[:-3] + (comp,)
+    out = torch.empty(n * comp, dtype=torch.float64, device=pred.device)
+    sse = torch.empty(n * comp, dtype=torch.int64, device=pred.device) if return_sse else None
+    if n:
+        ws, nbytes = _plane_workspace(n * comp, h, w, pred.device)
+        with torch.cuda.device(pred.device):
+            s = torch.cuda.current_stream(pred.device).cuda_stream
+            _native.check(_native.lib().fiunet_interleaved_psnr(
+                pred.data_ptr(), ps, pp, target.data_ptr(), ts, tp, bits, comp, n, h, w, out.data_ptr(),
+                None if sse is None else sse.data_ptr(), ws.data_ptr(), ctypes.c_size_t(nbytes), s),
+                "fiunet_interleaved_psnr")
+    return (out.view(lead), sse.view(lead)) if return_sse else out.view(lead)
+
+
 def ssim_planes(pred: torch.Tensor, target: torch.Tensor, bits: int) -> torch.Tensor:
-    """SSIM (skimage's defaults, data_range = the peak) of every [H, W] plane where it lies (fiunet_plane_ssim); the
-    arguments are `psnr_planes`'; H, W >= 7.  -> float64 [...]."""
-    n, h, w, (ps, pp), (ts, tp) = _plane_args(pred, target, bits)
+    """SSIM (skimage's defaults, data_range = the peak) of every [H, W] plane where it lies (fiunet_stepped_ssim);
+    the arguments are `psnr_planes`', and the last dimension may have a stride of 1..4 on either side (the view
+    `t[..., c]` of interleaved [..., H, W, S]); H, W >= 7.  -> float64 [...]."""
+    n, h, w, (ps, pp, pstep), (ts, tp, tstep) = _plane_args(pred, target, bits, max_step=4)
     if h < 7 or w < 7:
         raise ValueError(f"SSIM: the 7x7 window exceeds the {h}x{w} plane")
     out = torch.empty(n, dtype=torch.float64, device=pred.device)
@@ -134,9 +193,9 @@ def ssim_planes(pred: torch.Tensor, target: torch.Tensor, bits: int) -> torch.Te
         ws, nbytes = _plane_workspace(n, h, w, pred.device)
         with torch.cuda.device(pred.device):
             s = torch.cuda.current_stream(pred.device).cuda_stream
-            _native.check(_native.lib().fiunet_plane_ssim(
-                pred.data_ptr(), ps, pp, target.data_ptr(), ts, tp, bits, n, h, w, out.data_ptr(), ws.data_ptr(),
-                ctypes.c_size_t(nbytes), s), "fiunet_plane_ssim")
+            _native.check(_native.lib().fiunet_stepped_ssim(
+                pred.data_ptr(), ps, pp, pstep, target.data_ptr(), ts, tp, tstep, bits, n, h, w, out.data_ptr(),
+                ws.data_ptr(), ctypes.c_size_t(nbytes), s), "fiunet_stepped_ssim")
     return out.view(pred.shape[:-2])
 
 

@@ -35,7 +35,9 @@ extern "C" {
                                      workspace query); v8 also, added the same way: PSNR / SSIM on strided 8- and 10-bit
                                      planes (fiunet_plane_psnr, fiunet_plane_ssim and their workspace query); v8 also, added
                                      the same way: Farneback flow and flow-compensated warps (fiunet_flow_workspace_bytes,
-                                     fiunet_farneback_flow, fiunet_flow_warp, fiunet_flow_mode) */
+                                     fiunet_farneback_flow, fiunet_flow_warp, fiunet_flow_mode); v8 also, added the same
+                                     way: the plane metrics on interleaved samples (fiunet_interleaved_psnr,
+                                     fiunet_stepped_ssim) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -503,6 +505,34 @@ int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_ro
                       const void* target, size_t target_image_stride, size_t target_row_pitch,
                       int bits, int images, int H, int W, double* out_ssim,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* The plane metrics on INTERLEAVED samples (hold-out scoring of raw video: U V of NV12, the bytes of packed RGB, the
+ * byte positions of uyvy422 / yuyv422), with the depths, peaks and conventions of the two entry points above.
+ *
+ * fiunet_interleaved_psnr: an image is H rows of W * components samples, components S in {2, 3, 4}; the sample at
+ * position p of a row belongs to component p % S.  One pass over the bytes gives all S components: out_psnr is device
+ * double[images * S], out_sse (may be NULL) device uint64[images * S], both image-major (image i, component c at
+ * i * S + c); the mean is over the H*W samples of a component.  A component's PSNR and sse are, to the last bit, what
+ * fiunet_plane_psnr gives on a contiguous copy of that component.  Strides and pitches in samples; a row pitch below
+ * W * S is refused, as is images > 1 with an image stride below (H-1) * pitch + W*S, components outside 2..4 and
+ * images * S > 65535.  workspace: fiunet_plane_metrics_workspace_bytes(images * S, H, W) (there is no size function
+ * of its own), 256-B aligned.
+ *
+ * fiunet_stepped_ssim: fiunet_plane_ssim with a sample step in {1, 2, 3, 4} on each side: sample (y, x) of an
+ * image lies at y * row_pitch + x * step.  fiunet_plane_ssim is step 1 of the same kernel.  A row pitch below
+ * (W-1) * step + 1 is refused, as is images > 1 with an image stride below (H-1) * pitch + (W-1) * step + 1.
+ * workspace: fiunet_plane_metrics_workspace_bytes(images, H, W).
+ *
+ * Both: asynchronous on `stream`, no allocation, no synchronisation; every refusal is FIUNET_ERR_INVALID_ARG before any
+ * launch and before any pointer is used. */
+int fiunet_interleaved_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch,
+                            const void* target, size_t target_image_stride, size_t target_row_pitch,
+                            int bits, int components, int images, int H, int W, double* out_psnr,
+                            unsigned long long* out_sse, void* workspace, size_t workspace_bytes, void* stream);
+int fiunet_stepped_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, int pred_step,
+                              const void* target, size_t target_image_stride, size_t target_row_pitch, int target_step,
+                              int bits, int images, int H, int W, double* out_ssim,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* The classical motion-compensated baseline of the evaluators on device: dense Farneback flow with the
  * reference's parameters (model/evaluation_simple.py:76-103: pyr_scale 0.5, 3 levels, winsize 15, 3 iterations, poly_n 5,

@@ -1,0 +1,248 @@
+"""Host side of hold-out scoring of raw video and of scene cuts in it: no GPU.
+
+  1. the plane tables of holdout.raw_planes against the restatement (tests/holdout_raw_ref.py) for every raw format,
+     and every sample of a frame in exactly one plane
+  2. the exclusion rule for sliding and disjoint triplets, cuts at the first and last interval included
+  3. refusals before any device use
+  4. the text forms of a result with the scene-cut fields
+  5. the `evaluate` command's new flags
+  6. the synthetic cut clip flags exactly one interval at threshold 10 (tests/scene_ref.py)
+"""
+import io
+import os
+import re
+import sys
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import holdout_raw_ref as R  # noqa: E402
+import scene_ref as S  # noqa: E402
+
+import ai_based_frame_interpolation_amd as P  # noqa: E402
+from ai_based_frame_interpolation_amd import _native, cli, holdout, metrics, stream  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+H, W = 23, 35
+
+
+def _size(fmt):
+    return (H, W - 1) if fmt in R.CAPTURE else (H, W)
+
+
+def test_the_restatement_names_every_raw_format():
+    assert sorted(R.FORMATS) == sorted(stream.RAW_FORMATS)
+
+
+# ---- 1. plane tables --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", sorted(R.FORMATS))
+def test_plane_table_against_the_restatement(fmt):
+    h, w = _size(fmt)
+    planes, groups = holdout.raw_planes(fmt, h, w)
+    want = R.plane_indices(fmt, h, w)
+    assert [p[0] for p in planes] == list(want) == list(R.FORMATS[fmt][1])
+    n = R.frame_samples(fmt, h, w)
+    seen = np.zeros(n, np.int64)
+    for name, off, ph, pw, pitch, step in planes:
+        got = off + np.arange(ph)[:, None] * pitch + np.arange(pw)[None, :] * step
+        assert np.array_equal(got, want[name]), name
+        np.add.at(seen, got.ravel(), 1)
+    assert (seen == 1).all()   # every sample of the frame belongs to exactly one plane
+    # an interleaved group: component c of the [h, w, S] view is the plane that names it
+    for comp, off, gh, gw, pitch, names in groups:
+        view = off + np.arange(gh)[:, None, None] * pitch + np.arange(gw)[None, :, None] * comp + np.arange(comp)
+        assert view.max() < n and comp in (2, 3, 4)
+        for name, c in names.items():
+            assert np.array_equal(view[:, :, c], want[name]), (name, c)
+    grouped = {name for g in groups for name in g[5]}
+    assert grouped == {p[0] for p in planes if p[5] != 1}   # exactly the stepped planes go through a group
+
+
+def test_plane_table_frame_size_is_the_routes():
+    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3)
+    for fmt in R.FORMATS:
+        h, w = _size(fmt)
+        route = stream._raw_route(m, fmt, h, w, False, 8, "bt709", None)
+        assert route.row == R.frame_samples(fmt, h, w) and route.bits == R.FORMATS[fmt][0]
+
+
+def test_existing_sources_keep_pitch_w_and_step_1():
+    src = holdout._Source(None, None, [("y", 0, 4, 6), ("u", 24, 2, 3)], 0, None, lambda: None)
+    assert src.planes == [("y", 0, 4, 6, 6, 1), ("u", 24, 2, 3, 3, 1)] and src.groups == [] and src.lead == ("y",)
+    rows = torch.arange(2 * 40, dtype=torch.uint8).reshape(2, 40)
+    y, u = holdout._plane_views(rows[:, 2:], src)
+    assert torch.equal(y, rows[:, 2:26].unflatten(1, (4, 6))) and torch.equal(u, rows[:, 26:32].unflatten(1, (2, 3)))
+    assert y.stride() == (40, 6, 1)
+
+
+def test_plane_and_group_views_of_strided_rows():
+    h, w = 3, 4
+    rows = torch.arange(5 * 2 * h * w, dtype=torch.uint8).reshape(5, -1)[1::2]   # every second frame of a uyvy422 stack
+    planes, groups = holdout.raw_planes("uyvy422", h, w)
+    src = holdout._Source(None, None, planes, 0, None, lambda: None, groups, ("y",))
+    want = R.plane_indices("uyvy422", h, w)
+    for (name, *_), v in zip(planes, holdout._plane_views(rows, src)):
+        assert v.data_ptr() >= rows.data_ptr() and torch.equal(v, rows[:, torch.from_numpy(want[name])]), name
+    g2, g4 = holdout._group_views(rows, src)
+    assert g2.shape == (2, h, w, 2) and g4.shape == (2, h, w // 2, 4) and g2.stride() == (4 * h * w, 2 * w, 2, 1)
+    assert torch.equal(g2[..., 1], rows[:, torch.from_numpy(want["y"])])
+    assert torch.equal(g4[..., 2], rows[:, torch.from_numpy(want["v"])])
+
+
+def test_stepped_layouts_of_metrics():
+    t = torch.zeros((2, 9, 11, 3), dtype=torch.uint8)
+    assert metrics._stepped_layout(t[..., 1], "a", 4) == (297, 33, 3)
+    assert metrics._stepped_layout(t[0, :, :, 2], "a", 4) == (8 * 33 + 31, 33, 3)
+    assert metrics._interleaved_layout(t, "a") == (297, 33)
+    assert metrics._interleaved_layout(t[:, 1:8], "a") == (297, 33)
+    with pytest.raises(ValueError, match="stride 1..4"):
+        metrics._stepped_layout(torch.zeros((2, 9, 11, 5), dtype=torch.uint8)[..., 0], "a", 4)
+    with pytest.raises(ValueError, match="interleaved samples"):
+        metrics._interleaved_layout(t.permute(0, 1, 3, 2), "a")
+    with pytest.raises(ValueError, match="2, 3 or 4"):
+        metrics.psnr_interleaved(torch.zeros((2, 9, 11, 5), dtype=torch.uint8), torch.zeros((2, 9, 11, 5), dtype=torch.uint8), 8)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        metrics.psnr_interleaved(t, t, 8)
+
+
+# ---- 2. the exclusion rule ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cuts,sliding,disjoint", [
+    ([5], [5, 6], [5]), ([0], [1], [1]), ([10], [10], []), ([0, 10], [1, 10], [1]), ([], [], []),
+    ([3, 4], [3, 4, 5], [3, 5]), ([6], [6, 7], [7])])
+def test_exclusion_arithmetic(cuts, sliding, disjoint):
+    n = 12
+    flags = np.zeros(n - 1, np.uint8)
+    flags[cuts] = 1
+    for triplets, want in (("sliding", sliding), ("disjoint", disjoint)):
+        targets = [t for span in holdout.chunk_spans(n, 4, triplets) for t in span[2]]
+        got = holdout.excluded_targets(flags, targets)
+        assert got.dtype == bool and np.array_equal(got, R.excluded(flags, targets))
+        assert [t for t, e in zip(targets, got) if e] == want, triplets
+
+
+def test_all_excluded_summary_is_nan_without_a_warning():
+    a = {"psnr": np.array([30.0, 31.0]), "ssim": np.array([0.9, 0.8]), "sse": np.array([5, 0], np.uint64)}
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        s = holdout._kept_stats(a, np.zeros(2, bool), 100, 255)
+        part = holdout._kept_stats(a, np.array([True, False]), 100, 255)
+        empty = holdout.excluded_targets(np.zeros(3, np.uint8), [])
+    assert list(s) == list(holdout.STATS) and s["identical_frames"] == 0
+    assert all(np.isnan(v) for k, v in s.items() if k != "identical_frames")
+    assert part == holdout._stats(a["psnr"][:1], a["ssim"][:1], a["sse"][:1], 100, 255) and part["average_psnr"] == 30.0
+    assert holdout._kept_stats(a, None, 100, 255) == holdout._stats(a["psnr"], a["ssim"], a["sse"], 100, 255)
+    assert empty.shape == (0,)
+
+
+# ---- 3. refusals before any device use ------------------------------------------------------------------------------------
+@pytest.fixture
+def no_gpu(monkeypatch):
+    def boom(*a, **k):
+        raise AssertionError("GPU work started before the arguments were checked")
+    monkeypatch.setattr(holdout, "_score_chunk", boom)
+    monkeypatch.setattr(holdout.scene, "pair_sad", boom)
+    monkeypatch.setattr(torch.Tensor, "pin_memory", boom)
+
+
+def test_refusals_come_before_any_device_use(tmp_path, no_gpu):
+    rgb, gray = (P.FrameInterpolationUNet(bilinear=True, frame_channels=c) for c in (3, 1))
+    np.save(tmp_path / "clip.npy", np.zeros((5, H, W, 3), np.uint8))
+    raw = tmp_path / "clip.raw"
+    raw.write_bytes(bytes(3 * H * W * 3))
+    with pytest.raises(ValueError, match=r"\.npy"):
+        holdout.score_video(rgb, str(tmp_path / "clip.npy"), raw="rgb24", width=W, height=H)
+    with pytest.raises(ValueError, match="missing: height"):
+        holdout.score_video(rgb, str(raw), raw="rgb24", width=W)
+    with pytest.raises(ValueError, match="missing: width"):
+        holdout.score_video(rgb, io.BytesIO(b""), raw="nv12", height=H)
+    with pytest.raises(ValueError, match="raw must be one of"):
+        holdout.score_video(rgb, str(raw), raw="yuv420p", width=W, height=H)
+    with pytest.raises(ValueError, match="grayscale"):
+        holdout.score_video(gray, str(raw), raw="rgb24", width=W, height=H)
+    with pytest.raises(ValueError, match="even width"):
+        holdout.score_video(rgb, str(raw), raw="uyvy422", width=W, height=H)
+    with pytest.raises(ValueError, match="describe raw video"):
+        holdout.score_video(rgb, str(tmp_path / "clip.npy"), width=W, height=H)
+    for bad in (0, -1, 101, float("nan"), True, "10"):
+        with pytest.raises(ValueError, match="scene_cut"):
+            holdout.score_video(rgb, str(raw), raw="rgb24", width=W, height=H, scene_cut=bad)
+        with pytest.raises(ValueError, match="scene_cut"):
+            holdout.score_video(rgb, str(tmp_path / "clip.npy"), scene_cut=bad)
+    two = tmp_path / "two.raw"
+    two.write_bytes(bytes(2 * H * W * 3))
+    with pytest.raises(ValueError, match="at least 3 frames"):
+        holdout.score_video(rgb, str(two), raw="rgb24", width=W, height=H)
+    part = tmp_path / "part.raw"
+    part.write_bytes(bytes(3 * H * W * 3 + 1))
+    with pytest.raises(ValueError, match="whole number"):
+        holdout.score_video(rgb, str(part), raw="rgb24", width=W, height=H)
+    with pytest.raises(FileNotFoundError):
+        holdout.score_video(rgb, str(tmp_path / "none.raw"), raw="rgb24", width=W, height=H)
+
+
+# ---- 4. the result as text --------------------------------------------------------------------------------------------------
+def _result(with_cut):
+    per = {"psnr": np.array([30.0, 10.0, 11.0]), "ssim": np.array([0.9, 0.2, 0.3]), "sse": np.array([7, 900, 800], np.uint64)}
+    res = {"frames": 5, "triplets": "sliding", "bits": 8, "peak": 255, "planes": ["r"], "methods": ["linear"],
+           "fps": (24, 1), "scored_frames": np.array([1, 2, 3]), "per_frame": {"linear": {"r": per}},
+           "summary": {"linear": {"r": holdout._kept_stats(per, np.array([True, False, False]) if with_cut else None, 805, 255)}}}
+    if with_cut:
+        res.update({"scene_cut": 10.0, "scene_scores": np.array([0.5, 40.0, 0.25, 0.5]), "cut_intervals": np.array([1]),
+                    "excluded_frames": np.array([2, 3]), "excluded": np.array([False, True, True])})
+    return res
+
+
+def test_csv_and_table_with_and_without_the_mask():
+    plain, cut = _result(False), _result(True)
+    lines = list(holdout.csv_lines(plain))
+    assert lines[0] == "frame,time,linear_r_psnr,linear_r_ssim,linear_r_sse" and lines[1].startswith("1,")
+    lines = list(holdout.csv_lines(cut))
+    assert lines[0] == "frame,time,excluded,linear_r_psnr,linear_r_ssim,linear_r_sse"
+    assert [l.split(",")[2] for l in lines[1:]] == ["0", "1", "1"] and lines[2].split(",")[3] == "10.0"
+    assert holdout.summary_table(plain).splitlines()[0] == "5 frames, 3 held out (sliding), 8-bit, peak 255"
+    assert holdout.summary_table(cut).splitlines()[0] == ("5 frames, 3 held out (sliding), 8-bit, peak 255, 2 left out at "
+                                                         "1 scene cut")
+    j = holdout.to_jsonable(cut)
+    assert j["excluded"] == [False, True, True] and j["cut_intervals"] == [1] and j["scene_cut"] == 10.0
+    assert j["summary"]["linear"]["r"]["average_psnr"] == 30.0 and "excluded" not in holdout.to_jsonable(plain)
+
+
+# ---- 5. the command line ------------------------------------------------------------------------------------------------------
+def test_cli_evaluate_flags():
+    a = cli.parse_args(["evaluate", "--input", "-", "--raw", "nv12", "--size", "1920x1080", "--src-fps", "24", "--model",
+                        "rgb_model.pth", "--scene-cut", "10", "--json", "scores.json"])
+    assert (a.raw, a.size, a.scene_cut, a.json) == ("nv12", (1920, 1080), 10.0, "scores.json") and a.src_fps == 24
+    a = cli.parse_args(["evaluate", "--input", "clip.y4m"])
+    assert a.raw is None and a.size is None and a.scene_cut is None
+    assert cli.parse_args(["evaluate", "--input", "c.y4m", "--scene-cut", "none"]).scene_cut is None
+    for fmt in stream.RAW_FORMATS:
+        assert cli.parse_args(["evaluate", "--input", "-", "--raw", fmt, "--size", "34x23"]).raw == fmt
+        assert cli.parse_args(["video", "--input", "-", "--output", "-", "--raw", fmt, "--size", "34x23", "--src-fps",
+                               "24"]).raw == fmt
+    for bad in (["--raw", "rgb24"], ["--size", "35x23"], ["--raw", "yuv420p", "--size", "35x23"],
+                ["--raw", "rgb24", "--size", "35"]):
+        with pytest.raises(SystemExit):
+            cli.parse_args(["evaluate", "--input", "-"] + bad)
+
+
+def test_header_and_binding_name_the_new_entry_points():
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fiunet.h")).read(), flags=re.S)
+    for name in ("fiunet_interleaved_psnr", "fiunet_stepped_ssim"):
+        assert re.search(rf"\b{name}\s*\(", src) and name in _native.SYMBOLS
+        assert name in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+
+
+# ---- 6. the cut clip ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["npy", "i420", "nv12", "rgb24"])
+def test_the_cut_clip_flags_exactly_interval_5(kind):
+    clip = R.cut_clip(kind, H, W)
+    assert clip.shape[0] == 12
+    scores, flags = S.detect(clip.reshape(12, -1), 10.0)
+    print(kind, np.round(scores, 2).tolist())
+    assert np.flatnonzero(flags).tolist() == [5]
+    assert scores[5] > 20.0 and np.delete(scores, 5).max() < 5.0   # far from the threshold on both sides
+    if kind == "nv12":   # the same samples as the I420 rows, in another order: the same sums
+        assert np.array_equal(S.pair_sad(clip), S.pair_sad(R.cut_clip("i420", H, W)))

@@ -1,0 +1,202 @@
+"""Time the metrics on interleaved samples and hold-out scoring of raw video, in one process.
+
+  psnr      fiunet_interleaved_psnr on B images of H x W x S interleaved uint8 samples, S = 2, 3, 4 (B = 8, 1080p),
+            beside fiunet_plane_psnr on B contiguous planes of the same byte count (H x W*S), which is timed as two
+            cases (`_a`, `_b`): the difference between them is the run-to-run spread of this job.  Bytes moved: both
+            sides, once.
+  ssim      fiunet_stepped_ssim on B planes of H x W at sample steps 2, 3, 4 (component 0 of the interleaved images)
+            beside step 1 on contiguous planes (fiunet_plane_ssim, timed twice).  The bytes a plane's SSIM needs are
+            those of step 1; a stepped plane drags S times as many through the caches.
+            Through the C ABI with the workspace and the results allocated once; the calls rotate over a set of pred /
+            target pairs of at least `--set-gb` GB at S = 2 (several times the 256 MB Infinity Cache), so nothing comes
+            from a cache.  Device time from HIP events around `--iters` back-to-back calls after `--warmup` calls;
+            `--reps` repetitions interleaved over the cases; median and spread.
+  score     `holdout.score_video` of one `--clip-frames`-frame 1080p moving texture, sliding triplets, the default three
+            methods, RGB network at bf16, default chunk_frames: as C420jpeg Y4M (the yardstick of tools/holdout_timing.py),
+            as tight NV12 of the same planes, and as rgb24; wall time behind a device synchronise after a warm-up run,
+            scored frames per second.
+One JSON line last.
+
+    python tools/holdout_raw_timing.py [--batch 8 --set-gb 1 --iters 200 --reps 7 --clip-frames 65]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import ai_based_frame_interpolation_amd as P  # noqa: E402
+from ai_based_frame_interpolation_amd import _native, holdout, imageio_lite as IO  # noqa: E402
+from oracle import unet_oracle as O  # noqa: E402
+
+
+def _time(fn, iters):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / iters
+
+
+class _Rotate:
+    """Calls fn(k) with k = 0, 1, ..., n - 1, 0, ... : each call works on the next member of a set."""
+
+    def __init__(self, fn, n):
+        self.fn, self.n, self.k = fn, n, 0
+
+    def __call__(self):
+        self.fn(self.k)
+        self.k = (self.k + 1) % self.n
+
+
+def _kernel_cases(dev, b, h, w, set_bytes):
+    """A set of (pred, target) pairs of byte buffers of b x h x w x 4 bytes; every case reads its images out of them.
+    -> (cases, bytes read per case, the buffers, info)"""
+    L = _native.lib()
+    n = h * w
+    n_set = max(2, -(-set_bytes // (2 * b * n * 2)))
+    g = torch.Generator(device=dev).manual_seed(h)
+    pairs = [tuple(torch.randint(0, 256, (b * n * 4,), dtype=torch.uint8, device=dev, generator=g) for _ in (0, 1))
+             for _ in range(n_set)]
+    nbytes = L.fiunet_plane_metrics_workspace_bytes(b * 4, h, w * 4)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(b * 4, dtype=torch.float64, device=dev)
+    sse = torch.empty(b * 4, dtype=torch.int64, device=dev)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    wp, op, sp, sz = ws.data_ptr(), out.data_ptr(), sse.data_ptr(), ctypes.c_size_t(nbytes)
+    ptr = [(p.data_ptr(), t.data_ptr()) for p, t in pairs]
+    cases, moved = {}, {}
+
+    def add(name, fn, nb):
+        cases[name], moved[name] = _Rotate(fn, n_set), nb
+
+    def planar(tag):
+        for c in (2, 3, 4):   # B contiguous planes of h x (w * c): the bytes of the S = c case
+            add(f"psnr plane {c}x_{tag}", lambda k, c=c: _native.check(L.fiunet_plane_psnr(
+                ptr[k][0], n * c, w * c, ptr[k][1], n * c, w * c, 8, b, h, w * c, op, sp, wp, sz, s), "plane_psnr"), 2 * b * n * c)
+        add(f"ssim step1_{tag}", lambda k: _native.check(L.fiunet_plane_ssim(
+            ptr[k][0], n, w, ptr[k][1], n, w, 8, b, h, w, op, wp, sz, s), "plane_ssim"), 2 * b * n)
+    planar("a")
+    for c in (2, 3, 4):
+        add(f"psnr interleaved S={c}", lambda k, c=c: _native.check(L.fiunet_interleaved_psnr(
+            ptr[k][0], n * c, w * c, ptr[k][1], n * c, w * c, 8, c, b, h, w, op, sp, wp, sz, s), "interleaved_psnr"),
+            2 * b * n * c)
+        add(f"ssim step{c}", lambda k, c=c: _native.check(L.fiunet_stepped_ssim(
+            ptr[k][0], n * c, w * c, c, ptr[k][1], n * c, w * c, c, 8, b, h, w, op, wp, sz, s), "stepped_ssim"), 2 * b * n)
+    planar("b")
+    return cases, moved, pairs, dict(batch=b, set_members=n_set, set_mb_at_s2=round(n_set * 2 * b * n * 2 / 2**20))
+
+
+def _planes(frames, h, w):
+    """A moving texture: luma and chroma drift by 2 / 1 pixels a frame (the clip of tools/holdout_timing.py)."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    cy, cx = np.mgrid[0:(h + 1) // 2, 0:(w + 1) // 2].astype(np.float32)
+    for t in range(frames):
+        y = 128 + 90 * np.sin((xx - 2 * t) / 9.0) * np.cos(yy / 13.0) + 30 * np.cos((xx - 2 * t + yy) / 5.0)
+        u = 128 + 60 * np.sin((cx - t) / 11.0 + cy / 17.0)
+        v = 128 + 60 * np.cos((cx - t) / 7.0 - cy / 19.0)
+        yield tuple(np.clip(np.rint(p), 0, 255).astype(np.uint8) for p in (y, u, v))
+
+
+def _write_clips(tmp, frames, h, w):
+    y4m, nv12, rgb = (os.path.join(tmp, n) for n in ("clip.y4m", "clip.nv12", "clip.rgb"))
+    with IO.Y4MWriter(y4m, w, h, (24, 1), "420jpeg") as wr, open(nv12, "wb") as fn, open(rgb, "wb") as fr:
+        for y, u, v in _planes(frames, h, w):
+            wr.write(np.concatenate([p.ravel() for p in (y, u, v)])[None])
+            fn.write(y.tobytes() + np.stack([u, v], axis=-1).tobytes())
+            up = lambda c: np.repeat(np.repeat(c, 2, axis=0), 2, axis=1)[:h, :w]   # noqa: E731
+            fr.write(np.stack([y, up(u), up(v)], axis=-1).tobytes())   # (three textures as R, G, B)
+    return {"y4m": (y4m, {}), "nv12": (nv12, dict(raw="nv12", width=w, height=h, src_fps=24)),
+            "rgb24": (rgb, dict(raw="rgb24", width=w, height=h, src_fps=24))}
+
+
+def _score(dev, frames, h, w):
+    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
+    m.load_state_dict(O.make_interpolating_state_dict(n_channels=6, n_classes=3))
+    m = m.to(dev).eval()
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        clips = _write_clips(tmp, frames, h, w)
+        for name, (src, kw) in clips.items():
+            holdout.score_video(m, src, chunk_frames=8, **kw)   # warm-up: code objects, the allocator's pools
+        for rep in range(2):   # the three sources interleaved, twice: the second pass shows the spread
+            for name, (src, kw) in clips.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = holdout.score_video(m, src, **kw)
+                torch.cuda.synchronize()
+                wall = time.perf_counter() - t0
+                scored = len(res["scored_frames"])
+                out.setdefault(name, dict(frames=frames, scored_frames=scored, planes=res["planes"], wall_s=[],
+                                          scored_frames_per_s=[]))
+                out[name]["wall_s"].append(round(wall, 3))
+                out[name]["scored_frames_per_s"].append(round(scored / wall, 1))
+                if rep == 0:
+                    print(f"--- {name}\n{holdout.summary_table(res)}", flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--set-gb", type=float, default=1.0, help="least size of the rotating set of pairs at S = 2")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--shape", default="1080x1920")
+    ap.add_argument("--clip-frames", type=int, default=65)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "holdout_raw_timing measures on the GPU; there is no CPU path"
+    dev = torch.device("cuda:0")
+    h, w = (int(v) for v in a.shape.split("x"))
+    res = {"protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of {a.iters} "
+                       f"calls rotating over a set of at least {a.set_gb} GB"}
+    cases, moved, pairs, info = _kernel_cases(dev, a.batch, h, w, int(a.set_gb * 1e9))
+    for fn in cases.values():
+        for _ in range(a.warmup):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in cases}
+    for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
+        for k, fn in cases.items():
+            ms[k].append(_time(fn, a.iters))
+    leg = dict(info)
+    for k in cases:
+        med = statistics.median(ms[k])
+        leg[k] = dict(ms=round(med, 5), spread_ms=[round(min(ms[k]), 5), round(max(ms[k]), 5)],
+                      gb_per_s=round(moved[k] / (med * 1e-3) / 1e9, 1))
+        print(f"{a.batch}x{h}x{w} {k:24s} {med:8.5f} ms  (reps {min(ms[k]):.5f}-{max(ms[k]):.5f})  "
+              f"{leg[k]['gb_per_s']:7.1f} GB/s", flush=True)
+    for c in (2, 3, 4):
+        ta, tb = leg[f"psnr plane {c}x_a"]["ms"], leg[f"psnr plane {c}x_b"]["ms"]
+        leg[f"psnr S={c} yardstick_spread"] = round(abs(ta - tb) / min(ta, tb), 4)
+        leg[f"psnr S={c} time_vs_plane"] = round(leg[f"psnr interleaved S={c}"]["ms"] / max(ta, tb), 3)
+        print(f"psnr S={c}: in-job spread of the planar yardstick {leg[f'psnr S={c} yardstick_spread']:.4f}; interleaved / "
+              f"planar time {leg[f'psnr S={c} time_vs_plane']:.3f}", flush=True)
+    ta, tb = leg["ssim step1_a"]["ms"], leg["ssim step1_b"]["ms"]
+    leg["ssim yardstick_spread"] = round(abs(ta - tb) / min(ta, tb), 4)
+    for c in (2, 3, 4):
+        leg[f"ssim step{c} time_vs_step1"] = round(leg[f"ssim step{c}"]["ms"] / max(ta, tb), 3)
+    print(f"ssim: in-job spread of step 1 {leg['ssim yardstick_spread']:.4f}; step 2 / 3 / 4 over step 1 "
+          + " / ".join(f"{leg[f'ssim step{c} time_vs_step1']:.3f}" for c in (2, 3, 4)), flush=True)
+    res["kernels"] = leg
+    del cases, pairs
+    torch.cuda.empty_cache()
+    res["score_video"] = _score(dev, a.clip_frames, h, w)
+    print("score_video:", res["score_video"], flush=True)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
