@@ -519,9 +519,13 @@ struct PlanBuf { int kind, index; size_t bytes; int first, last; size_t* off; };
 // both figures).  FIUNET_OPT_KEEP_ALL (the debug read-back) pins every activation to the end (17.0 GB there); the ablation
 // path adds its concat scratch; the fused stem / fused head leave activations 0 / 17 out altogether.
 // `placed` (diagnostic): receives the buffers in placement order, their `off` pointing into `p`.
+// g_plan_refusal: why the last make_plan on this thread answered false.
+thread_local const char* g_plan_refusal = "";
 bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p, std::vector<PlanBuf>* placed = nullptr)
 {
+    g_plan_refusal = "B must be >= 1, H and W >= 16 (four 2x2 max-pools)";
     if (B < 1 || H < 16 || W < 16) return false;
+    g_plan_refusal = "H*W must be below 2^26 pixels per call: cut taller frames into bands (fiunet_forward_strip)";
     // the kernels address a pixel record inside one image plane with 32 bits: H*W*64 B < 4 GiB.
     // Larger frames go through fiunet_forward_strip band by band.
     if ((long long)H * W >= (1LL << 26)) return false;
@@ -530,6 +534,16 @@ bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p, st
     const size_t es = two_byte_elems(precision) ? 2 : 4;   // bytes per activation element (bf16x2: two pieces)
     p.hs[0] = H; p.ws[0] = W;
     for (int k = 1; k < 5; ++k) { p.hs[k] = p.hs[k - 1] / 2; p.ws[k] = p.ws[k - 1] / 2; }
+    // a materialised upsampled half is written by a grid of (row chunks, H / UPS_ROWS, B * planes): a shape whose grid.y or
+    // grid.z would pass the 65535 of the launch is refused here, before any stage of a forward runs
+    for (int i = 1; i < NCONV; ++i)
+        if (p.st[i].form == FORM_CONCAT_UP &&
+            ((p.hs[kLevel[i]] + UPS_ROWS - 1) / UPS_ROWS > 65535 ||
+             (long long)B * (n.cout[kSrc1[i]] / (precision == FIUNET_FP32 ? 16 : 32)) > 65535)) {
+            g_plan_refusal = "upsample grid too large: cut the frame into shorter bands (fiunet_forward_strip) or the batch "
+                             "into smaller ones";
+            return false;
+        }
     using Buf = PlanBuf;
     std::vector<Buf> bufs;
     const int END = NCONV;  // "still live after the last conv" (the unfused head, the debug read-back)
@@ -838,7 +852,7 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
             } else if (st.form == FORM_CONCAT_UP) {   // two full-resolution sources: skip planes, then these
                 const dim3 grid((unsigned)((a.W * 4 + 255) / 256), (unsigned)((a.H + UPS_ROWS - 1) / UPS_ROWS),
                                 (unsigned)(B * (a.C1 / Elem<T>::PL)));
-                if (grid.y > 65535u || grid.z > 65535u) return fail(FIUNET_ERR_INVALID_ARG, "upsample grid too large");
+                // (grid.y, grid.z <= 65535: make_plan refuses a shape that would pass it)
                 if (x2)
                     hipLaunchKernelGGL(x2_upsample_kernel, grid, dim3(256), 0, s, a, up);
                 else
@@ -1311,6 +1325,7 @@ size_t fiunet_workspace_bytes(const fiunet_ctx* ctx, int B, int H, int W, int pr
     Plan p;
     if (!ctx_plan(ctx, B, H, W, precision, p)) {
         g_err = "fiunet_workspace_bytes: bad arguments";
+        if (ctx && valid_precision(precision)) g_err += std::string(" (") + g_plan_refusal + ")";
         return 0;
     }
     return p.total;
@@ -1341,8 +1356,7 @@ int fiunet_forward_strip(fiunet_ctx* ctx, const float* frame1, const float* fram
         return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
     Plan p;
     if (!make_plan(net_of(ctx), B, H, W, precision, p))
-        return fail(FIUNET_ERR_BAD_SHAPE, "H*W must be below 2^26 pixels per call: cut taller frames into "
-                                          "bands (fiunet_forward_strip)");
+        return fail(FIUNET_ERR_BAD_SHAPE, g_plan_refusal);
     if (workspace_bytes < p.total) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2656,7 +2670,8 @@ int fiunet_debug_plan(int frame_channels, int bilinear, unsigned flags, int prec
     n.stem_w = frame_channels == 1;
     Plan p;
     std::vector<PlanBuf> bufs;
-    if (!make_plan(n, B, H, W, precision, p, &bufs)) return fail(FIUNET_ERR_BAD_SHAPE, "fiunet_debug_plan: bad shape");
+    if (!make_plan(n, B, H, W, precision, p, &bufs))
+        return fail(FIUNET_ERR_BAD_SHAPE, std::string("fiunet_debug_plan: bad shape: ") + g_plan_refusal);
     *n_records = (int)bufs.size();
     *total = p.total;
     if (bufs.size() > (size_t)capacity)

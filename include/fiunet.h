@@ -136,7 +136,10 @@ int fiunet_load_weights_device(fiunet_ctx* ctx, int n, const char* const* names,
  * whatever dtype the module's tensors have (model/inference.py:96). */
 int fiunet_prepare_precision(fiunet_ctx* ctx, int precision);
 
-/* Bytes of device scratch fiunet_forward needs for a [B,*,H,W] batch; 0 on bad arguments.
+/* Bytes of device scratch fiunet_forward needs for a [B,*,H,W] batch; 0 on bad arguments and for a shape no forward
+ * takes (fiunet_last_error_string says which: H or W below 16, 2^26 pixels or more, or a materialised upsample whose
+ * launch grid would pass 65535 - bf16x2 frames taller than 524 280 rows, batches of 4096 and more): the shape is refused
+ * here, where the plan is made, and a forward of it launches nothing.
  * Activations whose lifetimes do not overlap share bytes (the reference, under no_grad, frees every
  * non-skip tensor as it goes: model/unet.py:84-95), so the figure depends on the options in force
  * (FIUNET_OPT_KEEP_ALL pins all 18 activations, FIUNET_OPT_UNFUSED adds the concat scratch): query it

@@ -151,7 +151,8 @@ def run_windows(model, sd, variant, prec, frames, cache, stages, dither=False, s
                 if (b, h, w) == PINNED:
                     _, th, tw = bench_tile(variant, prec, st)
                 else:
-                    th, tw = stage_tile(bil, (b, h, w), max(st, 1), bool(stage_plan(cf, bil, prec, b, h, w, max(st, 1))[0]))
+                    i = 17 if st == S.HEAD else max(st, 1)      # (the head: the last conv's tile; the stem: conv 1's)
+                    th, tw = stage_tile(bil, (b, h, w), i, bool(stage_plan(cf, bil, prec, b, h, w, i)[0]))
                 lv = 0 if st == S.HEAD else LEVEL[10 + 2 * S.UP.index(st)] if isinstance(st, str) else LEVEL[st]
                 hl, wl = level_shape(h, w, lv)
                 wins = stage_windows(st, th, tw, b, hl, wl)
