@@ -206,6 +206,19 @@ int launch_conv_cfg(ConvArgs a, hipStream_t s)
 
 inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 256 * 32); }
 
+// `bytes` (a multiple of 4) of zeros from the 16-byte-aligned `p`, as a kernel on `s` (pointwise.hip.h, zero_fill_kernel:
+// why it is not hipMemsetAsync)
+int zero_fill_async(void* p, size_t bytes, hipStream_t s)
+{
+    if (((uintptr_t)p & 15) || (bytes & 3)) return fail(FIUNET_ERR_INVALID_ARG, "internal: zero-fill of an unaligned range");
+    if (!bytes) return FIUNET_OK;
+    const size_t n16 = bytes / 16;
+    hipLaunchKernelGGL(zero_fill_kernel, dim3(grid_for(std::max<size_t>(n16, 1))), dim3(256), 0, s, (uint4*)p, n16,
+                       (unsigned)((bytes % 16) / 4));
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
 inline long long padded_area(int H, int W, int TH, int TW)
 {
     return (long long)((H + TH - 1) / TH) * TH * ((W + TW - 1) / TW) * TW;
@@ -834,7 +847,7 @@ int forward_impl(fiunet_ctx* ctx, int precision, const float* f1, const float* f
                 c.padT = a.padT; c.padL = a.padL; c.upOffY = a.upOffY; c.lowOffY = a.lowOffY; c.lowHg = a.lowHg;
                 if (a.C1 != ct.cin) return fail(FIUNET_ERR_INVALID_ARG, "internal: transposed-conv channel plan mismatch");
                 if (y_origin != 0 || Hg != H || a.H != 2 * a.lowH || a.W != 2 * a.lowW)   // F.pad rows / columns (and a band's edges)
-                    HIP_TRY(hipMemsetAsync(up, 0, (size_t)B * a.H * a.W * ct.cout * es, s));
+                    if (int rc = zero_fill_async(up, (size_t)B * a.H * a.W * ct.cout * es, s)) return rc;
                 const long long units = (long long)B * a.lowH * ((a.lowW + 31) / 32) * (ct.cout / 64);   // 32 pixels per wave
                 const dim3 grid((unsigned)std::min<long long>((units + 3) / 4, 256 * 16));
                 if (x2) {
@@ -2108,7 +2121,7 @@ int fiunet_psnr_u8(const uint8_t* pred, const uint8_t* target, int images, int H
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* sums = (unsigned long long*)workspace;
     const size_t n = (size_t)H * W;
-    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)images * 8, s));
+    if (int rc = zero_fill_async(sums, (size_t)images * 8, s)) return rc;
     // ~4 x 16 B per thread and at most 128 workgroups (= atomics) per image
     const unsigned bx = (unsigned)std::min<size_t>((n / 64 + 255) / 256 + 1, 128);
     hipLaunchKernelGGL(sqdiff_u8_kernel, dim3(bx, (unsigned)images), dim3(256), 0, s, pred, target, n, sums);
@@ -2214,7 +2227,7 @@ int fiunet_plane_psnr(const void* pred, size_t pred_image_stride, size_t pred_ro
         return rc;
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* sums = (unsigned long long*)workspace;
-    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)images * 8, s));
+    if (int rc = zero_fill_async(sums, (size_t)images * 8, s)) return rc;
     if (int rc = bits == 10 ? launch_plane_psnr<uint16_t>(pred, pred_image_stride, pred_row_pitch, target,
                                                           target_image_stride, target_row_pitch, images, H, W, sums, s)
                             : launch_plane_psnr<uint8_t>(pred, pred_image_stride, pred_row_pitch, target,
@@ -2318,7 +2331,7 @@ int fiunet_interleaved_psnr(const void* pred, size_t pred_image_stride, size_t p
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* sums = (unsigned long long*)workspace;
     const int planes = images * components;
-    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)planes * 8, s));
+    if (int rc = zero_fill_async(sums, (size_t)planes * 8, s)) return rc;
     if (int rc = bits == 10 ? launch_interleaved_psnr<uint16_t>(components, pred, pred_image_stride, pred_row_pitch,
                                                                 target, target_image_stride, target_row_pitch, images,
                                                                 H, W, sums, s)
@@ -3001,7 +3014,7 @@ int fiunet_farneback_flow(const void* prev, const void* next, int bits, int B, i
     for (int k = levels; k >= 0; --k) {
         const int h = lv[k].h, w = lv[k].w;
         if (k == levels) {
-            HIP_TRY(hipMemsetAsync(fl[cur], 0, (size_t)B * 2 * h * w * 4, s));
+            if (int rc = zero_fill_async(fl[cur], (size_t)B * 2 * h * w * 4, s)) return rc;
         } else {
             if (int rc = flow_launch_resize(fl[cur], lv[k + 1].h, lv[k + 1].w, fl[cur ^ 1], h, w, B, 2, 2.0f, 2.0f, s)) return rc;
             cur ^= 1;

@@ -762,6 +762,17 @@ __global__ __launch_bounds__(256) void postprocess_u8_kernel(const float* __rest
     }
 }
 
+// Zero `n16` 16-byte pieces from the 16-byte-aligned `p`, then `tail` 4-byte words.  The library's zero-fills (F.pad of
+// the ConvTranspose2d halves, the metrics' integer sums, the coarsest flow) are this kernel and not hipMemsetAsync: a
+// memset recorded into a graph was carried out by the first replay only (tests/test_gpu_stream_contract.py), a kernel
+// node by every one.
+__global__ __launch_bounds__(256) void zero_fill_kernel(uint4* __restrict__ p, size_t n16, unsigned tail)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256)
+        p[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0 && threadIdx.x < tail) reinterpret_cast<unsigned*>(p + n16)[threadIdx.x] = 0u;
+}
+
 // 10-bit video: pre10(x) = x / 1023 * 2 - 1, x a 10-bit code in a uint16 word (above 1023 reads as
 // 1023).  The quotient is the IEEE one: __fdiv_rn is correctly rounded here (hipcc's default
 // -fhip-fp32-correctly-rounded-divide-sqrt), so no reciprocal trick has to be proved for 1023 (tests/test_gpu_p10.py
