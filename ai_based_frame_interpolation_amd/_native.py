@@ -47,6 +47,8 @@ SYMBOLS = (
     "fiunet_forward_yuv420p10",
     "fiunet_pair_sad_u8", "fiunet_pair_sad_p10", "fiunet_scene_cuts", "fiunet_hold_cut_frames",
     "fiunet_retime_u8", "fiunet_retime_p10",
+    # repeated frames in video
+    "fiunet_pair_peak_u8", "fiunet_pair_peak_p10", "fiunet_retime_table_u8", "fiunet_retime_table_p10",
     # YUV 4:2:2 / 4:4:4 frames
     "fiunet_yuv_to_rgb_u8", "fiunet_rgb_to_yuv_u8", "fiunet_yuv_to_rgb_p10", "fiunet_rgb_p10_to_yuv",
     "fiunet_workspace_bytes_yuv", "fiunet_forward_yuv", "fiunet_forward_yuv_p10",
@@ -72,6 +74,11 @@ def _surface(layout, frame_stride: int):
         return ctypes.byref(SurfaceLayout(0, 0, 0, frame_stride))
     return ctypes.byref(SurfaceLayout(layout.luma_pitch, layout.chroma_offset, layout.chroma_pitch, frame_stride))
 
+
+
+class RetimeEntry(ctypes.Structure):
+    """include/fiunet.h: fiunet_retime_entry (output row = grid row `row`, blended with the row after it by wn / den)."""
+    _fields_ = [("row", ctypes.c_uint32), ("wn", ctypes.c_uint32), ("den", ctypes.c_uint32)]
 
 
 class PackedLayout(ctypes.Structure):
@@ -175,6 +182,10 @@ def lib() -> ctypes.CDLL:
     u64, u32 = ctypes.c_uint64, ctypes.c_uint32
     L.fiunet_retime_u8.argtypes = [vp, ci, sz, ci, u64, u64, ci, u32, u32, ci, vp, vp, vp]
     L.fiunet_retime_p10.argtypes = [vp, ci, sz, ci, u64, u64, ci, u32, u32, ci, vp, vp, vp]
+    L.fiunet_pair_peak_u8.argtypes = [vp, ci, sz, vp, vp]
+    L.fiunet_pair_peak_p10.argtypes = [vp, ci, sz, vp, vp]
+    L.fiunet_retime_table_u8.argtypes = [vp, ci, sz, vp, ci, vp, vp]
+    L.fiunet_retime_table_p10.argtypes = [vp, ci, sz, vp, ci, vp, vp]
     L.fiunet_nv12_to_rgb_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_rgb_to_nv12_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_p010_to_rgb_p10.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
@@ -682,3 +693,39 @@ def retime(grid: "torch.Tensor", n_intervals: int, depth: int, first_interval: i
     check(fn(grid.data_ptr(), n_intervals, fs, depth, first_interval, j0, n_out, p, q, mode,
              None if flags is None else flags.data_ptr(), out.data_ptr(), s),
           "fiunet_retime_" + ("p10" if bits == 10 else "u8"))
+
+
+def pair_peak(frames: "torch.Tensor", peaks: "torch.Tensor", bits: int) -> None:
+    """fiunet_pair_peak_u8 / fiunet_pair_peak_p10: MAX-ACCUMULATES the largest 64-sample segment sum of |F[i+1] - F[i]|
+    of a contiguous stack [N, ...] (uint8 at 8 bits; 16-bit words, int16 or uint16, at 10) into the 32-bit `peaks`
+    [N-1] (int32 on the torch side: a peak is below 2**16)."""
+    n = frames.shape[0]
+    fs = frames[0].numel() if n else 0
+    fn = lib().fiunet_pair_peak_p10 if bits == 10 else lib().fiunet_pair_peak_u8
+    s = _stream(frames)
+    check(fn(frames.data_ptr(), n, fs, peaks.data_ptr(), s), "fiunet_pair_peak_" + ("p10" if bits == 10 else "u8"))
+
+
+def retime_entries(entries):
+    """A sequence of (row, wn, den) int triples -> the C array of fiunet_retime_entry (None when empty).  ValueError on a
+    value that does not fit 32 bits unsigned (the library checks the rest)."""
+    n = len(entries)
+    if not n:
+        return None
+    arr = (RetimeEntry * n)()
+    for k, (row, wn, den) in enumerate(entries):
+        if not (0 <= row < 1 << 32 and 0 <= wn < 1 << 32 and 0 <= den < 1 << 32):
+            raise ValueError(f"entry {k} = {(row, wn, den)} does not fit 32 bits unsigned")
+        arr[k] = RetimeEntry(row, wn, den)
+    return arr
+
+
+def retime_table(grid: "torch.Tensor", entries, out: "torch.Tensor", bits: int) -> None:
+    """fiunet_retime_table_u8 / fiunet_retime_table_p10: a contiguous grid [n_rows, ...] and (row, wn, den) triples, read
+    on the host during the call -> `out` [len(entries), ...]."""
+    arr = retime_entries(entries)
+    fs = grid[0].numel() if grid.shape[0] else 0
+    fn = lib().fiunet_retime_table_p10 if bits == 10 else lib().fiunet_retime_table_u8
+    s = _stream(grid)
+    check(fn(grid.data_ptr(), grid.shape[0], fs, arr, len(entries), out.data_ptr(), s),
+          "fiunet_retime_table_" + ("p10" if bits == 10 else "u8"))

@@ -2,7 +2,7 @@
 
 The reference's `main.py video` flags (--input, --output, --factor, --model, --device), plus --precision, --matrix,
 --siting, --scene-cut, --batch, --chunk-frames, the frame-rate conversion's --fps, --src-fps, --time-depth and
---retime, and --raw / --size for headerless NV12, packed RGB or 4:2:2 / 4:4:4 YUV video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
+--retime, --dedup and --max-gap for repeated frames, and --raw / --size for headerless NV12, packed RGB or 4:2:2 / 4:4:4 YUV video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
 the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 
     ffmpeg -i in.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - \\
@@ -10,6 +10,10 @@ the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 
 With `--fps 60000/1001` (a fraction or an integer, never a decimal) the output has that frame rate instead of
 --factor times the input's (retime.py): 23.976 -> 59.94, 24 -> 60, 25 -> 60, 50 -> 120.
+
+With `--dedup 0` (a tolerance in code values; `--max-gap 4`) runs of repeated frames - telecined film, animation on twos,
+a stalled capture - are re-timed instead of interpolated across (retime.py); one line on standard error
+says how many repeated frames were re-timed.
 
 With `--raw nv12 --size 1920x1080 --src-fps 24` input and output are headerless tight NV12 frames, the layout hardware
 decoders and encoders use, converted on the device without a repack:
@@ -93,6 +97,13 @@ def _fps(v: str):
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _dedup(v: str):
+    try:
+        return retime.check_dedup(float(v))[0]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def _size(v: str):
     """"WxH" -> (width, height)"""
     parts = v.lower().split("x")
@@ -139,6 +150,11 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--time-depth", type=int, default=2, choices=(1, 2, 3, 4), help="Bisection levels under --fps")
     v.add_argument("--retime", default="blend", choices=retime.MODES,
                    help="How --fps picks between the two bisection frames around an output time")
+    v.add_argument("--dedup", type=_dedup, default=None, metavar="TOL",
+                   help="Re-time repeated frames (telecine, animation on twos, stalled capture): frames that differ "
+                        "by at most TOL code values count as repeats (0: equal frames)")
+    v.add_argument("--max-gap", type=int, default=4, choices=tuple(range(2, 9)),
+                   help="Longest run of equal frames that --dedup re-times (a longer hold stays a hold)")
     v.add_argument("--raw", default=None, choices=RAW_CHOICES,
                    help="Headerless raw video in and out (tight NV12, packed RGB or 4:2:2 / 4:4:4 YUV frames, named as "
                         "ffmpeg's -pix_fmt); needs --size and --src-fps")
@@ -193,6 +209,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     return a
 
 
+def retimed_repeats(dedup_log, scene_log, max_gap: int) -> int:
+    """The number of repeated source frames a run re-timed: the dead intervals inside spans, from the run's logs."""
+    dead = [bool(v) for _, d in dedup_log for v in d]
+    cuts = [bool(v) for _, f in scene_log for v in f] if scene_log else None
+    return sum(ln - 1 for _, ln in retime.dedup_spans(dead, cuts, max_gap))
+
+
 def run_video(a: argparse.Namespace) -> int:
     from . import stream
     from .inference import FrameInterpolator, load_model
@@ -204,10 +227,16 @@ def run_video(a: argparse.Namespace) -> int:
     fi = FrameInterpolator(model=model, device=device, batch=a.batch)
     src = sys.stdin.buffer if a.input == "-" else a.input
     dst = sys.stdout.buffer if a.output == "-" else a.output
+    logs = {}
+    if a.dedup is not None:   # for the count below (the cut flags too: a run before a cut is not re-timed)
+        logs = dict(dedup_log=[], scene_log=[] if a.scene_cut is not None else None)
     n = fi.interpolate_video(src, dst, a.factor, matrix=a.matrix, siting=a.siting, scene_cut=a.scene_cut,
                              chunk_frames=a.chunk_frames, fps=a.fps, src_fps=a.src_fps, time_depth=a.time_depth,
                              retime=a.retime, raw=a.raw, width=a.size[0] if a.size else None,
-                             height=a.size[1] if a.size else None)
+                             height=a.size[1] if a.size else None, dedup=a.dedup, max_gap=a.max_gap, **logs)
+    if a.dedup is not None:
+        print(f"re-timed {retimed_repeats(logs['dedup_log'], logs['scene_log'], a.max_gap)} repeated frames",
+              file=sys.stderr)
     print(f"wrote {n} frames", file=sys.stderr)
     return n
 

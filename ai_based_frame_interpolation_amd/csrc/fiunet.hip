@@ -2477,6 +2477,35 @@ int fiunet_pair_sad_p10(const uint16_t* frames, int n_frames, size_t frame_sampl
     return pair_sad(frames, n_frames, frame_samples, sums, stream);
 }
 
+// repeated frames: the calling conventions of pair_sad
+extern "C++" {
+template <typename T>
+static int pair_peak(const T* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
+{
+    if (!frames || !peaks) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    if (n_frames < 2 || frame_samples == 0) return FIUNET_OK;
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
+    for (int p0 = 0; p0 < n_frames - 1; p0 += kMaxGridY) {
+        const int np = std::min(n_frames - 1 - p0, kMaxGridY);
+        hipLaunchKernelGGL(pair_peak_kernel<T>, dim3(bx, (unsigned)np), dim3(kSceneBlock), 0, (hipStream_t)stream,
+                           frames + (size_t)p0 * frame_samples, frame_samples, peaks + p0);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_pair_peak_u8(const uint8_t* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
+{
+    return pair_peak(frames, n_frames, frame_samples, peaks, stream);
+}
+
+int fiunet_pair_peak_p10(const uint16_t* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
+{
+    return pair_peak(frames, n_frames, frame_samples, peaks, stream);
+}
+
 int fiunet_scene_cuts(const int64_t* sums, int n_frames, size_t count, int bits, double threshold, double* scores,
                       uint8_t* flags, void* stream)
 {
@@ -2559,6 +2588,53 @@ int fiunet_retime_p10(const uint16_t* grid, int n_intervals, size_t frame_sample
                       void* stream)
 {
     return retime(grid, n_intervals, frame_samples, depth, first_interval, j0, n_out, p, q, mode, flags, out, stream);
+}
+
+// the table-driven form: every entry is checked here, on the host, before the first launch; the entries
+// travel in the kernel's arguments, kRetimeTableMax output frames per launch
+static_assert(sizeof(fiunet_retime_entry) == sizeof(RetimeEntry) && sizeof(RetimeEntry) == 12, "entry layout");
+
+extern "C++" {
+template <typename T>
+static int retime_table(const T* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries, int n_out,
+                        T* out, void* stream)
+{
+    if (!grid || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_rows < 0 || n_out < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
+    if (n_out == 0) return FIUNET_OK;
+    if (!entries) return fail(FIUNET_ERR_INVALID_ARG, "NULL entries");
+    for (int k = 0; k < n_out; ++k) {
+        const fiunet_retime_entry& e = entries[k];
+        if (e.den < 1 || e.den > kRetimeMaxQ) return fail(FIUNET_ERR_INVALID_ARG, "entry: den outside 1..2^20");
+        if (e.wn >= e.den) return fail(FIUNET_ERR_INVALID_ARG, "entry: wn >= den");
+        if ((uint64_t)e.row >= (uint64_t)n_rows) return fail(FIUNET_ERR_INVALID_ARG, "entry: row outside the grid");
+        if (e.wn > 0 && (uint64_t)e.row + 1 >= (uint64_t)n_rows)
+            return fail(FIUNET_ERR_INVALID_ARG, "entry: the row after `row` lies outside the grid");
+    }
+    if (frame_samples == 0) return FIUNET_OK;
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
+    for (int k0 = 0; k0 < n_out; k0 += kRetimeTableMax) {
+        const int nk = std::min(n_out - k0, kRetimeTableMax);
+        RetimeTable table = {};
+        for (int k = 0; k < nk; ++k) table.e[k] = RetimeEntry{entries[k0 + k].row, entries[k0 + k].wn, entries[k0 + k].den};
+        hipLaunchKernelGGL(retime_table_kernel<T>, dim3(bx, (unsigned)nk), dim3(kRetimeBlock), 0, (hipStream_t)stream,
+                           grid, frame_samples, table, out + (size_t)k0 * frame_samples);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_retime_table_u8(const uint8_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
+                           int n_out, uint8_t* out, void* stream)
+{
+    return retime_table(grid, n_rows, frame_samples, entries, n_out, out, stream);
+}
+
+int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
+                            int n_out, uint16_t* out, void* stream)
+{
+    return retime_table(grid, n_rows, frame_samples, entries, n_out, out, stream);
 }
 
 // diagnostic (not part of the ABI, no declaration in include/fiunet.h): override choose_conv_cfg for one conv (1..17) of

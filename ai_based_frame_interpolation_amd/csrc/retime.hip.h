@@ -120,4 +120,56 @@ __global__ __launch_bounds__(kRetimeBlock) void retime_kernel(const T* __restric
         po[i] = (T)retime_div(S::read(pa[i]) * wa + S::read(pb[i]) * wb + (q >> 1), q, rq);
 }
 
+// The table-driven form (repeated frames): where an output frame comes from is decided on the host, frame
+// by frame, and arrives as one entry per frame IN THE KERNEL'S ARGUMENTS (at most kRetimeTableMax per launch): there is
+// no device table, nothing is copied, and the kernel reads no index it was not handed.  Output row blockIdx.y is
+//   wn == 0   a byte copy of grid row `row`
+//   else      (A * (den - wn) + B * wn + den / 2) / den per sample, A = grid row `row`, B = the row after it
+// The host has checked row (+ 1 when wn > 0) < n_rows, wn < den and 1 <= den <= 2^20 for every entry before the first
+// launch, so retime_div's proof above holds with q = den.  Mode and cut flags are resolved into the entries on the host.
+constexpr int kRetimeTableMax = 64;
+struct RetimeEntry {
+    uint32_t row, wn, den;
+};
+struct RetimeTable {
+    RetimeEntry e[kRetimeTableMax];
+};
+
+template <typename T>
+__global__ __launch_bounds__(kRetimeBlock) void retime_table_kernel(const T* __restrict__ grid, size_t n,
+                                                                    const RetimeTable table, T* __restrict__ out)
+{
+    using S = RetimeSample<T>;
+    const RetimeEntry e = table.e[blockIdx.y];   // gridDim.y <= kRetimeTableMax
+    const unsigned wn = e.wn, q = e.den;
+    const T* pa = grid + (size_t)e.row * n;
+    T* po = out + (size_t)blockIdx.y * n;
+    constexpr size_t kPerVec = 16 / sizeof(T);
+    const size_t step = (size_t)gridDim.x * kRetimeBlock;
+    const size_t first = (size_t)blockIdx.x * kRetimeBlock + threadIdx.x;
+    if (wn == 0) {   // a copy of A: B is not read
+        const bool vec = (((uintptr_t)pa | (uintptr_t)po) & 15) == 0;
+        const size_t nv = vec ? n / kPerVec : 0;
+        for (size_t i = first; i < nv; i += step) reinterpret_cast<uint4*>(po)[i] = reinterpret_cast<const uint4*>(pa)[i];
+        for (size_t i = nv * kPerVec + first; i < n; i += step) po[i] = pa[i];
+        return;
+    }
+    const T* pb = pa + n;
+    const unsigned wa = q - wn, wb = wn;
+    const float rq = 1.0f / (float)q;
+    const bool vec = (((uintptr_t)pa | (uintptr_t)pb | (uintptr_t)po) & 15) == 0;
+    const size_t nv = vec ? n / kPerVec : 0;
+    for (size_t i = first; i < nv; i += step) {
+        const uint4 va = reinterpret_cast<const uint4*>(pa)[i], vb = reinterpret_cast<const uint4*>(pb)[i];
+        uint4 vo;
+        vo.x = S::blend_word(va.x, vb.x, wa, wb, q, rq);
+        vo.y = S::blend_word(va.y, vb.y, wa, wb, q, rq);
+        vo.z = S::blend_word(va.z, vb.z, wa, wb, q, rq);
+        vo.w = S::blend_word(va.w, vb.w, wa, wb, q, rq);
+        reinterpret_cast<uint4*>(po)[i] = vo;
+    }
+    for (size_t i = nv * kPerVec + first; i < n; i += step)
+        po[i] = (T)retime_div(S::read(pa[i]) * wa + S::read(pb[i]) * wb + (q >> 1), q, rq);
+}
+
 }  // namespace fiunet

@@ -12,6 +12,8 @@
 //
 //   pair_sad_kernel<T>     : accumulates sad into sums[n-1] (zeroed by the caller), so that one sad can span the
 //                            separate Y / U / V stacks of a planar layout.  grid = (blocks per pair, pairs).
+//   pair_peak_kernel<T>    : repeated frames: max-accumulates the largest 64-sample segment sum of
+//                            |F[i+1] - F[i]| into peaks[n-1] (zeroed by the caller); same grid
 //   scene_cuts_kernel      : one thread per interval -> scores (fp64) and flags (uint8)
 //   hold_cut_frames_kernel : on the interleaved result of a factor-`factor` loop, copies F[i] into its factor-1
 //                            successors for every flagged interval; the flags are read on the device, so the hold
@@ -91,6 +93,80 @@ __global__ __launch_bounds__(kSceneBlock) void pair_sad_kernel(const T* __restri
 #pragma unroll
         for (int w = 0; w < kSceneBlock / 64; ++w) t += part[w];
         if (t) atomicAdd(sums + pair, t);
+    }
+}
+
+// Repeated frames.  Pair i = blockIdx.y as above; peak[i] = the largest sum of |F[i+1] - F[i]| over the
+// aligned 64-sample segments of the frame, counted from its first sample (the last one may be short).  Max-accumulates
+// into peaks[pair] (zeroed by the caller): the maximum is order-independent, so one integer atomicMax per workgroup is
+// exact, and several stacks of the same frames share one result.  A segment sum is at most 64 * 1023 < 2^16.
+//   vector path   both frame bases 16-byte aligned: the n / 64 whole segments, 16 bytes per lane, kSegLanes = 4 (8-bit)
+//                 or 8 (10-bit) adjacent lanes per segment, summed inside the lane group (segment_sum); the loop runs
+//                 on a wave-uniform base with the load predicated, so every lane is active in every exchange
+//   sample path   a wave per segment, a lane per sample, summed over the wave: the short last segment after the vector
+//                 path, every segment where a base is unaligned (an odd n misaligns every second pair)
+// The sum of s over the aligned group of kLanes (4 or 8) adjacent lanes, in every lane of the group, with every lane of
+// the wave active: DPP moves on the VALU (lanes 1 and 2 apart inside a quad, then the other quad of the 8 by the mirror of
+// the half row, whose lanes all hold their quad's sum by then), where __shfl_xor would go through the LDS crossbar once
+// per 16 bytes loaded.
+template <int kLanes>
+__device__ __forceinline__ unsigned segment_sum(unsigned s)
+{
+    static_assert(kLanes == 4 || kLanes == 8, "a segment is 4 or 8 lanes");
+    s += (unsigned)__builtin_amdgcn_update_dpp(0, (int)s, 0xB1, 0xF, 0xF, true);        // quad_perm [1, 0, 3, 2]
+    s += (unsigned)__builtin_amdgcn_update_dpp(0, (int)s, 0x4E, 0xF, 0xF, true);        // quad_perm [2, 3, 0, 1]
+    if (kLanes == 8) s += (unsigned)__builtin_amdgcn_update_dpp(0, (int)s, 0x141, 0xF, 0xF, true);   // row_half_mirror
+    return s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSceneBlock) void pair_peak_kernel(const T* __restrict__ frames, size_t n,
+                                                                unsigned* __restrict__ peaks)
+{
+    using S = SceneSample<T>;
+    const size_t pair = blockIdx.y;
+    const T* pa = frames + pair * n;
+    const T* pb = pa + n;
+    constexpr size_t kPerVec = 16 / sizeof(T);
+    constexpr int kSegLanes = (int)(64 / kPerVec);
+    const bool vec = (((uintptr_t)pa | (uintptr_t)pb) & 15) == 0;
+    const size_t vseg = vec ? n / 64 : 0;      // whole segments of the vector path
+    const size_t nseg = (n + 63) / 64;
+    const unsigned lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * (kSceneBlock / 64) + (threadIdx.x >> 6);
+    const size_t waves = (size_t)gridDim.x * (kSceneBlock / 64);
+    unsigned m = 0;
+    const size_t nv = vseg * kSegLanes;        // vectors of the vector path: a multiple of kSegLanes
+    for (size_t base = wave * 64; base < nv; base += waves * 64) {
+        const size_t i = base + lane;
+        unsigned s = 0;
+        if (i < nv) {
+            const uint4 va = reinterpret_cast<const uint4*>(pa)[i], vb = reinterpret_cast<const uint4*>(pb)[i];
+            s = S::sad_word(va.x, vb.x) + S::sad_word(va.y, vb.y) + S::sad_word(va.z, vb.z) + S::sad_word(va.w, vb.w);
+        }
+        m = max(m, segment_sum<kSegLanes>(s));
+    }
+    for (size_t seg = vseg + wave; seg < nseg; seg += waves) {
+        const size_t k = seg * 64 + lane;
+        unsigned s = 0;
+        if (k < n) {
+            const int d = (int)S::read(pa[k]) - (int)S::read(pb[k]);
+            s = (unsigned)abs(d);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        m = max(m, s);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor(m, o));
+    __shared__ unsigned part[kSceneBlock / 64];
+    if (lane == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < kSceneBlock / 64; ++w) t = max(t, part[w]);
+        if (t) atomicMax(peaks + pair, t);
     }
 }
 

@@ -458,7 +458,7 @@ class FrameInterpolator:
 
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
                           chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend", raw=None,
-                          width=None, height=None):
+                          width=None, height=None, dedup=None, max_gap=4, dedup_log=None, scene_log=None):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -495,19 +495,33 @@ class FrameInterpolator:
         yuv422p10le`: ProRes / DNxHR decodes, capture cards), through the RGB network at their own chroma resolution
         (`interpolate_sequence_yuv`): matrix and siting apply as for nv12 (siting None: "mpeg2"; bt2020
         at 10 bits), the range is limited; run the 10-bit formats in precision fp16.  Y4M tagged C422 / C444 is still
-        refused by the RGB network: such clips take this raw route."""
+        refused by the RGB network: such clips take this raw route.
+        dedup: None, or a tolerance >= 0 in code values: re-time repeated frames (telecined film, animation on twos and
+        threes, a stalled capture; retime.py).  An interval whose frames differ by at most `dedup` per
+        sample on average over every aligned 64-sample segment (0: equal frames) is dead; a run of dead intervals and
+        the live one after it, max_gap frames at most (2..8), is covered evenly by the motion of that live interval,
+        taken from its bisection frames and blended as `retime` says.  A longer hold (a title card), a run before a
+        flagged cut and a run at the clip's end stay as they are.  Works with `factor` (at most 16) and with `fps`; the
+        frame count does not change.  Costs one small device-to-host read per chunk.
+        dedup_log: None, or a list that receives one (peaks, dead) pair of host arrays per chunk, over the chunk's own
+        intervals (a resident run: one pair, the whole clip's); concatenated they are `scene.pair_peak` of the clip and
+        its dead flags.  scene_log: the same for `scene_cut`: one (scores float64, flags uint8) pair per chunk, what the
+        stream routes' `scene_log` has always received (it costs one more device-to-host read per chunk); from the
+        two logs `retime.dedup_spans` gives the spans a run re-timed, which is how the command line counts them."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         from . import stream
         run = dict(batch=self.batch, chunk_frames=chunk_frames, scene_cut=thr, fps=fps, src_fps=src_fps,
-                   time_depth=time_depth, retime=retime)
+                   time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
+                   scene_log=scene_log)
         if raw is not None:
             return stream.interpolate_raw_stream(self.model, input_path, output_path, factor, raw=raw, width=width,
                                                  height=height, matrix=matrix, siting=siting, **run)
         if width is not None or height is not None:
             raise ValueError("width and height describe raw video: pass raw=\"nv12\" with them")
         stream.check_retime(fps, src_fps, time_depth, retime, factor)
+        stream.check_dedup(dedup, max_gap, fps, factor)
         if chunk_frames is not None:
             stream.check_chunk_frames(chunk_frames)
         is_path = isinstance(input_path, (str, os.PathLike))

@@ -16,9 +16,14 @@ frames gives J = (N - 1) * q // p + 1 frames; output frame j sits at input time 
 
 Every plane of a frame as stored is resampled by the same rule.  One HIP kernel (csrc/retime.hip.h): `fiunet_retime_u8`
 / `fiunet_retime_p10`; the flags are read on the device.
+
+Repeated frames (`dedup=`; the second half of this file): the spans of repeats are found on the host and
+every output frame becomes one (row, wn, den) entry of a table that a second kernel, `fiunet_retime_table_u8` / `_p10`,
+takes in its arguments.
 """
 from __future__ import annotations
 
+import math
 import numbers
 from fractions import Fraction
 from typing import Tuple
@@ -162,4 +167,166 @@ def resample(grid: torch.Tensor, plan: Plan, first_interval: int, j0: int, n_out
     return out
 
 
-__all__ = ["MAX_Q", "MODES", "Plan", "parse_fps", "check_time_depth", "check_mode", "plan", "resample"]
+# ---- repeated frames -------------------------------------------------------------------------------
+# Telecined film, animation on twos and threes, a stalled capture: A A A B.  The loops would ask the network for the
+# middle of (A, A) twice and squeeze the motion from A to B into the last interval.  With `dedup=` the output times
+# inside a run of repeats are mapped onto the grid of the one interval that carries the motion.  Integers and exact
+# rationals only:
+#
+#   peak[i]  the largest sum of |F[i+1] - F[i]| over the aligned 64-sample segments of a frame as stored
+#            (scene.pair_peak); interval i is DEAD iff peak[i] <= floor(dedup * 64), dedup a tolerance in code values
+#   span     a maximal run of m >= 1 dead intervals a .. a+m-1 followed by a live interval i = a+m that is not a flagged
+#            cut, with L = m + 1 <= max_gap: the intervals [a, i+1).  A longer hold, a run that reaches the clip's end,
+#            a run before a cut and every interval outside a run form no span and behave as without dedup.
+#   time     output frame j sits at t = j p / q; (a, i, L) the span that holds floor(t) (outside spans a = i = floor(t),
+#            L = 1): num = j p - a q, den = q L, lo = num G // den, wn = num G % den; the frame is grid row (i, lo)
+#            blended with the row after it by wn / den ("nearest": the closer of the two, a tie to the earlier one); an
+#            interval floor(t) flagged as a cut, off a source frame, stays a copy of grid row (floor(t), 0).
+#
+# With L = 1 this is the rule at the top of this file bit for bit.  den <= 2**20 keeps the kernel's 32-bit arithmetic.
+MAX_GAP_RANGE = (2, 8)
+DEDUP_MAX_FACTOR = 16
+
+
+def check_dedup(dedup, max_gap=4):
+    """-> (dedup as a float or None, max_gap as an int).  dedup: None (off) or a finite real number >= 0 (not a bool);
+    max_gap: an int in 2..8.  ValueError otherwise."""
+    if isinstance(max_gap, bool) or not isinstance(max_gap, numbers.Integral) or \
+            not MAX_GAP_RANGE[0] <= max_gap <= MAX_GAP_RANGE[1]:
+        raise ValueError(f"max_gap must be an int in {MAX_GAP_RANGE[0]}..{MAX_GAP_RANGE[1]}, got {max_gap!r}")
+    if dedup is None:
+        return None, int(max_gap)
+    if isinstance(dedup, bool) or not isinstance(dedup, numbers.Real):
+        raise ValueError(f"dedup must be None or a number >= 0 (a tolerance in code values), got {dedup!r}")
+    v = float(dedup)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError(f"dedup must be None or a finite number >= 0 (a tolerance in code values), got {dedup!r}")
+    return v, int(max_gap)
+
+
+def dead_limit(dedup: float) -> int:
+    """floor(dedup * 64): interval i is dead iff peak[i] <= this (a peak is below 2**16)."""
+    return int(min(math.floor(dedup * 64), (1 << 31) - 1))
+
+
+def dedup_plan(pl: "Plan | None", factor: int, max_gap: int) -> "Plan":
+    """The plan a run with `dedup` goes through: `pl` (from fps), or p / q = 1 / factor, G = factor.  ValueError when
+    factor > 16 (the grid's depth) or q * max_gap > 2**20 (the kernel's divisor)."""
+    if pl is None:
+        if factor > DEDUP_MAX_FACTOR:
+            raise ValueError(f"dedup re-times on the grid of a factor run of at most {DEDUP_MAX_FACTOR}: got "
+                             f"factor={factor!r}")
+        pl = Plan(Fraction(1), Fraction(factor), factor.bit_length() - 1)
+    if pl.q * max_gap > MAX_Q:
+        raise ValueError(f"with dedup, q * max_gap must not exceed 2**20 = {MAX_Q}: the rates reduce to "
+                         f"{pl.p}/{pl.q} and max_gap is {max_gap}")
+    return pl
+
+
+def dedup_spans(dead, cuts, max_gap: int):
+    """The spans of a clip: `dead` (one truth value per interval), `cuts` (the same length, or None) -> a list of
+    (a, L), first interval and length, in order."""
+    n, spans, k = len(dead), [], 0
+    while k < n:
+        if not dead[k]:
+            k += 1
+            continue
+        a = k
+        while k < n and dead[k]:
+            k += 1
+        # k: the live interval after the run, or n when the run reaches the end
+        if k < n and k - a + 1 <= max_gap and not (cuts is not None and cuts[k]):
+            spans.append((a, k - a + 1))
+            k += 1
+    return spans
+
+
+def classify_chunk(dead, cuts, carry: int, first_interval: int, c: int, max_gap: int):
+    """The spans that touch a chunk's own intervals first_interval .. first_interval + c, from what the chunk sees:
+    `dead` / `cuts` (or None) of the intervals from first_interval on (its own and the lookahead's: max_gap - 1 more, or
+    as many as the clip has; with cuts one more still, whose own flag is not relied on), and `carry`, the number of
+    dead intervals directly before first_interval, saturated at max_gap.  -> (spans as (a, L) with clip interval
+    numbers, e: the intervals past the chunk's end that they need, the carry of the next chunk).  Equals `dedup_spans`
+    on the whole clip (tests/test_dedup_host.py)."""
+    s = first_interval
+    local_dead = [True] * carry + [bool(v) for v in dead]
+    local_cuts = None if cuts is None else [False] * carry + [bool(v) for v in cuts]
+    spans = []
+    for a, ln in dedup_spans(local_dead, local_cuts, max_gap):
+        a += s - carry
+        # a saturated carry stands for a run of max_gap or more: no span (L > max_gap), which dedup_spans has found
+        if a + ln > s and a < s + c:
+            spans.append((a, ln))
+    e = max([a + ln - (s + c) for a, ln in spans] + [0])
+    own = local_dead[:carry + c]
+    trail = 0
+    while trail < len(own) and own[len(own) - 1 - trail]:
+        trail += 1
+    return spans, e, min(trail, max_gap)
+
+
+def table_entries(pl: Plan, spans, first_interval: int, j0: int, n_out: int, n_intervals: int, mode: str = "blend",
+                  cuts=None):
+    """(row, wn, den) of output frames j0 .. j0 + n_out - 1 on a grid of n_intervals * G + 1 rows that starts at clip
+    interval first_interval: what `resample_table` takes.  spans: (a, L) with clip interval numbers; cuts: truth values
+    of the grid's intervals (from first_interval), or None.  Python integers only; ValueError when a frame needs a row
+    outside the grid."""
+    mode = check_mode(mode)
+    p, q, G = pl
+    rows = n_intervals * G + 1
+    where = {}
+    for a, ln in spans:
+        for f in range(a, a + ln):
+            where[f] = (a, ln)
+    out = []
+    for j in range(j0, j0 + n_out):
+        f, r = divmod(j * p, q)
+        k = f - first_interval
+        if r != 0 and cuts is not None and 0 <= k < len(cuts) and cuts[k]:
+            row, wn, den = k * G, 0, 1
+        else:
+            a, ln = where.get(f, (f, 1))
+            num, den = j * p - a * q, q * ln
+            lo, wn = divmod(num * G, den)
+            row = (a + ln - 1 - first_interval) * G + lo
+            if mode == "nearest":
+                row, wn = row + (1 if 2 * wn > den else 0), 0
+            g = math.gcd(wn, den)
+            wn, den = wn // g, den // g      # (wn == 0: den = 1)
+        if k < 0 or row < 0 or row + (1 if wn else 0) >= rows:
+            raise ValueError(f"output frame {j} needs grid row {row}{' and the next' if wn else ''}: the grid has "
+                             f"{rows} rows from interval {first_interval}")
+        out.append((row, wn, den))
+    return out
+
+
+@torch.no_grad()
+def resample_table(grid: torch.Tensor, entries, bits: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One output frame per entry (row, wn, den) from `grid`, a contiguous device stack [rows, ...] (uint8 at 8 bits;
+    16-bit words at 10): a byte copy of grid[row] when wn == 0, else (A (den - wn) + B wn + den // 2) // den per sample
+    with B = grid[row + 1].  The entries are read on the host during the call and go to the kernel in its arguments
+    (`fiunet_retime_table_u8` / `_p10`).  Returns `out` ([len(entries), ...]; allocated when None)."""
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+    want = (torch.uint8,) if bits == 8 else (torch.int16, torch.uint16)
+    if grid.dtype not in want:
+        raise ValueError(f"a {bits}-bit grid must be {' or '.join(str(d) for d in want)}, got {grid.dtype}")
+    if not grid.is_cuda:
+        raise RuntimeError("the grid must be on the GPU: there is no CPU path in this package")
+    if not grid.is_contiguous():
+        raise ValueError("the grid must be contiguous")
+    entries = [tuple(int(v) for v in e) for e in entries]
+    shape = (len(entries),) + tuple(grid.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=grid.dtype, device=grid.device)
+    elif tuple(out.shape) != shape or out.dtype != grid.dtype or out.device != grid.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {grid.dtype} {shape} tensor on {grid.device}")
+    if entries:
+        with torch.cuda.device(grid.device):
+            _native.retime_table(grid, entries, out, bits)
+    return out
+
+
+__all__ = ["MAX_Q", "MODES", "Plan", "parse_fps", "check_time_depth", "check_mode", "plan", "resample",
+           "check_dedup", "dead_limit", "dedup_plan", "dedup_spans", "classify_chunk", "table_entries",
+           "resample_table"]

@@ -79,6 +79,25 @@ def pair_sad(stacks: Stacks, bits: int) -> torch.Tensor:
     return sums
 
 
+PEAK_SEGMENT = 64   # samples per segment of `pair_peak`
+
+
+@torch.no_grad()
+def pair_peak(stacks: Stacks, bits: int) -> torch.Tensor:
+    """int32 [N-1] device tensor: for every interval the largest sum of |F[i+1] - F[i]| over the aligned 64-sample
+    segments of a frame as stored (counted from the frame's first sample; the last one may be short; 10-bit words above
+    1023 read as 1023), the maximum taken over every stack.  The measure of repeated frames (retime.py):
+    a small object moving in a static shot has a tiny frame mean and a large segment sum.  `stacks` as for `pair_sad`;
+    the segments of each stack are counted from that stack's frames."""
+    st, n, dev = _stacks(stacks, bits)
+    peaks = torch.zeros(max(n - 1, 0), dtype=torch.int32, device=dev)
+    if n >= 2:
+        with torch.cuda.device(dev):
+            for s in st:
+                _native.pair_peak(s, peaks, bits)
+    return peaks
+
+
 @torch.no_grad()
 def detect_cuts(stacks: Stacks, threshold: float, bits: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (scores float64 [N-1], flags uint8 [N-1]), both on the device: what `scene_cut=threshold` would hold."""
@@ -145,4 +164,4 @@ def hold_cut_frames(video: torch.Tensor, flags: torch.Tensor, factor: int) -> to
     return video
 
 
-__all__ = ["check_threshold", "pair_sad", "detect_cuts", "score_window", "hold_cut_frames"]
+__all__ = ["check_threshold", "pair_sad", "pair_peak", "PEAK_SEGMENT", "detect_cuts", "score_window", "hold_cut_frames"]

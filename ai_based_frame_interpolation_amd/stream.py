@@ -24,6 +24,14 @@ writes); `FrameInterpolator.interpolate_video` dispatches into the three `interp
              `plan.span(s, c, last)` from it: a time belongs to exactly one chunk, so the overlap frame is written
              once.  A clip that ends on a chunk's edge sends one more chunk of no intervals for its last frame.
 
+  dedup      with `dedup=` (retime.py) a run always has a plan (without fps: p / q = 1 / factor).  A chunk
+             reads max_gap - 1 lookahead frames (max_gap with scene_cut), computes `scene.pair_peak` on its rows, reads
+             the dead (and cut) flags back - the one host read per chunk - and `retime.classify_chunk` finds its spans
+             from them and a carried count of dead intervals.  A span across the chunk's end makes the grid longer by
+             the lookahead intervals it needs; `retime.table_entries` turns the frames of `plan.span` into (row, wn,
+             den) entries and `retime.resample_table` writes them.  In the sizes below C + 2 becomes C + 1 + max_gap
+             and the output slots hold the frames of C + max_gap - 1 intervals (the last chunk; `_run`).
+
 Memory is bounded by the chunk, never by the clip (C = chunk_frames, F = factor, one frame of the input layout):
   host pinned    3 x (C + 2) input frames + 2 x (C x F + 1) output frames
   device         2 x (C + 2) input frames + one chunk's levels + the previous chunk's result (C x F + 1 frames of
@@ -353,16 +361,53 @@ class _Stopped(Exception):
     pass
 
 
+def check_dedup(dedup, max_gap, fps, factor):
+    """The checks of `dedup` / `max_gap` that need no source -> (the tolerance or None, max_gap)."""
+    tol, gap = _retime.check_dedup(dedup, max_gap)
+    if tol is not None and fps is None:
+        _retime.dedup_plan(None, factor, gap)   # (refuses factor > 16)
+    return tol, gap
+
+
+def _dedup_of(tol, gap, plan, factor):
+    """-> (the plan of the run, None or (dead limit, max_gap)): with dedup a run always has a plan."""
+    if tol is None:
+        return plan, None
+    return _retime.dedup_plan(plan, factor, gap), (_retime.dead_limit(tol), gap)
+
+
+def _dead_and_cuts(d, bits, limit, cut_flags):
+    """One device-to-host read: -> (peaks on the device, dead flags, cut flags or None as host bool arrays) of the
+    intervals of the device frames `d`; cut_flags: their uint8 device flags or None."""
+    peaks = scene.pair_peak([d], bits)
+    dead = (peaks <= limit).to(torch.uint8)
+    if cut_flags is None:
+        return peaks, dead.cpu().numpy().astype(bool), None
+    host = torch.stack([dead, cut_flags]).cpu().numpy().astype(bool)
+    return peaks, host[0], host[1]
+
+
 @torch.no_grad()
 def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, thr, scene_log=None, plan=None,
-         mode: str = "blend") -> int:
+         mode: str = "blend", dd=None, dedup_log=None) -> int:
     """Stream `reader` through `route` into `write(rows)`; returns the number of output frames.  plan: a `retime.Plan`
-    (then factor is its G): each chunk's grid is resampled to the plan's frames."""
+    (then factor is its G): each chunk's grid is resampled to the plan's frames.  dd: None or (dead limit, max_gap),
+    with a plan: repeated frames are re-timed (retime.py).
+
+    Sizes.  A chunk is read with `look` lookahead frames behind its C + 1 own: 0, 1 with scene_cut; with dd max_gap - 1,
+    and max_gap with scene_cut too.  A read that comes up short of C + 1 + look frames is the clip's last chunk, and
+    holds whatever is left: up to C + look - 1 intervals (C when look is 0 or 1).  `tail` is that bound, and the
+    pinned output slots and their device twins are sized for it; the pinned input slots and the device input twins
+    hold C + 1 + look frames, and the reader carries 1 + look of them over.  (C = 1, max_gap 4: 5 frames per read, 4
+    carried; a clip of 4 frames is one last chunk of 3 intervals, one of 5 a chunk of 1 interval and a last of 3.)"""
     dev = next(model.parameters()).device
     C, look = chunk_frames, 1 if thr is not None else 0
-    in_rows, out_rows = C + 1 + look, C * factor + 1
+    if dd is not None:
+        look = dd[1] if thr is not None else dd[1] - 1
+    tail = C + max(look - 1, 0)
+    in_rows, out_rows = C + 1 + look, tail * factor + 1
     if plan is not None:
-        out_rows = -(-C * plan.q // plan.p) + 1
+        out_rows = -(-tail * plan.q // plan.p) + 1
     in_slots = [torch.empty((in_rows, route.row), dtype=route.tdtype).pin_memory() for _ in range(R_IN)]
     out_slots = [torch.empty((out_rows, route.out_row), dtype=route.tdtype).pin_memory() for _ in range(R_OUT)]
     in_np = [s.numpy().view(route.ndtype) for s in in_slots]
@@ -428,6 +473,7 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
                                        for _ in range(R_OUT)]
     count = route.row       # samples per frame, as scene.detect_cuts counts them
     carried = None          # int64 [1]: the previous chunk's last interval sum
+    dead_before = 0         # dd: dead intervals directly before this chunk, saturated at max_gap
     total, j = 0, 0
     try:
         while True:
@@ -446,17 +492,30 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
                 up.record(h2d)
             compute.wait_event(up)
             d = d_in[j][:m]
-            flags = None
+            flags = seen = None
             if thr is not None and c > 0:
-                sums = scene.pair_sad([d], route.bits)   # c own intervals, then the lookahead interval if read
+                sums = scene.pair_sad([d], route.bits)   # c own intervals, then the lookahead intervals that were read
                 window = sums if carried is None else torch.cat([carried, sums])
                 scores, fl = scene.score_window(window, count, route.bits, thr)
                 off = 0 if carried is None else 1
                 flags = fl[off:off + c]
+                seen = fl[off:off + m - 1]   # every interval read (the last one's score lacks a neighbour: not used)
                 carried = sums[c - 1:c]
                 if scene_log is not None:
                     scene_log.append((scores[off:off + c].cpu().numpy(), flags.cpu().numpy()))
-            out = route.run(d[:c + 1], factor)   # (a one-frame clip: the frame itself)
+            spans, ext, cuts = [], 0, None
+            if dd is not None and c > 0:
+                # the plan of this chunk depends on its data: one small read of the dead (and cut) flags, which waits
+                # for the compute stream, the previous chunk's forwards included: the price of `dedup`
+                peaks, dead, cuts = _dead_and_cuts(d, route.bits, dd[0], seen)
+                spans, ext, dead_before = _retime.classify_chunk(dead, cuts, dead_before, s, c, dd[1])
+                if dedup_log is not None:
+                    dedup_log.append((peaks[:c].cpu().numpy(), dead[:c].copy()))
+                if ext and seen is not None:
+                    flags = seen[:c + ext]
+            # with a span across the chunk's end, the grid goes on over the ext <= max_gap - 1 lookahead intervals that
+            # the span needs (ext <= look, and the last chunk has ext == 0: no span reaches past the clip)
+            out = route.run(d[:c + 1 + ext], factor)   # (a one-frame clip: the frame itself)
             _hold(flags, factor, out)
             d_free[j] = torch.cuda.Event()
             d_free[j].record(compute)
@@ -465,8 +524,13 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
             else:
                 # (pinned slot o is free, so the D2H copy that last read d_out[o] has completed)
                 j0, nj = plan.span(s, c, last)
-                rows = _retime.resample(out, plan, s, j0, nj, bits=route.bits, flags=flags, mode=mode,
-                                        out=d_out[o][:nj])
+                if dd is None:
+                    rows = _retime.resample(out, plan, s, j0, nj, bits=route.bits, flags=flags, mode=mode,
+                                            out=d_out[o][:nj])
+                else:   # (every row an entry names is checked against `out` here, and again behind the C ABI)
+                    entries = _retime.table_entries(plan, spans, s, j0, nj, c + ext, mode,
+                                                    None if cuts is None else cuts[:c + ext])
+                    rows = _retime.resample_table(out, entries, route.bits, out=d_out[o][:nj])
                 out = None   # the grid is used on the compute stream alone: it may go back to the allocator now
             with torch.cuda.stream(d2h):
                 d2h.wait_stream(compute)
@@ -501,9 +565,11 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
 
 
 @torch.no_grad()
-def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode: str, n_frames=None) -> int:
+def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode: str, n_frames=None, dd=None,
+               dedup_log=None, scene_log=None) -> int:
     """The resident form of `_run`: the whole clip on the device as one chunk (flags once over every sample of the
-    packed rows, one run of the route, one hold at the full factor; with a plan: one grid, one resample).  n_frames: the
+    packed rows, one run of the route, one hold at the full factor; with a plan: one grid, one resample; with dd: one
+    read of the dead and cut flags, one table).  n_frames: the
     clip's frame count where it is known up front (a regular file): the clip is then read into one array; a stream of
     unknown length is uploaded 64 frames at a time, so that the host never holds it twice."""
     dev = next(model.parameters()).device
@@ -531,14 +597,26 @@ def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode
         del parts
     flags = None
     if thr is not None and d.shape[0] > 1:
-        flags = scene.detect_cuts([d], thr, route.bits)[1]
+        scores, flags = scene.detect_cuts([d], thr, route.bits)
+        if scene_log is not None:
+            scene_log.append((scores.cpu().numpy(), flags.cpu().numpy()))
     grid = route.run(d, factor)
     _hold(flags, factor, grid)
     if plan is None:   # (the raw route without fps: the factor run's frames as they are)
         write(grid.cpu().numpy().view(route.ndtype))
         return grid.shape[0]
     n = plan.n_out(d.shape[0])
-    rows = _retime.resample(grid, plan, 0, 0, n, bits=route.bits, flags=flags, mode=mode)
+    if dd is None:
+        rows = _retime.resample(grid, plan, 0, 0, n, bits=route.bits, flags=flags, mode=mode)
+    else:
+        spans, cuts = [], None
+        if d.shape[0] > 1:
+            peaks, dead, cuts = _dead_and_cuts(d, route.bits, dd[0], flags)
+            spans = _retime.dedup_spans(dead, cuts, dd[1])
+            if dedup_log is not None:
+                dedup_log.append((peaks.cpu().numpy(), dead.copy()))
+        entries = _retime.table_entries(plan, spans, 0, 0, n, d.shape[0] - 1, mode, cuts)
+        rows = _retime.resample_table(grid, entries, route.bits)
     write(rows.cpu().numpy().view(route.ndtype))
     return n
 
@@ -578,7 +656,7 @@ def _open_sink(dst):
 def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
                            matrix: str = "bt709", siting: str | None = None, scene_cut: float | None = None,
                            scene_log: list | None = None, fps=None, src_fps=None, time_depth: int = 2,
-                           retime: str = "blend") -> int:
+                           retime: str = "blend", dedup=None, max_gap: int = 4, dedup_log: list | None = None) -> int:
     """Y4M in (a path or a readable binary file: a pipe, `sys.stdin.buffer`) -> Y4M out (a path or a writable binary
     file), or a `.npy` path of the luma frames (grayscale network; the input must then be a regular file, whose frame
     count a first pass reads).  This is what `FrameInterpolator.interpolate_video` runs; the result is the same, byte
@@ -586,11 +664,16 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     output header has the input's `C` tag, rate x factor, and the input's `XCOLORRANGE` except on the 8-bit grayscale
     route, which writes none.  Returns the output frame count.  Every argument
     is checked before anything is pinned, before any GPU work and before the output exists.  scene_log: a list that
-    receives (scores float64, flags uint8) host arrays of each chunk's intervals (tests; costs a synchronise).
+    receives (scores float64, flags uint8) host arrays of each chunk's intervals (a resident run: of the clip's, once;
+    costs a synchronise).
     fps / src_fps / time_depth / retime: frame-rate conversion (retime.py): the output has `fps` frames per second,
-    resampled from a 2**time_depth bisection; src_fps overrides the header's rate; factor stays 2."""
+    resampled from a 2**time_depth bisection; src_fps overrides the header's rate; factor stays 2.
+    dedup / max_gap: re-time repeated frames (retime.py): dedup is None (off) or a tolerance >= 0 in
+    code values, max_gap (2..8) the longest run of equal frames that is re-timed; with `factor` (at most 16) or with
+    `fps`.  dedup_log: a list that receives (peaks, dead) host arrays of each chunk's intervals (scene_log's twin)."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
+    tol, gap = check_dedup(dedup, max_gap, fps, factor)
     npy_out = isinstance(dst, (str, os.PathLike)) and os.fspath(dst).lower().endswith(".npy")
     if npy_out:
         if not _is_path(src) or not stat.S_ISREG(os.stat(src).st_mode):
@@ -605,13 +688,14 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
             fps = (hdr["fps"][0] * factor, hdr["fps"][1])
         else:
             factor, fps = plan.G, (plan.fps.numerator, plan.fps.denominator)
+        plan, dd = _dedup_of(tol, gap, plan, factor)   # (without fps: p / q = 1 / factor; the header's rate as above)
 
         def run(write):
             if C is None:
                 count = (imageio_lite.y4m_frame_count(src)
                          if _is_path(src) and stat.S_ISREG(os.stat(src).st_mode) else None)
-                return _run_whole(model, route, reader, write, factor, thr, plan, mode, count)
-            return _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode)
+                return _run_whole(model, route, reader, write, factor, thr, plan, mode, count, dd, dedup_log, scene_log)
+            return _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log)
         if npy_out:
             n = imageio_lite.y4m_frame_count(src)
             shape = ((n - 1) * factor + 1 if plan is None else plan.n_out(n), hdr["height"], hdr["width"])
@@ -640,7 +724,8 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
 
 def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
                            scene_cut: float | None = None, scene_log: list | None = None, fps=None, src_fps=None,
-                           time_depth: int = 2, retime: str = "blend") -> int:
+                           time_depth: int = 2, retime: str = "blend", dedup=None, max_gap: int = 4,
+                           dedup_log: list | None = None) -> int:
     """`.npy` stack in (uint8 [N,H,W] or [N,H,W,C], read through `np.load(mmap_mode="r")`) -> `.npy` out (written
     through `np.lib.format.open_memmap`, the file `np.save` would write; a name without `.npy` gets it).  An
     [N,H,W,C] stack goes through the RGB network, or channel by channel through the grayscale one.  Returns the output
@@ -648,9 +733,11 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     stack carries no rate, so `fps` needs `src_fps`."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
+    tol, gap = check_dedup(dedup, max_gap, fps, factor)
     plan = _plan_of(fps, src_fps, None, depth)
     if plan is not None:
         factor = plan.G
+    plan, dd = _dedup_of(tol, gap, plan, factor)
     if not _is_path(dst):
         raise ValueError("a .npy output is a path")
     dst = os.fspath(dst)
@@ -667,9 +754,10 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     ok = False
     try:
         if C is None:
-            total = _run_whole(model, route, _NpyRows(mm), sink.write, factor, thr, plan, mode, mm.shape[0])
+            total = _run_whole(model, route, _NpyRows(mm), sink.write, factor, thr, plan, mode, mm.shape[0], dd,
+                               dedup_log, scene_log)
         else:
-            total = _run(model, route, _NpyRows(mm), sink.write, factor, C, thr, scene_log, plan, mode)
+            total = _run(model, route, _NpyRows(mm), sink.write, factor, C, thr, scene_log, plan, mode, dd, dedup_log)
         ok = True
     finally:
         sink.close(ok)
@@ -679,7 +767,8 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
 def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12", width=None, height=None,
                            batch: int = 8, chunk_frames: int | None = 32, matrix: str = "bt709",
                            siting: str | None = None, scene_cut: float | None = None, scene_log: list | None = None,
-                           fps=None, src_fps=None, time_depth: int = 2, retime: str = "blend") -> int:
+                           fps=None, src_fps=None, time_depth: int = 2, retime: str = "blend", dedup=None,
+                           max_gap: int = 4, dedup_log: list | None = None) -> int:
     """Headerless raw video in (a path or a readable binary file: a pipe) -> the same format out (a path or a writable
     binary file): tight NV12 frames of height x width (`ffmpeg ... -f rawvideo -pix_fmt nv12 -`) through the RGB
     network, `interpolate_sequence_nv12` per level; or, with raw "rgb24" / "bgr24" / "rgba" / "bgra", tight packed RGB
@@ -697,11 +786,13 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
         raise ValueError("raw video carries no frame rate: pass src_fps")
     src_rate = _retime.parse_fps(src_fps)
     fps, _, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
+    tol, gap = check_dedup(dedup, max_gap, fps, factor)
     npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
     route = _raw_route(model, raw, height, width, npy_out, batch, matrix, siting)
     plan = _plan_of(fps, src_rate, None, depth)
     if plan is not None:
         factor = plan.G
+    plan, dd = _dedup_of(tol, gap, plan, factor)
     wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire
     count = None
     if _is_path(src):
@@ -724,9 +815,10 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
             def write(rows):
                 f.write(np.ascontiguousarray(rows).data)
             if C is None:
-                total = _run_whole(model, route, reader, write, factor, thr, plan, mode, count)
+                total = _run_whole(model, route, reader, write, factor, thr, plan, mode, count, dd, dedup_log,
+                                   scene_log)
             else:
-                total = _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode)
+                total = _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log)
             ok = True
         finally:
             finish(ok)
@@ -736,5 +828,5 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
             fin.close()
 
 
-__all__ = ["check_chunk_frames", "check_retime", "interpolate_y4m_stream", "interpolate_npy_stream",
+__all__ = ["check_chunk_frames", "check_retime", "check_dedup", "interpolate_y4m_stream", "interpolate_npy_stream",
            "interpolate_raw_stream"]

@@ -37,7 +37,9 @@ extern "C" {
                                      the same way: Farneback flow and flow-compensated warps (fiunet_flow_workspace_bytes,
                                      fiunet_farneback_flow, fiunet_flow_warp, fiunet_flow_mode); v8 also, added the same
                                      way: the plane metrics on interleaved samples (fiunet_interleaved_psnr,
-                                     fiunet_stepped_ssim) */
+                                     fiunet_stepped_ssim); v8 also, added the same way: repeated frames in video
+                                     (fiunet_pair_peak_u8, fiunet_pair_peak_p10, fiunet_retime_table_u8,
+                                     fiunet_retime_table_p10) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -465,6 +467,35 @@ int fiunet_retime_u8(const uint8_t* grid, int n_intervals, size_t frame_samples,
 int fiunet_retime_p10(const uint16_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
                       uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint16_t* out,
                       void* stream);
+
+/* Repeated frames in video (ABI v8, added without a version bump: nothing existing changed).
+ * peak[i] = the largest sum of |F[i+1] - F[i]| over the aligned 64-sample segments of a frame of frame_samples samples,
+ * counted from its first sample (the last segment may be short; 10-bit samples above 1023 read as 1023): a frame-wide
+ * mean hides a small moving object, a maximum over short segments does not.  MAX-ACCUMULATES into peaks[n_frames - 1]
+ * (uint32, zeroed by the caller), so several planar stacks of the same frames can share one result.  Exact in any order.
+ * Calling conventions of fiunet_pair_sad_*: device pointers, asynchronous on `stream`, no allocation, no
+ * synchronisation, n_frames < 2 is a no-op, FIUNET_ERR_INVALID_ARG on NULL pointers or n_frames < 0. */
+int fiunet_pair_peak_u8(const uint8_t* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream);
+int fiunet_pair_peak_p10(const uint16_t* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream);
+
+/* Table-driven resampling: output row k of out[n_out][frame_samples] is, with e = entries[k] and A = row e.row of
+ * grid[n_rows][frame_samples], B the row after it,
+ *   e.wn == 0   a byte copy of A (B is not read)
+ *   else        (A * (e.den - e.wn) + B * e.wn + e.den / 2) / e.den per sample in integers; 10-bit words above 1023
+ *               read as 1023
+ * `entries` is HOST memory, read during the call: every entry is checked before the first launch and the entries
+ * travel in the kernels' arguments (64 output frames per launch), so there is no device table and no copy, nothing of
+ * the array is needed once the call has returned, and the call can be captured into a graph.  grid and out are device
+ * pointers; asynchronous on `stream`; no allocation, no synchronisation; n_out == 0 is a no-op.
+ * FIUNET_ERR_INVALID_ARG, before any launch and before a pointer is used: NULL grid / out / entries, a negative count,
+ * or an entry with row >= n_rows, wn >= den, wn > 0 and row + 1 >= n_rows, or den outside 1 .. 2^20. */
+typedef struct fiunet_retime_entry {
+    uint32_t row, wn, den;
+} fiunet_retime_entry;
+int fiunet_retime_table_u8(const uint8_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
+                           int n_out, uint8_t* out, void* stream);
+int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
+                            int n_out, uint16_t* out, void* stream);
 
 /* Replaces preprocess_image's arithmetic (model/inference.py:31-35): out = 2*(in/255) - 1. */
 int fiunet_preprocess_u8(const uint8_t* in, float* out, size_t n, void* stream);
