@@ -54,6 +54,8 @@ SYMBOLS = (
     "fiunet_workspace_bytes_yuv", "fiunet_forward_yuv", "fiunet_forward_yuv_p10",
     # Farneback flow and flow-compensated warps
     "fiunet_flow_workspace_bytes", "fiunet_farneback_flow", "fiunet_flow_warp",
+    # resizing frame planes
+    "fiunet_resize_planes_u8", "fiunet_resize_planes_p10",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -79,6 +81,13 @@ def _surface(layout, frame_stride: int):
 class RetimeEntry(ctypes.Structure):
     """include/fiunet.h: fiunet_retime_entry (output row = grid row `row`, blended with the row after it by wn / den)."""
     _fields_ = [("row", ctypes.c_uint32), ("wn", ctypes.c_uint32), ("den", ctypes.c_uint32)]
+
+
+class ResizePlane(ctypes.Structure):
+    """include/fiunet.h: fiunet_resize_plane (sample (y, x) of frame f at offset + f * frame_stride + y * pitch + x *
+    step, everything in samples)."""
+    _fields_ = [("offset", ctypes.c_size_t), ("pitch", ctypes.c_size_t), ("frame_stride", ctypes.c_size_t),
+                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("step", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class PackedLayout(ctypes.Structure):
@@ -186,6 +195,8 @@ def lib() -> ctypes.CDLL:
     L.fiunet_pair_peak_p10.argtypes = [vp, ci, sz, vp, vp]
     L.fiunet_retime_table_u8.argtypes = [vp, ci, sz, vp, ci, vp, vp]
     L.fiunet_retime_table_p10.argtypes = [vp, ci, sz, vp, ci, vp, vp]
+    L.fiunet_resize_planes_u8.argtypes = [vp, vp, vp, vp, ci, ci, vp]
+    L.fiunet_resize_planes_p10.argtypes = [vp, vp, vp, vp, ci, ci, vp]
     L.fiunet_nv12_to_rgb_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_rgb_to_nv12_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_p010_to_rgb_p10.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
@@ -704,6 +715,43 @@ def pair_peak(frames: "torch.Tensor", peaks: "torch.Tensor", bits: int) -> None:
     fn = lib().fiunet_pair_peak_p10 if bits == 10 else lib().fiunet_pair_peak_u8
     s = _stream(frames)
     check(fn(frames.data_ptr(), n, fs, peaks.data_ptr(), s), "fiunet_pair_peak_" + ("p10" if bits == 10 else "u8"))
+
+
+def resize_plane_array(planes):
+    """A sequence of (offset, h, w, pitch, step, frame_stride) int tuples, in samples -> the C array of
+    fiunet_resize_plane.  ValueError on a value that does not fit its field (the library checks the rest)."""
+    arr = (ResizePlane * max(len(planes), 1))()
+    for k, (off, h, w, pitch, step, fs) in enumerate(planes):
+        if not all(0 <= v < 1 << 64 for v in (off, pitch, fs)) or not all(-(1 << 31) <= v < 1 << 31 for v in (h, w, step)):
+            raise ValueError(f"plane {k} = {(off, h, w, pitch, step, fs)} does not fit fiunet_resize_plane")
+        arr[k] = ResizePlane(off, pitch, fs, h, w, step, 0)
+    return arr
+
+
+def _resize_extent(planes, n_frames: int) -> int:
+    """Samples from the buffer's start to the end of the last frame's last plane (0 for no frames)."""
+    if n_frames < 1:
+        return 0
+    return max(off + (n_frames - 1) * fs + (h - 1) * pitch + (w - 1) * step + 1 for off, h, w, pitch, step, fs in planes)
+
+
+def resize_planes(src: "torch.Tensor", src_planes, dst: "torch.Tensor", dst_planes, n_frames: int, bits: int,
+                  stream=None) -> None:
+    """fiunet_resize_planes_u8 / fiunet_resize_planes_p10: plane i of `src_planes` of every one of n_frames frames of the
+    dense buffer `src` (uint8 at 8 bits; 16-bit words at 10) -> plane i of `dst_planes` of `dst`.  A plane is (offset, h,
+    w, pitch, step, frame_stride) in samples from the tensor's first element.  ValueError, before the call, where well-
+    formed planes reach past either tensor."""
+    src_planes, dst_planes = [tuple(int(v) for v in p) for p in src_planes], [tuple(int(v) for v in p) for p in dst_planes]
+    if len(src_planes) != len(dst_planes):
+        raise ValueError(f"{len(src_planes)} source planes for {len(dst_planes)} destination planes")
+    for name, t, planes in (("src", src, src_planes), ("dst", dst, dst_planes)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be a dense buffer (the planes carry the pitches)")
+        if all(min(p) >= 0 and p[1] >= 1 and p[2] >= 1 for p in planes) and _resize_extent(planes, n_frames) > t.numel():
+            raise ValueError(f"the {name} planes reach sample {_resize_extent(planes, n_frames)} of a buffer of {t.numel()}")
+    fn = lib().fiunet_resize_planes_p10 if bits == 10 else lib().fiunet_resize_planes_u8
+    check(fn(src.data_ptr(), resize_plane_array(src_planes), dst.data_ptr(), resize_plane_array(dst_planes),
+             len(src_planes), n_frames, _stream(src, stream)), "fiunet_resize_planes_" + ("p10" if bits == 10 else "u8"))
 
 
 def retime_entries(entries):

@@ -57,6 +57,12 @@ the held-out frames next to a hard cut out of the summary:
 
     ffmpeg -i clip.mkv -f rawvideo -pix_fmt nv12 - | python -m ai_based_frame_interpolation_amd.cli evaluate \\
         --input - --raw nv12 --size 1920x1080 --src-fps 24 --model rgb_model.pth --scene-cut 10 --json scores.json
+
+`--resize WIDTHxHEIGHT` on either command resizes every frame on the GPU right after its upload (resize.py, DESIGN.md
+3.3q): `video` then writes a clip of that size, `evaluate` scores the checkpoint at that size - 256x256 is what the
+reference trains and evaluates at - and says so in its table.  --size stays the size of the --raw source.
+
+    python -m ai_based_frame_interpolation_amd.cli evaluate --input clip.y4m --resize 256x256 --model best_model.pth
 """
 from __future__ import annotations
 
@@ -159,6 +165,9 @@ def parser() -> argparse.ArgumentParser:
                    help="Headerless raw video in and out (tight NV12, packed RGB or 4:2:2 / 4:4:4 YUV frames, named as "
                         "ffmpeg's -pix_fmt); needs --size and --src-fps")
     v.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
+    v.add_argument("--resize", type=_size, default=None, metavar="WIDTHxHEIGHT",
+                   help="Resize every frame on the GPU before it is interpolated; the output has this size (--size "
+                        "stays the size of the --raw source)")
     e = sub.add_parser("evaluate", help="Score a checkpoint on a clip by hold-out (Y4M, .npy or --raw; '-' is stdin)")
     e.add_argument("--input", required=True,
                    help="Clip to score: a .y4m or .npy path, or - for standard input (Y4M, or --raw video)")
@@ -181,6 +190,9 @@ def parser() -> argparse.ArgumentParser:
     e.add_argument("--raw", default=None, choices=RAW_CHOICES,
                    help="Headerless raw video (tight frames, named as ffmpeg's -pix_fmt); needs --size")
     e.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
+    e.add_argument("--resize", type=_size, default=None, metavar="WIDTHxHEIGHT",
+                   help="Resize the clip on the GPU before frames are held out and score it at this size, such as the "
+                        "256x256 a checkpoint was trained at (--size stays the size of the --raw source)")
     e.add_argument("--scene-cut", type=_scene_cut, default=None,
                    help="Scene-cut threshold in (0, 100], or none: held-out frames next to a cut are left out of the "
                         "summary")
@@ -233,7 +245,8 @@ def run_video(a: argparse.Namespace) -> int:
     n = fi.interpolate_video(src, dst, a.factor, matrix=a.matrix, siting=a.siting, scene_cut=a.scene_cut,
                              chunk_frames=a.chunk_frames, fps=a.fps, src_fps=a.src_fps, time_depth=a.time_depth,
                              retime=a.retime, raw=a.raw, width=a.size[0] if a.size else None,
-                             height=a.size[1] if a.size else None, dedup=a.dedup, max_gap=a.max_gap, **logs)
+                             height=a.size[1] if a.size else None, dedup=a.dedup, max_gap=a.max_gap,
+                             resize=a.resize, **logs)
     if a.dedup is not None:
         print(f"re-timed {retimed_repeats(logs['dedup_log'], logs['scene_log'], a.max_gap)} repeated frames",
               file=sys.stderr)
@@ -255,7 +268,7 @@ def run_evaluate(a: argparse.Namespace) -> dict:
     res = holdout.score_video(model, src, triplets=a.triplets, methods=a.methods, batch=a.batch,
                               chunk_frames=a.chunk_frames, matrix=a.matrix, siting=a.siting, src_fps=a.src_fps,
                               raw=a.raw, width=a.size[0] if a.size else None, height=a.size[1] if a.size else None,
-                              scene_cut=a.scene_cut)
+                              scene_cut=a.scene_cut, resize=a.resize)
     print(holdout.summary_table(res), file=sys.stderr)
     if a.json:
         with open(a.json, "w") as f:

@@ -16,6 +16,7 @@
 #include "yuv4xx.hip.h"
 #include "scene.hip.h"
 #include "retime.hip.h"
+#include "resize.hip.h"
 #include "weights.hip.h"
 #include "flow.hip.h"
 
@@ -2635,6 +2636,104 @@ int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_sampl
                             int n_out, uint16_t* out, void* stream)
 {
     return retime_table(grid, n_rows, frame_samples, entries, n_out, out, stream);
+}
+
+// ---- resizing frame planes (csrc/resize.hip.h) ------------------------------------------------------
+extern "C++" {
+// the byte range [lo, hi) that n frames of the planes cover, from the buffer's first sample
+static void resize_extent(const fiunet_resize_plane* planes, int n_planes, int n_frames, size_t& lo, size_t& hi)
+{
+    lo = SIZE_MAX, hi = 0;
+    for (int i = 0; i < n_planes; ++i) {
+        const fiunet_resize_plane& p = planes[i];
+        const size_t end = p.offset + (size_t)(n_frames - 1) * p.frame_stride + (size_t)(p.h - 1) * p.pitch +
+                           (size_t)(p.w - 1) * p.step + 1;
+        lo = std::min(lo, p.offset), hi = std::max(hi, end);
+    }
+}
+
+static const char* resize_check_plane(const fiunet_resize_plane& p)
+{
+    if (p.h < 1 || p.w < 1) return "a plane's h and w must be positive";
+    if (p.h > kResizeMaxSize || p.w > kResizeMaxSize) return "a plane's h and w must not exceed 2^24";
+    if (p.step < 1 || p.step > 4) return "a plane's step must be 1..4";
+    if (p.pitch < (size_t)(p.w - 1) * p.step + 1) return "a plane's pitch must cover a row: (w - 1) * step + 1";
+    // (h, w <= 2^24, step <= 4: the row term is below 2^26; the others are checked against wrapping)
+    const size_t row = (size_t)(p.w - 1) * p.step + 1;
+    if (p.h > 1 && p.pitch > (SIZE_MAX - row) / (size_t)(p.h - 1)) return "a plane's pitch is too large";
+    const size_t body = (size_t)(p.h - 1) * p.pitch + row;
+    if (p.offset > p.frame_stride || body > p.frame_stride - p.offset) return "a plane must lie inside its frame stride";
+    return nullptr;
+}
+
+template <typename T>
+static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, const fiunet_resize_plane* dp,
+                         int n_planes, int n_frames, void* stream)
+{
+    if (!src || !dst || !sp || !dp) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (((uintptr_t)src | (uintptr_t)dst) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
+    if (n_planes < 1 || n_planes > kResizeMaxPlanes) return fail(FIUNET_ERR_INVALID_ARG, "n_planes must be 1..4");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    constexpr int V = ResizeSample<T>::kVec;
+    ResizeArgs base = {};
+    unsigned long long per_frame_max = 0;
+    for (int i = 0; i < n_planes; ++i) {
+        for (const fiunet_resize_plane* p : {&sp[i], &dp[i]}) {
+            if (const char* why = resize_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
+            // n frames of the plane stay inside the address space
+            if (n_frames > 1 && p->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_frames)
+                return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+        }
+        ResizePlane& P = base.p[i];
+        P.src_off = sp[i].offset, P.src_pitch = sp[i].pitch, P.src_fs = sp[i].frame_stride;
+        P.dst_off = dp[i].offset, P.dst_pitch = dp[i].pitch, P.dst_fs = dp[i].frame_stride;
+        P.sh = sp[i].h, P.sw = sp[i].w, P.dh = dp[i].h, P.dw = dp[i].w;
+        P.sstep = sp[i].step, P.dstep = dp[i].step;
+        P.sx = (double)P.sw / (double)P.dw, P.sy = (double)P.sh / (double)P.dh;
+        P.chunks = (unsigned)((P.dw + V - 1) / V) + (P.dstep == 1 ? 1u : 0u);
+        const unsigned long long per_frame = (unsigned long long)P.dh * P.chunks;
+        if (per_frame >= (1ull << 31)) return fail(FIUNET_ERR_UNSUPPORTED, "a destination plane of 2^31 or more store chunks");
+        per_frame_max = std::max(per_frame_max, per_frame);
+    }
+    if (n_frames == 0) return FIUNET_OK;
+    size_t slo, shi, dlo, dhi;
+    resize_extent(sp, n_planes, n_frames, slo, shi);
+    resize_extent(dp, n_planes, n_frames, dlo, dhi);
+    const uintptr_t s0 = (uintptr_t)src + slo * sizeof(T), s1 = (uintptr_t)src + shi * sizeof(T);
+    const uintptr_t d0 = (uintptr_t)dst + dlo * sizeof(T), d1 = (uintptr_t)dst + dhi * sizeof(T);
+    if (s0 < d1 && d0 < s1) return fail(FIUNET_ERR_INVALID_ARG, "source and destination overlap");
+    // frames per launch: every plane's item count stays below 2^31
+    const int batch = (int)std::min<unsigned long long>(((1ull << 31) - 1) / per_frame_max, (unsigned long long)n_frames);
+    for (int f0 = 0; f0 < n_frames; f0 += batch) {
+        const int nf = std::min(batch, n_frames - f0);
+        ResizeArgs args = base;
+        unsigned items_max = 0;
+        for (int i = 0; i < n_planes; ++i) {
+            ResizePlane& P = args.p[i];
+            P.src_off += (size_t)f0 * P.src_fs, P.dst_off += (size_t)f0 * P.dst_fs;
+            P.items = (unsigned)nf * (unsigned)P.dh * P.chunks;
+            items_max = std::max(items_max, P.items);
+        }
+        // one item per thread up to 8192 workgroups (32 per CU), a grid-stride loop beyond
+        const unsigned bx = std::min((items_max + kResizeBlock - 1) / kResizeBlock, 8192u);
+        hipLaunchKernelGGL(resize_planes_kernel<T>, dim3(bx, (unsigned)n_planes), dim3(kResizeBlock), 0,
+                           (hipStream_t)stream, src, dst, args);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_resize_planes_u8(const uint8_t* src, const fiunet_resize_plane* src_planes, uint8_t* dst,
+                            const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream)
+{
+    return resize_planes(src, src_planes, dst, dst_planes, n_planes, n_frames, stream);
+}
+
+int fiunet_resize_planes_p10(const uint16_t* src, const fiunet_resize_plane* src_planes, uint16_t* dst,
+                             const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream)
+{
+    return resize_planes(src, src_planes, dst, dst_planes, n_planes, n_frames, stream);
 }
 
 // diagnostic (not part of the ABI, no declaration in include/fiunet.h): override choose_conv_cfg for one conv (1..17) of

@@ -43,6 +43,10 @@ chunk.
              frame is scored exactly once and a pair's forward does not depend on the pairs that share its call
              (`_padded_chunk`), so the result is the same to the last bit for every chunk_frames.
 
+  resize     with `resize=` (resize.py) every uploaded chunk is resized on the device before frames are
+             dropped: the held-out truth is the resized frame, the protocol of the reference's evaluator, and the route,
+             planes, groups and pixel counts are those of the destination size; the host buffer keeps source frames.
+
 Out of scope: pitched raw input, several GPUs.
 """
 from __future__ import annotations
@@ -55,10 +59,11 @@ import numpy as np
 import torch
 
 from . import colour, imageio_lite, metrics, optical_flow, packed, scene
+from . import resize as _resize
 from . import retime as _retime
 from .inference import _interleave_average_p10, _interleave_average_u8
-from .stream import (RAW_FORMATS, _NpyRows, _RawReader, _is_path, _npy_route, _raw_route, _y4m_route,
-                     check_chunk_frames)
+from .stream import (RAW_FORMATS, _NpyRows, _RawReader, _is_path, _npy_route, _raw_resize, _raw_route, _y4m_resize,
+                     _y4m_route, check_chunk_frames)
 
 TRIPLETS = ("sliding", "disjoint")
 METHODS = ("unet", "linear", "repeat")
@@ -128,8 +133,9 @@ class _Source:
     `psnr_interleaved` call (w: samples per component and row); lead: the plane names the flow is estimated on (one:
     that plane; three: their rounded mean)."""
 
-    def __init__(self, route, reader, planes, channels, fps, close, groups=(), lead=None):
+    def __init__(self, route, reader, planes, channels, fps, close, groups=(), lead=None, rs=None):
         self.route, self.reader, self.channels, self.fps, self.close = route, reader, channels, fps, close
+        self.rs = rs   # None or a resize.FrameResize: the reader's frames are resized to the route's after upload
         self.planes = [tuple(p) + (p[3], 1) if len(p) == 4 else tuple(p) for p in planes]
         self.groups, self.lead = list(groups), lead or (self.planes[0][0],)
 
@@ -163,12 +169,16 @@ def raw_planes(raw: str, height: int, width: int):
     return [("y", 0, h, w, w, 1), ("u", h * w, h, cw, cw, 1), ("v", h * w + h * cw, h, cw, cw, 1)], []
 
 
-def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height) -> _Source:
+def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size=None) -> _Source:
     if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
         raise ValueError(f"raw={raw!r} describes headerless video; a .npy stack carries its own shape (leave raw None)")
     route = _raw_route(model, raw, height, width, False, batch, matrix, siting)
-    planes, groups = raw_planes(raw, height, width)
-    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire
+    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
+    rs = None
+    if size is not None:   # the route, the planes and the groups of the destination size
+        rs = _raw_resize(raw, route.bits, height, width, size)
+        route = _raw_route(model, raw, size[1], size[0], False, batch, matrix, siting)
+    planes, groups = raw_planes(raw, height, width) if size is None else raw_planes(raw, size[1], size[0])
     if _is_path(src):
         if not os.path.exists(src):
             raise FileNotFoundError(f"Video file not found: {src}")
@@ -181,31 +191,39 @@ def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height) ->
                 raise _too_short(st.st_size // wire_row)
     fin = open(src, "rb") if _is_path(src) else src
     return _Source(route, _RawReader(fin, wire_row), planes, 0, src_fps, fin.close if _is_path(src) else (lambda: None),
-                   groups, ("r", "g", "b") if raw in packed.FORMATS else ("y",))
+                   groups, ("r", "g", "b") if raw in packed.FORMATS else ("y",), rs)
 
 
-def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, height=None) -> _Source:
+def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, height=None, size=None) -> _Source:
     if raw is not None:
-        return _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height)
+        return _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size)
     if width is not None or height is not None:
         raise ValueError("width and height describe raw video: pass raw= with them")
     if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
         mm = np.load(src, mmap_mode="r")
         if mm.dtype != np.uint8 or mm.ndim not in (3, 4):
             raise ValueError("expected a uint8 .npy stack [N,H,W] or [N,H,W,3]")
-        route = _npy_route(model, mm.shape[1:], batch)
+        shape, rs = tuple(mm.shape[1:]), None
+        if size is not None:
+            kind = "npy" if len(shape) == 2 else ("npy", shape[2])
+            rs = _resize.FrameResize(_resize.frame_planes(kind, shape[0], shape[1]),
+                                     _resize.frame_planes(kind, size[1], size[0]), 8, size, (shape[1], shape[0]))
+            shape = (size[1], size[0]) + shape[2:]
+        route = _npy_route(model, shape, batch)
         if mm.shape[0] < 3:
             raise _too_short(mm.shape[0])
-        h, w = mm.shape[1:3]
+        h, w = shape[:2]
         if mm.ndim == 3:
             planes, channels = [("gray", 0, h, w)], 0
         else:
             channels = mm.shape[3]
             planes = [(f"c{i}", i * h * w, h, w) for i in range(channels)]
-        return _Source(route, _NpyRows(mm), planes, channels, src_fps, lambda: None)
+        return _Source(route, _NpyRows(mm), planes, channels, src_fps, lambda: None, rs=rs)
     reader = imageio_lite.Y4MReader(src)
     try:
-        hdr = reader.header
+        hdr, rs = reader.header, None
+        if size is not None:
+            rs, hdr = _y4m_resize(hdr, size), _resize.y4m_header_at(hdr, size)
         route = _y4m_route(model, hdr, False, batch, matrix, siting)
         h, w, (hc, wc) = hdr["height"], hdr["width"], hdr["chroma"]
         planes = [("y", 0, h, w)]
@@ -224,7 +242,7 @@ def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, heig
     except BaseException:
         reader.close()
         raise
-    return _Source(route, reader, planes, 0, fps, reader.close)
+    return _Source(route, reader, planes, 0, fps, reader.close, rs=rs)
 
 
 # ---- one chunk on the device ----------------------------------------------------------------------------------------
@@ -370,7 +388,7 @@ def excluded_targets(cut_flags, scored_frames) -> np.ndarray:
 @torch.no_grad()
 def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch: int = 8, chunk_frames: int = 32,
                 matrix: str = "bt709", siting=None, src_fps=None, raw=None, width=None, height=None,
-                scene_cut=None) -> dict:
+                scene_cut=None, resize=None) -> dict:
     """Hold-out scores of `model` on a clip (methods: any of ALL_METHODS; with "optical_flow" or "motion" the result
     also has "flow_backend").  src: a path (.y4m, or a uint8 .npy stack [N,H,W] / [N,H,W,C]) or a
     readable binary file object carrying Y4M (a pipe): what `interpolate_y4m_stream` / `interpolate_npy_stream` take
@@ -381,8 +399,12 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     frames per chunk (memory: chunk_frames + 2 source frames, "disjoint" 2 x chunk_frames + 1, on the host and on the
     device, beside each method's predictions); src_fps: the clip's frame rate where the stream carries none (kept in
     the result for time stamps); scene_cut: None, or scene.py's threshold in (0, 100]: held-out frames next to a cut
-    are left out of the summary (8 bytes per source frame are kept for it).  Every argument is checked before any GPU
-    work.  Returns
+    are left out of the summary (8 bytes per source frame are kept for it).  resize: None, or (width, height) / "WxH":
+    the clip is resized on the device (resize.py) before frames are dropped, so the held-out truth is the
+    resized frame - the protocol of the reference's evaluator, which scores a checkpoint at its training size against a
+    ground truth resized the same way; the route, planes and pixel counts are those of the new size, width / height stay
+    the size of a raw source, and the result gains "resize" [W, H] and "source_size" [w, h].  Every argument is checked
+    before any GPU work.  Returns
 
       {"frames", "triplets", "bits", "peak", "planes", "methods", "fps", "scored_frames": int64 source frame indices,
        "per_frame": {method: {plane: {"psnr": f64[], "ssim": f64[], "sse": uint64[]}}},
@@ -405,11 +427,16 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     thr = scene.check_threshold(scene_cut)
     if src_fps is not None:
         src_fps = _retime.parse_fps(src_fps)
-    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height)
+    size = None if resize is None else _resize.check_size(resize)
+    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height, size)
     try:
-        route, step = source.route, _step(triplets)
+        route, step, rs = source.route, _step(triplets), source.rs
         dev = next(model.parameters()).device
-        buf = np.empty((_nominal(0, c, triplets)[1], route.row), dtype=route.ndtype)
+
+        def upload(a):   # (the host buffer holds frames of the source size)
+            t = torch.from_numpy(a.view(np.int16) if route.bits == 10 else a).to(dev)
+            return t if rs is None else rs(t)
+        buf = np.empty((_nominal(0, c, triplets)[1], route.row if rs is None else rs.row), dtype=route.ndtype)
         have = frames = 0          # rows of buf carried over; frames read so far
         scored, parts = [], []
         sad = []                   # with scene_cut: (first interval, int64 sums) of every chunk: 8 bytes per frame
@@ -424,15 +451,14 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
             if thr is not None and got and have + got >= 2:
                 # every frame read, a trailing one no triplet uses included: the flags are the whole clip's
                 up = have + got
-                d_up = torch.from_numpy(buf[:up].view(np.int16) if route.bits == 10 else buf[:up]).to(dev)
+                d_up = upload(buf[:up])
                 sums = scene.pair_sad(d_up, route.bits).cpu().numpy()
                 # (an interval two chunks share has the same sum in both: only the new ones are kept)
                 sad.append((first + max(have - 1, 0), sums[max(have - 1, 0):]))
             if span is None:
                 break
             _, count, targets = span
-            d_all = (torch.from_numpy(buf[:count].view(np.int16) if route.bits == 10 else buf[:count]).to(dev)
-                     if d_up is None else d_up[:count])
+            d_all = upload(buf[:count]) if d_up is None else d_up[:count]
             parts.append(_score_chunk(source, methods, d_all, len(targets), step, int(batch)))
             scored += targets
             if have + got < want:   # the stream ended inside this chunk
@@ -470,6 +496,8 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
                     "excluded": excluded})
     if any(m in FLOW_METHODS for m in methods):
         out["flow_backend"] = FLOW_BACKEND
+    if rs is not None:
+        out.update({"resize": list(rs.size), "source_size": list(rs.source_size)})
     return out
 
 
@@ -522,8 +550,11 @@ def summary_table(result: dict) -> str:
         n_cuts = len(result["cut_intervals"])
         left_out = f", {int(np.sum(result['excluded']))} left out at {n_cuts} scene cut{'' if n_cuts == 1 else 's'}"
     lines = [f"{result['frames']} frames, {len(result['scored_frames'])} held out ({result['triplets']}), "
-             f"{result['bits']}-bit, peak {result['peak']}{left_out}",
-             f"{'method':<{mw}}{'plane':<6}{'PSNR mean':>11}{'std':>8}{'min':>9}{'max':>9}{'of mean MSE':>13}"
+             f"{result['bits']}-bit, peak {result['peak']}{left_out}"]
+    if "resize" in result:
+        (w, h), (sw, sh) = result["resize"], result["source_size"]
+        lines.append(f"scored at {w}x{h} (the {sw}x{sh} clip resized on the device before frames were held out)")
+    lines += [f"{'method':<{mw}}{'plane':<6}{'PSNR mean':>11}{'std':>8}{'min':>9}{'max':>9}{'of mean MSE':>13}"
              f"{'SSIM mean':>11}{'min':>9}{'identical':>11}"]
     for m in result["methods"]:
         for p in result["planes"]:

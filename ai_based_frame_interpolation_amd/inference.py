@@ -458,7 +458,7 @@ class FrameInterpolator:
 
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
                           chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend", raw=None,
-                          width=None, height=None, dedup=None, max_gap=4, dedup_log=None, scene_log=None):
+                          width=None, height=None, dedup=None, max_gap=4, dedup_log=None, scene_log=None, resize=None):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -507,14 +507,23 @@ class FrameInterpolator:
         intervals (a resident run: one pair, the whole clip's); concatenated they are `scene.pair_peak` of the clip and
         its dead flags.  scene_log: the same for `scene_cut`: one (scores float64, flags uint8) pair per chunk, what the
         stream routes' `scene_log` has always received (it costs one more device-to-host read per chunk); from the
-        two logs `retime.dedup_spans` gives the spans a run re-timed, which is how the command line counts them."""
+        two logs `retime.dedup_spans` gives the spans a run re-timed, which is how the command line counts them.
+        resize: None, or (width, height) / "WxH": every frame is resized on the device right after its upload, with the
+        bilinear filter of `preprocess_image` (resize.py, DESIGN.md 3.3q: each plane on its own grid, chroma at the size
+        the format gives at the new size, no siting offset; a large down-scale aliases as the reference's does), before
+        scene cuts, dedup and the first forward.  The route and its refusals are those of the new size, the output has
+        the new size (the Y4M header says so); width / height stay the size of a raw source.  The result is, byte for
+        byte, what the same call without `resize` writes for the clip resized beforehand, for every chunk_frames."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         from . import stream
         run = dict(batch=self.batch, chunk_frames=chunk_frames, scene_cut=thr, fps=fps, src_fps=src_fps,
                    time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
-                   scene_log=scene_log)
+                   scene_log=scene_log, resize=resize)
+        if resize is not None:
+            from . import resize as _resize
+            _resize.check_size(resize)
         if raw is not None:
             return stream.interpolate_raw_stream(self.model, input_path, output_path, factor, raw=raw, width=width,
                                                  height=height, matrix=matrix, siting=siting, **run)

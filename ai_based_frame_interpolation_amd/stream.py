@@ -48,6 +48,15 @@ With `fps=` (source / target rate = p / q, G = 2**time_depth) F is G in the leve
 R = ceil(C x q / p) + 1 resampled frames, and the device holds them beside the grid:
   host pinned    3 x (C + 2) input frames + 2 x R output frames
   device         2 x (C + 2) input frames + one chunk's levels (about 2 x (C x G + 1) frames) + 2 x R output frames
+
+With `resize=` (resize.py) the reader, the pinned input slots and their device twins hold frames of the
+SOURCE size; a chunk is resized once, right after its upload, into a tensor of its own, and scene cuts, dedup, the route
+and everything after them see frames of the DESTINATION size only:
+  host pinned    3 x (C + 2) source frames + 2 x (C x F + 1) destination frames
+  device         2 x (C + 2) source frames + (C + 2) destination frames (the resized chunk, until its levels have run)
+                 + one chunk's levels + the previous chunk's result, all at the destination size
+A resident run (`_run_whole`) uploads and resizes 64 frames at a time: the device holds the whole clip at the destination
+size and 64 frames at the source size.
 """
 from __future__ import annotations
 
@@ -61,6 +70,7 @@ import numpy as np
 import torch
 
 from . import colour, imageio_lite, packed, scene
+from . import resize as _resize
 from . import retime as _retime
 from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
                         interpolate_sequence_nv12, interpolate_sequence_p10, interpolate_sequence_rgb_packed,
@@ -389,10 +399,12 @@ def _dead_and_cuts(d, bits, limit, cut_flags):
 
 @torch.no_grad()
 def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, thr, scene_log=None, plan=None,
-         mode: str = "blend", dd=None, dedup_log=None) -> int:
+         mode: str = "blend", dd=None, dedup_log=None, rs=None) -> int:
     """Stream `reader` through `route` into `write(rows)`; returns the number of output frames.  plan: a `retime.Plan`
     (then factor is its G): each chunk's grid is resampled to the plan's frames.  dd: None or (dead limit, max_gap),
-    with a plan: repeated frames are re-timed (retime.py).
+    with a plan: repeated frames are re-timed (retime.py).  rs: None or a `resize.FrameResize`: the
+    reader, the pinned input slots and their device twins hold frames of rs.row samples; each chunk is resized once,
+    right after its upload, into rows of route.row samples, which is all that scene cuts, dedup and the route see.
 
     Sizes.  A chunk is read with `look` lookahead frames behind its C + 1 own: 0, 1 with scene_cut; with dd max_gap - 1,
     and max_gap with scene_cut too.  A read that comes up short of C + 1 + look frames is the clip's last chunk, and
@@ -408,7 +420,8 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
     in_rows, out_rows = C + 1 + look, tail * factor + 1
     if plan is not None:
         out_rows = -(-tail * plan.q // plan.p) + 1
-    in_slots = [torch.empty((in_rows, route.row), dtype=route.tdtype).pin_memory() for _ in range(R_IN)]
+    src_row = route.row if rs is None else rs.row
+    in_slots = [torch.empty((in_rows, src_row), dtype=route.tdtype).pin_memory() for _ in range(R_IN)]
     out_slots = [torch.empty((out_rows, route.out_row), dtype=route.tdtype).pin_memory() for _ in range(R_OUT)]
     in_np = [s.numpy().view(route.ndtype) for s in in_slots]
     out_np = [s.numpy().view(route.ndtype) for s in out_slots]
@@ -465,7 +478,7 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
         t.start()
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-    d_in = [torch.empty((in_rows, route.row), dtype=route.tdtype, device=dev) for _ in range(2)]
+    d_in = [torch.empty((in_rows, src_row), dtype=route.tdtype, device=dev) for _ in range(2)]
     d_free = [None, None]   # event: the compute stream's last read of d_in[j]
     # with a plan, the resampled frames of a chunk go into the device twin of its pinned output slot: every chunk's
     # result has the same allocation, whatever its frame count, and the grid is released before the next chunk runs
@@ -492,6 +505,8 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
                 up.record(h2d)
             compute.wait_event(up)
             d = d_in[j][:m]
+            if rs is not None:   # the chunk at the destination size: a tensor of its own, used on this stream alone
+                d = rs(d)
             flags = seen = None
             if thr is not None and c > 0:
                 sums = scene.pair_sad([d], route.bits)   # c own intervals, then the lookahead intervals that were read
@@ -566,26 +581,30 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
 
 @torch.no_grad()
 def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode: str, n_frames=None, dd=None,
-               dedup_log=None, scene_log=None) -> int:
-    """The resident form of `_run`: the whole clip on the device as one chunk (flags once over every sample of the
+               dedup_log=None, scene_log=None, rs=None) -> int:
+    """The resident form of `_run` (rs as there: every uploaded piece is resized as it arrives, so the device holds the
+    source-size frames of one piece only): the whole clip on the device as one chunk (flags once over every sample of the
     packed rows, one run of the route, one hold at the full factor; with a plan: one grid, one resample; with dd: one
     read of the dead and cut flags, one table).  n_frames: the
     clip's frame count where it is known up front (a regular file): the clip is then read into one array; a stream of
     unknown length is uploaded 64 frames at a time, so that the host never holds it twice."""
     dev = next(model.parameters()).device
 
+    src_row = route.row if rs is None else rs.row
+
     def upload(a):
-        return torch.from_numpy(a.view(np.int16) if route.bits == 10 else a).to(dev)
+        t = torch.from_numpy(a.view(np.int16) if route.bits == 10 else a).to(dev)
+        return t if rs is None else rs(t)
     if n_frames is not None:
-        frames = np.empty((n_frames, route.row), dtype=route.ndtype)
+        frames = np.empty((n_frames, src_row), dtype=route.ndtype)
         if reader.read_into(frames, n_frames) != n_frames:
             raise ValueError("the clip has fewer frames than were counted")
-        d = upload(frames)
+        d = upload(frames) if rs is None else torch.cat([upload(frames[i:i + 64]) for i in range(0, max(n_frames, 1), 64)])
         del frames
     else:
         parts = []
         while True:
-            buf = np.empty((64, route.row), dtype=route.ndtype)
+            buf = np.empty((64, src_row), dtype=route.ndtype)
             k = reader.read_into(buf, 64)
             if k:
                 parts.append(upload(buf[:k]))
@@ -619,6 +638,20 @@ def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode
         rows = _retime.resample_table(grid, entries, route.bits)
     write(rows.cpu().numpy().view(route.ndtype))
     return n
+
+
+def _y4m_resize(hdr, size) -> "_resize.FrameResize":
+    """The resize of the frames of a Y4M stream with header `hdr` to `size` = (width, height)."""
+    kind = ("y4m", hdr["colourspace"])
+    return _resize.FrameResize(_resize.frame_planes(kind, hdr["height"], hdr["width"]),
+                               _resize.frame_planes(kind, size[1], size[0]), hdr["bits"], size,
+                               (hdr["width"], hdr["height"]))
+
+
+def _raw_resize(raw, bits, height, width, size) -> "_resize.FrameResize":
+    """The resize of tight `raw` frames of height x width to `size` = (width, height)."""
+    return _resize.FrameResize(_resize.frame_planes(raw, height, width), _resize.frame_planes(raw, size[1], size[0]),
+                               bits, size, (int(width), int(height)))
 
 
 def _plan_of(fps, src_fps, header_fps, depth):
@@ -656,7 +689,8 @@ def _open_sink(dst):
 def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
                            matrix: str = "bt709", siting: str | None = None, scene_cut: float | None = None,
                            scene_log: list | None = None, fps=None, src_fps=None, time_depth: int = 2,
-                           retime: str = "blend", dedup=None, max_gap: int = 4, dedup_log: list | None = None) -> int:
+                           retime: str = "blend", dedup=None, max_gap: int = 4, dedup_log: list | None = None,
+                           resize=None) -> int:
     """Y4M in (a path or a readable binary file: a pipe, `sys.stdin.buffer`) -> Y4M out (a path or a writable binary
     file), or a `.npy` path of the luma frames (grayscale network; the input must then be a regular file, whose frame
     count a first pass reads).  This is what `FrameInterpolator.interpolate_video` runs; the result is the same, byte
@@ -670,10 +704,14 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     resampled from a 2**time_depth bisection; src_fps overrides the header's rate; factor stays 2.
     dedup / max_gap: re-time repeated frames (retime.py): dedup is None (off) or a tolerance >= 0 in
     code values, max_gap (2..8) the longest run of equal frames that is re-timed; with `factor` (at most 16) or with
-    `fps`.  dedup_log: a list that receives (peaks, dead) host arrays of each chunk's intervals (scene_log's twin)."""
+    `fps`.  dedup_log: a list that receives (peaks, dead) host arrays of each chunk's intervals (scene_log's twin).
+    resize: None, or (width, height) / "WxH": every frame is resized on the device right after its upload (resize.py,
+    DESIGN.md 3.3q; each plane on its own grid, the chroma size as the tag gives it at the new size), and the route, its
+    refusals, scene cuts, dedup and the output header are those of a clip of that size."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     tol, gap = check_dedup(dedup, max_gap, fps, factor)
+    size = None if resize is None else _resize.check_size(resize)
     npy_out = isinstance(dst, (str, os.PathLike)) and os.fspath(dst).lower().endswith(".npy")
     if npy_out:
         if not _is_path(src) or not stat.S_ISREG(os.stat(src).st_mode):
@@ -681,8 +719,10 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
                              "counted before it is read: write Y4M, or read the stream from a regular file")
     reader = imageio_lite.Y4MReader(src)
     try:
-        route = _y4m_route(model, reader.header, npy_out, batch, matrix, siting)
-        hdr = reader.header
+        hdr, rs = reader.header, None
+        if size is not None:   # everything from here on is a clip of the new size; the reader keeps the source's
+            rs, hdr = _y4m_resize(hdr, size), _resize.y4m_header_at(hdr, size)
+        route = _y4m_route(model, hdr, npy_out, batch, matrix, siting)
         plan = _plan_of(fps, src_fps, hdr["fps"], depth)
         if plan is None:
             fps = (hdr["fps"][0] * factor, hdr["fps"][1])
@@ -694,8 +734,9 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
             if C is None:
                 count = (imageio_lite.y4m_frame_count(src)
                          if _is_path(src) and stat.S_ISREG(os.stat(src).st_mode) else None)
-                return _run_whole(model, route, reader, write, factor, thr, plan, mode, count, dd, dedup_log, scene_log)
-            return _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log)
+                return _run_whole(model, route, reader, write, factor, thr, plan, mode, count, dd, dedup_log, scene_log,
+                                  rs)
+            return _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log, rs)
         if npy_out:
             n = imageio_lite.y4m_frame_count(src)
             shape = ((n - 1) * factor + 1 if plan is None else plan.n_out(n), hdr["height"], hdr["width"])
@@ -725,15 +766,17 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
 def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
                            scene_cut: float | None = None, scene_log: list | None = None, fps=None, src_fps=None,
                            time_depth: int = 2, retime: str = "blend", dedup=None, max_gap: int = 4,
-                           dedup_log: list | None = None) -> int:
+                           dedup_log: list | None = None, resize=None) -> int:
     """`.npy` stack in (uint8 [N,H,W] or [N,H,W,C], read through `np.load(mmap_mode="r")`) -> `.npy` out (written
     through `np.lib.format.open_memmap`, the file `np.save` would write; a name without `.npy` gets it).  An
     [N,H,W,C] stack goes through the RGB network, or channel by channel through the grayscale one.  Returns the output
     frame count.  fps / src_fps / time_depth / retime and chunk_frames None: as for `interpolate_y4m_stream`; a .npy
-    stack carries no rate, so `fps` needs `src_fps`."""
+    stack carries no rate, so `fps` needs `src_fps`.  resize: as for `interpolate_y4m_stream`; the output stack has the
+    new height and width."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     tol, gap = check_dedup(dedup, max_gap, fps, factor)
+    size = None if resize is None else _resize.check_size(resize)
     plan = _plan_of(fps, src_fps, None, depth)
     if plan is not None:
         factor = plan.G
@@ -748,16 +791,23 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
         raise ValueError("expected a uint8 .npy stack [N,H,W] or [N,H,W,3]")
     if mm.shape[0] < 1:
         raise ValueError("no frames to interpolate")
-    route = _npy_route(model, mm.shape[1:], batch)
+    shape, rs = tuple(mm.shape[1:]), None
+    if size is not None:
+        kind = "npy" if len(shape) == 2 else ("npy", shape[2])
+        rs = _resize.FrameResize(_resize.frame_planes(kind, shape[0], shape[1]),
+                                 _resize.frame_planes(kind, size[1], size[0]), 8, size, (shape[1], shape[0]))
+        shape = (size[1], size[0]) + shape[2:]
+    route = _npy_route(model, shape, batch)
     n_out = (mm.shape[0] - 1) * factor + 1 if plan is None else plan.n_out(mm.shape[0])
-    sink = _NpyWriter(dst, np.uint8, (n_out,) + mm.shape[1:])
+    sink = _NpyWriter(dst, np.uint8, (n_out,) + shape)
     ok = False
     try:
         if C is None:
             total = _run_whole(model, route, _NpyRows(mm), sink.write, factor, thr, plan, mode, mm.shape[0], dd,
-                               dedup_log, scene_log)
+                               dedup_log, scene_log, rs)
         else:
-            total = _run(model, route, _NpyRows(mm), sink.write, factor, C, thr, scene_log, plan, mode, dd, dedup_log)
+            total = _run(model, route, _NpyRows(mm), sink.write, factor, C, thr, scene_log, plan, mode, dd, dedup_log,
+                         rs)
         ok = True
     finally:
         sink.close(ok)
@@ -768,7 +818,7 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
                            batch: int = 8, chunk_frames: int | None = 32, matrix: str = "bt709",
                            siting: str | None = None, scene_cut: float | None = None, scene_log: list | None = None,
                            fps=None, src_fps=None, time_depth: int = 2, retime: str = "blend", dedup=None,
-                           max_gap: int = 4, dedup_log: list | None = None) -> int:
+                           max_gap: int = 4, dedup_log: list | None = None, resize=None) -> int:
     """Headerless raw video in (a path or a readable binary file: a pipe) -> the same format out (a path or a writable
     binary file): tight NV12 frames of height x width (`ffmpeg ... -f rawvideo -pix_fmt nv12 -`) through the RGB
     network, `interpolate_sequence_nv12` per level; or, with raw "rgb24" / "bgr24" / "rgba" / "bgra", tight packed RGB
@@ -780,7 +830,8 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     whatever reads the result).  siting None is "mpeg2", the range limited.  Every argument - the model's network, the
     output name, the size of a regular input file (a whole number of frames) - is checked before any GPU work and
     before the output exists; a pipe that ends inside a frame is an error at that point.  Returns the output frame
-    count."""
+    count.  resize: as for `interpolate_y4m_stream`: width and height stay the size of the source, the output is raw
+    video of the new size, and the format's refusals (an odd width of uyvy422 / yuyv422) apply to both sizes."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     if src_fps is None:
         raise ValueError("raw video carries no frame rate: pass src_fps")
@@ -788,12 +839,17 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     fps, _, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     tol, gap = check_dedup(dedup, max_gap, fps, factor)
     npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
+    size = None if resize is None else _resize.check_size(resize)
     route = _raw_route(model, raw, height, width, npy_out, batch, matrix, siting)
+    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
+    rs = None
+    if size is not None:
+        rs = _raw_resize(raw, route.bits, height, width, size)
+        route = _raw_route(model, raw, size[1], size[0], npy_out, batch, matrix, siting)
     plan = _plan_of(fps, src_rate, None, depth)
     if plan is not None:
         factor = plan.G
     plan, dd = _dedup_of(tol, gap, plan, factor)
-    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire
     count = None
     if _is_path(src):
         if not os.path.exists(src):
@@ -816,9 +872,9 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
                 f.write(np.ascontiguousarray(rows).data)
             if C is None:
                 total = _run_whole(model, route, reader, write, factor, thr, plan, mode, count, dd, dedup_log,
-                                   scene_log)
+                                   scene_log, rs)
             else:
-                total = _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log)
+                total = _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log, rs)
             ok = True
         finally:
             finish(ok)

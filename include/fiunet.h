@@ -39,7 +39,8 @@ extern "C" {
                                      way: the plane metrics on interleaved samples (fiunet_interleaved_psnr,
                                      fiunet_stepped_ssim); v8 also, added the same way: repeated frames in video
                                      (fiunet_pair_peak_u8, fiunet_pair_peak_p10, fiunet_retime_table_u8,
-                                     fiunet_retime_table_p10) */
+                                     fiunet_retime_table_p10); v8 also, added the same way: resizing frame planes
+                                     (fiunet_resize_plane, fiunet_resize_planes_u8, fiunet_resize_planes_p10) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -496,6 +497,31 @@ int fiunet_retime_table_u8(const uint8_t* grid, int n_rows, size_t frame_samples
                            int n_out, uint8_t* out, void* stream);
 int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
                             int n_out, uint16_t* out, void* stream);
+
+/* Bilinear resize of frame planes (csrc/resize.hip.h).  A plane is described in SAMPLES of its buffer:
+ * sample (y, x) of frame f lies at offset + f * frame_stride + y * pitch + x * step.  Plane i of `src_planes` is
+ * resampled into plane i of `dst_planes`, each pair on its own grid, for n_frames frames, in one launch per 2^31 store
+ * chunks (the descriptors travel in the kernel's arguments: `src_planes` / `dst_planes` are HOST memory, read during the
+ * call; there is no device table, no workspace and no copy, and the call can be captured into a graph).
+ *   8 bits    imageio_lite.resize_linear_u8 to the last bit: half-pixel centres, the coordinate in fp64 rounded to
+ *             fp32, 11-bit coefficients, OpenCV's two-stage vertical rounding (the project's statement of
+ *             cv2.resize(INTER_LINEAR) on uchar; not pinned against OpenCV itself)
+ *   10 bits   the same taps; samples above 1023 read as 1023; out = min((b0 * S0 + b1 * S1 + 2^21) >> 22, 1023)
+ *   equal h and w: a copy of the plane, sample for sample
+ * Asynchronous on `stream`; no allocation, no synchronisation; n_frames == 0 is a no-op.  FIUNET_ERR_INVALID_ARG, before
+ * any launch and before a device pointer is used: NULL pointers (a uint16_t pointer that is not 2-byte aligned), n_planes
+ * outside 1..4, n_frames < 0, a size outside 1 .. 2^24, a step outside 1..4, pitch < (w - 1) * step + 1, a plane that
+ * does not lie inside its frame stride (offset + (h - 1) * pitch + (w - 1) * step + 1 > frame_stride), or source and
+ * destination byte ranges (first sample of any plane of frame 0 to the last of frame n_frames - 1) that overlap.
+ * FIUNET_ERR_UNSUPPORTED: a destination plane of 2^31 or more 16-byte store chunks. */
+typedef struct fiunet_resize_plane {
+    size_t offset, pitch, frame_stride;
+    int32_t h, w, step, reserved;   /* reserved: 0 */
+} fiunet_resize_plane;
+int fiunet_resize_planes_u8(const uint8_t* src, const fiunet_resize_plane* src_planes, uint8_t* dst,
+                            const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream);
+int fiunet_resize_planes_p10(const uint16_t* src, const fiunet_resize_plane* src_planes, uint16_t* dst,
+                             const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream);
 
 /* Replaces preprocess_image's arithmetic (model/inference.py:31-35): out = 2*(in/255) - 1. */
 int fiunet_preprocess_u8(const uint8_t* in, float* out, size_t n, void* stream);
