@@ -102,11 +102,22 @@ def _packed(layout, frame_stride: int):
 _lib = None
 
 
+def build_jobs(environ=None) -> int:
+    """How many translation units `build` lets make compile at once: MAX_JOBS if set, else CMAKE_BUILD_PARALLEL_LEVEL if
+    set, else 8; never above 16 (never the machine's CPU count: a shared machine grants a process far fewer)."""
+    env = os.environ if environ is None else environ
+    asked = env.get("MAX_JOBS") or env.get("CMAKE_BUILD_PARALLEL_LEVEL")
+    return max(1, min(int(asked) if asked else 8, 16))
+
+
 def build(force: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    if force and os.path.exists(LIB_PATH):
-        os.remove(LIB_PATH)
-    res = subprocess.run(["make", "-C", CSRC], capture_output=True, text=True)
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU); force: from scratch, the
+    library's objects included."""
+    if force:
+        subprocess.run(["make", "-C", CSRC, "clean"], capture_output=True, text=True)
+        if os.path.exists(LIB_PATH):   # (FIUNET_LIB: not the Makefile's OUT)
+            os.remove(LIB_PATH)
+    res = subprocess.run(["make", "-C", CSRC, f"-j{build_jobs()}"], capture_output=True, text=True)
     if res.returncode != 0 or not os.path.exists(LIB_PATH):
         raise RuntimeError("building libfiunet_hip.so failed:\n" + res.stdout + res.stderr)
     return LIB_PATH
@@ -296,7 +307,7 @@ FLOW_STAGES = ("pyramid", "poly_exp", "update_matrices", "box_solve", "flow_resi
 
 def debug_flow_plan(h: int, w: int):
     """Diagnostic (tests; not part of the ABI): the pyramid fiunet_farneback_flow builds for an h x w frame -
-    fiunet_debug_flow_plan in csrc/fiunet.hip, pure host arithmetic.  -> [(h, w, ksize, sigma)] for level 0 .. levels."""
+    fiunet_debug_flow_plan in csrc/flow.hip, pure host arithmetic.  -> [(h, w, ksize, sigma)] for level 0 .. levels."""
     fn = lib().fiunet_debug_flow_plan
     fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                    ctypes.POINTER(ctypes.c_double)]
@@ -308,7 +319,7 @@ def debug_flow_plan(h: int, w: int):
 def debug_flow_stage(stage: str, in0, in1, in2, out, scratch, bits: int, level: int, b: int, H: int, W: int, h: int,
                      w: int, image_stride: int = 0, row_pitch: int = 0, mul=(1.0, 1.0)) -> None:
     """Diagnostic (tests; not part of the ABI): one stage of the flow (FLOW_STAGES) on the caller's buffers -
-    fiunet_debug_flow_stage in csrc/fiunet.hip says what each stage reads and writes."""
+    fiunet_debug_flow_stage in csrc/flow.hip says what each stage reads and writes."""
     fn = lib().fiunet_debug_flow_stage
     vp, ci, sz, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
     fn.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, sz, sz, cf, cf, vp]

@@ -7,27 +7,18 @@
 //   pre/post-processing arithmetic            /root/reference/model/inference.py:31-35, :54-61
 // Device code: conv3x3_mfma.hip.h (MFMA implicit-GEMM conv) and pointwise.hip.h.
 // gfx950 only; no CPU fallback: every entry point either launches HIP kernels or returns an error.
-#include "../../include/fiunet.h"
+//
+// One of the library's translation units (fiunet_internal.h lists them): this one holds the context, the weight loads,
+// the stage and workspace plans, the forward and its entry points, and the one definition of the state the units share.
+// The conv kernels are compiled in the conv units and launched through launch_conv (conv_launch.hip.h).
+#include "fiunet_internal.h"
 #include "pointwise.hip.h"
-#include "conv3x3_kwave.hip.h"
-#include "metrics.hip.h"
-#include "colour.hip.h"
-#include "packed.hip.h"
-#include "yuv4xx.hip.h"
-#include "scene.hip.h"
-#include "retime.hip.h"
-#include "resize.hip.h"
 #include "weights.hip.h"
-#include "flow.hip.h"
 
-#include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <string>
-#include <vector>
 
 using namespace fiunet;
 
@@ -35,20 +26,37 @@ namespace {
 
 thread_local std::string g_err;
 
+thread_local std::string* g_name_out = nullptr;  // where the next conv launch reports its kernel
+
+}  // namespace
+
+namespace fiunet {
+
+std::string& last_error() { return g_err; }
+
 int fail(int code, const std::string& msg)
 {
     g_err = msg;
     return code;
 }
 
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(FIUNET_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+std::string* name_out() { return g_name_out; }
 
-constexpr int NCONV = 18;
+int zero_fill_async(void* p, size_t bytes, hipStream_t s)
+{
+    if (((uintptr_t)p & 15) || (bytes & 3)) return fail(FIUNET_ERR_INVALID_ARG, "internal: zero-fill of an unaligned range");
+    if (!bytes) return FIUNET_OK;
+    const size_t n16 = bytes / 16;
+    hipLaunchKernelGGL(zero_fill_kernel, dim3(grid_for(std::max<size_t>(n16, 1))), dim3(256), 0, s, (uint4*)p, n16,
+                       (unsigned)((bytes % 16) / 4));
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+}  // namespace fiunet
+
+namespace {
+
 constexpr size_t kSlabBytes = 64u << 20;  // split-K slab: ksplit * B*H*W*Cout * 4 <= ~50 MB by construction
 [[maybe_unused]] constexpr size_t kStampWaves = 4 * 40000;  // diagnostic stamp records (128 B each); launches with more waves leave the rest unrecorded
 [[maybe_unused]] constexpr size_t kStampRec = 16;              // u64 slots per record
@@ -57,11 +65,6 @@ const char* const kBlockPrefix[9] = {
     "unet.inc", "unet.down1.maxpool_conv.1", "unet.down2.maxpool_conv.1",
     "unet.down3.maxpool_conv.1", "unet.down4.maxpool_conv.1", "unet.up1.conv", "unet.up2.conv",
     "unet.up3.conv", "unet.up4.conv"};
-// output channels of the 18 convs: bilinear=True (factor 2, Up's DoubleConv has mid = in / 2; the only variant a reference
-// caller constructs) and bilinear=False (the constructor's default, unet.py:66,99: factor 1, down4 -> 1024, Up =
-// ConvTranspose2d(in, in / 2, 2, 2) + DoubleConv(in, out), unet.py:42-44)
-const int kCoutBil[NCONV] = {64, 64, 128, 128, 256, 256, 512, 512, 512, 512, 512, 256, 256, 128, 128, 64, 64, 64};
-const int kCoutCT[NCONV] = {64, 64, 128, 128, 256, 256, 512, 512, 1024, 1024, 512, 512, 256, 256, 128, 128, 64, 64};
 const int kLevel[NCONV] = {0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 0, 0};
 // gather mode and sources (activation indices) of each conv; conv 0 is the fp32 stem kernel
 // SRC_POOL here means "reads MaxPool2d(2) of its source": the pooled tensor is written by the
@@ -76,62 +79,12 @@ const int kPoolOut[NCONV] = {-1, 0, -1, 1, -1, 2, -1, 3, -1, -1, -1, -1, -1, -1,
 const int kSrc0[NCONV] = {-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 7, 10, 5, 12, 3, 14, 1, 16};
 const int kSrc1[NCONV] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 9, -1, 11, -1, 13, -1, 15, -1};
 
-struct ConvWeights {
-    int cin = 0, cout = 0;
-    void* w_f32 = nullptr;   // packed [cin/16][kx][ky][cout][16] fp32   (conv 0: [9][cin][64])
-    void* w_bf16 = nullptr;  // packed [cin/32][kx][ky][cout][32] bf16
-    void* w_x2 = nullptr;    // FIUNET_BF16X2 (fiunet_prepare_precision): two pieces [wh | wl], each packed like w_bf16
-    void* w_f16 = nullptr;   // FIUNET_FP16 (fiunet_prepare_precision): packed like w_bf16, IEEE half values
-    float* scale = nullptr;
-    float* shift = nullptr;
-};
-
 // (bf16_row_to_cout, f32_to_bf16_rne, f32_to_bf16_feedback: weights.hip.h - one definition for the host loop of
 // fiunet_load_weights and the kernels of fiunet_load_weights_device)
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-inline bool valid_precision(int p) { return p == FIUNET_FP32 || p == FIUNET_BF16 || p == FIUNET_BF16X2 || p == FIUNET_FP16; }
 // bf16 and fp16: one 2-byte element per activation and weight (32 channels per 64-B plane, the same MFMA shape), so both
 // take every branch of the launch rule and the same workspace layout; fp32 and bf16x2 (two bf16 pieces) have 4 bytes
 inline bool two_byte_elems(int p) { return p != FIUNET_FP32 && p != FIUNET_BF16X2; }
-template <typename T> constexpr const char* elem_name()
-{
-    return std::is_same_v<T, _Float16> ? "f16" : sizeof(T) == 2 ? "bf16" : "f32";
-}
-
-}  // namespace
-
-struct fiunet_ctx {
-    int device = 0;
-    int cf = 1;  // channels per frame
-    bool bilinear = true;          // false: ConvTranspose2d decoder (unet.py:42-44)
-    const int* cout = kCoutBil;    // output channels per conv of this architecture
-    struct { int cin = 0, cout = 0; void* w_f32 = nullptr; void* w_bf16 = nullptr; void* w_x2 = nullptr; void* w_f16 = nullptr; float* bias = nullptr; } convt[4];
-    bool x2_ready = false;         // the two-piece weight copies exist (fiunet_prepare_precision(FIUNET_BF16X2))
-    bool f16_ready = false;        // the fp16 weight copies exist (fiunet_prepare_precision(FIUNET_FP16))
-    unsigned flags = 0;
-    bool loaded = false;
-    ConvWeights conv[NCONV];
-    float* head_w = nullptr;  // [cf][64]
-    float* head_b = nullptr;  // [cf]
-    void* stem_w_split = nullptr;  // gray stem weights x BatchNorm scale as bf16 hi/lo pairs [2][64][32] (fused stem)
-    unsigned long long* stamps = nullptr;  // per-wave cycle records (diagnostic -DFIUNET_STAMP builds)
-    int stamp_layer = -1;
-    int force_tile[NCONV] = {0};     // diagnostic overrides of choose_conv_cfg per conv (fiunet_debug_force_cfg; tools/cfg_sweep.py)
-    int force_ksplit[NCONV] = {0};
-    std::vector<void*> owned;
-    hipEvent_t load_done = nullptr;  // recorded behind the kernels of fiunet_load_weights_device (fiunet_prepare_precision waits for it)
-    // per-layer HIP-event profiling (fiunet_profile_*): NCONV+1 events per recorded forward
-    bool profiling = false;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    std::string layer_name[NCONV];
-    double layer_flops[NCONV] = {0};
-};
-
-namespace {
-
 
 int dev_upload(fiunet_ctx* ctx, const void* host, size_t bytes, void** out)
 {
@@ -158,82 +111,6 @@ void free_weights(fiunet_ctx* ctx)
     ctx->stamps = nullptr;
 }
 
-thread_local std::string* g_name_out = nullptr;  // where the next conv launch reports its kernel
-
-// One conv kernel on `nblk` workgroups of 256 threads with `lds` bytes of dynamic LDS: more than 64 KiB needs the opt-in
-// attribute, set once per kernel and device (a duplicate hipFuncSetAttribute is harmless); `name` is what the profiler
-// reports for the stage (fiunet_profile_read).
-template <auto Kernel>
-int launch_lds(const char* name, long long nblk, int lds, const ConvArgs& a, hipStream_t s)
-{
-    if (g_name_out) *g_name_out = name;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return fail(FIUNET_ERR_INVALID_ARG, "conv grid too large");
-    static std::atomic<bool> lds_attr_set[64];
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !lds_attr_set[dev].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        lds_attr_set[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(Kernel, dim3((unsigned)nblk), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-// One of a format conversion's two instantiations on blocks of kColourBlock threads: the one with vector accesses where
-// `vec` says that every base, pitch and stride allows them, the scalar one otherwise.
-template <auto VecKernel, auto ScalarKernel, typename... Args>
-int launch_vec(bool vec, dim3 grid, void* stream, Args... args)
-{
-    if (vec) hipLaunchKernelGGL(VecKernel, grid, dim3(kColourBlock), 0, (hipStream_t)stream, args...);
-    else hipLaunchKernelGGL(ScalarKernel, grid, dim3(kColourBlock), 0, (hipStream_t)stream, args...);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-template <typename T, int BN, int TH, int TW, int MODE, int EPI>
-int launch_conv_cfg(ConvArgs a, hipStream_t s)
-{
-    char name[128] = "";
-    if (g_name_out)
-        std::snprintf(name, sizeof name, "conv3x3_mfma_kernel<%s,%d,%d,%d,%d,%d>", elem_name<T>(), BN, TH, TW,
-                      MODE, EPI);
-    a.tilesX = (a.W + TW - 1) / TW;
-    a.tilesY = (a.H + TH - 1) / TH;
-    a.nct = a.Cout / BN;
-    const long long nblk = (long long)a.B * a.tilesX * a.tilesY * a.nct * (epi_is_splitk(EPI) ? a.ksplit : 1);
-    return launch_lds<&conv3x3_mfma_kernel<T, BN, TH, TW, MODE, EPI>>(name, nblk, ConvTile<BN, TH, TW, MODE>::LDS_BYTES, a, s);
-}
-
-inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 256 * 32); }
-
-// `bytes` (a multiple of 4) of zeros from the 16-byte-aligned `p`, as a kernel on `s` (pointwise.hip.h, zero_fill_kernel:
-// why it is not hipMemsetAsync)
-int zero_fill_async(void* p, size_t bytes, hipStream_t s)
-{
-    if (((uintptr_t)p & 15) || (bytes & 3)) return fail(FIUNET_ERR_INVALID_ARG, "internal: zero-fill of an unaligned range");
-    if (!bytes) return FIUNET_OK;
-    const size_t n16 = bytes / 16;
-    hipLaunchKernelGGL(zero_fill_kernel, dim3(grid_for(std::max<size_t>(n16, 1))), dim3(256), 0, s, (uint4*)p, n16,
-                       (unsigned)((bytes % 16) / 4));
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-inline long long padded_area(int H, int W, int TH, int TW)
-{
-    return (long long)((H + TH - 1) / TH) * TH * ((W + TW - 1) / TW) * TW;
-}
-
-// The 32-pixel-wide tiles are the tuned ones (whole 128-B lines per tile row, no register spills in
-// any variant); the narrow tiles only win when they save real padding work: more than 1/32 of it
-// (135x240 at 8x32 pads to 136x256 = +0.7 % over 16x16 and still runs 10 % faster per FLOP).
-inline bool prefer_wide(int H, int W, int THw, int TWw, int THn, int TWn)
-{
-    const long long wide = padded_area(H, W, THw, TWw), narrow = padded_area(H, W, THn, TWn);
-    return wide * 32 <= narrow * 33;
-}
-
 // ---- tile shape and K split of one conv launch ---------------------------------------------------------------------
 // Two tile families.  BIG (rounds 1-5, tuned on the 1080p workload): 64 couts x 16x32 / 32x16 pixels or 128 couts x 8x32 /
 // 16x16 pixels, every wave a 64 x 128 tile (128 accumulator registers), two workgroups per CU.  SMALL (round 6): 64 couts x
@@ -253,8 +130,7 @@ inline bool prefer_wide(int H, int W, int THw, int TWw, int THn, int TWn)
 // layers with >= 64 big-tile workgroups PER IMAGE are cut only below 128 workgroups in total, which such a layer never has
 // for B >= 2 (a SINGLE pair with 64..127 workgroups per image, e.g. the deepest level of a 720p frame, is); small frames,
 // where a single pair is cut anyway, below 256.  fiunet_min_unsplit_batch answers from the stage plan (plan_stages).
-struct TileShape { int BN, TH, TW; };
-struct ConvCfg { bool small; int ksplit; bool kwave = false; };   // kwave: the K loop cut over the four waves of a workgroup (conv3x3_kwave.hip.h)
+struct TileShape { int BN, TH, TW; };   // (ConvCfg, what the rule answers: fiunet_internal.h)
 
 inline TileShape big_tile(int H, int W, int Cout)
 {
@@ -611,92 +487,6 @@ bool make_plan(const NetDesc& n, int B, int H, int W, int precision, Plan& p, st
     p.total = total;
     if (placed) *placed = bufs;
     return true;
-}
-
-// The K loop cut over the four waves of a workgroup (small problems, direct sources, every precision): conv3x3_kwave.hip.h.
-template <typename T, int EPI, bool X2> int launch_kwave(ConvArgs a, hipStream_t s)
-{
-    using Tile = KWaveTile;
-    char name[96] = "";
-    if (g_name_out)
-        std::snprintf(name, sizeof name, "conv3x3_kwave_kernel<%s%s,64,2,32,%d>+kwave4", elem_name<T>(), X2 ? "x2" : "", EPI);
-    a.tilesX = (a.W + Tile::TW - 1) / Tile::TW;
-    a.tilesY = (a.H + Tile::TH - 1) / Tile::TH;
-    a.nct = a.Cout / Tile::BN;
-    return launch_lds<&conv3x3_kwave_kernel<EPI, X2, T>>(name, (long long)a.B * a.tilesX * a.tilesY * a.nct, Tile::LDS_BYTES, a, s);
-}
-
-// One conv launch in a given tile shape; ksplit > 1: the K loop (planes) cut over `ksplit` workgroups that store raw
-// fp32 partial sums, then splitk_finalize_tile_kernel adds them in slice order (deterministic) and runs the epilogue.
-template <typename T, int BN, int TH, int TW, int MODE, int EPI>
-int launch_conv_maybe_split(ConvArgs a, hipStream_t s, int ksplit)
-{
-    if constexpr (!src_is_stem(MODE) && (EPI == EPI_PLAIN || EPI == EPI_POOL)) {
-        if (ksplit > 1 && a.kslab && a.dst) {
-            ConvArgs k = a;
-            k.ksplit = ksplit;
-            int rc = launch_conv_cfg<T, BN, TH, TW, MODE, EPI_SPLITK>(k, s);
-            if (rc) return rc;
-            k.tilesX = (a.W + TW - 1) / TW;
-            k.tilesY = (a.H + TH - 1) / TH;
-            k.nct = a.Cout / BN;
-            const long long ntile = (long long)a.B * k.tilesX * k.tilesY * k.nct;
-            hipLaunchKernelGGL((splitk_finalize_tile_kernel<T, BN, TH, TW, EPI, src_is_x2(MODE)>), dim3((unsigned)(4 * ntile)), dim3(64), 0, s, k);
-            HIP_TRY(hipGetLastError());
-            if (g_name_out) *g_name_out += "+splitk" + std::to_string(ksplit);
-            return FIUNET_OK;
-        }
-    }
-    return launch_conv_cfg<T, BN, TH, TW, MODE, EPI>(a, s);
-}
-
-template <typename T, int MODE, int EPI> int launch_conv_shape(const ConvArgs& a, const ConvCfg& cfg, hipStream_t s)
-{
-    if (a.Cout != 64 && a.Cout % 128 != 0) return fail(FIUNET_ERR_INVALID_ARG, "Cout must be 64 or k*128");
-    if ((EPI == EPI_HEAD || EPI == EPI_HEAD3) && a.Cout != 64) return fail(FIUNET_ERR_INVALID_ARG, "fused head needs Cout == 64");
-    if constexpr ((MODE == SRC_DIRECT || MODE == SRC_DIRECT_X2) && (EPI == EPI_PLAIN || EPI == EPI_POOL)) {
-        if (cfg.kwave) return launch_kwave<T, EPI, MODE == SRC_DIRECT_X2>(a, s);
-    }
-    if (cfg.small) return launch_conv_maybe_split<T, 64, 8, 32, MODE, EPI>(a, s, cfg.ksplit);
-    if (a.Cout == 64) {
-        const bool wide = prefer_wide(a.H, a.W, 16, 32, 32, 16);
-        return wide ? launch_conv_maybe_split<T, 64, 16, 32, MODE, EPI>(a, s, cfg.ksplit)
-                    : launch_conv_maybe_split<T, 64, 32, 16, MODE, EPI>(a, s, cfg.ksplit);
-    }
-    if constexpr (EPI != EPI_HEAD && EPI != EPI_HEAD3) {
-        const bool wide = prefer_wide(a.H, a.W, 8, 32, 16, 16);
-        return wide ? launch_conv_maybe_split<T, 128, 8, 32, MODE, EPI>(a, s, cfg.ksplit)
-                    : launch_conv_maybe_split<T, 128, 16, 16, MODE, EPI>(a, s, cfg.ksplit);
-    }
-    return fail(FIUNET_ERR_INVALID_ARG, "fused head needs Cout == 64");
-}
-
-// mode: SRC_DIRECT | SRC_CONCAT_UP | SRC_DIRECT_X2 | SRC_STEM | SRC_STEM_X2; epi: EPI_PLAIN | EPI_HEAD | EPI_HEAD3 | EPI_POOL
-// (direct sources only); cfg: the stage's (plan_stages)
-template <typename T> int launch_conv(const ConvArgs& a, int mode, int epi, const ConvCfg& cfg, hipStream_t s)
-{
-    constexpr int PL = Elem<T>::PL;
-    if (a.C0 % PL || a.C1 % PL) return fail(FIUNET_ERR_INVALID_ARG, "channels not a plane multiple");
-    if (mode == SRC_CONCAT_UP && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_CONCAT_UP, EPI_PLAIN>(a, cfg, s);
-    if (mode == SRC_DIRECT && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_DIRECT, EPI_PLAIN>(a, cfg, s);
-    if (mode == SRC_DIRECT && epi == EPI_HEAD) return launch_conv_shape<T, SRC_DIRECT, EPI_HEAD>(a, cfg, s);
-    if (mode == SRC_DIRECT && epi == EPI_HEAD3) return launch_conv_shape<T, SRC_DIRECT, EPI_HEAD3>(a, cfg, s);
-    if (mode == SRC_DIRECT && epi == EPI_POOL) return launch_conv_shape<T, SRC_DIRECT, EPI_POOL>(a, cfg, s);
-    if constexpr (std::is_same_v<T, __bf16>) {   // FIUNET_BF16X2: two-piece operands
-        if (mode == SRC_DIRECT_X2 && epi == EPI_PLAIN) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_PLAIN>(a, cfg, s);
-        if (mode == SRC_DIRECT_X2 && epi == EPI_POOL) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_POOL>(a, cfg, s);
-        if (mode == SRC_DIRECT_X2 && epi == EPI_HEAD) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_HEAD>(a, cfg, s);
-        if (mode == SRC_DIRECT_X2 && epi == EPI_HEAD3) return launch_conv_shape<T, SRC_DIRECT_X2, EPI_HEAD3>(a, cfg, s);
-        if (mode == SRC_STEM_X2 && epi == EPI_POOL && a.Cout == 64)
-            return cfg.small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM_X2, EPI_POOL>(a, s)
-                             : launch_conv_cfg<T, 64, 16, 32, SRC_STEM_X2, EPI_POOL>(a, s);
-    }
-    if constexpr (sizeof(T) == 2) {   // the fused gray stem (bf16, fp16): 32-wide tiles only (the patch layout)
-        if (mode == SRC_STEM && epi == EPI_POOL && a.Cout == 64)
-            return cfg.small ? launch_conv_cfg<T, 64, 8, 32, SRC_STEM, EPI_POOL>(a, s)
-                             : launch_conv_cfg<T, 64, 16, 32, SRC_STEM, EPI_POOL>(a, s);
-    }
-    return fail(FIUNET_ERR_INVALID_ARG, "unsupported gather/epilogue combination");
 }
 
 // The band [y_origin, y_origin + H) of an image of Hg rows (un-tiled: y_origin = 0, Hg = H), launched as the plan `p.st`
@@ -1450,102 +1240,6 @@ int fiunet_forward_u8_strided(fiunet_ctx* ctx, const uint8_t* frame1, const uint
     return FIUNET_OK;
 }
 
-// ---- colour video (csrc/colour.hip.h): packed I420 <-> planar RGB, and the RGB network's forward between them ----
-static inline size_t i420_frame_bytes(int H, int W)   // (samples per frame, at either depth)
-{
-    return (size_t)H * W + 2 * (size_t)((H + 1) / 2) * ((W + 1) / 2);
-}
-
-// `colour` at an entry point of `bits` bits: FIUNET_YUV_BT2020 is a 10-bit flag, and excludes FIUNET_YUV_BT709
-static int check_colour_flags(unsigned colour, int bits)
-{
-    if (colour & ~(bits == 10 ? kColourFlagsP10 : kColourFlags))
-        return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits (FIUNET_YUV_BT2020 needs the 10-bit entry points)");
-    if ((colour & FIUNET_YUV_BT709) && (colour & FIUNET_YUV_BT2020))
-        return fail(FIUNET_ERR_INVALID_ARG, "colour: FIUNET_YUV_BT709 and FIUNET_YUV_BT2020 together");
-    return FIUNET_OK;
-}
-
-static int check_colour_args(const void* in, const void* out, int B, int H, int W, unsigned colour, int bits)
-{
-    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (int rc = check_colour_flags(colour, bits)) return rc;
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
-    return FIUNET_OK;
-}
-
-// the conversions' grid: a thread per four columns, `rows` rows (a chroma row covers two luma rows), B frames
-static dim3 colour_grid(int W, int rows, int B)
-{
-    return dim3((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)rows, (unsigned)B);
-}
-
-extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
-// the caller's frame stride (0 = tight) -> the resolved one, refused where a frame does not fit; `which`: "in" / "out"
-static int resolve_i420_stride(size_t* frame_stride, int H, int W, const char* which)
-{
-    const size_t fs = i420_frame_bytes(H, W);
-    if (*frame_stride == 0) *frame_stride = fs;
-    if (*frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, std::string(which) + "_frame_stride smaller than one frame");
-    return FIUNET_OK;
-}
-
-// one 4-sample access per luma quad and per chroma pair: W, the stride and both bases a multiple of 4 samples
-template <typename T>
-static bool i420_vec(int W, size_t frame_stride, const void* a, const void* b)
-{
-    return W % 4 == 0 && frame_stride % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
-}
-
-template <typename T>
-static int yuv420_to_rgb(const T* in, size_t in_frame_stride, T* out, int B, int H, int W, unsigned colour, int bits,
-                         void* stream)
-{
-    int rc;
-    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
-    if ((rc = resolve_i420_stride(&in_frame_stride, H, W, "in"))) return rc;
-    return launch_vec<&yuv420_to_rgb_kernel<T, true>, &yuv420_to_rgb_kernel<T, false>>(
-        i420_vec<T>(W, in_frame_stride, in, out), colour_grid(W, H, B), stream, in, in_frame_stride, out, H, W,
-        colour_coef(colour, bits));
-}
-
-template <typename T>
-static int rgb_to_yuv420(const T* in, T* out, size_t out_frame_stride, int B, int H, int W, unsigned colour, int bits,
-                         void* stream)
-{
-    int rc;
-    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
-    if ((rc = resolve_i420_stride(&out_frame_stride, H, W, "out"))) return rc;
-    return launch_vec<&rgb_to_yuv420_kernel<T, true>, &rgb_to_yuv420_kernel<T, false>>(
-        i420_vec<T>(W, out_frame_stride, in, out), colour_grid(W, (H + 1) / 2, B), stream, in, out, out_frame_stride, H, W,
-        colour_coef(colour, bits));
-}
-}  // extern "C++"
-
-int fiunet_yuv420_to_rgb_u8(const uint8_t* in, size_t in_frame_stride, uint8_t* out, int B, int H, int W,
-                            unsigned colour, void* stream)
-{
-    return yuv420_to_rgb<uint8_t>(in, in_frame_stride, out, B, H, W, colour, 8, stream);
-}
-
-int fiunet_rgb_to_yuv420_u8(const uint8_t* in, uint8_t* out, size_t out_frame_stride, int B, int H, int W,
-                            unsigned colour, void* stream)
-{
-    return rgb_to_yuv420<uint8_t>(in, out, out_frame_stride, B, H, W, colour, 8, stream);
-}
-
-int fiunet_yuv420p10_to_rgb_p10(const uint16_t* in, size_t in_frame_stride, uint16_t* out, int B, int H, int W,
-                                unsigned colour, void* stream)
-{
-    return yuv420_to_rgb<uint16_t>(in, in_frame_stride, out, B, H, W, colour, 10, stream);
-}
-
-int fiunet_rgb_p10_to_yuv420p10(const uint16_t* in, uint16_t* out, size_t out_frame_stride, int B, int H, int W,
-                                unsigned colour, void* stream)
-{
-    return rgb_to_yuv420<uint16_t>(in, out, out_frame_stride, B, H, W, colour, 10, stream);
-}
-
 // ---- 10-bit frames (ABI v7): uint16 samples, pre10 / post10 around the fp32 forward.  Strides are
 //      counted in samples.
 size_t fiunet_workspace_bytes_p10(const fiunet_ctx* ctx, int B, int H, int W, int precision)
@@ -1586,829 +1280,6 @@ int fiunet_forward_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* 
     return FIUNET_OK;
 }
 
-// ---- the staged-RGB forward: how a frame format goes through the RGB network.  Every
-//      fiunet_forward_<format> below is this chain with its own conversion pair; nothing else differs between them.
-// [the inner forward's workspace | frame1 RGB | frame2 RGB | output RGB]: planar [B, 3, H, W] batches of `sample`-byte
-// samples behind the workspace of fiunet_forward_u8 (1 byte) / fiunet_forward_p10 (2), every part rounded up to 256 B.
-struct StagedWorkspace {
-    size_t inner, rgb, total;   // total 0: bad arguments (the inner query has said which)
-};
-
-static StagedWorkspace staged_workspace(const fiunet_ctx* ctx, int B, int H, int W, int precision, size_t sample)
-{
-    const size_t inner = sample == 1 ? fiunet_workspace_bytes_u8(ctx, B, H, W, precision)
-                                     : fiunet_workspace_bytes_p10(ctx, B, H, W, precision);
-    if (inner == 0) return {0, 0, 0};
-    const size_t base = align256(inner), rgb = align256((size_t)B * 3 * H * W * sample);
-    return {base, rgb, base + 3 * rgb};
-}
-
-extern "C++" {
-// T: uint8_t (through fiunet_forward_u8_strided) or uint16_t (through fiunet_forward_p10).  What a format supplies:
-//   check()           host only: its format code, colour flags and both layouts (anything its conversions would refuse);
-//   to_rgb(in, rgb)   its frames -> a planar RGB batch;
-//   from_rgb(rgb)     a planar RGB batch -> `out` in its format.
-// Every refusal comes before the first launch.  `name`: the entry point, for the wrong-network message.
-template <typename T, typename Check, typename ToRgb, typename FromRgb>
-static int forward_staged(const char* name, fiunet_ctx* ctx, const T* frame1, const T* frame2, const T* out, int B,
-                          int H, int W, int precision, void* workspace, size_t workspace_bytes, void* stream,
-                          Check check, ToRgb to_rgb, FromRgb from_rgb)
-{
-    if (!frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
-    int rc;
-    if ((rc = check())) return rc;
-    if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->cf != 3)
-        return fail(FIUNET_ERR_UNSUPPORTED, std::string(name) + " needs the RGB network (frame_channels 3)");
-    if (!ctx->loaded) return fail(FIUNET_ERR_NOT_LOADED, "fiunet_forward before fiunet_load_weights");
-    const StagedWorkspace ws = staged_workspace(ctx, B, H, W, precision, sizeof(T));
-    if (ws.total == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
-    if (workspace_bytes < ws.total) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    T* a = (T*)((char*)workspace + ws.inner);
-    T* b = (T*)((char*)a + ws.rgb);
-    T* o = (T*)((char*)b + ws.rgb);
-    if ((rc = to_rgb(frame1, a)) || (rc = to_rgb(frame2, b))) return rc;
-    if constexpr (sizeof(T) == 1)
-        rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, ws.inner, stream);
-    else
-        rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, ws.inner, stream);
-    return rc ? rc : from_rgb(o);
-}
-
-template <typename T>
-static int forward_yuv420(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2, T* out,
-                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision, void* workspace,
-                          size_t workspace_bytes, void* stream)
-{
-    return forward_staged<T>(
-        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
-        [&] {
-            const int rc = check_colour_flags(colour, bits);
-            return rc ? rc : resolve_i420_stride(&out_frame_stride, H, W, "out");
-        },
-        [&](const T* in, T* rgb) { return yuv420_to_rgb<T>(in, 0, rgb, B, H, W, colour, bits, stream); },
-        [&](const T* rgb) { return rgb_to_yuv420<T>(rgb, out, out_frame_stride, B, H, W, colour, bits, stream); });
-}
-}  // extern "C++"
-
-size_t fiunet_workspace_bytes_yuv420(const fiunet_ctx* ctx, int B, int H, int W, int precision)
-{
-    return staged_workspace(ctx, B, H, W, precision, 1).total;
-}
-
-size_t fiunet_workspace_bytes_yuv420p10(const fiunet_ctx* ctx, int B, int H, int W, int precision)
-{
-    return staged_workspace(ctx, B, H, W, precision, 2).total;
-}
-
-int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
-                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
-                          void* workspace, size_t workspace_bytes, void* stream)
-{
-    return forward_yuv420<uint8_t>("fiunet_forward_yuv420", 8, ctx, frame1, frame2, out, out_frame_stride, B, H, W, colour,
-                                   precision, workspace, workspace_bytes, stream);
-}
-
-int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
-                             size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
-                             void* workspace, size_t workspace_bytes, void* stream)
-{
-    return forward_yuv420<uint16_t>("fiunet_forward_yuv420p10", 10, ctx, frame1, frame2, out, out_frame_stride, B, H, W,
-                                    colour, precision, workspace, workspace_bytes, stream);
-}
-
-// ---- NV12 / P010 decoder surfaces: the colour conversions on semi-planar, pitched frames ----
-// The caller's layout (NULL or zero fields = tight) -> the resolved one, refused before any launch where it cannot
-// hold an H x W frame.  Every quantity in samples.
-static int resolve_surface(const fiunet_surface_layout* l, int H, int W, ColourSurface* sf)
-{
-    const size_t Hc = (size_t)(H + 1) / 2, Wc = (size_t)(W + 1) / 2;
-    sf->luma_pitch = l && l->luma_pitch ? l->luma_pitch : (size_t)W;
-    sf->chroma_offset = l && l->chroma_offset ? l->chroma_offset : (size_t)H * W;
-    sf->chroma_pitch = l && l->chroma_pitch ? l->chroma_pitch : 2 * Wc;
-    sf->frame_stride = l && l->frame_stride ? l->frame_stride : i420_frame_bytes(H, W);
-    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
-    if (sf->luma_pitch > big || sf->chroma_pitch > big || sf->chroma_offset > big || sf->frame_stride > big)
-        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: a value above 2^40 samples");
-    if (sf->luma_pitch < (size_t)W) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: luma_pitch < W");
-    if (sf->chroma_pitch < 2 * Wc) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_pitch < 2*ceil(W/2)");
-    if (sf->chroma_offset < (size_t)(H - 1) * sf->luma_pitch + W)
-        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_offset inside the luma plane");
-    if (sf->frame_stride < sf->chroma_offset + (Hc - 1) * sf->chroma_pitch + 2 * Wc)
-        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: frame_stride does not cover the chroma plane");
-    return FIUNET_OK;
-}
-
-extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
-// one 4-sample access per luma quad and per pair of owned chroma pairs: everything a multiple of 4 samples
-template <typename T>
-static bool surface_vec(const ColourSurface& sf, int W, const void* a, const void* b)
-{
-    return W % 4 == 0 && (sf.luma_pitch | sf.chroma_offset | sf.chroma_pitch | sf.frame_stride) % 4 == 0 &&
-           (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
-}
-
-template <typename T>
-static int surface_to_rgb(const T* in, const fiunet_surface_layout* layout, T* out, int B, int H, int W,
-                          unsigned colour, int bits, void* stream)
-{
-    int rc;
-    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
-    ColourSurface sf;
-    if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
-    return launch_vec<&nv12_to_rgb_kernel<T, true>, &nv12_to_rgb_kernel<T, false>>(
-        surface_vec<T>(sf, W, in, out), colour_grid(W, H, B), stream, in, sf, out, H, W, colour_coef(colour, bits));
-}
-
-template <typename T>
-static int rgb_to_surface(const T* in, T* out, const fiunet_surface_layout* layout, int B, int H, int W,
-                          unsigned colour, int bits, void* stream)
-{
-    int rc;
-    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
-    ColourSurface sf;
-    if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
-    return launch_vec<&rgb_to_nv12_kernel<T, true>, &rgb_to_nv12_kernel<T, false>>(
-        surface_vec<T>(sf, W, in, out), colour_grid(W, (H + 1) / 2, B), stream, in, out, sf, H, W,
-        colour_coef(colour, bits));
-}
-
-template <typename T>
-static int forward_surface(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2,
-                           const fiunet_surface_layout* in_layout, T* out, const fiunet_surface_layout* out_layout, int B,
-                           int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
-                           void* stream)
-{
-    return forward_staged<T>(
-        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
-        [&] {
-            ColourSurface sf;
-            int rc = check_colour_flags(colour, bits);
-            if (!rc && !(rc = resolve_surface(in_layout, H, W, &sf))) rc = resolve_surface(out_layout, H, W, &sf);
-            return rc;
-        },
-        [&](const T* in, T* rgb) { return surface_to_rgb<T>(in, in_layout, rgb, B, H, W, colour, bits, stream); },
-        [&](const T* rgb) { return rgb_to_surface<T>(rgb, out, out_layout, B, H, W, colour, bits, stream); });
-}
-}  // extern "C++"
-
-int fiunet_nv12_to_rgb_u8(const uint8_t* in, const fiunet_surface_layout* in_layout, uint8_t* out, int B, int H, int W,
-                          unsigned colour, void* stream)
-{
-    return surface_to_rgb<uint8_t>(in, in_layout, out, B, H, W, colour, 8, stream);
-}
-
-int fiunet_rgb_to_nv12_u8(const uint8_t* in, uint8_t* out, const fiunet_surface_layout* out_layout, int B, int H, int W,
-                          unsigned colour, void* stream)
-{
-    return rgb_to_surface<uint8_t>(in, out, out_layout, B, H, W, colour, 8, stream);
-}
-
-int fiunet_p010_to_rgb_p10(const uint16_t* in, const fiunet_surface_layout* in_layout, uint16_t* out, int B, int H,
-                           int W, unsigned colour, void* stream)
-{
-    return surface_to_rgb<uint16_t>(in, in_layout, out, B, H, W, colour, 10, stream);
-}
-
-int fiunet_rgb_p10_to_p010(const uint16_t* in, uint16_t* out, const fiunet_surface_layout* out_layout, int B, int H,
-                           int W, unsigned colour, void* stream)
-{
-    return rgb_to_surface<uint16_t>(in, out, out_layout, B, H, W, colour, 10, stream);
-}
-
-size_t fiunet_workspace_bytes_nv12(const fiunet_ctx* ctx, int B, int H, int W, int precision)
-{
-    return staged_workspace(ctx, B, H, W, precision, 1).total;
-}
-
-size_t fiunet_workspace_bytes_p010(const fiunet_ctx* ctx, int B, int H, int W, int precision)
-{
-    return staged_workspace(ctx, B, H, W, precision, 2).total;
-}
-
-int fiunet_forward_nv12(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
-                        const fiunet_surface_layout* in_layout, uint8_t* out, const fiunet_surface_layout* out_layout,
-                        int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
-                        void* stream)
-{
-    return forward_surface<uint8_t>("fiunet_forward_nv12", 8, ctx, frame1, frame2, in_layout, out, out_layout, B, H, W,
-                                    colour, precision, workspace, workspace_bytes, stream);
-}
-
-int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2,
-                        const fiunet_surface_layout* in_layout, uint16_t* out, const fiunet_surface_layout* out_layout,
-                        int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
-                        void* stream)
-{
-    return forward_surface<uint16_t>("fiunet_forward_p010", 10, ctx, frame1, frame2, in_layout, out, out_layout, B, H, W,
-                                     colour, precision, workspace, workspace_bytes, stream);
-}
-
-// ---- YUV 4:2:2 / 4:4:4 frames (csrc/yuv4xx.hip.h): planar and one-plane packed, <-> planar RGB ----
-// samples of one tight frame of `format` (bytes at 8 bits); 0: not a fiunet_yuv_format
-static size_t yuv_frame_samples(int format, int H, int W)
-{
-    switch (format) {
-    case FIUNET_YUV_422P: return (size_t)H * W + 2 * (size_t)H * ((W + 1) / 2);
-    case FIUNET_YUV_444P: return 3 * (size_t)H * W;
-    case FIUNET_YUV_UYVY422:
-    case FIUNET_YUV_YUYV422: return 2 * (size_t)H * W;
-    default: return 0;
-    }
-}
-
-// The caller's pitch and stride (0 = tight) -> the resolved layout, with every refusal that needs no pointer: before
-// any launch.  bits: the entry point's sample depth.
-static int resolve_yuv(int format, int bits, size_t row_pitch, size_t frame_stride, int B, int H, int W, unsigned colour,
-                       YuvLayout* lay)
-{
-    if (int rc = check_colour_flags(colour, bits)) return rc;
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
-    const size_t tight = yuv_frame_samples(format, H, W);
-    if (!tight) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_yuv_format");
-    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
-    if (row_pitch > big || frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: a value above 2^40");
-    if (yuv_is_packed(format)) {
-        if (bits != 8) return fail(FIUNET_ERR_INVALID_ARG, "format: uyvy422 / yuyv422 are 8-bit formats");
-        if (W & 1) return fail(FIUNET_ERR_INVALID_ARG, "uyvy422 / yuyv422 need an even width");
-        const size_t row = 2 * (size_t)W;
-        lay->row_pitch = row_pitch ? row_pitch : row;
-        if (lay->row_pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: row_pitch < 2*W");
-        lay->frame_stride = frame_stride ? frame_stride : (size_t)H * lay->row_pitch;
-        if (lay->frame_stride < (size_t)(H - 1) * lay->row_pitch + row)
-            return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: frame_stride does not cover the last row");
-        return FIUNET_OK;
-    }
-    if (row_pitch) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: planar frames are tight (row_pitch must be 0)");
-    lay->row_pitch = 0;
-    lay->frame_stride = frame_stride ? frame_stride : tight;
-    if (lay->frame_stride < tight) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: frame_stride smaller than one frame");
-    return FIUNET_OK;
-}
-
-extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
-// vector accesses: W and every pitch and stride a multiple of 4 samples, bases aligned to 4 samples
-template <typename T>
-static bool yuv_vec(const YuvLayout& lay, int W, const void* a, const void* b)
-{
-    return W % 4 == 0 && (lay.row_pitch | lay.frame_stride) % 4 == 0 &&
-           (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
-}
-
-template <int F>
-using YuvFormat = std::integral_constant<int, F>;
-
-// go(YuvFormat<F>{}) for the resolved `format` (the one-plane formats exist at 8 bits only: resolve_yuv has refused them
-// at 10, and their uint16 kernels are never instantiated)
-template <typename T, typename Go>
-static int for_yuv_format(int format, Go go)
-{
-    if (format == FIUNET_YUV_422P) return go(YuvFormat<FIUNET_YUV_422P>{});
-    if (format == FIUNET_YUV_444P) return go(YuvFormat<FIUNET_YUV_444P>{});
-    if constexpr (sizeof(T) == 1)
-        return format == FIUNET_YUV_UYVY422 ? go(YuvFormat<FIUNET_YUV_UYVY422>{}) : go(YuvFormat<FIUNET_YUV_YUYV422>{});
-    return FIUNET_OK;
-}
-
-template <typename T>
-static int yuv_to_rgb(const T* in, int format, size_t row_pitch, size_t frame_stride, T* out, int B, int H, int W,
-                      unsigned colour, int bits, void* stream)
-{
-    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    YuvLayout lay;
-    if (int rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay)) return rc;
-    return for_yuv_format<T>(format, [&](auto f) {
-        constexpr int F = decltype(f)::value;
-        return launch_vec<&yuv_to_rgb_kernel<T, F, true>, &yuv_to_rgb_kernel<T, F, false>>(
-            yuv_vec<T>(lay, W, in, out), colour_grid(W, H, B), stream, in, lay, out, H, W, colour_coef(colour, bits));
-    });
-}
-
-template <typename T>
-static int rgb_to_yuv(const T* in, T* out, int format, size_t row_pitch, size_t frame_stride, int B, int H, int W,
-                      unsigned colour, int bits, void* stream)
-{
-    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    YuvLayout lay;
-    if (int rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay)) return rc;
-    return for_yuv_format<T>(format, [&](auto f) {
-        constexpr int F = decltype(f)::value;
-        return launch_vec<&rgb_to_yuv_kernel<T, F, true>, &rgb_to_yuv_kernel<T, F, false>>(
-            yuv_vec<T>(lay, W, in, out), colour_grid(W, H, B), stream, in, out, lay, H, W, colour_coef(colour, bits));
-    });
-}
-
-template <typename T>
-static int forward_yuv(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2, int format,
-                       size_t in_row_pitch, size_t in_frame_stride, T* out, size_t out_row_pitch, size_t out_frame_stride,
-                       int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
-                       void* stream)
-{
-    return forward_staged<T>(
-        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
-        [&] {
-            YuvLayout lay;
-            const int rc = resolve_yuv(format, bits, in_row_pitch, in_frame_stride, B, H, W, colour, &lay);
-            return rc ? rc : resolve_yuv(format, bits, out_row_pitch, out_frame_stride, B, H, W, colour, &lay);
-        },
-        [&](const T* in, T* rgb) {
-            return yuv_to_rgb<T>(in, format, in_row_pitch, in_frame_stride, rgb, B, H, W, colour, bits, stream);
-        },
-        [&](const T* rgb) {
-            return rgb_to_yuv<T>(rgb, out, format, out_row_pitch, out_frame_stride, B, H, W, colour, bits, stream);
-        });
-}
-}  // extern "C++"
-
-int fiunet_yuv_to_rgb_u8(const uint8_t* in, int format, size_t row_pitch, size_t frame_stride, uint8_t* out, int B,
-                         int H, int W, unsigned colour, void* stream)
-{
-    return yuv_to_rgb<uint8_t>(in, format, row_pitch, frame_stride, out, B, H, W, colour, 8, stream);
-}
-
-int fiunet_rgb_to_yuv_u8(const uint8_t* in, uint8_t* out, int format, size_t row_pitch, size_t frame_stride, int B,
-                         int H, int W, unsigned colour, void* stream)
-{
-    return rgb_to_yuv<uint8_t>(in, out, format, row_pitch, frame_stride, B, H, W, colour, 8, stream);
-}
-
-int fiunet_yuv_to_rgb_p10(const uint16_t* in, int format, size_t row_pitch, size_t frame_stride, uint16_t* out, int B,
-                          int H, int W, unsigned colour, void* stream)
-{
-    return yuv_to_rgb<uint16_t>(in, format, row_pitch, frame_stride, out, B, H, W, colour, 10, stream);
-}
-
-int fiunet_rgb_p10_to_yuv(const uint16_t* in, uint16_t* out, int format, size_t row_pitch, size_t frame_stride, int B,
-                          int H, int W, unsigned colour, void* stream)
-{
-    return rgb_to_yuv<uint16_t>(in, out, format, row_pitch, frame_stride, B, H, W, colour, 10, stream);
-}
-
-size_t fiunet_workspace_bytes_yuv(const fiunet_ctx* ctx, int B, int H, int W, int precision, int bits)
-{
-    if (bits == 8 || bits == 10) return staged_workspace(ctx, B, H, W, precision, bits == 8 ? 1 : 2).total;
-    g_err = "fiunet_workspace_bytes_yuv: bits must be 8 or 10";
-    return 0;
-}
-
-int fiunet_forward_yuv(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, int format, size_t in_row_pitch,
-                       size_t in_frame_stride, uint8_t* out, size_t out_row_pitch, size_t out_frame_stride, int B, int H,
-                       int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes, void* stream)
-{
-    return forward_yuv<uint8_t>("fiunet_forward_yuv", 8, ctx, frame1, frame2, format, in_row_pitch, in_frame_stride, out,
-                                out_row_pitch, out_frame_stride, B, H, W, colour, precision, workspace, workspace_bytes,
-                                stream);
-}
-
-int fiunet_forward_yuv_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, int format,
-                           size_t in_row_pitch, size_t in_frame_stride, uint16_t* out, size_t out_row_pitch,
-                           size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision, void* workspace,
-                           size_t workspace_bytes, void* stream)
-{
-    return forward_yuv<uint16_t>("fiunet_forward_yuv_p10", 10, ctx, frame1, frame2, format, in_row_pitch, in_frame_stride,
-                                 out, out_row_pitch, out_frame_stride, B, H, W, colour, precision, workspace,
-                                 workspace_bytes, stream);
-}
-
-// ---- packed RGB frames: rgb24 / bgr24 / rgba / bgra, rows a pitch apart, <-> planar RGB ----
-static int packed_bpp(int format)
-{
-    return format == FIUNET_PACKED_RGB24 || format == FIUNET_PACKED_BGR24 ? 3
-         : format == FIUNET_PACKED_RGBA || format == FIUNET_PACKED_BGRA ? 4 : 0;
-}
-
-// The caller's layout (NULL or zero fields = tight) -> the resolved one, refused before any launch where it cannot hold
-// an H x W frame of bpp bytes per pixel.  Every quantity in bytes.
-static int resolve_packed(const fiunet_packed_layout* l, int H, int W, int bpp, PackedLayout* pl)
-{
-    const size_t row = (size_t)W * bpp, big = (size_t)1 << 40;   // (keeps every product below in range)
-    pl->row_pitch = l && l->row_pitch ? l->row_pitch : row;
-    if (pl->row_pitch > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
-    pl->frame_stride = l && l->frame_stride ? l->frame_stride : (size_t)H * pl->row_pitch;
-    if (pl->frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
-    if (pl->row_pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: row_pitch < W*bpp");
-    if (pl->frame_stride < (size_t)(H - 1) * pl->row_pitch + row)
-        return fail(FIUNET_ERR_INVALID_ARG, "packed layout: frame_stride does not cover the last row");
-    return FIUNET_OK;
-}
-
-static int check_packed_args(const void* in, const void* out, int B, int H, int W, int format)
-{
-    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (!packed_bpp(format)) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
-    return FIUNET_OK;
-}
-
-// dword and 16-byte packed accesses, uchar4 plane accesses: W and every pitch, stride and base a multiple of 4 bytes
-static bool packed_vec(int W, const PackedLayout& l, uintptr_t bases)
-{
-    return W % 4 == 0 && (l.row_pitch | l.frame_stride) % 4 == 0 && (bases & 3) == 0;
-}
-
-extern "C++" {
-template <int BPP, bool SWAP>
-struct PackedFormat {
-    static constexpr int bpp = BPP;
-    static constexpr bool swap = SWAP;
-};
-
-// go(PackedFormat<bpp, swap>{}) for a format that packed_bpp() knows
-template <typename Go>
-static int for_packed_format(int format, Go go)
-{
-    switch (format) {
-    case FIUNET_PACKED_RGB24: return go(PackedFormat<3, false>{});
-    case FIUNET_PACKED_BGR24: return go(PackedFormat<3, true>{});
-    case FIUNET_PACKED_RGBA: return go(PackedFormat<4, false>{});
-    default: return go(PackedFormat<4, true>{});
-    }
-}
-}  // extern "C++"
-
-int fiunet_packed_to_rgb_u8(const uint8_t* in, const fiunet_packed_layout* in_layout, uint8_t* out_rgb,
-                            uint8_t* alpha_out, int B, int H, int W, int format, void* stream)
-{
-    int rc;
-    if ((rc = check_packed_args(in, out_rgb, B, H, W, format))) return rc;
-    const int bpp = packed_bpp(format);
-    if (alpha_out && bpp != 4) return fail(FIUNET_ERR_INVALID_ARG, "alpha_out: the format has no alpha byte");
-    PackedLayout li;
-    if ((rc = resolve_packed(in_layout, H, W, bpp, &li))) return rc;
-    const bool vec = packed_vec(W, li, (uintptr_t)in | (uintptr_t)out_rgb | (uintptr_t)alpha_out);
-    return for_packed_format(format, [&](auto f) {
-        using F = decltype(f);
-        return launch_vec<&packed_to_rgb_kernel<F::bpp, F::swap, true>, &packed_to_rgb_kernel<F::bpp, F::swap, false>>(
-            vec, colour_grid(W, H, B), stream, in, li, out_rgb, alpha_out, H, W);
-    });
-}
-
-int fiunet_rgb_to_packed_u8(const uint8_t* in_rgb, uint8_t* out, const fiunet_packed_layout* out_layout,
-                            const uint8_t* alpha1, const uint8_t* alpha2, const fiunet_packed_layout* alpha_layout,
-                            int B, int H, int W, int format, void* stream)
-{
-    int rc;
-    if ((rc = check_packed_args(in_rgb, out, B, H, W, format))) return rc;
-    const int bpp = packed_bpp(format);
-    if ((alpha1 || alpha2) && bpp != 4) return fail(FIUNET_ERR_INVALID_ARG, "alpha source: the format has no alpha byte");
-    if (alpha2 && !alpha1) return fail(FIUNET_ERR_INVALID_ARG, "alpha2 without alpha1");
-    PackedLayout lo, la;
-    if ((rc = resolve_packed(out_layout, H, W, bpp, &lo))) return rc;
-    if ((rc = resolve_packed(alpha_layout, H, W, bpp, &la))) return rc;
-    const bool vec = packed_vec(W, lo, (uintptr_t)in_rgb | (uintptr_t)out | (uintptr_t)alpha1 | (uintptr_t)alpha2) &&
-                     (!alpha1 || packed_vec(W, la, 0));
-    return for_packed_format(format, [&](auto f) {
-        using F = decltype(f);
-        return launch_vec<&rgb_to_packed_kernel<F::bpp, F::swap, true>, &rgb_to_packed_kernel<F::bpp, F::swap, false>>(
-            vec, colour_grid(W, H, B), stream, in_rgb, out, lo, alpha1, alpha2, la, H, W);
-    });
-}
-
-size_t fiunet_workspace_bytes_rgb_packed(const fiunet_ctx* ctx, int B, int H, int W, int precision)
-{
-    return staged_workspace(ctx, B, H, W, precision, 1).total;
-}
-
-int fiunet_forward_rgb_packed(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
-                              const fiunet_packed_layout* in_layout, uint8_t* out, const fiunet_packed_layout* out_layout,
-                              int B, int H, int W, int format, int precision, void* workspace, size_t workspace_bytes,
-                              void* stream)
-{
-    const int bpp = packed_bpp(format);
-    const bool alpha = bpp == 4;   // the inserted frame's alpha: the rounded average of its neighbours'
-    return forward_staged<uint8_t>(
-        "fiunet_forward_rgb_packed", ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
-        [&] {
-            if (!bpp) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
-            PackedLayout pl;
-            const int rc = resolve_packed(in_layout, H, W, bpp, &pl);
-            return rc ? rc : resolve_packed(out_layout, H, W, bpp, &pl);
-        },
-        [&](const uint8_t* in, uint8_t* rgb) { return fiunet_packed_to_rgb_u8(in, in_layout, rgb, NULL, B, H, W, format, stream); },
-        [&](const uint8_t* rgb) {
-            return fiunet_rgb_to_packed_u8(rgb, out, out_layout, alpha ? frame1 : NULL, alpha ? frame2 : NULL, in_layout, B,
-                                           H, W, format, stream);
-        });
-}
-
-static inline int ssim_tiles(int H, int W, int* tiles_x)
-{
-    const int ow = W - 2 * SSIM_PAD, oh = H - 2 * SSIM_PAD;
-    const int tx = (ow + SSIM_TX - 1) / SSIM_TX, ty = (oh + SSIM_TY - 1) / SSIM_TY;
-    if (tiles_x) *tiles_x = tx;
-    return tx * ty;
-}
-
-size_t fiunet_metrics_workspace_bytes(int images, int H, int W)
-{
-    if (images < 1 || H < 1 || W < 1) {
-        g_err = "fiunet_metrics_workspace_bytes: bad arguments";
-        return 0;
-    }
-    const size_t tiles = (H >= SSIM_WIN && W >= SSIM_WIN) ? (size_t)ssim_tiles(H, W, nullptr) : 0;
-    return align256((size_t)images * 8) + align256((size_t)images * tiles * 8);
-}
-
-int fiunet_psnr_u8(const uint8_t* pred, const uint8_t* target, int images, int H, int W, double* out,
-                   void* workspace, size_t workspace_bytes, void* stream)
-{
-    if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_BAD_SHAPE, "bad image shape");
-    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
-    if (workspace_bytes < align256((size_t)images * 8)) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
-    const size_t n = (size_t)H * W;
-    if (int rc = zero_fill_async(sums, (size_t)images * 8, s)) return rc;
-    // ~4 x 16 B per thread and at most 128 workgroups (= atomics) per image
-    const unsigned bx = (unsigned)std::min<size_t>((n / 64 + 255) / 256 + 1, 128);
-    hipLaunchKernelGGL(sqdiff_u8_kernel, dim3(bx, (unsigned)images), dim3(256), 0, s, pred, target, n, sums);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(psnr_finalize_kernel, dim3((images + 63) / 64), dim3(64), 0, s, sums, n, out, images);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int fiunet_ssim_u8(const uint8_t* pred, const uint8_t* target, int images, int H, int W, double* out,
-                   void* workspace, size_t workspace_bytes, void* stream)
-{
-    if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (images < 1) return fail(FIUNET_ERR_BAD_SHAPE, "bad image shape");
-    if (H < SSIM_WIN || W < SSIM_WIN)
-        return fail(FIUNET_ERR_BAD_SHAPE, "SSIM: the 7x7 window exceeds the image (skimage raises too)");
-    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
-    if (workspace_bytes < fiunet_metrics_workspace_bytes(images, H, W))
-        return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    hipStream_t s = (hipStream_t)stream;
-    int tx = 0;
-    const int tiles = ssim_tiles(H, W, &tx);
-    double* partial = (double*)((char*)workspace + align256((size_t)images * 8));
-    hipLaunchKernelGGL(ssim_u8_kernel, dim3((unsigned)tiles, (unsigned)images), dim3(256), 0, s, pred, target,
-                       H, W, tx, partial);
-    HIP_TRY(hipGetLastError());
-    const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
-    hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-size_t fiunet_plane_metrics_workspace_bytes(int images, int H, int W)
-{
-    if (images < 1 || H < 1 || W < 1) {
-        g_err = "fiunet_plane_metrics_workspace_bytes: bad arguments";
-        return 0;
-    }
-    return fiunet_metrics_workspace_bytes(images, H, W);
-}
-
-// The checks both plane metrics share; every refusal is FIUNET_ERR_INVALID_ARG and comes before any pointer is used.
-// pred_row / target_row: the samples a row spans on each side (W; W*S interleaved; (W-1)*step + 1 stepped).
-static int check_planes(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
-                        size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
-                        const void* out, const void* workspace, size_t workspace_bytes, size_t need,
-                        size_t pred_row = 0, size_t target_row = 0)
-{
-    if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
-    if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_INVALID_ARG, "bad plane shape");
-    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
-    if (!pred_row) pred_row = (size_t)W;
-    if (!target_row) target_row = (size_t)W;
-    if (pred_row_pitch < pred_row || target_row_pitch < target_row)
-        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: row_pitch < W");
-    const size_t limit = (size_t)1 << 40;
-    if (pred_row_pitch > limit || target_row_pitch > limit || pred_image_stride > limit || target_image_stride > limit)
-        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: a value above 2^40 samples");
-    if (images > 1 && (pred_image_stride < (size_t)(H - 1) * pred_row_pitch + pred_row ||
-                       target_image_stride < (size_t)(H - 1) * target_row_pitch + target_row))
-        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: image_stride smaller than one plane");
-    const size_t align = bits == 10 ? 1 : 0;
-    if ((((uintptr_t)pred | (uintptr_t)target) & align) != 0)
-        return fail(FIUNET_ERR_INVALID_ARG, "10-bit planes are 16-bit words: odd address");
-    if (workspace_bytes < need) return fail(FIUNET_ERR_INVALID_ARG, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    return FIUNET_OK;
-}
-
-extern "C++" {   // (a template over the sample type, inside this file's extern "C" part)
-template <typename T>
-static int launch_plane_psnr(const void* pred, size_t ps, size_t pp, const void* target, size_t ts, size_t tp,
-                             int images, int H, int W, unsigned long long* sums, hipStream_t s)
-{
-    // a plane whose rows follow each other on both sides is one run of H*W samples, cut into PLANE_SEG pieces
-    // (a multiple of 16 bytes, so every piece of an aligned plane keeps the 16-byte path)
-    const size_t n = (size_t)H * W;
-    const bool flat = pp == (size_t)W && tp == (size_t)W;
-    if (flat && (n + PLANE_SEG - 1) / PLANE_SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
-    const unsigned rows = flat ? (unsigned)((n + PLANE_SEG - 1) / PLANE_SEG) : (unsigned)H;
-    const unsigned w = flat ? (unsigned)PLANE_SEG : (unsigned)W;
-    const unsigned w_last = flat ? (unsigned)(n - (size_t)(rows - 1) * PLANE_SEG) : (unsigned)W;
-    const size_t pa = flat ? (size_t)PLANE_SEG : pp, pb = flat ? (size_t)PLANE_SEG : tp;
-    // one wave per row and step, at most 128 workgroups (= atomics) per image
-    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
-    hipLaunchKernelGGL(plane_sqdiff_kernel<T>, dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)pred, ps, pa,
-                       (const T*)target, ts, pb, rows, w, w_last, sums);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-}  // extern "C++"
-
-int fiunet_plane_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
-                      size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
-                      double* out_psnr, unsigned long long* out_sse, void* workspace, size_t workspace_bytes,
-                      void* stream)
-{
-    const size_t need = images > 0 ? align256((size_t)images * 8) : 0;
-    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
-                              bits, images, H, W, out_psnr, workspace, workspace_bytes, need))
-        return rc;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
-    if (int rc = zero_fill_async(sums, (size_t)images * 8, s)) return rc;
-    if (int rc = bits == 10 ? launch_plane_psnr<uint16_t>(pred, pred_image_stride, pred_row_pitch, target,
-                                                          target_image_stride, target_row_pitch, images, H, W, sums, s)
-                            : launch_plane_psnr<uint8_t>(pred, pred_image_stride, pred_row_pitch, target,
-                                                         target_image_stride, target_row_pitch, images, H, W, sums, s))
-        return rc;
-    hipLaunchKernelGGL(plane_psnr_finalize_kernel, dim3((images + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
-                       bits == 10 ? 1023.0 : 255.0, out_psnr, out_sse, images);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int fiunet_stepped_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, int pred_step,
-                              const void* target, size_t target_image_stride, size_t target_row_pitch, int target_step,
-                              int bits, int images, int H, int W, double* out_ssim, void* workspace,
-                              size_t workspace_bytes, void* stream)
-{
-    if (pred_step < 1 || pred_step > 4 || target_step < 1 || target_step > 4)
-        return fail(FIUNET_ERR_INVALID_ARG, "sample step must be 1, 2, 3 or 4");
-    if (H < SSIM_WIN || W < SSIM_WIN)
-        return fail(FIUNET_ERR_INVALID_ARG, "SSIM: the 7x7 window exceeds the plane (skimage raises too)");
-    const size_t need = images > 0 ? fiunet_metrics_workspace_bytes(images, H, W) : 0;
-    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
-                              bits, images, H, W, out_ssim, workspace, workspace_bytes, need,
-                              (size_t)(W - 1) * pred_step + 1, (size_t)(W - 1) * target_step + 1))
-        return rc;
-    hipStream_t s = (hipStream_t)stream;
-    int tx = 0;
-    const int tiles = ssim_tiles(H, W, &tx);
-    double* partial = (double*)((char*)workspace + align256((size_t)images * 8));
-    const dim3 grid((unsigned)tiles, (unsigned)images);
-    if (bits == 10)
-        hipLaunchKernelGGL(plane_ssim_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)pred, pred_image_stride,
-                           pred_row_pitch, (unsigned)pred_step, (const uint16_t*)target, target_image_stride,
-                           target_row_pitch, (unsigned)target_step, H, W, tx, partial);
-    else
-        hipLaunchKernelGGL(plane_ssim_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)pred, pred_image_stride,
-                           pred_row_pitch, (unsigned)pred_step, (const uint8_t*)target, target_image_stride,
-                           target_row_pitch, (unsigned)target_step, H, W, tx, partial);
-    HIP_TRY(hipGetLastError());
-    const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
-    hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out_ssim);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
-                      size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
-                      double* out_ssim, void* workspace, size_t workspace_bytes, void* stream)
-{
-    return fiunet_stepped_ssim(pred, pred_image_stride, pred_row_pitch, 1, target, target_image_stride,
-                                     target_row_pitch, 1, bits, images, H, W, out_ssim, workspace, workspace_bytes,
-                                     stream);
-}
-
-extern "C++" {
-template <typename T, int S>
-static int launch_interleaved_sqdiff(const void* pred, size_t ps, size_t pp, const void* target, size_t ts, size_t tp,
-                                     int images, int H, int W, unsigned long long* sums, hipStream_t s)
-{
-    // rows that follow each other on both sides are one run of H*W*S samples, cut into interleaved_seg(S) pieces (a
-    // multiple of S and of 16 bytes: a piece starts at component 0 and an aligned run keeps the 16-byte path)
-    constexpr size_t SEG = interleaved_seg(S);
-    const size_t row = (size_t)W * S, n = (size_t)H * row;
-    const bool flat = pp == row && tp == row;
-    if (flat && (n + SEG - 1) / SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
-    const unsigned rows = flat ? (unsigned)((n + SEG - 1) / SEG) : (unsigned)H;
-    const unsigned len = flat ? (unsigned)SEG : (unsigned)row;
-    const unsigned l_last = flat ? (unsigned)(n - (size_t)(rows - 1) * SEG) : (unsigned)row;
-    const size_t pa = flat ? SEG : pp, pb = flat ? SEG : tp;
-    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
-    hipLaunchKernelGGL((interleaved_sqdiff_kernel<T, S>), dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)pred, ps,
-                       pa, (const T*)target, ts, pb, rows, len, l_last, sums);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-template <typename T>
-static int launch_interleaved_psnr(int S, const void* pred, size_t ps, size_t pp, const void* target, size_t ts,
-                                   size_t tp, int images, int H, int W, unsigned long long* sums, hipStream_t s)
-{
-    if (S == 2) return launch_interleaved_sqdiff<T, 2>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
-    if (S == 3) return launch_interleaved_sqdiff<T, 3>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
-    return launch_interleaved_sqdiff<T, 4>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
-}
-}  // extern "C++"
-
-int fiunet_interleaved_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
-                            size_t target_image_stride, size_t target_row_pitch, int bits, int components, int images,
-                            int H, int W, double* out_psnr, unsigned long long* out_sse, void* workspace,
-                            size_t workspace_bytes, void* stream)
-{
-    if (components < 2 || components > 4) return fail(FIUNET_ERR_INVALID_ARG, "components must be 2, 3 or 4");
-    if (W > (1 << 29)) return fail(FIUNET_ERR_INVALID_ARG, "bad plane shape");
-    if (images > 65535 / components)
-        return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 component planes (images x components) per call");
-    const size_t row = W > 0 ? (size_t)W * components : 0;
-    const size_t need = images > 0 ? align256((size_t)images * components * 8) : 0;
-    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
-                              bits, images, H, W, out_psnr, workspace, workspace_bytes, need, row, row))
-        return rc;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
-    const int planes = images * components;
-    if (int rc = zero_fill_async(sums, (size_t)planes * 8, s)) return rc;
-    if (int rc = bits == 10 ? launch_interleaved_psnr<uint16_t>(components, pred, pred_image_stride, pred_row_pitch,
-                                                                target, target_image_stride, target_row_pitch, images,
-                                                                H, W, sums, s)
-                            : launch_interleaved_psnr<uint8_t>(components, pred, pred_image_stride, pred_row_pitch,
-                                                               target, target_image_stride, target_row_pitch, images, H,
-                                                               W, sums, s))
-        return rc;
-    hipLaunchKernelGGL(plane_psnr_finalize_kernel, dim3((planes + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
-                       bits == 10 ? 1023.0 : 255.0, out_psnr, out_sse, planes);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-static inline int gssim_tiles(int H, int W, int* tiles_x)
-{
-    const int tx = (W + GSSIM_TX - 1) / GSSIM_TX, ty = (H + GSSIM_TY - 1) / GSSIM_TY;
-    if (tiles_x) *tiles_x = tx;
-    return tx * ty;
-}
-
-size_t fiunet_ssim_gauss_workspace_bytes(int images, int H, int W)
-{
-    if (images < 1 || H < 1 || W < 1) {
-        g_err = "fiunet_ssim_gauss_workspace_bytes: bad arguments";
-        return 0;
-    }
-    return align256((size_t)images * gssim_tiles(H, W, nullptr) * 2 * 8);
-}
-
-int fiunet_ssim_gauss_f32(const float* img1, const float* img2, int images, int H, int W, int window_size,
-                          const float* window_1d, double* out_ssim, double* out_sqerr, void* workspace,
-                          size_t workspace_bytes, void* stream)
-{
-    if (!img1 || !img2 || !out_ssim || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_BAD_SHAPE, "bad image shape");
-    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
-    if (window_size < 1 || window_size > 2 * GSSIM_MAXR + 1 || !(window_size & 1))
-        return fail(FIUNET_ERR_UNSUPPORTED, "Gaussian SSIM: window_size must be odd and <= 31 (an even window "
-                                            "changes the map size in the reference: padding = window_size//2)");
-    if (workspace_bytes < fiunet_ssim_gauss_workspace_bytes(images, H, W))
-        return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    // train.py:27-29: fp32 tensor of exp(-(x - ws//2)^2 / (2 sigma^2)) (evaluated in double by numpy), sigma =
-    // 1.5 (:32), divided by its fp32 sum
-    const int R = window_size / 2;
-    GaussWindow win;
-    float sum = 0.f;
-    for (int x = 0; x < window_size; ++x) {
-        win.g[x] = (float)std::exp(-(double)((x - R) * (x - R)) / (2.0 * 1.5 * 1.5));
-        sum += win.g[x];
-    }
-    for (int x = 0; x < window_size; ++x) win.g[x] /= sum;
-    // the caller's own normalised window (torch's `gauss / gauss.sum()`: its reduction order decides the last
-    // bit of the sum, and the SSIM map's variance terms feel 1 ulp of the window's total at the 1e-7 level)
-    if (window_1d)
-        for (int x = 0; x < window_size; ++x) win.g[x] = window_1d[x];
-    for (int x = window_size; x < 2 * GSSIM_MAXR + 1; ++x) win.g[x] = 0.f;
-    hipStream_t s = (hipStream_t)stream;
-    int tx = 0;
-    const int tiles = gssim_tiles(H, W, &tx);
-    double* partial = (double*)workspace;
-    const int IH = GSSIM_TY + 2 * R, IW = GSSIM_TX + 2 * R;
-    const size_t lds = (size_t)5 * IH * GSSIM_TX * 8 + (size_t)2 * IH * (IW + 1) * 4;
-    if (R == 5)
-        hipLaunchKernelGGL((ssim_gauss_f32_kernel<5>), dim3((unsigned)tiles, (unsigned)images), dim3(256), lds, s,
-                           img1, img2, H, W, tx, R, win, partial);
-    else
-        hipLaunchKernelGGL((ssim_gauss_f32_kernel<0>), dim3((unsigned)tiles, (unsigned)images), dim3(256), lds, s,
-                           img1, img2, H, W, tx, R, win, partial);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ssim_gauss_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles,
-                       (double)H * (double)W, out_ssim, out_sqerr);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
 int fiunet_preprocess_u8(const uint8_t* in, float* out, size_t n, void* stream)
 {
     if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
@@ -2443,297 +1314,6 @@ int fiunet_postprocess_p10(const float* in, uint16_t* out, size_t n, void* strea
     hipLaunchKernelGGL(postprocess_p10_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, in, out, n);
     HIP_TRY(hipGetLastError());
     return FIUNET_OK;
-}
-
-// ---- scene cuts (csrc/scene.hip.h) -------------------------------------------------------------
-constexpr int kMaxGridY = 65535;   // pairs / intervals per launch (grid.y)
-
-extern "C++" {   // (a template inside the extern "C" block)
-template <typename T>
-static int pair_sad(const T* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
-{
-    if (!frames || !sums) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
-    if (n_frames < 2 || frame_samples == 0) return FIUNET_OK;
-    // ~4 x 16 B per thread and at most 128 workgroups (= atomics) per pair, as fiunet_psnr_u8
-    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
-    for (int p0 = 0; p0 < n_frames - 1; p0 += kMaxGridY) {
-        const int np = std::min(n_frames - 1 - p0, kMaxGridY);
-        hipLaunchKernelGGL(pair_sad_kernel<T>, dim3(bx, (unsigned)np), dim3(kSceneBlock), 0, (hipStream_t)stream,
-                           frames + (size_t)p0 * frame_samples, frame_samples,
-                           reinterpret_cast<unsigned long long*>(sums + p0));
-        HIP_TRY(hipGetLastError());
-    }
-    return FIUNET_OK;
-}
-}  // extern "C++"
-
-int fiunet_pair_sad_u8(const uint8_t* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
-{
-    return pair_sad(frames, n_frames, frame_samples, sums, stream);
-}
-
-int fiunet_pair_sad_p10(const uint16_t* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
-{
-    return pair_sad(frames, n_frames, frame_samples, sums, stream);
-}
-
-// repeated frames: the calling conventions of pair_sad
-extern "C++" {
-template <typename T>
-static int pair_peak(const T* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
-{
-    if (!frames || !peaks) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
-    if (n_frames < 2 || frame_samples == 0) return FIUNET_OK;
-    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
-    for (int p0 = 0; p0 < n_frames - 1; p0 += kMaxGridY) {
-        const int np = std::min(n_frames - 1 - p0, kMaxGridY);
-        hipLaunchKernelGGL(pair_peak_kernel<T>, dim3(bx, (unsigned)np), dim3(kSceneBlock), 0, (hipStream_t)stream,
-                           frames + (size_t)p0 * frame_samples, frame_samples, peaks + p0);
-        HIP_TRY(hipGetLastError());
-    }
-    return FIUNET_OK;
-}
-}  // extern "C++"
-
-int fiunet_pair_peak_u8(const uint8_t* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
-{
-    return pair_peak(frames, n_frames, frame_samples, peaks, stream);
-}
-
-int fiunet_pair_peak_p10(const uint16_t* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
-{
-    return pair_peak(frames, n_frames, frame_samples, peaks, stream);
-}
-
-int fiunet_scene_cuts(const int64_t* sums, int n_frames, size_t count, int bits, double threshold, double* scores,
-                      uint8_t* flags, void* stream)
-{
-    if (!sums || !scores || !flags) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
-    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
-    if (!(threshold > 0.0 && threshold <= 100.0)) return fail(FIUNET_ERR_INVALID_ARG, "threshold outside (0, 100]");
-    if (count == 0) return fail(FIUNET_ERR_INVALID_ARG, "count == 0");
-    if (n_frames < 2) return FIUNET_OK;
-    const int intervals = n_frames - 1;
-    hipLaunchKernelGGL(scene_cuts_kernel, dim3((unsigned)((intervals + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, reinterpret_cast<const long long*>(sums), intervals, (double)count,
-                       (double)(1 << bits), threshold, scores, flags);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int fiunet_hold_cut_frames(uint8_t* video, int n_frames, size_t frame_bytes, int factor, const uint8_t* flags,
-                           void* stream)
-{
-    if (!video || !flags) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
-    if (factor < 2 || (factor & (factor - 1)) || factor > (1 << 20))
-        return fail(FIUNET_ERR_INVALID_ARG, "factor must be a power of two in [2, 2^20]");
-    if (n_frames < 2 || frame_bytes == 0) return FIUNET_OK;
-    const unsigned gx = (unsigned)kHoldBlocks * (unsigned)(factor - 1);
-    for (int i0 = 0; i0 < n_frames - 1; i0 += kMaxGridY) {
-        const int ni = std::min(n_frames - 1 - i0, kMaxGridY);
-        hipLaunchKernelGGL(hold_cut_frames_kernel, dim3(gx, (unsigned)ni), dim3(kSceneBlock), 0, (hipStream_t)stream,
-                           video + (size_t)i0 * factor * frame_bytes, frame_bytes, factor, flags + i0);
-        HIP_TRY(hipGetLastError());
-    }
-    return FIUNET_OK;
-}
-
-// ---- frame-rate conversion (csrc/retime.hip.h) ---------------------------------------------------
-extern "C++" {
-template <typename T>
-static int retime(const T* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval, uint64_t j0,
-                  int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, T* out, void* stream)
-{
-    if (!grid || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (n_intervals < 0 || n_out < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
-    if (depth < 1 || depth > 4) return fail(FIUNET_ERR_INVALID_ARG, "depth outside 1..4");
-    if (p == 0 || p >= q) return fail(FIUNET_ERR_INVALID_ARG, "need 0 < p < q");
-    if (q > kRetimeMaxQ) return fail(FIUNET_ERR_INVALID_ARG, "q above 2^20");
-    if (mode != 0 && mode != 1) return fail(FIUNET_ERR_INVALID_ARG, "mode must be 0 (blend) or 1 (nearest)");
-    if (n_out == 0) return FIUNET_OK;
-    // the first and the last requested frame lie in the grid (the times in between do, being monotonic); in 128 bits,
-    // so that the kernel's 64-bit j * p cannot wrap
-    const unsigned __int128 t0 = (unsigned __int128)j0 * p, t1 = ((unsigned __int128)j0 + (unsigned)(n_out - 1)) * p;
-    if (t1 >> 64) return fail(FIUNET_ERR_INVALID_ARG, "frame index too large");
-    const unsigned __int128 end = (unsigned __int128)first_interval + (unsigned)n_intervals;
-    if (t0 / q < first_interval) return fail(FIUNET_ERR_INVALID_ARG, "first frame lies before the grid");
-    if (t1 / q > end || (t1 / q == end && t1 % q != 0))
-        return fail(FIUNET_ERR_INVALID_ARG, "last frame lies behind the grid");
-    if (frame_samples == 0) return FIUNET_OK;
-    // ~4 x 16 B per thread and at most 128 workgroups per frame, as fiunet_pair_sad_u8
-    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
-    for (int k0 = 0; k0 < n_out; k0 += kMaxGridY) {
-        const int nk = std::min(n_out - k0, kMaxGridY);
-        hipLaunchKernelGGL(retime_kernel<T>, dim3(bx, (unsigned)nk), dim3(kRetimeBlock), 0, (hipStream_t)stream, grid,
-                           frame_samples, depth, (unsigned long long)first_interval, (unsigned long long)(j0 + k0), p, q,
-                           mode, flags, out + (size_t)k0 * frame_samples);
-        HIP_TRY(hipGetLastError());
-    }
-    return FIUNET_OK;
-}
-}  // extern "C++"
-
-int fiunet_retime_u8(const uint8_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
-                     uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint8_t* out,
-                     void* stream)
-{
-    return retime(grid, n_intervals, frame_samples, depth, first_interval, j0, n_out, p, q, mode, flags, out, stream);
-}
-
-int fiunet_retime_p10(const uint16_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
-                      uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint16_t* out,
-                      void* stream)
-{
-    return retime(grid, n_intervals, frame_samples, depth, first_interval, j0, n_out, p, q, mode, flags, out, stream);
-}
-
-// the table-driven form: every entry is checked here, on the host, before the first launch; the entries
-// travel in the kernel's arguments, kRetimeTableMax output frames per launch
-static_assert(sizeof(fiunet_retime_entry) == sizeof(RetimeEntry) && sizeof(RetimeEntry) == 12, "entry layout");
-
-extern "C++" {
-template <typename T>
-static int retime_table(const T* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries, int n_out,
-                        T* out, void* stream)
-{
-    if (!grid || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (n_rows < 0 || n_out < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
-    if (n_out == 0) return FIUNET_OK;
-    if (!entries) return fail(FIUNET_ERR_INVALID_ARG, "NULL entries");
-    for (int k = 0; k < n_out; ++k) {
-        const fiunet_retime_entry& e = entries[k];
-        if (e.den < 1 || e.den > kRetimeMaxQ) return fail(FIUNET_ERR_INVALID_ARG, "entry: den outside 1..2^20");
-        if (e.wn >= e.den) return fail(FIUNET_ERR_INVALID_ARG, "entry: wn >= den");
-        if ((uint64_t)e.row >= (uint64_t)n_rows) return fail(FIUNET_ERR_INVALID_ARG, "entry: row outside the grid");
-        if (e.wn > 0 && (uint64_t)e.row + 1 >= (uint64_t)n_rows)
-            return fail(FIUNET_ERR_INVALID_ARG, "entry: the row after `row` lies outside the grid");
-    }
-    if (frame_samples == 0) return FIUNET_OK;
-    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
-    for (int k0 = 0; k0 < n_out; k0 += kRetimeTableMax) {
-        const int nk = std::min(n_out - k0, kRetimeTableMax);
-        RetimeTable table = {};
-        for (int k = 0; k < nk; ++k) table.e[k] = RetimeEntry{entries[k0 + k].row, entries[k0 + k].wn, entries[k0 + k].den};
-        hipLaunchKernelGGL(retime_table_kernel<T>, dim3(bx, (unsigned)nk), dim3(kRetimeBlock), 0, (hipStream_t)stream,
-                           grid, frame_samples, table, out + (size_t)k0 * frame_samples);
-        HIP_TRY(hipGetLastError());
-    }
-    return FIUNET_OK;
-}
-}  // extern "C++"
-
-int fiunet_retime_table_u8(const uint8_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
-                           int n_out, uint8_t* out, void* stream)
-{
-    return retime_table(grid, n_rows, frame_samples, entries, n_out, out, stream);
-}
-
-int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
-                            int n_out, uint16_t* out, void* stream)
-{
-    return retime_table(grid, n_rows, frame_samples, entries, n_out, out, stream);
-}
-
-// ---- resizing frame planes (csrc/resize.hip.h) ------------------------------------------------------
-extern "C++" {
-// the byte range [lo, hi) that n frames of the planes cover, from the buffer's first sample
-static void resize_extent(const fiunet_resize_plane* planes, int n_planes, int n_frames, size_t& lo, size_t& hi)
-{
-    lo = SIZE_MAX, hi = 0;
-    for (int i = 0; i < n_planes; ++i) {
-        const fiunet_resize_plane& p = planes[i];
-        const size_t end = p.offset + (size_t)(n_frames - 1) * p.frame_stride + (size_t)(p.h - 1) * p.pitch +
-                           (size_t)(p.w - 1) * p.step + 1;
-        lo = std::min(lo, p.offset), hi = std::max(hi, end);
-    }
-}
-
-static const char* resize_check_plane(const fiunet_resize_plane& p)
-{
-    if (p.h < 1 || p.w < 1) return "a plane's h and w must be positive";
-    if (p.h > kResizeMaxSize || p.w > kResizeMaxSize) return "a plane's h and w must not exceed 2^24";
-    if (p.step < 1 || p.step > 4) return "a plane's step must be 1..4";
-    if (p.pitch < (size_t)(p.w - 1) * p.step + 1) return "a plane's pitch must cover a row: (w - 1) * step + 1";
-    // (h, w <= 2^24, step <= 4: the row term is below 2^26; the others are checked against wrapping)
-    const size_t row = (size_t)(p.w - 1) * p.step + 1;
-    if (p.h > 1 && p.pitch > (SIZE_MAX - row) / (size_t)(p.h - 1)) return "a plane's pitch is too large";
-    const size_t body = (size_t)(p.h - 1) * p.pitch + row;
-    if (p.offset > p.frame_stride || body > p.frame_stride - p.offset) return "a plane must lie inside its frame stride";
-    return nullptr;
-}
-
-template <typename T>
-static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, const fiunet_resize_plane* dp,
-                         int n_planes, int n_frames, void* stream)
-{
-    if (!src || !dst || !sp || !dp) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (((uintptr_t)src | (uintptr_t)dst) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
-    if (n_planes < 1 || n_planes > kResizeMaxPlanes) return fail(FIUNET_ERR_INVALID_ARG, "n_planes must be 1..4");
-    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
-    constexpr int V = ResizeSample<T>::kVec;
-    ResizeArgs base = {};
-    unsigned long long per_frame_max = 0;
-    for (int i = 0; i < n_planes; ++i) {
-        for (const fiunet_resize_plane* p : {&sp[i], &dp[i]}) {
-            if (const char* why = resize_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
-            // n frames of the plane stay inside the address space
-            if (n_frames > 1 && p->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_frames)
-                return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
-        }
-        ResizePlane& P = base.p[i];
-        P.src_off = sp[i].offset, P.src_pitch = sp[i].pitch, P.src_fs = sp[i].frame_stride;
-        P.dst_off = dp[i].offset, P.dst_pitch = dp[i].pitch, P.dst_fs = dp[i].frame_stride;
-        P.sh = sp[i].h, P.sw = sp[i].w, P.dh = dp[i].h, P.dw = dp[i].w;
-        P.sstep = sp[i].step, P.dstep = dp[i].step;
-        P.sx = (double)P.sw / (double)P.dw, P.sy = (double)P.sh / (double)P.dh;
-        P.chunks = (unsigned)((P.dw + V - 1) / V) + (P.dstep == 1 ? 1u : 0u);
-        const unsigned long long per_frame = (unsigned long long)P.dh * P.chunks;
-        if (per_frame >= (1ull << 31)) return fail(FIUNET_ERR_UNSUPPORTED, "a destination plane of 2^31 or more store chunks");
-        per_frame_max = std::max(per_frame_max, per_frame);
-    }
-    if (n_frames == 0) return FIUNET_OK;
-    size_t slo, shi, dlo, dhi;
-    resize_extent(sp, n_planes, n_frames, slo, shi);
-    resize_extent(dp, n_planes, n_frames, dlo, dhi);
-    const uintptr_t s0 = (uintptr_t)src + slo * sizeof(T), s1 = (uintptr_t)src + shi * sizeof(T);
-    const uintptr_t d0 = (uintptr_t)dst + dlo * sizeof(T), d1 = (uintptr_t)dst + dhi * sizeof(T);
-    if (s0 < d1 && d0 < s1) return fail(FIUNET_ERR_INVALID_ARG, "source and destination overlap");
-    // frames per launch: every plane's item count stays below 2^31
-    const int batch = (int)std::min<unsigned long long>(((1ull << 31) - 1) / per_frame_max, (unsigned long long)n_frames);
-    for (int f0 = 0; f0 < n_frames; f0 += batch) {
-        const int nf = std::min(batch, n_frames - f0);
-        ResizeArgs args = base;
-        unsigned items_max = 0;
-        for (int i = 0; i < n_planes; ++i) {
-            ResizePlane& P = args.p[i];
-            P.src_off += (size_t)f0 * P.src_fs, P.dst_off += (size_t)f0 * P.dst_fs;
-            P.items = (unsigned)nf * (unsigned)P.dh * P.chunks;
-            items_max = std::max(items_max, P.items);
-        }
-        // one item per thread up to 8192 workgroups (32 per CU), a grid-stride loop beyond
-        const unsigned bx = std::min((items_max + kResizeBlock - 1) / kResizeBlock, 8192u);
-        hipLaunchKernelGGL(resize_planes_kernel<T>, dim3(bx, (unsigned)n_planes), dim3(kResizeBlock), 0,
-                           (hipStream_t)stream, src, dst, args);
-        HIP_TRY(hipGetLastError());
-    }
-    return FIUNET_OK;
-}
-}  // extern "C++"
-
-int fiunet_resize_planes_u8(const uint8_t* src, const fiunet_resize_plane* src_planes, uint8_t* dst,
-                            const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream)
-{
-    return resize_planes(src, src_planes, dst, dst_planes, n_planes, n_frames, stream);
-}
-
-int fiunet_resize_planes_p10(const uint16_t* src, const fiunet_resize_plane* src_planes, uint16_t* dst,
-                             const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream)
-{
-    return resize_planes(src, src_planes, dst, dst_planes, n_planes, n_frames, stream);
 }
 
 // diagnostic (not part of the ABI, no declaration in include/fiunet.h): override choose_conv_cfg for one conv (1..17) of
@@ -2986,310 +1566,6 @@ int fiunet_debug_read_activation(fiunet_ctx* ctx, const void* workspace, int B, 
                            (hipStream_t)stream, (const float*)src, dst, B, C, h, w);
     HIP_TRY(hipGetLastError());
     return FIUNET_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Farneback flow and flow-compensated warps (flow.hip.h).  The level arithmetic is
-// optical_flow.py's: Python's round() is round-half-to-even, which rint() is in the default rounding mode (a
-// 130-wide frame has a 32-wide level 2, not 33).
-extern "C++" {
-namespace {
-constexpr int kFlowLevels = 3, kFlowMinSize = 32, kFlowIters = 3;
-constexpr size_t kFlowMaxBatch = 4096, kFlowMaxSide = 32768;
-
-struct FlowLevel { int h, w, ksize; double sigma; };
-
-// -> number of pyramid levels above level 0 (0..3); lv[k] for k = 0..levels
-int flow_levels(int H, int W, FlowLevel lv[kFlowLevels + 1])
-{
-    int levels = 0;
-    double scale = 1.0;
-    while (levels < kFlowLevels) {
-        scale *= 0.5;
-        if (W * scale < kFlowMinSize || H * scale < kFlowMinSize) break;
-        ++levels;
-    }
-    for (int k = 0; k <= levels; ++k) {
-        const double sc = std::ldexp(1.0, -k);
-        lv[k].sigma = (1.0 / sc - 1.0) * 0.5;
-        lv[k].ksize = std::max((int)std::rint(lv[k].sigma * 5) | 1, 3);
-        lv[k].w = (int)std::rint(W * sc);
-        lv[k].h = (int)std::rint(H * sc);
-    }
-    return levels;
-}
-
-// cv2.getGaussianKernel as optical_flow._gauss_kernel_cv states it (ksize 3 with sigma <= 0: the fixed kernel)
-FlowBlurTaps flow_blur_taps(int ksize, double sigma, int H, int W)
-{
-    FlowBlurTaps t = {};
-    t.r = ksize / 2;
-    t.reflect = std::min(H, W) > t.r ? 1 : 0;
-    if (sigma <= 0 && ksize == 3) {
-        t.k[0] = 0.25f; t.k[1] = 0.5f; t.k[2] = 0.25f;
-        return t;
-    }
-    if (sigma <= 0) sigma = 0.3 * ((ksize - 1) * 0.5 - 1) + 0.8;
-    double v[2 * FLOW_BLUR_MAXR + 1], sum = 0;
-    for (int i = 0; i < ksize; ++i) {
-        const double x = i - (ksize - 1) * 0.5;
-        v[i] = std::exp(-(x * x) / (2.0 * sigma * sigma));
-        sum += v[i];
-    }
-    for (int i = 0; i < ksize; ++i) t.k[i] = (float)(v[i] / sum);
-    return t;
-}
-
-// FarnebackPrepareGaussian (optical_flow._poly_exp_setup): g, x g, x^2 g in fp32 and four entries of the inverse of
-// the 6x6 Gram matrix of {1, x, y, x^2, y^2, xy} under g(x) g(y), all made in fp64
-FlowPolyTaps flow_poly_taps()
-{
-    constexpr int N = FLOW_POLY_N, K = 2 * N + 1;
-    const double sigma = 1.1;
-    double g[K], sum = 0;
-    for (int i = 0; i < K; ++i) {
-        const double x = i - N;
-        g[i] = std::exp(-(x * x) / (2.0 * sigma * sigma));
-        sum += g[i];
-    }
-    FlowPolyTaps t = {};
-    for (int i = 0; i < K; ++i) {
-        const double x = i - N;
-        g[i] /= sum;
-        t.g[i] = (float)g[i];
-        t.xg[i] = (float)(x * g[i]);
-        t.xxg[i] = (float)(x * x * g[i]);
-    }
-    double G[6][12] = {};
-    for (int iy = 0; iy < K; ++iy)
-        for (int ix = 0; ix < K; ++ix) {
-            const double x = ix - N, y = iy - N, wgt = g[iy] * g[ix];
-            const double basis[6] = {1.0, x, y, x * x, y * y, x * y};
-            for (int a = 0; a < 6; ++a)
-                for (int b = 0; b < 6; ++b) G[a][b] += wgt * basis[a] * basis[b];
-        }
-    for (int a = 0; a < 6; ++a) G[a][6 + a] = 1.0;
-    for (int c = 0; c < 6; ++c) {   // Gauss-Jordan with partial pivoting
-        int piv = c;
-        for (int r = c + 1; r < 6; ++r)
-            if (std::fabs(G[r][c]) > std::fabs(G[piv][c])) piv = r;
-        for (int j = 0; j < 12; ++j) std::swap(G[c][j], G[piv][j]);
-        const double d = G[c][c];
-        for (int j = 0; j < 12; ++j) G[c][j] /= d;
-        for (int r = 0; r < 6; ++r) {
-            if (r == c) continue;
-            const double f = G[r][c];
-            for (int j = 0; j < 12; ++j) G[r][j] -= f * G[c][j];
-        }
-    }
-    t.ig11 = (float)G[1][6 + 1];
-    t.ig03 = (float)G[0][6 + 3];
-    t.ig33 = (float)G[3][6 + 3];
-    t.ig55 = (float)G[5][6 + 5];
-    return t;
-}
-
-inline dim3 flow_tiles(int h, int w, int B) { return dim3((w + FLOW_TX - 1) / FLOW_TX, (h + FLOW_TY - 1) / FLOW_TY, B); }
-inline dim3 flow_rows(int h, int w, int z) { return dim3((w + 63) / 64, (h + 3) / 4, z); }
-
-int flow_check_frames(int bits, int B, int H, int W, size_t image_stride, size_t row_pitch, const void* a, const void* b)
-{
-    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
-    if (B < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_INVALID_ARG, "bad frame shape");
-    if ((size_t)B > kFlowMaxBatch || (size_t)H > kFlowMaxSide || (size_t)W > kFlowMaxSide)
-        return fail(FIUNET_ERR_INVALID_ARG, "flow: more than 4096 pairs per call or a side above 32768");
-    if (row_pitch < (size_t)W) return fail(FIUNET_ERR_INVALID_ARG, "frame layout: row_pitch < W");
-    const size_t limit = (size_t)1 << 40;
-    if (row_pitch > limit || image_stride > limit) return fail(FIUNET_ERR_INVALID_ARG, "frame layout: a value above 2^40 samples");
-    if (B > 1 && image_stride < (size_t)(H - 1) * row_pitch + W)
-        return fail(FIUNET_ERR_INVALID_ARG, "frame layout: image_stride smaller than one frame");
-    if (bits == 10 && ((((uintptr_t)a | (uintptr_t)b) & 1) != 0))
-        return fail(FIUNET_ERR_INVALID_ARG, "10-bit frames are 16-bit words: odd address");
-    return FIUNET_OK;
-}
-
-int flow_launch_blur(const void* src, int bits, size_t image_stride, size_t row_pitch, int B, int H, int W,
-                     const FlowBlurTaps& taps, float* dst, hipStream_t s)
-{
-    if (bits == 10)
-        hipLaunchKernelGGL(flow_blur_kernel<uint16_t>, flow_tiles(H, W, B), dim3(256), 0, s, (const uint16_t*)src,
-                           image_stride, row_pitch, H, W, taps, dst);
-    else
-        hipLaunchKernelGGL(flow_blur_kernel<uint8_t>, flow_tiles(H, W, B), dim3(256), 0, s, (const uint8_t*)src,
-                           image_stride, row_pitch, H, W, taps, dst);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int flow_launch_resize(const float* src, int hs, int ws, float* dst, int hd, int wd, int B, int C, float m0, float m1,
-                       hipStream_t s)
-{
-    hipLaunchKernelGGL(flow_resize_kernel, flow_rows(hd, wd, B * C), dim3(256), 0, s, src, hs, ws, dst, hd, wd, C, m0, m1);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int flow_launch_polyexp(const float* img, int h, int w, int B, const FlowPolyTaps& tp, float* R, hipStream_t s)
-{
-    hipLaunchKernelGGL(flow_polyexp_kernel, flow_tiles(h, w, B), dim3(256), 0, s, img, h, w, tp, R);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int flow_launch_matrices(const float* R0, const float* R1, const float* flow, int h, int w, int B, float* M, hipStream_t s)
-{
-    hipLaunchKernelGGL(flow_update_matrices_kernel, flow_rows(h, w, B), dim3(256), 0, s, R0, R1, flow, h, w, M);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-int flow_launch_boxsolve(const float* M, int h, int w, int B, float* out, bool interleaved, hipStream_t s)
-{
-    const size_t hw = (size_t)h * w;
-    hipLaunchKernelGGL(flow_boxsolve_kernel, flow_tiles(h, w, B), dim3(256), 0, s, M, h, w, out, 2 * hw,
-                       interleaved ? (size_t)1 : hw, interleaved ? (size_t)2 : (size_t)1);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-size_t fiunet_flow_workspace_bytes(int B, int H, int W)
-{
-    if (B < 1 || H < 1 || W < 1 || (size_t)B > kFlowMaxBatch || (size_t)H > kFlowMaxSide || (size_t)W > kFlowMaxSide) {
-        g_err = "fiunet_flow_workspace_bytes: bad arguments";
-        return 0;
-    }
-    // blurred frame, level image, R0, R1, M (5 channels each), two flow fields (2 channels each)
-    const size_t plane = align256((size_t)B * H * W * 4);
-    return (2 + 3 * 5 + 2 * 2) * plane;
-}
-
-int fiunet_farneback_flow(const void* prev, const void* next, int bits, int B, int H, int W, size_t image_stride,
-                          size_t row_pitch, float* flow_out, void* workspace, size_t workspace_bytes, void* stream)
-{
-    if (!prev || !next || !flow_out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (int rc = flow_check_frames(bits, B, H, W, image_stride, row_pitch, prev, next)) return rc;
-    if (workspace_bytes < fiunet_flow_workspace_bytes(B, H, W)) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    if ((uintptr_t)flow_out & 7) return fail(FIUNET_ERR_INVALID_ARG, "flow_out not 8-B aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t plane = align256((size_t)B * H * W * 4);
-    char* base = (char*)workspace;
-    float* blur = (float*)base;
-    float* img = (float*)(base + plane);
-    float* R[2] = {(float*)(base + 2 * plane), (float*)(base + 7 * plane)};
-    float* M = (float*)(base + 12 * plane);
-    float* fl[2] = {(float*)(base + 17 * plane), (float*)(base + 19 * plane)};
-    FlowLevel lv[kFlowLevels + 1];
-    const int levels = flow_levels(H, W, lv);
-    const FlowPolyTaps tp = flow_poly_taps();
-    const void* frames[2] = {prev, next};
-    int cur = 0;   // fl[cur] holds the flow of the level being refined
-    for (int k = levels; k >= 0; --k) {
-        const int h = lv[k].h, w = lv[k].w;
-        if (k == levels) {
-            if (int rc = zero_fill_async(fl[cur], (size_t)B * 2 * h * w * 4, s)) return rc;
-        } else {
-            if (int rc = flow_launch_resize(fl[cur], lv[k + 1].h, lv[k + 1].w, fl[cur ^ 1], h, w, B, 2, 2.0f, 2.0f, s)) return rc;
-            cur ^= 1;
-        }
-        const FlowBlurTaps taps = flow_blur_taps(lv[k].ksize, lv[k].sigma, H, W);
-        for (int f = 0; f < 2; ++f) {
-            if (int rc = flow_launch_blur(frames[f], bits, image_stride, row_pitch, B, H, W, taps, blur, s)) return rc;
-            if (int rc = flow_launch_resize(blur, H, W, img, h, w, B, 1, 1.0f, 1.0f, s)) return rc;
-            if (int rc = flow_launch_polyexp(img, h, w, B, tp, R[f], s)) return rc;
-        }
-        if (int rc = flow_launch_matrices(R[0], R[1], fl[cur], h, w, B, M, s)) return rc;
-        for (int i = 0; i < kFlowIters; ++i) {
-            const bool last = k == 0 && i == kFlowIters - 1;
-            float* dst = last ? flow_out : fl[cur ^ 1];
-            if (int rc = flow_launch_boxsolve(M, h, w, B, dst, last, s)) return rc;
-            if (last) break;
-            cur ^= 1;
-            if (i < kFlowIters - 1)
-                if (int rc = flow_launch_matrices(R[0], R[1], fl[cur], h, w, B, M, s)) return rc;
-        }
-    }
-    return FIUNET_OK;
-}
-
-int fiunet_flow_warp(const void* frame0, const void* frame1, const float* flow, int mode, int bits, int B, int H, int W,
-                     size_t image_stride, size_t row_pitch, int flow_h, int flow_w, void* out, size_t out_image_stride,
-                     size_t out_row_pitch, void* stream)
-{
-    if (!frame0 || !frame1 || !flow || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (mode != FLOW_MODE_REFERENCE && mode != FLOW_MODE_MOTION)
-        return fail(FIUNET_ERR_INVALID_ARG, "mode must be FIUNET_FLOW_REFERENCE or FIUNET_FLOW_MOTION");
-    if (int rc = flow_check_frames(bits, B, H, W, image_stride, row_pitch, frame0, frame1)) return rc;
-    if (int rc = flow_check_frames(bits, B, H, W, out_image_stride, out_row_pitch, out, out)) return rc;
-    if (flow_h < 1 || flow_w < 1 || (size_t)flow_h > kFlowMaxSide || (size_t)flow_w > kFlowMaxSide)
-        return fail(FIUNET_ERR_INVALID_ARG, "bad flow shape");
-    if ((uintptr_t)flow & 7) return fail(FIUNET_ERR_INVALID_ARG, "flow not 8-B aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const float mx = (float)((double)W / (double)flow_w), my = (float)((double)H / (double)flow_h);
-    if (bits == 10)
-        hipLaunchKernelGGL(flow_warp_kernel<uint16_t>, flow_rows(H, W, B), dim3(256), 0, s, (const uint16_t*)frame0,
-                           (const uint16_t*)frame1, image_stride, row_pitch, flow, flow_h, flow_w, mode, H, W, mx, my,
-                           (uint16_t*)out, out_image_stride, out_row_pitch);
-    else
-        hipLaunchKernelGGL(flow_warp_kernel<uint8_t>, flow_rows(H, W, B), dim3(256), 0, s, (const uint8_t*)frame0,
-                           (const uint8_t*)frame1, image_stride, row_pitch, flow, flow_h, flow_w, mode, H, W, mx, my,
-                           (uint8_t*)out, out_image_stride, out_row_pitch);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-// Diagnostic (tests; not part of the ABI): the pyramid of an H x W frame, pure host arithmetic.  dims[k] = {h, w,
-// ksize}, sigma[k] for k = 0..*levels.
-int fiunet_debug_flow_plan(int H, int W, int* levels, int dims[12], double sigma[4])
-{
-    if (H < 1 || W < 1 || !levels || !dims || !sigma) return fail(FIUNET_ERR_INVALID_ARG, "bad arguments");
-    FlowLevel lv[kFlowLevels + 1];
-    *levels = flow_levels(H, W, lv);
-    for (int k = 0; k <= *levels; ++k) {
-        dims[3 * k] = lv[k].h; dims[3 * k + 1] = lv[k].w; dims[3 * k + 2] = lv[k].ksize;
-        sigma[k] = lv[k].sigma;
-    }
-    return FIUNET_OK;
-}
-
-// Diagnostic (tests; not part of the ABI): one stage of fiunet_farneback_flow on the caller's buffers, B pairs.
-//   1 pyramid level `level` of B frames (in0: samples of `bits` with image_stride / row_pitch, H x W; scratch: fp32
-//     [B, H, W]; out: fp32 [B, h, w], h x w the level's size)       2 polynomial expansion (in0 [B, h, w] -> [B, 5, h, w])
-//   3 update matrices (in0 R0, in1 R1 [B, 5, h, w], in2 flow [B, 2, h, w] -> [B, 5, h, w])
-//   4 box mean and solve (in0 [B, 5, h, w] -> flow [B, 2, h, w])    5 flow resize (in0 [B, 2, H, W] -> [B, 2, h, w] times
-//     (mul0, mul1))
-int fiunet_debug_flow_stage(int stage, const void* in0, const void* in1, const void* in2, void* out, void* scratch,
-                            int bits, int level, int B, int H, int W, int h, int w, size_t image_stride,
-                            size_t row_pitch, float mul0, float mul1, void* stream)
-{
-    if (!in0 || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (B < 1 || (size_t)B > kFlowMaxBatch || h < 1 || w < 1 || (size_t)h > kFlowMaxSide || (size_t)w > kFlowMaxSide)
-        return fail(FIUNET_ERR_INVALID_ARG, "bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    switch (stage) {
-    case 1: {
-        if (!scratch) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-        if (int rc = flow_check_frames(bits, B, H, W, image_stride, row_pitch, in0, in0)) return rc;
-        FlowLevel lv[kFlowLevels + 1];
-        const int levels = flow_levels(H, W, lv);
-        if (level < 0 || level > levels || lv[level].h != h || lv[level].w != w)
-            return fail(FIUNET_ERR_INVALID_ARG, "not a level of this frame size");
-        const FlowBlurTaps taps = flow_blur_taps(lv[level].ksize, lv[level].sigma, H, W);
-        if (int rc = flow_launch_blur(in0, bits, image_stride, row_pitch, B, H, W, taps, (float*)scratch, s)) return rc;
-        return flow_launch_resize((const float*)scratch, H, W, (float*)out, h, w, B, 1, 1.0f, 1.0f, s);
-    }
-    case 2: return flow_launch_polyexp((const float*)in0, h, w, B, flow_poly_taps(), (float*)out, s);
-    case 3:
-        if (!in1 || !in2) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-        return flow_launch_matrices((const float*)in0, (const float*)in1, (const float*)in2, h, w, B, (float*)out, s);
-    case 4: return flow_launch_boxsolve((const float*)in0, h, w, B, (float*)out, false, s);
-    case 5:
-        if (H < 1 || W < 1 || (size_t)H > kFlowMaxSide || (size_t)W > kFlowMaxSide) return fail(FIUNET_ERR_INVALID_ARG, "bad shape");
-        return flow_launch_resize((const float*)in0, H, W, (float*)out, h, w, B, 2, mul0, mul1, s);
-    }
-    return fail(FIUNET_ERR_INVALID_ARG, "stage must be 1..5");
 }
 
 }  // extern "C"

@@ -1,0 +1,631 @@
+// formats.hip -- the frame formats that go through the RGB network as staged planar RGB: packed I420
+// at 8 and 10 bits, NV12 / P010 surfaces, YUV 4:2:2 / 4:4:4 and packed RGB - their conversions (colour.hip.h, yuv4xx.hip.h,
+// packed.hip.h) and the fiunet_forward_<format> entry points around fiunet_forward_u8_strided / fiunet_forward_p10.
+#include "fiunet_internal.h"
+#include "colour.hip.h"
+#include "packed.hip.h"
+#include "yuv4xx.hip.h"
+
+using namespace fiunet;
+
+namespace {
+
+// One of a format conversion's two instantiations on blocks of kColourBlock threads: the one with vector accesses where
+// `vec` says that every base, pitch and stride allows them, the scalar one otherwise.
+template <auto VecKernel, auto ScalarKernel, typename... Args>
+int launch_vec(bool vec, dim3 grid, void* stream, Args... args)
+{
+    if (vec) hipLaunchKernelGGL(VecKernel, grid, dim3(kColourBlock), 0, (hipStream_t)stream, args...);
+    else hipLaunchKernelGGL(ScalarKernel, grid, dim3(kColourBlock), 0, (hipStream_t)stream, args...);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- colour video (csrc/colour.hip.h): packed I420 <-> planar RGB, and the RGB network's forward between them ----
+static inline size_t i420_frame_bytes(int H, int W)   // (samples per frame, at either depth)
+{
+    return (size_t)H * W + 2 * (size_t)((H + 1) / 2) * ((W + 1) / 2);
+}
+
+// `colour` at an entry point of `bits` bits: FIUNET_YUV_BT2020 is a 10-bit flag, and excludes FIUNET_YUV_BT709
+static int check_colour_flags(unsigned colour, int bits)
+{
+    if (colour & ~(bits == 10 ? kColourFlagsP10 : kColourFlags))
+        return fail(FIUNET_ERR_INVALID_ARG, "colour: unknown flag bits (FIUNET_YUV_BT2020 needs the 10-bit entry points)");
+    if ((colour & FIUNET_YUV_BT709) && (colour & FIUNET_YUV_BT2020))
+        return fail(FIUNET_ERR_INVALID_ARG, "colour: FIUNET_YUV_BT709 and FIUNET_YUV_BT2020 together");
+    return FIUNET_OK;
+}
+
+static int check_colour_args(const void* in, const void* out, int B, int H, int W, unsigned colour, int bits)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = check_colour_flags(colour, bits)) return rc;
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    return FIUNET_OK;
+}
+
+// the conversions' grid: a thread per four columns, `rows` rows (a chroma row covers two luma rows), B frames
+static dim3 colour_grid(int W, int rows, int B)
+{
+    return dim3((unsigned)(((W + 3) / 4 + kColourBlock - 1) / kColourBlock), (unsigned)rows, (unsigned)B);
+}
+
+extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
+// the caller's frame stride (0 = tight) -> the resolved one, refused where a frame does not fit; `which`: "in" / "out"
+static int resolve_i420_stride(size_t* frame_stride, int H, int W, const char* which)
+{
+    const size_t fs = i420_frame_bytes(H, W);
+    if (*frame_stride == 0) *frame_stride = fs;
+    if (*frame_stride < fs) return fail(FIUNET_ERR_INVALID_ARG, std::string(which) + "_frame_stride smaller than one frame");
+    return FIUNET_OK;
+}
+
+// one 4-sample access per luma quad and per chroma pair: W, the stride and both bases a multiple of 4 samples
+template <typename T>
+static bool i420_vec(int W, size_t frame_stride, const void* a, const void* b)
+{
+    return W % 4 == 0 && frame_stride % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
+}
+
+template <typename T>
+static int yuv420_to_rgb(const T* in, size_t in_frame_stride, T* out, int B, int H, int W, unsigned colour, int bits,
+                         void* stream)
+{
+    int rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
+    if ((rc = resolve_i420_stride(&in_frame_stride, H, W, "in"))) return rc;
+    return launch_vec<&yuv420_to_rgb_kernel<T, true>, &yuv420_to_rgb_kernel<T, false>>(
+        i420_vec<T>(W, in_frame_stride, in, out), colour_grid(W, H, B), stream, in, in_frame_stride, out, H, W,
+        colour_coef(colour, bits));
+}
+
+template <typename T>
+static int rgb_to_yuv420(const T* in, T* out, size_t out_frame_stride, int B, int H, int W, unsigned colour, int bits,
+                         void* stream)
+{
+    int rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
+    if ((rc = resolve_i420_stride(&out_frame_stride, H, W, "out"))) return rc;
+    return launch_vec<&rgb_to_yuv420_kernel<T, true>, &rgb_to_yuv420_kernel<T, false>>(
+        i420_vec<T>(W, out_frame_stride, in, out), colour_grid(W, (H + 1) / 2, B), stream, in, out, out_frame_stride, H, W,
+        colour_coef(colour, bits));
+}
+}  // extern "C++"
+
+int fiunet_yuv420_to_rgb_u8(const uint8_t* in, size_t in_frame_stride, uint8_t* out, int B, int H, int W,
+                            unsigned colour, void* stream)
+{
+    return yuv420_to_rgb<uint8_t>(in, in_frame_stride, out, B, H, W, colour, 8, stream);
+}
+
+int fiunet_rgb_to_yuv420_u8(const uint8_t* in, uint8_t* out, size_t out_frame_stride, int B, int H, int W,
+                            unsigned colour, void* stream)
+{
+    return rgb_to_yuv420<uint8_t>(in, out, out_frame_stride, B, H, W, colour, 8, stream);
+}
+
+int fiunet_yuv420p10_to_rgb_p10(const uint16_t* in, size_t in_frame_stride, uint16_t* out, int B, int H, int W,
+                                unsigned colour, void* stream)
+{
+    return yuv420_to_rgb<uint16_t>(in, in_frame_stride, out, B, H, W, colour, 10, stream);
+}
+
+int fiunet_rgb_p10_to_yuv420p10(const uint16_t* in, uint16_t* out, size_t out_frame_stride, int B, int H, int W,
+                                unsigned colour, void* stream)
+{
+    return rgb_to_yuv420<uint16_t>(in, out, out_frame_stride, B, H, W, colour, 10, stream);
+}
+
+// ---- the staged-RGB forward: how a frame format goes through the RGB network.  Every
+//      fiunet_forward_<format> below is this chain with its own conversion pair; nothing else differs between them.
+// [the inner forward's workspace | frame1 RGB | frame2 RGB | output RGB]: planar [B, 3, H, W] batches of `sample`-byte
+// samples behind the workspace of fiunet_forward_u8 (1 byte) / fiunet_forward_p10 (2), every part rounded up to 256 B.
+struct StagedWorkspace {
+    size_t inner, rgb, total;   // total 0: bad arguments (the inner query has said which)
+};
+
+static StagedWorkspace staged_workspace(const fiunet_ctx* ctx, int B, int H, int W, int precision, size_t sample)
+{
+    const size_t inner = sample == 1 ? fiunet_workspace_bytes_u8(ctx, B, H, W, precision)
+                                     : fiunet_workspace_bytes_p10(ctx, B, H, W, precision);
+    if (inner == 0) return {0, 0, 0};
+    const size_t base = align256(inner), rgb = align256((size_t)B * 3 * H * W * sample);
+    return {base, rgb, base + 3 * rgb};
+}
+
+extern "C++" {
+// T: uint8_t (through fiunet_forward_u8_strided) or uint16_t (through fiunet_forward_p10).  What a format supplies:
+//   check()           host only: its format code, colour flags and both layouts (anything its conversions would refuse);
+//   to_rgb(in, rgb)   its frames -> a planar RGB batch;
+//   from_rgb(rgb)     a planar RGB batch -> `out` in its format.
+// Every refusal comes before the first launch.  `name`: the entry point, for the wrong-network message.
+template <typename T, typename Check, typename ToRgb, typename FromRgb>
+static int forward_staged(const char* name, fiunet_ctx* ctx, const T* frame1, const T* frame2, const T* out, int B,
+                          int H, int W, int precision, void* workspace, size_t workspace_bytes, void* stream,
+                          Check check, ToRgb to_rgb, FromRgb from_rgb)
+{
+    if (!frame1 || !frame2 || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (H < 16 || W < 16) return fail(FIUNET_ERR_BAD_SHAPE, "H and W must be >= 16 (four 2x2 max-pools)");
+    int rc;
+    if ((rc = check())) return rc;
+    if (!ctx) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->cf != 3)
+        return fail(FIUNET_ERR_UNSUPPORTED, std::string(name) + " needs the RGB network (frame_channels 3)");
+    if (!ctx->loaded) return fail(FIUNET_ERR_NOT_LOADED, "fiunet_forward before fiunet_load_weights");
+    const StagedWorkspace ws = staged_workspace(ctx, B, H, W, precision, sizeof(T));
+    if (ws.total == 0) return fail(FIUNET_ERR_INVALID_ARG, "bad precision or shape");
+    if (workspace_bytes < ws.total) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    T* a = (T*)((char*)workspace + ws.inner);
+    T* b = (T*)((char*)a + ws.rgb);
+    T* o = (T*)((char*)b + ws.rgb);
+    if ((rc = to_rgb(frame1, a)) || (rc = to_rgb(frame2, b))) return rc;
+    if constexpr (sizeof(T) == 1)
+        rc = fiunet_forward_u8_strided(ctx, a, b, o, 0, B, H, W, precision, workspace, ws.inner, stream);
+    else
+        rc = fiunet_forward_p10(ctx, a, b, o, 0, B, H, W, precision, workspace, ws.inner, stream);
+    return rc ? rc : from_rgb(o);
+}
+
+template <typename T>
+static int forward_yuv420(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2, T* out,
+                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision, void* workspace,
+                          size_t workspace_bytes, void* stream)
+{
+    return forward_staged<T>(
+        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
+        [&] {
+            const int rc = check_colour_flags(colour, bits);
+            return rc ? rc : resolve_i420_stride(&out_frame_stride, H, W, "out");
+        },
+        [&](const T* in, T* rgb) { return yuv420_to_rgb<T>(in, 0, rgb, B, H, W, colour, bits, stream); },
+        [&](const T* rgb) { return rgb_to_yuv420<T>(rgb, out, out_frame_stride, B, H, W, colour, bits, stream); });
+}
+}  // extern "C++"
+
+size_t fiunet_workspace_bytes_yuv420(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return staged_workspace(ctx, B, H, W, precision, 1).total;
+}
+
+size_t fiunet_workspace_bytes_yuv420p10(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return staged_workspace(ctx, B, H, W, precision, 2).total;
+}
+
+int fiunet_forward_yuv420(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, uint8_t* out,
+                          size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
+                          void* workspace, size_t workspace_bytes, void* stream)
+{
+    return forward_yuv420<uint8_t>("fiunet_forward_yuv420", 8, ctx, frame1, frame2, out, out_frame_stride, B, H, W, colour,
+                                   precision, workspace, workspace_bytes, stream);
+}
+
+int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, uint16_t* out,
+                             size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision,
+                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    return forward_yuv420<uint16_t>("fiunet_forward_yuv420p10", 10, ctx, frame1, frame2, out, out_frame_stride, B, H, W,
+                                    colour, precision, workspace, workspace_bytes, stream);
+}
+
+// ---- NV12 / P010 decoder surfaces: the colour conversions on semi-planar, pitched frames ----
+// The caller's layout (NULL or zero fields = tight) -> the resolved one, refused before any launch where it cannot
+// hold an H x W frame.  Every quantity in samples.
+static int resolve_surface(const fiunet_surface_layout* l, int H, int W, ColourSurface* sf)
+{
+    const size_t Hc = (size_t)(H + 1) / 2, Wc = (size_t)(W + 1) / 2;
+    sf->luma_pitch = l && l->luma_pitch ? l->luma_pitch : (size_t)W;
+    sf->chroma_offset = l && l->chroma_offset ? l->chroma_offset : (size_t)H * W;
+    sf->chroma_pitch = l && l->chroma_pitch ? l->chroma_pitch : 2 * Wc;
+    sf->frame_stride = l && l->frame_stride ? l->frame_stride : i420_frame_bytes(H, W);
+    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
+    if (sf->luma_pitch > big || sf->chroma_pitch > big || sf->chroma_offset > big || sf->frame_stride > big)
+        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: a value above 2^40 samples");
+    if (sf->luma_pitch < (size_t)W) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: luma_pitch < W");
+    if (sf->chroma_pitch < 2 * Wc) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_pitch < 2*ceil(W/2)");
+    if (sf->chroma_offset < (size_t)(H - 1) * sf->luma_pitch + W)
+        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_offset inside the luma plane");
+    if (sf->frame_stride < sf->chroma_offset + (Hc - 1) * sf->chroma_pitch + 2 * Wc)
+        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: frame_stride does not cover the chroma plane");
+    return FIUNET_OK;
+}
+
+extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
+// one 4-sample access per luma quad and per pair of owned chroma pairs: everything a multiple of 4 samples
+template <typename T>
+static bool surface_vec(const ColourSurface& sf, int W, const void* a, const void* b)
+{
+    return W % 4 == 0 && (sf.luma_pitch | sf.chroma_offset | sf.chroma_pitch | sf.frame_stride) % 4 == 0 &&
+           (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
+}
+
+template <typename T>
+static int surface_to_rgb(const T* in, const fiunet_surface_layout* layout, T* out, int B, int H, int W,
+                          unsigned colour, int bits, void* stream)
+{
+    int rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
+    ColourSurface sf;
+    if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
+    return launch_vec<&nv12_to_rgb_kernel<T, true>, &nv12_to_rgb_kernel<T, false>>(
+        surface_vec<T>(sf, W, in, out), colour_grid(W, H, B), stream, in, sf, out, H, W, colour_coef(colour, bits));
+}
+
+template <typename T>
+static int rgb_to_surface(const T* in, T* out, const fiunet_surface_layout* layout, int B, int H, int W,
+                          unsigned colour, int bits, void* stream)
+{
+    int rc;
+    if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
+    ColourSurface sf;
+    if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
+    return launch_vec<&rgb_to_nv12_kernel<T, true>, &rgb_to_nv12_kernel<T, false>>(
+        surface_vec<T>(sf, W, in, out), colour_grid(W, (H + 1) / 2, B), stream, in, out, sf, H, W,
+        colour_coef(colour, bits));
+}
+
+template <typename T>
+static int forward_surface(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2,
+                           const fiunet_surface_layout* in_layout, T* out, const fiunet_surface_layout* out_layout, int B,
+                           int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                           void* stream)
+{
+    return forward_staged<T>(
+        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
+        [&] {
+            ColourSurface sf;
+            int rc = check_colour_flags(colour, bits);
+            if (!rc && !(rc = resolve_surface(in_layout, H, W, &sf))) rc = resolve_surface(out_layout, H, W, &sf);
+            return rc;
+        },
+        [&](const T* in, T* rgb) { return surface_to_rgb<T>(in, in_layout, rgb, B, H, W, colour, bits, stream); },
+        [&](const T* rgb) { return rgb_to_surface<T>(rgb, out, out_layout, B, H, W, colour, bits, stream); });
+}
+}  // extern "C++"
+
+int fiunet_nv12_to_rgb_u8(const uint8_t* in, const fiunet_surface_layout* in_layout, uint8_t* out, int B, int H, int W,
+                          unsigned colour, void* stream)
+{
+    return surface_to_rgb<uint8_t>(in, in_layout, out, B, H, W, colour, 8, stream);
+}
+
+int fiunet_rgb_to_nv12_u8(const uint8_t* in, uint8_t* out, const fiunet_surface_layout* out_layout, int B, int H, int W,
+                          unsigned colour, void* stream)
+{
+    return rgb_to_surface<uint8_t>(in, out, out_layout, B, H, W, colour, 8, stream);
+}
+
+int fiunet_p010_to_rgb_p10(const uint16_t* in, const fiunet_surface_layout* in_layout, uint16_t* out, int B, int H,
+                           int W, unsigned colour, void* stream)
+{
+    return surface_to_rgb<uint16_t>(in, in_layout, out, B, H, W, colour, 10, stream);
+}
+
+int fiunet_rgb_p10_to_p010(const uint16_t* in, uint16_t* out, const fiunet_surface_layout* out_layout, int B, int H,
+                           int W, unsigned colour, void* stream)
+{
+    return rgb_to_surface<uint16_t>(in, out, out_layout, B, H, W, colour, 10, stream);
+}
+
+size_t fiunet_workspace_bytes_nv12(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return staged_workspace(ctx, B, H, W, precision, 1).total;
+}
+
+size_t fiunet_workspace_bytes_p010(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return staged_workspace(ctx, B, H, W, precision, 2).total;
+}
+
+int fiunet_forward_nv12(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
+                        const fiunet_surface_layout* in_layout, uint8_t* out, const fiunet_surface_layout* out_layout,
+                        int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                        void* stream)
+{
+    return forward_surface<uint8_t>("fiunet_forward_nv12", 8, ctx, frame1, frame2, in_layout, out, out_layout, B, H, W,
+                                    colour, precision, workspace, workspace_bytes, stream);
+}
+
+int fiunet_forward_p010(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2,
+                        const fiunet_surface_layout* in_layout, uint16_t* out, const fiunet_surface_layout* out_layout,
+                        int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                        void* stream)
+{
+    return forward_surface<uint16_t>("fiunet_forward_p010", 10, ctx, frame1, frame2, in_layout, out, out_layout, B, H, W,
+                                     colour, precision, workspace, workspace_bytes, stream);
+}
+
+// ---- YUV 4:2:2 / 4:4:4 frames (csrc/yuv4xx.hip.h): planar and one-plane packed, <-> planar RGB ----
+// samples of one tight frame of `format` (bytes at 8 bits); 0: not a fiunet_yuv_format
+static size_t yuv_frame_samples(int format, int H, int W)
+{
+    switch (format) {
+    case FIUNET_YUV_422P: return (size_t)H * W + 2 * (size_t)H * ((W + 1) / 2);
+    case FIUNET_YUV_444P: return 3 * (size_t)H * W;
+    case FIUNET_YUV_UYVY422:
+    case FIUNET_YUV_YUYV422: return 2 * (size_t)H * W;
+    default: return 0;
+    }
+}
+
+// The caller's pitch and stride (0 = tight) -> the resolved layout, with every refusal that needs no pointer: before
+// any launch.  bits: the entry point's sample depth.
+static int resolve_yuv(int format, int bits, size_t row_pitch, size_t frame_stride, int B, int H, int W, unsigned colour,
+                       YuvLayout* lay)
+{
+    if (int rc = check_colour_flags(colour, bits)) return rc;
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    const size_t tight = yuv_frame_samples(format, H, W);
+    if (!tight) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_yuv_format");
+    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
+    if (row_pitch > big || frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: a value above 2^40");
+    if (yuv_is_packed(format)) {
+        if (bits != 8) return fail(FIUNET_ERR_INVALID_ARG, "format: uyvy422 / yuyv422 are 8-bit formats");
+        if (W & 1) return fail(FIUNET_ERR_INVALID_ARG, "uyvy422 / yuyv422 need an even width");
+        const size_t row = 2 * (size_t)W;
+        lay->row_pitch = row_pitch ? row_pitch : row;
+        if (lay->row_pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: row_pitch < 2*W");
+        lay->frame_stride = frame_stride ? frame_stride : (size_t)H * lay->row_pitch;
+        if (lay->frame_stride < (size_t)(H - 1) * lay->row_pitch + row)
+            return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: frame_stride does not cover the last row");
+        return FIUNET_OK;
+    }
+    if (row_pitch) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: planar frames are tight (row_pitch must be 0)");
+    lay->row_pitch = 0;
+    lay->frame_stride = frame_stride ? frame_stride : tight;
+    if (lay->frame_stride < tight) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: frame_stride smaller than one frame");
+    return FIUNET_OK;
+}
+
+extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
+// vector accesses: W and every pitch and stride a multiple of 4 samples, bases aligned to 4 samples
+template <typename T>
+static bool yuv_vec(const YuvLayout& lay, int W, const void* a, const void* b)
+{
+    return W % 4 == 0 && (lay.row_pitch | lay.frame_stride) % 4 == 0 &&
+           (((uintptr_t)a | (uintptr_t)b) & (4 * sizeof(T) - 1)) == 0;
+}
+
+template <int F>
+using YuvFormat = std::integral_constant<int, F>;
+
+// go(YuvFormat<F>{}) for the resolved `format` (the one-plane formats exist at 8 bits only: resolve_yuv has refused them
+// at 10, and their uint16 kernels are never instantiated)
+template <typename T, typename Go>
+static int for_yuv_format(int format, Go go)
+{
+    if (format == FIUNET_YUV_422P) return go(YuvFormat<FIUNET_YUV_422P>{});
+    if (format == FIUNET_YUV_444P) return go(YuvFormat<FIUNET_YUV_444P>{});
+    if constexpr (sizeof(T) == 1)
+        return format == FIUNET_YUV_UYVY422 ? go(YuvFormat<FIUNET_YUV_UYVY422>{}) : go(YuvFormat<FIUNET_YUV_YUYV422>{});
+    return FIUNET_OK;
+}
+
+template <typename T>
+static int yuv_to_rgb(const T* in, int format, size_t row_pitch, size_t frame_stride, T* out, int B, int H, int W,
+                      unsigned colour, int bits, void* stream)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    YuvLayout lay;
+    if (int rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay)) return rc;
+    return for_yuv_format<T>(format, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        return launch_vec<&yuv_to_rgb_kernel<T, F, true>, &yuv_to_rgb_kernel<T, F, false>>(
+            yuv_vec<T>(lay, W, in, out), colour_grid(W, H, B), stream, in, lay, out, H, W, colour_coef(colour, bits));
+    });
+}
+
+template <typename T>
+static int rgb_to_yuv(const T* in, T* out, int format, size_t row_pitch, size_t frame_stride, int B, int H, int W,
+                      unsigned colour, int bits, void* stream)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    YuvLayout lay;
+    if (int rc = resolve_yuv(format, bits, row_pitch, frame_stride, B, H, W, colour, &lay)) return rc;
+    return for_yuv_format<T>(format, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        return launch_vec<&rgb_to_yuv_kernel<T, F, true>, &rgb_to_yuv_kernel<T, F, false>>(
+            yuv_vec<T>(lay, W, in, out), colour_grid(W, H, B), stream, in, out, lay, H, W, colour_coef(colour, bits));
+    });
+}
+
+template <typename T>
+static int forward_yuv(const char* name, int bits, fiunet_ctx* ctx, const T* frame1, const T* frame2, int format,
+                       size_t in_row_pitch, size_t in_frame_stride, T* out, size_t out_row_pitch, size_t out_frame_stride,
+                       int B, int H, int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes,
+                       void* stream)
+{
+    return forward_staged<T>(
+        name, ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
+        [&] {
+            YuvLayout lay;
+            const int rc = resolve_yuv(format, bits, in_row_pitch, in_frame_stride, B, H, W, colour, &lay);
+            return rc ? rc : resolve_yuv(format, bits, out_row_pitch, out_frame_stride, B, H, W, colour, &lay);
+        },
+        [&](const T* in, T* rgb) {
+            return yuv_to_rgb<T>(in, format, in_row_pitch, in_frame_stride, rgb, B, H, W, colour, bits, stream);
+        },
+        [&](const T* rgb) {
+            return rgb_to_yuv<T>(rgb, out, format, out_row_pitch, out_frame_stride, B, H, W, colour, bits, stream);
+        });
+}
+}  // extern "C++"
+
+int fiunet_yuv_to_rgb_u8(const uint8_t* in, int format, size_t row_pitch, size_t frame_stride, uint8_t* out, int B,
+                         int H, int W, unsigned colour, void* stream)
+{
+    return yuv_to_rgb<uint8_t>(in, format, row_pitch, frame_stride, out, B, H, W, colour, 8, stream);
+}
+
+int fiunet_rgb_to_yuv_u8(const uint8_t* in, uint8_t* out, int format, size_t row_pitch, size_t frame_stride, int B,
+                         int H, int W, unsigned colour, void* stream)
+{
+    return rgb_to_yuv<uint8_t>(in, out, format, row_pitch, frame_stride, B, H, W, colour, 8, stream);
+}
+
+int fiunet_yuv_to_rgb_p10(const uint16_t* in, int format, size_t row_pitch, size_t frame_stride, uint16_t* out, int B,
+                          int H, int W, unsigned colour, void* stream)
+{
+    return yuv_to_rgb<uint16_t>(in, format, row_pitch, frame_stride, out, B, H, W, colour, 10, stream);
+}
+
+int fiunet_rgb_p10_to_yuv(const uint16_t* in, uint16_t* out, int format, size_t row_pitch, size_t frame_stride, int B,
+                          int H, int W, unsigned colour, void* stream)
+{
+    return rgb_to_yuv<uint16_t>(in, out, format, row_pitch, frame_stride, B, H, W, colour, 10, stream);
+}
+
+size_t fiunet_workspace_bytes_yuv(const fiunet_ctx* ctx, int B, int H, int W, int precision, int bits)
+{
+    if (bits == 8 || bits == 10) return staged_workspace(ctx, B, H, W, precision, bits == 8 ? 1 : 2).total;
+    last_error() = "fiunet_workspace_bytes_yuv: bits must be 8 or 10";
+    return 0;
+}
+
+int fiunet_forward_yuv(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2, int format, size_t in_row_pitch,
+                       size_t in_frame_stride, uint8_t* out, size_t out_row_pitch, size_t out_frame_stride, int B, int H,
+                       int W, unsigned colour, int precision, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return forward_yuv<uint8_t>("fiunet_forward_yuv", 8, ctx, frame1, frame2, format, in_row_pitch, in_frame_stride, out,
+                                out_row_pitch, out_frame_stride, B, H, W, colour, precision, workspace, workspace_bytes,
+                                stream);
+}
+
+int fiunet_forward_yuv_p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, int format,
+                           size_t in_row_pitch, size_t in_frame_stride, uint16_t* out, size_t out_row_pitch,
+                           size_t out_frame_stride, int B, int H, int W, unsigned colour, int precision, void* workspace,
+                           size_t workspace_bytes, void* stream)
+{
+    return forward_yuv<uint16_t>("fiunet_forward_yuv_p10", 10, ctx, frame1, frame2, format, in_row_pitch, in_frame_stride,
+                                 out, out_row_pitch, out_frame_stride, B, H, W, colour, precision, workspace,
+                                 workspace_bytes, stream);
+}
+
+// ---- packed RGB frames: rgb24 / bgr24 / rgba / bgra, rows a pitch apart, <-> planar RGB ----
+static int packed_bpp(int format)
+{
+    return format == FIUNET_PACKED_RGB24 || format == FIUNET_PACKED_BGR24 ? 3
+         : format == FIUNET_PACKED_RGBA || format == FIUNET_PACKED_BGRA ? 4 : 0;
+}
+
+// The caller's layout (NULL or zero fields = tight) -> the resolved one, refused before any launch where it cannot hold
+// an H x W frame of bpp bytes per pixel.  Every quantity in bytes.
+static int resolve_packed(const fiunet_packed_layout* l, int H, int W, int bpp, PackedLayout* pl)
+{
+    const size_t row = (size_t)W * bpp, big = (size_t)1 << 40;   // (keeps every product below in range)
+    pl->row_pitch = l && l->row_pitch ? l->row_pitch : row;
+    if (pl->row_pitch > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
+    pl->frame_stride = l && l->frame_stride ? l->frame_stride : (size_t)H * pl->row_pitch;
+    if (pl->frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
+    if (pl->row_pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: row_pitch < W*bpp");
+    if (pl->frame_stride < (size_t)(H - 1) * pl->row_pitch + row)
+        return fail(FIUNET_ERR_INVALID_ARG, "packed layout: frame_stride does not cover the last row");
+    return FIUNET_OK;
+}
+
+static int check_packed_args(const void* in, const void* out, int B, int H, int W, int format)
+{
+    if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (!packed_bpp(format)) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    return FIUNET_OK;
+}
+
+// dword and 16-byte packed accesses, uchar4 plane accesses: W and every pitch, stride and base a multiple of 4 bytes
+static bool packed_vec(int W, const PackedLayout& l, uintptr_t bases)
+{
+    return W % 4 == 0 && (l.row_pitch | l.frame_stride) % 4 == 0 && (bases & 3) == 0;
+}
+
+extern "C++" {
+template <int BPP, bool SWAP>
+struct PackedFormat {
+    static constexpr int bpp = BPP;
+    static constexpr bool swap = SWAP;
+};
+
+// go(PackedFormat<bpp, swap>{}) for a format that packed_bpp() knows
+template <typename Go>
+static int for_packed_format(int format, Go go)
+{
+    switch (format) {
+    case FIUNET_PACKED_RGB24: return go(PackedFormat<3, false>{});
+    case FIUNET_PACKED_BGR24: return go(PackedFormat<3, true>{});
+    case FIUNET_PACKED_RGBA: return go(PackedFormat<4, false>{});
+    default: return go(PackedFormat<4, true>{});
+    }
+}
+}  // extern "C++"
+
+int fiunet_packed_to_rgb_u8(const uint8_t* in, const fiunet_packed_layout* in_layout, uint8_t* out_rgb,
+                            uint8_t* alpha_out, int B, int H, int W, int format, void* stream)
+{
+    int rc;
+    if ((rc = check_packed_args(in, out_rgb, B, H, W, format))) return rc;
+    const int bpp = packed_bpp(format);
+    if (alpha_out && bpp != 4) return fail(FIUNET_ERR_INVALID_ARG, "alpha_out: the format has no alpha byte");
+    PackedLayout li;
+    if ((rc = resolve_packed(in_layout, H, W, bpp, &li))) return rc;
+    const bool vec = packed_vec(W, li, (uintptr_t)in | (uintptr_t)out_rgb | (uintptr_t)alpha_out);
+    return for_packed_format(format, [&](auto f) {
+        using F = decltype(f);
+        return launch_vec<&packed_to_rgb_kernel<F::bpp, F::swap, true>, &packed_to_rgb_kernel<F::bpp, F::swap, false>>(
+            vec, colour_grid(W, H, B), stream, in, li, out_rgb, alpha_out, H, W);
+    });
+}
+
+int fiunet_rgb_to_packed_u8(const uint8_t* in_rgb, uint8_t* out, const fiunet_packed_layout* out_layout,
+                            const uint8_t* alpha1, const uint8_t* alpha2, const fiunet_packed_layout* alpha_layout,
+                            int B, int H, int W, int format, void* stream)
+{
+    int rc;
+    if ((rc = check_packed_args(in_rgb, out, B, H, W, format))) return rc;
+    const int bpp = packed_bpp(format);
+    if ((alpha1 || alpha2) && bpp != 4) return fail(FIUNET_ERR_INVALID_ARG, "alpha source: the format has no alpha byte");
+    if (alpha2 && !alpha1) return fail(FIUNET_ERR_INVALID_ARG, "alpha2 without alpha1");
+    PackedLayout lo, la;
+    if ((rc = resolve_packed(out_layout, H, W, bpp, &lo))) return rc;
+    if ((rc = resolve_packed(alpha_layout, H, W, bpp, &la))) return rc;
+    const bool vec = packed_vec(W, lo, (uintptr_t)in_rgb | (uintptr_t)out | (uintptr_t)alpha1 | (uintptr_t)alpha2) &&
+                     (!alpha1 || packed_vec(W, la, 0));
+    return for_packed_format(format, [&](auto f) {
+        using F = decltype(f);
+        return launch_vec<&rgb_to_packed_kernel<F::bpp, F::swap, true>, &rgb_to_packed_kernel<F::bpp, F::swap, false>>(
+            vec, colour_grid(W, H, B), stream, in_rgb, out, lo, alpha1, alpha2, la, H, W);
+    });
+}
+
+size_t fiunet_workspace_bytes_rgb_packed(const fiunet_ctx* ctx, int B, int H, int W, int precision)
+{
+    return staged_workspace(ctx, B, H, W, precision, 1).total;
+}
+
+int fiunet_forward_rgb_packed(fiunet_ctx* ctx, const uint8_t* frame1, const uint8_t* frame2,
+                              const fiunet_packed_layout* in_layout, uint8_t* out, const fiunet_packed_layout* out_layout,
+                              int B, int H, int W, int format, int precision, void* workspace, size_t workspace_bytes,
+                              void* stream)
+{
+    const int bpp = packed_bpp(format);
+    const bool alpha = bpp == 4;   // the inserted frame's alpha: the rounded average of its neighbours'
+    return forward_staged<uint8_t>(
+        "fiunet_forward_rgb_packed", ctx, frame1, frame2, out, B, H, W, precision, workspace, workspace_bytes, stream,
+        [&] {
+            if (!bpp) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
+            PackedLayout pl;
+            const int rc = resolve_packed(in_layout, H, W, bpp, &pl);
+            return rc ? rc : resolve_packed(out_layout, H, W, bpp, &pl);
+        },
+        [&](const uint8_t* in, uint8_t* rgb) { return fiunet_packed_to_rgb_u8(in, in_layout, rgb, NULL, B, H, W, format, stream); },
+        [&](const uint8_t* rgb) {
+            return fiunet_rgb_to_packed_u8(rgb, out, out_layout, alpha ? frame1 : NULL, alpha ? frame2 : NULL, in_layout, B,
+                                           H, W, format, stream);
+        });
+}
+
+}  // extern "C"

@@ -1,0 +1,328 @@
+// metrics.hip -- PSNR and SSIM on the GPU (metrics.hip.h): the uint8 batch metrics, the plane / interleaved / stepped
+// metrics of hold-out scoring and the Gaussian SSIM of the training loss.
+#include "fiunet_internal.h"
+#include "metrics.hip.h"
+
+#include <cmath>
+
+using namespace fiunet;
+
+extern "C" {
+
+static inline int ssim_tiles(int H, int W, int* tiles_x)
+{
+    const int ow = W - 2 * SSIM_PAD, oh = H - 2 * SSIM_PAD;
+    const int tx = (ow + SSIM_TX - 1) / SSIM_TX, ty = (oh + SSIM_TY - 1) / SSIM_TY;
+    if (tiles_x) *tiles_x = tx;
+    return tx * ty;
+}
+
+size_t fiunet_metrics_workspace_bytes(int images, int H, int W)
+{
+    if (images < 1 || H < 1 || W < 1) {
+        last_error() = "fiunet_metrics_workspace_bytes: bad arguments";
+        return 0;
+    }
+    const size_t tiles = (H >= SSIM_WIN && W >= SSIM_WIN) ? (size_t)ssim_tiles(H, W, nullptr) : 0;
+    return align256((size_t)images * 8) + align256((size_t)images * tiles * 8);
+}
+
+int fiunet_psnr_u8(const uint8_t* pred, const uint8_t* target, int images, int H, int W, double* out,
+                   void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_BAD_SHAPE, "bad image shape");
+    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
+    if (workspace_bytes < align256((size_t)images * 8)) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* sums = (unsigned long long*)workspace;
+    const size_t n = (size_t)H * W;
+    if (int rc = zero_fill_async(sums, (size_t)images * 8, s)) return rc;
+    // ~4 x 16 B per thread and at most 128 workgroups (= atomics) per image
+    const unsigned bx = (unsigned)std::min<size_t>((n / 64 + 255) / 256 + 1, 128);
+    hipLaunchKernelGGL(sqdiff_u8_kernel, dim3(bx, (unsigned)images), dim3(256), 0, s, pred, target, n, sums);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(psnr_finalize_kernel, dim3((images + 63) / 64), dim3(64), 0, s, sums, n, out, images);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_ssim_u8(const uint8_t* pred, const uint8_t* target, int images, int H, int W, double* out,
+                   void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (images < 1) return fail(FIUNET_ERR_BAD_SHAPE, "bad image shape");
+    if (H < SSIM_WIN || W < SSIM_WIN)
+        return fail(FIUNET_ERR_BAD_SHAPE, "SSIM: the 7x7 window exceeds the image (skimage raises too)");
+    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
+    if (workspace_bytes < fiunet_metrics_workspace_bytes(images, H, W))
+        return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    int tx = 0;
+    const int tiles = ssim_tiles(H, W, &tx);
+    double* partial = (double*)((char*)workspace + align256((size_t)images * 8));
+    hipLaunchKernelGGL(ssim_u8_kernel, dim3((unsigned)tiles, (unsigned)images), dim3(256), 0, s, pred, target,
+                       H, W, tx, partial);
+    HIP_TRY(hipGetLastError());
+    const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
+    hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+size_t fiunet_plane_metrics_workspace_bytes(int images, int H, int W)
+{
+    if (images < 1 || H < 1 || W < 1) {
+        last_error() = "fiunet_plane_metrics_workspace_bytes: bad arguments";
+        return 0;
+    }
+    return fiunet_metrics_workspace_bytes(images, H, W);
+}
+
+// The checks both plane metrics share; every refusal is FIUNET_ERR_INVALID_ARG and comes before any pointer is used.
+// pred_row / target_row: the samples a row spans on each side (W; W*S interleaved; (W-1)*step + 1 stepped).
+static int check_planes(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                        size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
+                        const void* out, const void* workspace, size_t workspace_bytes, size_t need,
+                        size_t pred_row = 0, size_t target_row = 0)
+{
+    if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
+    if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_INVALID_ARG, "bad plane shape");
+    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
+    if (!pred_row) pred_row = (size_t)W;
+    if (!target_row) target_row = (size_t)W;
+    if (pred_row_pitch < pred_row || target_row_pitch < target_row)
+        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: row_pitch < W");
+    const size_t limit = (size_t)1 << 40;
+    if (pred_row_pitch > limit || target_row_pitch > limit || pred_image_stride > limit || target_image_stride > limit)
+        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: a value above 2^40 samples");
+    if (images > 1 && (pred_image_stride < (size_t)(H - 1) * pred_row_pitch + pred_row ||
+                       target_image_stride < (size_t)(H - 1) * target_row_pitch + target_row))
+        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: image_stride smaller than one plane");
+    const size_t align = bits == 10 ? 1 : 0;
+    if ((((uintptr_t)pred | (uintptr_t)target) & align) != 0)
+        return fail(FIUNET_ERR_INVALID_ARG, "10-bit planes are 16-bit words: odd address");
+    if (workspace_bytes < need) return fail(FIUNET_ERR_INVALID_ARG, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    return FIUNET_OK;
+}
+
+extern "C++" {   // (a template over the sample type, inside this file's extern "C" part)
+template <typename T>
+static int launch_plane_psnr(const void* pred, size_t ps, size_t pp, const void* target, size_t ts, size_t tp,
+                             int images, int H, int W, unsigned long long* sums, hipStream_t s)
+{
+    // a plane whose rows follow each other on both sides is one run of H*W samples, cut into PLANE_SEG pieces
+    // (a multiple of 16 bytes, so every piece of an aligned plane keeps the 16-byte path)
+    const size_t n = (size_t)H * W;
+    const bool flat = pp == (size_t)W && tp == (size_t)W;
+    if (flat && (n + PLANE_SEG - 1) / PLANE_SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
+    const unsigned rows = flat ? (unsigned)((n + PLANE_SEG - 1) / PLANE_SEG) : (unsigned)H;
+    const unsigned w = flat ? (unsigned)PLANE_SEG : (unsigned)W;
+    const unsigned w_last = flat ? (unsigned)(n - (size_t)(rows - 1) * PLANE_SEG) : (unsigned)W;
+    const size_t pa = flat ? (size_t)PLANE_SEG : pp, pb = flat ? (size_t)PLANE_SEG : tp;
+    // one wave per row and step, at most 128 workgroups (= atomics) per image
+    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
+    hipLaunchKernelGGL(plane_sqdiff_kernel<T>, dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)pred, ps, pa,
+                       (const T*)target, ts, pb, rows, w, w_last, sums);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_plane_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                      size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
+                      double* out_psnr, unsigned long long* out_sse, void* workspace, size_t workspace_bytes,
+                      void* stream)
+{
+    const size_t need = images > 0 ? align256((size_t)images * 8) : 0;
+    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
+                              bits, images, H, W, out_psnr, workspace, workspace_bytes, need))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* sums = (unsigned long long*)workspace;
+    if (int rc = zero_fill_async(sums, (size_t)images * 8, s)) return rc;
+    if (int rc = bits == 10 ? launch_plane_psnr<uint16_t>(pred, pred_image_stride, pred_row_pitch, target,
+                                                          target_image_stride, target_row_pitch, images, H, W, sums, s)
+                            : launch_plane_psnr<uint8_t>(pred, pred_image_stride, pred_row_pitch, target,
+                                                         target_image_stride, target_row_pitch, images, H, W, sums, s))
+        return rc;
+    hipLaunchKernelGGL(plane_psnr_finalize_kernel, dim3((images + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
+                       bits == 10 ? 1023.0 : 255.0, out_psnr, out_sse, images);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_stepped_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, int pred_step,
+                              const void* target, size_t target_image_stride, size_t target_row_pitch, int target_step,
+                              int bits, int images, int H, int W, double* out_ssim, void* workspace,
+                              size_t workspace_bytes, void* stream)
+{
+    if (pred_step < 1 || pred_step > 4 || target_step < 1 || target_step > 4)
+        return fail(FIUNET_ERR_INVALID_ARG, "sample step must be 1, 2, 3 or 4");
+    if (H < SSIM_WIN || W < SSIM_WIN)
+        return fail(FIUNET_ERR_INVALID_ARG, "SSIM: the 7x7 window exceeds the plane (skimage raises too)");
+    const size_t need = images > 0 ? fiunet_metrics_workspace_bytes(images, H, W) : 0;
+    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
+                              bits, images, H, W, out_ssim, workspace, workspace_bytes, need,
+                              (size_t)(W - 1) * pred_step + 1, (size_t)(W - 1) * target_step + 1))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    int tx = 0;
+    const int tiles = ssim_tiles(H, W, &tx);
+    double* partial = (double*)((char*)workspace + align256((size_t)images * 8));
+    const dim3 grid((unsigned)tiles, (unsigned)images);
+    if (bits == 10)
+        hipLaunchKernelGGL(plane_ssim_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)pred, pred_image_stride,
+                           pred_row_pitch, (unsigned)pred_step, (const uint16_t*)target, target_image_stride,
+                           target_row_pitch, (unsigned)target_step, H, W, tx, partial);
+    else
+        hipLaunchKernelGGL(plane_ssim_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)pred, pred_image_stride,
+                           pred_row_pitch, (unsigned)pred_step, (const uint8_t*)target, target_image_stride,
+                           target_row_pitch, (unsigned)target_step, H, W, tx, partial);
+    HIP_TRY(hipGetLastError());
+    const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
+    hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out_ssim);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                      size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
+                      double* out_ssim, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return fiunet_stepped_ssim(pred, pred_image_stride, pred_row_pitch, 1, target, target_image_stride,
+                                     target_row_pitch, 1, bits, images, H, W, out_ssim, workspace, workspace_bytes,
+                                     stream);
+}
+
+extern "C++" {
+template <typename T, int S>
+static int launch_interleaved_sqdiff(const void* pred, size_t ps, size_t pp, const void* target, size_t ts, size_t tp,
+                                     int images, int H, int W, unsigned long long* sums, hipStream_t s)
+{
+    // rows that follow each other on both sides are one run of H*W*S samples, cut into interleaved_seg(S) pieces (a
+    // multiple of S and of 16 bytes: a piece starts at component 0 and an aligned run keeps the 16-byte path)
+    constexpr size_t SEG = interleaved_seg(S);
+    const size_t row = (size_t)W * S, n = (size_t)H * row;
+    const bool flat = pp == row && tp == row;
+    if (flat && (n + SEG - 1) / SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
+    const unsigned rows = flat ? (unsigned)((n + SEG - 1) / SEG) : (unsigned)H;
+    const unsigned len = flat ? (unsigned)SEG : (unsigned)row;
+    const unsigned l_last = flat ? (unsigned)(n - (size_t)(rows - 1) * SEG) : (unsigned)row;
+    const size_t pa = flat ? SEG : pp, pb = flat ? SEG : tp;
+    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
+    hipLaunchKernelGGL((interleaved_sqdiff_kernel<T, S>), dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)pred, ps,
+                       pa, (const T*)target, ts, pb, rows, len, l_last, sums);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+template <typename T>
+static int launch_interleaved_psnr(int S, const void* pred, size_t ps, size_t pp, const void* target, size_t ts,
+                                   size_t tp, int images, int H, int W, unsigned long long* sums, hipStream_t s)
+{
+    if (S == 2) return launch_interleaved_sqdiff<T, 2>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
+    if (S == 3) return launch_interleaved_sqdiff<T, 3>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
+    return launch_interleaved_sqdiff<T, 4>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
+}
+}  // extern "C++"
+
+int fiunet_interleaved_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
+                            size_t target_image_stride, size_t target_row_pitch, int bits, int components, int images,
+                            int H, int W, double* out_psnr, unsigned long long* out_sse, void* workspace,
+                            size_t workspace_bytes, void* stream)
+{
+    if (components < 2 || components > 4) return fail(FIUNET_ERR_INVALID_ARG, "components must be 2, 3 or 4");
+    if (W > (1 << 29)) return fail(FIUNET_ERR_INVALID_ARG, "bad plane shape");
+    if (images > 65535 / components)
+        return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 component planes (images x components) per call");
+    const size_t row = W > 0 ? (size_t)W * components : 0;
+    const size_t need = images > 0 ? align256((size_t)images * components * 8) : 0;
+    if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
+                              bits, images, H, W, out_psnr, workspace, workspace_bytes, need, row, row))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* sums = (unsigned long long*)workspace;
+    const int planes = images * components;
+    if (int rc = zero_fill_async(sums, (size_t)planes * 8, s)) return rc;
+    if (int rc = bits == 10 ? launch_interleaved_psnr<uint16_t>(components, pred, pred_image_stride, pred_row_pitch,
+                                                                target, target_image_stride, target_row_pitch, images,
+                                                                H, W, sums, s)
+                            : launch_interleaved_psnr<uint8_t>(components, pred, pred_image_stride, pred_row_pitch,
+                                                               target, target_image_stride, target_row_pitch, images, H,
+                                                               W, sums, s))
+        return rc;
+    hipLaunchKernelGGL(plane_psnr_finalize_kernel, dim3((planes + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
+                       bits == 10 ? 1023.0 : 255.0, out_psnr, out_sse, planes);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+static inline int gssim_tiles(int H, int W, int* tiles_x)
+{
+    const int tx = (W + GSSIM_TX - 1) / GSSIM_TX, ty = (H + GSSIM_TY - 1) / GSSIM_TY;
+    if (tiles_x) *tiles_x = tx;
+    return tx * ty;
+}
+
+size_t fiunet_ssim_gauss_workspace_bytes(int images, int H, int W)
+{
+    if (images < 1 || H < 1 || W < 1) {
+        last_error() = "fiunet_ssim_gauss_workspace_bytes: bad arguments";
+        return 0;
+    }
+    return align256((size_t)images * gssim_tiles(H, W, nullptr) * 2 * 8);
+}
+
+int fiunet_ssim_gauss_f32(const float* img1, const float* img2, int images, int H, int W, int window_size,
+                          const float* window_1d, double* out_ssim, double* out_sqerr, void* workspace,
+                          size_t workspace_bytes, void* stream)
+{
+    if (!img1 || !img2 || !out_ssim || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_BAD_SHAPE, "bad image shape");
+    if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
+    if (window_size < 1 || window_size > 2 * GSSIM_MAXR + 1 || !(window_size & 1))
+        return fail(FIUNET_ERR_UNSUPPORTED, "Gaussian SSIM: window_size must be odd and <= 31 (an even window "
+                                            "changes the map size in the reference: padding = window_size//2)");
+    if (workspace_bytes < fiunet_ssim_gauss_workspace_bytes(images, H, W))
+        return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
+    // train.py:27-29: fp32 tensor of exp(-(x - ws//2)^2 / (2 sigma^2)) (evaluated in double by numpy), sigma =
+    // 1.5 (:32), divided by its fp32 sum
+    const int R = window_size / 2;
+    GaussWindow win;
+    float sum = 0.f;
+    for (int x = 0; x < window_size; ++x) {
+        win.g[x] = (float)std::exp(-(double)((x - R) * (x - R)) / (2.0 * 1.5 * 1.5));
+        sum += win.g[x];
+    }
+    for (int x = 0; x < window_size; ++x) win.g[x] /= sum;
+    // the caller's own normalised window (torch's `gauss / gauss.sum()`: its reduction order decides the last
+    // bit of the sum, and the SSIM map's variance terms feel 1 ulp of the window's total at the 1e-7 level)
+    if (window_1d)
+        for (int x = 0; x < window_size; ++x) win.g[x] = window_1d[x];
+    for (int x = window_size; x < 2 * GSSIM_MAXR + 1; ++x) win.g[x] = 0.f;
+    hipStream_t s = (hipStream_t)stream;
+    int tx = 0;
+    const int tiles = gssim_tiles(H, W, &tx);
+    double* partial = (double*)workspace;
+    const int IH = GSSIM_TY + 2 * R, IW = GSSIM_TX + 2 * R;
+    const size_t lds = (size_t)5 * IH * GSSIM_TX * 8 + (size_t)2 * IH * (IW + 1) * 4;
+    if (R == 5)
+        hipLaunchKernelGGL((ssim_gauss_f32_kernel<5>), dim3((unsigned)tiles, (unsigned)images), dim3(256), lds, s,
+                           img1, img2, H, W, tx, R, win, partial);
+    else
+        hipLaunchKernelGGL((ssim_gauss_f32_kernel<0>), dim3((unsigned)tiles, (unsigned)images), dim3(256), lds, s,
+                           img1, img2, H, W, tx, R, win, partial);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ssim_gauss_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles,
+                       (double)H * (double)W, out_ssim, out_sqerr);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+}  // extern "C"

@@ -10,7 +10,7 @@
 //
 // Thread shape as in colour.hip.h: a thread covers 4 pixels of a row, grid = (ceil(ceil(W/4) / 128), H, B), so a wave
 // moves 256 contiguous pixels of a row: 768 or 1024 contiguous bytes on the packed side, 256 on each plane.  With VEC -
-// W % 4 == 0 and every pitch, stride and base a multiple of 4 bytes (the host decides: packed_vec in fiunet.hip) - the
+// W % 4 == 0 and every pitch, stride and base a multiple of 4 bytes (the host decides: packed_vec in formats.hip) - the
 // thread's 12 packed bytes are three dword accesses and its 16 packed bytes one 16-byte access, each plane quad one
 // uchar4; the bytes change place in registers.  The 16-byte access is declared dword-aligned (PackedQuad below), which is
 // all a global access wider than a dword needs on this hardware, so a pitch of W*4 + 4 keeps it.  Without VEC every

@@ -13,7 +13,7 @@
 //   pre/postprocess kernels: model/inference.py:31-35 and :54-61 on device; their 10-bit counterparts (pre10 / post10,
 //                            DESIGN.md 3.3d) for the 10-bit video path
 #pragma once
-#include "conv3x3_mfma.hip.h"
+#include "conv_common.hip.h"
 
 namespace fiunet {
 

@@ -1,0 +1,303 @@
+// video.hip -- operations on frame sequences: scene cuts and repeated frames (scene.hip.h), frame-rate conversion
+// (retime.hip.h) and resizing frame planes (resize.hip.h).
+#include "fiunet_internal.h"
+#include "scene.hip.h"
+#include "retime.hip.h"
+#include "resize.hip.h"
+
+using namespace fiunet;
+
+extern "C" {
+
+// ---- scene cuts (csrc/scene.hip.h) -------------------------------------------------------------
+constexpr int kMaxGridY = 65535;   // pairs / intervals per launch (grid.y)
+
+extern "C++" {   // (a template inside the extern "C" block)
+template <typename T>
+static int pair_sad(const T* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
+{
+    if (!frames || !sums) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    if (n_frames < 2 || frame_samples == 0) return FIUNET_OK;
+    // ~4 x 16 B per thread and at most 128 workgroups (= atomics) per pair, as fiunet_psnr_u8
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
+    for (int p0 = 0; p0 < n_frames - 1; p0 += kMaxGridY) {
+        const int np = std::min(n_frames - 1 - p0, kMaxGridY);
+        hipLaunchKernelGGL(pair_sad_kernel<T>, dim3(bx, (unsigned)np), dim3(kSceneBlock), 0, (hipStream_t)stream,
+                           frames + (size_t)p0 * frame_samples, frame_samples,
+                           reinterpret_cast<unsigned long long*>(sums + p0));
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_pair_sad_u8(const uint8_t* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
+{
+    return pair_sad(frames, n_frames, frame_samples, sums, stream);
+}
+
+int fiunet_pair_sad_p10(const uint16_t* frames, int n_frames, size_t frame_samples, int64_t* sums, void* stream)
+{
+    return pair_sad(frames, n_frames, frame_samples, sums, stream);
+}
+
+// repeated frames: the calling conventions of pair_sad
+extern "C++" {
+template <typename T>
+static int pair_peak(const T* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
+{
+    if (!frames || !peaks) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    if (n_frames < 2 || frame_samples == 0) return FIUNET_OK;
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
+    for (int p0 = 0; p0 < n_frames - 1; p0 += kMaxGridY) {
+        const int np = std::min(n_frames - 1 - p0, kMaxGridY);
+        hipLaunchKernelGGL(pair_peak_kernel<T>, dim3(bx, (unsigned)np), dim3(kSceneBlock), 0, (hipStream_t)stream,
+                           frames + (size_t)p0 * frame_samples, frame_samples, peaks + p0);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_pair_peak_u8(const uint8_t* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
+{
+    return pair_peak(frames, n_frames, frame_samples, peaks, stream);
+}
+
+int fiunet_pair_peak_p10(const uint16_t* frames, int n_frames, size_t frame_samples, uint32_t* peaks, void* stream)
+{
+    return pair_peak(frames, n_frames, frame_samples, peaks, stream);
+}
+
+int fiunet_scene_cuts(const int64_t* sums, int n_frames, size_t count, int bits, double threshold, double* scores,
+                      uint8_t* flags, void* stream)
+{
+    if (!sums || !scores || !flags) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
+    if (!(threshold > 0.0 && threshold <= 100.0)) return fail(FIUNET_ERR_INVALID_ARG, "threshold outside (0, 100]");
+    if (count == 0) return fail(FIUNET_ERR_INVALID_ARG, "count == 0");
+    if (n_frames < 2) return FIUNET_OK;
+    const int intervals = n_frames - 1;
+    hipLaunchKernelGGL(scene_cuts_kernel, dim3((unsigned)((intervals + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, reinterpret_cast<const long long*>(sums), intervals, (double)count,
+                       (double)(1 << bits), threshold, scores, flags);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+int fiunet_hold_cut_frames(uint8_t* video, int n_frames, size_t frame_bytes, int factor, const uint8_t* flags,
+                           void* stream)
+{
+    if (!video || !flags) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    if (factor < 2 || (factor & (factor - 1)) || factor > (1 << 20))
+        return fail(FIUNET_ERR_INVALID_ARG, "factor must be a power of two in [2, 2^20]");
+    if (n_frames < 2 || frame_bytes == 0) return FIUNET_OK;
+    const unsigned gx = (unsigned)kHoldBlocks * (unsigned)(factor - 1);
+    for (int i0 = 0; i0 < n_frames - 1; i0 += kMaxGridY) {
+        const int ni = std::min(n_frames - 1 - i0, kMaxGridY);
+        hipLaunchKernelGGL(hold_cut_frames_kernel, dim3(gx, (unsigned)ni), dim3(kSceneBlock), 0, (hipStream_t)stream,
+                           video + (size_t)i0 * factor * frame_bytes, frame_bytes, factor, flags + i0);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+
+// ---- frame-rate conversion (csrc/retime.hip.h) ---------------------------------------------------
+extern "C++" {
+template <typename T>
+static int retime(const T* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval, uint64_t j0,
+                  int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, T* out, void* stream)
+{
+    if (!grid || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_intervals < 0 || n_out < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
+    if (depth < 1 || depth > 4) return fail(FIUNET_ERR_INVALID_ARG, "depth outside 1..4");
+    if (p == 0 || p >= q) return fail(FIUNET_ERR_INVALID_ARG, "need 0 < p < q");
+    if (q > kRetimeMaxQ) return fail(FIUNET_ERR_INVALID_ARG, "q above 2^20");
+    if (mode != 0 && mode != 1) return fail(FIUNET_ERR_INVALID_ARG, "mode must be 0 (blend) or 1 (nearest)");
+    if (n_out == 0) return FIUNET_OK;
+    // the first and the last requested frame lie in the grid (the times in between do, being monotonic); in 128 bits,
+    // so that the kernel's 64-bit j * p cannot wrap
+    const unsigned __int128 t0 = (unsigned __int128)j0 * p, t1 = ((unsigned __int128)j0 + (unsigned)(n_out - 1)) * p;
+    if (t1 >> 64) return fail(FIUNET_ERR_INVALID_ARG, "frame index too large");
+    const unsigned __int128 end = (unsigned __int128)first_interval + (unsigned)n_intervals;
+    if (t0 / q < first_interval) return fail(FIUNET_ERR_INVALID_ARG, "first frame lies before the grid");
+    if (t1 / q > end || (t1 / q == end && t1 % q != 0))
+        return fail(FIUNET_ERR_INVALID_ARG, "last frame lies behind the grid");
+    if (frame_samples == 0) return FIUNET_OK;
+    // ~4 x 16 B per thread and at most 128 workgroups per frame, as fiunet_pair_sad_u8
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
+    for (int k0 = 0; k0 < n_out; k0 += kMaxGridY) {
+        const int nk = std::min(n_out - k0, kMaxGridY);
+        hipLaunchKernelGGL(retime_kernel<T>, dim3(bx, (unsigned)nk), dim3(kRetimeBlock), 0, (hipStream_t)stream, grid,
+                           frame_samples, depth, (unsigned long long)first_interval, (unsigned long long)(j0 + k0), p, q,
+                           mode, flags, out + (size_t)k0 * frame_samples);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_retime_u8(const uint8_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
+                     uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint8_t* out,
+                     void* stream)
+{
+    return retime(grid, n_intervals, frame_samples, depth, first_interval, j0, n_out, p, q, mode, flags, out, stream);
+}
+
+int fiunet_retime_p10(const uint16_t* grid, int n_intervals, size_t frame_samples, int depth, uint64_t first_interval,
+                      uint64_t j0, int n_out, uint32_t p, uint32_t q, int mode, const uint8_t* flags, uint16_t* out,
+                      void* stream)
+{
+    return retime(grid, n_intervals, frame_samples, depth, first_interval, j0, n_out, p, q, mode, flags, out, stream);
+}
+
+// the table-driven form: every entry is checked here, on the host, before the first launch; the entries
+// travel in the kernel's arguments, kRetimeTableMax output frames per launch
+static_assert(sizeof(fiunet_retime_entry) == sizeof(RetimeEntry) && sizeof(RetimeEntry) == 12, "entry layout");
+
+extern "C++" {
+template <typename T>
+static int retime_table(const T* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries, int n_out,
+                        T* out, void* stream)
+{
+    if (!grid || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_rows < 0 || n_out < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
+    if (n_out == 0) return FIUNET_OK;
+    if (!entries) return fail(FIUNET_ERR_INVALID_ARG, "NULL entries");
+    for (int k = 0; k < n_out; ++k) {
+        const fiunet_retime_entry& e = entries[k];
+        if (e.den < 1 || e.den > kRetimeMaxQ) return fail(FIUNET_ERR_INVALID_ARG, "entry: den outside 1..2^20");
+        if (e.wn >= e.den) return fail(FIUNET_ERR_INVALID_ARG, "entry: wn >= den");
+        if ((uint64_t)e.row >= (uint64_t)n_rows) return fail(FIUNET_ERR_INVALID_ARG, "entry: row outside the grid");
+        if (e.wn > 0 && (uint64_t)e.row + 1 >= (uint64_t)n_rows)
+            return fail(FIUNET_ERR_INVALID_ARG, "entry: the row after `row` lies outside the grid");
+    }
+    if (frame_samples == 0) return FIUNET_OK;
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 64 + 255) / 256 + 1, 128);
+    for (int k0 = 0; k0 < n_out; k0 += kRetimeTableMax) {
+        const int nk = std::min(n_out - k0, kRetimeTableMax);
+        RetimeTable table = {};
+        for (int k = 0; k < nk; ++k) table.e[k] = RetimeEntry{entries[k0 + k].row, entries[k0 + k].wn, entries[k0 + k].den};
+        hipLaunchKernelGGL(retime_table_kernel<T>, dim3(bx, (unsigned)nk), dim3(kRetimeBlock), 0, (hipStream_t)stream,
+                           grid, frame_samples, table, out + (size_t)k0 * frame_samples);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_retime_table_u8(const uint8_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
+                           int n_out, uint8_t* out, void* stream)
+{
+    return retime_table(grid, n_rows, frame_samples, entries, n_out, out, stream);
+}
+
+int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
+                            int n_out, uint16_t* out, void* stream)
+{
+    return retime_table(grid, n_rows, frame_samples, entries, n_out, out, stream);
+}
+
+// ---- resizing frame planes (csrc/resize.hip.h) ------------------------------------------------------
+extern "C++" {
+// the byte range [lo, hi) that n frames of the planes cover, from the buffer's first sample
+static void resize_extent(const fiunet_resize_plane* planes, int n_planes, int n_frames, size_t& lo, size_t& hi)
+{
+    lo = SIZE_MAX, hi = 0;
+    for (int i = 0; i < n_planes; ++i) {
+        const fiunet_resize_plane& p = planes[i];
+        const size_t end = p.offset + (size_t)(n_frames - 1) * p.frame_stride + (size_t)(p.h - 1) * p.pitch +
+                           (size_t)(p.w - 1) * p.step + 1;
+        lo = std::min(lo, p.offset), hi = std::max(hi, end);
+    }
+}
+
+static const char* resize_check_plane(const fiunet_resize_plane& p)
+{
+    if (p.h < 1 || p.w < 1) return "a plane's h and w must be positive";
+    if (p.h > kResizeMaxSize || p.w > kResizeMaxSize) return "a plane's h and w must not exceed 2^24";
+    if (p.step < 1 || p.step > 4) return "a plane's step must be 1..4";
+    if (p.pitch < (size_t)(p.w - 1) * p.step + 1) return "a plane's pitch must cover a row: (w - 1) * step + 1";
+    // (h, w <= 2^24, step <= 4: the row term is below 2^26; the others are checked against wrapping)
+    const size_t row = (size_t)(p.w - 1) * p.step + 1;
+    if (p.h > 1 && p.pitch > (SIZE_MAX - row) / (size_t)(p.h - 1)) return "a plane's pitch is too large";
+    const size_t body = (size_t)(p.h - 1) * p.pitch + row;
+    if (p.offset > p.frame_stride || body > p.frame_stride - p.offset) return "a plane must lie inside its frame stride";
+    return nullptr;
+}
+
+template <typename T>
+static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, const fiunet_resize_plane* dp,
+                         int n_planes, int n_frames, void* stream)
+{
+    if (!src || !dst || !sp || !dp) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (((uintptr_t)src | (uintptr_t)dst) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
+    if (n_planes < 1 || n_planes > kResizeMaxPlanes) return fail(FIUNET_ERR_INVALID_ARG, "n_planes must be 1..4");
+    if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
+    constexpr int V = ResizeSample<T>::kVec;
+    ResizeArgs base = {};
+    unsigned long long per_frame_max = 0;
+    for (int i = 0; i < n_planes; ++i) {
+        for (const fiunet_resize_plane* p : {&sp[i], &dp[i]}) {
+            if (const char* why = resize_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
+            // n frames of the plane stay inside the address space
+            if (n_frames > 1 && p->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_frames)
+                return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+        }
+        ResizePlane& P = base.p[i];
+        P.src_off = sp[i].offset, P.src_pitch = sp[i].pitch, P.src_fs = sp[i].frame_stride;
+        P.dst_off = dp[i].offset, P.dst_pitch = dp[i].pitch, P.dst_fs = dp[i].frame_stride;
+        P.sh = sp[i].h, P.sw = sp[i].w, P.dh = dp[i].h, P.dw = dp[i].w;
+        P.sstep = sp[i].step, P.dstep = dp[i].step;
+        P.sx = (double)P.sw / (double)P.dw, P.sy = (double)P.sh / (double)P.dh;
+        P.chunks = (unsigned)((P.dw + V - 1) / V) + (P.dstep == 1 ? 1u : 0u);
+        const unsigned long long per_frame = (unsigned long long)P.dh * P.chunks;
+        if (per_frame >= (1ull << 31)) return fail(FIUNET_ERR_UNSUPPORTED, "a destination plane of 2^31 or more store chunks");
+        per_frame_max = std::max(per_frame_max, per_frame);
+    }
+    if (n_frames == 0) return FIUNET_OK;
+    size_t slo, shi, dlo, dhi;
+    resize_extent(sp, n_planes, n_frames, slo, shi);
+    resize_extent(dp, n_planes, n_frames, dlo, dhi);
+    const uintptr_t s0 = (uintptr_t)src + slo * sizeof(T), s1 = (uintptr_t)src + shi * sizeof(T);
+    const uintptr_t d0 = (uintptr_t)dst + dlo * sizeof(T), d1 = (uintptr_t)dst + dhi * sizeof(T);
+    if (s0 < d1 && d0 < s1) return fail(FIUNET_ERR_INVALID_ARG, "source and destination overlap");
+    // frames per launch: every plane's item count stays below 2^31
+    const int batch = (int)std::min<unsigned long long>(((1ull << 31) - 1) / per_frame_max, (unsigned long long)n_frames);
+    for (int f0 = 0; f0 < n_frames; f0 += batch) {
+        const int nf = std::min(batch, n_frames - f0);
+        ResizeArgs args = base;
+        unsigned items_max = 0;
+        for (int i = 0; i < n_planes; ++i) {
+            ResizePlane& P = args.p[i];
+            P.src_off += (size_t)f0 * P.src_fs, P.dst_off += (size_t)f0 * P.dst_fs;
+            P.items = (unsigned)nf * (unsigned)P.dh * P.chunks;
+            items_max = std::max(items_max, P.items);
+        }
+        // one item per thread up to 8192 workgroups (32 per CU), a grid-stride loop beyond
+        const unsigned bx = std::min((items_max + kResizeBlock - 1) / kResizeBlock, 8192u);
+        hipLaunchKernelGGL(resize_planes_kernel<T>, dim3(bx, (unsigned)n_planes), dim3(kResizeBlock), 0,
+                           (hipStream_t)stream, src, dst, args);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_resize_planes_u8(const uint8_t* src, const fiunet_resize_plane* src_planes, uint8_t* dst,
+                            const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream)
+{
+    return resize_planes(src, src_planes, dst, dst_planes, n_planes, n_frames, stream);
+}
+
+int fiunet_resize_planes_p10(const uint16_t* src, const fiunet_resize_plane* src_planes, uint16_t* dst,
+                             const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream)
+{
+    return resize_planes(src, src_planes, dst, dst_planes, n_planes, n_frames, stream);
+}
+
+}  // extern "C"

@@ -424,7 +424,7 @@ def _pointwise_rows():
 
 
 # ---- colour: the fourteen conversions, each on its vector and its scalar path --------------------------------------
-#: W % 4 == 0 and tight layouts whose every value is a multiple of 4 samples: the `*_vec` predicates of csrc/fiunet.hip
+#: W % 4 == 0 and tight layouts whose every value is a multiple of 4 samples: the `*_vec` predicates of csrc/formats.hip
 #: hold; W % 4 == 2 (even, for the one-plane 4:2:2 formats) and an odd H: they do not
 COLOUR_SHAPES = {"vector": (2, 36, 72), "scalar": (2, 33, 70)}
 

@@ -2,7 +2,7 @@
 exercise (VERDICT r01 "Next round" item 1), all through the C ABI:
 
   config 2   B=16 256x256 fp32 -- a different kernel path from the B=1 golden (the split-K
-             decision depends on the number of workgroups, csrc/fiunet.hip launch_conv_maybe_split)
+             decision depends on the number of workgroups, csrc/conv_launch.hip.h launch_conv_maybe_split)
   config 4   the video loop at FULL frame size (1080p), short length, device and host variants
   RGB bf16   conv3x3_first_kernel<bf16,3> + EPI_HEAD3 in bf16, fused and unfused, odd size
   RGB fp32   pinned to the reference's own UNet(6,3) outputs (tests/golden/out_rgb_*.npz)

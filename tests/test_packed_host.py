@@ -239,8 +239,3 @@ def test_new_header_names_are_in_the_binding():
     assert "typedef struct fiunet_packed_layout" in src
     assert [f for f, _ in _native.PackedLayout._fields_] == list(packed.PackedLayout._fields) == \
         re.search(r"fiunet_packed_layout \{\s*size_t ([^;]+);", src).group(1).replace(" ", "").split(",")
-
-
-def test_makefile_sees_the_header():
-    mk = open(os.path.join(ROOT, "ai_based_frame_interpolation_amd", "csrc", "Makefile")).read()
-    assert "packed.hip.h" in re.search(r"^HDRS := (.*)$", mk, flags=re.M).group(1)

@@ -20,7 +20,7 @@ from ai_based_frame_interpolation_amd import _native
 FP32, BF16, BF16X2 = _native.FP32, _native.BF16, _native.BF16X2
 # source forms (csrc/fiunet.hip SrcForm)
 DIRECT, POOL, GATHER, UP, CONVT, UPCAT, STEM = range(7)
-# output channels of convs 0..17 (csrc/fiunet.hip kCoutBil / kCoutCT: /root/reference/model/unet.py:65-82) and their level
+# output channels of convs 0..17 (csrc/fiunet_internal.h kCoutBil / kCoutCT: /root/reference/model/unet.py:65-82) and their level
 COUT = {True: [64, 64, 128, 128, 256, 256, 512, 512, 512, 512, 512, 256, 256, 128, 128, 64, 64, 64],
         False: [64, 64, 128, 128, 256, 256, 512, 512, 1024, 1024, 512, 512, 256, 256, 128, 128, 64, 64]}
 LEVEL = [0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 0, 0]

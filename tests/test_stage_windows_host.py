@@ -262,8 +262,8 @@ def level_shape(h, w, level):
 
 
 def tile_shape(small, cout, h, w):
-    """(TH, TW) of a conv launch on an h x w level, restated from csrc/fiunet.hip (kSmallTile, big_tile, prefer_wide): the
-    32-wide tile unless the narrow one saves more than 1/32 of the padded area."""
+    """(TH, TW) of a conv launch on an h x w level, restated from csrc/fiunet.hip (kSmallTile, big_tile) and
+    csrc/fiunet_internal.h (prefer_wide): the 32-wide tile unless the narrow one saves more than 1/32 of the padded area."""
     def padded(th, tw):
         return -(-h // th) * th * (-(-w // tw) * tw)
 

@@ -434,5 +434,3 @@ def test_new_header_names_are_in_the_binding():
     sym = list(_native.SYMBOLS)
     assert max(sym.index(n) for n in NEW) < sym.index("fiunet_packed_to_rgb_u8")
     assert sym[-1] == "fiunet_forward_p010"
-    mk = open(os.path.join(ROOT, "ai_based_frame_interpolation_amd", "csrc", "Makefile")).read()
-    assert "yuv4xx.hip.h" in re.search(r"^HDRS := (.*)$", mk, flags=re.M).group(1)
