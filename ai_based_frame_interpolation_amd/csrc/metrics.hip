@@ -1,5 +1,6 @@
-// metrics.hip -- PSNR and SSIM on the GPU (metrics.hip.h): the uint8 batch metrics, the plane / interleaved / stepped
-// metrics of hold-out scoring and the Gaussian SSIM of the training loss.
+// metrics.hip -- PSNR and SSIM on the GPU (metrics.hip.h): the uint8 batch metrics and the plane / interleaved / stepped
+// metrics of hold-out scoring - each entry point its own argument checks, then the same launches - and the Gaussian SSIM
+// of the training loss.
 #include "fiunet_internal.h"
 #include "metrics.hip.h"
 
@@ -27,6 +28,90 @@ size_t fiunet_metrics_workspace_bytes(int images, int H, int W)
     return align256((size_t)images * 8) + align256((size_t)images * tiles * 8);
 }
 
+// What every entry point does once its own checks have passed.  One side of a comparison: `images` images `image`
+// samples apart, rows `pitch` samples apart, SSIM's samples `step` apart (the squared error has no step: its samples
+// follow each other).
+struct PlaneSide { const void* p; size_t image, pitch; unsigned step; };
+
+extern "C++" {   // (templates over the sample type, inside this file's extern "C" part)
+template <typename T, int S>
+static int launch_sqdiff(const PlaneSide& a, const PlaneSide& b, int images, int H, int W, unsigned long long* sums,
+                         hipStream_t s)
+{
+    // rows that follow each other on both sides are one run of H*W*S samples, cut into sqdiff_seg(S) pieces (a
+    // multiple of S and of 16 bytes: a piece starts at component 0 and an aligned run keeps the 16-byte path).  (The
+    // refusal needs more than 2^44 samples per plane, which no buffer holds: fiunet_psnr_u8, always flat, never
+    // answers it in practice.)
+    constexpr size_t SEG = sqdiff_seg(S);
+    const size_t row = (size_t)W * S, n = (size_t)H * row;
+    const bool flat = a.pitch == row && b.pitch == row;
+    if (flat && (n + SEG - 1) / SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
+    const unsigned rows = flat ? (unsigned)((n + SEG - 1) / SEG) : (unsigned)H;
+    const unsigned len = flat ? (unsigned)SEG : (unsigned)row;
+    const unsigned l_last = flat ? (unsigned)(n - (size_t)(rows - 1) * SEG) : (unsigned)row;
+    const size_t pa = flat ? SEG : a.pitch, pb = flat ? SEG : b.pitch;
+    // one wave per row and step, at most 128 workgroups (= atomics) per image
+    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
+    hipLaunchKernelGGL((sqdiff_kernel<T, S>), dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)a.p, a.image, pa,
+                       (const T*)b.p, b.image, pb, rows, len, l_last, sums);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+template <typename T>
+static int launch_sqdiff(int S, const PlaneSide& a, const PlaneSide& b, int images, int H, int W,
+                         unsigned long long* sums, hipStream_t s)
+{
+    if (S == 1) return launch_sqdiff<T, 1>(a, b, images, H, W, sums, s);
+    if (S == 2) return launch_sqdiff<T, 2>(a, b, images, H, W, sums, s);
+    if (S == 3) return launch_sqdiff<T, 3>(a, b, images, H, W, sums, s);
+    return launch_sqdiff<T, 4>(a, b, images, H, W, sums, s);
+}
+}  // extern "C++"
+
+// PSNR (and sse where out_sse is given) of the S components of every image: zero-fill, squared error, finalize.
+// `workspace` holds the images * S sums.
+static int run_psnr(const PlaneSide& a, const PlaneSide& b, int bits, int S, int images, int H, int W, double* out,
+                    unsigned long long* out_sse, void* workspace, hipStream_t s)
+{
+    unsigned long long* sums = (unsigned long long*)workspace;
+    const int planes = images * S;
+    if (int rc = zero_fill_async(sums, (size_t)planes * 8, s)) return rc;
+    if (int rc = bits == 10 ? launch_sqdiff<uint16_t>(S, a, b, images, H, W, sums, s)
+                            : launch_sqdiff<uint8_t>(S, a, b, images, H, W, sums, s))
+        return rc;
+    hipLaunchKernelGGL(psnr_finalize_kernel, dim3((planes + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
+                       bits == 10 ? 1023.0 : 255.0, out, out_sse, planes);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+// SSIM of every image: the tile kernel into the partials behind the workspace's sums, then the finalize.
+// tight: fiunet_ssim_u8's contiguous uint8 batch, both sides {p, H*W, W, 1}: ssim_u8_kernel takes the two pointers
+// and forms that layout from H and W itself.
+static int run_ssim(const PlaneSide& a, const PlaneSide& b, int bits, bool tight, int images, int H, int W,
+                    double* out, void* workspace, hipStream_t s)
+{
+    int tx = 0;
+    const int tiles = ssim_tiles(H, W, &tx);
+    double* partial = (double*)((char*)workspace + align256((size_t)images * 8));
+    const dim3 grid((unsigned)tiles, (unsigned)images);
+    if (bits == 10)
+        hipLaunchKernelGGL(ssim_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)a.p, a.image, a.pitch, a.step,
+                           (const uint16_t*)b.p, b.image, b.pitch, b.step, H, W, tx, partial);
+    else if (tight)
+        hipLaunchKernelGGL(ssim_u8_kernel, grid, dim3(256), 0, s, (const uint8_t*)a.p, (const uint8_t*)b.p, H, W, tx,
+                           partial);
+    else
+        hipLaunchKernelGGL(ssim_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)a.p, a.image, a.pitch, a.step,
+                           (const uint8_t*)b.p, b.image, b.pitch, b.step, H, W, tx, partial);
+    HIP_TRY(hipGetLastError());
+    const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
+    hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
 int fiunet_psnr_u8(const uint8_t* pred, const uint8_t* target, int images, int H, int W, double* out,
                    void* workspace, size_t workspace_bytes, void* stream)
 {
@@ -35,17 +120,9 @@ int fiunet_psnr_u8(const uint8_t* pred, const uint8_t* target, int images, int H
     if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
     if (workspace_bytes < align256((size_t)images * 8)) return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
     const size_t n = (size_t)H * W;
-    if (int rc = zero_fill_async(sums, (size_t)images * 8, s)) return rc;
-    // ~4 x 16 B per thread and at most 128 workgroups (= atomics) per image
-    const unsigned bx = (unsigned)std::min<size_t>((n / 64 + 255) / 256 + 1, 128);
-    hipLaunchKernelGGL(sqdiff_u8_kernel, dim3(bx, (unsigned)images), dim3(256), 0, s, pred, target, n, sums);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(psnr_finalize_kernel, dim3((images + 63) / 64), dim3(64), 0, s, sums, n, out, images);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return run_psnr({pred, n, (size_t)W, 1}, {target, n, (size_t)W, 1}, 8, 1, images, H, W, out, nullptr, workspace,
+                    (hipStream_t)stream);
 }
 
 int fiunet_ssim_u8(const uint8_t* pred, const uint8_t* target, int images, int H, int W, double* out,
@@ -59,17 +136,9 @@ int fiunet_ssim_u8(const uint8_t* pred, const uint8_t* target, int images, int H
     if (workspace_bytes < fiunet_metrics_workspace_bytes(images, H, W))
         return fail(FIUNET_ERR_WORKSPACE, "workspace too small");
     if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
-    hipStream_t s = (hipStream_t)stream;
-    int tx = 0;
-    const int tiles = ssim_tiles(H, W, &tx);
-    double* partial = (double*)((char*)workspace + align256((size_t)images * 8));
-    hipLaunchKernelGGL(ssim_u8_kernel, dim3((unsigned)tiles, (unsigned)images), dim3(256), 0, s, pred, target,
-                       H, W, tx, partial);
-    HIP_TRY(hipGetLastError());
-    const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
-    hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    const size_t n = (size_t)H * W;
+    return run_ssim({pred, n, (size_t)W, 1}, {target, n, (size_t)W, 1}, 8, true, images, H, W, out, workspace,
+                    (hipStream_t)stream);
 }
 
 size_t fiunet_plane_metrics_workspace_bytes(int images, int H, int W)
@@ -110,29 +179,6 @@ static int check_planes(const void* pred, size_t pred_image_stride, size_t pred_
     return FIUNET_OK;
 }
 
-extern "C++" {   // (a template over the sample type, inside this file's extern "C" part)
-template <typename T>
-static int launch_plane_psnr(const void* pred, size_t ps, size_t pp, const void* target, size_t ts, size_t tp,
-                             int images, int H, int W, unsigned long long* sums, hipStream_t s)
-{
-    // a plane whose rows follow each other on both sides is one run of H*W samples, cut into PLANE_SEG pieces
-    // (a multiple of 16 bytes, so every piece of an aligned plane keeps the 16-byte path)
-    const size_t n = (size_t)H * W;
-    const bool flat = pp == (size_t)W && tp == (size_t)W;
-    if (flat && (n + PLANE_SEG - 1) / PLANE_SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
-    const unsigned rows = flat ? (unsigned)((n + PLANE_SEG - 1) / PLANE_SEG) : (unsigned)H;
-    const unsigned w = flat ? (unsigned)PLANE_SEG : (unsigned)W;
-    const unsigned w_last = flat ? (unsigned)(n - (size_t)(rows - 1) * PLANE_SEG) : (unsigned)W;
-    const size_t pa = flat ? (size_t)PLANE_SEG : pp, pb = flat ? (size_t)PLANE_SEG : tp;
-    // one wave per row and step, at most 128 workgroups (= atomics) per image
-    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
-    hipLaunchKernelGGL(plane_sqdiff_kernel<T>, dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)pred, ps, pa,
-                       (const T*)target, ts, pb, rows, w, w_last, sums);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-}  // extern "C++"
-
 int fiunet_plane_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
                       size_t target_image_stride, size_t target_row_pitch, int bits, int images, int H, int W,
                       double* out_psnr, unsigned long long* out_sse, void* workspace, size_t workspace_bytes,
@@ -142,18 +188,8 @@ int fiunet_plane_psnr(const void* pred, size_t pred_image_stride, size_t pred_ro
     if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
                               bits, images, H, W, out_psnr, workspace, workspace_bytes, need))
         return rc;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
-    if (int rc = zero_fill_async(sums, (size_t)images * 8, s)) return rc;
-    if (int rc = bits == 10 ? launch_plane_psnr<uint16_t>(pred, pred_image_stride, pred_row_pitch, target,
-                                                          target_image_stride, target_row_pitch, images, H, W, sums, s)
-                            : launch_plane_psnr<uint8_t>(pred, pred_image_stride, pred_row_pitch, target,
-                                                         target_image_stride, target_row_pitch, images, H, W, sums, s))
-        return rc;
-    hipLaunchKernelGGL(plane_psnr_finalize_kernel, dim3((images + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
-                       bits == 10 ? 1023.0 : 255.0, out_psnr, out_sse, images);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return run_psnr({pred, pred_image_stride, pred_row_pitch, 1}, {target, target_image_stride, target_row_pitch, 1},
+                    bits, 1, images, H, W, out_psnr, out_sse, workspace, (hipStream_t)stream);
 }
 
 int fiunet_stepped_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, int pred_step,
@@ -170,24 +206,9 @@ int fiunet_stepped_ssim(const void* pred, size_t pred_image_stride, size_t pred_
                               bits, images, H, W, out_ssim, workspace, workspace_bytes, need,
                               (size_t)(W - 1) * pred_step + 1, (size_t)(W - 1) * target_step + 1))
         return rc;
-    hipStream_t s = (hipStream_t)stream;
-    int tx = 0;
-    const int tiles = ssim_tiles(H, W, &tx);
-    double* partial = (double*)((char*)workspace + align256((size_t)images * 8));
-    const dim3 grid((unsigned)tiles, (unsigned)images);
-    if (bits == 10)
-        hipLaunchKernelGGL(plane_ssim_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)pred, pred_image_stride,
-                           pred_row_pitch, (unsigned)pred_step, (const uint16_t*)target, target_image_stride,
-                           target_row_pitch, (unsigned)target_step, H, W, tx, partial);
-    else
-        hipLaunchKernelGGL(plane_ssim_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)pred, pred_image_stride,
-                           pred_row_pitch, (unsigned)pred_step, (const uint8_t*)target, target_image_stride,
-                           target_row_pitch, (unsigned)target_step, H, W, tx, partial);
-    HIP_TRY(hipGetLastError());
-    const double count = (double)(H - 2 * SSIM_PAD) * (double)(W - 2 * SSIM_PAD);
-    hipLaunchKernelGGL(ssim_finalize_kernel, dim3((unsigned)images), dim3(256), 0, s, partial, tiles, count, out_ssim);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return run_ssim({pred, pred_image_stride, pred_row_pitch, (unsigned)pred_step},
+                    {target, target_image_stride, target_row_pitch, (unsigned)target_step}, bits, false, images, H,
+                    W, out_ssim, workspace, (hipStream_t)stream);
 }
 
 int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
@@ -198,38 +219,6 @@ int fiunet_plane_ssim(const void* pred, size_t pred_image_stride, size_t pred_ro
                                      target_row_pitch, 1, bits, images, H, W, out_ssim, workspace, workspace_bytes,
                                      stream);
 }
-
-extern "C++" {
-template <typename T, int S>
-static int launch_interleaved_sqdiff(const void* pred, size_t ps, size_t pp, const void* target, size_t ts, size_t tp,
-                                     int images, int H, int W, unsigned long long* sums, hipStream_t s)
-{
-    // rows that follow each other on both sides are one run of H*W*S samples, cut into interleaved_seg(S) pieces (a
-    // multiple of S and of 16 bytes: a piece starts at component 0 and an aligned run keeps the 16-byte path)
-    constexpr size_t SEG = interleaved_seg(S);
-    const size_t row = (size_t)W * S, n = (size_t)H * row;
-    const bool flat = pp == row && tp == row;
-    if (flat && (n + SEG - 1) / SEG > 0xffffffffull) return fail(FIUNET_ERR_INVALID_ARG, "plane too large");
-    const unsigned rows = flat ? (unsigned)((n + SEG - 1) / SEG) : (unsigned)H;
-    const unsigned len = flat ? (unsigned)SEG : (unsigned)row;
-    const unsigned l_last = flat ? (unsigned)(n - (size_t)(rows - 1) * SEG) : (unsigned)row;
-    const size_t pa = flat ? SEG : pp, pb = flat ? SEG : tp;
-    const unsigned bx = std::min<unsigned>((rows + 3) / 4, 128u);
-    hipLaunchKernelGGL((interleaved_sqdiff_kernel<T, S>), dim3(bx, (unsigned)images), dim3(256), 0, s, (const T*)pred, ps,
-                       pa, (const T*)target, ts, pb, rows, len, l_last, sums);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
-}
-
-template <typename T>
-static int launch_interleaved_psnr(int S, const void* pred, size_t ps, size_t pp, const void* target, size_t ts,
-                                   size_t tp, int images, int H, int W, unsigned long long* sums, hipStream_t s)
-{
-    if (S == 2) return launch_interleaved_sqdiff<T, 2>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
-    if (S == 3) return launch_interleaved_sqdiff<T, 3>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
-    return launch_interleaved_sqdiff<T, 4>(pred, ps, pp, target, ts, tp, images, H, W, sums, s);
-}
-}  // extern "C++"
 
 int fiunet_interleaved_psnr(const void* pred, size_t pred_image_stride, size_t pred_row_pitch, const void* target,
                             size_t target_image_stride, size_t target_row_pitch, int bits, int components, int images,
@@ -245,21 +234,8 @@ int fiunet_interleaved_psnr(const void* pred, size_t pred_image_stride, size_t p
     if (int rc = check_planes(pred, pred_image_stride, pred_row_pitch, target, target_image_stride, target_row_pitch,
                               bits, images, H, W, out_psnr, workspace, workspace_bytes, need, row, row))
         return rc;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
-    const int planes = images * components;
-    if (int rc = zero_fill_async(sums, (size_t)planes * 8, s)) return rc;
-    if (int rc = bits == 10 ? launch_interleaved_psnr<uint16_t>(components, pred, pred_image_stride, pred_row_pitch,
-                                                                target, target_image_stride, target_row_pitch, images,
-                                                                H, W, sums, s)
-                            : launch_interleaved_psnr<uint8_t>(components, pred, pred_image_stride, pred_row_pitch,
-                                                               target, target_image_stride, target_row_pitch, images, H,
-                                                               W, sums, s))
-        return rc;
-    hipLaunchKernelGGL(plane_psnr_finalize_kernel, dim3((planes + 63) / 64), dim3(64), 0, s, sums, (size_t)H * W,
-                       bits == 10 ? 1023.0 : 255.0, out_psnr, out_sse, planes);
-    HIP_TRY(hipGetLastError());
-    return FIUNET_OK;
+    return run_psnr({pred, pred_image_stride, pred_row_pitch, 1}, {target, target_image_stride, target_row_pitch, 1},
+                    bits, components, images, H, W, out_psnr, out_sse, workspace, (hipStream_t)stream);
 }
 
 static inline int gssim_tiles(int H, int W, int* tiles_x)

@@ -7,162 +7,28 @@
 // GPU those two host passes (plus the device->host copy of every frame) become the bottleneck of an
 // evaluation run, so both are computed here from the uint8 frames fiunet_forward_u8 leaves in HBM.
 //
-//   sqdiff_u8_kernel / psnr_finalize_kernel : sum (a-b)^2 as an exact 64-bit integer, then
-//                                             10*log10(255^2 / (sum/n)) in fp64
-//   ssim_u8_kernel / ssim_finalize_kernel   : skimage's default SSIM: 7x7 uniform window, sample
-//                                             covariance (49/48), K1 = 0.01, K2 = 0.03, mean over the
-//                                             image minus a 3-pixel border.  Window sums of a, b, a^2,
-//                                             b^2, ab are exact int32; the per-pixel map and its mean
-//                                             are fp64 in a fixed order (deterministic).
+//   sqdiff_kernel / psnr_finalize_kernel : sum (a-b)^2 as an exact 64-bit integer, then
+//                                          10*log10(peak^2 / (sum/n)) in fp64
+//   SSIM_OF_TILE / ssim_finalize_kernel  : skimage's default SSIM: 7x7 uniform window, sample covariance
+//                                          (49/48), K1 = 0.01, K2 = 0.03, data_range = the peak, mean over
+//                                          the image minus a 3-pixel border.  Window sums of a, b, a^2, b^2,
+//                                          ab are exact int32; the per-pixel map and its mean are fp64 in a
+//                                          fixed order (deterministic).
 // Both are HBM-bound (2 bytes read per pixel).
+//
+// Each is written ONCE, over the sample type and the layout, and every metric entry point runs it: the contiguous
+// uint8 batch of the evaluators (fiunet_psnr_u8 / fiunet_ssim_u8) is the tight layout of the planes hold-out scoring
+// (holdout.py) reads where they lie - images `image stride` samples apart, rows `row pitch` samples apart, 8-bit
+// samples (uint8_t, peak 255) or 10-bit codes in 16-bit words (uint16_t, peak 1023; a word above 1023 reads as 1023,
+// as in every 10-bit kernel here, so every sum below stays inside int32).  The evaluators' numbers and the hold-out
+// scorer's are therefore the same to the last bit (tests/test_gpu_metrics_bits.py pins them).  SSIM has two kernels
+// around its one text, because the tight layout's address arithmetic is measurably cheaper (see ssim_u8_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace fiunet {
 
-// grid = (blocks per image, images); `sums` zeroed by the caller.  Integer atomics: exact in any order.
-__global__ __launch_bounds__(256) void sqdiff_u8_kernel(const uint8_t* __restrict__ a,
-                                                        const uint8_t* __restrict__ b, size_t n,
-                                                        unsigned long long* __restrict__ sums)
-{
-    const size_t img = blockIdx.y;
-    const uint8_t* pa = a + img * n;
-    const uint8_t* pb = b + img * n;
-    unsigned long long s = 0;
-    // 16 bytes per lane per step where the image base allows it, bytes otherwise
-    const bool vec = (((uintptr_t)pa | (uintptr_t)pb) & 15) == 0;
-    const size_t nv = vec ? n / 16 : 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (size_t)gridDim.x * 256) {
-        const uint4 va = reinterpret_cast<const uint4*>(pa)[i], vb = reinterpret_cast<const uint4*>(pb)[i];
-        const unsigned wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
-        unsigned acc = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int d = (int)((wa[k] >> (8 * j)) & 255u) - (int)((wb[k] >> (8 * j)) & 255u);
-                acc += (unsigned)(d * d);
-            }
-        s += acc;
-    }
-    for (size_t i = nv * 16 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const int d = (int)pa[i] - (int)pb[i];
-        s += (unsigned)(d * d);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    // one atomic per workgroup (the 8 per-image counters are a serialisation point in L2)
-    __shared__ unsigned long long part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
-        if (t) atomicAdd(sums + img, t);
-    }
-}
-
-__global__ void psnr_finalize_kernel(const unsigned long long* __restrict__ sums, size_t n,
-                                     double* __restrict__ out, int images)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= images) return;
-    const double mse = (double)sums[i] / (double)n;
-    out[i] = sums[i] == 0 ? __longlong_as_double(0x7ff0000000000000LL)  // +inf, as skimage
-                          : 10.0 * log10((255.0 * 255.0) / mse);
-}
-
-constexpr int SSIM_WIN = 7, SSIM_PAD = 3;
-constexpr int SSIM_TX = 64, SSIM_TY = 16;  // output pixels per workgroup
-
-// grid = (tiles_x * tiles_y, images): S over the tile's valid-window pixels, summed in a fixed
-// order into partial[img][tile].
-__global__ __launch_bounds__(256) void ssim_u8_kernel(const uint8_t* __restrict__ a,
-                                                      const uint8_t* __restrict__ b, int H, int W,
-                                                      int tiles_x, double* __restrict__ partial)
-{
-    constexpr int IW = SSIM_TX + SSIM_WIN - 1, IH = SSIM_TY + SSIM_WIN - 1, IWP = IW + 2;
-    __shared__ uint8_t ta[IH * IWP], tb[IH * IWP];
-    __shared__ int hs[5][IH][SSIM_TX];  // horizontal 7-sums of a, b, a^2, b^2, ab
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    const int tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x;
-    const size_t img = blockIdx.y;
-    const uint8_t* pa = a + img * (size_t)H * W;
-    const uint8_t* pb = b + img * (size_t)H * W;
-    // output pixel (oy, ox) of the cropped map <-> window rows oy..oy+6, cols ox..ox+6 of the image
-    const int oy0 = ty * SSIM_TY, ox0 = tx * SSIM_TX;
-    const int OH = H - 2 * SSIM_PAD, OW = W - 2 * SSIM_PAD;
-    for (int i = tid; i < IH * IW; i += 256) {
-        const int r = i / IW, c = i - r * IW;
-        const int y = min(oy0 + r, H - 1), x = min(ox0 + c, W - 1);
-        ta[r * IWP + c] = pa[(size_t)y * W + x];
-        tb[r * IWP + c] = pb[(size_t)y * W + x];
-    }
-    __syncthreads();
-    for (int i = tid; i < IH * SSIM_TX; i += 256) {
-        const int r = i / SSIM_TX, c = i - r * SSIM_TX;
-        int sa = 0, sb = 0, saa = 0, sbb = 0, sab = 0;
-#pragma unroll
-        for (int k = 0; k < SSIM_WIN; ++k) {
-            const int va = ta[r * IWP + c + k], vb = tb[r * IWP + c + k];
-            sa += va; sb += vb; saa += va * va; sbb += vb * vb; sab += va * vb;
-        }
-        hs[0][r][c] = sa; hs[1][r][c] = sb; hs[2][r][c] = saa; hs[3][r][c] = sbb; hs[4][r][c] = sab;
-    }
-    __syncthreads();
-    const double NP = 49.0, cov_norm = NP / (NP - 1.0);
-    const double C1 = (0.01 * 255.0) * (0.01 * 255.0), C2 = (0.03 * 255.0) * (0.03 * 255.0);
-    double acc = 0.0;
-    for (int i = tid; i < SSIM_TY * SSIM_TX; i += 256) {
-        const int r = i / SSIM_TX, c = i - r * SSIM_TX;
-        if (oy0 + r >= OH || ox0 + c >= OW) continue;
-        int s[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < SSIM_WIN; ++k)
-#pragma unroll
-            for (int q = 0; q < 5; ++q) s[q] += hs[q][r + k][c];
-        const double ux = (double)s[0] / NP, uy = (double)s[1] / NP;
-        const double uxx = (double)s[2] / NP, uyy = (double)s[3] / NP, uxy = (double)s[4] / NP;
-        const double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy);
-        const double vxy = cov_norm * (uxy - ux * uy);
-        const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2;
-        const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
-        acc += (A1 * A2) / (B1 * B2);
-    }
-    red[tid] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) partial[img * gridDim.x + tile] = red[0];
-}
-
-// one workgroup per image: fixed-order sum of the tile partials, then the mean
-__global__ __launch_bounds__(256) void ssim_finalize_kernel(const double* __restrict__ partial, int tiles,
-                                                            double count, double* __restrict__ out)
-{
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    const double* p = partial + (size_t)blockIdx.x * tiles;
-    double acc = 0.0;
-    for (int i = tid; i < tiles; i += 256) acc += p[i];
-    red[tid] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) out[blockIdx.x] = red[0] / count;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The same two metrics on planes where they lie (hold-out scoring, holdout.py): images `image stride`
-// samples apart, rows `row pitch` samples apart, 8-bit samples (uint8_t, peak 255) or 10-bit codes in
-// 16-bit words (uint16_t, peak 1023; a word above 1023 reads as 1023, as in every 10-bit kernel here, so
-// every sum below stays inside int32).  One template over the sample type; at uint8_t the arithmetic is
-// that of the two kernels above, statement for statement, so the values are the same to the last bit.
 template <typename T> struct PlaneSample;
 template <> struct PlaneSample<uint8_t> {
     static constexpr int PEAK = 255;
@@ -173,79 +39,16 @@ template <> struct PlaneSample<uint16_t> {
     static __device__ __forceinline__ int get(unsigned v) { return (int)min(v, 1023u); }
 };
 
-constexpr int PLANE_SEG = 4096;  // samples per wave and step of a plane whose rows are contiguous
-
-// sum (a-b)^2 of every sample of one 32-bit word pair
-template <typename T> __device__ __forceinline__ unsigned sqdiff_word(unsigned wa, unsigned wb)
-{
-    constexpr int BITS = 8 * sizeof(T), N = 4 / sizeof(T);
-    constexpr unsigned MASK = (1u << BITS) - 1u;
-    unsigned acc = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const int d = PlaneSample<T>::get((wa >> (BITS * j)) & MASK) - PlaneSample<T>::get((wb >> (BITS * j)) & MASK);
-        acc += (unsigned)(d * d);
-    }
-    return acc;
-}
-
-// grid = (blocks per image, images); `sums` zeroed by the caller.  One wave per row at a time: `rows` rows of
-// `W` samples (the last one `w_last`).  A row whose two base addresses sit at the same offset inside a 16-byte
-// line goes 16 bytes per lane from the first aligned sample on, with a scalar head and tail; any other row
-// (an I420 chroma plane against a contiguous copy, an odd pitch on one side) is read sample by sample.
-template <typename T>
-__global__ __launch_bounds__(256) void plane_sqdiff_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
-                                                           const T* __restrict__ b, size_t b_image, size_t b_pitch,
-                                                           unsigned rows, unsigned W, unsigned w_last,
-                                                           unsigned long long* __restrict__ sums)
-{
-    constexpr unsigned VEC = 16 / sizeof(T);
-    const size_t img = blockIdx.y;
-    const T* ia = a + img * a_image;
-    const T* ib = b + img * b_image;
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long s = 0;
-    for (unsigned r = blockIdx.x * 4 + wave; r < rows; r += gridDim.x * 4) {
-        const T* pa = ia + (size_t)r * a_pitch;
-        const T* pb = ib + (size_t)r * b_pitch;
-        const unsigned len = r + 1 == rows ? w_last : W;
-        const bool same = (((uintptr_t)pa ^ (uintptr_t)pb) & 15) == 0;
-        const unsigned head = same ? min(len, (unsigned)(((16 - ((uintptr_t)pa & 15)) & 15) / sizeof(T))) : len;
-        const unsigned nv = (len - head) / VEC;
-        for (unsigned i = lane; i < head; i += 64) {
-            const int d = PlaneSample<T>::get(pa[i]) - PlaneSample<T>::get(pb[i]);
-            s += (unsigned)(d * d);
-        }
-        const uint4* qa = reinterpret_cast<const uint4*>(pa + head);
-        const uint4* qb = reinterpret_cast<const uint4*>(pb + head);
-        for (unsigned i = lane; i < nv; i += 64) {
-            const uint4 va = qa[i], vb = qb[i];
-            s += sqdiff_word<T>(va.x, vb.x) + sqdiff_word<T>(va.y, vb.y) + sqdiff_word<T>(va.z, vb.z) +
-                 sqdiff_word<T>(va.w, vb.w);
-        }
-        for (unsigned i = head + nv * VEC + lane; i < len; i += 64) {
-            const int d = PlaneSample<T>::get(pa[i]) - PlaneSample<T>::get(pb[i]);
-            s += (unsigned)(d * d);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    __shared__ unsigned long long part[4];
-    if (lane == 0) part[wave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
-        if (t) atomicAdd(sums + img, t);
-    }
-}
-
-// Interleaved rows: a row is W*S samples and the sample at position p belongs to component p % S (U V of NV12,
-// R G B [A] of packed RGB, the byte positions of uyvy422 / yuyv422).  plane_sqdiff_kernel's access pattern - one wave
-// per row at a time, 16 bytes per lane between a scalar head and tail where both row bases share their place in a
-// 16-byte line, sample by sample otherwise - with S sums per lane, so one pass over the bytes gives every component.
-// Where the rows follow each other on both sides the host cuts the run into pieces of interleaved_seg(S) samples, a
-// multiple of S and of 16 bytes: every row and every piece starts at component 0.
-__host__ __device__ constexpr unsigned interleaved_seg(int S) { return S == 3 ? 3072u : (unsigned)PLANE_SEG; }
+// ---------------------------------------------------------------------------------------------------
+// Squared error.  A row is W*S samples and the sample at position p belongs to component p % S: S = 1 is a plane of
+// its own, S = 2..4 interleaved components (U V of NV12, R G B [A] of packed RGB, the byte positions of uyvy422 /
+// yuyv422), with S sums per lane, so one pass over the bytes gives every component.  One wave per row at a time.  A
+// row whose two base addresses sit at the same offset inside a 16-byte line goes 16 bytes per lane from the first
+// aligned sample on, with a scalar head and tail; any other row (an I420 chroma plane against a contiguous copy, an
+// odd pitch on one side) is read sample by sample.  Where the rows follow each other on both sides the host cuts the
+// run into pieces of sqdiff_seg(S) samples, a multiple of S and of 16 bytes: every row and every piece starts at
+// component 0, and every piece of an aligned run keeps the 16-byte path.
+__host__ __device__ constexpr unsigned sqdiff_seg(int S) { return S == 3 ? 3072u : 4096u; }
 
 // (a-b)^2 of sample J of a 16-byte vector pair
 template <typename T, int J> __device__ __forceinline__ unsigned sqdiff_at(const unsigned (&wa)[4], const unsigned (&wb)[4])
@@ -268,12 +71,13 @@ template <typename T, int S> struct VecSlots<T, S, (int)(16 / sizeof(T))> {
     static __device__ __forceinline__ void add(const unsigned (&)[4], const unsigned (&)[4], unsigned (&)[S]) {}
 };
 
-// grid = (blocks per image, images); `sums` [images * S] zeroed by the caller, image-major.
+// grid = (blocks per image, images); `sums` [images * S] zeroed by the caller, image-major.  Integer atomics, one per
+// workgroup and component (the per-image counters are a serialisation point in L2): exact in any order.
 template <typename T, int S>
-__global__ __launch_bounds__(256) void interleaved_sqdiff_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
-                                                                 const T* __restrict__ b, size_t b_image, size_t b_pitch,
-                                                                 unsigned rows, unsigned L, unsigned l_last,
-                                                                 unsigned long long* __restrict__ sums)
+__global__ __launch_bounds__(256) void sqdiff_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
+                                                     const T* __restrict__ b, size_t b_image, size_t b_pitch,
+                                                     unsigned rows, unsigned L, unsigned l_last,
+                                                     unsigned long long* __restrict__ sums)
 {
     constexpr unsigned VEC = 16 / sizeof(T);
     const size_t img = blockIdx.y;
@@ -340,10 +144,9 @@ __global__ __launch_bounds__(256) void interleaved_sqdiff_kernel(const T* __rest
     }
 }
 
-// psnr_finalize_kernel with the peak as an argument; out_sse (may be NULL) receives the integer sums
-__global__ void plane_psnr_finalize_kernel(const unsigned long long* __restrict__ sums, size_t n, double peak,
-                                           double* __restrict__ out, unsigned long long* __restrict__ out_sse,
-                                           int images)
+// one thread per sum; +inf for identical planes, as skimage; out_sse (may be NULL) receives the integer sums
+__global__ void psnr_finalize_kernel(const unsigned long long* __restrict__ sums, size_t n, double peak,
+                                     double* __restrict__ out, unsigned long long* __restrict__ out_sse, int images)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= images) return;
@@ -352,16 +155,95 @@ __global__ void plane_psnr_finalize_kernel(const unsigned long long* __restrict_
     if (out_sse) out_sse[i] = sums[i];
 }
 
-// ssim_u8_kernel on strided planes of either depth: same tiles, same order of every sum.  Sample (y, x) of an image
-// lies at y * pitch + x * step (step 1: a plane of its own; 2..4: one component of interleaved samples, the U of NV12,
-// a byte of packed RGB, the Y of uyvy422).  The step enters the tile load and nothing else.
-template <typename T>
-__global__ __launch_bounds__(256) void plane_ssim_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
-                                                         unsigned a_step, const T* __restrict__ b, size_t b_image,
-                                                         size_t b_pitch, unsigned b_step, int H, int W, int tiles_x,
-                                                         double* __restrict__ partial)
+// ---------------------------------------------------------------------------------------------------
+// SSIM.  A kernel loads its workgroup's tile of both images into LDS, which is all that depends on where the samples
+// lie; the arithmetic is FIUNET_SSIM_OF_TILE, one text for every kernel.
+constexpr int SSIM_WIN = 7, SSIM_PAD = 3;
+constexpr int SSIM_TX = 64, SSIM_TY = 16;  // output pixels per workgroup
+constexpr int SSIM_IW = SSIM_TX + SSIM_WIN - 1, SSIM_IH = SSIM_TY + SSIM_WIN - 1, SSIM_IWP = SSIM_IW + 2;  // the tile
+
+// S over the valid-window pixels of the tile in ta, tb (output pixel (oy, ox) of the cropped map <-> window rows
+// oy..oy+6, cols ox..ox+6 of the image), summed in a fixed order into partial[img][tile]: everything after a kernel's
+// tile load.  It expands in the kernel, on the kernel's own names (ta, tb, hs, red, tid, oy0, ox0, H, W, img, tile,
+// partial), and is not a function on purpose: inlined from one, the same statements compile to other code (another
+// prologue order, six more VGPRs at uint16), and this kernel's time moves by 1 % with as little as that
+// (profiles/metrics_unify_ab.txt).  Expanded in place, every kernel is byte for byte what it was when each carried its
+// own copy (profiles/metrics_unify_kernel_compare.txt), so the speed is unchanged by construction.
+#define FIUNET_SSIM_OF_TILE(T)                                                                                     \
+    const int OH = H - 2 * SSIM_PAD, OW = W - 2 * SSIM_PAD;                                                        \
+    __syncthreads();                                                                                               \
+    for (int i = tid; i < IH * SSIM_TX; i += 256) {                                                                \
+        const int r = i / SSIM_TX, c = i - r * SSIM_TX;                                                            \
+        int sa = 0, sb = 0, saa = 0, sbb = 0, sab = 0;                                                             \
+        _Pragma("unroll") for (int k = 0; k < SSIM_WIN; ++k) {                                                     \
+            const int va = ta[r * IWP + c + k], vb = tb[r * IWP + c + k];                                          \
+            sa += va; sb += vb; saa += va * va; sbb += vb * vb; sab += va * vb;                                    \
+        }                                                                                                          \
+        hs[0][r][c] = sa; hs[1][r][c] = sb; hs[2][r][c] = saa; hs[3][r][c] = sbb; hs[4][r][c] = sab;               \
+    }                                                                                                              \
+    __syncthreads();                                                                                               \
+    constexpr double PEAK = (double)PlaneSample<T>::PEAK;                                                          \
+    const double NP = 49.0, cov_norm = NP / (NP - 1.0);                                                            \
+    const double C1 = (0.01 * PEAK) * (0.01 * PEAK), C2 = (0.03 * PEAK) * (0.03 * PEAK);                           \
+    double acc = 0.0;                                                                                              \
+    for (int i = tid; i < SSIM_TY * SSIM_TX; i += 256) {                                                           \
+        const int r = i / SSIM_TX, c = i - r * SSIM_TX;                                                            \
+        if (oy0 + r >= OH || ox0 + c >= OW) continue;                                                              \
+        int s[5] = {0, 0, 0, 0, 0}; /* <= 49 * 1023^2 = 51,279,921 */                                              \
+        _Pragma("unroll") for (int k = 0; k < SSIM_WIN; ++k)                                                       \
+            _Pragma("unroll") for (int q = 0; q < 5; ++q) s[q] += hs[q][r + k][c];                                 \
+        const double ux = (double)s[0] / NP, uy = (double)s[1] / NP;                                               \
+        const double uxx = (double)s[2] / NP, uyy = (double)s[3] / NP, uxy = (double)s[4] / NP;                    \
+        const double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy);                             \
+        const double vxy = cov_norm * (uxy - ux * uy);                                                             \
+        const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2;                                                 \
+        const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;                                               \
+        acc += (A1 * A2) / (B1 * B2);                                                                              \
+    }                                                                                                              \
+    red[tid] = acc;                                                                                                \
+    __syncthreads();                                                                                               \
+    for (int o = 128; o > 0; o >>= 1) {                                                                            \
+        if (tid < o) red[tid] += red[tid + o];                                                                     \
+        __syncthreads();                                                                                           \
+    }                                                                                                              \
+    if (tid == 0) partial[img * gridDim.x + tile] = red[0];
+
+// The evaluators' contiguous uint8 batch: images of H rows of W samples, one after the other.  grid = (tiles_x *
+// tiles_y, images) -> partial[img][tile].  A kernel of its own because one 32 x 32-bit row offset shared by both sides
+// is measurably cheaper in the tile load than two 64-bit pitches and two steps: fiunet_ssim_u8 through
+// ssim_kernel<uint8_t> took 2.5 % longer (profiles/metrics_unify_ab.txt).
+__global__ __launch_bounds__(256) void ssim_u8_kernel(const uint8_t* __restrict__ a,
+                                                      const uint8_t* __restrict__ b, int H, int W,
+                                                      int tiles_x, double* __restrict__ partial)
 {
-    constexpr int IW = SSIM_TX + SSIM_WIN - 1, IH = SSIM_TY + SSIM_WIN - 1, IWP = IW + 2;
+    constexpr int IW = SSIM_IW, IH = SSIM_IH, IWP = SSIM_IWP;
+    __shared__ uint8_t ta[IH * IWP], tb[IH * IWP];
+    __shared__ int hs[5][IH][SSIM_TX];  // horizontal 7-sums of a, b, a^2, b^2, ab
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x;
+    const size_t img = blockIdx.y;
+    const uint8_t* pa = a + img * (size_t)H * W;
+    const uint8_t* pb = b + img * (size_t)H * W;
+    const int oy0 = ty * SSIM_TY, ox0 = tx * SSIM_TX;
+    for (int i = tid; i < IH * IW; i += 256) {
+        const int r = i / IW, c = i - r * IW;
+        const int y = min(oy0 + r, H - 1), x = min(ox0 + c, W - 1);
+        ta[r * IWP + c] = pa[(size_t)y * W + x];
+        tb[r * IWP + c] = pb[(size_t)y * W + x];
+    }
+    FIUNET_SSIM_OF_TILE(uint8_t)
+}
+
+// Planes where they lie, either depth, same grid: sample (y, x) of an image lies at y * pitch + x * step (step 1: a
+// plane of its own; 2..4: one component of interleaved samples, the U of NV12, a byte of packed RGB, the Y of uyvy422).
+template <typename T>
+__global__ __launch_bounds__(256) void ssim_kernel(const T* __restrict__ a, size_t a_image, size_t a_pitch,
+                                                   unsigned a_step, const T* __restrict__ b, size_t b_image,
+                                                   size_t b_pitch, unsigned b_step, int H, int W, int tiles_x,
+                                                   double* __restrict__ partial)
+{
+    constexpr int IW = SSIM_IW, IH = SSIM_IH, IWP = SSIM_IWP;
     __shared__ T ta[IH * IWP], tb[IH * IWP];
     __shared__ int hs[5][IH][SSIM_TX];  // horizontal 7-sums of a, b, a^2, b^2, ab (<= 7 * 1023^2)
     __shared__ double red[256];
@@ -371,54 +253,33 @@ __global__ __launch_bounds__(256) void plane_ssim_kernel(const T* __restrict__ a
     const T* pa = a + img * a_image;
     const T* pb = b + img * b_image;
     const int oy0 = ty * SSIM_TY, ox0 = tx * SSIM_TX;
-    const int OH = H - 2 * SSIM_PAD, OW = W - 2 * SSIM_PAD;
     for (int i = tid; i < IH * IW; i += 256) {
         const int r = i / IW, c = i - r * IW;
         const int y = min(oy0 + r, H - 1), x = min(ox0 + c, W - 1);
         ta[r * IWP + c] = (T)PlaneSample<T>::get(pa[(size_t)y * a_pitch + (size_t)x * a_step]);
         tb[r * IWP + c] = (T)PlaneSample<T>::get(pb[(size_t)y * b_pitch + (size_t)x * b_step]);
     }
-    __syncthreads();
-    for (int i = tid; i < IH * SSIM_TX; i += 256) {
-        const int r = i / SSIM_TX, c = i - r * SSIM_TX;
-        int sa = 0, sb = 0, saa = 0, sbb = 0, sab = 0;
-#pragma unroll
-        for (int k = 0; k < SSIM_WIN; ++k) {
-            const int va = ta[r * IWP + c + k], vb = tb[r * IWP + c + k];
-            sa += va; sb += vb; saa += va * va; sbb += vb * vb; sab += va * vb;
-        }
-        hs[0][r][c] = sa; hs[1][r][c] = sb; hs[2][r][c] = saa; hs[3][r][c] = sbb; hs[4][r][c] = sab;
-    }
-    __syncthreads();
-    constexpr double PEAK = (double)PlaneSample<T>::PEAK;
-    const double NP = 49.0, cov_norm = NP / (NP - 1.0);
-    const double C1 = (0.01 * PEAK) * (0.01 * PEAK), C2 = (0.03 * PEAK) * (0.03 * PEAK);
+    FIUNET_SSIM_OF_TILE(T)
+}
+#undef FIUNET_SSIM_OF_TILE
+
+// one workgroup per image: fixed-order sum of the tile partials, then the mean
+__global__ __launch_bounds__(256) void ssim_finalize_kernel(const double* __restrict__ partial, int tiles,
+                                                            double count, double* __restrict__ out)
+{
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const double* p = partial + (size_t)blockIdx.x * tiles;
     double acc = 0.0;
-    for (int i = tid; i < SSIM_TY * SSIM_TX; i += 256) {
-        const int r = i / SSIM_TX, c = i - r * SSIM_TX;
-        if (oy0 + r >= OH || ox0 + c >= OW) continue;
-        int s[5] = {0, 0, 0, 0, 0};  // <= 49 * 1023^2 = 51,279,921
-#pragma unroll
-        for (int k = 0; k < SSIM_WIN; ++k)
-#pragma unroll
-            for (int q = 0; q < 5; ++q) s[q] += hs[q][r + k][c];
-        const double ux = (double)s[0] / NP, uy = (double)s[1] / NP;
-        const double uxx = (double)s[2] / NP, uyy = (double)s[3] / NP, uxy = (double)s[4] / NP;
-        const double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy);
-        const double vxy = cov_norm * (uxy - ux * uy);
-        const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2;
-        const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
-        acc += (A1 * A2) / (B1 * B2);
-    }
+    for (int i = tid; i < tiles; i += 256) acc += p[i];
     red[tid] = acc;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (tid < o) red[tid] += red[tid + o];
         __syncthreads();
     }
-    if (tid == 0) partial[img * gridDim.x + tile] = red[0];
+    if (tid == 0) out[blockIdx.x] = red[0] / count;
 }
-
 
 // ---------------------------------------------------------------------------------------------------
 // Gaussian-window SSIM of the training loss (/root/reference/model/train.py:18-73, SSIMLoss._ssim):

@@ -20,7 +20,7 @@
 //                            needs no host round trip.  grid = (kHoldBlocks * (factor - 1), intervals).
 //
 // All three are HBM-bound.  The sums are integer atomics, one per workgroup, so the result is exact in any order
-// (as sqdiff_u8_kernel in metrics.hip.h).  The library is built with -ffp-contract=off, so the multiply and the two
+// (as sqdiff_kernel in metrics.hip.h).  The library is built with -ffp-contract=off, so the multiply and the two
 // divisions of mafd are separate IEEE operations (v_mul_f64 and the div_scale / div_fmas / div_fixup sequence).
 #pragma once
 #include <hip/hip_runtime.h>

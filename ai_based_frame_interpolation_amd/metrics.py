@@ -63,6 +63,17 @@ def ssim_u8(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _run("fiunet_ssim_u8", pred, target)
 
 
+def _image_stride(t: torch.Tensor, name: str, tail: int, image: int) -> int:
+    """The one stride the dimensions before the last `tail` advance by; `image` samples where there is one image."""
+    st = t.stride()
+    lead = [(n, s) for n, s in zip(t.shape[:-tail], st[:-tail]) if n != 1]
+    for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
+        if s0 != s1 * n1:
+            raise ValueError(f"{name}: the leading dimensions must advance by one stride (shape {tuple(t.shape)}, "
+                             f"strides {tuple(st)})")
+    return lead[-1][1] if lead else image
+
+
 def _stepped_layout(t: torch.Tensor, name: str, max_step: int):
     """[..., H, W] -> (image stride, row pitch, sample step) in samples, as the tensor lies: no copy.  The leading
     dimensions must advance by one stride (a stack, every second frame of one, channel c of [N, C, H, W], a slice of
@@ -75,12 +86,7 @@ def _stepped_layout(t: torch.Tensor, name: str, max_step: int):
                          f"(strides {tuple(st)})")
     row = (w - 1) * step + 1
     pitch = st[-2] if h > 1 else row
-    lead = [(n, s) for n, s in zip(t.shape[:-2], st[:-2]) if n != 1]
-    for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
-        if s0 != s1 * n1:
-            raise ValueError(f"{name}: the leading dimensions must advance by one stride (shape {tuple(t.shape)}, "
-                             f"strides {tuple(st)})")
-    return (lead[-1][1] if lead else (h - 1) * pitch + row), pitch, step
+    return _image_stride(t, name, 2, (h - 1) * pitch + row), pitch, step
 
 
 def _plane_layout(t: torch.Tensor, name: str):
@@ -110,11 +116,25 @@ def _plane_args(pred: torch.Tensor, target: torch.Tensor, bits: int, max_step: i
     return n, h, w, _stepped_layout(pred, "pred", max_step), _stepped_layout(target, "target", max_step)
 
 
-def _plane_workspace(n, h, w, device):
-    nbytes = _native.lib().fiunet_plane_metrics_workspace_bytes(n, h, w)
-    if nbytes == 0:
-        _native.check(1, "fiunet_plane_metrics_workspace_bytes")
-    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+def _plane_call(fn_name: str, args: tuple, count: int, h: int, w: int, device, *, takes_sse: bool,
+                want_sse: bool = False):
+    """What every plane metric ends in: `count` float64 results, the workspace, the current stream and the call
+    `fn_name(*args, out, [sse,] workspace, bytes, stream)`.  takes_sse: the entry point has an sse pointer; want_sse: it
+    gets `count` int64 sums to fill (NULL otherwise).  -> (out, sums or None)"""
+    out = torch.empty(count, dtype=torch.float64, device=device)
+    sums = torch.empty(count, dtype=torch.int64, device=device) if want_sse else None
+    if count:
+        L = _native.lib()
+        nbytes = L.fiunet_plane_metrics_workspace_bytes(count, h, w)
+        if nbytes == 0:
+            _native.check(1, "fiunet_plane_metrics_workspace_bytes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        sse_arg = (None if sums is None else sums.data_ptr(),) if takes_sse else ()
+        with torch.cuda.device(device):
+            s = torch.cuda.current_stream(device).cuda_stream
+            _native.check(getattr(L, fn_name)(*args, out.data_ptr(), *sse_arg, ws.data_ptr(), ctypes.c_size_t(nbytes),
+                                              s), fn_name)
+    return out, sums
 
 
 def psnr_planes(pred: torch.Tensor, target: torch.Tensor, bits: int, *, return_sse: bool = False):
@@ -125,15 +145,8 @@ def psnr_planes(pred: torch.Tensor, target: torch.Tensor, bits: int, *, return_s
     library's uint64)."""
     n, h, w, (ps, pp, _), (ts, tp, _) = _plane_args(pred, target, bits)
     lead = pred.shape[:-2]
-    out = torch.empty(n, dtype=torch.float64, device=pred.device)
-    sse = torch.empty(n, dtype=torch.int64, device=pred.device) if return_sse else None
-    if n:
-        ws, nbytes = _plane_workspace(n, h, w, pred.device)
-        with torch.cuda.device(pred.device):
-            s = torch.cuda.current_stream(pred.device).cuda_stream
-            _native.check(_native.lib().fiunet_plane_psnr(
-                pred.data_ptr(), ps, pp, target.data_ptr(), ts, tp, bits, n, h, w, out.data_ptr(),
-                None if sse is None else sse.data_ptr(), ws.data_ptr(), ctypes.c_size_t(nbytes), s), "fiunet_plane_psnr")
+    out, sse = _plane_call("fiunet_plane_psnr", (pred.data_ptr(), ps, pp, target.data_ptr(), ts, tp, bits, n, h, w),
+                           n, h, w, pred.device, takes_sse=True, want_sse=bool(return_sse))
     return (out.view(lead), sse.view(lead)) if return_sse else out.view(lead)
 
 
@@ -145,12 +158,7 @@ def _interleaved_layout(t: torch.Tensor, name: str):
         raise ValueError(f"{name}: interleaved samples have stride 1 in the last dimension and S = {comp} in the one "
                          f"before it (strides {tuple(st)})")
     pitch = st[-3] if h > 1 else w * comp
-    lead = [(n, s) for n, s in zip(t.shape[:-3], st[:-3]) if n != 1]
-    for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
-        if s0 != s1 * n1:
-            raise ValueError(f"{name}: the leading dimensions must advance by one stride (shape {tuple(t.shape)}, "
-                             f"strides {tuple(st)})")
-    return (lead[-1][1] if lead else (h - 1) * pitch + w * comp), pitch
+    return _image_stride(t, name, 3, (h - 1) * pitch + w * comp), pitch
 
 
 def psnr_interleaved(pred: torch.Tensor, target: torch.Tensor, bits: int, *, return_sse: bool = False):
@@ -168,16 +176,9 @@ def psnr_interleaved(pred: torch.Tensor, target: torch.Tensor, bits: int, *, ret
     n = pred.numel() // (h * w * comp)
     (ps, pp), (ts, tp) = _interleaved_layout(pred, "pred"), _interleaved_layout(target, "target")
     lead = pred.shape[:-3] + (comp,)
-    out = torch.empty(n * comp, dtype=torch.float64, device=pred.device)
-    sse = torch.empty(n * comp, dtype=torch.int64, device=pred.device) if return_sse else None
-    if n:
-        ws, nbytes = _plane_workspace(n * comp, h, w, pred.device)
-        with torch.cuda.device(pred.device):
-            s = torch.cuda.current_stream(pred.device).cuda_stream
-            _native.check(_native.lib().fiunet_interleaved_psnr(
-                pred.data_ptr(), ps, pp, target.data_ptr(), ts, tp, bits, comp, n, h, w, out.data_ptr(),
-                None if sse is None else sse.data_ptr(), ws.data_ptr(), ctypes.c_size_t(nbytes), s),
-                "fiunet_interleaved_psnr")
+    out, sse = _plane_call("fiunet_interleaved_psnr",
+                           (pred.data_ptr(), ps, pp, target.data_ptr(), ts, tp, bits, comp, n, h, w),
+                           n * comp, h, w, pred.device, takes_sse=True, want_sse=bool(return_sse))
     return (out.view(lead), sse.view(lead)) if return_sse else out.view(lead)
 
 
@@ -188,14 +189,9 @@ def ssim_planes(pred: torch.Tensor, target: torch.Tensor, bits: int) -> torch.Te
     n, h, w, (ps, pp, pstep), (ts, tp, tstep) = _plane_args(pred, target, bits, max_step=4)
     if h < 7 or w < 7:
         raise ValueError(f"SSIM: the 7x7 window exceeds the {h}x{w} plane")
-    out = torch.empty(n, dtype=torch.float64, device=pred.device)
-    if n:
-        ws, nbytes = _plane_workspace(n, h, w, pred.device)
-        with torch.cuda.device(pred.device):
-            s = torch.cuda.current_stream(pred.device).cuda_stream
-            _native.check(_native.lib().fiunet_stepped_ssim(
-                pred.data_ptr(), ps, pp, pstep, target.data_ptr(), ts, tp, tstep, bits, n, h, w, out.data_ptr(),
-                ws.data_ptr(), ctypes.c_size_t(nbytes), s), "fiunet_stepped_ssim")
+    out, _ = _plane_call("fiunet_stepped_ssim",
+                         (pred.data_ptr(), ps, pp, pstep, target.data_ptr(), ts, tp, tstep, bits, n, h, w),
+                         n, h, w, pred.device, takes_sse=False)
     return out.view(pred.shape[:-2])
 
 
