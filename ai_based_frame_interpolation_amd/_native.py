@@ -85,9 +85,12 @@ class RetimeEntry(ctypes.Structure):
 
 class ResizePlane(ctypes.Structure):
     """include/fiunet.h: fiunet_resize_plane (sample (y, x) of frame f at offset + f * frame_stride + y * pitch + x *
-    step, everything in samples)."""
+    step, everything in samples; filter: RESIZE_LINEAR / RESIZE_AREA in a destination plane, 0 in a source plane)."""
     _fields_ = [("offset", ctypes.c_size_t), ("pitch", ctypes.c_size_t), ("frame_stride", ctypes.c_size_t),
-                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("step", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("step", ctypes.c_int32), ("filter", ctypes.c_int32)]
+
+
+RESIZE_LINEAR, RESIZE_AREA = 0, 1   # include/fiunet.h: fiunet_resize_filter
 
 
 class PackedLayout(ctypes.Structure):
@@ -728,14 +731,17 @@ def pair_peak(frames: "torch.Tensor", peaks: "torch.Tensor", bits: int) -> None:
     check(fn(frames.data_ptr(), n, fs, peaks.data_ptr(), s), "fiunet_pair_peak_" + ("p10" if bits == 10 else "u8"))
 
 
-def resize_plane_array(planes):
+def resize_plane_array(planes, filter: int = 0):
     """A sequence of (offset, h, w, pitch, step, frame_stride) int tuples, in samples -> the C array of
-    fiunet_resize_plane.  ValueError on a value that does not fit its field (the library checks the rest)."""
+    fiunet_resize_plane, every one with `filter` in its filter member (the library reads it from destination planes;
+    source planes carry 0).  ValueError on a value that does not fit its field (the library checks the rest)."""
     arr = (ResizePlane * max(len(planes), 1))()
+    if not -(1 << 31) <= filter < 1 << 31:
+        raise ValueError(f"filter = {filter} does not fit fiunet_resize_plane")
     for k, (off, h, w, pitch, step, fs) in enumerate(planes):
         if not all(0 <= v < 1 << 64 for v in (off, pitch, fs)) or not all(-(1 << 31) <= v < 1 << 31 for v in (h, w, step)):
             raise ValueError(f"plane {k} = {(off, h, w, pitch, step, fs)} does not fit fiunet_resize_plane")
-        arr[k] = ResizePlane(off, pitch, fs, h, w, step, 0)
+        arr[k] = ResizePlane(off, pitch, fs, h, w, step, filter)
     return arr
 
 
@@ -747,10 +753,11 @@ def _resize_extent(planes, n_frames: int) -> int:
 
 
 def resize_planes(src: "torch.Tensor", src_planes, dst: "torch.Tensor", dst_planes, n_frames: int, bits: int,
-                  stream=None) -> None:
+                  stream=None, filter: int = 0) -> None:
     """fiunet_resize_planes_u8 / fiunet_resize_planes_p10: plane i of `src_planes` of every one of n_frames frames of the
     dense buffer `src` (uint8 at 8 bits; 16-bit words at 10) -> plane i of `dst_planes` of `dst`.  A plane is (offset, h,
-    w, pitch, step, frame_stride) in samples from the tensor's first element.  ValueError, before the call, where well-
+    w, pitch, step, frame_stride) in samples from the tensor's first element; filter: RESIZE_LINEAR (0) or RESIZE_AREA,
+    carried by every destination plane (the library refuses any other value).  ValueError, before the call, where well-
     formed planes reach past either tensor."""
     src_planes, dst_planes = [tuple(int(v) for v in p) for p in src_planes], [tuple(int(v) for v in p) for p in dst_planes]
     if len(src_planes) != len(dst_planes):
@@ -761,7 +768,7 @@ def resize_planes(src: "torch.Tensor", src_planes, dst: "torch.Tensor", dst_plan
         if all(min(p) >= 0 and p[1] >= 1 and p[2] >= 1 for p in planes) and _resize_extent(planes, n_frames) > t.numel():
             raise ValueError(f"the {name} planes reach sample {_resize_extent(planes, n_frames)} of a buffer of {t.numel()}")
     fn = lib().fiunet_resize_planes_p10 if bits == 10 else lib().fiunet_resize_planes_u8
-    check(fn(src.data_ptr(), resize_plane_array(src_planes), dst.data_ptr(), resize_plane_array(dst_planes),
+    check(fn(src.data_ptr(), resize_plane_array(src_planes), dst.data_ptr(), resize_plane_array(dst_planes, int(filter)),
              len(src_planes), n_frames, _stream(src, stream)), "fiunet_resize_planes_" + ("p10" if bits == 10 else "u8"))
 
 

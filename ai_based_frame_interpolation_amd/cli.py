@@ -61,8 +61,12 @@ the held-out frames next to a hard cut out of the summary:
 `--resize WIDTHxHEIGHT` on either command resizes every frame on the GPU right after its upload (resize.py, DESIGN.md
 3.3q): `video` then writes a clip of that size, `evaluate` scores the checkpoint at that size - 256x256 is what the
 reference trains and evaluates at - and says so in its table.  --size stays the size of the --raw source.
+`--resize-filter area` (with --resize) down-scales without aliasing: every sample is the rounded mean of the source area
+it covers; the default, linear, is the two-tap filter of the reference's cv2.resize.
 
     python -m ai_based_frame_interpolation_amd.cli evaluate --input clip.y4m --resize 256x256 --model best_model.pth
+    python -m ai_based_frame_interpolation_amd.cli video --input uhd.y4m --output hd.y4m --resize 1920x1080 \
+        --resize-filter area --model rgb_model.pth
 """
 from __future__ import annotations
 
@@ -168,6 +172,9 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--resize", type=_size, default=None, metavar="WIDTHxHEIGHT",
                    help="Resize every frame on the GPU before it is interpolated; the output has this size (--size "
                         "stays the size of the --raw source)")
+    v.add_argument("--resize-filter", default=None, choices=("linear", "area"),
+                   help="Filter of --resize: linear (default; cv2.resize's two taps per axis) or area (alias-free "
+                        "down-scaling: the mean of the covered source area)")
     e = sub.add_parser("evaluate", help="Score a checkpoint on a clip by hold-out (Y4M, .npy or --raw; '-' is stdin)")
     e.add_argument("--input", required=True,
                    help="Clip to score: a .y4m or .npy path, or - for standard input (Y4M, or --raw video)")
@@ -193,6 +200,9 @@ def parser() -> argparse.ArgumentParser:
     e.add_argument("--resize", type=_size, default=None, metavar="WIDTHxHEIGHT",
                    help="Resize the clip on the GPU before frames are held out and score it at this size, such as the "
                         "256x256 a checkpoint was trained at (--size stays the size of the --raw source)")
+    e.add_argument("--resize-filter", default=None, choices=("linear", "area"),
+                   help="Filter of --resize: linear (default; cv2.resize's two taps per axis) or area (alias-free "
+                        "down-scaling: the mean of the covered source area)")
     e.add_argument("--scene-cut", type=_scene_cut, default=None,
                    help="Scene-cut threshold in (0, 100], or none: held-out frames next to a cut are left out of the "
                         "summary")
@@ -206,6 +216,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     a = ap.parse_args(argv)
     if a.chunk_frames is None:
         a.chunk_frames = 4 * a.batch
+    if a.command in ("evaluate", "video"):
+        if a.resize_filter is not None and a.resize is None:
+            ap.error("--resize-filter names the filter of --resize WIDTHxHEIGHT")
+        a.resize_filter = a.resize_filter or "linear"
     if a.command == "evaluate":
         if a.raw is not None and a.size is None:
             ap.error("--raw needs --size WIDTHxHEIGHT (raw video has no header)")
@@ -246,7 +260,7 @@ def run_video(a: argparse.Namespace) -> int:
                              chunk_frames=a.chunk_frames, fps=a.fps, src_fps=a.src_fps, time_depth=a.time_depth,
                              retime=a.retime, raw=a.raw, width=a.size[0] if a.size else None,
                              height=a.size[1] if a.size else None, dedup=a.dedup, max_gap=a.max_gap,
-                             resize=a.resize, **logs)
+                             resize=a.resize, resize_filter=a.resize_filter, **logs)
     if a.dedup is not None:
         print(f"re-timed {retimed_repeats(logs['dedup_log'], logs['scene_log'], a.max_gap)} repeated frames",
               file=sys.stderr)
@@ -268,7 +282,7 @@ def run_evaluate(a: argparse.Namespace) -> dict:
     res = holdout.score_video(model, src, triplets=a.triplets, methods=a.methods, batch=a.batch,
                               chunk_frames=a.chunk_frames, matrix=a.matrix, siting=a.siting, src_fps=a.src_fps,
                               raw=a.raw, width=a.size[0] if a.size else None, height=a.size[1] if a.size else None,
-                              scene_cut=a.scene_cut, resize=a.resize)
+                              scene_cut=a.scene_cut, resize=a.resize, resize_filter=a.resize_filter)
     print(holdout.summary_table(res), file=sys.stderr)
     if a.json:
         with open(a.json, "w") as f:

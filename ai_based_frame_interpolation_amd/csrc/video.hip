@@ -239,7 +239,18 @@ static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, co
     if (n_planes < 1 || n_planes > kResizeMaxPlanes) return fail(FIUNET_ERR_INVALID_ARG, "n_planes must be 1..4");
     if (n_frames < 0) return fail(FIUNET_ERR_INVALID_ARG, "n_frames < 0");
     constexpr int V = ResizeSample<T>::kVec;
-    ResizeArgs base = {};
+    // the filter is the destination planes' (they agree); a source plane carries 0
+    const int filter = dp[0].filter;
+    for (int i = 0; i < n_planes; ++i) {
+        if (sp[i].filter != 0) return fail(FIUNET_ERR_INVALID_ARG, "a source plane's filter must be 0");
+        if (dp[i].filter != FIUNET_RESIZE_LINEAR && dp[i].filter != FIUNET_RESIZE_AREA)
+            return fail(FIUNET_ERR_INVALID_ARG, "a destination plane's filter must be FIUNET_RESIZE_LINEAR or FIUNET_RESIZE_AREA");
+        if (dp[i].filter != filter) return fail(FIUNET_ERR_INVALID_ARG, "the destination planes of one call must name one filter");
+    }
+    // the planes of a launch: the linear kernel's (under the area filter, the planes of equal size: its copy) and the
+    // area kernel's
+    ResizeArgs base[2] = {};
+    int count[2] = {0, 0};
     unsigned long long per_frame_max = 0;
     for (int i = 0; i < n_planes; ++i) {
         for (const fiunet_resize_plane* p : {&sp[i], &dp[i]}) {
@@ -248,13 +259,23 @@ static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, co
             if (n_frames > 1 && p->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_frames)
                 return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
         }
-        ResizePlane& P = base.p[i];
+        const bool equal = sp[i].h == dp[i].h && sp[i].w == dp[i].w;
+        if (filter == FIUNET_RESIZE_AREA) {
+            if (dp[i].w > sp[i].w || dp[i].h > sp[i].h)
+                return fail(FIUNET_ERR_INVALID_ARG, "the area filter only down-scales a plane: use the linear filter to enlarge");
+            if ((long long)sp[i].w > (long long)kResizeAreaMaxRatio * dp[i].w ||
+                (long long)sp[i].h > (long long)kResizeAreaMaxRatio * dp[i].h)
+                return fail(FIUNET_ERR_UNSUPPORTED, "the area filter covers ratios up to 64 on either axis");
+        }
+        const int which = filter == FIUNET_RESIZE_AREA && !equal ? 1 : 0;
+        ResizePlane& P = base[which].p[count[which]++];
         P.src_off = sp[i].offset, P.src_pitch = sp[i].pitch, P.src_fs = sp[i].frame_stride;
         P.dst_off = dp[i].offset, P.dst_pitch = dp[i].pitch, P.dst_fs = dp[i].frame_stride;
         P.sh = sp[i].h, P.sw = sp[i].w, P.dh = dp[i].h, P.dw = dp[i].w;
         P.sstep = sp[i].step, P.dstep = dp[i].step;
         P.sx = (double)P.sw / (double)P.dw, P.sy = (double)P.sh / (double)P.dh;
         P.chunks = (unsigned)((P.dw + V - 1) / V) + (P.dstep == 1 ? 1u : 0u);
+        P.inv_dw = 1.0 / (double)P.dw, P.inv_dh = 1.0 / (double)P.dh, P.inv_chunks = 1.0 / (double)P.chunks;
         const unsigned long long per_frame = (unsigned long long)P.dh * P.chunks;
         if (per_frame >= (1ull << 31)) return fail(FIUNET_ERR_UNSUPPORTED, "a destination plane of 2^31 or more store chunks");
         per_frame_max = std::max(per_frame_max, per_frame);
@@ -270,19 +291,30 @@ static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, co
     const int batch = (int)std::min<unsigned long long>(((1ull << 31) - 1) / per_frame_max, (unsigned long long)n_frames);
     for (int f0 = 0; f0 < n_frames; f0 += batch) {
         const int nf = std::min(batch, n_frames - f0);
-        ResizeArgs args = base;
-        unsigned items_max = 0;
-        for (int i = 0; i < n_planes; ++i) {
-            ResizePlane& P = args.p[i];
-            P.src_off += (size_t)f0 * P.src_fs, P.dst_off += (size_t)f0 * P.dst_fs;
-            P.items = (unsigned)nf * (unsigned)P.dh * P.chunks;
-            items_max = std::max(items_max, P.items);
+        for (int which = 0; which < 2; ++which) {
+            if (!count[which]) continue;
+            ResizeArgs args = base[which];
+            unsigned items_max = 0;
+            for (int i = 0; i < count[which]; ++i) {
+                ResizePlane& P = args.p[i];
+                P.src_off += (size_t)f0 * P.src_fs, P.dst_off += (size_t)f0 * P.dst_fs;
+                P.items = (unsigned)nf * (unsigned)P.dh * P.chunks;
+                items_max = std::max(items_max, P.items);
+            }
+            if (which == 0) {
+                // one item per thread up to 8192 workgroups (32 per CU), a grid-stride loop beyond
+                const unsigned bx = std::min((items_max + kResizeBlock - 1) / kResizeBlock, 8192u);
+                hipLaunchKernelGGL(resize_planes_kernel<T>, dim3(bx, (unsigned)count[0]), dim3(kResizeBlock), 0,
+                                   (hipStream_t)stream, src, dst, args);
+            } else {
+                // kVec lanes per item: kResizeBlock / kVec items per workgroup, up to 65536 workgroups
+                constexpr unsigned per_wg = kResizeBlock / V;
+                const unsigned bx = std::min((items_max + per_wg - 1) / per_wg, 65536u);
+                hipLaunchKernelGGL(resize_area_kernel<T>, dim3(bx, (unsigned)count[1]), dim3(kResizeBlock), 0,
+                                   (hipStream_t)stream, src, dst, args);
+            }
+            HIP_TRY(hipGetLastError());
         }
-        // one item per thread up to 8192 workgroups (32 per CU), a grid-stride loop beyond
-        const unsigned bx = std::min((items_max + kResizeBlock - 1) / kResizeBlock, 8192u);
-        hipLaunchKernelGGL(resize_planes_kernel<T>, dim3(bx, (unsigned)n_planes), dim3(kResizeBlock), 0,
-                           (hipStream_t)stream, src, dst, args);
-        HIP_TRY(hipGetLastError());
     }
     return FIUNET_OK;
 }

@@ -169,14 +169,14 @@ def raw_planes(raw: str, height: int, width: int):
     return [("y", 0, h, w, w, 1), ("u", h * w, h, cw, cw, 1), ("v", h * w + h * cw, h, cw, cw, 1)], []
 
 
-def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size=None) -> _Source:
+def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size=None, rfilter="linear") -> _Source:
     if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
         raise ValueError(f"raw={raw!r} describes headerless video; a .npy stack carries its own shape (leave raw None)")
     route = _raw_route(model, raw, height, width, False, batch, matrix, siting)
     wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
     rs = None
     if size is not None:   # the route, the planes and the groups of the destination size
-        rs = _raw_resize(raw, route.bits, height, width, size)
+        rs = _raw_resize(raw, route.bits, height, width, size, rfilter)
         route = _raw_route(model, raw, size[1], size[0], False, batch, matrix, siting)
     planes, groups = raw_planes(raw, height, width) if size is None else raw_planes(raw, size[1], size[0])
     if _is_path(src):
@@ -194,9 +194,10 @@ def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, si
                    groups, ("r", "g", "b") if raw in packed.FORMATS else ("y",), rs)
 
 
-def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, height=None, size=None) -> _Source:
+def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, height=None, size=None,
+          rfilter="linear") -> _Source:
     if raw is not None:
-        return _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size)
+        return _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter)
     if width is not None or height is not None:
         raise ValueError("width and height describe raw video: pass raw= with them")
     if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
@@ -207,7 +208,8 @@ def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, heig
         if size is not None:
             kind = "npy" if len(shape) == 2 else ("npy", shape[2])
             rs = _resize.FrameResize(_resize.frame_planes(kind, shape[0], shape[1]),
-                                     _resize.frame_planes(kind, size[1], size[0]), 8, size, (shape[1], shape[0]))
+                                     _resize.frame_planes(kind, size[1], size[0]), 8, size, (shape[1], shape[0]),
+                                     rfilter)
             shape = (size[1], size[0]) + shape[2:]
         route = _npy_route(model, shape, batch)
         if mm.shape[0] < 3:
@@ -223,7 +225,7 @@ def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, heig
     try:
         hdr, rs = reader.header, None
         if size is not None:
-            rs, hdr = _y4m_resize(hdr, size), _resize.y4m_header_at(hdr, size)
+            rs, hdr = _y4m_resize(hdr, size, rfilter), _resize.y4m_header_at(hdr, size)
         route = _y4m_route(model, hdr, False, batch, matrix, siting)
         h, w, (hc, wc) = hdr["height"], hdr["width"], hdr["chroma"]
         planes = [("y", 0, h, w)]
@@ -388,7 +390,7 @@ def excluded_targets(cut_flags, scored_frames) -> np.ndarray:
 @torch.no_grad()
 def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch: int = 8, chunk_frames: int = 32,
                 matrix: str = "bt709", siting=None, src_fps=None, raw=None, width=None, height=None,
-                scene_cut=None, resize=None) -> dict:
+                scene_cut=None, resize=None, resize_filter: str = "linear") -> dict:
     """Hold-out scores of `model` on a clip (methods: any of ALL_METHODS; with "optical_flow" or "motion" the result
     also has "flow_backend").  src: a path (.y4m, or a uint8 .npy stack [N,H,W] / [N,H,W,C]) or a
     readable binary file object carrying Y4M (a pipe): what `interpolate_y4m_stream` / `interpolate_npy_stream` take
@@ -403,8 +405,10 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     the clip is resized on the device (resize.py) before frames are dropped, so the held-out truth is the
     resized frame - the protocol of the reference's evaluator, which scores a checkpoint at its training size against a
     ground truth resized the same way; the route, planes and pixel counts are those of the new size, width / height stay
-    the size of a raw source, and the result gains "resize" [W, H] and "source_size" [w, h].  Every argument is checked
-    before any GPU work.  Returns
+    the size of a raw source, and the result gains "resize" [W, H] and "source_size" [w, h].  resize_filter: "linear" or
+    "area" (alias-free down-scaling; an error without `resize`, and where a plane would grow or shrink
+    more than 64 times); with a filter other than "linear" the result also has "resize_filter".  Every argument is
+    checked before any GPU work.  Returns
 
       {"frames", "triplets", "bits", "peak", "planes", "methods", "fps", "scored_frames": int64 source frame indices,
        "per_frame": {method: {plane: {"psnr": f64[], "ssim": f64[], "sse": uint64[]}}},
@@ -428,7 +432,8 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     if src_fps is not None:
         src_fps = _retime.parse_fps(src_fps)
     size = None if resize is None else _resize.check_size(resize)
-    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height, size)
+    rfilter = _resize.check_resize_filter(resize, resize_filter)
+    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter)
     try:
         route, step, rs = source.route, _step(triplets), source.rs
         dev = next(model.parameters()).device
@@ -498,6 +503,8 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
         out["flow_backend"] = FLOW_BACKEND
     if rs is not None:
         out.update({"resize": list(rs.size), "source_size": list(rs.source_size)})
+        if rs.filter != "linear":
+            out["resize_filter"] = rs.filter
     return out
 
 
@@ -553,7 +560,8 @@ def summary_table(result: dict) -> str:
              f"{result['bits']}-bit, peak {result['peak']}{left_out}"]
     if "resize" in result:
         (w, h), (sw, sh) = result["resize"], result["source_size"]
-        lines.append(f"scored at {w}x{h} (the {sw}x{sh} clip resized on the device before frames were held out)")
+        how = f" with the {result['resize_filter']} filter" if "resize_filter" in result else ""
+        lines.append(f"scored at {w}x{h} (the {sw}x{sh} clip resized on the device{how} before frames were held out)")
     lines += [f"{'method':<{mw}}{'plane':<6}{'PSNR mean':>11}{'std':>8}{'min':>9}{'max':>9}{'of mean MSE':>13}"
              f"{'SSIM mean':>11}{'min':>9}{'identical':>11}"]
     for m in result["methods"]:

@@ -9,6 +9,8 @@ The reference reads its frames with `cv2.imread(path, cv2.IMREAD_GRAYSCALE)`, re
                              converted with OpenCV's BGR2GRAY weights in its fixed-point form.
   resize_linear_u8(img, wh)  cv2.resize's INTER_LINEAR for uint8: half-pixel centres, edge clamp,
                              11-bit fixed-point coefficients and its two-stage rounding.
+  resize_area(img, wh, bits) the device resize's area filter (down-scaling, integers, exact): the host
+                             statement of csrc/resize.hip.h's resize_area_kernel.
   write_png(path, img)       8-bit gray or RGB PNG.
 
 Restated from OpenCV's published implementation (imgproc/resize.cpp `resizeGeneric_` with
@@ -201,6 +203,48 @@ def resize_linear_u8(img: np.ndarray, target_size) -> np.ndarray:
     # VResizeLinear<uchar,int,short>: ((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2
     out = (((b0[:, None] * (r0 >> 4)) >> 16) + ((b1[:, None] * (r1 >> 4)) >> 16) + 2) >> 2
     return np.clip(out, 0, 255).astype(np.uint8)
+
+
+AREA_MAX_RATIO = 64   # csrc/resize.hip.h kResizeAreaMaxRatio: the device kernel's limit (the host statement has none)
+
+
+def check_area(sh: int, sw: int, th: int, tw: int, max_ratio: int | None = None) -> None:
+    """The refusals of the area filter for one sh x sw plane resized to th x tw (ValueError): a plane that grows, and,
+    with max_ratio (the device's AREA_MAX_RATIO), one that shrinks more than that on either axis."""
+    if tw > sw or th > sh:
+        raise ValueError(f"the area filter only down-scales: {sw}x{sh} -> {tw}x{th} enlarges a plane; use the linear filter")
+    if max_ratio is not None and (sw > max_ratio * tw or sh > max_ratio * th):
+        raise ValueError(f"the device's area filter covers ratios up to {max_ratio} on either axis, got {sw}x{sh} -> "
+                         f"{tw}x{th}")
+
+
+def _area_weights(dst_n: int, src_n: int) -> np.ndarray:
+    """[dst_n, src_n] int64: the overlap of [d * src_n, (d + 1) * src_n) and [j * dst_n, (j + 1) * dst_n)."""
+    d = np.arange(dst_n, dtype=np.int64)[:, None]
+    j = np.arange(src_n, dtype=np.int64)[None, :]
+    return np.maximum(np.minimum((d + 1) * src_n, (j + 1) * dst_n) - np.maximum(d * src_n, j * dst_n), 0)
+
+
+def resize_area(img: np.ndarray, target_size, bits: int = 8) -> np.ndarray:
+    """The area filter of the device resize (csrc/resize.hip.h) on a uint8 (bits=8) or uint16 (bits=10)
+    [H,W] plane, target_size = (W, H) no larger than the plane on either axis: every destination sample is the mean of
+    the source area it covers, the weights the overlap lengths in units of 1 / n_dst of a source sample, in integers:
+    out = (N + D // 2) // D with D = sw * sh.  At 10 bits samples above 1023 read as 1023; equal size is the plane."""
+    tw, th = int(target_size[0]), int(target_size[1])
+    sh, sw = img.shape[:2]
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+    if tw < 1 or th < 1:
+        raise ValueError(f"target_size must be positive, got {target_size!r}")
+    check_area(sh, sw, th, tw)
+    if (sh, sw) == (th, tw):
+        return img
+    v = img.astype(np.int64)
+    if bits == 10:
+        v = np.minimum(v, 1023)
+    n = _area_weights(th, sh) @ v @ _area_weights(tw, sw).T   # < 2^24 * 2^24 * 1023: int64
+    d = sw * sh
+    return ((n + d // 2) // d).astype(img.dtype)
 
 
 def write_png(path: str, img: np.ndarray) -> None:

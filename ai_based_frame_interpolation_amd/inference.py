@@ -458,7 +458,8 @@ class FrameInterpolator:
 
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
                           chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend", raw=None,
-                          width=None, height=None, dedup=None, max_gap=4, dedup_log=None, scene_log=None, resize=None):
+                          width=None, height=None, dedup=None, max_gap=4, dedup_log=None, scene_log=None, resize=None,
+                          resize_filter="linear"):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -513,17 +514,21 @@ class FrameInterpolator:
         the format gives at the new size, no siting offset; a large down-scale aliases as the reference's does), before
         scene cuts, dedup and the first forward.  The route and its refusals are those of the new size, the output has
         the new size (the Y4M header says so); width / height stay the size of a raw source.  The result is, byte for
-        byte, what the same call without `resize` writes for the clip resized beforehand, for every chunk_frames."""
+        byte, what the same call without `resize` writes for the clip resized beforehand, for every chunk_frames.
+        resize_filter: "linear", or "area" for an alias-free down-scale (every destination sample is the
+        exact rounded mean of the source area it covers; refused where a plane would grow on either axis or shrink more
+        than 64 times).  Anything but "linear" is an error without `resize`."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
         from . import stream
         run = dict(batch=self.batch, chunk_frames=chunk_frames, scene_cut=thr, fps=fps, src_fps=src_fps,
                    time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
-                   scene_log=scene_log, resize=resize)
+                   scene_log=scene_log, resize=resize, resize_filter=resize_filter)
+        from . import resize as _resize
         if resize is not None:
-            from . import resize as _resize
             _resize.check_size(resize)
+        _resize.check_resize_filter(resize, resize_filter)
         if raw is not None:
             return stream.interpolate_raw_stream(self.model, input_path, output_path, factor, raw=raw, width=width,
                                                  height=height, matrix=matrix, siting=siting, **run)

@@ -640,18 +640,18 @@ def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode
     return n
 
 
-def _y4m_resize(hdr, size) -> "_resize.FrameResize":
+def _y4m_resize(hdr, size, filter: str = "linear") -> "_resize.FrameResize":
     """The resize of the frames of a Y4M stream with header `hdr` to `size` = (width, height)."""
     kind = ("y4m", hdr["colourspace"])
     return _resize.FrameResize(_resize.frame_planes(kind, hdr["height"], hdr["width"]),
                                _resize.frame_planes(kind, size[1], size[0]), hdr["bits"], size,
-                               (hdr["width"], hdr["height"]))
+                               (hdr["width"], hdr["height"]), filter)
 
 
-def _raw_resize(raw, bits, height, width, size) -> "_resize.FrameResize":
+def _raw_resize(raw, bits, height, width, size, filter: str = "linear") -> "_resize.FrameResize":
     """The resize of tight `raw` frames of height x width to `size` = (width, height)."""
     return _resize.FrameResize(_resize.frame_planes(raw, height, width), _resize.frame_planes(raw, size[1], size[0]),
-                               bits, size, (int(width), int(height)))
+                               bits, size, (int(width), int(height)), filter)
 
 
 def _plan_of(fps, src_fps, header_fps, depth):
@@ -690,7 +690,7 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
                            matrix: str = "bt709", siting: str | None = None, scene_cut: float | None = None,
                            scene_log: list | None = None, fps=None, src_fps=None, time_depth: int = 2,
                            retime: str = "blend", dedup=None, max_gap: int = 4, dedup_log: list | None = None,
-                           resize=None) -> int:
+                           resize=None, resize_filter: str = "linear") -> int:
     """Y4M in (a path or a readable binary file: a pipe, `sys.stdin.buffer`) -> Y4M out (a path or a writable binary
     file), or a `.npy` path of the luma frames (grayscale network; the input must then be a regular file, whose frame
     count a first pass reads).  This is what `FrameInterpolator.interpolate_video` runs; the result is the same, byte
@@ -707,11 +707,14 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     `fps`.  dedup_log: a list that receives (peaks, dead) host arrays of each chunk's intervals (scene_log's twin).
     resize: None, or (width, height) / "WxH": every frame is resized on the device right after its upload (resize.py,
     DESIGN.md 3.3q; each plane on its own grid, the chroma size as the tag gives it at the new size), and the route, its
-    refusals, scene cuts, dedup and the output header are those of a clip of that size."""
+    refusals, scene cuts, dedup and the output header are those of a clip of that size.  resize_filter: "linear" (the
+    filter of cv2.resize's INTER_LINEAR) or "area" (alias-free down-scaling, DESIGN.md 3.3r: refused where a plane would
+    grow on either axis, or shrink more than 64 times); anything but "linear" is an error without `resize`."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     tol, gap = check_dedup(dedup, max_gap, fps, factor)
     size = None if resize is None else _resize.check_size(resize)
+    rfilter = _resize.check_resize_filter(resize, resize_filter)
     npy_out = isinstance(dst, (str, os.PathLike)) and os.fspath(dst).lower().endswith(".npy")
     if npy_out:
         if not _is_path(src) or not stat.S_ISREG(os.stat(src).st_mode):
@@ -721,7 +724,7 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     try:
         hdr, rs = reader.header, None
         if size is not None:   # everything from here on is a clip of the new size; the reader keeps the source's
-            rs, hdr = _y4m_resize(hdr, size), _resize.y4m_header_at(hdr, size)
+            rs, hdr = _y4m_resize(hdr, size, rfilter), _resize.y4m_header_at(hdr, size)
         route = _y4m_route(model, hdr, npy_out, batch, matrix, siting)
         plan = _plan_of(fps, src_fps, hdr["fps"], depth)
         if plan is None:
@@ -766,17 +769,18 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
 def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
                            scene_cut: float | None = None, scene_log: list | None = None, fps=None, src_fps=None,
                            time_depth: int = 2, retime: str = "blend", dedup=None, max_gap: int = 4,
-                           dedup_log: list | None = None, resize=None) -> int:
+                           dedup_log: list | None = None, resize=None, resize_filter: str = "linear") -> int:
     """`.npy` stack in (uint8 [N,H,W] or [N,H,W,C], read through `np.load(mmap_mode="r")`) -> `.npy` out (written
     through `np.lib.format.open_memmap`, the file `np.save` would write; a name without `.npy` gets it).  An
     [N,H,W,C] stack goes through the RGB network, or channel by channel through the grayscale one.  Returns the output
     frame count.  fps / src_fps / time_depth / retime and chunk_frames None: as for `interpolate_y4m_stream`; a .npy
-    stack carries no rate, so `fps` needs `src_fps`.  resize: as for `interpolate_y4m_stream`; the output stack has the
-    new height and width."""
+    stack carries no rate, so `fps` needs `src_fps`.  resize / resize_filter: as for `interpolate_y4m_stream`; the output
+    stack has the new height and width."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     tol, gap = check_dedup(dedup, max_gap, fps, factor)
     size = None if resize is None else _resize.check_size(resize)
+    rfilter = _resize.check_resize_filter(resize, resize_filter)
     plan = _plan_of(fps, src_fps, None, depth)
     if plan is not None:
         factor = plan.G
@@ -795,7 +799,8 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     if size is not None:
         kind = "npy" if len(shape) == 2 else ("npy", shape[2])
         rs = _resize.FrameResize(_resize.frame_planes(kind, shape[0], shape[1]),
-                                 _resize.frame_planes(kind, size[1], size[0]), 8, size, (shape[1], shape[0]))
+                                 _resize.frame_planes(kind, size[1], size[0]), 8, size, (shape[1], shape[0]),
+                                 rfilter)
         shape = (size[1], size[0]) + shape[2:]
     route = _npy_route(model, shape, batch)
     n_out = (mm.shape[0] - 1) * factor + 1 if plan is None else plan.n_out(mm.shape[0])
@@ -818,7 +823,8 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
                            batch: int = 8, chunk_frames: int | None = 32, matrix: str = "bt709",
                            siting: str | None = None, scene_cut: float | None = None, scene_log: list | None = None,
                            fps=None, src_fps=None, time_depth: int = 2, retime: str = "blend", dedup=None,
-                           max_gap: int = 4, dedup_log: list | None = None, resize=None) -> int:
+                           max_gap: int = 4, dedup_log: list | None = None, resize=None,
+                           resize_filter: str = "linear") -> int:
     """Headerless raw video in (a path or a readable binary file: a pipe) -> the same format out (a path or a writable
     binary file): tight NV12 frames of height x width (`ffmpeg ... -f rawvideo -pix_fmt nv12 -`) through the RGB
     network, `interpolate_sequence_nv12` per level; or, with raw "rgb24" / "bgr24" / "rgba" / "bgra", tight packed RGB
@@ -830,8 +836,8 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     whatever reads the result).  siting None is "mpeg2", the range limited.  Every argument - the model's network, the
     output name, the size of a regular input file (a whole number of frames) - is checked before any GPU work and
     before the output exists; a pipe that ends inside a frame is an error at that point.  Returns the output frame
-    count.  resize: as for `interpolate_y4m_stream`: width and height stay the size of the source, the output is raw
-    video of the new size, and the format's refusals (an odd width of uyvy422 / yuyv422) apply to both sizes."""
+    count.  resize / resize_filter: as for `interpolate_y4m_stream`: width and height stay the size of the source, the
+    output is raw video of the new size, and the format's refusals (an odd width of uyvy422 / yuyv422) apply to both sizes."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     if src_fps is None:
         raise ValueError("raw video carries no frame rate: pass src_fps")
@@ -840,11 +846,12 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     tol, gap = check_dedup(dedup, max_gap, fps, factor)
     npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
     size = None if resize is None else _resize.check_size(resize)
+    rfilter = _resize.check_resize_filter(resize, resize_filter)
     route = _raw_route(model, raw, height, width, npy_out, batch, matrix, siting)
     wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
     rs = None
     if size is not None:
-        rs = _raw_resize(raw, route.bits, height, width, size)
+        rs = _raw_resize(raw, route.bits, height, width, size, rfilter)
         route = _raw_route(model, raw, size[1], size[0], npy_out, batch, matrix, siting)
     plan = _plan_of(fps, src_rate, None, depth)
     if plan is not None:

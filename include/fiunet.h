@@ -40,7 +40,9 @@ extern "C" {
                                      fiunet_stepped_ssim); v8 also, added the same way: repeated frames in video
                                      (fiunet_pair_peak_u8, fiunet_pair_peak_p10, fiunet_retime_table_u8,
                                      fiunet_retime_table_p10); v8 also, added the same way: resizing frame planes
-                                     (fiunet_resize_plane, fiunet_resize_planes_u8, fiunet_resize_planes_p10) */
+                                     (fiunet_resize_plane, fiunet_resize_planes_u8, fiunet_resize_planes_p10); v8 also: the
+                                     `reserved` member of fiunet_resize_plane, which had to be 0, is `filter`
+                                     (FIUNET_RESIZE_LINEAR = 0, FIUNET_RESIZE_AREA); no entry point is added */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -498,7 +500,7 @@ int fiunet_retime_table_u8(const uint8_t* grid, int n_rows, size_t frame_samples
 int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
                             int n_out, uint16_t* out, void* stream);
 
-/* Bilinear resize of frame planes (csrc/resize.hip.h).  A plane is described in SAMPLES of its buffer:
+/* Resize of frame planes, bilinear or by area (csrc/resize.hip.h).  A plane is described in SAMPLES of its buffer:
  * sample (y, x) of frame f lies at offset + f * frame_stride + y * pitch + x * step.  Plane i of `src_planes` is
  * resampled into plane i of `dst_planes`, each pair on its own grid, for n_frames frames, in one launch per 2^31 store
  * chunks (the descriptors travel in the kernel's arguments: `src_planes` / `dst_planes` are HOST memory, read during the
@@ -513,10 +515,30 @@ int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_sampl
  * outside 1..4, n_frames < 0, a size outside 1 .. 2^24, a step outside 1..4, pitch < (w - 1) * step + 1, a plane that
  * does not lie inside its frame stride (offset + (h - 1) * pitch + (w - 1) * step + 1 > frame_stride), or source and
  * destination byte ranges (first sample of any plane of frame 0 to the last of frame n_frames - 1) that overlap.
- * FIUNET_ERR_UNSUPPORTED: a destination plane of 2^31 or more 16-byte store chunks. */
+ * FIUNET_ERR_UNSUPPORTED: a destination plane of 2^31 or more 16-byte store chunks.
+ *
+ * The filter is the `filter` member of the DESTINATION planes, which must agree within a call; source planes carry 0.  A
+ * source filter other than 0, a destination filter that is neither value below, or destination planes that disagree are
+ * FIUNET_ERR_INVALID_ARG, before any launch.  FIUNET_RESIZE_LINEAR (0) is everything above.  FIUNET_RESIZE_AREA is the
+ * alias-free down-scaling filter, in integers, at 8 and 10 bits alike (tests/resize_area_ref.py):
+ *   axis      n_src -> n_dst, n_dst <= n_src, in units of 1 / n_dst of a source sample: destination index d covers
+ *             [d * n_src, (d + 1) * n_src), source index j covers [j * n_dst, (j + 1) * n_dst), and the weight is the
+ *             length of the overlap, w(d, j) = max(0, min((d + 1) * n_src, (j + 1) * n_dst) - max(d * n_src, j * n_dst));
+ *             the weights of one d sum to n_src
+ *   plane     source sh x sw, destination dh x dw: N = sum_y wy(r, y) * sum_x wx(c, x) * v(y, x), D = sw * sh,
+ *             out = (N + D / 2) / D in integer division: exact, half up; samples above 1023 read as 1023 at 10 bits
+ *   equal h and w: the same copy as under the linear filter
+ * A constant plane stays constant; for whole ratios rx, ry it is the rounded mean of each rx x ry block.  Two refusals of
+ * its own, before any launch: a plane pair with a destination wider or taller than its source is FIUNET_ERR_INVALID_ARG
+ * (the area filter only down-scales: enlarge with the linear filter), and a ratio above 64 on either axis (sw > 64 * dw
+ * or sh > 64 * dh) is FIUNET_ERR_UNSUPPORTED (one thread sums at most 66 x 66 samples). */
+enum fiunet_resize_filter {
+    FIUNET_RESIZE_LINEAR = 0,
+    FIUNET_RESIZE_AREA = 1
+};
 typedef struct fiunet_resize_plane {
     size_t offset, pitch, frame_stride;
-    int32_t h, w, step, reserved;   /* reserved: 0 */
+    int32_t h, w, step, filter;   /* filter: a fiunet_resize_filter in a destination plane, 0 in a source plane */
 } fiunet_resize_plane;
 int fiunet_resize_planes_u8(const uint8_t* src, const fiunet_resize_plane* src_planes, uint8_t* dst,
                             const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream);
