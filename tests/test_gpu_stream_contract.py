@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import stream_contract as SC  # noqa: E402
+import stream_delay as SD  # noqa: E402
 
 from ai_based_frame_interpolation_amd import _native  # noqa: E402
 from oracle import unet_oracle as O  # noqa: E402
@@ -54,6 +55,11 @@ def _serial(ctx, f1, f2, code):
     return out
 
 
+#: the delay ahead of the device load: everything behind it is enqueued within a few milliseconds of host time, so work
+#: that does not wait for the load has run long before the load starts
+LOAD_DELAY_MS = 50.0
+
+
 def test_device_load_and_forward_on_one_side_stream(env):
     """fiunet_load_weights_device (the second load of a context, new weights) and fiunet_forward behind it on one
     non-blocking side stream with no host synchronisation in between, in fp32 and bf16; then again with
@@ -61,9 +67,14 @@ def test_device_load_and_forward_on_one_side_stream(env):
     not on the host", also when the load is not on the null stream.  The results are bit for bit those of a context that
     loaded the same weights through the host path.
 
-    This test CAN PASS BY LUCK: a missing wait shows only when the race is lost.  The 2x270x480 forwards queued on the
-    stream ahead of the load are there to make that unlikely - the load's kernels cannot start before they are done, so
-    work that does not wait for the load runs long before it."""
+    What is forced and what is not.  A delay kernel (tests/stream_delay.py, LOAD_DELAY_MS) sits on the side stream behind
+    the 2x270x480 forwards and ahead of the load, so the load's kernels cannot start before it has passed, tens of
+    milliseconds after the host has enqueued everything.  Work on ANOTHER stream that does not wait for the load - the
+    packing of fiunet_prepare_precision, which goes to the null stream and has only the load's event to hold it back - now
+    runs before the load every time and packs the previous weights: that race is no longer left to luck.  What is still
+    not forced: work that wrongly went to the side stream itself runs behind the delay and the load in stream order and is
+    right whatever it waits for, and a wait on the wrong event that happens to complete later than the load looks like the
+    right one."""
     dev = env.dev
     sds =[O.make_seeded_state_dict(seed) for seed in (1234, 4321, 999, 31)]
     on_dev = [{k: v.to(device=dev, dtype=torch.float32).contiguous() for k, v in sd.items()
@@ -89,6 +100,7 @@ def test_device_load_and_forward_on_one_side_stream(env):
             with torch.cuda.stream(side):
                 for _ in range(4):
                     _forward_on(ctx, big1, big2, big_out, _native.BF16, big_ws, side.cuda_stream)
+                SD.delay(side, LOAD_DELAY_MS)
                 ctx.load_state_dict(on_dev[which], prep="device")   # on the current stream: `side`
                 if prepare is not None:
                     ctx.prepare(prepare)
