@@ -56,6 +56,8 @@ SYMBOLS = (
     "fiunet_flow_workspace_bytes", "fiunet_farneback_flow", "fiunet_flow_warp",
     # resizing frame planes
     "fiunet_resize_planes_u8", "fiunet_resize_planes_p10",
+    # 10-bit 4:2:2 wire packings
+    "fiunet_unpack_422p10", "fiunet_pack_422p10",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -226,6 +228,8 @@ def lib() -> ctypes.CDLL:
     L.fiunet_workspace_bytes_rgb_packed.argtypes = [vp, ci, ci, ci, ci]
     L.fiunet_workspace_bytes_rgb_packed.restype = sz
     L.fiunet_forward_rgb_packed.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, sz, vp]
+    L.fiunet_unpack_422p10.argtypes = [vp, ci, vp, vp, vp, sz, ci, ci, ci, vp]
+    L.fiunet_pack_422p10.argtypes = [vp, sz, vp, ci, vp, vp, ci, ci, ci, vp]
     L.fiunet_yuv_to_rgb_u8.argtypes = [vp, ci, sz, sz, vp, ci, ci, ci, cu, vp]
     L.fiunet_yuv_to_rgb_p10.argtypes = [vp, ci, sz, sz, vp, ci, ci, ci, cu, vp]
     L.fiunet_rgb_to_yuv_u8.argtypes = [vp, vp, ci, sz, sz, ci, ci, ci, cu, vp]
@@ -680,6 +684,39 @@ def rgb_to_yuv(rgb: "torch.Tensor", out: "torch.Tensor", fmt: int, layout, colou
     fn, name = ((lib().fiunet_rgb_p10_to_yuv, "fiunet_rgb_p10_to_yuv") if bits == 10 else
                 (lib().fiunet_rgb_to_yuv_u8, "fiunet_rgb_to_yuv_u8"))
     check(fn(rgb.data_ptr(), out.data_ptr(), fmt, layout.row_pitch, _row_stride(out), b, h, w, colour, s), name)
+
+
+PACK10_V210, PACK10_Y210, PACK10_P210 = 0, 1, 2   # include/fiunet.h: enum fiunet_packing10
+
+
+def _wire10_layouts(packing: int, layout, frame_stride_bytes: int):
+    """(packed layout, surface layout) arguments of the two wire10 entry points: `layout` is a resolved
+    packed.PackedLayout in bytes (v210 / y210le) or colour.SurfaceLayout in samples (p210le), the frames
+    `frame_stride_bytes` apart."""
+    if packing == PACK10_P210:
+        return None, ctypes.byref(SurfaceLayout(layout.luma_pitch, layout.chroma_offset, layout.chroma_pitch,
+                                                frame_stride_bytes // 2))
+    return ctypes.byref(PackedLayout(layout.row_pitch, frame_stride_bytes)), None
+
+
+def _row_stride_bytes(t: "torch.Tensor") -> int:
+    return _row_stride(t) * t.element_size()
+
+
+def unpack_422p10(frames: "torch.Tensor", packing: int, layout, out: "torch.Tensor", h: int, w: int, stream=None) -> None:
+    """fiunet_unpack_422p10: [B, frame_stride] wire frames of the fiunet_packing10 `packing` (rows contiguous, any row
+    stride) in the resolved `layout` -> 16-bit [B, >= samples] yuv422p10le frames (rows contiguous, any row stride)."""
+    pl, sl = _wire10_layouts(packing, layout, _row_stride_bytes(frames))
+    check(lib().fiunet_unpack_422p10(frames.data_ptr(), packing, pl, sl, out.data_ptr(), _row_stride(out),
+                                     frames.shape[0], h, w, _stream(frames, stream)), "fiunet_unpack_422p10")
+
+
+def pack_422p10(planar: "torch.Tensor", out: "torch.Tensor", packing: int, layout, h: int, w: int, stream=None) -> None:
+    """fiunet_pack_422p10: 16-bit [B, >= samples] yuv422p10le frames (rows contiguous, any row stride) -> [B,
+    frame_stride] wire frames of `packing` in the resolved `layout` (rows contiguous, any row stride)."""
+    pl, sl = _wire10_layouts(packing, layout, _row_stride_bytes(out))
+    check(lib().fiunet_pack_422p10(planar.data_ptr(), _row_stride(planar), out.data_ptr(), packing, pl, sl,
+                                   planar.shape[0], h, w, _stream(planar, stream)), "fiunet_pack_422p10")
 
 
 def pair_sad(frames: "torch.Tensor", sums: "torch.Tensor", bits: int) -> None:

@@ -2,7 +2,7 @@
 
 The reference's `main.py video` flags (--input, --output, --factor, --model, --device), plus --precision, --matrix,
 --siting, --scene-cut, --batch, --chunk-frames, the frame-rate conversion's --fps, --src-fps, --time-depth and
---retime, --dedup and --max-gap for repeated frames, and --raw / --size for headerless NV12, packed RGB or 4:2:2 / 4:4:4 YUV video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
+--retime, --dedup and --max-gap for repeated frames, and --raw / --size (and --packing) for headerless NV12, packed RGB or 4:2:2 / 4:4:4 YUV video.  The command always streams (stream.py), so a clip of any length runs in memory bounded by
 the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 
     ffmpeg -i in.mkv -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - \\
@@ -41,6 +41,15 @@ resolution: what ProRes, DNxHR and XDCAM decode to and what cap
     ffmpeg -f decklink -i 'DeckLink Mini Recorder' -f rawvideo -pix_fmt uyvy422 - | \\
         python -m ai_based_frame_interpolation_amd.cli video --input - --output - --raw uyvy422 --size 1920x1080 \\
         --src-fps 30 --model rgb.pth | ffmpeg -f rawvideo -pix_fmt uyvy422 -s 1920x1080 -r 60 -i - out.mkv
+
+`--raw yuv422p10le --packing v210` (or y210le, p210le) takes the same samples as 10-bit capture cards and uncompressed
+broadcast files pack them (wire10.py): the frames are unpacked and packed on the GPU, so ffmpeg neither
+unpacks v210 to yuv422p10le before the pipe nor repacks behind it.  The result is the yuv422p10le route's, byte for byte:
+
+    ffmpeg -f decklink -raw_format yuv422p10 -i 'DeckLink Mini Recorder' -c:v v210 -f rawvideo - | \\
+        python -m ai_based_frame_interpolation_amd.cli video --input - --output - --raw yuv422p10le --packing v210 \\
+        --size 1920x1080 --src-fps 30 --precision fp16 --model rgb.pth | \\
+        ffmpeg -f rawvideo -c:v v210 -s 1920x1080 -r 60 -i - -c:v v210 out.mov
 
 Standard output then carries nothing but video: the model-loading lines go to standard error.  The network (grayscale
 2->1 or RGB 6->3) is read from the checkpoint.
@@ -131,6 +140,7 @@ def _methods(v: str):
     return names
 
 
+PACKING_CHOICES = ("v210", "y210le", "p210le")   # wire10.PACKINGS
 RAW_CHOICES = ("nv12", "rgb24", "bgr24", "rgba", "bgra", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le", "uyvy422",
                "yuyv422")
 
@@ -168,6 +178,8 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--raw", default=None, choices=RAW_CHOICES,
                    help="Headerless raw video in and out (tight NV12, packed RGB or 4:2:2 / 4:4:4 YUV frames, named as "
                         "ffmpeg's -pix_fmt); needs --size and --src-fps")
+    v.add_argument("--packing", default=None, choices=PACKING_CHOICES,
+                   help="With --raw yuv422p10le: the frames are packed on the wire as v210, y210le or p210le, in and out")
     v.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
     v.add_argument("--resize", type=_size, default=None, metavar="WIDTHxHEIGHT",
                    help="Resize every frame on the GPU before it is interpolated; the output has this size (--size "
@@ -196,6 +208,8 @@ def parser() -> argparse.ArgumentParser:
                    help="Source frame rate as n or n/d, for the time stamps (default: the Y4M header's)")
     e.add_argument("--raw", default=None, choices=RAW_CHOICES,
                    help="Headerless raw video (tight frames, named as ffmpeg's -pix_fmt); needs --size")
+    e.add_argument("--packing", default=None, choices=PACKING_CHOICES,
+                   help="With --raw yuv422p10le: the frames are packed on the wire as v210, y210le or p210le")
     e.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
     e.add_argument("--resize", type=_size, default=None, metavar="WIDTHxHEIGHT",
                    help="Resize the clip on the GPU before frames are held out and score it at this size, such as the "
@@ -217,6 +231,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     if a.chunk_frames is None:
         a.chunk_frames = 4 * a.batch
     if a.command in ("evaluate", "video"):
+        if a.packing is not None and a.raw != "yuv422p10le":
+            ap.error("--packing says how yuv422p10le samples are packed on the wire: pass --raw yuv422p10le with it")
         if a.resize_filter is not None and a.resize is None:
             ap.error("--resize-filter names the filter of --resize WIDTHxHEIGHT")
         a.resize_filter = a.resize_filter or "linear"
@@ -253,9 +269,9 @@ def run_video(a: argparse.Namespace) -> int:
     fi = FrameInterpolator(model=model, device=device, batch=a.batch)
     src = sys.stdin.buffer if a.input == "-" else a.input
     dst = sys.stdout.buffer if a.output == "-" else a.output
-    logs = {}
+    logs = {} if a.packing is None else dict(packing=a.packing)
     if a.dedup is not None:   # for the count below (the cut flags too: a run before a cut is not re-timed)
-        logs = dict(dedup_log=[], scene_log=[] if a.scene_cut is not None else None)
+        logs.update(dedup_log=[], scene_log=[] if a.scene_cut is not None else None)
     n = fi.interpolate_video(src, dst, a.factor, matrix=a.matrix, siting=a.siting, scene_cut=a.scene_cut,
                              chunk_frames=a.chunk_frames, fps=a.fps, src_fps=a.src_fps, time_depth=a.time_depth,
                              retime=a.retime, raw=a.raw, width=a.size[0] if a.size else None,
@@ -282,7 +298,8 @@ def run_evaluate(a: argparse.Namespace) -> dict:
     res = holdout.score_video(model, src, triplets=a.triplets, methods=a.methods, batch=a.batch,
                               chunk_frames=a.chunk_frames, matrix=a.matrix, siting=a.siting, src_fps=a.src_fps,
                               raw=a.raw, width=a.size[0] if a.size else None, height=a.size[1] if a.size else None,
-                              scene_cut=a.scene_cut, resize=a.resize, resize_filter=a.resize_filter)
+                              scene_cut=a.scene_cut, resize=a.resize, resize_filter=a.resize_filter,
+                              **({} if a.packing is None else dict(packing=a.packing)))
     print(holdout.summary_table(res), file=sys.stderr)
     if a.json:
         with open(a.json, "w") as f:

@@ -4,6 +4,7 @@
 #include "fiunet_internal.h"
 #include "colour.hip.h"
 #include "packed.hip.h"
+#include "wire10.hip.h"
 #include "yuv4xx.hip.h"
 
 using namespace fiunet;
@@ -626,6 +627,112 @@ int fiunet_forward_rgb_packed(fiunet_ctx* ctx, const uint8_t* frame1, const uint
             return fiunet_rgb_to_packed_u8(rgb, out, out_layout, alpha ? frame1 : NULL, alpha ? frame2 : NULL, in_layout, B,
                                            H, W, format, stream);
         });
+}
+
+// ---- 10-bit 4:2:2 wire packings (csrc/wire10.hip.h): v210 / y210le / p210le <-> yuv422p10le ----
+// bytes of one tight row of a one-plane packing
+static size_t wire10_row_bytes(int packing, int W)
+{
+    return packing == FIUNET_PACK10_V210 ? 128 * (size_t)((W + 47) / 48) : 4 * (size_t)W;
+}
+
+// The caller's layouts (NULL or zero fields = tight) and the working frames' stride (0 = tight) -> the resolved ones and
+// whether the vector path applies, with every refusal: before any launch.  wire / work: the two base pointers.
+static int resolve_wire10(const void* wire, int packing, const fiunet_packed_layout* pl, const fiunet_surface_layout* sl,
+                          const void* work, size_t* work_stride, int B, int H, int W, Wire10Layout* lay, bool* vec)
+{
+    if (!wire || !work) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (packing != FIUNET_PACK10_V210 && packing != FIUNET_PACK10_Y210 && packing != FIUNET_PACK10_P210)
+        return fail(FIUNET_ERR_INVALID_ARG, "packing: not a fiunet_packing10");
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    if (((uintptr_t)wire | (uintptr_t)work) & 1) return fail(FIUNET_ERR_INVALID_ARG, "wire10: a pointer is not 2-byte aligned");
+    const size_t Wc = (size_t)(W + 1) / 2, tight = (size_t)H * W + 2 * (size_t)H * Wc;
+    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
+    if (*work_stride == 0) *work_stride = tight;
+    if (*work_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "wire10: a value above 2^40");
+    if (*work_stride < tight) return fail(FIUNET_ERR_INVALID_ARG, "wire10: the planar frame stride is smaller than one frame");
+    bool aligned = W % 8 == 0 && *work_stride % 8 == 0 && (((uintptr_t)wire | (uintptr_t)work) & 15) == 0;
+    if (packing == FIUNET_PACK10_P210) {
+        if (pl) return fail(FIUNET_ERR_INVALID_ARG, "p210le takes a fiunet_surface_layout, not a fiunet_packed_layout");
+        lay->pitch = sl && sl->luma_pitch ? sl->luma_pitch : (size_t)W;
+        lay->chroma_offset = sl && sl->chroma_offset ? sl->chroma_offset : (size_t)H * W;
+        lay->chroma_pitch = sl && sl->chroma_pitch ? sl->chroma_pitch : 2 * Wc;
+        lay->frame_stride = sl && sl->frame_stride ? sl->frame_stride : tight;
+        if (lay->pitch > big || lay->chroma_pitch > big || lay->chroma_offset > big || lay->frame_stride > big)
+            return fail(FIUNET_ERR_INVALID_ARG, "surface layout: a value above 2^40 samples");
+        if (lay->pitch < (size_t)W) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: luma_pitch < W");
+        if (lay->chroma_pitch < 2 * Wc) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_pitch < 2*ceil(W/2)");
+        if (lay->chroma_offset < (size_t)(H - 1) * lay->pitch + W)
+            return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_offset inside the luma plane");
+        if (lay->frame_stride < lay->chroma_offset + (size_t)(H - 1) * lay->chroma_pitch + 2 * Wc)
+            return fail(FIUNET_ERR_INVALID_ARG, "surface layout: frame_stride does not cover the chroma plane");
+        *vec = aligned && (lay->pitch | lay->chroma_offset | lay->chroma_pitch | lay->frame_stride) % 8 == 0;
+        return FIUNET_OK;
+    }
+    if (sl) return fail(FIUNET_ERR_INVALID_ARG, "v210 / y210le take a fiunet_packed_layout, not a fiunet_surface_layout");
+    if (W & 1) return fail(FIUNET_ERR_INVALID_ARG, "v210 / y210le need an even width");
+    const size_t row = wire10_row_bytes(packing, W);
+    lay->chroma_offset = lay->chroma_pitch = 0;
+    lay->pitch = pl && pl->row_pitch ? pl->row_pitch : row;
+    if (lay->pitch > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
+    lay->frame_stride = pl && pl->frame_stride ? pl->frame_stride : (size_t)H * lay->pitch;
+    if (lay->frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
+    if (lay->pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: row_pitch below the tight row");
+    if (lay->frame_stride < (size_t)(H - 1) * lay->pitch + row)
+        return fail(FIUNET_ERR_INVALID_ARG, "packed layout: frame_stride does not cover the last row");
+    if ((lay->pitch | lay->frame_stride) & 1)
+        return fail(FIUNET_ERR_INVALID_ARG, "packed layout: row_pitch and frame_stride must be even (16-bit words)");
+    *vec = aligned && (lay->pitch | lay->frame_stride) % 16 == 0;
+    return FIUNET_OK;
+}
+
+extern "C++" {
+template <int P>
+using Packing10 = std::integral_constant<int, P>;
+
+// go(Packing10<P>{}) for a packing that resolve_wire10 has accepted
+template <typename Go>
+static int for_packing10(int packing, Go go)
+{
+    switch (packing) {
+    case FIUNET_PACK10_V210: return go(Packing10<FIUNET_PACK10_V210>{});
+    case FIUNET_PACK10_Y210: return go(Packing10<FIUNET_PACK10_Y210>{});
+    default: return go(Packing10<FIUNET_PACK10_P210>{});
+    }
+}
+}  // extern "C++"
+
+static dim3 wire10_grid(int packing, bool vec, int W, int H, int B)
+{
+    return dim3((unsigned)wire10_blocks(packing, vec, W), (unsigned)H, (unsigned)B);
+}
+
+int fiunet_unpack_422p10(const void* in, int packing, const fiunet_packed_layout* in_packed,
+                         const fiunet_surface_layout* in_surface, uint16_t* out, size_t out_frame_stride, int B, int H,
+                         int W, void* stream)
+{
+    Wire10Layout lay;
+    bool vec;
+    if (int rc = resolve_wire10(in, packing, in_packed, in_surface, out, &out_frame_stride, B, H, W, &lay, &vec)) return rc;
+    return for_packing10(packing, [&](auto p) {
+        constexpr int P = decltype(p)::value;
+        return launch_vec<&unpack_422p10_kernel<P, true>, &unpack_422p10_kernel<P, false>>(
+            vec, wire10_grid(packing, vec, W, H, B), stream, (const uint16_t*)in, lay, out, out_frame_stride, H, W);
+    });
+}
+
+int fiunet_pack_422p10(const uint16_t* in, size_t in_frame_stride, void* out, int packing,
+                       const fiunet_packed_layout* out_packed, const fiunet_surface_layout* out_surface, int B, int H,
+                       int W, void* stream)
+{
+    Wire10Layout lay;
+    bool vec;
+    if (int rc = resolve_wire10(out, packing, out_packed, out_surface, in, &in_frame_stride, B, H, W, &lay, &vec)) return rc;
+    return for_packing10(packing, [&](auto p) {
+        constexpr int P = decltype(p)::value;
+        return launch_vec<&pack_422p10_kernel<P, true>, &pack_422p10_kernel<P, false>>(
+            vec, wire10_grid(packing, vec, W, H, B), stream, in, in_frame_stride, (uint16_t*)out, lay, H, W);
+    });
 }
 
 }  // extern "C"

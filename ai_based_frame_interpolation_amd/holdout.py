@@ -63,6 +63,7 @@ from . import resize as _resize
 from . import retime as _retime
 from .inference import _interleave_average_p10, _interleave_average_u8
 from .stream import (RAW_FORMATS, _NpyRows, _RawReader, _is_path, _npy_route, _raw_resize, _raw_route, _y4m_resize,
+                     check_packing,
                      _y4m_route, check_chunk_frames)
 
 TRIPLETS = ("sliding", "disjoint")
@@ -133,9 +134,10 @@ class _Source:
     `psnr_interleaved` call (w: samples per component and row); lead: the plane names the flow is estimated on (one:
     that plane; three: their rounded mean)."""
 
-    def __init__(self, route, reader, planes, channels, fps, close, groups=(), lead=None, rs=None):
+    def __init__(self, route, reader, planes, channels, fps, close, groups=(), lead=None, rs=None, wire=None):
         self.route, self.reader, self.channels, self.fps, self.close = route, reader, channels, fps, close
         self.rs = rs   # None or a resize.FrameResize: the reader's frames are resized to the route's after upload
+        self.wire = wire   # None or a stream._Wire: the reader's frames are unpacked to the route's rows before that
         self.planes = [tuple(p) + (p[3], 1) if len(p) == 4 else tuple(p) for p in planes]
         self.groups, self.lead = list(groups), lead or (self.planes[0][0],)
 
@@ -169,11 +171,15 @@ def raw_planes(raw: str, height: int, width: int):
     return [("y", 0, h, w, w, 1), ("u", h * w, h, cw, cw, 1), ("v", h * w + h * cw, h, cw, cw, 1)], []
 
 
-def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size=None, rfilter="linear") -> _Source:
+def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size=None, rfilter="linear",
+              packing=None) -> _Source:
     if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
         raise ValueError(f"raw={raw!r} describes headerless video; a .npy stack carries its own shape (leave raw None)")
     route = _raw_route(model, raw, height, width, False, batch, matrix, siting)
+    wire = check_packing(packing, raw, height, width)   # (the scored planes are the working format's: nothing is packed)
     wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
+    if wire is not None:
+        wire_row = 2 * wire.in_row
     rs = None
     if size is not None:   # the route, the planes and the groups of the destination size
         rs = _raw_resize(raw, route.bits, height, width, size, rfilter)
@@ -186,18 +192,19 @@ def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, si
         if stat.S_ISREG(st.st_mode):
             if st.st_size % wire_row:
                 raise ValueError(f"{os.fspath(src)}: {st.st_size} bytes is not a whole number of {width}x{height} "
-                                 f"{raw} frames of {wire_row} bytes")
+                                 f"{raw if wire is None else packing} frames of {wire_row} bytes")
             if st.st_size // wire_row < 3:
                 raise _too_short(st.st_size // wire_row)
     fin = open(src, "rb") if _is_path(src) else src
     return _Source(route, _RawReader(fin, wire_row), planes, 0, src_fps, fin.close if _is_path(src) else (lambda: None),
-                   groups, ("r", "g", "b") if raw in packed.FORMATS else ("y",), rs)
+                   groups, ("r", "g", "b") if raw in packed.FORMATS else ("y",), rs, wire)
 
 
 def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, height=None, size=None,
-          rfilter="linear") -> _Source:
+          rfilter="linear", packing=None) -> _Source:
     if raw is not None:
-        return _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter)
+        return _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter, packing)
+    check_packing(packing, raw)   # (refuses: Y4M and .npy video take no packing)
     if width is not None or height is not None:
         raise ValueError("width and height describe raw video: pass raw= with them")
     if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
@@ -390,7 +397,7 @@ def excluded_targets(cut_flags, scored_frames) -> np.ndarray:
 @torch.no_grad()
 def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch: int = 8, chunk_frames: int = 32,
                 matrix: str = "bt709", siting=None, src_fps=None, raw=None, width=None, height=None,
-                scene_cut=None, resize=None, resize_filter: str = "linear") -> dict:
+                scene_cut=None, resize=None, resize_filter: str = "linear", packing=None) -> dict:
     """Hold-out scores of `model` on a clip (methods: any of ALL_METHODS; with "optical_flow" or "motion" the result
     also has "flow_backend").  src: a path (.y4m, or a uint8 .npy stack [N,H,W] / [N,H,W,C]) or a
     readable binary file object carrying Y4M (a pipe): what `interpolate_y4m_stream` / `interpolate_npy_stream` take
@@ -407,7 +414,10 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     ground truth resized the same way; the route, planes and pixel counts are those of the new size, width / height stay
     the size of a raw source, and the result gains "resize" [W, H] and "source_size" [w, h].  resize_filter: "linear" or
     "area" (alias-free down-scaling; an error without `resize`, and where a plane would grow or shrink
-    more than 64 times); with a filter other than "linear" the result also has "resize_filter".  Every argument is
+    more than 64 times); with a filter other than "linear" the result also has "resize_filter".  packing: None, or with
+    raw="yuv422p10le" one of wire10.PACKINGS ("v210", "y210le", "p210le"): the source is tight frames of
+    that packing, unpacked on the device where a chunk is uploaded (before `resize`); the planes are scored where they
+    lie in the working format, so the result equals that of the unpacked clip.  Every argument is
     checked before any GPU work.  Returns
 
       {"frames", "triplets", "bits", "peak", "planes", "methods", "fps", "scored_frames": int64 source frame indices,
@@ -433,15 +443,18 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
         src_fps = _retime.parse_fps(src_fps)
     size = None if resize is None else _resize.check_size(resize)
     rfilter = _resize.check_resize_filter(resize, resize_filter)
-    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter)
+    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter, packing)
     try:
-        route, step, rs = source.route, _step(triplets), source.rs
+        route, step, rs, wire = source.route, _step(triplets), source.rs, source.wire
         dev = next(model.parameters()).device
 
-        def upload(a):   # (the host buffer holds frames of the source size)
+        def upload(a):   # (the host buffer holds frames of the source size, as they are on the wire)
             t = torch.from_numpy(a.view(np.int16) if route.bits == 10 else a).to(dev)
+            if wire is not None:
+                t = wire.unpack(t)
             return t if rs is None else rs(t)
-        buf = np.empty((_nominal(0, c, triplets)[1], route.row if rs is None else rs.row), dtype=route.ndtype)
+        src_row = wire.in_row if wire is not None else route.row if rs is None else rs.row
+        buf = np.empty((_nominal(0, c, triplets)[1], src_row), dtype=route.ndtype)
         have = frames = 0          # rows of buf carried over; frames read so far
         scored, parts = [], []
         sad = []                   # with scene_cut: (first interval, int64 sums) of every chunk: 8 bytes per frame

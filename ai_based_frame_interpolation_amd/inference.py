@@ -459,7 +459,7 @@ class FrameInterpolator:
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
                           chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend", raw=None,
                           width=None, height=None, dedup=None, max_gap=4, dedup_log=None, scene_log=None, resize=None,
-                          resize_filter="linear"):
+                          resize_filter="linear", packing=None):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -517,7 +517,12 @@ class FrameInterpolator:
         byte, what the same call without `resize` writes for the clip resized beforehand, for every chunk_frames.
         resize_filter: "linear", or "area" for an alias-free down-scale (every destination sample is the
         exact rounded mean of the source area it covers; refused where a plane would grow on either axis or shrink more
-        than 64 times).  Anything but "linear" is an error without `resize`."""
+        than 64 times).  Anything but "linear" is an error without `resize`.
+        packing: None, or with raw="yuv422p10le" one of "v210", "y210le", "p210le" (wire10.py): the
+        samples are yuv422p10le's, packed on the wire as 10-bit capture cards and uncompressed broadcast files carry
+        them (`ffmpeg -c:v v210 -f rawvideo`).  Input and output are tight frames of that packing; each chunk is unpacked
+        on the device after its upload and packed before its download, everything between is the yuv422p10le route, and
+        the output is that route's output packed, byte for byte.  An error with any other raw, with Y4M and with .npy."""
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
@@ -530,8 +535,11 @@ class FrameInterpolator:
             _resize.check_size(resize)
         _resize.check_resize_filter(resize, resize_filter)
         if raw is not None:
+            if packing is not None:   # (a new keyword beside raw: without it the call is what it always was)
+                run["packing"] = packing
             return stream.interpolate_raw_stream(self.model, input_path, output_path, factor, raw=raw, width=width,
                                                  height=height, matrix=matrix, siting=siting, **run)
+        stream.check_packing(packing, raw)   # (refuses: Y4M and .npy video take no packing)
         if width is not None or height is not None:
             raise ValueError("width and height describe raw video: pass raw=\"nv12\" with them")
         stream.check_retime(fps, src_fps, time_depth, retime, factor)

@@ -57,6 +57,14 @@ and everything after them see frames of the DESTINATION size only:
                  + one chunk's levels + the previous chunk's result, all at the destination size
 A resident run (`_run_whole`) uploads and resizes 64 frames at a time: the device holds the whole clip at the destination
 size and 64 frames at the source size.
+
+With `packing=` (wire10.py; raw "yuv422p10le" only) the reader, the pinned slots and their device twins
+hold v210 / y210le / p210le frames (`_Wire`): a chunk is unpacked once, right after its upload and before the resize,
+into yuv422p10le rows in a tensor of its own, and the rows about to be downloaded are packed into a device twin of
+their pinned output slot.  Everything between is the yuv422p10le route, so the output is that route's output packed:
+  host pinned    3 x (C + 2) wire frames in + 2 x (C x F + 1) wire frames out
+  device         2 x (C + 2) wire frames + (C + 2) working frames (the unpacked chunk, until its levels have run) + one
+                 chunk's levels + the previous chunk's result + 2 x (C x F + 1) wire frames out
 """
 from __future__ import annotations
 
@@ -69,7 +77,7 @@ import threading
 import numpy as np
 import torch
 
-from . import colour, imageio_lite, packed, scene
+from . import colour, imageio_lite, packed, scene, wire10
 from . import resize as _resize
 from . import retime as _retime
 from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
@@ -274,6 +282,44 @@ class _RawReader:
         return k
 
 
+class _Wire:
+    """A 10-bit 4:2:2 wire packing around the yuv422p10le raw route (wire10.py): the reader, the pinned
+    slots and their device twins hold `packing` frames - in_row int16 words a source frame, out_row an output frame (the
+    size after `resize=`) - and `unpack` / `pack` move a chunk between them and the rows of the working format, which
+    is all that resize, scene cuts, dedup, the route and the retime kernels see."""
+
+    def __init__(self, packing: str, height: int, width: int, out_height: int, out_width: int):
+        self.packing, self.src, self.dst = packing, (int(height), int(width)), (int(out_height), int(out_width))
+        self.in_row = wire10.frame_bytes(packing, *self.src) // 2    # (refuses an odd width of v210 / y210le)
+        self.out_row = wire10.frame_bytes(packing, *self.dst) // 2
+
+    def unpack(self, d: torch.Tensor) -> torch.Tensor:
+        """int16 [k, in_row] wire frames -> int16 [k, samples] working rows in a tensor of their own."""
+        out = torch.empty((d.shape[0], wire10.planar_samples(*self.src)), dtype=torch.int16, device=d.device)
+        return wire10.unpack(d, *self.src, self.packing, out=out)
+
+    def pack(self, rows: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """int16 [k, samples] working rows of the output size -> int16 [k, out_row] wire frames (`out`, or a new tensor)."""
+        if out is None:
+            out = torch.empty((rows.shape[0], self.out_row), dtype=torch.int16, device=rows.device)
+        return wire10.pack(rows, *self.dst, self.packing, out=out)
+
+
+def check_packing(packing, raw, height=None, width=None, size=None):
+    """The host checks of `packing` (None passes as None) -> a `_Wire` for `raw` video of height x width written at `size`
+    = (width, height) or None: packing describes yuv422p10le samples only, is one of wire10.PACKINGS, and v210 / y210le
+    need an even width at both sizes."""
+    if packing is None:
+        return None
+    if raw != wire10.WORKING_FORMAT:
+        raise ValueError(f"packing={packing!r} says how {wire10.WORKING_FORMAT} samples are packed on the wire: pass "
+                         f"raw=\"{wire10.WORKING_FORMAT}\" with it (got raw={raw!r}; Y4M and .npy video take no packing)")
+    if packing not in wire10.PACKINGS:
+        raise ValueError(f"packing must be one of {list(wire10.PACKINGS)} (or None), got {packing!r}")
+    oh, ow = (height, width) if size is None else (size[1], size[0])
+    return _Wire(packing, height, width, oh, ow)
+
+
 def _npy_route(model, shape, batch: int) -> _Route:
     """The .npy route for uint8 frames of `shape` ([H,W] or [H,W,C])."""
     row = int(np.prod(shape))
@@ -399,12 +445,14 @@ def _dead_and_cuts(d, bits, limit, cut_flags):
 
 @torch.no_grad()
 def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, thr, scene_log=None, plan=None,
-         mode: str = "blend", dd=None, dedup_log=None, rs=None) -> int:
+         mode: str = "blend", dd=None, dedup_log=None, rs=None, wire=None) -> int:
     """Stream `reader` through `route` into `write(rows)`; returns the number of output frames.  plan: a `retime.Plan`
     (then factor is its G): each chunk's grid is resampled to the plan's frames.  dd: None or (dead limit, max_gap),
     with a plan: repeated frames are re-timed (retime.py).  rs: None or a `resize.FrameResize`: the
     reader, the pinned input slots and their device twins hold frames of rs.row samples; each chunk is resized once,
     right after its upload, into rows of route.row samples, which is all that scene cuts, dedup and the route see.
+    wire: None or a `_Wire`: the reader and every slot hold frames of its packing; a chunk is unpacked once, right after
+    its upload and before rs, and the rows about to be downloaded are packed into the device twin of their output slot.
 
     Sizes.  A chunk is read with `look` lookahead frames behind its C + 1 own: 0, 1 with scene_cut; with dd max_gap - 1,
     and max_gap with scene_cut too.  A read that comes up short of C + 1 + look frames is the clip's last chunk, and
@@ -421,8 +469,11 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
     if plan is not None:
         out_rows = -(-tail * plan.q // plan.p) + 1
     src_row = route.row if rs is None else rs.row
+    dst_row = route.out_row
+    if wire is not None:
+        src_row, dst_row = wire.in_row, wire.out_row
     in_slots = [torch.empty((in_rows, src_row), dtype=route.tdtype).pin_memory() for _ in range(R_IN)]
-    out_slots = [torch.empty((out_rows, route.out_row), dtype=route.tdtype).pin_memory() for _ in range(R_OUT)]
+    out_slots = [torch.empty((out_rows, dst_row), dtype=route.tdtype).pin_memory() for _ in range(R_OUT)]
     in_np = [s.numpy().view(route.ndtype) for s in in_slots]
     out_np = [s.numpy().view(route.ndtype) for s in out_slots]
     free_in, filled, free_out, done = queue.Queue(), queue.Queue(), queue.Queue(), queue.Queue()
@@ -484,6 +535,8 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
     # result has the same allocation, whatever its frame count, and the grid is released before the next chunk runs
     d_out = None if plan is None else [torch.empty((out_rows, route.out_row), dtype=route.tdtype, device=dev)
                                        for _ in range(R_OUT)]
+    # the packed rows of a chunk go into a device twin of their own in the same way
+    d_wire = None if wire is None else [torch.empty(tuple(slot.shape), dtype=route.tdtype, device=dev) for slot in out_slots]
     count = route.row       # samples per frame, as scene.detect_cuts counts them
     carried = None          # int64 [1]: the previous chunk's last interval sum
     dead_before = 0         # dd: dead intervals directly before this chunk, saturated at max_gap
@@ -505,6 +558,8 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
                 up.record(h2d)
             compute.wait_event(up)
             d = d_in[j][:m]
+            if wire is not None:   # the chunk in the working format: a tensor of its own, as the resized one below
+                d = wire.unpack(d)
             if rs is not None:   # the chunk at the destination size: a tensor of its own, used on this stream alone
                 d = rs(d)
             flags = seen = None
@@ -547,10 +602,13 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
                                                     None if cuts is None else cuts[:c + ext])
                     rows = _retime.resample_table(out, entries, route.bits, out=d_out[o][:nj])
                 out = None   # the grid is used on the compute stream alone: it may go back to the allocator now
+            if wire is not None:   # (pinned slot o is free: the copy that last read d_wire[o] has completed)
+                rows = wire.pack(rows, d_wire[o][:rows.shape[0]])
+                out = None
             with torch.cuda.stream(d2h):
                 d2h.wait_stream(compute)
                 out_slots[o][:rows.shape[0]].copy_(rows, non_blocking=True)
-                if plan is None:   # `rows` is a view of this chunk's `out`, which is dropped while the copy may run;
+                if plan is None and wire is None:   # `rows` is a view of this chunk's `out`, which is dropped while the copy may run;
                     rows.record_stream(d2h)   # d_out[o] lives for the whole run and is guarded by the free_out queue
                 ev = torch.cuda.Event()
                 ev.record(d2h)
@@ -581,7 +639,7 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
 
 @torch.no_grad()
 def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode: str, n_frames=None, dd=None,
-               dedup_log=None, scene_log=None, rs=None) -> int:
+               dedup_log=None, scene_log=None, rs=None, wire=None) -> int:
     """The resident form of `_run` (rs as there: every uploaded piece is resized as it arrives, so the device holds the
     source-size frames of one piece only): the whole clip on the device as one chunk (flags once over every sample of the
     packed rows, one run of the route, one hold at the full factor; with a plan: one grid, one resample; with dd: one
@@ -591,15 +649,20 @@ def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode
     dev = next(model.parameters()).device
 
     src_row = route.row if rs is None else rs.row
+    if wire is not None:   # (as in `_run`: wire frames in, unpacked piece by piece before the resize)
+        src_row = wire.in_row
 
     def upload(a):
         t = torch.from_numpy(a.view(np.int16) if route.bits == 10 else a).to(dev)
+        if wire is not None:
+            t = wire.unpack(t)
         return t if rs is None else rs(t)
+    whole = rs is None and wire is None
     if n_frames is not None:
         frames = np.empty((n_frames, src_row), dtype=route.ndtype)
         if reader.read_into(frames, n_frames) != n_frames:
             raise ValueError("the clip has fewer frames than were counted")
-        d = upload(frames) if rs is None else torch.cat([upload(frames[i:i + 64]) for i in range(0, max(n_frames, 1), 64)])
+        d = upload(frames) if whole else torch.cat([upload(frames[i:i + 64]) for i in range(0, max(n_frames, 1), 64)])
         del frames
     else:
         parts = []
@@ -622,7 +685,7 @@ def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode
     grid = route.run(d, factor)
     _hold(flags, factor, grid)
     if plan is None:   # (the raw route without fps: the factor run's frames as they are)
-        write(grid.cpu().numpy().view(route.ndtype))
+        write((grid if wire is None else wire.pack(grid)).cpu().numpy().view(route.ndtype))
         return grid.shape[0]
     n = plan.n_out(d.shape[0])
     if dd is None:
@@ -636,7 +699,7 @@ def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode
                 dedup_log.append((peaks.cpu().numpy(), dead.copy()))
         entries = _retime.table_entries(plan, spans, 0, 0, n, d.shape[0] - 1, mode, cuts)
         rows = _retime.resample_table(grid, entries, route.bits)
-    write(rows.cpu().numpy().view(route.ndtype))
+    write((rows if wire is None else wire.pack(rows)).cpu().numpy().view(route.ndtype))
     return n
 
 
@@ -824,7 +887,7 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
                            siting: str | None = None, scene_cut: float | None = None, scene_log: list | None = None,
                            fps=None, src_fps=None, time_depth: int = 2, retime: str = "blend", dedup=None,
                            max_gap: int = 4, dedup_log: list | None = None, resize=None,
-                           resize_filter: str = "linear") -> int:
+                           resize_filter: str = "linear", packing: str | None = None) -> int:
     """Headerless raw video in (a path or a readable binary file: a pipe) -> the same format out (a path or a writable
     binary file): tight NV12 frames of height x width (`ffmpeg ... -f rawvideo -pix_fmt nv12 -`) through the RGB
     network, `interpolate_sequence_nv12` per level; or, with raw "rgb24" / "bgr24" / "rgba" / "bgra", tight packed RGB
@@ -837,7 +900,12 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     output name, the size of a regular input file (a whole number of frames) - is checked before any GPU work and
     before the output exists; a pipe that ends inside a frame is an error at that point.  Returns the output frame
     count.  resize / resize_filter: as for `interpolate_y4m_stream`: width and height stay the size of the source, the
-    output is raw video of the new size, and the format's refusals (an odd width of uyvy422 / yuyv422) apply to both sizes."""
+    output is raw video of the new size, and the format's refusals (an odd width of uyvy422 / yuyv422) apply to both sizes.
+    packing: None, or with raw "yuv422p10le" one of wire10.PACKINGS ("v210", "y210le", "p210le"; wire10.py, DESIGN.md
+    3.3s): input and output are tight frames of that 10-bit 4:2:2 packing (`ffmpeg -c:v v210 -f rawvideo`), unpacked to
+    yuv422p10le rows on the device right after each chunk's upload and packed again before its download; everything
+    between is the yuv422p10le route, and the output is, byte for byte, that route's output packed.  The file size of a
+    regular input counts wire frames (`wire10.frame_bytes`); v210 / y210le need an even width at both sizes."""
     thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
     if src_fps is None:
         raise ValueError("raw video carries no frame rate: pass src_fps")
@@ -848,7 +916,10 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     size = None if resize is None else _resize.check_size(resize)
     rfilter = _resize.check_resize_filter(resize, resize_filter)
     route = _raw_route(model, raw, height, width, npy_out, batch, matrix, siting)
+    wire = check_packing(packing, raw, height, width, size)
     wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
+    if wire is not None:
+        wire_row = 2 * wire.in_row
     rs = None
     if size is not None:
         rs = _raw_resize(raw, route.bits, height, width, size, rfilter)
@@ -865,7 +936,7 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
         if stat.S_ISREG(st.st_mode):
             if st.st_size % wire_row:
                 raise ValueError(f"{os.fspath(src)}: {st.st_size} bytes is not a whole number of {width}x{height} "
-                                 f"{raw} frames of {wire_row} bytes")
+                                 f"{raw if wire is None else packing} frames of {wire_row} bytes")
             count = st.st_size // wire_row
             if count == 0:
                 raise ValueError("no frames to interpolate")
@@ -879,9 +950,10 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
                 f.write(np.ascontiguousarray(rows).data)
             if C is None:
                 total = _run_whole(model, route, reader, write, factor, thr, plan, mode, count, dd, dedup_log,
-                                   scene_log, rs)
+                                   scene_log, rs, wire=wire)
             else:
-                total = _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log, rs)
+                total = _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log, rs,
+                             wire=wire)
             ok = True
         finally:
             finish(ok)

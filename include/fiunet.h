@@ -42,7 +42,9 @@ extern "C" {
                                      fiunet_retime_table_p10); v8 also, added the same way: resizing frame planes
                                      (fiunet_resize_plane, fiunet_resize_planes_u8, fiunet_resize_planes_p10); v8 also: the
                                      `reserved` member of fiunet_resize_plane, which had to be 0, is `filter`
-                                     (FIUNET_RESIZE_LINEAR = 0, FIUNET_RESIZE_AREA); no entry point is added */
+                                     (FIUNET_RESIZE_LINEAR = 0, FIUNET_RESIZE_AREA); no entry point is added; v8 also,
+                                     added the same way: 10-bit 4:2:2 wire packings (fiunet_packing10,
+                                     fiunet_unpack_422p10, fiunet_pack_422p10) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -429,6 +431,40 @@ int fiunet_forward_rgb_packed(fiunet_ctx* ctx, const uint8_t* frame1, const uint
                               const fiunet_packed_layout* in_layout, uint8_t* out, const fiunet_packed_layout* out_layout,
                               int B, int H, int W, int format, int precision, void* workspace, size_t workspace_bytes,
                               void* stream);
+
+/* 10-bit 4:2:2 wire packings (ABI v8, added without a version bump: nothing existing changed): v210,
+ * y210le and p210le carry the samples of yuv422p10le - FIUNET_YUV_422P at 10 bits: tight frames of uint16 words holding
+ * the code, Y H x W, then U, then V, each H x ceil(W/2) - and only the place of the bits differs.  These two entry points
+ * move the bits between a packing and that working format; everything else takes the working format.  All wire words
+ * are little-endian.
+ *   FIUNET_PACK10_V210  one plane, W even.  Group g holds pixels 6g .. 6g+5 in four 32-bit words, each with a low, a
+ *                       middle and a high 10-bit field (bits 0-9, 10-19, 20-29): w0 = U0 Y0 V0, w1 = Y1 U1 Y2,
+ *                       w2 = V1 Y3 U2, w3 = Y4 V2 Y5 (Uk, Vk: chroma sample 3g + k).  Tight row: 128 * ceil(W / 48) bytes.
+ *   FIUNET_PACK10_Y210  one plane, W even.  16-bit words Y0 U0 Y1 V0 per two pixels, each code << 6.  Tight row: 4 W bytes.
+ *   FIUNET_PACK10_P210  two planes, any W: a Y plane of H x W words, then H rows of interleaved U V pairs (2 ceil(W/2)
+ *                       words), each word code << 6: P010 with chroma of full height.
+ * Reading: bits 30-31 of a v210 word and the low six bits of a y210 / p210 word are ignored; v210 fields past column W
+ * and row padding are never interpreted.  Writing: the ignored bits are zero, v210 fields past W in the last group are
+ * zero, and so are the bytes from the end of the last group to the tight row size, so a tight frame is fully determined;
+ * bytes between the tight row and a larger pitch, and between frames, are never read and never written.  A working word
+ * above 1023 packs as 1023; no code is clamped to 4..1019.
+ * Layouts: v210 / y210le take a fiunet_packed_layout (BYTES, both even; NULL or 0 = tight) and a NULL surface layout;
+ * p210le takes a fiunet_surface_layout (SAMPLES; NULL or 0 = tight: chroma_offset H*W, chroma_pitch 2*ceil(W/2),
+ * frame_stride H*W + 2*H*ceil(W/2); the chroma plane has H rows) and a NULL packed layout.  out_frame_stride /
+ * in_frame_stride: the working frames' distance in samples (0 = tight).  With W % 8 == 0 and every base, pitch, offset
+ * and stride a multiple of 16 bytes every access is a 16-, 8- or 4-byte vector with consecutive lanes on consecutive
+ * vectors (v210 through LDS), otherwise a thread moves its 24 pixels in 16-bit accesses; both give the same bytes.
+ * Device pointers, 2-byte aligned; any H, W >= 1; asynchronous on `stream`; no allocation, no synchronisation.
+ * FIUNET_ERR_INVALID_ARG, before any launch: NULL pointers, an unknown packing, an odd W with a one-plane packing, a
+ * pitch below the tight row, a stride that does not cover a frame, an odd byte pitch or stride, the layout of the other
+ * kind; a bad shape is FIUNET_ERR_BAD_SHAPE. */
+enum fiunet_packing10 { FIUNET_PACK10_V210 = 0, FIUNET_PACK10_Y210 = 1, FIUNET_PACK10_P210 = 2 };
+int fiunet_unpack_422p10(const void* in, int packing, const fiunet_packed_layout* in_packed,
+                         const fiunet_surface_layout* in_surface, uint16_t* out, size_t out_frame_stride, int B, int H,
+                         int W, void* stream);
+int fiunet_pack_422p10(const uint16_t* in, size_t in_frame_stride, void* out, int packing,
+                       const fiunet_packed_layout* out_packed, const fiunet_surface_layout* out_surface, int B, int H,
+                       int W, void* stream);
 
 /* Scene cuts in the video loops (ABI v8, added without a version bump: nothing existing changed).  The reference has
  * no video loop; the definition is our own.  For N frames and the N-1 intervals i between F[i] and
