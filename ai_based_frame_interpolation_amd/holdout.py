@@ -6,8 +6,8 @@ chunk.
              "sliding": the reference's triplet set (model/train.py: (f[i], f[i+2]) -> f[i+1]), every frame 1 .. n-2;
              it is the disjoint evaluation of the clip together with that of the clip without its first frame.
   methods    each turns a decimated chunk d [k, row] into [2k-1, out_row] rows whose odd rows are the predictions:
-             "unet" is `route.run(d, 2)`, the forward of whatever route the clip takes (stream.py: `_y4m_route`,
-             `_npy_route`, with their refusals); "linear" the project's integer average (a + b + 1) >> 1 of every
+             "unet" is `route.run(d, 2)`, the forward of whatever route the clip takes (stream.py: the source is opened
+             by the video routes' own openers `_open_y4m`, `_open_npy`, `_open_raw`, with their refusals); "linear" the project's integer average (a + b + 1) >> 1 of every
              sample of the row; "repeat" the earlier neighbour, which is what a frame duplicator shows.  Beyond the
              default three (ALL_METHODS), the classical motion-compensated baseline: Farneback flow
              between the two neighbours on the device (optical_flow.farneback_flow, the HIP kernels; its source is the Y
@@ -22,9 +22,9 @@ chunk.
              go to `metrics.psnr_planes` / `ssim_planes` as they lie in the rows: no plane is copied.  A plane smaller
              than 7x7 gets PSNR only (its SSIM is NaN).
   raw        with `raw=` (one of stream.RAW_FORMATS, with width and height) the source is headerless tight frames, what
-             `interpolate_raw_stream` takes, through `stream._raw_route`: "y" "u" "v" for nv12, the planar 4:2:2 /
+             `interpolate_raw_stream` takes, through `stream._open_raw`: "y" "u" "v" for nv12, the planar 4:2:2 /
              4:4:4 formats and uyvy422 / yuyv422, "r" "g" "b" (and "a": the alpha of an inserted frame is what the route
-             writes, so it is scored) for packed RGB (`raw_planes`).  A plane is (name, offset, h, w, row
+             writes, so it is scored) for packed RGB (the layout table, layout.py).  A plane is (name, offset, h, w, row
              pitch, sample step): interleaved planes (U V of nv12, the bytes of packed RGB, the byte positions of the
              capture formats) are scored where they lie - all components of a group in one `metrics.psnr_interleaved`
              call per method, SSIM plane by plane through the stepped kernel.  Contiguous copies of stepped planes exist
@@ -53,18 +53,16 @@ from __future__ import annotations
 
 import math
 import os
-import stat
 
 import numpy as np
 import torch
 
-from . import colour, imageio_lite, metrics, optical_flow, packed, scene
+from . import metrics, optical_flow, packed, scene
 from . import resize as _resize
 from . import retime as _retime
 from .inference import _interleave_average_p10, _interleave_average_u8
-from .stream import (RAW_FORMATS, _NpyRows, _RawReader, _is_path, _npy_route, _raw_resize, _raw_route, _y4m_resize,
-                     check_packing,
-                     _y4m_route, check_chunk_frames)
+from .layout import frame_layout
+from .stream import _is_path, _open_npy, _open_raw, _open_y4m, check_chunk_frames, check_packing
 
 TRIPLETS = ("sliding", "disjoint")
 METHODS = ("unet", "linear", "repeat")
@@ -128,130 +126,55 @@ def _too_short(n):
 
 
 class _Source:
-    """route, reader, the planes [(name, offset in the row, h, w, row pitch, sample step)] in samples (channels: the C of
-    an [N,H,W,C] stack, whose planes are cut after a permute), the frame rate (a Fraction or None) and close().
-    groups: [(S, offset, h, w, row pitch, {plane name: component})], the interleaved groups whose PSNR comes from one
-    `psnr_interleaved` call (w: samples per component and row); lead: the plane names the flow is estimated on (one:
-    that plane; three: their rounded mean)."""
+    """What scoring adds to an opened source (`stream._Opened`: the route, the reader, `upload`, `close`): the planes
+    [(name, offset in the row, h, w, row pitch, sample step)] and the interleaved groups [(S, offset, h, w, row pitch,
+    {plane name: component})], whose PSNR comes from one `psnr_interleaved` call (w: samples per component and row), both
+    in samples as the layout table gives them; channels: the C of an [N,H,W,C] stack, whose planes are cut after a
+    permute; lead: the plane names the flow is estimated on (one: that plane; three: their rounded mean); fps: the frame
+    rate (a Fraction or None)."""
 
-    def __init__(self, route, reader, planes, channels, fps, close, groups=(), lead=None, rs=None, wire=None):
-        self.route, self.reader, self.channels, self.fps, self.close = route, reader, channels, fps, close
-        self.rs = rs   # None or a resize.FrameResize: the reader's frames are resized to the route's after upload
-        self.wire = wire   # None or a stream._Wire: the reader's frames are unpacked to the route's rows before that
-        self.planes = [tuple(p) + (p[3], 1) if len(p) == 4 else tuple(p) for p in planes]
-        self.groups, self.lead = list(groups), lead or (self.planes[0][0],)
-
-
-_PACKED_BYTES = {"rgb24": "rgb", "bgr24": "bgr", "rgba": "rgba", "bgra": "bgra"}
+    def __init__(self, opened, planes, channels=0, groups=(), lead=None, fps=None):
+        self.opened, self.channels, self.fps = opened, channels, fps
+        self.planes, self.groups = [tuple(p) for p in planes], list(groups)
+        self.lead = lead or (self.planes[0][0],)
 
 
 def raw_planes(raw: str, height: int, width: int):
-    """The planes of one tight frame of `raw` (stream.RAW_FORMATS) -> (planes [(name, offset, h, w, row pitch, sample
-    step)], groups [(S, offset, h, w, row pitch, {name: component})]), everything in samples.  Every sample of the frame
-    belongs to exactly one plane."""
-    if raw not in RAW_FORMATS:
-        raise ValueError(f"raw must be one of {list(RAW_FORMATS)}, got {raw!r}")
-    h, w = int(height), int(width)
-    hc, wc = (h + 1) // 2, (w + 1) // 2
-    if raw == "nv12":
-        return ([("y", 0, h, w, w, 1), ("u", h * w, hc, wc, 2 * wc, 2), ("v", h * w + 1, hc, wc, 2 * wc, 2)],
-                [(2, h * w, hc, wc, 2 * wc, {"u": 0, "v": 1})])
-    if raw in _PACKED_BYTES:
-        order = _PACKED_BYTES[raw]
-        s = len(order)
-        names = "rgb" + ("a" if s == 4 else "")
-        return ([(c, order.index(c), h, w, s * w, s) for c in names], [(s, 0, h, w, s * w, {c: order.index(c) for c in names})])
-    kind = colour.YUV_FORMATS[raw][2]
-    if kind == "packed":
-        colour.yuv_frame_samples(raw, h, w)   # (refuses an odd width)
-        y, u, v = (1, 0, 2) if raw == "uyvy422" else (0, 1, 3)
-        return ([("y", y, h, w, 2 * w, 2), ("u", u, h, w // 2, 2 * w, 4), ("v", v, h, w // 2, 2 * w, 4)],
-                [(2, 0, h, w, 2 * w, {"y": y}), (4, 0, h, w // 2, 2 * w, {"u": u, "v": v})])
-    cw = w if kind == "444" else wc
-    return [("y", 0, h, w, w, 1), ("u", h * w, h, cw, cw, 1), ("v", h * w + h * cw, h, cw, cw, 1)], []
-
-
-def _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size=None, rfilter="linear",
-              packing=None) -> _Source:
-    if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
-        raise ValueError(f"raw={raw!r} describes headerless video; a .npy stack carries its own shape (leave raw None)")
-    route = _raw_route(model, raw, height, width, False, batch, matrix, siting)
-    wire = check_packing(packing, raw, height, width)   # (the scored planes are the working format's: nothing is packed)
-    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
-    if wire is not None:
-        wire_row = 2 * wire.in_row
-    rs = None
-    if size is not None:   # the route, the planes and the groups of the destination size
-        rs = _raw_resize(raw, route.bits, height, width, size, rfilter)
-        route = _raw_route(model, raw, size[1], size[0], False, batch, matrix, siting)
-    planes, groups = raw_planes(raw, height, width) if size is None else raw_planes(raw, size[1], size[0])
-    if _is_path(src):
-        if not os.path.exists(src):
-            raise FileNotFoundError(f"Video file not found: {src}")
-        st = os.stat(src)
-        if stat.S_ISREG(st.st_mode):
-            if st.st_size % wire_row:
-                raise ValueError(f"{os.fspath(src)}: {st.st_size} bytes is not a whole number of {width}x{height} "
-                                 f"{raw if wire is None else packing} frames of {wire_row} bytes")
-            if st.st_size // wire_row < 3:
-                raise _too_short(st.st_size // wire_row)
-    fin = open(src, "rb") if _is_path(src) else src
-    return _Source(route, _RawReader(fin, wire_row), planes, 0, src_fps, fin.close if _is_path(src) else (lambda: None),
-                   groups, ("r", "g", "b") if raw in packed.FORMATS else ("y",), rs, wire)
+    """The planes and the interleaved groups of one tight frame of `raw` (stream.RAW_FORMATS), in samples: the layout
+    table's (`layout.frame_layout`) -> (planes, groups)."""
+    return frame_layout(raw, height, width)[:2]
 
 
 def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, height=None, size=None,
           rfilter="linear", packing=None) -> _Source:
+    """The source of a scoring run through the video routes' openers, with their refusals; a clip whose frame count is
+    known up front has at least three frames."""
+    npy = _is_path(src) and os.fspath(src).lower().endswith(".npy")
+    channels, lead, fps = 0, None, src_fps
     if raw is not None:
-        return _open_raw(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter, packing)
-    check_packing(packing, raw)   # (refuses: Y4M and .npy video take no packing)
-    if width is not None or height is not None:
-        raise ValueError("width and height describe raw video: pass raw= with them")
-    if _is_path(src) and os.fspath(src).lower().endswith(".npy"):
-        mm = np.load(src, mmap_mode="r")
-        if mm.dtype != np.uint8 or mm.ndim not in (3, 4):
-            raise ValueError("expected a uint8 .npy stack [N,H,W] or [N,H,W,3]")
-        shape, rs = tuple(mm.shape[1:]), None
-        if size is not None:
-            kind = "npy" if len(shape) == 2 else ("npy", shape[2])
-            rs = _resize.FrameResize(_resize.frame_planes(kind, shape[0], shape[1]),
-                                     _resize.frame_planes(kind, size[1], size[0]), 8, size, (shape[1], shape[0]),
-                                     rfilter)
-            shape = (size[1], size[0]) + shape[2:]
-        route = _npy_route(model, shape, batch)
-        if mm.shape[0] < 3:
-            raise _too_short(mm.shape[0])
-        h, w = shape[:2]
-        if mm.ndim == 3:
-            planes, channels = [("gray", 0, h, w)], 0
+        if npy:
+            raise ValueError(f"raw={raw!r} describes headerless video; a .npy stack carries its own shape (leave raw None)")
+        opened = _open_raw(model, src, raw, width, height, False, batch, matrix, siting, size, rfilter, packing)
+        if raw in packed.FORMATS:
+            lead = ("r", "g", "b")
+    else:
+        check_packing(packing, raw)   # (refuses: Y4M and .npy video take no packing)
+        if width is not None or height is not None:
+            raise ValueError("width and height describe raw video: pass raw= with them")
+        if npy:
+            opened = _open_npy(model, src, batch, size, rfilter)
+            channels = opened.shape[2] if len(opened.shape) == 3 else 0
         else:
-            channels = mm.shape[3]
-            planes = [(f"c{i}", i * h * w, h, w) for i in range(channels)]
-        return _Source(route, _NpyRows(mm), planes, channels, src_fps, lambda: None, rs=rs)
-    reader = imageio_lite.Y4MReader(src)
-    try:
-        hdr, rs = reader.header, None
-        if size is not None:
-            rs, hdr = _y4m_resize(hdr, size, rfilter), _resize.y4m_header_at(hdr, size)
-        route = _y4m_route(model, hdr, False, batch, matrix, siting)
-        h, w, (hc, wc) = hdr["height"], hdr["width"], hdr["chroma"]
-        planes = [("y", 0, h, w)]
-        if hc * wc:
-            planes += [("u", h * w, hc, wc), ("v", h * w + hc * wc, hc, wc)]
-        fps = src_fps
-        if fps is None:
-            try:
-                fps = _retime.parse_fps(tuple(int(v) for v in hdr["fps"]))
-            except ValueError:
-                fps = None
-        if _is_path(src) and os.path.isfile(src):
-            n = imageio_lite.y4m_frame_count(src)
-            if n < 3:
-                raise _too_short(n)
-    except BaseException:
-        reader.close()
-        raise
-    return _Source(route, reader, planes, 0, fps, reader.close, rs=rs)
+            opened = _open_y4m(model, src, False, batch, matrix, siting, size, rfilter, count=True)
+            if fps is None:
+                try:
+                    fps = _retime.parse_fps(tuple(int(v) for v in opened.fps))
+                except ValueError:
+                    pass
+    if opened.count is not None and opened.count < 3:
+        opened.close()
+        raise _too_short(opened.count)
+    return _Source(opened, opened.layout.planes, channels, opened.layout.groups, lead, fps)
 
 
 # ---- one chunk on the device ----------------------------------------------------------------------------------------
@@ -269,7 +192,7 @@ def _predict(method: str, route, d: torch.Tensor) -> torch.Tensor:
 def _predict_flow(methods, source: _Source, d: torch.Tensor, batch: int) -> dict:
     """The k-1 predicted rows of a decimated chunk d [k, row] for each of the flow methods asked for: one flow per
     pair, shared by the methods, `batch` pairs at a time (a pair's flow and warp do not depend on the pairs beside it)."""
-    bits, k = source.route.bits, d.shape[0]
+    bits, k = source.opened.route.bits, d.shape[0]
     if source.channels:   # [N,H,W,C]: planar copies, flow on the rounded channel mean
         c = source.channels
         _, _, h, w = source.planes[0][:4]
@@ -329,7 +252,7 @@ def _group_views(rows: torch.Tensor, source: _Source):
 def _score_chunk(source: _Source, methods, d_all: torch.Tensor, n_targets: int, step: int, batch: int = 8):
     """-> {method: {plane: (psnr, ssim, sse)}}, host arrays over the chunk's targets in order."""
     flow_methods = [m for m in methods if m in FLOW_METHODS]
-    bits = source.route.bits
+    bits = source.opened.route.bits
     res = {m: {p[0]: (np.empty(n_targets), np.full(n_targets, np.nan), np.empty(n_targets, np.uint64))
                for p in source.planes} for m in methods}
     grouped = {name for g in source.groups for name in g[5]}
@@ -343,7 +266,7 @@ def _score_chunk(source: _Source, methods, d_all: torch.Tensor, n_targets: int, 
         where = slice(off, None, 2) if step == 1 else slice(None)
         flowed = _predict_flow(flow_methods, source, d, batch) if flow_methods else {}
         for m in methods:
-            rows = flowed[m] if m in flowed else _predict(m, source.route, d)
+            rows = flowed[m] if m in flowed else _predict(m, source.opened.route, d)
             # every component of an interleaved group in one pass over its samples
             for g, p, t in zip(source.groups, _group_views(rows, source), truth_groups):
                 ps, sse = metrics.psnr_interleaved(p, t, bits, return_sse=True)
@@ -445,23 +368,20 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     rfilter = _resize.check_resize_filter(resize, resize_filter)
     source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter, packing)
     try:
-        route, step, rs, wire = source.route, _step(triplets), source.rs, source.wire
+        opened, step = source.opened, _step(triplets)
+        route, rs = opened.route, opened.rs
         dev = next(model.parameters()).device
 
-        def upload(a):   # (the host buffer holds frames of the source size, as they are on the wire)
-            t = torch.from_numpy(a.view(np.int16) if route.bits == 10 else a).to(dev)
-            if wire is not None:
-                t = wire.unpack(t)
-            return t if rs is None else rs(t)
-        src_row = wire.in_row if wire is not None else route.row if rs is None else rs.row
-        buf = np.empty((_nominal(0, c, triplets)[1], src_row), dtype=route.ndtype)
+        def upload(a):   # (the host buffer holds frames as they are on the wire: the source size, the packing)
+            return opened.upload(a, dev)
+        buf = np.empty((_nominal(0, c, triplets)[1], opened.row), dtype=route.ndtype)
         have = frames = 0          # rows of buf carried over; frames read so far
         scored, parts = [], []
         sad = []                   # with scene_cut: (first interval, int64 sums) of every chunk: 8 bytes per frame
         i = 0
         while True:
             first, want = _nominal(i, c, triplets)
-            got = source.reader.read_into(buf[have:], want - have)
+            got = opened.reader.read_into(buf[have:], want - have)
             frames += got
             span = _span(i, frames, c, triplets)
             count = 0 if span is None else span[1]
@@ -487,7 +407,7 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
         if frames < 3:
             raise _too_short(frames)
     finally:
-        source.close()
+        opened.close()
     peak = 255 if route.bits == 8 else 1023
     names = [p[0] for p in source.planes]
     per = {m: {p: {key: np.concatenate([part[m][p][j] for part in parts])

@@ -9,8 +9,8 @@ descriptors, and an area filter for alias-free down-scaling as a second kernel o
               + 2^21) >> 22, 1023) with samples above 1023 read as 1023 (OpenCV's ushort path is float arithmetic, whose
               bits hang on summation order).  A destination of the source's size is a copy, sample for sample.
               tests/resize_ref.py restates all of it in numpy.
-  planes      a plane is (name, offset, h, w, row pitch, sample step) in samples of one tight frame, what
-              `holdout.raw_planes` gives for raw video; `frame_planes` gives the same for Y4M and .npy frames.  Every
+  planes      a plane is (name, offset, h, w, row pitch, sample step) in samples of one tight frame, what the layout
+              table (layout.py) gives for every frame kind: raw video, Y4M and .npy; `frame_planes` forwards to it.  Every
               plane of the source format is resampled on its own grid into the same plane of the destination format;
               chroma planes get the size the format gives at the destination size.
   aliasing    the linear filter reads two samples per axis whatever the scale: a large down-scale aliases, as it does in
@@ -34,6 +34,7 @@ import re
 import torch
 
 from . import _native, imageio_lite
+from .layout import frame_layout, frame_samples
 
 MAX_PLANES = 4   # csrc/resize.hip.h kResizeMaxPlanes: plane pairs per launch
 FILTERS = {"linear": _native.RESIZE_LINEAR, "area": _native.RESIZE_AREA}
@@ -96,38 +97,9 @@ def y4m_header_at(hdr: dict, size) -> dict:
 
 
 def frame_planes(kind, h: int, w: int):
-    """The planes [(name, offset, h, w, row pitch, sample step)] of one tight h x w frame, in samples; every sample of
-    the frame belongs to exactly one plane.  kind: a name of `stream.RAW_FORMATS` (through `holdout.raw_planes`);
-    ("y4m", tag) for a Y4M stream of colourspace `tag` ("mono", "420jpeg", "420p10", ...: Y, then U and V of the chroma
-    size the header parser derives); "npy" for a [H,W] frame, ("npy", C) for [H,W,C]."""
-    h, w = int(h), int(w)
-    if h < 1 or w < 1:
-        raise ValueError(f"a frame's height and width must be positive, got {h} x {w}")
-    if kind == "npy":
-        return [("gray", 0, h, w, w, 1)]
-    if isinstance(kind, tuple) and len(kind) == 2 and kind[0] == "npy":
-        c = int(kind[1])
-        if c < 1:
-            raise ValueError(f"an [H,W,C] frame has at least one channel, got {kind[1]!r}")
-        return [(f"c{i}", i, h, w, c * w, c) for i in range(c)]
-    if isinstance(kind, tuple) and len(kind) == 2 and kind[0] == "y4m":
-        tag = str(kind[1])
-        bits = 10 if tag in imageio_lite.Y4M_P10_TAGS else 8
-        hdr = imageio_lite._y4m_stream_header(imageio_lite._y4m_header_line(w, h, (30, 1), tag, None, bits), bits)
-        hc, wc = hdr["chroma"]
-        planes = [("y", 0, h, w, w, 1)]
-        if hc * wc:
-            planes += [("u", h * w, hc, wc, wc, 1), ("v", h * w + hc * wc, hc, wc, wc, 1)]
-        return planes
-    if isinstance(kind, str):
-        from . import holdout   # (holdout imports stream, which imports this module)
-        return [tuple(p) for p in holdout.raw_planes(kind, h, w)[0]]
-    raise ValueError(f"unknown frame kind {kind!r}")
-
-
-def frame_samples(planes) -> int:
-    """Samples of the tight frame that `planes` describe (the end of its last sample)."""
-    return max(off + (h - 1) * pitch + (w - 1) * step + 1 for _, off, h, w, pitch, step in planes)
+    """The planes [(name, offset, h, w, row pitch, sample step)] of one tight h x w frame of `kind`, in samples: the
+    layout table's (`layout.frame_layout`, which names the kinds)."""
+    return [tuple(p) for p in frame_layout(kind, h, w).planes]
 
 
 def _launch(src, src_planes, dst, dst_planes, n: int, bits: int, stream=None, filter: str = "linear") -> None:

@@ -1,7 +1,11 @@
 """The video routes: interpolate a clip of any length, from a file or a pipe, whole or in memory bounded by the chunk.
 
 There is one implementation of each route (`_y4m_route`, `_npy_route`, `_raw_route`: what it computes, refuses and
-writes); `FrameInterpolator.interpolate_video` dispatches into the three `interpolate_*_stream` functions here.
+writes; `row` and `bits` from the layout table, layout.py); `FrameInterpolator.interpolate_video` dispatches into the
+three `interpolate_*_stream` functions here.  A source is opened in one place (`_open_y4m`, `_open_npy`, `_open_raw` ->
+`_Opened`: every host-side check of the source, the route at the destination size, the reader, the resize, the packing,
+`ingest` and `upload`), which hold-out scoring (holdout.py) uses too; `_job` turns a route's keyword arguments into the
+`_Job` that the engines take as `_run(model, route, reader, write, job)` / `_run_whole(...)`.
 "Resident" (chunk_frames=None) means one chunk: `_run_whole` holds the whole clip in host memory and on the device.
 `_run` takes the same route chunk by chunk:
 
@@ -68,6 +72,7 @@ their pinned output slot.  Everything between is the yuv422p10le route, so the o
 """
 from __future__ import annotations
 
+import dataclasses
 import numbers
 import os
 import queue
@@ -80,6 +85,7 @@ import torch
 from . import colour, imageio_lite, packed, scene, wire10
 from . import resize as _resize
 from . import retime as _retime
+from .layout import RAW_FORMATS, frame_layout
 from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
                         interpolate_sequence_nv12, interpolate_sequence_p10, interpolate_sequence_rgb_packed,
                         interpolate_sequence_yuv, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10)
@@ -139,8 +145,9 @@ def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
     """The route of Y4M video for this stream header and model, with its refusals and messages: the RGB network on
     4:2:0 frames (8-bit: siting from the tag; `C420p10`: siting None is "mpeg2"; range from `XCOLORRANGE`), or the
     grayscale network on the luma plane with the chroma of an inserted frame the rounded average of its neighbours'."""
-    h, w, (hc, wc), bits = hdr["height"], hdr["width"], hdr["chroma"], hdr["bits"]
-    ny, nc, row = h * w, hc * wc, hdr["frame_samples"]
+    h, w, (hc, wc) = hdr["height"], hdr["width"], hdr["chroma"]
+    _, _, bits, row = frame_layout(("y4m", hdr["colourspace"]), h, w)
+    ny, nc = h * w, hc * wc
     if model.frame_channels == 3:
         rng = "full" if hdr["colour_range"] == "FULL" else "limited"
         if bits == 10:
@@ -202,9 +209,6 @@ def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
     return _Route(bits, row, out_row, run)
 
 
-RAW_FORMATS = ("nv12", "rgb24", "bgr24", "rgba", "bgra") + tuple(colour.YUV_FORMATS)
-
-
 def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, siting) -> _Route:
     """The route of headerless raw video (`raw`: one of RAW_FORMATS, tight frames), with its refusals.  Nothing in the
     stream says how it was made: for "nv12" siting None is "mpeg2" (what decoders produce) and the range is limited.
@@ -223,17 +227,14 @@ def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, sit
     if npy_out:
         raise ValueError(f"raw {raw} video through the RGB network is written as raw {raw} (no .npy output)")
     h, w = int(height), int(width)
+    _, _, bits, row = frame_layout(raw, h, w)   # (refuses an odd width of uyvy422 / yuyv422)
     if raw in packed.FORMATS:
-        row = packed.frame_bytes(raw, h, w)
-
         def run_packed(d, factor):
             for _ in range(_levels(factor)):
                 d = interpolate_sequence_rgb_packed(model, d, h, w, raw, batch)
             return d
         return _Route(8, row, row, run_packed)
     if raw in colour.YUV_FORMATS:
-        bits = colour.YUV_FORMATS[raw][1]
-        row = colour.yuv_frame_samples(raw, h, w)   # (refuses an odd width of uyvy422 / yuyv422)
         opts = dict(siting=siting, matrix=matrix, colour_range="limited")
         colour.yuv_flags(raw, **opts)
 
@@ -245,7 +246,6 @@ def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, sit
         return _Route(bits, row, row, run_yuv)
     opts = dict(siting="mpeg2" if siting is None else siting, matrix=matrix, colour_range="limited")
     colour.colour_flags(**opts)
-    row = colour.i420_frame_bytes(h, w)
 
     def run(d, factor):
         for _ in range(_levels(factor)):
@@ -392,6 +392,106 @@ class _NpyWriter:
             os.remove(self.part)
 
 
+# ---- opened sources: every host-side check of a source, no GPU work ----------------------------------------------------
+class _Opened:
+    """An opened video source, what the video routes and hold-out scoring (holdout.py) run on.  route: the route at the
+    destination size; reader: `read_into` over frames as they are on the wire; rs: None or the `resize.FrameResize` from
+    the source size; wire: None or the `_Wire` of the packing; layout: the `layout.Layout` of a route frame (the
+    destination size, the working format); row / out_row: samples per frame as read / as written; count: the frame
+    count where it is known up front (a regular file), else None; header: the Y4M header at the destination size (else
+    None) and fps its rate; shape: the destination shape of a .npy frame (else None); close(): releases the source."""
+
+    def __init__(self, route, reader, layout, rs=None, wire=None, count=None, header=None, shape=None, close=None):
+        self.route, self.reader, self.layout, self.rs, self.wire = route, reader, layout, rs, wire
+        self.count, self.header, self.shape = count, header, shape
+        self.fps = None if header is None else header["fps"]
+        self.close = close or (lambda: None)
+        self.row = wire.in_row if wire is not None else route.row if rs is None else rs.row
+        self.out_row = route.out_row if wire is None else wire.out_row
+
+    def ingest(self, d: torch.Tensor) -> torch.Tensor:
+        """Device frames as read [k, row] -> the route's rows [k, route.row]: unpacked, then resized, each into a tensor
+        of its own (neither: `d` itself)."""
+        if self.wire is not None:
+            d = self.wire.unpack(d)
+        return d if self.rs is None else self.rs(d)
+
+    def upload(self, a: np.ndarray, device) -> torch.Tensor:
+        """Host frames as read -> the route's rows on `device` (10 bits: the uint16 words as int16)."""
+        return self.ingest(torch.from_numpy(a.view(np.int16) if self.route.bits == 10 else a).to(device))
+
+
+def _is_file(src) -> bool:
+    return _is_path(src) and stat.S_ISREG(os.stat(src).st_mode)
+
+
+def _resized(kind, height, width, size, rfilter):
+    """-> (None or the `resize.FrameResize` of tight `kind` frames of height x width to `size` = (width, height), the
+    layout at the size that results)."""
+    lay = frame_layout(kind, height, width)
+    if size is None:
+        return None, lay
+    dst = frame_layout(kind, size[1], size[0])
+    return _resize.FrameResize(lay.planes, dst.planes, lay.bits, size, (int(width), int(height)), rfilter), dst
+
+
+def _open_y4m(model, src, npy_out: bool, batch, matrix, siting, size, rfilter, count: bool) -> _Opened:
+    """Y4M from a path or a readable binary file.  count: whether the frames of a regular file are counted (one pass
+    over its FRAME lines)."""
+    if npy_out and not _is_file(src):
+        raise ValueError("a .npy output needs the frame count up front, and a Y4M stream from a pipe cannot be "
+                         "counted before it is read: write Y4M, or read the stream from a regular file")
+    reader = imageio_lite.Y4MReader(src)
+    try:
+        hdr = reader.header
+        rs, lay = _resized(("y4m", hdr["colourspace"]), hdr["height"], hdr["width"], size, rfilter)
+        if size is not None:   # everything from here on is a clip of the new size; the reader keeps the source's
+            hdr = _resize.y4m_header_at(hdr, size)
+        route = _y4m_route(model, hdr, npy_out, batch, matrix, siting)
+        n = imageio_lite.y4m_frame_count(src) if count and _is_file(src) else None
+    except BaseException:
+        reader.close()
+        raise
+    return _Opened(route, reader, lay, rs, count=n, header=hdr, close=reader.close)
+
+
+def _open_npy(model, src, batch, size, rfilter) -> _Opened:
+    """A uint8 .npy stack [N,H,W] or [N,H,W,C], memory-mapped."""
+    mm = np.load(src, mmap_mode="r")
+    if mm.dtype != np.uint8 or mm.ndim not in (3, 4):
+        raise ValueError("expected a uint8 .npy stack [N,H,W] or [N,H,W,3]")
+    shape = tuple(mm.shape[1:])
+    rs, lay = _resized("npy" if len(shape) == 2 else ("npy", shape[2]), shape[0], shape[1], size, rfilter)
+    if size is not None:
+        shape = (size[1], size[0]) + shape[2:]
+    return _Opened(_npy_route(model, shape, batch), _NpyRows(mm), lay, rs, count=mm.shape[0], shape=shape)
+
+
+def _open_raw(model, src, raw, width, height, npy_out: bool, batch, matrix, siting, size, rfilter, packing) -> _Opened:
+    """Headerless tight `raw` frames (or, with `packing`, wire frames) of height x width from a path or a readable binary
+    file; a regular file must hold a whole number of them."""
+    route = _raw_route(model, raw, height, width, npy_out, batch, matrix, siting)
+    wire = check_packing(packing, raw, height, width, size)
+    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
+    if wire is not None:
+        wire_row = 2 * wire.in_row
+    rs, lay = _resized(raw, height, width, size, rfilter)
+    if size is not None:
+        route = _raw_route(model, raw, size[1], size[0], npy_out, batch, matrix, siting)
+    count = None
+    if _is_path(src):
+        if not os.path.exists(src):
+            raise FileNotFoundError(f"Video file not found: {src}")
+        st = os.stat(src)
+        if stat.S_ISREG(st.st_mode):
+            if st.st_size % wire_row:
+                raise ValueError(f"{os.fspath(src)}: {st.st_size} bytes is not a whole number of {width}x{height} "
+                                 f"{raw if wire is None else packing} frames of {wire_row} bytes")
+            count = st.st_size // wire_row
+    fin = open(src, "rb") if _is_path(src) else src
+    return _Opened(route, _RawReader(fin, wire_row), lay, rs, wire, count, close=fin.close if _is_path(src) else None)
+
+
 # ---- the engine ---------------------------------------------------------------------------------------------------
 class _Failure:
     def __init__(self):
@@ -443,16 +543,33 @@ def _dead_and_cuts(d, bits, limit, cut_flags):
     return peaks, host[0], host[1]
 
 
+@dataclasses.dataclass
+class _Job:
+    """What a run is asked to do, beside (model, route, reader, write): the engines' fifth argument.  source: the
+    `_Opened` source (`ingest`, `row`, `out_row`, `count`, `wire`); factor: the frames per interval of the levels (with
+    fps: the plan's G); chunk_frames: None for a resident run; thr: the scene-cut threshold or None; plan: None or a
+    `retime.Plan`: each chunk's grid is resampled to the plan's frames; mode: the retime mode; dd: None or (dead limit,
+    max_gap), with a plan: repeated frames are re-timed (retime.py); rate: the output's frame rate (n, d)
+    where the source's header carries one; scene_log / dedup_log: None or the lists that receive each chunk's arrays."""
+    source: _Opened
+    factor: int
+    chunk_frames: int | None = None
+    thr: float | None = None
+    plan: object = None
+    mode: str = "blend"
+    dd: tuple | None = None
+    rate: tuple | None = None
+    scene_log: list | None = None
+    dedup_log: list | None = None
+
+
 @torch.no_grad()
-def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, thr, scene_log=None, plan=None,
-         mode: str = "blend", dd=None, dedup_log=None, rs=None, wire=None) -> int:
-    """Stream `reader` through `route` into `write(rows)`; returns the number of output frames.  plan: a `retime.Plan`
-    (then factor is its G): each chunk's grid is resampled to the plan's frames.  dd: None or (dead limit, max_gap),
-    with a plan: repeated frames are re-timed (retime.py).  rs: None or a `resize.FrameResize`: the
-    reader, the pinned input slots and their device twins hold frames of rs.row samples; each chunk is resized once,
-    right after its upload, into rows of route.row samples, which is all that scene cuts, dedup and the route see.
-    wire: None or a `_Wire`: the reader and every slot hold frames of its packing; a chunk is unpacked once, right after
-    its upload and before rs, and the rows about to be downloaded are packed into the device twin of their output slot.
+def _run(model, route: _Route, reader, write, job: _Job) -> int:
+    """Stream `reader` through `route` into `write(rows)` as `job` says; returns the number of output frames.  The
+    reader, the pinned input slots and their device twins hold frames as read (source.row samples: the source size, the
+    packing); each chunk goes through `source.ingest` once, right after its upload, into rows of route.row samples, which
+    is all that scene cuts, dedup and the route see.  With a packing the rows about to be downloaded are packed into the
+    device twin of their output slot.
 
     Sizes.  A chunk is read with `look` lookahead frames behind its C + 1 own: 0, 1 with scene_cut; with dd max_gap - 1,
     and max_gap with scene_cut too.  A read that comes up short of C + 1 + look frames is the clip's last chunk, and
@@ -461,17 +578,16 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
     hold C + 1 + look frames, and the reader carries 1 + look of them over.  (C = 1, max_gap 4: 5 frames per read, 4
     carried; a clip of 4 frames is one last chunk of 3 intervals, one of 5 a chunk of 1 interval and a last of 3.)"""
     dev = next(model.parameters()).device
-    C, look = chunk_frames, 1 if thr is not None else 0
+    source, factor, thr, plan, mode, dd = job.source, job.factor, job.thr, job.plan, job.mode, job.dd
+    scene_log, dedup_log, wire = job.scene_log, job.dedup_log, source.wire
+    C, look = job.chunk_frames, 1 if thr is not None else 0
     if dd is not None:
         look = dd[1] if thr is not None else dd[1] - 1
     tail = C + max(look - 1, 0)
     in_rows, out_rows = C + 1 + look, tail * factor + 1
     if plan is not None:
         out_rows = -(-tail * plan.q // plan.p) + 1
-    src_row = route.row if rs is None else rs.row
-    dst_row = route.out_row
-    if wire is not None:
-        src_row, dst_row = wire.in_row, wire.out_row
+    src_row, dst_row = source.row, source.out_row
     in_slots = [torch.empty((in_rows, src_row), dtype=route.tdtype).pin_memory() for _ in range(R_IN)]
     out_slots = [torch.empty((out_rows, dst_row), dtype=route.tdtype).pin_memory() for _ in range(R_OUT)]
     in_np = [s.numpy().view(route.ndtype) for s in in_slots]
@@ -557,11 +673,7 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
                 up = torch.cuda.Event()
                 up.record(h2d)
             compute.wait_event(up)
-            d = d_in[j][:m]
-            if wire is not None:   # the chunk in the working format: a tensor of its own, as the resized one below
-                d = wire.unpack(d)
-            if rs is not None:   # the chunk at the destination size: a tensor of its own, used on this stream alone
-                d = rs(d)
+            d = source.ingest(d_in[j][:m])   # unpacked, resized: tensors of their own, used on this stream alone
             flags = seen = None
             if thr is not None and c > 0:
                 sums = scene.pair_sad([d], route.bits)   # c own intervals, then the lookahead intervals that were read
@@ -638,26 +750,20 @@ def _run(model, route: _Route, reader, write, factor: int, chunk_frames: int, th
 
 
 @torch.no_grad()
-def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode: str, n_frames=None, dd=None,
-               dedup_log=None, scene_log=None, rs=None, wire=None) -> int:
-    """The resident form of `_run` (rs as there: every uploaded piece is resized as it arrives, so the device holds the
-    source-size frames of one piece only): the whole clip on the device as one chunk (flags once over every sample of the
-    packed rows, one run of the route, one hold at the full factor; with a plan: one grid, one resample; with dd: one
-    read of the dead and cut flags, one table).  n_frames: the
-    clip's frame count where it is known up front (a regular file): the clip is then read into one array; a stream of
-    unknown length is uploaded 64 frames at a time, so that the host never holds it twice."""
+def _run_whole(model, route: _Route, reader, write, job: _Job) -> int:
+    """The resident form of `_run` (every uploaded piece goes through `source.upload` as it arrives, so the device holds
+    the frames of one piece only as they were read): the whole clip on the device as one chunk (flags once over every
+    sample of the packed rows, one run of the route, one hold at the full factor; with a plan: one grid, one resample;
+    with dd: one read of the dead and cut flags, one table).  Where source.count, the clip's frame count, is known up
+    front (a regular file) the clip is read into one array; a stream of unknown length is uploaded 64 frames at a time,
+    so that the host never holds it twice."""
     dev = next(model.parameters()).device
-
-    src_row = route.row if rs is None else rs.row
-    if wire is not None:   # (as in `_run`: wire frames in, unpacked piece by piece before the resize)
-        src_row = wire.in_row
+    source, factor, thr, plan, mode, dd = job.source, job.factor, job.thr, job.plan, job.mode, job.dd
+    scene_log, dedup_log, wire, n_frames, src_row = job.scene_log, job.dedup_log, source.wire, source.count, source.row
 
     def upload(a):
-        t = torch.from_numpy(a.view(np.int16) if route.bits == 10 else a).to(dev)
-        if wire is not None:
-            t = wire.unpack(t)
-        return t if rs is None else rs(t)
-    whole = rs is None and wire is None
+        return source.upload(a, dev)
+    whole = source.rs is None and wire is None
     if n_frames is not None:
         frames = np.empty((n_frames, src_row), dtype=route.ndtype)
         if reader.read_into(frames, n_frames) != n_frames:
@@ -703,20 +809,6 @@ def _run_whole(model, route: _Route, reader, write, factor: int, thr, plan, mode
     return n
 
 
-def _y4m_resize(hdr, size, filter: str = "linear") -> "_resize.FrameResize":
-    """The resize of the frames of a Y4M stream with header `hdr` to `size` = (width, height)."""
-    kind = ("y4m", hdr["colourspace"])
-    return _resize.FrameResize(_resize.frame_planes(kind, hdr["height"], hdr["width"]),
-                               _resize.frame_planes(kind, size[1], size[0]), hdr["bits"], size,
-                               (hdr["width"], hdr["height"]), filter)
-
-
-def _raw_resize(raw, bits, height, width, size, filter: str = "linear") -> "_resize.FrameResize":
-    """The resize of tight `raw` frames of height x width to `size` = (width, height)."""
-    return _resize.FrameResize(_resize.frame_planes(raw, height, width), _resize.frame_planes(raw, size[1], size[0]),
-                               bits, size, (int(width), int(height)), filter)
-
-
 def _plan_of(fps, src_fps, header_fps, depth):
     """The plan of a checked `fps` (None: no plan) against `src_fps`, or the stream header's rate when that is None."""
     if fps is None:
@@ -730,6 +822,47 @@ def _plan_of(fps, src_fps, header_fps, depth):
             raise ValueError(f"the Y4M header's frame rate F{header_fps[0]}:{header_fps[1]} is not a rate: pass "
                              "src_fps") from None
     return _retime.plan(src_fps, fps, depth)
+
+
+def _job(open_source, *, factor, batch, chunk_frames, scene_cut, scene_log, fps, src_fps, time_depth, retime, dedup,
+         max_gap, dedup_log, resize, resize_filter, headerless: bool = False) -> _Job:
+    """The job of a route's keyword arguments: every check that needs no source, in the routes' order; then
+    `open_source(size, filter)` -> the `_Opened` source, with its own checks; then the plan, which may need the source's
+    rate.  headerless: the stream carries no rate, so src_fps is required.  Nothing here touches the device; a
+    refusal after the source was opened closes it."""
+    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
+    if headerless:
+        if src_fps is None:
+            raise ValueError("raw video carries no frame rate: pass src_fps")
+        _retime.parse_fps(src_fps)
+    fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
+    tol, gap = check_dedup(dedup, max_gap, fps, factor)
+    size = None if resize is None else _resize.check_size(resize)
+    source = open_source(size, _resize.check_resize_filter(resize, resize_filter))
+    try:
+        plan, rate = _plan_of(fps, src_fps, source.fps, depth), None
+        if plan is not None:
+            factor, rate = plan.G, (plan.fps.numerator, plan.fps.denominator)
+        elif source.fps is not None:
+            rate = (source.fps[0] * factor, source.fps[1])
+        plan, dd = _dedup_of(tol, gap, plan, factor)   # (without fps: p / q = 1 / factor; the rate as above)
+    except BaseException:
+        source.close()
+        raise
+    return _Job(source, factor, C, thr, plan, mode, dd, rate, scene_log, dedup_log)
+
+
+def _drive(model, job: _Job, make_write, finish) -> int:
+    """Run `job` into the sink: make_write() -> write(rows), made once the sink is open; finish(ok) closes the sink.
+    `_run` and `_run_whole` are looked up when the job runs (tests replace them)."""
+    ok = False
+    try:
+        engine = _run_whole if job.chunk_frames is None else _run
+        total = engine(model, job.source.route, job.source.reader, make_write(), job)
+        ok = True
+    finally:
+        finish(ok)
+    return total
 
 
 def _open_sink(dst):
@@ -773,60 +906,24 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     refusals, scene cuts, dedup and the output header are those of a clip of that size.  resize_filter: "linear" (the
     filter of cv2.resize's INTER_LINEAR) or "area" (alias-free down-scaling, DESIGN.md 3.3r: refused where a plane would
     grow on either axis, or shrink more than 64 times); anything but "linear" is an error without `resize`."""
-    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
-    fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
-    tol, gap = check_dedup(dedup, max_gap, fps, factor)
-    size = None if resize is None else _resize.check_size(resize)
-    rfilter = _resize.check_resize_filter(resize, resize_filter)
-    npy_out = isinstance(dst, (str, os.PathLike)) and os.fspath(dst).lower().endswith(".npy")
-    if npy_out:
-        if not _is_path(src) or not stat.S_ISREG(os.stat(src).st_mode):
-            raise ValueError("a .npy output needs the frame count up front, and a Y4M stream from a pipe cannot be "
-                             "counted before it is read: write Y4M, or read the stream from a regular file")
-    reader = imageio_lite.Y4MReader(src)
+    npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
+    job = _job(lambda size, rfilter: _open_y4m(model, src, npy_out, batch, matrix, siting, size, rfilter,
+                                               count=chunk_frames is None or npy_out),
+               factor=factor, batch=batch, chunk_frames=chunk_frames, scene_cut=scene_cut, scene_log=scene_log, fps=fps,
+               src_fps=src_fps, time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
+               resize=resize, resize_filter=resize_filter)
+    source, hdr, bits = job.source, job.source.header, job.source.route.bits
     try:
-        hdr, rs = reader.header, None
-        if size is not None:   # everything from here on is a clip of the new size; the reader keeps the source's
-            rs, hdr = _y4m_resize(hdr, size, rfilter), _resize.y4m_header_at(hdr, size)
-        route = _y4m_route(model, hdr, npy_out, batch, matrix, siting)
-        plan = _plan_of(fps, src_fps, hdr["fps"], depth)
-        if plan is None:
-            fps = (hdr["fps"][0] * factor, hdr["fps"][1])
-        else:
-            factor, fps = plan.G, (plan.fps.numerator, plan.fps.denominator)
-        plan, dd = _dedup_of(tol, gap, plan, factor)   # (without fps: p / q = 1 / factor; the header's rate as above)
-
-        def run(write):
-            if C is None:
-                count = (imageio_lite.y4m_frame_count(src)
-                         if _is_path(src) and stat.S_ISREG(os.stat(src).st_mode) else None)
-                return _run_whole(model, route, reader, write, factor, thr, plan, mode, count, dd, dedup_log, scene_log,
-                                  rs)
-            return _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log, rs)
         if npy_out:
-            n = imageio_lite.y4m_frame_count(src)
-            shape = ((n - 1) * factor + 1 if plan is None else plan.n_out(n), hdr["height"], hdr["width"])
-            sink = _NpyWriter(os.fspath(dst), np.uint16 if route.bits == 10 else np.uint8, shape)
-            ok = False
-            try:
-                total = run(sink.write)
-                ok = True
-            finally:
-                sink.close(ok)
-            return total
+            n_out = (source.count - 1) * job.factor + 1 if job.plan is None else job.plan.n_out(source.count)
+            sink = _NpyWriter(os.fspath(dst), source.route.ndtype, (n_out, hdr["height"], hdr["width"]))
+            return _drive(model, job, lambda: sink.write, sink.close)
         f, finish = _open_sink(dst)
-        ok = False
-        try:
-            w = imageio_lite.Y4MWriter(f, hdr["width"], hdr["height"], fps, hdr["colourspace"],
-                                       hdr["colour_range"] if (route.bits == 10 or model.frame_channels == 3) else None,
-                                       bits=route.bits)
-            total = run(w.write)
-            ok = True
-        finally:
-            finish(ok)
-        return total
+        return _drive(model, job, lambda: imageio_lite.Y4MWriter(
+            f, hdr["width"], hdr["height"], job.rate, hdr["colourspace"],
+            hdr["colour_range"] if (bits == 10 or model.frame_channels == 3) else None, bits=bits).write, finish)
     finally:
-        reader.close()
+        source.close()
 
 
 def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
@@ -839,47 +936,22 @@ def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     frame count.  fps / src_fps / time_depth / retime and chunk_frames None: as for `interpolate_y4m_stream`; a .npy
     stack carries no rate, so `fps` needs `src_fps`.  resize / resize_filter: as for `interpolate_y4m_stream`; the output
     stack has the new height and width."""
-    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
-    fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
-    tol, gap = check_dedup(dedup, max_gap, fps, factor)
-    size = None if resize is None else _resize.check_size(resize)
-    rfilter = _resize.check_resize_filter(resize, resize_filter)
-    plan = _plan_of(fps, src_fps, None, depth)
-    if plan is not None:
-        factor = plan.G
-    plan, dd = _dedup_of(tol, gap, plan, factor)
-    if not _is_path(dst):
-        raise ValueError("a .npy output is a path")
+    def open_source(size, rfilter):
+        if not _is_path(dst):
+            raise ValueError("a .npy output is a path")
+        return _open_npy(model, src, batch, size, rfilter)
+    job = _job(open_source, factor=factor, batch=batch, chunk_frames=chunk_frames, scene_cut=scene_cut,
+               scene_log=scene_log, fps=fps, src_fps=src_fps, time_depth=time_depth, retime=retime, dedup=dedup,
+               max_gap=max_gap, dedup_log=dedup_log, resize=resize, resize_filter=resize_filter)
+    n = job.source.count
+    if n < 1:
+        raise ValueError("no frames to interpolate")
     dst = os.fspath(dst)
     if not dst.endswith(".npy"):   # what np.save does with the name
         dst += ".npy"
-    mm = np.load(src, mmap_mode="r")
-    if mm.dtype != np.uint8 or mm.ndim not in (3, 4):
-        raise ValueError("expected a uint8 .npy stack [N,H,W] or [N,H,W,3]")
-    if mm.shape[0] < 1:
-        raise ValueError("no frames to interpolate")
-    shape, rs = tuple(mm.shape[1:]), None
-    if size is not None:
-        kind = "npy" if len(shape) == 2 else ("npy", shape[2])
-        rs = _resize.FrameResize(_resize.frame_planes(kind, shape[0], shape[1]),
-                                 _resize.frame_planes(kind, size[1], size[0]), 8, size, (shape[1], shape[0]),
-                                 rfilter)
-        shape = (size[1], size[0]) + shape[2:]
-    route = _npy_route(model, shape, batch)
-    n_out = (mm.shape[0] - 1) * factor + 1 if plan is None else plan.n_out(mm.shape[0])
-    sink = _NpyWriter(dst, np.uint8, (n_out,) + shape)
-    ok = False
-    try:
-        if C is None:
-            total = _run_whole(model, route, _NpyRows(mm), sink.write, factor, thr, plan, mode, mm.shape[0], dd,
-                               dedup_log, scene_log, rs)
-        else:
-            total = _run(model, route, _NpyRows(mm), sink.write, factor, C, thr, scene_log, plan, mode, dd, dedup_log,
-                         rs)
-        ok = True
-    finally:
-        sink.close(ok)
-    return total
+    n_out = (n - 1) * job.factor + 1 if job.plan is None else job.plan.n_out(n)
+    sink = _NpyWriter(dst, np.uint8, (n_out,) + job.source.shape)
+    return _drive(model, job, lambda: sink.write, sink.close)
 
 
 def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12", width=None, height=None,
@@ -906,61 +978,22 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     yuv422p10le rows on the device right after each chunk's upload and packed again before its download; everything
     between is the yuv422p10le route, and the output is, byte for byte, that route's output packed.  The file size of a
     regular input counts wire frames (`wire10.frame_bytes`); v210 / y210le need an even width at both sizes."""
-    thr, C = _check_common(factor, batch, chunk_frames, scene_cut)
-    if src_fps is None:
-        raise ValueError("raw video carries no frame rate: pass src_fps")
-    src_rate = _retime.parse_fps(src_fps)
-    fps, _, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
-    tol, gap = check_dedup(dedup, max_gap, fps, factor)
     npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
-    size = None if resize is None else _resize.check_size(resize)
-    rfilter = _resize.check_resize_filter(resize, resize_filter)
-    route = _raw_route(model, raw, height, width, npy_out, batch, matrix, siting)
-    wire = check_packing(packing, raw, height, width, size)
-    wire_row = route.row * np.dtype(route.ndtype).itemsize   # bytes per frame on the wire: the source's
-    if wire is not None:
-        wire_row = 2 * wire.in_row
-    rs = None
-    if size is not None:
-        rs = _raw_resize(raw, route.bits, height, width, size, rfilter)
-        route = _raw_route(model, raw, size[1], size[0], npy_out, batch, matrix, siting)
-    plan = _plan_of(fps, src_rate, None, depth)
-    if plan is not None:
-        factor = plan.G
-    plan, dd = _dedup_of(tol, gap, plan, factor)
-    count = None
-    if _is_path(src):
-        if not os.path.exists(src):
-            raise FileNotFoundError(f"Video file not found: {src}")
-        st = os.stat(src)
-        if stat.S_ISREG(st.st_mode):
-            if st.st_size % wire_row:
-                raise ValueError(f"{os.fspath(src)}: {st.st_size} bytes is not a whole number of {width}x{height} "
-                                 f"{raw if wire is None else packing} frames of {wire_row} bytes")
-            count = st.st_size // wire_row
-            if count == 0:
-                raise ValueError("no frames to interpolate")
-    fin = open(src, "rb") if _is_path(src) else src
+    job = _job(lambda size, rfilter: _open_raw(model, src, raw, width, height, npy_out, batch, matrix, siting, size,
+                                               rfilter, packing),
+               factor=factor, batch=batch, chunk_frames=chunk_frames, scene_cut=scene_cut, scene_log=scene_log, fps=fps,
+               src_fps=src_fps, time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
+               resize=resize, resize_filter=resize_filter, headerless=True)
     try:
-        reader = _RawReader(fin, wire_row)
+        if job.source.count == 0:
+            raise ValueError("no frames to interpolate")
         f, finish = _open_sink(dst)
-        ok = False
-        try:
-            def write(rows):
-                f.write(np.ascontiguousarray(rows).data)
-            if C is None:
-                total = _run_whole(model, route, reader, write, factor, thr, plan, mode, count, dd, dedup_log,
-                                   scene_log, rs, wire=wire)
-            else:
-                total = _run(model, route, reader, write, factor, C, thr, scene_log, plan, mode, dd, dedup_log, rs,
-                             wire=wire)
-            ok = True
-        finally:
-            finish(ok)
-        return total
+
+        def write(rows):
+            f.write(np.ascontiguousarray(rows).data)
+        return _drive(model, job, lambda: write, finish)
     finally:
-        if _is_path(src):
-            fin.close()
+        job.source.close()
 
 
 __all__ = ["check_chunk_frames", "check_retime", "check_dedup", "interpolate_y4m_stream", "interpolate_npy_stream",

@@ -70,7 +70,7 @@ def test_plane_table_frame_size_is_the_routes():
 
 
 def test_existing_sources_keep_pitch_w_and_step_1():
-    src = holdout._Source(None, None, [("y", 0, 4, 6), ("u", 24, 2, 3)], 0, None, lambda: None)
+    src = holdout._Source(None, [("y", 0, 4, 6, 6, 1), ("u", 24, 2, 3, 3, 1)])
     assert src.planes == [("y", 0, 4, 6, 6, 1), ("u", 24, 2, 3, 3, 1)] and src.groups == [] and src.lead == ("y",)
     rows = torch.arange(2 * 40, dtype=torch.uint8).reshape(2, 40)
     y, u = holdout._plane_views(rows[:, 2:], src)
@@ -82,7 +82,7 @@ def test_plane_and_group_views_of_strided_rows():
     h, w = 3, 4
     rows = torch.arange(5 * 2 * h * w, dtype=torch.uint8).reshape(5, -1)[1::2]   # every second frame of a uyvy422 stack
     planes, groups = holdout.raw_planes("uyvy422", h, w)
-    src = holdout._Source(None, None, planes, 0, None, lambda: None, groups, ("y",))
+    src = holdout._Source(None, planes, 0, groups, ("y",))
     want = R.plane_indices("uyvy422", h, w)
     for (name, *_), v in zip(planes, holdout._plane_views(rows, src)):
         assert v.data_ptr() >= rows.data_ptr() and torch.equal(v, rows[:, torch.from_numpy(want[name])]), name

@@ -237,9 +237,52 @@ def test_video_refusals(tmp_path, no_gpu, kw, match):
     with pytest.raises(ValueError, match=match):
         _fi().interpolate_video(str(src), str(tmp_path / "out.v210"), **dict(GOOD, **kw))
     assert _no_output(tmp_path)
-    if "resize" not in kw:   # (hold-out scoring packs nothing: the resized working planes may have any width)
-        with pytest.raises(ValueError, match=match):
-            holdout.score_video(_model(), str(src), **dict(GOOD, **kw))
+    with pytest.raises(ValueError, match=match):   # (the same opener: the packing's rules hold at both sizes here too)
+        holdout.score_video(_model(), str(src), **dict(GOOD, **kw))
+
+
+def _raw_file(frames):
+    return lambda tmp_path, kw: _write(tmp_path / "in.raw", bytes(int(frames * (
+        wire10.frame_bytes(kw["packing"], 6, 8) if kw.get("packing") else 2 * wire10.planar_samples(6, 8)))))
+
+
+def _write(path, data):
+    path.write_bytes(data)
+    return path
+
+
+def _npy_u16(tmp_path, kw):
+    np.save(tmp_path / "in.npy", np.zeros((5, 6, 8), np.uint16))
+    return tmp_path / "in.npy"
+
+
+PLAIN = dict(GOOD, packing=None)
+SOURCE_FAULTS = [   # (what makes the source, the keywords of both calls, the exception, a piece of its message)
+    (_raw_file(1.5), PLAIN, ValueError, "288 bytes is not a whole number of 8x6 yuv422p10le frames of 192 bytes"),
+    (_raw_file(1.5), GOOD, ValueError, "1152 bytes is not a whole number of 8x6 v210 frames of 768 bytes"),
+    (lambda tmp_path, kw: tmp_path / "none.raw", GOOD, FileNotFoundError, "Video file not found"),
+    (_raw_file(3), dict(GOOD, raw="nv12"), ValueError, "pass raw=\"yuv422p10le\" with it"),
+    (_raw_file(3), dict(GOOD, width=7), ValueError, "even width"),
+    (_raw_file(3), dict(GOOD, resize=(7, 6)), ValueError, "even width"),
+    (_npy_u16, {}, ValueError, "expected a uint8 .npy stack"),
+    (_raw_file(3), dict(GOOD, resize=(16, 6), resize_filter="area"), ValueError, "area"),
+]
+
+
+@pytest.mark.parametrize("make,kw,exc,piece", SOURCE_FAULTS,
+                         ids=["part-frame-plain", "part-frame-v210", "missing", "packing-nv12", "odd-source", "odd-resize",
+                              "npy-uint16", "area-grows"])
+def test_a_source_fault_is_the_same_refusal_from_both_entry_points(tmp_path, no_gpu, make, kw, exc, piece):
+    """The video routes and hold-out scoring open a source through the same opener (stream.py): the same exception type
+    with the same text, before any GPU work, and no output file (`.part` included)."""
+    src = make(tmp_path, kw)
+    with pytest.raises(exc) as video:
+        _fi(1 if src.suffix == ".npy" else 3).interpolate_video(str(src), str(tmp_path / ("out" + src.suffix)), **kw)
+    with pytest.raises(exc) as scoring:
+        holdout.score_video(_model(1 if src.suffix == ".npy" else 3), str(src), **kw)
+    assert type(video.value) is type(scoring.value) is exc
+    assert str(video.value) == str(scoring.value) and piece in str(video.value)
+    assert _no_output(tmp_path)
 
 
 def test_whole_wire_frames_are_counted_not_working_frames(tmp_path, no_gpu):

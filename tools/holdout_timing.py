@@ -37,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native, holdout, imageio_lite as IO  # noqa: E402
+from ai_based_frame_interpolation_amd import _native, holdout, stream, imageio_lite as IO  # noqa: E402
 from oracle import unet_oracle as O  # noqa: E402
 
 
@@ -125,7 +125,7 @@ def _score(dev, frames, h, w):
     m.load_state_dict(O.make_interpolating_state_dict(n_channels=6, n_classes=3))
     m = m.to(dev).eval()
     spent = [0.0]
-    make_route = holdout._y4m_route
+    make_route = stream._y4m_route
 
     def timed_route(*a, **k):
         route = make_route(*a, **k)
@@ -149,14 +149,14 @@ def _score(dev, frames, h, w):
         res = holdout.score_video(m, src)
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
-        holdout._y4m_route = timed_route
+        stream._y4m_route = timed_route
         try:
             t0 = time.perf_counter()
             holdout.score_video(m, src)
             torch.cuda.synchronize()
             wall2 = time.perf_counter() - t0
         finally:
-            holdout._y4m_route = make_route
+            stream._y4m_route = make_route
     scored = len(res["scored_frames"])
     print(holdout.summary_table(res), flush=True)
     return dict(frames=frames, scored_frames=scored, wall_s=round(wall, 3), scored_frames_per_s=round(scored / wall, 2),
