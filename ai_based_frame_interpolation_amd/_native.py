@@ -58,6 +58,8 @@ SYMBOLS = (
     "fiunet_resize_planes_u8", "fiunet_resize_planes_p10",
     # 10-bit 4:2:2 wire packings
     "fiunet_unpack_422p10", "fiunet_pack_422p10",
+    # motion-compensated resampling
+    "fiunet_warp_table_u8", "fiunet_warp_table_p10",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -83,6 +85,16 @@ def _surface(layout, frame_stride: int):
 class RetimeEntry(ctypes.Structure):
     """include/fiunet.h: fiunet_retime_entry (output row = grid row `row`, blended with the row after it by wn / den)."""
     _fields_ = [("row", ctypes.c_uint32), ("wn", ctypes.c_uint32), ("den", ctypes.c_uint32)]
+
+
+class WarpEntry(ctypes.Structure):
+    """include/fiunet.h: fiunet_warp_entry (grid rows `row` and the one after, warped to wn / den along flow field `flow`;
+    flag: an index into the device flags, or WARP_NO_FLAG)."""
+    _fields_ = [("row", ctypes.c_uint32), ("wn", ctypes.c_uint32), ("den", ctypes.c_uint32), ("flow", ctypes.c_uint32),
+                ("flag", ctypes.c_int32)]
+
+
+WARP_NO_FLAG = -1   # include/fiunet.h: FIUNET_WARP_NO_FLAG
 
 
 class ResizePlane(ctypes.Structure):
@@ -213,6 +225,8 @@ def lib() -> ctypes.CDLL:
     L.fiunet_retime_table_p10.argtypes = [vp, ci, sz, vp, ci, vp, vp]
     L.fiunet_resize_planes_u8.argtypes = [vp, vp, vp, vp, ci, ci, vp]
     L.fiunet_resize_planes_p10.argtypes = [vp, vp, vp, vp, ci, ci, vp]
+    L.fiunet_warp_table_u8.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp]
+    L.fiunet_warp_table_p10.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp]
     L.fiunet_nv12_to_rgb_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_rgb_to_nv12_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_p010_to_rgb_p10.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
@@ -832,3 +846,42 @@ def retime_table(grid: "torch.Tensor", entries, out: "torch.Tensor", bits: int) 
     s = _stream(grid)
     check(fn(grid.data_ptr(), grid.shape[0], fs, arr, len(entries), out.data_ptr(), s),
           "fiunet_retime_table_" + ("p10" if bits == 10 else "u8"))
+
+
+def warp_entries(entries):
+    """A sequence of (row, wn, den, flow, flag) int tuples -> the C array of fiunet_warp_entry (None when empty).
+    ValueError on a value that does not fit its field (the library checks the rest)."""
+    n = len(entries)
+    if not n:
+        return None
+    arr = (WarpEntry * n)()
+    for k, (row, wn, den, flow, flag) in enumerate(entries):
+        if not all(0 <= v < 1 << 32 for v in (row, wn, den, flow)) or not -(1 << 31) <= flag < 1 << 31:
+            raise ValueError(f"entry {k} = {(row, wn, den, flow, flag)} does not fit fiunet_warp_entry")
+        arr[k] = WarpEntry(row, wn, den, flow, flag)
+    return arr
+
+
+def warp_table(grid: "torch.Tensor", n_rows: int, grid_plane, flow: "torch.Tensor", flags, entries, out: "torch.Tensor",
+               out_plane, bits: int, stream=None) -> None:
+    """fiunet_warp_table_u8 / fiunet_warp_table_p10: one plane of len(entries) output frames, each warped along a field of
+    `flow` (contiguous float32 [n_flows, flow_h, flow_w, 2]) between two rows of the dense buffer `grid` to its time
+    wn / den.  A plane is (offset, h, w, pitch, step, frame_stride) in samples from the tensor's first element; entries:
+    (row, wn, den, flow, flag) with flag WARP_NO_FLAG or an index into the uint8 device tensor `flags` (or None).
+    ValueError, before the call, where well-formed planes reach past either tensor."""
+    grid_plane, out_plane = tuple(int(v) for v in grid_plane), tuple(int(v) for v in out_plane)
+    entries = [tuple(int(v) for v in e) for e in entries]
+    for name, t, plane, n in (("grid", grid, grid_plane, n_rows), ("out", out, out_plane, len(entries))):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be a dense buffer (the plane carries the pitch)")
+        if min(plane) >= 0 and plane[1] >= 1 and plane[2] >= 1 and _resize_extent([plane], n) > t.numel():
+            raise ValueError(f"the {name} plane reaches sample {_resize_extent([plane], n)} of a buffer of {t.numel()}")
+    if flow.dtype != torch.float32 or flow.dim() != 4 or flow.shape[3] != 2 or not flow.is_contiguous():
+        raise ValueError(f"flow: expected a contiguous float32 [n, h, w, 2] tensor, got {flow.dtype} {tuple(flow.shape)}")
+    if flags is not None and (flags.dtype != torch.uint8 or not flags.is_contiguous()):
+        raise ValueError("flags must be a contiguous uint8 tensor")
+    fn = lib().fiunet_warp_table_p10 if bits == 10 else lib().fiunet_warp_table_u8
+    check(fn(grid.data_ptr(), n_rows, resize_plane_array([grid_plane]), flow.data_ptr(), flow.shape[0], flow.shape[1],
+             flow.shape[2], None if flags is None else flags.data_ptr(), 0 if flags is None else flags.numel(),
+             warp_entries(entries), len(entries), out.data_ptr(), resize_plane_array([out_plane]), _stream(grid, stream)),
+          "fiunet_warp_table_" + ("p10" if bits == 10 else "u8"))

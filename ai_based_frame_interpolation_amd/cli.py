@@ -168,8 +168,10 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--src-fps", type=_fps, default=None,
                    help="Source frame rate as n or n/d (default: the Y4M header's)")
     v.add_argument("--time-depth", type=int, default=2, choices=(1, 2, 3, 4), help="Bisection levels under --fps")
-    v.add_argument("--retime", default="blend", choices=retime.MODES,
-                   help="How --fps picks between the two bisection frames around an output time")
+    v.add_argument("--retime", default="blend", choices=retime.VIDEO_MODES,
+                   help="How --fps makes a frame between two bisection frames: blend (a cross-fade), nearest (the "
+                        "closer one) or motion (both warped along the optical flow between them to the frame's own "
+                        "time: no double edges where things move, at the cost of one flow per pair)")
     v.add_argument("--dedup", type=_dedup, default=None, metavar="TOL",
                    help="Re-time repeated frames (telecine, animation on twos, stalled capture): frames that differ "
                         "by at most TOL code values count as repeats (0: equal frames)")

@@ -260,6 +260,106 @@ int fiunet_flow_warp(const void* frame0, const void* frame1, const float* flow, 
     return FIUNET_OK;
 }
 
+// ---- motion-compensated resampling (flow_warp_table_kernel) -----------------------------------------
+// Everything a thread indexes is checked here, on the host, before the first launch and before a pointer is used.
+static_assert(sizeof(fiunet_warp_entry) == 20, "entry layout");
+
+extern "C++" {
+namespace {
+// fiunet_resize_planes' rule for one plane (video.hip: resize_check_plane), with the flow's bound on a side
+const char* warp_check_plane(const fiunet_resize_plane& p)
+{
+    if (p.h < 1 || p.w < 1) return "a plane's h and w must be positive";
+    if ((size_t)p.h > kFlowMaxSide || (size_t)p.w > kFlowMaxSide) return "a plane's h and w must not exceed 32768";
+    if (p.step < 1 || p.step > 4) return "a plane's step must be 1..4";
+    if (p.filter != 0) return "a plane's filter must be 0";
+    const size_t row = (size_t)(p.w - 1) * p.step + 1;
+    if (p.pitch < row) return "a plane's pitch must cover a row: (w - 1) * step + 1";
+    if (p.h > 1 && p.pitch > (SIZE_MAX - row) / (size_t)(p.h - 1)) return "a plane's pitch is too large";
+    const size_t body = (size_t)(p.h - 1) * p.pitch + row;
+    if (p.offset > p.frame_stride || body > p.frame_stride - p.offset) return "a plane must lie inside its frame stride";
+    return nullptr;
+}
+
+template <typename T>
+int flow_warp_table(const T* grid, int n_rows, const fiunet_resize_plane* gp, const float* flow, int n_flows, int flow_h,
+                    int flow_w, const uint8_t* flags, int n_flags, const fiunet_warp_entry* entries, int n_out, T* out,
+                    const fiunet_resize_plane* op, void* stream)
+{
+    if (!grid || !out || !gp || !op || !flow) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (((uintptr_t)grid | (uintptr_t)out) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
+    if (n_rows < 0 || n_out < 0 || n_flows < 0 || n_flags < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
+    if (n_flags > 0 && !flags) return fail(FIUNET_ERR_INVALID_ARG, "NULL flags");
+    for (const fiunet_resize_plane* p : {gp, op})
+        if (const char* why = warp_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
+    if (gp->h != op->h || gp->w != op->w) return fail(FIUNET_ERR_INVALID_ARG, "the grid's plane and out's differ in size");
+    if (flow_h < 1 || flow_w < 1 || (size_t)flow_h > kFlowMaxSide || (size_t)flow_w > kFlowMaxSide)
+        return fail(FIUNET_ERR_INVALID_ARG, "bad flow shape");
+    if ((uintptr_t)flow & 7) return fail(FIUNET_ERR_INVALID_ARG, "flow not 8-B aligned");
+    if (n_out == 0) return FIUNET_OK;
+    if (!entries) return fail(FIUNET_ERR_INVALID_ARG, "NULL entries");
+    for (int k = 0; k < n_out; ++k) {
+        const fiunet_warp_entry& e = entries[k];
+        if (e.den < 1 || e.den > kRetimeMaxQ) return fail(FIUNET_ERR_INVALID_ARG, "entry: den outside 1..2^20");
+        if (e.wn >= e.den) return fail(FIUNET_ERR_INVALID_ARG, "entry: wn >= den");
+        if ((uint64_t)e.row + 1 >= (uint64_t)n_rows)
+            return fail(FIUNET_ERR_INVALID_ARG, "entry: `row` and the row after it must lie inside the grid");
+        if ((uint64_t)e.flow >= (uint64_t)n_flows) return fail(FIUNET_ERR_INVALID_ARG, "entry: flow outside the flow fields");
+        if (e.flag != FIUNET_WARP_NO_FLAG && (e.flag < 0 || e.flag >= n_flags))
+            return fail(FIUNET_ERR_INVALID_ARG, "entry: flag outside the flags");
+    }
+    // n_rows frames of the grid's plane and n_out of out's stay inside the address space and apart from each other
+    const size_t gbody = (size_t)(gp->h - 1) * gp->pitch + (size_t)(gp->w - 1) * gp->step + 1;
+    const size_t obody = (size_t)(op->h - 1) * op->pitch + (size_t)(op->w - 1) * op->step + 1;
+    if (gp->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_rows || op->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_out)
+        return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+    const uintptr_t g0 = (uintptr_t)grid + gp->offset * sizeof(T);
+    const uintptr_t g1 = g0 + ((size_t)(n_rows - 1) * gp->frame_stride + gbody) * sizeof(T);
+    const uintptr_t o0 = (uintptr_t)out + op->offset * sizeof(T);
+    const uintptr_t o1 = o0 + ((size_t)(n_out - 1) * op->frame_stride + obody) * sizeof(T);
+    if (g0 < o1 && o0 < g1) return fail(FIUNET_ERR_INVALID_ARG, "out overlaps the grid");
+    const int h = gp->h, w = gp->w;
+    const float mx = (float)((double)w / (double)flow_w), my = (float)((double)h / (double)flow_h);
+    const FlowWarpPlane G = {gp->offset, gp->pitch, gp->frame_stride, gp->step};
+    constexpr int V = FlowWarpVec<T>::V;
+    const unsigned bx = (unsigned)(((w + V - 1) / V + 63) / 64), by = (unsigned)((h + 3) / 4);
+    for (int k0 = 0; k0 < n_out; k0 += kFlowWarpTableMax) {
+        const int nk = std::min(n_out - k0, kFlowWarpTableMax);
+        FlowWarpTable table = {};
+        for (int k = 0; k < nk; ++k) {
+            const fiunet_warp_entry& e = entries[k0 + k];
+            // s0, s1: computed in double, rounded once
+            table.e[k] = FlowWarpEntry{e.row, e.wn, e.den, e.flow, e.flag, (float)((double)e.wn / (double)e.den),
+                                       (float)((double)(e.den - e.wn) / (double)e.den)};
+        }
+        const FlowWarpPlane O = {op->offset + (size_t)k0 * op->frame_stride, op->pitch, op->frame_stride, op->step};
+        hipLaunchKernelGGL(flow_warp_table_kernel<T>, dim3(bx, by, (unsigned)nk), dim3(256), 0, (hipStream_t)stream, grid,
+                           G, flow, flow_h, flow_w, mx, my, flags, table, h, w, out, O);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int fiunet_warp_table_u8(const uint8_t* grid, int n_rows, const fiunet_resize_plane* grid_plane, const float* flow,
+                              int n_flows, int flow_h, int flow_w, const uint8_t* flags, int n_flags,
+                              const fiunet_warp_entry* entries, int n_out, uint8_t* out,
+                              const fiunet_resize_plane* out_plane, void* stream)
+{
+    return flow_warp_table(grid, n_rows, grid_plane, flow, n_flows, flow_h, flow_w, flags, n_flags, entries, n_out, out,
+                           out_plane, stream);
+}
+
+int fiunet_warp_table_p10(const uint16_t* grid, int n_rows, const fiunet_resize_plane* grid_plane, const float* flow,
+                               int n_flows, int flow_h, int flow_w, const uint8_t* flags, int n_flags,
+                               const fiunet_warp_entry* entries, int n_out, uint16_t* out,
+                               const fiunet_resize_plane* out_plane, void* stream)
+{
+    return flow_warp_table(grid, n_rows, grid_plane, flow, n_flows, flow_h, flow_w, flags, n_flags, entries, n_out, out,
+                           out_plane, stream);
+}
+
 // Diagnostic (tests; not part of the ABI): the pyramid of an H x W frame, pure host arithmetic.  dims[k] = {h, w,
 // ksize}, sigma[k] for k = 0..*levels.
 int fiunet_debug_flow_plan(int H, int W, int* levels, int dims[12], double sigma[4])

@@ -27,11 +27,16 @@
 //                                is needed (tests/test_flow_host.py compares all 1024 cells with the Python code).
 //                                A flow field of another size than the plane (luma flow, chroma plane) is resampled
 //                                at the pixel with flow_resize_kernel's arithmetic and scaled per axis.
+//   flow_warp_table_kernel       motion-compensated resampling: one plane of up to 64 output frames,
+//                                each warped along the flow between two neighbouring grid rows to its own time
+//                                wn / den; planes are read and written where they lie (offset, pitch, step)
 // Every one is a stencil or a gather: HBM- or LDS-bound, no MFMA, no atomics.  The build has -ffp-contract=off, so
 // every product and sum below rounds on its own, in the order written.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "retime.hip.h"   // retime_div: the blend's exact division by den
 
 namespace fiunet {
 
@@ -373,6 +378,116 @@ __global__ __launch_bounds__(256) void flow_warp_kernel(const T* __restrict__ f0
         v = (a + b + 1) >> 1;
     }
     out[(size_t)blockIdx.z * out_image_stride + (size_t)y * out_row_pitch + x] = (T)v;
+}
+
+// ---- motion-compensated resampling (retime "motion") ------------------------------------------------
+// Output frame blockIdx.z of the launch is entry e = table.e[blockIdx.z]: A = grid row e.row, B = the row after it,
+// (dx, dy) the flow A -> B at the sample (field e.flow of `flow`, resampled and scaled as in flow_warp_kernel where the
+// plane is not the field's size), s0 = fp32(wn / den), s1 = fp32((den - wn) / den), both rounded once on the host:
+//   a   = remap(A, clamp(x - s0 dx), clamp(y - s0 dy))        b = remap(B, clamp(x + s1 dx), clamp(y + s1 dy))
+//   out = ((den - wn) a + wn b + den / 2) / den               (retime_div: a, b <= 1023 and den <= 2^20)
+// every product rounded to fp32, then every sum (__fmul_rn / __fadd_rn / __fsub_rn: never contracted).  2 wn == den is
+// flow_warp_kernel's FLOW_MODE_MOTION bit for bit, a zero flow is retime_table_kernel's blend; wn == 0 copies A's samples.
+// An entry whose flag (e.flag >= 0: flags[e.flag] on the device) is set writes nothing.  The entries travel in the
+// kernel's arguments, as RetimeTable does; the host has checked every index below before the launch.
+// One thread makes the consecutive samples of a row that fill a dword (FlowWarpVec<T>: 4 bytes or 2 words); where the
+// plane's samples are contiguous (step 1), all of them lie inside the row and the address is aligned, they leave as one
+// 4-byte store (8 bytes a thread at 10 bits measured 17 % behind fiunet_flow_warp, a dword level with it).  Eight gathered loads per sample,
+// no LDS, no atomics.
+constexpr int kFlowWarpTableMax = 64;
+template <typename T> struct FlowWarpVec { static constexpr int V = 4 / sizeof(T); };
+struct FlowWarpEntry {
+    uint32_t row, wn, den, flow;
+    int32_t flag;
+    float s0, s1;
+};
+struct FlowWarpTable {
+    FlowWarpEntry e[kFlowWarpTableMax];
+};
+struct FlowWarpPlane {   // sample (y, x) of frame f at off + f * fs + y * pitch + x * step
+    size_t off, pitch, fs;
+    int step;
+};
+
+// remap on a plane whose samples lie `step` apart
+template <typename T>
+__device__ __forceinline__ int flow_remap_stepped(const T* __restrict__ p, size_t pitch, int step, int h, int w, float mx,
+                                                  float my)
+{
+    const int sx = (int)rintf(mx * 32.f), sy = (int)rintf(my * 32.f);
+    const int xq = sx >> 5, yq = sy >> 5, a = sx & 31, b = sy & 31;
+    const size_t xa = (size_t)flow_clampi(xq, 0, w - 1) * step, xb = (size_t)flow_clampi(xq + 1, 0, w - 1) * step;
+    const size_t ya = (size_t)flow_clampi(yq, 0, h - 1) * pitch, yb = (size_t)flow_clampi(yq + 1, 0, h - 1) * pitch;
+    const int acc = FlowSample<T>::code(p[ya + xa]) * ((32 - a) * (32 - b) * 32) +
+                    FlowSample<T>::code(p[ya + xb]) * (a * (32 - b) * 32) +
+                    FlowSample<T>::code(p[yb + xa]) * ((32 - a) * b * 32) +
+                    FlowSample<T>::code(p[yb + xb]) * (a * b * 32);
+    return (acc + (1 << 14)) >> 15;
+}
+
+// grid = (ceil(ceil(w / V) / 64), ceil(h / 4), entries of the launch), block (64, 4)
+template <typename T>
+__global__ __launch_bounds__(256) void flow_warp_table_kernel(const T* __restrict__ grid, FlowWarpPlane gp,
+                                                              const float* __restrict__ flow, int fh, int fw,
+                                                              float mulx, float muly, const uint8_t* __restrict__ flags,
+                                                              const FlowWarpTable table, int h, int w,
+                                                              T* __restrict__ out, FlowWarpPlane op)
+{
+    constexpr int V = FlowWarpVec<T>::V;
+    const FlowWarpEntry e = table.e[blockIdx.z];   // gridDim.z <= kFlowWarpTableMax
+    if (e.flag >= 0 && flags[e.flag]) return;      // (uniform over the workgroup)
+    const int x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * V, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x0 >= w || y >= h) return;
+    const T* pa = grid + gp.off + (size_t)e.row * gp.fs;
+    const T* pb = pa + gp.fs;
+    T* po = out + op.off + (size_t)blockIdx.z * op.fs + (size_t)y * op.pitch + (size_t)x0 * op.step;
+    const float* fl = flow + (size_t)e.flow * fh * fw * 2;
+    const float xm = (float)(w - 1), ym = (float)(h - 1), rq = 1.0f / (float)e.den;
+    const unsigned wa = e.den - e.wn, wb = e.wn, half = e.den >> 1;
+    const bool same = fh == h && fw == w;
+    int y0 = 0, y1 = 0;
+    float ty = 0.f;
+    if (!same) flow_axis(y, h, fh, y0, y1, ty);
+    const int nv = min(V, w - x0);
+    unsigned v[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        v[k] = 0;
+        if (k >= nv) continue;
+        const int x = x0 + k;
+        if (wb == 0) {   // a copy of A's sample as it is stored
+            v[k] = pa[(size_t)y * gp.pitch + (size_t)x * gp.step];
+            continue;
+        }
+        float dx, dy;
+        if (same) {
+            const float2 f = reinterpret_cast<const float2*>(fl)[(size_t)y * w + x];
+            dx = f.x;
+            dy = f.y;
+        } else {
+            int xa, xb;
+            float tx;
+            flow_axis(x, w, fw, xa, xb, tx);
+            dx = flow_resample(fl, fw, 2, y0, y1, ty, xa, xb, tx) * mulx;
+            dy = flow_resample(fl + 1, fw, 2, y0, y1, ty, xa, xb, tx) * muly;
+        }
+        const float fx = (float)x, fy = (float)y;
+        const int a = flow_remap_stepped<T>(pa, gp.pitch, gp.step, h, w,
+                                            flow_clampf(__fsub_rn(fx, __fmul_rn(e.s0, dx)), xm),
+                                            flow_clampf(__fsub_rn(fy, __fmul_rn(e.s0, dy)), ym));
+        const int b = flow_remap_stepped<T>(pb, gp.pitch, gp.step, h, w,
+                                            flow_clampf(__fadd_rn(fx, __fmul_rn(e.s1, dx)), xm),
+                                            flow_clampf(__fadd_rn(fy, __fmul_rn(e.s1, dy)), ym));
+        v[k] = retime_div((unsigned)a * wa + (unsigned)b * wb + half, e.den, rq);
+    }
+    if (op.step == 1 && nv == V && ((uintptr_t)po & (V * sizeof(T) - 1)) == 0) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int k = 0; k < V; ++k) word |= v[k] << (8 * sizeof(T) * k);
+        *reinterpret_cast<uint32_t*>(po) = word;
+        return;
+    }
+    for (int k = 0; k < nv; ++k) po[(size_t)k * op.step] = (T)v[k];
 }
 
 }  // namespace fiunet

@@ -480,8 +480,10 @@ class FrameInterpolator:
         string such as "60000/1001" (no floats: 59.94 is not 60000/1001).  `factor` then stays 2; every route builds
         the frames of a 2**time_depth bisection (time_depth 1..4; what factor = 2**time_depth computes, cut holds
         included) and resamples them on the device to the times j x source rate / fps (retime.py):
-        retime "blend" weighs the two bisection frames around each time, "nearest" takes the closer one; no frame
-        blends across a flagged cut.  The Y4M header carries fps reduced.  src_fps: the source rate, required for
+        retime "blend" weighs the two bisection frames around each time, "nearest" takes the closer one, "motion"
+        warps both along the optical flow between them to the frame's own time (no double edges where
+        things move, one Farneback flow per pair of bisection frames; it loses a few dB on sub-pixel motion and where
+        the flow fails, so "blend" stays the default); no frame blends or warps across a flagged cut.  The Y4M header carries fps reduced.  src_fps: the source rate, required for
         .npy input; for Y4M it overrides the header's.
         raw: None, or "nv12": input and output are headerless tight NV12 frames of `height` x `width` (files, or file
         objects: pipes), what `ffmpeg -f rawvideo -pix_fmt nv12` reads and writes and what a hardware decoder's

@@ -410,6 +410,33 @@ def _warp_torch(f0: torch.Tensor, f1: torch.Tensor, flow: torch.Tensor, mode: st
     return (back + fwd + 1) >> 1
 
 
+def _warp_time_torch(f0: torch.Tensor, f1: torch.Tensor, flow: torch.Tensor, wn: int, den: int, bits: int) -> torch.Tensor:
+    """One [H, W] plane of the frame at time wn / den between A = f0 and B = f1 along the [h, w, 2] flow A -> B, the
+    definition of retime "motion" (`fiunet_warp_table_*` is held to it bit for bit) -> int64 [H, W].
+    0 < wn < den <= 2**20.  s0 = fp32(wn / den) and s1 = fp32((den - wn) / den), each computed in double and rounded
+    once; A is sampled at p - s0 * flow(p) and B at p + s1 * flow(p), every product rounded to fp32 and then every sum
+    (separate torch float32 operations: no fused multiply-add), clamped to the plane, through `_remap_bilinear`;
+    out = ((den - wn) a + wn b + den // 2) // den, the blend's rounding.  2 wn == den is `_warp_torch(..., "motion")`,
+    a zero flow is the blend of `retime.resample_table`."""
+    wn, den = int(wn), int(den)
+    if not 0 < wn < den <= 1 << 20:
+        raise ValueError(f"need 0 < wn < den <= 2**20, got wn = {wn}, den = {den}")
+    h, w = f0.shape
+    flow = resample_flow(flow.to(torch.float32), h, w)
+    dev = flow.device
+    ys, xs = torch.meshgrid(torch.arange(h, device=dev, dtype=torch.float32),
+                            torch.arange(w, device=dev, dtype=torch.float32), indexing="ij")
+    s0 = torch.tensor(wn / den, dtype=torch.float64).to(torch.float32).to(dev)
+    s1 = torch.tensor((den - wn) / den, dtype=torch.float64).to(torch.float32).to(dev)
+    dx, dy = flow[..., 0], flow[..., 1]
+
+    def clamp(v, hi):   # fmin(fmax(v, 0), hi): a NaN comes out as 0
+        return torch.nan_to_num(v, nan=0.0).clamp(0, hi)
+    a = _remap_bilinear(_codes(f0, bits), clamp(xs - s0 * dx, w - 1), clamp(ys - s0 * dy, h - 1))
+    b = _remap_bilinear(_codes(f1, bits), clamp(xs + s1 * dx, w - 1), clamp(ys + s1 * dy, h - 1))
+    return ((den - wn) * a + wn * b + den // 2) // den
+
+
 @torch.no_grad()
 def warp(frame0: torch.Tensor, frame1: torch.Tensor, flow: torch.Tensor, mode: str = "reference",
          backend: str = "hip", *, bits: int = 8, out: torch.Tensor = None) -> torch.Tensor:

@@ -12,6 +12,8 @@ frames gives J = (N - 1) * q // p + 1 frames; output frame j sits at input time 
   blend    (A * (q - wn) + B * wn + q // 2) // q per sample in integers, A = grid[i * G + lo], B the row after it;
            10-bit words above 1023 read as 1023; wn == 0: a byte copy of A
   nearest  a byte copy of B if 2 * wn > q, else of A
+  motion   (the video routes only, VIDEO_MODES; the last section of this file) blend's frames, but where
+           wn != 0 A and B are first warped along the optical flow between them to the frame's time wn / q
   cut      interval i flagged (scene_cut) and r != 0: a byte copy of input frame i, so that no frame blends across a cut
 
 Every plane of a frame as stored is resampled by the same rule.  One HIP kernel (csrc/retime.hip.h): `fiunet_retime_u8`
@@ -34,6 +36,7 @@ from . import _native
 
 MAX_Q = 1 << 20
 MODES = ("blend", "nearest")
+VIDEO_MODES = MODES + ("motion",)   # what the video routes take; MODES: what the retime kernels themselves know
 
 
 def parse_fps(x) -> Fraction:
@@ -73,8 +76,8 @@ def check_time_depth(time_depth) -> int:
 
 
 def check_mode(retime) -> str:
-    if retime not in MODES:
-        raise ValueError(f"retime must be one of {MODES}, got {retime!r}")
+    if retime not in VIDEO_MODES:
+        raise ValueError(f"retime must be one of {VIDEO_MODES}, got {retime!r}")
     return retime
 
 
@@ -130,11 +133,14 @@ def plan(src_fps, fps, time_depth: int = 2) -> Plan:
 
 @torch.no_grad()
 def resample(grid: torch.Tensor, plan: Plan, first_interval: int, j0: int, n_out: int, *, bits: int, flags=None,
-             mode: str = "blend", out: torch.Tensor | None = None) -> torch.Tensor:
+             mode: str = "blend", out: torch.Tensor | None = None, layout=None, batch: int = 8) -> torch.Tensor:
     """Output frames j0 .. j0 + n_out - 1 of the clip from `grid`: a contiguous device stack [n_intervals * G + 1, ...]
     (uint8 at 8 bits; 16-bit words, int16 or uint16, at 10) that covers clip intervals first_interval ..
     first_interval + n_intervals.  flags: uint8 [n_intervals] on the same device (the chunk's cut flags) or None.
-    Returns `out` ([n_out, ...] of the grid's dtype; allocated when None)."""
+    Returns `out` ([n_out, ...] of the grid's dtype; allocated when None).
+    mode "motion" (the second half of this file's last section): the blend pass first, then every frame with wn != 0
+    outside a flagged interval is warped to its time; layout: the `layout.Layout` of a frame (None: an [H, W] or
+    [H, W, C] frame, from the grid's shape); batch: the pairs per flow call."""
     if bits not in (8, 10):
         raise ValueError(f"bits must be 8 or 10, got {bits!r}")
     mode = check_mode(mode)
@@ -162,8 +168,15 @@ def resample(grid: torch.Tensor, plan: Plan, first_interval: int, j0: int, n_out
         raise ValueError(f"out must be a contiguous {grid.dtype} {shape} tensor on {grid.device}")
     if n_out:
         with torch.cuda.device(grid.device):
-            _native.retime(grid, n_int, plan.depth, first_interval, j0, n_out, plan.p, plan.q, MODES.index(mode),
-                           flags if n_int else None, out, bits)
+            _native.retime(grid, n_int, plan.depth, first_interval, j0, n_out, plan.p, plan.q,
+                           MODES.index("blend" if mode == "motion" else mode), flags if n_int else None, out, bits)
+            if mode == "motion":
+                entries = []
+                for k in range(n_out):
+                    i, _, lo, wn = plan.frame(j0 + k)
+                    li = i - first_interval   # (wn != 0: the frame lies inside interval li, which the C call checked)
+                    entries.append(((li << plan.depth) + lo, wn, plan.q, -1 if flags is None else li))
+                _motion(grid, entries, bits, out, layout, flags, batch)
     return out
 
 
@@ -301,11 +314,15 @@ def table_entries(pl: Plan, spans, first_interval: int, j0: int, n_out: int, n_i
 
 
 @torch.no_grad()
-def resample_table(grid: torch.Tensor, entries, bits: int, out: torch.Tensor | None = None) -> torch.Tensor:
+def resample_table(grid: torch.Tensor, entries, bits: int, out: torch.Tensor | None = None, mode: str = "blend",
+                   layout=None, batch: int = 8) -> torch.Tensor:
     """One output frame per entry (row, wn, den) from `grid`, a contiguous device stack [rows, ...] (uint8 at 8 bits;
     16-bit words at 10): a byte copy of grid[row] when wn == 0, else (A (den - wn) + B wn + den // 2) // den per sample
     with B = grid[row + 1].  The entries are read on the host during the call and go to the kernel in its arguments
-    (`fiunet_retime_table_u8` / `_p10`).  Returns `out` ([len(entries), ...]; allocated when None)."""
+    (`fiunet_retime_table_u8` / `_p10`).  Returns `out` ([len(entries), ...]; allocated when None).
+    mode "motion": after that pass every entry with wn != 0 is warped to its time (layout, batch: as for `resample`);
+    "blend" and "nearest" are resolved into the entries by `table_entries` and change nothing here."""
+    mode = check_mode(mode)
     if bits not in (8, 10):
         raise ValueError(f"bits must be 8 or 10, got {bits!r}")
     want = (torch.uint8,) if bits == 8 else (torch.int16, torch.uint16)
@@ -324,9 +341,97 @@ def resample_table(grid: torch.Tensor, entries, bits: int, out: torch.Tensor | N
     if entries:
         with torch.cuda.device(grid.device):
             _native.retime_table(grid, entries, out, bits)
+            if mode == "motion":
+                _motion(grid, [e + (-1,) for e in entries], bits, out, layout, None, batch)
     return out
 
 
-__all__ = ["MAX_Q", "MODES", "Plan", "parse_fps", "check_time_depth", "check_mode", "plan", "resample",
+# ---- motion-compensated resampling -----------------------------------------------------------------
+# retime "motion": an output frame between two grid rows A and B (wn != 0) is not their cross-fade but both of them
+# warped along the dense flow A -> B to the frame's own time wn / den (optical_flow._warp_time_torch is the definition,
+# `fiunet_warp_table_u8` / `_p10` the kernel).  The blend pass runs first over the same output rows: it gives the
+# wn == 0 copies and the held frames of flagged intervals, whose flags the warp reads on the device and leaves alone.
+# The flow is Farneback's on the LEAD plane of the pair: the first plane of the layout, or the rounded mean of r, g and
+# b (packed RGB) / of the channels of an [H, W, C] frame, hold-out scoring's rule.  Every plane of the layout is then
+# warped where it lies, one call per plane.  A pair's flow does not depend on the pairs beside it (the C ABI says so),
+# so neither does an output frame: a streamed run equals a resident one byte for byte.  At most `batch` flow fields
+# (8 bytes a lead sample) and one flow workspace are alive at a time.
+def _motion_layout(grid: torch.Tensor, layout, bits: int):
+    from . import layout as _layout
+    if layout is None:
+        if grid.dim() == 3:
+            layout = _layout.frame_layout("npy", grid.shape[1], grid.shape[2])
+        elif grid.dim() == 4:
+            layout = _layout.frame_layout(("npy", grid.shape[3]), grid.shape[1], grid.shape[2])
+        else:
+            raise ValueError(f'retime "motion" needs the layout of a frame: a grid {tuple(grid.shape)} does not say '
+                             "where its planes lie (pass layout=layout.frame_layout(...))")
+    planes = [tuple(p) for p in layout.planes]
+    row = grid[0].numel()
+    if _layout.frame_samples(planes) > row:
+        raise ValueError(f"the layout's planes reach sample {_layout.frame_samples(planes)} of a frame of {row}")
+    if bits == 10 and len(lead_planes(planes)) > 1:
+        raise ValueError('retime "motion": the mean of several lead planes is defined for 8-bit frames only')
+    return planes
+
+
+def lead_planes(planes):
+    """The names of the planes the flow is estimated on: r, g and b of packed RGB, every channel of an [H, W, C]
+    frame (their rounded mean), else the first plane."""
+    names = [p[0] for p in planes]
+    if {"r", "g", "b"} <= set(names):
+        return ["r", "g", "b"]
+    if len(names) > 1 and all(n == f"c{i}" for i, n in enumerate(names)):
+        return names
+    return names[:1]
+
+
+def _plane_rows(flat: torch.Tensor, plane, idx: torch.Tensor) -> torch.Tensor:
+    """Plane `plane` of the rows `idx` of the [rows, row] buffer `flat` as a contiguous [len(idx), h, w] tensor."""
+    _, off, h, w, pitch, step = plane
+    view = flat.as_strided((flat.shape[0], h, w), (flat.stride(0), pitch, step), flat.storage_offset() + off)
+    return view.index_select(0, idx)
+
+
+def _motion(grid, entries, bits, out, layout, flags, batch):
+    """Overwrite, in `out`, every plane of the frames whose entry (row, wn, den, flag) has wn != 0."""
+    from . import optical_flow
+    if isinstance(batch, bool) or not isinstance(batch, numbers.Integral) or batch < 1:
+        raise ValueError(f"batch must be a positive int, got {batch!r}")
+    planes = _motion_layout(grid, layout, bits)
+    todo = [(k, e) for k, e in enumerate(entries) if e[1] != 0]
+    if not todo:
+        return
+    rows, row = grid.shape[0], grid[0].numel()
+    flat, oflat = grid.reshape(rows, row), out.reshape(out.shape[0], row)
+    lead = [p for p in planes if p[0] in lead_planes(planes)]
+    pairs = sorted({e[0] for _, e in todo})
+    for s in range(0, len(pairs), batch):
+        part = pairs[s:s + batch]
+        idx = torch.tensor(part, dtype=torch.int64, device=grid.device)
+        if len(lead) == 1:
+            prev, nxt = _plane_rows(flat, lead[0], idx), _plane_rows(flat, lead[0], idx + 1)
+        else:   # the rounded mean of the lead planes (8-bit formats only)
+            c = len(lead)
+            prev, nxt = (((sum(_plane_rows(flat, p, i).to(torch.int32) for p in lead) * 2 + c) // (2 * c)).to(torch.uint8)
+                         for i in (idx, idx + 1))
+        flow = optical_flow.farneback_flow(prev, nxt, "hip", bits=bits)
+        where = {r: f for f, r in enumerate(part)}
+        mine = [(k, e) for k, e in todo if e[0] in where]
+        # runs of consecutive output frames: one call per run and plane (`out`'s plane starts at the run's first frame)
+        runs, start = [], 0
+        for n in range(1, len(mine) + 1):
+            if n == len(mine) or mine[n][0] != mine[n - 1][0] + 1:
+                runs.append(mine[start:n])
+                start = n
+        for run in runs:
+            k0 = run[0][0]
+            table = [(e[0], e[1], e[2], where[e[0]], e[3]) for _, e in run]
+            for _, off, h, w, pitch, step in planes:
+                _native.warp_table(flat, rows, (off, h, w, pitch, step, row), flow, flags, table, oflat[k0:k0 + len(run)],
+                                   (off, h, w, pitch, step, row), bits)
+
+
+__all__ = ["MAX_Q", "MODES", "VIDEO_MODES", "lead_planes", "Plan", "parse_fps", "check_time_depth", "check_mode", "plan", "resample",
            "check_dedup", "dead_limit", "dedup_plan", "dedup_spans", "classify_chunk", "table_entries",
            "resample_table"]

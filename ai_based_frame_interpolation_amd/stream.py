@@ -69,6 +69,12 @@ their pinned output slot.  Everything between is the yuv422p10le route, so the o
   host pinned    3 x (C + 2) wire frames in + 2 x (C x F + 1) wire frames out
   device         2 x (C + 2) wire frames + (C + 2) working frames (the unpacked chunk, until its levels have run) + one
                  chunk's levels + the previous chunk's result + 2 x (C x F + 1) wire frames out
+
+With retime="motion" (retime.py) every resampled frame between two grid rows is warped along the flow
+between them, after the blend pass and into the same output rows: the planes come from the source's layout (the
+destination size, the working format), flows are computed `batch` pairs at a time, and the device holds beside the grid
+  device         2 x batch lead planes + batch flow fields (8 bytes a lead sample each) + the flow workspace of batch
+                 pairs (21 fp32 planes a pair, `fiunet_flow_workspace_bytes`), kept per frame size
 """
 from __future__ import annotations
 
@@ -561,6 +567,31 @@ class _Job:
     rate: tuple | None = None
     scene_log: list | None = None
     dedup_log: list | None = None
+    batch: int = 8
+
+
+def _retime_opts(job: "_Job") -> dict:
+    """The keywords `retime.resample` / `resample_table` take beside the mode: nothing, or for "motion" the layout of an
+    output row (the source's; a luma-only .npy output of Y4M: its luma plane alone) and the pairs per flow call."""
+    if job.mode != "motion":
+        return {}
+    lay, row = job.source.layout, job.source.route.out_row
+    if lay.samples != row:
+        planes = [p for p in lay.planes if p[1] + (p[2] - 1) * p[4] + (p[3] - 1) * p[5] + 1 <= row]
+        lay = type(lay)(planes, [], lay.bits, row)
+    return dict(layout=lay, batch=job.batch)
+
+
+def check_motion_layout(lay, what) -> None:
+    """ValueError where samples of a tight frame belong to no plane of its layout, or to two: retime "motion" warps
+    plane by plane, and would leave such samples blended."""
+    seen = np.zeros(lay.samples, dtype=np.uint8)
+    for _, off, h, w, pitch, step in lay.planes:
+        idx = off + np.arange(h)[:, None] * pitch + np.arange(w)[None, :] * step
+        np.add.at(seen, idx.ravel(), 1)
+    if not (seen == 1).all():
+        raise ValueError(f'retime="motion" is not available for {what}: {int((seen != 1).sum())} samples of a frame '
+                         "belong to no plane of its layout, or to more than one")
 
 
 @torch.no_grad()
@@ -580,6 +611,7 @@ def _run(model, route: _Route, reader, write, job: _Job) -> int:
     dev = next(model.parameters()).device
     source, factor, thr, plan, mode, dd = job.source, job.factor, job.thr, job.plan, job.mode, job.dd
     scene_log, dedup_log, wire = job.scene_log, job.dedup_log, source.wire
+    motion, table_mode = _retime_opts(job), "blend" if mode == "motion" else mode
     C, look = job.chunk_frames, 1 if thr is not None else 0
     if dd is not None:
         look = dd[1] if thr is not None else dd[1] - 1
@@ -708,11 +740,11 @@ def _run(model, route: _Route, reader, write, job: _Job) -> int:
                 j0, nj = plan.span(s, c, last)
                 if dd is None:
                     rows = _retime.resample(out, plan, s, j0, nj, bits=route.bits, flags=flags, mode=mode,
-                                            out=d_out[o][:nj])
+                                            out=d_out[o][:nj], **motion)
                 else:   # (every row an entry names is checked against `out` here, and again behind the C ABI)
-                    entries = _retime.table_entries(plan, spans, s, j0, nj, c + ext, mode,
+                    entries = _retime.table_entries(plan, spans, s, j0, nj, c + ext, table_mode,
                                                     None if cuts is None else cuts[:c + ext])
-                    rows = _retime.resample_table(out, entries, route.bits, out=d_out[o][:nj])
+                    rows = _retime.resample_table(out, entries, route.bits, out=d_out[o][:nj], mode=mode, **motion)
                 out = None   # the grid is used on the compute stream alone: it may go back to the allocator now
             if wire is not None:   # (pinned slot o is free: the copy that last read d_wire[o] has completed)
                 rows = wire.pack(rows, d_wire[o][:rows.shape[0]])
@@ -760,6 +792,7 @@ def _run_whole(model, route: _Route, reader, write, job: _Job) -> int:
     dev = next(model.parameters()).device
     source, factor, thr, plan, mode, dd = job.source, job.factor, job.thr, job.plan, job.mode, job.dd
     scene_log, dedup_log, wire, n_frames, src_row = job.scene_log, job.dedup_log, source.wire, source.count, source.row
+    motion, table_mode = _retime_opts(job), "blend" if mode == "motion" else mode
 
     def upload(a):
         return source.upload(a, dev)
@@ -795,7 +828,7 @@ def _run_whole(model, route: _Route, reader, write, job: _Job) -> int:
         return grid.shape[0]
     n = plan.n_out(d.shape[0])
     if dd is None:
-        rows = _retime.resample(grid, plan, 0, 0, n, bits=route.bits, flags=flags, mode=mode)
+        rows = _retime.resample(grid, plan, 0, 0, n, bits=route.bits, flags=flags, mode=mode, **motion)
     else:
         spans, cuts = [], None
         if d.shape[0] > 1:
@@ -803,8 +836,8 @@ def _run_whole(model, route: _Route, reader, write, job: _Job) -> int:
             spans = _retime.dedup_spans(dead, cuts, dd[1])
             if dedup_log is not None:
                 dedup_log.append((peaks.cpu().numpy(), dead.copy()))
-        entries = _retime.table_entries(plan, spans, 0, 0, n, d.shape[0] - 1, mode, cuts)
-        rows = _retime.resample_table(grid, entries, route.bits)
+        entries = _retime.table_entries(plan, spans, 0, 0, n, d.shape[0] - 1, table_mode, cuts)
+        rows = _retime.resample_table(grid, entries, route.bits, mode=mode, **motion)
     write((rows if wire is None else wire.pack(rows)).cpu().numpy().view(route.ndtype))
     return n
 
@@ -846,10 +879,12 @@ def _job(open_source, *, factor, batch, chunk_frames, scene_cut, scene_log, fps,
         elif source.fps is not None:
             rate = (source.fps[0] * factor, source.fps[1])
         plan, dd = _dedup_of(tol, gap, plan, factor)   # (without fps: p / q = 1 / factor; the rate as above)
+        if mode == "motion" and plan is not None:   # (without a plan `retime` has no effect, as for "nearest")
+            check_motion_layout(source.layout, "this source's frame format")
     except BaseException:
         source.close()
         raise
-    return _Job(source, factor, C, thr, plan, mode, dd, rate, scene_log, dedup_log)
+    return _Job(source, factor, C, thr, plan, mode, dd, rate, scene_log, dedup_log, int(batch))
 
 
 def _drive(model, job: _Job, make_write, finish) -> int:

@@ -44,7 +44,9 @@ extern "C" {
                                      `reserved` member of fiunet_resize_plane, which had to be 0, is `filter`
                                      (FIUNET_RESIZE_LINEAR = 0, FIUNET_RESIZE_AREA); no entry point is added; v8 also,
                                      added the same way: 10-bit 4:2:2 wire packings (fiunet_packing10,
-                                     fiunet_unpack_422p10, fiunet_pack_422p10) */
+                                     fiunet_unpack_422p10, fiunet_pack_422p10); v8 also, added the same way:
+                                     motion-compensated resampling (fiunet_warp_entry, fiunet_warp_table_u8,
+                                     fiunet_warp_table_p10) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -678,6 +680,45 @@ int fiunet_farneback_flow(const void* prev, const void* next, int bits, int B, i
 int fiunet_flow_warp(const void* frame0, const void* frame1, const float* flow, int mode, int bits, int B, int H, int W,
                      size_t image_stride, size_t row_pitch, int flow_h, int flow_w, void* out, size_t out_image_stride,
                      size_t out_row_pitch, void* stream);
+
+/* Motion-compensated resampling (retime "motion"; added without a version bump): ONE PLANE of n_out
+ * output frames, each warped along the flow between two neighbouring rows of a grid of n_rows frames to its own time.
+ * A plane is a fiunet_resize_plane (samples of its buffer; filter 0): `grid_plane` lies in `grid`, `out_plane`, of the
+ * same h x w, in `out`, so the U / V of NV12, the bytes of packed RGB and the capture formats are read and written where
+ * they lie.  Output frame k is e = entries[k]: A = grid row e.row, B = the row after it, (dx, dy) = field e.flow of
+ * `flow` [n_flows, flow_h, flow_w, 2] (A -> B on the lead plane) at the sample, resampled and scaled as in
+ * fiunet_flow_warp where flow_h x flow_w is not h x w; s0 = fp32(wn / den), s1 = fp32((den - wn) / den), each computed
+ * in double and rounded once:
+ *   a   = remap(A, clamp(x - s0 * dx, 0, w - 1), clamp(y - s0 * dy, 0, h - 1))
+ *   b   = remap(B, clamp(x + s1 * dx, 0, w - 1), clamp(y + s1 * dy, 0, h - 1))
+ *   out = ((den - wn) * a + wn * b + den / 2) / den      in integer division
+ * every product rounded to fp32, then every sum (no fused multiply-add); remap as in fiunet_flow_warp (1/32 pixel, 15-bit
+ * weights, (acc + 2^14) >> 15; 10-bit words above 1023 read as 1023; a NaN flow clamps to coordinate 0).  2 * wn == den
+ * is FIUNET_FLOW_MOTION to the last bit, an all-zero flow is the blend of fiunet_retime_table_*; wn == 0 copies the
+ * samples of A as they are stored.  e.flag: FIUNET_WARP_NO_FLAG, or an index into the device array `flags` [n_flags]
+ * (NULL with n_flags 0): a frame whose flag is non-zero on the device is NOT WRITTEN.  Samples of `out` outside the
+ * plane are never written.  `entries` and the planes are HOST memory, read during the call; the entries travel in the
+ * kernel's arguments, 64 output frames per launch: no device table, no allocation, no synchronisation, capturable.
+ * A pair's flow does not depend on its batch (fiunet_farneback_flow), so neither does a frame made here.
+ * FIUNET_ERR_INVALID_ARG, before any launch and before a pointer is used: NULL grid / out / planes / flow (entries with
+ * n_out > 0; flags with n_flags > 0), a uint16_t pointer that is not 2-byte aligned, a negative count, a plane that
+ * breaks fiunet_resize_planes' rules (sizes, step 1..4, pitch, inside its frame stride) or has a side above 32768 or a
+ * filter other than 0, planes of different h x w, a bad flow shape, flow not 8-byte aligned, an entry with
+ * row + 1 >= n_rows, flow >= n_flows, wn >= den, den outside 1 .. 2^20 or a flag outside -1 .. n_flags - 1, and an
+ * out plane range that overlaps the grid plane's. */
+#define FIUNET_WARP_NO_FLAG (-1)
+typedef struct fiunet_warp_entry {
+    uint32_t row, wn, den, flow;
+    int32_t flag;
+} fiunet_warp_entry;
+int fiunet_warp_table_u8(const uint8_t* grid, int n_rows, const fiunet_resize_plane* grid_plane, const float* flow,
+                              int n_flows, int flow_h, int flow_w, const uint8_t* flags, int n_flags,
+                              const fiunet_warp_entry* entries, int n_out, uint8_t* out,
+                              const fiunet_resize_plane* out_plane, void* stream);
+int fiunet_warp_table_p10(const uint16_t* grid, int n_rows, const fiunet_resize_plane* grid_plane, const float* flow,
+                               int n_flows, int flow_h, int flow_w, const uint8_t* flags, int n_flags,
+                               const fiunet_warp_entry* entries, int n_out, uint16_t* out,
+                               const fiunet_resize_plane* out_plane, void* stream);
 
 /* The training loss' SSIM on device: SSIMLoss._ssim (model/train.py:37-56) - the
  * window_size x window_size Gaussian window (sigma 1.5, normalised as at train.py:27-35) applied as a
