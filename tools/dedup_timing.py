@@ -21,60 +21,15 @@ written to `--out` when given.  One JSON line last.
     python tools/dedup_timing.py [--set-gb 1 --frames 257 --chunk 32 --reps 5 --out profiles/dedup_timing.txt]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native, imageio_lite as IO  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-
-LINES = []
-
-
-def say(text):
-    print(text, flush=True)
-    LINES.append(text)
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-def _capture(fn, iters):
-    """A graph of `iters` calls of fn (every entry point here promises: asynchronous on the stream, no allocation, no
-    synchronisation - so it captures)."""
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(iters):
-            fn()
-    return g
-
-
-class _Rotate:
-    """Calls fn(k) with k = 0, 1, ..., n - 1, 0, ... : each call works on the next member of a set."""
-
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+import ai_based_frame_interpolation_amd as P
+from ai_based_frame_interpolation_amd import _native, imageio_lite as IO
 
 
 def _kernel_cases(dev, bits, h, w, n_int, plan, set_bytes):
@@ -96,18 +51,18 @@ def _kernel_cases(dev, bits, h, w, n_int, plan, set_bytes):
     assert blends == sum(1 for j in range(j0, j0 + n_out) if plan.frame(j)[3])
 
     def sad():
-        return _Rotate(lambda k: _native.pair_sad(stacks[k], sums, bits), n_det)
+        return H.Rotate(lambda k: _native.pair_sad(stacks[k], sums, bits), n_det)
 
     def retime():
-        return _Rotate(lambda k: P.retime.resample(grids[k], plan, 0, j0, n_out, bits=bits, out=outs[k]), n_set)
+        return H.Rotate(lambda k: P.retime.resample(grids[k], plan, 0, j0, n_out, bits=bits, out=outs[k]), n_set)
     detect_bytes = 2 * n_int * fb
     moved = (3 * blends + 2 * (n_out - blends)) * fb
     cases = {
         "sad": (sad(), detect_bytes),
-        "peak": (_Rotate(lambda k: _native.pair_peak(stacks[k], peaks, bits), n_det), detect_bytes),
+        "peak": (H.Rotate(lambda k: _native.pair_peak(stacks[k], peaks, bits), n_det), detect_bytes),
         "sad_again": (sad(), detect_bytes),
         "retime": (retime(), moved),
-        "table": (_Rotate(lambda k: P.retime.resample_table(grids[k], entries, bits, out=outs[k]), n_set), moved),
+        "table": (H.Rotate(lambda k: P.retime.resample_table(grids[k], entries, bits, out=outs[k]), n_set), moved),
         "retime_again": (retime(), moved),
     }
     return cases, dict(frame_bytes=fb, intervals=n_int, out_frames=n_out, blended_frames=blends, members=n_set,
@@ -143,85 +98,76 @@ def main():
     ap.add_argument("--dir", default=None, help="directory of the clip files (default: the system temp dir)")
     ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "dedup_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
+    dev = H.need_gpu("dedup_timing")
+    report = H.Report(a.out)
+    say = report.say
     h, w = a.height, a.width
     plan = P.retime.plan(24, 60, 2)
     res = {"shape": [h, w], "kernel": {}, "streamed": {},
-           "protocol": f"kernel: HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of "
-                       f"{a.replays} replays of a graph of {a.iters} calls (eager: of {a.iters} calls from Python) "
-                       f"rotating over a set of at least {a.set_gb} GB; streamed: host wall clock, one "
-                       f"warm-up run per case, median of {a.reps} interleaved runs"}
+           "protocol": "kernel: " + H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, replays=a.replays,
+                                               set_gb=a.set_gb, wall_reps=a.reps)
+                       + f"; eager: of {a.iters} calls from Python, each case's after its graph"}
     say(f"dedup_timing: {torch.cuda.get_device_name(dev)}; {res['protocol']}")
     for bits in (8, 10):
         cases, info = _kernel_cases(dev, bits, h, w, a.intervals, plan, int(a.set_gb * 1e9))
-        for fn, _ in cases.values():
-            for _ in range(a.warmup):
-                fn()
-        torch.cuda.synchronize()
+        H.interleaved({k: fn for k, (fn, _) in cases.items()}, warmup=a.warmup, reps=0, iters=a.iters)   # (the warm-up alone)
         # the figure is taken from a captured graph of `--iters` calls (on the members of the set in turn), replayed
         # `--replays` times: the device runs the kernels back to back, with no Python call, ctypes array or launch from
-        # the host in between.  The same calls issued eagerly from Python are timed beside it, to show the host's share.
-        graphs = {k: _capture(fn, a.iters) for k, (fn, _) in cases.items()}
-        for g in graphs.values():
-            g.replay()
-        torch.cuda.synchronize()
-        ms, eager = {k: [] for k in cases}, {k: [] for k in cases}
-        for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
-            for k, (fn, _) in cases.items():
-                ms[k].append(_time(graphs[k].replay, a.replays) / a.iters)
-                eager[k].append(_time(fn, a.iters))
+        # the host in between.  The same calls issued eagerly from Python are timed beside it, each case's directly
+        # after its graph, to show the host's share.
+        timed, count = {}, {}
+        for k, (fn, _) in cases.items():
+            graph = H.graph_of(fn, a.iters)
+            graph.replay()
+            timed[k], count[k] = graph.replay, a.replays
+            timed[k + " eager"], count[k + " eager"] = fn, a.iters
+        got = H.interleaved(timed, warmup=0, reps=a.reps, iters=count)
+        ms, eager = {k: [v / a.iters for v in got[k]] for k in cases}, {k: got[k + " eager"] for k in cases}
         leg = dict(info)
         for k, (_, moved) in cases.items():
-            med, med_e = statistics.median(ms[k]), statistics.median(eager[k])
-            leg[k] = dict(ms=round(med, 4), spread_ms=[round(min(ms[k]), 4), round(max(ms[k]), 4)],
+            (med, lo, hi), (med_e, lo_e, hi_e) = H.summary(ms[k]), H.summary(eager[k])
+            leg[k] = dict(ms=round(med, 4), spread_ms=[round(lo, 4), round(hi, 4)],
                           gb_per_s=round(moved / (med * 1e-3) / 1e9, 1), eager_ms=round(med_e, 4),
-                          eager_spread_ms=[round(min(eager[k]), 4), round(max(eager[k]), 4)])
-            say(f"{bits:2d} bit {k:12s} graph {med:8.4f} ms  (reps {min(ms[k]):.4f}-{max(ms[k]):.4f})  "
-                f"{leg[k]['gb_per_s']:7.1f} GB/s   eager {med_e:8.4f} ms  (reps {min(eager[k]):.4f}-{max(eager[k]):.4f})")
-        del graphs
+                          eager_spread_ms=[round(lo_e, 4), round(hi_e, 4)])
+            say(f"{bits:2d} bit {k:12s} graph {med:8.4f} ms  (reps {lo:.4f}-{hi:.4f})  "
+                f"{leg[k]['gb_per_s']:7.1f} GB/s   eager {med_e:8.4f} ms  (reps {lo_e:.4f}-{hi_e:.4f})")
         for new, old in (("peak", "sad"), ("table", "retime")):
             a_, b_ = leg[old]["ms"], leg[old + "_again"]["ms"]
-            spread = abs(a_ - b_) / min(a_, b_)
+            spread = H.pair_spread(a_, b_)
             ratio = leg[new]["ms"] / max(a_, b_)
             leg[f"{new}_vs_{old}"] = dict(ratio_to_slower_yardstick=round(ratio, 3), yardstick_spread=round(spread, 3),
                                           within_spread=bool(leg[new]["ms"] <= max(a_, b_)))
             say(f"{bits:2d} bit {new} / {old}: {ratio:.3f} of the slower of the yardstick's two timings "
                 f"(they differ by {100 * spread:.1f} %)")
         res["kernel"][f"{bits}bit"] = leg
-        del cases
+        del cases, timed   # (`fn` and `graph`, the loop's last, hold `retime_again`'s set until the next leg has allocated
+        #                    its own, as this tool's loop variables always have: where a set lands is part of its figures)
         torch.cuda.empty_cache()
 
     if a.frames:
-        m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
-        m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
-        fi = P.FrameInterpolator(model=m.to(dev).eval(), device=dev, batch=8)
+        _, fi = H.seeded_model(3, "bf16", dev)
         tmp = tempfile.mkdtemp(dir=a.dir)
         src, out = os.path.join(tmp, "in.y4m"), os.path.join(tmp, "out.y4m")
         repeats = _write_clip(src, a.frames, h, w)
         log = []
+
+        def dedup():
+            log.clear()   # (each run logs the same intervals: the last run's are counted below)
+            return fi.interpolate_video(src, out, 4, chunk_frames=a.chunk, dedup=0, dedup_log=log)
         runs = {
             "plain": lambda: fi.interpolate_video(src, out, 4, chunk_frames=a.chunk),
-            "dedup": lambda: fi.interpolate_video(src, out, 4, chunk_frames=a.chunk, dedup=0, dedup_log=log),
+            "dedup": dedup,
             "plain_again": lambda: fi.interpolate_video(src, out, 4, chunk_frames=a.chunk),
         }
-        written = {k: fn() for k, fn in runs.items()}   # warm-up
+        written = {}
+        wall = H.interleaved_wall(runs, reps=a.reps, device=dev, results=written)
         dead = int(sum(d.sum() for _, d in log))
-        wall = {k: [] for k in runs}
-        for _ in range(a.reps):
-            for k, fn in runs.items():
-                log.clear()
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-                fn()
-                torch.cuda.synchronize(dev)
-                wall[k].append(time.perf_counter() - t0)
         for k in runs:
-            med = statistics.median(wall[k])
+            med, lo, hi = H.summary(wall[k])
             res["streamed"][k] = dict(input_frames_per_s=round(a.frames / med, 2), wall_s=round(med, 3),
-                                      spread_s=[round(min(wall[k]), 3), round(max(wall[k]), 3)], frames_out=written[k])
+                                      spread_s=[round(lo, 3), round(hi, 3)], frames_out=written[k])
             say(f"streamed {k:12s} {a.frames / med:7.2f} input frames/s  wall {med:.3f} s  "
-                f"(runs {min(wall[k]):.3f}-{max(wall[k]):.3f})  {written[k]} frames out")
+                f"(runs {lo:.3f}-{hi:.3f})  {written[k]} frames out")
         s = res["streamed"]
         slower = max(s["plain"]["wall_s"], s["plain_again"]["wall_s"])
         s.update(frames=a.frames, repeated_frames=repeats, dead_intervals=dead, chunk_frames=a.chunk, network="rgb",
@@ -232,11 +178,7 @@ def main():
             if os.path.exists(f):
                 os.remove(f)
         os.rmdir(tmp)
-    say(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    report.finish(res)
 
 
 if __name__ == "__main__":

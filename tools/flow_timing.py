@@ -20,43 +20,17 @@ One JSON line last.
     python tools/flow_timing.py [--batch 8 --iters 20 --torch-iters 1 --reps 5 --clip-frames 65]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import holdout, optical_flow as OF  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-from holdout_timing import _clip  # noqa: E402
-
-
-def _events(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-def _wall(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / iters
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+import ai_based_frame_interpolation_amd as P
+from ai_based_frame_interpolation_amd import holdout, optical_flow as OF
+from oracle import unet_oracle as O
+from holdout_timing import _clip
 
 
 def _pairs(dev, b, h, w):
@@ -69,35 +43,29 @@ def _pairs(dev, b, h, w):
     return q(f0), q(f1)
 
 
-def _pair_leg(dev, b, h, w, a):
+def _pair_leg(dev, b, h, w, a, say):
     f0, f1 = _pairs(dev, b, h, w)
     both = lambda backend: OF.warp(f0, f1, OF.farneback_flow(f0, f1, backend), "motion", backend)
-    cases = {"hip flow": (lambda: OF.farneback_flow(f0, f1, "hip"), _events, a.iters),
-             "hip flow+warp": (lambda: both("hip"), _events, a.iters),
-             "torch flow": (lambda: OF.farneback_flow(f0, f1, "torch"), _wall, a.torch_iters),
-             "torch flow+warp": (lambda: both("torch"), _wall, a.torch_iters)}
-    gap = (both("hip").int() - both("torch").int()).abs()            # (also the warm-up of both)
-    for name, (fn, _, _) in cases.items():
-        for _ in range(a.warmup if name.startswith("hip") else 0):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(a.reps):
-        for k, (fn, timer, iters) in cases.items():
-            ms[k].append(timer(fn, iters) / b)
+    gap = (both("hip").int() - both("torch").int()).abs()
+    ms = H.interleaved({"hip flow": lambda: OF.farneback_flow(f0, f1, "hip"), "hip flow+warp": lambda: both("hip")},
+                       warmup=a.warmup, reps=a.reps, iters=a.iters)
+    n = a.torch_iters
+    secs = H.interleaved_wall({"torch flow": lambda: [OF.farneback_flow(f0, f1, "torch") for _ in range(n)],
+                               "torch flow+warp": lambda: [both("torch") for _ in range(n)]}, reps=a.reps, device=dev)
+    ms.update({k: [s * 1e3 / n for s in v] for k, v in secs.items()})
     leg = dict(batch=b, shape=f"{h}x{w}", pixels_differing=round(float((gap != 0).float().mean()), 6),
                largest_difference=int(gap.max()))
-    for k in cases:
-        med = statistics.median(ms[k])
-        leg[k] = dict(ms_per_pair=round(med, 4), spread_ms=[round(min(ms[k]), 4), round(max(ms[k]), 4)])
-        print(f"{b}x{h}x{w} {k:16s} {med:10.4f} ms / pair  (reps {min(ms[k]):.4f}-{max(ms[k]):.4f})", flush=True)
+    for k in ms:
+        med, lo, hi = (v / b for v in H.summary(ms[k]))
+        leg[k] = dict(ms_per_pair=round(med, 4), spread_ms=[round(lo, 4), round(hi, 4)])
+        say(f"{b}x{h}x{w} {k:16s} {med:10.4f} ms / pair  (reps {lo:.4f}-{hi:.4f})")
     for k in ("flow", "flow+warp"):
         leg[f"torch / hip time, {k}"] = round(leg[f"torch {k}"]["ms_per_pair"] / leg[f"hip {k}"]["ms_per_pair"], 2)
-        print(f"{b}x{h}x{w} torch / hip time, {k}: {leg[f'torch / hip time, {k}']}", flush=True)
+        say(f"{b}x{h}x{w} torch / hip time, {k}: {leg[f'torch / hip time, {k}']}")
     return leg
 
 
-def _score(dev, frames, h, w):
+def _score(dev, frames, h, w, say):
     m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
     m.load_state_dict(O.make_interpolating_state_dict(n_channels=6, n_classes=3))
     m = m.to(dev).eval()
@@ -105,32 +73,24 @@ def _score(dev, frames, h, w):
     inner = holdout._predict_flow
 
     def timed(*a, **k):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = inner(*a, **k)
-        torch.cuda.synchronize()
-        spent[0] += time.perf_counter() - t0
-        return res
+        got = []
+        spent[0] += H.wall_s(lambda: got.append(inner(*a, **k)))
+        return got[0]
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         src = os.path.join(tmp, "clip.y4m")
         _clip(src, frames, h, w)
         holdout.score_video(m, src, methods=holdout.ALL_METHODS, chunk_frames=8)   # warm-up
         for name, methods in (("three methods", holdout.METHODS), ("five methods", holdout.ALL_METHODS)):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = holdout.score_video(m, src, methods=methods)
-            torch.cuda.synchronize()
-            out[f"wall_s, {name}"] = round(time.perf_counter() - t0, 3)
+            got = []
+            out[f"wall_s, {name}"] = round(H.wall_s(lambda: got.append(holdout.score_video(m, src, methods=methods))), 3)
+            res = got[0]
         holdout._predict_flow = timed
         try:
-            t0 = time.perf_counter()
-            holdout.score_video(m, src, methods=holdout.ALL_METHODS)
-            torch.cuda.synchronize()
-            wall2 = time.perf_counter() - t0
+            wall2 = H.wall_s(lambda: holdout.score_video(m, src, methods=holdout.ALL_METHODS))
         finally:
             holdout._predict_flow = inner
-    print(holdout.summary_table(res), flush=True)
+    say(holdout.summary_table(res))
     out.update(frames=frames, scored_frames=len(res["scored_frames"]), timed_run_wall_s=round(wall2, 3),
                flow_s=round(spent[0], 3), flow_share=round(spent[0] / wall2, 3))
     return out
@@ -144,17 +104,19 @@ def main():
     ap.add_argument("--torch-iters", type=int, default=1)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--clip-frames", type=int, default=65)
+    ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "flow_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
-    res = {"protocol": f"hip: HIP events, {a.warmup} warm-up calls, {a.iters} calls; torch: wall clock behind a synchronise, "
-                       f"{a.torch_iters} call(s); median of {a.reps} interleaved reps, per pair"}
-    res["1080p"] = _pair_leg(dev, a.batch, 1080, 1920, a)
-    res["256x256"] = _pair_leg(dev, a.batch, 256, 256, a)
+    dev = H.need_gpu("flow_timing")
+    report = H.Report(a.out)
+    res = {"protocol": "hip: " + H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters) + f"; torch: host clock behind a "
+                       f"device synchronise on either side, one untimed round, median of {a.reps} interleaved runs of "
+                       f"{a.torch_iters} call(s); per pair"}
+    res["1080p"] = _pair_leg(dev, a.batch, 1080, 1920, a, report.say)
+    res["256x256"] = _pair_leg(dev, a.batch, 256, 256, a, report.say)
     torch.cuda.empty_cache()
-    res["score_video"] = _score(dev, a.clip_frames, 1080, 1920)
-    print("score_video:", res["score_video"], flush=True)
-    print(json.dumps(res))
+    res["score_video"] = _score(dev, a.clip_frames, 1080, 1920, report.say)
+    report.say(f"score_video: {res['score_video']}")
+    report.finish(res)
 
 
 if __name__ == "__main__":

@@ -21,43 +21,16 @@ One JSON line last.
 """
 import argparse
 import ctypes
-import json
 import os
-import statistics
-import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native, holdout, imageio_lite as IO  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-class _Rotate:
-    """Calls fn(k) with k = 0, 1, ..., n - 1, 0, ... : each call works on the next member of a set."""
-
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+import ai_based_frame_interpolation_amd as P
+from ai_based_frame_interpolation_amd import _native, holdout, imageio_lite as IO
+from oracle import unet_oracle as O
 
 
 def _kernel_cases(dev, b, h, w, set_bytes):
@@ -79,7 +52,7 @@ def _kernel_cases(dev, b, h, w, set_bytes):
     cases, moved = {}, {}
 
     def add(name, fn, nb):
-        cases[name], moved[name] = _Rotate(fn, n_set), nb
+        cases[name], moved[name] = H.Rotate(fn, n_set), nb
 
     def planar(tag):
         for c in (2, 3, 4):   # B contiguous planes of h x (w * c): the bytes of the S = c case
@@ -121,29 +94,21 @@ def _write_clips(tmp, frames, h, w):
             "rgb24": (rgb, dict(raw="rgb24", width=w, height=h, src_fps=24))}
 
 
-def _score(dev, frames, h, w):
+def _score(dev, frames, h, w, say):
     m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
     m.load_state_dict(O.make_interpolating_state_dict(n_channels=6, n_classes=3))
     m = m.to(dev).eval()
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         clips = _write_clips(tmp, frames, h, w)
-        for name, (src, kw) in clips.items():
-            holdout.score_video(m, src, chunk_frames=8, **kw)   # warm-up: code objects, the allocator's pools
-        for rep in range(2):   # the three sources interleaved, twice: the second pass shows the spread
-            for name, (src, kw) in clips.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                res = holdout.score_video(m, src, **kw)
-                torch.cuda.synchronize()
-                wall = time.perf_counter() - t0
-                scored = len(res["scored_frames"])
-                out.setdefault(name, dict(frames=frames, scored_frames=scored, planes=res["planes"], wall_s=[],
-                                          scored_frames_per_s=[]))
-                out[name]["wall_s"].append(round(wall, 3))
-                out[name]["scored_frames_per_s"].append(round(scored / wall, 1))
-                if rep == 0:
-                    print(f"--- {name}\n{holdout.summary_table(res)}", flush=True)
+        runs = {name: (lambda src=src, kw=kw: holdout.score_video(m, src, **kw)) for name, (src, kw) in clips.items()}
+        got = {}
+        walls = H.interleaved_wall(runs, reps=2, device=dev, results=got)   # twice: the second pass shows the spread
+    for name, res in got.items():
+        scored = len(res["scored_frames"])
+        out[name] = dict(frames=frames, scored_frames=scored, planes=res["planes"], wall_s=[round(s, 3) for s in walls[name]],
+                         scored_frames_per_s=[round(scored / s, 1) for s in walls[name]])
+        say(f"--- {name}\n{holdout.summary_table(res)}")
     return out
 
 
@@ -156,46 +121,39 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--shape", default="1080x1920")
     ap.add_argument("--clip-frames", type=int, default=65)
+    ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "holdout_raw_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
+    dev = H.need_gpu("holdout_raw_timing")
+    report = H.Report(a.out)
+    say = report.say
     h, w = (int(v) for v in a.shape.split("x"))
-    res = {"protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of {a.iters} "
-                       f"calls rotating over a set of at least {a.set_gb} GB"}
+    res = {"protocol": H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, set_gb=a.set_gb)}
     cases, moved, pairs, info = _kernel_cases(dev, a.batch, h, w, int(a.set_gb * 1e9))
-    for fn in cases.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
-        for k, fn in cases.items():
-            ms[k].append(_time(fn, a.iters))
+    ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters)
     leg = dict(info)
     for k in cases:
-        med = statistics.median(ms[k])
-        leg[k] = dict(ms=round(med, 5), spread_ms=[round(min(ms[k]), 5), round(max(ms[k]), 5)],
+        med, lo, hi = H.summary(ms[k])
+        leg[k] = dict(ms=round(med, 5), spread_ms=[round(lo, 5), round(hi, 5)],
                       gb_per_s=round(moved[k] / (med * 1e-3) / 1e9, 1))
-        print(f"{a.batch}x{h}x{w} {k:24s} {med:8.5f} ms  (reps {min(ms[k]):.5f}-{max(ms[k]):.5f})  "
-              f"{leg[k]['gb_per_s']:7.1f} GB/s", flush=True)
+        say(f"{a.batch}x{h}x{w} {k:24s} {med:8.5f} ms  (reps {lo:.5f}-{hi:.5f})  {leg[k]['gb_per_s']:7.1f} GB/s")
     for c in (2, 3, 4):
         ta, tb = leg[f"psnr plane {c}x_a"]["ms"], leg[f"psnr plane {c}x_b"]["ms"]
-        leg[f"psnr S={c} yardstick_spread"] = round(abs(ta - tb) / min(ta, tb), 4)
+        leg[f"psnr S={c} yardstick_spread"] = round(H.pair_spread(ta, tb), 4)
         leg[f"psnr S={c} time_vs_plane"] = round(leg[f"psnr interleaved S={c}"]["ms"] / max(ta, tb), 3)
-        print(f"psnr S={c}: in-job spread of the planar yardstick {leg[f'psnr S={c} yardstick_spread']:.4f}; interleaved / "
-              f"planar time {leg[f'psnr S={c} time_vs_plane']:.3f}", flush=True)
+        say(f"psnr S={c}: in-job spread of the planar yardstick {leg[f'psnr S={c} yardstick_spread']:.4f}; interleaved / "
+            f"planar time {leg[f'psnr S={c} time_vs_plane']:.3f}")
     ta, tb = leg["ssim step1_a"]["ms"], leg["ssim step1_b"]["ms"]
-    leg["ssim yardstick_spread"] = round(abs(ta - tb) / min(ta, tb), 4)
+    leg["ssim yardstick_spread"] = round(H.pair_spread(ta, tb), 4)
     for c in (2, 3, 4):
         leg[f"ssim step{c} time_vs_step1"] = round(leg[f"ssim step{c}"]["ms"] / max(ta, tb), 3)
-    print(f"ssim: in-job spread of step 1 {leg['ssim yardstick_spread']:.4f}; step 2 / 3 / 4 over step 1 "
-          + " / ".join(f"{leg[f'ssim step{c} time_vs_step1']:.3f}" for c in (2, 3, 4)), flush=True)
+    say(f"ssim: in-job spread of step 1 {leg['ssim yardstick_spread']:.4f}; step 2 / 3 / 4 over step 1 "
+        + " / ".join(f"{leg[f'ssim step{c} time_vs_step1']:.3f}" for c in (2, 3, 4)))
     res["kernels"] = leg
     del cases, pairs
     torch.cuda.empty_cache()
-    res["score_video"] = _score(dev, a.clip_frames, h, w)
-    print("score_video:", res["score_video"], flush=True)
-    print(json.dumps(res))
+    res["score_video"] = _score(dev, a.clip_frames, h, w, say)
+    say(f"score_video: {res['score_video']}")
+    report.finish(res)
 
 
 if __name__ == "__main__":

@@ -23,43 +23,16 @@ One JSON line last.
 """
 import argparse
 import ctypes
-import json
 import os
-import statistics
-import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native, holdout, stream, imageio_lite as IO  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-class _Rotate:
-    """Calls fn(k) with k = 0, 1, ..., n - 1, 0, ... : each call works on the next member of a set."""
-
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+import ai_based_frame_interpolation_amd as P
+from ai_based_frame_interpolation_amd import _native, holdout, stream, imageio_lite as IO
+from oracle import unet_oracle as O
 
 
 def _kernel_cases(dev, b, h, w, set_bytes):
@@ -83,7 +56,7 @@ def _kernel_cases(dev, b, h, w, set_bytes):
     cases, moved = {}, {}
 
     def add(name, fn, nb):
-        cases[name], moved[name] = _Rotate(fn, n_set), nb
+        cases[name], moved[name] = H.Rotate(fn, n_set), nb
 
     def u8(tag):
         add(f"psnr u8_{tag}", lambda k: _native.check(L.fiunet_psnr_u8(ptr[k][0], ptr[k][1], b, h, w, op, wp, sz, s), "psnr_u8"),
@@ -120,7 +93,7 @@ def _clip(path, frames, h, w):
             wr.write(row[None])
 
 
-def _score(dev, frames, h, w):
+def _score(dev, frames, h, w, say):
     m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
     m.load_state_dict(O.make_interpolating_state_dict(n_channels=6, n_classes=3))
     m = m.to(dev).eval()
@@ -132,33 +105,25 @@ def _score(dev, frames, h, w):
         run = route.run
 
         def timed(d, factor):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = run(d, factor)
-            torch.cuda.synchronize()
-            spent[0] += time.perf_counter() - t0
-            return res
+            got = []
+            spent[0] += H.wall_s(lambda: got.append(run(d, factor)))
+            return got[0]
         route.run = timed
         return route
     with tempfile.TemporaryDirectory() as tmp:
         src = os.path.join(tmp, "clip.y4m")
         _clip(src, frames, h, w)
         holdout.score_video(m, src, chunk_frames=8)   # warm-up: code objects, the allocator's pools
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = holdout.score_video(m, src)
-        torch.cuda.synchronize()
-        wall = time.perf_counter() - t0
+        got = []
+        wall = H.wall_s(lambda: got.append(holdout.score_video(m, src)))
+        res = got[0]
         stream._y4m_route = timed_route
         try:
-            t0 = time.perf_counter()
-            holdout.score_video(m, src)
-            torch.cuda.synchronize()
-            wall2 = time.perf_counter() - t0
+            wall2 = H.wall_s(lambda: holdout.score_video(m, src))
         finally:
             stream._y4m_route = make_route
     scored = len(res["scored_frames"])
-    print(holdout.summary_table(res), flush=True)
+    say(holdout.summary_table(res))
     return dict(frames=frames, scored_frames=scored, wall_s=round(wall, 3), scored_frames_per_s=round(scored / wall, 2),
                 timed_run_wall_s=round(wall2, 3), forward_s=round(spent[0], 3), forward_share=round(spent[0] / wall2, 3))
 
@@ -172,42 +137,35 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--shape", default="1080x1920")
     ap.add_argument("--clip-frames", type=int, default=65)
+    ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "holdout_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
+    dev = H.need_gpu("holdout_timing")
+    report = H.Report(a.out)
+    say = report.say
     h, w = (int(v) for v in a.shape.split("x"))
-    res = {"protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of {a.iters} "
-                       f"calls rotating over a set of at least {a.set_gb} GB"}
+    res = {"protocol": H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, set_gb=a.set_gb)}
     cases, moved, pairs, info = _kernel_cases(dev, a.batch, h, w, int(a.set_gb * 1e9))
-    for fn in cases.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
-        for k, fn in cases.items():
-            ms[k].append(_time(fn, a.iters))
+    ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters)
     leg = dict(info)
     for k in cases:
-        med = statistics.median(ms[k])
-        leg[k] = dict(ms=round(med, 5), spread_ms=[round(min(ms[k]), 5), round(max(ms[k]), 5)],
+        med, lo, hi = H.summary(ms[k])
+        leg[k] = dict(ms=round(med, 5), spread_ms=[round(lo, 5), round(hi, 5)],
                       gb_per_s=round(moved[k] / (med * 1e-3) / 1e9, 1))
-        print(f"{a.batch}x{h}x{w} {k:20s} {med:8.5f} ms  (reps {min(ms[k]):.5f}-{max(ms[k]):.5f})  "
-              f"{leg[k]['gb_per_s']:7.1f} GB/s", flush=True)
+        say(f"{a.batch}x{h}x{w} {k:20s} {med:8.5f} ms  (reps {lo:.5f}-{hi:.5f})  {leg[k]['gb_per_s']:7.1f} GB/s")
     for name in ("psnr", "ssim"):
         ta, tb = leg[f"{name} u8_a"]["ms"], leg[f"{name} u8_b"]["ms"]
-        leg[f"{name} u8_spread"] = round(abs(ta - tb) / min(ta, tb), 4)
+        leg[f"{name} u8_spread"] = round(H.pair_spread(ta, tb), 4)
         for k in cases:
             if k.startswith(name) and "u8_" not in k:
                 leg[f"{k} time_vs_u8"] = round(leg[k]["ms"] / max(ta, tb), 3)
-        print(f"{name}: in-job spread of the u8 yardstick {leg[f'{name} u8_spread']:.4f}; plane8 / u8 time "
-              f"{leg[f'{name} plane8 time_vs_u8']:.3f}", flush=True)
+        say(f"{name}: in-job spread of the u8 yardstick {leg[f'{name} u8_spread']:.4f}; plane8 / u8 time "
+            f"{leg[f'{name} plane8 time_vs_u8']:.3f}")
     res["kernels"] = leg
     del cases, pairs
     torch.cuda.empty_cache()
-    res["score_video"] = _score(dev, a.clip_frames, h, w)
-    print("score_video:", res["score_video"], flush=True)
-    print(json.dumps(res))
+    res["score_video"] = _score(dev, a.clip_frames, h, w, say)
+    say(f"score_video: {res['score_video']}")
+    report.finish(res)
 
 
 if __name__ == "__main__":

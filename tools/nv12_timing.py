@@ -16,41 +16,13 @@ One JSON line last.
     python tools/nv12_timing.py [--batch 8 --set-gb 1 --iters 200 --reps 7]
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native  # noqa: E402
-from ai_based_frame_interpolation_amd.colour import SurfaceLayout, resolve_layout  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-class _Rotate:
-    """Calls fn(k) with k = 0, 1, ..., n - 1, 0, ... : each call works on the next member of a set."""
-
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+import ai_based_frame_interpolation_amd as P
+from ai_based_frame_interpolation_amd import _native
+from ai_based_frame_interpolation_amd.colour import SurfaceLayout, resolve_layout
 
 
 def _kernel_cases(dev, bits, b, h, w, set_bytes):
@@ -74,14 +46,14 @@ def _kernel_cases(dev, bits, b, h, w, set_bytes):
 
     def planar(decode):
         if decode:
-            return _Rotate(lambda k: _native.yuv420_to_rgb(yuv[k][:, :fs], rgb[k], h, w, flags, bits), n_set)
-        return _Rotate(lambda k: _native.rgb_to_yuv420(rgb[k], yuv[k][:, :fs], flags, bits), n_set)
+            return H.Rotate(lambda k: _native.yuv420_to_rgb(yuv[k][:, :fs], rgb[k], h, w, flags, bits), n_set)
+        return H.Rotate(lambda k: _native.rgb_to_yuv420(rgb[k], yuv[k][:, :fs], flags, bits), n_set)
 
     def semi(decode, lay):
         n = lay.frame_stride
         if decode:
-            return _Rotate(lambda k: _native.surface_to_rgb(yuv[k][:, :n], lay, rgb[k], h, w, flags, bits), n_set)
-        return _Rotate(lambda k: _native.rgb_to_surface(rgb[k], yuv[k][:, :n], lay, flags, bits), n_set)
+            return H.Rotate(lambda k: _native.surface_to_rgb(yuv[k][:, :n], lay, rgb[k], h, w, flags, bits), n_set)
+        return H.Rotate(lambda k: _native.rgb_to_surface(rgb[k], yuv[k][:, :n], lay, flags, bits), n_set)
     cases = {}
     for name, decode in (("decode", True), ("encode", False)):
         cases[f"{name} i420_a"] = planar(decode)
@@ -100,34 +72,27 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--shapes", default="1080x1920,2160x3840")
+    ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "nv12_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
+    dev = H.need_gpu("nv12_timing")
+    report = H.Report(a.out)
     res = {"kernels": {}, "forward": {},
-           "protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of {a.iters} "
-                       f"calls rotating over a set of at least {a.set_gb} GB"}
+           "protocol": H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, set_gb=a.set_gb)}
     for shape in a.shapes.split(","):
         h, w = (int(v) for v in shape.split("x"))
         for bits in (8, 10):
             cases, moved, info = _kernel_cases(dev, bits, a.batch, h, w, int(a.set_gb * 1e9))
-            for fn in cases.values():
-                for _ in range(a.warmup):
-                    fn()
-            torch.cuda.synchronize()
-            ms = {k: [] for k in cases}
-            for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
-                for k, fn in cases.items():
-                    ms[k].append(_time(fn, a.iters))
+            ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters)
             leg = dict(info)
             for k in cases:
-                med = statistics.median(ms[k])
-                leg[k] = dict(ms=round(med, 4), spread_ms=[round(min(ms[k]), 4), round(max(ms[k]), 4)],
+                med, lo, hi = H.summary(ms[k])
+                leg[k] = dict(ms=round(med, 4), spread_ms=[round(lo, 4), round(hi, 4)],
                               gb_per_s=round(moved / (med * 1e-3) / 1e9, 1))
-                print(f"{h}x{w} {bits:2d} bit {k:20s} {med:8.4f} ms  (reps {min(ms[k]):.4f}-{max(ms[k]):.4f})  "
-                      f"{leg[k]['gb_per_s']:7.1f} GB/s", flush=True)
+                report.say(f"{h}x{w} {bits:2d} bit {k:20s} {med:8.4f} ms  (reps {lo:.4f}-{hi:.4f})  "
+                           f"{leg[k]['gb_per_s']:7.1f} GB/s")
             for name in ("decode", "encode"):
                 ia, ib = leg[f"{name} i420_a"]["gb_per_s"], leg[f"{name} i420_b"]["gb_per_s"]
-                leg[f"{name} i420_spread"] = round(abs(ia - ib) / max(ia, ib), 4)
+                leg[f"{name} i420_spread"] = round(H.pair_spread(ia, ib), 4)
                 leg[f"{name} nv12_vs_i420"] = round(leg[f"{name} nv12"]["gb_per_s"] / min(ia, ib), 3)
                 leg[f"{name} nv12_pitched_vs_i420"] = round(leg[f"{name} nv12_pitched"]["gb_per_s"] / min(ia, ib), 3)
             res["kernels"][f"{h}x{w}_{bits}bit"] = leg
@@ -135,9 +100,7 @@ def main():
             torch.cuda.empty_cache()
 
     b, h, w = 8, 1080, 1920
-    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
-    m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
-    m = m.to(dev).eval()
+    m, _ = H.seeded_model(3, "bf16", dev, b)
     g = torch.Generator(device=dev).manual_seed(1)
     f1, f2 = (torch.randint(0, 256, (b, P.i420_frame_bytes(h, w)), dtype=torch.uint8, device=dev, generator=g)
               for _ in range(2))
@@ -146,21 +109,14 @@ def main():
     runs = {"forward_yuv420_a": lambda: m.forward_yuv420(f1, f2, h, w, out=out, **opts),
             "forward_nv12": lambda: m.forward_nv12(f1, f2, h, w, out=out, **opts),
             "forward_yuv420_b": lambda: m.forward_yuv420(f1, f2, h, w, out=out, **opts)}
-    for fn in runs.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in runs}
-    for _ in range(a.reps):
-        for k, fn in runs.items():
-            ms[k].append(_time(fn, 5))
+    ms = H.interleaved(runs, warmup=a.warmup, reps=a.reps, iters=5)
     for k in runs:
-        med = statistics.median(ms[k])
-        res["forward"][k] = dict(ms=round(med, 3), spread_ms=[round(min(ms[k]), 3), round(max(ms[k]), 3)],
+        med, lo, hi = H.summary(ms[k])
+        res["forward"][k] = dict(ms=round(med, 3), spread_ms=[round(lo, 3), round(hi, 3)],
                                  frames_per_s=round(b / (med * 1e-3), 1))
-        print(f"{b}x{h}x{w} bf16 {k:18s} {med:8.3f} ms  (reps {min(ms[k]):.3f}-{max(ms[k]):.3f})  "
-              f"{res['forward'][k]['frames_per_s']:7.1f} frames/s", flush=True)
-    print(json.dumps(res))
+        report.say(f"{b}x{h}x{w} bf16 {k:18s} {med:8.3f} ms  (reps {lo:.3f}-{hi:.3f})  "
+                   f"{res['forward'][k]['frames_per_s']:7.1f} frames/s")
+    report.finish(res)
 
 
 if __name__ == "__main__":

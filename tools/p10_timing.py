@@ -12,28 +12,11 @@ last.
     python tools/p10_timing.py [--batch 8 --height 1080 --width 1920 --precisions bf16,bf16x2]
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+import ai_based_frame_interpolation_amd as P
 
 
 def main():
@@ -45,14 +28,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "p10_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
+    dev = H.need_gpu("p10_timing")
+    report = H.Report(a.out)
     b, h, w = a.batch, a.height, a.width
     fs = P.yuv420p10_frame_samples(h, w)
-    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3)
-    m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
-    m = m.to(dev).eval()
+    m, _ = H.seeded_model(3, a.precisions.split(",")[0], dev, b)
     g = torch.Generator(device=dev).manual_seed(0)
     # uint16 tensors are made as int16 and viewed (torch's uint16 has limited GPU support)
     y1, y2 = (torch.randint(0, 1024, (b, fs), dtype=torch.int16, device=dev, generator=g).view(torch.uint16)
@@ -70,28 +52,20 @@ def main():
         "forward_u8": lambda: m.forward_u8(u1, u2, out=u8_out),
     }
     res = {"shape": [b, h, w], "network": "rgb 6->3", "ms": {}, "spread_ms": {}, "share_of_step": {},
-           "protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of "
-                       f"{a.iters} calls"}
+           "protocol": H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters)}
     for prec in a.precisions.split(","):
         m.precision = prec
-        for fn in cases.values():
-            for _ in range(a.warmup):
-                fn()
-        torch.cuda.synchronize()
-        ms = {k: [] for k in cases}
-        for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
-            for k, fn in cases.items():
-                ms[k].append(_time(fn, a.iters))
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters)
+        med = {k: H.summary(v)[0] for k, v in ms.items()}
         res["ms"][prec] = med
         res["spread_ms"][prec] = {k: [min(v), max(v)] for k, v in ms.items()}
         res["share_of_step"][prec] = {k: (med[k] - med["forward"]) / med[k]
                                       for k in ("forward_p10", "forward_yuv420p10")}
         for k in cases:
-            print(f"{prec:7s} {k:18s} {med[k]:8.3f} ms  (reps {min(ms[k]):.3f}-{max(ms[k]):.3f})")
+            report.say(f"{prec:7s} {k:18s} {med[k]:8.3f} ms  (reps {min(ms[k]):.3f}-{max(ms[k]):.3f})")
         for k, v in res["share_of_step"][prec].items():
-            print(f"{prec:7s} extra passes of {k}: {100 * v:.2f} % of its step")
-    print(json.dumps(res))
+            report.say(f"{prec:7s} extra passes of {k}: {100 * v:.2f} % of its step")
+    report.finish(res)
 
 
 if __name__ == "__main__":

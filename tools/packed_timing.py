@@ -17,40 +17,12 @@ One JSON line last.
     python tools/packed_timing.py [--batch 8 --set-gb 1 --iters 200 --reps 7]
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native, packed  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-class _Rotate:
-    """Calls fn(k) with k = 0, 1, ..., n - 1, 0, ... : each call works on the next member of a set."""
-
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+import ai_based_frame_interpolation_amd as P
+from ai_based_frame_interpolation_amd import _native, packed
 
 
 def _kernel_cases(dev, b, h, w, set_bytes):
@@ -71,7 +43,7 @@ def _kernel_cases(dev, b, h, w, set_bytes):
     cases, moved = {}, {}
 
     def add(name, fn, nbytes):
-        cases[name], moved[name] = _Rotate(fn, n_set), b * nbytes
+        cases[name], moved[name] = H.Rotate(fn, n_set), b * nbytes
 
     def i420(tag):
         add(f"unpack i420_{tag}", lambda k: _native.yuv420_to_rgb(pk[k][:, :fs], rgb[k], h, w, flags, 8), fs + 3 * h * w)
@@ -102,33 +74,25 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--shapes", default="1080x1920,2160x3840")
+    ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "packed_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
+    dev = H.need_gpu("packed_timing")
+    report = H.Report(a.out)
     res = {"kernels": {}, "forward": {},
-           "protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of {a.iters} "
-                       f"calls rotating over a set of at least {a.set_gb} GB"}
+           "protocol": H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, set_gb=a.set_gb)}
     for shape in a.shapes.split(","):
         h, w = (int(v) for v in shape.split("x"))
         cases, moved, info = _kernel_cases(dev, a.batch, h, w, int(a.set_gb * 1e9))
-        for fn in cases.values():
-            for _ in range(a.warmup):
-                fn()
-        torch.cuda.synchronize()
-        ms = {k: [] for k in cases}
-        for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
-            for k, fn in cases.items():
-                ms[k].append(_time(fn, a.iters))
+        ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters)
         leg = dict(info)
         for k in cases:
-            med = statistics.median(ms[k])
-            leg[k] = dict(ms=round(med, 4), spread_ms=[round(min(ms[k]), 4), round(max(ms[k]), 4)],
+            med, lo, hi = H.summary(ms[k])
+            leg[k] = dict(ms=round(med, 4), spread_ms=[round(lo, 4), round(hi, 4)],
                           gb_per_s=round(moved[k] / (med * 1e-3) / 1e9, 1))
-            print(f"{h}x{w} {k:22s} {med:8.4f} ms  (reps {min(ms[k]):.4f}-{max(ms[k]):.4f})  "
-                  f"{leg[k]['gb_per_s']:7.1f} GB/s", flush=True)
+            report.say(f"{h}x{w} {k:22s} {med:8.4f} ms  (reps {lo:.4f}-{hi:.4f})  {leg[k]['gb_per_s']:7.1f} GB/s")
         for name in ("unpack", "pack"):
             ia, ib = leg[f"{name} i420_a"]["gb_per_s"], leg[f"{name} i420_b"]["gb_per_s"]
-            leg[f"{name} i420_spread"] = round(abs(ia - ib) / max(ia, ib), 4)
+            leg[f"{name} i420_spread"] = round(H.pair_spread(ia, ib), 4)
         # the yardstick of every case: the I420 encode's bytes per second
         enc = min(leg["pack i420_a"]["gb_per_s"], leg["pack i420_b"]["gb_per_s"])
         for k in cases:
@@ -139,9 +103,7 @@ def main():
         torch.cuda.empty_cache()
 
     b, h, w = 8, 1080, 1920
-    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
-    m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
-    m = m.to(dev).eval()
+    m, _ = H.seeded_model(3, "bf16", dev, b)
     g = torch.Generator(device=dev).manual_seed(1)
     p1, p2 = (torch.randint(0, 256, (b, 3, h, w), dtype=torch.uint8, device=dev, generator=g) for _ in range(2))
     pout = torch.empty_like(p1)
@@ -155,21 +117,14 @@ def main():
         runs[f"forward_rgb_packed {fmt}"] = (lambda f1=f1, f2=f2, out=out, fmt=fmt:
                                              m.forward_rgb_packed(f1, f2, h, w, format=fmt, out=out))
     runs["forward_u8_b"] = lambda: m.forward_u8(p1, p2, out=pout)
-    for fn in runs.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in runs}
-    for _ in range(a.reps):
-        for k, fn in runs.items():
-            ms[k].append(_time(fn, 5))
+    ms = H.interleaved(runs, warmup=a.warmup, reps=a.reps, iters=5)
     for k in runs:
-        med = statistics.median(ms[k])
-        res["forward"][k] = dict(ms=round(med, 3), spread_ms=[round(min(ms[k]), 3), round(max(ms[k]), 3)],
+        med, lo, hi = H.summary(ms[k])
+        res["forward"][k] = dict(ms=round(med, 3), spread_ms=[round(lo, 3), round(hi, 3)],
                                  frames_per_s=round(b / (med * 1e-3), 1))
-        print(f"{b}x{h}x{w} bf16 {k:26s} {med:8.3f} ms  (reps {min(ms[k]):.3f}-{max(ms[k]):.3f})  "
-              f"{res['forward'][k]['frames_per_s']:7.1f} frames/s", flush=True)
-    print(json.dumps(res))
+        report.say(f"{b}x{h}x{w} bf16 {k:26s} {med:8.3f} ms  (reps {lo:.3f}-{hi:.3f})  "
+                   f"{res['forward'][k]['frames_per_s']:7.1f} frames/s")
+    report.finish(res)
 
 
 if __name__ == "__main__":

@@ -21,47 +21,20 @@ One JSON line last; the text goes to `--out` as well (default profiles/resize_ar
     python tools/resize_area_timing.py [--batch 8 --set-gb 1 --iters 50 --reps 7]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import imageio_lite, resize  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+from ai_based_frame_interpolation_amd import imageio_lite, resize
 
 FORMATS = {"i420": (("y4m", "420jpeg"), 8), "yuv422p10le": ("yuv422p10le", 10), "nv12": ("nv12", 8), "rgb24": ("rgb24", 8)}
 #: (format, source (h, w), destination (h, w))
 CASES = [("i420", (1080, 1920), (256, 256)), ("yuv422p10le", (1080, 1920), (256, 256)), ("nv12", (1080, 1920), (256, 256)),
          ("rgb24", (1080, 1920), (256, 256)), ("i420", (2160, 3840), (1080, 1920))]
 PLANAR_YARDSTICK = {"nv12": "i420", "rgb24": "yuv422p10le"}
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-class _Rotate:
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
 
 
 def _kernel_case(dev, name, b, src_hw, dst_hw, set_bytes):
@@ -85,7 +58,7 @@ def _kernel_case(dev, name, b, src_hw, dst_hw, set_bytes):
 
     def linear(k):
         resize.resize_frames(src[k], sp, dp, bits, out=small[k], filter="linear")
-    cases = {f"{n}_{r}": _Rotate(fn, n_set) for r in "ab" for n, fn in (("copy", copy), ("area", area), ("linear", linear))}
+    cases = {f"{n}_{r}": H.Rotate(fn, n_set) for r in "ab" for n, fn in (("copy", copy), ("area", area), ("linear", linear))}
     return cases, rbytes
 
 
@@ -94,15 +67,8 @@ def _kernels(dev, a, say):
     for name, src_hw, dst_hw in CASES:
         label = f"{name} {src_hw[0]}x{src_hw[1]}->{dst_hw[0]}x{dst_hw[1]}"
         cases, rbytes = _kernel_case(dev, name, a.batch, src_hw, dst_hw, int(a.set_gb * 1e9))
-        for fn in cases.values():
-            for _ in range(a.warmup):
-                fn()
-        torch.cuda.synchronize()
-        ms = {k: [] for k in cases}
-        for _ in range(a.reps):
-            for k, fn in cases.items():
-                ms[k].append(_time(fn, a.iters))
-        us = {k: statistics.median(v) * 1e3 for k, v in ms.items()}
+        ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters)
+        us = {k: H.summary(v)[0] * 1e3 for k, v in ms.items()}
         leg = {n: [round(us[n + "_a"], 1), round(us[n + "_b"], 1)] for n in ("copy", "area", "linear")}
         spread = max(abs(us[n + "_a"] - us[n + "_b"]) for n in ("copy", "area"))
         worst, yard = max(leg["area"]), min(leg["copy"])
@@ -128,9 +94,7 @@ def _kernels(dev, a, say):
 
 def _stream(dev, a, say):
     n, (h, w), size = a.stream_frames, (1080, 1920), (256, 256)
-    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=1, precision="bf16")
-    m.load_state_dict(O.make_seeded_state_dict(1234))
-    fi = P.FrameInterpolator(model=m.to(dev).eval(), device=dev, batch=8)
+    _, fi = H.seeded_model(1, "bf16", dev)
     sp = resize.frame_planes(("y4m", "420jpeg"), h, w)
     rng = np.random.default_rng(1)
     base = rng.integers(0, 256, resize.frame_samples(sp), dtype=np.uint8)
@@ -141,23 +105,14 @@ def _stream(dev, a, say):
             wr.write(rows)
 
         def run(**kw):
-            with open(os.devnull, "wb") as sink:
-                fi.interpolate_video(big, sink, 2, chunk_frames=8, resize=size, **kw)
-            torch.cuda.synchronize()
+            fi.interpolate_video(big, H.NullSink(), 2, chunk_frames=8, resize=size, **kw)
         runs = {"linear": lambda: run(resize_filter="linear"), "area": lambda: run(resize_filter="area")}
-        secs = {k: [] for k in runs}
-        for fn in runs.values():
-            fn()
-        for _ in range(a.stream_reps):
-            for k, fn in runs.items():
-                t0 = time.perf_counter()
-                fn()
-                secs[k].append(time.perf_counter() - t0)
+        secs = H.interleaved_wall(runs, reps=a.stream_reps, device=dev)
     out = {}
     for k, v in secs.items():
-        med = statistics.median(v)
-        out[k] = dict(s=round(med, 4), spread_s=[round(min(v), 4), round(max(v), 4)], frames_per_s=round(n / med, 1))
-        say(f"stream {n} x 1080p -> 256x256, gray bf16, chunks of 8: {k:7s} {med:8.4f} s (reps {min(v):.4f}-{max(v):.4f})  "
+        med, lo, hi = H.summary(v)
+        out[k] = dict(s=round(med, 4), spread_s=[round(lo, 4), round(hi, 4)], frames_per_s=round(n / med, 1))
+        say(f"stream {n} x 1080p -> 256x256, gray bf16, chunks of 8: {k:7s} {med:8.4f} s (reps {lo:.4f}-{hi:.4f})  "
             f"{out[k]['frames_per_s']:8.1f} source frames/s")
     return out
 
@@ -171,22 +126,15 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--stream-frames", type=int, default=33)
     ap.add_argument("--stream-reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resize_area_timing.txt"))
+    ap.add_argument("--out", default=os.path.join(H.ROOT, "profiles", "resize_area_timing.txt"))
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "resize_area_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-    say(f"# tools/resize_area_timing.py: B = {a.batch}; HIP events, {a.warmup} warm-up calls per case, median of {a.reps} "
-        f"interleaved reps of {a.iters} calls rotating over a set of at least {a.set_gb} GB; {torch.cuda.get_device_name(0)}")
-    res = {"kernel": _kernels(dev, a, say), "stream": _stream(dev, a, say)}
-    say(json.dumps(res))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    dev = H.need_gpu("resize_area_timing")
+    report = H.Report(a.out)
+    say = report.say
+    say(f"# tools/resize_area_timing.py: B = {a.batch}; "
+        f"{H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, set_gb=a.set_gb, wall_reps=a.stream_reps)}; "
+        f"{torch.cuda.get_device_name(0)}")
+    report.finish({"kernel": _kernels(dev, a, say), "stream": _stream(dev, a, say)})
 
 
 if __name__ == "__main__":

@@ -21,44 +21,17 @@ One JSON line last; the text goes to `--out` as well (default profiles/resize_ti
     python tools/resize_timing.py [--batch 8 --set-gb 1 --iters 50 --reps 7]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native, imageio_lite, resize  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+from ai_based_frame_interpolation_amd import _native, imageio_lite, resize
 
 FORMATS = {"i420": (("y4m", "420jpeg"), 8), "nv12": ("nv12", 8), "rgb24": ("rgb24", 8), "yuv422p10le": ("yuv422p10le", 10)}
 SCALES = [((1080, 1920), (256, 256)), ((2160, 3840), (1080, 1920)), ((1080, 1920), (1080, 1920)), ((540, 960), (1080, 1920))]
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-class _Rotate:
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
 
 
 def _kernel_case(dev, name, b, src_hw, dst_hw, set_bytes):
@@ -79,9 +52,9 @@ def _kernel_case(dev, name, b, src_hw, dst_hw, set_bytes):
     vid = [torch.randint(0, 256, (2 * b + 1, rd * item), dtype=torch.uint8, device=dev, generator=g) for _ in range(n_hold)]
     flags = torch.ones(b, dtype=torch.uint8, device=dev)
     cases = {
-        "hold_a": _Rotate(lambda k: _native.hold_cut_frames(vid[k], b + 1, 2, flags), n_hold),
-        "resize": _Rotate(lambda k: resize.resize_frames(src[k], sp, dp, bits, out=dst[k]), n_set),
-        "hold_b": _Rotate(lambda k: _native.hold_cut_frames(vid[k], b + 1, 2, flags), n_hold),
+        "hold_a": H.Rotate(lambda k: _native.hold_cut_frames(vid[k], b + 1, 2, flags), n_hold),
+        "resize": H.Rotate(lambda k: resize.resize_frames(src[k], sp, dp, bits, out=dst[k]), n_set),
+        "hold_b": H.Rotate(lambda k: _native.hold_cut_frames(vid[k], b + 1, 2, flags), n_hold),
     }
     return cases, rbytes, wbytes
 
@@ -92,22 +65,15 @@ def _kernels(dev, a, say):
         for name in FORMATS:
             label = f"{name} {src_hw[0]}x{src_hw[1]}->{dst_hw[0]}x{dst_hw[1]}"
             cases, rbytes, wbytes = _kernel_case(dev, name, a.batch, src_hw, dst_hw, int(a.set_gb * 1e9))
-            for fn in cases.values():
-                for _ in range(a.warmup):
-                    fn()
-            torch.cuda.synchronize()
-            ms = {k: [] for k in cases}
-            for _ in range(a.reps):
-                for k, fn in cases.items():
-                    ms[k].append(_time(fn, a.iters))
-            med = {k: statistics.median(v) for k, v in ms.items()}
+            ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters)
+            med = {k: H.summary(v)[0] for k, v in ms.items()}
             hold = [wbytes / (med[k] * 1e-3) / 1e9 for k in ("hold_a", "hold_b")]
             written = wbytes / (med["resize"] * 1e-3) / 1e9
             leg = dict(us=round(med["resize"] * 1e3, 1), spread_us=[round(min(ms["resize"]) * 1e3, 1), round(max(ms["resize"]) * 1e3, 1)],
                        gb_per_s=round((rbytes + wbytes) / (med["resize"] * 1e-3) / 1e9, 1), written_gb_per_s=round(written, 1),
                        hold_us=[round(med["hold_a"] * 1e3, 1), round(med["hold_b"] * 1e3, 1)],
                        hold_written_gb_per_s=[round(v, 1) for v in hold],
-                       hold_spread=round(abs(hold[0] - hold[1]) / max(hold), 4), vs_hold=round(written / min(hold), 3))
+                       hold_spread=round(H.pair_spread(*hold), 4), vs_hold=round(written / min(hold), 3))
             out[label] = leg
             say(f"{label:38s} {leg['us']:9.1f} us (reps {leg['spread_us'][0]:.1f}-{leg['spread_us'][1]:.1f})  "
                 f"{leg['gb_per_s']:7.1f} GB/s r+w  {leg['written_gb_per_s']:7.1f} GB/s written | hold "
@@ -120,9 +86,7 @@ def _kernels(dev, a, say):
 
 def _stream(dev, a, say):
     n, (h, w), size = a.stream_frames, (1080, 1920), (256, 256)
-    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=1, precision="bf16")
-    m.load_state_dict(O.make_seeded_state_dict(1234))
-    fi = P.FrameInterpolator(model=m.to(dev).eval(), device=dev, batch=8)
+    _, fi = H.seeded_model(1, "bf16", dev)
     kind = ("y4m", "420jpeg")
     sp, dp = resize.frame_planes(kind, h, w), resize.frame_planes(kind, size[1], size[0])
     rng = np.random.default_rng(1)
@@ -143,9 +107,7 @@ def _stream(dev, a, say):
             wr.write(host_resize(rows))
 
         def run(path, **kw):
-            with open(os.devnull, "wb") as sink:
-                fi.interpolate_video(path, sink, 2, chunk_frames=8, **kw)
-            torch.cuda.synchronize()
+            fi.interpolate_video(path, H.NullSink(), 2, chunk_frames=8, **kw)
 
         def host():
             frames = imageio_lite.read_y4m_packed(big)[0]
@@ -153,19 +115,12 @@ def _stream(dev, a, say):
                 wr.write(host_resize(frames))
             run(tmp)
         runs = {"device": lambda: run(big, resize=size), "pre": lambda: run(small), "host": host}
-        secs = {k: [] for k in runs}
-        for fn in runs.values():
-            fn()
-        for _ in range(a.stream_reps):
-            for k, fn in runs.items():
-                t0 = time.perf_counter()
-                fn()
-                secs[k].append(time.perf_counter() - t0)
+        secs = H.interleaved_wall(runs, reps=a.stream_reps, device=dev)
     out = {}
     for k, v in secs.items():
-        med = statistics.median(v)
-        out[k] = dict(s=round(med, 4), spread_s=[round(min(v), 4), round(max(v), 4)], frames_per_s=round(n / med, 1))
-        say(f"stream {n} x 1080p -> 256x256, gray bf16, chunks of 8: {k:7s} {med:8.4f} s (reps {min(v):.4f}-{max(v):.4f})  "
+        med, lo, hi = H.summary(v)
+        out[k] = dict(s=round(med, 4), spread_s=[round(lo, 4), round(hi, 4)], frames_per_s=round(n / med, 1))
+        say(f"stream {n} x 1080p -> 256x256, gray bf16, chunks of 8: {k:7s} {med:8.4f} s (reps {lo:.4f}-{hi:.4f})  "
             f"{out[k]['frames_per_s']:8.1f} source frames/s")
     return out
 
@@ -179,22 +134,15 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--stream-frames", type=int, default=33)
     ap.add_argument("--stream-reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resize_timing.txt"))
+    ap.add_argument("--out", default=os.path.join(H.ROOT, "profiles", "resize_timing.txt"))
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "resize_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-    say(f"# tools/resize_timing.py: B = {a.batch}; HIP events, {a.warmup} warm-up calls per case, median of {a.reps} "
-        f"interleaved reps of {a.iters} calls rotating over a set of at least {a.set_gb} GB; {torch.cuda.get_device_name(0)}")
-    res = {"kernel": _kernels(dev, a, say), "stream": _stream(dev, a, say)}
-    say(json.dumps(res))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    dev = H.need_gpu("resize_timing")
+    report = H.Report(a.out)
+    say = report.say
+    say(f"# tools/resize_timing.py: B = {a.batch}; "
+        f"{H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, set_gb=a.set_gb, wall_reps=a.stream_reps)}; "
+        f"{torch.cuda.get_device_name(0)}")
+    report.finish({"kernel": _kernels(dev, a, say), "stream": _stream(dev, a, say)})
 
 
 if __name__ == "__main__":

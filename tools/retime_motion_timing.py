@@ -22,57 +22,15 @@ line last.
     python tools/retime_motion_timing.py [--set-gb 1 --frames 257 --chunk 32 --reps 5 --out profiles/retime_motion_timing.txt]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
 import tempfile
-import time
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+from ai_based_frame_interpolation_amd import _native, optical_flow as OF
 
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native, imageio_lite as IO, optical_flow as OF  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-
-LINES = []
 B = 8
-
-
-def say(text):
-    print(text, flush=True)
-    LINES.append(text)
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-def _capture(fn, iters):
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(iters):
-            fn()
-    return g
-
-
-class _Rotate:
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
 
 
 def _kernel_cases(dev, h, w, set_bytes):
@@ -96,7 +54,7 @@ def _kernel_cases(dev, h, w, set_bytes):
         else:
             def fn(k):
                 _native.warp_table(grids[k], B + 1, plane, flows[k], None, entries, outs[k], plane, bits)
-        cases[name] = _Rotate(fn, n_set)
+        cases[name] = H.Rotate(fn, n_set)
     add("warp", 8, 1, True)
     add("table", 8, 1, False)
     add("warp_again", 8, 1, True)
@@ -106,13 +64,6 @@ def _kernel_cases(dev, h, w, set_bytes):
     add("table10", 10, 1, False)
     add("warp10_again", 10, 1, True)
     return cases, flows, dict(members=n_set, set_mb=round(n_set * member / 2**20))
-
-
-def _write_clip(path, n, h, w):
-    pics = np.random.default_rng(0).integers(0, 256, (8, P.i420_frame_bytes(h, w))).astype(np.uint8)
-    with IO.Y4MWriter(path, w, h, (24, 1), "420jpeg", bits=8) as wr:
-        for i in range(n):
-            wr.write(pics[i % 8:i % 8 + 1])
 
 
 def main():
@@ -129,83 +80,56 @@ def main():
     ap.add_argument("--dir", default=None, help="directory of the clip files (default: the system temp dir)")
     ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "retime_motion_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
+    dev = H.need_gpu("retime_motion_timing")
+    report = H.Report(a.out)
+    say = report.say
     h, w = a.height, a.width
     res = {"shape": [h, w], "planes_per_call": B, "kernel": {}, "streamed": {},
-           "protocol": f"kernel: HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of "
-                       f"{a.replays} replays of a graph of {a.iters} calls rotating over a set of at least {a.set_gb} GB; "
-                       f"streamed: host wall clock, one warm-up run per case, interleaved runs"}
+           "protocol": "kernel: " + H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, replays=a.replays,
+                                               set_gb=a.set_gb, wall_reps=max(1, a.reps // 2))}
     say(f"retime_motion_timing: {torch.cuda.get_device_name(dev)}; {res['protocol']}")
     cases, flows, info = _kernel_cases(dev, h, w, int(a.set_gb * 1e9))
-    for fn in cases.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    graphs = {k: _capture(fn, a.iters) for k, fn in cases.items()}
-    for g in graphs.values():
-        g.replay()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(a.reps):
-        for k in cases:
-            ms[k].append(_time(graphs[k].replay, a.replays) / a.iters)
+    ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters, graph=True, replays=a.replays)
     leg = dict(info)
     for k in cases:
-        med = statistics.median(ms[k])
-        leg[k] = dict(ms=round(med, 4), us_per_plane=round(1e3 * med / B, 2),
-                      spread_ms=[round(min(ms[k]), 4), round(max(ms[k]), 4)])
-        say(f"{k:14s} graph {med:8.4f} ms a call, {1e3 * med / B:8.2f} us a warped plane  "
-            f"(reps {min(ms[k]):.4f}-{max(ms[k]):.4f})")
+        med, lo, hi = H.summary(ms[k])
+        leg[k] = dict(ms=round(med, 4), us_per_plane=round(1e3 * med / B, 2), spread_ms=[round(lo, 4), round(hi, 4)])
+        say(f"{k:14s} graph {med:8.4f} ms a call, {1e3 * med / B:8.2f} us a warped plane  (reps {lo:.4f}-{hi:.4f})")
     for new, old in (("table", "warp"), ("table10", "warp10")):
         a_, b_ = leg[old]["ms"], leg[old + "_again"]["ms"]
-        spread, ratio = abs(a_ - b_) / min(a_, b_), leg[new]["ms"] / max(a_, b_)
+        spread, ratio = H.pair_spread(a_, b_), leg[new]["ms"] / max(a_, b_)
         leg[f"{new}_vs_{old}"] = dict(ratio_to_slower_yardstick=round(ratio, 3), yardstick_spread=round(spread, 3),
                                       within_spread=bool(leg[new]["ms"] <= max(a_, b_)))
         say(f"{new} / {old}: {ratio:.3f} of the slower of the yardstick's two timings (they differ by {100 * spread:.1f} %)")
-    del graphs
     lead = torch.randint(0, 256, (B + 1, h, w), dtype=torch.uint8, device=dev)
-    flow_fn = lambda: OF.farneback_flow(lead[:B], lead[1:], "hip")  # noqa: E731
-    for _ in range(a.warmup):
-        flow_fn()
-    fl = [_time(flow_fn, 3) for _ in range(a.reps)]
-    leg["flow"] = dict(ms=round(statistics.median(fl), 3), ms_per_pair=round(statistics.median(fl) / B, 3),
-                       spread_ms=[round(min(fl), 3), round(max(fl), 3)])
-    say(f"flow           eager {statistics.median(fl):8.3f} ms a call of {B} pairs, {statistics.median(fl) / B:.3f} ms a pair  "
-        f"(reps {min(fl):.3f}-{max(fl):.3f})")
+    fl = H.interleaved({"flow": lambda: OF.farneback_flow(lead[:B], lead[1:], "hip")}, warmup=a.warmup, reps=a.reps, iters=3)
+    med, lo, hi = H.summary(fl["flow"])
+    leg["flow"] = dict(ms=round(med, 3), ms_per_pair=round(med / B, 3), spread_ms=[round(lo, 3), round(hi, 3)])
+    say(f"flow           eager {med:8.3f} ms a call of {B} pairs, {med / B:.3f} ms a pair  (reps {lo:.3f}-{hi:.3f})")
     res["kernel"] = leg
     del cases, flows, lead
     torch.cuda.empty_cache()
 
     if a.frames:
-        m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="bf16")
-        m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
-        fi = P.FrameInterpolator(model=m.to(dev).eval(), device=dev, batch=8)
+        _, fi = H.seeded_model(3, "bf16", dev)
         tmp = tempfile.mkdtemp(dir=a.dir)
         src, out = os.path.join(tmp, "in.y4m"), os.path.join(tmp, "out.y4m")
-        _write_clip(src, a.frames, h, w)
+        H.write_y4m_clip(src, a.frames, h, w)
 
         def run(mode):
             return lambda: fi.interpolate_video(src, out, fps=60, time_depth=2, retime=mode, chunk_frames=a.chunk)
         runs = {"blend": run("blend"), "motion": run("motion"), "blend_again": run("blend"), "motion_again": run("motion")}
-        written = {k: fn() for k, fn in list(runs.items())[:2]}   # warm-up
-        wall = {k: [] for k in runs}
-        for _ in range(max(1, a.reps // 2)):
-            for k, fn in runs.items():
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-                fn()
-                torch.cuda.synchronize(dev)
-                wall[k].append(time.perf_counter() - t0)
+        written = {}
+        # (each mode is run twice a round, so half of `--reps` rounds give `--reps` runs of it)
+        wall = H.interleaved_wall(runs, reps=max(1, a.reps // 2), device=dev, results=written)
         for k in runs:
-            med = statistics.median(wall[k])
+            med, lo, hi = H.summary(wall[k])
             res["streamed"][k] = dict(input_frames_per_s=round(a.frames / med, 2), wall_s=round(med, 3),
-                                      spread_s=[round(min(wall[k]), 3), round(max(wall[k]), 3)])
-            say(f"streamed {k:13s} {a.frames / med:7.2f} input frames/s  wall {med:.3f} s  "
-                f"(runs {min(wall[k]):.3f}-{max(wall[k]):.3f})")
+                                      spread_s=[round(lo, 3), round(hi, 3)])
+            say(f"streamed {k:13s} {a.frames / med:7.2f} input frames/s  wall {med:.3f} s  (runs {lo:.3f}-{hi:.3f})")
         s = res["streamed"]
-        blend = statistics.median(wall["blend"] + wall["blend_again"])
-        motion = statistics.median(wall["motion"] + wall["motion_again"])
+        blend = H.summary(wall["blend"] + wall["blend_again"])[0]
+        motion = H.summary(wall["motion"] + wall["motion_again"])[0]
         s.update(frames=a.frames, frames_out=written["motion"], chunk_frames=a.chunk, network="rgb", precision="bf16",
                  motion_vs_blend=round(motion / blend, 3), flow_and_warp_share=round((motion - blend) / motion, 3))
         say(f"streamed: motion takes {motion / blend:.3f} of blend's wall time; flow and warp are "
@@ -214,11 +138,7 @@ def main():
             if os.path.exists(f):
                 os.remove(f)
         os.rmdir(tmp)
-    say(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(LINES) + "\n")
+    report.finish(res)
 
 
 if __name__ == "__main__":

@@ -13,28 +13,11 @@ JSON line last.
     python tools/scene_timing.py [--frames 33 --height 1080 --width 1920 --precision bf16]
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+import ai_based_frame_interpolation_amd as P
 
 
 def main():
@@ -47,14 +30,13 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--loop-iters", type=int, default=2)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "scene_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
+    dev = H.need_gpu("scene_timing")
+    report = H.Report(a.out)
     n, h, w = a.frames, a.height, a.width
     fb = P.i420_frame_bytes(h, w)
-    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision=a.precision)
-    m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
-    m = m.to(dev).eval()
+    m, _ = H.seeded_model(3, a.precision, dev)
     g = torch.Generator(device=dev).manual_seed(0)
     frames = torch.randint(0, 256, (n, fb), dtype=torch.uint8, device=dev, generator=g)
     out = P.interpolate_sequence_yuv420(m, frames, h, w)
@@ -62,20 +44,14 @@ def main():
     every = torch.ones(n - 1, dtype=torch.uint8, device=dev)
 
     cases = {
-        "detect": (lambda: P.scene.detect_cuts(frames, 10.0, 8), a.iters),
-        "hold_none": (lambda: P.scene.hold_cut_frames(out, none, 2), a.iters),
-        "hold_all": (lambda: P.scene.hold_cut_frames(out, every, 2), a.iters),
-        "loop": (lambda: P.interpolate_sequence_yuv420(m, frames, h, w), a.loop_iters),
+        "detect": lambda: P.scene.detect_cuts(frames, 10.0, 8),
+        "hold_none": lambda: P.scene.hold_cut_frames(out, none, 2),
+        "hold_all": lambda: P.scene.hold_cut_frames(out, every, 2),
+        "loop": lambda: P.interpolate_sequence_yuv420(m, frames, h, w),
     }
-    for fn, _ in cases.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(a.reps):   # interleaved repetitions: drift on a shared host hits every case alike
-        for k, (fn, iters) in cases.items():
-            ms[k].append(_time(fn, iters))
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    iters = {k: a.loop_iters if k == "loop" else a.iters for k in cases}
+    ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=iters)
+    med = {k: H.summary(v)[0] for k, v in ms.items()}
     pairs = n - 1
     res = {"shape": [n, h, w], "precision": a.precision, "ms": med,
            "spread_ms": {k: [min(v), max(v)] for k, v in ms.items()},
@@ -84,15 +60,14 @@ def main():
            "held_frame_us": 1e3 * (med["hold_all"] - med["hold_none"]) / pairs,
            "share_detect_plus_empty_hold": (med["detect"] + med["hold_none"]) / med["loop"],
            "share_every_interval_held": (med["detect"] + med["hold_all"]) / med["loop"],
-           "protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of "
-                       f"{a.iters} (scene kernels) / {a.loop_iters} (loop) calls"}
+           "protocol": H.protocol(warmup=a.warmup, reps=a.reps, iters=f"{a.iters} (scene kernels) / {a.loop_iters} (loop)")}
     for k in cases:
-        print(f"{k:10s} {med[k]:9.3f} ms  (reps {min(ms[k]):.3f}-{max(ms[k]):.3f})")
-    print(f"detect reads {res['detect_gb_per_s']:.0f} GB/s of input; loop {res['loop_pairs_per_s']:.0f} pairs/s; "
-          f"one held frame {res['held_frame_us']:.1f} us")
-    print(f"share of the loop: detect + empty hold {100 * res['share_detect_plus_empty_hold']:.3f} %, "
-          f"every interval held {100 * res['share_every_interval_held']:.3f} %")
-    print(json.dumps(res))
+        report.say(f"{k:10s} {med[k]:9.3f} ms  (reps {min(ms[k]):.3f}-{max(ms[k]):.3f})")
+    report.say(f"detect reads {res['detect_gb_per_s']:.0f} GB/s of input; loop {res['loop_pairs_per_s']:.0f} pairs/s; "
+               f"one held frame {res['held_frame_us']:.1f} us")
+    report.say(f"share of the loop: detect + empty hold {100 * res['share_detect_plus_empty_hold']:.3f} %, "
+               f"every interval held {100 * res['share_every_interval_held']:.3f} %")
+    report.finish(res)
 
 
 if __name__ == "__main__":

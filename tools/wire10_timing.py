@@ -16,44 +16,15 @@ Every line goes to standard output and to `--out`; one JSON line last.
     python tools/wire10_timing.py [--batch 8 --set-gb 1 --iters 200 --reps 7 --out profiles/wire10_timing.txt]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import ai_based_frame_interpolation_amd as P  # noqa: E402
-from ai_based_frame_interpolation_amd import _native, wire10  # noqa: E402
-from ai_based_frame_interpolation_amd.colour import YUV_FORMATS, resolve_yuv_layout, yuv_flags  # noqa: E402
-from oracle import unet_oracle as O  # noqa: E402
+import timing_harness as H  # first: it puts the repository on sys.path for the imports below
+from ai_based_frame_interpolation_amd import _native, wire10
+from ai_based_frame_interpolation_amd.colour import YUV_FORMATS, resolve_yuv_layout, yuv_flags
 
 FMT = wire10.WORKING_FORMAT
-
-
-def _time(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-class _Rotate:
-    """Calls fn(k) with k = 0, 1, ..., n - 1, 0, ... : each call works on the next member of a set."""
-
-    def __init__(self, fn, n):
-        self.fn, self.n, self.k = fn, n, 0
-
-    def __call__(self):
-        self.fn(self.k)
-        self.k = (self.k + 1) % self.n
 
 
 def _words(dev, g, shape, top=1024):
@@ -73,14 +44,14 @@ def _kernel_cases(dev, b, h, w, set_bytes):
 
     def yard(decode):
         if decode:
-            return _Rotate(lambda k: _native.yuv_to_rgb(work[k].view(torch.uint16), code, lay, rgb[k], h, w, flags, 10), n_set)
-        return _Rotate(lambda k: _native.rgb_to_yuv(rgb[k], work[k].view(torch.uint16), code, lay, flags, 10), n_set)
+            return H.Rotate(lambda k: _native.yuv_to_rgb(work[k].view(torch.uint16), code, lay, rgb[k], h, w, flags, 10), n_set)
+        return H.Rotate(lambda k: _native.rgb_to_yuv(rgb[k], work[k].view(torch.uint16), code, lay, flags, 10), n_set)
 
     def new(unpack, p):
         m = wire10.frame_bytes(p, h, w) // 2
         if unpack:
-            return _Rotate(lambda k: wire10.unpack(wire[k][:, :m], h, w, p, out=work[k]), n_set)
-        return _Rotate(lambda k: wire10.pack(work[k], h, w, p, out=wire[k][:, :m]), n_set)
+            return H.Rotate(lambda k: wire10.unpack(wire[k][:, :m], h, w, p, out=work[k]), n_set)
+        return H.Rotate(lambda k: wire10.pack(work[k], h, w, p, out=wire[k][:, :m]), n_set)
     cases, moved = {}, {}
     for name, first in (("unpack", True), ("pack", False)):
         cases[f"{name} yard_a"] = yard(first)
@@ -90,40 +61,6 @@ def _kernel_cases(dev, b, h, w, set_bytes):
         cases[f"{name} yard_b"] = yard(first)
         moved[f"{name} yard_a"] = moved[f"{name} yard_b"] = 2 * b * (n + 3 * h * w)
     return cases, moved, dict(batch=b, set_members=n_set, set_mb=round(2 * n_set * b * (widest + n) / 2**20))
-
-
-def _run_cases(cases, warmup, reps, iters):
-    for fn in cases.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in cases}
-    for _ in range(reps):   # interleaved repetitions: drift on a shared host hits every case alike
-        for k, fn in cases.items():
-            ms[k].append(_time(fn, iters))
-    return ms
-
-
-class _Clip:
-    """A readable binary source of `frames` frames that repeats a few frames held in memory."""
-
-    def __init__(self, members: bytes, frame: int, frames: int):
-        self.data, self.left, self.pos = memoryview(members), frame * frames, 0
-
-    def readinto(self, b):
-        n = min(len(b), self.left, len(self.data) - self.pos)
-        b[:n] = self.data[self.pos:self.pos + n]
-        self.pos = (self.pos + n) % len(self.data)
-        self.left -= n
-        return n
-
-
-class _Null:
-    def write(self, b):
-        return len(b)
-
-    def flush(self):
-        pass
 
 
 def main():
@@ -136,34 +73,27 @@ def main():
     ap.add_argument("--shapes", default="1080x1920,2160x3840")
     ap.add_argument("--stream-frames", type=int, default=257)
     ap.add_argument("--stream-reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wire10_timing.txt"))
+    ap.add_argument("--out", default=os.path.join(H.ROOT, "profiles", "wire10_timing.txt"))
     a = ap.parse_args()
-    assert torch.cuda.is_available(), "wire10_timing measures on the GPU; there is no CPU path"
-    dev = torch.device("cuda:0")
-    log = open(a.out, "w")
-
-    def say(line):
-        print(line, flush=True)
-        log.write(line + "\n")
-        log.flush()
+    dev = H.need_gpu("wire10_timing")
+    report = H.Report(a.out)
+    say = report.say
     res = {"kernels": {}, "stream": {},
-           "protocol": f"HIP events, {a.warmup} warm-up calls per case, median of {a.reps} interleaved reps of {a.iters} "
-                       f"calls rotating over a set of at least {a.set_gb} GB"}
+           "protocol": H.protocol(warmup=a.warmup, reps=a.reps, iters=a.iters, set_gb=a.set_gb, wall_reps=a.stream_reps)}
     say(res["protocol"])
     for shape in a.shapes.split(","):
         h, w = (int(v) for v in shape.split("x"))
         cases, moved, info = _kernel_cases(dev, a.batch, h, w, int(a.set_gb * 1e9))
-        ms = _run_cases(cases, a.warmup, a.reps, a.iters)
+        ms = H.interleaved(cases, warmup=a.warmup, reps=a.reps, iters=a.iters)
         leg = dict(info)
         for k in cases:
-            med = statistics.median(ms[k])
-            leg[k] = dict(ms=round(med, 4), spread_ms=[round(min(ms[k]), 4), round(max(ms[k]), 4)],
+            med, lo, hi = H.summary(ms[k])
+            leg[k] = dict(ms=round(med, 4), spread_ms=[round(lo, 4), round(hi, 4)],
                           gb_per_s=round(moved[k] / (med * 1e-3) / 1e9, 1))
-            say(f"{h}x{w} B={a.batch} {k:16s} {med:8.4f} ms  (reps {min(ms[k]):.4f}-{max(ms[k]):.4f})  "
-                f"{leg[k]['gb_per_s']:7.1f} GB/s")
+            say(f"{h}x{w} B={a.batch} {k:16s} {med:8.4f} ms  (reps {lo:.4f}-{hi:.4f})  {leg[k]['gb_per_s']:7.1f} GB/s")
         for name in ("unpack", "pack"):
             ya, yb = leg[f"{name} yard_a"]["gb_per_s"], leg[f"{name} yard_b"]["gb_per_s"]
-            spread = abs(ya - yb) / max(ya, yb)
+            spread = H.pair_spread(ya, yb)
             leg[f"{name} yard_spread"] = round(spread, 4)
             bar = min(ya, yb) * (1 - spread)
             for p in wire10.PACKINGS:
@@ -177,30 +107,23 @@ def main():
         torch.cuda.empty_cache()
 
     h, w, frames = 1080, 1920, a.stream_frames
-    m = P.FrameInterpolationUNet(bilinear=True, frame_channels=3, precision="fp16")
-    m.load_state_dict(O.make_seeded_state_dict(77, n_channels=6, n_classes=3))
-    fi = P.FrameInterpolator(model=m.to(dev).eval(), device="cuda", batch=a.batch)
+    _, fi = H.seeded_model(3, "fp16", dev, a.batch)
     g = torch.Generator(device=dev).manual_seed(2)
     members = _words(dev, g, (4, wire10.planar_samples(h, w)))
     sources = {FMT: (members.cpu().numpy().tobytes(), 2 * wire10.planar_samples(h, w), {}),
                "v210": (wire10.pack(members, h, w, "v210").cpu().numpy().tobytes(), wire10.frame_bytes("v210", h, w),
                         dict(packing="v210"))}
-    secs = {k: [] for k in sources}
-    for rep in range(a.stream_reps + 1):   # (the first round warms every shape up and is not kept)
-        for k, (data, frame, kw) in sources.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            n = fi.interpolate_video(_Clip(data, frame, frames), _Null(), raw=FMT, width=w, height=h, src_fps=24,
-                                     chunk_frames=32, **kw)
-            torch.cuda.synchronize()
-            if rep:
-                secs[k].append(time.perf_counter() - t0)
-            assert n == 2 * frames - 1
+    runs = {k: (lambda data=data, frame=frame, kw=kw: fi.interpolate_video(
+        H.MemoryClip(data, frame, frames), H.NullSink(), raw=FMT, width=w, height=h, src_fps=24, chunk_frames=32, **kw))
+        for k, (data, frame, kw) in sources.items()}
+    written = {}
+    secs = H.interleaved_wall(runs, reps=a.stream_reps, device=dev, results=written)
+    assert all(n == 2 * frames - 1 for n in written.values()), written
     for k, v in secs.items():
-        med = statistics.median(v)
-        res["stream"][k] = dict(s=round(med, 4), spread_s=[round(min(v), 4), round(max(v), 4)],
+        med, lo, hi = H.summary(v)
+        res["stream"][k] = dict(s=round(med, 4), spread_s=[round(lo, 4), round(hi, 4)],
                                 source_frames_per_s=round(frames / med, 1))
-        say(f"stream {frames} x {h}x{w} fp16 factor 2 {k:12s} {med:7.4f} s  (runs {min(v):.4f}-{max(v):.4f})  "
+        say(f"stream {frames} x {h}x{w} fp16 factor 2 {k:12s} {med:7.4f} s  (runs {lo:.4f}-{hi:.4f})  "
             f"{frames / med:7.1f} source frames/s")
     base, new = res["stream"][FMT], res["stream"]["v210"]
     spread = max(base["spread_s"][1] - base["spread_s"][0], new["spread_s"][1] - new["spread_s"][0])
@@ -208,8 +131,7 @@ def main():
     res["stream"]["aim"] = "met" if new["s"] - base["s"] <= spread else "missed"
     say(f"stream: v210 / {FMT} time {res['stream']['v210_vs_working']:.4f}; run-to-run spread {spread:.4f} s: the aim "
         f"(within that spread) is {res['stream']['aim']}")
-    say(json.dumps(res))
-    log.close()
+    report.finish(res)
 
 
 if __name__ == "__main__":
