@@ -60,6 +60,8 @@ SYMBOLS = (
     "fiunet_unpack_422p10", "fiunet_pack_422p10",
     # motion-compensated resampling
     "fiunet_warp_table_u8", "fiunet_warp_table_p10",
+    # motion-guided chroma
+    "fiunet_chroma_pick_u8", "fiunet_chroma_pick_p10", "fiunet_chroma_fill_u8", "fiunet_chroma_fill_p10",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -227,6 +229,10 @@ def lib() -> ctypes.CDLL:
     L.fiunet_resize_planes_p10.argtypes = [vp, vp, vp, vp, ci, ci, vp]
     L.fiunet_warp_table_u8.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp]
     L.fiunet_warp_table_p10.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp]
+    L.fiunet_chroma_pick_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp]
+    L.fiunet_chroma_pick_p10.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp]
+    L.fiunet_chroma_fill_u8.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, vp, vp, vp]
+    L.fiunet_chroma_fill_p10.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, vp, vp, vp]
     L.fiunet_nv12_to_rgb_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_rgb_to_nv12_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_p010_to_rgb_p10.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
@@ -885,3 +891,57 @@ def warp_table(grid: "torch.Tensor", n_rows: int, grid_plane, flow: "torch.Tenso
              flow.shape[2], None if flags is None else flags.data_ptr(), 0 if flags is None else flags.numel(),
              warp_entries(entries), len(entries), out.data_ptr(), resize_plane_array([out_plane]), _stream(grid, stream)),
           "fiunet_warp_table_" + ("p10" if bits == 10 else "u8"))
+
+
+def _room(t: "torch.Tensor") -> int:
+    """Samples from the first element of `t` (a tensor or a view) to the end of its storage."""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def _chroma_planes(name, t, planes, n):
+    planes = [tuple(int(v) for v in p) for p in planes]
+    for p in planes:
+        if min(p) >= 0 and p[1] >= 1 and p[2] >= 1 and _resize_extent([p], n) > _room(t):
+            raise ValueError(f"the {name} plane reaches sample {_resize_extent([p], n)} of a buffer of {_room(t)}")
+    return planes
+
+
+def chroma_pick(a: "torch.Tensor", a_plane, b: "torch.Tensor", b_plane, m: "torch.Tensor", m_plane, flow: "torch.Tensor",
+                pick: "torch.Tensor", bits: int, stream=None) -> None:
+    """fiunet_chroma_pick_u8 / fiunet_chroma_pick_p10: the pick map [n, ceil(h / 8), ceil(w / 8)] (contiguous uint8) of n
+    frames from the luma of A, B and M and `flow` (contiguous float32 [n, h, w, 2]).  A plane is (offset, h, w, pitch,
+    step, frame_stride) in samples from the first element of its tensor, which may be a view: a, b and m may be three
+    views of one buffer.  ValueError, before the call, where well-formed planes reach past a tensor's storage."""
+    if flow.dtype != torch.float32 or flow.dim() != 4 or flow.shape[3] != 2 or not flow.is_contiguous():
+        raise ValueError(f"flow: expected a contiguous float32 [n, h, w, 2] tensor, got {flow.dtype} {tuple(flow.shape)}")
+    n = flow.shape[0]
+    (ap,), (bp,), (mp,) = (_chroma_planes(k, t, [p], n) for k, t, p in (("a", a, a_plane), ("b", b, b_plane), ("m", m, m_plane)))
+    if tuple(flow.shape[1:3]) != (ap[1], ap[2]):
+        raise ValueError(f"flow: expected [n, {ap[1]}, {ap[2]}, 2], the luma size, got {tuple(flow.shape)}")
+    want = (n, -(-ap[1] // 8), -(-ap[2] // 8))
+    if pick.dtype != torch.uint8 or tuple(pick.shape) != want or not pick.is_contiguous():
+        raise ValueError(f"pick: expected a contiguous uint8 {want} tensor, got {pick.dtype} {tuple(pick.shape)}")
+    fn = lib().fiunet_chroma_pick_p10 if bits == 10 else lib().fiunet_chroma_pick_u8
+    check(fn(a.data_ptr(), resize_plane_array([ap]), b.data_ptr(), resize_plane_array([bp]), m.data_ptr(),
+             resize_plane_array([mp]), flow.data_ptr(), n, pick.data_ptr(), _stream(a, stream)),
+          "fiunet_chroma_pick_" + ("p10" if bits == 10 else "u8"))
+
+
+def chroma_fill(a: "torch.Tensor", a_planes, b: "torch.Tensor", b_planes, flow: "torch.Tensor", pick: "torch.Tensor",
+                sub, out: "torch.Tensor", out_planes, bits: int, stream=None) -> None:
+    """fiunet_chroma_fill_u8 / fiunet_chroma_fill_p10: both chroma planes of n frames, sub-sampled by sub = (sy, sx)
+    against the luma that `flow` (contiguous float32 [n, h, w, 2]) and `pick` (contiguous uint8 [n, ceil(h / 8),
+    ceil(w / 8)]) belong to.  a_planes, b_planes, out_planes: two planes each, as for `chroma_pick`."""
+    if flow.dtype != torch.float32 or flow.dim() != 4 or flow.shape[3] != 2 or not flow.is_contiguous():
+        raise ValueError(f"flow: expected a contiguous float32 [n, h, w, 2] tensor, got {flow.dtype} {tuple(flow.shape)}")
+    n, fh, fw = flow.shape[:3]
+    want = (n, -(-fh // 8), -(-fw // 8))
+    if pick.dtype != torch.uint8 or tuple(pick.shape) != want or not pick.is_contiguous():
+        raise ValueError(f"pick: expected a contiguous uint8 {want} tensor, got {pick.dtype} {tuple(pick.shape)}")
+    ap, bp, op = (_chroma_planes(k, t, p, n) for k, t, p in (("a", a, a_planes), ("b", b, b_planes), ("out", out, out_planes)))
+    if not len(ap) == len(bp) == len(op) == 2:
+        raise ValueError("a_planes, b_planes and out_planes are two planes each (U, V)")
+    fn = lib().fiunet_chroma_fill_p10 if bits == 10 else lib().fiunet_chroma_fill_u8
+    check(fn(a.data_ptr(), resize_plane_array(ap), b.data_ptr(), resize_plane_array(bp), flow.data_ptr(), fh, fw,
+             pick.data_ptr(), int(sub[0]), int(sub[1]), n, out.data_ptr(), resize_plane_array(op), _stream(a, stream)),
+          "fiunet_chroma_fill_" + ("p10" if bits == 10 else "u8"))

@@ -15,6 +15,9 @@ With `--dedup 0` (a tolerance in code values; `--max-gap 4`) runs of repeated fr
 a stalled capture - are re-timed instead of interpolated across (retime.py); one line on standard error
 says how many repeated frames were re-timed.
 
+With `--chroma motion` a grayscale checkpoint carries the chroma of colour Y4M video along the motion instead of averaging
+it (chroma.py); one line on standard error says in how many blocks the chroma was warped.
+
 With `--raw nv12 --size 1920x1080 --src-fps 24` input and output are headerless tight NV12 frames, the layout hardware
 decoders and encoders use, converted on the device without a repack:
 
@@ -141,6 +144,7 @@ def _methods(v: str):
 
 
 PACKING_CHOICES = ("v210", "y210le", "p210le")   # wire10.PACKINGS
+CHROMA_CHOICES = ("average", "motion")           # chroma.MODES
 RAW_CHOICES = ("nv12", "rgb24", "bgr24", "rgba", "bgra", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le", "uyvy422",
                "yuyv422")
 
@@ -189,6 +193,10 @@ def parser() -> argparse.ArgumentParser:
     v.add_argument("--resize-filter", default=None, choices=("linear", "area"),
                    help="Filter of --resize: linear (default; cv2.resize's two taps per axis) or area (alias-free "
                         "down-scaling: the mean of the covered source area)")
+    v.add_argument("--chroma", default="average", choices=CHROMA_CHOICES,
+                   help="Chroma of the frames the grayscale network inserts into colour Y4M video: average (of the two "
+                        "neighbours) or motion (warped along the optical flow where the network's luma agrees with it: "
+                        "no colour ghosts around what moves, at the cost of one flow per inserted frame)")
     e = sub.add_parser("evaluate", help="Score a checkpoint on a clip by hold-out (Y4M, .npy or --raw; '-' is stdin)")
     e.add_argument("--input", required=True,
                    help="Clip to score: a .y4m or .npy path, or - for standard input (Y4M, or --raw video)")
@@ -222,6 +230,9 @@ def parser() -> argparse.ArgumentParser:
     e.add_argument("--scene-cut", type=_scene_cut, default=None,
                    help="Scene-cut threshold in (0, 100], or none: held-out frames next to a cut are left out of the "
                         "summary")
+    e.add_argument("--chroma", default="average", choices=CHROMA_CHOICES,
+                   help="Chroma of the unet method's frames on colour Y4M video through the grayscale network: average "
+                        "or motion (see video --chroma); the u and v rows of the table show the difference")
     e.add_argument("--json", default=None, metavar="FILE", help="Write the whole result here (arrays as lists)")
     e.add_argument("--csv", default=None, metavar="FILE", help="Write one line per scored frame here")
     return ap
@@ -238,6 +249,9 @@ def parse_args(argv=None) -> argparse.Namespace:
         if a.resize_filter is not None and a.resize is None:
             ap.error("--resize-filter names the filter of --resize WIDTHxHEIGHT")
         a.resize_filter = a.resize_filter or "linear"
+        if a.chroma == "motion" and (a.raw is not None or a.input.lower().endswith(".npy")):
+            ap.error("--chroma motion carries the separate chroma planes of Y4M video through the grayscale network "
+                     "along the motion: --raw and .npy video have none")
     if a.command == "evaluate":
         if a.raw is not None and a.size is None:
             ap.error("--raw needs --size WIDTHxHEIGHT (raw video has no header)")
@@ -253,6 +267,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     return a
 
 
+def _refuse_rgb_chroma(chroma: str, frame_channels: int) -> None:
+    """ValueError for --chroma motion with an RGB checkpoint, before the model is loaded."""
+    if frame_channels == 3:
+        from . import chroma as _chroma
+        _chroma.refuse_motion(chroma, "the RGB network (its colour goes through the network itself)")
+
+
 def retimed_repeats(dedup_log, scene_log, max_gap: int) -> int:
     """The number of repeated source frames a run re-timed: the dead intervals inside spans, from the run's logs."""
     dead = [bool(v) for _, d in dedup_log for v in d]
@@ -266,12 +287,15 @@ def run_video(a: argparse.Namespace) -> int:
     stream.check_chunk_frames(a.chunk_frames)
     device = torch.device("cuda" if a.device in ("auto", None) else a.device)
     fc = frame_channels_of(torch.load(a.model, map_location="cpu"))
+    _refuse_rgb_chroma(a.chroma, fc)
     with contextlib.redirect_stdout(sys.stderr):   # standard output carries the video only
         model = load_model(a.model, device, a.precision, frame_channels=fc, weight_prep=a.weight_prep)
     fi = FrameInterpolator(model=model, device=device, batch=a.batch)
     src = sys.stdin.buffer if a.input == "-" else a.input
     dst = sys.stdout.buffer if a.output == "-" else a.output
     logs = {} if a.packing is None else dict(packing=a.packing)
+    if a.chroma != "average":   # (and its count, printed below)
+        logs.update(chroma=a.chroma, chroma_log=[])
     if a.dedup is not None:   # for the count below (the cut flags too: a run before a cut is not re-timed)
         logs.update(dedup_log=[], scene_log=[] if a.scene_cut is not None else None)
     n = fi.interpolate_video(src, dst, a.factor, matrix=a.matrix, siting=a.siting, scene_cut=a.scene_cut,
@@ -281,6 +305,9 @@ def run_video(a: argparse.Namespace) -> int:
                              resize=a.resize, resize_filter=a.resize_filter, **logs)
     if a.dedup is not None:
         print(f"re-timed {retimed_repeats(logs['dedup_log'], logs['scene_log'], a.max_gap)} repeated frames",
+              file=sys.stderr)
+    for warped, blocks in logs.get("chroma_log") or []:
+        print(f"chroma warped along the motion in {warped} of {blocks} blocks ({warped / max(blocks, 1):.1%})",
               file=sys.stderr)
     print(f"wrote {n} frames", file=sys.stderr)
     return n
@@ -294,6 +321,7 @@ def run_evaluate(a: argparse.Namespace) -> dict:
     stream.check_chunk_frames(a.chunk_frames)
     device = torch.device("cuda" if a.device in ("auto", None) else a.device)
     fc = frame_channels_of(torch.load(a.model, map_location="cpu"))
+    _refuse_rgb_chroma(a.chroma, fc)
     with contextlib.redirect_stdout(sys.stderr):
         model = load_model(a.model, device, a.precision, frame_channels=fc, weight_prep=a.weight_prep)
     src = sys.stdin.buffer if a.input == "-" else a.input
@@ -301,7 +329,8 @@ def run_evaluate(a: argparse.Namespace) -> dict:
                               chunk_frames=a.chunk_frames, matrix=a.matrix, siting=a.siting, src_fps=a.src_fps,
                               raw=a.raw, width=a.size[0] if a.size else None, height=a.size[1] if a.size else None,
                               scene_cut=a.scene_cut, resize=a.resize, resize_filter=a.resize_filter,
-                              **({} if a.packing is None else dict(packing=a.packing)))
+                              **({} if a.packing is None else dict(packing=a.packing)),
+                              **({} if a.chroma == "average" else dict(chroma=a.chroma)))
     print(holdout.summary_table(res), file=sys.stderr)
     if a.json:
         with open(a.json, "w") as f:

@@ -1,6 +1,8 @@
-// flow.hip -- Farneback flow and flow-compensated warps (flow.hip.h), with the flow's debug entry points.
+// flow.hip -- Farneback flow and flow-compensated warps (flow.hip.h), with the flow's debug entry points,
+// and the motion-guided chroma that is built on the warp (chroma.hip.h).
 #include "fiunet_internal.h"
 #include "flow.hip.h"
+#include "chroma.hip.h"
 
 #include <cmath>
 
@@ -358,6 +360,148 @@ int fiunet_warp_table_p10(const uint16_t* grid, int n_rows, const fiunet_resize_
 {
     return flow_warp_table(grid, n_rows, grid_plane, flow, n_flows, flow_h, flow_w, flags, n_flags, entries, n_out, out,
                            out_plane, stream);
+}
+
+// ---- motion-guided chroma (chroma.hip.h) -----------------------------------------------------------------
+// As above: everything a thread indexes is checked here, before the first launch and before a pointer is used.
+extern "C++" {
+namespace {
+// [p0, p1) in bytes of n frames of a checked plane in a buffer of T; false where it leaves the address space
+template <typename T>
+bool chroma_extent(const T* base, const fiunet_resize_plane& p, int n, uintptr_t& p0, uintptr_t& p1)
+{
+    const size_t body = (size_t)(p.h - 1) * p.pitch + (size_t)(p.w - 1) * p.step + 1;
+    const size_t room = SIZE_MAX / sizeof(T);   // (offset + body <= frame_stride: warp_check_plane)
+    if (p.offset + body > room || p.frame_stride > (room - body - p.offset) / (size_t)n) return false;
+    p0 = (uintptr_t)base + p.offset * sizeof(T);
+    p1 = p0 + ((size_t)(n - 1) * p.frame_stride + body) * sizeof(T);
+    return p1 >= p0;
+}
+
+inline FlowWarpPlane chroma_plane(const fiunet_resize_plane& p) { return FlowWarpPlane{p.offset, p.pitch, p.frame_stride, p.step}; }
+
+template <typename T>
+int chroma_pick(const T* a, const fiunet_resize_plane* ap, const T* b, const fiunet_resize_plane* bp, const T* m,
+                const fiunet_resize_plane* mp, const float* flow, int n, uint8_t* pick, void* stream)
+{
+    if (!a || !b || !m || !ap || !bp || !mp || !flow || !pick) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)m) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
+    if (n < 0 || (size_t)n > kFlowMaxBatch) return fail(FIUNET_ERR_INVALID_ARG, "n must be 0..4096");
+    for (const fiunet_resize_plane* p : {ap, bp, mp})
+        if (const char* why = warp_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
+    if (ap->h != bp->h || ap->w != bp->w || ap->h != mp->h || ap->w != mp->w)
+        return fail(FIUNET_ERR_INVALID_ARG, "the three luma planes differ in size");
+    if ((uintptr_t)flow & 7) return fail(FIUNET_ERR_INVALID_ARG, "flow not 8-B aligned");
+    if (n == 0) return FIUNET_OK;
+    const int h = ap->h, w = ap->w, ph = (h + CHROMA_BLOCK - 1) / CHROMA_BLOCK, pw = (w + CHROMA_BLOCK - 1) / CHROMA_BLOCK;
+    const uintptr_t k0 = (uintptr_t)pick, k1 = k0 + (size_t)n * ph * pw;
+    if (k1 < k0) return fail(FIUNET_ERR_INVALID_ARG, "the pick map leaves the address space");
+    const T* bases[3] = {a, b, m};
+    const fiunet_resize_plane* planes[3] = {ap, bp, mp};
+    for (int i = 0; i < 3; ++i) {
+        uintptr_t p0, p1;
+        if (!chroma_extent(bases[i], *planes[i], n, p0, p1)) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+        if (p0 < k1 && k0 < p1) return fail(FIUNET_ERR_INVALID_ARG, "the pick map overlaps a luma plane");
+    }
+    const dim3 grid((unsigned)((pw + CHROMA_TILE_X - 1) / CHROMA_TILE_X), (unsigned)((ph + CHROMA_TILE_Y - 1) / CHROMA_TILE_Y),
+                    (unsigned)n);
+    hipLaunchKernelGGL(chroma_pick_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, a, chroma_plane(*ap), b,
+                       chroma_plane(*bp), m, chroma_plane(*mp), flow, h, w, ph, pw, pick);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+template <typename T>
+int chroma_fill(const T* a, const fiunet_resize_plane* ap, const T* b, const fiunet_resize_plane* bp, const float* flow,
+                int flow_h, int flow_w, const uint8_t* pick, int sy, int sx, int n, T* out, const fiunet_resize_plane* op,
+                void* stream)
+{
+    if (!a || !b || !ap || !bp || !flow || !pick || !out || !op) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
+    if (n < 0 || (size_t)n > kFlowMaxBatch) return fail(FIUNET_ERR_INVALID_ARG, "n must be 0..4096");
+    if ((sy != 1 && sy != 2) || (sx != 1 && sx != 2)) return fail(FIUNET_ERR_INVALID_ARG, "sy and sx must be 1 or 2");
+    for (int i = 0; i < 2; ++i)
+        for (const fiunet_resize_plane* p : {ap + i, bp + i, op + i}) {
+            if (const char* why = warp_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
+            if (p->h != ap->h || p->w != ap->w) return fail(FIUNET_ERR_INVALID_ARG, "the chroma planes differ in size");
+        }
+    if (flow_h < 1 || flow_w < 1 || (size_t)flow_h > kFlowMaxSide || (size_t)flow_w > kFlowMaxSide)
+        return fail(FIUNET_ERR_INVALID_ARG, "bad flow shape");
+    if ((uintptr_t)flow & 7) return fail(FIUNET_ERR_INVALID_ARG, "flow not 8-B aligned");
+    const int h = ap->h, w = ap->w;
+    // the last chroma sample's luma position lies inside the flow's plane, so its block lies inside the pick map
+    if ((int64_t)(h - 1) * sy >= flow_h || (int64_t)(w - 1) * sx >= flow_w)
+        return fail(FIUNET_ERR_INVALID_ARG, "a chroma plane of this size and sub-sampling reaches past the luma plane");
+    if (n == 0) return FIUNET_OK;
+    const int ph = (flow_h + CHROMA_BLOCK - 1) / CHROMA_BLOCK, pw = (flow_w + CHROMA_BLOCK - 1) / CHROMA_BLOCK;
+    uintptr_t o0[2], o1[2];
+    for (int i = 0; i < 2; ++i)
+        if (!chroma_extent(out, op[i], n, o0[i], o1[i])) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+    // U and V of a frame usually share a frame stride and lie side by side inside it: then one frame's two planes must
+    // not overlap (each lies inside the stride, so frames do not meet); with two strides the whole ranges must not
+    {
+        uintptr_t u0 = o0[0], u1 = o1[0], v0 = o0[1], v1 = o1[1];
+        if (op[0].frame_stride == op[1].frame_stride) {
+            chroma_extent(out, op[0], 1, u0, u1);
+            chroma_extent(out, op[1], 1, v0, v1);
+        }
+        if (u0 < v1 && v0 < u1 && (op[0].step == 1 || op[1].step == 1))
+            return fail(FIUNET_ERR_INVALID_ARG, "out's two planes overlap");
+    }
+    for (int i = 0; i < 2; ++i) {
+        uintptr_t p0, p1;
+        if (!chroma_extent(a, ap[i], n, p0, p1)) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+        for (int j = 0; j < 2; ++j)
+            if (p0 < o1[j] && o0[j] < p1) return fail(FIUNET_ERR_INVALID_ARG, "out overlaps A");
+        if (!chroma_extent(b, bp[i], n, p0, p1)) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+        for (int j = 0; j < 2; ++j)
+            if (p0 < o1[j] && o0[j] < p1) return fail(FIUNET_ERR_INVALID_ARG, "out overlaps B");
+    }
+    ChromaPlanes P;
+    for (int i = 0; i < 2; ++i) {
+        P.a[i] = chroma_plane(ap[i]);
+        P.b[i] = chroma_plane(bp[i]);
+        P.o[i] = chroma_plane(op[i]);
+    }
+    const float mx = (float)((double)w / (double)flow_w), my = (float)((double)h / (double)flow_h);
+    constexpr int V = FlowWarpVec<T>::V;
+    const dim3 grid((unsigned)(((w + V - 1) / V + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)(2 * n));
+    hipLaunchKernelGGL(chroma_fill_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, a, b, P, flow, flow_h, flow_w, mx, my,
+                       pick, ph, pw, sy, sx, h, w, out);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int fiunet_chroma_pick_u8(const uint8_t* a, const fiunet_resize_plane* a_plane, const uint8_t* b,
+                          const fiunet_resize_plane* b_plane, const uint8_t* m, const fiunet_resize_plane* m_plane,
+                          const float* field, int n, uint8_t* pick, void* stream)
+{
+    return chroma_pick(a, a_plane, b, b_plane, m, m_plane, field, n, pick, stream);
+}
+
+int fiunet_chroma_pick_p10(const uint16_t* a, const fiunet_resize_plane* a_plane, const uint16_t* b,
+                           const fiunet_resize_plane* b_plane, const uint16_t* m, const fiunet_resize_plane* m_plane,
+                           const float* field, int n, uint8_t* pick, void* stream)
+{
+    return chroma_pick(a, a_plane, b, b_plane, m, m_plane, field, n, pick, stream);
+}
+
+int fiunet_chroma_fill_u8(const uint8_t* a, const fiunet_resize_plane* a_planes, const uint8_t* b,
+                          const fiunet_resize_plane* b_planes, const float* field, int field_h, int field_w,
+                          const uint8_t* pick, int sy, int sx, int n, uint8_t* out, const fiunet_resize_plane* out_planes,
+                          void* stream)
+{
+    return chroma_fill(a, a_planes, b, b_planes, field, field_h, field_w, pick, sy, sx, n, out, out_planes, stream);
+}
+
+int fiunet_chroma_fill_p10(const uint16_t* a, const fiunet_resize_plane* a_planes, const uint16_t* b,
+                           const fiunet_resize_plane* b_planes, const float* field, int field_h, int field_w,
+                           const uint8_t* pick, int sy, int sx, int n, uint16_t* out,
+                           const fiunet_resize_plane* out_planes, void* stream)
+{
+    return chroma_fill(a, a_planes, b, b_planes, field, field_h, field_w, pick, sy, sx, n, out, out_planes, stream);
 }
 
 // Diagnostic (tests; not part of the ABI): the pyramid of an H x W frame, pure host arithmetic.  dims[k] = {h, w,

@@ -30,6 +30,8 @@
 //   flow_warp_table_kernel       motion-compensated resampling: one plane of up to 64 output frames,
 //                                each warped along the flow between two neighbouring grid rows to its own time
 //                                wn / den; planes are read and written where they lie (offset, pitch, step)
+//   flow_fetch, flow_warp_pair   the warp's arithmetic at one sample, stated once: flow_warp_table_kernel and the chroma
+//                                kernels of chroma.hip.h go through them
 // Every one is a stencil or a gather: HBM- or LDS-bound, no MFMA, no atomics.  The build has -ffp-contract=off, so
 // every product and sum below rounds on its own, in the order written.
 #pragma once
@@ -425,6 +427,39 @@ __device__ __forceinline__ int flow_remap_stepped(const T* __restrict__ p, size_
     return (acc + (1 << 14)) >> 15;
 }
 
+// (dx, dy) of the flow at sample (x, y) of a plane `w` wide: the field's own value where the field has the plane's size
+// (`same`), else resampled and scaled as in flow_warp_kernel; (y0, y1, ty): flow_axis of the row, made once by the caller
+__device__ __forceinline__ void flow_fetch(const float* __restrict__ fl, int fh, int fw, bool same, int w, int x, int y,
+                                           int y0, int y1, float ty, float mulx, float muly, float& dx, float& dy)
+{
+    if (same) {
+        const float2 f = reinterpret_cast<const float2*>(fl)[(size_t)y * w + x];
+        dx = f.x;
+        dy = f.y;
+    } else {
+        int xa, xb;
+        float tx;
+        flow_axis(x, w, fw, xa, xb, tx);
+        dx = flow_resample(fl, fw, 2, y0, y1, ty, xa, xb, tx) * mulx;
+        dy = flow_resample(fl + 1, fw, 2, y0, y1, ty, xa, xb, tx) * muly;
+    }
+}
+
+// The warp's two samples at (x, y): a = remap(A, clamp(p - s0 d)), b = remap(B, clamp(p + s1 d)), every product rounded
+// to fp32, then every sum.  The one statement of this arithmetic: flow_warp_table_kernel and the chroma kernels
+// (chroma.hip.h) both go through it.
+template <typename T>
+__device__ __forceinline__ void flow_warp_pair(const T* __restrict__ pa, size_t pitch_a, int step_a,
+                                               const T* __restrict__ pb, size_t pitch_b, int step_b, int h, int w, int x,
+                                               int y, float dx, float dy, float s0, float s1, int& a, int& b)
+{
+    const float fx = (float)x, fy = (float)y, xm = (float)(w - 1), ym = (float)(h - 1);
+    a = flow_remap_stepped<T>(pa, pitch_a, step_a, h, w, flow_clampf(__fsub_rn(fx, __fmul_rn(s0, dx)), xm),
+                              flow_clampf(__fsub_rn(fy, __fmul_rn(s0, dy)), ym));
+    b = flow_remap_stepped<T>(pb, pitch_b, step_b, h, w, flow_clampf(__fadd_rn(fx, __fmul_rn(s1, dx)), xm),
+                              flow_clampf(__fadd_rn(fy, __fmul_rn(s1, dy)), ym));
+}
+
 // grid = (ceil(ceil(w / V) / 64), ceil(h / 4), entries of the launch), block (64, 4)
 template <typename T>
 __global__ __launch_bounds__(256) void flow_warp_table_kernel(const T* __restrict__ grid, FlowWarpPlane gp,
@@ -442,7 +477,7 @@ __global__ __launch_bounds__(256) void flow_warp_table_kernel(const T* __restric
     const T* pb = pa + gp.fs;
     T* po = out + op.off + (size_t)blockIdx.z * op.fs + (size_t)y * op.pitch + (size_t)x0 * op.step;
     const float* fl = flow + (size_t)e.flow * fh * fw * 2;
-    const float xm = (float)(w - 1), ym = (float)(h - 1), rq = 1.0f / (float)e.den;
+    const float rq = 1.0f / (float)e.den;
     const unsigned wa = e.den - e.wn, wb = e.wn, half = e.den >> 1;
     const bool same = fh == h && fw == w;
     int y0 = 0, y1 = 0;
@@ -460,24 +495,9 @@ __global__ __launch_bounds__(256) void flow_warp_table_kernel(const T* __restric
             continue;
         }
         float dx, dy;
-        if (same) {
-            const float2 f = reinterpret_cast<const float2*>(fl)[(size_t)y * w + x];
-            dx = f.x;
-            dy = f.y;
-        } else {
-            int xa, xb;
-            float tx;
-            flow_axis(x, w, fw, xa, xb, tx);
-            dx = flow_resample(fl, fw, 2, y0, y1, ty, xa, xb, tx) * mulx;
-            dy = flow_resample(fl + 1, fw, 2, y0, y1, ty, xa, xb, tx) * muly;
-        }
-        const float fx = (float)x, fy = (float)y;
-        const int a = flow_remap_stepped<T>(pa, gp.pitch, gp.step, h, w,
-                                            flow_clampf(__fsub_rn(fx, __fmul_rn(e.s0, dx)), xm),
-                                            flow_clampf(__fsub_rn(fy, __fmul_rn(e.s0, dy)), ym));
-        const int b = flow_remap_stepped<T>(pb, gp.pitch, gp.step, h, w,
-                                            flow_clampf(__fadd_rn(fx, __fmul_rn(e.s1, dx)), xm),
-                                            flow_clampf(__fadd_rn(fy, __fmul_rn(e.s1, dy)), ym));
+        flow_fetch(fl, fh, fw, same, w, x, y, y0, y1, ty, mulx, muly, dx, dy);
+        int a, b;
+        flow_warp_pair<T>(pa, gp.pitch, gp.step, pb, gp.pitch, gp.step, h, w, x, y, dx, dy, e.s0, e.s1, a, b);
         v[k] = retime_div((unsigned)a * wa + (unsigned)b * wb + half, e.den, rq);
     }
     if (op.step == 1 && nv == V && ((uintptr_t)po & (V * sizeof(T) - 1)) == 0) {

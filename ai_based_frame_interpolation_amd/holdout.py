@@ -57,6 +57,7 @@ import os
 import numpy as np
 import torch
 
+from . import chroma as _chroma
 from . import metrics, optical_flow, packed, scene
 from . import resize as _resize
 from . import retime as _retime
@@ -146,7 +147,7 @@ def raw_planes(raw: str, height: int, width: int):
 
 
 def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, height=None, size=None,
-          rfilter="linear", packing=None) -> _Source:
+          rfilter="linear", packing=None, chroma="average") -> _Source:
     """The source of a scoring run through the video routes' openers, with their refusals; a clip whose frame count is
     known up front has at least three frames."""
     npy = _is_path(src) and os.fspath(src).lower().endswith(".npy")
@@ -154,6 +155,7 @@ def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, heig
     if raw is not None:
         if npy:
             raise ValueError(f"raw={raw!r} describes headerless video; a .npy stack carries its own shape (leave raw None)")
+        _chroma.refuse_motion(chroma, f"raw {raw} video")
         opened = _open_raw(model, src, raw, width, height, False, batch, matrix, siting, size, rfilter, packing)
         if raw in packed.FORMATS:
             lead = ("r", "g", "b")
@@ -162,10 +164,11 @@ def _open(model, src, batch, matrix, siting, src_fps, raw=None, width=None, heig
         if width is not None or height is not None:
             raise ValueError("width and height describe raw video: pass raw= with them")
         if npy:
+            _chroma.refuse_motion(chroma, ".npy video")
             opened = _open_npy(model, src, batch, size, rfilter)
             channels = opened.shape[2] if len(opened.shape) == 3 else 0
         else:
-            opened = _open_y4m(model, src, False, batch, matrix, siting, size, rfilter, count=True)
+            opened = _open_y4m(model, src, False, batch, matrix, siting, size, rfilter, count=True, chroma=chroma)
             if fps is None:
                 try:
                     fps = _retime.parse_fps(tuple(int(v) for v in opened.fps))
@@ -320,7 +323,8 @@ def excluded_targets(cut_flags, scored_frames) -> np.ndarray:
 @torch.no_grad()
 def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch: int = 8, chunk_frames: int = 32,
                 matrix: str = "bt709", siting=None, src_fps=None, raw=None, width=None, height=None,
-                scene_cut=None, resize=None, resize_filter: str = "linear", packing=None) -> dict:
+                scene_cut=None, resize=None, resize_filter: str = "linear", packing=None,
+                chroma: str = "average") -> dict:
     """Hold-out scores of `model` on a clip (methods: any of ALL_METHODS; with "optical_flow" or "motion" the result
     also has "flow_backend").  src: a path (.y4m, or a uint8 .npy stack [N,H,W] / [N,H,W,C]) or a
     readable binary file object carrying Y4M (a pipe): what `interpolate_y4m_stream` / `interpolate_npy_stream` take
@@ -340,7 +344,10 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     more than 64 times); with a filter other than "linear" the result also has "resize_filter".  packing: None, or with
     raw="yuv422p10le" one of wire10.PACKINGS ("v210", "y210le", "p210le"): the source is tight frames of
     that packing, unpacked on the device where a chunk is uploaded (before `resize`); the planes are scored where they
-    lie in the working format, so the result equals that of the unpacked clip.  Every argument is
+    lie in the working format, so the result equals that of the unpacked clip.  chroma: "average" or "motion", the
+    chroma of the "unet" method's frames on colour Y4M video through the grayscale network (chroma.py; its
+    `u` and `v` planes show what carrying the chroma along the motion buys on this footage); "motion" is refused for an
+    RGB model, a .npy stack and raw video; the result names the mode as "chroma".  Every argument is
     checked before any GPU work.  Returns
 
       {"frames", "triplets", "bits", "peak", "planes", "methods", "fps", "scored_frames": int64 source frame indices,
@@ -362,11 +369,12 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
         raise ValueError(f"batch must be a positive int, got {batch!r}")
     thr = scene.check_threshold(scene_cut)
+    _chroma.check_mode(chroma)
     if src_fps is not None:
         src_fps = _retime.parse_fps(src_fps)
     size = None if resize is None else _resize.check_size(resize)
     rfilter = _resize.check_resize_filter(resize, resize_filter)
-    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter, packing)
+    source = _open(model, src, batch, matrix, siting, src_fps, raw, width, height, size, rfilter, packing, chroma)
     try:
         opened, step = source.opened, _step(triplets)
         route, rs = opened.route, opened.rs
@@ -426,7 +434,7 @@ def score_video(model, src, *, triplets: str = "sliding", methods=METHODS, batch
     out = {"frames": frames, "triplets": triplets, "bits": route.bits, "peak": peak, "planes": names,
            "methods": list(methods), "fps": None if source.fps is None else (source.fps.numerator,
                                                                              source.fps.denominator),
-           "scored_frames": scored, "per_frame": per,
+           "scored_frames": scored, "per_frame": per, "chroma": chroma,
            "summary": {m: {p: _kept_stats(per[m][p], keep, pixels[p], peak) for p in names} for m in methods}}
     if thr is not None:
         out.update({"scene_cut": thr, "scene_scores": scores.cpu().numpy(),

@@ -459,7 +459,7 @@ class FrameInterpolator:
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
                           chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend", raw=None,
                           width=None, height=None, dedup=None, max_gap=4, dedup_log=None, scene_log=None, resize=None,
-                          resize_filter="linear", packing=None):
+                          resize_filter="linear", packing=None, chroma="average", chroma_log=None):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -524,7 +524,19 @@ class FrameInterpolator:
         samples are yuv422p10le's, packed on the wire as 10-bit capture cards and uncompressed broadcast files carry
         them (`ffmpeg -c:v v210 -f rawvideo`).  Input and output are tight frames of that packing; each chunk is unpacked
         on the device after its upload and packed before its download, everything between is the yuv422p10le route, and
-        the output is that route's output packed, byte for byte.  An error with any other raw, with Y4M and with .npy."""
+        the output is that route's output packed, byte for byte.  An error with any other raw, with Y4M and with .npy.
+        chroma: how colour Y4M video through the GRAYSCALE network gets the chroma of an inserted frame (chroma.py,
+        DESIGN.md 3.3u).  "average": the rounded average of its neighbours' (what this call has always written).
+        "motion": carried along the motion - 8x8 luma block by block, the chroma planes are warped along the optical flow
+        between the two neighbours where the network's own luma for the frame agrees with that flow, and averaged
+        elsewhere, so a coloured object that moves keeps its colour in place instead of a double exposure.  The luma of
+        every frame and the source frames are unchanged; works with factor, fps, retime, scene_cut, dedup, resize and
+        chunk_frames, 8 and 10 bits, 4:2:0, 4:2:2 and 4:4:4; a mono stream has no chroma and is unchanged.  Costs one
+        Farneback flow per inserted frame.  "motion" is refused by name for an RGB model, .npy input and every raw=
+        route: none of them has separate chroma planes.  chroma_log: None, or a list that receives one (warped blocks,
+        blocks) pair after a "motion" run."""
+        from . import chroma as _chroma
+        _chroma.check_mode(chroma)
         thr = scene.check_threshold(scene_cut)
         if factor < 2 or factor & (factor - 1):
             raise ValueError("factor must be a power of two (the network has no time input)")
@@ -537,6 +549,7 @@ class FrameInterpolator:
             _resize.check_size(resize)
         _resize.check_resize_filter(resize, resize_filter)
         if raw is not None:
+            _chroma.refuse_motion(chroma, f"raw {raw} video")
             if packing is not None:   # (a new keyword beside raw: without it the call is what it always was)
                 run["packing"] = packing
             return stream.interpolate_raw_stream(self.model, input_path, output_path, factor, raw=raw, width=width,
@@ -552,11 +565,16 @@ class FrameInterpolator:
         if is_path and not os.path.exists(input_path):
             raise FileNotFoundError(f"Video file not found: {input_path}")
         if is_path and not str(input_path).lower().endswith(".y4m"):
+            _chroma.refuse_motion(chroma, ".npy video")
             return stream.interpolate_npy_stream(self.model, input_path, output_path, factor, **run)
         if chunk_frames is None and fps is None and isinstance(output_path, (str, os.PathLike)):
             # the whole-clip call's older naming rule: whatever is not `.y4m` is a `.npy` stack, named as np.save names it
             name = os.fspath(output_path)
             if not name.lower().endswith(".y4m") and not name.endswith(".npy"):
                 output_path = name + ".npy"
+        if chroma != "average":   # (a new keyword: without it the call is what it always was)
+            if self.model.frame_channels == 3:
+                _chroma.refuse_motion(chroma, "the RGB network (its colour goes through the network itself)")
+            run.update(chroma=chroma, chroma_log=chroma_log)
         return stream.interpolate_y4m_stream(self.model, input_path, output_path, factor, matrix=matrix, siting=siting,
                                              **run)

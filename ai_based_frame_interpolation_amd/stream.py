@@ -75,6 +75,10 @@ between them, after the blend pass and into the same output rows: the planes com
 destination size, the working format), flows are computed `batch` pairs at a time, and the device holds beside the grid
   device         2 x batch lead planes + batch flow fields (8 bytes a lead sample each) + the flow workspace of batch
                  pairs (21 fp32 planes a pair, `fiunet_flow_workspace_bytes`), kept per frame size
+
+With chroma="motion" (chroma.py; Y4M through the grayscale network) a level holds beside its luma result
+  device         the level's chroma stack (2 chroma planes a frame) + batch flow fields + batch pick maps (a byte per 8x8
+                 luma block) + the flow workspace of batch pairs
 """
 from __future__ import annotations
 
@@ -88,11 +92,13 @@ import threading
 import numpy as np
 import torch
 
+from . import chroma as _chroma
 from . import colour, imageio_lite, packed, scene, wire10
 from . import resize as _resize
 from . import retime as _retime
 from .layout import RAW_FORMATS, frame_layout
-from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, interpolate_sequence,
+from . import optical_flow as _flow
+from .inference import (_hold, _interleave_average_p10, _interleave_average_u8, _pair_batches, interpolate_sequence,
                         interpolate_sequence_nv12, interpolate_sequence_p10, interpolate_sequence_rgb_packed,
                         interpolate_sequence_yuv, interpolate_sequence_yuv420, interpolate_sequence_yuv420p10)
 
@@ -147,11 +153,17 @@ class _Route:
         self.ndtype = np.uint8 if bits == 8 else np.uint16
 
 
-def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
+def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting, chroma: str = "average") -> _Route:
     """The route of Y4M video for this stream header and model, with its refusals and messages: the RGB network on
     4:2:0 frames (8-bit: siting from the tag; `C420p10`: siting None is "mpeg2"; range from `XCOLORRANGE`), or the
-    grayscale network on the luma plane with the chroma of an inserted frame the rounded average of its neighbours'."""
+    grayscale network on the luma plane with the chroma of an inserted frame the rounded average of its neighbours'
+    (chroma "average") or carried along the motion where the network's luma confirms it (chroma "motion": chroma.py,
+    DESIGN.md 3.3u; the route's `chroma_stats` then counts the blocks that were warped)."""
     h, w, (hc, wc) = hdr["height"], hdr["width"], hdr["chroma"]
+    if model.frame_channels == 3:
+        _chroma.refuse_motion(chroma, "the RGB network (its colour goes through the network itself)")
+    else:
+        _chroma.check_mode(chroma)
     _, _, bits, row = frame_layout(("y4m", hdr["colourspace"]), h, w)
     ny, nc = h * w, hc * wc
     if model.frame_channels == 3:
@@ -212,7 +224,39 @@ def _y4m_route(model, hdr, npy_out: bool, batch: int, matrix, siting) -> _Route:
         if npy_out or cu is None:
             return y
         return torch.cat([y] + [c.to(y.dtype).reshape(n, nc) for c in (cu, cv)], dim=1)
-    return _Route(bits, row, out_row, run)
+    if chroma != "motion" or not nc or npy_out:   # (a mono stream has no chroma, a luma .npy output writes none)
+        return _Route(bits, row, out_row, run)
+    sub = _chroma.subsampling((h, w), (hc, wc))
+    stats = {"warped": None, "blocks": 0}
+
+    def run_motion(d, factor):
+        # luma: the frames of `run`.  Chroma: U and V of a frame side by side, [k, 2, hc, wc], as they are stored; at
+        # each level the flows of the stored pairs, `batch` at a time (a pair's flow does not depend on its batch),
+        # the pick from (y[k], y[k + 1], y'[2k + 1]) where the level's result holds them, and the fill of u and v
+        y = d[:, :ny].reshape(d.shape[0], h, w).contiguous()
+        c = d[:, ny:ny + 2 * nc].reshape(d.shape[0], 2, hc, wc).contiguous()
+        if bits == 10:
+            y = y.view(torch.uint16)
+        for _ in range(_levels(factor)):
+            k = y.shape[0]
+            y2 = interpolate_sequence_p10(model, y, batch) if bits == 10 else interpolate_sequence(model, y, batch)
+            c2 = torch.empty((2 * k - 1, 2, hc, wc), dtype=c.dtype, device=c.device)
+            c2[0::2] = c
+            for s, cnt in _pair_batches(k - 1, batch):
+                ya, yb, ym = (y2[2 * s + o:2 * (s + cnt) + o:2] for o in (0, 2, 1))
+                field = _flow.farneback_flow(ya, yb, "hip", bits=bits)
+                pk = _chroma.pick(ya, yb, ym, field, bits)
+                _chroma.fill(c[s:s + cnt], c[s + 1:s + cnt + 1], field, pk, c2[2 * s + 1:2 * (s + cnt):2], bits, sub=sub)
+                warped = pk.sum(dtype=torch.int64)
+                stats["warped"] = warped if stats["warped"] is None else stats["warped"] + warped
+                stats["blocks"] += pk.numel()
+            y, c = y2, c2
+        n = y.shape[0]
+        y = (y.view(torch.int16) if bits == 10 else y).reshape(n, ny)
+        return torch.cat([y, c.reshape(n, 2 * nc)], dim=1)
+    route = _Route(bits, row, out_row, run_motion)
+    route.chroma_stats = stats
+    return route
 
 
 def _raw_route(model, raw, height, width, npy_out: bool, batch: int, matrix, siting) -> _Route:
@@ -441,7 +485,8 @@ def _resized(kind, height, width, size, rfilter):
     return _resize.FrameResize(lay.planes, dst.planes, lay.bits, size, (int(width), int(height)), rfilter), dst
 
 
-def _open_y4m(model, src, npy_out: bool, batch, matrix, siting, size, rfilter, count: bool) -> _Opened:
+def _open_y4m(model, src, npy_out: bool, batch, matrix, siting, size, rfilter, count: bool,
+              chroma: str = "average") -> _Opened:
     """Y4M from a path or a readable binary file.  count: whether the frames of a regular file are counted (one pass
     over its FRAME lines)."""
     if npy_out and not _is_file(src):
@@ -453,7 +498,7 @@ def _open_y4m(model, src, npy_out: bool, batch, matrix, siting, size, rfilter, c
         rs, lay = _resized(("y4m", hdr["colourspace"]), hdr["height"], hdr["width"], size, rfilter)
         if size is not None:   # everything from here on is a clip of the new size; the reader keeps the source's
             hdr = _resize.y4m_header_at(hdr, size)
-        route = _y4m_route(model, hdr, npy_out, batch, matrix, siting)
+        route = _y4m_route(model, hdr, npy_out, batch, matrix, siting, chroma)
         n = imageio_lite.y4m_frame_count(src) if count and _is_file(src) else None
     except BaseException:
         reader.close()
@@ -921,7 +966,8 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
                            matrix: str = "bt709", siting: str | None = None, scene_cut: float | None = None,
                            scene_log: list | None = None, fps=None, src_fps=None, time_depth: int = 2,
                            retime: str = "blend", dedup=None, max_gap: int = 4, dedup_log: list | None = None,
-                           resize=None, resize_filter: str = "linear") -> int:
+                           resize=None, resize_filter: str = "linear", chroma: str = "average",
+                           chroma_log: list | None = None) -> int:
     """Y4M in (a path or a readable binary file: a pipe, `sys.stdin.buffer`) -> Y4M out (a path or a writable binary
     file), or a `.npy` path of the luma frames (grayscale network; the input must then be a regular file, whose frame
     count a first pass reads).  This is what `FrameInterpolator.interpolate_video` runs; the result is the same, byte
@@ -940,10 +986,17 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     DESIGN.md 3.3q; each plane on its own grid, the chroma size as the tag gives it at the new size), and the route, its
     refusals, scene cuts, dedup and the output header are those of a clip of that size.  resize_filter: "linear" (the
     filter of cv2.resize's INTER_LINEAR) or "area" (alias-free down-scaling, DESIGN.md 3.3r: refused where a plane would
-    grow on either axis, or shrink more than 64 times); anything but "linear" is an error without `resize`."""
+    grow on either axis, or shrink more than 64 times); anything but "linear" is an error without `resize`.
+    chroma: "average", or "motion" (grayscale network; chroma.py): the chroma of every inserted frame is
+    warped along the luma flow of its two neighbours, 8x8 luma block by block, where the network's luma for the frame
+    is closer to the warped luma than to the averaged one, and is the average elsewhere; the luma of every frame and
+    the source frames are those of "average", for every chunk_frames.  One Farneback flow per inserted frame.  Refused for
+    the RGB network; no effect on a mono stream or a luma .npy output.  chroma_log: a list that receives one (warped
+    blocks, blocks) pair of ints after a "motion" run that had chroma to make (one device-to-host read, at the end)."""
     npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
+    _chroma.check_mode(chroma)
     job = _job(lambda size, rfilter: _open_y4m(model, src, npy_out, batch, matrix, siting, size, rfilter,
-                                               count=chunk_frames is None or npy_out),
+                                               chunk_frames is None or npy_out, chroma),
                factor=factor, batch=batch, chunk_frames=chunk_frames, scene_cut=scene_cut, scene_log=scene_log, fps=fps,
                src_fps=src_fps, time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
                resize=resize, resize_filter=resize_filter)
@@ -954,9 +1007,13 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
             sink = _NpyWriter(os.fspath(dst), source.route.ndtype, (n_out, hdr["height"], hdr["width"]))
             return _drive(model, job, lambda: sink.write, sink.close)
         f, finish = _open_sink(dst)
-        return _drive(model, job, lambda: imageio_lite.Y4MWriter(
+        total = _drive(model, job, lambda: imageio_lite.Y4MWriter(
             f, hdr["width"], hdr["height"], job.rate, hdr["colourspace"],
             hdr["colour_range"] if (bits == 10 or model.frame_channels == 3) else None, bits=bits).write, finish)
+        stats = getattr(source.route, "chroma_stats", None)
+        if chroma_log is not None and stats is not None:
+            chroma_log.append((0 if stats["warped"] is None else int(stats["warped"]), stats["blocks"]))
+        return total
     finally:
         source.close()
 

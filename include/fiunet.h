@@ -46,7 +46,9 @@ extern "C" {
                                      added the same way: 10-bit 4:2:2 wire packings (fiunet_packing10,
                                      fiunet_unpack_422p10, fiunet_pack_422p10); v8 also, added the same way:
                                      motion-compensated resampling (fiunet_warp_entry, fiunet_warp_table_u8,
-                                     fiunet_warp_table_p10) */
+                                     fiunet_warp_table_p10); v8 also, added the same way: motion-guided chroma
+                                     (fiunet_chroma_pick_u8, fiunet_chroma_pick_p10, fiunet_chroma_fill_u8,
+                                     fiunet_chroma_fill_p10) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -719,6 +721,45 @@ int fiunet_warp_table_p10(const uint16_t* grid, int n_rows, const fiunet_resize_
                                int n_flows, int flow_h, int flow_w, const uint8_t* flags, int n_flags,
                                const fiunet_warp_entry* entries, int n_out, uint16_t* out,
                                const fiunet_resize_plane* out_plane, void* stream);
+
+/* Motion-guided chroma for the grayscale video route (added without a version bump; the definition is
+ * the package's chroma.py).  One inserted frame M between the stored frames A and B: M's luma comes from the network, and
+ * its chroma is, 8x8 luma block by block, the warp of A's and B's chroma to the middle of the interval along the luma flow
+ * A -> B, or their rounded average, whichever the network's luma says fits there.
+ * fiunet_chroma_pick_*: n frames.  a, b, m: the luma of A, B and M, each a fiunet_resize_plane (filter 0) in a buffer of
+ * its own or at another offset of the same one, all of one h x w; frame k of a plane lies k * frame_stride on.  `field`:
+ * device float [n, h, w, 2], the flow A -> B on the luma (fiunet_farneback_flow), 8-byte aligned.  With
+ * Ym = fiunet_warp_table_* at wn = 1, den = 2 and Ya = (A + B + 1) >> 1, block (by, bx) of the ceil(h / 8) x ceil(w / 8)
+ * blocks has cost_m = sum |Ym - M| and cost_a = sum |Ya - M| over rows 8 by - 4 .. 8 by + 11 and columns
+ * 8 bx - 4 .. 8 bx + 11, every index clamped to the plane (a clamped index counts again: 256 terms); pick [n, ceil(h / 8),
+ * ceil(w / 8)] uint8 = 1 iff cost_m < cost_a (a tie takes the average).  10-bit words above 1023 read as 1023.
+ * fiunet_chroma_fill_*: both chroma planes of n frames.  a_planes, b_planes, out_planes: two planes each (U, V), all six
+ * of one h x w, sub-sampled against the luma by (sy, sx), each 1 or 2; `field` [n, field_h, field_w, 2] and `pick`
+ * [n, ceil(field_h / 8), ceil(field_w / 8)] as above, field_h x field_w the luma size.  Sample (cy, cx) is, where
+ * pick[(cy * sy) >> 3][(cx * sx) >> 3] is non-zero, what fiunet_warp_table_* writes for wn = 1, den = 2 (the field
+ * resampled to the chroma plane by that call's rule), to the last bit; elsewhere (A + B + 1) >> 1.  Samples of `out`
+ * outside its planes are never written.
+ * Both: the planes are HOST memory, read during the call; asynchronous on `stream`, no allocation, no synchronisation,
+ * capturable; n == 0 is a no-op.  FIUNET_ERR_INVALID_ARG, before any launch and before a pointer is used: a NULL
+ * argument, a uint16_t pointer that is not 2-byte aligned, n outside 0 .. 4096, a plane that breaks
+ * fiunet_warp_table_*'s plane rules, planes of different h x w, `field` not 8-byte aligned, a plane range that leaves the
+ * address space, pick overlapping a luma plane; for the fill also sy or sx other than 1 or 2, a bad field shape, a
+ * chroma plane with (h - 1) * sy >= field_h or (w - 1) * sx >= field_w, out's planes overlapping each other or A's or
+ * B's. */
+int fiunet_chroma_pick_u8(const uint8_t* a, const fiunet_resize_plane* a_plane, const uint8_t* b,
+                          const fiunet_resize_plane* b_plane, const uint8_t* m, const fiunet_resize_plane* m_plane,
+                          const float* field, int n, uint8_t* pick, void* stream);
+int fiunet_chroma_pick_p10(const uint16_t* a, const fiunet_resize_plane* a_plane, const uint16_t* b,
+                           const fiunet_resize_plane* b_plane, const uint16_t* m, const fiunet_resize_plane* m_plane,
+                           const float* field, int n, uint8_t* pick, void* stream);
+int fiunet_chroma_fill_u8(const uint8_t* a, const fiunet_resize_plane* a_planes, const uint8_t* b,
+                          const fiunet_resize_plane* b_planes, const float* field, int field_h, int field_w,
+                          const uint8_t* pick, int sy, int sx, int n, uint8_t* out, const fiunet_resize_plane* out_planes,
+                          void* stream);
+int fiunet_chroma_fill_p10(const uint16_t* a, const fiunet_resize_plane* a_planes, const uint16_t* b,
+                           const fiunet_resize_plane* b_planes, const float* field, int field_h, int field_w,
+                           const uint8_t* pick, int sy, int sx, int n, uint16_t* out,
+                           const fiunet_resize_plane* out_planes, void* stream);
 
 /* The training loss' SSIM on device: SSIMLoss._ssim (model/train.py:37-56) - the
  * window_size x window_size Gaussian window (sigma 1.5, normalised as at train.py:27-35) applied as a
