@@ -809,6 +809,14 @@ def _resize_extent(planes, n_frames: int) -> int:
     return max(off + (n_frames - 1) * fs + (h - 1) * pitch + (w - 1) * step + 1 for off, h, w, pitch, step, fs in planes)
 
 
+def _planes_fit(name: str, planes, n: int, room: int) -> None:
+    """ValueError where n frames of `planes` ("src planes", "grid plane": `name`), taken together, reach past a buffer of
+    `room` samples.  Only well-formed planes are judged: the library refuses the others."""
+    if all(min(p) >= 0 and p[1] >= 1 and p[2] >= 1 for p in planes) and _resize_extent(planes, n) > room:
+        verb = "reach" if name.endswith("s") else "reaches"
+        raise ValueError(f"the {name} {verb} sample {_resize_extent(planes, n)} of a buffer of {room}")
+
+
 def resize_planes(src: "torch.Tensor", src_planes, dst: "torch.Tensor", dst_planes, n_frames: int, bits: int,
                   stream=None, filter: int = 0) -> None:
     """fiunet_resize_planes_u8 / fiunet_resize_planes_p10: plane i of `src_planes` of every one of n_frames frames of the
@@ -822,8 +830,7 @@ def resize_planes(src: "torch.Tensor", src_planes, dst: "torch.Tensor", dst_plan
     for name, t, planes in (("src", src, src_planes), ("dst", dst, dst_planes)):
         if not t.is_contiguous():
             raise ValueError(f"{name} must be a dense buffer (the planes carry the pitches)")
-        if all(min(p) >= 0 and p[1] >= 1 and p[2] >= 1 for p in planes) and _resize_extent(planes, n_frames) > t.numel():
-            raise ValueError(f"the {name} planes reach sample {_resize_extent(planes, n_frames)} of a buffer of {t.numel()}")
+        _planes_fit(name + " planes", planes, n_frames, t.numel())
     fn = lib().fiunet_resize_planes_p10 if bits == 10 else lib().fiunet_resize_planes_u8
     check(fn(src.data_ptr(), resize_plane_array(src_planes), dst.data_ptr(), resize_plane_array(dst_planes, int(filter)),
              len(src_planes), n_frames, _stream(src, stream)), "fiunet_resize_planes_" + ("p10" if bits == 10 else "u8"))
@@ -880,8 +887,7 @@ def warp_table(grid: "torch.Tensor", n_rows: int, grid_plane, flow: "torch.Tenso
     for name, t, plane, n in (("grid", grid, grid_plane, n_rows), ("out", out, out_plane, len(entries))):
         if not t.is_contiguous():
             raise ValueError(f"{name} must be a dense buffer (the plane carries the pitch)")
-        if min(plane) >= 0 and plane[1] >= 1 and plane[2] >= 1 and _resize_extent([plane], n) > t.numel():
-            raise ValueError(f"the {name} plane reaches sample {_resize_extent([plane], n)} of a buffer of {t.numel()}")
+        _planes_fit(name + " plane", [plane], n, t.numel())
     if flow.dtype != torch.float32 or flow.dim() != 4 or flow.shape[3] != 2 or not flow.is_contiguous():
         raise ValueError(f"flow: expected a contiguous float32 [n, h, w, 2] tensor, got {flow.dtype} {tuple(flow.shape)}")
     if flags is not None and (flags.dtype != torch.uint8 or not flags.is_contiguous()):
@@ -901,8 +907,7 @@ def _room(t: "torch.Tensor") -> int:
 def _chroma_planes(name, t, planes, n):
     planes = [tuple(int(v) for v in p) for p in planes]
     for p in planes:
-        if min(p) >= 0 and p[1] >= 1 and p[2] >= 1 and _resize_extent([p], n) > _room(t):
-            raise ValueError(f"the {name} plane reaches sample {_resize_extent([p], n)} of a buffer of {_room(t)}")
+        _planes_fit(name + " plane", [p], n, _room(t))   # (plane by plane: U and V may lie in any order)
     return planes
 
 

@@ -1,6 +1,7 @@
 // flow.hip -- Farneback flow and flow-compensated warps (flow.hip.h), with the flow's debug entry points,
 // and the motion-guided chroma that is built on the warp (chroma.hip.h).
 #include "fiunet_internal.h"
+#include "plane_check.h"
 #include "flow.hip.h"
 #include "chroma.hip.h"
 
@@ -18,6 +19,15 @@ extern "C++" {
 namespace {
 constexpr int kFlowLevels = 3, kFlowMinSize = 32, kFlowIters = 3;
 constexpr size_t kFlowMaxBatch = 4096, kFlowMaxSide = 32768;
+
+// a fiunet_resize_plane that plane_check has passed, as the warp kernels take it
+inline FlowWarpPlane warp_plane(const fiunet_resize_plane& p) { return FlowWarpPlane{p.offset, p.pitch, p.frame_stride, p.step}; }
+
+// a plane that is warped or read along a flow carries no filter; plane_check with the flow's bound on a side
+const char* warp_plane_check(const fiunet_resize_plane& p)
+{
+    return p.filter != 0 ? "a plane's filter must be 0" : plane_check(p, (int)kFlowMaxSide);
+}
 
 struct FlowLevel { int h, w, ksize; double sigma; };
 
@@ -116,17 +126,11 @@ inline dim3 flow_rows(int h, int w, int z) { return dim3((w + 63) / 64, (h + 3) 
 
 int flow_check_frames(int bits, int B, int H, int W, size_t image_stride, size_t row_pitch, const void* a, const void* b)
 {
-    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
     if (B < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_INVALID_ARG, "bad frame shape");
     if ((size_t)B > kFlowMaxBatch || (size_t)H > kFlowMaxSide || (size_t)W > kFlowMaxSide)
         return fail(FIUNET_ERR_INVALID_ARG, "flow: more than 4096 pairs per call or a side above 32768");
-    if (row_pitch < (size_t)W) return fail(FIUNET_ERR_INVALID_ARG, "frame layout: row_pitch < W");
-    const size_t limit = (size_t)1 << 40;
-    if (row_pitch > limit || image_stride > limit) return fail(FIUNET_ERR_INVALID_ARG, "frame layout: a value above 2^40 samples");
-    if (B > 1 && image_stride < (size_t)(H - 1) * row_pitch + W)
-        return fail(FIUNET_ERR_INVALID_ARG, "frame layout: image_stride smaller than one frame");
-    if (bits == 10 && ((((uintptr_t)a | (uintptr_t)b) & 1) != 0))
-        return fail(FIUNET_ERR_INVALID_ARG, "10-bit frames are 16-bit words: odd address");
+    if (const char* why = check_pitched(bits, B, H, (size_t)W, image_stride, row_pitch, a, b))
+        return fail(FIUNET_ERR_INVALID_ARG, std::string("frame layout: ") + why);
     return FIUNET_OK;
 }
 
@@ -268,21 +272,6 @@ static_assert(sizeof(fiunet_warp_entry) == 20, "entry layout");
 
 extern "C++" {
 namespace {
-// fiunet_resize_planes' rule for one plane (video.hip: resize_check_plane), with the flow's bound on a side
-const char* warp_check_plane(const fiunet_resize_plane& p)
-{
-    if (p.h < 1 || p.w < 1) return "a plane's h and w must be positive";
-    if ((size_t)p.h > kFlowMaxSide || (size_t)p.w > kFlowMaxSide) return "a plane's h and w must not exceed 32768";
-    if (p.step < 1 || p.step > 4) return "a plane's step must be 1..4";
-    if (p.filter != 0) return "a plane's filter must be 0";
-    const size_t row = (size_t)(p.w - 1) * p.step + 1;
-    if (p.pitch < row) return "a plane's pitch must cover a row: (w - 1) * step + 1";
-    if (p.h > 1 && p.pitch > (SIZE_MAX - row) / (size_t)(p.h - 1)) return "a plane's pitch is too large";
-    const size_t body = (size_t)(p.h - 1) * p.pitch + row;
-    if (p.offset > p.frame_stride || body > p.frame_stride - p.offset) return "a plane must lie inside its frame stride";
-    return nullptr;
-}
-
 template <typename T>
 int flow_warp_table(const T* grid, int n_rows, const fiunet_resize_plane* gp, const float* flow, int n_flows, int flow_h,
                     int flow_w, const uint8_t* flags, int n_flags, const fiunet_warp_entry* entries, int n_out, T* out,
@@ -293,7 +282,7 @@ int flow_warp_table(const T* grid, int n_rows, const fiunet_resize_plane* gp, co
     if (n_rows < 0 || n_out < 0 || n_flows < 0 || n_flags < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
     if (n_flags > 0 && !flags) return fail(FIUNET_ERR_INVALID_ARG, "NULL flags");
     for (const fiunet_resize_plane* p : {gp, op})
-        if (const char* why = warp_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
+        if (const char* why = warp_plane_check(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
     if (gp->h != op->h || gp->w != op->w) return fail(FIUNET_ERR_INVALID_ARG, "the grid's plane and out's differ in size");
     if (flow_h < 1 || flow_w < 1 || (size_t)flow_h > kFlowMaxSide || (size_t)flow_w > kFlowMaxSide)
         return fail(FIUNET_ERR_INVALID_ARG, "bad flow shape");
@@ -311,18 +300,13 @@ int flow_warp_table(const T* grid, int n_rows, const fiunet_resize_plane* gp, co
             return fail(FIUNET_ERR_INVALID_ARG, "entry: flag outside the flags");
     }
     // n_rows frames of the grid's plane and n_out of out's stay inside the address space and apart from each other
-    const size_t gbody = (size_t)(gp->h - 1) * gp->pitch + (size_t)(gp->w - 1) * gp->step + 1;
-    const size_t obody = (size_t)(op->h - 1) * op->pitch + (size_t)(op->w - 1) * op->step + 1;
-    if (gp->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_rows || op->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_out)
+    uintptr_t g0, g1, o0, o1;
+    if (!plane_range(grid, sizeof(T), *gp, n_rows, &g0, &g1) || !plane_range(out, sizeof(T), *op, n_out, &o0, &o1))
         return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
-    const uintptr_t g0 = (uintptr_t)grid + gp->offset * sizeof(T);
-    const uintptr_t g1 = g0 + ((size_t)(n_rows - 1) * gp->frame_stride + gbody) * sizeof(T);
-    const uintptr_t o0 = (uintptr_t)out + op->offset * sizeof(T);
-    const uintptr_t o1 = o0 + ((size_t)(n_out - 1) * op->frame_stride + obody) * sizeof(T);
-    if (g0 < o1 && o0 < g1) return fail(FIUNET_ERR_INVALID_ARG, "out overlaps the grid");
+    if (ranges_overlap(g0, g1, o0, o1)) return fail(FIUNET_ERR_INVALID_ARG, "out overlaps the grid");
     const int h = gp->h, w = gp->w;
     const float mx = (float)((double)w / (double)flow_w), my = (float)((double)h / (double)flow_h);
-    const FlowWarpPlane G = {gp->offset, gp->pitch, gp->frame_stride, gp->step};
+    const FlowWarpPlane G = warp_plane(*gp);
     constexpr int V = FlowWarpVec<T>::V;
     const unsigned bx = (unsigned)(((w + V - 1) / V + 63) / 64), by = (unsigned)((h + 3) / 4);
     for (int k0 = 0; k0 < n_out; k0 += kFlowWarpTableMax) {
@@ -334,7 +318,8 @@ int flow_warp_table(const T* grid, int n_rows, const fiunet_resize_plane* gp, co
             table.e[k] = FlowWarpEntry{e.row, e.wn, e.den, e.flow, e.flag, (float)((double)e.wn / (double)e.den),
                                        (float)((double)(e.den - e.wn) / (double)e.den)};
         }
-        const FlowWarpPlane O = {op->offset + (size_t)k0 * op->frame_stride, op->pitch, op->frame_stride, op->step};
+        FlowWarpPlane O = warp_plane(*op);
+        O.off += (size_t)k0 * op->frame_stride;
         hipLaunchKernelGGL(flow_warp_table_kernel<T>, dim3(bx, by, (unsigned)nk), dim3(256), 0, (hipStream_t)stream, grid,
                            G, flow, flow_h, flow_w, mx, my, flags, table, h, w, out, O);
         HIP_TRY(hipGetLastError());
@@ -366,20 +351,6 @@ int fiunet_warp_table_p10(const uint16_t* grid, int n_rows, const fiunet_resize_
 // As above: everything a thread indexes is checked here, before the first launch and before a pointer is used.
 extern "C++" {
 namespace {
-// [p0, p1) in bytes of n frames of a checked plane in a buffer of T; false where it leaves the address space
-template <typename T>
-bool chroma_extent(const T* base, const fiunet_resize_plane& p, int n, uintptr_t& p0, uintptr_t& p1)
-{
-    const size_t body = (size_t)(p.h - 1) * p.pitch + (size_t)(p.w - 1) * p.step + 1;
-    const size_t room = SIZE_MAX / sizeof(T);   // (offset + body <= frame_stride: warp_check_plane)
-    if (p.offset + body > room || p.frame_stride > (room - body - p.offset) / (size_t)n) return false;
-    p0 = (uintptr_t)base + p.offset * sizeof(T);
-    p1 = p0 + ((size_t)(n - 1) * p.frame_stride + body) * sizeof(T);
-    return p1 >= p0;
-}
-
-inline FlowWarpPlane chroma_plane(const fiunet_resize_plane& p) { return FlowWarpPlane{p.offset, p.pitch, p.frame_stride, p.step}; }
-
 template <typename T>
 int chroma_pick(const T* a, const fiunet_resize_plane* ap, const T* b, const fiunet_resize_plane* bp, const T* m,
                 const fiunet_resize_plane* mp, const float* flow, int n, uint8_t* pick, void* stream)
@@ -388,7 +359,7 @@ int chroma_pick(const T* a, const fiunet_resize_plane* ap, const T* b, const fiu
     if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)m) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
     if (n < 0 || (size_t)n > kFlowMaxBatch) return fail(FIUNET_ERR_INVALID_ARG, "n must be 0..4096");
     for (const fiunet_resize_plane* p : {ap, bp, mp})
-        if (const char* why = warp_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
+        if (const char* why = warp_plane_check(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
     if (ap->h != bp->h || ap->w != bp->w || ap->h != mp->h || ap->w != mp->w)
         return fail(FIUNET_ERR_INVALID_ARG, "the three luma planes differ in size");
     if ((uintptr_t)flow & 7) return fail(FIUNET_ERR_INVALID_ARG, "flow not 8-B aligned");
@@ -400,13 +371,13 @@ int chroma_pick(const T* a, const fiunet_resize_plane* ap, const T* b, const fiu
     const fiunet_resize_plane* planes[3] = {ap, bp, mp};
     for (int i = 0; i < 3; ++i) {
         uintptr_t p0, p1;
-        if (!chroma_extent(bases[i], *planes[i], n, p0, p1)) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
-        if (p0 < k1 && k0 < p1) return fail(FIUNET_ERR_INVALID_ARG, "the pick map overlaps a luma plane");
+        if (!plane_range(bases[i], sizeof(T), *planes[i], n, &p0, &p1)) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+        if (ranges_overlap(p0, p1, k0, k1)) return fail(FIUNET_ERR_INVALID_ARG, "the pick map overlaps a luma plane");
     }
     const dim3 grid((unsigned)((pw + CHROMA_TILE_X - 1) / CHROMA_TILE_X), (unsigned)((ph + CHROMA_TILE_Y - 1) / CHROMA_TILE_Y),
                     (unsigned)n);
-    hipLaunchKernelGGL(chroma_pick_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, a, chroma_plane(*ap), b,
-                       chroma_plane(*bp), m, chroma_plane(*mp), flow, h, w, ph, pw, pick);
+    hipLaunchKernelGGL(chroma_pick_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, a, warp_plane(*ap), b,
+                       warp_plane(*bp), m, warp_plane(*mp), flow, h, w, ph, pw, pick);
     HIP_TRY(hipGetLastError());
     return FIUNET_OK;
 }
@@ -422,7 +393,7 @@ int chroma_fill(const T* a, const fiunet_resize_plane* ap, const T* b, const fiu
     if ((sy != 1 && sy != 2) || (sx != 1 && sx != 2)) return fail(FIUNET_ERR_INVALID_ARG, "sy and sx must be 1 or 2");
     for (int i = 0; i < 2; ++i)
         for (const fiunet_resize_plane* p : {ap + i, bp + i, op + i}) {
-            if (const char* why = warp_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
+            if (const char* why = warp_plane_check(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
             if (p->h != ap->h || p->w != ap->w) return fail(FIUNET_ERR_INVALID_ARG, "the chroma planes differ in size");
         }
     if (flow_h < 1 || flow_w < 1 || (size_t)flow_h > kFlowMaxSide || (size_t)flow_w > kFlowMaxSide)
@@ -436,32 +407,27 @@ int chroma_fill(const T* a, const fiunet_resize_plane* ap, const T* b, const fiu
     const int ph = (flow_h + CHROMA_BLOCK - 1) / CHROMA_BLOCK, pw = (flow_w + CHROMA_BLOCK - 1) / CHROMA_BLOCK;
     uintptr_t o0[2], o1[2];
     for (int i = 0; i < 2; ++i)
-        if (!chroma_extent(out, op[i], n, o0[i], o1[i])) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+        if (!plane_range(out, sizeof(T), op[i], n, &o0[i], &o1[i])) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
     // U and V of a frame usually share a frame stride and lie side by side inside it: then one frame's two planes must
     // not overlap (each lies inside the stride, so frames do not meet); with two strides the whole ranges must not
-    {
-        uintptr_t u0 = o0[0], u1 = o1[0], v0 = o0[1], v1 = o1[1];
-        if (op[0].frame_stride == op[1].frame_stride) {
-            chroma_extent(out, op[0], 1, u0, u1);
-            chroma_extent(out, op[1], 1, v0, v1);
-        }
-        if (u0 < v1 && v0 < u1 && (op[0].step == 1 || op[1].step == 1))
-            return fail(FIUNET_ERR_INVALID_ARG, "out's two planes overlap");
-    }
-    for (int i = 0; i < 2; ++i) {
+    const int nuv = op[0].frame_stride == op[1].frame_stride ? 1 : n;   // (n frames fit: so do nuv)
+    uintptr_t u0, u1, v0, v1;
+    plane_range(out, sizeof(T), op[0], nuv, &u0, &u1), plane_range(out, sizeof(T), op[1], nuv, &v0, &v1);
+    if (ranges_overlap(u0, u1, v0, v1) && (op[0].step == 1 || op[1].step == 1))
+        return fail(FIUNET_ERR_INVALID_ARG, "out's two planes overlap");
+    for (int i = 0; i < 4; ++i) {   // A's two planes, then B's, against out's two
+        const bool is_b = i >= 2;
         uintptr_t p0, p1;
-        if (!chroma_extent(a, ap[i], n, p0, p1)) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+        if (!plane_range(is_b ? b : a, sizeof(T), (is_b ? bp : ap)[i & 1], n, &p0, &p1))
+            return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
         for (int j = 0; j < 2; ++j)
-            if (p0 < o1[j] && o0[j] < p1) return fail(FIUNET_ERR_INVALID_ARG, "out overlaps A");
-        if (!chroma_extent(b, bp[i], n, p0, p1)) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
-        for (int j = 0; j < 2; ++j)
-            if (p0 < o1[j] && o0[j] < p1) return fail(FIUNET_ERR_INVALID_ARG, "out overlaps B");
+            if (ranges_overlap(p0, p1, o0[j], o1[j])) return fail(FIUNET_ERR_INVALID_ARG, is_b ? "out overlaps B" : "out overlaps A");
     }
     ChromaPlanes P;
     for (int i = 0; i < 2; ++i) {
-        P.a[i] = chroma_plane(ap[i]);
-        P.b[i] = chroma_plane(bp[i]);
-        P.o[i] = chroma_plane(op[i]);
+        P.a[i] = warp_plane(ap[i]);
+        P.b[i] = warp_plane(bp[i]);
+        P.o[i] = warp_plane(op[i]);
     }
     const float mx = (float)((double)w / (double)flow_w), my = (float)((double)h / (double)flow_h);
     constexpr int V = FlowWarpVec<T>::V;

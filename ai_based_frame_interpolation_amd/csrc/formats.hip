@@ -2,6 +2,7 @@
 // at 8 and 10 bits, NV12 / P010 surfaces, YUV 4:2:2 / 4:4:4 and packed RGB - their conversions (colour.hip.h, yuv4xx.hip.h,
 // packed.hip.h) and the fiunet_forward_<format> entry points around fiunet_forward_u8_strided / fiunet_forward_p10.
 #include "fiunet_internal.h"
+#include "plane_check.h"
 #include "colour.hip.h"
 #include "packed.hip.h"
 #include "wire10.hip.h"
@@ -46,7 +47,7 @@ static int check_colour_args(const void* in, const void* out, int B, int H, int 
 {
     if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
     if (int rc = check_colour_flags(colour, bits)) return rc;
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    if (const char* why = check_frame_shape(B, H, W)) return fail(FIUNET_ERR_BAD_SHAPE, why);
     return FIUNET_OK;
 }
 
@@ -216,24 +217,13 @@ int fiunet_forward_yuv420p10(fiunet_ctx* ctx, const uint16_t* frame1, const uint
 }
 
 // ---- NV12 / P010 decoder surfaces: the colour conversions on semi-planar, pitched frames ----
-// The caller's layout (NULL or zero fields = tight) -> the resolved one, refused before any launch where it cannot
-// hold an H x W frame.  Every quantity in samples.
-static int resolve_surface(const fiunet_surface_layout* l, int H, int W, ColourSurface* sf)
+// The caller's layout -> the resolved one (plane_check.h: resolve_surface, the chroma plane ceil(H/2) rows high), refused
+// before any launch.  Every quantity in samples.
+static int resolve_nv12(const fiunet_surface_layout* l, int H, int W, ColourSurface* sf)
 {
-    const size_t Hc = (size_t)(H + 1) / 2, Wc = (size_t)(W + 1) / 2;
-    sf->luma_pitch = l && l->luma_pitch ? l->luma_pitch : (size_t)W;
-    sf->chroma_offset = l && l->chroma_offset ? l->chroma_offset : (size_t)H * W;
-    sf->chroma_pitch = l && l->chroma_pitch ? l->chroma_pitch : 2 * Wc;
-    sf->frame_stride = l && l->frame_stride ? l->frame_stride : i420_frame_bytes(H, W);
-    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
-    if (sf->luma_pitch > big || sf->chroma_pitch > big || sf->chroma_offset > big || sf->frame_stride > big)
-        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: a value above 2^40 samples");
-    if (sf->luma_pitch < (size_t)W) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: luma_pitch < W");
-    if (sf->chroma_pitch < 2 * Wc) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_pitch < 2*ceil(W/2)");
-    if (sf->chroma_offset < (size_t)(H - 1) * sf->luma_pitch + W)
-        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_offset inside the luma plane");
-    if (sf->frame_stride < sf->chroma_offset + (Hc - 1) * sf->chroma_pitch + 2 * Wc)
-        return fail(FIUNET_ERR_INVALID_ARG, "surface layout: frame_stride does not cover the chroma plane");
+    fiunet_surface_layout r;
+    if (const char* why = resolve_surface(l, H, W, ((size_t)H + 1) / 2, &r)) return fail(FIUNET_ERR_INVALID_ARG, why);
+    *sf = ColourSurface{r.luma_pitch, r.chroma_offset, r.chroma_pitch, r.frame_stride};
     return FIUNET_OK;
 }
 
@@ -253,7 +243,7 @@ static int surface_to_rgb(const T* in, const fiunet_surface_layout* layout, T* o
     int rc;
     if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
     ColourSurface sf;
-    if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
+    if ((rc = resolve_nv12(layout, H, W, &sf))) return rc;
     return launch_vec<&nv12_to_rgb_kernel<T, true>, &nv12_to_rgb_kernel<T, false>>(
         surface_vec<T>(sf, W, in, out), colour_grid(W, H, B), stream, in, sf, out, H, W, colour_coef(colour, bits));
 }
@@ -265,7 +255,7 @@ static int rgb_to_surface(const T* in, T* out, const fiunet_surface_layout* layo
     int rc;
     if ((rc = check_colour_args(in, out, B, H, W, colour, bits))) return rc;
     ColourSurface sf;
-    if ((rc = resolve_surface(layout, H, W, &sf))) return rc;
+    if ((rc = resolve_nv12(layout, H, W, &sf))) return rc;
     return launch_vec<&rgb_to_nv12_kernel<T, true>, &rgb_to_nv12_kernel<T, false>>(
         surface_vec<T>(sf, W, in, out), colour_grid(W, (H + 1) / 2, B), stream, in, out, sf, H, W,
         colour_coef(colour, bits));
@@ -282,7 +272,7 @@ static int forward_surface(const char* name, int bits, fiunet_ctx* ctx, const T*
         [&] {
             ColourSurface sf;
             int rc = check_colour_flags(colour, bits);
-            if (!rc && !(rc = resolve_surface(in_layout, H, W, &sf))) rc = resolve_surface(out_layout, H, W, &sf);
+            if (!rc && !(rc = resolve_nv12(in_layout, H, W, &sf))) rc = resolve_nv12(out_layout, H, W, &sf);
             return rc;
         },
         [&](const T* in, T* rgb) { return surface_to_rgb<T>(in, in_layout, rgb, B, H, W, colour, bits, stream); },
@@ -361,20 +351,17 @@ static int resolve_yuv(int format, int bits, size_t row_pitch, size_t frame_stri
                        YuvLayout* lay)
 {
     if (int rc = check_colour_flags(colour, bits)) return rc;
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    if (const char* why = check_frame_shape(B, H, W)) return fail(FIUNET_ERR_BAD_SHAPE, why);
     const size_t tight = yuv_frame_samples(format, H, W);
     if (!tight) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_yuv_format");
-    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
-    if (row_pitch > big || frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: a value above 2^40");
+    if (row_pitch > kLayoutMax || frame_stride > kLayoutMax) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: a value above 2^40");
     if (yuv_is_packed(format)) {
         if (bits != 8) return fail(FIUNET_ERR_INVALID_ARG, "format: uyvy422 / yuyv422 are 8-bit formats");
         if (W & 1) return fail(FIUNET_ERR_INVALID_ARG, "uyvy422 / yuyv422 need an even width");
-        const size_t row = 2 * (size_t)W;
-        lay->row_pitch = row_pitch ? row_pitch : row;
-        if (lay->row_pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: row_pitch < 2*W");
-        lay->frame_stride = frame_stride ? frame_stride : (size_t)H * lay->row_pitch;
-        if (lay->frame_stride < (size_t)(H - 1) * lay->row_pitch + row)
-            return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: frame_stride does not cover the last row");
+        const fiunet_packed_layout l = {row_pitch, frame_stride};   // (one plane of rows of 2 * W bytes)
+        fiunet_packed_layout r;
+        if (const char* why = resolve_rows(&l, H, 2 * (size_t)W, &r)) return fail(FIUNET_ERR_INVALID_ARG, why);
+        *lay = YuvLayout{r.row_pitch, r.frame_stride};
         return FIUNET_OK;
     }
     if (row_pitch) return fail(FIUNET_ERR_INVALID_ARG, "yuv layout: planar frames are tight (row_pitch must be 0)");
@@ -515,18 +502,12 @@ static int packed_bpp(int format)
          : format == FIUNET_PACKED_RGBA || format == FIUNET_PACKED_BGRA ? 4 : 0;
 }
 
-// The caller's layout (NULL or zero fields = tight) -> the resolved one, refused before any launch where it cannot hold
-// an H x W frame of bpp bytes per pixel.  Every quantity in bytes.
+// The caller's layout -> the resolved one (plane_check.h: resolve_rows, rows of W * bpp bytes), refused before any launch.
 static int resolve_packed(const fiunet_packed_layout* l, int H, int W, int bpp, PackedLayout* pl)
 {
-    const size_t row = (size_t)W * bpp, big = (size_t)1 << 40;   // (keeps every product below in range)
-    pl->row_pitch = l && l->row_pitch ? l->row_pitch : row;
-    if (pl->row_pitch > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
-    pl->frame_stride = l && l->frame_stride ? l->frame_stride : (size_t)H * pl->row_pitch;
-    if (pl->frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
-    if (pl->row_pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: row_pitch < W*bpp");
-    if (pl->frame_stride < (size_t)(H - 1) * pl->row_pitch + row)
-        return fail(FIUNET_ERR_INVALID_ARG, "packed layout: frame_stride does not cover the last row");
+    fiunet_packed_layout r;
+    if (const char* why = resolve_rows(l, H, (size_t)W * bpp, &r)) return fail(FIUNET_ERR_INVALID_ARG, why);
+    *pl = PackedLayout{r.row_pitch, r.frame_stride};
     return FIUNET_OK;
 }
 
@@ -534,7 +515,7 @@ static int check_packed_args(const void* in, const void* out, int B, int H, int 
 {
     if (!in || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
     if (!packed_bpp(format)) return fail(FIUNET_ERR_INVALID_ARG, "format: not a fiunet_packed_format");
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    if (const char* why = check_frame_shape(B, H, W)) return fail(FIUNET_ERR_BAD_SHAPE, why);
     return FIUNET_OK;
 }
 
@@ -644,42 +625,26 @@ static int resolve_wire10(const void* wire, int packing, const fiunet_packed_lay
     if (!wire || !work) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
     if (packing != FIUNET_PACK10_V210 && packing != FIUNET_PACK10_Y210 && packing != FIUNET_PACK10_P210)
         return fail(FIUNET_ERR_INVALID_ARG, "packing: not a fiunet_packing10");
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return fail(FIUNET_ERR_BAD_SHAPE, "bad frame shape");
+    if (const char* why = check_frame_shape(B, H, W)) return fail(FIUNET_ERR_BAD_SHAPE, why);
     if (((uintptr_t)wire | (uintptr_t)work) & 1) return fail(FIUNET_ERR_INVALID_ARG, "wire10: a pointer is not 2-byte aligned");
     const size_t Wc = (size_t)(W + 1) / 2, tight = (size_t)H * W + 2 * (size_t)H * Wc;
-    const size_t big = (size_t)1 << 40;   // (keeps every product below in range)
     if (*work_stride == 0) *work_stride = tight;
-    if (*work_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "wire10: a value above 2^40");
+    if (*work_stride > kLayoutMax) return fail(FIUNET_ERR_INVALID_ARG, "wire10: a value above 2^40");
     if (*work_stride < tight) return fail(FIUNET_ERR_INVALID_ARG, "wire10: the planar frame stride is smaller than one frame");
     bool aligned = W % 8 == 0 && *work_stride % 8 == 0 && (((uintptr_t)wire | (uintptr_t)work) & 15) == 0;
     if (packing == FIUNET_PACK10_P210) {
         if (pl) return fail(FIUNET_ERR_INVALID_ARG, "p210le takes a fiunet_surface_layout, not a fiunet_packed_layout");
-        lay->pitch = sl && sl->luma_pitch ? sl->luma_pitch : (size_t)W;
-        lay->chroma_offset = sl && sl->chroma_offset ? sl->chroma_offset : (size_t)H * W;
-        lay->chroma_pitch = sl && sl->chroma_pitch ? sl->chroma_pitch : 2 * Wc;
-        lay->frame_stride = sl && sl->frame_stride ? sl->frame_stride : tight;
-        if (lay->pitch > big || lay->chroma_pitch > big || lay->chroma_offset > big || lay->frame_stride > big)
-            return fail(FIUNET_ERR_INVALID_ARG, "surface layout: a value above 2^40 samples");
-        if (lay->pitch < (size_t)W) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: luma_pitch < W");
-        if (lay->chroma_pitch < 2 * Wc) return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_pitch < 2*ceil(W/2)");
-        if (lay->chroma_offset < (size_t)(H - 1) * lay->pitch + W)
-            return fail(FIUNET_ERR_INVALID_ARG, "surface layout: chroma_offset inside the luma plane");
-        if (lay->frame_stride < lay->chroma_offset + (size_t)(H - 1) * lay->chroma_pitch + 2 * Wc)
-            return fail(FIUNET_ERR_INVALID_ARG, "surface layout: frame_stride does not cover the chroma plane");
+        fiunet_surface_layout r;
+        if (const char* why = resolve_surface(sl, H, W, (size_t)H, &r)) return fail(FIUNET_ERR_INVALID_ARG, why);
+        *lay = Wire10Layout{r.luma_pitch, r.chroma_offset, r.chroma_pitch, r.frame_stride};
         *vec = aligned && (lay->pitch | lay->chroma_offset | lay->chroma_pitch | lay->frame_stride) % 8 == 0;
         return FIUNET_OK;
     }
     if (sl) return fail(FIUNET_ERR_INVALID_ARG, "v210 / y210le take a fiunet_packed_layout, not a fiunet_surface_layout");
     if (W & 1) return fail(FIUNET_ERR_INVALID_ARG, "v210 / y210le need an even width");
-    const size_t row = wire10_row_bytes(packing, W);
-    lay->chroma_offset = lay->chroma_pitch = 0;
-    lay->pitch = pl && pl->row_pitch ? pl->row_pitch : row;
-    if (lay->pitch > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
-    lay->frame_stride = pl && pl->frame_stride ? pl->frame_stride : (size_t)H * lay->pitch;
-    if (lay->frame_stride > big) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: a value above 2^40 bytes");
-    if (lay->pitch < row) return fail(FIUNET_ERR_INVALID_ARG, "packed layout: row_pitch below the tight row");
-    if (lay->frame_stride < (size_t)(H - 1) * lay->pitch + row)
-        return fail(FIUNET_ERR_INVALID_ARG, "packed layout: frame_stride does not cover the last row");
+    fiunet_packed_layout r;
+    if (const char* why = resolve_rows(pl, H, wire10_row_bytes(packing, W), &r)) return fail(FIUNET_ERR_INVALID_ARG, why);
+    *lay = Wire10Layout{r.row_pitch, 0, 0, r.frame_stride};
     if ((lay->pitch | lay->frame_stride) & 1)
         return fail(FIUNET_ERR_INVALID_ARG, "packed layout: row_pitch and frame_stride must be even (16-bit words)");
     *vec = aligned && (lay->pitch | lay->frame_stride) % 16 == 0;

@@ -2,6 +2,7 @@
 // metrics of hold-out scoring - each entry point its own argument checks, then the same launches - and the Gaussian SSIM
 // of the training loss.
 #include "fiunet_internal.h"
+#include "plane_check.h"
 #include "metrics.hip.h"
 
 #include <cmath>
@@ -158,22 +159,11 @@ static int check_planes(const void* pred, size_t pred_image_stride, size_t pred_
                         size_t pred_row = 0, size_t target_row = 0)
 {
     if (!pred || !target || !out || !workspace) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
-    if (bits != 8 && bits != 10) return fail(FIUNET_ERR_INVALID_ARG, "bits must be 8 or 10");
     if (images < 1 || H < 1 || W < 1) return fail(FIUNET_ERR_INVALID_ARG, "bad plane shape");
     if (images > 65535) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 planes per call");
-    if (!pred_row) pred_row = (size_t)W;
-    if (!target_row) target_row = (size_t)W;
-    if (pred_row_pitch < pred_row || target_row_pitch < target_row)
-        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: row_pitch < W");
-    const size_t limit = (size_t)1 << 40;
-    if (pred_row_pitch > limit || target_row_pitch > limit || pred_image_stride > limit || target_image_stride > limit)
-        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: a value above 2^40 samples");
-    if (images > 1 && (pred_image_stride < (size_t)(H - 1) * pred_row_pitch + pred_row ||
-                       target_image_stride < (size_t)(H - 1) * target_row_pitch + target_row))
-        return fail(FIUNET_ERR_INVALID_ARG, "plane layout: image_stride smaller than one plane");
-    const size_t align = bits == 10 ? 1 : 0;
-    if ((((uintptr_t)pred | (uintptr_t)target) & align) != 0)
-        return fail(FIUNET_ERR_INVALID_ARG, "10-bit planes are 16-bit words: odd address");
+    const char* why = check_pitched(bits, images, H, pred_row ? pred_row : (size_t)W, pred_image_stride, pred_row_pitch, pred, pred);
+    if (!why) why = check_pitched(bits, images, H, target_row ? target_row : (size_t)W, target_image_stride, target_row_pitch, target, target);
+    if (why) return fail(FIUNET_ERR_INVALID_ARG, std::string("plane layout: ") + why);
     if (workspace_bytes < need) return fail(FIUNET_ERR_INVALID_ARG, "workspace too small");
     if ((uintptr_t)workspace & 255) return fail(FIUNET_ERR_INVALID_ARG, "workspace not 256-B aligned");
     return FIUNET_OK;

@@ -1,6 +1,7 @@
 // video.hip -- operations on frame sequences: scene cuts and repeated frames (scene.hip.h), frame-rate conversion
 // (retime.hip.h) and resizing frame planes (resize.hip.h).
 #include "fiunet_internal.h"
+#include "plane_check.h"
 #include "scene.hip.h"
 #include "retime.hip.h"
 #include "resize.hip.h"
@@ -204,32 +205,6 @@ int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_sampl
 
 // ---- resizing frame planes (csrc/resize.hip.h) ------------------------------------------------------
 extern "C++" {
-// the byte range [lo, hi) that n frames of the planes cover, from the buffer's first sample
-static void resize_extent(const fiunet_resize_plane* planes, int n_planes, int n_frames, size_t& lo, size_t& hi)
-{
-    lo = SIZE_MAX, hi = 0;
-    for (int i = 0; i < n_planes; ++i) {
-        const fiunet_resize_plane& p = planes[i];
-        const size_t end = p.offset + (size_t)(n_frames - 1) * p.frame_stride + (size_t)(p.h - 1) * p.pitch +
-                           (size_t)(p.w - 1) * p.step + 1;
-        lo = std::min(lo, p.offset), hi = std::max(hi, end);
-    }
-}
-
-static const char* resize_check_plane(const fiunet_resize_plane& p)
-{
-    if (p.h < 1 || p.w < 1) return "a plane's h and w must be positive";
-    if (p.h > kResizeMaxSize || p.w > kResizeMaxSize) return "a plane's h and w must not exceed 2^24";
-    if (p.step < 1 || p.step > 4) return "a plane's step must be 1..4";
-    if (p.pitch < (size_t)(p.w - 1) * p.step + 1) return "a plane's pitch must cover a row: (w - 1) * step + 1";
-    // (h, w <= 2^24, step <= 4: the row term is below 2^26; the others are checked against wrapping)
-    const size_t row = (size_t)(p.w - 1) * p.step + 1;
-    if (p.h > 1 && p.pitch > (SIZE_MAX - row) / (size_t)(p.h - 1)) return "a plane's pitch is too large";
-    const size_t body = (size_t)(p.h - 1) * p.pitch + row;
-    if (p.offset > p.frame_stride || body > p.frame_stride - p.offset) return "a plane must lie inside its frame stride";
-    return nullptr;
-}
-
 template <typename T>
 static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, const fiunet_resize_plane* dp,
                          int n_planes, int n_frames, void* stream)
@@ -252,12 +227,17 @@ static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, co
     ResizeArgs base[2] = {};
     int count[2] = {0, 0};
     unsigned long long per_frame_max = 0;
+    // the bytes [lo, hi) of n_frames frames of all source planes [0] and of all destination planes [1]
+    uintptr_t lo[2] = {UINTPTR_MAX, UINTPTR_MAX}, hi[2] = {0, 0};
     for (int i = 0; i < n_planes; ++i) {
-        for (const fiunet_resize_plane* p : {&sp[i], &dp[i]}) {
-            if (const char* why = resize_check_plane(*p)) return fail(FIUNET_ERR_INVALID_ARG, why);
-            // n frames of the plane stay inside the address space
-            if (n_frames > 1 && p->frame_stride > (SIZE_MAX / sizeof(T)) / (size_t)n_frames)
+        for (int d = 0; d < 2; ++d) {
+            const fiunet_resize_plane& p = d ? dp[i] : sp[i];
+            if (const char* why = plane_check(p, kResizeMaxSize)) return fail(FIUNET_ERR_INVALID_ARG, why);
+            if (n_frames == 0) continue;
+            uintptr_t p0, p1;
+            if (!plane_range(d ? (const void*)dst : src, sizeof(T), p, n_frames, &p0, &p1))
                 return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+            lo[d] = std::min(lo[d], p0), hi[d] = std::max(hi[d], p1);
         }
         const bool equal = sp[i].h == dp[i].h && sp[i].w == dp[i].w;
         if (filter == FIUNET_RESIZE_AREA) {
@@ -281,12 +261,7 @@ static int resize_planes(const T* src, const fiunet_resize_plane* sp, T* dst, co
         per_frame_max = std::max(per_frame_max, per_frame);
     }
     if (n_frames == 0) return FIUNET_OK;
-    size_t slo, shi, dlo, dhi;
-    resize_extent(sp, n_planes, n_frames, slo, shi);
-    resize_extent(dp, n_planes, n_frames, dlo, dhi);
-    const uintptr_t s0 = (uintptr_t)src + slo * sizeof(T), s1 = (uintptr_t)src + shi * sizeof(T);
-    const uintptr_t d0 = (uintptr_t)dst + dlo * sizeof(T), d1 = (uintptr_t)dst + dhi * sizeof(T);
-    if (s0 < d1 && d0 < s1) return fail(FIUNET_ERR_INVALID_ARG, "source and destination overlap");
+    if (ranges_overlap(lo[0], hi[0], lo[1], hi[1])) return fail(FIUNET_ERR_INVALID_ARG, "source and destination overlap");
     // frames per launch: every plane's item count stays below 2^31
     const int batch = (int)std::min<unsigned long long>(((1ull << 31) - 1) / per_frame_max, (unsigned long long)n_frames);
     for (int f0 = 0; f0 < n_frames; f0 += batch) {

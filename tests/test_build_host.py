@@ -74,6 +74,11 @@ def test_a_periphery_header_recompiles_its_unit_alone(objdir):
     assert _compiled(res) == {"video"} and "libfiunet_hip.so" in res.stdout
 
 
+def test_the_layout_rules_recompile_the_units_that_check_layouts(objdir):
+    """csrc/plane_check.h is host code of the four periphery units: no conv unit and not the core unit include it."""
+    assert _compiled(_make("-n", "-W", "plane_check.h", objdir)) == {"formats", "metrics", "video", "flow"}
+
+
 def test_the_conv_kernels_recompile_every_conv_unit(objdir, units):
     for header in ("conv3x3_mfma.hip.h", "conv3x3_kwave.hip.h", "conv_launch.hip.h"):
         assert _compiled(_make("-n", "-W", header, objdir)) == set(CONV_UNITS), header
