@@ -62,6 +62,8 @@ SYMBOLS = (
     "fiunet_warp_table_u8", "fiunet_warp_table_p10",
     # motion-guided chroma
     "fiunet_chroma_pick_u8", "fiunet_chroma_pick_p10", "fiunet_chroma_fill_u8", "fiunet_chroma_fill_p10",
+    # deinterlacing
+    "fiunet_deinterlace_u8", "fiunet_deinterlace_p10",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -233,6 +235,8 @@ def lib() -> ctypes.CDLL:
     L.fiunet_chroma_pick_p10.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp]
     L.fiunet_chroma_fill_u8.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, vp, vp, vp]
     L.fiunet_chroma_fill_p10.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, vp, vp, vp]
+    L.fiunet_deinterlace_u8.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+    L.fiunet_deinterlace_p10.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
     L.fiunet_nv12_to_rgb_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_rgb_to_nv12_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_p010_to_rgb_p10.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
@@ -950,3 +954,29 @@ def chroma_fill(a: "torch.Tensor", a_planes, b: "torch.Tensor", b_planes, flow: 
     check(fn(a.data_ptr(), resize_plane_array(ap), b.data_ptr(), resize_plane_array(bp), flow.data_ptr(), fh, fw,
              pick.data_ptr(), int(sub[0]), int(sub[1]), n, out.data_ptr(), resize_plane_array(op), _stream(a, stream)),
           "fiunet_chroma_fill_" + ("p10" if bits == 10 else "u8"))
+
+
+# include/fiunet.h: enum fiunet_deint
+DEINT_TFF, DEINT_BFF = 0, 1
+DEINT_FIELD_RATE, DEINT_FRAME_RATE = 0, 1
+DEINT_ADAPTIVE, DEINT_BOB, DEINT_NO_SPATIAL_CHECK = 0, 1, 256
+
+
+def deinterlace(src: "torch.Tensor", n_src: int, src_planes, dst: "torch.Tensor", dst_planes, first: int, n_frames: int,
+                order: int, rate: int, method_flags: int, bits: int, stream=None) -> None:
+    """fiunet_deinterlace_u8 / fiunet_deinterlace_p10: frames first .. first + n_frames - 1 of the window of n_src frames
+    in the dense buffer `src` -> n_frames (DEINT_FRAME_RATE) or 2 * n_frames (DEINT_FIELD_RATE) frames of `dst`, 1..4
+    planes (offset, h, w, pitch, step, frame_stride) in samples from each tensor's first element.  ValueError, before the
+    call, where well-formed planes reach past either tensor."""
+    src_planes, dst_planes = [tuple(int(v) for v in p) for p in src_planes], [tuple(int(v) for v in p) for p in dst_planes]
+    if len(src_planes) != len(dst_planes):
+        raise ValueError(f"{len(src_planes)} source planes for {len(dst_planes)} destination planes")
+    n_out = n_frames * (2 if rate == DEINT_FIELD_RATE else 1)
+    for name, t, planes, n in (("src", src, src_planes, n_src), ("dst", dst, dst_planes, n_out)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be a dense buffer (the planes carry the pitches)")
+        _planes_fit(name + " planes", planes, n, t.numel())
+    fn = lib().fiunet_deinterlace_p10 if bits == 10 else lib().fiunet_deinterlace_u8
+    check(fn(src.data_ptr(), n_src, resize_plane_array(src_planes), dst.data_ptr(), resize_plane_array(dst_planes),
+             len(src_planes), first, n_frames, order, rate, method_flags, _stream(src, stream)),
+          "fiunet_deinterlace_" + ("p10" if bits == 10 else "u8"))

@@ -70,6 +70,17 @@ the held-out frames next to a hard cut out of the summary:
     ffmpeg -i clip.mkv -f rawvideo -pix_fmt nv12 - | python -m ai_based_frame_interpolation_amd.cli evaluate \\
         --input - --raw nv12 --size 1920x1080 --src-fps 24 --model rgb_model.pth --scene-cut 10 --json scores.json
 
+`deinterlace` turns the fields of interlaced video into frames (deinterlace.py) and needs no model.  It
+sits in front of `video`, which - like `evaluate` - warns where a Y4M header says interlaced and treats the frames as
+they are:
+
+    ffmpeg -i 1080i.mxf -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli deinterlace --input - \\
+        --output - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - --model best_model.pth \\
+        --fps 100 | ffmpeg -f yuv4mpegpipe -i - out.mkv
+
+--order auto (the default) reads `It` / `Ib` off the Y4M header; --rate field (the default) writes one frame per field
+at twice the rate; --raw / --size / --packing take headerless video as `video` does, with --order tff or bff.
+
 `--resize WIDTHxHEIGHT` on either command resizes every frame on the GPU right after its upload (resize.py, DESIGN.md
 3.3q): `video` then writes a clip of that size, `evaluate` scores the checkpoint at that size - 256x256 is what the
 reference trains and evaluates at - and says so in its table.  --size stays the size of the --raw source.
@@ -235,12 +246,46 @@ def parser() -> argparse.ArgumentParser:
                         "or motion (see video --chroma); the u and v rows of the table show the difference")
     e.add_argument("--json", default=None, metavar="FILE", help="Write the whole result here (arrays as lists)")
     e.add_argument("--csv", default=None, metavar="FILE", help="Write one line per scored frame here")
+    d = sub.add_parser("deinterlace", help="Deinterlace interlaced video: fields to frames (Y4M or --raw; '-' is stdin / "
+                                            "stdout; needs no model)")
+    d.add_argument("--input", required=True, help="Interlaced video path, or - for standard input")
+    d.add_argument("--output", required=True, help="Output video path, or - for standard output (the input's format)")
+    d.add_argument("--order", default="auto", choices=("auto", "tff", "bff"),
+                   help="Field order: tff (even rows first in time), bff, or auto (the Y4M header's It / Ib)")
+    d.add_argument("--rate", default="field", choices=("field", "frame"),
+                   help="field: one frame per field, the frame rate doubles (default); frame: one per frame")
+    d.add_argument("--method", default="adaptive", choices=("adaptive", "bob"),
+                   help="adaptive: motion-adaptive with an edge-directed spatial estimate (default); bob: the average of "
+                        "the rows above and below")
+    d.add_argument("--no-spatial-check", action="store_true",
+                   help="Leave out the spatial interlacing check of the adaptive method (static areas then pass through "
+                        "exactly)")
+    d.add_argument("--device", default="auto", help="Device to use (cuda/auto)")
+    d.add_argument("--chunk-frames", type=int, default=32, help="Source frames per step (memory is bounded by it)")
+    d.add_argument("--src-fps", type=_fps, default=None,
+                   help="Source frame rate as n or n/d, for the Y4M header of the result (default: the input header's)")
+    d.add_argument("--raw", default=None, choices=RAW_CHOICES,
+                   help="Headerless raw video in and out (tight frames, named as ffmpeg's -pix_fmt); needs --size and "
+                        "--order tff or bff")
+    d.add_argument("--packing", default=None, choices=PACKING_CHOICES,
+                   help="With --raw yuv422p10le: the frames are packed on the wire as v210, y210le or p210le, in and out")
+    d.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
     return ap
 
 
 def parse_args(argv=None) -> argparse.Namespace:
     ap = parser()
     a = ap.parse_args(argv)
+    if a.command == "deinterlace":
+        if a.packing is not None and a.raw != "yuv422p10le":
+            ap.error("--packing says how yuv422p10le samples are packed on the wire: pass --raw yuv422p10le with it")
+        if a.raw is not None and a.size is None:
+            ap.error("--raw needs --size WIDTHxHEIGHT (raw video has no header)")
+        if a.raw is None and a.size is not None:
+            ap.error("--size describes --raw video")
+        if a.raw is not None and a.order == "auto":
+            ap.error("--raw video has no header to read the field order from: pass --order tff or --order bff")
+        return a
     if a.chunk_frames is None:
         a.chunk_frames = 4 * a.batch
     if a.command in ("evaluate", "video"):
@@ -341,9 +386,24 @@ def run_evaluate(a: argparse.Namespace) -> dict:
     return res
 
 
+def run_deinterlace(a: argparse.Namespace) -> int:
+    from . import deinterlace
+    device = torch.device("cuda" if a.device in ("auto", None) else a.device)
+    src = sys.stdin.buffer if a.input == "-" else a.input
+    dst = sys.stdout.buffer if a.output == "-" else a.output
+    n = deinterlace.deinterlace_video(src, dst, order=a.order, rate=a.rate, method=a.method,
+                                      spatial_check=not a.no_spatial_check, chunk_frames=a.chunk_frames, raw=a.raw,
+                                      width=a.size[0] if a.size else None, height=a.size[1] if a.size else None,
+                                      src_fps=a.src_fps, packing=a.packing, device=device)
+    print(f"wrote {n} frames", file=sys.stderr)
+    return n
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
-    if a.command == "video":
+    if a.command == "deinterlace":
+        run_deinterlace(a)
+    elif a.command == "video":
         run_video(a)
     elif a.command == "evaluate":
         run_evaluate(a)

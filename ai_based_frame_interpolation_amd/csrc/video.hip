@@ -1,10 +1,11 @@
 // video.hip -- operations on frame sequences: scene cuts and repeated frames (scene.hip.h), frame-rate conversion
-// (retime.hip.h) and resizing frame planes (resize.hip.h).
+// (retime.hip.h), resizing frame planes (resize.hip.h) and deinterlacing (deinterlace.hip.h).
 #include "fiunet_internal.h"
 #include "plane_check.h"
 #include "scene.hip.h"
 #include "retime.hip.h"
 #include "resize.hip.h"
+#include "deinterlace.hip.h"
 
 using namespace fiunet;
 
@@ -305,6 +306,91 @@ int fiunet_resize_planes_p10(const uint16_t* src, const fiunet_resize_plane* src
                              const fiunet_resize_plane* dst_planes, int n_planes, int n_frames, void* stream)
 {
     return resize_planes(src, src_planes, dst, dst_planes, n_planes, n_frames, stream);
+}
+
+// ---- deinterlacing (csrc/deinterlace.hip.h) -------------------------------------------------------------
+extern "C++" {
+template <typename T, int V>
+static void deinterlace_launch(const T* src, T* dst, const DeintPlane& P, dim3 grid, int n_src, int first, int bff, int field,
+                               int method, bool spatial, hipStream_t stream)
+{
+    if (method == FIUNET_DEINT_BOB)
+        hipLaunchKernelGGL((deinterlace_kernel<T, V, 0, false>), grid, dim3(kDeintBlock), 0, stream, src, dst, P, n_src, first, bff, field);
+    else if (spatial)
+        hipLaunchKernelGGL((deinterlace_kernel<T, V, 1, true>), grid, dim3(kDeintBlock), 0, stream, src, dst, P, n_src, first, bff, field);
+    else
+        hipLaunchKernelGGL((deinterlace_kernel<T, V, 1, false>), grid, dim3(kDeintBlock), 0, stream, src, dst, P, n_src, first, bff, field);
+}
+
+template <typename T>
+static int deinterlace(const T* src, int n_src, const fiunet_resize_plane* sp, T* dst, const fiunet_resize_plane* dp,
+                       int n_planes, int first, int n_frames, int order, int rate, int method_flags, void* stream)
+{
+    if (!src || !dst || !sp || !dp) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (((uintptr_t)src | (uintptr_t)dst) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
+    if (n_planes < 1 || n_planes > kResizeMaxPlanes) return fail(FIUNET_ERR_INVALID_ARG, "n_planes must be 1..4");
+    if (order != FIUNET_DEINT_TFF && order != FIUNET_DEINT_BFF) return fail(FIUNET_ERR_INVALID_ARG, "order must be FIUNET_DEINT_TFF or FIUNET_DEINT_BFF");
+    if (rate != FIUNET_DEINT_FIELD_RATE && rate != FIUNET_DEINT_FRAME_RATE)
+        return fail(FIUNET_ERR_INVALID_ARG, "rate must be FIUNET_DEINT_FIELD_RATE or FIUNET_DEINT_FRAME_RATE");
+    const int method = method_flags & 0xff;
+    if ((method != FIUNET_DEINT_ADAPTIVE && method != FIUNET_DEINT_BOB) || (method_flags & ~(0xff | FIUNET_DEINT_NO_SPATIAL_CHECK)))
+        return fail(FIUNET_ERR_INVALID_ARG, "method_flags: FIUNET_DEINT_ADAPTIVE or FIUNET_DEINT_BOB, with or without FIUNET_DEINT_NO_SPATIAL_CHECK");
+    if (n_src < 0 || first < 0 || n_frames < 0 || first > n_src || n_frames > n_src - first)
+        return fail(FIUNET_ERR_INVALID_ARG, "first and n_frames must name frames of the window of n_src");
+    const int per = rate == FIUNET_DEINT_FIELD_RATE ? 2 : 1;
+    if (n_frames > kDeintMaxOut / per) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 output frames in one call");
+    const int n_out = n_frames * per;
+    uintptr_t lo[2] = {UINTPTR_MAX, UINTPTR_MAX}, hi[2] = {0, 0};   // [0]: n_src source frames, [1]: n_out of dst
+    for (int i = 0; i < n_planes; ++i) {
+        for (int d = 0; d < 2; ++d) {
+            const fiunet_resize_plane& p = d ? dp[i] : sp[i];
+            if (const char* why = plane_check(p, kResizeMaxSize)) return fail(FIUNET_ERR_INVALID_ARG, why);
+            if (p.filter != 0) return fail(FIUNET_ERR_INVALID_ARG, "a plane's filter must be 0");
+            if (p.h < 2) return fail(FIUNET_ERR_INVALID_ARG, "a plane needs two rows or more: h < 2");
+            const int n = d ? n_out : n_src;
+            if (n == 0) continue;
+            uintptr_t p0, p1;
+            if (!plane_range(d ? (const void*)dst : src, sizeof(T), p, n, &p0, &p1))
+                return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+            lo[d] = std::min(lo[d], p0), hi[d] = std::max(hi[d], p1);
+        }
+        if (sp[i].h != dp[i].h || sp[i].w != dp[i].w)
+            return fail(FIUNET_ERR_INVALID_ARG, "a source plane and its destination plane differ in size");
+    }
+    if (n_frames == 0) return FIUNET_OK;
+    if (ranges_overlap(lo[0], hi[0], lo[1], hi[1])) return fail(FIUNET_ERR_INVALID_ARG, "source and destination overlap");
+    const bool spatial = !(method_flags & FIUNET_DEINT_NO_SPATIAL_CHECK);
+    constexpr int V = 16 / (int)sizeof(T);
+    for (int i = 0; i < n_planes; ++i) {
+        const DeintPlane P = {sp[i].offset, sp[i].pitch, sp[i].frame_stride, dp[i].offset, dp[i].pitch, dp[i].frame_stride,
+                              sp[i].h, sp[i].w, sp[i].step, dp[i].step};
+        // the vector path: step 1 and every row of every frame 16-byte aligned, on both sides
+        const size_t bytes = ((uintptr_t)(src + P.src_off) | (uintptr_t)(dst + P.dst_off) |
+                              (P.src_pitch | P.src_fs | P.dst_pitch | P.dst_fs) * sizeof(T));
+        const bool vec = P.sstep == 1 && P.dstep == 1 && bytes % 16 == 0;
+        const unsigned per_lane = vec ? V : 1;
+        const unsigned lanes = ((unsigned)P.w + per_lane - 1) / per_lane;
+        const dim3 grid((lanes + 63) / 64, std::min(((unsigned)(P.h + 1) / 2 + 3) / 4, kDeintMaxRowGroups), (unsigned)n_out);
+        if (vec) deinterlace_launch<T, V>(src, dst, P, grid, n_src, first, order == FIUNET_DEINT_BFF, per == 2, method, spatial, (hipStream_t)stream);
+        else deinterlace_launch<T, 1>(src, dst, P, grid, n_src, first, order == FIUNET_DEINT_BFF, per == 2, method, spatial, (hipStream_t)stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_deinterlace_u8(const uint8_t* src, int n_src, const fiunet_resize_plane* src_planes, uint8_t* dst,
+                          const fiunet_resize_plane* dst_planes, int n_planes, int first, int n_frames, int order, int rate,
+                          int method_flags, void* stream)
+{
+    return deinterlace(src, n_src, src_planes, dst, dst_planes, n_planes, first, n_frames, order, rate, method_flags, stream);
+}
+
+int fiunet_deinterlace_p10(const uint16_t* src, int n_src, const fiunet_resize_plane* src_planes, uint16_t* dst,
+                           const fiunet_resize_plane* dst_planes, int n_planes, int first, int n_frames, int order, int rate,
+                           int method_flags, void* stream)
+{
+    return deinterlace(src, n_src, src_planes, dst, dst_planes, n_planes, first, n_frames, order, rate, method_flags, stream);
 }
 
 }  // extern "C"

@@ -469,6 +469,16 @@ def y4m_colourspace(path: str) -> str:
     return "420jpeg"
 
 
+def y4m_interlace(header_line: bytes):
+    """The `I` token of a Y4M stream header line: "p" (progressive), "t" (interlaced, top field first), "b" (bottom
+    field first), "m" (mixed), or None where the header has none; any other text as it stands (the readers never
+    refused one).  (The header dicts of the readers do not carry it: `Y4MReader.interlace` does.)"""
+    for tok in header_line.rstrip(b"\n").split(b" ")[1:]:
+        if tok[:1] == b"I":
+            return tok[1:].decode(errors="replace")
+    return None
+
+
 def _y4m_header_line(w: int, h: int, fps, cs: str, colour_range, bits: int) -> bytes:
     """The stream header `write_y4m` (bits 8) / `write_y4m_p10` (bits 10) write: 10-bit layouts other than mono carry
     ffmpeg's `XYSCSS=` token; `XCOLORRANGE=` only when colour_range is given."""
@@ -521,6 +531,7 @@ class Y4MReader:
             if not line.endswith(b"\n"):
                 raise ValueError("Y4M: truncated stream header")
             self.header = _y4m_stream_header(line, bits)
+            self.interlace = y4m_interlace(line)   # (not a key of `header`)
         except BaseException:
             self.close()
             raise

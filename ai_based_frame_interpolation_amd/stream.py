@@ -93,6 +93,7 @@ import numpy as np
 import torch
 
 from . import chroma as _chroma
+from . import deinterlace as _deinterlace
 from . import colour, imageio_lite, packed, scene, wire10
 from . import resize as _resize
 from . import retime as _retime
@@ -494,6 +495,7 @@ def _open_y4m(model, src, npy_out: bool, batch, matrix, siting, size, rfilter, c
                          "counted before it is read: write Y4M, or read the stream from a regular file")
     reader = imageio_lite.Y4MReader(src)
     try:
+        _deinterlace.interlaced_warning(reader.interlace, "video")   # (the frames go on as they are)
         hdr = reader.header
         rs, lay = _resized(("y4m", hdr["colourspace"]), hdr["height"], hdr["width"], size, rfilter)
         if size is not None:   # everything from here on is a clip of the new size; the reader keeps the source's

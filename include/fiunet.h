@@ -48,7 +48,8 @@ extern "C" {
                                      motion-compensated resampling (fiunet_warp_entry, fiunet_warp_table_u8,
                                      fiunet_warp_table_p10); v8 also, added the same way: motion-guided chroma
                                      (fiunet_chroma_pick_u8, fiunet_chroma_pick_p10, fiunet_chroma_fill_u8,
-                                     fiunet_chroma_fill_p10) */
+                                     fiunet_chroma_fill_p10); v8 also, added the same way: deinterlacing
+                                     (fiunet_deinterlace_u8, fiunet_deinterlace_p10) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -760,6 +761,52 @@ int fiunet_chroma_fill_p10(const uint16_t* a, const fiunet_resize_plane* a_plane
                            const fiunet_resize_plane* b_planes, const float* field, int field_h, int field_w,
                            const uint8_t* pick, int sy, int sx, int n, uint16_t* out,
                            const fiunet_resize_plane* out_planes, void* stream);
+
+/* Deinterlacing (added without a version bump: nothing existing changed).  An interlaced frame holds two
+ * fields taken half a frame period apart: FIUNET_DEINT_TFF, the even rows come first in time; FIUNET_DEINT_BFF, the odd
+ * rows.  Field i (0: the first in time) of a frame keeps the rows of parity p = (order == BFF) ^ i, which are copied; the
+ * rows of the other parity are filled in.  The definition is the project's own, in integers, in the spirit of yadif and
+ * not pinned against ffmpeg; tests/deinterlace_ref.py states it in numpy and the kernels equal it bit for bit.  With
+ * cur = F[t], prev = F[t - 1], next = F[t + 1], (prev2, next2) = (prev, cur) for i == 0 and (cur, next) for i == 1,
+ * ym = y - 1 (y + 1 at y == 0), yp = y + 1 (y - 1 at y == h - 1), all in int32:
+ *   c = cur[ym][x], e = cur[yp][x], pred = (c + e) >> 1                                   FIUNET_DEINT_BOB writes pred
+ *   d = (prev2[y][x] + next2[y][x]) >> 1, t0 = |prev2[y][x] - next2[y][x]|,
+ *   t1 = (|prev[ym][x] - c| + |prev[yp][x] - e|) >> 1, t2 the same with next, diff = max(t0 >> 1, t1, t2)
+ *   where 3 <= x < w - 3: S(j) = sum over k = -1, 0, 1 of |cur[ym][x + k + j] - cur[yp][x + k - j]|, score = S(0) - 1;
+ *     if S(-1) < score: score = S(-1), pred = (cur[ym][x - 1] + cur[yp][x + 1]) >> 1, and only then j = -2 the same way;
+ *     then j = +1 and, if it was taken, j = +2, against the score as it stands
+ *   unless FIUNET_DEINT_NO_SPATIAL_CHECK, where 2 <= y < h - 2: b = (prev2[y - 2][x] + next2[y - 2][x]) >> 1, f the same
+ *     at y + 2, mx = max(d - e, d - c, min(b - c, f - e)), mn = min(d - e, d - c, max(b - c, f - e)),
+ *     diff = max(diff, mn, -mx)
+ *   out = min(max(pred, d - diff), d + diff)
+ * A result lies between the smallest and the largest input sample: 16-bit words are neither masked nor clamped.
+ * `src` is a window of n_src frames; frames first .. first + n_frames - 1 of it are deinterlaced, and their neighbours
+ * t - 1 and t + 1 come from the window, clamped to 0 .. n_src - 1: a streaming caller hands over one context frame either
+ * side, and at the ends of a clip the clamp is the definition itself.  FIUNET_DEINT_FIELD_RATE: dst receives 2 * n_frames
+ * frames, frame 2 * k + i from field i of window frame first + k; FIUNET_DEINT_FRAME_RATE: n_frames frames, each from
+ * field 0.  method_flags: FIUNET_DEINT_ADAPTIVE or FIUNET_DEINT_BOB, or-ed with FIUNET_DEINT_NO_SPATIAL_CHECK or not.
+ * Planes: 1..4 fiunet_resize_plane pairs (HOST memory, read during the call; filter 0; step 1..4), plane i of src_planes
+ * in `src` and of dst_planes in `dst`, of one h x w; every plane is filtered on its own with the same p, so the U and V of
+ * NV12, the bytes of uyvy422 and packed RGB are filtered where they lie.  Samples of dst outside its planes are never
+ * written.  Step-1 planes whose bases, pitches and frame strides are multiples of 16 bytes on both sides take a path of
+ * 16-byte accesses; every other plane is computed sample by sample, to the same bits.
+ * Asynchronous on `stream`, no allocation, no synchronisation, capturable; n_frames == 0 is a no-op.
+ * FIUNET_ERR_INVALID_ARG, before any launch and before a pointer is used: a NULL argument, a uint16_t pointer that is not
+ * 2-byte aligned, n_planes outside 1..4, an unknown order, rate or method_flags, first or n_frames outside the window,
+ * more than 65535 output frames, a plane that breaks fiunet_resize_planes' rules or has filter != 0 or h < 2, a plane pair
+ * of different h x w, a plane range that leaves the address space, dst's planes overlapping src's. */
+enum fiunet_deint {
+    FIUNET_DEINT_TFF = 0, FIUNET_DEINT_BFF = 1,                  /* order */
+    FIUNET_DEINT_FIELD_RATE = 0, FIUNET_DEINT_FRAME_RATE = 1,    /* rate */
+    FIUNET_DEINT_ADAPTIVE = 0, FIUNET_DEINT_BOB = 1,             /* method_flags: the method ... */
+    FIUNET_DEINT_NO_SPATIAL_CHECK = 256                          /* ... and this flag */
+};
+int fiunet_deinterlace_u8(const uint8_t* src, int n_src, const fiunet_resize_plane* src_planes, uint8_t* dst,
+                          const fiunet_resize_plane* dst_planes, int n_planes, int first, int n_frames, int order, int rate,
+                          int method_flags, void* stream);
+int fiunet_deinterlace_p10(const uint16_t* src, int n_src, const fiunet_resize_plane* src_planes, uint16_t* dst,
+                           const fiunet_resize_plane* dst_planes, int n_planes, int first, int n_frames, int order, int rate,
+                           int method_flags, void* stream);
 
 /* The training loss' SSIM on device: SSIMLoss._ssim (model/train.py:37-56) - the
  * window_size x window_size Gaussian window (sigma 1.5, normalised as at train.py:27-35) applied as a
