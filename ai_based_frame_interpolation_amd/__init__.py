@@ -15,7 +15,7 @@ from .colour import (  # noqa: F401
     YUV_FORMATS, rgb_to_yuv, yuv_frame_samples, yuv_to_rgb,
 )
 from .packed import PackedLayout  # noqa: F401
-from . import chroma, colour, deinterlace, evaluation, holdout, layout, metrics, optical_flow, packed, resize, retime, scene, serving, stream, synthetic, tiling, transport, video, wire10  # noqa: F401
+from . import chroma, colour, deinterlace, evaluation, holdout, ivtc, layout, metrics, optical_flow, packed, resize, retime, scene, serving, stream, synthetic, tiling, transport, video, wire10  # noqa: F401
 
 __all__ = [
     "FrameInterpolationUNet", "GraphedForward", "UNet", "count_parameters", "FrameInterpolator",
@@ -29,5 +29,5 @@ __all__ = [
     "SurfaceLayout", "nv12_to_rgb", "rgb_to_nv12", "p010_to_rgb", "rgb_to_p010", "interpolate_sequence_nv12",
     "packed", "PackedLayout", "interpolate_sequence_rgb_packed", "holdout",
     "YUV_FORMATS", "yuv_to_rgb", "rgb_to_yuv", "yuv_frame_samples", "interpolate_sequence_yuv", "resize",
-    "wire10", "layout", "chroma", "deinterlace",
+    "wire10", "layout", "chroma", "deinterlace", "ivtc",
 ]

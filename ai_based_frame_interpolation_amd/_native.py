@@ -64,6 +64,8 @@ SYMBOLS = (
     "fiunet_chroma_pick_u8", "fiunet_chroma_pick_p10", "fiunet_chroma_fill_u8", "fiunet_chroma_fill_p10",
     # deinterlacing
     "fiunet_deinterlace_u8", "fiunet_deinterlace_p10",
+    # inverse telecine
+    "fiunet_field_match_u8", "fiunet_field_match_p10", "fiunet_field_weave_u8", "fiunet_field_weave_p10",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -237,6 +239,10 @@ def lib() -> ctypes.CDLL:
     L.fiunet_chroma_fill_p10.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, vp, vp, vp]
     L.fiunet_deinterlace_u8.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
     L.fiunet_deinterlace_p10.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+    L.fiunet_field_match_u8.argtypes = [vp, ci, vp, ci, ci, ci, ci, vp, vp]
+    L.fiunet_field_match_p10.argtypes = [vp, ci, vp, ci, ci, ci, ci, vp, vp]
+    L.fiunet_field_weave_u8.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, ci, vp]
+    L.fiunet_field_weave_p10.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, ci, vp]
     L.fiunet_nv12_to_rgb_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_rgb_to_nv12_u8.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
     L.fiunet_p010_to_rgb_p10.argtypes = [vp, vp, vp, ci, ci, ci, cu, vp]
@@ -980,3 +986,61 @@ def deinterlace(src: "torch.Tensor", n_src: int, src_planes, dst: "torch.Tensor"
     check(fn(src.data_ptr(), n_src, resize_plane_array(src_planes), dst.data_ptr(), resize_plane_array(dst_planes),
              len(src_planes), first, n_frames, order, rate, method_flags, _stream(src, stream)),
           "fiunet_deinterlace_" + ("p10" if bits == 10 else "u8"))
+
+
+class WeaveEntry(ctypes.Structure):
+    """include/fiunet.h: fiunet_weave_entry (an output frame: the rows of the kept parity from window frame `keep`, the
+    others from `other`)."""
+    _fields_ = [("keep", ctypes.c_uint32), ("other", ctypes.c_uint32)]
+
+
+def weave_entries(entries):
+    """A sequence of (keep, other) int pairs -> the C array of fiunet_weave_entry (None when empty).  ValueError on a value
+    that does not fit 32 bits unsigned (the library checks the rest)."""
+    n = len(entries)
+    if not n:
+        return None
+    arr = (WeaveEntry * n)()
+    for k, (keep, other) in enumerate(entries):
+        if not (0 <= keep < 1 << 32 and 0 <= other < 1 << 32):
+            raise ValueError(f"entry {k} = {(keep, other)} does not fit 32 bits unsigned")
+        arr[k] = WeaveEntry(keep, other)
+    return arr
+
+
+def field_match(src: "torch.Tensor", n_src: int, plane, first: int, n_frames: int, order: int, threshold: int,
+                scores: "torch.Tensor", bits: int, stream=None) -> None:
+    """fiunet_field_match_u8 / fiunet_field_match_p10: MAX-ACCUMULATES the comb scores (p, c, n) of frames first .. first +
+    n_frames - 1 of the window of n_src frames in the dense buffer `src`, on one plane (offset, h, w, pitch, step,
+    frame_stride) in samples from the tensor's first element, into the contiguous int32 `scores` [n_frames, 3] (int32 on
+    the torch side: a score is at most 1024).  ValueError, before the call, where a well-formed plane reaches past `src`."""
+    plane = tuple(int(v) for v in plane)
+    if not src.is_contiguous():
+        raise ValueError("src must be a dense buffer (the plane carries the pitch)")
+    _planes_fit("src plane", [plane], n_src, src.numel())
+    if scores.dtype != torch.int32 or tuple(scores.shape) != (n_frames, 3) or not scores.is_contiguous():
+        raise ValueError(f"scores: expected a contiguous int32 [{n_frames}, 3] tensor, got {scores.dtype} {tuple(scores.shape)}")
+    fn = lib().fiunet_field_match_p10 if bits == 10 else lib().fiunet_field_match_u8
+    check(fn(src.data_ptr(), n_src, resize_plane_array([plane]), first, n_frames, order, threshold, scores.data_ptr(),
+             _stream(src, stream)), "fiunet_field_match_" + ("p10" if bits == 10 else "u8"))
+
+
+def field_weave(src: "torch.Tensor", n_src: int, src_planes, dst: "torch.Tensor", dst_planes, entries, parity: int,
+                bits: int, stream=None) -> None:
+    """fiunet_field_weave_u8 / fiunet_field_weave_p10: len(entries) frames of `dst`, frame j with the rows of parity
+    `parity` from frame keep_j of the window of n_src frames in the dense buffer `src` and the other rows from frame
+    other_j; entries: (keep, other) pairs, read on the host during the call; 1..4 planes (offset, h, w, pitch, step,
+    frame_stride) in samples from each tensor's first element.  ValueError, before the call, where well-formed planes reach
+    past either tensor."""
+    src_planes, dst_planes = [tuple(int(v) for v in p) for p in src_planes], [tuple(int(v) for v in p) for p in dst_planes]
+    entries = [tuple(int(v) for v in e) for e in entries]
+    if len(src_planes) != len(dst_planes):
+        raise ValueError(f"{len(src_planes)} source planes for {len(dst_planes)} destination planes")
+    for name, t, planes, n in (("src", src, src_planes, n_src), ("dst", dst, dst_planes, len(entries))):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be a dense buffer (the planes carry the pitches)")
+        _planes_fit(name + " planes", planes, n, t.numel())
+    fn = lib().fiunet_field_weave_p10 if bits == 10 else lib().fiunet_field_weave_u8
+    check(fn(src.data_ptr(), n_src, resize_plane_array(src_planes), dst.data_ptr(), resize_plane_array(dst_planes),
+             len(src_planes), weave_entries(entries), len(entries), parity, _stream(src, stream)),
+          "fiunet_field_weave_" + ("p10" if bits == 10 else "u8"))

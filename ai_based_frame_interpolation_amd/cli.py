@@ -81,6 +81,18 @@ they are:
 --order auto (the default) reads `It` / `Ib` off the Y4M header; --rate field (the default) writes one frame per field
 at twice the rate; --raw / --size / --packing take headerless video as `video` does, with --order tff or bff.
 
+`ivtc` undoes 2:3 pulldown (ivtc.py): hard-telecined film - 24 fps carried as 29.97 fps interlaced video -
+becomes its film frames again, byte for byte, at 23.976 fps, which `video --fps` then takes to any rate.  It needs no
+model, takes `deinterlace`'s --order / --raw / --size / --packing / --src-fps / --chunk-frames, and prints what it matched,
+flagged and dropped to standard error:
+
+    ffmpeg -i telecined.vob -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli ivtc --input - \\
+        --output - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - --model best_model.pth \\
+        --fps 60000/1001 | ffmpeg -f yuv4mpegpipe -i - out.mkv
+
+--no-decimate writes every matched frame at the source rate; --cycle, --comb-threshold, --combed and --fallback are the
+parameters of the definition.
+
 `--resize WIDTHxHEIGHT` on either command resizes every frame on the GPU right after its upload (resize.py, DESIGN.md
 3.3q): `video` then writes a clip of that size, `evaluate` scores the checkpoint at that size - 256x256 is what the
 reference trains and evaluates at - and says so in its table.  --size stays the size of the --raw source.
@@ -270,13 +282,38 @@ def parser() -> argparse.ArgumentParser:
     d.add_argument("--packing", default=None, choices=PACKING_CHOICES,
                    help="With --raw yuv422p10le: the frames are packed on the wire as v210, y210le or p210le, in and out")
     d.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
+    t = sub.add_parser("ivtc", help="Inverse telecine: hard-telecined film (2:3 pulldown) back to its film frames (Y4M or "
+                                    "--raw; '-' is stdin / stdout; needs no model)")
+    t.add_argument("--input", required=True, help="Telecined video path, or - for standard input")
+    t.add_argument("--output", required=True, help="Output video path, or - for standard output (the input's format)")
+    t.add_argument("--order", default="auto", choices=("auto", "tff", "bff"),
+                   help="Field order: tff (even rows first in time), bff, or auto (the Y4M header's It / Ib)")
+    t.add_argument("--no-decimate", action="store_true",
+                   help="Match the fields only: write every frame, at the source rate")
+    t.add_argument("--cycle", type=int, default=5, help="Frames per decimation cycle: one of them is dropped (default 5)")
+    t.add_argument("--comb-threshold", type=int, default=None,
+                   help="T of the comb test (u - m) * (d - m) > T * T (default: 12 at 8 bits, 48 at 10)")
+    t.add_argument("--combed", type=int, default=48,
+                   help="Largest count of combed samples in a 16 x 64 block that a matched frame may have (default 48)")
+    t.add_argument("--fallback", default="deinterlace", choices=("deinterlace", "keep"),
+                   help="A frame no pairing cleans: deinterlace it (default) or keep the best weave")
+    t.add_argument("--device", default="auto", help="Device to use (cuda/auto)")
+    t.add_argument("--chunk-frames", type=int, default=32, help="Source frames per step (memory is bounded by it)")
+    t.add_argument("--src-fps", type=_fps, default=None,
+                   help="Source frame rate as n or n/d, for the Y4M header of the result (default: the input header's)")
+    t.add_argument("--raw", default=None, choices=RAW_CHOICES,
+                   help="Headerless raw video in and out (tight frames, named as ffmpeg's -pix_fmt); needs --size and "
+                        "--order tff or bff")
+    t.add_argument("--packing", default=None, choices=PACKING_CHOICES,
+                   help="With --raw yuv422p10le: the frames are packed on the wire as v210, y210le or p210le, in and out")
+    t.add_argument("--size", type=_size, default=None, help="Frame size of --raw video as WIDTHxHEIGHT")
     return ap
 
 
 def parse_args(argv=None) -> argparse.Namespace:
     ap = parser()
     a = ap.parse_args(argv)
-    if a.command == "deinterlace":
+    if a.command in ("deinterlace", "ivtc"):
         if a.packing is not None and a.raw != "yuv422p10le":
             ap.error("--packing says how yuv422p10le samples are packed on the wire: pass --raw yuv422p10le with it")
         if a.raw is not None and a.size is None:
@@ -399,10 +436,29 @@ def run_deinterlace(a: argparse.Namespace) -> int:
     return n
 
 
+def run_ivtc(a: argparse.Namespace) -> dict:
+    from . import ivtc
+    device = torch.device("cuda" if a.device in ("auto", None) else a.device)
+    src = sys.stdin.buffer if a.input == "-" else a.input
+    dst = sys.stdout.buffer if a.output == "-" else a.output
+    rep = ivtc.ivtc_video(src, dst, order=a.order, decimate=not a.no_decimate, cycle=a.cycle, threshold=a.comb_threshold,
+                          combed=a.combed, fallback=a.fallback, chunk_frames=a.chunk_frames, raw=a.raw,
+                          width=a.size[0] if a.size else None, height=a.size[1] if a.size else None, src_fps=a.src_fps,
+                          packing=a.packing, device=device)
+    m = rep["matches"]
+    print(f"matched {rep['frames_in']} frames: p {m['p']}, c {m['c']}, n {m['n']}; combed {len(rep['combed'])}"
+          + (f" (frames {', '.join(map(str, rep['combed']))})" if rep["combed"] else "")
+          + f"; dropped {len(rep['dropped'])}", file=sys.stderr)
+    print(f"wrote {rep['frames_out']} frames", file=sys.stderr)
+    return rep
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
     if a.command == "deinterlace":
         run_deinterlace(a)
+    elif a.command == "ivtc":
+        run_ivtc(a)
     elif a.command == "video":
         run_video(a)
     elif a.command == "evaluate":

@@ -6,6 +6,7 @@
 #include "retime.hip.h"
 #include "resize.hip.h"
 #include "deinterlace.hip.h"
+#include "ivtc.hip.h"
 
 using namespace fiunet;
 
@@ -391,6 +392,127 @@ int fiunet_deinterlace_p10(const uint16_t* src, int n_src, const fiunet_resize_p
                            int method_flags, void* stream)
 {
     return deinterlace(src, n_src, src_planes, dst, dst_planes, n_planes, first, n_frames, order, rate, method_flags, stream);
+}
+
+// ---- inverse telecine (csrc/ivtc.hip.h) -----------------------------------------------------------------
+static_assert(sizeof(fiunet_weave_entry) == 8, "entry layout");
+
+extern "C++" {
+template <typename T>
+static int field_match(const T* src, int n_src, const fiunet_resize_plane* plane, int first, int n_frames, int order,
+                       int threshold, uint32_t* scores, void* stream)
+{
+    if (!src || !plane || !scores) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if ((uintptr_t)src % sizeof(T) || (uintptr_t)scores % sizeof(uint32_t)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
+    if (order != FIUNET_DEINT_TFF && order != FIUNET_DEINT_BFF) return fail(FIUNET_ERR_INVALID_ARG, "order must be FIUNET_DEINT_TFF or FIUNET_DEINT_BFF");
+    if (threshold < 0 || threshold > kMatchMaxThreshold) return fail(FIUNET_ERR_INVALID_ARG, "threshold outside 0..1023");
+    if (n_src < 0 || first < 0 || n_frames < 0 || first > n_src || n_frames > n_src - first)
+        return fail(FIUNET_ERR_INVALID_ARG, "first and n_frames must name frames of the window of n_src");
+    if (n_frames > kMatchMaxFrames) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 frames in one call");
+    if (const char* why = plane_check(*plane, kResizeMaxSize)) return fail(FIUNET_ERR_INVALID_ARG, why);
+    if (plane->filter != 0) return fail(FIUNET_ERR_INVALID_ARG, "a plane's filter must be 0");
+    if (plane->h < 3) return fail(FIUNET_ERR_INVALID_ARG, "the comb score needs three rows or more: h < 3");
+    if (n_frames == 0) return FIUNET_OK;
+    uintptr_t s0, s1;
+    if (!plane_range(src, sizeof(T), *plane, n_src, &s0, &s1)) return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+    const uintptr_t d0 = (uintptr_t)scores;
+    if (ranges_overlap(s0, s1, d0, d0 + (size_t)n_frames * 3 * sizeof(uint32_t)))
+        return fail(FIUNET_ERR_INVALID_ARG, "source and destination overlap");
+    const MatchPlane P = {plane->offset, plane->pitch, plane->frame_stride, plane->h, plane->w, plane->step};
+    constexpr int V = 16 / (int)sizeof(T);
+    // the vector path: step 1 and every row of every frame 16-byte aligned
+    const bool vec = P.step == 1 && ((uintptr_t)(src + P.off) | (P.pitch | P.fs) * sizeof(T)) % 16 == 0;
+    const unsigned per_lane = vec ? V : 1;
+    const unsigned lanes = ((unsigned)P.w + per_lane - 1) / per_lane;
+    const unsigned block_rows = ((unsigned)P.h + kMatchRows - 1) / kMatchRows;
+    const dim3 grid((lanes + 63) / 64, std::min((block_rows + 3) / 4, kMatchMaxRowGroups), (unsigned)n_frames);
+    const int keep = order == FIUNET_DEINT_BFF, t2 = threshold * threshold;
+    if (vec) hipLaunchKernelGGL((field_match_kernel<T, V>), grid, dim3(kMatchBlock), 0, (hipStream_t)stream, src, P, n_src, first, keep, t2, scores);
+    else hipLaunchKernelGGL((field_match_kernel<T, 1>), grid, dim3(kMatchBlock), 0, (hipStream_t)stream, src, P, n_src, first, keep, t2, scores);
+    HIP_TRY(hipGetLastError());
+    return FIUNET_OK;
+}
+
+template <typename T>
+static int field_weave(const T* src, int n_src, const fiunet_resize_plane* sp, T* dst, const fiunet_resize_plane* dp, int n_planes,
+                       const fiunet_weave_entry* entries, int n_out, int parity, void* stream)
+{
+    if (!src || !dst || !sp || !dp) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (((uintptr_t)src | (uintptr_t)dst) % sizeof(T)) return fail(FIUNET_ERR_INVALID_ARG, "misaligned pointer");
+    if (n_planes < 1 || n_planes > kWeaveMaxPlanes) return fail(FIUNET_ERR_INVALID_ARG, "n_planes must be 1..4");
+    if (parity != 0 && parity != 1) return fail(FIUNET_ERR_INVALID_ARG, "parity must be 0 (even rows) or 1 (odd rows)");
+    if (n_src < 0 || n_out < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
+    if (n_out > kWeaveMaxOut) return fail(FIUNET_ERR_INVALID_ARG, "more than 65535 output frames in one call");
+    if (n_out > 0 && !entries) return fail(FIUNET_ERR_INVALID_ARG, "NULL entries");
+    for (int k = 0; k < n_out; ++k)
+        if (std::max(entries[k].keep, entries[k].other) >= (uint32_t)n_src)
+            return fail(FIUNET_ERR_INVALID_ARG, "entry: a frame outside the window of n_src");
+    uintptr_t lo[2] = {UINTPTR_MAX, UINTPTR_MAX}, hi[2] = {0, 0};   // [0]: n_src source frames, [1]: n_out of dst
+    WeaveArgs base = {};
+    int rows_max = 0;
+    for (int i = 0; i < n_planes; ++i) {
+        for (int d = 0; d < 2; ++d) {
+            const fiunet_resize_plane& p = d ? dp[i] : sp[i];
+            if (const char* why = plane_check(p, kResizeMaxSize)) return fail(FIUNET_ERR_INVALID_ARG, why);
+            if (p.filter != 0) return fail(FIUNET_ERR_INVALID_ARG, "a plane's filter must be 0");
+            if (p.h < 2) return fail(FIUNET_ERR_INVALID_ARG, "a plane needs two rows or more: h < 2");
+            const int n = d ? n_out : n_src;
+            if (n == 0) continue;
+            uintptr_t p0, p1;
+            if (!plane_range(d ? (const void*)dst : src, sizeof(T), p, n, &p0, &p1))
+                return fail(FIUNET_ERR_INVALID_ARG, "a plane's frame stride is too large");
+            lo[d] = std::min(lo[d], p0), hi[d] = std::max(hi[d], p1);
+        }
+        if (sp[i].h != dp[i].h || sp[i].w != dp[i].w)
+            return fail(FIUNET_ERR_INVALID_ARG, "a source plane and its destination plane differ in size");
+        WeavePlane& P = base.p[i];
+        P = {sp[i].offset, sp[i].pitch, sp[i].frame_stride, dp[i].offset, dp[i].pitch, dp[i].frame_stride,
+             sp[i].h, sp[i].w, sp[i].step, dp[i].step, 0};
+        const size_t bytes = ((uintptr_t)(src + P.src_off) | (uintptr_t)(dst + P.dst_off) |
+                              (P.src_pitch | P.src_fs | P.dst_pitch | P.dst_fs) * sizeof(T));
+        P.vec = P.sstep == 1 && P.dstep == 1 && bytes % 16 == 0;
+        rows_max = std::max(rows_max, P.h);
+    }
+    if (n_out == 0) return FIUNET_OK;
+    if (ranges_overlap(lo[0], hi[0], lo[1], hi[1])) return fail(FIUNET_ERR_INVALID_ARG, "source and destination overlap");
+    const unsigned gx = std::min(((unsigned)rows_max + 3) / 4, kWeaveMaxRowGroups);
+    for (int k0 = 0; k0 < n_out; k0 += kWeaveMax) {
+        const int nk = std::min(n_out - k0, kWeaveMax);
+        WeaveArgs args = base;
+        for (int i = 0; i < n_planes; ++i) args.p[i].dst_off += (size_t)k0 * args.p[i].dst_fs;
+        for (int k = 0; k < nk; ++k) args.keep[k] = entries[k0 + k].keep, args.other[k] = entries[k0 + k].other;
+        hipLaunchKernelGGL(field_weave_kernel<T>, dim3(gx, (unsigned)n_planes, (unsigned)nk), dim3(kWeaveBlock), 0,
+                           (hipStream_t)stream, src, dst, args, parity);
+        HIP_TRY(hipGetLastError());
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_field_match_u8(const uint8_t* src, int n_src, const fiunet_resize_plane* plane, int first, int n_frames, int order,
+                          int threshold, uint32_t* scores, void* stream)
+{
+    return field_match(src, n_src, plane, first, n_frames, order, threshold, scores, stream);
+}
+
+int fiunet_field_match_p10(const uint16_t* src, int n_src, const fiunet_resize_plane* plane, int first, int n_frames, int order,
+                           int threshold, uint32_t* scores, void* stream)
+{
+    return field_match(src, n_src, plane, first, n_frames, order, threshold, scores, stream);
+}
+
+int fiunet_field_weave_u8(const uint8_t* src, int n_src, const fiunet_resize_plane* src_planes, uint8_t* dst,
+                          const fiunet_resize_plane* dst_planes, int n_planes, const fiunet_weave_entry* entries, int n_out,
+                          int parity, void* stream)
+{
+    return field_weave(src, n_src, src_planes, dst, dst_planes, n_planes, entries, n_out, parity, stream);
+}
+
+int fiunet_field_weave_p10(const uint16_t* src, int n_src, const fiunet_resize_plane* src_planes, uint16_t* dst,
+                           const fiunet_resize_plane* dst_planes, int n_planes, const fiunet_weave_entry* entries, int n_out,
+                           int parity, void* stream)
+{
+    return field_weave(src, n_src, src_planes, dst, dst_planes, n_planes, entries, n_out, parity, stream);
 }
 
 }  // extern "C"

@@ -21,8 +21,8 @@ one instant per frame.
     ffmpeg -i 1080i.mxf -f yuv4mpegpipe - | python -m ai_based_frame_interpolation_amd.cli deinterlace --input - \\
         --output - | python -m ai_based_frame_interpolation_amd.cli video --input - --output - --model best_model.pth
 
-Out of scope: inverse telecine (`--dedup` re-times repeated frames behind it), bwdif / w3fdif taps, .npy input, a
-deinterlacer inside the `video` / `evaluate` engine (they warn where a Y4M header says interlaced, and pipe)."""
+Out of scope: bwdif / w3fdif taps, .npy input, a deinterlacer inside the `video` / `evaluate` engine (they warn where a
+Y4M header says interlaced, and pipe).  Hard-telecined film goes through `ivtc.py` instead, which matches its fields."""
 from __future__ import annotations
 
 import os
@@ -267,5 +267,8 @@ def deinterlace_video(src, dst, order: str = "auto", rate: str = "field", method
                 close()
 
 
-__all__ = ["ORDERS", "RATES", "METHODS", "deinterlace", "interlace", "deinterlace_video", "interlaced_warning", "order_of",
-           "double_rate", "check_options"]
+# the helpers other modules build on (ivtc.py), under public names
+choice, planes_of, bits_of, is_path, fps_pair = _choice, _planes_of, _bits_of, _is_path, _fps_pair
+
+__all__ = ["ORDERS", "RATES", "METHODS", "MAX_PLANES", "deinterlace", "interlace", "deinterlace_video", "interlaced_warning",
+           "order_of", "double_rate", "check_options", "choice", "planes_of", "bits_of", "is_path", "fps_pair"]

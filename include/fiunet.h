@@ -49,7 +49,9 @@ extern "C" {
                                      fiunet_warp_table_p10); v8 also, added the same way: motion-guided chroma
                                      (fiunet_chroma_pick_u8, fiunet_chroma_pick_p10, fiunet_chroma_fill_u8,
                                      fiunet_chroma_fill_p10); v8 also, added the same way: deinterlacing
-                                     (fiunet_deinterlace_u8, fiunet_deinterlace_p10) */
+                                     (fiunet_deinterlace_u8, fiunet_deinterlace_p10); v8 also, added the same way: inverse
+                                     telecine (fiunet_weave_entry, fiunet_field_match_u8, fiunet_field_match_p10,
+                                     fiunet_field_weave_u8, fiunet_field_weave_p10) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -807,6 +809,59 @@ int fiunet_deinterlace_u8(const uint8_t* src, int n_src, const fiunet_resize_pla
 int fiunet_deinterlace_p10(const uint16_t* src, int n_src, const fiunet_resize_plane* src_planes, uint16_t* dst,
                            const fiunet_resize_plane* dst_planes, int n_planes, int first, int n_frames, int order, int rate,
                            int method_flags, void* stream);
+
+/* Inverse telecine (added without a version bump: nothing existing changed).  Hard-telecined film - 24 fps
+ * carried as 29.97 fps interlaced video by 2:3 pulldown - holds every film frame whole, but two of every five video frames
+ * are woven from the fields of two different film frames.  The two kernels here score the three field pairings of a frame
+ * and weave the chosen fields; the choice and the decimation are host arithmetic on the scores (stated below for the
+ * record, done by the caller).  The definition is the project's own, in integers, in the spirit of ffmpeg's fieldmatch +
+ * decimate and not pinned against ffmpeg; tests/ivtc_ref.py states it in numpy and the kernels equal it bit for bit.
+ *   candidates  frame F[t] of field order `order` keeps the rows of its first field's parity k (FIUNET_DEINT_TFF: 0, the
+ *               even rows; FIUNET_DEINT_BFF: 1); the other rows come from F[t - 1] (candidate p), F[t] (c) or F[t + 1]
+ *               (n), t - 1 and t + 1 clamped to the window 0 .. n_src - 1; every plane of a frame uses the same choice
+ *   comb score  of a candidate W on an h x w plane, h >= 3, in int32: for 1 <= y <= h - 2 and every x, with u = W[y-1][x],
+ *               m = W[y][x], d = W[y+1][x] (10-bit words above 1023 read as 1023), the sample is combed iff
+ *               (u - m) * (d - m) > T * T, T = threshold in 0..1023 (the Python default: 12 at 8 bits, 48 at 10).  The
+ *               plane is cut into blocks of 16 rows x 64 columns aligned to its origin (row y in block row y / 16; the
+ *               last block row and column may be partial); the score is the LARGEST count of combed samples of a block,
+ *               so that a small moving object shows, as in fiunet_pair_peak_u8.  uint32, exact in any order
+ *   choice      scores (sp, sc, sn): c if sc <= min(sp, sn), else p if sp <= sn, else n (ties prefer c, then p); a frame
+ *               whose chosen score exceeds `combed` (default 48) is an orphan field at an edit or true interlaced video,
+ *               and is replaced by fiunet_deinterlace_u8 / _p10 of F[t] (frame rate, adaptive) or kept as woven
+ *   decimation  cycles of `cycle` (5) frames aligned to the clip's frame index; in every complete cycle the output frame
+ *               with the smallest fiunet_pair_peak_u8 / _p10 value against the output frame before it (the whole tight
+ *               frame; the clip's first frame counts as infinite; ties drop the earliest) is dropped, a trailing incomplete
+ *               cycle is kept whole, and the rate becomes rate * (cycle - 1) / cycle
+ * fiunet_field_match_u8 / _p10: `src` is a window of n_src frames; the three scores of frames first .. first + n_frames - 1
+ * on `plane` (ONE fiunet_resize_plane in HOST memory, read during the call; filter 0; step 1..4: the luma of uyvy422, the Y
+ * of NV12 or a byte of packed RGB serves where it lies) are MAX-ACCUMULATED into the device array `scores`
+ * [n_frames][3], order p, c, n, which the caller zeroed: several planes may share one result, and the call captures into a
+ * graph.  One launch computes the three candidates; step-1 planes whose base, pitch and frame stride are multiples of 16
+ * bytes take a path of 16-byte loads, every other plane is read sample by sample, to the same bits.
+ * fiunet_field_weave_u8 / _p10: output frame j of `dst`, j < n_out, takes the rows of parity `parity` (0: even, 1: odd) of
+ * every plane from frame entries[j].keep of the window `src` and the other rows from frame entries[j].other; bytes are moved
+ * and nothing else (16-bit words are not clamped), keep == other is a copy.  Planes: 1..4 fiunet_resize_plane pairs as
+ * fiunet_deinterlace_u8 takes them.  `entries` is HOST memory, read during the call; every entry is checked before the
+ * first launch, and the entries travel in the kernel's arguments, 64 output frames a launch.
+ * Both: asynchronous on `stream`, no allocation, no synchronisation, capturable; no frames is a no-op.
+ * FIUNET_ERR_INVALID_ARG, before any launch and before a pointer is used: a NULL argument, a misaligned pointer, an unknown
+ * order or parity, a threshold outside 0..1023, first or n_frames outside the window, an entry that names a frame outside
+ * the window, more than 65535 frames in one call, n_planes outside 1..4, a plane that breaks fiunet_resize_planes' rules
+ * or has filter != 0, h < 3 (match) or h < 2 (weave), a plane pair of different h x w, a plane range that leaves the
+ * address space, the destination (the scores; dst's planes) overlapping the source. */
+typedef struct fiunet_weave_entry {
+    uint32_t keep, other;
+} fiunet_weave_entry;
+int fiunet_field_match_u8(const uint8_t* src, int n_src, const fiunet_resize_plane* plane, int first, int n_frames,
+                          int order, int threshold, uint32_t* scores, void* stream);
+int fiunet_field_match_p10(const uint16_t* src, int n_src, const fiunet_resize_plane* plane, int first, int n_frames,
+                           int order, int threshold, uint32_t* scores, void* stream);
+int fiunet_field_weave_u8(const uint8_t* src, int n_src, const fiunet_resize_plane* src_planes, uint8_t* dst,
+                          const fiunet_resize_plane* dst_planes, int n_planes, const fiunet_weave_entry* entries, int n_out,
+                          int parity, void* stream);
+int fiunet_field_weave_p10(const uint16_t* src, int n_src, const fiunet_resize_plane* src_planes, uint16_t* dst,
+                           const fiunet_resize_plane* dst_planes, int n_planes, const fiunet_weave_entry* entries, int n_out,
+                           int parity, void* stream);
 
 /* The training loss' SSIM on device: SSIMLoss._ssim (model/train.py:37-56) - the
  * window_size x window_size Gaussian window (sigma 1.5, normalised as at train.py:27-35) applied as a
