@@ -5,6 +5,9 @@ definition `optical_flow._warp_time_torch` applied to whole frames as stored, th
             by plane of a layout (offset, pitch, step: the samples are read and written where they lie), on the CPU, in
             torch; wn == 0 and a set flag leave the frame to the caller's blend pass, as the kernel does
   blend     `blend_rows`: the integer formula of retime.py, 10-bit words above 1023 read as 1023
+  dedup     `dedup_entries`: the entries of a clip with repeated frames and flagged cuts, from tests/dedup_ref.py's `place`
+            (Fractions, Python ints): "motion" under dedup with scene cuts, which neither restatement had on its own (an
+            extension for tests/test_gpu_video_matrix.py; without dead intervals it is the rule of tests/retime_ref.py)
   lead      `lead_of`: the plane the flow is estimated on (retime.lead_planes' rule, stated again)
   texture   `texture(h, w, t, step, seed)`: a band-limited picture (24 sinusoids, angular frequency up to 0.8 rad / px on
             each axis, 8 bits) moved by t * step pixels, evaluated analytically: the true frame at any time
@@ -88,6 +91,22 @@ def plan_entries(plan, n_out, flagged=False):
     for j in range(n_out):
         i, _, lo, wn = plan.frame(j)
         out.append((i * plan.G + lo, wn, plan.q, i if flagged else -1))
+    return out
+
+
+def dedup_entries(n_out, step, G, dead, cuts, max_gap):
+    """(row, wn, den, -1) of output frames 0 .. n_out - 1 at times j * step on the factor-G grid of the whole clip:
+    `dedup_ref.place` gives the interval, the row below and the weight of the row above as a Fraction, whose numerator and
+    denominator are the time wn / den of the warp (`_warp_time_torch` rounds wn / den once, so the reduced fraction is the
+    time itself); a frame held by the cut rule, and one that sits on a grid row, has wn == 0: a copy, never warped."""
+    import dedup_ref
+    out = []
+    for j in range(n_out):
+        i, lo, w = dedup_ref.place(j, step, G, dead, cuts, max_gap)
+        if w is None or w == 0:
+            out.append((i * G + lo, 0, 1, -1))
+        else:
+            out.append((i * G + lo, w.numerator, w.denominator, -1))
     return out
 
 
