@@ -66,6 +66,8 @@ SYMBOLS = (
     "fiunet_deinterlace_u8", "fiunet_deinterlace_p10",
     # inverse telecine
     "fiunet_field_match_u8", "fiunet_field_match_p10", "fiunet_field_weave_u8", "fiunet_field_weave_p10",
+    # a synthesized shutter for lower frame rates
+    "fiunet_shutter_u8", "fiunet_shutter_p10",
     # (the packed RGB entry points stand before the surface ones: tests/test_nv12_host.py reads those off the tail)
     "fiunet_packed_to_rgb_u8", "fiunet_rgb_to_packed_u8", "fiunet_workspace_bytes_rgb_packed",
     "fiunet_forward_rgb_packed",
@@ -229,6 +231,8 @@ def lib() -> ctypes.CDLL:
     L.fiunet_pair_peak_p10.argtypes = [vp, ci, sz, vp, vp]
     L.fiunet_retime_table_u8.argtypes = [vp, ci, sz, vp, ci, vp, vp]
     L.fiunet_retime_table_p10.argtypes = [vp, ci, sz, vp, ci, vp, vp]
+    L.fiunet_shutter_u8.argtypes = [vp, ci, sz, vp, ci, vp, vp]
+    L.fiunet_shutter_p10.argtypes = [vp, ci, sz, vp, ci, vp, vp]
     L.fiunet_resize_planes_u8.argtypes = [vp, vp, vp, vp, ci, ci, vp]
     L.fiunet_resize_planes_p10.argtypes = [vp, vp, vp, vp, ci, ci, vp]
     L.fiunet_warp_table_u8.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, ci, vp, ci, vp, vp, vp]
@@ -869,6 +873,31 @@ def retime_table(grid: "torch.Tensor", entries, out: "torch.Tensor", bits: int) 
     s = _stream(grid)
     check(fn(grid.data_ptr(), grid.shape[0], fs, arr, len(entries), out.data_ptr(), s),
           "fiunet_retime_table_" + ("p10" if bits == 10 else "u8"))
+
+
+SHUTTER_MAX_TAPS = 48   # csrc/shutter.hip.h: kShutterMaxTaps
+
+
+def shutter_entries(entries):
+    """A sequence of (first_row, weights) -> the C array of 32-bit words fiunet_shutter_* takes (first_row, n_taps, the
+    weights; None when empty).  ValueError on a value that does not fit 32 bits unsigned (the library checks the rest)."""
+    words = []
+    for k, (row, w) in enumerate(entries):
+        w = [int(v) for v in w]
+        if not (0 <= row < 1 << 32 and all(0 <= v < 1 << 32 for v in w)):
+            raise ValueError(f"entry {k} = {(row, w)} does not fit 32 bits unsigned")
+        words += [int(row), len(w)] + w
+    return (ctypes.c_uint32 * len(words))(*words) if words else None
+
+
+def shutter(grid: "torch.Tensor", entries, out: "torch.Tensor", bits: int, stream=None) -> None:
+    """fiunet_shutter_u8 / fiunet_shutter_p10: a contiguous grid [n_rows, ...] and (first_row, weights) entries, read on
+    the host during the call -> `out` [len(entries), ...]."""
+    arr = shutter_entries(entries)
+    fs = grid[0].numel() if grid.shape[0] else 0
+    fn = lib().fiunet_shutter_p10 if bits == 10 else lib().fiunet_shutter_u8
+    check(fn(grid.data_ptr(), grid.shape[0], fs, arr, len(entries), out.data_ptr(), _stream(grid, stream)),
+          "fiunet_shutter_" + ("p10" if bits == 10 else "u8"))
 
 
 def warp_entries(entries):

@@ -11,6 +11,13 @@ the chunk, and `-` is standard input / output: it sits in an ffmpeg pipe
 With `--fps 60000/1001` (a fraction or an integer, never a decimal) the output has that frame rate instead of
 --factor times the input's (retime.py): 23.976 -> 59.94, 24 -> 60, 25 -> 60, 50 -> 120.
 
+With `--shutter 1/2` (a fraction in 0 .. 1 of the OUTPUT frame period, never a decimal) --fps may be any rate, a lower one
+included - 59.94 -> 50, 60 -> 24, 30 -> 25 - and every output frame is the clip averaged over the time such a shutter is
+open, the exposure of the slower camera (retime.py); `--shutter 0` point-samples.  After `deinterlace`:
+
+    ... cli deinterlace --input - --output - | python -m ai_based_frame_interpolation_amd.cli video --input - \\
+        --output - --fps 50 --shutter 1/2 --model best_model.pth | ffmpeg -f yuv4mpegpipe -i - out.mkv
+
 With `--dedup 0` (a tolerance in code values; `--max-gap 4`) runs of repeated frames - telecined film, animation on twos,
 a stalled capture - are re-timed instead of interpolated across (retime.py); one line on standard error
 says how many repeated frames were re-timed.
@@ -142,6 +149,13 @@ def _fps(v: str):
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _shutter(v: str):
+    try:
+        return retime.check_shutter(v)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def _dedup(v: str):
     try:
         return retime.check_dedup(float(v))[0]
@@ -199,6 +213,9 @@ def parser() -> argparse.ArgumentParser:
                    help="How --fps makes a frame between two bisection frames: blend (a cross-fade), nearest (the "
                         "closer one) or motion (both warped along the optical flow between them to the frame's own "
                         "time: no double edges where things move, at the cost of one flow per pair)")
+    v.add_argument("--shutter", type=_shutter, default=None, metavar="N/D",
+                   help="Synthesize a shutter open for N/D (0 .. 1) of the output frame period; --fps may then be any "
+                        "rate, a lower one included (60 -> 24, 60000/1001 -> 50); 1/2 is 180 degrees, 0 point-samples")
     v.add_argument("--dedup", type=_dedup, default=None, metavar="TOL",
                    help="Re-time repeated frames (telecine, animation on twos, stalled capture): frames that differ "
                         "by at most TOL code values count as repeats (0: equal frames)")
@@ -378,6 +395,8 @@ def run_video(a: argparse.Namespace) -> int:
     logs = {} if a.packing is None else dict(packing=a.packing)
     if a.chroma != "average":   # (and its count, printed below)
         logs.update(chroma=a.chroma, chroma_log=[])
+    if a.shutter is not None:
+        logs.update(shutter=a.shutter)
     if a.dedup is not None:   # for the count below (the cut flags too: a run before a cut is not re-timed)
         logs.update(dedup_log=[], scene_log=[] if a.scene_cut is not None else None)
     n = fi.interpolate_video(src, dst, a.factor, matrix=a.matrix, siting=a.siting, scene_cut=a.scene_cut,

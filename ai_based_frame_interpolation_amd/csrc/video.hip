@@ -1,9 +1,10 @@
 // video.hip -- operations on frame sequences: scene cuts and repeated frames (scene.hip.h), frame-rate conversion
-// (retime.hip.h), resizing frame planes (resize.hip.h) and deinterlacing (deinterlace.hip.h).
+// (retime.hip.h, shutter.hip.h), resizing frame planes (resize.hip.h) and deinterlacing (deinterlace.hip.h).
 #include "fiunet_internal.h"
 #include "plane_check.h"
 #include "scene.hip.h"
 #include "retime.hip.h"
+#include "shutter.hip.h"
 #include "resize.hip.h"
 #include "deinterlace.hip.h"
 #include "ivtc.hip.h"
@@ -203,6 +204,67 @@ int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_sampl
                             int n_out, uint16_t* out, void* stream)
 {
     return retime_table(grid, n_rows, frame_samples, entries, n_out, out, stream);
+}
+
+// ---- a synthesized shutter (csrc/shutter.hip.h) ---------------------------------------------------------
+// `entries` is a run of 32-bit words, per output frame: first_row, n_taps, then n_taps weights.  Every entry is checked
+// here, on the host, before the first launch (n_taps before its weights are read); the entries travel in the kernel's
+// arguments, as many frames per launch as ShutterArgs holds.
+extern "C++" {
+template <typename T>
+static int shutter(const T* grid, int n_rows, size_t frame_samples, const uint32_t* entries, int n_out, T* out, void* stream)
+{
+    if (!grid || !out) return fail(FIUNET_ERR_INVALID_ARG, "NULL argument");
+    if (n_rows < 0 || n_out < 0) return fail(FIUNET_ERR_INVALID_ARG, "negative count");
+    if (n_out == 0) return FIUNET_OK;
+    if (!entries) return fail(FIUNET_ERR_INVALID_ARG, "NULL entries");
+    const uint32_t* e = entries;
+    for (int k = 0; k < n_out; ++k) {
+        const uint32_t row = e[0], taps = e[1];
+        if (taps < 1 || taps > (uint32_t)kShutterMaxTaps) return fail(FIUNET_ERR_INVALID_ARG, "entry: n_taps outside 1..48");
+        if ((uint64_t)row + taps > (uint64_t)n_rows) return fail(FIUNET_ERR_INVALID_ARG, "entry: a tap row outside the grid");
+        uint64_t sum = 0;
+        for (uint32_t t = 0; t < taps; ++t) sum += e[2 + t];
+        if (sum != kShutterOne) return fail(FIUNET_ERR_INVALID_ARG, "entry: the weights do not sum to 2^20");
+        e += 2 + taps;
+    }
+    if (frame_samples == 0) return FIUNET_OK;
+    // ~2 x 16 B per thread and at most 256 workgroups per frame
+    const unsigned bx = (unsigned)std::min<size_t>((frame_samples * sizeof(T) / 32 + 255) / 256 + 1, 256);
+    e = entries;
+    for (int k0 = 0; k0 < n_out;) {
+        ShutterArgs args = {};
+        int nk = 0, nw = 0;
+        const int most = std::min(n_out - k0, kShutterMaxFrames);   // (one frame always fits: n_taps <= 48)
+        while (nk < most && nw + (int)e[1] <= kShutterMaxWeights) {
+            uint32_t row = e[0], taps = e[1];
+            const uint32_t* w = e + 2;
+            for (uint32_t t = 0; t < taps; ++t)
+                if (w[t] == kShutterOne) { row += t, w += t, taps = 1; break; }   // one live tap: the kernel's copy
+            args.row[nk] = row, args.off[nk] = (uint16_t)nw, args.taps[nk] = (uint16_t)taps;
+            for (uint32_t t = 0; t < taps; ++t) args.w[nw + t] = w[t];
+            nw += (int)taps, ++nk;
+            e += 2 + e[1];
+        }
+        hipLaunchKernelGGL(shutter_kernel<T>, dim3(bx, (unsigned)nk), dim3(kShutterBlock), 0, (hipStream_t)stream, grid,
+                           frame_samples, args, out + (size_t)k0 * frame_samples);
+        HIP_TRY(hipGetLastError());
+        k0 += nk;
+    }
+    return FIUNET_OK;
+}
+}  // extern "C++"
+
+int fiunet_shutter_u8(const uint8_t* grid, int n_rows, size_t frame_samples, const uint32_t* entries, int n_out,
+                      uint8_t* out, void* stream)
+{
+    return shutter(grid, n_rows, frame_samples, entries, n_out, out, stream);
+}
+
+int fiunet_shutter_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const uint32_t* entries, int n_out,
+                       uint16_t* out, void* stream)
+{
+    return shutter(grid, n_rows, frame_samples, entries, n_out, out, stream);
 }
 
 // ---- resizing frame planes (csrc/resize.hip.h) ------------------------------------------------------

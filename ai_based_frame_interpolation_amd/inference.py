@@ -459,7 +459,7 @@ class FrameInterpolator:
     def interpolate_video(self, input_path, output_path, factor=2, *, matrix="bt709", siting=None, scene_cut=None,
                           chunk_frames=None, fps=None, src_fps=None, time_depth=2, retime="blend", raw=None,
                           width=None, height=None, dedup=None, max_gap=4, dedup_log=None, scene_log=None, resize=None,
-                          resize_filter="linear", packing=None, chroma="average", chroma_log=None):
+                          resize_filter="linear", packing=None, chroma="average", chroma_log=None, shutter=None):
         """matrix: the YUV matrix of colour Y4M video through the RGB network ("bt709" by convention for HD video,
         "bt601", or for 10-bit video "bt2020", the matrix of HDR10 / HLG content; the container does not carry it).
         siting: the chroma siting of colour Y4M video through the RGB network, "jpeg" or "mpeg2"; None takes it from the
@@ -534,7 +534,17 @@ class FrameInterpolator:
         chunk_frames, 8 and 10 bits, 4:2:0, 4:2:2 and 4:4:4; a mono stream has no chroma and is unchanged.  Costs one
         Farneback flow per inserted frame.  "motion" is refused by name for an RGB model, .npy input and every raw=
         route: none of them has separate chroma planes.  chroma_log: None, or a list that receives one (warped blocks,
-        blocks) pair after a "motion" run."""
+        blocks) pair after a "motion" run.
+        shutter: None, or an exact rational in [0, 1] (an int, a Fraction, an (n, d) pair or an "n/d" string; no floats):
+        conversion to ANY frame rate, a lower one included, with a synthesized shutter (retime.py).  `fps`
+        is then required and may be at, below or above the source rate (60 -> 24, 60000/1001 -> 50, 30 -> 25).  Point
+        sampling a lower rate strobes, since every frame keeps the source's short exposure; so each output frame is the
+        mean of the clip - the bisection frames and the straight lines between them - over the time a shutter that is
+        open for `shutter` of the OUTPUT frame period would expose it, from the frame's own time on (1/2: 180 degrees).
+        No exposure crosses a flagged cut or the clip's end.  shutter=0 is point sampling, with every `retime`; above 0
+        `retime` must be "blend".  Works on every route, with scene_cut, resize and every chunk_frames (byte-identical);
+        refused with dedup; a window of more than 8 source intervals or 48 bisection frames is refused with the remedy
+        (a lower time_depth or shutter).  A streamed chunk reads ceil(shutter x source rate / fps) frames ahead."""
         from . import chroma as _chroma
         _chroma.check_mode(chroma)
         thr = scene.check_threshold(scene_cut)
@@ -544,6 +554,8 @@ class FrameInterpolator:
         run = dict(batch=self.batch, chunk_frames=chunk_frames, scene_cut=thr, fps=fps, src_fps=src_fps,
                    time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
                    scene_log=scene_log, resize=resize, resize_filter=resize_filter)
+        if shutter is not None:   # (a new keyword: without it the call is what it always was)
+            run["shutter"] = shutter
         from . import resize as _resize
         if resize is not None:
             _resize.check_size(resize)
@@ -559,6 +571,7 @@ class FrameInterpolator:
             raise ValueError("width and height describe raw video: pass raw=\"nv12\" with them")
         stream.check_retime(fps, src_fps, time_depth, retime, factor)
         stream.check_dedup(dedup, max_gap, fps, factor)
+        stream.check_shutter(shutter, fps, retime, dedup)
         if chunk_frames is not None:
             stream.check_chunk_frames(chunk_frames)
         is_path = isinstance(input_path, (str, os.PathLike))

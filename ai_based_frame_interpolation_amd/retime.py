@@ -22,6 +22,32 @@ Every plane of a frame as stored is resampled by the same rule.  One HIP kernel 
 Repeated frames (`dedup=`; the second half of this file): the spans of repeats are found on the host and
 every output frame becomes one (row, wn, den) entry of a table that a second kernel, `fiunet_retime_table_u8` / `_p10`,
 takes in its arguments.
+
+Lower rates and a synthesized shutter (`shutter=`; the section after the repeated frames).  With
+`plan(any_rate=True)` Fo is any positive rate, 1 <= p, q <= 2**20, and J and the frame times stay as above.  Dropping
+to a lower rate by point sampling strobes: each frame keeps the source's short exposure.  So the exposure of the slower
+camera is synthesized, by averaging the clip over a shutter window.  Exact rationals and Python integers only:
+
+  time     grid time is u = t * G; grid row k sits at u = k.  Between rows the clip c(u) is the straight line between
+           row floor(u) and the next row (blend before rounding); in an interval i flagged by scene_cut c(u) is row
+           i * G throughout (the hold rule)
+  shutter  s, an exact rational in [0, 1]: the fraction of the OUTPUT frame period the shutter is open (180 degrees =
+           1/2); parsed like a frame rate (`check_shutter`), floats refused
+  window   frame j opens at u0 = j p G / q and closes at u1 = u0 + s p G / q, cut short at the clip's last frame
+           (u1 <= (N - 1) G) and at the end of the first flagged interval it touches (u1 <= (i + 1) G: no exposure
+           crosses a cut).  Interval floor(u0 / G) is touched; a later interval i is where i G < u1
+  weights  the frame is the mean of c(u) over [u0, u1]: W_k, the weight of row k, is the integral of its hat function
+           over the window divided by u1 - u0 (a zero-width window: the two rows around u0 by its phase), the share
+           inside a flagged interval i going to row i G.  Quantised to D = 2**20: w_k = floor(W_k D), and the
+           D - sum w_k left-over units go one each to the rows with the largest fractional parts, ties to the lower
+           row; sum w_k == D always; rows with w_k == 0 are dropped
+  frame    out = (sum_k w_k x_k + D / 2) >> 20 per sample, 10-bit words above 1023 read as 1023 (the sum stays below
+           2**30); a frame with a single tap is a byte copy of that row, as wn == 0 above
+  limits   at most 48 rows from the first to the last tap of a frame (SHUTTER_MAX_TAPS); s p / q <= 8 source intervals
+
+One HIP kernel (csrc/shutter.hip.h): `fiunet_shutter_u8` / `fiunet_shutter_p10`, the entries (first row, weights) in
+its arguments.  shutter = 0 is point sampling and goes through `table_entries` / `resample_table`, whose rule holds for
+p >= q as it stands.
 """
 from __future__ import annotations
 
@@ -42,9 +68,17 @@ VIDEO_MODES = MODES + ("motion",)   # what the video routes take; MODES: what th
 def parse_fps(x) -> Fraction:
     """A frame rate as an exact rational: an int, a `Fraction`, an `(n, d)` pair of ints or an "n/d" / "n" string.
     Floats are refused: 59.94 is not 60000/1001."""
+    f = _parse_rational(x, "a frame rate", 'such as "60000/1001" for 59.94 or "24000/1001" for 23.976')
+    if f <= 0:
+        raise ValueError(f"a frame rate must be positive, got {x!r}")
+    return f
+
+
+def _parse_rational(x, what: str, such_as: str) -> Fraction:
+    """`x` as an exact rational >= 0 (what `parse_fps` and `check_shutter` share); `what` and `such_as` word the
+    refusals."""
     if isinstance(x, float):
-        raise ValueError(f"a frame rate must be exact, got the float {x!r}: pass a fraction as a string or a pair, "
-                         'such as "60000/1001" for 59.94 or "24000/1001" for 23.976')
+        raise ValueError(f"{what} must be exact, got the float {x!r}: pass a fraction as a string or a pair, {such_as}")
     try:
         if isinstance(x, bool):
             raise TypeError
@@ -63,9 +97,7 @@ def parse_fps(x) -> Fraction:
         else:
             raise TypeError
     except (TypeError, ValueError, ZeroDivisionError):
-        raise ValueError(f'a frame rate is an int, a Fraction, an (n, d) pair or an "n/d" string, got {x!r}') from None
-    if f <= 0:
-        raise ValueError(f"a frame rate must be positive, got {x!r}")
+        raise ValueError(f'{what} is an int, a Fraction, an (n, d) pair or an "n/d" string, got {x!r}') from None
     return f
 
 
@@ -116,17 +148,21 @@ class Plan:
         return j0, j1 - j0
 
 
-def plan(src_fps, fps, time_depth: int = 2) -> Plan:
+def plan(src_fps, fps, time_depth: int = 2, any_rate: bool = False) -> Plan:
     """The plan of a conversion from `src_fps` to `fps` (anything `parse_fps` takes).  ValueError unless fps > src_fps
-    and the reduced q fits 2**20."""
+    and the reduced q fits 2**20.  any_rate (what `shutter=` asks for): any positive fps, a lower one and the source's
+    own included; the reduced p must then fit 2**20 as q does."""
     depth = check_time_depth(time_depth)
     fi, fo = parse_fps(src_fps), parse_fps(fps)
-    if fo <= fi:
+    if fo <= fi and not any_rate:
         raise ValueError(f"fps must be above the source rate: fps {fo} <= source {fi} (lowering the frame rate, or "
                          "keeping it, is not interpolation)")
     pl = Plan(fi, fo, depth)
     if pl.q > MAX_Q:
         raise ValueError(f"source rate {fi} / fps {fo} reduces to {pl.p}/{pl.q}: the denominator must not exceed "
+                         f"2**20 = {MAX_Q}")
+    if pl.p > MAX_Q:
+        raise ValueError(f"source rate {fi} / fps {fo} reduces to {pl.p}/{pl.q}: the numerator must not exceed "
                          f"2**20 = {MAX_Q}")
     return pl
 
@@ -346,6 +382,170 @@ def resample_table(grid: torch.Tensor, entries, bits: int, out: torch.Tensor | N
     return out
 
 
+# ---- lower rates: a synthesized shutter ----------------------------------------------------------------
+# The definition stands at the top of this file.  Everything here is Python integers and `Fraction`s; the device sees
+# (first row, weights) entries whose weights sum to 2**20.
+SHUTTER_ONE = 1 << 20            # D
+SHUTTER_MAX_TAPS = 48            # csrc/shutter.hip.h: kShutterMaxTaps
+SHUTTER_MAX_INTERVALS = 8        # s p / q: source intervals per window
+
+
+def check_shutter(x):
+    """-> None (no shutter asked for) or the shutter as an exact `Fraction` in [0, 1]: an int, a `Fraction`, an (n, d)
+    pair or an "n/d" string, as a frame rate.  Floats are refused as `parse_fps` refuses them."""
+    if x is None:
+        return None
+    s = _parse_rational(x, "a shutter", 'such as "1/2" for 180 degrees')
+    if not 0 <= s <= 1:
+        raise ValueError(f"a shutter is the fraction of the output frame period it is open, 0 to 1, got {x!r}")
+    return s
+
+
+def shutter_lookahead(pl: Plan, s: Fraction) -> int:
+    """ceil(s p / q): the source frames behind a chunk's own that its frames' windows can reach."""
+    return -((-s.numerator * pl.p) // (s.denominator * pl.q))
+
+
+def check_shutter_plan(pl: Plan, s: Fraction) -> None:
+    """The limits of a shutter `s` > 0 on plan `pl`, from the rates alone: ValueError when a window spans more than 8
+    source intervals, or when a frame's taps can span more than 48 grid rows (the bound: a window of length
+    L = s p G / q that opens at phase f of a grid cell covers the rows 0 .. ceil(f + L), and f takes every multiple of
+    1 / q' below 1, q' the denominator of p G / q)."""
+    p, q, G = pl
+    if s * p > SHUTTER_MAX_INTERVALS * q:
+        raise ValueError(f"a shutter of {s} at source / fps = {p}/{q} keeps the window open over {s * p / q} source "
+                         f"intervals; at most {SHUTTER_MAX_INTERVALS} are supported: lower `shutter`, or convert in "
+                         "two steps")
+    length, unit = s * Fraction(p * G, q), Fraction(p * G, q).denominator
+    top = Fraction(unit - 1, unit) + length
+    taps = -((-top.numerator) // top.denominator) + 1
+    if taps > SHUTTER_MAX_TAPS:
+        raise ValueError(f"a shutter of {s} at source / fps = {p}/{q} and time_depth {pl.depth} averages up to {taps} "
+                         f"grid rows per frame; at most {SHUTTER_MAX_TAPS} are supported: lower `time_depth` or "
+                         "`shutter`")
+
+
+def _flagged(cuts, k: int) -> bool:
+    return cuts is not None and 0 <= k < len(cuts) and bool(cuts[k])
+
+
+def shutter_window(pl: Plan, s: Fraction, j: int, first_interval: int = 0, cuts=None, clip_last=None):
+    """(u0, u1) of output frame j in grid time, as `Fraction`s.  cuts: truth values of the intervals from
+    first_interval on, or None; clip_last: the number of the clip's last frame, N - 1, or None where the clip is
+    known to go on past every window."""
+    p, q, G = pl
+    u0 = Fraction(j * p * G, q)
+    u1 = u0 + s * Fraction(p * G, q)
+    if clip_last is not None:
+        u1 = max(u0, min(u1, Fraction(clip_last * G)))
+    if cuts is not None:
+        i = u0.numerator // (u0.denominator * G)
+        while True:
+            if _flagged(cuts, i - first_interval):
+                u1 = min(u1, Fraction((i + 1) * G))
+                break
+            i += 1
+            if i * G >= u1:
+                break
+    return u0, u1
+
+
+def shutter_weights(u0: Fraction, u1: Fraction, G: int, first_interval: int = 0, cuts=None):
+    """{grid row of the clip: weight} of the window [u0, u1], quantised to 2**20 (the weights sum to SHUTTER_ONE; rows
+    of weight 0 are left out)."""
+    W = {}
+
+    def add(k, v):
+        if v:
+            W[k] = W.get(k, 0) + v
+    m = u0.numerator // u0.denominator
+    if u0 == u1:
+        if _flagged(cuts, m // G - first_interval):
+            add(m // G * G, Fraction(1))
+        else:
+            add(m, 1 - (u0 - m))
+            add(m + 1, u0 - m)
+    else:
+        while m < u1:
+            x0, x1 = max(u0, Fraction(m)), min(u1, Fraction(m + 1))
+            if _flagged(cuts, m // G - first_interval):
+                add(m // G * G, x1 - x0)
+            else:
+                mid = (x0 + x1) / 2
+                add(m, (x1 - x0) * (m + 1 - mid))
+                add(m + 1, (x1 - x0) * (mid - m))
+            m += 1
+        W = {k: v / (u1 - u0) for k, v in W.items()}
+    rows = sorted(W)
+    w = {k: (W[k] * SHUTTER_ONE).numerator // (W[k] * SHUTTER_ONE).denominator for k in rows}
+    left = SHUTTER_ONE - sum(w.values())
+    # the left-over units: the largest fractional parts first, ties to the lower row
+    for k in sorted(rows, key=lambda k: (-(W[k] * SHUTTER_ONE - w[k]), k))[:left]:
+        w[k] += 1
+    return {k: v for k, v in w.items() if v}
+
+
+def shutter_reach(pl: Plan, s: Fraction, first_interval: int, n_own: int, j0: int, n_out: int, cuts=None,
+                  clip_last=None) -> int:
+    """How many intervals past first_interval + n_own the windows of frames j0 .. j0 + n_out - 1 reach: what a chunk's
+    grid is extended by."""
+    end = 0
+    for j in range(j0, j0 + n_out):
+        u1 = shutter_window(pl, s, j, first_interval, cuts, clip_last)[1] / pl.G
+        end = max(end, -((-u1.numerator) // u1.denominator))
+    return max(0, end - (first_interval + n_own))
+
+
+def shutter_entries(pl: Plan, s: Fraction, first_interval: int, j0: int, n_out: int, n_intervals: int, cuts=None,
+                    clip_last=None):
+    """(first_row, [w ...]) of output frames j0 .. j0 + n_out - 1 on a grid of n_intervals * G + 1 rows that starts at
+    clip interval first_interval: what `resample_shutter` takes.  The taps are consecutive grid rows from first_row, a
+    row the definition dropped carrying weight 0.  cuts, clip_last: as for `shutter_window`.  Python integers only;
+    ValueError when a frame needs a row outside the grid, or more than 48 rows."""
+    G = pl.G
+    rows = n_intervals * G + 1
+    out = []
+    for j in range(j0, j0 + n_out):
+        u0, u1 = shutter_window(pl, s, j, first_interval, cuts, clip_last)
+        w = shutter_weights(u0, u1, G, first_interval, cuts)
+        lo, hi = min(w) - first_interval * G, max(w) - first_interval * G
+        if lo < 0 or hi >= rows:
+            raise ValueError(f"output frame {j} needs grid rows {lo} .. {hi}: the grid has {rows} rows from interval "
+                             f"{first_interval}")
+        if hi - lo + 1 > SHUTTER_MAX_TAPS:
+            raise ValueError(f"output frame {j} averages {hi - lo + 1} grid rows; at most {SHUTTER_MAX_TAPS} are "
+                             "supported: lower `time_depth` or `shutter`")
+        out.append((lo, [w.get(k + first_interval * G, 0) for k in range(lo, hi + 1)]))
+    return out
+
+
+@torch.no_grad()
+def resample_shutter(grid: torch.Tensor, entries, bits: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One output frame per entry (first_row, weights) from `grid`, a contiguous device stack [rows, ...] (uint8 at 8
+    bits; 16-bit words at 10): (sum_t w[t] grid[first_row + t] + 2**19) >> 20 per sample, a byte copy of the row where
+    one weight is 2**20.  The entries are read on the host during the call and go to the kernel in its arguments
+    (`fiunet_shutter_u8` / `_p10`).  Returns `out` ([len(entries), ...]; allocated when None)."""
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, got {bits!r}")
+    want = (torch.uint8,) if bits == 8 else (torch.int16, torch.uint16)
+    if grid.dtype not in want:
+        raise ValueError(f"a {bits}-bit grid must be {' or '.join(str(d) for d in want)}, got {grid.dtype}")
+    if not grid.is_cuda:
+        raise RuntimeError("the grid must be on the GPU: there is no CPU path in this package")
+    if not grid.is_contiguous():
+        raise ValueError("the grid must be contiguous")
+    entries = [(int(r), [int(v) for v in w]) for r, w in entries]
+    shape = (len(entries),) + tuple(grid.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=grid.dtype, device=grid.device)
+    elif tuple(out.shape) != shape or out.dtype != grid.dtype or out.device != grid.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {grid.dtype} {shape} tensor on {grid.device}")
+    if entries:
+        with torch.cuda.device(grid.device):
+            _native.shutter(grid, entries, out, bits)
+    return out
+
+
 # ---- motion-compensated resampling (DESIGN.md 3.3t) -----------------------------------------------------------------
 # retime "motion": an output frame between two grid rows A and B (wn != 0) is not their cross-fade but both of them
 # warped along the dense flow A -> B to the frame's own time wn / den (optical_flow._warp_time_torch is the definition,
@@ -434,4 +634,6 @@ def _motion(grid, entries, bits, out, layout, flags, batch):
 
 __all__ = ["MAX_Q", "MODES", "VIDEO_MODES", "lead_planes", "Plan", "parse_fps", "check_time_depth", "check_mode", "plan", "resample",
            "check_dedup", "dead_limit", "dedup_plan", "dedup_spans", "classify_chunk", "table_entries",
-           "resample_table"]
+           "resample_table", "SHUTTER_ONE", "SHUTTER_MAX_TAPS", "SHUTTER_MAX_INTERVALS", "check_shutter",
+           "shutter_lookahead", "check_shutter_plan", "shutter_window", "shutter_weights", "shutter_reach",
+           "shutter_entries", "resample_shutter"]

@@ -36,6 +36,13 @@ three `interpolate_*_stream` functions here.  A source is opened in one place (`
              den) entries and `retime.resample_table` writes them.  In the sizes below C + 2 becomes C + 1 + max_gap
              and the output slots hold the frames of C + max_gap - 1 intervals (the last chunk; `_run`).
 
+  shutter    with `shutter=` (retime.py) fps may be any rate, a lower one included.  A chunk reads
+             ceil(shutter x p / q) lookahead frames (one more with scene_cut), and its grid goes on over the lookahead
+             intervals that the windows of its own frames reach (`retime.shutter_reach`); a frame belongs to the chunk
+             that holds its opening time, and a chunk without one (p > q) writes nothing.  `retime.shutter_entries` /
+             `resample_shutter` write the frames; shutter 0 point-samples through `table_entries` / `resample_table`.
+             With scene_cut the cut flags are read back once per chunk: the windows end at a cut.
+
 Memory is bounded by the chunk, never by the clip (C = chunk_frames, F = factor, one frame of the input layout):
   host pinned    3 x (C + 2) input frames + 2 x (C x F + 1) output frames
   device         2 x (C + 2) input frames + one chunk's levels + the previous chunk's result (C x F + 1 frames of
@@ -615,6 +622,36 @@ class _Job:
     scene_log: list | None = None
     dedup_log: list | None = None
     batch: int = 8
+    shutter: object = None   # None, or the checked shutter (a Fraction in [0, 1]): any rate, retime.py / DESIGN.md 3.3y
+
+
+def check_shutter(shutter, fps, retime, dedup):
+    """The checks of `shutter` that need no source -> None or the shutter as a Fraction.  With a shutter, fps is
+    required and may be any positive rate; dedup is refused; a shutter above 0 needs retime "blend"."""
+    s = _retime.check_shutter(shutter)
+    if s is None:
+        return None
+    if fps is None:
+        raise ValueError(f"shutter={shutter!r} says how a frame of the new rate is exposed: pass fps with shutter")
+    if dedup is not None:
+        raise ValueError(f"shutter={shutter!r} and dedup={dedup!r} do not go together: re-time the repeated frames "
+                         "first, then convert the result with shutter")
+    if s > 0 and retime != "blend":
+        raise ValueError(f'a shutter above 0 averages the frames of retime="blend": got retime={retime!r} with '
+                         f'shutter={shutter!r} (shutter=0, point sampling, takes every retime)')
+    return s
+
+
+def _shutter_frames(job: "_Job", grid, first: int, n_own: int, ext: int, j0: int, nj: int, cuts, clip_last, out=None):
+    """The frames j0 .. j0 + nj - 1 of a run with a shutter from `grid`, which covers intervals first .. first + n_own +
+    ext: the synthesized exposure, or for shutter 0 the point samples of `retime.table_entries` (cuts: host truth values
+    of the grid's intervals or None; clip_last: the clip's last frame number where the chunk is the last)."""
+    plan, bits = job.plan, job.source.route.bits
+    if job.shutter > 0:
+        entries = _retime.shutter_entries(plan, job.shutter, first, j0, nj, n_own + ext, cuts, clip_last)
+        return _retime.resample_shutter(grid, entries, bits, out=out)
+    entries = _retime.table_entries(plan, [], first, j0, nj, n_own, "blend" if job.mode == "motion" else job.mode, cuts)
+    return _retime.resample_table(grid, entries, bits, out=out, mode=job.mode, **_retime_opts(job))
 
 
 def _retime_opts(job: "_Job") -> dict:
@@ -650,7 +687,8 @@ def _run(model, route: _Route, reader, write, job: _Job) -> int:
     device twin of their output slot.
 
     Sizes.  A chunk is read with `look` lookahead frames behind its C + 1 own: 0, 1 with scene_cut; with dd max_gap - 1,
-    and max_gap with scene_cut too.  A read that comes up short of C + 1 + look frames is the clip's last chunk, and
+    and max_gap with scene_cut too; with a shutter ceil(shutter x p / q) more.
+    A read that comes up short of C + 1 + look frames is the clip's last chunk, and
     holds whatever is left: up to C + look - 1 intervals (C when look is 0 or 1).  `tail` is that bound, and the
     pinned output slots and their device twins are sized for it; the pinned input slots and the device input twins
     hold C + 1 + look frames, and the reader carries 1 + look of them over.  (C = 1, max_gap 4: 5 frames per read, 4
@@ -662,6 +700,9 @@ def _run(model, route: _Route, reader, write, job: _Job) -> int:
     C, look = job.chunk_frames, 1 if thr is not None else 0
     if dd is not None:
         look = dd[1] if thr is not None else dd[1] - 1
+    sh = job.shutter
+    if sh is not None:   # the frames its windows can reach, and with scene_cut one more: the last flag read is not used
+        look += _retime.shutter_lookahead(plan, sh)
     tail = C + max(look - 1, 0)
     in_rows, out_rows = C + 1 + look, tail * factor + 1
     if plan is not None:
@@ -774,6 +815,19 @@ def _run(model, route: _Route, reader, write, job: _Job) -> int:
                     dedup_log.append((peaks[:c].cpu().numpy(), dead[:c].copy()))
                 if ext and seen is not None:
                     flags = seen[:c + ext]
+            if sh is not None:
+                # a frame belongs to the chunk that holds its opening time; the grid goes on over the lookahead
+                # intervals that this chunk's windows reach.  With scene_cut the windows depend on the flags: one small
+                # read, which waits for the compute stream as dedup's does
+                j0, nj = plan.span(s, c, last)
+                clip_last = s + c if last else None
+                cuts = None if seen is None else seen.cpu().numpy().astype(bool)
+                if sh > 0:
+                    ext = _retime.shutter_reach(plan, sh, s, c, j0, nj, cuts, clip_last)
+                    if ext and seen is not None:
+                        flags = seen[:c + ext]
+                if cuts is not None:
+                    cuts = cuts[:c + ext]
             # with a span across the chunk's end, the grid goes on over the ext <= max_gap - 1 lookahead intervals that
             # the span needs (ext <= look, and the last chunk has ext == 0: no span reaches past the clip)
             out = route.run(d[:c + 1 + ext], factor)   # (a one-frame clip: the frame itself)
@@ -785,7 +839,9 @@ def _run(model, route: _Route, reader, write, job: _Job) -> int:
             else:
                 # (pinned slot o is free, so the D2H copy that last read d_out[o] has completed)
                 j0, nj = plan.span(s, c, last)
-                if dd is None:
+                if sh is not None:   # (a chunk without a frame of its own, p > q, writes nothing)
+                    rows = _shutter_frames(job, out, s, c, ext, j0, nj, cuts, clip_last, out=d_out[o][:nj])
+                elif dd is None:
                     rows = _retime.resample(out, plan, s, j0, nj, bits=route.bits, flags=flags, mode=mode,
                                             out=d_out[o][:nj], **motion)
                 else:   # (every row an entry names is checked against `out` here, and again behind the C ABI)
@@ -874,7 +930,10 @@ def _run_whole(model, route: _Route, reader, write, job: _Job) -> int:
         write((grid if wire is None else wire.pack(grid)).cpu().numpy().view(route.ndtype))
         return grid.shape[0]
     n = plan.n_out(d.shape[0])
-    if dd is None:
+    if job.shutter is not None:
+        cuts = None if flags is None else flags.cpu().numpy().astype(bool)
+        rows = _shutter_frames(job, grid, 0, d.shape[0] - 1, 0, 0, n, cuts, d.shape[0] - 1)
+    elif dd is None:
         rows = _retime.resample(grid, plan, 0, 0, n, bits=route.bits, flags=flags, mode=mode, **motion)
     else:
         spans, cuts = [], None
@@ -889,8 +948,9 @@ def _run_whole(model, route: _Route, reader, write, job: _Job) -> int:
     return n
 
 
-def _plan_of(fps, src_fps, header_fps, depth):
-    """The plan of a checked `fps` (None: no plan) against `src_fps`, or the stream header's rate when that is None."""
+def _plan_of(fps, src_fps, header_fps, depth, any_rate: bool = False):
+    """The plan of a checked `fps` (None: no plan) against `src_fps`, or the stream header's rate when that is None.
+    any_rate: with a shutter, a rate at or below the source's is a plan too."""
     if fps is None:
         return None
     if src_fps is None:
@@ -901,11 +961,11 @@ def _plan_of(fps, src_fps, header_fps, depth):
         except ValueError:
             raise ValueError(f"the Y4M header's frame rate F{header_fps[0]}:{header_fps[1]} is not a rate: pass "
                              "src_fps") from None
-    return _retime.plan(src_fps, fps, depth)
+    return _retime.plan(src_fps, fps, depth, any_rate)
 
 
 def _job(open_source, *, factor, batch, chunk_frames, scene_cut, scene_log, fps, src_fps, time_depth, retime, dedup,
-         max_gap, dedup_log, resize, resize_filter, headerless: bool = False) -> _Job:
+         max_gap, dedup_log, resize, resize_filter, headerless: bool = False, shutter=None) -> _Job:
     """The job of a route's keyword arguments: every check that needs no source, in the routes' order; then
     `open_source(size, filter)` -> the `_Opened` source, with its own checks; then the plan, which may need the source's
     rate.  headerless: the stream carries no rate, so src_fps is required.  Nothing here touches the device; a
@@ -917,10 +977,13 @@ def _job(open_source, *, factor, batch, chunk_frames, scene_cut, scene_log, fps,
         _retime.parse_fps(src_fps)
     fps, src_fps, depth, mode = check_retime(fps, src_fps, time_depth, retime, factor)
     tol, gap = check_dedup(dedup, max_gap, fps, factor)
+    sh = check_shutter(shutter, fps, mode, tol)
     size = None if resize is None else _resize.check_size(resize)
     source = open_source(size, _resize.check_resize_filter(resize, resize_filter))
     try:
-        plan, rate = _plan_of(fps, src_fps, source.fps, depth), None
+        plan, rate = _plan_of(fps, src_fps, source.fps, depth, sh is not None), None
+        if sh:
+            _retime.check_shutter_plan(plan, sh)
         if plan is not None:
             factor, rate = plan.G, (plan.fps.numerator, plan.fps.denominator)
         elif source.fps is not None:
@@ -931,7 +994,7 @@ def _job(open_source, *, factor, batch, chunk_frames, scene_cut, scene_log, fps,
     except BaseException:
         source.close()
         raise
-    return _Job(source, factor, C, thr, plan, mode, dd, rate, scene_log, dedup_log, int(batch))
+    return _Job(source, factor, C, thr, plan, mode, dd, rate, scene_log, dedup_log, int(batch), sh)
 
 
 def _drive(model, job: _Job, make_write, finish) -> int:
@@ -969,7 +1032,7 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
                            scene_log: list | None = None, fps=None, src_fps=None, time_depth: int = 2,
                            retime: str = "blend", dedup=None, max_gap: int = 4, dedup_log: list | None = None,
                            resize=None, resize_filter: str = "linear", chroma: str = "average",
-                           chroma_log: list | None = None) -> int:
+                           chroma_log: list | None = None, shutter=None) -> int:
     """Y4M in (a path or a readable binary file: a pipe, `sys.stdin.buffer`) -> Y4M out (a path or a writable binary
     file), or a `.npy` path of the luma frames (grayscale network; the input must then be a regular file, whose frame
     count a first pass reads).  This is what `FrameInterpolator.interpolate_video` runs; the result is the same, byte
@@ -994,14 +1057,19 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
     is closer to the warped luma than to the averaged one, and is the average elsewhere; the luma of every frame and
     the source frames are those of "average", for every chunk_frames.  One Farneback flow per inserted frame.  Refused for
     the RGB network; no effect on a mono stream or a luma .npy output.  chroma_log: a list that receives one (warped
-    blocks, blocks) pair of ints after a "motion" run that had chroma to make (one device-to-host read, at the end)."""
+    blocks, blocks) pair of ints after a "motion" run that had chroma to make (one device-to-host read, at the end).
+    shutter: None, or an exact rational in [0, 1] (an int, a Fraction, an (n, d) pair or "n/d"; retime.py):
+    with it `fps` is required and may be ANY positive rate, a lower one included (60 -> 24, 59.94 -> 50); every output
+    frame is the clip averaged over that fraction of the output frame period from its own time on (1/2: a 180 degree
+    shutter), never across a scene cut or past the clip's end.  0 is point sampling and takes every `retime`; above 0
+    `retime` must be "blend".  Refused with dedup."""
     npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
     _chroma.check_mode(chroma)
     job = _job(lambda size, rfilter: _open_y4m(model, src, npy_out, batch, matrix, siting, size, rfilter,
                                                chunk_frames is None or npy_out, chroma),
                factor=factor, batch=batch, chunk_frames=chunk_frames, scene_cut=scene_cut, scene_log=scene_log, fps=fps,
                src_fps=src_fps, time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
-               resize=resize, resize_filter=resize_filter)
+               resize=resize, resize_filter=resize_filter, shutter=shutter)
     source, hdr, bits = job.source, job.source.header, job.source.route.bits
     try:
         if npy_out:
@@ -1023,20 +1091,21 @@ def interpolate_y4m_stream(model, src, dst, factor: int = 2, *, batch: int = 8, 
 def interpolate_npy_stream(model, src, dst, factor: int = 2, *, batch: int = 8, chunk_frames: int = 32,
                            scene_cut: float | None = None, scene_log: list | None = None, fps=None, src_fps=None,
                            time_depth: int = 2, retime: str = "blend", dedup=None, max_gap: int = 4,
-                           dedup_log: list | None = None, resize=None, resize_filter: str = "linear") -> int:
+                           dedup_log: list | None = None, resize=None, resize_filter: str = "linear",
+                           shutter=None) -> int:
     """`.npy` stack in (uint8 [N,H,W] or [N,H,W,C], read through `np.load(mmap_mode="r")`) -> `.npy` out (written
     through `np.lib.format.open_memmap`, the file `np.save` would write; a name without `.npy` gets it).  An
     [N,H,W,C] stack goes through the RGB network, or channel by channel through the grayscale one.  Returns the output
     frame count.  fps / src_fps / time_depth / retime and chunk_frames None: as for `interpolate_y4m_stream`; a .npy
     stack carries no rate, so `fps` needs `src_fps`.  resize / resize_filter: as for `interpolate_y4m_stream`; the output
-    stack has the new height and width."""
+    stack has the new height and width.  shutter: as for `interpolate_y4m_stream`."""
     def open_source(size, rfilter):
         if not _is_path(dst):
             raise ValueError("a .npy output is a path")
         return _open_npy(model, src, batch, size, rfilter)
     job = _job(open_source, factor=factor, batch=batch, chunk_frames=chunk_frames, scene_cut=scene_cut,
                scene_log=scene_log, fps=fps, src_fps=src_fps, time_depth=time_depth, retime=retime, dedup=dedup,
-               max_gap=max_gap, dedup_log=dedup_log, resize=resize, resize_filter=resize_filter)
+               max_gap=max_gap, dedup_log=dedup_log, resize=resize, resize_filter=resize_filter, shutter=shutter)
     n = job.source.count
     if n < 1:
         raise ValueError("no frames to interpolate")
@@ -1053,7 +1122,7 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
                            siting: str | None = None, scene_cut: float | None = None, scene_log: list | None = None,
                            fps=None, src_fps=None, time_depth: int = 2, retime: str = "blend", dedup=None,
                            max_gap: int = 4, dedup_log: list | None = None, resize=None,
-                           resize_filter: str = "linear", packing: str | None = None) -> int:
+                           resize_filter: str = "linear", packing: str | None = None, shutter=None) -> int:
     """Headerless raw video in (a path or a readable binary file: a pipe) -> the same format out (a path or a writable
     binary file): tight NV12 frames of height x width (`ffmpeg ... -f rawvideo -pix_fmt nv12 -`) through the RGB
     network, `interpolate_sequence_nv12` per level; or, with raw "rgb24" / "bgr24" / "rgba" / "bgra", tight packed RGB
@@ -1071,13 +1140,14 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
     3.3s): input and output are tight frames of that 10-bit 4:2:2 packing (`ffmpeg -c:v v210 -f rawvideo`), unpacked to
     yuv422p10le rows on the device right after each chunk's upload and packed again before its download; everything
     between is the yuv422p10le route, and the output is, byte for byte, that route's output packed.  The file size of a
-    regular input counts wire frames (`wire10.frame_bytes`); v210 / y210le need an even width at both sizes."""
+    regular input counts wire frames (`wire10.frame_bytes`); v210 / y210le need an even width at both sizes.
+    shutter: as for `interpolate_y4m_stream`."""
     npy_out = _is_path(dst) and os.fspath(dst).lower().endswith(".npy")
     job = _job(lambda size, rfilter: _open_raw(model, src, raw, width, height, npy_out, batch, matrix, siting, size,
                                                rfilter, packing),
                factor=factor, batch=batch, chunk_frames=chunk_frames, scene_cut=scene_cut, scene_log=scene_log, fps=fps,
                src_fps=src_fps, time_depth=time_depth, retime=retime, dedup=dedup, max_gap=max_gap, dedup_log=dedup_log,
-               resize=resize, resize_filter=resize_filter, headerless=True)
+               resize=resize, resize_filter=resize_filter, headerless=True, shutter=shutter)
     try:
         if job.source.count == 0:
             raise ValueError("no frames to interpolate")
@@ -1090,5 +1160,5 @@ def interpolate_raw_stream(model, src, dst, factor: int = 2, *, raw: str = "nv12
         job.source.close()
 
 
-__all__ = ["check_chunk_frames", "check_retime", "check_dedup", "interpolate_y4m_stream", "interpolate_npy_stream",
+__all__ = ["check_chunk_frames", "check_retime", "check_dedup", "check_shutter", "interpolate_y4m_stream", "interpolate_npy_stream",
            "interpolate_raw_stream"]

@@ -51,7 +51,8 @@ extern "C" {
                                      fiunet_chroma_fill_p10); v8 also, added the same way: deinterlacing
                                      (fiunet_deinterlace_u8, fiunet_deinterlace_p10); v8 also, added the same way: inverse
                                      telecine (fiunet_weave_entry, fiunet_field_match_u8, fiunet_field_match_p10,
-                                     fiunet_field_weave_u8, fiunet_field_weave_p10) */
+                                     fiunet_field_weave_u8, fiunet_field_weave_p10); v8 also, added the same way: a
+                                     synthesized shutter for lower frame rates (fiunet_shutter_u8, fiunet_shutter_p10) */
 
 enum fiunet_status {
     FIUNET_OK = 0,
@@ -542,6 +543,26 @@ int fiunet_retime_table_u8(const uint8_t* grid, int n_rows, size_t frame_samples
                            int n_out, uint8_t* out, void* stream);
 int fiunet_retime_table_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const fiunet_retime_entry* entries,
                             int n_out, uint16_t* out, void* stream);
+
+/* A synthesized shutter (ABI v8, added without a version bump: nothing existing changed; csrc/shutter.hip.h, DESIGN.md
+ * 3.3y): conversion to a lower frame rate averages the clip over the time the slower camera's shutter is open.  Output
+ * row k of out[n_out][frame_samples] is a weighted mean of consecutive rows of grid[n_rows][frame_samples].  `entries` is
+ * a run of 32-bit words, per output frame
+ *   first_row, n_taps, w[0] .. w[n_taps - 1]        (n_taps + 2 words; the next frame's entry follows at once)
+ * and the frame is, per sample in integers,
+ *   (sum_t w[t] * grid[first_row + t] + 2^19) >> 20   with sum_t w[t] == 2^20; 10-bit words above 1023 read as 1023
+ *   a byte copy of the row whose weight is 2^20        (one live tap; words above 1023 stay as they are)
+ * A row whose weight is 0 is not read.  `entries` is HOST memory, read during the call: every entry is checked before the
+ * first launch (n_taps before the weights behind it are read) and the entries travel in the kernels' arguments (up to 32
+ * output frames and 864 weights per launch), so there is no device table and no copy, nothing of the array is needed once
+ * the call has returned, and the call can be captured into a graph.  grid and out are device pointers; asynchronous on
+ * `stream`; no allocation, no synchronisation; n_out == 0 is a no-op.
+ * FIUNET_ERR_INVALID_ARG, before any launch and before a pointer is used: NULL grid / out / entries, a negative count, or
+ * an entry with n_taps outside 1 .. 48, first_row + n_taps > n_rows, or weights that do not sum to 2^20. */
+int fiunet_shutter_u8(const uint8_t* grid, int n_rows, size_t frame_samples, const uint32_t* entries, int n_out,
+                      uint8_t* out, void* stream);
+int fiunet_shutter_p10(const uint16_t* grid, int n_rows, size_t frame_samples, const uint32_t* entries, int n_out,
+                       uint16_t* out, void* stream);
 
 /* Resize of frame planes, bilinear or by area (csrc/resize.hip.h).  A plane is described in SAMPLES of its buffer:
  * sample (y, x) of frame f lies at offset + f * frame_stride + y * pitch + x * step.  Plane i of `src_planes` is
